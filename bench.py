@@ -6,13 +6,17 @@ A step = one scene::render of the workload: scenes/balls.scene (loaded through t
 1920x1080 with `refl 0.2 0.25` (exactly four reflection generations), 1 ray per pixel,
 inputs resident in HBM.  A ray = one BVT query (primary, reflection, refraction or shadow; src/scene.rs:153,166).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, the workload and its rays per frame; at N = 1 also value_traced, below).  --dump-outputs DIR writes what
+the last timed step computed (the frame, and at N = 1 its ray classes) as DIR/<name>.npy.  Everything else below is
+measured and checked with --full only.
 For N > 1 the driver launches it under torch.distributed.run, one rank per GPU: the frame is tiled in 16-row bands
 dealt round-robin to the ranks, each rank renders its compact tile, grouped RCCL send / receive brings the tiles to
 GPU 0, a HIP kernel un-permutes them — all inside the library (nrays_render_multi_device, one C call per frame; strong
 scaling: the frame is fixed).  Rank 0 prints ONE JSON line.  (`--gpus N` without a launcher: one process drives N owners.)
 
-At N = 1 the line also carries
+With --full, at N = 1 the line also carries
   roofline       contract fields (achieved = algorithmic bytes / kernel time against the 8 TB/s HBM peak) PLUS what
                  actually bounds the kernel: `bound` / `limiter` (longest wave tile vs sum of tile cycles per resident
                  wave, from the library's per-tile cycle counts), dram_frac, valu_active_frac, wave_wait_frac,
@@ -50,13 +54,43 @@ CYCLES_PER_F64_WAVE_INSTR = 1.35
 CYCLES_PER_F64_TRANS_WAVE_INSTR = 5.2
 
 
+_SCENES = None
+
+
+def scenes_dir():
+    """A private copy of scenes/ (a temporary directory, removed at exit) in which tools/gen_assets.py writes the media the scene files
+    name: scenes/media/ is not shipped (as upstream), and the benchmark may run on a checkout it cannot write to.  Whatever
+    scenes/media/ already holds is linked into the copy, so real assets dropped there are used instead of the procedural stand-ins."""
+    global _SCENES
+    if _SCENES is None:
+        import atexit
+        import shutil
+        import tempfile
+        from tools import gen_assets
+        src = os.path.join(ROOT, "scenes")
+        d = tempfile.mkdtemp(prefix="nrays_scenes_")
+        atexit.register(shutil.rmtree, d, True)
+        for f in os.listdir(src):
+            if os.path.isfile(os.path.join(src, f)):
+                shutil.copy(os.path.join(src, f), d)
+        media = os.path.join(d, "media")
+        os.makedirs(media)
+        if os.path.isdir(os.path.join(src, "media")):
+            for f in os.listdir(os.path.join(src, "media")):
+                os.symlink(os.path.join(src, "media", f), os.path.join(media, f))
+        gen_assets.MEDIA = media
+        _SCENES = d
+    return _SCENES
+
+
 def load_workload(name):
     """Returns (scene object with .descriptor / .device_handle(), camera dict, description with %d x %d for the resolution)."""
     if name == "balls":
         from tools import gen_assets
         from nrays_amd import scenefile
-        gen_assets.gen_globe()  # scenes/media/ is not shipped (as upstream, SURVEY F7): deterministic procedural globe.png
-        fs = scenefile.FileScene(os.path.join(ROOT, "scenes", "balls.scene"))
+        d = scenes_dir()
+        gen_assets.gen_globe()  # deterministic procedural globe.png
+        fs = scenefile.FileScene(os.path.join(d, "balls.scene"))
         cam = fs.camera_dict()
         return fs, cam, "scenes/balls.scene via the loader3d front-end, %dx%d, refl 0.2 0.25 (4 reflection bounces), 1 ray/pixel, procedural globe.png"
     from tools import standins
@@ -287,9 +321,10 @@ def reference_toolchain_probe():
             "rust_reference_timed": False}
 
 
-def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
-    """One workload on the current device: what a caller gets on a fresh handle (scene build, cold first frame), the
-    steady-state loop the contract times, a moving-camera figure, roofline + limiter, CPU baseline."""
+def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True, full=True, keep_outputs=False):
+    """One workload on the current device: the steady-state loop the contract times; with `full`, also what a caller gets on a
+    fresh handle (scene build, cold first frame), a moving-camera figure, roofline + limiter, CPU baseline.
+    Returns (result dict, {name: host array} of what the last timed step computed, empty unless `keep_outputs`)."""
     import torch
     import nrays_amd as nr
     from nrays_amd import abi
@@ -312,7 +347,7 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
     # history (mesh scenes: k_seed_costs' guess; analytic scenes: image-order work lists), cost recording on.  Median over
     # several fresh handles (the frame is host-synchronised: launch latency + GPU time + wake-up).
     cold_walls, cold_gpu = [], []
-    for _ in range(3):
+    for _ in range(3 if full else 0):
         cs, _, _ = load_workload(name)
         ch = cs.device_handle()
         torch.cuda.synchronize()
@@ -336,15 +371,16 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
     cold_walls.append(first[0])
     cold_ms = sorted(cold_walls)[len(cold_walls) // 2]
 
-    # two instrumented renders: the reference algorithm's counts (every ray scene.rs traces: rays_per_frame, the metric's rays), and the counts of the work the
-    # timed plain kernel really does (the shadow rays it skips skipped: the roofline's units)
+    # an instrumented render: the reference algorithm's counts (every ray scene.rs traces: rays_per_frame, the metric's rays); with `full`, a second one
+    # counts the work the timed plain kernel really does (the shadow rays it skips skipped: the roofline's units)
     render_on(handle, p, True)
     st = nr.get_stats(scene)
-    pk_ref = abi.NraysStats()
-    abi.check(lib.nrays_get_primary_kernel_stats(handle, C.byref(pk_ref)))
-    abi.check(lib.nrays_render_device_counted(handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(stream), abi.COUNT_AS_TIMED))
-    pk = abi.NraysStats()
-    abi.check(lib.nrays_get_primary_kernel_stats(handle, C.byref(pk)))
+    if full:
+        pk_ref = abi.NraysStats()
+        abi.check(lib.nrays_get_primary_kernel_stats(handle, C.byref(pk_ref)))
+        abi.check(lib.nrays_render_device_counted(handle, C.byref(p), C.c_void_p(out.data_ptr()), C.c_void_p(stream), abi.COUNT_AS_TIMED))
+        pk = abi.NraysStats()
+        abi.check(lib.nrays_get_primary_kernel_stats(handle, C.byref(pk)))
     # (3) the contract's loop.  Untimed, before --warmup: the library settles its per-camera scheduling state in three plain
     # frames of a resting camera (tile costs recorded -> sorted -> order decided; pixels never depend on it), so the timed
     # steps are RESTING-CAMERA STEADY-STATE frames whatever --warmup says (cold_frame_ms / moving_camera_ms_per_frame are the others)
@@ -352,9 +388,10 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
     for _ in range(settle):
         render_on(handle, p)
     torch.cuda.synchronize()
-    tile_costs = abi.NraysTileCosts()
-    if lib.nrays_get_tile_costs(handle, C.byref(tile_costs)) != 0:
-        tile_costs = None
+    if full:
+        tile_costs = abi.NraysTileCosts()
+        if lib.nrays_get_tile_costs(handle, C.byref(tile_costs)) != 0:
+            tile_costs = None
     for _ in range(warmup):
         render_on(handle, p)
     nr.get_stats(scene)
@@ -365,14 +402,11 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     tst = nr.get_stats(scene)
-    # the same resting frame, host-synchronised one at a time: what the cold frame's wall time has to be compared with
-    sync_walls = []
-    for _ in range(10):
-        t0 = time.perf_counter()
-        render_on(handle, p)
-        torch.cuda.synchronize()
-        sync_walls.append((time.perf_counter() - t0) * 1e3)
-    nr.get_stats(scene)
+    outputs = {}
+    if keep_outputs:  # the frame and the ray classes of the last timed step, before anything else renders into `out`
+        import numpy as np
+        outputs = {"image": out.cpu().numpy(),
+                   "rays_per_frame": np.array([tst.total_rays(), tst.rays_primary, tst.rays_reflection, tst.rays_refraction, tst.rays_shadow], dtype=np.float64)}
     plain = st  # the instrumented frame's counters: rays_primary_traced (what reached a BVT query) is only counted there
     # shadow rays whose result is multiplied by exactly 0 (light samples behind the surface; hits that contribute nothing of their own: fully transparent
     # points, perfect mirrors): counted in rays_shadow — the reference traces them — but not traced by the plain (timed) frames; not part of the traced rate
@@ -386,7 +420,18 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
            # background without one (same pixels; the reference would have queried) — the rate on them is the honest traversal rate
            "rays_traced_per_frame": int(plain.rays_traced()) - elided,
            "rays_shadow_counted_not_traced_per_frame": elided,
-           "value_traced": round((plain.rays_traced() - elided) * steps / dt / 1e6, 3),
+           "value_traced": round((plain.rays_traced() - elided) * steps / dt / 1e6, 3)}
+    if not full:
+        return res, outputs
+    # the same resting frame, host-synchronised one at a time: what the cold frame's wall time has to be compared with
+    sync_walls = []
+    for _ in range(10):
+        t0 = time.perf_counter()
+        render_on(handle, p)
+        torch.cuda.synchronize()
+        sync_walls.append((time.perf_counter() - t0) * 1e3)
+    nr.get_stats(scene)
+    res.update({
            "scene_build_s": round(scene_build_s, 4),
            "scene_build_note": "nrays_scene_create as the caller sees it; BLASes of >= 2 000 triangles are built on the GPU (nrays_amd/csrc/bvh_device.hip), smaller ones and the TLASes on the host",
            "cold_frame_ms": round(cold_ms, 4), "cold_frame_gpu_ms": round(sorted(cold_gpu)[len(cold_gpu) // 2], 4),
@@ -396,7 +441,7 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
            # wall time of the first frame of a fresh handle (steady_frame_sync_ms is the resting frame measured the same way)
            "value_cold": round(st.total_rays() / (cold_ms * 1e-3) / 1e6, 3),
            "cold_frame_note": "fresh handle in a warm process (kernels loaded), median of %d: first scene::render of a camera — no cost history "
-                              "(mesh scenes: guessed order; analytic scenes: image-order lists), cost recording; host-synchronised wall time" % len(cold_walls)}
+                              "(mesh scenes: guessed order; analytic scenes: image-order lists), cost recording; host-synchronised wall time" % len(cold_walls)})
     if moving and cam.get("spp", 1) == 1:
         # a camera that moves every frame (eye shifted by 1e-3 of its distance per frame): the library re-sorts mesh frames from the previous
         # frame's costs, analytic frames keep a nearby camera's order for a few frames; frames pipelined like the steady loop
@@ -463,7 +508,7 @@ def single_gpu_measure(name, W, H, steps, warmup, args, pmc=True, moving=True):
         # the same two ratios with the GPU's rate on the rays it really sent through a BVT query (the CPU port traces every ray it counts)
         res["gpu_traced_over_cpu"] = round(res["value_traced"] / max(res["cpu_baseline"]["value"], 1e-9), 1)
         res["gpu_traced_over_cpu_at_full_host"] = round(res["value_traced"] / max(res["cpu_baseline"]["value_at_full_host"], 1e-9), 1)
-    return res
+    return res, outputs
 
 
 def drop_in_end_to_end(args):
@@ -477,8 +522,9 @@ def drop_in_end_to_end(args):
     from tools import gen_assets
     from nrays_amd import scenefile
     import oracle
+    sd = scenes_dir()
     gen_assets.gen_sponza(1.0)
-    scene = os.path.join(ROOT, "scenes", "crytek_sponza.scene")
+    scene = os.path.join(sd, "crytek_sponza.scene")
     exe = os.path.join(ROOT, "nrays_amd", "lib", "loader3d")
     runs = []
     tmp = tempfile.mkdtemp(prefix="nrays_e2e_")
@@ -496,7 +542,7 @@ def drop_in_end_to_end(args):
             runs.append(d)
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
-    res = {"command": "nrays_amd/lib/loader3d scenes/crytek_sponza.scene --times (1920x1080, one camera, stand-in OBJ %.1f MB + MTL + PNG textures)" % (os.path.getsize(os.path.join(ROOT, "scenes", "media", "crytek-sponza", "sponza.obj")) / 1e6),
+    res = {"command": "nrays_amd/lib/loader3d scenes/crytek_sponza.scene --times (1920x1080, one camera, stand-in OBJ %.1f MB + MTL + PNG textures)" % (os.path.getsize(os.path.join(sd, "media", "crytek-sponza", "sponza.obj")) / 1e6),
            "first_process": runs[0], "second_process": runs[1]}
     if not args.no_cpu_baseline:
         t0 = time.perf_counter()
@@ -520,6 +566,24 @@ def drop_in_end_to_end(args):
     return res
 
 
+DUMP_BYTES = 64e6  # what --dump-outputs may write in all
+
+
+def dump_outputs(d, outputs):
+    """--dump-outputs: one DIR/<name>.npy (float32 / float64) per array.  A frame larger than the budget is written as every s-th pixel of every
+    s-th row, as image_stride<s>.npy: the same sample in every run with the same arguments."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    budget = DUMP_BYTES - sum(a.nbytes for k, a in outputs.items() if k != "image")
+    for name, a in outputs.items():
+        if name == "image" and a.nbytes > budget:
+            s = 2
+            while a[::s, ::s].nbytes > budget:
+                s += 1
+            name, a = "image_stride%d" % s, a[::s, ::s]
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(a))
+
+
 WORKLOAD_RES = {"config4": (3840, 2160), "config5": (3840, 2160)}  # BASELINE configs 4 (sponza, 8 lights) and 5 (hairball, 64 spp)
 
 
@@ -532,6 +596,10 @@ def main():
     ap.add_argument("--height", type=int, default=0, help="default: 1080 (2160 for --scene config4)")
     ap.add_argument("--scene", default="balls", choices=["balls", "sponza", "hairball", "config4", "config5"],
                     help="balls = BASELINE config 2 (the metric's workload); config4 = crytek_sponza stand-in 3840x2160 with 8 lights")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: cold / moving / two-in-flight regimes, roofline with live "
+                         "counters, CPU baselines, the secondary workloads, the tiled frame against a single-GPU render; the options below apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary blocks (sponza / hairball stand-ins; config 4 at N > 1)")
     ap.add_argument("--steady-only", action="store_true", help="no moving-camera / two-frames-in-flight extras (for a rocprofv3 --stats run whose per-kernel averages should be the steady-state launches)")
@@ -561,16 +629,16 @@ def main():
     import __graft_entry__ as graft
     if rank == 0:
         graft.build()
-        from tools import gen_assets
-        gen_assets.gen_globe()  # before the other ranks load scenes/balls.scene
     if world > 1:
         dist.barrier()
 
     if world == 1 and args.gpus == 1:
-        result = run_single(args)
+        result, outputs = run_single(args)
     else:
-        result = run_tiled(args, rank, world, args.gpus)
+        result, outputs = run_tiled(args, rank, world, args.gpus)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, outputs)
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()
@@ -583,7 +651,8 @@ METRIC = "Mrays/s (primary+shadow+reflection), 1920x1080, 4 bounces"
 
 def run_single(args):
     W, H = args.width, args.height
-    m = single_gpu_measure(args.scene, W, H, args.steps, args.warmup, args, moving=not args.steady_only)
+    m, outputs = single_gpu_measure(args.scene, W, H, args.steps, args.warmup, args, moving=not args.steady_only, full=args.full,
+                                    keep_outputs=bool(args.dump_outputs))
     result = {
         "metric": METRIC,
         "value": m["value"], "unit": "Mrays/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -593,6 +662,10 @@ def run_single(args):
                    "rays_per_frame": m["rays_per_frame"], "rays_traced_per_frame": m["rays_traced_per_frame"],
                    "steady_state": m["steady_state"]},
         "value_traced": m["value_traced"],
+    }
+    if not args.full:
+        return result, outputs
+    result.update({
         # the other two regimes a caller can be in, as rates of the same rays: one render per camera on a fresh handle
         # (host-synchronised: compare with steady_frame_sync_ms, not with ms_per_step), and a camera that moves every frame (pipelined)
         "value_cold": m["value_cold"], "value_moving": m.get("value_moving"),
@@ -603,14 +676,14 @@ def run_single(args):
         "two_frames_in_flight_ms_per_frame": m.get("two_frames_in_flight_ms_per_frame"),
         "two_frames_in_flight_identical": m.get("two_frames_in_flight_identical"),
         "roofline": m["roofline"],
-    }
+    })
     if "cpu_baseline" in m:
         result["cpu_baseline"] = m["cpu_baseline"]
     if args.scene == "balls" and not args.no_secondary:
         # BASELINE config 3 / the north star's ">= 100x CPU on crytek_sponza at 1 GPU", and the hairball (BVH stress): same process, same run
         sec_steps, sec_warm = max(10, min(args.steps, 60)), max(3, min(args.warmup, 10))
-        result["secondary"] = {"sponza_standin": single_gpu_measure("sponza", W, H, sec_steps, sec_warm, args),
-                               "hairball_standin": single_gpu_measure("hairball", W, H, max(10, min(args.steps, 30)), sec_warm, args, moving=False)}
+        result["secondary"] = {"sponza_standin": single_gpu_measure("sponza", W, H, sec_steps, sec_warm, args)[0],
+                               "hairball_standin": single_gpu_measure("hairball", W, H, max(10, min(args.steps, 30)), sec_warm, args, moving=False)[0]}
     sp = result.get("secondary", {}).get("sponza_standin", m if args.scene == "sponza" else None)
     if sp and "gpu_over_cpu" in sp:
         # the north star's ">= 100x CPU-baseline Mrays/s on crytek_sponza at 1 GPU", on the stand-in; both legs count the same rays
@@ -627,10 +700,10 @@ def run_single(args):
         except Exception as e:  # a report, never a reason to lose the bench line
             result["secondary"]["drop_in_end_to_end"] = {"error": repr(e)}
     result["reference_toolchain"] = reference_toolchain_probe()
-    return result
+    return result, outputs
 
 
-def tiled_measure(name, W, H, steps, warmup, rank, world, owners):
+def tiled_measure(name, W, H, steps, warmup, rank, world, owners, full_run=True, keep_outputs=False):
     """N > 1 through the library's own multi-GPU path (nrays_render_multi_device, multi_gpu.cpp): band
     tiling, grouped RCCL send / receive to owner 0, k_untile — one C call per frame and rank, no Python in the step.
       world > 1   one process per GPU (torch.distributed.run): rank r drives owner r; torch.distributed only ships the
@@ -666,22 +739,24 @@ def tiled_measure(name, W, H, steps, warmup, rank, world, owners):
             dist.barrier()
         torch.cuda.synchronize()
 
-    # untimed: this rank's first owner renders its tile instrumented -> units of the dominant kernel; one plain frame -> ray classes
+    # untimed: with `full_run`, this rank's first owner renders its tile instrumented -> units of the dominant kernel; plain frames -> ray classes
     owner0, h0 = ss.local_scenes()[0]
     band = tiling.DEFAULT_BAND_ROWS
-    tp = tiling.tile_params(full, owner0, owners, band)
-    rows = lib.nrays_tile_rows(C.byref(tp))
-    scratch = torch.empty((rows, W, 3), dtype=torch.float32, device="cuda")
-    abi.check(lib.nrays_render_device_counted(h0, C.byref(tp), C.c_void_p(scratch.data_ptr()), None, abi.COUNT_AS_TIMED))  # the timed tile kernel's own work
-    pk = abi.NraysStats()
-    abi.check(lib.nrays_get_primary_kernel_stats(h0, C.byref(pk)))
+    if full_run:
+        tp = tiling.tile_params(full, owner0, owners, band)
+        rows = lib.nrays_tile_rows(C.byref(tp))
+        scratch = torch.empty((rows, W, 3), dtype=torch.float32, device="cuda")
+        abi.check(lib.nrays_render_device_counted(h0, C.byref(tp), C.c_void_p(scratch.data_ptr()), None, abi.COUNT_AS_TIMED))  # the timed tile kernel's own work
+        pk = abi.NraysStats()
+        abi.check(lib.nrays_get_primary_kernel_stats(h0, C.byref(pk)))
     for _ in range(4):  # plain frames: ray classes, and the per-camera scheduling state of every owner settles (see single_gpu_measure)
         ss.render_device(full, fptr)
     ss.sync()
     st = ss.stats()
-    tile_costs = abi.NraysTileCosts()
-    if lib.nrays_get_tile_costs(h0, C.byref(tile_costs)) != 0:
-        tile_costs = None
+    if full_run:
+        tile_costs = abi.NraysTileCosts()
+        if lib.nrays_get_tile_costs(h0, C.byref(tile_costs)) != 0:
+            tile_costs = None
     rays_t = torch.tensor([st.total_rays(), st.rays_primary, st.rays_reflection, st.rays_refraction, st.rays_shadow],
                           dtype=torch.float64, device="cuda")
     if world > 1:
@@ -703,6 +778,18 @@ def tiled_measure(name, W, H, steps, warmup, rank, world, owners):
         dt_t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(dt_t, op=dist.ReduceOp.MAX)
         dt = float(dt_t.item())
+    outputs = {"image": frame.cpu().numpy()} if (keep_outputs and rank == 0) else {}
+    res = None
+    if rank == 0:
+        res = {"value": round(rays_total * steps / dt / 1e6, 3), "unit": "Mrays/s", "steps": steps, "warmup": warmup,
+               "ms_per_step": round(dt / steps * 1e3, 5),
+               "config": {"workload": desc % (W, H), "resolution": [W, H], "ray_per_pixel": int(cam.get("spp", 1)), "parallelism": mode,
+                          "rays_per_frame": {"total": int(rays_total), "primary": int(rays_t[1].item()), "reflection": int(rays_t[2].item()),
+                                             "refraction": int(rays_t[3].item()), "shadow": int(rays_t[4].item())}}}
+    if not full_run:
+        ss.close()
+        lib.nrays_comm_destroy(comm)
+        return res, outputs
     tst = ss.stats()  # HIP-event timings of this rank's first owner over the timed steps
     # where a frame spends its time on every rank (nrays_multi_get_timings: events on the owner's render / communication streams)
     tm = ss.timings()
@@ -714,7 +801,6 @@ def tiled_measure(name, W, H, steps, warmup, rank, world, owners):
         all_tm = [tm_t]
     per_rank = [{"owner": int(v[3].item()), "render_ms": round(v[0].item(), 4), "exchange_ms": round(v[1].item(), 4), "untile_ms": round(v[2].item(), 4)} for v in all_tm]
 
-    check = None
     if rank == 0:  # the gathered, un-permuted frame equals a direct single-GPU render of the whole frame (untimed)
         direct = torch.empty((H, W, 3), dtype=torch.float32, device="cuda")
         abi.check(lib.nrays_render_device(scene.device_handle(), C.byref(full), C.c_void_p(direct.data_ptr()), None))
@@ -723,43 +809,38 @@ def tiled_measure(name, W, H, steps, warmup, rank, world, owners):
         elided = int(nr.get_stats(scene).rays_shadow_elided)  # the plain frame's shadow rays that are multiplied by 0: counted, not traced
         abi.check(lib.nrays_render_device_instrumented(scene.device_handle(), C.byref(full), C.c_void_p(direct.data_ptr()), None))
         traced = nr.get_stats(scene).rays_traced() - elided  # (rays_primary_traced is counted by instrumented renders only)
-    res = None
-    if rank == 0:
         owned = len(tiling.owned_rows(H, band, owner0, owners))
-        res = {"value": round(rays_total * steps / dt / 1e6, 3), "unit": "Mrays/s", "steps": steps, "warmup": warmup,
-               "ms_per_step": round(dt / steps * 1e3, 5), "value_traced": round(traced * steps / dt / 1e6, 3),
-               # per rank (one process per GPU) or of the first owner (one process for all owners): tile render / exchange / un-permute
-               "per_rank_ms": per_rank,
-               "config": {"workload": desc % (W, H), "resolution": [W, H], "ray_per_pixel": int(cam.get("spp", 1)), "parallelism": mode,
-                          "tiled_frame_identical_to_single_gpu_render": check,
-                          "rays_per_frame": {"total": int(rays_total), "primary": int(rays_t[1].item()), "reflection": int(rays_t[2].item()),
-                                             "refraction": int(rays_t[3].item()), "shadow": int(rays_t[4].item())},
-                          "rays_traced_per_frame": int(traced), "rays_shadow_counted_not_traced_per_frame": elided},
-               # owner 0's tile kernel; no counters at N > 1 (the profiler leg runs at N = 1 only)
-               "roofline": roofline_block(pk, tst, W, owned, lib.nrays_scene_device_bytes(h0), None, None, tile_costs)}
+        res["value_traced"] = round(traced * steps / dt / 1e6, 3)
+        # per rank (one process per GPU) or of the first owner (one process for all owners): tile render / exchange / un-permute
+        res["per_rank_ms"] = per_rank
+        res["config"].update({"tiled_frame_identical_to_single_gpu_render": check,
+                              "rays_traced_per_frame": int(traced), "rays_shadow_counted_not_traced_per_frame": elided})
+        # owner 0's tile kernel; no counters at N > 1 (the profiler leg runs at N = 1 only)
+        res["roofline"] = roofline_block(pk, tst, W, owned, lib.nrays_scene_device_bytes(h0), None, None, tile_costs)
     ss.close()
     lib.nrays_comm_destroy(comm)
-    return res
+    return res, outputs
 
 
 def run_tiled(args, rank, world, owners):
     W, H = args.width, args.height
-    m = tiled_measure(args.scene, W, H, args.steps, args.warmup, rank, world, owners)
+    m, outputs = tiled_measure(args.scene, W, H, args.steps, args.warmup, rank, world, owners, full_run=args.full, keep_outputs=bool(args.dump_outputs))
     # the frame DESIGN.md 7 names as the one to tile (the metric's balls frame takes 0.05 ms on one GPU: the worst possible
     # strong-scaling workload): BASELINE config 4, reported beside the contract's line at every N > 1
     sec = None
-    if args.scene == "balls" and not args.no_secondary:
+    if args.full and args.scene == "balls" and not args.no_secondary:
         cw, ch = WORKLOAD_RES["config4"]
-        sec = tiled_measure("config4", cw, ch, max(5, min(args.steps, 20)), max(2, min(args.warmup, 5)), rank, world, owners)
+        sec = tiled_measure("config4", cw, ch, max(5, min(args.steps, 20)), max(2, min(args.warmup, 5)), rank, world, owners)[0]
     if rank != 0:
-        return None
+        return None, outputs
     result = {"metric": METRIC, "value": m["value"], "unit": "Mrays/s", "n_gpus": owners, "steps": args.steps, "warmup": args.warmup,
               "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-              "dtype": "f64", "data": "synthetic", "config": m["config"], "value_traced": m["value_traced"], "per_rank_ms": m["per_rank_ms"],
-              "roofline": m["roofline"]}
+              "dtype": "f64", "data": "synthetic", "config": m["config"]}
+    if args.full:
+        result.update({"value_traced": m["value_traced"], "per_rank_ms": m["per_rank_ms"], "roofline": m["roofline"]})
     if sec is not None:
         result["secondary"] = {"config4_sponza_standin_4k_8_lights": sec}
-    return result
+    return result, outputs
 
 
 if __name__ == "__main__":

@@ -47,3 +47,62 @@ def test_roofline_block_units_and_fractions():
     tc.shader_clock_hz = 0.0
     r2 = bench.roofline_block(pk, tst, W, H, 2_000_000, None, None, tc, step_ms=0.048, pk_ref=pk_ref)
     assert r2["frac"] is None and "unmeasured" in r2["bound"] and "limiter" not in r2 and r2["contract_frac"] == r["contract_frac"]
+
+
+def test_benchmark_media_are_written_outside_the_checkout(built, monkeypatch):
+    """The benchmark may run on a checkout it cannot write to: the procedural media go into a private copy of scenes/, from which
+    scenes/balls.scene loads, and nothing is written under scenes/."""
+    import bench
+    from tools import gen_assets
+    from nrays_amd import scenefile
+    monkeypatch.setattr(gen_assets, "MEDIA", gen_assets.MEDIA)  # restored after the test
+    monkeypatch.setattr(bench, "_SCENES", None)
+    scenes = os.path.join(ROOT, "scenes")
+    before = sorted(os.listdir(scenes))
+    d = bench.scenes_dir()
+    assert not d.startswith(ROOT) and gen_assets.gen_globe() == os.path.join(d, "media", "globe.png")
+    fs = scenefile.FileScene(os.path.join(d, "balls.scene"))
+    assert len(fs.cameras) == 1
+    fs.close()
+    assert sorted(os.listdir(scenes)) == before
+
+
+def test_dump_outputs_keeps_within_the_budget(tmp_path):
+    """--dump-outputs: a 1080p frame is written whole, a 4K frame as every second pixel of every second row; at most 64 MB in all, dtypes kept."""
+    import numpy as np
+    import bench
+    rays = np.arange(5, dtype=np.float64)
+    for (h, w), name, shape in (((1080, 1920), "image", (1080, 1920, 3)), ((2160, 3840), "image_stride2", (1080, 1920, 3))):
+        img = np.random.default_rng(0).random((h, w, 3), dtype=np.float32)
+        d = tmp_path / name
+        bench.dump_outputs(str(d), {"image": img, "rays_per_frame": rays})
+        assert sorted(os.listdir(d)) == sorted([name + ".npy", "rays_per_frame.npy"])
+        assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= bench.DUMP_BYTES
+        got = np.load(d / (name + ".npy"))
+        assert got.dtype == np.float32 and got.shape == shape and np.array_equal(got, img[::h // 1080, ::w // 1920])
+        r = np.load(d / "rays_per_frame.npy")
+        assert r.dtype == np.float64 and np.array_equal(r, rays)
+
+
+def test_drop_in_end_to_end_reports_both_processes(built, monkeypatch):
+    """--full's drop_in_end_to_end block, with loader3d's two runs stubbed (they need a GPU): both processes' stage times reach the block, and
+    loader3d reads the scene from the private copy of scenes/."""
+    import json
+    import subprocess
+    import types
+    import bench
+    from tools import gen_assets
+    monkeypatch.setattr(gen_assets, "MEDIA", gen_assets.MEDIA)  # restored after the test
+    monkeypatch.setattr(bench, "_SCENES", None)
+    times = {"total": 400.0, "render_gpu_events": 3.0, "parse_scene_obj_mtl_textures": 230.0, "nrays_scene_create_incl_hip_init": 120.0}
+    calls = []
+
+    def run(cmd, **kw):
+        calls.append(cmd)
+        return types.SimpleNamespace(returncode=0, stdout=json.dumps({"loader3d_times_ms": times}) + "\n", stderr="")
+    monkeypatch.setattr(subprocess, "run", run)
+    res = bench.drop_in_end_to_end(types.SimpleNamespace(no_cpu_baseline=True))
+    assert "error" not in res, res
+    assert res["first_process"]["loader3d_times_ms"] == times and res["second_process"]["loader3d_times_ms"] == times
+    assert "MB + MTL" in res["command"] and "0.8 %" in res["note"]
+    assert len(calls) == 2 and all(c[1] == os.path.join(bench.scenes_dir(), "crytek_sponza.scene") for c in calls)

@@ -1,16 +1,17 @@
 """The Rust side of the drop-in (integration/rust/) cannot be compiled here (no Rust toolchain), so
 these tests keep it honest mechanically: the `#[repr(C)]` structs of gpu_ffi.rs list exactly the fields of
 include/nrays_abi.h in the same order, every entry point of the header is declared, every type gpu.rs relies on is
-defined, and the patch applies cleanly to the reference checkout where it is mounted."""
+defined, and the patch applies cleanly to the reference checkout (checked against digests of the checkout's text, see
+tests/golden/make_reference_patch_digests.py)."""
+import hashlib
+import json
 import os
 import re
-import shutil
-import subprocess
-
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RUST = os.path.join(ROOT, "integration", "rust")
+PATCH = os.path.join(RUST, "patches", "0001-gpu-trace-loop.patch")
+PREIMAGE_DIGESTS = os.path.join(ROOT, "tests", "golden", "reference_patch_preimage.json")
 HEADER = open(os.path.join(ROOT, "include", "nrays_abi.h")).read()
 FFI = open(os.path.join(RUST, "src", "gpu_ffi.rs")).read()
 GPU = open(os.path.join(RUST, "src", "gpu.rs")).read()
@@ -63,11 +64,45 @@ def test_gpu_rs_defines_what_it_uses():
         assert "pub fn %s(" % name in FFI, name
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/src") or shutil.which("patch") is None, reason="the reference checkout is only mounted in the build container")
-def test_patch_applies_to_the_reference_checkout(tmp_path):
-    work = tmp_path / "nrays"
-    shutil.copytree("/root/reference", str(work), ignore=shutil.ignore_patterns(".git"))
-    r = subprocess.run(["patch", "-p1", "--dry-run", "-i", os.path.join(RUST, "patches", "0001-gpu-trace-loop.patch")], cwd=str(work),
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "FAILED" not in r.stdout and "fuzz" not in r.stdout
+def patch_hunks(text):
+    """{path: [(first old line, old line count, pre-image lines)]} of a unified diff with a/ b/ prefixes; the hunk headers' counts are checked."""
+    out, path, lines = {}, None, iter(text.split("\n"))
+    for line in lines:
+        if line.startswith("+++ "):
+            path = line[4:].split("\t")[0].split("/", 1)[1]
+            out[path] = []
+        m = re.match(r"@@ -(\d+)(?:,(\d+))? \+(\d+)(?:,(\d+))? @@", line)
+        if not m:
+            continue
+        n_old, n_new = int(m.group(2) or 1), int(m.group(4) or 1)
+        pre, new = [], 0
+        while len(pre) < n_old or new < n_new:
+            body = next(lines)
+            if body.startswith("\\"):  # "\ No newline at end of file"
+                continue
+            tag = body[:1] or " "
+            assert tag in " -+", (path, body)
+            if tag in " -":
+                pre.append(body[1:])
+            if tag in " +":
+                new += 1
+        assert len(pre) == n_old and new == n_new, (path, line)
+        out[path].append((int(m.group(1)), n_old, pre))
+    return out
+
+
+def test_patch_applies_to_the_reference_checkout():
+    """Every hunk's pre-image (context and '-' lines) is the reference checkout's text at the lines its header names — `patch -p1` applies it
+    without offset or fuzz — checked against sha256 digests of those lines of the checkout (tests/golden/reference_patch_preimage.json)."""
+    pinned = json.load(open(PREIMAGE_DIGESTS))
+    assert pinned["patch"] == os.path.relpath(PATCH, ROOT)
+    hunks = patch_hunks(open(PATCH, newline="").read())
+    assert sorted(hunks) == sorted(pinned["files"])
+    for path, hs in hunks.items():
+        ref = pinned["files"][path]
+        assert [(start, n) for start, n, _ in hs] == [(start, n) for start, n, _ in ref["hunks"]], path
+        end = 0
+        for (start, n, pre), (_, _, digest) in zip(hs, ref["hunks"]):
+            assert end < start and start - 1 + n <= ref["lines"], (path, start)  # in order, inside the file
+            assert hashlib.sha256("\n".join(pre).encode()).hexdigest() == digest, (path, start)
+            end = start - 1 + n
