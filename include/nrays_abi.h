@@ -29,8 +29,9 @@
 extern "C" {
 #endif
 
-/* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6). */
-#define NRAYS_ABI_VERSION 5
+/* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6); 6 = nrays_trace_rays_device / nrays_trace_rays /
+ * nrays_intersects_rays_device (caller-supplied rays). */
+#define NRAYS_ABI_VERSION 6
 
 typedef enum NraysStatus {
     NRAYS_OK = 0,
@@ -237,6 +238,36 @@ int nrays_render_device_instrumented(NraysScene* scene, const NraysRenderParams*
  * (bench.py: roofline_block).  Pixels are the same either way. */
 #define NRAYS_COUNT_AS_TIMED 1u
 int nrays_render_device_counted(NraysScene* scene, const NraysRenderParams* params, float* out_rgb_device, void* hip_stream, uint32_t flags);
+
+/* Scene::trace (src/scene.rs:163-193) on n caller-supplied rays: out_rgb[3i..3i+2] = trace(ray i), with the reflection / refraction recursion,
+ * the lights and the generation rules of a render.  Replaces direct calls of scene.trace (own camera models, light / AO baking, picking).
+ *   origins, dirs  n x 3 doubles, xyz interleaved.  Directions are used as given: unit length is expected (every ray the reference builds is
+ *                  normalised, scene.rs:87,200,236); the library does not normalise.
+ *   refr           n doubles, RayWithEnergy::refr; NULL = 1.0 for every ray (RayWithEnergy::new, ray_with_energy.rs:11).
+ *   energy         n floats, RayWithEnergy::energy; NULL = 1.0.
+ *   keys           n RNG path keys (area-light sampling hashes them exactly as a render hashes a primary ray's); NULL = the key of ray i is i.
+ *   max_depth      as NraysRenderParams::max_depth (0 = the energy rule only; the hard cap of 64 generations applies); the input rays are depth 0.
+ *   out_rgb        n x 3 floats.
+ * NULL scene / origins / dirs / out_rgb -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK without work; a continuation-queue overflow ->
+ * NRAYS_ERR_QUEUE_OVERFLOW.  The rays are traced in chunks of at most 2^22 (results do not depend on it) with a workspace the handle owns
+ * (allocated on first use, grown only when a chunk needs more, freed by nrays_scene_destroy).  A batch follows the handle's threading
+ * contract and leaves what the handle reports about its renders (nrays_get_stats, nrays_get_primary_kernel_stats, nrays_get_tile_costs) and
+ * its per-camera scheduling state untouched.
+ * Every pointer is DEVICE memory on the scene's device and the work is enqueued on `hip_stream` (a hipStream_t, NULL = default stream)
+ * without a final synchronisation unless the scene needs host-side generation control (transparent scenes). */
+int nrays_trace_rays_device(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy,
+                            const uint64_t* keys, uint32_t max_depth, float* out_rgb, void* hip_stream);
+
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_trace_rays(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy,
+                     const uint64_t* keys, uint32_t max_depth, float* out_rgb);
+
+/* Scene::intersects_ray (src/scene.rs:147-161), the transparent-shadow query, on n caller-supplied rays with max_toi[i]: out_lit[i] = 1 and
+ * out_filter[3i..3i+2] = the colour filter where the reference returns Some(filter), out_lit[i] = 0 and out_filter = (0, 0, 0) where it
+ * returns None.  origins / dirs n x 3 doubles, max_toi n doubles, out_filter n x 3 floats, out_lit n words; all DEVICE memory, enqueued on
+ * `hip_stream` without synchronisation.  NULL arguments -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK. */
+int nrays_intersects_rays_device(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
+                                 float* out_filter, uint32_t* out_lit, void* hip_stream);
 
 /* Number of rows in the compact output buffer of a (possibly tiled) render. */
 uint32_t nrays_tile_rows(const NraysRenderParams* params);

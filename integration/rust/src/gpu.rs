@@ -23,6 +23,7 @@ use ncollide3d::shape::{Ball, Capsule, Cone, Cuboid, Cylinder, Plane, TriMesh};
 use gpu_ffi::*;
 use image::Image;
 use light::Light;
+use ray_with_energy::RayWithEnergy;
 use math::{Isometry, Point, Scalar};
 use scene::{Scene, Vless};
 use scene_node::SceneNode;
@@ -351,6 +352,36 @@ impl GpuScene {
         let mut st = NraysStats::default();
         unsafe { nrays_get_stats(self.raw, &mut st) };
         st
+    }
+
+    /// `scene.trace(ray)` (src/scene.rs:163-193) for every ray of the batch, in one call (nrays_trace_rays, blocking).  `keys[i]`
+    /// is ray i's RNG path key for area-light sampling (None: key i); `max_depth` 0 = the energy rule alone, as `trace` does.
+    pub fn trace_rays(&self, rays: &[RayWithEnergy], keys: Option<&[u64]>, max_depth: u32) -> Result<Vec<Vector3<f32>>, String> {
+        if let Some(k) = keys { if k.len() != rays.len() { return Err(format!("{} keys for {} rays", k.len(), rays.len())); } }
+        let n = rays.len();
+        let mut o = Vec::with_capacity(3 * n);
+        let mut d = Vec::with_capacity(3 * n);
+        let mut refr = Vec::with_capacity(n);
+        let mut energy = Vec::with_capacity(n);
+        for r in rays {
+            o.extend_from_slice(&[r.ray.origin.x, r.ray.origin.y, r.ray.origin.z]);
+            d.extend_from_slice(&[r.ray.dir.x, r.ray.dir.y, r.ray.dir.z]);
+            refr.push(r.refr);
+            energy.push(r.energy);
+        }
+        let mut px: Vec<Vector3<f32>> = vec![Vector3::new(0.0f32, 0.0, 0.0); n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_trace_rays(self.raw, n as u32, o.as_ptr(), d.as_ptr(), refr.as_ptr(), energy.as_ptr(), kp, max_depth, px.as_mut_ptr() as *mut f32) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(px)
+    }
+
+    /// `scene.intersects_ray(ray, max_toi)` (src/scene.rs:147-161) for n rays in DEVICE memory (nrays_intersects_rays_device): origins / dirs
+    /// n x 3 f64, max_toi n f64, out_filter n x 3 f32, out_lit n u32 (1 = Some(filter), 0 = None), enqueued on `hip_stream`.
+    pub unsafe fn intersects_rays(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32,
+                                  hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_intersects_rays_device(self.raw, n, origins, dirs, max_toi, out_filter, out_lit, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
     }
 }
 

@@ -135,6 +135,75 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DSc
     }
 }
 
+// Scene::trace (scene.rs:163-193) on caller-supplied rays (nrays_trace_rays_device): ray i of the chunk is loaded as a depth-0 RayWithEnergy
+// of weight 1 whose "pixel" is i, and traced exactly as k_primary traces a primary ray — the chain's sum goes straight to out[3i..3i+2],
+// second children to the queue, whose k_bounce rounds and k_fold_fixed then add them as in a frame.  A ray's arithmetic is a one-sample
+// pixel's.  NULL refr / energy: 1.0 (RayWithEnergy::new, ray_with_energy.rs:11); NULL keys: key_base + i.  `keyed`: the scene samples
+// an area light (the keys are read by nothing else).
+template <bool STATS, int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_trace_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                              const double* __restrict__ refr, const float* __restrict__ energy,
+                                                                              const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
+                                                                              uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st;
+    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
+    st.spill_stride = gridDim.x * kBlock;
+    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    st.lds0 = Stack::addr((lds_u32*)lds_stack);
+    st.park = nullptr;
+    st.init();
+    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
+#ifdef NR_PHASE_TIMING
+    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
+#endif
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t idx = base + threadIdx.x;
+        const bool active = idx < n;
+        RayState ray;
+        ray.o = D3(0, 0, 0); ray.d = D3(0, 0, 1); ray.refr = 1.0; ray.energy = 0.0f; ray.weight = 0.0f; ray.key = 0; ray.pixel = 0;
+        if (active) {
+            const size_t i3 = 3 * (size_t)idx;
+            ray.o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]); ray.d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
+            ray.refr = refr ? refr[idx] : 1.0; ray.energy = energy ? energy[idx] : 1.0f; ray.weight = 1.0f;
+            ray.key = keys ? keys[idx] : key_base + idx; ray.pixel = idx;
+        }
+        const f3 c = trace_chain<STATS, FEAT>(S, st, active, ray, 0u, max_depth, qo, cnt, keyed != 0u);
+        if (active) { out[3 * (size_t)idx] = c.x; out[3 * (size_t)idx + 1] = c.y; out[3 * (size_t)idx + 2] = c.z; }
+    }
+    flush_counters(ctr, cnt, STATS);
+}
+
+// Scene::intersects_ray (scene.rs:147-161) on caller-supplied rays (nrays_intersects_rays_device): k_cast_batch's mode 1 with the
+// reference's Option<filter> as a lit flag and the filter (0, 0, 0 where an opaque node blocks the ray).
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                                   const double* __restrict__ max_toi, float* __restrict__ out_filter,
+                                                                                   uint32_t* __restrict__ out_lit, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st;
+    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
+    st.spill_stride = gridDim.x * kBlock;
+    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    st.lds0 = Stack::addr((lds_u32*)lds_stack);
+    st.park = nullptr;
+    st.init();
+    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
+#ifdef NR_PHASE_TIMING
+    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
+#endif
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const size_t i3 = 3 * (size_t)i;
+        const d3 o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]), d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
+        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+        const bool blocked = traverse<true, false, FEAT>(S, st, o, d, max_toi[i], hit, filter, cnt);
+        out_lit[i] = blocked ? 0u : 1u;
+        out_filter[i3] = blocked ? 0.0f : filter.x; out_filter[i3 + 1] = blocked ? 0.0f : filter.y; out_filter[i3 + 2] = blocked ? 0.0f : filter.z;
+    }
+}
+
 // Wave tiles in descending order of last frame's cost.  XCD x's work list is the subset { i : i mod 8 == x } of the
 // wave tiles (a uniform sample of the image), sorted by workgroup x with a 256-bucket counting sort in LDS
 // on (exponent, 3 mantissa bits) of the cycle counts — an approximate order is all a work queue needs.
@@ -418,17 +487,19 @@ static int upload_joined(NraysScene* sc, const std::vector<std::pair<const T*, s
     return NRAYS_OK;
 }
 
-static int ensure_queue(NraysScene* sc, uint32_t capacity) {
-    if (capacity <= sc->queue_capacity) return NRAYS_OK;
+// The two continuation queues of a render (the handle's) or of a caller-ray batch (TraceWorkspace), grown to `capacity` rays.
+static int ensure_queue_pair(QueueMem* queue, uint32_t& queue_capacity, uint32_t capacity) {
+    if (capacity <= queue_capacity) return NRAYS_OK;
+    queue_capacity = 0; // (a failure below leaves the pair empty, not half-sized)
     for (int k = 0; k < 2; ++k) {
-        if (sc->queue[k].block) { (void)hipFree(sc->queue[k].block); sc->queue[k].block = nullptr; }
+        if (queue[k].block) { (void)hipFree(queue[k].block); queue[k].block = nullptr; }
         size_t cap = capacity;
         size_t bytes = cap * (8 * 7 + 4 * 4 + 8);
         void* p = nullptr;
         HIP_TRY(hipMalloc(&p, bytes));
-        sc->queue[k].block = p;
+        queue[k].block = p;
         char* c = (char*)p;
-        RayQueue& q = sc->queue[k].q;
+        RayQueue& q = queue[k].q;
         for (int a = 0; a < 3; ++a) { q.o[a] = (double*)c; c += cap * 8; }
         for (int a = 0; a < 3; ++a) { q.d[a] = (double*)c; c += cap * 8; }
         q.refr = (double*)c; c += cap * 8;
@@ -438,9 +509,10 @@ static int ensure_queue(NraysScene* sc, uint32_t capacity) {
         q.pixel = (uint32_t*)c; c += cap * 4;
         q.depth = (uint32_t*)c; c += cap * 4;
     }
-    sc->queue_capacity = capacity;
+    queue_capacity = capacity;
     return NRAYS_OK;
 }
+static int ensure_queue(NraysScene* sc, uint32_t capacity) { return ensure_queue_pair(sc->queue, sc->queue_capacity, capacity); }
 
 // Words of the cost-ordered work list (k_tile_order): entry k of XCD list x lives at order[8 k + x], and a list holds the wave
 // tiles i = x (mod 8) — up to ceil(nwt / 8) of them — each as up to 2^lsl light-parallel parts.  The array therefore needs
@@ -882,6 +954,130 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     return NRAYS_OK;
 }
 
+// ---- caller-ray batches: nrays_trace_rays*, nrays_intersects_rays_device (Scene::trace / Scene::intersects_ray, scene.rs:147-193) ----------------
+static int trace_workspace(NraysScene* sc, TraceWorkspace** out) {
+    if (!sc->tw) {
+        sc->tw = new (std::nothrow) TraceWorkspace();
+        if (!sc->tw) return fail(NRAYS_ERR_OOM, "trace workspace");
+    }
+    TraceWorkspace* w = sc->tw;
+    if (!w->d_counts) HIP_TRY(hipMalloc((void**)&w->d_counts, kTraceCountWords * sizeof(uint32_t)));
+    if (!w->d_counters) HIP_TRY(hipMalloc((void**)&w->d_counters, sizeof(DeviceCounters)));
+    if (sc->spill_entries && !w->d_spill) HIP_TRY(hipMalloc((void**)&w->d_spill, (size_t)kMaxGrid * kBlock * sc->spill_entries * sizeof(uint32_t)));
+    *out = w;
+    return NRAYS_OK;
+}
+static void trace_workspace_release(NraysScene* sc) {
+    TraceWorkspace* w = sc->tw;
+    if (!w) return;
+    if (w->used) (void)hipStreamSynchronize(w->last_stream);
+    for (int k = 0; k < 2; ++k) if (w->queue[k].block) (void)hipFree(w->queue[k].block);
+    if (w->d_fixed) (void)hipFree(w->d_fixed);
+    if (w->d_counts) (void)hipFree(w->d_counts);
+    if (w->d_counters) (void)hipFree(w->d_counters);
+    if (w->d_spill) (void)hipFree(w->d_spill);
+    if (w->d_stage) (void)hipFree(w->d_stage);
+    delete w;
+    sc->tw = nullptr;
+}
+// The handle's threading contract: a batch on another stream than the handle's previous work (its last render, its last batch) is
+// ordered behind it, and a render that follows on yet another stream is ordered behind the batch (render_impl waits on ev_switch
+// recorded on sc->last_stream when last_timed is false).  Nothing a render reports (counters, timings, tile costs) is touched.
+static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
+    const hipStream_t prev[2] = {sc->have_last ? sc->last_stream : stream, w->used ? w->last_stream : stream};
+    for (int k = 0; k < 2; ++k) {
+        if (prev[k] == stream || (k == 1 && prev[1] == prev[0])) continue;
+        if (!sc->ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(sc->ev_switch, prev[k]));
+        HIP_TRY(hipStreamWaitEvent(stream, sc->ev_switch, 0));
+    }
+    return NRAYS_OK;
+}
+static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
+    w->last_stream = stream; w->used = true;
+    if (sc->have_last) { sc->last_stream = stream; sc->last_timed = false; }
+}
+// Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
+static bool batch_mesh_only(const NraysScene* sc) { return (sc->features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
+
+// One chunk (n <= kTraceChunk) of nrays_trace_rays_device: k_trace_rays, then — double-branching scenes only — the k_bounce rounds of the
+// queued second children and k_fold_fixed, as render_impl runs them for a sample batch (the host reads the queue count every fourth round).
+static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
+                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream) {
+    const bool queued = sc->host.any_double_branch;
+    if (queued) { // render_impl's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
+        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
+        if (rc != NRAYS_OK) return rc;
+        const size_t slots = (size_t)n * 3;
+        if (slots > w->fixed_slots) {
+            if (w->d_fixed) { (void)hipFree(w->d_fixed); w->d_fixed = nullptr; w->fixed_slots = 0; }
+            HIP_TRY(hipMalloc((void**)&w->d_fixed, slots * sizeof(long long)));
+            HIP_TRY(hipMemsetAsync(w->d_fixed, 0, slots * sizeof(long long), stream)); // k_fold_fixed leaves it cleared
+            w->fixed_slots = slots;
+        }
+        if (w->fixed_dirty) { HIP_TRY(hipMemsetAsync(w->d_fixed, 0, w->fixed_slots * sizeof(long long), stream)); w->fixed_dirty = false; }
+    }
+    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
+    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
+    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
+    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const uint32_t keyed = sc->host.any_area_light ? 1u : 0u;
+    // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
+    if (sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else hipLaunchKernelGGL((k_trace_rays<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    HIP_TRY(hipGetLastError());
+    if (!queued) return NRAYS_OK;
+    uint32_t seen[2] = {0u, 0u}; // queue count of the round, overflow word — read together, after every round before it has run
+    bool drained = false, folded = true;
+    for (uint32_t r = 1; r <= (uint32_t)kMaxGenerations; ++r) {
+        if ((r - 1u) % 4u == 0u) {
+            HIP_TRY(hipMemcpyAsync(&seen[0], w->d_counts + r, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(&seen[1], overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (seen[0] == 0u) { drained = true; break; }
+        }
+        const uint32_t launch_n = std::min<uint32_t>(seen[0], w->queue_capacity);
+        const uint32_t g = std::max<uint32_t>(std::min<uint32_t>((launch_n + kBlock - 1) / kBlock, kMaxGrid), std::min<uint32_t>((uint32_t)sc->num_cus, kMaxGrid));
+        QueueOut qn; qn.q = w->queue[(r + 1) & 1].q; qn.capacity = w->queue_capacity; qn.count = w->d_counts + r + 1; qn.overflow = overflow;
+        if (sc->d.no_elide) hipLaunchKernelGGL(k_bounce<true>, dim3(g), dim3(kBlock), 0, stream, sc->d, w->queue[r & 1].q, w->d_counts + r, w->queue_capacity, qn, w->d_fixed, w->d_counters, w->d_spill, max_depth);
+        else hipLaunchKernelGGL(k_bounce<false>, dim3(g), dim3(kBlock), 0, stream, sc->d, w->queue[r & 1].q, w->d_counts + r, w->queue_capacity, qn, w->d_fixed, w->d_counters, w->d_spill, max_depth);
+        HIP_TRY(hipGetLastError());
+        folded = false; w->fixed_dirty = true;
+    }
+    if (!folded) {
+        const size_t m = (size_t)n * 3;
+        hipLaunchKernelGGL(k_fold_fixed, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream, out, w->d_fixed, m);
+        HIP_TRY(hipGetLastError());
+        w->fixed_dirty = false;
+    }
+    if (!drained) { // the generation cap ended the rounds: the overflow word has not been read after the last of them
+        HIP_TRY(hipMemcpyAsync(&seen[1], overflow, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    if (seen[1]) return fail(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some traced colours are incomplete");
+    return NRAYS_OK;
+}
+
+static int trace_rays_device_impl(NraysScene* sc, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
+                                  const uint64_t* keys, uint32_t max_depth, float* out, hipStream_t stream) {
+    if (!sc || !o || !d || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        rc = trace_chunk(sc, w, nc, o + 3 * (size_t)c0, d + 3 * (size_t)c0, refr ? refr + c0 : nullptr, energy ? energy + c0 : nullptr,
+                         keys ? (const unsigned long long*)keys + c0 : nullptr, (unsigned long long)c0, max_depth, out + 3 * (size_t)c0, stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 } // namespace nrays
 
 extern "C" {
@@ -1177,6 +1373,7 @@ void nrays_scene_destroy(NraysScene* sc) {
         if (sc->ev_end[k]) (void)hipEventDestroy(sc->ev_end[k]);
     }
     wavefront_release(sc);
+    trace_workspace_release(sc);
     if (sc->own_stream) (void)hipStreamDestroy(sc->own_stream);
     delete sc;
 }
@@ -1437,6 +1634,76 @@ int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const doub
 #undef CAST_TRY
     release();
     return NRAYS_OK;
+}
+
+int nrays_trace_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                            uint32_t max_depth, float* out_rgb, void* hip_stream) {
+    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, (hipStream_t)hip_stream);
+}
+
+int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                     uint32_t max_depth, float* out_rgb) {
+    if (!sc || !origins || !dirs || !out_rgb) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    // device copies of one chunk's arrays: origins, directions (3 f64), refr (f64), keys (u64), energy (f32), colours (3 f32) — 80 bytes a ray
+    const size_t per = std::min<uint32_t>(n, kTraceChunk);
+    if (per > w->stage_rays) {
+        if (w->d_stage) { (void)hipFree(w->d_stage); w->d_stage = nullptr; w->stage_rays = 0; }
+        HIP_TRY(hipMalloc(&w->d_stage, per * 80));
+        w->stage_rays = per;
+    }
+    const size_t cap = w->stage_rays;
+    double* s_o = (double*)w->d_stage; double* s_d = s_o + 3 * cap; double* s_r = s_d + 3 * cap;
+    unsigned long long* s_k = (unsigned long long*)(s_r + cap); float* s_e = (float*)(s_k + cap); float* s_out = s_e + cap;
+    const hipStream_t stream = sc->own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream); };
+        hipError_t e = up(s_o, origins + 3 * (size_t)c0, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_d, dirs + 3 * (size_t)c0, (size_t)nc * 24);
+        if (e == hipSuccess && refr) e = up(s_r, refr + c0, (size_t)nc * 8);
+        if (e == hipSuccess && keys) e = up(s_k, keys + c0, (size_t)nc * 8);
+        if (e == hipSuccess && energy) e = up(s_e, energy + c0, (size_t)nc * 4);
+        if (e != hipSuccess) { rc = fail(NRAYS_ERR_HIP, std::string("trace batch upload: ") + hipGetErrorString(e)); break; }
+        rc = trace_chunk(sc, w, nc, s_o, s_d, refr ? s_r : nullptr, energy ? s_e : nullptr, keys ? s_k : nullptr, (unsigned long long)c0, max_depth, s_out, stream);
+        if (rc == NRAYS_OK) {
+            e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_out, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) rc = fail(NRAYS_ERR_HIP, std::string("trace batch read-back: ") + hipGetErrorString(e));
+        }
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                 uint32_t* out_lit, void* hip_stream) {
+    if (!sc || !origins || !dirs || !max_toi || !out_filter || !out_lit) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool mesh = (sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
+    for (uint32_t c0 = 0; c0 < n; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit ray indices far from overflow)
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const double *o = origins + 3 * (size_t)c0, *d = dirs + 3 * (size_t)c0, *t = max_toi + c0;
+        if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else hipLaunchKernelGGL((k_intersects_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { rc = fail(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e)); break; }
+    }
+    batch_end(sc, w, stream);
+    return rc;
 }
 
 int nrays_untile_device(const float* gathered, float* out_rgb_device, uint32_t width, uint32_t height, uint32_t band_rows,

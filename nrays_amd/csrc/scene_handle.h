@@ -27,6 +27,23 @@ struct CamSnap { double eye[3] = {0, 0, 0}; double dir[4][3] = {}; double pix_an
 constexpr int kNumCounts = kMaxGenerations + 2 + 8; // queue round counters + 8 per-XCD work counters
 constexpr int kMaxGrid = 2048;     // upper bound of the persistent grid (the launch uses CUs x waves/SIMD workgroups)
 
+// Workspace of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device; nrays_hip.hip): created on first use, grown
+// only when a chunk needs more, freed with the handle.  It shares no device memory with the renders, so that a batch leaves their
+// per-frame state (queues, counters, fixed-point sums, scheduling state) exactly as it found it.
+constexpr uint32_t kTraceChunk = 1u << 22; // rays per chunk of a batch: bounds the queues and sums below for any batch size
+constexpr int kTraceCountWords = kMaxGenerations + 3; // round counters 0..kMaxGenerations + 1, then the batch's queue-overflow word
+struct TraceWorkspace {
+    QueueMem queue[2];
+    uint32_t queue_capacity = 0;
+    long long* d_fixed = nullptr; size_t fixed_slots = 0; // left cleared by k_fold_fixed
+    bool fixed_dirty = false;                               // rounds were enqueued and their k_fold_fixed was not (an error in between)
+    uint32_t* d_counts = nullptr;                           // kTraceCountWords
+    DeviceCounters* d_counters = nullptr;                   // sink of the kernels' ray-class counters (never reported)
+    uint32_t* d_spill = nullptr;                            // traversal-stack spill region of the batch kernels
+    void* d_stage = nullptr; size_t stage_rays = 0;         // nrays_trace_rays: device copies of one chunk's host arrays
+    hipStream_t last_stream = nullptr; bool used = false;   // stream of the last batch (ordering, nrays_scene_destroy)
+};
+
 } // namespace nrays
 
 using nrays::DeviceCounters; using nrays::DScene; using nrays::HostScene; using nrays::QueueMem;
@@ -119,6 +136,7 @@ struct NraysScene {
     int occ_override = -1;                          // NRAYS_OCC=2|3: waves per SIMD of the alpha-shadow mesh kernels (A/B)
     bool cull_enabled = true;                       // NRAYS_SCREEN_CULL=0: no wave tile is decided from the scene's screen bounds
     nrays::WavefrontState* wf = nullptr;            // staged (wavefront) path: queues, chunk tables, sums (wavefront.hip)
+    nrays::TraceWorkspace* tw = nullptr;            // caller-ray batches (nrays_trace_rays*), created on first use
     int wavefront_mode = -1;                        // NRAYS_WAVEFRONT: 0 = never, 1 = whenever the scene is eligible, -1 = the library's rule (wavefront.hip)
     NraysStats last;
     uint64_t last_primary = 0, last_primary_first_batch = 0;

@@ -441,3 +441,186 @@ def get_stats(scene):
     st = abi.NraysStats()
     abi.check(abi.load_hip_lib().nrays_get_stats(scene.device_handle(), C.byref(st)))
     return st
+
+
+# ---- caller-supplied rays: Scene::trace / Scene::intersects_ray (src/scene.rs:147-193) in batches ----------------------------------------
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def _n_of(origins, dirs):
+    """Number of rays of an (n, 3) origins / directions pair (numpy arrays or torch tensors), checked before any device work."""
+    for name, a in (("origins", origins), ("dirs", dirs)):
+        if a is None:
+            raise ValueError("%s is required" % name)
+        if len(a.shape) != 2 or a.shape[1] != 3:
+            raise ValueError("%s must have shape (n, 3), got %s" % (name, tuple(a.shape)))
+    if origins.shape[0] != dirs.shape[0]:
+        raise ValueError("origins and dirs hold %d and %d rays" % (origins.shape[0], dirs.shape[0]))
+    n = int(origins.shape[0])
+    if n >= 1 << 32:
+        raise ValueError("at most 2^32 - 1 rays per call")
+    return n
+
+
+def _check_vec(name, a, n):
+    if a is not None and (len(a.shape) != 1 or a.shape[0] != n):
+        raise ValueError("%s must have shape (%d,), got %s" % (name, n, tuple(a.shape)))
+
+
+def _np_floats(name, a, dtype):
+    a = np.asarray(a)
+    if not np.issubdtype(a.dtype, np.floating):
+        raise ValueError("%s must be floating point, got %s" % (name, a.dtype))
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _np_keys(keys):
+    k = np.asarray(keys)
+    if not np.issubdtype(k.dtype, np.integer):
+        raise ValueError("keys must be integers, got %s" % k.dtype)
+    return np.ascontiguousarray(k.astype(np.uint64, copy=False))
+
+
+def _torch_args(named, device):
+    """Checks dtypes and the device of torch arguments: (name, tensor or None, allowed dtypes) -> contiguous tensors."""
+    out = []
+    for name, t, dtypes in named:
+        if t is None:
+            out.append(None)
+            continue
+        if not _is_tensor(t):
+            raise ValueError("%s: torch tensors and numpy arrays cannot be mixed in one call" % name)
+        if t.dtype not in dtypes:
+            raise ValueError("%s must be %s, got %s" % (name, " or ".join(str(d) for d in dtypes), t.dtype))
+        if t.device != device:
+            raise ValueError("%s is on %s, origins on %s" % (name, t.device, device))
+        out.append(t.contiguous())
+    return out
+
+
+def trace_rays(scene, origins, dirs, refr=None, energy=None, keys=None, max_depth=0):
+    """Scene::trace (src/scene.rs:163-193) on n caller-supplied rays: the colour of each, with the reflection / refraction recursion
+    and the lights of a render.  `origins`, `dirs`: (n, 3); `refr` (n,) refraction index of the medium the ray is in (default 1.0),
+    `energy` (n,) (default 1.0), `keys` (n,) RNG path keys for area-light sampling (default: ray i has key i); directions are used as
+    given (unit length expected).  `max_depth` as in render().
+    numpy arrays -> nrays_trace_rays (blocking), (n, 3) float32 numpy array.  torch tensors on the scene's GPU (float64, energy float32,
+    keys int64 / uint64) -> nrays_trace_rays_device on torch.cuda.current_stream(), (n, 3) float32 tensor."""
+    n = _n_of(origins, dirs)
+    for name, a in (("refr", refr), ("energy", energy), ("keys", keys)):
+        _check_vec(name, a, n)
+    if int(max_depth) < 0 or int(max_depth) >= 1 << 32:
+        raise ValueError("max_depth must be in [0, 2^32)")
+    lib = abi.load_hip_lib()
+    if _is_tensor(origins):
+        import torch
+        if origins.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, origins is on %s" % origins.device)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        o, d, r, e, k = _torch_args((("origins", origins, (torch.float64,)), ("dirs", dirs, (torch.float64,)), ("refr", refr, (torch.float64,)),
+                                     ("energy", energy, (torch.float32,)), ("keys", keys, keys_dt)), origins.device)
+        out = torch.empty((n, 3), dtype=torch.float32, device=origins.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(origins.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            abi.check(lib.nrays_trace_rays_device(scene.device_handle(), n, ptr(o), ptr(d), ptr(r), ptr(e), ptr(k), int(max_depth), ptr(out), stream))
+        return out
+    if any(_is_tensor(a) for a in (dirs, refr, energy, keys)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    o, d = _np_floats("origins", origins, np.float64), _np_floats("dirs", dirs, np.float64)
+    r = None if refr is None else _np_floats("refr", refr, np.float64)
+    e = None if energy is None else _np_floats("energy", energy, np.float32)
+    k = None if keys is None else _np_keys(keys)
+    out = np.empty((n, 3), dtype=np.float32)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    abi.check(lib.nrays_trace_rays(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(r, C.c_double), ptr(e, C.c_float),
+                                   ptr(k, C.c_uint64), int(max_depth), ptr(out, C.c_float)))
+    return out
+
+
+def intersects_rays(scene, origins, dirs, max_toi):
+    """Scene::intersects_ray (src/scene.rs:147-161) on n caller-supplied rays, through nrays_intersects_rays_device: returns
+    (lit mask, (n, 3) float32 colour filters) — lit where the reference returns Some(filter); the filter is (0, 0, 0) elsewhere.
+    numpy arrays in -> numpy out (blocking); torch tensors on the GPU (float64) -> tensors (bool, float32) on torch.cuda.current_stream()."""
+    n = _n_of(origins, dirs)
+    _check_vec("max_toi", max_toi, n)
+    lib = abi.load_hip_lib()
+    import torch
+    if _is_tensor(origins):
+        if origins.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, origins is on %s" % origins.device)
+        o, d, t = _torch_args((("origins", origins, (torch.float64,)), ("dirs", dirs, (torch.float64,)), ("max_toi", max_toi, (torch.float64,))), origins.device)
+        device, host = origins.device, False
+    else:
+        if any(_is_tensor(a) for a in (dirs, max_toi)):
+            raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+        on = _np_floats("origins", origins, np.float64)
+        dn, tn = _np_floats("dirs", dirs, np.float64), _np_floats("max_toi", max_toi, np.float64)
+        device, host = torch.device("cuda", torch.cuda.current_device()), True
+        o, d, t = (torch.from_numpy(a).to(device) for a in (on, dn, tn))
+    filt = torch.empty((n, 3), dtype=torch.float32, device=device)
+    lit = torch.empty((n,), dtype=torch.int32, device=device)
+    with torch.cuda.device(device):
+        stream = torch.cuda.current_stream().cuda_stream
+        abi.check(lib.nrays_intersects_rays_device(scene.device_handle(), n, o.data_ptr(), d.data_ptr(), t.data_ptr(), filt.data_ptr(), lit.data_ptr(), stream))
+    if host:
+        return lit.cpu().numpy() != 0, filt.cpu().numpy()
+    return lit != 0, filt
+
+
+_U64 = (1 << 64) - 1
+
+
+def _rng_mix(z):
+    z = z ^ (z >> np.uint64(30))
+    z = z * np.uint64(0xbf58476d1ce4e5b9)
+    z = z ^ (z >> np.uint64(27))
+    z = z * np.uint64(0x94d049bb133111eb)
+    return z ^ (z >> np.uint64(31))
+
+
+def _rng_hash(key, salt):
+    """The library's counter-based RNG on uint64 arrays: mix((key ^ salt * golden) + c), wrapping.  `salt`: an int or a uint64 array."""
+    with np.errstate(over="ignore"):
+        if isinstance(salt, np.ndarray):
+            s = salt.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        else:
+            s = np.uint64((int(salt) * 0x9E3779B97F4A7C15) & _U64)
+        return _rng_mix((np.asarray(key, dtype=np.uint64) ^ s) + np.uint64(0xD1B54A32D192ED03))
+
+
+def camera_rays(resolution, camera_eye, projection, ray_per_pixel=1, window_width=0.0, seed=0):
+    """The rays scene::render traces (src/scene.rs:67-89), for trace_rays: returns (origins (n, 3) float64, dirs (n, 3) float64,
+    keys (n,) uint64) with n = width * height * ray_per_pixel, pixel-major (pixel i + j * width) with the samples innermost.
+    Same f64 operations in the same order as a render: jitter (window_width), NDC, unprojection by the column-major inverse
+    projection-view matrix, v / sqrt(x^2 + y^2 + z^2); key = hash(hash(hash(seed, pixel), sample), path salt).  Averaging the traced
+    colours of a pixel's samples in order (f32 sum, then / ray_per_pixel) gives render()'s pixel."""
+    from .math3d import column_major16
+    w, h, spp = int(resolution[0]), int(resolution[1]), int(ray_per_pixel)
+    if w <= 0 or h <= 0 or spp <= 0:
+        raise ValueError("empty resolution or ray_per_pixel <= 0")
+    M = [float(x) for x in column_major16(projection)]
+    eye0 = [float(x) for x in camera_eye]
+    pix = np.repeat(np.arange(w * h, dtype=np.uint64), spp)
+    s = np.tile(np.arange(spp, dtype=np.uint64), w * h)
+    i = (pix % np.uint64(w)).astype(np.float64)
+    j = (pix // np.uint64(w)).astype(np.float64)
+    pkey = _rng_hash(np.full(pix.shape, int(seed) & _U64, dtype=np.uint64), pix)
+    skey = _rng_hash(pkey, s)
+    ox, oy = i, j
+    if float(window_width) != 0.0:  # scene.rs:74-76
+        u0 = (_rng_hash(skey, 0x1000) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        u1 = (_rng_hash(skey, 0x1001) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        ox = ox + (u0 - 0.5) * float(window_width)
+        oy = oy + (u1 - 0.5) * float(window_width)
+    dx = (ox / float(w) - 0.5) * 2.0
+    dy = -(oy / float(h) - 0.5) * 2.0
+    hv = [M[r] * dx + M[4 + r] * dy + M[8 + r] * -1.0 + M[12 + r] * 1.0 for r in range(4)]
+    v = [hv[a] / hv[3] - eye0[a] for a in range(3)]
+    nrm = np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    dirs = np.stack([v[0] / nrm, v[1] / nrm, v[2] / nrm], axis=1)
+    origins = np.empty_like(dirs)
+    origins[:] = eye0
+    keys = _rng_hash(skey, 2)  # RNG_SALT_PATH
+    return origins, dirs, keys
