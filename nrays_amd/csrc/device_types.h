@@ -165,6 +165,20 @@ struct RayQueue {
     unsigned long long* key; // RNG path key
 };
 
+// A TLAS leaf of a kFeatTinyScene kernel, as the stackless queries read it (trace_device.h: tiny_closest, tiny_shadow): wave-uniform
+// scalar loads of a ball's whole test and of the node's reference AABB gate; other shapes go through their Instance.
+struct TinyLeaf {
+    uint32_t kind;     // NraysShapeKind
+    uint32_t flags;    // InstanceFlags
+    int32_t node_id;   // scene node (the closest-hit tie-break)
+    uint32_t inst;     // index into the TLAS's instance array
+    double radius;     // balls: Instance::params[0]
+    double center[3];  // balls: Instance::trans
+    double aabb[6];    // DScene::node_aabbs of node_id (planes: unused)
+};
+static_assert(sizeof(TinyLeaf) == 96, "TinyLeaf layout");
+constexpr uint32_t kTinyLeaves = 8; // most TLAS leaves a kFeatTinyScene scene may have
+
 struct DScene {
     const BvhNode* nodes;     // all BVH nodes (both TLASes and every BLAS)
     const TriRec* tris;       // leaf-ordered triangles of every BLAS
@@ -197,6 +211,10 @@ struct DScene {
     const uint32_t* lds_blob;
     uint32_t lds_bytes; // multiple of 16
     uint32_t lds_off[10];
+    // kFeatTinyScene kernels: one TinyLeaf per TLAS leaf (planes included), the closest-hit TLAS's leaves first, then the
+    // shadow TLAS's; null when the scene does not qualify (nrays_scene_create)
+    const TinyLeaf* tiny;
+    uint32_t tiny_n, tiny_shadow_n;
 };
 enum LdsSection { kLdsNodes = 0, kLdsInstances, kLdsShadowInstances, kLdsLinks, kLdsShadowLinks, kLdsShade, kLdsNodeAabbs, kLdsLights, kLdsPlanes, kLdsShadowPlanes };
 constexpr uint32_t kLdsSceneBytes = 8192;
@@ -267,9 +285,11 @@ enum Features : int {
     kFeatNoXform = 64,     // every TLAS leaf is an untransformed BLAS (identity rotation, zero translation: local space == world space):
                            // the traversal keeps ONE ray instead of a world and a local one — 12 VGPRs and the two ray set-ups per BLAS
                            // visit (the three-wave multi-light kernel: 170 -> 123 spilled dwords, config 4 12.5 -> 11.3 ms)
-    kFeatPark = 128        // the three-wave multi-light permutations park a hit's shading state (normal, point, ray direction: 18 dwords
+    kFeatPark = 128,       // the three-wave multi-light permutations park a hit's shading state (normal, point, ray direction: 18 dwords
                            // per lane) in LDS across each of its shadow traversals, so that it does not sit in — or get spilled around —
                            // the traversal's inner loops (Stack::park; trace_device.h: material_compute)
+    kFeatTinyScene = 256   // opaque analytic-only scenes of at most kTinyLeaves TLAS leaves: the closest-hit and shadow queries test every leaf
+                           // (DScene::tiny) instead of walking the TLAS (trace_device.h: tiny_closest, tiny_shadow)
 };
 
 } // namespace nrays

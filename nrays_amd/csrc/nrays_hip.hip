@@ -535,14 +535,14 @@ static bool primary_permutation_exists(int feat) { // (of the full build; a tuni
 #undef X
     return false;
 }
-static void launch_primary(bool instrumented, int features, bool noxform, bool park, int occ, uint32_t grid, hipStream_t stream, const DScene& d, const DRender& R,
+static void launch_primary(bool instrumented, int features, bool noxform, bool park, bool tiny, int occ, uint32_t grid, hipStream_t stream, const DScene& d, const DRender& R,
                            const QueueOut& qo, float* out, DeviceCounters* ctr, uint32_t* spill, uint32_t tx, uint32_t ty, uint32_t* work, uint32_t grab,
                            uint32_t* zero_counts, DeviceCounters* zero_ctr) {
     const PrimaryLaunch a{grid, stream, &d, &R, &qo, out, ctr, spill, tx, ty, work, grab, zero_counts, zero_ctr};
     auto launch = [&](bool stats, int feat, bool plain_, int occ_) {
         return launch_primary_group0(a, stats, feat, plain_, occ_) || launch_primary_group1(a, stats, feat, plain_, occ_) || launch_primary_group2(a, stats, feat, plain_, occ_) ||
                launch_primary_group3(a, stats, feat, plain_, occ_) || launch_primary_group4(a, stats, feat, plain_, occ_) || launch_primary_group5(a, stats, feat, plain_, occ_) ||
-               launch_primary_group6(a, stats, feat, plain_, occ_);
+               launch_primary_group6(a, stats, feat, plain_, occ_) || launch_primary_group7(a, stats, feat, plain_, occ_);
     };
     if (instrumented) { launch(true, kFeatAll, false, 0); return; }
     // plain frames: no RNG keys, one sample per pixel
@@ -553,6 +553,8 @@ static void launch_primary(bool instrumented, int features, bool noxform, bool p
         else if (features == 7 || features == 23) { if (launch(false, features, false, 3)) return; }
     }
     if (noxform && mesh_only && launch(false, features + (int)kFeatNoXform, plain, 0)) return;
+    if (tiny && plain && launch(false, features | (int)kFeatTinyScene, true, 0)) return; // (a tuning build without them: the permutations below)
+    if (tiny && launch(false, features | (int)kFeatTinyScene, false, 0)) return;
     if (plain && launch(false, features, true, 0)) return;
     if (launch(false, features, false, 0)) return;
     launch(false, kFeatAll, false, 0); // bit 8 (double branching) only in the full kernels
@@ -892,7 +894,7 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
             dsc.stats_elide = 1u | (((f & kFeatMesh) && (f & kFeatAlphaShadow)) ? 2u : 0u);
         }
         // (a scene with a non-finite light / colour / texel: every frame by the kernel that skips nothing)
-        launch_primary(instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, occ, grid_primary, stream, dsc, R, qo, d_out, sc->d_counters, sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr);
+        launch_primary(instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, stream, dsc, R, qo, d_out, sc->d_counters, sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr);
         HIP_TRY(hipGetLastError());
         if (first_primary) ht("k_primary launch");
         if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[1], stream));
@@ -1250,6 +1252,32 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
             sc->d.lds_bytes = (uint32_t)blob.size();
             sc->features |= kFeatLdsScene;
         }
+      }
+    }
+    // opaque analytic scenes of at most kTinyLeaves TLAS leaves (planes included) with their records in LDS: one TinyLeaf per leaf of each TLAS for the
+    // stackless queries of the kFeatTinyScene kernels (trace_device.h: tiny_closest, tiny_shadow).  Pixels do not depend on it (NRAYS_TINY_SCENE=0: the TLAS walk, A/B)
+    sc->d.tiny = nullptr; sc->d.tiny_n = sc->d.tiny_shadow_n = 0u;
+    { const char* e = getenv("NRAYS_TINY_SCENE");
+      const int f = sc->features;
+      if ((f == (kFeatAnalytic | kFeatLdsScene) || f == (kFeatAnalytic | kFeatMultiSample | kFeatLdsScene)) && !h.instances.empty() &&
+          h.instances.size() <= kTinyLeaves && h.shadow_instances.size() <= kTinyLeaves && !(e && atoi(e) == 0)) {
+        std::vector<TinyLeaf> leaves;
+        auto add = [&](const std::vector<Instance>& insts) {
+            for (size_t k = 0; k < insts.size(); ++k) {
+                const Instance& in = insts[k];
+                TinyLeaf lf{};
+                lf.kind = in.kind; lf.flags = in.flags; lf.node_id = in.node_id; lf.inst = (uint32_t)k;
+                lf.radius = in.params[0];
+                for (int a = 0; a < 3; ++a) lf.center[a] = in.trans[a];
+                if (in.node_id >= 0 && 6 * (size_t)in.node_id + 6 <= h.node_aabbs.size())
+                    for (int a = 0; a < 6; ++a) lf.aabb[a] = h.node_aabbs[6 * (size_t)in.node_id + a];
+                leaves.push_back(lf);
+            }
+        };
+        add(h.instances); add(h.shadow_instances);
+        if ((rc = upload(sc, leaves, &sc->d.tiny)) != NRAYS_OK) return bail(rc);
+        sc->d.tiny_n = (uint32_t)h.instances.size(); sc->d.tiny_shadow_n = (uint32_t)h.shadow_instances.size();
+        sc->tiny = true;
       }
     }
     {   // k_seed_costs: world AABBs of the nodes that can continue a chain (transparent / alpha-mapped / reflective), as f32

@@ -3,7 +3,7 @@
 #include "primary_kernel.h"
 
 #ifndef NR_PRIMARY_GROUP
-#error "compile with -DNR_PRIMARY_GROUP=<0..6>"
+#error "compile with -DNR_PRIMARY_GROUP=<0..7>"
 #endif
 
 namespace nrays {

@@ -498,8 +498,10 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
     X(5, false, 7, false, 3) X(5, false, 23, false, 3)                                                                       \
     /* group 6: ... of the untransformed ones */                                                                             \
     X(6, false, 198, true, 3) X(6, false, 198, false, 3) X(6, false, 70, true, 3) X(6, false, 70, false, 3)                   \
-    X(6, false, 214, true, 3) X(6, false, 214, false, 3) X(6, false, 86, true, 3) X(6, false, 86, false, 3)
-constexpr int kPrimaryGroups = 7;
+    X(6, false, 214, true, 3) X(6, false, 214, false, 3) X(6, false, 86, true, 3) X(6, false, 86, false, 3)                   \
+    /* group 7: opaque analytic scenes of at most kTinyLeaves leaves, records in LDS (256 = kFeatTinyScene: stackless queries) */ \
+    X(7, false, 289, true, 0) X(7, false, 305, true, 0) X(7, false, 289, false, 0) X(7, false, 305, false, 0)
+constexpr int kPrimaryGroups = 8;
 
 namespace nrays {
 
@@ -515,5 +517,6 @@ bool launch_primary_group3(const PrimaryLaunch& a, bool stats, int feat, bool pl
 bool launch_primary_group4(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ);
 bool launch_primary_group5(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ);
 bool launch_primary_group6(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ);
+bool launch_primary_group7(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ);
 
 } // namespace nrays

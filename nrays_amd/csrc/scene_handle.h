@@ -100,6 +100,7 @@ struct NraysScene {
     int features = nrays::kFeatAll;
     bool park = true;     // kFeatPark permutations for the three-wave multi-light kernels (NRAYS_PARK=0: off)
     bool noxform = false; // every BLAS untransformed: the kFeatNoXform permutations of the mesh kernels render this scene
+    bool tiny = false;    // opaque analytic scene of at most kTinyLeaves TLAS leaves: the kFeatTinyScene permutations render it (NRAYS_TINY_SCENE=0: off)
     float* d_frame = nullptr; size_t frame_floats = 0;
     uint8_t* d_rgb8 = nullptr; size_t rgb8_bytes = 0; // nrays_render_rgb8
     hipStream_t own_stream = nullptr;
