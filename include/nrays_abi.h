@@ -30,8 +30,8 @@ extern "C" {
 #endif
 
 /* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6); 6 = nrays_trace_rays_device / nrays_trace_rays /
- * nrays_intersects_rays_device (caller-supplied rays). */
-#define NRAYS_ABI_VERSION 6
+ * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation. */
+#define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
     NRAYS_OK = 0,
@@ -324,10 +324,19 @@ int nrays_debug_cast_batch(NraysScene* scene, uint32_t mode, uint32_t n, const d
  * a node whose AABB the ray passes, src/scene.rs:276).  out = {min x, y, z, max x, y, z}. */
 int nrays_debug_node_aabb(NraysScene* scene, uint32_t node, double out[6]);
 
-/* How the library classified the scene (test probe): out[0] = kernel permutation it renders with (1 analytic shapes, 2 meshes,
- * 4 some node may be non-opaque to shadow rays, 16 more than one light sample per hit), out[1] = 1 when a hair-like mesh makes the
- * BVT queries end their node phases by quorum (NRAYS_NODE_QUORUM=0 in the environment of nrays_scene_create turns that off). */
+/* How the library classified the scene's content (test probe): out[0] = the feature bits of the descriptor (1 analytic shapes, 2 meshes,
+ * 4 some node may be non-opaque to shadow rays, 16 more than one light sample per hit; 15 / 31 when a node can both reflect and refract),
+ * out[1] = 1 when a hair-like mesh makes the BVT queries end their node phases by quorum (NRAYS_NODE_QUORUM=0 in the environment of
+ * nrays_scene_create turns that off).  out[0] is NOT the kernel a frame runs: the handle's switches, the frame's kind and its size choose
+ * that per render — nrays_debug_last_permutation reports it. */
 int nrays_debug_scene_flags(const NraysScene* scene, uint32_t out[2]);
+
+/* The k_primary permutation the most recent render of this handle actually launched (test probe; host bookkeeping only, no device work):
+ * out[0..3] = STATS, FEAT, PLAIN, OCC of its last k_primary launch — the template arguments listed in NR_PRIMARY_PERMUTATIONS of
+ * nrays_amd/csrc/primary_kernel.h, after every fall-back to a more general kernel; out[4] = the number of k_primary launches of that
+ * render (sample batches; 0 = no render yet, or the staged path rendered the frame: out[0..3] are then 0); out[5] = 1 when those
+ * launches did not all run the same permutation (of a batched frame only the first batch can be a plain one). */
+int nrays_debug_last_permutation(const NraysScene* scene, uint32_t out[6]);
 
 /* Test probe of `Scene::new`'s BVT construction for one TriMesh (src/scene.rs:119-133; ncollide's BVT::new_balanced inside TriMesh::new,
  * examples/loader3d.rs:695): builds the BLAS of `mesh` with the host builder (flags bit 0 clear) or the device builder (bit 0 set;

@@ -6,7 +6,7 @@ and types must match include/nrays_abi.h exactly (tests/test_abi.py checks sizes
 import ctypes as C
 import os
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 COUNT_AS_TIMED = 1  # nrays_render_device_counted: count the work of the plain (timed) render, include/nrays_abi.h
 
 # NraysStatus
@@ -118,6 +118,7 @@ HIP_SYMBOLS = {
     "nrays_debug_blas_build": (C.c_int, [C.POINTER(NraysMesh), C.c_uint32, C.POINTER(NraysBlasDump)]),
     "nrays_debug_node_aabb": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
     "nrays_debug_scene_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "nrays_debug_last_permutation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "nrays_get_tile_costs": (C.c_int, [C.c_void_p, C.POINTER(NraysTileCosts)]),
     "nrays_debug_cast_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(NraysCastResult)]),

@@ -535,14 +535,22 @@ static bool primary_permutation_exists(int feat) { // (of the full build; a tuni
 #undef X
     return false;
 }
-static void launch_primary(bool instrumented, int features, bool noxform, bool park, bool tiny, int occ, uint32_t grid, hipStream_t stream, const DScene& d, const DRender& R,
+static void launch_primary(NraysScene* sc, bool instrumented, int features, bool noxform, bool park, bool tiny, int occ, uint32_t grid, hipStream_t stream, const DScene& d, const DRender& R,
                            const QueueOut& qo, float* out, DeviceCounters* ctr, uint32_t* spill, uint32_t tx, uint32_t ty, uint32_t* work, uint32_t grab,
                            uint32_t* zero_counts, DeviceCounters* zero_ctr) {
     const PrimaryLaunch a{grid, stream, &d, &R, &qo, out, ctr, spill, tx, ty, work, grab, zero_counts, zero_ctr};
     auto launch = [&](bool stats, int feat, bool plain_, int occ_) {
-        return launch_primary_group0(a, stats, feat, plain_, occ_) || launch_primary_group1(a, stats, feat, plain_, occ_) || launch_primary_group2(a, stats, feat, plain_, occ_) ||
+        const bool launched =
+               launch_primary_group0(a, stats, feat, plain_, occ_) || launch_primary_group1(a, stats, feat, plain_, occ_) || launch_primary_group2(a, stats, feat, plain_, occ_) ||
                launch_primary_group3(a, stats, feat, plain_, occ_) || launch_primary_group4(a, stats, feat, plain_, occ_) || launch_primary_group5(a, stats, feat, plain_, occ_) ||
                launch_primary_group6(a, stats, feat, plain_, occ_) || launch_primary_group7(a, stats, feat, plain_, occ_);
+        if (launched) { // what nrays_debug_last_permutation reports: the permutation that ran, not the one the frame asked for first
+            const uint32_t t[4] = {stats ? 1u : 0u, (uint32_t)feat, plain_ ? 1u : 0u, (uint32_t)occ_};
+            if (sc->perm_launches && std::memcmp(t, sc->perm_last, sizeof t) != 0) sc->perm_mixed = true;
+            std::memcpy(sc->perm_last, t, sizeof t);
+            sc->perm_launches++;
+        }
+        return launched;
     };
     if (instrumented) { launch(true, kFeatAll, false, 0); return; }
     // plain frames: no RNG keys, one sample per pixel
@@ -587,6 +595,7 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     if (p->width == 0 || p->height == 0) return fail(NRAYS_ERR_BAD_ARG, "empty resolution");
     if (p->band_owners > 1 && (p->band_rows == 0 || p->band_owner >= p->band_owners)) return fail(NRAYS_ERR_BAD_ARG, "bad band parameters");
     HIP_TRY(hipSetDevice(sc->device));
+    sc->perm_launches = 0; sc->perm_mixed = false; // (nrays_debug_last_permutation speaks of this render from here on)
 
     ht("hipSetDevice");
     const uint32_t rows = tile_rows(p);
@@ -894,7 +903,7 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
             dsc.stats_elide = 1u | (((f & kFeatMesh) && (f & kFeatAlphaShadow)) ? 2u : 0u);
         }
         // (a scene with a non-finite light / colour / texel: every frame by the kernel that skips nothing)
-        launch_primary(instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, stream, dsc, R, qo, d_out, sc->d_counters, sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr);
+        launch_primary(sc, instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, stream, dsc, R, qo, d_out, sc->d_counters, sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr);
         HIP_TRY(hipGetLastError());
         if (first_primary) ht("k_primary launch");
         if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[1], stream));
@@ -1614,6 +1623,13 @@ int nrays_render_rgb8(NraysScene* sc, const NraysRenderParams* p, uint8_t* out_r
 int nrays_debug_scene_flags(const NraysScene* sc, uint32_t out[2]) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     out[0] = (uint32_t)sc->host.features; out[1] = sc->d.incoherent;
+    return NRAYS_OK;
+}
+
+int nrays_debug_last_permutation(const NraysScene* sc, uint32_t out[6]) {
+    if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    for (int a = 0; a < 4; ++a) out[a] = sc->perm_launches ? sc->perm_last[a] : 0u;
+    out[4] = sc->perm_launches; out[5] = sc->perm_mixed ? 1u : 0u;
     return NRAYS_OK;
 }
 

@@ -142,5 +142,9 @@ struct NraysScene {
     NraysStats last;
     uint64_t last_primary = 0, last_primary_first_batch = 0;
     bool last_instrumented = false;
+    // nrays_debug_last_permutation: the k_primary permutation(s) the most recent render launched (host bookkeeping of launch_primary(), no device work)
+    uint32_t perm_last[4] = {0, 0, 0, 0}; // STATS, FEAT, PLAIN, OCC of the last launch
+    uint32_t perm_launches = 0;           // k_primary launches of that render (0: none yet, or the staged path rendered it)
+    bool perm_mixed = false;              // its launches did not all run the same permutation (sample batches: only the first can be plain)
 };
 

@@ -443,6 +443,14 @@ def get_stats(scene):
     return st
 
 
+def last_permutation(scene):
+    """Test probe (nrays_debug_last_permutation): the k_primary permutation the handle's most recent render launched, as
+    ((stats, feat, plain, occ), launches, mixed) — the template arguments of csrc/primary_kernel.h: NR_PRIMARY_PERMUTATIONS."""
+    out = (C.c_uint32 * 6)()
+    abi.check(abi.load_hip_lib().nrays_debug_last_permutation(scene.device_handle(), out))
+    return (bool(out[0]), int(out[1]), bool(out[2]), int(out[3])), int(out[4]), bool(out[5])
+
+
 # ---- caller-supplied rays: Scene::trace / Scene::intersects_ray (src/scene.rs:147-193) in batches ----------------------------------------
 
 def _is_tensor(x):

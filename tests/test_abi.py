@@ -72,6 +72,9 @@ def test_null_arguments_are_errors_not_crashes(built):
     assert lib.nrays_scene_create(None, None) == abi.ERR_BAD_ARG
     assert lib.nrays_render(None, None, None) == abi.ERR_BAD_ARG
     assert b"null" in lib.nrays_last_error()
+    assert lib.nrays_debug_scene_flags(None, None) == abi.ERR_BAD_ARG
+    assert lib.nrays_debug_last_permutation(None, None) == abi.ERR_BAD_ARG
+    assert lib.nrays_debug_last_permutation(None, (C.c_uint32 * 6)()) == abi.ERR_BAD_ARG
     lib.nrays_scene_destroy(None)
 
 

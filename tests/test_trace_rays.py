@@ -71,10 +71,10 @@ def shim(tmp_path_factory):
     return build_shim(tmp_path_factory.mktemp("trace_shim"))
 
 
-def test_abi_version_6(built):
-    assert abi.ABI_VERSION == 6
-    assert "#define NRAYS_ABI_VERSION 6" in open(os.path.join(ROOT, "include", "nrays_abi.h")).read()
-    assert abi.load_hip_lib().nrays_abi_version() == 6
+def test_abi_version_7(built):
+    assert abi.ABI_VERSION == 7
+    assert "#define NRAYS_ABI_VERSION 7" in open(os.path.join(ROOT, "include", "nrays_abi.h")).read()
+    assert abi.load_hip_lib().nrays_abi_version() == 7
 
 
 def test_new_symbols_are_exported_with_signatures(built):

@@ -156,8 +156,10 @@ def main():
             worst = max(worst, err)
             ok = err <= 1e-4 and same
             bad += 0 if ok else 1
-            print("seed %d frame %d %dx%d spp %d nodes %d lights %d rays %d: max err %.3g counts %s %s" % (
-                seed, rep, w, h, spp, len(sc._nodes), len(sc._lights), st.total_rays(), err, "equal" if same else "DIFFER", "" if ok else "<-- MISMATCH"), flush=True)
+            perm, launches, mixed = nr.last_permutation(sc)  # (stats, feat, plain, occ) of the k_primary that rendered this frame
+            print("seed %d frame %d %dx%d spp %d nodes %d lights %d flags %d/%d k_primary<%d, %d, %d, %d>%s rays %d: max err %.3g counts %s %s" % (
+                seed, rep, w, h, spp, len(sc._nodes), len(sc._lights), flags[0], flags[1], perm[0], perm[1], perm[2], perm[3],
+                " x%d%s" % (launches, " mixed" if mixed else "") if launches != 1 else "", st.total_rays(), err, "equal" if same else "DIFFER", "" if ok else "<-- MISMATCH"), flush=True)
     print("worst error %.3g over %d cases, %d mismatches; %d scenes rendered with quorum-ended node phases" % (worst, 2 * count, bad, quorum_scenes))
     return 1 if bad else 0
 
