@@ -266,6 +266,9 @@ struct DRender {
     // XCD x's list (k_tile_order expands the tiles above its cost threshold).  Scheduling only: pixels do not depend on it.
     const uint32_t* order_len;
     uint32_t light_lsl;
+    // 1: this launch writes the window's pixels only — the rows and columns outside the window are somebody else's (the trace half of a
+    // pipelined frame, nrays_hip.hip: render_impl; k_compose writes them).  k_primary only.
+    uint32_t no_rows;
 };
 constexpr uint32_t kEntrySplit = 0x80000000u, kEntryTileMask = 0x0fffffffu;
 // A recorded tile cost (DRender::tile_cost, 16-cycle units): bit 31 = the tile ran as light-parallel / pixel-split parts and the value is its most expensive part's, scaled to the tile.

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <climits>
 #include <cmath>
@@ -422,6 +423,39 @@ __global__ void k_resolve(float* out, size_t n, float spp) { // pxs.push(tot_c /
     if (i < n) out[i] = out[i] / spp;
 }
 
+// The second half of a pipelined frame (render_impl): every float of `out`, one workgroup per row — the window of blocks that can see the
+// scene copied from the staging frame `win` the trace wrote (addressed like `out`), the background sums of fill_background_row_body
+// everywhere else.  Frames without bands only (row = global row, no padding rows).  It runs beside the next frame's persistent trace
+// grid: no LDS, a few registers, streaming 16-byte accesses.  [wi0, wi1) x [wr0, wr1): the window in pixels.
+__global__ void __launch_bounds__(256) k_compose(float* __restrict__ out, const float* __restrict__ win, uint32_t width, uint32_t spp, float bg0, float bg1, float bg2,
+                                                 uint32_t wi0, uint32_t wi1, uint32_t wr0, uint32_t wr1) {
+    const uint32_t rl = blockIdx.x;
+    float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
+    for (uint32_t s = 0; s < spp; ++s) { b0 = b0 + bg0; b1 = b1 + bg1; b2 = b2 + bg2; }
+    const bool split = rl >= wr0 && rl < wr1 && wi1 > wi0; // this row crosses the window
+    const uint32_t f_lo = 3u * wi0, f_hi = 3u * wi1;       // floats [f_lo, f_hi) of such a row belong to the window
+    __attribute__((address_space(1))) float* row = (__attribute__((address_space(1))) float*)(out + (size_t)rl * width * 3);
+    const __attribute__((address_space(1))) float* src = (const __attribute__((address_space(1))) float*)(win + (size_t)rl * width * 3);
+    if (((width * 3u) & 3u) == 0u && (((uintptr_t)out) & 15u) == 0u && (((uintptr_t)win) & 15u) == 0u) {
+        typedef float f4v __attribute__((ext_vector_type(4)));
+        const uint32_t nq = width * 3u / 4u;
+        for (uint32_t q = threadIdx.x; q < nq; q += 256u) { // chunk q holds the floats 4q .. 4q + 3: the channels (q mod 3), (q + 1) mod 3, ...
+            const uint32_t f = 4u * q, ph = q % 3u;
+            f4v v = ph == 0u ? f4v{b0, b1, b2, b0} : (ph == 1u ? f4v{b1, b2, b0, b1} : f4v{b2, b0, b1, b2});
+            if (split && f + 4u > f_lo && f < f_hi) {
+                const f4v w = __builtin_nontemporal_load((const __attribute__((address_space(1))) f4v*)(src + f));
+                for (uint32_t k = 0; k < 4u; ++k) if (f + k >= f_lo && f + k < f_hi) v[k] = w[k]; // (a chunk across the window's edge keeps the background outside)
+            }
+            __builtin_nontemporal_store(v, (__attribute__((address_space(1))) f4v*)(row + f));
+        }
+        return;
+    }
+    for (uint32_t f = threadIdx.x; f < width * 3u; f += 256u) {
+        const uint32_t i = f / 3u, c = f - i * 3u;
+        row[f] = (split && i >= wi0 && i < wi1) ? src[f] : (c == 0u ? b0 : (c == 1u ? b1 : b2));
+    }
+}
+
 __global__ void k_untile(const float* __restrict__ gathered, float* __restrict__ out, uint32_t width, uint32_t height,
                          uint32_t band_rows, uint32_t owners, uint32_t rows_local) {
     size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -537,8 +571,8 @@ static bool primary_permutation_exists(int feat) { // (of the full build; a tuni
 }
 static void launch_primary(NraysScene* sc, bool instrumented, int features, bool noxform, bool park, bool tiny, int occ, uint32_t grid, hipStream_t stream, const DScene& d, const DRender& R,
                            const QueueOut& qo, float* out, DeviceCounters* ctr, uint32_t* spill, uint32_t tx, uint32_t ty, uint32_t* work, uint32_t grab,
-                           uint32_t* zero_counts, DeviceCounters* zero_ctr) {
-    const PrimaryLaunch a{grid, stream, &d, &R, &qo, out, ctr, spill, tx, ty, work, grab, zero_counts, zero_ctr};
+                           uint32_t* zero_counts, DeviceCounters* zero_ctr, hipEvent_t done = nullptr) {
+    const PrimaryLaunch a{grid, stream, &d, &R, &qo, out, ctr, spill, tx, ty, work, grab, zero_counts, zero_ctr, done};
     auto launch = [&](bool stats, int feat, bool plain_, int occ_) {
         const bool launched =
                launch_primary_group0(a, stats, feat, plain_, occ_) || launch_primary_group1(a, stats, feat, plain_, occ_) || launch_primary_group2(a, stats, feat, plain_, occ_) ||
@@ -584,10 +618,45 @@ static int alloc_cost_stats(NraysScene* sc) {
     return NRAYS_OK;
 }
 
+// Pipelined frames: the two internal streams (non-blocking: the caller's stream may be the legacy null stream, which a blocking stream would
+// serialise with), their events, and a staging frame per slot for frames of up to `floats` floats.  Growing the staging frames drains the handle first.
+static int pipeline_ensure(NraysScene* sc, size_t floats) {
+    for (int k = 0; k < 2; ++k) if (!sc->pipe_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&sc->pipe_stream[k], hipStreamNonBlocking));
+    for (int k = 0; k < NraysScene::kPipeSlots; ++k) {
+        if (!sc->ev_traced[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_traced[k], hipEventDisableTiming));
+        if (!sc->ev_composed[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_composed[k], hipEventDisableTiming));
+    }
+    for (int k = 0; k < 2; ++k) if (sc->spill_entries && !sc->pipe_spill[k]) HIP_TRY(hipMalloc((void**)&sc->pipe_spill[k], (size_t)kMaxGrid * kBlock * sc->spill_entries * sizeof(uint32_t)));
+    if (floats > sc->pipe_floats) {
+        if (sc->have_last) HIP_TRY(hipStreamSynchronize(sc->last_stream)); // every trace in flight has its compose there, or ordered before it
+        for (int k = 0; k < NraysScene::kPipeSlots; ++k) if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
+        sc->pipe_floats = 0;
+        for (int k = 0; k < NraysScene::kPipeSlots; ++k) HIP_TRY(hipMalloc((void**)&sc->pipe_stage[k], floats * sizeof(float)));
+        sc->pipe_floats = floats;
+    }
+    return NRAYS_OK;
+}
+static void pipeline_release(NraysScene* sc) {
+    for (int k = 0; k < 2; ++k) if (sc->pipe_stream[k]) { (void)hipStreamSynchronize(sc->pipe_stream[k]); (void)hipStreamDestroy(sc->pipe_stream[k]); sc->pipe_stream[k] = nullptr; }
+    for (int k = 0; k < 2; ++k) if (sc->pipe_spill[k]) { (void)hipFree(sc->pipe_spill[k]); sc->pipe_spill[k] = nullptr; }
+    for (int k = 0; k < NraysScene::kPipeSlots; ++k) {
+        if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
+        if (sc->ev_traced[k]) { (void)hipEventDestroy(sc->ev_traced[k]); sc->ev_traced[k] = nullptr; }
+        if (sc->ev_composed[k]) { (void)hipEventDestroy(sc->ev_composed[k]); sc->ev_composed[k] = nullptr; }
+    }
+    sc->pipe_floats = 0;
+}
+
+// The handle that rendered last, process-wide: a caller that alternates between handles (two handles, two streams, two frame buffers) already overlaps its frames on the
+// device, and pipelining each handle on top of that oversubscribes the hardware queues (six streams: 0.044 ms per frame against 0.0285 on the direct path,
+// profiles/pipelined_frames_full.log) — such frames stay on the direct path.
+static std::atomic<NraysScene*> g_last_renderer{nullptr};
+
 static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStream_t stream, bool instrumented, uint32_t count_flags = 0u) {
     if (!sc || !p || !d_out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    // NRAYS_HOST_TIMES=1 (read by nrays_scene_create): microseconds of host time this call spends up to a few marks, for the handle's first frames (tools/cold_probe.py)
-    const bool host_times = sc->host_times && sc->frames_total < 4;
+    const bool interleaved = g_last_renderer.exchange(sc, std::memory_order_relaxed) != sc;
+    // NRAYS_HOST_TIMES=n (read by nrays_scene_create): microseconds of host time this call spends up to a few marks, for the handle's frames n .. n + 3 (1: its first frames, tools/cold_probe.py)
+    const bool host_times = sc->host_times_from && sc->frames_total + 1 >= sc->host_times_from && sc->frames_total + 1 < sc->host_times_from + 4;
     const unsigned long long ht_frame = sc->frames_total;
     const auto ht0 = std::chrono::steady_clock::now();
     auto ht = [&](const char* what) { if (host_times) fprintf(stderr, "  render_impl frame %llu: +%.1f us %s\n", ht_frame, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - ht0).count(), what); };
@@ -695,8 +764,9 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
                                                      (uint32_t)sc->num_cus * (uint32_t)(occ ? NR_OCC3_AS : waves_per_simd(instrumented ? kFeatAll : sc->features)) * 256u / (uint32_t)kBlock);
     if (sc->grid_wg_per_cu > 0) grid_primary = std::min<uint32_t>(grid_primary, (uint32_t)sc->num_cus * (uint32_t)sc->grid_wg_per_cu); // NRAYS_GRID_WG_PER_CU: occupancy sensitivity runs
 
-    // All per-handle state (double-buffered counters, queues, raygen tables, tile costs) assumes that the renders of one
-    // handle execute one after the other: a render on a different stream than its predecessor is ordered behind it.
+    // The per-handle state (queues, raygen tables, tile costs) assumes that the renders of one handle execute one after the other — pipelined
+    // frames, below, are the exception and say what they share — and `out` is written in call order: a render on a different stream than its
+    // predecessor is ordered behind it.
     if (sc->have_last && sc->last_stream != stream) {
         if (sc->last_timed && sc->last_done) HIP_TRY(hipStreamWaitEvent(stream, sc->last_done, 0));
         else { // the previous frame recorded no event (event_stride): mark the end of ITS stream now and wait on that — no host stall
@@ -715,9 +785,10 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     // The staged ("wavefront") form of the trace loop (wavefront.hip) renders this frame instead of k_primary when the scene is eligible and
     // NRAYS_WAVEFRONT / the library's rule say so; pixels are identical either way.
     const bool staged = !instrumented && wavefront_wanted(sc, p, lane_log2);
+    bool pipelined = false; // this frame was split into a trace on an internal stream and a compose on the caller's (below)
     const bool single_launch = !staged && !instrumented && !queued && p->ray_per_pixel <= batch && p->ray_per_pixel == 1;
-    sc->d_counters = sc->d_counters_set[sc->frame_index & 1];
-    DeviceCounters* next_ctr = sc->d_counters_set[(sc->frame_index + 1) & 1];
+    sc->d_counters = sc->d_counters_set[sc->frame_index % NraysScene::kCountSets];
+    DeviceCounters* next_ctr = sc->d_counters_set[(sc->frame_index + 2) % NraysScene::kCountSets];
     sc->frame_index++;
     R.use_rng = (p->window_width != 0.0 || sc->host.any_area_light) ? 1u : 0u;
     // mesh scenes: longest-processing-time-first from the previous frame of the same geometry (pixels do not depend on it)
@@ -727,8 +798,8 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     // and far more even; recording, sorting and following the order costs more than the tail it removes: hairball 4K 64 spp
     // 251 -> 222 ms without it, sponza 1080p 4 / 16 / 64 spp 2-4 %, profiles/r02_aa_lpt.log)
     if (staged) {
-        sc->d_counts = sc->d_counts_set[sc->launch_index & 1];
-        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 1) & 1];
+        sc->d_counts = sc->d_counts_set[sc->launch_index % NraysScene::kCountSets];
+        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 2) % NraysScene::kCountSets];
         sc->launch_index++;
         const int rc = wavefront_render(sc, p, R, d_out, stream, tiles_x, tiles_y, timed, slot, next_ctr, next_counts);
         if (rc != NRAYS_OK) return rc;
@@ -882,16 +953,56 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     if (R.tile_cost) { sc->cost_tiles = lane_log2 ? win_units : win_units * 4u; sc->cost_grid = grid_primary; sc->cost_split_lsl = R.light_lsl; }
     R.cost_meta = sc->d_cost_meta; // (read by the instrumented kernel only)
     ht("scheduling state (seed / sort launches)");
+    // ---- pipelined frames ----------------------------------------------------------------------------------------------------------
+    // A frame of an analytic scene that arrives while the handle's previous work is still in flight is split in two.  TRACE: the very
+    // k_primary launch of the direct path, on the internal stream of the launch's parity, storing the window's pixels into the staging
+    // frame of slot `ps` (launch index mod 4) and no background rows; it reads only what the library owns (scene records, the by-value camera, an order no frame in
+    // flight writes), so it is not ordered against the caller's stream and overlaps the tail of the frame before it.  COMPOSE: k_compose on
+    // the caller's stream behind the trace — `out` is written there alone, in call order, as on the direct path.
+    // Ordering of the shared state: launches of the same parity share counter sets (n mod 4 used, (n + 2) mod 4 cleared), staging frames
+    // (n mod 4) and the traversal-stack spill region of their stream (pipe_spill; never the handle's d_spill) and run on the same internal stream (the trace also waits for the compose that read its staging frame four launches ago); every direct frame comes behind all composes on the
+    // caller's stream, and the first pipelined frame after direct work makes BOTH internal streams wait for the end of that work.
+    // Not pipelined: frames that record or sort tile costs, instrumented / multi-sample / queued / banded / staged frames, mesh scenes
+    // (their moving frames sort every time), windows beyond half the frame (the copy would outweigh the rows it takes off the tracing waves).
+    bool pipe = sc->pipeline && single_launch && !sc->d.no_elide && !banded && !sc->host.any_mesh && grab == 0u && lane_log2 == 0u && !R.tile_cost &&
+                !sc->has_prepass[slot] && sc->have_last && win_units > 0u && 2ull * win_units <= (uint64_t)tiles_x * tiles_y;
+#ifdef NR_DEBUG_TILE_COSTS
+    pipe = false;
+#endif
+    if (pipe && !sc->pipeline_always && interleaved) pipe = false; // another handle rendered in between (above)
+    if (pipe && !sc->pipeline_always) { // is the predecessor still in flight?  (a caller that waits for every frame stays on the direct path)
+        const hipError_t q = sc->last_pipelined ? hipEventQuery(sc->last_done) : hipStreamQuery(sc->last_stream);
+        if (q != hipSuccess) (void)hipGetLastError();
+        pipe = q == hipErrorNotReady;
+        ht("pipeline: in-flight query");
+    }
+    if (pipe && pipeline_ensure(sc, (size_t)npix_local * 3) != NRAYS_OK) { // no room for the staging frames: direct from here on, and said so once
+        (void)hipGetLastError(); sc->pipeline = false; pipe = false;
+        fprintf(stderr, "nrays: the staging frames of pipelined frames could not be allocated (%s); this handle renders every frame on the direct path\n", g_last_error.c_str());
+    }
+    const int ps = (int)(sc->launch_index % NraysScene::kPipeSlots);
+    const hipStream_t lstream = pipe ? sc->pipe_stream[ps & 1] : stream;
+    if (pipe) {
+        if (!sc->last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: both internal streams behind its end
+            if (!sc->ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(sc->ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
+            for (int k = 0; k < 2; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe_stream[k], sc->ev_switch, 0));
+        }
+        // the compose that last read this slot's staging frame, four frames ago: when the host can see that it is over (a query costs 0.6 us) the wait (5 us
+        // of host time, which bounds the pipelined frame rate) is not enqueued
+        if (hipEventQuery(sc->ev_composed[ps]) != hipSuccess) { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(lstream, sc->ev_composed[ps], 0)); }
+        ht("pipeline: waits of the trace stream");
+    }
     bool first_primary = true;
     for (uint32_t s0 = 0; s0 < p->ray_per_pixel; s0 += batch) {
         R.sample_begin = s0; R.sample_end = std::min<uint32_t>(p->ray_per_pixel, s0 + batch);
         R.first_batch = s0 == 0 ? 1u : 0u;
-        sc->d_counts = sc->d_counts_set[sc->launch_index & 1];
-        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 1) & 1];
+        sc->d_counts = sc->d_counts_set[sc->launch_index % NraysScene::kCountSets];
+        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 2) % NraysScene::kCountSets];
         sc->launch_index++;
         QueueOut qo; qo.q = sc->queue[1].q; qo.capacity = queued ? sc->queue_capacity : 0; qo.count = sc->d_counts + 1;
         qo.overflow = &sc->d_counters->overflow;
-        if (first_primary && timed) HIP_TRY(hipEventRecord(sc->ev_pbegin[slot], stream));
+        if (first_primary && timed) HIP_TRY(hipEventRecord(sc->ev_pbegin[slot], lstream));
         if (first_primary) ht("event record before the launch");
         // a launch that records its tile costs is timed (nrays_get_tile_costs: NraysTileCosts::kernel_ms): by the ring's events when the frame has them, by a pair of its own otherwise
         const bool rec_events = first_primary && R.tile_cost && !timed && sc->ev_rec[0] && sc->ev_rec[1];
@@ -903,12 +1014,14 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
             dsc.stats_elide = 1u | (((f & kFeatMesh) && (f & kFeatAlphaShadow)) ? 2u : 0u);
         }
         // (a scene with a non-finite light / colour / texel: every frame by the kernel that skips nothing)
-        launch_primary(sc, instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, stream, dsc, R, qo, d_out, sc->d_counters, sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr);
+        R.no_rows = pipe ? 1u : 0u; // a trace launch writes the window only
+        launch_primary(sc, instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, lstream, dsc, R, qo, pipe ? sc->pipe_stage[ps] : d_out, sc->d_counters,
+                       pipe ? sc->pipe_spill[ps & 1] : sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr, pipe ? sc->ev_traced[ps] : nullptr);
         HIP_TRY(hipGetLastError());
         if (first_primary) ht("k_primary launch");
         if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[1], stream));
         if (first_primary) {
-            if (timed) HIP_TRY(hipEventRecord(sc->ev_pend[slot], stream));
+            if (timed) HIP_TRY(hipEventRecord(sc->ev_pend[slot], lstream));
             if (instrumented) HIP_TRY(hipMemcpyAsync(sc->d_counters_primary, sc->d_counters, sizeof(DeviceCounters), hipMemcpyDeviceToDevice, stream));
             first_primary = false;
         }
@@ -940,19 +1053,33 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
             folded = true; sc->fixed_dirty = false;
         }
     }
+    if (pipe) {
+        // (an error from here on leaves a trace in flight that no compose follows: it is drained, and what comes next is ordered as after direct work)
+        auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(lstream); sc->last_pipelined = false; } return e; };
+        HIP_TRY(drained(hipStreamWaitEvent(stream, sc->ev_traced[ps], 0)));
+        ht("pipeline: wait of the caller's stream");
+        const uint32_t wi0 = R.win_x0 << bwl, wi1 = std::min<uint32_t>((R.win_x0 + R.win_nx) << bwl, p->width), wr0 = R.win_y0 << bhl, wr1 = (R.win_y0 + R.win_ny) << bhl;
+        hipExtLaunchKernelGGL(k_compose, dim3(rows), dim3(256), 0, stream, nullptr, sc->ev_composed[ps], 0, d_out, (const float*)sc->pipe_stage[ps], p->width, p->ray_per_pixel, sc->d.background[0], sc->d.background[1], sc->d.background[2], wi0, wi1, wr0, wr1);
+        HIP_TRY(drained(hipGetLastError()));
+        ht("pipeline: k_compose launch");
+    }
+    pipelined = pipe;
     } // !staged
     if (p->ray_per_pixel > 1) {
         size_t n = (size_t)npix_local * 3;
         hipLaunchKernelGGL(k_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, n, (float)p->ray_per_pixel);
         HIP_TRY(hipGetLastError());
     }
-    if (!single_launch && timed) HIP_TRY(hipEventRecord(sc->ev_end[slot], stream));
-    sc->last_timed = timed;
+    // (a pipelined frame's kernel_ms_total runs from its trace to the end of its compose; its "done" event is the compose's)
+    if ((!single_launch || pipelined) && timed) HIP_TRY(hipEventRecord(sc->ev_end[slot], stream));
+    sc->last_timed = timed || pipelined;
     if (timed) {
-        sc->single_launch[slot] = single_launch;
-        sc->last_done = single_launch ? sc->ev_pend[slot] : sc->ev_end[slot];
+        sc->single_launch[slot] = single_launch && !pipelined;
+        sc->last_done = sc->single_launch[slot] ? sc->ev_pend[slot] : sc->ev_end[slot];
         sc->frames_recorded++;
     }
+    if (pipelined) sc->last_done = sc->ev_composed[(sc->launch_index - 1u) % NraysScene::kPipeSlots];
+    sc->last_pipelined = pipelined;
     sc->last_stream = stream; sc->have_last = true;
     ht("end (event records after the launch)");
     // owned rows only (padding rows of the last band carry no rays)
@@ -1006,7 +1133,7 @@ static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
 }
 static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
     w->last_stream = stream; w->used = true;
-    if (sc->have_last) { sc->last_stream = stream; sc->last_timed = false; }
+    if (sc->have_last) { sc->last_stream = stream; sc->last_timed = false; sc->last_pipelined = false; }
 }
 // Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
 static bool batch_mesh_only(const NraysScene* sc) { return (sc->features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
@@ -1329,7 +1456,8 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     // 0.0565 at 16 / 64, 0.0550 with an order that is never refreshed; 0.049 at rest).
     sc->near_pixels = sc->host.any_mesh ? kNearPixels : 2.0 * kNearPixels; sc->max_order_age = sc->host.any_mesh ? 0u : 16u;
     if (const char* e = getenv("NRAYS_SPLIT_HYST")) sc->split_hyst = (float)atof(e);
-    sc->host_times = getenv("NRAYS_HOST_TIMES") != nullptr;
+    if (const char* e = getenv("NRAYS_HOST_TIMES")) sc->host_times_from = (uint64_t)std::max(1ll, atoll(e));
+    if (const char* e = getenv("NRAYS_PIPELINE")) { sc->pipeline = atoi(e) != 0; sc->pipeline_always = atoi(e) == 2; }
     if (const char* e = getenv("NRAYS_NEAR_PIXELS")) sc->near_pixels = atof(e);
     if (const char* e = getenv("NRAYS_ORDER_AGE")) sc->max_order_age = (uint32_t)std::max(0, atoi(e));
     if (const char* e = getenv("NRAYS_LEAD_WGS")) sc->lead_mode = atoi(e) != 0;
@@ -1339,7 +1467,7 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     // release bulk host copies
     std::vector<BvhNode>().swap(h.nodes); std::vector<TriRec>().swap(h.tris); std::vector<TriUv>().swap(h.triuvs);
 
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NraysScene::kCountSets; ++k) {
         if (hipMalloc((void**)&sc->d_counts_set[k], kNumCounts * sizeof(uint32_t)) != hipSuccess ||
             hipMalloc((void**)&sc->d_counters_set[k], sizeof(DeviceCounters)) != hipSuccess)
             return bail(fail(NRAYS_ERR_OOM, "counter allocation failed"));
@@ -1381,11 +1509,12 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
 void nrays_scene_destroy(NraysScene* sc) {
     if (!sc) return;
     (void)hipSetDevice(sc->device);
-    if (sc->have_last) (void)hipStreamSynchronize(sc->last_stream);
+    if (sc->have_last) (void)hipStreamSynchronize(sc->last_stream); // (the compose of every pipelined frame is there or ordered before it, behind its trace)
+    pipeline_release(sc);
     for (void* p : sc->allocs) (void)hipFree(p);
     for (nrays::DeviceBlas& b : sc->host.dev_blas) nrays::free_device_blas(b); // a creation that failed between the build and the upload
     for (int k = 0; k < 2; ++k) if (sc->queue[k].block) (void)hipFree(sc->queue[k].block);
-    for (int k = 0; k < 2; ++k) {
+    for (int k = 0; k < NraysScene::kCountSets; ++k) {
         if (sc->d_counts_set[k]) (void)hipFree(sc->d_counts_set[k]);
         if (sc->d_counters_set[k]) (void)hipFree(sc->d_counters_set[k]);
     }

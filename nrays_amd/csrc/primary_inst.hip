@@ -23,8 +23,11 @@ template <int GROUP, bool STATS, int FEAT, bool PLAIN, int OCC>
 static bool launch_if(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ) {
     if constexpr (GROUP == NR_PRIMARY_GROUP && wanted(FEAT)) {
         if (stats != STATS || feat != FEAT || plain != PLAIN || occ != OCC) return false;
-        hipLaunchKernelGGL((k_primary<STATS, FEAT, PLAIN, OCC>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, *a.R, *a.qo, a.out, a.ctr, a.spill,
-                           a.tiles_x, a.tiles_y, a.work, a.grab, a.zero_counts, a.zero_ctr);
+        // (a.done: recorded behind this launch by the launch itself — one call for the kernel and its event)
+        if (a.done) hipExtLaunchKernelGGL((k_primary<STATS, FEAT, PLAIN, OCC>), dim3(a.grid), dim3(kBlock), 0, a.stream, nullptr, a.done, 0, *a.d, *a.R, *a.qo, a.out, a.ctr, a.spill,
+                                          a.tiles_x, a.tiles_y, a.work, a.grab, a.zero_counts, a.zero_ctr);
+        else hipLaunchKernelGGL((k_primary<STATS, FEAT, PLAIN, OCC>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, *a.R, *a.qo, a.out, a.ctr, a.spill,
+                                a.tiles_x, a.tiles_y, a.work, a.grab, a.zero_counts, a.zero_ctr);
         return true;
     } else {
         return false;

@@ -4,6 +4,7 @@
 // kernels compile side by side; nrays_hip.hip holds the host side and the small kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <cstddef>
 #ifndef NR_TILE_PRIO
 #define NR_TILE_PRIO 0 // k < NR_TILE_PRIO: priority 3, < 3x: 2, < 8x: 1 (0 = off)
@@ -163,7 +164,7 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
         if (threadIdx.x == 0) block_next = 0u;
         __syncthreads();
     }
-    // Counters are double-buffered: this launch clears the set the NEXT launch / frame will use (nothing
+    // Counter sets rotate (scene_handle.h: kCountSets): this launch clears the set a LATER launch / frame will use (nothing
     // else touches it while this kernel runs), which removes every hipMemsetAsync from the frame.
     if (blockIdx.x == 0) {
         if (threadIdx.x < kNumCounts) zero_counts[threadIdx.x] = 0u;
@@ -218,7 +219,7 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
     // rows in a prologue, all threads of the workgroup on one row; with workgroup lists (grab == 0) the rows are the TAIL of
     // the list — a quarter of a row per entry — so they are written by whichever waves run out of tiles first, not by the wave that
     // still sits on the frame's longest tile.
-    const bool fill_rows = R.win_nx < tiles_x || R.win_ny < tiles_y;
+    const bool fill_rows = !R.no_rows && (R.win_nx < tiles_x || R.win_ny < tiles_y);
     auto fill_row = [&](uint32_t rl, uint32_t t0, uint32_t tstep) { // threads t0, t0 + tstep, ... of the row's W * 3 floats
         fill_background_row(S.background[0], S.background[1], S.background[2], R.spp, out, R.width, R.height, R.band_rows, R.band_owner, R.band_owners,
                             R.win_x0, R.win_nx, R.win_y0, R.win_ny, lane_log2, rl, t0, tstep);
@@ -508,6 +509,7 @@ namespace nrays {
 struct PrimaryLaunch { // the arguments of one k_primary launch
     uint32_t grid; hipStream_t stream; const DScene* d; const DRender* R; const QueueOut* qo; float* out; DeviceCounters* ctr; uint32_t* spill;
     uint32_t tiles_x, tiles_y; uint32_t* work; uint32_t grab; uint32_t* zero_counts; DeviceCounters* zero_ctr;
+    hipEvent_t done; // nullptr, or the event this launch records behind itself (pipelined frames)
 };
 // true = this group holds the permutation and has launched it (hipGetLastError() tells how that went)
 bool launch_primary_group0(const PrimaryLaunch& a, bool stats, int feat, bool plain, int occ);

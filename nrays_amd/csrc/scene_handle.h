@@ -57,8 +57,11 @@ struct NraysScene {
     // per-scene transient state, grown on demand
     QueueMem queue[2];
     uint32_t queue_capacity = 0;
-    uint32_t* d_counts_set[2] = {nullptr, nullptr};         // double-buffered, kNumCounts each
-    DeviceCounters* d_counters_set[2] = {nullptr, nullptr}; // double-buffered per frame
+    // Four sets each: launch n uses set n mod 4 and clears set (n + 2) mod 4 (frames likewise), so that two consecutive frames, which may
+    // overlap on the device (pipelined frames below), share no set; launches of the same parity are ordered among themselves.
+    static constexpr int kCountSets = 4;
+    uint32_t* d_counts_set[kCountSets] = {};         // kNumCounts each
+    DeviceCounters* d_counters_set[kCountSets] = {}; // per frame
     uint32_t* d_counts = nullptr;         // set used by the last launch
     DeviceCounters* d_counters = nullptr; // set used by the last frame
     uint64_t launch_index = 0, frame_index = 0;
@@ -82,7 +85,7 @@ struct NraysScene {
     // ... and by cameras NEAR the one whose costs it was sorted from (nrays_hip.hip: cam_shift_px) for up to kMaxOrderAge frames, so that a moving camera does not
     // record and sort on every frame.  order_seeded: the order comes from k_seed_costs' guess, the next frame replaces it.
     nrays::CamSnap cost_snap, order_snap; bool order_seeded = false;
-    bool host_times = false;                        // NRAYS_HOST_TIMES: render_impl prints where the host time of a handle's first frames goes
+    uint64_t host_times_from = 0;                   // NRAYS_HOST_TIMES=n: render_impl prints where the host time of the handle's frames n .. n + 3 goes (1: its first frames)
     bool near_reuse = true;                         // NRAYS_NEAR_REUSE=0: only the very same camera reuses an order (A/B)
     double near_pixels = 16.0; uint32_t max_order_age = 8; // NRAYS_NEAR_PIXELS / NRAYS_ORDER_AGE
     float split_hyst = 0.5f;                        // NRAYS_SPLIT_HYST: a tile that ran in parts stays split down to this fraction of the split threshold (k_tile_order)
@@ -116,6 +119,19 @@ struct NraysScene {
     hipEvent_t last_done = nullptr; // last event recorded by the previous render (one of the ring's events)
     hipEvent_t ev_switch = nullptr; // recorded on the previous render's stream when a render arrives on another one
     bool have_last = false;
+    // Pipelined frames (nrays_hip.hip: render_impl): a frame enqueued while its predecessor is still in flight traces its window on one of two
+    // library-owned non-blocking streams into a staging frame and is composed into `out` on the caller's stream (k_compose).  Slot s = launch
+    // index mod 4: its stream (s mod 2), its staging frame, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
+    bool pipeline = true;                            // NRAYS_PIPELINE=0: every frame on the direct path (A/B, tests)
+    bool pipeline_always = false;                    // NRAYS_PIPELINE=2: every eligible frame is pipelined, in flight or not (tests: no dependence on timing)
+    // (four slots on two streams: with two, the trace of frame k + 2 waited for the compose of frame k, and a wait across queues costs 12 - 23 us on
+    // this stack — the chain trace -> compose -> trace made the pipelined frame slower than the direct one; profiles/pipelined_frames_ab.log)
+    static constexpr int kPipeSlots = 4;
+    hipStream_t pipe_stream[2] = {nullptr, nullptr};
+    float* pipe_stage[kPipeSlots] = {}; size_t pipe_floats = 0;
+    uint32_t* pipe_spill[2] = {nullptr, nullptr};    // a traversal-stack spill region per internal stream (spill_entries != 0): two traces that overlap must not share d_spill
+    hipEvent_t ev_traced[kPipeSlots] = {}, ev_composed[kPipeSlots] = {};
+    bool last_pipelined = false;                     // the previous work of the handle was a pipelined frame: last_done is its "composed" event
     // A/B and test switches, read ONCE when the handle is created (never in the frame path)
     uint64_t max_primary_per_launch = 32ull << 20; // NRAYS_MAX_PRIMARY: sample batching threshold (tests force several launches)
     bool max_primary_forced = false;

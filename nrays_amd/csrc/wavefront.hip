@@ -249,7 +249,7 @@ __global__ void __launch_bounds__(kBlock, NR_WF_OCC) k_wf_primary(DScene S, DRen
                                                                   uint32_t* spill, uint32_t tiles_x, uint32_t tiles_y, uint32_t tile_begin, uint32_t tile_end,
                                                                   uint32_t* claim_next, uint32_t* clear_next, uint32_t* zero_counts, DeviceCounters* zero_ctr) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    if (blockIdx.x == 0) { // the counter sets of the NEXT launch / frame (double-buffered: nrays_hip.hip, k_primary)
+    if (blockIdx.x == 0) { // the counter sets of a LATER launch / frame (rotating sets: scene_handle.h kCountSets; nrays_hip.hip, k_primary)
         if (zero_counts && threadIdx.x < kNumCounts) zero_counts[threadIdx.x] = 0u;
         if (zero_ctr && threadIdx.x < sizeof(DeviceCounters) / 4) ((uint32_t*)zero_ctr)[threadIdx.x] = 0u;
     }

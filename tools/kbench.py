@@ -2,7 +2,10 @@
 """Kernel tuning harness (GPU box): times the HIP path on the BASELINE scenes for one or several
 builds of libnrays_hip.so (A/B in one gpurun call; each build runs in its own process).
 
-  python tools/kbench.py [--libs a.so,b.so] [--scenes balls,sponza,hairball] [--steps 20]
+  python tools/kbench.py [--libs a.so,b.so] [--scenes balls,sponza,hairball] [--steps 20] [--pipeline 0,1]
+
+--pipeline: NRAYS_PIPELINE of the handles (0 = every frame on the direct path, 1 = frames enqueued behind a frame in flight are
+pipelined); several values give one row each.  host_us_per_call is the host time of one nrays_render_device in the timed loop.
 """
 import argparse
 import ctypes as C
@@ -63,10 +66,11 @@ def run_one(scene_name, steps, width, height, check):
     t0 = time.perf_counter()
     for _ in range(steps):
         render()
+    t_host = (time.perf_counter() - t0) / steps
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     ts = nr.get_stats(sc)
-    res = {"scene": scene_name, "res": [width, height], "ms": round(dt * 1e3, 4), "mrays_s": round(st.total_rays() / dt / 1e6, 1),
+    res = {"scene": scene_name, "pipeline": os.environ.get("NRAYS_PIPELINE", "default"), "res": [width, height], "ms": round(dt * 1e3, 4), "host_us_per_call": round(t_host * 1e6, 2), "mrays_s": round(st.total_rays() / dt / 1e6, 1),
            "rays": st.total_rays(), "primary_ms": round(ts.kernel_ms_primary, 4), "gpu_ms": round(ts.kernel_ms_total, 4),
            "node_per_ray": round(st.node_tests / st.total_rays(), 1), "tri_per_ray": round(st.tri_tests / st.total_rays(), 2),
            "gens": st.generations, "build_s": round(t_build, 2), "shadow": st.rays_shadow, "shadow_not_traced": ts.rays_shadow_elided,
@@ -92,6 +96,7 @@ def main():
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--check", action="store_true")
     ap.add_argument("--child", default="")
+    ap.add_argument("--pipeline", default="", help="comma-separated NRAYS_PIPELINE values, one row each (default: the environment's)")
     a = ap.parse_args()
     if a.child:
         run_one(a.child, a.steps, a.width, a.height, a.check)
@@ -102,7 +107,9 @@ def main():
         if lib:
             env["NRAYS_HIP_LIB"] = os.path.abspath(lib)
         print("== lib:", lib or "default", flush=True)
-        for s in a.scenes.split(","):
+        for s, pl in [(s, pl) for s in a.scenes.split(",") for pl in (a.pipeline.split(",") if a.pipeline else [None])]:
+            if pl is not None:
+                env["NRAYS_PIPELINE"] = pl
             cmd = [sys.executable, os.path.abspath(__file__), "--child", s, "--steps", str(a.steps), "--width", str(a.width), "--height", str(a.height)]
             if a.check:
                 cmd.append("--check")

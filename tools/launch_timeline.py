@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Kernel durations against the launch period (GPU box): runs tools/kbench.py --child <scene> under
 rocprofv3 --kernel-trace and prints, per kernel name, the launches, the mean duration and the mean distance between the
-starts of consecutive launches — what a frame costs beyond the time its kernel is executing.
+starts of consecutive launches — what a frame costs beyond the time its kernel is executing — and overlap_share: over the
+timed loop (the last `steps` launches of the kernel), the share of the time in which two launches of it run at once
+(pipelined frames, NRAYS_PIPELINE, taken from the environment).
 
   python tools/launch_timeline.py balls [width height [steps]]
 """
@@ -38,8 +40,12 @@ def main():
         per = [v[i + 1][0] - v[i][0] for i in range(len(v) - 1)]
         per = sorted(per)[: max(1, len(per) * 3 // 4)]  # drop the gaps between the timing loops
         gaps = sorted(v[i + 1][0] - v[i][1] for i in range(len(v) - 1))[: max(1, (len(v) - 1) * 3 // 4)]
+        t = v[-min(len(v), int(steps)):]
+        both = sum(max(0, min(t[i][1], t[i + 1][1]) - t[i + 1][0]) for i in range(len(t) - 1))
         print(json.dumps({"kernel": k, "launches": len(v), "duration_us": round(sum(dur) / len(dur) / 1e3, 2),
-                          "period_us": round(sum(per) / max(len(per), 1) / 1e3, 2), "gap_us": round(sum(gaps) / max(len(gaps), 1) / 1e3, 2)}))
+                          "period_us": round(sum(per) / max(len(per), 1) / 1e3, 2), "gap_us": round(sum(gaps) / max(len(gaps), 1) / 1e3, 2),
+                          "timed_loop_duration_us": round(sum(e - s for s, e in t) / len(t) / 1e3, 2),
+                          "overlap_share": round(both / max(1, t[-1][1] - t[0][0]), 3)}))
 
 
 if __name__ == "__main__":
