@@ -618,27 +618,30 @@ static int alloc_cost_stats(NraysScene* sc) {
     return NRAYS_OK;
 }
 
-// Pipelined frames: the two internal streams (non-blocking: the caller's stream may be the legacy null stream, which a blocking stream would
-// serialise with), their events, and a staging frame per slot for frames of up to `floats` floats.  Growing the staging frames drains the handle first.
+// Pipelined frames: the handle's internal streams (pipe_depth of them; non-blocking: the caller's stream may be the legacy null stream, which a blocking stream would
+// serialise with), their events, and per slot the staging rows of a window of up to `floats` floats.  Growing the staging rows drains the handle first.
 static int pipeline_ensure(NraysScene* sc, size_t floats) {
-    for (int k = 0; k < 2; ++k) if (!sc->pipe_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&sc->pipe_stream[k], hipStreamNonBlocking));
-    for (int k = 0; k < NraysScene::kPipeSlots; ++k) {
+    for (int k = 0; k < sc->pipe_depth; ++k) if (!sc->pipe_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&sc->pipe_stream[k], hipStreamNonBlocking));
+    for (int k = 0; k < sc->pipe_slots; ++k) {
         if (!sc->ev_traced[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_traced[k], hipEventDisableTiming));
         if (!sc->ev_composed[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_composed[k], hipEventDisableTiming));
     }
-    for (int k = 0; k < 2; ++k) if (sc->spill_entries && !sc->pipe_spill[k]) HIP_TRY(hipMalloc((void**)&sc->pipe_spill[k], (size_t)kMaxGrid * kBlock * sc->spill_entries * sizeof(uint32_t)));
+    for (int k = 0; k < sc->pipe_depth; ++k) if (sc->spill_entries && !sc->pipe_spill[k]) HIP_TRY(hipMalloc((void**)&sc->pipe_spill[k], (size_t)kMaxGrid * kBlock * sc->spill_entries * sizeof(uint32_t)));
     if (floats > sc->pipe_floats) {
         if (sc->have_last) HIP_TRY(hipStreamSynchronize(sc->last_stream)); // every trace in flight has its compose there, or ordered before it
-        for (int k = 0; k < NraysScene::kPipeSlots; ++k) if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
+        for (int k = 0; k < sc->pipe_slots; ++k) if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
         sc->pipe_floats = 0;
-        for (int k = 0; k < NraysScene::kPipeSlots; ++k) HIP_TRY(hipMalloc((void**)&sc->pipe_stage[k], floats * sizeof(float)));
+        for (int k = 0; k < sc->pipe_slots; ++k) HIP_TRY(hipMalloc((void**)&sc->pipe_stage[k], floats * sizeof(float)));
         sc->pipe_floats = floats;
     }
     return NRAYS_OK;
 }
 static void pipeline_release(NraysScene* sc) {
-    for (int k = 0; k < 2; ++k) if (sc->pipe_stream[k]) { (void)hipStreamSynchronize(sc->pipe_stream[k]); (void)hipStreamDestroy(sc->pipe_stream[k]); sc->pipe_stream[k] = nullptr; }
-    for (int k = 0; k < 2; ++k) if (sc->pipe_spill[k]) { (void)hipFree(sc->pipe_spill[k]); sc->pipe_spill[k] = nullptr; }
+    for (int k = 0; k < NraysScene::kPipeStreams; ++k) if (sc->pipe_stream[k]) (void)hipStreamSynchronize(sc->pipe_stream[k]); // all of them drained before anything they use is freed
+    for (int k = 0; k < NraysScene::kPipeStreams; ++k) {
+        if (sc->pipe_stream[k]) { (void)hipStreamDestroy(sc->pipe_stream[k]); sc->pipe_stream[k] = nullptr; }
+        if (sc->pipe_spill[k]) { (void)hipFree(sc->pipe_spill[k]); sc->pipe_spill[k] = nullptr; }
+    }
     for (int k = 0; k < NraysScene::kPipeSlots; ++k) {
         if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
         if (sc->ev_traced[k]) { (void)hipEventDestroy(sc->ev_traced[k]); sc->ev_traced[k] = nullptr; }
@@ -651,6 +654,12 @@ static void pipeline_release(NraysScene* sc) {
 // device, and pipelining each handle on top of that oversubscribes the hardware queues (six streams: 0.044 ms per frame against 0.0285 on the direct path,
 // profiles/pipelined_frames_full.log) — such frames stay on the direct path.
 static std::atomic<NraysScene*> g_last_renderer{nullptr};
+
+// The stream of the blocking entry points (nrays_render, nrays_render_rgb8, nrays_trace_rays, the debug casts): created on first use.
+static int ensure_own_stream(NraysScene* sc) {
+    if (!sc->own_stream) HIP_TRY(hipStreamCreate(&sc->own_stream));
+    return NRAYS_OK;
+}
 
 static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStream_t stream, bool instrumented, uint32_t count_flags = 0u) {
     if (!sc || !p || !d_out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
@@ -787,8 +796,8 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     const bool staged = !instrumented && wavefront_wanted(sc, p, lane_log2);
     bool pipelined = false; // this frame was split into a trace on an internal stream and a compose on the caller's (below)
     const bool single_launch = !staged && !instrumented && !queued && p->ray_per_pixel <= batch && p->ray_per_pixel == 1;
-    sc->d_counters = sc->d_counters_set[sc->frame_index % NraysScene::kCountSets];
-    DeviceCounters* next_ctr = sc->d_counters_set[(sc->frame_index + 2) % NraysScene::kCountSets];
+    sc->d_counters = sc->d_counters_set[sc->frame_index % (uint64_t)sc->count_rot];
+    DeviceCounters* next_ctr = sc->d_counters_set[(sc->frame_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot]; // (scene_handle.h: the set of the next frame on this frame's stream)
     sc->frame_index++;
     R.use_rng = (p->window_width != 0.0 || sc->host.any_area_light) ? 1u : 0u;
     // mesh scenes: longest-processing-time-first from the previous frame of the same geometry (pixels do not depend on it)
@@ -798,8 +807,8 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     // and far more even; recording, sorting and following the order costs more than the tail it removes: hairball 4K 64 spp
     // 251 -> 222 ms without it, sponza 1080p 4 / 16 / 64 spp 2-4 %, profiles/r02_aa_lpt.log)
     if (staged) {
-        sc->d_counts = sc->d_counts_set[sc->launch_index % NraysScene::kCountSets];
-        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 2) % NraysScene::kCountSets];
+        sc->d_counts = sc->d_counts_set[sc->launch_index % (uint64_t)sc->count_rot];
+        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot];
         sc->launch_index++;
         const int rc = wavefront_render(sc, p, R, d_out, stream, tiles_x, tiles_y, timed, slot, next_ctr, next_counts);
         if (rc != NRAYS_OK) return rc;
@@ -955,13 +964,14 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     ht("scheduling state (seed / sort launches)");
     // ---- pipelined frames ----------------------------------------------------------------------------------------------------------
     // A frame of an analytic scene that arrives while the handle's previous work is still in flight is split in two.  TRACE: the very
-    // k_primary launch of the direct path, on the internal stream of the launch's parity, storing the window's pixels into the staging
-    // frame of slot `ps` (launch index mod 4) and no background rows; it reads only what the library owns (scene records, the by-value camera, an order no frame in
+    // k_primary launch of the direct path, on internal stream `ps` mod pipe_depth, storing the window's pixels into the staging rows
+    // of slot `ps` (launch index mod pipe_slots) and no background rows; it reads only what the library owns (scene records, the by-value camera, an order no frame in
     // flight writes), so it is not ordered against the caller's stream and overlaps the tail of the frame before it.  COMPOSE: k_compose on
     // the caller's stream behind the trace — `out` is written there alone, in call order, as on the direct path.
-    // Ordering of the shared state: launches of the same parity share counter sets (n mod 4 used, (n + 2) mod 4 cleared), staging frames
-    // (n mod 4) and the traversal-stack spill region of their stream (pipe_spill; never the handle's d_spill) and run on the same internal stream (the trace also waits for the compose that read its staging frame four launches ago); every direct frame comes behind all composes on the
-    // caller's stream, and the first pipelined frame after direct work makes BOTH internal streams wait for the end of that work.
+    // Ordering of the shared state: launches n and n + pipe_depth run on the same internal stream, and only such launches share counter sets (n mod count_rot
+    // used, (n + pipe_depth) mod count_rot cleared: scene_handle.h), staging rows (n mod pipe_slots) and the traversal-stack spill region of their stream (pipe_spill; never the
+    // handle's d_spill); the trace also waits for the compose that read its staging rows pipe_slots launches ago.  Every direct frame comes behind all composes on the
+    // caller's stream, and the first pipelined frame after direct work makes ALL internal streams wait for the end of that work.
     // Not pipelined: frames that record or sort tile costs, instrumented / multi-sample / queued / banded / staged frames, mesh scenes
     // (their moving frames sort every time), windows beyond half the frame (the copy would outweigh the rows it takes off the tracing waves).
     bool pipe = sc->pipeline && single_launch && !sc->d.no_elide && !banded && !sc->host.any_mesh && grab == 0u && lane_log2 == 0u && !R.tile_cost &&
@@ -976,19 +986,29 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
         pipe = q == hipErrorNotReady;
         ht("pipeline: in-flight query");
     }
-    if (pipe && pipeline_ensure(sc, (size_t)npix_local * 3) != NRAYS_OK) { // no room for the staging frames: direct from here on, and said so once
+    // the window in pixels; a slot holds its rows [wr0, wr1s) and is handed to the kernels as if it began at row 0 (no pitch, no kernel argument: the trace writes and the
+    // compose reads those rows only)
+    const uint32_t wi0 = R.win_x0 << bwl, wi1 = std::min<uint32_t>((R.win_x0 + R.win_nx) << bwl, p->width), wr0 = R.win_y0 << bhl, wr1 = (R.win_y0 + R.win_ny) << bhl;
+    const uint32_t wr1s = std::min<uint32_t>(wr1, rows);
+    const size_t stage_skip = (size_t)wr0 * p->width * 3;
+    if (pipe && pipeline_ensure(sc, (size_t)(wr1s - wr0) * p->width * 3) != NRAYS_OK) { // no room for the staging frames: direct from here on, and said so once
         (void)hipGetLastError(); sc->pipeline = false; pipe = false;
         fprintf(stderr, "nrays: the staging frames of pipelined frames could not be allocated (%s); this handle renders every frame on the direct path\n", g_last_error.c_str());
     }
-    const int ps = (int)(sc->launch_index % NraysScene::kPipeSlots);
-    const hipStream_t lstream = pipe ? sc->pipe_stream[ps & 1] : stream;
+    // Three persistent trace grids compete for the two wave slots of a SIMD: with lead + second workgroups (two per CU) a trace holds every slot of the chip while its
+    // long tiles run, and the third trace in flight mostly waits for slots; with ONE workgroup per CU (the NRAYS_LEAD_WGS=0 shape of the cost-ordered lists) two traces
+    // fit side by side and the third takes the slots of whichever retires waves first.  Pixels do not depend on the shape of the lists.
+    if (pipe && !sc->pipe_lead_wgs && R.lead_wgs) { R.lead_wgs = 0u; R.lead_entries = 0u; grid_primary = std::min<uint32_t>(grid_primary, (uint32_t)sc->num_cus); }
+    const int ps = (int)(sc->launch_index % (uint64_t)sc->pipe_slots), pst = ps % sc->pipe_depth;
+    const hipStream_t lstream = pipe ? sc->pipe_stream[pst] : stream;
+    float* const stage = pipe ? sc->pipe_stage[ps] - stage_skip : nullptr;
     if (pipe) {
-        if (!sc->last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: both internal streams behind its end
+        if (!sc->last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: every internal stream behind its end
             if (!sc->ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming));
             HIP_TRY(hipEventRecord(sc->ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
-            for (int k = 0; k < 2; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe_stream[k], sc->ev_switch, 0));
+            for (int k = 0; k < sc->pipe_depth; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe_stream[k], sc->ev_switch, 0));
         }
-        // the compose that last read this slot's staging frame, four frames ago: when the host can see that it is over (a query costs 0.6 us) the wait (5 us
+        // the compose that last read this slot's staging rows, pipe_slots frames ago: when the host can see that it is over (a query costs 0.6 us) the wait (5 us
         // of host time, which bounds the pipelined frame rate) is not enqueued
         if (hipEventQuery(sc->ev_composed[ps]) != hipSuccess) { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(lstream, sc->ev_composed[ps], 0)); }
         ht("pipeline: waits of the trace stream");
@@ -997,8 +1017,8 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
     for (uint32_t s0 = 0; s0 < p->ray_per_pixel; s0 += batch) {
         R.sample_begin = s0; R.sample_end = std::min<uint32_t>(p->ray_per_pixel, s0 + batch);
         R.first_batch = s0 == 0 ? 1u : 0u;
-        sc->d_counts = sc->d_counts_set[sc->launch_index % NraysScene::kCountSets];
-        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + 2) % NraysScene::kCountSets];
+        sc->d_counts = sc->d_counts_set[sc->launch_index % (uint64_t)sc->count_rot];
+        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot];
         sc->launch_index++;
         QueueOut qo; qo.q = sc->queue[1].q; qo.capacity = queued ? sc->queue_capacity : 0; qo.count = sc->d_counts + 1;
         qo.overflow = &sc->d_counters->overflow;
@@ -1015,8 +1035,8 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
         }
         // (a scene with a non-finite light / colour / texel: every frame by the kernel that skips nothing)
         R.no_rows = pipe ? 1u : 0u; // a trace launch writes the window only
-        launch_primary(sc, instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, lstream, dsc, R, qo, pipe ? sc->pipe_stage[ps] : d_out, sc->d_counters,
-                       pipe ? sc->pipe_spill[ps & 1] : sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr, pipe ? sc->ev_traced[ps] : nullptr);
+        launch_primary(sc, instrumented || sc->d.no_elide != 0u, sc->features, sc->noxform, sc->park, sc->tiny, occ, grid_primary, lstream, dsc, R, qo, pipe ? stage : d_out, sc->d_counters,
+                       pipe ? sc->pipe_spill[pst] : sc->d_spill, tiles_x, tiles_y, sc->d_counts + kMaxGenerations + 2, grab, next_counts, R.first_batch ? next_ctr : nullptr, pipe ? sc->ev_traced[ps] : nullptr);
         HIP_TRY(hipGetLastError());
         if (first_primary) ht("k_primary launch");
         if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[1], stream));
@@ -1058,8 +1078,7 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
         auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(lstream); sc->last_pipelined = false; } return e; };
         HIP_TRY(drained(hipStreamWaitEvent(stream, sc->ev_traced[ps], 0)));
         ht("pipeline: wait of the caller's stream");
-        const uint32_t wi0 = R.win_x0 << bwl, wi1 = std::min<uint32_t>((R.win_x0 + R.win_nx) << bwl, p->width), wr0 = R.win_y0 << bhl, wr1 = (R.win_y0 + R.win_ny) << bhl;
-        hipExtLaunchKernelGGL(k_compose, dim3(rows), dim3(256), 0, stream, nullptr, sc->ev_composed[ps], 0, d_out, (const float*)sc->pipe_stage[ps], p->width, p->ray_per_pixel, sc->d.background[0], sc->d.background[1], sc->d.background[2], wi0, wi1, wr0, wr1);
+        hipExtLaunchKernelGGL(k_compose, dim3(rows), dim3(256), 0, stream, nullptr, sc->ev_composed[ps], 0, d_out, (const float*)stage, p->width, p->ray_per_pixel, sc->d.background[0], sc->d.background[1], sc->d.background[2], wi0, wi1, wr0, wr1);
         HIP_TRY(drained(hipGetLastError()));
         ht("pipeline: k_compose launch");
     }
@@ -1078,7 +1097,7 @@ static int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out,
         sc->last_done = sc->single_launch[slot] ? sc->ev_pend[slot] : sc->ev_end[slot];
         sc->frames_recorded++;
     }
-    if (pipelined) sc->last_done = sc->ev_composed[(sc->launch_index - 1u) % NraysScene::kPipeSlots];
+    if (pipelined) sc->last_done = sc->ev_composed[(sc->launch_index - 1u) % (uint64_t)sc->pipe_slots];
     sc->last_pipelined = pipelined;
     sc->last_stream = stream; sc->have_last = true;
     ht("end (event records after the launch)");
@@ -1458,6 +1477,10 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     if (const char* e = getenv("NRAYS_SPLIT_HYST")) sc->split_hyst = (float)atof(e);
     if (const char* e = getenv("NRAYS_HOST_TIMES")) sc->host_times_from = (uint64_t)std::max(1ll, atoll(e));
     if (const char* e = getenv("NRAYS_PIPELINE")) { sc->pipeline = atoi(e) != 0; sc->pipeline_always = atoi(e) == 2; }
+    if (const char* e = getenv("NRAYS_PIPELINE_DEPTH")) sc->pipe_depth = std::max(1, std::min((int)NraysScene::kPipeStreams, atoi(e)));
+    sc->pipe_slots = sc->pipe_depth == 3 ? 6 : 4; sc->count_rot = sc->pipe_slots; // (depth 2: the rotation and the slots of the two-stream pipeline)
+    sc->pipe_lead_wgs = sc->pipe_depth < 3;
+    if (const char* e = getenv("NRAYS_PIPELINE_LEAD_WGS")) sc->pipe_lead_wgs = atoi(e) != 0;
     if (const char* e = getenv("NRAYS_NEAR_PIXELS")) sc->near_pixels = atof(e);
     if (const char* e = getenv("NRAYS_ORDER_AGE")) sc->max_order_age = (uint32_t)std::max(0, atoi(e));
     if (const char* e = getenv("NRAYS_LEAD_WGS")) sc->lead_mode = atoi(e) != 0;
@@ -1481,7 +1504,8 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     stage("records, switches, counters");
     if (hipMalloc((void**)&sc->d_counters_primary, sizeof(DeviceCounters)) != hipSuccess)
         return bail(fail(NRAYS_ERR_OOM, "counter allocation failed"));
-    if (hipStreamCreate(&sc->own_stream) != hipSuccess) return bail(fail(NRAYS_ERR_HIP, "stream creation failed"));
+    // (own_stream is created by the first entry point that needs it, ensure_own_stream(): a handle that is only ever rendered on the caller's streams leaves its
+    // hardware queue to the internal streams of the pipelined frames — a stream that exists holds a queue, and a process has four)
     // (the ring's timing events are created by the first frame that records into a slot: 1 024 hipEventCreate cost 0.6 ms of every scene creation)
     stage("stream + event ring");
     {   // What a first frame would allocate, sized for frames up to 4K (larger ones re-allocate as before): the reference's caller
@@ -1707,6 +1731,7 @@ int nrays_render(NraysScene* sc, const NraysRenderParams* p, float* out_rgb) {
         HIP_TRY(hipMalloc((void**)&sc->d_frame, floats * sizeof(float)));
         sc->frame_floats = floats;
     }
+    { const int rs = ensure_own_stream(sc); if (rs != NRAYS_OK) return rs; }
     int rc = render_impl(sc, p, sc->d_frame, sc->own_stream, false);
     if (rc != NRAYS_OK) return rc;
     HIP_TRY(hipMemcpyAsync(out_rgb, sc->d_frame, floats * sizeof(float), hipMemcpyDeviceToHost, sc->own_stream));
@@ -1733,6 +1758,7 @@ int nrays_render_rgb8(NraysScene* sc, const NraysRenderParams* p, uint8_t* out_r
         HIP_TRY(hipMalloc((void**)&sc->d_rgb8, n));
         sc->rgb8_bytes = n;
     }
+    { const int rs = ensure_own_stream(sc); if (rs != NRAYS_OK) return rs; }
     int rc = render_impl(sc, p, sc->d_frame, sc->own_stream, false);
     if (rc != NRAYS_OK) return rc;
     if (n) {
@@ -1799,6 +1825,7 @@ int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const doub
     CAST_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CAST_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
     if (mode == 1u) { CAST_TRY(hipMalloc((void**)&d_t, (size_t)n * sizeof(double))); CAST_TRY(hipMemcpy(d_t, max_toi, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
     const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    CAST_TRY(sc->own_stream ? hipSuccess : hipStreamCreate(&sc->own_stream));
     if ((sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
     else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
     CAST_TRY(hipGetLastError());
@@ -1832,6 +1859,8 @@ int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const do
     const size_t cap = w->stage_rays;
     double* s_o = (double*)w->d_stage; double* s_d = s_o + 3 * cap; double* s_r = s_d + 3 * cap;
     unsigned long long* s_k = (unsigned long long*)(s_r + cap); float* s_e = (float*)(s_k + cap); float* s_out = s_e + cap;
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
     const hipStream_t stream = sc->own_stream;
     rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;

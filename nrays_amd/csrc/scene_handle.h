@@ -57,9 +57,12 @@ struct NraysScene {
     // per-scene transient state, grown on demand
     QueueMem queue[2];
     uint32_t queue_capacity = 0;
-    // Four sets each: launch n uses set n mod 4 and clears set (n + 2) mod 4 (frames likewise), so that two consecutive frames, which may
-    // overlap on the device (pipelined frames below), share no set; launches of the same parity are ordered among themselves.
-    static constexpr int kCountSets = 4;
+    // Rotating sets: launch n uses set n mod count_rot and clears set (n + count_rot / 2) mod count_rot (frames likewise), count_rot = 2 x the streams
+    // the handle's traces may run on (pipelined frames below; at least 4).  The launch whose set is cleared is the NEXT one on the clearing launch's own
+    // stream, so no launch that can overlap this one reads or counts into the set being cleared; launches on the same stream are ordered among themselves.
+    // (With three streams "clear n + 2" would be wrong: launch n + 2 runs on another stream and may have started.)
+    static constexpr int kCountSets = 6;
+    int count_rot = 4;                               // 4 (pipeline depth 1, 2) or 6 (depth 3): fixed when the handle is created
     uint32_t* d_counts_set[kCountSets] = {};         // kNumCounts each
     DeviceCounters* d_counters_set[kCountSets] = {}; // per frame
     uint32_t* d_counts = nullptr;         // set used by the last launch
@@ -119,17 +122,23 @@ struct NraysScene {
     hipEvent_t last_done = nullptr; // last event recorded by the previous render (one of the ring's events)
     hipEvent_t ev_switch = nullptr; // recorded on the previous render's stream when a render arrives on another one
     bool have_last = false;
-    // Pipelined frames (nrays_hip.hip: render_impl): a frame enqueued while its predecessor is still in flight traces its window on one of two
+    // Pipelined frames (nrays_hip.hip: render_impl): a frame enqueued while its predecessor is still in flight traces its window on one of up to three
     // library-owned non-blocking streams into a staging frame and is composed into `out` on the caller's stream (k_compose).  Slot s = launch
-    // index mod 4: its stream (s mod 2), its staging frame, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
+    // index mod pipe_slots: its stream (s mod pipe_depth), its staging rows, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
     bool pipeline = true;                            // NRAYS_PIPELINE=0: every frame on the direct path (A/B, tests)
     bool pipeline_always = false;                    // NRAYS_PIPELINE=2: every eligible frame is pipelined, in flight or not (tests: no dependence on timing)
-    // (four slots on two streams: with two, the trace of frame k + 2 waited for the compose of frame k, and a wait across queues costs 12 - 23 us on
+    // (twice as many slots as streams: with as many, the trace of frame k + depth waited for the compose of frame k, and a wait across queues costs 12 - 23 us on
     // this stack — the chain trace -> compose -> trace made the pipelined frame slower than the direct one; profiles/pipelined_frames_ab.log)
-    static constexpr int kPipeSlots = 4;
-    hipStream_t pipe_stream[2] = {nullptr, nullptr};
+    static constexpr int kPipeStreams = 3, kPipeSlots = 2 * kPipeStreams; // the most a handle uses: the caller's stream + 3 fill a process's four hardware queues
+    int pipe_depth = 3;                              // NRAYS_PIPELINE_DEPTH=1|2|3: traces of the handle in flight at once = internal streams (read when the handle is created)
+    int pipe_slots = 6;                              // 4 at depth 1 and 2, 6 at depth 3
+    bool pipe_lead_wgs = false;                      // NRAYS_PIPELINE_LEAD_WGS: a pipelined trace keeps the lead + second workgroups of a direct frame (default at depth 1, 2) or runs
+                                                     // its cost-ordered lists on one workgroup per CU (default at depth 3: three grids share two wave slots per SIMD)
+    hipStream_t pipe_stream[kPipeStreams] = {};
+    // A slot holds the rows [wr0, wr1) of the window only (the trace with DRender::no_rows writes nothing else; k_compose reads nothing else): the kernels get
+    // `pipe_stage[s] - wr0 * width * 3`, which they address like `out`.  pipe_floats: floats allocated per slot; grown when a window needs more rows.
     float* pipe_stage[kPipeSlots] = {}; size_t pipe_floats = 0;
-    uint32_t* pipe_spill[2] = {nullptr, nullptr};    // a traversal-stack spill region per internal stream (spill_entries != 0): two traces that overlap must not share d_spill
+    uint32_t* pipe_spill[kPipeStreams] = {};         // a traversal-stack spill region per internal stream (spill_entries != 0): traces that overlap must not share d_spill
     hipEvent_t ev_traced[kPipeSlots] = {}, ev_composed[kPipeSlots] = {};
     bool last_pipelined = false;                     // the previous work of the handle was a pipelined frame: last_done is its "composed" event
     // A/B and test switches, read ONCE when the handle is created (never in the frame path)

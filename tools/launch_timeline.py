@@ -2,8 +2,9 @@
 """Kernel durations against the launch period (GPU box): runs tools/kbench.py --child <scene> under
 rocprofv3 --kernel-trace and prints, per kernel name, the launches, the mean duration and the mean distance between the
 starts of consecutive launches — what a frame costs beyond the time its kernel is executing — and overlap_share: over the
-timed loop (the last `steps` launches of the kernel), the share of the time in which two launches of it run at once
-(pipelined frames, NRAYS_PIPELINE, taken from the environment).
+timed loop (the last `steps` launches of the kernel), the share of the time in which consecutive launches of it run at once
+(pipelined frames; NRAYS_PIPELINE and NRAYS_PIPELINE_DEPTH are taken from the environment), beside share_ge2 / share_ge3: the
+share of that loop in which at least two / at least three launches of the kernel are running (a sweep over their starts and ends).
 
   python tools/launch_timeline.py balls [width height [steps]]
 """
@@ -16,6 +17,20 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def running_shares(t):
+    """Shares of [first start, last end] of the launches `t` = [(start, end), ...] with at least 2 and at least 3 of them running."""
+    ev = sorted([(s, 1) for s, _ in t] + [(e, -1) for _, e in t])  # (an end sorts before a start at the same tick)
+    n, last, ge2, ge3 = 0, ev[0][0], 0, 0
+    for x, d in ev:
+        if n >= 2:
+            ge2 += x - last
+        if n >= 3:
+            ge3 += x - last
+        n, last = n + d, x
+    span = max(1, max(e for _, e in t) - min(s for s, _ in t))
+    return ge2 / span, ge3 / span
 
 
 def main():
@@ -45,7 +60,8 @@ def main():
         print(json.dumps({"kernel": k, "launches": len(v), "duration_us": round(sum(dur) / len(dur) / 1e3, 2),
                           "period_us": round(sum(per) / max(len(per), 1) / 1e3, 2), "gap_us": round(sum(gaps) / max(len(gaps), 1) / 1e3, 2),
                           "timed_loop_duration_us": round(sum(e - s for s, e in t) / len(t) / 1e3, 2),
-                          "overlap_share": round(both / max(1, t[-1][1] - t[0][0]), 3)}))
+                          "overlap_share": round(both / max(1, t[-1][1] - t[0][0]), 3),
+                          "share_ge2": round(running_shares(t)[0], 3), "share_ge3": round(running_shares(t)[1], 3)}))
 
 
 if __name__ == "__main__":
