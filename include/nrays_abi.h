@@ -30,7 +30,9 @@ extern "C" {
 #endif
 
 /* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6); 6 = nrays_trace_rays_device / nrays_trace_rays /
- * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation. */
+ * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation.
+ * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
+ * nrays_intersects_rays_device_ex / nrays_debug_ray_order.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -268,6 +270,35 @@ int nrays_trace_rays(NraysScene* scene, uint32_t n, const double* origins, const
  * `hip_stream` without synchronisation.  NULL arguments -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK. */
 int nrays_intersects_rays_device(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
                                  float* out_filter, uint32_t* out_lit, void* hip_stream);
+
+/* The three entry points above with `flags`.  flags == 0 IS the entry point without _ex: the same kernels with the same arguments.  Any bit
+ * other than the ones below -> NRAYS_ERR_BAD_ARG.  Everything else of their contracts holds unchanged.
+ *   NRAYS_RAYS_UNORDERED  a statement about the INPUT, like the coherent / incoherent hints of other ray-casting libraries: the rays come in
+ *                         no useful order (baking, ambient occlusion, shuffled or gathered rays), so the library may trace them in an order
+ *                         of its own.  It then computes a spatial key per ray on the device (origin cell, direction signs, direction cell, in
+ *                         a frame fitted to each chunk), bins the rays of the chunk by it and traces them bin by bin; every result is written
+ *                         to the slot of the ray it belongs to and is BIT-IDENTICAL to the unhinted call's — only the time changes.  The
+ *                         inputs are not modified; the reorder is launches on the same stream, without read-back or synchronisation.  The
+ *                         library cannot find incoherence out cheaply itself (that is reading the whole batch once more); under the hint it
+ *                         still skips the reorder where the host can see that it does not pay (small batches).  NRAYS_RAY_REORDER=0 in the
+ *                         environment of nrays_scene_create: never reorder; =2: reorder every hinted batch whatever its size. */
+#define NRAYS_RAYS_UNORDERED 1u
+int nrays_trace_rays_device_ex(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy,
+                               const uint64_t* keys, uint32_t max_depth, float* out_rgb, uint32_t flags, void* hip_stream);
+int nrays_trace_rays_ex(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy,
+                        const uint64_t* keys, uint32_t max_depth, float* out_rgb, uint32_t flags);
+int nrays_intersects_rays_device_ex(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
+                                    float* out_filter, uint32_t* out_lit, uint32_t flags, void* hip_stream);
+
+/* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
+ *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),
+ *   out_frame  NRAYS_RAY_FRAME_DOUBLES doubles: the quantisation frame the keys were computed in (layout: ray_key.h),
+ *   out_info   {K: significant bits of a key, B: leading bits the binning orders by, 1 if a hinted batch of n rays on this handle would be
+ *              reordered, 0}.  n == 0: out_info only.
+ * All HOST memory.  Blocking. */
+#define NRAYS_RAY_FRAME_DOUBLES 20
+int nrays_debug_ray_order(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order,
+                          double* out_frame, uint32_t out_info[4]);
 
 /* Number of rows in the compact output buffer of a (possibly tiled) render. */
 uint32_t nrays_tile_rows(const NraysRenderParams* params);

@@ -357,6 +357,16 @@ impl GpuScene {
     /// `scene.trace(ray)` (src/scene.rs:163-193) for every ray of the batch, in one call (nrays_trace_rays, blocking).  `keys[i]`
     /// is ray i's RNG path key for area-light sampling (None: key i); `max_depth` 0 = the energy rule alone, as `trace` does.
     pub fn trace_rays(&self, rays: &[RayWithEnergy], keys: Option<&[u64]>, max_depth: u32) -> Result<Vec<Vector3<f32>>, String> {
+        self.trace_rays_flags(rays, keys, max_depth, 0)
+    }
+
+    /// `trace_rays` for a batch that comes in no useful order (AO / baking rays, shuffled or gathered rays; NRAYS_RAYS_UNORDERED): the library
+    /// may bin the rays by a spatial key on the device and trace them in that order.  The colours are bit-identical to `trace_rays`'.
+    pub fn trace_rays_unordered(&self, rays: &[RayWithEnergy], keys: Option<&[u64]>, max_depth: u32) -> Result<Vec<Vector3<f32>>, String> {
+        self.trace_rays_flags(rays, keys, max_depth, NRAYS_RAYS_UNORDERED)
+    }
+
+    fn trace_rays_flags(&self, rays: &[RayWithEnergy], keys: Option<&[u64]>, max_depth: u32, flags: u32) -> Result<Vec<Vector3<f32>>, String> {
         if let Some(k) = keys { if k.len() != rays.len() { return Err(format!("{} keys for {} rays", k.len(), rays.len())); } }
         let n = rays.len();
         let mut o = Vec::with_capacity(3 * n);
@@ -371,7 +381,7 @@ impl GpuScene {
         }
         let mut px: Vec<Vector3<f32>> = vec![Vector3::new(0.0f32, 0.0, 0.0); n];
         let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
-        let rc = unsafe { nrays_trace_rays(self.raw, n as u32, o.as_ptr(), d.as_ptr(), refr.as_ptr(), energy.as_ptr(), kp, max_depth, px.as_mut_ptr() as *mut f32) };
+        let rc = unsafe { nrays_trace_rays_ex(self.raw, n as u32, o.as_ptr(), d.as_ptr(), refr.as_ptr(), energy.as_ptr(), kp, max_depth, px.as_mut_ptr() as *mut f32, flags) };
         if rc != NRAYS_OK { return Err(last_error()); }
         Ok(px)
     }
@@ -381,6 +391,13 @@ impl GpuScene {
     pub unsafe fn intersects_rays(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32,
                                   hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_intersects_rays_device(self.raw, n, origins, dirs, max_toi, out_filter, out_lit, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// `intersects_rays` for rays that come in no useful order (NRAYS_RAYS_UNORDERED, as `trace_rays_unordered`): the same results, bit for bit.
+    pub unsafe fn intersects_rays_unordered(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32,
+                                            hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_intersects_rays_device_ex(self.raw, n, origins, dirs, max_toi, out_filter, out_lit, NRAYS_RAYS_UNORDERED, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 }

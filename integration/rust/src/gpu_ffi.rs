@@ -13,6 +13,8 @@ pub const NRAYS_ERR_UNSUPPORTED: c_int = -4;
 pub const NRAYS_ERR_NO_DEVICE: c_int = -5;
 pub const NRAYS_ERR_QUEUE_OVERFLOW: c_int = -6;
 pub const NRAYS_ERR_RCCL: c_int = -7;
+/// flags of the `_ex` batch entry points: the rays come in no useful order, the library may trace them in an order of its own
+pub const NRAYS_RAYS_UNORDERED: u32 = 1;
 
 // NraysShapeKind (examples/loader3d.rs:593-695)
 pub const NRAYS_SHAPE_BALL: u32 = 0;
@@ -225,6 +227,11 @@ extern "C" {
     pub fn nrays_trace_rays_device(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_trace_rays(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32) -> c_int;
     pub fn nrays_intersects_rays_device(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32, hip_stream: *mut c_void) -> c_int;
+    // (added after ABI version 7 without a bump: plain functions; flags = 0 or NRAYS_RAYS_UNORDERED)
+    pub fn nrays_trace_rays_device_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_trace_rays_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, flags: u32) -> c_int;
+    pub fn nrays_intersects_rays_device_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;
     pub fn nrays_comm_create(id: *const u8, num_ranks: u32, rank: u32, out_comm: *mut *mut NraysComm) -> c_int;

@@ -126,6 +126,13 @@ HIP_SYMBOLS = {
     "nrays_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float),
                                    C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_float)]),
     "nrays_intersects_rays_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "nrays_trace_rays_device_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_void_p]),
+    "nrays_trace_rays_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                      C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_float), C.c_uint32]),
+    "nrays_intersects_rays_device_ex": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_debug_ray_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "nrays_scene_create": (C.c_int, [C.POINTER(NraysSceneDesc), C.POINTER(C.c_void_p)]),
     "nrays_render": (C.c_int, [C.c_void_p, C.POINTER(NraysRenderParams), C.POINTER(C.c_float)]),
     "nrays_render_rgb8": (C.c_int, [C.c_void_p, C.POINTER(NraysRenderParams), C.POINTER(C.c_uint8)]),
@@ -156,6 +163,11 @@ HIP_SYMBOLS = {
     "nrays_abi_version": (C.c_uint32, []),
 }
 
+# Added after ABI version 7 without a bump: an older version-7 library (NRAYS_HIP_LIB: A/B runs against a parent build) may lack them.
+POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_intersects_rays_device_ex", "nrays_debug_ray_order")
+RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
+RAY_FRAME_DOUBLES = 20      # NRAYS_RAY_FRAME_DOUBLES
+
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # NRAYS_HIP_LIB overrides the library path (kernel A/B tuning with tools/kbench.py only).
 HIP_LIB_PATH = os.environ.get("NRAYS_HIP_LIB") or os.path.join(_REPO, "nrays_amd", "lib", "libnrays_hip.so")
@@ -185,6 +197,8 @@ def load_hip_lib():
     import torch  # noqa: F401
     lib = C.CDLL(HIP_LIB_PATH)
     for name, (res, args) in HIP_SYMBOLS.items():
+        if name in POST_V7_SYMBOLS and os.environ.get("NRAYS_HIP_LIB") and not hasattr(lib, name):
+            continue  # an older library named explicitly: calling the missing entry point is an AttributeError then
         fn = getattr(lib, name)  # AttributeError if the export is missing
         fn.restype = res
         fn.argtypes = args

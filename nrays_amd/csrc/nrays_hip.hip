@@ -34,6 +34,9 @@
 #include "trace_device.h"
 #include "wavefront.h"
 #include "primary_kernel.h"
+#include "ray_batch_kernel.h"
+#include "ray_key.h"
+#include "ray_order.h"
 
 namespace nrays {
 
@@ -133,75 +136,6 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DSc
             }
         }
         out[i] = r;
-    }
-}
-
-// Scene::trace (scene.rs:163-193) on caller-supplied rays (nrays_trace_rays_device): ray i of the chunk is loaded as a depth-0 RayWithEnergy
-// of weight 1 whose "pixel" is i, and traced exactly as k_primary traces a primary ray — the chain's sum goes straight to out[3i..3i+2],
-// second children to the queue, whose k_bounce rounds and k_fold_fixed then add them as in a frame.  A ray's arithmetic is a one-sample
-// pixel's.  NULL refr / energy: 1.0 (RayWithEnergy::new, ray_with_energy.rs:11); NULL keys: key_base + i.  `keyed`: the scene samples
-// an area light (the keys are read by nothing else).
-template <bool STATS, int FEAT>
-__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_trace_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
-                                                                              const double* __restrict__ refr, const float* __restrict__ energy,
-                                                                              const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
-                                                                              uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
-    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    Stack st;
-    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-    st.spill_stride = gridDim.x * kBlock;
-    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-    st.lds0 = Stack::addr((lds_u32*)lds_stack);
-    st.park = nullptr;
-    st.init();
-    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
-#ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
-#endif
-    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
-        const uint32_t idx = base + threadIdx.x;
-        const bool active = idx < n;
-        RayState ray;
-        ray.o = D3(0, 0, 0); ray.d = D3(0, 0, 1); ray.refr = 1.0; ray.energy = 0.0f; ray.weight = 0.0f; ray.key = 0; ray.pixel = 0;
-        if (active) {
-            const size_t i3 = 3 * (size_t)idx;
-            ray.o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]); ray.d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
-            ray.refr = refr ? refr[idx] : 1.0; ray.energy = energy ? energy[idx] : 1.0f; ray.weight = 1.0f;
-            ray.key = keys ? keys[idx] : key_base + idx; ray.pixel = idx;
-        }
-        const f3 c = trace_chain<STATS, FEAT>(S, st, active, ray, 0u, max_depth, qo, cnt, keyed != 0u);
-        if (active) { out[3 * (size_t)idx] = c.x; out[3 * (size_t)idx + 1] = c.y; out[3 * (size_t)idx + 2] = c.z; }
-    }
-    flush_counters(ctr, cnt, STATS);
-}
-
-// Scene::intersects_ray (scene.rs:147-161) on caller-supplied rays (nrays_intersects_rays_device): k_cast_batch's mode 1 with the
-// reference's Option<filter> as a lit flag and the filter (0, 0, 0 where an opaque node blocks the ray).
-template <int FEAT>
-__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
-                                                                                   const double* __restrict__ max_toi, float* __restrict__ out_filter,
-                                                                                   uint32_t* __restrict__ out_lit, uint32_t* spill) {
-    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    Stack st;
-    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-    st.spill_stride = gridDim.x * kBlock;
-    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-    st.lds0 = Stack::addr((lds_u32*)lds_stack);
-    st.park = nullptr;
-    st.init();
-    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
-#ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
-#endif
-    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
-        const uint32_t i = base + threadIdx.x;
-        if (i >= n) continue;
-        const size_t i3 = 3 * (size_t)i;
-        const d3 o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]), d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
-        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
-        const bool blocked = traverse<true, false, FEAT>(S, st, o, d, max_toi[i], hit, filter, cnt);
-        out_lit[i] = blocked ? 0u : 1u;
-        out_filter[i3] = blocked ? 0.0f : filter.x; out_filter[i3 + 1] = blocked ? 0.0f : filter.y; out_filter[i3 + 2] = blocked ? 0.0f : filter.z;
     }
 }
 
@@ -1134,6 +1068,7 @@ static void trace_workspace_release(NraysScene* sc) {
     if (w->d_counters) (void)hipFree(w->d_counters);
     if (w->d_spill) (void)hipFree(w->d_spill);
     if (w->d_stage) (void)hipFree(w->d_stage);
+    ray_order_release(w);
     delete w;
     sc->tw = nullptr;
 }
@@ -1157,10 +1092,25 @@ static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
 // Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
 static bool batch_mesh_only(const NraysScene* sc) { return (sc->features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
 
-// One chunk (n <= kTraceChunk) of nrays_trace_rays_device: k_trace_rays, then — double-branching scenes only — the k_bounce rounds of the
+// A batch the caller called unordered (NRAYS_RAYS_UNORDERED) is reordered when the host can see that it pays: the reorder is eight launches in
+// front of the trace (a launch of a handle has a period of ~11 us), which a small batch does not earn back.  kReorderMinRays: DESIGN §5b.
+constexpr uint32_t kReorderMinRays = 1u << 19;
+static bool reorder_pays(const NraysScene* sc, uint32_t n) { return sc->ray_reorder == 2 || (sc->ray_reorder != 0 && n >= kReorderMinRays); }
+static int check_ray_flags(uint32_t flags) { return (flags & ~(uint32_t)NRAYS_RAYS_UNORDERED) ? fail(NRAYS_ERR_BAD_ARG, "unknown ray-batch flag") : NRAYS_OK; }
+// The reorder of one chunk (ray_order.hip) when it is due: *order = the order to trace in, or nullptr (trace the rays as they come).
+static int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, const double* o, const double* d, hipStream_t stream, const uint32_t** order) {
+    *order = nullptr;
+    if (!reorder) return NRAYS_OK;
+    int rc = ray_order_ensure(w, n);
+    if (rc == NRAYS_OK) rc = ray_order_chunk(sc, w, n, o, d, stream);
+    if (rc == NRAYS_OK) *order = w->d_ray_order;
+    return rc;
+}
+
+// One chunk (n <= kTraceChunk) of nrays_trace_rays_device: k_trace_rays (`order`: its ordered form, lane j traces ray order[j]), then — double-branching scenes only — the k_bounce rounds of the
 // queued second children and k_fold_fixed, as render_impl runs them for a sample batch (the host reads the queue count every fourth round).
 static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
-                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream) {
+                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream, const uint32_t* order) {
     const bool queued = sc->host.any_double_branch;
     if (queued) { // render_impl's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
         const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
@@ -1181,7 +1131,8 @@ static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const doub
     const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
     const uint32_t keyed = sc->host.any_area_light ? 1u : 0u;
     // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
-    if (sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    if (order) launch_trace_rays_ordered(sc->d.no_elide, batch_mesh_only(sc) ? (int)kFeatMesh : (int)kFeatAll, grid, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
     else if (batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
     else hipLaunchKernelGGL((k_trace_rays<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
     HIP_TRY(hipGetLastError());
@@ -1218,18 +1169,23 @@ static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const doub
 }
 
 static int trace_rays_device_impl(NraysScene* sc, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
-                                  const uint64_t* keys, uint32_t max_depth, float* out, hipStream_t stream) {
+                                  const uint64_t* keys, uint32_t max_depth, float* out, uint32_t flags, hipStream_t stream) {
     if (!sc || !o || !d || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->device));
     TraceWorkspace* w = nullptr;
     int rc = trace_workspace(sc, &w);
     if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
         const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, o + 3 * (size_t)c0, d + 3 * (size_t)c0, stream, &order);
+        if (rc != NRAYS_OK) break;
         rc = trace_chunk(sc, w, nc, o + 3 * (size_t)c0, d + 3 * (size_t)c0, refr ? refr + c0 : nullptr, energy ? energy + c0 : nullptr,
-                         keys ? (const unsigned long long*)keys + c0 : nullptr, (unsigned long long)c0, max_depth, out + 3 * (size_t)c0, stream);
+                         keys ? (const unsigned long long*)keys + c0 : nullptr, (unsigned long long)c0, max_depth, out + 3 * (size_t)c0, stream, order);
     }
     batch_end(sc, w, stream);
     return rc;
@@ -1453,6 +1409,7 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
         sc->d_seed_boxes = dptr; sc->seed_boxes = (uint32_t)(boxes.size() / 6);
         if (const char* e = getenv("NRAYS_COST_SEED")) { sc->seed_enabled = atoi(e) != 0; if (atoi(e) == 4) sc->seed_rays = 4u; if (atoi(e) == 1) sc->seed_rays = 1u; }
     }
+    if (const char* e = getenv("NRAYS_RAY_REORDER")) sc->ray_reorder = atoi(e); // 0: never, 2: every batch the caller called unordered (tests), else by size
     if (const char* e = getenv("NRAYS_MAX_PRIMARY")) { sc->max_primary_per_launch = (uint64_t)std::max(1ll, atoll(e)); sc->max_primary_forced = true; }
     if (const char* e = getenv("NRAYS_LANE_LOG2")) sc->lane_log2_override = std::max(0, std::min(6, atoi(e)));
     if (const char* e = getenv("NRAYS_EVENT_STRIDE")) sc->event_stride = (uint32_t)std::max(1, atoi(e));
@@ -1838,12 +1795,17 @@ int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const doub
 
 int nrays_trace_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
                             uint32_t max_depth, float* out_rgb, void* hip_stream) {
-    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, (hipStream_t)hip_stream);
+    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u, (hipStream_t)hip_stream);
+}
+int nrays_trace_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                               uint32_t max_depth, float* out_rgb, uint32_t flags, void* hip_stream) {
+    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags, (hipStream_t)hip_stream);
 }
 
-int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
-                     uint32_t max_depth, float* out_rgb) {
+static int trace_rays_host_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                                uint32_t max_depth, float* out_rgb, uint32_t flags) {
     if (!sc || !origins || !dirs || !out_rgb) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->device));
     TraceWorkspace* w = nullptr;
@@ -1864,6 +1826,7 @@ int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const do
     const hipStream_t stream = sc->own_stream;
     rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
         const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
         auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream); };
@@ -1873,7 +1836,10 @@ int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const do
         if (e == hipSuccess && keys) e = up(s_k, keys + c0, (size_t)nc * 8);
         if (e == hipSuccess && energy) e = up(s_e, energy + c0, (size_t)nc * 4);
         if (e != hipSuccess) { rc = fail(NRAYS_ERR_HIP, std::string("trace batch upload: ") + hipGetErrorString(e)); break; }
-        rc = trace_chunk(sc, w, nc, s_o, s_d, refr ? s_r : nullptr, energy ? s_e : nullptr, keys ? s_k : nullptr, (unsigned long long)c0, max_depth, s_out, stream);
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, s_o, s_d, stream, &order);
+        if (rc != NRAYS_OK) break;
+        rc = trace_chunk(sc, w, nc, s_o, s_d, refr ? s_r : nullptr, energy ? s_e : nullptr, keys ? s_k : nullptr, (unsigned long long)c0, max_depth, s_out, stream, order);
         if (rc == NRAYS_OK) {
             e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_out, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
             if (e == hipSuccess) e = hipStreamSynchronize(stream);
@@ -1883,10 +1849,19 @@ int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const do
     batch_end(sc, w, stream);
     return rc;
 }
+int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                     uint32_t max_depth, float* out_rgb) {
+    return trace_rays_host_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u);
+}
+int nrays_trace_rays_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                        uint32_t max_depth, float* out_rgb, uint32_t flags) {
+    return trace_rays_host_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags);
+}
 
-int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
-                                 uint32_t* out_lit, void* hip_stream) {
+static int intersects_rays_device_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                       uint32_t* out_lit, uint32_t flags, void* hip_stream) {
     if (!sc || !origins || !dirs || !max_toi || !out_filter || !out_lit) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->device));
     const hipStream_t stream = (hipStream_t)hip_stream;
@@ -1895,16 +1870,62 @@ int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origi
     if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
     const bool mesh = (sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     for (uint32_t c0 = 0; c0 < n; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit ray indices far from overflow)
         const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
         const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
         const double *o = origins + 3 * (size_t)c0, *d = dirs + 3 * (size_t)c0, *t = max_toi + c0;
-        if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, o, d, stream, &order);
+        if (rc != NRAYS_OK) break;
+        if (order) launch_intersects_rays_ordered(mesh ? (int)kFeatMesh : (int)kFeatAll, grid, stream, sc->d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
         else hipLaunchKernelGGL((k_intersects_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { rc = fail(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e)); break; }
     }
     batch_end(sc, w, stream);
+    return rc;
+}
+int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                 uint32_t* out_lit, void* hip_stream) {
+    return intersects_rays_device_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, 0u, hip_stream);
+}
+int nrays_intersects_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                    uint32_t* out_lit, uint32_t flags, void* hip_stream) {
+    return intersects_rays_device_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, flags, hip_stream);
+}
+
+int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,
+                          uint32_t out_info[4]) {
+    if (!sc || !origins || !dirs || !out_keys || !out_order || !out_frame || !out_info) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n > kTraceChunk) return fail(NRAYS_ERR_BAD_ARG, "nrays_debug_ray_order: at most one chunk (2^22 rays)");
+    out_info[0] = (uint32_t)kRayKeyBits; out_info[1] = (uint32_t)kRayBinBits; out_info[2] = reorder_pays(sc, n) ? 1u : 0u; out_info[3] = 0u;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = ray_order_ensure(w, n);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->own_stream;
+    double* d_od = nullptr; // origins, then directions
+    HIP_TRY(hipMalloc((void**)&d_od, (size_t)n * 48));
+    rc = batch_begin(sc, w, stream);
+    hipError_t e = hipSuccess;
+    if (rc == NRAYS_OK) {
+        e = hipMemcpyAsync(d_od, origins, (size_t)n * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_od + 3 * (size_t)n, dirs, (size_t)n * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) rc = ray_order_chunk(sc, w, n, d_od, d_od + 3 * (size_t)n, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_keys, w->d_ray_keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_order, w->d_ray_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_frame, w->d_ray_frame, NRAYS_RAY_FRAME_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = es;
+        batch_end(sc, w, stream);
+    }
+    (void)hipFree(d_od);
+    if (rc == NRAYS_OK && e != hipSuccess) rc = fail(NRAYS_ERR_HIP, std::string("nrays_debug_ray_order: ") + hipGetErrorString(e));
     return rc;
 }
 

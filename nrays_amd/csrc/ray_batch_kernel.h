@@ -1,0 +1,114 @@
+// ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*): k_trace_rays and
+// k_intersects_rays trace ray j of a chunk in lane j (nrays_hip.hip launches them); their _ordered forms trace ray order[j] there and
+// write its result to ITS slot (ray_order.hip holds them: a batch the caller called unordered, binned by ray_key.h's key).  One body
+// each, so that the two forms cannot drift apart.  Device code only.
+#pragma once
+#include "primary_kernel.h"
+
+namespace nrays {
+
+// Scene::trace (scene.rs:163-193) on caller-supplied rays (nrays_trace_rays_device): ray i of the chunk is loaded as a depth-0 RayWithEnergy
+// of weight 1 whose "pixel" is i, and traced exactly as k_primary traces a primary ray — the chain's sum goes straight to out[3i..3i+2],
+// second children to the queue, whose k_bounce rounds and k_fold_fixed then add them as in a frame.  A ray's arithmetic is a one-sample
+// pixel's.  NULL refr / energy: 1.0 (RayWithEnergy::new, ray_with_energy.rs:11); NULL keys: key_base + i.  `keyed`: the scene samples
+// an area light (the keys are read by nothing else).
+// ORDERED: lane j traces ray i = order[j].  Everything that names the ray — its arrays, its key, its output slot, the "pixel" of its queued
+// chains and fixed-point sums — uses i, so a ray's result does not depend on where it was traced.
+template <bool STATS, int FEAT, bool ORDERED>
+__device__ __forceinline__ void trace_rays_body(uint32_t* lds_stack, const DScene& S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                                const double* __restrict__ rd, const double* __restrict__ refr, const float* __restrict__ energy,
+                                                const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
+                                                uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
+    Stack st;
+    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
+    st.spill_stride = gridDim.x * kBlock;
+    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    st.lds0 = Stack::addr((lds_u32*)lds_stack);
+    st.park = nullptr;
+    st.init();
+    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
+#ifdef NR_PHASE_TIMING
+    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
+#endif
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t slot = base + threadIdx.x;
+        const bool active = slot < n;
+        uint32_t idx = slot;
+        if (ORDERED) idx = active ? order[slot] : 0u;
+        RayState ray;
+        ray.o = D3(0, 0, 0); ray.d = D3(0, 0, 1); ray.refr = 1.0; ray.energy = 0.0f; ray.weight = 0.0f; ray.key = 0; ray.pixel = 0;
+        if (active) {
+            const size_t i3 = 3 * (size_t)idx;
+            ray.o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]); ray.d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
+            ray.refr = refr ? refr[idx] : 1.0; ray.energy = energy ? energy[idx] : 1.0f; ray.weight = 1.0f;
+            ray.key = keys ? keys[idx] : key_base + idx; ray.pixel = idx;
+        }
+        const f3 c = trace_chain<STATS, FEAT>(S, st, active, ray, 0u, max_depth, qo, cnt, keyed != 0u);
+        if (active) { out[3 * (size_t)idx] = c.x; out[3 * (size_t)idx + 1] = c.y; out[3 * (size_t)idx + 2] = c.z; }
+    }
+    flush_counters(ctr, cnt, STATS);
+}
+
+template <bool STATS, int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_trace_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                              const double* __restrict__ refr, const float* __restrict__ energy,
+                                                                              const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
+                                                                              uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    trace_rays_body<STATS, FEAT, false>(lds_stack, S, n, nullptr, ro, rd, refr, energy, keys, key_base, keyed, max_depth, out, qo, ctr, spill);
+}
+template <bool STATS, int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_trace_rays_ordered(DScene S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                                                                      const double* __restrict__ rd, const double* __restrict__ refr, const float* __restrict__ energy,
+                                                                                      const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
+                                                                                      uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    trace_rays_body<STATS, FEAT, true>(lds_stack, S, n, order, ro, rd, refr, energy, keys, key_base, keyed, max_depth, out, qo, ctr, spill);
+}
+
+// Scene::intersects_ray (scene.rs:147-161) on caller-supplied rays (nrays_intersects_rays_device): k_cast_batch's mode 1 with the
+// reference's Option<filter> as a lit flag and the filter (0, 0, 0 where an opaque node blocks the ray).
+template <int FEAT, bool ORDERED>
+__device__ __forceinline__ void intersects_rays_body(uint32_t* lds_stack, const DScene& S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                                     const double* __restrict__ rd, const double* __restrict__ max_toi, float* __restrict__ out_filter,
+                                                     uint32_t* __restrict__ out_lit, uint32_t* spill) {
+    Stack st;
+    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
+    st.spill_stride = gridDim.x * kBlock;
+    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
+    st.lds0 = Stack::addr((lds_u32*)lds_stack);
+    st.park = nullptr;
+    st.init();
+    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
+#ifdef NR_PHASE_TIMING
+    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
+#endif
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t slot = base + threadIdx.x;
+        if (slot >= n) continue;
+        const uint32_t i = ORDERED ? order[slot] : slot;
+        const size_t i3 = 3 * (size_t)i;
+        const d3 o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]), d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
+        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+        const bool blocked = traverse<true, false, FEAT>(S, st, o, d, max_toi[i], hit, filter, cnt);
+        out_lit[i] = blocked ? 0u : 1u;
+        out_filter[i3] = blocked ? 0.0f : filter.x; out_filter[i3 + 1] = blocked ? 0.0f : filter.y; out_filter[i3 + 2] = blocked ? 0.0f : filter.z;
+    }
+}
+
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                                   const double* __restrict__ max_toi, float* __restrict__ out_filter,
+                                                                                   uint32_t* __restrict__ out_lit, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    intersects_rays_body<FEAT, false>(lds_stack, S, n, nullptr, ro, rd, max_toi, out_filter, out_lit, spill);
+}
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_rays_ordered(DScene S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                                                                           const double* __restrict__ rd, const double* __restrict__ max_toi,
+                                                                                           float* __restrict__ out_filter, uint32_t* __restrict__ out_lit, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    intersects_rays_body<FEAT, true>(lds_stack, S, n, order, ro, rd, max_toi, out_filter, out_lit, spill);
+}
+
+} // namespace nrays

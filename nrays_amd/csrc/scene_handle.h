@@ -42,6 +42,10 @@ struct TraceWorkspace {
     uint32_t* d_spill = nullptr;                            // traversal-stack spill region of the batch kernels
     void* d_stage = nullptr; size_t stage_rays = 0;         // nrays_trace_rays: device copies of one chunk's host arrays
     hipStream_t last_stream = nullptr; bool used = false;   // stream of the last batch (ordering, nrays_scene_destroy)
+    // Batches the caller called unordered (NRAYS_RAYS_UNORDERED; ray_order.hip): created on the first such chunk, grown only when a chunk holds more rays
+    uint64_t* d_ray_keys = nullptr; uint32_t* d_ray_rank = nullptr; uint32_t* d_ray_order = nullptr; size_t order_rays = 0; // per ray: key, place inside its bin, order[j] = ray traced j-th
+    double* d_ray_frame = nullptr; double* d_ray_partial = nullptr; // the chunk's quantisation frame (ray_key.h) and the per-workgroup bounds it is reduced from
+    uint32_t* d_ray_bins = nullptr; uint32_t* d_ray_scan = nullptr; // bin counts, scanned in place into bin starts; block sums of that scan
 };
 
 } // namespace nrays
@@ -163,6 +167,7 @@ struct NraysScene {
     bool cull_enabled = true;                       // NRAYS_SCREEN_CULL=0: no wave tile is decided from the scene's screen bounds
     nrays::WavefrontState* wf = nullptr;            // staged (wavefront) path: queues, chunk tables, sums (wavefront.hip)
     nrays::TraceWorkspace* tw = nullptr;            // caller-ray batches (nrays_trace_rays*), created on first use
+    int ray_reorder = 1;                            // NRAYS_RAY_REORDER: 0 = a batch called unordered is traced as it comes, 2 = every such batch is reordered, else by its size (nrays_hip.hip: reorder_pays)
     int wavefront_mode = -1;                        // NRAYS_WAVEFRONT: 0 = never, 1 = whenever the scene is eligible, -1 = the library's rule (wavefront.hip)
     NraysStats last;
     uint64_t last_primary = 0, last_primary_first_batch = 0;

@@ -508,11 +508,13 @@ def _torch_args(named, device):
     return out
 
 
-def trace_rays(scene, origins, dirs, refr=None, energy=None, keys=None, max_depth=0):
+def trace_rays(scene, origins, dirs, refr=None, energy=None, keys=None, max_depth=0, unordered=False):
     """Scene::trace (src/scene.rs:163-193) on n caller-supplied rays: the colour of each, with the reflection / refraction recursion
     and the lights of a render.  `origins`, `dirs`: (n, 3); `refr` (n,) refraction index of the medium the ray is in (default 1.0),
     `energy` (n,) (default 1.0), `keys` (n,) RNG path keys for area-light sampling (default: ray i has key i); directions are used as
     given (unit length expected).  `max_depth` as in render().
+    `unordered=True` (NRAYS_RAYS_UNORDERED) says that the rays come in no useful order — AO / baking rays, shuffled or gathered rays: the
+    library may then bin them by a spatial key and trace them in that order.  The colours are bit-identical either way; only the time changes.
     numpy arrays -> nrays_trace_rays (blocking), (n, 3) float32 numpy array.  torch tensors on the scene's GPU (float64, energy float32,
     keys int64 / uint64) -> nrays_trace_rays_device on torch.cuda.current_stream(), (n, 3) float32 tensor."""
     n = _n_of(origins, dirs)
@@ -532,7 +534,11 @@ def trace_rays(scene, origins, dirs, refr=None, energy=None, keys=None, max_dept
         ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
         with torch.cuda.device(origins.device):
             stream = torch.cuda.current_stream().cuda_stream
-            abi.check(lib.nrays_trace_rays_device(scene.device_handle(), n, ptr(o), ptr(d), ptr(r), ptr(e), ptr(k), int(max_depth), ptr(out), stream))
+            if unordered:
+                abi.check(lib.nrays_trace_rays_device_ex(scene.device_handle(), n, ptr(o), ptr(d), ptr(r), ptr(e), ptr(k), int(max_depth), ptr(out),
+                                                         abi.RAYS_UNORDERED, stream))
+            else:
+                abi.check(lib.nrays_trace_rays_device(scene.device_handle(), n, ptr(o), ptr(d), ptr(r), ptr(e), ptr(k), int(max_depth), ptr(out), stream))
         return out
     if any(_is_tensor(a) for a in (dirs, refr, energy, keys)):
         raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
@@ -542,15 +548,20 @@ def trace_rays(scene, origins, dirs, refr=None, energy=None, keys=None, max_dept
     k = None if keys is None else _np_keys(keys)
     out = np.empty((n, 3), dtype=np.float32)
     ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
-    abi.check(lib.nrays_trace_rays(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(r, C.c_double), ptr(e, C.c_float),
-                                   ptr(k, C.c_uint64), int(max_depth), ptr(out, C.c_float)))
+    if unordered:
+        abi.check(lib.nrays_trace_rays_ex(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(r, C.c_double), ptr(e, C.c_float),
+                                          ptr(k, C.c_uint64), int(max_depth), ptr(out, C.c_float), abi.RAYS_UNORDERED))
+    else:
+        abi.check(lib.nrays_trace_rays(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(r, C.c_double), ptr(e, C.c_float),
+                                       ptr(k, C.c_uint64), int(max_depth), ptr(out, C.c_float)))
     return out
 
 
-def intersects_rays(scene, origins, dirs, max_toi):
+def intersects_rays(scene, origins, dirs, max_toi, unordered=False):
     """Scene::intersects_ray (src/scene.rs:147-161) on n caller-supplied rays, through nrays_intersects_rays_device: returns
     (lit mask, (n, 3) float32 colour filters) — lit where the reference returns Some(filter); the filter is (0, 0, 0) elsewhere.
-    numpy arrays in -> numpy out (blocking); torch tensors on the GPU (float64) -> tensors (bool, float32) on torch.cuda.current_stream()."""
+    numpy arrays in -> numpy out (blocking); torch tensors on the GPU (float64) -> tensors (bool, float32) on torch.cuda.current_stream().
+    `unordered=True`: as for trace_rays (nrays_intersects_rays_device_ex with NRAYS_RAYS_UNORDERED); the results are bit-identical."""
     n = _n_of(origins, dirs)
     _check_vec("max_toi", max_toi, n)
     lib = abi.load_hip_lib()
@@ -571,10 +582,33 @@ def intersects_rays(scene, origins, dirs, max_toi):
     lit = torch.empty((n,), dtype=torch.int32, device=device)
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream().cuda_stream
-        abi.check(lib.nrays_intersects_rays_device(scene.device_handle(), n, o.data_ptr(), d.data_ptr(), t.data_ptr(), filt.data_ptr(), lit.data_ptr(), stream))
+        if unordered:
+            abi.check(lib.nrays_intersects_rays_device_ex(scene.device_handle(), n, o.data_ptr(), d.data_ptr(), t.data_ptr(), filt.data_ptr(), lit.data_ptr(),
+                                                          abi.RAYS_UNORDERED, stream))
+        else:
+            abi.check(lib.nrays_intersects_rays_device(scene.device_handle(), n, o.data_ptr(), d.data_ptr(), t.data_ptr(), filt.data_ptr(), lit.data_ptr(), stream))
     if host:
         return lit.cpu().numpy() != 0, filt.cpu().numpy()
     return lit != 0, filt
+
+
+def ray_order(scene, origins, dirs):
+    """Test probe (nrays_debug_ray_order): the key and binning kernels of one unordered chunk on n <= 2^22 rays (numpy, (n, 3)).  Returns
+    (keys uint64 (n,), order uint32 (n,) — order[j] = index of the ray traced j-th —, frame float64 (abi.RAY_FRAME_DOUBLES,),
+    (K, B, reordered): significant bits of a key, leading bits the binning orders by, whether a hinted batch of n rays on this handle
+    would be reordered)."""
+    n = _n_of(origins, dirs)
+    if n > 1 << 22:
+        raise ValueError("at most one chunk (2^22 rays)")
+    if _is_tensor(origins) or _is_tensor(dirs):
+        raise ValueError("ray_order takes numpy arrays")
+    o, d = _np_floats("origins", origins, np.float64), _np_floats("dirs", dirs, np.float64)
+    keys, order = np.zeros(n, np.uint64), np.zeros(n, np.uint32)
+    frame, info = np.zeros(abi.RAY_FRAME_DOUBLES, np.float64), (C.c_uint32 * 4)()
+    dp = C.POINTER(C.c_double)
+    abi.check(abi.load_hip_lib().nrays_debug_ray_order(scene.device_handle(), n, o.ctypes.data_as(dp), d.ctypes.data_as(dp), keys.ctypes.data_as(C.POINTER(C.c_uint64)),
+                                                       order.ctypes.data_as(C.POINTER(C.c_uint32)), frame.ctypes.data_as(dp), info))
+    return keys, order, frame, (int(info[0]), int(info[1]), bool(info[2]))
 
 
 _U64 = (1 << 64) - 1

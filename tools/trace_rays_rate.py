@@ -5,11 +5,19 @@
   (b) the same rays shuffled (incoherent order)
   (c) sponza stand-in 1080p camera rays, then AO-style cosine-weighted rays from their first hits (normal side, 1e-3 off the surface),
       timed as one batch (camera + AO) and the AO rays alone
+  (d) the sponza camera rays shuffled, the AO rays shuffled
 
 Each batch and each frame: warm-up, then 20 launches timed by HIP events around all of them.  The render's value_traced is bench.py's
 figure (rays that went through a BVT query per second, from an instrumented frame counted as the timed kernel traces).
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick]
+Every batch is timed as it comes ("ms") and with the caller's hint that it comes in no useful order ("hinted_ms": unordered=True, the
+library bins the rays by a spatial key first; left out when the library under NRAYS_HIP_LIB is older than the hint).  --coherence adds two
+CPU figures per batch and order (as given / in the order the reorder probe returns): "tiles_per_wave", the mean number of distinct
+8 x 8-pixel tiles the 64 consecutive rays of a wave come from (an AO ray counts for the pixel whose camera ray spawned it), and
+"one_octant_waves", the share of waves whose 64 rays share their direction signs.  --sweep times the shuffled camera rays of both scenes
+for n = 2^10 .. 2^22 hinted and unhinted with every hinted batch reordered (NRAYS_RAY_REORDER=2): the threshold of DESIGN §5b.
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep]
 """
 import argparse
 import ctypes as C
@@ -39,13 +47,54 @@ def _time(fn, reps, warmup=3):
     return e0.elapsed_time(e1) / reps  # ms per launch
 
 
-def _batch(sc, o, d, reps, keys=None):
+def _has_hint():
+    from nrays_amd import abi
+    return hasattr(abi.load_hip_lib(), "nrays_trace_rays_device_ex")
+
+
+def _coherence(pix, d, width, order=None):
+    """(tiles per wave, share of one-octant waves) of the rays in `order` (None: as given); pix = the pixel a ray belongs to."""
+    idx = np.arange(len(pix)) if order is None else np.asarray(order, dtype=np.int64)
+    n = len(idx) // 64 * 64
+    if n == 0:
+        return None
+    p = np.asarray(pix, dtype=np.int64)[idx[:n]]
+    tile = (p // width // 8) * ((width + 7) // 8) + (p % width) // 8
+    t = np.sort(tile.reshape(-1, 64), axis=1)
+    tiles = float((1 + (np.diff(t, axis=1) != 0).sum(axis=1)).mean())
+    sign = np.signbit(d[idx[:n]])
+    octant = (sign[:, 0] * 1 + sign[:, 1] * 2 + sign[:, 2] * 4).reshape(-1, 64)
+    return {"tiles_per_wave": round(tiles, 2), "one_octant_waves": round(float((octant.min(axis=1) == octant.max(axis=1)).mean()), 4)}
+
+
+def _batch(sc, o, d, reps, keys=None, pix=None, width=0):
     import torch
     import nrays_amd as nr
-    to, td = torch.from_numpy(np.ascontiguousarray(o)).cuda(), torch.from_numpy(np.ascontiguousarray(d)).cuda()
+    o, d = np.ascontiguousarray(o), np.ascontiguousarray(d)
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
     tk = None if keys is None else torch.from_numpy(keys.astype(np.int64)).cuda()
     ms = _time(lambda: nr.trace_rays(sc, to, td, keys=tk), reps)
-    return {"rays": int(len(o)), "ms": round(ms, 4), "mrays_per_s": round(len(o) / (ms * 1e-3) / 1e6, 2)}
+    out = {"rays": int(len(o)), "ms": round(ms, 4), "mrays_per_s": round(len(o) / (ms * 1e-3) / 1e6, 2)}
+    if _has_hint():
+        hms = _time(lambda: nr.trace_rays(sc, to, td, keys=tk, unordered=True), reps)
+        out.update(hinted_ms=round(hms, 4), hinted_mrays_per_s=round(len(o) / (hms * 1e-3) / 1e6, 2))
+    if pix is not None:
+        out["as_given"] = _coherence(pix, d, width)
+        if _has_hint() and len(o) <= 1 << 22:
+            out["reordered"] = _coherence(pix, d, width, nr.ray_order(sc, o, d)[1])
+    return out
+
+
+def _sweep(sc, o, d, k, reps):
+    """Shuffled camera rays, the first n of them: unhinted and hinted ms for n = 2^10 .. 2^22 (every hinted batch reordered)."""
+    rows = []
+    for lg in range(10, 23):
+        n = min(1 << lg, len(o))
+        r = _batch(sc, o[:n], d[:n], reps, k[:n])
+        rows.append({"n": n, "ms": r["ms"], "hinted_ms": r.get("hinted_ms")})
+        if n == len(o):
+            break
+    return rows
 
 
 def _render(sc, p, reps):
@@ -65,7 +114,8 @@ def _render(sc, p, reps):
 
 
 def _first_hits(sc, o, d):
-    """Closest hits of the camera rays (nrays_debug_cast_batch mode 0, blocking): AO rays from each hit, cosine-weighted about the normal."""
+    """Closest hits of the camera rays (nrays_debug_cast_batch mode 0, blocking): AO rays from each hit, cosine-weighted about the normal,
+    and the index of the camera ray each came from."""
     from nrays_amd import abi
     n = len(o)
     res = np.zeros(n, dtype=CAST_DTYPE)
@@ -86,7 +136,7 @@ def _first_hits(sc, o, d):
     b = np.cross(nrm, t)
     dirs = local[:, 0:1] * t + local[:, 1:2] * b + local[:, 2:3] * nrm
     dirs /= np.linalg.norm(dirs, axis=1)[:, None]
-    return pt + nrm * 1e-3, dirs
+    return pt + nrm * 1e-3, dirs, np.nonzero(hit)[0]
 
 
 def main():
@@ -94,7 +144,11 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trace_rays_rate.json"))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="320x180 instead of 1920x1080 (a rehearsal of the tool, not a measurement)")
+    ap.add_argument("--coherence", action="store_true", help="add the CPU coherence figures of every batch, as given and reordered")
+    ap.add_argument("--sweep", action="store_true", help="time the shuffled camera rays for n = 2^10 .. 2^22 with every hinted batch reordered, nothing else")
     a = ap.parse_args()
+    if a.sweep:
+        os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
     import nrays_amd as nr
     from nrays_amd import math3d
@@ -103,26 +157,38 @@ def main():
     assert torch.cuda.is_available(), "the rate tool measures the GPU; there is nothing to measure without one"
     torch.cuda.set_device(0)
     w, h = (320, 180) if a.quick else (1920, 1080)
-    res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0), "workloads": {}}
+    res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
+           "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
 
     sc, cam = su.balls_scene()
     proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
     o, d, k = nr.camera_rays((w, h), cam["eye"], proj)
-    res["workloads"]["a_balls_image_order"] = _batch(sc, o, d, a.reps, k)
     perm = np.random.default_rng(1).permutation(len(o))
-    res["workloads"]["b_balls_shuffled"] = _batch(sc, o[perm], d[perm], a.reps, k[perm])
-    res["workloads"]["balls_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
+    pix = np.arange(len(o)) if a.coherence else None
+    coh = lambda p: dict(pix=p, width=w) if a.coherence else {}  # noqa: E731
+    if a.sweep:
+        res["sweep"] = {"balls_shuffled": _sweep(sc, o[perm], d[perm], k[perm], a.reps)}
+    else:
+        res["workloads"]["a_balls_image_order"] = _batch(sc, o, d, a.reps, k, **coh(pix))
+        res["workloads"]["b_balls_shuffled"] = _batch(sc, o[perm], d[perm], a.reps, k[perm], **coh(perm))
+        res["workloads"]["balls_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
     del sc
 
     sc, cam = standins.sponza_scene()
     proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
     o, d, k = nr.camera_rays((w, h), cam["eye"], proj)
-    ao_o, ao_d = _first_hits(sc, o, d)
-    res["workloads"]["c_sponza_camera_plus_ao"] = dict(_batch(sc, np.concatenate([o, ao_o]), np.concatenate([d, ao_d]), a.reps),
-                                                       camera_rays=int(len(o)), ao_rays=int(len(ao_o)))
-    res["workloads"]["c_sponza_camera_only"] = _batch(sc, o, d, a.reps, k)
-    res["workloads"]["c_sponza_ao_only"] = _batch(sc, ao_o, ao_d, a.reps)
-    res["workloads"]["sponza_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
+    if a.sweep:
+        res["sweep"]["sponza_shuffled"] = _sweep(sc, o[perm], d[perm], k[perm], a.reps)
+    else:
+        ao_o, ao_d, ao_pix = _first_hits(sc, o, d)
+        ao_perm = np.random.default_rng(2).permutation(len(ao_o))
+        res["workloads"]["c_sponza_camera_plus_ao"] = dict(_batch(sc, np.concatenate([o, ao_o]), np.concatenate([d, ao_d]), a.reps, **coh(np.concatenate([np.arange(len(o)), ao_pix]))),
+                                                           camera_rays=int(len(o)), ao_rays=int(len(ao_o)))
+        res["workloads"]["c_sponza_camera_only"] = _batch(sc, o, d, a.reps, k, **coh(pix))
+        res["workloads"]["c_sponza_ao_only"] = _batch(sc, ao_o, ao_d, a.reps, **coh(ao_pix))
+        res["workloads"]["d_sponza_camera_shuffled"] = _batch(sc, o[perm], d[perm], a.reps, k[perm], **coh(perm))
+        res["workloads"]["d_sponza_ao_shuffled"] = _batch(sc, ao_o[ao_perm], ao_d[ao_perm], a.reps, **coh(ao_pix[ao_perm]))
+        res["workloads"]["sponza_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
