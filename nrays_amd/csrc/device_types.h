@@ -231,7 +231,7 @@ struct DRender {
     uint32_t lane_log2;          // log2 of the lanes that share one pixel (sample-major mapping of AA frames; 0 = one lane per pixel)
     // Pixels outside [cull_i0, cull_i1] x [cull_j0, cull_j1] (global column / row) cannot reach the scene's bounding box
     // with any of their primary rays: a wave tile without a pixel inside writes the background without generating a ray
-    // (nrays_hip.hip: screen_bounds()).  INT_MIN / INT_MAX = every pixel may hit (camera inside the box, planes, ...).
+    // (frame_path.hip: screen_bounds()).  INT_MIN / INT_MAX = every pixel may hit (camera inside the box, planes, ...).
     int32_t cull_i0, cull_i1, cull_j0, cull_j1;
     // The same bounds in units of scheduling blocks (16 x 16 pixels at one lane per pixel, the wave's pixel block of an
     // anti-aliased frame), local rows: only the blocks [win_x0, win_x0 + win_nx) x [win_y0, win_y0 + win_ny) enter the
@@ -267,7 +267,7 @@ struct DRender {
     const uint32_t* order_len;
     uint32_t light_lsl;
     // 1: this launch writes the window's pixels only — the rows and columns outside the window are somebody else's (the trace half of a
-    // pipelined frame, nrays_hip.hip: render_impl; k_compose writes them).  k_primary only.
+    // pipelined frame, frame_path.hip: pipeline_prepare; k_compose writes them).  k_primary only.
     uint32_t no_rows;
 };
 constexpr uint32_t kEntrySplit = 0x80000000u, kEntryTileMask = 0x0fffffffu;

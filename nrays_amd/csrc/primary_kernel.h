@@ -1,7 +1,7 @@
 // primary_kernel.h — k_primary, the persistent-grid megakernel of the trace loop (replaces the pixel loop of scene::render,
-// src/scene.rs:49-116), with the helpers it shares with k_bounce / k_cast_batch (nrays_hip.hip).  Device code only: the
+// src/scene.rs:49-116), with the helpers it shares with k_bounce (bounce.hip) and the caller-ray kernels (ray_order.hip).  Device code only: the
 // permutations are instantiated by primary_inst.hip, one translation unit per group (NR_PRIMARY_GROUP), so that the ~57
-// kernels compile side by side; nrays_hip.hip holds the host side and the small kernels.
+// kernels compile side by side; frame_path.hip holds the host side and the small kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -122,7 +122,7 @@ constexpr int waves_per_simd(int feat) { return (feat & ~(kFeatMultiSample | kFe
 
 // OCC != 0: the alpha-shadow mesh permutations also exist at three waves per SIMD (168 VGPRs, ~64 dwords of scratch per lane): a
 // wave then runs slower, which lengthens a frame that is as long as its longest tile (sponza 1080p: 1.40 -> 1.67 ms) and shortens a
-// frame that is bound by the sum of its tiles (sponza 4K: 4.12 -> 3.65 ms, config 4: 14.6 -> 12.5 ms) — render_impl chooses per frame.
+// frame that is bound by the sum of its tiles (sponza 4K: 4.12 -> 3.65 ms, config 4: 14.6 -> 12.5 ms) — plan_frame (frame_path.hip) chooses per frame.
 #ifndef NR_PIXEL_SPLIT
 #define NR_PIXEL_SPLIT 1 // long tiles of one-light alpha-mapped mesh frames are split by pixels (the light-parallel machinery with one light)
 #endif
@@ -172,22 +172,15 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
     }
     constexpr bool kPark = (FEAT & kFeatPark) != 0;
     __shared__ uint32_t lds_park[kPark ? park_slots(FEAT) * kBlock : 4];
-    Stack st;
-    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-    st.spill_stride = gridDim.x * kBlock;
-    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-    st.lds0 = Stack::addr((lds_u32*)lds_stack);
-    st.park = (lds_u32*)(lds_park + threadIdx.x);
-    st.init();
+    Stack st; st.setup(lds_stack, spill, (lds_u32*)(lds_park + threadIdx.x));
     // a launch that records its tile costs also records itself (DRender::cost_meta): its first wave brackets its lifetime with both clocks, every wave leaves its end tick
     // The instrumented kernel also measures the shader clock (DRender::cost_meta): the first wave of every 32nd workgroup brackets its lifetime with both clocks.  Not the
     // plain kernels: every wave doing so in a cost-recording launch (three atomics each on one line) cost the balls frame 0.062 -> 0.10 ms, and even the sampled form's code
     // 0.5 - 1 % of the analytic kernels' steady frames.
     __shared__ uint32_t clk_start[STATS ? 2 : 1];
     if (STATS && R.cost_meta && (blockIdx.x & 31u) == 0u && threadIdx.x == 0u) { clk_start[0] = (uint32_t)__builtin_readcyclecounter(); clk_start[1] = (uint32_t)__builtin_amdgcn_s_memrealtime(); }
-    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
+    Cnt cnt; cnt.zero();
 #ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
     unsigned long long twave = __builtin_readcyclecounter();
 #endif
 
@@ -473,7 +466,7 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
 // ---------------------------------------------------------------------------------------------------------------------
 // The permutations of k_primary and the translation units that hold them.  X(group, STATS, FEAT, PLAIN, OCC); FEAT is a
 // sum of device_types.h: Features bits.  primary_inst.hip is compiled once per group (-DNR_PRIMARY_GROUP=g) and defines
-// launch_primary_group<g>(); nrays_hip.hip: launch_primary() names the permutation a frame wants and asks the groups in
+// launch_primary_group<g>(); frame_path.hip: launch_primary() names the permutation a frame wants and asks the groups in
 // turn.  A tuning build (-DNR_ONLY=33 or -DNR_ONLY=6,70,...: the FEAT codes an A/B run touches, tools/build_variant.sh)
 // compiles only those permutations + the two full kernels; every other frame then renders with the full kernel — same
 // pixels, slower.

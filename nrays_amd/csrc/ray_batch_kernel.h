@@ -1,6 +1,6 @@
 // ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*): k_trace_rays and
-// k_intersects_rays trace ray j of a chunk in lane j (nrays_hip.hip launches them); their _ordered forms trace ray order[j] there and
-// write its result to ITS slot (ray_order.hip holds them: a batch the caller called unordered, binned by ray_key.h's key).  One body
+// k_intersects_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
+// write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  Device code only.
 #pragma once
 #include "primary_kernel.h"
@@ -19,17 +19,8 @@ __device__ __forceinline__ void trace_rays_body(uint32_t* lds_stack, const DScen
                                                 const double* __restrict__ rd, const double* __restrict__ refr, const float* __restrict__ energy,
                                                 const unsigned long long* __restrict__ keys, unsigned long long key_base, uint32_t keyed,
                                                 uint32_t max_depth, float* __restrict__ out, QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
-    Stack st;
-    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-    st.spill_stride = gridDim.x * kBlock;
-    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-    st.lds0 = Stack::addr((lds_u32*)lds_stack);
-    st.park = nullptr;
-    st.init();
-    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
-#ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
-#endif
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
         const uint32_t slot = base + threadIdx.x;
         const bool active = slot < n;
@@ -72,17 +63,8 @@ template <int FEAT, bool ORDERED>
 __device__ __forceinline__ void intersects_rays_body(uint32_t* lds_stack, const DScene& S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
                                                      const double* __restrict__ rd, const double* __restrict__ max_toi, float* __restrict__ out_filter,
                                                      uint32_t* __restrict__ out_lit, uint32_t* spill) {
-    Stack st;
-    st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-    st.spill_stride = gridDim.x * kBlock;
-    st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-    st.lds0 = Stack::addr((lds_u32*)lds_stack);
-    st.park = nullptr;
-    st.init();
-    Cnt cnt; cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
-#ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
-#endif
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
         const uint32_t slot = base + threadIdx.x;
         if (slot >= n) continue;

@@ -1,4 +1,5 @@
-// ray_order.hip — caller-ray batches that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_debug_cast_batch; host side below the kernels), and
+// first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
 // of 64 unrelated rays gets none of it.
@@ -18,12 +19,15 @@
 // DESIGN §5 "Scheduling").
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <new>
 #include <string>
 
 #include "../../include/nrays_abi.h"
+#include "bounce.h"
 #include "ray_batch_kernel.h"
 #include "ray_key.h"
-#include "ray_order.h"
+#include "scene_handle.h"
 
 static_assert(NRAYS_RAY_FRAME_DOUBLES == nrays::kRayFrameDoubles, "include/nrays_abi.h and ray_key.h disagree on the frame");
 
@@ -159,19 +163,13 @@ __global__ void __launch_bounds__(kOrderBlock) k_ray_place(uint32_t n, const uin
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
-#define RO_TRY(expr)                                                                                                                          \
-    do {                                                                                                                                      \
-        hipError_t e_ = (expr);                                                                                                               \
-        if (e_ != hipSuccess) return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static void free_per_ray(TraceWorkspace* w) {
     if (w->d_ray_keys) (void)hipFree(w->d_ray_keys);
     if (w->d_ray_rank) (void)hipFree(w->d_ray_rank);
     if (w->d_ray_order) (void)hipFree(w->d_ray_order);
     w->d_ray_keys = nullptr; w->d_ray_rank = nullptr; w->d_ray_order = nullptr; w->order_rays = 0;
 }
-void ray_order_release(TraceWorkspace* w) {
+static void ray_order_release(TraceWorkspace* w) {
     free_per_ray(w);
     if (w->d_ray_frame) (void)hipFree(w->d_ray_frame);
     if (w->d_ray_partial) (void)hipFree(w->d_ray_partial);
@@ -179,29 +177,33 @@ void ray_order_release(TraceWorkspace* w) {
     if (w->d_ray_scan) (void)hipFree(w->d_ray_scan);
     w->d_ray_frame = nullptr; w->d_ray_partial = nullptr; w->d_ray_bins = nullptr; w->d_ray_scan = nullptr;
 }
-int ray_order_ensure(TraceWorkspace* w, uint32_t n) {
+// Grows the reorder buffers of `w` to n rays (n <= kTraceChunk).  NRAYS_OK or a negative status with the last error set.
+static int ray_order_ensure(TraceWorkspace* w, uint32_t n) {
     if (n > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_order_ensure: more rays than a chunk");
-    if (!w->d_ray_frame) RO_TRY(hipMalloc((void**)&w->d_ray_frame, kRayFrameDoubles * sizeof(double)));
-    if (!w->d_ray_partial) RO_TRY(hipMalloc((void**)&w->d_ray_partial, (size_t)kBoundsMaxGrid * 10 * sizeof(double)));
-    if (!w->d_ray_bins) RO_TRY(hipMalloc((void**)&w->d_ray_bins, (size_t)kNumBins * sizeof(uint32_t)));
-    if (!w->d_ray_scan) RO_TRY(hipMalloc((void**)&w->d_ray_scan, (size_t)((kNumBins + kScanBlock - 1u) / kScanBlock) * sizeof(uint32_t)));
+    if (!w->d_ray_frame) HIP_TRY(hipMalloc((void**)&w->d_ray_frame, kRayFrameDoubles * sizeof(double)));
+    if (!w->d_ray_partial) HIP_TRY(hipMalloc((void**)&w->d_ray_partial, (size_t)kBoundsMaxGrid * 10 * sizeof(double)));
+    if (!w->d_ray_bins) HIP_TRY(hipMalloc((void**)&w->d_ray_bins, (size_t)kNumBins * sizeof(uint32_t)));
+    if (!w->d_ray_scan) HIP_TRY(hipMalloc((void**)&w->d_ray_scan, (size_t)((kNumBins + kScanBlock - 1u) / kScanBlock) * sizeof(uint32_t)));
     if (n > w->order_rays) {
         free_per_ray(w);
-        RO_TRY(hipMalloc((void**)&w->d_ray_keys, (size_t)n * sizeof(uint64_t)));
-        RO_TRY(hipMalloc((void**)&w->d_ray_rank, (size_t)n * sizeof(uint32_t)));
-        RO_TRY(hipMalloc((void**)&w->d_ray_order, (size_t)n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&w->d_ray_keys, (size_t)n * sizeof(uint64_t)));
+        HIP_TRY(hipMalloc((void**)&w->d_ray_rank, (size_t)n * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc((void**)&w->d_ray_order, (size_t)n * sizeof(uint32_t)));
         w->order_rays = n;
     }
     return NRAYS_OK;
 }
 
-int ray_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* origins, const double* dirs, hipStream_t stream) {
+// Enqueues the reorder of one chunk (device pointers) on `stream`: frame reduction, keys + bin counts, prefix sum, placement.  Launches only —
+// nothing is read back and nothing waits.  Afterwards (in stream order) w->d_ray_order[j] = the ray to trace j-th, w->d_ray_keys / d_ray_frame
+// hold the keys and the frame.
+static int ray_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* origins, const double* dirs, hipStream_t stream) {
     if (n == 0u || n > w->order_rays) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_order_chunk: workspace too small");
     SceneBox box;
     for (int a = 0; a < 3; ++a) { box.v[a] = (double)sc->host.bounds_mn[a]; box.v[3 + a] = (double)sc->host.bounds_mx[a]; }
     const uint32_t ray_grid = (n + kOrderBlock - 1u) / kOrderBlock, parts = ray_grid < kBoundsMaxGrid ? ray_grid : kBoundsMaxGrid;
     const uint32_t scan_grid = (kNumBins + kScanBlock - 1u) / kScanBlock;
-    RO_TRY(hipMemsetAsync(w->d_ray_bins, 0, (size_t)kNumBins * sizeof(uint32_t), stream));
+    HIP_TRY(hipMemsetAsync(w->d_ray_bins, 0, (size_t)kNumBins * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(k_ray_bounds, dim3(parts), dim3(kOrderBlock), 0, stream, n, origins, dirs, box, w->d_ray_partial);
     hipLaunchKernelGGL(k_ray_frame, dim3(1), dim3(kOrderBlock), 0, stream, (const double*)w->d_ray_partial, parts, box, w->d_ray_frame);
     hipLaunchKernelGGL(k_ray_keys, dim3(ray_grid), dim3(kOrderBlock), 0, stream, n, origins, dirs, (const double*)w->d_ray_frame, w->d_ray_keys, w->d_ray_bins, w->d_ray_rank);
@@ -209,21 +211,321 @@ int ray_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t n, const d
     hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream, w->d_ray_scan, scan_grid);
     hipLaunchKernelGGL(k_bin_apply, dim3(scan_grid), dim3(kOrderBlock), 0, stream, w->d_ray_bins, kNumBins, (const uint32_t*)w->d_ray_scan);
     hipLaunchKernelGGL(k_ray_place, dim3(ray_grid), dim3(kOrderBlock), 0, stream, n, (const uint64_t*)w->d_ray_keys, (const uint32_t*)w->d_ray_rank, (const uint32_t*)w->d_ray_bins, w->d_ray_order);
-    RO_TRY(hipGetLastError());
+    HIP_TRY(hipGetLastError());
     return NRAYS_OK;
 }
 
-void launch_trace_rays_ordered(bool stats, int feat, uint32_t grid, hipStream_t stream, const DScene& S, uint32_t n, const uint32_t* order, const double* ro, const double* rd,
-                               const double* refr, const float* energy, const unsigned long long* keys, unsigned long long key_base, uint32_t keyed, uint32_t max_depth,
-                               float* out, const QueueOut& qo, DeviceCounters* ctr, uint32_t* spill) {
-    if (stats) hipLaunchKernelGGL((k_trace_rays_ordered<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, S, n, order, ro, rd, refr, energy, keys, key_base, keyed, max_depth, out, qo, ctr, spill);
-    else if (feat == (int)kFeatMesh) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, S, n, order, ro, rd, refr, energy, keys, key_base, keyed, max_depth, out, qo, ctr, spill);
-    else hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, S, n, order, ro, rd, refr, energy, keys, key_base, keyed, max_depth, out, qo, ctr, spill);
+// (FEAT: kFeatAll, or kFeatMesh for scenes of opaque TriMesh nodes only — the permutation whose node phases end by quorum in
+// hair-like meshes, so that the independent fixtures also cover that path.)
+// nrays_debug_cast_batch: the closest-hit query with the deferred exact gates exactly as shade_hit runs it (ungated traversal, the
+// winner checked against the reference's AABB gates, fully gated repeat for knife-edge rays), or the shadow query, on rays from memory.
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DScene S, uint32_t mode, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                              const double* __restrict__ max_toi, NraysCastResult* __restrict__ out, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const d3 o = D3(ro[3 * (size_t)i], ro[3 * (size_t)i + 1], ro[3 * (size_t)i + 2]), d = D3(rd[3 * (size_t)i], rd[3 * (size_t)i + 1], rd[3 * (size_t)i + 2]);
+        NraysCastResult r; r.toi = 0.0; r.normal[0] = r.normal[1] = r.normal[2] = 0.0; r.uv[0] = r.uv[1] = 0.0; r.node_id = -1; r.flags = 0u;
+        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+        if (mode == 1u) {
+            const bool blocked = traverse<true, false, FEAT>(S, st, o, d, max_toi[i], hit, filter, cnt);
+            r.flags = blocked ? 1u : 0u; r.normal[0] = filter.x; r.normal[1] = filter.y; r.normal[2] = filter.z;
+        } else {
+            Isect is; uint32_t node_id = 0; bool gated = false, any = false;
+            for (;;) {
+                any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
+                if (!any) break;
+                if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
+                gated = true;
+            }
+            if (any) {
+                r.toi = hit.t; r.normal[0] = is.n.x; r.normal[1] = is.n.y; r.normal[2] = is.n.z; r.uv[0] = is.u; r.uv[1] = is.v;
+                r.node_id = (int32_t)node_id; r.flags = 1u | (is.has_uv ? 2u : 0u);
+            }
+        }
+        out[i] = r;
+    }
 }
-void launch_intersects_rays_ordered(int feat, uint32_t grid, hipStream_t stream, const DScene& S, uint32_t n, const uint32_t* order, const double* ro, const double* rd,
-                                    const double* max_toi, float* out_filter, uint32_t* out_lit, uint32_t* spill) {
-    if (feat == (int)kFeatMesh) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, S, n, order, ro, rd, max_toi, out_filter, out_lit, spill);
-    else hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, S, n, order, ro, rd, max_toi, out_filter, out_lit, spill);
+
+// ---- caller-ray batches: nrays_trace_rays*, nrays_intersects_rays_device (Scene::trace / Scene::intersects_ray, scene.rs:147-193) ----------------
+static int trace_workspace(NraysScene* sc, TraceWorkspace** out) {
+    if (!sc->tw) {
+        sc->tw = new (std::nothrow) TraceWorkspace();
+        if (!sc->tw) return set_last_error(NRAYS_ERR_OOM, "trace workspace");
+    }
+    TraceWorkspace* w = sc->tw;
+    if (!w->d_counts) HIP_TRY(hipMalloc((void**)&w->d_counts, kTraceCountWords * sizeof(uint32_t)));
+    if (!w->d_counters) HIP_TRY(hipMalloc((void**)&w->d_counters, sizeof(DeviceCounters)));
+    { const int rs = ensure_spill(sc, &w->d_spill); if (rs != NRAYS_OK) return rs; }
+    *out = w;
+    return NRAYS_OK;
+}
+void trace_workspace_release(NraysScene* sc) {
+    TraceWorkspace* w = sc->tw;
+    if (!w) return;
+    if (w->used) (void)hipStreamSynchronize(w->last_stream);
+    for (int k = 0; k < 2; ++k) if (w->queue[k].block) (void)hipFree(w->queue[k].block);
+    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage}) if (q) (void)hipFree(q);
+    ray_order_release(w);
+    delete w;
+    sc->tw = nullptr;
+}
+// The handle's threading contract: a batch on another stream than the handle's previous work (its last render, its last batch) is
+// ordered behind it, and a render that follows on yet another stream is ordered behind the batch (frame_path.hip: order_behind_previous waits on ev_switch
+// recorded on sc->last_stream when last_timed is false).  Nothing a render reports (counters, timings, tile costs) is touched.
+static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
+    const hipStream_t prev[2] = {sc->have_last ? sc->last_stream : stream, w->used ? w->last_stream : stream};
+    for (int k = 0; k < 2; ++k) {
+        if (prev[k] == stream || (k == 1 && prev[1] == prev[0])) continue;
+        const int rc = order_behind_stream(sc, prev[k], stream);
+        if (rc != NRAYS_OK) return rc;
+    }
+    return NRAYS_OK;
+}
+static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
+    w->last_stream = stream; w->used = true;
+    if (sc->have_last) { sc->last_stream = stream; sc->last_timed = false; sc->last_pipelined = false; }
+}
+// Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
+static bool batch_mesh_only(const NraysScene* sc) { return (sc->features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
+
+// A batch the caller called unordered (NRAYS_RAYS_UNORDERED) is reordered when the host can see that it pays: the reorder is eight launches in
+// front of the trace (a launch of a handle has a period of ~11 us), which a small batch does not earn back.  kReorderMinRays: DESIGN §5b.
+constexpr uint32_t kReorderMinRays = 1u << 19;
+static bool reorder_pays(const NraysScene* sc, uint32_t n) { return sc->ray_reorder == 2 || (sc->ray_reorder != 0 && n >= kReorderMinRays); }
+static int check_ray_flags(uint32_t flags) { return (flags & ~(uint32_t)NRAYS_RAYS_UNORDERED) ? set_last_error(NRAYS_ERR_BAD_ARG, "unknown ray-batch flag") : NRAYS_OK; }
+// The reorder of one chunk (ray_order.hip) when it is due: *order = the order to trace in, or nullptr (trace the rays as they come).
+static int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, const double* o, const double* d, hipStream_t stream, const uint32_t** order) {
+    *order = nullptr;
+    if (!reorder) return NRAYS_OK;
+    int rc = ray_order_ensure(w, n);
+    if (rc == NRAYS_OK) rc = ray_order_chunk(sc, w, n, o, d, stream);
+    if (rc == NRAYS_OK) *order = w->d_ray_order;
+    return rc;
+}
+
+// One chunk (n <= kTraceChunk) of nrays_trace_rays_device: k_trace_rays (`order`: its ordered form, lane j traces ray order[j]), then — double-branching scenes only — the k_bounce rounds of the
+// queued second children and k_fold_fixed, as a frame runs them for a sample batch (bounce.h: run_bounce_rounds).
+static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
+                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream, const uint32_t* order) {
+    const bool queued = sc->host.any_double_branch;
+    if (queued) { // a frame's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
+        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
+        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, (size_t)n * 3, stream);
+        if (rc != NRAYS_OK) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
+    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
+    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
+    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const uint32_t keyed = sc->host.any_area_light ? 1u : 0u;
+    // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
+    if (order && sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays_ordered<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (order && batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (order) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else hipLaunchKernelGGL((k_trace_rays<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    HIP_TRY(hipGetLastError());
+    if (!queued) return NRAYS_OK;
+    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->d, sc->d.no_elide != 0u, max_depth, out, (size_t)n * 3, sc->num_cus};
+    uint32_t overflowed = 0u;
+    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
+    if (rc != NRAYS_OK) return rc;
+    if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some traced colours are incomplete");
+    return NRAYS_OK;
+}
+
+static int trace_rays_device_impl(NraysScene* sc, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
+                                  const uint64_t* keys, uint32_t max_depth, float* out, uint32_t flags, hipStream_t stream) {
+    if (!sc || !o || !d || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, o + 3 * (size_t)c0, d + 3 * (size_t)c0, stream, &order);
+        if (rc != NRAYS_OK) break;
+        rc = trace_chunk(sc, w, nc, o + 3 * (size_t)c0, d + 3 * (size_t)c0, refr ? refr + c0 : nullptr, energy ? energy + c0 : nullptr,
+                         keys ? (const unsigned long long*)keys + c0 : nullptr, (unsigned long long)c0, max_depth, out + 3 * (size_t)c0, stream, order);
+    }
+    batch_end(sc, w, stream);
+    return rc;
 }
 
 } // namespace nrays
+
+using namespace nrays;
+
+extern "C" {
+
+int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* max_toi, NraysCastResult* out) {
+    if (!sc || !origins || !dirs || !out || mode > 1u || (mode == 1u && !max_toi)) return set_last_error(NRAYS_ERR_BAD_ARG, "bad cast-batch arguments");
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    if (sc->have_last) HIP_TRY(hipStreamSynchronize(sc->last_stream));
+    { const int rs = ensure_spill(sc, &sc->d_spill); if (rs != NRAYS_OK) return rs; }
+    double *d_o = nullptr, *d_d = nullptr, *d_t = nullptr; NraysCastResult* d_r = nullptr;
+    auto release = [&]() { if (d_o) (void)hipFree(d_o); if (d_d) (void)hipFree(d_d); if (d_t) (void)hipFree(d_t); if (d_r) (void)hipFree(d_r); };
+#define CAST_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    const size_t vb = (size_t)n * 3 * sizeof(double);
+    CAST_TRY(hipMalloc((void**)&d_o, vb)); CAST_TRY(hipMalloc((void**)&d_d, vb)); CAST_TRY(hipMalloc((void**)&d_r, (size_t)n * sizeof(NraysCastResult)));
+    CAST_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CAST_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
+    if (mode == 1u) { CAST_TRY(hipMalloc((void**)&d_t, (size_t)n * sizeof(double))); CAST_TRY(hipMemcpy(d_t, max_toi, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
+    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    CAST_TRY(sc->own_stream ? hipSuccess : hipStreamCreate(&sc->own_stream));
+    if ((sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
+    else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
+    CAST_TRY(hipGetLastError());
+    CAST_TRY(hipStreamSynchronize(sc->own_stream));
+    CAST_TRY(hipMemcpy(out, d_r, (size_t)n * sizeof(NraysCastResult), hipMemcpyDeviceToHost));
+#undef CAST_TRY
+    release();
+    return NRAYS_OK;
+}
+
+int nrays_trace_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                            uint32_t max_depth, float* out_rgb, void* hip_stream) {
+    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u, (hipStream_t)hip_stream);
+}
+int nrays_trace_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                               uint32_t max_depth, float* out_rgb, uint32_t flags, void* hip_stream) {
+    return trace_rays_device_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags, (hipStream_t)hip_stream);
+}
+
+static int trace_rays_host_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                                uint32_t max_depth, float* out_rgb, uint32_t flags) {
+    if (!sc || !origins || !dirs || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    // device copies of one chunk's arrays: origins, directions (3 f64), refr (f64), keys (u64), energy (f32), colours (3 f32) — 80 bytes a ray
+    rc = grow_device(&w->d_stage, &w->stage_rays, std::min<uint32_t>(n, kTraceChunk), 80);
+    if (rc != NRAYS_OK) return rc;
+    const size_t cap = w->stage_rays;
+    double* s_o = (double*)w->d_stage; double* s_d = s_o + 3 * cap; double* s_r = s_d + 3 * cap;
+    unsigned long long* s_k = (unsigned long long*)(s_r + cap); float* s_e = (float*)(s_k + cap); float* s_out = s_e + cap;
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        auto up = [&](void* dst, const void* src, size_t bytes) { return hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream); };
+        hipError_t e = up(s_o, origins + 3 * (size_t)c0, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_d, dirs + 3 * (size_t)c0, (size_t)nc * 24);
+        if (e == hipSuccess && refr) e = up(s_r, refr + c0, (size_t)nc * 8);
+        if (e == hipSuccess && keys) e = up(s_k, keys + c0, (size_t)nc * 8);
+        if (e == hipSuccess && energy) e = up(s_e, energy + c0, (size_t)nc * 4);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("trace batch upload: ") + hipGetErrorString(e)); break; }
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, s_o, s_d, stream, &order);
+        if (rc != NRAYS_OK) break;
+        rc = trace_chunk(sc, w, nc, s_o, s_d, refr ? s_r : nullptr, energy ? s_e : nullptr, keys ? s_k : nullptr, (unsigned long long)c0, max_depth, s_out, stream, order);
+        if (rc == NRAYS_OK) {
+            e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_out, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("trace batch read-back: ") + hipGetErrorString(e));
+        }
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                     uint32_t max_depth, float* out_rgb) {
+    return trace_rays_host_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u);
+}
+int nrays_trace_rays_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                        uint32_t max_depth, float* out_rgb, uint32_t flags) {
+    return trace_rays_host_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags);
+}
+
+static int intersects_rays_device_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                       uint32_t* out_lit, uint32_t flags, void* hip_stream) {
+    if (!sc || !origins || !dirs || !max_toi || !out_filter || !out_lit) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool mesh = (sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    for (uint32_t c0 = 0; c0 < n; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit ray indices far from overflow)
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const double *o = origins + 3 * (size_t)c0, *d = dirs + 3 * (size_t)c0, *t = max_toi + c0;
+        const uint32_t* order = nullptr;
+        rc = chunk_order(sc, w, reorder, nc, o, d, stream, &order);
+        if (rc != NRAYS_OK) break;
+        if (order && mesh) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else if (order) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else hipLaunchKernelGGL((k_intersects_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e)); break; }
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                 uint32_t* out_lit, void* hip_stream) {
+    return intersects_rays_device_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, 0u, hip_stream);
+}
+int nrays_intersects_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                    uint32_t* out_lit, uint32_t flags, void* hip_stream) {
+    return intersects_rays_device_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, flags, hip_stream);
+}
+
+int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,
+                          uint32_t out_info[4]) {
+    if (!sc || !origins || !dirs || !out_keys || !out_order || !out_frame || !out_info) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_debug_ray_order: at most one chunk (2^22 rays)");
+    out_info[0] = (uint32_t)kRayKeyBits; out_info[1] = (uint32_t)kRayBinBits; out_info[2] = reorder_pays(sc, n) ? 1u : 0u; out_info[3] = 0u;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = ray_order_ensure(w, n);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->own_stream;
+    double* d_od = nullptr; // origins, then directions
+    HIP_TRY(hipMalloc((void**)&d_od, (size_t)n * 48));
+    rc = batch_begin(sc, w, stream);
+    hipError_t e = hipSuccess;
+    if (rc == NRAYS_OK) {
+        e = hipMemcpyAsync(d_od, origins, (size_t)n * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d_od + 3 * (size_t)n, dirs, (size_t)n * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) rc = ray_order_chunk(sc, w, n, d_od, d_od + 3 * (size_t)n, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_keys, w->d_ray_keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_order, w->d_ray_order, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_frame, w->d_ray_frame, NRAYS_RAY_FRAME_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = es;
+        batch_end(sc, w, stream);
+    }
+    (void)hipFree(d_od);
+    if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_ray_order: ") + hipGetErrorString(e));
+    return rc;
+}
+
+} // extern "C"

@@ -36,7 +36,7 @@ struct HostScene {
     std::vector<LightRec> lights;
     int32_t closest_root = kEmptyChild, shadow_root = kEmptyChild;
     float background[3] = {1.f, 1.f, 1.f};
-    // generation control (see nrays_hip.hip)
+    // generation control (see frame_path.hip)
     bool any_reflective = false;   // some node has refl_mix != 0 (scene.rs:204)
     bool any_transparent = false;  // some node can produce alpha != 1 (scene.rs:229)
     bool any_area_light = false;   // some light has radius != 0 (light.rs:60 consumes random numbers)

@@ -1,5 +1,6 @@
 // scene_handle.h — the scene handle behind the C ABI (NraysScene) and what the library's translation units share
-// around it.  Host only; nrays_hip.hip owns the megakernel path (k_primary), wavefront.hip the staged path.
+// around it.  Host only; frame_path.hip owns the megakernel path (k_primary), wavefront.hip the staged path, ray_order.hip the
+// caller-ray batches, nrays_hip.hip the handle's lifetime.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,19 +16,27 @@ namespace nrays {
 int set_last_error(int status, const std::string& msg); // nrays_hip.hip: sets nrays_last_error(), returns `status`
 struct WavefrontState;                                   // wavefront.hip: buffers of the staged path, created on first use
 
+// A failed HIP call ends the function: its status (out of memory told apart) and the call's text become the last error.
+#define HIP_TRY(expr)                                                                                                                  \
+    do {                                                                                                                               \
+        hipError_t e_ = (expr);                                                                                                        \
+        if (e_ != hipSuccess)                                                                                                          \
+            return nrays::set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
 struct QueueMem {
     RayQueue q;
     void* block = nullptr;
 };
 
-// A camera as the scheduler sees it (nrays_hip.hip: cam_snapshot): eye, unit rays through the four corners of the frame, the angle of a pixel,
+// A camera as the scheduler sees it (frame_path.hip: cam_snapshot): eye, unit rays through the four corners of the frame, the angle of a pixel,
 // the distance to the scene's bounding box.
 struct CamSnap { double eye[3] = {0, 0, 0}; double dir[4][3] = {}; double pix_angle = 0.0, depth = 1.0; bool valid = false; };
 
 constexpr int kNumCounts = kMaxGenerations + 2 + 8; // queue round counters + 8 per-XCD work counters
 constexpr int kMaxGrid = 2048;     // upper bound of the persistent grid (the launch uses CUs x waves/SIMD workgroups)
 
-// Workspace of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device; nrays_hip.hip): created on first use, grown
+// Workspace of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device; ray_order.hip): created on first use, grown
 // only when a chunk needs more, freed with the handle.  It shares no device memory with the renders, so that a batch leaves their
 // per-frame state (queues, counters, fixed-point sums, scheduling state) exactly as it found it.
 constexpr uint32_t kTraceChunk = 1u << 22; // rays per chunk of a batch: bounds the queues and sums below for any batch size
@@ -89,10 +98,10 @@ struct NraysScene {
     // analytic scenes (workgroup lists): costs are recorded on the first frame of a camera, sorted once on the second, and
     // the order is then reused as long as the camera stays (the scene of a handle never changes)
     uint64_t cost_cam = 0, order_key = 0, order_cam = 0; bool order_valid = false; uint32_t order_age = 0;
-    // ... and by cameras NEAR the one whose costs it was sorted from (nrays_hip.hip: cam_shift_px) for up to kMaxOrderAge frames, so that a moving camera does not
+    // ... and by cameras NEAR the one whose costs it was sorted from (frame_path.hip: cam_shift_px) for up to kMaxOrderAge frames, so that a moving camera does not
     // record and sort on every frame.  order_seeded: the order comes from k_seed_costs' guess, the next frame replaces it.
     nrays::CamSnap cost_snap, order_snap; bool order_seeded = false;
-    uint64_t host_times_from = 0;                   // NRAYS_HOST_TIMES=n: render_impl prints where the host time of the handle's frames n .. n + 3 goes (1: its first frames)
+    uint64_t host_times_from = 0;                   // NRAYS_HOST_TIMES=n: render_impl (frame_path.hip) prints where the host time of the handle's frames n .. n + 3 goes (1: its first frames)
     bool near_reuse = true;                         // NRAYS_NEAR_REUSE=0: only the very same camera reuses an order (A/B)
     double near_pixels = 16.0; uint32_t max_order_age = 8; // NRAYS_NEAR_PIXELS / NRAYS_ORDER_AGE
     float split_hyst = 0.5f;                        // NRAYS_SPLIT_HYST: a tile that ran in parts stays split down to this fraction of the split threshold (k_tile_order)
@@ -126,7 +135,7 @@ struct NraysScene {
     hipEvent_t last_done = nullptr; // last event recorded by the previous render (one of the ring's events)
     hipEvent_t ev_switch = nullptr; // recorded on the previous render's stream when a render arrives on another one
     bool have_last = false;
-    // Pipelined frames (nrays_hip.hip: render_impl): a frame enqueued while its predecessor is still in flight traces its window on one of up to three
+    // Pipelined frames (frame_path.hip: pipeline_prepare, pipeline_compose): a frame enqueued while its predecessor is still in flight traces its window on one of up to three
     // library-owned non-blocking streams into a staging frame and is composed into `out` on the caller's stream (k_compose).  Slot s = launch
     // index mod pipe_slots: its stream (s mod pipe_depth), its staging rows, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
     bool pipeline = true;                            // NRAYS_PIPELINE=0: every frame on the direct path (A/B, tests)
@@ -167,7 +176,7 @@ struct NraysScene {
     bool cull_enabled = true;                       // NRAYS_SCREEN_CULL=0: no wave tile is decided from the scene's screen bounds
     nrays::WavefrontState* wf = nullptr;            // staged (wavefront) path: queues, chunk tables, sums (wavefront.hip)
     nrays::TraceWorkspace* tw = nullptr;            // caller-ray batches (nrays_trace_rays*), created on first use
-    int ray_reorder = 1;                            // NRAYS_RAY_REORDER: 0 = a batch called unordered is traced as it comes, 2 = every such batch is reordered, else by its size (nrays_hip.hip: reorder_pays)
+    int ray_reorder = 1;                            // NRAYS_RAY_REORDER: 0 = a batch called unordered is traced as it comes, 2 = every such batch is reordered, else by its size (ray_order.hip: reorder_pays)
     int wavefront_mode = -1;                        // NRAYS_WAVEFRONT: 0 = never, 1 = whenever the scene is eligible, -1 = the library's rule (wavefront.hip)
     NraysStats last;
     uint64_t last_primary = 0, last_primary_first_batch = 0;
@@ -178,3 +187,22 @@ struct NraysScene {
     bool perm_mixed = false;              // its launches did not all run the same permutation (sample batches: only the first can be plain)
 };
 
+namespace nrays {
+// ---- what the translation units call of each other ----
+// nrays_hip.hip.  ensure_spill: a traversal-stack spill region (the handle's, a pipeline stream's, the caller-ray workspace's), allocated on first use when the scene's trees are
+// deeper than the LDS part of the stack (spill_entries != 0); *region stays null otherwise.  ensure_own_stream: the stream of the blocking entry points, created on first use.
+// order_behind_stream: work enqueued on `stream` from here on runs behind what `prev` holds now (ev_switch recorded there and waited for: no host stall).
+// grow_device: a device buffer that only grows — freed and re-allocated (contents not kept) when it holds fewer than `want` elements of `elem` bytes.
+int ensure_spill(const NraysScene* sc, uint32_t** region);
+int ensure_own_stream(NraysScene* sc);
+int order_behind_stream(NraysScene* sc, hipStream_t prev, hipStream_t stream);
+int grow_device(void** buffer, size_t* have, size_t want, size_t elem);
+// frame_path.hip.  render_impl: one frame of `p` into d_out on `stream`.  tile_rows: rows of the local frame buffer (the image's, or this owner's bands).
+// preallocate_first_frame: what a first frame would allocate (nrays_scene_create).  pipeline_release: the pipelined frames' streams, events and buffers (nrays_scene_destroy).
+int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStream_t stream, bool instrumented, uint32_t count_flags = 0u);
+uint32_t tile_rows(const NraysRenderParams* p);
+void preallocate_first_frame(NraysScene* sc);
+void pipeline_release(NraysScene* sc);
+constexpr double kNearPixels = 16.0; // (frame_path.hip: cam_shift_px; nrays_scene_create derives the handle's default from it)
+void trace_workspace_release(NraysScene* sc); // ray_order.hip: drains and frees the caller-ray workspace, if a batch ever ran
+} // namespace nrays

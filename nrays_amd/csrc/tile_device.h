@@ -1,4 +1,4 @@
-// tile_device.h — device code shared by the frame kernels of the megakernel path (nrays_hip.hip: k_primary) and of the
+// tile_device.h — device code shared by the frame kernels of the megakernel path (primary_kernel.h: k_primary) and of the
 // staged path (wavefront.hip: k_wf_primary): the background rows outside the window of blocks that can see the scene.
 #pragma once
 #include <hip/hip_runtime.h>

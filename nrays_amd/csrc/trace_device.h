@@ -132,6 +132,12 @@ struct Cnt {
     unsigned cyc_x[8];                               // wave cycles outside the queries (DeviceCounters::dbg2)
     unsigned cyc_closest0, cyc_closestN, cyc_shadow; // wave cycles inside the closest-hit query of primary rays / of continuation rays / inside shadow queries
 #endif
+    NR_DEV void zero() { // once per kernel
+        node = tri = prim = hit = tex = shadow = refl = refr = max_depth = max_chain_nodes = traced = elided = fetch = 0;
+#ifdef NR_PHASE_TIMING
+        cyc_node = cyc_leaf = cyc_other = cyc_tri = 0; wv_node = ln_node = wv_tri = ln_tri = 0; cyc_closest0 = cyc_closestN = cyc_shadow = 0; wv_uni = 0; inq_node = inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cyc_x[k_] = 0;
+#endif
+    }
 };
 
 // ---------------------------------------------------------------- traversal stack ------------
@@ -165,6 +171,16 @@ struct Stack {
     }
     NR_DEV static uint32_t addr(const lds_u32* p) { return (uint32_t)(uintptr_t)p; }
     NR_DEV void init() { lds[0] = (uint32_t)kEmptyChild; top = lds + kBlock; } // once per kernel: nothing ever overwrites slot 0
+    // once per kernel: this lane's column of the workgroup's lds_stack[kLdsStack * kBlock], its column of the launch's HBM spill region (null when the tree depth fits
+    // in LDS), its column of the workgroup's park array (kFeatPark kernels; null elsewhere), and the bottom marker
+    NR_DEV void setup(uint32_t* lds_stack, uint32_t* spill_region, lds_u32* park_column) {
+        lds = (lds_u32*)(lds_stack + threadIdx.x);
+        spill_stride = gridDim.x * kBlock;
+        spill = spill_region ? (global_u32*)(spill_region + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
+        lds0 = addr((lds_u32*)lds_stack);
+        park = park_column;
+        init();
+    }
     NR_DEV void reset() { top = lds + kBlock; }
     NR_DEV int slots() const { return (int)(top - lds) / kBlock; }
     // true iff every active lane of the wave can take `n` more slots inside the LDS part

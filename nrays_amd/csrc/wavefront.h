@@ -1,5 +1,5 @@
 // wavefront.h — entry points of the staged ("wavefront") form of the trace loop (wavefront.hip), called by
-// render_impl (nrays_hip.hip).  Host only.
+// render_impl (frame_path.hip).  Host only.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +11,7 @@ namespace nrays {
 // no double branching, point-like lights (racsample 1), and NRAYS_WAVEFRONT / the library's rule say so.
 bool wavefront_wanted(const NraysScene* sc, const NraysRenderParams* p, uint32_t lane_log2);
 
-// Renders the frame described by `R` (window, cull bounds, raygen tables, lane mapping already decided by render_impl)
+// Renders the frame described by `R` (window, cull bounds, raygen tables, lane mapping already decided by plan_frame, frame_path.hip)
 // into d_out: primary stage, then closest / shadow / shade stages generation after generation, every sample of a pixel
 // in one pass over sub-ranges of the wave tiles.  Records [ev_pbegin .. ev_pend] around the first sub-range's stages when
 // `timed`.  Pixels are bit-identical to the megakernel's.

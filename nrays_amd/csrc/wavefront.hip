@@ -1,7 +1,7 @@
 // wavefront.hip — the trace loop of scene::render (src/scene.rs:29-116) as STAGES over compacted ray queues in HBM, for
 // scenes of TriMesh nodes: the north star's "wavefront ballot / prefix-sum ray compaction" on the main path.
 //
-// The megakernel (nrays_hip.hip: k_primary) keeps a pixel's whole chain — closest hit, shadow rays, Phong, continuation —
+// The megakernel (primary_kernel.h: k_primary) keeps a pixel's whole chain — closest hit, shadow rays, Phong, continuation —
 // in the registers of one lane; a wave then carries the union of every code path (207 - 249 VGPRs: two waves per SIMD),
 // lanes whose ray missed or whose chain ended idle until the wave tile ends, and a frame cannot end before its deepest
 // tile does.  Here one kernel does ONE thing to 64 consecutive rays of a queue:
@@ -190,22 +190,6 @@ NR_DEV uint32_t wf_hit_node(const DScene& S, const Hit& h) {
     return S.tris[h.prim].node_id;
 }
 
-struct WfStackInit {
-    NR_DEV static void make(Stack& st, uint32_t* lds_stack, uint32_t* spill) {
-        st.lds = (lds_u32*)(lds_stack + threadIdx.x);
-        st.spill_stride = gridDim.x * kBlock;
-        st.spill = spill ? (global_u32*)(spill + (size_t)blockIdx.x * kBlock + threadIdx.x) : nullptr;
-        st.lds0 = Stack::addr((lds_u32*)lds_stack);
-        st.park = nullptr;
-        st.init();
-    }
-};
-NR_DEV void wf_cnt_init(Cnt& cnt) {
-    cnt.node = cnt.tri = cnt.prim = cnt.hit = cnt.tex = cnt.shadow = cnt.refl = cnt.refr = cnt.max_depth = cnt.max_chain_nodes = cnt.traced = cnt.elided = cnt.fetch = 0;
-#ifdef NR_PHASE_TIMING
-    cnt.cyc_node = cnt.cyc_leaf = cnt.cyc_other = cnt.cyc_tri = 0; cnt.wv_node = cnt.ln_node = cnt.wv_tri = cnt.ln_tri = 0; cnt.cyc_closest0 = cnt.cyc_closestN = cnt.cyc_shadow = 0; cnt.wv_uni = 0; cnt.inq_node = cnt.inq_tri = 0; for (int k_ = 0; k_ < 8; ++k_) cnt.cyc_x[k_] = 0;
-#endif
-}
 // ray classes of the frame (NraysStats): wave-level reduction, one atomic per wave and class
 NR_DEV void wf_flush(DeviceCounters* ctr, const Cnt& c) {
     unsigned sh = c.shadow, rl = c.refl, rf = c.refr, md = c.max_depth;
@@ -249,13 +233,13 @@ __global__ void __launch_bounds__(kBlock, NR_WF_OCC) k_wf_primary(DScene S, DRen
                                                                   uint32_t* spill, uint32_t tiles_x, uint32_t tiles_y, uint32_t tile_begin, uint32_t tile_end,
                                                                   uint32_t* claim_next, uint32_t* clear_next, uint32_t* zero_counts, DeviceCounters* zero_ctr) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
-    if (blockIdx.x == 0) { // the counter sets of a LATER launch / frame (rotating sets: scene_handle.h kCountSets; nrays_hip.hip, k_primary)
+    if (blockIdx.x == 0) { // the counter sets of a LATER launch / frame (rotating sets: scene_handle.h kCountSets; frame_path.hip, k_primary)
         if (zero_counts && threadIdx.x < kNumCounts) zero_counts[threadIdx.x] = 0u;
         if (zero_ctr && threadIdx.x < sizeof(DeviceCounters) / 4) ((uint32_t*)zero_ctr)[threadIdx.x] = 0u;
     }
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t lane_log2 = PLAIN ? 0u : R.lane_log2;
     const bool fill_rows = (R.win_nx < tiles_x || R.win_ny < tiles_y) && tile_begin == 0u;
@@ -317,8 +301,8 @@ template <int FEAT>
 __global__ void __launch_bounds__(kBlock, NR_WF_OCC) k_wf_closest(DScene S, WfQueue q, uint32_t* spill, uint32_t* claim_next, uint32_t* clear_next) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t total_waves = gridDim.x * (kBlock / 64);
     const uint32_t my_wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -352,8 +336,8 @@ template <int FEAT>
 __global__ void __launch_bounds__(kBlock, NR_WF_OCC) k_wf_shadow(DScene S, WfQueue q, uint4* __restrict__ shres, DeviceCounters* ctr, uint32_t* spill, uint32_t* claim_next, uint32_t* clear_next) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t total_waves = gridDim.x * (kBlock / 64);
     const uint32_t my_wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -444,8 +428,8 @@ __global__ void __launch_bounds__(kBlock, NR_WF_OCC_SHADE) k_wf_shade(DScene S, 
                                                                        uint32_t* spill, uint32_t depth, uint32_t max_depth, uint32_t keyed, uint32_t emit, uint32_t* claim_next, uint32_t* clear_next) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t total_waves = gridDim.x * (kBlock / 64);
     const uint32_t my_wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -652,8 +636,8 @@ __global__ void __launch_bounds__(kBlock, NR_WF_OCC_RF) k_wf_primary_rf(DScene S
         if (zero_ctr && threadIdx.x < sizeof(DeviceCounters) / 4) ((uint32_t*)zero_ctr)[threadIdx.x] = 0u;
     }
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t lane_log2 = PLAIN ? 0u : R.lane_log2;
     const bool fill_rows = (R.win_nx < tiles_x || R.win_ny < tiles_y) && tile_begin == 0u;
     if (fill_rows)
@@ -712,8 +696,8 @@ template <int FEAT>
 __global__ void __launch_bounds__(kBlock, NR_WF_OCC_RF) k_wf_closest_rf(DScene S, WfQueue q, uint32_t* spill, uint32_t* claim_next, uint32_t* clear_next) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t total_waves = gridDim.x * (kBlock / 64);
     const uint32_t my_wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WfClaim work; work.init(claim_next, *q.nblocks * kWfChunksPerBlock, my_wave, total_waves);
@@ -776,8 +760,8 @@ template <int FEAT>
 __global__ void __launch_bounds__(kBlock, NR_WF_OCC_RF) k_wf_shadow_rf(DScene S, WfQueue q, uint4* __restrict__ shres, DeviceCounters* ctr, uint32_t* spill, uint32_t* claim_next, uint32_t* clear_next) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     wf_clear_next(clear_next, kWfMaxSegs);
-    Stack st; WfStackInit::make(st, lds_stack, spill);
-    Cnt cnt; wf_cnt_init(cnt);
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
     const uint32_t total_waves = gridDim.x * (kBlock / 64);
     const uint32_t my_wave = blockIdx.x * (kBlock / 64) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     WfClaim work; work.init(claim_next, *q.nblocks * kWfChunksPerBlock * S.num_lights, my_wave, total_waves);
@@ -788,13 +772,6 @@ __global__ void __launch_bounds__(kBlock, NR_WF_OCC_RF) k_wf_shadow_rf(DScene S,
 }
 
 // ================================================================================================ host side
-#define WF_TRY(expr)                                                                                               \
-    do {                                                                                                           \
-        hipError_t e_ = (expr);                                                                                    \
-        if (e_ != hipSuccess)                                                                                      \
-            return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct WavefrontState {
     void* block[2] = {nullptr, nullptr}; // ray records of the two alternating generations
     WfQueue q[2];
@@ -818,11 +795,11 @@ static int wf_ensure(NraysScene* sc, uint32_t slots, size_t shres_vecs, size_t a
         if (const char* e = getenv("NRAYS_WF_MAX_PATHS")) w.max_paths = (uint64_t)std::max(4096ll, atoll(e));
         if (const char* e = getenv("NRAYS_WF_FUSE")) w.fuse = atoi(e) != 0;
         if (const char* e = getenv("NRAYS_WF_REFILL")) w.refill = atoi(e) != 0; // 2: also in anti-aliased frames
-        WF_TRY(hipMalloc((void**)&w.d_nblocks, (kMaxGenerations + 2) * sizeof(uint32_t)));
-        WF_TRY(hipHostMalloc((void**)&w.h_nblocks, 4 * sizeof(uint32_t), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void**)&w.d_nblocks, (kMaxGenerations + 2) * sizeof(uint32_t)));
+        HIP_TRY(hipHostMalloc((void**)&w.h_nblocks, 4 * sizeof(uint32_t), hipHostMallocDefault));
         for (int k = 0; k < 2; ++k) {
-            WF_TRY(hipMalloc((void**)&w.d_claim[k], kWfMaxSegs * sizeof(uint32_t)));
-            WF_TRY(hipMemset(w.d_claim[k], 0, kWfMaxSegs * sizeof(uint32_t)));
+            HIP_TRY(hipMalloc((void**)&w.d_claim[k], kWfMaxSegs * sizeof(uint32_t)));
+            HIP_TRY(hipMemset(w.d_claim[k], 0, kWfMaxSegs * sizeof(uint32_t)));
         }
     }
     WavefrontState& w = *sc->wf;
@@ -833,7 +810,7 @@ static int wf_ensure(NraysScene* sc, uint32_t slots, size_t shres_vecs, size_t a
         const size_t nblk = slots / kWfBlock;
         const size_t bytes = (size_t)slots * per_slot + nblk * sizeof(uint32_t) + 256;
         for (int k = 0; k < 2; ++k) {
-            WF_TRY(hipMalloc(&w.block[k], bytes));
+            HIP_TRY(hipMalloc(&w.block[k], bytes));
             char* c = (char*)w.block[k];
             WfQueue& q = w.q[k];
             q.o01 = (double2*)c; c += (size_t)slots * 16; q.o2d0 = (double2*)c; c += (size_t)slots * 16; q.d12 = (double2*)c; c += (size_t)slots * 16;
@@ -846,12 +823,12 @@ static int wf_ensure(NraysScene* sc, uint32_t slots, size_t shres_vecs, size_t a
     }
     if (shres_vecs > w.shres_vecs) {
         if (w.d_shres) { (void)hipFree(w.d_shres); w.d_shres = nullptr; w.shres_vecs = 0; }
-        WF_TRY(hipMalloc((void**)&w.d_shres, shres_vecs * sizeof(uint4)));
+        HIP_TRY(hipMalloc((void**)&w.d_shres, shres_vecs * sizeof(uint4)));
         w.shres_vecs = shres_vecs;
     }
     if (acc_floats > w.acc_floats) {
         if (w.d_acc) { (void)hipFree(w.d_acc); w.d_acc = nullptr; w.acc_floats = 0; }
-        WF_TRY(hipMalloc((void**)&w.d_acc, acc_floats * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&w.d_acc, acc_floats * sizeof(float)));
         w.acc_floats = acc_floats;
     }
     return NRAYS_OK;
@@ -924,8 +901,8 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
     bool first_pass = true;
     for (uint32_t t0 = 0; t0 < std::max<uint32_t>(nwt, 1u); t0 += tiles_per_pass) {
         const uint32_t t1 = std::min<uint32_t>(nwt, t0 + tiles_per_pass);
-        if (first_pass && timed) WF_TRY(hipEventRecord(sc->ev_pbegin[slot], stream));
-        WF_TRY(hipMemsetAsync(w.d_nblocks, 0, (kMaxGenerations + 2) * sizeof(uint32_t), stream));
+        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ev_pbegin[slot], stream));
+        HIP_TRY(hipMemsetAsync(w.d_nblocks, 0, (kMaxGenerations + 2) * sizeof(uint32_t), stream));
         WfQueue q0 = w.q[0]; q0.nblocks = w.d_nblocks;
         {
             uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
@@ -935,7 +912,7 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
                 else hipLaunchKernelGGL((k_wf_primary_rf<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
             } else if (plain) hipLaunchKernelGGL((k_wf_primary<FEAT, true>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
             else hipLaunchKernelGGL((k_wf_primary<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
-            WF_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
         uint32_t grid = grid_full; // workgroups of the generation's stage kernels (sized from its block count once that is known)
         for (uint32_t g = 0; g <= (uint32_t)kMaxGenerations; ++g) {
@@ -945,7 +922,7 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
                 uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
                 if (refill_on) hipLaunchKernelGGL((k_wf_closest_rf<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, sc->d_spill, cn, cl);
                 else hipLaunchKernelGGL((k_wf_closest<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, sc->d_spill, cn, cl);
-                WF_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
             }
             const bool fused = !kMulti && w.fuse;
             if (!fused) {
@@ -953,7 +930,7 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
                 uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
                 if (refill_on) hipLaunchKernelGGL((k_wf_shadow_rf<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->d, q, w.d_shres, sc->d_counters, sc->d_spill, cn, cl);
                 else hipLaunchKernelGGL((k_wf_shadow<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->d, q, w.d_shres, sc->d_counters, sc->d_spill, cn, cl);
-                WF_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
             }
             const bool emit = can_continue && g < (uint32_t)kMaxGenerations;
             {
@@ -963,20 +940,20 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
                                                               g, p->max_depth, keyed, emit ? 1u : 0u, cn, cl);
                 } else hipLaunchKernelGGL((k_wf_shade<FEAT, true>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, qn, (const uint4*)w.d_shres, acc, sc->d_counters, sc->d_spill,
                                           g, p->max_depth, keyed, emit ? 1u : 0u, cn, cl);
-                WF_TRY(hipGetLastError());
+                HIP_TRY(hipGetLastError());
             }
             if (!emit) break;
-            WF_TRY(hipMemcpyAsync(w.h_nblocks, qn.nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-            WF_TRY(hipStreamSynchronize(stream));
+            HIP_TRY(hipMemcpyAsync(w.h_nblocks, qn.nblocks, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
             if (w.h_nblocks[0] == 0u) break;
             grid = std::max<uint32_t>(1u, std::min<uint32_t>(grid_full, (w.h_nblocks[0] * kWfChunksPerBlock + 3u) / 4u));
         }
         if (spp > 1 && t1 > t0) {
             const size_t n = (size_t)(t1 - t0) * (64u >> lane_log2);
             hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, R, (const float*)w.d_acc, d_out, t0, t1);
-            WF_TRY(hipGetLastError());
+            HIP_TRY(hipGetLastError());
         }
-        if (first_pass && timed) WF_TRY(hipEventRecord(sc->ev_pend[slot], stream));
+        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ev_pend[slot], stream));
         first_pass = false;
     }
     return NRAYS_OK;

@@ -3,7 +3,7 @@ have no exact permutation and must fall back to a named more general kernel.  Pl
 checks it on any machine (against the parsed list, and every scene against the oracle's view of it), tests/test_permutations_gpu.py
 renders it and asks the library which permutation ran (nrays_debug_last_permutation).
 
-What selects a permutation (nrays_hip.hip: nrays_scene_create, render_impl, launch_primary):
+What selects a permutation (nrays_hip.hip: nrays_scene_create; frame_path.hip: plan_frame, render_impl, launch_primary):
   scene content   1 analytic shapes, 2 meshes with triangles, 4 some node not opaque to shadow rays, 16 unless exactly one light with one
                   sample; a node that both reflects and refracts makes it 15 (31 with bit 16)             scene_build.cpp
   handle          + 32 analytic-only and the records fit LDS (NRAYS_LDS_SCENE=0: off); + 256 additionally opaque with <= 8 leaves in each

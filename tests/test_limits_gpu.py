@@ -67,7 +67,7 @@ def test_capped_double_branching_chain_equals_the_oracle(gpu):
 
 def test_queue_overflow_is_reported_and_the_next_frame_is_clean(gpu):
     sc, cam = _facing_panes()
-    w = h = 256  # capacity = 4 rays per pixel (nrays_hip.hip: render_impl); every pixel queues one refraction per generation
+    w = h = 256  # capacity = 4 rays per pixel (frame_path.hip: ensure_frame_buffers); every pixel queues one refraction per generation
     p, _ = su.camera_params(cam, w, h)
     img = np.empty((h, w, 3), np.float32)
     lib = abi.load_hip_lib()

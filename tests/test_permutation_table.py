@@ -59,7 +59,7 @@ def test_groups_and_build_units():
     assert "NR_PRIMARY_PERMUTATIONS(X)" in inst
     decl = set(re.findall(r"bool launch_primary_group(\d+)\(", open(pc.PRIMARY_KERNEL_H).read()))
     assert decl == {str(k) for k in range(n)}
-    hip = open(pc.PRIMARY_KERNEL_H.replace("primary_kernel.h", "nrays_hip.hip")).read()
+    hip = open(pc.PRIMARY_KERNEL_H.replace("primary_kernel.h", "frame_path.hip")).read()
     assert set(re.findall(r"launch_primary_group(\d+)\(a,", hip)) == decl, "launch_primary() does not ask every group"
 
 

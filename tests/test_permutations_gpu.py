@@ -7,7 +7,7 @@ Per case:
   2. each frame is within TOL = 1e-4 per channel of oracle.render of the same descriptor and parameters (BASELINE.json north_star, as
      tests/test_parity_gpu.py) and the four ray classes equal the oracle's exactly;
   3. each frame is BIT-identical to the same handle's nrays_render_device_instrumented frame (k_primary<true, 31>: "their results are
-     identical, only slower", nrays_hip.hip) and the two frames to each other: one ulp of one pixel fails.
+     identical, only slower", frame_path.hip) and the two frames to each other: one ulp of one pixel fails.
 The last test of the module asserts that the tuples the probe reported are exactly the header's list: a skipped, deselected or
 mis-parametrised case cannot hide a hole (run the module whole)."""
 import ctypes as C

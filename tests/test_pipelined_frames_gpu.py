@@ -1,4 +1,4 @@
-"""Pipelined frames of one handle (nrays_hip.hip: render_impl — a frame enqueued while its predecessor is in flight traces its window on an
+"""Pipelined frames of one handle (frame_path.hip: pipeline_prepare / pipeline_compose — a frame enqueued while its predecessor is in flight traces its window on an
 internal stream and is composed into `out` on the caller's stream, k_compose) against the direct path (NRAYS_PIPELINE=0, read once per scene
 handle): every frame bit for bit, `out` written in the caller's stream order, the counters, and everything that has to order itself behind
 frames in flight.  NRAYS_PIPELINE=2 pipelines every eligible frame whether its predecessor has finished or not, so that the cases do not

@@ -1,4 +1,4 @@
-"""The per-camera scheduling state of a handle (nrays_hip.hip: render_impl — resting camera / nearby camera / cold camera; k_seed_costs, k_tile_order, order reuse, cost
+"""The per-camera scheduling state of a handle (frame_path.hip: schedule_mesh / schedule_analytic — resting camera / nearby camera / cold camera; k_seed_costs, k_tile_order, order reuse, cost
 recording) never changes a pixel: a camera's first frame on a fresh handle, the frames of a camera that moves a little every frame, a jump to a far camera and back are
 the bit-identical frames of a settled handle (reference: the thread partition of src/scene.rs:49-66 never changes a pixel either; examples/loader3d.rs:67-93 renders every
 camera once).  Also: the instrumented render that counts what the timed kernel does (NRAYS_COUNT_AS_TIMED) and the recording launch's own duration / clock."""

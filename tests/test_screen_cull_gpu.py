@@ -1,4 +1,4 @@
-"""Screen bounds of the scene (nrays_hip.hip: screen_bounds()): wave tiles without a pixel inside the projected bounding box
+"""Screen bounds of the scene (frame_path.hip: screen_bounds()): wave tiles without a pixel inside the projected bounding box
 of the scene write the background without generating a ray.  It must never change a pixel or a ray count: every frame here
 is rendered by two handles of the same scene, one with the bounds in use and one created under NRAYS_SCREEN_CULL=0, and
 compared bit for bit (and a few against the oracle, which knows nothing of screen bounds).  Cameras: the bench view, the
