@@ -253,14 +253,14 @@ struct Collapser {
 
 } // namespace
 
-BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, int max_leaf, float prim_cost) {
+BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, int max_leaf, float prim_cost, bool times) {
     BuiltBvh out;
     out.max_depth = 0;
     out.order.resize(prims.size());
     for (size_t i = 0; i < prims.size(); ++i) out.order[i] = (uint32_t)i;
     if (prims.empty()) { out.root = kEmptyChild; return out; }
     max_leaf = std::min(std::max(max_leaf, 1), 8);
-    const bool verbose = prims.size() > 1000000 && getenv("NRAYS_BUILD_TIMES");
+    const bool verbose = prims.size() > 1000000 && times;
     auto T0 = std::chrono::steady_clock::now();
     std::vector<Node2> binary;
     binary.reserve(prims.size());

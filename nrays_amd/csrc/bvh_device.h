@@ -36,6 +36,10 @@ struct DeviceBuildOptions {
     double budget = 1.0, budget_hairy = 5.0, min_gain = 1.0, min_gain_hairy = 0.02, hairy_emptiness = 0.9;
     bool presplit = true;
     int debug_cap_div = 1;    // NRAYS_DEBUG_BUILD_CAPS=n (tests): the builder's internal lists get 1 / n of their capacity, so that their overflow path — an error the caller answers with the host builder — runs
+    uint32_t split_grid_max = 512; // NRAYS_SPLIT_GRID: most workgroups of k_presplit (each thread owns a 6.9 KB stack of frames)
+    bool one_walk = true;     // NRAYS_PRESPLIT_ONE_WALK=0: pre-splitting walks twice instead of keeping the pieces of its last counting pass (A/B)
+    uint32_t debug_piece_cap = 0; // NRAYS_DEBUG_PIECE_CAP=c (tests): c places per piece region — the regions overflow and the second walk takes over (0: sized by the budget)
+    bool verbose = false;     // NRAYS_BUILD_TIMES: the builder's stage times on stderr
     size_t node_tail = 16384; // spare node slots behind the BLAS: a scene with ONE device-built BLAS adopts its arrays as they are (no second copy of GBs)
 };
 

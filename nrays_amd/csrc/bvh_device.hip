@@ -915,15 +915,14 @@ struct Stopwatch {
 
 int build_impl(const std::vector<DeviceMeshPart>& parts, const DeviceBuildOptions& opt, int32_t node_base, uint32_t prim_base, DeviceBlas& out, std::string& err,
                Arena& a1, Arena& a2, Arena& a3) {
-    const bool verbose = getenv("NRAYS_BUILD_TIMES") != nullptr;
+    const bool verbose = opt.verbose;
     Stopwatch sw(verbose);
     size_t n = 0;
     for (const DeviceMeshPart& p : parts) n += p.num_triangles;
     if (n == 0 || n >= (1u << 28)) { err = "device BLAS build: bad triangle count"; return NRAYS_ERR_BAD_ARG; }
     out.num_triangles = n;
     const uint32_t nblocks_tri = [&] { uint32_t b = 0; for (const DeviceMeshPart& p : parts) b += (p.num_triangles + 255u) / 256u; return b; }();
-    const uint32_t split_grid_max = getenv("NRAYS_SPLIT_GRID") ? (uint32_t)std::max(1, atoi(getenv("NRAYS_SPLIT_GRID"))) : 512u; // workgroups of k_presplit (each thread owns a 6.9 KB stack of frames)
-    const uint32_t split_grid = (uint32_t)std::min<size_t>(split_grid_max, (n + 255) / 256);
+    const uint32_t split_grid = (uint32_t)std::min<size_t>(opt.split_grid_max, (n + 255) / 256);
 
     // ---- phase 1: inputs, triangle records, pre-split counts ----
     std::map<const void*, std::pair<size_t, void*>> uploads; // host array -> (bytes, device copy): meshes alias their vertex arrays
@@ -940,9 +939,9 @@ int build_impl(const std::vector<DeviceMeshPart>& parts, const DeviceBuildOption
     const size_t scan_bytes = ((n + 1 + kScanBlock - 1) / kScanBlock) * sizeof(uint32_t); // block sums of the prefix sum over the per-triangle reference counts (exclusive_scan_u32)
     // one-walk pre-splitting: the pieces of the last counting pass are kept (PieceList): 1.25 x the larger budget in all, dealt to the workgroups' regions (their triangles are
     // a uniform sample of the mesh); NRAYS_PRESPLIT_ONE_WALK=0: walk twice as before (A/B)
-    const bool one_walk = may_split && !(getenv("NRAYS_PRESPLIT_ONE_WALK") && atoi(getenv("NRAYS_PRESPLIT_ONE_WALK")) == 0);
+    const bool one_walk = may_split && opt.one_walk;
     // (NRAYS_DEBUG_PIECE_CAP=c: c places per region — tests: the regions overflow and the second walk takes over)
-    const uint32_t region_cap = !one_walk ? 0u : getenv("NRAYS_DEBUG_PIECE_CAP") ? (uint32_t)std::max(1, atoi(getenv("NRAYS_DEBUG_PIECE_CAP")))
+    const uint32_t region_cap = !one_walk ? 0u : opt.debug_piece_cap ? opt.debug_piece_cap
                                 : (uint32_t)((size_t)(1.25 * std::max(opt.budget, opt.budget_hairy) * (double)n) / split_grid + 1024u);
     const size_t u_pieces = (size_t)region_cap * split_grid;
     bytes1 += padded<TriRec>(n) + padded<TriUv>(n) + padded<float>(6 * n) + 2 * padded<double>(nblocks_tri) + padded<Counters>(1) + 2 * padded<uint32_t>(n + 1) +

@@ -308,9 +308,9 @@ static void launch_primary(NraysScene* sc, bool instrumented, int features, bool
                launch_primary_group6(a, stats, feat, plain_, occ_) || launch_primary_group7(a, stats, feat, plain_, occ_);
         if (launched) { // what nrays_debug_last_permutation reports: the permutation that ran, not the one the frame asked for first
             const uint32_t t[4] = {stats ? 1u : 0u, (uint32_t)feat, plain_ ? 1u : 0u, (uint32_t)occ_};
-            if (sc->perm_launches && std::memcmp(t, sc->perm_last, sizeof t) != 0) sc->perm_mixed = true;
-            std::memcpy(sc->perm_last, t, sizeof t);
-            sc->perm_launches++;
+            if (sc->last.perm_launches && std::memcmp(t, sc->last.perm_last, sizeof t) != 0) sc->last.perm_mixed = true;
+            std::memcpy(sc->last.perm_last, t, sizeof t);
+            sc->last.perm_launches++;
         }
         return launched;
     };
@@ -331,52 +331,53 @@ static void launch_primary(NraysScene* sc, bool instrumented, int features, bool
 }
 
 // The ring's timing events are created by the first frame that records into a slot (1 024 hipEventCreate cost 0.6 ms of every scene creation; the
-// first slots are created with the handle).  Every handle of the slot is checked: a creation that failed half-way is retried by the next frame.
+// first slots are created with the handle).  Every handle of the slot is checked: a creation that failed half-way is retried by the next frame.  Touches sc->ring only.
 static int ensure_ring_slot(NraysScene* sc, int slot) {
-    hipEvent_t* ev[4] = {&sc->ev_begin[slot], &sc->ev_pbegin[slot], &sc->ev_pend[slot], &sc->ev_end[slot]};
+    hipEvent_t* ev[4] = {&sc->ring.ev_begin[slot], &sc->ring.ev_pbegin[slot], &sc->ring.ev_pend[slot], &sc->ring.ev_end[slot]};
     for (hipEvent_t* e : ev) if (!*e && hipEventCreate(e) != hipSuccess) { *e = nullptr; return set_last_error(NRAYS_ERR_HIP, "event creation failed"); }
     return NRAYS_OK;
 }
 
 // analytic scenes: the sums / maxima k_tile_order reports per list, their pinned landing place and the event behind the read-back
-// Every member is checked: an allocation that failed half-way (nrays_scene_create tolerates it) is completed by the first frame that sorts.
+// Every member is checked: an allocation that failed half-way (nrays_scene_create tolerates it) is completed by the first frame that sorts.  Touches sc->order only.
 static int alloc_cost_stats(NraysScene* sc) {
-    if (!sc->d_cost_stats && hipMalloc((void**)&sc->d_cost_stats, 16 * sizeof(unsigned long long)) != hipSuccess) { sc->d_cost_stats = nullptr; return set_last_error(NRAYS_ERR_OOM, "tile-cost statistics: device allocation failed"); }
-    if (!sc->h_cost_stats && hipHostMalloc((void**)&sc->h_cost_stats, 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { sc->h_cost_stats = nullptr; return set_last_error(NRAYS_ERR_OOM, "tile-cost statistics: pinned allocation failed"); }
-    if (!sc->ev_stats && hipEventCreateWithFlags(&sc->ev_stats, hipEventDisableTiming) != hipSuccess) { sc->ev_stats = nullptr; return set_last_error(NRAYS_ERR_HIP, "tile-cost statistics: event creation failed"); }
+    if (!sc->order.d_cost_stats && hipMalloc((void**)&sc->order.d_cost_stats, 16 * sizeof(unsigned long long)) != hipSuccess) { sc->order.d_cost_stats = nullptr; return set_last_error(NRAYS_ERR_OOM, "tile-cost statistics: device allocation failed"); }
+    if (!sc->order.h_cost_stats && hipHostMalloc((void**)&sc->order.h_cost_stats, 16 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { sc->order.h_cost_stats = nullptr; return set_last_error(NRAYS_ERR_OOM, "tile-cost statistics: pinned allocation failed"); }
+    if (!sc->order.ev_stats && hipEventCreateWithFlags(&sc->order.ev_stats, hipEventDisableTiming) != hipSuccess) { sc->order.ev_stats = nullptr; return set_last_error(NRAYS_ERR_HIP, "tile-cost statistics: event creation failed"); }
     return NRAYS_OK;
 }
 
 // Pipelined frames: the handle's internal streams (pipe_depth of them; non-blocking: the caller's stream may be the legacy null stream, which a blocking stream would
 // serialise with), their events, and per slot the staging rows of a window of up to `floats` floats.  Growing the staging rows drains the handle first.
+// pipeline_ensure and pipeline_release change sc->pipe only (they read sw.pipe_depth, facts.spill_entries and, to drain, last.stream).
 static int pipeline_ensure(NraysScene* sc, size_t floats) {
-    for (int k = 0; k < sc->pipe_depth; ++k) if (!sc->pipe_stream[k]) HIP_TRY(hipStreamCreateWithFlags(&sc->pipe_stream[k], hipStreamNonBlocking));
-    for (int k = 0; k < sc->pipe_slots; ++k) {
-        if (!sc->ev_traced[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_traced[k], hipEventDisableTiming));
-        if (!sc->ev_composed[k]) HIP_TRY(hipEventCreateWithFlags(&sc->ev_composed[k], hipEventDisableTiming));
+    for (int k = 0; k < sc->sw.pipe_depth; ++k) if (!sc->pipe.stream[k]) HIP_TRY(hipStreamCreateWithFlags(&sc->pipe.stream[k], hipStreamNonBlocking));
+    for (int k = 0; k < sc->pipe.slots; ++k) {
+        if (!sc->pipe.ev_traced[k]) HIP_TRY(hipEventCreateWithFlags(&sc->pipe.ev_traced[k], hipEventDisableTiming));
+        if (!sc->pipe.ev_composed[k]) HIP_TRY(hipEventCreateWithFlags(&sc->pipe.ev_composed[k], hipEventDisableTiming));
     }
-    for (int k = 0; k < sc->pipe_depth; ++k) { const int rs = ensure_spill(sc, &sc->pipe_spill[k]); if (rs != NRAYS_OK) return rs; }
-    if (floats > sc->pipe_floats) {
-        if (sc->have_last) HIP_TRY(hipStreamSynchronize(sc->last_stream)); // every trace in flight has its compose there, or ordered before it
-        for (int k = 0; k < sc->pipe_slots; ++k) if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
-        sc->pipe_floats = 0;
-        for (int k = 0; k < sc->pipe_slots; ++k) HIP_TRY(hipMalloc((void**)&sc->pipe_stage[k], floats * sizeof(float)));
-        sc->pipe_floats = floats;
+    for (int k = 0; k < sc->sw.pipe_depth; ++k) { const int rs = ensure_spill(sc, &sc->pipe.spill[k]); if (rs != NRAYS_OK) return rs; }
+    if (floats > sc->pipe.floats) {
+        if (sc->last.have) HIP_TRY(hipStreamSynchronize(sc->last.stream)); // every trace in flight has its compose there, or ordered before it
+        for (int k = 0; k < sc->pipe.slots; ++k) if (sc->pipe.stage[k]) { (void)hipFree(sc->pipe.stage[k]); sc->pipe.stage[k] = nullptr; }
+        sc->pipe.floats = 0;
+        for (int k = 0; k < sc->pipe.slots; ++k) HIP_TRY(hipMalloc((void**)&sc->pipe.stage[k], floats * sizeof(float)));
+        sc->pipe.floats = floats;
     }
     return NRAYS_OK;
 }
 void pipeline_release(NraysScene* sc) {
-    for (int k = 0; k < NraysScene::kPipeStreams; ++k) if (sc->pipe_stream[k]) (void)hipStreamSynchronize(sc->pipe_stream[k]); // all of them drained before anything they use is freed
+    for (int k = 0; k < NraysScene::kPipeStreams; ++k) if (sc->pipe.stream[k]) (void)hipStreamSynchronize(sc->pipe.stream[k]); // all of them drained before anything they use is freed
     for (int k = 0; k < NraysScene::kPipeStreams; ++k) {
-        if (sc->pipe_stream[k]) { (void)hipStreamDestroy(sc->pipe_stream[k]); sc->pipe_stream[k] = nullptr; }
-        if (sc->pipe_spill[k]) { (void)hipFree(sc->pipe_spill[k]); sc->pipe_spill[k] = nullptr; }
+        if (sc->pipe.stream[k]) { (void)hipStreamDestroy(sc->pipe.stream[k]); sc->pipe.stream[k] = nullptr; }
+        if (sc->pipe.spill[k]) { (void)hipFree(sc->pipe.spill[k]); sc->pipe.spill[k] = nullptr; }
     }
     for (int k = 0; k < NraysScene::kPipeSlots; ++k) {
-        if (sc->pipe_stage[k]) { (void)hipFree(sc->pipe_stage[k]); sc->pipe_stage[k] = nullptr; }
-        if (sc->ev_traced[k]) { (void)hipEventDestroy(sc->ev_traced[k]); sc->ev_traced[k] = nullptr; }
-        if (sc->ev_composed[k]) { (void)hipEventDestroy(sc->ev_composed[k]); sc->ev_composed[k] = nullptr; }
+        if (sc->pipe.stage[k]) { (void)hipFree(sc->pipe.stage[k]); sc->pipe.stage[k] = nullptr; }
+        if (sc->pipe.ev_traced[k]) { (void)hipEventDestroy(sc->pipe.ev_traced[k]); sc->pipe.ev_traced[k] = nullptr; }
+        if (sc->pipe.ev_composed[k]) { (void)hipEventDestroy(sc->pipe.ev_composed[k]); sc->pipe.ev_composed[k] = nullptr; }
     }
-    sc->pipe_floats = 0;
+    sc->pipe.floats = 0;
 }
 
 // The handle that rendered last, process-wide: a caller that alternates between handles (two handles, two streams, two frame buffers) already overlaps its frames on the
@@ -385,7 +386,8 @@ void pipeline_release(NraysScene* sc) {
 static std::atomic<NraysScene*> g_last_renderer{nullptr};
 
 // ---- the frame's plan ------------------------------------------------------------------------------------------------------------------
-// What plan_frame decides once per frame.  The phases read it; the header comment of each names what it may still change: grid, grab, R.lead_*, R.tile_order, R.tile_cost.
+// What plan_frame decides once per frame.  The phases read it; the header comment of each names what it may still change: grid, grab, R.lead_*, R.tile_order, R.tile_cost —
+// and which group of the handle (scene_handle.h) it writes.  Every phase reads sc->sw and sc->facts; none writes them.
 struct FramePlan {
     uint32_t rows; uint64_t npix_local;    // rows and pixels of the local frame buffer
     bool queued; uint32_t batch;           // the scene needs the HBM queue (double branching); samples per k_primary launch
@@ -398,13 +400,13 @@ struct FramePlan {
     uint64_t sched_key, cam; CamSnap snap; // geometry key, camera hash and camera of the per-camera scheduling state (not filled for staged frames)
 };
 
-// NRAYS_HOST_TIMES=n (read by nrays_scene_create): microseconds of host time this call spends up to a few marks, for the handle's frames n .. n + 3 (1: its first frames, tools/cold_probe.py)
+// NRAYS_HOST_TIMES=n (Switches::host_times_from): microseconds of host time this call spends up to a few marks, for the handle's frames n .. n + 3 (1: its first frames, tools/cold_probe.py)
 struct HostTimes {
     bool on; unsigned long long frame; std::chrono::steady_clock::time_point t0;
     void mark(const char* what) const { if (on) fprintf(stderr, "  render_impl frame %llu: +%.1f us %s\n", frame, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), what); }
 };
 
-// Fills the plan and the by-value DRender (everything but the sample range of a launch and what the schedulers decide).  No HIP call.
+// Fills the plan and the by-value DRender (everything but the sample range of a launch and what the schedulers decide).  No HIP call; the handle is only read.
 static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool instrumented, FramePlan& f, DRender& R) {
     if (p->ray_per_pixel == 0) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_per_pixel must be > 0 (scene.rs:37)");
     if (p->width == 0 || p->height == 0) return set_last_error(NRAYS_ERR_BAD_ARG, "empty resolution");
@@ -416,11 +418,11 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
     // sample batching keeps the number of primary rays (and hence continuation rays) per launch bounded
     // Continuation rays stay in registers (trace_chain); the HBM queue is only needed when one hit can
     // spawn both a reflection and a refraction.
-    f.queued = sc->host.any_double_branch;
+    f.queued = sc->facts.host.any_double_branch;
     // Sample batching bounds the continuation rays one launch can append to that queue; a frame without a queue renders
     // all its samples in ONE launch (NRAYS_MAX_PRIMARY forces batching for the tests).
-    const uint64_t kMaxPrimaryPerLaunch = sc->max_primary_per_launch;
-    const uint32_t batch = f.batch = (f.queued || sc->max_primary_forced)
+    const uint64_t kMaxPrimaryPerLaunch = sc->sw.max_primary_per_launch;
+    const uint32_t batch = f.batch = (f.queued || sc->sw.max_primary_forced)
         ? (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(p->ray_per_pixel, kMaxPrimaryPerLaunch / std::max<uint64_t>(1, npix_local)))
         : p->ray_per_pixel;
 
@@ -432,14 +434,14 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
     for (int a = 0; a < 3; ++a) R.eye[a] = p->camera_eye[a];
     for (int a = 0; a < 16; ++a) R.m[a] = p->inv_proj_view[a];
     R.seed = p->seed;
-    R.use_rng = (p->window_width != 0.0 || sc->host.any_area_light) ? 1u : 0u;
-    { const ScreenBounds sb = sc->cull_enabled ? screen_bounds(sc->host, p) : ScreenBounds{INT32_MIN, INT32_MAX, INT32_MIN, INT32_MAX};
+    R.use_rng = (p->window_width != 0.0 || sc->facts.host.any_area_light) ? 1u : 0u;
+    { const ScreenBounds sb = sc->sw.cull_enabled ? screen_bounds(sc->facts.host, p) : ScreenBounds{INT32_MIN, INT32_MAX, INT32_MIN, INT32_MAX};
       R.cull_i0 = sb.i0; R.cull_i1 = sb.i1; R.cull_j0 = sb.j0; R.cull_j1 = sb.j1; }
 
     // lanes per pixel of an anti-aliased frame (sample-major mapping, see k_primary): the largest power of two <= min(batch, 64)
     uint32_t lane_log2 = 0;
     if (batch >= 2) { while (lane_log2 < 6u && (2u << lane_log2) <= batch) ++lane_log2; }
-    if (sc->lane_log2_override >= 0) lane_log2 = std::min<uint32_t>((uint32_t)sc->lane_log2_override, lane_log2);
+    if (sc->sw.lane_log2_override >= 0) lane_log2 = std::min<uint32_t>((uint32_t)sc->sw.lane_log2_override, lane_log2);
     R.lane_log2 = f.lane_log2 = lane_log2;
     const uint32_t bwl = f.bwl = lane_log2 ? (7u - lane_log2) >> 1 : 4u, bhl = f.bhl = lane_log2 ? (6u - lane_log2) >> 1 : 4u; // pixel block of a scheduling unit
     const uint32_t tiles_x = f.tiles_x = (p->width + (1u << bwl) - 1) >> bwl, tiles_y = f.tiles_y = (rows + (1u << bhl) - 1) >> bhl;
@@ -464,35 +466,35 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
         R.win_x0 = x0; R.win_nx = nx; R.win_y0 = y0; R.win_ny = ny;
     }
     f.win_units = R.win_nx * R.win_ny; // scheduling blocks inside the window
-    f.grab = sc->host.any_mesh ? 1u : 0u; // 0 = workgroup lists through LDS; the specialised kernels fix their path at compile time
-    if (sc->grab_override >= 0) f.grab = (uint32_t)sc->grab_override; // tiles per dequeue of the mesh kernels, A/B only (NRAYS_GRAB); pixels do not depend on it
+    f.grab = sc->facts.host.any_mesh ? 1u : 0u; // 0 = workgroup lists through LDS; the specialised kernels fix their path at compile time
+    if (sc->sw.grab_override >= 0) f.grab = (uint32_t)sc->sw.grab_override; // tiles per dequeue of the mesh kernels, A/B only (NRAYS_GRAB); pixels do not depend on it
     // persistent grid: exactly the workgroups that can be resident (one 4-wave workgroup per CU per wave/SIMD)
     // Waves per SIMD of the alpha-shadow mesh permutations (k_primary's OCC): three for multi-light frames (their long tiles are split
     // into light-parallel parts, so the frame is bound by its sum) and for frames with many tiles per resident wave, two otherwise
     // (the frame is as long as its longest tile, and that tile's wave is fastest at two).  NRAYS_OCC overrides.
     int occ = 0;
-    if (!instrumented && (sc->features == 6 || sc->features == 7 || sc->features == 22 || sc->features == 23) && lane_log2 == 0u) {
-        const uint64_t wave_tiles = (uint64_t)ntiles * 4u, waves2 = (uint64_t)sc->num_cus * 8u;
+    if (!instrumented && (sc->facts.features == 6 || sc->facts.features == 7 || sc->facts.features == 22 || sc->facts.features == 23) && lane_log2 == 0u) {
+        const uint64_t wave_tiles = (uint64_t)ntiles * 4u, waves2 = (uint64_t)sc->facts.num_cus * 8u;
         // (multi-light frames: from 6 wave tiles per resident wave on.  Round 5, after the shadow rays that are multiplied by 0 stopped being traced
         // (light_is_dark()): an owner's eighth of a 4K frame, 16 320 wave tiles, runs 1.22 - 1.29 ms at three waves against 1.40 - 1.44 at two, half a
         // 1080p frame 1.48 against 1.74; at 8 160 - 8 640 wave tiles the frame is as long as its longest split tile and two waves win, 1.10 / 0.97 ms
         // against 1.46 / 1.24: profiles/r05_rank_occupancy.log.  Round 4's threshold was 12: the eighth then ran 1.9 ms at two against 2.0 - 2.9.)
-        const bool multi = (sc->features & kFeatMultiSample) && sc->light_lsl && sc->light_split_factor != 0.0f;
+        const bool multi = (sc->facts.features & kFeatMultiSample) && sc->facts.light_lsl && sc->sw.light_split_factor != 0.0f;
         // One light: from 14 wave tiles per resident wave on (round 5: the 1080p sponza stand-in, 32 640 wave tiles, 1.125 ms at three waves against 1.23 at two — its sum of
         // tile cycles per resident wave, 1.14 ms at two waves, had passed its longest tile, 0.89; at 1600 x 900, 22 800 wave tiles, the longest tile still leads and two waves
         // win, 0.93 against 1.12: profiles/r05_rank_occupancy.log.  Round 4's threshold was 24.)
         // (with the long tiles of one-light frames split by pixels, NR_PIXEL_SPLIT, the longest tile stops leading earlier: 22 800 wave tiles 0.86 ms at three waves against 0.95,
         // 14 400 wave tiles 0.75 against 0.73 — from 9 on)
-        occ = wave_tiles >= (multi ? 6u : (NR_PIXEL_SPLIT && sc->light_lsl ? 9u : 14u)) * waves2 ? 3 : 0;
-        if (sc->occ_override >= 0) occ = sc->occ_override == 3 ? 3 : 0;
+        occ = wave_tiles >= (multi ? 6u : (NR_PIXEL_SPLIT && sc->facts.light_lsl ? 9u : 14u)) * waves2 ? 3 : 0;
+        if (sc->sw.occ_override >= 0) occ = sc->sw.occ_override == 3 ? 3 : 0;
     }
     f.occ = occ;
     f.grid = std::min<uint32_t>(std::min<uint32_t>(((ntiles + 7u) / 8u) * 8u, (uint32_t)kMaxGrid),
-                                (uint32_t)sc->num_cus * (uint32_t)(occ ? NR_OCC3_AS : waves_per_simd(instrumented ? kFeatAll : sc->features)) * 256u / (uint32_t)kBlock);
-    if (sc->grid_wg_per_cu > 0) f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->num_cus * (uint32_t)sc->grid_wg_per_cu); // NRAYS_GRID_WG_PER_CU: occupancy sensitivity runs
+                                (uint32_t)sc->facts.num_cus * (uint32_t)(occ ? NR_OCC3_AS : waves_per_simd(instrumented ? kFeatAll : sc->facts.features)) * 256u / (uint32_t)kBlock);
+    if (sc->sw.grid_wg_per_cu > 0) f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus * (uint32_t)sc->sw.grid_wg_per_cu); // NRAYS_GRID_WG_PER_CU: occupancy sensitivity runs
 
-    f.timed = instrumented || (sc->frames_total % sc->event_stride) == 0;
-    f.slot = (int)(sc->frames_recorded % NraysScene::kRing);
+    f.timed = instrumented || (sc->ring.frames_total % sc->sw.event_stride) == 0;
+    f.slot = (int)(sc->ring.frames_recorded % NraysScene::kRing);
     // The staged ("wavefront") form of the trace loop (wavefront.hip) renders this frame instead of k_primary when the scene is eligible and
     // NRAYS_WAVEFRONT / the library's rule say so; pixels are identical either way.
     f.staged = !instrumented && wavefront_wanted(sc, p, lane_log2);
@@ -506,32 +508,35 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
         mix(p->inv_proj_view, sizeof p->inv_proj_view); mix(p->camera_eye, sizeof p->camera_eye); mix(&p->window_width, sizeof p->window_width);
         mix(&p->ray_per_pixel, sizeof p->ray_per_pixel); mix(&p->max_depth, sizeof p->max_depth);
         f.cam = cam;
-        f.snap = cam_snapshot(sc->host, p);
+        f.snap = cam_snapshot(sc->facts.host, p);
     }
     return NRAYS_OK;
 }
 
-// What the frame's launches write besides `out`: the queue pair and the fixed-point sums of a double-branching scene, the spill region of deep trees.
+// What the frame's launches write besides `out`: the queue pair and the fixed-point sums of a double-branching scene, the spill region of deep trees.  Touches sc->buf only.
 static int ensure_frame_buffers(NraysScene* sc, const FramePlan& f, hipStream_t stream) {
     if (f.queued) {
         const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4 * f.npix_local * f.batch, 1u << 16), 1ull << 27);
-        int rc = ensure_queue_pair(sc->queue, sc->queue_capacity, (uint32_t)want);
-        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&sc->d_fixed, &sc->fixed_slots, &sc->fixed_dirty, (size_t)f.npix_local * 3, stream);
+        int rc = ensure_queue_pair(sc->buf.queue, sc->buf.queue_capacity, (uint32_t)want);
+        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&sc->buf.d_fixed, &sc->buf.fixed_slots, &sc->buf.fixed_dirty, (size_t)f.npix_local * 3, stream);
         if (rc != NRAYS_OK) return rc;
     }
-    return ensure_spill(sc, &sc->d_spill);
+    return ensure_spill(sc, &sc->buf.d_spill);
 }
 
 // The per-handle state (queues, raygen tables, tile costs) assumes that the renders of one handle execute one after the other — pipelined
 // frames, below, are the exception and say what they share — and `out` is written in call order: a render on a different stream than its
-// predecessor is ordered behind it.
+// predecessor is ordered behind it.  Touches sc->last only.
 static int order_behind_previous(NraysScene* sc, hipStream_t stream) {
-    if (!sc->have_last || sc->last_stream == stream) return NRAYS_OK;
-    if (sc->last_timed && sc->last_done) { HIP_TRY(hipStreamWaitEvent(stream, sc->last_done, 0)); return NRAYS_OK; }
-    return order_behind_stream(sc, sc->last_stream, stream); // the previous frame recorded no event (event_stride): mark the end of ITS stream now and wait on that — no host stall
+    if (!sc->last.have || sc->last.stream == stream) return NRAYS_OK;
+    if (sc->last.timed && sc->last.done) { HIP_TRY(hipStreamWaitEvent(stream, sc->last.done, 0)); return NRAYS_OK; }
+    return order_behind_stream(sc, sc->last.stream, stream); // the previous frame recorded no event (event_stride): mark the end of ITS stream now and wait on that — no host stall
 }
 
 // ---- per-camera scheduling state (pixels never depend on it) -----------------------------------------------------------------
+// sc->order belongs to the phases of this section: record_costs, ensure_tile_arrays, schedule_mesh and schedule_analytic are the only code that writes it
+// (render_impl adds the recording launch's events and cost_tiles / cost_grid / cost_split_lsl).  Of the rest of the handle the two schedulers write
+// ring.ev_begin / ring.has_prepass of the frame's slot — a sort is part of the timed frame — and nothing else.
 // The reference's caller renders every camera ONCE (examples/loader3d.rs:67-93), an interactive caller moves it a little every
 // frame: what a frame may cost besides its tiles is decided here.
 //   resting camera    the order recorded for it is reused; nothing is recorded, nothing sorted;
@@ -540,37 +545,37 @@ static int order_behind_previous(NraysScene* sc, hipStream_t stream) {
 //                     which also clears the cost array) — a moving camera pays the sort every kMaxOrderAge + 1 frames;
 //   cold camera       no usable history: mesh scenes guess (k_seed_costs + k_tile_order), analytic scenes run image-order lists;
 //                     the frame records its costs, its successor sorts them.
-static bool near_cam(const NraysScene* sc, const CamSnap& other, const CamSnap& snap) { return sc->near_reuse && cam_shift_px(other, snap) <= sc->near_pixels; }
+static bool near_cam(const NraysScene* sc, const CamSnap& other, const CamSnap& snap) { return sc->sw.near_reuse && cam_shift_px(other, snap) <= sc->order.near_pixels; }
 // This frame records its tile costs (DRender::tile_cost), for this geometry and camera.
 static void record_costs(NraysScene* sc, const FramePlan& f, DRender& R, uint64_t key) {
-    R.tile_cost = sc->d_tile_cost; sc->cost_key = key; sc->cost_cam = f.cam; sc->cost_snap = f.snap; sc->cost_valid = true;
+    R.tile_cost = sc->order.d_tile_cost; sc->order.cost_key = key; sc->order.cost_cam = f.cam; sc->order.cost_snap = f.snap; sc->order.cost_valid = true;
 }
 // d_tile_cost / d_tile_order for nwt wave tiles (order_words words of order): re-allocated when too small, which invalidates the recorded costs and the order.
 static int ensure_tile_arrays(NraysScene* sc, uint32_t nwt, size_t order_words) {
-    if (nwt <= sc->tile_slots) return NRAYS_OK;
-    if (sc->d_tile_cost) { (void)hipFree(sc->d_tile_cost); sc->d_tile_cost = nullptr; }
-    if (sc->d_tile_order) { (void)hipFree(sc->d_tile_order); sc->d_tile_order = nullptr; }
-    sc->tile_slots = 0; sc->cost_valid = false; sc->order_valid = false;
-    HIP_TRY(hipMalloc((void**)&sc->d_tile_cost, (size_t)nwt * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc((void**)&sc->d_tile_order, order_words * sizeof(uint32_t)));
-    sc->tile_slots = nwt;
+    if (nwt <= sc->order.tile_slots) return NRAYS_OK;
+    if (sc->order.d_tile_cost) { (void)hipFree(sc->order.d_tile_cost); sc->order.d_tile_cost = nullptr; }
+    if (sc->order.d_tile_order) { (void)hipFree(sc->order.d_tile_order); sc->order.d_tile_order = nullptr; }
+    sc->order.tile_slots = 0; sc->order.cost_valid = false; sc->order.order_valid = false;
+    HIP_TRY(hipMalloc((void**)&sc->order.d_tile_cost, (size_t)nwt * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc((void**)&sc->order.d_tile_order, order_words * sizeof(uint32_t)));
+    sc->order.tile_slots = nwt;
     return NRAYS_OK;
 }
 
 // What a first frame would allocate, sized for frames up to 4K (larger ones re-allocate as before): the reference's caller
 // renders a camera ONCE (loader3d.rs:67-93), so the first frame of a handle is the one that counts for it.  Failures are tolerated: the frame that needs a buffer tries again.
+// (nrays_scene_create: allocate_handle_state calls it unless NRAYS_PREALLOC=0.)  Sets the tile arrays, list lengths, read-back buffers and events of sc->order, last.ev_switch,
+// the ring's first slots, buf.d_spill.
 void preallocate_first_frame(NraysScene* sc) {
-    const char* e = getenv("NRAYS_PREALLOC"); // =0: allocate on the first frame (A/B switch)
-    if (e && atoi(e) == 0) return;
     const uint32_t nwt = (3840u / 16u) * (2160u / 16u) * 4u;
-    if (ensure_tile_arrays(sc, nwt, order_slots(nwt, sc->light_lsl)) != NRAYS_OK) (void)hipGetLastError();
-    if (sc->light_lsl && hipMalloc((void**)&sc->d_order_len, 8 * sizeof(uint32_t)) != hipSuccess) { sc->d_order_len = nullptr; (void)hipGetLastError(); }
+    if (ensure_tile_arrays(sc, nwt, order_slots(nwt, sc->facts.light_lsl)) != NRAYS_OK) (void)hipGetLastError();
+    if (sc->facts.light_lsl && hipMalloc((void**)&sc->order.d_order_len, 8 * sizeof(uint32_t)) != hipSuccess) { sc->order.d_order_len = nullptr; (void)hipGetLastError(); }
     // ... the analytic scenes' read-back buffers, the event a render on another stream waits for, and the ring's first slots
-    if (!sc->host.any_mesh && alloc_cost_stats(sc) != NRAYS_OK) { (void)hipGetLastError(); }
-    if (hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming) != hipSuccess) { sc->ev_switch = nullptr; (void)hipGetLastError(); }
-    for (int k = 0; k < 2; ++k) if (hipEventCreate(&sc->ev_rec[k]) != hipSuccess) { sc->ev_rec[k] = nullptr; (void)hipGetLastError(); }
+    if (!sc->facts.host.any_mesh && alloc_cost_stats(sc) != NRAYS_OK) { (void)hipGetLastError(); }
+    if (hipEventCreateWithFlags(&sc->last.ev_switch, hipEventDisableTiming) != hipSuccess) { sc->last.ev_switch = nullptr; (void)hipGetLastError(); }
+    for (int k = 0; k < 2; ++k) if (hipEventCreate(&sc->order.ev_rec[k]) != hipSuccess) { sc->order.ev_rec[k] = nullptr; (void)hipGetLastError(); }
     for (int k = 0; k < 8; ++k) (void)ensure_ring_slot(sc, k);
-    if (ensure_spill(sc, &sc->d_spill) != NRAYS_OK) { sc->d_spill = nullptr; (void)hipGetLastError(); }
+    if (ensure_spill(sc, &sc->buf.d_spill) != NRAYS_OK) { sc->buf.d_spill = nullptr; (void)hipGetLastError(); }
 }
 
 // mesh scenes: longest-processing-time-first from the previous frame of the same geometry (pixels do not depend on it)
@@ -579,57 +584,57 @@ void preallocate_first_frame(NraysScene* sc) {
 // 251 -> 222 ms without it, sponza 1080p 4 / 16 / 64 spp 2-4 %, profiles/r02_aa_lpt.log)
 // May change: f.grab (1 when the frame follows an order); R.tile_order, R.tile_cost, R.light_lsl, R.order_len.  Launches k_seed_costs / k_tile_order.
 static int schedule_mesh(NraysScene* sc, FramePlan& f, DRender& R, hipStream_t stream, bool instrumented) {
-    const uint32_t kMaxOrderAge = sc->max_order_age;
+    const uint32_t kMaxOrderAge = sc->order.max_order_age;
     bool lpt = f.grab >= 1u && f.lane_log2 == 0u;
-    lpt = lpt && sc->lpt_enabled; // A/B switch (NRAYS_LPT=0)
-    if (instrumented && sc->light_lsl) lpt = false; // the instrumented kernel does not decode the split entries a plain frame's order may hold
+    lpt = lpt && sc->sw.lpt_enabled; // A/B switch (NRAYS_LPT=0)
+    if (instrumented && sc->facts.light_lsl) lpt = false; // the instrumented kernel does not decode the split entries a plain frame's order may hold
     if (!lpt) return NRAYS_OK;
     const uint32_t nwt = std::max<uint32_t>(1u, f.lane_log2 ? f.win_units : f.win_units * 4u);
     // light-parallel tiles (DRender::light_lsl): multi-light mesh scenes; the order array then holds up to 2^lsl entries per tile
     // (one-light frames, NR_PIXEL_SPLIT: only while a single tile can lead the frame — below 24 wave tiles per resident wave at two waves per SIMD; beyond, no tile comes near
     // the frame's work per wave and the split machinery costs 0.7 %: profiles/r05_pixel_split_ab.log)
-    const bool pixel_split_only = sc->light_lsl && !(sc->features & kFeatMultiSample);
-    const uint32_t split_lsl = (sc->light_lsl && sc->light_split_factor != 0.0f && !instrumented && !(pixel_split_only && (uint64_t)nwt >= 24ull * (uint64_t)sc->num_cus * 8ull)) ? sc->light_lsl : 0u;
-    { const int rc = ensure_tile_arrays(sc, nwt, order_slots(nwt, sc->light_lsl)); if (rc != NRAYS_OK) return rc; }
-    if (split_lsl && !sc->d_order_len) HIP_TRY(hipMalloc((void**)&sc->d_order_len, 8 * sizeof(uint32_t)));
-    R.light_lsl = split_lsl; R.order_len = split_lsl ? sc->d_order_len : nullptr;
+    const bool pixel_split_only = sc->facts.light_lsl && !(sc->facts.features & kFeatMultiSample);
+    const uint32_t split_lsl = (sc->facts.light_lsl && sc->sw.light_split_factor != 0.0f && !instrumented && !(pixel_split_only && (uint64_t)nwt >= 24ull * (uint64_t)sc->facts.num_cus * 8ull)) ? sc->facts.light_lsl : 0u;
+    { const int rc = ensure_tile_arrays(sc, nwt, order_slots(nwt, sc->facts.light_lsl)); if (rc != NRAYS_OK) return rc; }
+    if (split_lsl && !sc->order.d_order_len) HIP_TRY(hipMalloc((void**)&sc->order.d_order_len, 8 * sizeof(uint32_t)));
+    R.light_lsl = split_lsl; R.order_len = split_lsl ? sc->order.d_order_len : nullptr;
     const uint64_t key = f.sched_key ^ ((uint64_t)split_lsl << 56); // (an order that holds split entries is not one without them)
-    const bool order_here = sc->order_valid && sc->order_key == key && !sc->order_seeded && sc->lpt_reuse;
+    const bool order_here = sc->order.order_valid && sc->order.order_key == key && !sc->order.order_seeded && sc->sw.lpt_reuse;
     bool record = false;
-    if (order_here && sc->order_cam == f.cam) {
-        R.tile_order = sc->d_tile_order; // resting camera
-    } else if (order_here && kMaxOrderAge != 0u && sc->order_age < kMaxOrderAge && near_cam(sc, sc->order_snap, f.snap)) {
-        R.tile_order = sc->d_tile_order; // nearby camera: the order as it is
-        record = ++sc->order_age == kMaxOrderAge;
-        if (record && split_lsl) HIP_TRY(hipMemsetAsync(sc->d_tile_cost, 0, (size_t)nwt * sizeof(uint32_t), stream)); // split entries record by atomicMax (rare frame: every kMaxOrderAge-th)
+    if (order_here && sc->order.order_cam == f.cam) {
+        R.tile_order = sc->order.d_tile_order; // resting camera
+    } else if (order_here && kMaxOrderAge != 0u && sc->order.order_age < kMaxOrderAge && near_cam(sc, sc->order.order_snap, f.snap)) {
+        R.tile_order = sc->order.d_tile_order; // nearby camera: the order as it is
+        record = ++sc->order.order_age == kMaxOrderAge;
+        if (record && split_lsl) HIP_TRY(hipMemsetAsync(sc->order.d_tile_cost, 0, (size_t)nwt * sizeof(uint32_t), stream)); // split entries record by atomicMax (rare frame: every kMaxOrderAge-th)
     } else {
-        const bool costs_here = sc->cost_valid && sc->cost_key == key && (sc->cost_cam == f.cam || near_cam(sc, sc->cost_snap, f.snap));
+        const bool costs_here = sc->order.cost_valid && sc->order.cost_key == key && (sc->order.cost_cam == f.cam || near_cam(sc, sc->order.cost_snap, f.snap));
         // no history for this view: a first guess from the boxes of the nodes that can continue a chain (k_seed_costs)
-        const bool seeded = !costs_here && sc->seed_enabled && sc->seed_boxes != 0u && f.win_units > 0;
+        const bool seeded = !costs_here && sc->sw.seed_enabled && sc->facts.seed_boxes != 0u && f.win_units > 0;
         if (seeded) {
-            if (f.timed) HIP_TRY(hipEventRecord(sc->ev_begin[f.slot], stream));
-            hipLaunchKernelGGL(k_seed_costs, dim3((nwt + 255u) / 256u), dim3(256), 0, stream, R, (const float*)sc->d_seed_boxes, sc->seed_boxes, sc->d_tile_cost, nwt, sc->seed_rays);
+            if (f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_begin[f.slot], stream));
+            hipLaunchKernelGGL(k_seed_costs, dim3((nwt + 255u) / 256u), dim3(256), 0, stream, R, (const float*)sc->facts.d_seed_boxes, sc->facts.seed_boxes, sc->order.d_tile_cost, nwt, sc->sw.seed_rays);
             HIP_TRY(hipGetLastError());
 #ifdef NR_DEBUG_TILE_COSTS
-            if (!sc->d_seed_copy) HIP_TRY(hipMalloc((void**)&sc->d_seed_copy, (size_t)sc->tile_slots * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpyAsync(sc->d_seed_copy, sc->d_tile_cost, (size_t)nwt * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream)); // tools/tile_dump.py: the guess beside the recorded costs
+            if (!sc->order.d_seed_copy) HIP_TRY(hipMalloc((void**)&sc->order.d_seed_copy, (size_t)sc->order.tile_slots * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(sc->order.d_seed_copy, sc->order.d_tile_cost, (size_t)nwt * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream)); // tools/tile_dump.py: the guess beside the recorded costs
 #endif
         }
         if (seeded || costs_here) {
-            if (f.timed && !seeded) HIP_TRY(hipEventRecord(sc->ev_begin[f.slot], stream));
-            sc->has_prepass[f.slot] = true;
-            hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, stream, sc->d_tile_cost, sc->d_tile_order, nwt, (unsigned long long*)nullptr,
-                               split_lsl, sc->light_split_factor, f.grid * (uint32_t)(kBlock / 64), split_lsl ? sc->d_order_len : (uint32_t*)nullptr, split_lsl ? 1u : 0u, sc->split_hyst);
+            if (f.timed && !seeded) HIP_TRY(hipEventRecord(sc->ring.ev_begin[f.slot], stream));
+            sc->ring.has_prepass[f.slot] = true;
+            hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, stream, sc->order.d_tile_cost, sc->order.d_tile_order, nwt, (unsigned long long*)nullptr,
+                               split_lsl, sc->sw.light_split_factor, f.grid * (uint32_t)(kBlock / 64), split_lsl ? sc->order.d_order_len : (uint32_t*)nullptr, split_lsl ? 1u : 0u, sc->sw.split_hyst);
             HIP_TRY(hipGetLastError());
-            R.tile_order = sc->d_tile_order;
-            sc->order_valid = true; sc->order_key = key; sc->order_seeded = seeded; sc->order_age = 0;
-            if (!seeded) { sc->order_cam = sc->cost_cam; sc->order_snap = sc->cost_snap; }
-        } else if (split_lsl) HIP_TRY(hipMemsetAsync(sc->d_tile_cost, 0, (size_t)nwt * sizeof(uint32_t), stream));
+            R.tile_order = sc->order.d_tile_order;
+            sc->order.order_valid = true; sc->order.order_key = key; sc->order.order_seeded = seeded; sc->order.order_age = 0;
+            if (!seeded) { sc->order.order_cam = sc->order.cost_cam; sc->order.order_snap = sc->order.cost_snap; }
+        } else if (split_lsl) HIP_TRY(hipMemsetAsync(sc->order.d_tile_cost, 0, (size_t)nwt * sizeof(uint32_t), stream));
         // a guessed order is replaced by the recorded one on the next frame; an order sorted from a NEARBY camera's costs serves this
         // one as it is (it ages like any other).  The frame that sorts its OWN camera's costs records once more: under the order it will
         // keep (nrays_get_tile_costs reports these).
-        record = seeded || !costs_here || !sc->lpt_reuse || sc->cost_cam == f.cam || kMaxOrderAge == 0u;
-        if (!record) sc->cost_valid = false; // consumed (and, with split entries, cleared) by the sort
+        record = seeded || !costs_here || !sc->sw.lpt_reuse || sc->order.cost_cam == f.cam || kMaxOrderAge == 0u;
+        if (!record) sc->order.cost_valid = false; // consumed (and, with split entries, cleared) by the sort
     }
     if (R.tile_order) f.grab = 1u;
     if (record) record_costs(sc, f, R, key);
@@ -644,54 +649,54 @@ static int schedule_mesh(NraysScene* sc, FramePlan& f, DRender& R, hipStream_t s
 // as before (profiles/r02_analytic_lpt.log: balls 70.0 -> 52.4 us; primitives, whose every tile is long, stays at 201 us).
 // May change: f.grid (NRAYS_LEAD_WGS=0: one workgroup per CU); R.tile_cost, R.tile_order, R.lead_wgs, R.lead_entries.  Launches k_tile_order.
 static int schedule_analytic(NraysScene* sc, FramePlan& f, DRender& R, hipStream_t stream, bool instrumented) {
-    if (!(f.grab == 0u && sc->lpt_analytic && !instrumented && f.win_units > 0)) return NRAYS_OK;
-    const uint32_t kMaxOrderAge = sc->max_order_age;
+    if (!(f.grab == 0u && sc->sw.lpt_analytic && !instrumented && f.win_units > 0)) return NRAYS_OK;
+    const uint32_t kMaxOrderAge = sc->order.max_order_age;
     const uint32_t nwt = f.lane_log2 ? f.win_units : f.win_units * 4u;
     { const int rc = ensure_tile_arrays(sc, nwt, nwt); if (rc != NRAYS_OK) return rc; }
-    if (!sc->d_cost_stats || !sc->h_cost_stats || !sc->ev_stats) { const int rc = alloc_cost_stats(sc); if (rc != NRAYS_OK) return rc; }
+    if (!sc->order.d_cost_stats || !sc->order.h_cost_stats || !sc->order.ev_stats) { const int rc = alloc_cost_stats(sc); if (rc != NRAYS_OK) return rc; }
     const uint64_t key = f.sched_key;
-    const hipError_t stats_ready = sc->stats_pending ? hipEventQuery(sc->ev_stats) : hipErrorNotReady;
-    if (sc->stats_pending && stats_ready != hipSuccess) (void)hipGetLastError(); // "not ready" must not surface as the launch error checked below
-    if (sc->stats_pending && stats_ready == hipSuccess) { // the sums / maxima of the last sort's eight lists have arrived
+    const hipError_t stats_ready = sc->order.stats_pending ? hipEventQuery(sc->order.ev_stats) : hipErrorNotReady;
+    if (sc->order.stats_pending && stats_ready != hipSuccess) (void)hipGetLastError(); // "not ready" must not surface as the launch error checked below
+    if (sc->order.stats_pending && stats_ready == hipSuccess) { // the sums / maxima of the last sort's eight lists have arrived
         double sum = 0.0, mx = 0.0;
-        for (int x = 0; x < 8; ++x) { sum += (double)sc->h_cost_stats[2 * x]; mx = std::max(mx, (double)sc->h_cost_stats[2 * x + 1]); }
-        sc->lone_waves = mx > 0.0 && sum / mx < sc->lone_factor * 4.0 * (double)sc->num_cus;
-        sc->lone_known = true; sc->lone_key = sc->stats_key;
-        sc->stats_pending = false;
+        for (int x = 0; x < 8; ++x) { sum += (double)sc->order.h_cost_stats[2 * x]; mx = std::max(mx, (double)sc->order.h_cost_stats[2 * x + 1]); }
+        sc->order.lone_waves = mx > 0.0 && sum / mx < sc->sw.lone_factor * 4.0 * (double)sc->facts.num_cus;
+        sc->order.lone_known = true; sc->order.lone_key = sc->order.stats_key;
+        sc->order.stats_pending = false;
     }
     auto sort_costs = [&]() -> int {
-        if (sc->stats_pending) HIP_TRY(hipEventSynchronize(sc->ev_stats)); // (a camera that changes every few frames: the previous read-back is long done)
-        if (f.timed) HIP_TRY(hipEventRecord(sc->ev_begin[f.slot], stream));
-        sc->has_prepass[f.slot] = true;
-        hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, stream, sc->d_tile_cost, sc->d_tile_order, nwt, sc->d_cost_stats, 0u, 0.0f, 0u, (uint32_t*)nullptr, 0u, 1.0f);
+        if (sc->order.stats_pending) HIP_TRY(hipEventSynchronize(sc->order.ev_stats)); // (a camera that changes every few frames: the previous read-back is long done)
+        if (f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_begin[f.slot], stream));
+        sc->ring.has_prepass[f.slot] = true;
+        hipLaunchKernelGGL(k_tile_order, dim3(8), dim3(1024), 0, stream, sc->order.d_tile_cost, sc->order.d_tile_order, nwt, sc->order.d_cost_stats, 0u, 0.0f, 0u, (uint32_t*)nullptr, 0u, 1.0f);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(sc->h_cost_stats, sc->d_cost_stats, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipEventRecord(sc->ev_stats, stream));
-        sc->stats_pending = true; sc->stats_key = key;
-        sc->order_valid = true; sc->order_key = key; sc->order_cam = sc->cost_cam; sc->order_snap = sc->cost_snap; sc->order_age = 0;
+        HIP_TRY(hipMemcpyAsync(sc->order.h_cost_stats, sc->order.d_cost_stats, 16 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipEventRecord(sc->order.ev_stats, stream));
+        sc->order.stats_pending = true; sc->order.stats_key = key;
+        sc->order.order_valid = true; sc->order.order_key = key; sc->order.order_cam = sc->order.cost_cam; sc->order.order_snap = sc->order.cost_snap; sc->order.order_age = 0;
         return NRAYS_OK;
     };
-    const bool order_here = sc->order_valid && sc->order_key == key;
+    const bool order_here = sc->order.order_valid && sc->order.order_key == key;
     bool record = false;
-    if (order_here && sc->order_cam == f.cam) {
+    if (order_here && sc->order.order_cam == f.cam) {
         // steady state of a resting camera: nothing recorded, nothing sorted
-    } else if (order_here && sc->order_age < kMaxOrderAge && near_cam(sc, sc->order_snap, f.snap)) {
-        record = ++sc->order_age == kMaxOrderAge; // nearby camera: the order as it is; its last frame records for the re-sort
-    } else if (sc->cost_valid && sc->cost_key == key && (sc->cost_cam == f.cam || near_cam(sc, sc->cost_snap, f.snap))) {
+    } else if (order_here && sc->order.order_age < kMaxOrderAge && near_cam(sc, sc->order.order_snap, f.snap)) {
+        record = ++sc->order.order_age == kMaxOrderAge; // nearby camera: the order as it is; its last frame records for the re-sort
+    } else if (sc->order.cost_valid && sc->order.cost_key == key && (sc->order.cost_cam == f.cam || near_cam(sc, sc->order.cost_snap, f.snap))) {
         const int rc = sort_costs(); if (rc != NRAYS_OK) return rc; // the frame after a recording one
     } else {
-        sc->order_valid = false; // a cold camera: image-order lists, costs recorded
+        sc->order.order_valid = false; // a cold camera: image-order lists, costs recorded
         record = true;
     }
     if (record) record_costs(sc, f, R, key);
     // (while the sums of a re-sort are on their way the decision of the previous sort of this geometry stands)
-    if (sc->order_valid && sc->order_key == key && sc->lone_known && sc->lone_key == key && sc->lone_waves) {
-        R.tile_order = sc->d_tile_order;
-        if (sc->lead_mode) { R.lead_wgs = std::min<uint32_t>(f.grid, (uint32_t)sc->num_cus); R.lead_entries = R.lead_wgs * (uint32_t)sc->lead_per_wg; } // two workgroups per CU: one of them owns the long tiles
-        else f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->num_cus);                         // NRAYS_LEAD_WGS=0: one workgroup per CU
+    if (sc->order.order_valid && sc->order.order_key == key && sc->order.lone_known && sc->order.lone_key == key && sc->order.lone_waves) {
+        R.tile_order = sc->order.d_tile_order;
+        if (sc->sw.lead_mode) { R.lead_wgs = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus); R.lead_entries = R.lead_wgs * (uint32_t)sc->sw.lead_per_wg; } // two workgroups per CU: one of them owns the long tiles
+        else f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus);                         // NRAYS_LEAD_WGS=0: one workgroup per CU
     }
 #ifdef NR_DEBUG_TILE_COSTS
-    if (getenv("NRAYS_DEBUG_RECORD_ALWAYS")) R.tile_cost = sc->d_tile_cost; // tools/tile_costs.py: the costs of the steady-state frames
+    if (sc->sw.debug_record_always) R.tile_cost = sc->order.d_tile_cost; // tools/tile_costs.py: the costs of the steady-state frames
 #endif
     return NRAYS_OK;
 }
@@ -716,15 +721,16 @@ struct PipeFrame {
     uint32_t wi0, wi1, wr0, wr1;     // the window in pixels
 };
 // Decides and prepares: eligibility, in-flight query, staging rows, slot and stream, the waits of the trace stream.  May change: f.grid, R.lead_wgs, R.lead_entries (the shape of the lists).
+// Of the handle it writes sc->pipe (and creates last.ev_switch when no frame has yet); it reads order's outcome through R, ring.has_prepass, last.* and buf.launch_index.
 static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePlan& f, DRender& R, hipStream_t stream, bool interleaved, const HostTimes& ht, PipeFrame& pf) {
-    bool pipe = sc->pipeline && f.single_launch && !sc->d.no_elide && !f.banded && !sc->host.any_mesh && f.grab == 0u && f.lane_log2 == 0u && !R.tile_cost &&
-                !sc->has_prepass[f.slot] && sc->have_last && f.win_units > 0u && 2ull * f.win_units <= (uint64_t)f.tiles_x * f.tiles_y;
+    bool pipe = sc->pipe.enabled && f.single_launch && !sc->facts.d.no_elide && !f.banded && !sc->facts.host.any_mesh && f.grab == 0u && f.lane_log2 == 0u && !R.tile_cost &&
+                !sc->ring.has_prepass[f.slot] && sc->last.have && f.win_units > 0u && 2ull * f.win_units <= (uint64_t)f.tiles_x * f.tiles_y;
 #ifdef NR_DEBUG_TILE_COSTS
     pipe = false;
 #endif
-    if (pipe && !sc->pipeline_always && interleaved) pipe = false; // another handle rendered in between (g_last_renderer)
-    if (pipe && !sc->pipeline_always) { // is the predecessor still in flight?  (a caller that waits for every frame stays on the direct path)
-        const hipError_t q = sc->last_pipelined ? hipEventQuery(sc->last_done) : hipStreamQuery(sc->last_stream);
+    if (pipe && !sc->sw.pipeline_always && interleaved) pipe = false; // another handle rendered in between (g_last_renderer)
+    if (pipe && !sc->sw.pipeline_always) { // is the predecessor still in flight?  (a caller that waits for every frame stays on the direct path)
+        const hipError_t q = sc->pipe.last_pipelined ? hipEventQuery(sc->last.done) : hipStreamQuery(sc->last.stream);
         if (q != hipSuccess) (void)hipGetLastError();
         pipe = q == hipErrorNotReady;
         ht.mark("pipeline: in-flight query");
@@ -735,64 +741,65 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
     const uint32_t wr1s = std::min<uint32_t>(pf.wr1, f.rows);
     const size_t stage_skip = (size_t)pf.wr0 * p->width * 3;
     if (pipe && pipeline_ensure(sc, (size_t)(wr1s - pf.wr0) * p->width * 3) != NRAYS_OK) { // no room for the staging frames: direct from here on, and said so once
-        (void)hipGetLastError(); sc->pipeline = false; pipe = false;
+        (void)hipGetLastError(); sc->pipe.enabled = false; pipe = false;
         fprintf(stderr, "nrays: the staging frames of pipelined frames could not be allocated (%s); this handle renders every frame on the direct path\n", nrays_last_error());
     }
     // Three persistent trace grids compete for the two wave slots of a SIMD: with lead + second workgroups (two per CU) a trace holds every slot of the chip while its
     // long tiles run, and the third trace in flight mostly waits for slots; with ONE workgroup per CU (the NRAYS_LEAD_WGS=0 shape of the cost-ordered lists) two traces
     // fit side by side and the third takes the slots of whichever retires waves first.  Pixels do not depend on the shape of the lists.
-    if (pipe && !sc->pipe_lead_wgs && R.lead_wgs) { R.lead_wgs = 0u; R.lead_entries = 0u; f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->num_cus); }
+    if (pipe && !sc->pipe.lead_wgs && R.lead_wgs) { R.lead_wgs = 0u; R.lead_entries = 0u; f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus); }
     pf.on = pipe;
-    pf.ps = (int)(sc->launch_index % (uint64_t)sc->pipe_slots); pf.pst = pf.ps % sc->pipe_depth;
-    pf.lstream = pipe ? sc->pipe_stream[pf.pst] : stream;
-    pf.stage = pipe ? sc->pipe_stage[pf.ps] - stage_skip : nullptr;
+    pf.ps = (int)(sc->buf.launch_index % (uint64_t)sc->pipe.slots); pf.pst = pf.ps % sc->sw.pipe_depth;
+    pf.lstream = pipe ? sc->pipe.stream[pf.pst] : stream;
+    pf.stage = pipe ? sc->pipe.stage[pf.ps] - stage_skip : nullptr;
     if (pipe) {
-        if (!sc->last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: every internal stream behind its end
-            if (!sc->ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(sc->ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
-            for (int k = 0; k < sc->pipe_depth; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe_stream[k], sc->ev_switch, 0));
+        if (!sc->pipe.last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: every internal stream behind its end
+            if (!sc->last.ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->last.ev_switch, hipEventDisableTiming));
+            HIP_TRY(hipEventRecord(sc->last.ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
+            for (int k = 0; k < sc->sw.pipe_depth; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe.stream[k], sc->last.ev_switch, 0));
         }
         // the compose that last read this slot's staging rows, pipe_slots frames ago: when the host can see that it is over (a query costs 0.6 us) the wait (5 us
         // of host time, which bounds the pipelined frame rate) is not enqueued
-        if (hipEventQuery(sc->ev_composed[pf.ps]) != hipSuccess) { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->ev_composed[pf.ps], 0)); }
+        if (hipEventQuery(sc->pipe.ev_composed[pf.ps]) != hipSuccess) { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->pipe.ev_composed[pf.ps], 0)); }
         ht.mark("pipeline: waits of the trace stream");
     }
     return NRAYS_OK;
 }
 // The second half of a pipelined frame: the caller's stream waits for the trace, then k_compose writes every float of `out`.
-// (an error from here on leaves a trace in flight that no compose follows: it is drained, and what comes next is ordered as after direct work)
+// (an error from here on leaves a trace in flight that no compose follows: it is drained, and what comes next is ordered as after direct work)  Touches sc->pipe only.
 static int pipeline_compose(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, float* d_out, hipStream_t stream, const HostTimes& ht) {
-    auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(pf.lstream); sc->last_pipelined = false; } return e; };
-    HIP_TRY(drained(hipStreamWaitEvent(stream, sc->ev_traced[pf.ps], 0)));
+    auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(pf.lstream); sc->pipe.last_pipelined = false; } return e; };
+    HIP_TRY(drained(hipStreamWaitEvent(stream, sc->pipe.ev_traced[pf.ps], 0)));
     ht.mark("pipeline: wait of the caller's stream");
-    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->d.background[0], sc->d.background[1], sc->d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1);
+    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->pipe.ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->facts.d.background[0], sc->facts.d.background[1], sc->facts.d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1);
     HIP_TRY(drained(hipGetLastError()));
     ht.mark("pipeline: k_compose launch");
     return NRAYS_OK;
 }
 
-// End-of-frame bookkeeping: the frame's last event, what the handle's next call orders itself behind, what nrays_get_stats reports.
+// End-of-frame bookkeeping: the frame's last event, what the handle's next call orders itself behind, what nrays_get_stats reports.  Writes sc->last, the frame's
+// slot of sc->ring and pipe.last_pipelined.
 static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, hipStream_t stream, bool instrumented, const HostTimes& ht) {
     const bool pipelined = pf.on;
     // (a pipelined frame's kernel_ms_total runs from its trace to the end of its compose; its "done" event is the compose's)
-    if ((!f.single_launch || pipelined) && f.timed) HIP_TRY(hipEventRecord(sc->ev_end[f.slot], stream));
-    sc->last_timed = f.timed || pipelined;
+    if ((!f.single_launch || pipelined) && f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_end[f.slot], stream));
+    sc->last.timed = f.timed || pipelined;
     if (f.timed) {
-        sc->single_launch[f.slot] = f.single_launch && !pipelined;
-        sc->last_done = sc->single_launch[f.slot] ? sc->ev_pend[f.slot] : sc->ev_end[f.slot];
-        sc->frames_recorded++;
+        sc->ring.single_launch[f.slot] = f.single_launch && !pipelined;
+        sc->last.done = sc->ring.single_launch[f.slot] ? sc->ring.ev_pend[f.slot] : sc->ring.ev_end[f.slot];
+        sc->ring.frames_recorded++;
     }
-    if (pipelined) sc->last_done = sc->ev_composed[pf.ps];
-    sc->last_pipelined = pipelined;
-    sc->last_stream = stream; sc->have_last = true;
+    if (pipelined) sc->last.done = sc->pipe.ev_composed[pf.ps];
+    sc->pipe.last_pipelined = pipelined;
+    sc->last.stream = stream; sc->last.have = true;
     ht.mark("end (event records after the launch)");
     // owned rows only (padding rows of the last band carry no rays)
     uint64_t owned_rows = 0;
     if (p->band_rows == 0 || p->band_owners <= 1) owned_rows = p->height;
     else for (uint32_t j = 0; j < p->height; ++j) if (((j / p->band_rows) % p->band_owners) == p->band_owner) ++owned_rows;
-    sc->last_primary = owned_rows * p->width * p->ray_per_pixel;
-    sc->last_primary_first_batch = owned_rows * p->width * std::min<uint32_t>(f.batch, p->ray_per_pixel);
-    sc->last_instrumented = instrumented;
+    sc->last.primary = owned_rows * p->width * p->ray_per_pixel;
+    sc->last.primary_first_batch = owned_rows * p->width * std::min<uint32_t>(f.batch, p->ray_per_pixel);
+    sc->last.instrumented = instrumented;
     return NRAYS_OK;
 }
 
@@ -800,75 +807,75 @@ static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FrameP
 int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStream_t stream, bool instrumented, uint32_t count_flags) {
     if (!sc || !p || !d_out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     const bool interleaved = g_last_renderer.exchange(sc, std::memory_order_relaxed) != sc;
-    const HostTimes ht{sc->host_times_from && sc->frames_total + 1 >= sc->host_times_from && sc->frames_total + 1 < sc->host_times_from + 4, sc->frames_total, std::chrono::steady_clock::now()};
+    const HostTimes ht{sc->sw.host_times_from && sc->ring.frames_total + 1 >= sc->sw.host_times_from && sc->ring.frames_total + 1 < sc->sw.host_times_from + 4, sc->ring.frames_total, std::chrono::steady_clock::now()};
     FramePlan f; DRender R;
     { const int rc = plan_frame(sc, p, instrumented, f, R); if (rc != NRAYS_OK) return rc; }
-    HIP_TRY(hipSetDevice(sc->device));
-    sc->perm_launches = 0; sc->perm_mixed = false; // (nrays_debug_last_permutation speaks of this render from here on)
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    sc->last.perm_launches = 0; sc->last.perm_mixed = false; // (nrays_debug_last_permutation speaks of this render from here on)
     ht.mark("hipSetDevice");
     { int rc = ensure_frame_buffers(sc, f, stream); if (rc == NRAYS_OK) rc = order_behind_previous(sc, stream); if (rc != NRAYS_OK) return rc; }
     ht.mark("parameters, screen bounds, window");
-    sc->frames_total++;
+    sc->ring.frames_total++;
     if (f.timed) { const int rc = ensure_ring_slot(sc, f.slot); if (rc != NRAYS_OK) return rc; }
     // events: [pbegin .. pend] brackets the first primary launch; the frame spans [pbegin .. end], and
     // `end` is only recorded separately when something follows the primary kernel
-    sc->d_counters = sc->d_counters_set[sc->frame_index % (uint64_t)sc->count_rot];
-    DeviceCounters* next_ctr = sc->d_counters_set[(sc->frame_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot]; // (scene_handle.h: the set of the next frame on this frame's stream)
-    sc->frame_index++;
-    sc->has_prepass[f.slot] = false;
+    sc->buf.d_counters = sc->buf.d_counters_set[sc->buf.frame_index % (uint64_t)sc->buf.count_rot];
+    DeviceCounters* next_ctr = sc->buf.d_counters_set[(sc->buf.frame_index + (uint64_t)sc->buf.count_rot / 2u) % (uint64_t)sc->buf.count_rot]; // (scene_handle.h: the set of the next frame on this frame's stream)
+    sc->buf.frame_index++;
+    sc->ring.has_prepass[f.slot] = false;
     PipeFrame pf{}; // (direct until pipeline_prepare says otherwise)
     if (f.staged) {
-        sc->d_counts = sc->d_counts_set[sc->launch_index % (uint64_t)sc->count_rot];
-        uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot];
-        sc->launch_index++;
+        sc->buf.d_counts = sc->buf.d_counts_set[sc->buf.launch_index % (uint64_t)sc->buf.count_rot];
+        uint32_t* next_counts = sc->buf.d_counts_set[(sc->buf.launch_index + (uint64_t)sc->buf.count_rot / 2u) % (uint64_t)sc->buf.count_rot];
+        sc->buf.launch_index++;
         const int rc = wavefront_render(sc, p, R, d_out, stream, f.tiles_x, f.tiles_y, f.timed, f.slot, next_ctr, next_counts);
         if (rc != NRAYS_OK) return rc;
     } else {
         { int rc = schedule_mesh(sc, f, R, stream, instrumented); if (rc == NRAYS_OK) rc = schedule_analytic(sc, f, R, stream, instrumented); if (rc != NRAYS_OK) return rc; }
 #ifdef NR_DEBUG_TILE_COSTS
-        if (!sc->d_wave_times) HIP_TRY(hipMalloc((void**)&sc->d_wave_times, (size_t)kMaxGrid * (kBlock / 64) * 8 * sizeof(uint32_t)));
-        HIP_TRY(hipMemsetAsync(sc->d_wave_times, 0, (size_t)kMaxGrid * (kBlock / 64) * 8 * sizeof(uint32_t), stream));
-        R.wave_times = sc->d_wave_times; sc->dbg_grid = f.grid; R.dbg_mode = getenv("NRAYS_DEBUG_WAVE_WORK") ? (uint32_t)atoi(getenv("NRAYS_DEBUG_WAVE_WORK")) : 0u;
+        if (!sc->order.d_wave_times) HIP_TRY(hipMalloc((void**)&sc->order.d_wave_times, (size_t)kMaxGrid * (kBlock / 64) * 8 * sizeof(uint32_t)));
+        HIP_TRY(hipMemsetAsync(sc->order.d_wave_times, 0, (size_t)kMaxGrid * (kBlock / 64) * 8 * sizeof(uint32_t), stream));
+        R.wave_times = sc->order.d_wave_times; sc->order.dbg_grid = f.grid; R.dbg_mode = sc->sw.debug_wave_work;
 #endif
-        if (R.tile_cost) { sc->cost_tiles = f.lane_log2 ? f.win_units : f.win_units * 4u; sc->cost_grid = f.grid; sc->cost_split_lsl = R.light_lsl; }
-        R.cost_meta = sc->d_cost_meta; // (read by the instrumented kernel only)
+        if (R.tile_cost) { sc->order.cost_tiles = f.lane_log2 ? f.win_units : f.win_units * 4u; sc->order.cost_grid = f.grid; sc->order.cost_split_lsl = R.light_lsl; }
+        R.cost_meta = sc->order.d_cost_meta; // (read by the instrumented kernel only)
         ht.mark("scheduling state (seed / sort launches)");
         { const int rc = pipeline_prepare(sc, p, f, R, stream, interleaved, ht, pf); if (rc != NRAYS_OK) return rc; }
         bool first_primary = true;
         for (uint32_t s0 = 0; s0 < p->ray_per_pixel; s0 += f.batch) {
             R.sample_begin = s0; R.sample_end = std::min<uint32_t>(p->ray_per_pixel, s0 + f.batch);
             R.first_batch = s0 == 0 ? 1u : 0u;
-            sc->d_counts = sc->d_counts_set[sc->launch_index % (uint64_t)sc->count_rot];
-            uint32_t* next_counts = sc->d_counts_set[(sc->launch_index + (uint64_t)sc->count_rot / 2u) % (uint64_t)sc->count_rot];
-            sc->launch_index++;
-            QueueOut qo; qo.q = sc->queue[1].q; qo.capacity = f.queued ? sc->queue_capacity : 0; qo.count = sc->d_counts + 1;
-            qo.overflow = &sc->d_counters->overflow;
-            if (first_primary && f.timed) HIP_TRY(hipEventRecord(sc->ev_pbegin[f.slot], pf.lstream));
+            sc->buf.d_counts = sc->buf.d_counts_set[sc->buf.launch_index % (uint64_t)sc->buf.count_rot];
+            uint32_t* next_counts = sc->buf.d_counts_set[(sc->buf.launch_index + (uint64_t)sc->buf.count_rot / 2u) % (uint64_t)sc->buf.count_rot];
+            sc->buf.launch_index++;
+            QueueOut qo; qo.q = sc->buf.queue[1].q; qo.capacity = f.queued ? sc->buf.queue_capacity : 0; qo.count = sc->buf.d_counts + 1;
+            qo.overflow = &sc->buf.d_counters->overflow;
+            if (first_primary && f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_pbegin[f.slot], pf.lstream));
             if (first_primary) ht.mark("event record before the launch");
             // a launch that records its tile costs is timed (nrays_get_tile_costs: NraysTileCosts::kernel_ms): by the ring's events when the frame has them, by a pair of its own otherwise
-            const bool rec_events = first_primary && R.tile_cost && !f.timed && sc->ev_rec[0] && sc->ev_rec[1];
-            if (first_primary && R.tile_cost) { sc->rec_events_valid = rec_events; sc->rec_slot = f.timed ? f.slot : -1; }
-            if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[0], stream));
-            DScene dsc = sc->d;
-            if (instrumented && (count_flags & NRAYS_COUNT_AS_TIMED) && !sc->d.no_elide) { // what the scene's plain kernel skips (trace_device.h: light_is_dark everywhere; shade_hit in the alpha-mapped mesh kernels)
-                const int ft = primary_permutation_exists(sc->features & ~(int)kFeatLdsScene) ? sc->features : (int)kFeatAll; // the FEAT a plain frame of this scene is launched with
+            const bool rec_events = first_primary && R.tile_cost && !f.timed && sc->order.ev_rec[0] && sc->order.ev_rec[1];
+            if (first_primary && R.tile_cost) { sc->order.rec_events_valid = rec_events; sc->order.rec_slot = f.timed ? f.slot : -1; }
+            if (rec_events) HIP_TRY(hipEventRecord(sc->order.ev_rec[0], stream));
+            DScene dsc = sc->facts.d;
+            if (instrumented && (count_flags & NRAYS_COUNT_AS_TIMED) && !sc->facts.d.no_elide) { // what the scene's plain kernel skips (trace_device.h: light_is_dark everywhere; shade_hit in the alpha-mapped mesh kernels)
+                const int ft = primary_permutation_exists(sc->facts.features & ~(int)kFeatLdsScene) ? sc->facts.features : (int)kFeatAll; // the FEAT a plain frame of this scene is launched with
                 dsc.stats_elide = 1u | (((ft & kFeatMesh) && (ft & kFeatAlphaShadow)) ? 2u : 0u);
             }
             // (a scene with a non-finite light / colour / texel: every frame by the kernel that skips nothing)
-            const bool stats = instrumented || sc->d.no_elide != 0u;
+            const bool stats = instrumented || sc->facts.d.no_elide != 0u;
             R.no_rows = pf.on ? 1u : 0u; // a trace launch writes the window only
-            launch_primary(sc, stats, sc->features, sc->noxform, sc->park, sc->tiny, f.occ, f.grid, pf.lstream, dsc, R, qo, pf.on ? pf.stage : d_out, sc->d_counters,
-                           pf.on ? sc->pipe_spill[pf.pst] : sc->d_spill, f.tiles_x, f.tiles_y, sc->d_counts + kMaxGenerations + 2, f.grab, next_counts, R.first_batch ? next_ctr : nullptr, pf.on ? sc->ev_traced[pf.ps] : nullptr);
+            launch_primary(sc, stats, sc->facts.features, sc->facts.noxform, sc->facts.park, sc->facts.tiny, f.occ, f.grid, pf.lstream, dsc, R, qo, pf.on ? pf.stage : d_out, sc->buf.d_counters,
+                           pf.on ? sc->pipe.spill[pf.pst] : sc->buf.d_spill, f.tiles_x, f.tiles_y, sc->buf.d_counts + kMaxGenerations + 2, f.grab, next_counts, R.first_batch ? next_ctr : nullptr, pf.on ? sc->pipe.ev_traced[pf.ps] : nullptr);
             HIP_TRY(hipGetLastError());
             if (first_primary) ht.mark("k_primary launch");
-            if (rec_events) HIP_TRY(hipEventRecord(sc->ev_rec[1], stream));
+            if (rec_events) HIP_TRY(hipEventRecord(sc->order.ev_rec[1], stream));
             if (first_primary) {
-                if (f.timed) HIP_TRY(hipEventRecord(sc->ev_pend[f.slot], pf.lstream));
-                if (instrumented) HIP_TRY(hipMemcpyAsync(sc->d_counters_primary, sc->d_counters, sizeof(DeviceCounters), hipMemcpyDeviceToDevice, stream));
+                if (f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_pend[f.slot], pf.lstream));
+                if (instrumented) HIP_TRY(hipMemcpyAsync(sc->ring.d_counters_primary, sc->buf.d_counters, sizeof(DeviceCounters), hipMemcpyDeviceToDevice, stream));
                 first_primary = false;
             }
             if (f.queued) { // the queued second children of this batch: k_bounce rounds, folded into d_out before the next batch's k_primary continues its sums
-                const BounceRounds rounds{sc->queue, sc->queue_capacity, sc->d_counts, &sc->d_counters->overflow, sc->d_fixed, &sc->fixed_dirty, sc->d_counters, sc->d_spill, &dsc, stats, p->max_depth, d_out, (size_t)f.npix_local * 3, sc->num_cus};
+                const BounceRounds rounds{sc->buf.queue, sc->buf.queue_capacity, sc->buf.d_counts, &sc->buf.d_counters->overflow, sc->buf.d_fixed, &sc->buf.fixed_dirty, sc->buf.d_counters, sc->buf.d_spill, &dsc, stats, p->max_depth, d_out, (size_t)f.npix_local * 3, sc->facts.num_cus};
                 const int rc = run_bounce_rounds(rounds, stream, nullptr);
                 if (rc != NRAYS_OK) return rc;
             }

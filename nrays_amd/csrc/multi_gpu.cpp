@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/nrays_abi.h"
+#include "switches.h"
 
 namespace nrays { int set_last_error(int status, const std::string& msg); }
 
@@ -218,7 +219,7 @@ int nrays_scene_set_create(const NraysSceneDesc* desc, NraysComm* comm, NraysSce
     *out_set = nullptr;
     NraysSceneSet* s = new NraysSceneSet();
     s->comm = comm;
-    if (const char* e = getenv("NRAYS_MULTI_DIRECT")) s->direct = atoi(e) != 0;
+    s->direct = nrays::read_switches().multi_direct.value_or(s->direct);
     DeviceGuard guard;
     auto bail = [&](int rc) { nrays_scene_set_destroy(s); return rc; };
     const uint32_t first = comm->ranked ? comm->rank : 0u, count = comm->ranked ? 1u : comm->owners;

@@ -57,11 +57,11 @@ static int fail(int status, const std::string& msg) { g_last_error = msg; return
 int set_last_error(int status, const std::string& msg) { return fail(status, msg); } // for the library's other translation units
 
 int ensure_spill(const NraysScene* sc, uint32_t** region) {
-    if (sc->spill_entries && !*region) HIP_TRY(hipMalloc((void**)region, (size_t)kMaxGrid * kBlock * sc->spill_entries * sizeof(uint32_t)));
+    if (sc->facts.spill_entries && !*region) HIP_TRY(hipMalloc((void**)region, (size_t)kMaxGrid * kBlock * sc->facts.spill_entries * sizeof(uint32_t)));
     return NRAYS_OK;
 }
 int ensure_own_stream(NraysScene* sc) {
-    if (!sc->own_stream) HIP_TRY(hipStreamCreate(&sc->own_stream));
+    if (!sc->buf.own_stream) HIP_TRY(hipStreamCreate(&sc->buf.own_stream));
     return NRAYS_OK;
 }
 int grow_device(void** buffer, size_t* have, size_t want, size_t elem) {
@@ -72,11 +72,27 @@ int grow_device(void** buffer, size_t* have, size_t want, size_t elem) {
     return NRAYS_OK;
 }
 int order_behind_stream(NraysScene* sc, hipStream_t prev, hipStream_t stream) {
-    if (!sc->ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->ev_switch, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(sc->ev_switch, prev));
-    HIP_TRY(hipStreamWaitEvent(stream, sc->ev_switch, 0));
+    if (!sc->last.ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->last.ev_switch, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(sc->last.ev_switch, prev));
+    HIP_TRY(hipStreamWaitEvent(stream, sc->last.ev_switch, 0));
     return NRAYS_OK;
 }
+
+// ---- scene creation, in phases (nrays_scene_create is the driver below) ---------------------------------------------------------------
+// Every phase works on the handle `sc` whose sw (the switches) and facts.host (build_host_scene's result) are complete, and returns NRAYS_OK or an error
+// that ends the creation.  The header of each names what it reads and what it sets.  Their order is the order of the HIP calls of a creation
+// (tools/cold_probe.py and the bench's cold figure measure this path).
+
+// NRAYS_BUILD_TIMES: where nrays_scene_create spends its time.
+struct StageClock {
+    bool on; std::chrono::steady_clock::time_point t;
+    void mark(const char* what) {
+        if (!on) return;
+        const auto now = std::chrono::steady_clock::now();
+        fprintf(stderr, "  nrays_scene_create: %s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t).count());
+        t = now;
+    }
+};
 
 // Device-built segments first (device-to-device), then the host-built part: the layout HostScene's refs address.
 template <typename T>
@@ -87,8 +103,8 @@ static int upload_joined(NraysScene* sc, const std::vector<std::pair<const T*, s
     if (total == 0) return NRAYS_OK;
     void* p = nullptr;
     HIP_TRY(hipMalloc(&p, total * sizeof(T)));
-    sc->allocs.push_back(p);
-    sc->scene_bytes += total * sizeof(T);
+    sc->facts.allocs.push_back(p);
+    sc->facts.scene_bytes += total * sizeof(T);
     size_t at = 0;
     for (const auto& s : segs) { if (s.second) HIP_TRY(hipMemcpy((T*)p + at, s.first, s.second * sizeof(T), hipMemcpyDeviceToDevice)); at += s.second; }
     if (!v.empty()) HIP_TRY(hipMemcpy((T*)p + at, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -97,6 +113,255 @@ static int upload_joined(NraysScene* sc, const std::vector<std::pair<const T*, s
 }
 template <typename T>
 static int upload(NraysScene* sc, const std::vector<T>& v, const T** out) { return upload_joined<T>(sc, {}, v, out); }
+
+// Reads host.dev_blas (released or adopted here), host.nodes / tris / triuvs.  Sets d.nodes, d.tris, d.triuvs; facts.allocs, facts.scene_bytes.
+static int upload_bvh_arrays(NraysScene* sc) {
+    HostScene& h = sc->facts.host; DScene& d = sc->facts.d;
+    if (h.dev_blas.size() == 1 && h.tris.empty() && h.triuvs.empty() && h.dev_blas[0].nodes && h.dev_blas[0].num_nodes + h.nodes.size() <= h.dev_blas[0].node_capacity) {
+        // ONE device-built BLAS and nothing but TLAS nodes from the host (a single large mesh): the builder's arrays ARE the scene's arrays — the host
+        // nodes go into the spare slots behind the BLAS; no second allocation, no copy and no release of gigabytes (0.2 s for the hairball stand-in)
+        DeviceBlas& b = h.dev_blas[0];
+        if (!h.nodes.empty() && hipMemcpy(b.nodes + b.num_nodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice) != hipSuccess)
+            return fail(NRAYS_ERR_HIP, "upload of the TLAS nodes failed");
+        d.nodes = b.nodes; d.tris = b.tris; d.triuvs = b.uvs;
+        sc->facts.allocs.push_back(b.nodes); sc->facts.allocs.push_back(b.tris); sc->facts.allocs.push_back(b.uvs);
+        sc->facts.scene_bytes += (b.num_nodes + h.nodes.size()) * sizeof(BvhNode) + b.num_refs * (sizeof(TriRec) + sizeof(TriUv));
+        b.nodes = nullptr; b.tris = nullptr; b.uvs = nullptr;
+        h.dev_blas.clear();
+        return NRAYS_OK;
+    }
+    std::vector<std::pair<const BvhNode*, size_t>> nseg; std::vector<std::pair<const TriRec*, size_t>> tseg; std::vector<std::pair<const TriUv*, size_t>> useg;
+    for (const DeviceBlas& b : h.dev_blas) { nseg.push_back({b.nodes, b.num_nodes}); tseg.push_back({b.tris, b.num_refs}); useg.push_back({b.uvs, b.num_refs}); }
+    int rc = upload_joined(sc, nseg, h.nodes, &d.nodes);
+    if (rc == NRAYS_OK) rc = upload_joined(sc, tseg, h.tris, &d.tris);
+    if (rc == NRAYS_OK) rc = upload_joined(sc, useg, h.triuvs, &d.triuvs);
+    if (rc != NRAYS_OK) return rc;
+    for (DeviceBlas& b : h.dev_blas) free_device_blas(b);
+    h.dev_blas.clear();
+    return NRAYS_OK;
+}
+
+// The scene's small record arrays: ONE allocation and ONE copy (eight synchronous hipMalloc + hipMemcpy pairs before).
+// Reads host.instances .. shadow_planes.  Sets the eight record pointers of d; facts.allocs, facts.scene_bytes.
+static int upload_record_block(NraysScene* sc) {
+    const HostScene& h = sc->facts.host; DScene& d = sc->facts.d;
+    struct Part { const void* src; size_t bytes; const void** out; size_t at; };
+    std::vector<Part> parts;
+    size_t total = 0;
+    auto add = [&](const auto& v, auto** out) {
+        *out = nullptr;
+        if (v.empty()) return;
+        total = (total + 255u) & ~(size_t)255u;
+        parts.push_back(Part{v.data(), v.size() * sizeof(v[0]), (const void**)out, total});
+        total += v.size() * sizeof(v[0]);
+    };
+    add(h.instances, &d.instances); add(h.shadow_instances, &d.shadow_instances); add(h.links, &d.links); add(h.shadow_links, &d.shadow_links);
+    add(h.node_aabbs, &d.node_aabbs); add(h.lights, &d.lights); add(h.planes, &d.planes); add(h.shadow_planes, &d.shadow_planes);
+    if (!total) return NRAYS_OK;
+    void* blk = nullptr;
+    if (hipMalloc(&blk, total) != hipSuccess) return fail(NRAYS_ERR_OOM, "record allocation failed");
+    sc->facts.allocs.push_back(blk); sc->facts.scene_bytes += total;
+    std::vector<char> stage(total);
+    for (const Part& pt : parts) { std::memcpy(stage.data() + pt.at, pt.src, pt.bytes); *pt.out = (const char*)blk + pt.at; }
+    if (hipMemcpy(blk, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) return fail(NRAYS_ERR_HIP, "record upload failed");
+    return NRAYS_OK;
+}
+
+// Nodes, triangles and uvs, the joined record block, the textures, the shading records (with the textures' device pointers patched in).
+// Reads facts.host.  Sets every array pointer of facts.d except lds_blob and tiny (d is zeroed first); facts.allocs, facts.scene_bytes.
+static int upload_scene_arrays(NraysScene* sc) {
+    HostScene& h = sc->facts.host;
+    std::memset(&sc->facts.d, 0, sizeof sc->facts.d);
+    int rc = upload_bvh_arrays(sc);
+    if (rc == NRAYS_OK) rc = upload_record_block(sc);
+    if (rc != NRAYS_OK) return rc;
+    std::vector<TextureRec> trecs;
+    for (const HostTexture& t : h.textures) { // (the host copies of the texels stay until derive_scene_facts has looked at them)
+        void* p = nullptr;
+        if (hipMalloc(&p, t.bytes.size()) != hipSuccess) return fail(NRAYS_ERR_OOM, "texture allocation failed");
+        sc->facts.allocs.push_back(p);
+        sc->facts.scene_bytes += t.bytes.size();
+        if (hipMemcpy(p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) return fail(NRAYS_ERR_HIP, "texture upload failed");
+        TextureRec r = t.rec; r.texels = p; trecs.push_back(r);
+    }
+    for (size_t i = 0; i < h.shade.size(); ++i) { // patch the device texel pointers into the per-node shading records
+        if (h.shade_tex[i] >= 0) h.shade[i].tex.texels = trecs[h.shade_tex[i]].texels;
+        if (h.shade_alpha_tex[i] >= 0) h.shade[i].alpha_tex.texels = trecs[h.shade_alpha_tex[i]].texels;
+    }
+    return upload(sc, h.shade, &sc->facts.d.shade);
+}
+
+// The elisions (trace_device.h: light_is_dark, shade_hit) need x * 0 == 0 for everything they skip: any non-finite light, material colour or float texel, or a
+// negative shininess (0 * inf), switches them off for the scene (phong_material.rs:109-141, scene.rs:179-190 then produce NaN, and so do we).
+static bool scene_is_finite(const HostScene& h) {
+    bool finite = true;
+    for (const LightRec& l : h.lights) { for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(l.pos[a]) && std::isfinite(l.color[a]); finite = finite && std::isfinite(l.radius); }
+    for (const ShadeRec& m : h.shade) {
+        for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(m.ka[a]) && std::isfinite(m.kd[a]) && std::isfinite(m.ks[a]);
+        finite = finite && std::isfinite(m.shininess) && m.shininess >= 0.0f && std::isfinite(m.alpha) && std::isfinite(m.refl_mix) && std::isfinite(m.refl_atenuation) && std::isfinite(m.refr_coeff);
+    }
+    for (const HostTexture& t : h.textures) {
+        if (t.rec.format != NRAYS_TEXEL_RGBA32F) continue;
+        const float* f = (const float*)t.bytes.data();
+        for (size_t i = 0, n = t.bytes.size() / sizeof(float); i < n && finite; ++i) finite = std::isfinite(f[i]);
+    }
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(h.background[a]);
+    return finite;
+}
+
+// What follows from the scene and the switches alone: no HIP call except the query of the CU count.
+// Reads facts.host, facts.device, sw.  Sets d.no_elide, d.incoherent, the roots, counts and background of d; facts.spill_entries, num_cus, features, noxform,
+// park, light_lsl; the defaults that depend on the scene or on another switch: order.near_pixels, order.max_order_age, pipe.enabled, pipe.slots, pipe.lead_wgs, buf.count_rot.
+static void derive_scene_facts(NraysScene* sc) {
+    const HostScene& h = sc->facts.host; const Switches& sw = sc->sw; DScene& d = sc->facts.d;
+    d.no_elide = (!scene_is_finite(h) || !sw.elide) ? 1u : 0u;
+    // (such a scene's frames are rendered by the instrumented kernel, which does not decode the split entries of a cost-ordered list: no light-parallel / pixel-split tiles — light_lsl stays 0 below)
+    d.closest_root = h.closest_root; d.shadow_root = h.shadow_root;
+    d.num_planes = (uint32_t)h.planes.size(); d.num_lights = (uint32_t)h.lights.size();
+    for (int a = 0; a < 3; ++a) d.background[a] = h.background[a];
+    d.incoherent = h.any_incoherent && sw.node_quorum ? 1u : 0u; // quorum-ended node phases for hair-like meshes
+    // worst-case stack use: up to 3 deferred siblings per level of TLAS + BLAS (max_bvh_depth bounds each),
+    // one sentinel, the plane pseudo-leaves, a little slack; whatever exceeds the LDS part spills to HBM
+    const uint32_t need = 6u * (uint32_t)(h.max_bvh_depth + 1) + (uint32_t)h.planes.size() + 9u; // + the bottom marker
+    sc->facts.spill_entries = need > (uint32_t)kLdsStack ? need - (uint32_t)kLdsStack : 0u;
+    int cus = 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, sc->facts.device) == hipSuccess && cus > 0) sc->facts.num_cus = cus;
+    const int f = sc->facts.features = h.features ? h.features : kFeatAll;
+    // kFeatNoXform: scenes of TriMesh nodes only whose BLASes all sit in world space
+    bool all = (f == 2 || f == 6 || f == 18 || f == 22) && !h.links.empty();
+    for (const InstLink& l : h.links) all = all && (l.flags & kInstNoXform);
+    for (const InstLink& l : h.shadow_links) all = all && (l.flags & kInstNoXform);
+    sc->facts.noxform = all && sw.noxform;
+    sc->facts.park = sw.park;
+    // multi-light mesh scenes without double branching: 2, 4 or 8 lanes per pixel in a split tile
+    if (d.no_elide) sc->facts.light_lsl = 0;
+    else if ((f & kFeatMultiSample) && (f & kFeatMesh) && !(f & kFeatDouble) && h.lights.size() >= 2) { uint32_t l = 1; while (l < 3u && (2u << l) <= h.lights.size()) ++l; sc->facts.light_lsl = l; }
+    else if (NR_PIXEL_SPLIT && !(f & kFeatMultiSample) && (f & kFeatMesh) && (f & kFeatAlphaShadow) && !(f & kFeatDouble)) sc->facts.light_lsl = 3; // pixel split: 8 pixels per part
+    // Mesh scenes re-sort on every frame of a moving camera (age 0): the deep foliage chains of the sponza stand-in move between tiles with every pixel of camera motion, and a
+    // frame that reuses an order a few frames old waits for tiles it started late — 1.20 ms against 1.145 with the previous frame's costs, 1.04 at rest
+    // (profiles/r06_regimes_sweep.log).  Analytic scenes keep an order for 16 frames of a camera within two blocks (balls, moving: 0.0576 ms at 8 frames / 16 pixels,
+    // 0.0565 at 16 / 64, 0.0550 with an order that is never refreshed; 0.049 at rest).
+    sc->order.near_pixels = sw.near_pixels.value_or(h.any_mesh ? kNearPixels : 2.0 * kNearPixels);
+    sc->order.max_order_age = sw.max_order_age.value_or(h.any_mesh ? 0u : 16u);
+    sc->pipe.enabled = sw.pipeline;
+    sc->pipe.slots = sw.pipe_depth == 3 ? 6 : 4; sc->buf.count_rot = sc->pipe.slots; // (depth 2: the rotation and the slots of the two-stream pipeline)
+    sc->pipe.lead_wgs = sw.pipe_lead_wgs.value_or(sw.pipe_depth < 3);
+}
+
+// Small analytic scenes: one packed copy of the records for the kernels that read them from LDS (DScene::lds_blob).  Not when NRAYS_LDS_SCENE=0, for other
+// scenes, or when the copy exceeds kLdsSceneBytes.  Reads facts.host, facts.features, sw.lds_scene.  Sets d.lds_blob, d.lds_bytes, d.lds_off; adds kFeatLdsScene to facts.features.
+static int upload_lds_scene(NraysScene* sc) {
+    const HostScene& h = sc->facts.host; DScene& d = sc->facts.d;
+    d.lds_blob = nullptr; d.lds_bytes = 0;
+    const int f = sc->facts.features;
+    if (!(f == 1 || f == 5 || f == 17 || f == 21) || !sc->sw.lds_scene) return NRAYS_OK;
+    std::vector<uint8_t> blob;
+    auto section = [&](int k, const void* q, size_t n) { // 16-byte aligned sections
+        blob.resize((blob.size() + 15u) & ~(size_t)15u);
+        d.lds_off[k] = (uint32_t)blob.size();
+        const uint8_t* b = (const uint8_t*)q;
+        blob.insert(blob.end(), b, b + n);
+    };
+    section(kLdsNodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode));
+    section(kLdsInstances, h.instances.data(), h.instances.size() * sizeof(Instance));
+    section(kLdsShadowInstances, h.shadow_instances.data(), h.shadow_instances.size() * sizeof(Instance));
+    section(kLdsLinks, h.links.data(), h.links.size() * sizeof(InstLink));
+    section(kLdsShadowLinks, h.shadow_links.data(), h.shadow_links.size() * sizeof(InstLink));
+    section(kLdsShade, h.shade.data(), h.shade.size() * sizeof(ShadeRec));
+    section(kLdsNodeAabbs, h.node_aabbs.data(), h.node_aabbs.size() * sizeof(double));
+    section(kLdsLights, h.lights.data(), h.lights.size() * sizeof(LightRec));
+    section(kLdsPlanes, h.planes.data(), h.planes.size() * sizeof(int32_t));
+    section(kLdsShadowPlanes, h.shadow_planes.data(), h.shadow_planes.size() * sizeof(int32_t));
+    blob.resize((blob.size() + 15u) & ~(size_t)15u);
+    if (blob.empty() || blob.size() > kLdsSceneBytes) return NRAYS_OK;
+    std::vector<uint32_t> words(blob.size() / 4);
+    std::memcpy(words.data(), blob.data(), blob.size());
+    const int rc = upload(sc, words, &d.lds_blob);
+    if (rc != NRAYS_OK) return rc;
+    d.lds_bytes = (uint32_t)blob.size();
+    sc->facts.features |= kFeatLdsScene;
+    return NRAYS_OK;
+}
+
+// Opaque analytic scenes of at most kTinyLeaves TLAS leaves (planes included) with their records in LDS: one TinyLeaf per leaf of each TLAS for the
+// stackless queries of the kFeatTinyScene kernels (trace_device.h: tiny_closest, tiny_shadow).  Pixels do not depend on it (NRAYS_TINY_SCENE=0: the TLAS walk, A/B).
+// Reads facts.host, facts.features (after upload_lds_scene), sw.tiny_scene.  Sets d.tiny, d.tiny_n, d.tiny_shadow_n, facts.tiny.
+static int upload_tiny_leaves(NraysScene* sc) {
+    const HostScene& h = sc->facts.host; DScene& d = sc->facts.d;
+    d.tiny = nullptr; d.tiny_n = d.tiny_shadow_n = 0u;
+    const int f = sc->facts.features;
+    if (!((f == (kFeatAnalytic | kFeatLdsScene) || f == (kFeatAnalytic | kFeatMultiSample | kFeatLdsScene)) && !h.instances.empty() &&
+          h.instances.size() <= kTinyLeaves && h.shadow_instances.size() <= kTinyLeaves && sc->sw.tiny_scene)) return NRAYS_OK;
+    std::vector<TinyLeaf> leaves;
+    auto add = [&](const std::vector<Instance>& insts) {
+        for (size_t k = 0; k < insts.size(); ++k) {
+            const Instance& in = insts[k];
+            TinyLeaf lf{};
+            lf.kind = in.kind; lf.flags = in.flags; lf.node_id = in.node_id; lf.inst = (uint32_t)k;
+            lf.radius = in.params[0];
+            for (int a = 0; a < 3; ++a) lf.center[a] = in.trans[a];
+            if (in.node_id >= 0 && 6 * (size_t)in.node_id + 6 <= h.node_aabbs.size())
+                for (int a = 0; a < 6; ++a) lf.aabb[a] = h.node_aabbs[6 * (size_t)in.node_id + a];
+            leaves.push_back(lf);
+        }
+    };
+    add(h.instances); add(h.shadow_instances);
+    const int rc = upload(sc, leaves, &d.tiny);
+    if (rc != NRAYS_OK) return rc;
+    d.tiny_n = (uint32_t)h.instances.size(); d.tiny_shadow_n = (uint32_t)h.shadow_instances.size();
+    sc->facts.tiny = true;
+    return NRAYS_OK;
+}
+
+// k_seed_costs: world AABBs of the nodes that can continue a chain (transparent / alpha-mapped / reflective), as f32.  A scene without such a node uploads nothing.
+// Reads facts.host.  Sets facts.d_seed_boxes, facts.seed_boxes.
+static int upload_seed_boxes(NraysScene* sc) {
+    const HostScene& h = sc->facts.host;
+    std::vector<float> boxes;
+    for (size_t i = 0; i < h.shade.size() && boxes.size() < 6u * 2048u; ++i) {
+        const ShadeRec& sr = h.shade[i];
+        if (!(sr.alpha < 1.0f || h.shade_alpha_tex[i] >= 0 || sr.refl_mix != 0.0f)) continue;
+        const double* b = h.node_aabbs.data() + 6 * i;
+        bool finite = true;
+        for (int a = 0; a < 6; ++a) finite = finite && std::isfinite(b[a]) && std::fabs(b[a]) < 1e30;
+        if (!finite) continue;
+        for (int a = 0; a < 6; ++a) boxes.push_back((float)b[a]);
+    }
+    // (scenes without such a node — opaque hair — get no guess: a frame in image order.  Their nodes' boxes priced by the chord a ray spends inside, round 6: hairball
+    // cold frame 2.18 ms against 2.13 without — the order it buys is worth less than the two launches it costs: profiles/r06_regimes_sweep.log)
+    const float* dptr = nullptr;
+    const int rc = upload(sc, boxes, &dptr);
+    if (rc != NRAYS_OK) return rc;
+    sc->facts.d_seed_boxes = dptr; sc->facts.seed_boxes = (uint32_t)(boxes.size() / 6);
+    return NRAYS_OK;
+}
+
+// The handle's own device state: the rotating counter sets, the cost meta words, the primary-kernel counter snapshot, and what a first frame would allocate
+// (preallocate_first_frame, unless NRAYS_PREALLOC=0).  Reads sw.prealloc and what preallocate_first_frame reads.  Sets buf.d_counts_set, d_counters_set, d_counts,
+// d_counters; order.d_cost_meta; ring.d_counters_primary; the first-frame buffers of buf, order, ring and last.
+static int allocate_handle_state(NraysScene* sc, StageClock& clock) {
+    for (int k = 0; k < NraysScene::kCountSets; ++k) {
+        if (hipMalloc((void**)&sc->buf.d_counts_set[k], kNumCounts * sizeof(uint32_t)) != hipSuccess ||
+            hipMalloc((void**)&sc->buf.d_counters_set[k], sizeof(DeviceCounters)) != hipSuccess)
+            return fail(NRAYS_ERR_OOM, "counter allocation failed");
+        if (hipMemset(sc->buf.d_counts_set[k], 0, kNumCounts * sizeof(uint32_t)) != hipSuccess ||
+            hipMemset(sc->buf.d_counters_set[k], 0, sizeof(DeviceCounters)) != hipSuccess)
+            return fail(NRAYS_ERR_HIP, "counter memset failed");
+    }
+    sc->buf.d_counts = sc->buf.d_counts_set[0]; sc->buf.d_counters = sc->buf.d_counters_set[0];
+    if (hipMalloc((void**)&sc->order.d_cost_meta, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(sc->order.d_cost_meta, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
+        return fail(NRAYS_ERR_OOM, "cost-meta allocation failed");
+    clock.mark("records, switches, counters");
+    if (hipMalloc((void**)&sc->ring.d_counters_primary, sizeof(DeviceCounters)) != hipSuccess)
+        return fail(NRAYS_ERR_OOM, "counter allocation failed");
+    // (own_stream is created by the first entry point that needs it, ensure_own_stream(): a handle that is only ever rendered on the caller's streams leaves its
+    // hardware queue to the internal streams of the pipelined frames — a stream that exists holds a queue, and a process has four)
+    // (the ring's timing events are created by the first frame that records into a slot: 1 024 hipEventCreate cost 0.6 ms of every scene creation)
+    clock.mark("stream + event ring");
+    if (sc->sw.prealloc) preallocate_first_frame(sc);
+    clock.mark("first-frame buffers");
+    return NRAYS_OK;
+}
 
 } // namespace nrays
 
@@ -107,8 +372,9 @@ extern "C" {
 uint32_t nrays_abi_version(void) { return NRAYS_ABI_VERSION; }
 const char* nrays_last_error(void) { return g_last_error.c_str(); }
 uint32_t nrays_tile_rows(const NraysRenderParams* params) { return params ? tile_rows(params) : 0; }
-uint64_t nrays_scene_device_bytes(const NraysScene* scene) { return scene ? scene->scene_bytes : 0; }
+uint64_t nrays_scene_device_bytes(const NraysScene* scene) { return scene ? scene->facts.scene_bytes : 0; }
 
+// The driver: switches, host scene, then the phases above in the order of their HIP calls.
 int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     if (!desc || !out_scene) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     *out_scene = nullptr;
@@ -117,296 +383,61 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
     NraysScene* sc = new (std::nothrow) NraysScene();
     if (!sc) return fail(NRAYS_ERR_OOM, "host allocation failed");
     auto bail = [&](int rc) { nrays_scene_destroy(sc); return rc; };
-    if (hipGetDevice(&sc->device) != hipSuccess) return bail(fail(NRAYS_ERR_HIP, "hipGetDevice failed"));
+    if (hipGetDevice(&sc->facts.device) != hipSuccess) return bail(fail(NRAYS_ERR_HIP, "hipGetDevice failed"));
+    sc->sw = read_switches();
+    HostScene& h = sc->facts.host;
     std::string err;
     const auto t_create0 = std::chrono::steady_clock::now();
-    auto t_stage = t_create0;
-    const bool stage_times = getenv("NRAYS_BUILD_TIMES") != nullptr;
-    auto stage = [&](const char* what) { // NRAYS_BUILD_TIMES: where nrays_scene_create spends its time
-        if (!stage_times) return;
-        const auto now = std::chrono::steady_clock::now();
-        fprintf(stderr, "  nrays_scene_create: %s %.2f ms\n", what, std::chrono::duration<double, std::milli>(now - t_stage).count());
-        t_stage = now;
-    };
-    int rc = build_host_scene(desc, sc->host, err);
-    stage("build_host_scene (BLAS + TLAS builds)");
+    StageClock clock{sc->sw.build_times, t_create0};
+    int rc = build_host_scene(desc, sc->sw, h, err);
+    clock.mark("build_host_scene (BLAS + TLAS builds)");
     if (rc != NRAYS_OK) return bail(fail(rc, err));
-    HostScene& h = sc->host;
     const auto t_create1 = std::chrono::steady_clock::now();
-    std::memset(&sc->d, 0, sizeof sc->d);
-    if (h.dev_blas.size() == 1 && h.tris.empty() && h.triuvs.empty() && h.dev_blas[0].nodes && h.dev_blas[0].num_nodes + h.nodes.size() <= h.dev_blas[0].node_capacity) {
-        // ONE device-built BLAS and nothing but TLAS nodes from the host (a single large mesh): the builder's arrays ARE the scene's arrays — the host
-        // nodes go into the spare slots behind the BLAS; no second allocation, no copy and no release of gigabytes (0.2 s for the hairball stand-in)
-        nrays::DeviceBlas& b = h.dev_blas[0];
-        if (!h.nodes.empty() && hipMemcpy(b.nodes + b.num_nodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode), hipMemcpyHostToDevice) != hipSuccess)
-            return bail(fail(NRAYS_ERR_HIP, "upload of the TLAS nodes failed"));
-        sc->d.nodes = b.nodes; sc->d.tris = b.tris; sc->d.triuvs = b.uvs;
-        sc->allocs.push_back(b.nodes); sc->allocs.push_back(b.tris); sc->allocs.push_back(b.uvs);
-        sc->scene_bytes += (b.num_nodes + h.nodes.size()) * sizeof(BvhNode) + b.num_refs * (sizeof(TriRec) + sizeof(TriUv));
-        b.nodes = nullptr; b.tris = nullptr; b.uvs = nullptr;
-        h.dev_blas.clear();
-    } else {
-        std::vector<std::pair<const BvhNode*, size_t>> nseg; std::vector<std::pair<const TriRec*, size_t>> tseg; std::vector<std::pair<const TriUv*, size_t>> useg;
-        for (const nrays::DeviceBlas& b : h.dev_blas) { nseg.push_back({b.nodes, b.num_nodes}); tseg.push_back({b.tris, b.num_refs}); useg.push_back({b.uvs, b.num_refs}); }
-        if ((rc = upload_joined(sc, nseg, h.nodes, &sc->d.nodes)) != NRAYS_OK) return bail(rc);
-        if ((rc = upload_joined(sc, tseg, h.tris, &sc->d.tris)) != NRAYS_OK) return bail(rc);
-        if ((rc = upload_joined(sc, useg, h.triuvs, &sc->d.triuvs)) != NRAYS_OK) return bail(rc);
-        for (nrays::DeviceBlas& b : h.dev_blas) nrays::free_device_blas(b);
-        h.dev_blas.clear();
-    }
-    {   // the scene's small record arrays: ONE allocation and ONE copy (eight synchronous hipMalloc + hipMemcpy pairs before)
-        struct Part { const void* src; size_t bytes; const void** out; size_t at; };
-        std::vector<Part> parts;
-        size_t total = 0;
-        auto add = [&](const auto& v, auto** out) {
-            *out = nullptr;
-            if (v.empty()) return;
-            total = (total + 255u) & ~(size_t)255u;
-            parts.push_back(Part{v.data(), v.size() * sizeof(v[0]), (const void**)out, total});
-            total += v.size() * sizeof(v[0]);
-        };
-        add(h.instances, &sc->d.instances); add(h.shadow_instances, &sc->d.shadow_instances); add(h.links, &sc->d.links); add(h.shadow_links, &sc->d.shadow_links);
-        add(h.node_aabbs, &sc->d.node_aabbs); add(h.lights, &sc->d.lights); add(h.planes, &sc->d.planes); add(h.shadow_planes, &sc->d.shadow_planes);
-        if (total) {
-            void* blk = nullptr;
-            if (hipMalloc(&blk, total) != hipSuccess) return bail(fail(NRAYS_ERR_OOM, "record allocation failed"));
-            sc->allocs.push_back(blk); sc->scene_bytes += total;
-            std::vector<char> stage(total);
-            for (const Part& pt : parts) { std::memcpy(stage.data() + pt.at, pt.src, pt.bytes); *pt.out = (const char*)blk + pt.at; }
-            if (hipMemcpy(blk, stage.data(), total, hipMemcpyHostToDevice) != hipSuccess) return bail(fail(NRAYS_ERR_HIP, "record upload failed"));
-        }
-    }
-    {   // the elisions (trace_device.h: light_is_dark, shade_hit) need x * 0 == 0 for everything they skip: any non-finite light, material colour or float texel, or a
-        // negative shininess (0 * inf), switches them off for this scene (phong_material.rs:109-141, scene.rs:179-190 then produce NaN, and so do we)
-        bool finite = true;
-        for (const LightRec& l : h.lights) { for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(l.pos[a]) && std::isfinite(l.color[a]); finite = finite && std::isfinite(l.radius); }
-        for (const ShadeRec& m : h.shade) {
-            for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(m.ka[a]) && std::isfinite(m.kd[a]) && std::isfinite(m.ks[a]);
-            finite = finite && std::isfinite(m.shininess) && m.shininess >= 0.0f && std::isfinite(m.alpha) && std::isfinite(m.refl_mix) && std::isfinite(m.refl_atenuation) && std::isfinite(m.refr_coeff);
-        }
-        for (const HostTexture& t : h.textures) {
-            if (t.rec.format != NRAYS_TEXEL_RGBA32F) continue;
-            const float* f = (const float*)t.bytes.data();
-            for (size_t i = 0, n = t.bytes.size() / sizeof(float); i < n && finite; ++i) finite = std::isfinite(f[i]);
-        }
-        for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(h.background[a]);
-        const char* e = getenv("NRAYS_ELIDE"); // =0: never (A/B)
-        sc->d.no_elide = (!finite || (e && atoi(e) == 0)) ? 1u : 0u;
-        // (such a scene's frames are rendered by the instrumented kernel, which does not decode the split entries of a cost-ordered list: no light-parallel / pixel-split tiles — light_lsl stays 0 below)
-    }
-    std::vector<TextureRec> trecs;
-    for (HostTexture& t : h.textures) {
-        void* p = nullptr;
-        if (hipMalloc(&p, t.bytes.size()) != hipSuccess) return bail(fail(NRAYS_ERR_OOM, "texture allocation failed"));
-        sc->allocs.push_back(p);
-        sc->scene_bytes += t.bytes.size();
-        if (hipMemcpy(p, t.bytes.data(), t.bytes.size(), hipMemcpyHostToDevice) != hipSuccess) return bail(fail(NRAYS_ERR_HIP, "texture upload failed"));
-        TextureRec r = t.rec; r.texels = p; trecs.push_back(r);
-        std::vector<uint8_t>().swap(t.bytes);
-    }
-    for (size_t i = 0; i < h.shade.size(); ++i) { // patch the device texel pointers into the per-node shading records
-        if (h.shade_tex[i] >= 0) h.shade[i].tex.texels = trecs[h.shade_tex[i]].texels;
-        if (h.shade_alpha_tex[i] >= 0) h.shade[i].alpha_tex.texels = trecs[h.shade_alpha_tex[i]].texels;
-    }
-    if ((rc = upload(sc, h.shade, &sc->d.shade)) != NRAYS_OK) return bail(rc);
-    stage("uploads (nodes, triangles, records, textures)");
-    if (getenv("NRAYS_BUILD_TIMES") && h.tris.size() + h.dev_tris > 1000000)
+    if ((rc = upload_scene_arrays(sc)) != NRAYS_OK) return bail(rc);
+    clock.mark("uploads (nodes, triangles, records, textures)");
+    if (sc->sw.build_times && h.tris.size() + h.dev_tris > 1000000)
         fprintf(stderr, "  nrays_scene_create: build_host_scene %.2f s, uploads %.2f s\n", std::chrono::duration<double>(t_create1 - t_create0).count(),
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create1).count());
-    sc->d.closest_root = h.closest_root; sc->d.shadow_root = h.shadow_root;
-    sc->d.num_planes = (uint32_t)h.planes.size(); sc->d.num_lights = (uint32_t)h.lights.size();
-    for (int a = 0; a < 3; ++a) sc->d.background[a] = h.background[a];
-    {   // NRAYS_NODE_QUORUM=0 keeps every node phase running until its last lane holds a leaf (A/B switch)
-        const char* e = getenv("NRAYS_NODE_QUORUM");
-        sc->d.incoherent = h.any_incoherent && !(e && atoi(e) == 0) ? 1u : 0u;
-    }
-    // stack bound: one deferred sibling per level of TLAS and BLAS, plus the sentinel
-    // worst-case stack use: up to 3 deferred siblings per level of TLAS + BLAS (max_bvh_depth bounds each),
-    // one sentinel, the plane pseudo-leaves, a little slack; whatever exceeds the LDS part spills to HBM
-    {
-        uint32_t need = 6u * (uint32_t)(h.max_bvh_depth + 1) + (uint32_t)h.planes.size() + 9u; // + the bottom marker
-        sc->spill_entries = need > (uint32_t)kLdsStack ? need - (uint32_t)kLdsStack : 0u;
-    }
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, sc->device) == hipSuccess && cus > 0) sc->num_cus = cus;
-    }
-    sc->features = h.features ? h.features : kFeatAll;
-    {   // kFeatNoXform: scenes of TriMesh nodes only whose BLASes all sit in world space (NRAYS_NOXFORM=0: the general permutations, A/B)
-        const int f = sc->features;
-        bool all = (f == 2 || f == 6 || f == 18 || f == 22) && !h.links.empty();
-        for (const InstLink& l : h.links) all = all && (l.flags & kInstNoXform);
-        for (const InstLink& l : h.shadow_links) all = all && (l.flags & kInstNoXform);
-        const char* e = getenv("NRAYS_NOXFORM");
-        sc->noxform = all && !(e && atoi(e) == 0);
-        const char* pe = getenv("NRAYS_PARK"); // =0: the three-wave multi-light kernels keep a hit's shading state in registers / scratch (A/B)
-        sc->park = !(pe && atoi(pe) == 0);
-    }
-    // small analytic scenes: one packed copy of the records for the kernels that read them from LDS (DScene::lds_blob)
-    sc->d.lds_blob = nullptr; sc->d.lds_bytes = 0;
-    { const char* e = getenv("NRAYS_LDS_SCENE");
-      const int f = sc->features;
-      if ((f == 1 || f == 5 || f == 17 || f == 21) && !(e && atoi(e) == 0)) {
-        std::vector<uint8_t> blob;
-        auto section = [&](int k, const void* q, size_t n) { // 16-byte aligned sections
-            blob.resize((blob.size() + 15u) & ~(size_t)15u);
-            sc->d.lds_off[k] = (uint32_t)blob.size();
-            const uint8_t* b = (const uint8_t*)q;
-            blob.insert(blob.end(), b, b + n);
-        };
-        section(kLdsNodes, h.nodes.data(), h.nodes.size() * sizeof(BvhNode));
-        section(kLdsInstances, h.instances.data(), h.instances.size() * sizeof(Instance));
-        section(kLdsShadowInstances, h.shadow_instances.data(), h.shadow_instances.size() * sizeof(Instance));
-        section(kLdsLinks, h.links.data(), h.links.size() * sizeof(InstLink));
-        section(kLdsShadowLinks, h.shadow_links.data(), h.shadow_links.size() * sizeof(InstLink));
-        section(kLdsShade, h.shade.data(), h.shade.size() * sizeof(ShadeRec));
-        section(kLdsNodeAabbs, h.node_aabbs.data(), h.node_aabbs.size() * sizeof(double));
-        section(kLdsLights, h.lights.data(), h.lights.size() * sizeof(LightRec));
-        section(kLdsPlanes, h.planes.data(), h.planes.size() * sizeof(int32_t));
-        section(kLdsShadowPlanes, h.shadow_planes.data(), h.shadow_planes.size() * sizeof(int32_t));
-        blob.resize((blob.size() + 15u) & ~(size_t)15u);
-        if (!blob.empty() && blob.size() <= kLdsSceneBytes) {
-            std::vector<uint32_t> words(blob.size() / 4);
-            std::memcpy(words.data(), blob.data(), blob.size());
-            if ((rc = upload(sc, words, &sc->d.lds_blob)) != NRAYS_OK) return bail(rc);
-            sc->d.lds_bytes = (uint32_t)blob.size();
-            sc->features |= kFeatLdsScene;
-        }
-      }
-    }
-    // opaque analytic scenes of at most kTinyLeaves TLAS leaves (planes included) with their records in LDS: one TinyLeaf per leaf of each TLAS for the
-    // stackless queries of the kFeatTinyScene kernels (trace_device.h: tiny_closest, tiny_shadow).  Pixels do not depend on it (NRAYS_TINY_SCENE=0: the TLAS walk, A/B)
-    sc->d.tiny = nullptr; sc->d.tiny_n = sc->d.tiny_shadow_n = 0u;
-    { const char* e = getenv("NRAYS_TINY_SCENE");
-      const int f = sc->features;
-      if ((f == (kFeatAnalytic | kFeatLdsScene) || f == (kFeatAnalytic | kFeatMultiSample | kFeatLdsScene)) && !h.instances.empty() &&
-          h.instances.size() <= kTinyLeaves && h.shadow_instances.size() <= kTinyLeaves && !(e && atoi(e) == 0)) {
-        std::vector<TinyLeaf> leaves;
-        auto add = [&](const std::vector<Instance>& insts) {
-            for (size_t k = 0; k < insts.size(); ++k) {
-                const Instance& in = insts[k];
-                TinyLeaf lf{};
-                lf.kind = in.kind; lf.flags = in.flags; lf.node_id = in.node_id; lf.inst = (uint32_t)k;
-                lf.radius = in.params[0];
-                for (int a = 0; a < 3; ++a) lf.center[a] = in.trans[a];
-                if (in.node_id >= 0 && 6 * (size_t)in.node_id + 6 <= h.node_aabbs.size())
-                    for (int a = 0; a < 6; ++a) lf.aabb[a] = h.node_aabbs[6 * (size_t)in.node_id + a];
-                leaves.push_back(lf);
-            }
-        };
-        add(h.instances); add(h.shadow_instances);
-        if ((rc = upload(sc, leaves, &sc->d.tiny)) != NRAYS_OK) return bail(rc);
-        sc->d.tiny_n = (uint32_t)h.instances.size(); sc->d.tiny_shadow_n = (uint32_t)h.shadow_instances.size();
-        sc->tiny = true;
-      }
-    }
-    {   // k_seed_costs: world AABBs of the nodes that can continue a chain (transparent / alpha-mapped / reflective), as f32
-        std::vector<float> boxes;
-        for (size_t i = 0; i < h.shade.size() && boxes.size() < 6u * 2048u; ++i) {
-            const ShadeRec& sr = h.shade[i];
-            if (!(sr.alpha < 1.0f || h.shade_alpha_tex[i] >= 0 || sr.refl_mix != 0.0f)) continue;
-            const double* b = h.node_aabbs.data() + 6 * i;
-            bool finite = true;
-            for (int a = 0; a < 6; ++a) finite = finite && std::isfinite(b[a]) && std::fabs(b[a]) < 1e30;
-            if (!finite) continue;
-            for (int a = 0; a < 6; ++a) boxes.push_back((float)b[a]);
-        }
-        // (scenes without such a node — opaque hair — get no guess: a frame in image order.  Their nodes' boxes priced by the chord a ray spends inside, round 6: hairball
-        // cold frame 2.18 ms against 2.13 without — the order it buys is worth less than the two launches it costs: profiles/r06_regimes_sweep.log)
-        const float* dptr = nullptr;
-        if ((rc = upload(sc, boxes, &dptr)) != NRAYS_OK) return bail(rc);
-        sc->d_seed_boxes = dptr; sc->seed_boxes = (uint32_t)(boxes.size() / 6);
-        if (const char* e = getenv("NRAYS_COST_SEED")) { sc->seed_enabled = atoi(e) != 0; if (atoi(e) == 4) sc->seed_rays = 4u; if (atoi(e) == 1) sc->seed_rays = 1u; }
-    }
-    if (const char* e = getenv("NRAYS_RAY_REORDER")) sc->ray_reorder = atoi(e); // 0: never, 2: every batch the caller called unordered (tests), else by size
-    if (const char* e = getenv("NRAYS_MAX_PRIMARY")) { sc->max_primary_per_launch = (uint64_t)std::max(1ll, atoll(e)); sc->max_primary_forced = true; }
-    if (const char* e = getenv("NRAYS_LANE_LOG2")) sc->lane_log2_override = std::max(0, std::min(6, atoi(e)));
-    if (const char* e = getenv("NRAYS_EVENT_STRIDE")) sc->event_stride = (uint32_t)std::max(1, atoi(e));
-    if (const char* e = getenv("NRAYS_GRAB")) sc->grab_override = std::max(0, atoi(e));
-    if (const char* e = getenv("NRAYS_LPT")) sc->lpt_enabled = atoi(e) != 0;
-    if (const char* e = getenv("NRAYS_SCREEN_CULL")) sc->cull_enabled = atoi(e) != 0;
-    { const int f = sc->features; // multi-light mesh scenes without double branching: 2, 4 or 8 lanes per pixel in a split tile
-      if (sc->d.no_elide) sc->light_lsl = 0;
-      else if ((f & kFeatMultiSample) && (f & kFeatMesh) && !(f & kFeatDouble) && h.lights.size() >= 2) { uint32_t l = 1; while (l < 3u && (2u << l) <= h.lights.size()) ++l; sc->light_lsl = l; }
-      else if (NR_PIXEL_SPLIT && !(f & kFeatMultiSample) && (f & kFeatMesh) && (f & kFeatAlphaShadow) && !(f & kFeatDouble)) sc->light_lsl = 3; } // pixel split: 8 pixels per part
-    if (const char* e = getenv("NRAYS_LIGHT_SPLIT")) sc->light_split_factor = (float)atof(e);
-    if (const char* e = getenv("NRAYS_OCC")) sc->occ_override = atoi(e);
-    if (const char* e = getenv("NRAYS_WAVEFRONT")) sc->wavefront_mode = atoi(e);
-    if (const char* e = getenv("NRAYS_LPT_ANALYTIC")) sc->lpt_analytic = atoi(e) != 0;
-    if (const char* e = getenv("NRAYS_LPT_REUSE")) sc->lpt_reuse = atoi(e) != 0;
-    if (const char* e = getenv("NRAYS_NEAR_REUSE")) sc->near_reuse = atoi(e) != 0;
-    // Mesh scenes re-sort on every frame of a moving camera (age 0): the deep foliage chains of the sponza stand-in move between tiles with every pixel of camera motion, and a
-    // frame that reuses an order a few frames old waits for tiles it started late — 1.20 ms against 1.145 with the previous frame's costs, 1.04 at rest
-    // (profiles/r06_regimes_sweep.log).  Analytic scenes keep an order for 16 frames of a camera within two blocks (balls, moving: 0.0576 ms at 8 frames / 16 pixels,
-    // 0.0565 at 16 / 64, 0.0550 with an order that is never refreshed; 0.049 at rest).
-    sc->near_pixels = sc->host.any_mesh ? kNearPixels : 2.0 * kNearPixels; sc->max_order_age = sc->host.any_mesh ? 0u : 16u;
-    if (const char* e = getenv("NRAYS_SPLIT_HYST")) sc->split_hyst = (float)atof(e);
-    if (const char* e = getenv("NRAYS_HOST_TIMES")) sc->host_times_from = (uint64_t)std::max(1ll, atoll(e));
-    if (const char* e = getenv("NRAYS_PIPELINE")) { sc->pipeline = atoi(e) != 0; sc->pipeline_always = atoi(e) == 2; }
-    if (const char* e = getenv("NRAYS_PIPELINE_DEPTH")) sc->pipe_depth = std::max(1, std::min((int)NraysScene::kPipeStreams, atoi(e)));
-    sc->pipe_slots = sc->pipe_depth == 3 ? 6 : 4; sc->count_rot = sc->pipe_slots; // (depth 2: the rotation and the slots of the two-stream pipeline)
-    sc->pipe_lead_wgs = sc->pipe_depth < 3;
-    if (const char* e = getenv("NRAYS_PIPELINE_LEAD_WGS")) sc->pipe_lead_wgs = atoi(e) != 0;
-    if (const char* e = getenv("NRAYS_NEAR_PIXELS")) sc->near_pixels = atof(e);
-    if (const char* e = getenv("NRAYS_ORDER_AGE")) sc->max_order_age = (uint32_t)std::max(0, atoi(e));
-    if (const char* e = getenv("NRAYS_LEAD_WGS")) sc->lead_mode = atoi(e) != 0;
-    if (const char* e = getenv("NRAYS_LONE_FACTOR")) sc->lone_factor = atof(e);
-    if (const char* e = getenv("NRAYS_LEAD_PER_WG")) sc->lead_per_wg = std::max(1, std::min(64, atoi(e)));
-    if (const char* e = getenv("NRAYS_GRID_WG_PER_CU")) sc->grid_wg_per_cu = std::max(0, atoi(e));
+    derive_scene_facts(sc);
+    if ((rc = upload_lds_scene(sc)) != NRAYS_OK || (rc = upload_tiny_leaves(sc)) != NRAYS_OK || (rc = upload_seed_boxes(sc)) != NRAYS_OK) return bail(rc);
     // release bulk host copies
     std::vector<BvhNode>().swap(h.nodes); std::vector<TriRec>().swap(h.tris); std::vector<TriUv>().swap(h.triuvs);
-
-    for (int k = 0; k < NraysScene::kCountSets; ++k) {
-        if (hipMalloc((void**)&sc->d_counts_set[k], kNumCounts * sizeof(uint32_t)) != hipSuccess ||
-            hipMalloc((void**)&sc->d_counters_set[k], sizeof(DeviceCounters)) != hipSuccess)
-            return bail(fail(NRAYS_ERR_OOM, "counter allocation failed"));
-        if (hipMemset(sc->d_counts_set[k], 0, kNumCounts * sizeof(uint32_t)) != hipSuccess ||
-            hipMemset(sc->d_counters_set[k], 0, sizeof(DeviceCounters)) != hipSuccess)
-            return bail(fail(NRAYS_ERR_HIP, "counter memset failed"));
-    }
-    sc->d_counts = sc->d_counts_set[0]; sc->d_counters = sc->d_counters_set[0];
-    if (hipMalloc((void**)&sc->d_cost_meta, 4 * sizeof(unsigned long long)) != hipSuccess || hipMemset(sc->d_cost_meta, 0, 4 * sizeof(unsigned long long)) != hipSuccess)
-        return bail(fail(NRAYS_ERR_OOM, "cost-meta allocation failed"));
-    stage("records, switches, counters");
-    if (hipMalloc((void**)&sc->d_counters_primary, sizeof(DeviceCounters)) != hipSuccess)
-        return bail(fail(NRAYS_ERR_OOM, "counter allocation failed"));
-    // (own_stream is created by the first entry point that needs it, ensure_own_stream(): a handle that is only ever rendered on the caller's streams leaves its
-    // hardware queue to the internal streams of the pipelined frames — a stream that exists holds a queue, and a process has four)
-    // (the ring's timing events are created by the first frame that records into a slot: 1 024 hipEventCreate cost 0.6 ms of every scene creation)
-    stage("stream + event ring");
-    preallocate_first_frame(sc);
-    stage("first-frame buffers");
+    for (HostTexture& t : h.textures) std::vector<uint8_t>().swap(t.bytes);
+    if ((rc = allocate_handle_state(sc, clock)) != NRAYS_OK) return bail(rc);
     *out_scene = sc;
     return NRAYS_OK;
 }
 
+// Frees the handle group by group, behind its last work.
 void nrays_scene_destroy(NraysScene* sc) {
     if (!sc) return;
-    (void)hipSetDevice(sc->device);
-    if (sc->have_last) (void)hipStreamSynchronize(sc->last_stream); // (the compose of every pipelined frame is there or ordered before it, behind its trace)
-    pipeline_release(sc);
-    for (void* p : sc->allocs) (void)hipFree(p);
-    for (nrays::DeviceBlas& b : sc->host.dev_blas) nrays::free_device_blas(b); // a creation that failed between the build and the upload
-    for (int k = 0; k < 2; ++k) if (sc->queue[k].block) (void)hipFree(sc->queue[k].block);
+    (void)hipSetDevice(sc->facts.device);
+    if (sc->last.have) (void)hipStreamSynchronize(sc->last.stream); // (the compose of every pipelined frame is there or ordered before it, behind its trace)
+    pipeline_release(sc); // pipe
+    // facts
+    for (void* p : sc->facts.allocs) (void)hipFree(p);
+    for (DeviceBlas& b : sc->facts.host.dev_blas) free_device_blas(b); // a creation that failed between the build and the upload
+    // buf (own_stream last, below)
+    for (int k = 0; k < 2; ++k) if (sc->buf.queue[k].block) (void)hipFree(sc->buf.queue[k].block);
     for (int k = 0; k < NraysScene::kCountSets; ++k) {
-        if (sc->d_counts_set[k]) (void)hipFree(sc->d_counts_set[k]);
-        if (sc->d_counters_set[k]) (void)hipFree(sc->d_counters_set[k]);
+        if (sc->buf.d_counts_set[k]) (void)hipFree(sc->buf.d_counts_set[k]);
+        if (sc->buf.d_counters_set[k]) (void)hipFree(sc->buf.d_counters_set[k]);
     }
-    for (void* q : {(void*)sc->d_spill, (void*)sc->d_fixed, (void*)sc->d_frame, (void*)sc->d_tile_cost, (void*)sc->d_tile_order, (void*)sc->d_order_len, (void*)sc->d_cost_stats, (void*)sc->d_cost_meta,
-                    (void*)sc->d_rgb8, (void*)sc->d_counters_primary}) if (q) (void)hipFree(q);
-    if (sc->h_cost_stats) (void)hipHostFree(sc->h_cost_stats);
-    if (sc->ev_stats) (void)hipEventDestroy(sc->ev_stats);
-    if (sc->ev_switch) (void)hipEventDestroy(sc->ev_switch);
-    for (int k = 0; k < 2; ++k) if (sc->ev_rec[k]) (void)hipEventDestroy(sc->ev_rec[k]);
-    for (int k = 0; k < NraysScene::kRing; ++k) {
-        if (sc->ev_begin[k]) (void)hipEventDestroy(sc->ev_begin[k]);
-        if (sc->ev_pbegin[k]) (void)hipEventDestroy(sc->ev_pbegin[k]);
-        if (sc->ev_pend[k]) (void)hipEventDestroy(sc->ev_pend[k]);
-        if (sc->ev_end[k]) (void)hipEventDestroy(sc->ev_end[k]);
-    }
+    for (void* q : {(void*)sc->buf.d_spill, (void*)sc->buf.d_fixed, (void*)sc->buf.d_frame, (void*)sc->buf.d_rgb8}) if (q) (void)hipFree(q);
+    // order
+    for (void* q : {(void*)sc->order.d_tile_cost, (void*)sc->order.d_tile_order, (void*)sc->order.d_order_len, (void*)sc->order.d_cost_stats, (void*)sc->order.d_cost_meta}) if (q) (void)hipFree(q);
+    if (sc->order.h_cost_stats) (void)hipHostFree(sc->order.h_cost_stats);
+    if (sc->order.ev_stats) (void)hipEventDestroy(sc->order.ev_stats);
+    for (int k = 0; k < 2; ++k) if (sc->order.ev_rec[k]) (void)hipEventDestroy(sc->order.ev_rec[k]);
+    // ring
+    if (sc->ring.d_counters_primary) (void)hipFree(sc->ring.d_counters_primary);
+    for (int k = 0; k < NraysScene::kRing; ++k)
+        for (hipEvent_t e : {sc->ring.ev_begin[k], sc->ring.ev_pbegin[k], sc->ring.ev_pend[k], sc->ring.ev_end[k]}) if (e) (void)hipEventDestroy(e);
+    // last
+    if (sc->last.ev_switch) (void)hipEventDestroy(sc->last.ev_switch);
     wavefront_release(sc);
     trace_workspace_release(sc);
-    if (sc->own_stream) (void)hipStreamDestroy(sc->own_stream);
+    if (sc->buf.own_stream) (void)hipStreamDestroy(sc->buf.own_stream);
     delete sc;
 }
 
@@ -432,27 +463,27 @@ static void fill_counters(NraysStats* out, const DeviceCounters& c) {
 int nrays_get_stats(NraysScene* sc, NraysStats* out) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     std::memset(out, 0, sizeof *out);
-    if (!sc->have_last) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
+    if (!sc->last.have) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
     DeviceCounters c;
-    HIP_TRY(hipMemcpy(&c, sc->d_counters, sizeof c, hipMemcpyDeviceToHost));
-    out->rays_primary = sc->last_primary;
+    HIP_TRY(hipMemcpy(&c, sc->buf.d_counters, sizeof c, hipMemcpyDeviceToHost));
+    out->rays_primary = sc->last.primary;
     fill_counters(out, c);
-    out->generations = c.max_depth; out->instrumented = sc->last_instrumented ? 1u : 0u;
+    out->generations = c.max_depth; out->instrumented = sc->last.instrumented ? 1u : 0u;
     out->reserved = c.max_chain_nodes; // instrumented renders: most AABB tests spent on one pixel's whole chain
     out->rays_shadow_elided = c.shadow_elided;
     // average the event timings of the frames recorded since the previous call (at most kRing)
-    uint64_t first = sc->frames_reported;
-    if (sc->frames_recorded - first > (uint64_t)NraysScene::kRing) first = sc->frames_recorded - NraysScene::kRing;
+    uint64_t first = sc->ring.frames_reported;
+    if (sc->ring.frames_recorded - first > (uint64_t)NraysScene::kRing) first = sc->ring.frames_recorded - NraysScene::kRing;
     double sum_p = 0.0, sum_t = 0.0; uint64_t n = 0;
-    for (uint64_t f = first; f < sc->frames_recorded; ++f) {
+    for (uint64_t f = first; f < sc->ring.frames_recorded; ++f) {
         int k = (int)(f % NraysScene::kRing);
         float ms_p = 0.f, ms_t = 0.f;
-        if (hipEventElapsedTime(&ms_p, sc->ev_pbegin[k], sc->ev_pend[k]) == hipSuccess &&
-            hipEventElapsedTime(&ms_t, sc->has_prepass[k] ? sc->ev_begin[k] : sc->ev_pbegin[k], sc->single_launch[k] ? sc->ev_pend[k] : sc->ev_end[k]) == hipSuccess) { sum_p += ms_p; sum_t += ms_t; ++n; }
+        if (hipEventElapsedTime(&ms_p, sc->ring.ev_pbegin[k], sc->ring.ev_pend[k]) == hipSuccess &&
+            hipEventElapsedTime(&ms_t, sc->ring.has_prepass[k] ? sc->ring.ev_begin[k] : sc->ring.ev_pbegin[k], sc->ring.single_launch[k] ? sc->ring.ev_pend[k] : sc->ring.ev_end[k]) == hipSuccess) { sum_p += ms_p; sum_t += ms_t; ++n; }
     }
-    sc->frames_reported = sc->frames_recorded;
+    sc->ring.frames_reported = sc->ring.frames_recorded;
     if (n) { out->kernel_ms_primary = sum_p / (double)n; out->kernel_ms_total = sum_t / (double)n; }
     out->frames_timed = (uint32_t)n;
     if (c.overflow) return fail(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: image is incomplete");
@@ -462,33 +493,33 @@ int nrays_get_stats(NraysScene* sc, NraysStats* out) {
 int nrays_get_tile_costs(NraysScene* sc, NraysTileCosts* out) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     std::memset(out, 0, sizeof *out);
-    if (!sc->have_last || !sc->d_tile_cost || !sc->cost_valid || sc->cost_tiles == 0) return fail(NRAYS_ERR_BAD_ARG, "no frame of this handle has recorded its tile costs");
-    HIP_TRY(hipSetDevice(sc->device));
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    std::vector<uint32_t> c(sc->cost_tiles);
-    HIP_TRY(hipMemcpy(c.data(), sc->d_tile_cost, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!sc->last.have || !sc->order.d_tile_cost || !sc->order.cost_valid || sc->order.cost_tiles == 0) return fail(NRAYS_ERR_BAD_ARG, "no frame of this handle has recorded its tile costs");
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    std::vector<uint32_t> c(sc->order.cost_tiles);
+    HIP_TRY(hipMemcpy(c.data(), sc->order.d_tile_cost, c.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     // The unit the schedule deals is a wave tile — or ONE PART of a tile the cost-ordered lists split: k_primary marks the record of a tile that ran in parts
     // (kCostSplit; the value is its most expensive part's cycles x 2^lsl, or x 3 for the pixel-split tiles of one-light frames).  max_cycles is the longest such
     // unit, sum_cycles what the waves spend: every part of a split tile counted (at its most expensive part's price: an upper bound).
-    const uint32_t lsl = sc->cost_split_lsl;
-    const bool multi = (sc->features & kFeatMultiSample) != 0;
+    const uint32_t lsl = sc->order.cost_split_lsl;
+    const bool multi = (sc->facts.features & kFeatMultiSample) != 0;
     for (uint32_t rec : c) {
         const uint32_t v = rec & kCostMask;
         uint64_t unit = v, n = 1;
         if (lsl && (rec & kCostSplit)) { unit = multi ? (uint64_t)(v >> lsl) : (uint64_t)(v / 3u); n = 1ull << lsl; }
         out->sum_cycles += unit * n * 16u; out->max_cycles = std::max<uint64_t>(out->max_cycles, unit * 16u);
     }
-    out->tiles = c.size(); out->resident_waves = (uint64_t)sc->cost_grid * (kBlock / 64);
-    if (sc->d_cost_meta) { // the recording launch about itself (DRender::cost_meta)
+    out->tiles = c.size(); out->resident_waves = (uint64_t)sc->order.cost_grid * (kBlock / 64);
+    if (sc->order.d_cost_meta) { // the recording launch about itself (DRender::cost_meta)
         unsigned long long m[4] = {0, 0, 0, 0};
-        HIP_TRY(hipMemcpy(m, sc->d_cost_meta, sizeof m, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(m, sc->order.d_cost_meta, sizeof m, hipMemcpyDeviceToHost));
         out->shader_clock_hz = m[3] ? (double)m[2] / ((double)m[3] * 1e-8) : 0.0;
     }
     {   // the recording launch between its events
         float ms = 0.0f;
         hipError_t e = hipErrorInvalidValue;
-        if (sc->rec_events_valid) e = hipEventElapsedTime(&ms, sc->ev_rec[0], sc->ev_rec[1]);
-        else if (sc->rec_slot >= 0 && sc->ev_pbegin[sc->rec_slot] && sc->ev_pend[sc->rec_slot]) e = hipEventElapsedTime(&ms, sc->ev_pbegin[sc->rec_slot], sc->ev_pend[sc->rec_slot]); // (the ring holds 256 timed frames)
+        if (sc->order.rec_events_valid) e = hipEventElapsedTime(&ms, sc->order.ev_rec[0], sc->order.ev_rec[1]);
+        else if (sc->order.rec_slot >= 0 && sc->ring.ev_pbegin[sc->order.rec_slot] && sc->ring.ev_pend[sc->order.rec_slot]) e = hipEventElapsedTime(&ms, sc->ring.ev_pbegin[sc->order.rec_slot], sc->ring.ev_pend[sc->order.rec_slot]); // (the ring holds 256 timed frames)
         if (e == hipSuccess) out->kernel_ms = ms; else (void)hipGetLastError();
     }
     return NRAYS_OK;
@@ -497,10 +528,10 @@ int nrays_get_tile_costs(NraysScene* sc, NraysTileCosts* out) {
 #if defined(NR_PHASE_TIMING) || defined(NR_DEBUG_TILE_COSTS)
 // Tuning builds only (tools/tile_costs.py): the per-wave-tile cycle counts (>> 4) of the last frame that recorded them.
 int nrays_debug_tile_costs(NraysScene* sc, uint32_t* out, uint32_t capacity, uint32_t* out_count) {
-    if (!sc || !sc->have_last || !sc->d_tile_cost) return NRAYS_ERR_BAD_ARG;
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    const uint32_t n = std::min(capacity, sc->tile_slots);
-    HIP_TRY(hipMemcpy(out, sc->d_tile_cost, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!sc || !sc->last.have || !sc->order.d_tile_cost) return NRAYS_ERR_BAD_ARG;
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    const uint32_t n = std::min(capacity, sc->order.tile_slots);
+    HIP_TRY(hipMemcpy(out, sc->order.d_tile_cost, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_count = n;
     return NRAYS_OK;
 }
@@ -508,28 +539,28 @@ int nrays_debug_tile_costs(NraysScene* sc, uint32_t* out, uint32_t capacity, uin
 #ifdef NR_DEBUG_TILE_COSTS
 // Tuning builds only (tools/tile_dump.py): k_seed_costs' guess of the last cold frame.
 int nrays_debug_seed_costs(NraysScene* sc, uint32_t* out, uint32_t capacity, uint32_t* out_count) {
-    if (!sc || !sc->have_last || !sc->d_seed_copy) return NRAYS_ERR_BAD_ARG;
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    const uint32_t n = std::min(capacity, sc->tile_slots);
-    HIP_TRY(hipMemcpy(out, sc->d_seed_copy, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!sc || !sc->last.have || !sc->order.d_seed_copy) return NRAYS_ERR_BAD_ARG;
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    const uint32_t n = std::min(capacity, sc->order.tile_slots);
+    HIP_TRY(hipMemcpy(out, sc->order.d_seed_copy, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_count = n;
     return NRAYS_OK;
 }
 // Tuning builds only (tools/wave_timeline.py): {kernel entry, first tile, exit, tiles} per wave of the last primary launch, 10 ns ticks.
 int nrays_debug_wave_times(NraysScene* sc, uint32_t* out, uint32_t capacity_waves, uint32_t* out_waves) {
-    if (!sc || !sc->have_last || !sc->d_wave_times) return NRAYS_ERR_BAD_ARG;
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    const uint32_t n = std::min<uint32_t>(capacity_waves, sc->dbg_grid * (kBlock / 64));
-    HIP_TRY(hipMemcpy(out, sc->d_wave_times, (size_t)n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!sc || !sc->last.have || !sc->order.d_wave_times) return NRAYS_ERR_BAD_ARG;
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    const uint32_t n = std::min<uint32_t>(capacity_waves, sc->order.dbg_grid * (kBlock / 64));
+    HIP_TRY(hipMemcpy(out, sc->order.d_wave_times, (size_t)n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_waves = n;
     return NRAYS_OK;
 }
 // The second record per wave: {ticks in work tiles, ticks in tiles that traced nothing, ticks in background rows, work tiles | miss tiles << 8 | rows << 16 | longest work tile / 16 ticks << 24}.
 int nrays_debug_wave_times2(NraysScene* sc, uint32_t* out, uint32_t capacity_waves, uint32_t* out_waves) {
-    if (!sc || !sc->have_last || !sc->d_wave_times) return NRAYS_ERR_BAD_ARG;
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    const uint32_t n = std::min<uint32_t>(capacity_waves, sc->dbg_grid * (kBlock / 64));
-    HIP_TRY(hipMemcpy(out, sc->d_wave_times + (size_t)kMaxGrid * (kBlock / 64) * 4, (size_t)n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (!sc || !sc->last.have || !sc->order.d_wave_times) return NRAYS_ERR_BAD_ARG;
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    const uint32_t n = std::min<uint32_t>(capacity_waves, sc->order.dbg_grid * (kBlock / 64));
+    HIP_TRY(hipMemcpy(out, sc->order.d_wave_times + (size_t)kMaxGrid * (kBlock / 64) * 4, (size_t)n * 4 * sizeof(uint32_t), hipMemcpyDeviceToHost));
     *out_waves = n;
     return NRAYS_OK;
 }
@@ -537,10 +568,10 @@ int nrays_debug_wave_times2(NraysScene* sc, uint32_t* out, uint32_t capacity_wav
 #ifdef NR_PHASE_TIMING
 // Tuning builds only (tools/phase_timing.py): wave / lane iteration counts of the node loops and the triangle loops.
 int nrays_debug_counters(NraysScene* sc, unsigned long long out[16]) {
-    if (!sc || !sc->have_last) return NRAYS_ERR_BAD_ARG;
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
+    if (!sc || !sc->last.have) return NRAYS_ERR_BAD_ARG;
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
     DeviceCounters c;
-    HIP_TRY(hipMemcpy(&c, sc->d_counters, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, sc->buf.d_counters, sizeof c, hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; ++k) out[k] = c.dbg[k];
     for (int k = 0; k < 8; ++k) out[8 + k] = c.dbg2[k];
     return NRAYS_OK;
@@ -550,12 +581,12 @@ int nrays_debug_counters(NraysScene* sc, unsigned long long out[16]) {
 int nrays_get_primary_kernel_stats(NraysScene* sc, NraysStats* out) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     std::memset(out, 0, sizeof *out);
-    if (!sc->have_last || !sc->last_instrumented) return fail(NRAYS_ERR_BAD_ARG, "the last render was not instrumented");
-    HIP_TRY(hipSetDevice(sc->device));
-    HIP_TRY(hipStreamSynchronize(sc->last_stream));
+    if (!sc->last.have || !sc->last.instrumented) return fail(NRAYS_ERR_BAD_ARG, "the last render was not instrumented");
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    HIP_TRY(hipStreamSynchronize(sc->last.stream));
     DeviceCounters c;
-    HIP_TRY(hipMemcpy(&c, sc->d_counters_primary, sizeof c, hipMemcpyDeviceToHost));
-    out->rays_primary = sc->last_primary_first_batch;
+    HIP_TRY(hipMemcpy(&c, sc->ring.d_counters_primary, sizeof c, hipMemcpyDeviceToHost));
+    out->rays_primary = sc->last.primary_first_batch;
     fill_counters(out, c);
     out->rays_shadow_elided = c.shadow_elided;
     // single continuations (reflection OR refraction) are traced by the primary kernel itself (trace_chain); only the
@@ -566,54 +597,54 @@ int nrays_get_primary_kernel_stats(NraysScene* sc, NraysStats* out) {
 
 // What the blocking renders report of the frame's continuation queue, once the frame is over.
 static int check_overflow(NraysScene* sc) {
-    if (!sc->host.any_double_branch) return NRAYS_OK; // only scenes with a continuation queue can overflow it: the others skip the extra blocking copy
+    if (!sc->facts.host.any_double_branch) return NRAYS_OK; // only scenes with a continuation queue can overflow it: the others skip the extra blocking copy
     unsigned int overflow = 0;
-    HIP_TRY(hipMemcpy(&overflow, &sc->d_counters->overflow, sizeof overflow, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&overflow, &sc->buf.d_counters->overflow, sizeof overflow, hipMemcpyDeviceToHost));
     if (overflow) return fail(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: image is incomplete");
     return NRAYS_OK;
 }
 
 int nrays_render(NraysScene* sc, const NraysRenderParams* p, float* out_rgb) {
     if (!sc || !p || !out_rgb) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     size_t floats = (size_t)tile_rows(p) * p->width * 3;
-    int rc = grow_device((void**)&sc->d_frame, &sc->frame_floats, floats, sizeof(float));
+    int rc = grow_device((void**)&sc->buf.d_frame, &sc->buf.frame_floats, floats, sizeof(float));
     if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
-    if (rc == NRAYS_OK) rc = render_impl(sc, p, sc->d_frame, sc->own_stream, false);
+    if (rc == NRAYS_OK) rc = render_impl(sc, p, sc->buf.d_frame, sc->buf.own_stream, false);
     if (rc != NRAYS_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out_rgb, sc->d_frame, floats * sizeof(float), hipMemcpyDeviceToHost, sc->own_stream));
-    HIP_TRY(hipStreamSynchronize(sc->own_stream));
+    HIP_TRY(hipMemcpyAsync(out_rgb, sc->buf.d_frame, floats * sizeof(float), hipMemcpyDeviceToHost, sc->buf.own_stream));
+    HIP_TRY(hipStreamSynchronize(sc->buf.own_stream));
     return check_overflow(sc);
 }
 
 int nrays_render_rgb8(NraysScene* sc, const NraysRenderParams* p, uint8_t* out_rgb8) {
     if (!sc || !p || !out_rgb8) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     const size_t n = (size_t)tile_rows(p) * p->width * 3;
-    int rc = grow_device((void**)&sc->d_frame, &sc->frame_floats, n, sizeof(float));
-    if (rc == NRAYS_OK) rc = grow_device((void**)&sc->d_rgb8, &sc->rgb8_bytes, n, 1);
+    int rc = grow_device((void**)&sc->buf.d_frame, &sc->buf.frame_floats, n, sizeof(float));
+    if (rc == NRAYS_OK) rc = grow_device((void**)&sc->buf.d_rgb8, &sc->buf.rgb8_bytes, n, 1);
     if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
-    if (rc == NRAYS_OK) rc = render_impl(sc, p, sc->d_frame, sc->own_stream, false);
+    if (rc == NRAYS_OK) rc = render_impl(sc, p, sc->buf.d_frame, sc->buf.own_stream, false);
     if (rc != NRAYS_OK) return rc;
     if (n) {
-        hipLaunchKernelGGL(k_quantize_rgb8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->own_stream, sc->d_frame, sc->d_rgb8, n);
+        hipLaunchKernelGGL(k_quantize_rgb8, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, sc->buf.own_stream, sc->buf.d_frame, sc->buf.d_rgb8, n);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out_rgb8, sc->d_rgb8, n, hipMemcpyDeviceToHost, sc->own_stream));
+        HIP_TRY(hipMemcpyAsync(out_rgb8, sc->buf.d_rgb8, n, hipMemcpyDeviceToHost, sc->buf.own_stream));
     }
-    HIP_TRY(hipStreamSynchronize(sc->own_stream));
+    HIP_TRY(hipStreamSynchronize(sc->buf.own_stream));
     return check_overflow(sc);
 }
 
 int nrays_debug_scene_flags(const NraysScene* sc, uint32_t out[2]) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    out[0] = (uint32_t)sc->host.features; out[1] = sc->d.incoherent;
+    out[0] = (uint32_t)sc->facts.host.features; out[1] = sc->facts.d.incoherent;
     return NRAYS_OK;
 }
 
 int nrays_debug_last_permutation(const NraysScene* sc, uint32_t out[6]) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    for (int a = 0; a < 4; ++a) out[a] = sc->perm_launches ? sc->perm_last[a] : 0u;
-    out[4] = sc->perm_launches; out[5] = sc->perm_mixed ? 1u : 0u;
+    for (int a = 0; a < 4; ++a) out[a] = sc->last.perm_launches ? sc->last.perm_last[a] : 0u;
+    out[4] = sc->last.perm_launches; out[5] = sc->last.perm_mixed ? 1u : 0u;
     return NRAYS_OK;
 }
 
@@ -622,7 +653,7 @@ int nrays_debug_blas_build(const NraysMesh* mesh, uint32_t flags, NraysBlasDump*
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(NRAYS_ERR_NO_DEVICE, "no HIP device visible");
     nrays::BlasProbe probe; std::string err;
-    const int rc = nrays::build_blas_probe(mesh, (flags & 1u) != 0, (flags & 2u) == 0, probe, err);
+    const int rc = nrays::build_blas_probe(mesh, nrays::read_switches(), (flags & 1u) != 0, (flags & 2u) == 0, probe, err);
     if (rc != NRAYS_OK) return fail(rc, err);
     out->num_nodes = (uint32_t)probe.nodes.size(); out->num_refs = (uint32_t)probe.tri_ids.size();
     out->root = probe.root; out->max_depth = probe.max_depth; out->hairy = probe.hairy ? 1u : 0u;
@@ -634,9 +665,9 @@ int nrays_debug_blas_build(const NraysMesh* mesh, uint32_t flags, NraysBlasDump*
 
 int nrays_debug_node_aabb(NraysScene* sc, uint32_t node, double out[6]) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
-    if (!sc->d.node_aabbs || (size_t)node * 6 + 6 > sc->host.node_aabbs.size()) return fail(NRAYS_ERR_BAD_ARG, "node index out of range");
-    HIP_TRY(hipSetDevice(sc->device));
-    HIP_TRY(hipMemcpy(out, sc->d.node_aabbs + 6 * (size_t)node, 6 * sizeof(double), hipMemcpyDeviceToHost));
+    if (!sc->facts.d.node_aabbs || (size_t)node * 6 + 6 > sc->facts.host.node_aabbs.size()) return fail(NRAYS_ERR_BAD_ARG, "node index out of range");
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    HIP_TRY(hipMemcpy(out, sc->facts.d.node_aabbs + 6 * (size_t)node, 6 * sizeof(double), hipMemcpyDeviceToHost));
     return NRAYS_OK;
 }
 

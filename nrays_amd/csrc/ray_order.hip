@@ -200,7 +200,7 @@ static int ray_order_ensure(TraceWorkspace* w, uint32_t n) {
 static int ray_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* origins, const double* dirs, hipStream_t stream) {
     if (n == 0u || n > w->order_rays) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_order_chunk: workspace too small");
     SceneBox box;
-    for (int a = 0; a < 3; ++a) { box.v[a] = (double)sc->host.bounds_mn[a]; box.v[3 + a] = (double)sc->host.bounds_mx[a]; }
+    for (int a = 0; a < 3; ++a) { box.v[a] = (double)sc->facts.host.bounds_mn[a]; box.v[3 + a] = (double)sc->facts.host.bounds_mx[a]; }
     const uint32_t ray_grid = (n + kOrderBlock - 1u) / kOrderBlock, parts = ray_grid < kBoundsMaxGrid ? ray_grid : kBoundsMaxGrid;
     const uint32_t scan_grid = (kNumBins + kScanBlock - 1u) / kScanBlock;
     HIP_TRY(hipMemsetAsync(w->d_ray_bins, 0, (size_t)kNumBins * sizeof(uint32_t), stream));
@@ -276,9 +276,9 @@ void trace_workspace_release(NraysScene* sc) {
 }
 // The handle's threading contract: a batch on another stream than the handle's previous work (its last render, its last batch) is
 // ordered behind it, and a render that follows on yet another stream is ordered behind the batch (frame_path.hip: order_behind_previous waits on ev_switch
-// recorded on sc->last_stream when last_timed is false).  Nothing a render reports (counters, timings, tile costs) is touched.
+// recorded on sc->last.stream when last_timed is false).  Nothing a render reports (counters, timings, tile costs) is touched.
 static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
-    const hipStream_t prev[2] = {sc->have_last ? sc->last_stream : stream, w->used ? w->last_stream : stream};
+    const hipStream_t prev[2] = {sc->last.have ? sc->last.stream : stream, w->used ? w->last_stream : stream};
     for (int k = 0; k < 2; ++k) {
         if (prev[k] == stream || (k == 1 && prev[1] == prev[0])) continue;
         const int rc = order_behind_stream(sc, prev[k], stream);
@@ -288,15 +288,15 @@ static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
 }
 static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
     w->last_stream = stream; w->used = true;
-    if (sc->have_last) { sc->last_stream = stream; sc->last_timed = false; sc->last_pipelined = false; }
+    if (sc->last.have) { sc->last.stream = stream; sc->last.timed = false; sc->pipe.last_pipelined = false; }
 }
 // Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
-static bool batch_mesh_only(const NraysScene* sc) { return (sc->features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
+static bool batch_mesh_only(const NraysScene* sc) { return (sc->facts.features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }
 
 // A batch the caller called unordered (NRAYS_RAYS_UNORDERED) is reordered when the host can see that it pays: the reorder is eight launches in
 // front of the trace (a launch of a handle has a period of ~11 us), which a small batch does not earn back.  kReorderMinRays: DESIGN §5b.
 constexpr uint32_t kReorderMinRays = 1u << 19;
-static bool reorder_pays(const NraysScene* sc, uint32_t n) { return sc->ray_reorder == 2 || (sc->ray_reorder != 0 && n >= kReorderMinRays); }
+static bool reorder_pays(const NraysScene* sc, uint32_t n) { return sc->sw.ray_reorder == 2 || (sc->sw.ray_reorder != 0 && n >= kReorderMinRays); }
 static int check_ray_flags(uint32_t flags) { return (flags & ~(uint32_t)NRAYS_RAYS_UNORDERED) ? set_last_error(NRAYS_ERR_BAD_ARG, "unknown ray-batch flag") : NRAYS_OK; }
 // The reorder of one chunk (ray_order.hip) when it is due: *order = the order to trace in, or nullptr (trace the rays as they come).
 static int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, const double* o, const double* d, hipStream_t stream, const uint32_t** order) {
@@ -312,7 +312,7 @@ static int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t
 // queued second children and k_fold_fixed, as a frame runs them for a sample batch (bounce.h: run_bounce_rounds).
 static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
                        const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream, const uint32_t* order) {
-    const bool queued = sc->host.any_double_branch;
+    const bool queued = sc->facts.host.any_double_branch;
     if (queued) { // a frame's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
         const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
         int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
@@ -323,17 +323,17 @@ static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const doub
     unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
     QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
     const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-    const uint32_t keyed = sc->host.any_area_light ? 1u : 0u;
+    const uint32_t keyed = sc->facts.host.any_area_light ? 1u : 0u;
     // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
-    if (order && sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays_ordered<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
-    else if (order && batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
-    else if (order) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
-    else if (sc->d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
-    else if (batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
-    else hipLaunchKernelGGL((k_trace_rays<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    if (order && sc->facts.d.no_elide) hipLaunchKernelGGL((k_trace_rays_ordered<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (order && batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (order) hipLaunchKernelGGL((k_trace_rays_ordered<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (sc->facts.d.no_elide) hipLaunchKernelGGL((k_trace_rays<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else if (batch_mesh_only(sc)) hipLaunchKernelGGL((k_trace_rays<false, kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
+    else hipLaunchKernelGGL((k_trace_rays<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill);
     HIP_TRY(hipGetLastError());
     if (!queued) return NRAYS_OK;
-    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->d, sc->d.no_elide != 0u, max_depth, out, (size_t)n * 3, sc->num_cus};
+    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, sc->facts.d.no_elide != 0u, max_depth, out, (size_t)n * 3, sc->facts.num_cus};
     uint32_t overflowed = 0u;
     const int rc = run_bounce_rounds(rounds, stream, &overflowed);
     if (rc != NRAYS_OK) return rc;
@@ -346,7 +346,7 @@ static int trace_rays_device_impl(NraysScene* sc, uint32_t n, const double* o, c
     if (!sc || !o || !d || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     TraceWorkspace* w = nullptr;
     int rc = trace_workspace(sc, &w);
     if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
@@ -373,9 +373,9 @@ extern "C" {
 int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* max_toi, NraysCastResult* out) {
     if (!sc || !origins || !dirs || !out || mode > 1u || (mode == 1u && !max_toi)) return set_last_error(NRAYS_ERR_BAD_ARG, "bad cast-batch arguments");
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
-    if (sc->have_last) HIP_TRY(hipStreamSynchronize(sc->last_stream));
-    { const int rs = ensure_spill(sc, &sc->d_spill); if (rs != NRAYS_OK) return rs; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    if (sc->last.have) HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    { const int rs = ensure_spill(sc, &sc->buf.d_spill); if (rs != NRAYS_OK) return rs; }
     double *d_o = nullptr, *d_d = nullptr, *d_t = nullptr; NraysCastResult* d_r = nullptr;
     auto release = [&]() { if (d_o) (void)hipFree(d_o); if (d_d) (void)hipFree(d_d); if (d_t) (void)hipFree(d_t); if (d_r) (void)hipFree(d_r); };
 #define CAST_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
@@ -384,11 +384,11 @@ int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const doub
     CAST_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CAST_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
     if (mode == 1u) { CAST_TRY(hipMalloc((void**)&d_t, (size_t)n * sizeof(double))); CAST_TRY(hipMemcpy(d_t, max_toi, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
     const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-    CAST_TRY(sc->own_stream ? hipSuccess : hipStreamCreate(&sc->own_stream));
-    if ((sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
-    else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->own_stream, sc->d, mode, n, d_o, d_d, d_t, d_r, sc->d_spill);
+    CAST_TRY(sc->buf.own_stream ? hipSuccess : hipStreamCreate(&sc->buf.own_stream));
+    if ((sc->facts.features & ~(int)kFeatMultiSample) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
+    else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
     CAST_TRY(hipGetLastError());
-    CAST_TRY(hipStreamSynchronize(sc->own_stream));
+    CAST_TRY(hipStreamSynchronize(sc->buf.own_stream));
     CAST_TRY(hipMemcpy(out, d_r, (size_t)n * sizeof(NraysCastResult), hipMemcpyDeviceToHost));
 #undef CAST_TRY
     release();
@@ -409,7 +409,7 @@ static int trace_rays_host_impl(NraysScene* sc, uint32_t n, const double* origin
     if (!sc || !origins || !dirs || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     TraceWorkspace* w = nullptr;
     int rc = trace_workspace(sc, &w);
     if (rc != NRAYS_OK) return rc;
@@ -421,7 +421,7 @@ static int trace_rays_host_impl(NraysScene* sc, uint32_t n, const double* origin
     unsigned long long* s_k = (unsigned long long*)(s_r + cap); float* s_e = (float*)(s_k + cap); float* s_out = s_e + cap;
     rc = ensure_own_stream(sc);
     if (rc != NRAYS_OK) return rc;
-    const hipStream_t stream = sc->own_stream;
+    const hipStream_t stream = sc->buf.own_stream;
     rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
     const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
@@ -461,13 +461,13 @@ static int intersects_rays_device_impl(NraysScene* sc, uint32_t n, const double*
     if (!sc || !origins || !dirs || !max_toi || !out_filter || !out_lit) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     const hipStream_t stream = (hipStream_t)hip_stream;
     TraceWorkspace* w = nullptr;
     int rc = trace_workspace(sc, &w);
     if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
-    const bool mesh = (sc->features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
+    const bool mesh = (sc->facts.features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
     const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     for (uint32_t c0 = 0; c0 < n; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit ray indices far from overflow)
         const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
@@ -476,10 +476,10 @@ static int intersects_rays_device_impl(NraysScene* sc, uint32_t n, const double*
         const uint32_t* order = nullptr;
         rc = chunk_order(sc, w, reorder, nc, o, d, stream, &order);
         if (rc != NRAYS_OK) break;
-        if (order && mesh) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
-        else if (order) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
-        else if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
-        else hipLaunchKernelGGL((k_intersects_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        if (order && mesh) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else if (order) hipLaunchKernelGGL((k_intersects_rays_ordered<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, order, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else if (mesh) hipLaunchKernelGGL((k_intersects_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
+        else hipLaunchKernelGGL((k_intersects_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, o, d, t, out_filter + 3 * (size_t)c0, out_lit + c0, w->d_spill);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e)); break; }
     }
@@ -501,13 +501,13 @@ int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, con
     if (n > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_debug_ray_order: at most one chunk (2^22 rays)");
     out_info[0] = (uint32_t)kRayKeyBits; out_info[1] = (uint32_t)kRayBinBits; out_info[2] = reorder_pays(sc, n) ? 1u : 0u; out_info[3] = 0u;
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->device));
+    HIP_TRY(hipSetDevice(sc->facts.device));
     TraceWorkspace* w = nullptr;
     int rc = trace_workspace(sc, &w);
     if (rc == NRAYS_OK) rc = ray_order_ensure(w, n);
     if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
     if (rc != NRAYS_OK) return rc;
-    const hipStream_t stream = sc->own_stream;
+    const hipStream_t stream = sc->buf.own_stream;
     double* d_od = nullptr; // origins, then directions
     HIP_TRY(hipMalloc((void**)&d_od, (size_t)n * 48));
     rc = batch_begin(sc, w, stream);

@@ -282,42 +282,34 @@ static bool presplit(const std::vector<TriRec>& recs, std::vector<PrimBounds>& r
 #endif
 // Triangle count from which a BLAS is built on the GPU (bvh_device.hip); NRAYS_GPU_BUILD=0: never, NRAYS_GPU_BUILD_MIN=n: from n triangles.
 // Crossover on MI355X (tools/build_crossover.py, profiles/r04_build_crossover.log): 1 000 triangles host 1.6 / device 2.1 ms, 3 000: 3.9 / 2.5, 50 000: 65 / 3.6, 1 M: 337 / 15.
-static size_t device_build_min() { // read per scene (not cached): tests and A/B runs flip it between two nrays_scene_create calls
-    if (const char* e = getenv("NRAYS_GPU_BUILD")) if (atoi(e) == 0) return std::numeric_limits<size_t>::max();
-    if (const char* e = getenv("NRAYS_GPU_BUILD_MIN")) return (size_t)std::max(1ll, atoll(e));
-    return (size_t)2000;
-}
-static DeviceBuildOptions device_options(bool presplit_on) {
+// (the switches are read per scene, not cached: tests and A/B runs flip them between two nrays_scene_create calls)
+static size_t device_build_min(const Switches& sw) { return sw.gpu_build ? sw.gpu_build_min : std::numeric_limits<size_t>::max(); }
+static DeviceBuildOptions device_options(const Switches& sw, bool presplit_on) {
     DeviceBuildOptions o;
-    o.max_leaf = NR_MAX_LEAF; o.prim_cost = NR_PRIM_COST; o.prim_cost_hairy = NR_PRIM_COST_HAIRY;
-    o.budget = NR_PRESPLIT_BUDGET; o.budget_hairy = NR_PRESPLIT_BUDGET_HAIRY; o.min_gain = NR_PRESPLIT_MINGAIN; o.min_gain_hairy = NR_PRESPLIT_MINGAIN_HAIRY;
+    // the compiled defaults, or the tuning overrides (tools/build_sweep.py): a device build costs milliseconds, so the quality knobs can be swept in one process
+    o.max_leaf = sw.max_leaf.value_or(NR_MAX_LEAF); o.prim_cost = sw.prim_cost.value_or(NR_PRIM_COST); o.prim_cost_hairy = sw.prim_cost_hairy.value_or(NR_PRIM_COST_HAIRY);
+    o.budget = sw.presplit_budget.value_or(NR_PRESPLIT_BUDGET); o.budget_hairy = sw.presplit_budget_hairy.value_or(NR_PRESPLIT_BUDGET_HAIRY);
+    o.min_gain = sw.presplit_mingain.value_or(NR_PRESPLIT_MINGAIN); o.min_gain_hairy = sw.presplit_mingain_hairy.value_or(NR_PRESPLIT_MINGAIN_HAIRY);
     o.hairy_emptiness = NR_PRESPLIT_HAIRY; o.presplit = presplit_on;
-    // tuning overrides, read per scene (tools/build_sweep.py): a device build costs milliseconds, so the quality knobs can be swept in one process
-    auto envd = [](const char* name, double& v) { if (const char* e = getenv(name)) v = atof(e); };
-    auto envf = [](const char* name, float& v) { if (const char* e = getenv(name)) v = (float)atof(e); };
-    envd("NRAYS_PRESPLIT_BUDGET", o.budget); envd("NRAYS_PRESPLIT_BUDGET_HAIRY", o.budget_hairy);
-    envd("NRAYS_PRESPLIT_MINGAIN", o.min_gain); envd("NRAYS_PRESPLIT_MINGAIN_HAIRY", o.min_gain_hairy);
-    envf("NRAYS_PRIM_COST", o.prim_cost); envf("NRAYS_PRIM_COST_HAIRY", o.prim_cost_hairy);
-    if (const char* e = getenv("NRAYS_MAX_LEAF")) o.max_leaf = atoi(e);
-    if (const char* e = getenv("NRAYS_DEBUG_BUILD_CAPS")) o.debug_cap_div = std::max(1, atoi(e));
+    o.debug_cap_div = sw.debug_build_caps; o.split_grid_max = sw.split_grid; o.one_walk = sw.presplit_one_walk; o.debug_piece_cap = sw.debug_piece_cap; o.verbose = sw.build_times;
     return o;
 }
 
 // which: 0 = by size (device_build_min), 1 = host builder, 2 = device builder
-int append_blas(const NraysSceneDesc* d, const std::vector<uint32_t>& node_ids, HostScene& out, Blas& blas, std::string& err, int which = 0, bool presplit_on = true) {
+int append_blas(const NraysSceneDesc* d, const Switches& sw, const std::vector<uint32_t>& node_ids, HostScene& out, Blas& blas, std::string& err, int which = 0, bool presplit_on = true) {
     const auto TA = std::chrono::steady_clock::now();
     {
         size_t total = 0;
         for (uint32_t ni : node_ids) total += d->meshes[d->nodes[ni].mesh_id].num_triangles;
-        if (which == 2 || (which == 0 && total >= device_build_min())) {
+        if (which == 2 || (which == 0 && total >= device_build_min(sw))) {
             std::vector<DeviceMeshPart> parts;
             for (uint32_t ni : node_ids) {
                 const NraysMesh& m = d->meshes[d->nodes[ni].mesh_id];
                 parts.push_back(DeviceMeshPart{m.vertices, m.uvs, m.indices, m.num_vertices, m.num_triangles, ni});
             }
             DeviceBlas db;
-            const int rc = build_blas_device(parts, device_options(presplit_on), (int32_t)out.dev_nodes, (uint32_t)out.dev_tris, db, err);
-            if (getenv("NRAYS_BUILD_TIMES")) fprintf(stderr, "device BLAS build %.3f s (%zu triangles, %zu refs%s)%s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - TA).count(),
+            const int rc = build_blas_device(parts, device_options(sw, presplit_on), (int32_t)out.dev_nodes, (uint32_t)out.dev_tris, db, err);
+            if (sw.build_times) fprintf(stderr, "device BLAS build %.3f s (%zu triangles, %zu refs%s)%s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - TA).count(),
                                                      total, db.num_refs, db.hairy ? ", hair-like" : "", rc == NRAYS_OK ? "" : " FAILED");
             if (rc == NRAYS_OK) {
                 blas.root = db.root; blas.hairy = db.hairy; blas.device = true;
@@ -377,10 +369,10 @@ int append_blas(const NraysSceneDesc* d, const std::vector<uint32_t>& node_ids, 
     auto T1 = std::chrono::steady_clock::now();
     // thin tubes: a leaf's triangles mostly miss, and a node visit is cheap — leaves split sooner (hairball 2.96 -> 2.91 ms; the
     // architectural stand-in is 4 % slower with this value, profiles/r02_nodeloop_ab.log)
-    BuiltBvh bvh = build_bvh(pb, NR_MAX_LEAF, hairy ? NR_PRIM_COST_HAIRY : 0.0f);
+    BuiltBvh bvh = build_bvh(pb, NR_MAX_LEAF, hairy ? NR_PRIM_COST_HAIRY : 0.0f, sw.build_times);
     auto T2 = std::chrono::steady_clock::now();
-    if (getenv("NRAYS_BUILD_TIMES") && recs.size() > 1000000) fprintf(stderr, "  append_blas: triangle records %.2f s\n", std::chrono::duration<double>(T0 - TA).count());
-    if (getenv("NRAYS_BUILD_TIMES")) fprintf(stderr, "presplit %.2f s, build_bvh %.2f s (%zu triangles, %zu refs%s)\n", std::chrono::duration<double>(T1 - T0).count(), std::chrono::duration<double>(T2 - T1).count(), recs.size(), pb.size(), hairy ? ", hair-like" : "");
+    if (sw.build_times && recs.size() > 1000000) fprintf(stderr, "  append_blas: triangle records %.2f s\n", std::chrono::duration<double>(T0 - TA).count());
+    if (sw.build_times) fprintf(stderr, "presplit %.2f s, build_bvh %.2f s (%zu triangles, %zu refs%s)\n", std::chrono::duration<double>(T1 - T0).count(), std::chrono::duration<double>(T2 - T1).count(), recs.size(), pb.size(), hairy ? ", hair-like" : "");
     if (out.tris.size() + pb.size() >= (1u << 28)) { err = "too many triangles"; return NRAYS_ERR_UNSUPPORTED; }
     rebase_bvh(bvh, (int32_t)out.nodes.size(), (uint32_t)out.tris.size());
     out.max_bvh_depth = std::max(out.max_bvh_depth, bvh.max_depth);
@@ -398,7 +390,7 @@ int append_blas(const NraysSceneDesc* d, const std::vector<uint32_t>& node_ids, 
     blas.root = bvh.root;
     blas.hairy = hairy;
     blas.device = false; // (the caller may hand in the Blas of an earlier, device-built group)
-    if (getenv("NRAYS_BUILD_TIMES") && recs.size() > 1000000) fprintf(stderr, "  append_blas: after the build (rebase, gather, node copy) %.2f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - T2).count());
+    if (sw.build_times && recs.size() > 1000000) fprintf(stderr, "  append_blas: after the build (rebase, gather, node copy) %.2f s\n", std::chrono::duration<double>(std::chrono::steady_clock::now() - T2).count());
     return NRAYS_OK;
 }
 
@@ -427,14 +419,14 @@ int32_t append_tlas(std::vector<Instance>& insts, const std::vector<PrimBounds>&
 
 } // namespace
 
-int build_blas_probe(const NraysMesh* mesh, bool device, bool presplit_on, BlasProbe& out, std::string& err) {
+int build_blas_probe(const NraysMesh* mesh, const Switches& sw, bool device, bool presplit_on, BlasProbe& out, std::string& err) {
     if (!mesh || !mesh->vertices || !mesh->indices || mesh->num_triangles == 0) { err = "bad mesh"; return NRAYS_ERR_BAD_ARG; }
     NraysNode node; std::memset(&node, 0, sizeof node);
     node.shape_kind = NRAYS_SHAPE_TRIMESH; node.mesh_id = 0;
     NraysSceneDesc d; std::memset(&d, 0, sizeof d);
     d.meshes = mesh; d.num_meshes = 1; d.nodes = &node; d.num_nodes = 1;
     HostScene hs; Blas blas;
-    const int rc = append_blas(&d, std::vector<uint32_t>{0u}, hs, blas, err, device ? 2 : 1, presplit_on);
+    const int rc = append_blas(&d, sw, std::vector<uint32_t>{0u}, hs, blas, err, device ? 2 : 1, presplit_on);
     if (rc != NRAYS_OK) { for (DeviceBlas& b : hs.dev_blas) free_device_blas(b); return rc; }
     out.root = blas.root; out.hairy = blas.hairy; out.max_depth = hs.max_bvh_depth;
     if (device) {
@@ -453,7 +445,7 @@ int build_blas_probe(const NraysMesh* mesh, bool device, bool presplit_on, BlasP
     return NRAYS_OK;
 }
 
-int build_host_scene(const NraysSceneDesc* d, HostScene& out, std::string& err) {
+int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out, std::string& err) {
     if (!d) { err = "null scene descriptor"; return NRAYS_ERR_BAD_ARG; }
     if ((d->num_lights && !d->lights) || (d->num_materials && !d->materials) || (d->num_textures && !d->textures) ||
         (d->num_meshes && !d->meshes) || (d->num_nodes && !d->nodes)) { err = "null array with non-zero count"; return NRAYS_ERR_BAD_ARG; }
@@ -538,7 +530,7 @@ int build_host_scene(const NraysSceneDesc* d, HostScene& out, std::string& err) 
             float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
             // A mesh large enough for the device builder gets its local AABB from that build (k_tri_records reduces the same f32 min / max over the faces' vertices and checks
             // the indices): the host scan of the hairball stand-in's 8.6 M indices — random vertex reads — took 8 of its 100 ms.  Filled in below, once its BLAS exists.
-            if (n.shape_kind == NRAYS_SHAPE_TRIMESH && d->meshes[n.mesh_id].num_triangles >= device_build_min()) { // (NRAYS_GPU_BUILD=0: the minimum is SIZE_MAX)
+            if (n.shape_kind == NRAYS_SHAPE_TRIMESH && d->meshes[n.mesh_id].num_triangles >= device_build_min(sw)) { // (NRAYS_GPU_BUILD=0: the minimum is SIZE_MAX)
                 pending_aabb.push_back(i);
                 out.node_aabbs.insert(out.node_aabbs.end(), 6, 0.0);
                 continue;
@@ -618,7 +610,7 @@ int build_host_scene(const NraysSceneDesc* d, HostScene& out, std::string& err) 
         const std::vector<uint32_t>& ids = groups[key];
         uint32_t n0 = ids[0];
         auto add = [&](const std::vector<uint32_t>& sub, bool closest, bool shadow, bool anyhit, const Blas* reuse, Blas& blas) -> int {
-            if (!reuse) { int rc = append_blas(d, sub, out, blas, err); if (rc != NRAYS_OK) return rc; } else blas = *reuse;
+            if (!reuse) { int rc = append_blas(d, sw, sub, out, blas, err); if (rc != NRAYS_OK) return rc; } else blas = *reuse;
             if (!reuse && sub.size() == 1 && blas.device) single_bounds[sub[0]] = std::array<float, 6>{blas.mn[0], blas.mn[1], blas.mn[2], blas.mx[0], blas.mx[1], blas.mx[2]};
             Instance in = base_instance(n0);
             in.flags &= ~(uint32_t)kInstSolid; // TriMesh ignores `solid` (SURVEY B-8)

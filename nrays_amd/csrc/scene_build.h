@@ -7,6 +7,7 @@
 #include "../../include/nrays_abi.h"
 #include "bvh_device.h"
 #include "device_types.h"
+#include "switches.h"
 
 namespace nrays {
 
@@ -53,11 +54,11 @@ struct HostScene {
 };
 
 // Returns NRAYS_OK or a negative NraysStatus with `err` set.
-int build_host_scene(const NraysSceneDesc* desc, HostScene& out, std::string& err);
+int build_host_scene(const NraysSceneDesc* desc, const Switches& sw, HostScene& out, std::string& err);
 
 // Test probe behind nrays_debug_blas_build: the BLAS of ONE mesh from the host builder or the device builder, copied to the host.
 // nodes: local indices (root = node 0 unless the BLAS is a single leaf), tri_ids: TriRec::tri_id per leaf slot.
 struct BlasProbe { std::vector<BvhNode> nodes; std::vector<uint32_t> tri_ids; int32_t root = kEmptyChild; int max_depth = 0; bool hairy = false; };
-int build_blas_probe(const NraysMesh* mesh, bool device, bool presplit_on, BlasProbe& out, std::string& err);
+int build_blas_probe(const NraysMesh* mesh, const Switches& sw, bool device, bool presplit_on, BlasProbe& out, std::string& err);
 
 } // namespace nrays

@@ -10,6 +10,7 @@
 #include "../../include/nrays_abi.h"
 #include "device_types.h"
 #include "scene_build.h"
+#include "switches.h"
 
 namespace nrays {
 
@@ -61,130 +62,128 @@ struct TraceWorkspace {
 
 using nrays::DeviceCounters; using nrays::DScene; using nrays::HostScene; using nrays::QueueMem;
 
+// The handle, in parts: what is fixed when it is created (sw, facts), device memory that only grows (buf), and the bookkeeping of the frame path, one
+// group per concern.  The phases of frame_path.hip name the group they own in their headers.
 struct NraysScene {
-    int device = 0;
-    HostScene host;          // kept for counts only; bulk arrays are released after upload
-    DScene d;
-    std::vector<void*> allocs;
-    uint64_t scene_bytes = 0; // device bytes of the uploaded scene arrays (BVH nodes, triangles, records, textures)
-    // per-scene transient state, grown on demand
-    QueueMem queue[2];
-    uint32_t queue_capacity = 0;
-    // Rotating sets: launch n uses set n mod count_rot and clears set (n + count_rot / 2) mod count_rot (frames likewise), count_rot = 2 x the streams
-    // the handle's traces may run on (pipelined frames below; at least 4).  The launch whose set is cleared is the NEXT one on the clearing launch's own
-    // stream, so no launch that can overlap this one reads or counts into the set being cleared; launches on the same stream are ordered among themselves.
-    // (With three streams "clear n + 2" would be wrong: launch n + 2 runs on another stream and may have started.)
-    static constexpr int kCountSets = 6;
-    int count_rot = 4;                               // 4 (pipeline depth 1, 2) or 6 (depth 3): fixed when the handle is created
-    uint32_t* d_counts_set[kCountSets] = {};         // kNumCounts each
-    DeviceCounters* d_counters_set[kCountSets] = {}; // per frame
-    uint32_t* d_counts = nullptr;         // set used by the last launch
-    DeviceCounters* d_counters = nullptr; // set used by the last frame
-    uint64_t launch_index = 0, frame_index = 0;
-    uint32_t* d_spill = nullptr;
-    long long* d_fixed = nullptr; size_t fixed_slots = 0; // per-pixel fixed-point sums of the queued chains (double-branching scenes)
-    bool fixed_dirty = false; // k_bounce rounds were enqueued and their k_fold_fixed was not (an error in between): cleared at the next frame's start
-    // previous frame's wave-tile costs (k_primary) and the order derived from them (k_tile_order); valid for one
-    // (width, rows, band) geometry at a time
-    uint32_t* d_tile_cost = nullptr; uint32_t* d_tile_order = nullptr; uint32_t tile_slots = 0;
-    hipEvent_t ev_rec[2] = {nullptr, nullptr}; bool rec_events_valid = false; int rec_slot = -1; // around the last primary launch that recorded tile costs (NraysTileCosts::kernel_ms)
-    unsigned long long* d_cost_meta = nullptr; // DRender::cost_meta: start / end ticks and the measured clock of the launch that recorded d_tile_cost
-    // light-parallel tiles: log2 of the lanes per pixel (0 = the scene is not eligible), the split threshold in units of the frame's
-    // work per resident wave (NRAYS_LIGHT_SPLIT: 0 = never, < 0 = every tile, default 1), the lengths of the eight lists
-    uint32_t light_lsl = 0; float light_split_factor = 1.0f; uint32_t* d_order_len = nullptr;
-    const float* d_seed_boxes = nullptr; uint32_t seed_boxes = 0; bool seed_enabled = true; uint32_t seed_rays = 1; // k_seed_costs: first guess of a cold camera's tile costs (NRAYS_COST_SEED=0: none)
-    uint64_t cost_key = 0; bool cost_valid = false;
-    uint32_t cost_tiles = 0, cost_grid = 0, cost_split_lsl = 0; // wave tiles / workgroups / log2 of a split tile's parts of the frame that recorded d_tile_cost last (nrays_get_tile_costs)
-    // analytic scenes (workgroup lists): costs are recorded on the first frame of a camera, sorted once on the second, and
-    // the order is then reused as long as the camera stays (the scene of a handle never changes)
-    uint64_t cost_cam = 0, order_key = 0, order_cam = 0; bool order_valid = false; uint32_t order_age = 0;
-    // ... and by cameras NEAR the one whose costs it was sorted from (frame_path.hip: cam_shift_px) for up to kMaxOrderAge frames, so that a moving camera does not
-    // record and sort on every frame.  order_seeded: the order comes from k_seed_costs' guess, the next frame replaces it.
-    nrays::CamSnap cost_snap, order_snap; bool order_seeded = false;
-    uint64_t host_times_from = 0;                   // NRAYS_HOST_TIMES=n: render_impl (frame_path.hip) prints where the host time of the handle's frames n .. n + 3 goes (1: its first frames)
-    bool near_reuse = true;                         // NRAYS_NEAR_REUSE=0: only the very same camera reuses an order (A/B)
-    double near_pixels = 16.0; uint32_t max_order_age = 8; // NRAYS_NEAR_PIXELS / NRAYS_ORDER_AGE
-    float split_hyst = 0.5f;                        // NRAYS_SPLIT_HYST: a tile that ran in parts stays split down to this fraction of the split threshold (k_tile_order)
-    bool lone_known = false; uint64_t lone_key = 0, stats_key = 0; // the lead / second decision of the last sort that reported, and the geometry it belongs to
-    // ... and the sort also reports the sum and the maximum of the costs: their ratio is the frame's parallelism, which
-    // decides between cost-ordered lists with the long tiles on the first workgroup of each CU (few long tiles) and image-order
-    // lists (many tiles: throughput)
+    static constexpr int kCountSets = 6;  // counter sets a handle allocates (Buffers)
+    static constexpr int kPipeStreams = 3, kPipeSlots = 2 * kPipeStreams; // the most a handle uses: the caller's stream + 3 fill a process's four hardware queues
+    static constexpr int kRing = 256;     // slots of the event ring
+
+    nrays::Switches sw; // the environment's switches as nrays_scene_create found them: never written afterwards, never re-read in the frame path (switches.h)
+
+    // Fixed when the handle is created (nrays_hip.hip: upload_scene_arrays, derive_scene_facts and the three optional tables).
+    struct Facts {
+        int device = 0;
+        HostScene host;          // kept for counts only; bulk arrays are released after upload
+        DScene d;
+        std::vector<void*> allocs;
+        uint64_t scene_bytes = 0; // device bytes of the uploaded scene arrays (BVH nodes, triangles, records, textures)
+        int num_cus = 256;
+        int features = nrays::kFeatAll;
+        bool park = true;     // kFeatPark permutations for the three-wave multi-light kernels (Switches::park)
+        bool noxform = false; // every BLAS untransformed: the kFeatNoXform permutations of the mesh kernels render this scene
+        bool tiny = false;    // opaque analytic scene of at most kTinyLeaves TLAS leaves: the kFeatTinyScene permutations render it (Switches::tiny_scene)
+        uint32_t light_lsl = 0;     // light-parallel tiles: log2 of the lanes per pixel (0 = the scene is not eligible)
+        uint32_t spill_entries = 0; // HBM stack entries per lane beyond the kLdsStack entries kept in LDS (0 = never needed)
+        const float* d_seed_boxes = nullptr; uint32_t seed_boxes = 0; // k_seed_costs: world boxes of the nodes that can continue a chain
+    } facts;
+
+    // Device memory that only grows, and the indices that rotate through it.
+    struct Buffers {
+        QueueMem queue[2];
+        uint32_t queue_capacity = 0;
+        // Rotating sets: launch n uses set n mod count_rot and clears set (n + count_rot / 2) mod count_rot (frames likewise), count_rot = 2 x the streams
+        // the handle's traces may run on (pipelined frames below; at least 4).  The launch whose set is cleared is the NEXT one on the clearing launch's own
+        // stream, so no launch that can overlap this one reads or counts into the set being cleared; launches on the same stream are ordered among themselves.
+        // (With three streams "clear n + 2" would be wrong: launch n + 2 runs on another stream and may have started.)
+        int count_rot = 4;                               // 4 (pipeline depth 1, 2) or 6 (depth 3): fixed when the handle is created
+        uint32_t* d_counts_set[kCountSets] = {};         // kNumCounts each
+        DeviceCounters* d_counters_set[kCountSets] = {}; // per frame
+        uint32_t* d_counts = nullptr;         // set used by the last launch
+        DeviceCounters* d_counters = nullptr; // set used by the last frame
+        uint64_t launch_index = 0, frame_index = 0;
+        uint32_t* d_spill = nullptr;
+        long long* d_fixed = nullptr; size_t fixed_slots = 0; // per-pixel fixed-point sums of the queued chains (double-branching scenes)
+        bool fixed_dirty = false; // k_bounce rounds were enqueued and their k_fold_fixed was not (an error in between): cleared at the next frame's start
+        float* d_frame = nullptr; size_t frame_floats = 0;
+        uint8_t* d_rgb8 = nullptr; size_t rgb8_bytes = 0; // nrays_render_rgb8
+        hipStream_t own_stream = nullptr;                 // the stream of the blocking entry points (ensure_own_stream)
+    } buf;
+
+    // The per-camera scheduling state (frame_path.hip: schedule_mesh, schedule_analytic, record_costs, ensure_tile_arrays).  No pixel depends on it.
+    struct Order {
+        // previous frame's wave-tile costs (k_primary) and the order derived from them (k_tile_order); valid for one
+        // (width, rows, band) geometry at a time
+        uint32_t* d_tile_cost = nullptr; uint32_t* d_tile_order = nullptr; uint32_t tile_slots = 0;
+        hipEvent_t ev_rec[2] = {nullptr, nullptr}; bool rec_events_valid = false; int rec_slot = -1; // around the last primary launch that recorded tile costs (NraysTileCosts::kernel_ms)
+        unsigned long long* d_cost_meta = nullptr; // DRender::cost_meta: start / end ticks and the measured clock of the launch that recorded d_tile_cost
+        uint32_t* d_order_len = nullptr;           // light-parallel tiles: the lengths of the eight lists
+        uint64_t cost_key = 0; bool cost_valid = false;
+        uint32_t cost_tiles = 0, cost_grid = 0, cost_split_lsl = 0; // wave tiles / workgroups / log2 of a split tile's parts of the frame that recorded d_tile_cost last (nrays_get_tile_costs)
+        // analytic scenes (workgroup lists): costs are recorded on the first frame of a camera, sorted once on the second, and
+        // the order is then reused as long as the camera stays (the scene of a handle never changes)
+        uint64_t cost_cam = 0, order_key = 0, order_cam = 0; bool order_valid = false; uint32_t order_age = 0;
+        // ... and by cameras NEAR the one whose costs it was sorted from (frame_path.hip: cam_shift_px) for up to max_order_age frames, so that a moving camera does not
+        // record and sort on every frame.  order_seeded: the order comes from k_seed_costs' guess, the next frame replaces it.
+        nrays::CamSnap cost_snap, order_snap; bool order_seeded = false;
+        double near_pixels = 16.0; uint32_t max_order_age = 8; // Switches::near_pixels / max_order_age, or the scene's defaults (derive_scene_facts)
+        bool lone_known = false; uint64_t lone_key = 0, stats_key = 0; // the lead / second decision of the last sort that reported, and the geometry it belongs to
+        // ... and the sort also reports the sum and the maximum of the costs: their ratio is the frame's parallelism, which
+        // decides between cost-ordered lists with the long tiles on the first workgroup of each CU (few long tiles) and image-order
+        // lists (many tiles: throughput)
 #ifdef NR_DEBUG_TILE_COSTS
-    uint32_t* d_wave_times = nullptr; uint32_t dbg_grid = 0; uint32_t* d_seed_copy = nullptr;
+        uint32_t* d_wave_times = nullptr; uint32_t dbg_grid = 0; uint32_t* d_seed_copy = nullptr;
 #endif
-    unsigned long long* d_cost_stats = nullptr; unsigned long long* h_cost_stats = nullptr; hipEvent_t ev_stats = nullptr;
-    bool stats_pending = false, lone_waves = false;
-    uint32_t spill_entries = 0; // HBM stack entries per lane beyond the kLdsStack entries kept in LDS (0 = never needed)
-    int num_cus = 256;
-    int features = nrays::kFeatAll;
-    bool park = true;     // kFeatPark permutations for the three-wave multi-light kernels (NRAYS_PARK=0: off)
-    bool noxform = false; // every BLAS untransformed: the kFeatNoXform permutations of the mesh kernels render this scene
-    bool tiny = false;    // opaque analytic scene of at most kTinyLeaves TLAS leaves: the kFeatTinyScene permutations render it (NRAYS_TINY_SCENE=0: off)
-    float* d_frame = nullptr; size_t frame_floats = 0;
-    uint8_t* d_rgb8 = nullptr; size_t rgb8_bytes = 0; // nrays_render_rgb8
-    hipStream_t own_stream = nullptr;
-    // ring of HIP event triples (frame begin, primary kernel begin/end, frame end) recorded on the render
-    // stream; nrays_get_stats averages the frames recorded since its previous call.
-    static constexpr int kRing = 256;
-    hipEvent_t ev_begin[kRing] = {}, ev_pbegin[kRing] = {}, ev_pend[kRing] = {}, ev_end[kRing] = {};
-    bool single_launch[kRing] = {};
-    bool has_prepass[kRing] = {}; // the frame started with k_tile_order: ev_begin was recorded before it
-    uint64_t frames_recorded = 0, frames_reported = 0;
-    DeviceCounters* d_counters_primary = nullptr; // snapshot taken right after the primary kernel
-    hipStream_t last_stream = nullptr;
-    hipEvent_t last_done = nullptr; // last event recorded by the previous render (one of the ring's events)
-    hipEvent_t ev_switch = nullptr; // recorded on the previous render's stream when a render arrives on another one
-    bool have_last = false;
+        unsigned long long* d_cost_stats = nullptr; unsigned long long* h_cost_stats = nullptr; hipEvent_t ev_stats = nullptr;
+        bool stats_pending = false, lone_waves = false;
+    } order;
+
     // Pipelined frames (frame_path.hip: pipeline_prepare, pipeline_compose): a frame enqueued while its predecessor is still in flight traces its window on one of up to three
     // library-owned non-blocking streams into a staging frame and is composed into `out` on the caller's stream (k_compose).  Slot s = launch
-    // index mod pipe_slots: its stream (s mod pipe_depth), its staging rows, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
-    bool pipeline = true;                            // NRAYS_PIPELINE=0: every frame on the direct path (A/B, tests)
-    bool pipeline_always = false;                    // NRAYS_PIPELINE=2: every eligible frame is pipelined, in flight or not (tests: no dependence on timing)
-    // (twice as many slots as streams: with as many, the trace of frame k + depth waited for the compose of frame k, and a wait across queues costs 12 - 23 us on
-    // this stack — the chain trace -> compose -> trace made the pipelined frame slower than the direct one; profiles/pipelined_frames_ab.log)
-    static constexpr int kPipeStreams = 3, kPipeSlots = 2 * kPipeStreams; // the most a handle uses: the caller's stream + 3 fill a process's four hardware queues
-    int pipe_depth = 3;                              // NRAYS_PIPELINE_DEPTH=1|2|3: traces of the handle in flight at once = internal streams (read when the handle is created)
-    int pipe_slots = 6;                              // 4 at depth 1 and 2, 6 at depth 3
-    bool pipe_lead_wgs = false;                      // NRAYS_PIPELINE_LEAD_WGS: a pipelined trace keeps the lead + second workgroups of a direct frame (default at depth 1, 2) or runs
-                                                     // its cost-ordered lists on one workgroup per CU (default at depth 3: three grids share two wave slots per SIMD)
-    hipStream_t pipe_stream[kPipeStreams] = {};
-    // A slot holds the rows [wr0, wr1) of the window only (the trace with DRender::no_rows writes nothing else; k_compose reads nothing else): the kernels get
-    // `pipe_stage[s] - wr0 * width * 3`, which they address like `out`.  pipe_floats: floats allocated per slot; grown when a window needs more rows.
-    float* pipe_stage[kPipeSlots] = {}; size_t pipe_floats = 0;
-    uint32_t* pipe_spill[kPipeStreams] = {};         // a traversal-stack spill region per internal stream (spill_entries != 0): traces that overlap must not share d_spill
-    hipEvent_t ev_traced[kPipeSlots] = {}, ev_composed[kPipeSlots] = {};
-    bool last_pipelined = false;                     // the previous work of the handle was a pipelined frame: last_done is its "composed" event
-    // A/B and test switches, read ONCE when the handle is created (never in the frame path)
-    uint64_t max_primary_per_launch = 32ull << 20; // NRAYS_MAX_PRIMARY: sample batching threshold (tests force several launches)
-    bool max_primary_forced = false;
-    int lane_log2_override = -1;                    // NRAYS_LANE_LOG2: cap of the lanes per pixel of AA frames (A/B)
-    // The HIP events behind NraysStats::kernel_ms_* are recorded on every 4th frame of a handle (and on every instrumented
-    // one): three event records per frame cost ~6 us of a 85 us frame (balls: 0.0849 -> 0.0789 ms per step); the averages
-    // nrays_get_stats reports are over the sampled frames.  NRAYS_EVENT_STRIDE overrides it (1 = every frame).
-    uint32_t event_stride = 4;
-    uint64_t frames_total = 0;
-    bool last_timed = true;
-    int grab_override = -1;                         // NRAYS_GRAB
-    bool lpt_enabled = true;                        // NRAYS_LPT=0 restores image order
-    bool lpt_reuse = true;                          // NRAYS_LPT_REUSE=0: mesh scenes re-sort their tiles every frame even when the camera rests
-    bool lpt_analytic = true;                       // NRAYS_LPT_ANALYTIC=0: analytic scenes never switch to cost-ordered lists
-    int grid_wg_per_cu = 0;                         // NRAYS_GRID_WG_PER_CU=n caps the persistent grid at n workgroups per CU (tuning)
-    double lone_factor = 1.5;                       // NRAYS_LONE_FACTOR: cost-ordered lead / second lists when sum / max of the tile costs < factor * SIMDs
-    int lead_per_wg = 4;                            // NRAYS_LEAD_PER_WG=1..4: long entries per lead workgroup
-    bool lead_mode = true;                          // NRAYS_LEAD_WGS=0: cost-ordered lists run on one workgroup per CU instead of lead + second workgroups
-    int occ_override = -1;                          // NRAYS_OCC=2|3: waves per SIMD of the alpha-shadow mesh kernels (A/B)
-    bool cull_enabled = true;                       // NRAYS_SCREEN_CULL=0: no wave tile is decided from the scene's screen bounds
+    // index mod slots: its stream (s mod Switches::pipe_depth), its staging rows, "traced" (recorded behind the trace) and "composed" (behind the compose that read the slot).
+    struct Pipe {
+        bool enabled = true;                    // Switches::pipeline, until the staging frames cannot be allocated: every frame on the direct path from then on
+        // (twice as many slots as streams: with as many, the trace of frame k + depth waited for the compose of frame k, and a wait across queues costs 12 - 23 us on
+        // this stack — the chain trace -> compose -> trace made the pipelined frame slower than the direct one; profiles/pipelined_frames_ab.log)
+        int slots = 6;                          // 4 at depth 1 and 2, 6 at depth 3
+        bool lead_wgs = false;                  // a pipelined trace keeps the lead + second workgroups of a direct frame (default at depth 1, 2) or runs its cost-ordered
+                                                // lists on one workgroup per CU (default at depth 3: three grids share two wave slots per SIMD); Switches::pipe_lead_wgs overrides
+        hipStream_t stream[kPipeStreams] = {};
+        // A slot holds the rows [wr0, wr1) of the window only (the trace with DRender::no_rows writes nothing else; k_compose reads nothing else): the kernels get
+        // `stage[s] - wr0 * width * 3`, which they address like `out`.  floats: floats allocated per slot; grown when a window needs more rows.
+        float* stage[kPipeSlots] = {}; size_t floats = 0;
+        uint32_t* spill[kPipeStreams] = {};     // a traversal-stack spill region per internal stream (spill_entries != 0): traces that overlap must not share buf.d_spill
+        hipEvent_t ev_traced[kPipeSlots] = {}, ev_composed[kPipeSlots] = {};
+        bool last_pipelined = false;            // the previous work of the handle was a pipelined frame: last.done is its "composed" event
+    } pipe;
+
+    // Ring of HIP event triples (frame begin, primary kernel begin/end, frame end) recorded on the render
+    // stream; nrays_get_stats averages the frames recorded since its previous call.  Only every Switches::event_stride-th frame of a handle (and every
+    // instrumented one) records them; the averages are over the sampled frames.
+    struct Ring {
+        hipEvent_t ev_begin[kRing] = {}, ev_pbegin[kRing] = {}, ev_pend[kRing] = {}, ev_end[kRing] = {};
+        bool single_launch[kRing] = {};
+        bool has_prepass[kRing] = {}; // the frame started with k_tile_order: ev_begin was recorded before it
+        uint64_t frames_recorded = 0, frames_reported = 0, frames_total = 0;
+        DeviceCounters* d_counters_primary = nullptr; // snapshot taken right after the primary kernel
+    } ring;
+
+    // The last render: what the next call orders itself behind, what nrays_get_stats and the probes report.
+    struct Last {
+        hipStream_t stream = nullptr;
+        hipEvent_t done = nullptr;      // last event recorded by the previous render (one of the ring's events)
+        hipEvent_t ev_switch = nullptr; // recorded on the previous render's stream when a render arrives on another one
+        bool have = false, timed = true; // a render has run; it recorded `done`
+        uint64_t primary = 0, primary_first_batch = 0;
+        bool instrumented = false;
+        // nrays_debug_last_permutation: the k_primary permutation(s) the most recent render launched (host bookkeeping of launch_primary(), no device work)
+        uint32_t perm_last[4] = {0, 0, 0, 0}; // STATS, FEAT, PLAIN, OCC of the last launch
+        uint32_t perm_launches = 0;           // k_primary launches of that render (0: none yet, or the staged path rendered it)
+        bool perm_mixed = false;              // its launches did not all run the same permutation (sample batches: only the first can be plain)
+    } last;
+
     nrays::WavefrontState* wf = nullptr;            // staged (wavefront) path: queues, chunk tables, sums (wavefront.hip)
     nrays::TraceWorkspace* tw = nullptr;            // caller-ray batches (nrays_trace_rays*), created on first use
-    int ray_reorder = 1;                            // NRAYS_RAY_REORDER: 0 = a batch called unordered is traced as it comes, 2 = every such batch is reordered, else by its size (ray_order.hip: reorder_pays)
-    int wavefront_mode = -1;                        // NRAYS_WAVEFRONT: 0 = never, 1 = whenever the scene is eligible, -1 = the library's rule (wavefront.hip)
-    NraysStats last;
-    uint64_t last_primary = 0, last_primary_first_batch = 0;
-    bool last_instrumented = false;
-    // nrays_debug_last_permutation: the k_primary permutation(s) the most recent render launched (host bookkeeping of launch_primary(), no device work)
-    uint32_t perm_last[4] = {0, 0, 0, 0}; // STATS, FEAT, PLAIN, OCC of the last launch
-    uint32_t perm_launches = 0;           // k_primary launches of that render (0: none yet, or the staged path rendered it)
-    bool perm_mixed = false;              // its launches did not all run the same permutation (sample batches: only the first can be plain)
 };
 
 namespace nrays {

@@ -782,9 +782,6 @@ struct WavefrontState {
     int claim_parity = 0;           // d_claim[claim_parity] is all zero
     uint4* d_shres = nullptr; size_t shres_vecs = 0;
     float* d_acc = nullptr; size_t acc_floats = 0;
-    uint64_t max_paths = 64ull << 20; // NRAYS_WF_MAX_PATHS: (pixel, sample) paths per pass over a range of wave tiles
-    bool refill = true;               // NRAYS_WF_REFILL=0: the traversal stages run every 64 rays from start to end together (traverse()) instead of refilling free lanes
-    bool fuse = false;                // NRAYS_WF_FUSE=1: single-light scenes trace their shadow ray inside k_wf_shade instead of k_wf_shadow (A/B)
 };
 
 static int wf_ensure(NraysScene* sc, uint32_t slots, size_t shres_vecs, size_t acc_floats) {
@@ -792,9 +789,6 @@ static int wf_ensure(NraysScene* sc, uint32_t slots, size_t shres_vecs, size_t a
         sc->wf = new (std::nothrow) WavefrontState();
         if (!sc->wf) return set_last_error(NRAYS_ERR_OOM, "host allocation failed");
         WavefrontState& w = *sc->wf;
-        if (const char* e = getenv("NRAYS_WF_MAX_PATHS")) w.max_paths = (uint64_t)std::max(4096ll, atoll(e));
-        if (const char* e = getenv("NRAYS_WF_FUSE")) w.fuse = atoi(e) != 0;
-        if (const char* e = getenv("NRAYS_WF_REFILL")) w.refill = atoi(e) != 0; // 2: also in anti-aliased frames
         HIP_TRY(hipMalloc((void**)&w.d_nblocks, (kMaxGenerations + 2) * sizeof(uint32_t)));
         HIP_TRY(hipHostMalloc((void**)&w.h_nblocks, 4 * sizeof(uint32_t), hipHostMallocDefault));
         for (int k = 0; k < 2; ++k) {
@@ -848,17 +842,17 @@ void wavefront_release(NraysScene* sc) {
 }
 
 static bool wf_eligible(const NraysScene* sc) {
-    const int f = sc->features;
+    const int f = sc->facts.features;
     if (!(f == 2 || f == 6 || f == 18 || f == 22)) return false; // TriMesh nodes only (+ alpha shadows, + several lights)
-    if (sc->host.any_double_branch || sc->max_primary_forced) return false;
-    for (const LightRec& l : sc->host.lights) if (l.racsample != 1u) return false;
-    if (sc->host.lights.empty()) return false;
+    if (sc->facts.host.any_double_branch || sc->sw.max_primary_forced) return false;
+    for (const LightRec& l : sc->facts.host.lights) if (l.racsample != 1u) return false;
+    if (sc->facts.host.lights.empty()) return false;
     return true;
 }
 
 bool wavefront_wanted(const NraysScene* sc, const NraysRenderParams* p, uint32_t lane_log2) {
-    if (sc->wavefront_mode == 0 || !wf_eligible(sc)) return false;
-    if (sc->wavefront_mode == 1) return true;
+    if (sc->sw.wavefront_mode == 0 || !wf_eligible(sc)) return false;
+    if (sc->sw.wavefront_mode == 1) return true;
     // The library's rule (profiles/r04_wavefront_ab.log): frames bound by the SUM of their rays gain from dense lanes and four waves
     // per SIMD; a frame that is as long as its deepest chain (one light, 1080p) is faster in the megakernel, whose long tiles start
     // first and overlap with everything else.
@@ -875,12 +869,12 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
     const uint64_t paths_per_tile = (uint64_t)(64u >> lane_log2) * spp;
     // lane refill pays where the lanes of a wave part ways early (one ray per pixel: hairball 2.98 -> 2.67 ms); the samples of ONE pixel walk
     // together, and mixing in the next pixel's costs them their wave-uniform node fetches (16 spp: 22.0 -> 26.5 ms) — profiles/r04_wavefront_refill_ab.log
-    const bool refill_on = (sc->wf ? sc->wf->refill : !(getenv("NRAYS_WF_REFILL") && atoi(getenv("NRAYS_WF_REFILL")) == 0)) && (lane_log2 == 0u || (getenv("NRAYS_WF_REFILL") && atoi(getenv("NRAYS_WF_REFILL")) == 2));
-    const uint32_t grid_full = std::min<uint32_t>((uint32_t)kMaxGrid, (uint32_t)sc->num_cus * (uint32_t)(refill_on ? NR_WF_OCC_RF : NR_WF_OCC));
+    // (NRAYS_WF_REFILL=0: the traversal stages run every 64 rays from start to end together, traverse(), instead of refilling free lanes; =2: refill in anti-aliased frames too)
+    const bool refill_on = sc->sw.wf_refill && (lane_log2 == 0u || sc->sw.wf_refill_aa);
+    const uint32_t grid_full = std::min<uint32_t>((uint32_t)kMaxGrid, (uint32_t)sc->facts.num_cus * (uint32_t)(refill_on ? NR_WF_OCC_RF : NR_WF_OCC));
     const uint32_t waves_full = grid_full * (kBlock / 64);
     // tile ranges: every sample of a range's pixels in one pass (the samples of a pixel stay side by side in the queues)
-    uint64_t max_paths = 64ull << 20;
-    if (sc->wf) max_paths = sc->wf->max_paths; else if (const char* e = getenv("NRAYS_WF_MAX_PATHS")) max_paths = (uint64_t)std::max(4096ll, atoll(e));
+    const uint64_t max_paths = sc->sw.wf_max_paths;
     const uint32_t tiles_per_pass = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::max<uint32_t>(nwt, 1u), max_paths / std::max<uint64_t>(paths_per_tile, 1)));
     // slots: every path of a pass may hit, plus one partly filled block per producer wave — of the grid this frame launches (every stage
     // kernel runs on at most grid_full workgroups), not of the largest grid the library knows: that was 0.8 GB per queue for any frame
@@ -888,12 +882,12 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
     if (slots64 >= (1ull << 31)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "staged path: pass too large");
     const uint32_t slots = (uint32_t)slots64;
     const size_t acc_floats = spp > 1 ? (size_t)tiles_per_pass * paths_per_tile * 3 : 0;
-    int rc = wf_ensure(sc, slots, (size_t)slots * sc->d.num_lights, acc_floats);
+    int rc = wf_ensure(sc, slots, (size_t)slots * sc->facts.d.num_lights, acc_floats);
     if (rc != NRAYS_OK) return rc;
     WavefrontState& w = *sc->wf;
     float* acc = spp > 1 ? w.d_acc : d_out;
     const bool plain = R.window_width == 0.0 && !R.use_rng && spp == 1u && R.width <= 16384u && R.height <= 16384u;
-    const bool can_continue = sc->host.any_reflective || sc->host.any_transparent;
+    const bool can_continue = sc->facts.host.any_reflective || sc->facts.host.any_transparent;
     const uint32_t keyed = R.use_rng ? 1u : 0u;
     R.sample_begin = 0; R.sample_end = spp; R.first_batch = 1u;
     // every stage kernel claims its items from d_claim[parity] (all zero) and clears the other set for its successor
@@ -901,17 +895,17 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
     bool first_pass = true;
     for (uint32_t t0 = 0; t0 < std::max<uint32_t>(nwt, 1u); t0 += tiles_per_pass) {
         const uint32_t t1 = std::min<uint32_t>(nwt, t0 + tiles_per_pass);
-        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ev_pbegin[slot], stream));
+        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ring.ev_pbegin[slot], stream));
         HIP_TRY(hipMemsetAsync(w.d_nblocks, 0, (kMaxGenerations + 2) * sizeof(uint32_t), stream));
         WfQueue q0 = w.q[0]; q0.nblocks = w.d_nblocks;
         {
             uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
             uint32_t* zc = first_pass ? next_counts : nullptr; DeviceCounters* zctr = first_pass ? next_ctr : nullptr;
             if (refill_on) {
-                if (plain) hipLaunchKernelGGL((k_wf_primary_rf<FEAT, true>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
-                else hipLaunchKernelGGL((k_wf_primary_rf<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
-            } else if (plain) hipLaunchKernelGGL((k_wf_primary<FEAT, true>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
-            else hipLaunchKernelGGL((k_wf_primary<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->d, R, q0, d_out, acc, sc->d_counters, sc->d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
+                if (plain) hipLaunchKernelGGL((k_wf_primary_rf<FEAT, true>), dim3(grid_full), dim3(kBlock), 0, stream, sc->facts.d, R, q0, d_out, acc, sc->buf.d_counters, sc->buf.d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
+                else hipLaunchKernelGGL((k_wf_primary_rf<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->facts.d, R, q0, d_out, acc, sc->buf.d_counters, sc->buf.d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
+            } else if (plain) hipLaunchKernelGGL((k_wf_primary<FEAT, true>), dim3(grid_full), dim3(kBlock), 0, stream, sc->facts.d, R, q0, d_out, acc, sc->buf.d_counters, sc->buf.d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
+            else hipLaunchKernelGGL((k_wf_primary<FEAT, false>), dim3(grid_full), dim3(kBlock), 0, stream, sc->facts.d, R, q0, d_out, acc, sc->buf.d_counters, sc->buf.d_spill, tiles_x, tiles_y, t0, t1, cn, cl, zc, zctr);
             HIP_TRY(hipGetLastError());
         }
         uint32_t grid = grid_full; // workgroups of the generation's stage kernels (sized from its block count once that is known)
@@ -920,25 +914,25 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
             q.nblocks = w.d_nblocks + g; qn.nblocks = w.d_nblocks + g + 1;
             if (g > 0) {
                 uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
-                if (refill_on) hipLaunchKernelGGL((k_wf_closest_rf<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, sc->d_spill, cn, cl);
-                else hipLaunchKernelGGL((k_wf_closest<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, sc->d_spill, cn, cl);
+                if (refill_on) hipLaunchKernelGGL((k_wf_closest_rf<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, q, sc->buf.d_spill, cn, cl);
+                else hipLaunchKernelGGL((k_wf_closest<FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, q, sc->buf.d_spill, cn, cl);
                 HIP_TRY(hipGetLastError());
             }
-            const bool fused = !kMulti && w.fuse;
+            const bool fused = !kMulti && sc->sw.wf_fuse;
             if (!fused) {
-                const uint32_t grid_sh = g == 0 ? grid_full : std::min<uint32_t>(grid_full, grid * sc->d.num_lights);
+                const uint32_t grid_sh = g == 0 ? grid_full : std::min<uint32_t>(grid_full, grid * sc->facts.d.num_lights);
                 uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
-                if (refill_on) hipLaunchKernelGGL((k_wf_shadow_rf<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->d, q, w.d_shres, sc->d_counters, sc->d_spill, cn, cl);
-                else hipLaunchKernelGGL((k_wf_shadow<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->d, q, w.d_shres, sc->d_counters, sc->d_spill, cn, cl);
+                if (refill_on) hipLaunchKernelGGL((k_wf_shadow_rf<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->facts.d, q, w.d_shres, sc->buf.d_counters, sc->buf.d_spill, cn, cl);
+                else hipLaunchKernelGGL((k_wf_shadow<FEAT>), dim3(grid_sh), dim3(kBlock), 0, stream, sc->facts.d, q, w.d_shres, sc->buf.d_counters, sc->buf.d_spill, cn, cl);
                 HIP_TRY(hipGetLastError());
             }
             const bool emit = can_continue && g < (uint32_t)kMaxGenerations;
             {
                 uint32_t* cn = claim(); uint32_t* cl = w.d_claim[w.claim_parity];
                 if (fused) {
-                    if constexpr (!kMulti) hipLaunchKernelGGL((k_wf_shade<FEAT, false>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, qn, (const uint4*)w.d_shres, acc, sc->d_counters, sc->d_spill,
+                    if constexpr (!kMulti) hipLaunchKernelGGL((k_wf_shade<FEAT, false>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, q, qn, (const uint4*)w.d_shres, acc, sc->buf.d_counters, sc->buf.d_spill,
                                                               g, p->max_depth, keyed, emit ? 1u : 0u, cn, cl);
-                } else hipLaunchKernelGGL((k_wf_shade<FEAT, true>), dim3(grid), dim3(kBlock), 0, stream, sc->d, q, qn, (const uint4*)w.d_shres, acc, sc->d_counters, sc->d_spill,
+                } else hipLaunchKernelGGL((k_wf_shade<FEAT, true>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, q, qn, (const uint4*)w.d_shres, acc, sc->buf.d_counters, sc->buf.d_spill,
                                           g, p->max_depth, keyed, emit ? 1u : 0u, cn, cl);
                 HIP_TRY(hipGetLastError());
             }
@@ -953,7 +947,7 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
             hipLaunchKernelGGL(k_wf_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, R, (const float*)w.d_acc, d_out, t0, t1);
             HIP_TRY(hipGetLastError());
         }
-        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ev_pend[slot], stream));
+        if (first_pass && timed) HIP_TRY(hipEventRecord(sc->ring.ev_pend[slot], stream));
         first_pass = false;
     }
     return NRAYS_OK;
@@ -961,7 +955,7 @@ static int wf_render_feat(NraysScene* sc, const NraysRenderParams* p, DRender R,
 
 int wavefront_render(NraysScene* sc, const NraysRenderParams* p, DRender R, float* d_out, hipStream_t stream, uint32_t tiles_x, uint32_t tiles_y,
                      bool timed, int slot, DeviceCounters* next_ctr, uint32_t* next_counts) {
-    switch (sc->features) {
+    switch (sc->facts.features) {
     case 2: return wf_render_feat<2>(sc, p, R, d_out, stream, tiles_x, tiles_y, timed, slot, next_ctr, next_counts);
     case 6: return wf_render_feat<6>(sc, p, R, d_out, stream, tiles_x, tiles_y, timed, slot, next_ctr, next_counts);
     case 18: return wf_render_feat<18>(sc, p, R, d_out, stream, tiles_x, tiles_y, timed, slot, next_ctr, next_counts);

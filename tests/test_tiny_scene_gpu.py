@@ -10,6 +10,7 @@ import pytest
 
 import nrays_amd as nr
 from nrays_amd import math3d
+from tests.permutation_cases import TINY
 from tools import scenes_util as su
 
 pytestmark = pytest.mark.gpu
@@ -143,3 +144,33 @@ def test_caller_supplied_rays_identical(gpu):
     (c1, l1, f1), (c0, l0, f0) = res
     assert np.array_equal(c1.view(np.uint32), c0.view(np.uint32))
     assert np.array_equal(l1, l0) and np.array_equal(f1.view(np.uint32), f0.view(np.uint32))
+
+
+def test_switches_are_read_when_the_handle_is_created(gpu, monkeypatch):
+    """A switch holds for a handle as nrays_scene_create found it, whatever the environment says afterwards: handle A is created with
+    NRAYS_TINY_SCENE=0 and rendered after the variable is gone, handle B is created without it.  A never launches a kFeatTinyScene
+    permutation, B always does, and all four frames are bit-identical (the smallest frame that runs such a permutation: 64 x 64, 1 spp)."""
+    def three_balls():
+        mat = su.default_material()
+        nodes = [nr.SceneNode(mat, 0.0, 0.25, 1.0, 1.0, nr.Isometry3((x, 0.0, 0.0)), nr.Ball(0.8)) for x in (-2.0, 0.0, 2.0)]
+        return nr.Scene(nodes, [nr.Light((1.0, 8.0, -3.0), 0.0, 1, (1, 1, 1))], (0.2, 0.3, 0.4))
+
+    monkeypatch.setenv("NRAYS_TINY_SCENE", "0")
+    a = three_balls()
+    a.device_handle()
+    monkeypatch.delenv("NRAYS_TINY_SCENE")
+    b = three_balls()
+    b.device_handle()
+    cam = dict(eye=(0.0, 2.0, -8.0), at=(0.0, 0.0, 0.0), fovy=45.0)
+    proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], 64, 64)
+    frames = []
+    for _ in range(2):
+        for sc, tiny in ((a, 0), (b, TINY)):
+            frames.append(nr.render(sc, (64, 64), 1, 0.0, cam["eye"], proj))
+            (_, feat, _, _), launches, _ = nr.last_permutation(sc)
+            assert launches == 1 and feat & TINY == tiny, (feat, launches)
+    a._release()
+    b._release()
+    for f in frames[1:]:
+        assert np.array_equal(f.view(np.uint32), frames[0].view(np.uint32))
+    assert len(np.unique(frames[0].reshape(-1, 3), axis=0)) > 8  # (the balls are in the frame)
