@@ -244,9 +244,11 @@ __global__ void k_resolve(float* out, size_t n, float spp) { // pxs.push(tot_c /
 // scene copied from the staging frame `win` the trace wrote (addressed like `out`), the background sums of fill_background_row_body
 // everywhere else.  Frames without bands only (row = global row, no padding rows).  It runs beside the next frame's persistent trace
 // grid: no LDS, a few registers, streaming 16-byte accesses.  [wi0, wi1) x [wr0, wr1): the window in pixels.
+// stamp: null, or the frame's words of the ring's stamps (DRender::stamp) — thread 0 of every workgroup leaves its exit tick in the third.
 __global__ void __launch_bounds__(256) k_compose(float* __restrict__ out, const float* __restrict__ win, uint32_t width, uint32_t spp, float bg0, float bg1, float bg2,
-                                                 uint32_t wi0, uint32_t wi1, uint32_t wr0, uint32_t wr1) {
+                                                 uint32_t wi0, uint32_t wi1, uint32_t wr0, uint32_t wr1, unsigned long long* stamp) {
     const uint32_t rl = blockIdx.x;
+    auto leave = [&]() { if (stamp && threadIdx.x == 0u) atomicMax(&stamp[2], (unsigned long long)__builtin_amdgcn_s_memrealtime()); };
     float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
     for (uint32_t s = 0; s < spp; ++s) { b0 = b0 + bg0; b1 = b1 + bg1; b2 = b2 + bg2; }
     const bool split = rl >= wr0 && rl < wr1 && wi1 > wi0; // this row crosses the window
@@ -265,12 +267,14 @@ __global__ void __launch_bounds__(256) k_compose(float* __restrict__ out, const 
             }
             __builtin_nontemporal_store(v, (__attribute__((address_space(1))) f4v*)(row + f));
         }
+        leave();
         return;
     }
     for (uint32_t f = threadIdx.x; f < width * 3u; f += 256u) {
         const uint32_t i = f / 3u, c = f - i * 3u;
         row[f] = (split && i >= wi0 && i < wi1) ? src[f] : (c == 0u ? b0 : (c == 1u ? b1 : b2));
     }
+    leave();
 }
 
 // =============================================================================================
@@ -386,19 +390,7 @@ void pipeline_release(NraysScene* sc) {
 static std::atomic<NraysScene*> g_last_renderer{nullptr};
 
 // ---- the frame's plan ------------------------------------------------------------------------------------------------------------------
-// What plan_frame decides once per frame.  The phases read it; the header comment of each names what it may still change: grid, grab, R.lead_*, R.tile_order, R.tile_cost —
-// and which group of the handle (scene_handle.h) it writes.  Every phase reads sc->sw and sc->facts; none writes them.
-struct FramePlan {
-    uint32_t rows; uint64_t npix_local;    // rows and pixels of the local frame buffer
-    bool queued; uint32_t batch;           // the scene needs the HBM queue (double branching); samples per k_primary launch
-    uint32_t lane_log2, bwl, bhl;          // log2 of the lanes per pixel of an anti-aliased frame, of the width / height of a scheduling unit's pixel block
-    uint32_t tiles_x, tiles_y, ntiles;     // scheduling blocks of the frame; ntiles in units of four wave tiles
-    bool banded; uint32_t win_units;       // the frame owns bands of rows only; scheduling blocks inside the window (DRender::win_*)
-    int occ; uint32_t grid, grab;          // k_primary's OCC (0 or 3), its persistent grid, tiles per dequeue (0 = workgroup lists through LDS)
-    bool timed; int slot;                  // this frame records the ring's events, into this slot
-    bool single_launch, staged;            // nothing follows the one k_primary launch; the staged path (wavefront.hip) renders the frame
-    uint64_t sched_key, cam; CamSnap snap; // geometry key, camera hash and camera of the per-camera scheduling state (not filled for staged frames)
-};
+// FramePlan (scene_handle.h): what plan_frame decides once per frame; the handle keeps the plan of its last parameter block (NraysScene::plan).
 
 // NRAYS_HOST_TIMES=n (Switches::host_times_from): microseconds of host time this call spends up to a few marks, for the handle's frames n .. n + 3 (1: its first frames, tools/cold_probe.py)
 struct HostTimes {
@@ -406,7 +398,8 @@ struct HostTimes {
     void mark(const char* what) const { if (on) fprintf(stderr, "  render_impl frame %llu: +%.1f us %s\n", frame, std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), what); }
 };
 
-// Fills the plan and the by-value DRender (everything but the sample range of a launch and what the schedulers decide).  No HIP call; the handle is only read.
+// Fills the plan and the by-value DRender (everything but the sample range of a launch, what the schedulers decide and f.timed / f.slot).  No HIP call; the handle is only
+// read, and only what never changes of it (sw, facts): the same parameter block gives the same plan (NraysScene::plan).
 static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool instrumented, FramePlan& f, DRender& R) {
     if (p->ray_per_pixel == 0) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_per_pixel must be > 0 (scene.rs:37)");
     if (p->width == 0 || p->height == 0) return set_last_error(NRAYS_ERR_BAD_ARG, "empty resolution");
@@ -414,6 +407,10 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
     const uint32_t rows = f.rows = tile_rows(p);
     const uint64_t npix_local = f.npix_local = (uint64_t)rows * p->width;
     if (npix_local >= (1ull << 31)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "tile too large");
+    // owned rows only (padding rows of the last band carry no rays)
+    f.owned_rows = 0;
+    if (p->band_rows == 0 || p->band_owners <= 1) f.owned_rows = p->height;
+    else for (uint32_t j = 0; j < p->height; ++j) if (((j / p->band_rows) % p->band_owners) == p->band_owner) ++f.owned_rows;
 
     // sample batching keeps the number of primary rays (and hence continuation rays) per launch bounded
     // Continuation rays stay in registers (trace_chain); the HBM queue is only needed when one hit can
@@ -493,8 +490,7 @@ static int plan_frame(const NraysScene* sc, const NraysRenderParams* p, bool ins
                                 (uint32_t)sc->facts.num_cus * (uint32_t)(occ ? NR_OCC3_AS : waves_per_simd(instrumented ? kFeatAll : sc->facts.features)) * 256u / (uint32_t)kBlock);
     if (sc->sw.grid_wg_per_cu > 0) f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus * (uint32_t)sc->sw.grid_wg_per_cu); // NRAYS_GRID_WG_PER_CU: occupancy sensitivity runs
 
-    f.timed = instrumented || (sc->ring.frames_total % sc->sw.event_stride) == 0;
-    f.slot = (int)(sc->ring.frames_recorded % NraysScene::kRing);
+    f.timed = false; f.slot = 0; // (render_impl: they change from call to call)
     // The staged ("wavefront") form of the trace loop (wavefront.hip) renders this frame instead of k_primary when the scene is eligible and
     // NRAYS_WAVEFRONT / the library's rule say so; pixels are identical either way.
     f.staged = !instrumented && wavefront_wanted(sc, p, lane_log2);
@@ -716,6 +712,7 @@ static int schedule_analytic(NraysScene* sc, FramePlan& f, DRender& R, hipStream
 struct PipeFrame {
     bool on;                         // this frame is split into a trace on an internal stream and a compose on the caller's
     int ps, pst;                     // its slot (staging rows, events) and its internal stream
+    uint64_t launch;                 // its launch number (NraysScene::Pipe: composed_seen)
     hipStream_t lstream;             // the stream of the k_primary launch: the internal one, or the caller's on the direct path
     float* stage;                    // the slot's staging rows, addressed like `out`
     uint32_t wi0, wi1, wr0, wr1;     // the window in pixels
@@ -732,6 +729,7 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
     if (pipe && !sc->sw.pipeline_always) { // is the predecessor still in flight?  (a caller that waits for every frame stays on the direct path)
         const hipError_t q = sc->pipe.last_pipelined ? hipEventQuery(sc->last.done) : hipStreamQuery(sc->last.stream);
         if (q != hipSuccess) (void)hipGetLastError();
+        else if (sc->pipe.last_pipelined) sc->pipe.composed_seen = sc->pipe.newest_launch; // (last.done is the newest compose's event)
         pipe = q == hipErrorNotReady;
         ht.mark("pipeline: in-flight query");
     }
@@ -749,7 +747,7 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
     // fit side by side and the third takes the slots of whichever retires waves first.  Pixels do not depend on the shape of the lists.
     if (pipe && !sc->pipe.lead_wgs && R.lead_wgs) { R.lead_wgs = 0u; R.lead_entries = 0u; f.grid = std::min<uint32_t>(f.grid, (uint32_t)sc->facts.num_cus); }
     pf.on = pipe;
-    pf.ps = (int)(sc->buf.launch_index % (uint64_t)sc->pipe.slots); pf.pst = pf.ps % sc->sw.pipe_depth;
+    pf.ps = (int)(sc->buf.launch_index % (uint64_t)sc->pipe.slots); pf.pst = pf.ps % sc->sw.pipe_depth; pf.launch = sc->buf.launch_index + 1u;
     pf.lstream = pipe ? sc->pipe.stream[pf.pst] : stream;
     pf.stage = pipe ? sc->pipe.stage[pf.ps] - stage_skip : nullptr;
     if (pipe) {
@@ -758,33 +756,48 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
             HIP_TRY(hipEventRecord(sc->last.ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
             for (int k = 0; k < sc->sw.pipe_depth; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe.stream[k], sc->last.ev_switch, 0));
         }
-        // the compose that last read this slot's staging rows, pipe_slots frames ago: when the host can see that it is over (a query costs 0.6 us) the wait (5 us
-        // of host time, which bounds the pipelined frame rate) is not enqueued
-        if (hipEventQuery(sc->pipe.ev_composed[pf.ps]) != hipSuccess) { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->pipe.ev_composed[pf.ps], 0)); }
+        // the compose that last read this slot's staging rows, pipe_slots frames ago: when the host can see that it is over the wait (5 us of host time, which bounds
+        // the pipelined frame rate) is not enqueued.  It sees that without a call when a compose at or after that one has been seen finished (Pipe::composed_seen); else
+        // from ONE query (1.2 - 1.4 us) of the newest compose that is pipe_depth launches old — the younger ones are surely in flight — whose answer also covers the
+        // pipe_depth frames that follow; only when that one is not over from the slot's own event, as every frame did before (NRAYS_PIPELINE_LEAN=0: still does).
+        const uint64_t need = sc->pipe.slot_launch[pf.ps];
+        bool proved = sc->sw.lean_slots && need <= sc->pipe.composed_seen;
+        if (!proved && sc->sw.lean_slots && pf.launch > (uint64_t)sc->sw.pipe_depth) {
+            const uint64_t cand = pf.launch - (uint64_t)sc->sw.pipe_depth; const int cs = (int)((cand - 1u) % (uint64_t)sc->pipe.slots);
+            if (cand > need && sc->pipe.slot_launch[cs] == cand) { // (a direct frame took that launch number: no event of its own)
+                if (hipEventQuery(sc->pipe.ev_composed[cs]) == hipSuccess) { sc->pipe.composed_seen = cand; proved = true; } else (void)hipGetLastError();
+            }
+        }
+        if (!proved) {
+            if (hipEventQuery(sc->pipe.ev_composed[pf.ps]) == hipSuccess) sc->pipe.composed_seen = std::max(sc->pipe.composed_seen, need);
+            else { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->pipe.ev_composed[pf.ps], 0)); }
+        }
         ht.mark("pipeline: waits of the trace stream");
     }
     return NRAYS_OK;
 }
 // The second half of a pipelined frame: the caller's stream waits for the trace, then k_compose writes every float of `out`.
 // (an error from here on leaves a trace in flight that no compose follows: it is drained, and what comes next is ordered as after direct work)  Touches sc->pipe only.
-static int pipeline_compose(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, float* d_out, hipStream_t stream, const HostTimes& ht) {
+static int pipeline_compose(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, float* d_out, hipStream_t stream, unsigned long long* stamp, const HostTimes& ht) {
     auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(pf.lstream); sc->pipe.last_pipelined = false; } return e; };
     HIP_TRY(drained(hipStreamWaitEvent(stream, sc->pipe.ev_traced[pf.ps], 0)));
     ht.mark("pipeline: wait of the caller's stream");
-    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->pipe.ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->facts.d.background[0], sc->facts.d.background[1], sc->facts.d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1);
+    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->pipe.ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->facts.d.background[0], sc->facts.d.background[1], sc->facts.d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1, stamp);
     HIP_TRY(drained(hipGetLastError()));
+    sc->pipe.slot_launch[pf.ps] = sc->pipe.newest_launch = pf.launch;
     ht.mark("pipeline: k_compose launch");
     return NRAYS_OK;
 }
 
 // End-of-frame bookkeeping: the frame's last event, what the handle's next call orders itself behind, what nrays_get_stats reports.  Writes sc->last, the frame's
 // slot of sc->ring and pipe.last_pipelined.
-static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, hipStream_t stream, bool instrumented, const HostTimes& ht) {
+static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, hipStream_t stream, bool instrumented, uint8_t timed_by, const HostTimes& ht) {
     const bool pipelined = pf.on;
     // (a pipelined frame's kernel_ms_total runs from its trace to the end of its compose; its "done" event is the compose's)
-    if ((!f.single_launch || pipelined) && f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_end[f.slot], stream));
+    if ((!f.single_launch || pipelined) && f.timed && timed_by == NraysScene::Ring::kByEvents) HIP_TRY(hipEventRecord(sc->ring.ev_end[f.slot], stream));
     sc->last.timed = f.timed || pipelined;
     if (f.timed) {
+        sc->ring.timed_by[f.slot] = timed_by;
         sc->ring.single_launch[f.slot] = f.single_launch && !pipelined;
         sc->last.done = sc->ring.single_launch[f.slot] ? sc->ring.ev_pend[f.slot] : sc->ring.ev_end[f.slot];
         sc->ring.frames_recorded++;
@@ -793,12 +806,8 @@ static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FrameP
     sc->pipe.last_pipelined = pipelined;
     sc->last.stream = stream; sc->last.have = true;
     ht.mark("end (event records after the launch)");
-    // owned rows only (padding rows of the last band carry no rays)
-    uint64_t owned_rows = 0;
-    if (p->band_rows == 0 || p->band_owners <= 1) owned_rows = p->height;
-    else for (uint32_t j = 0; j < p->height; ++j) if (((j / p->band_rows) % p->band_owners) == p->band_owner) ++owned_rows;
-    sc->last.primary = owned_rows * p->width * p->ray_per_pixel;
-    sc->last.primary_first_batch = owned_rows * p->width * std::min<uint32_t>(f.batch, p->ray_per_pixel);
+    sc->last.primary = f.owned_rows * p->width * p->ray_per_pixel;
+    sc->last.primary_first_batch = f.owned_rows * p->width * std::min<uint32_t>(f.batch, p->ray_per_pixel);
     sc->last.instrumented = instrumented;
     return NRAYS_OK;
 }
@@ -809,7 +818,14 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
     const bool interleaved = g_last_renderer.exchange(sc, std::memory_order_relaxed) != sc;
     const HostTimes ht{sc->sw.host_times_from && sc->ring.frames_total + 1 >= sc->sw.host_times_from && sc->ring.frames_total + 1 < sc->sw.host_times_from + 4, sc->ring.frames_total, std::chrono::steady_clock::now()};
     FramePlan f; DRender R;
-    { const int rc = plan_frame(sc, p, instrumented, f, R); if (rc != NRAYS_OK) return rc; }
+    if (sc->sw.lean_plan && sc->plan.valid && sc->plan.instrumented == instrumented && std::memcmp(&sc->plan.p, p, sizeof *p) == 0) { f = sc->plan.f; R = sc->plan.R; } // a resting camera
+    else {
+        sc->plan.valid = false;
+        const int rc = plan_frame(sc, p, instrumented, f, R); if (rc != NRAYS_OK) return rc;
+        if (sc->sw.lean_plan) { std::memcpy(&sc->plan.p, p, sizeof *p); sc->plan.instrumented = instrumented; sc->plan.f = f; sc->plan.R = R; sc->plan.valid = true; }
+    }
+    f.timed = instrumented || (sc->ring.frames_total % sc->sw.event_stride) == 0;
+    f.slot = (int)(sc->ring.frames_recorded % NraysScene::kRing);
     HIP_TRY(hipSetDevice(sc->facts.device));
     sc->last.perm_launches = 0; sc->last.perm_mixed = false; // (nrays_debug_last_permutation speaks of this render from here on)
     ht.mark("hipSetDevice");
@@ -824,6 +840,7 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
     sc->buf.frame_index++;
     sc->ring.has_prepass[f.slot] = false;
     PipeFrame pf{}; // (direct until pipeline_prepare says otherwise)
+    uint8_t timed_by = NraysScene::Ring::kByEvents;
     if (f.staged) {
         sc->buf.d_counts = sc->buf.d_counts_set[sc->buf.launch_index % (uint64_t)sc->buf.count_rot];
         uint32_t* next_counts = sc->buf.d_counts_set[(sc->buf.launch_index + (uint64_t)sc->buf.count_rot / 2u) % (uint64_t)sc->buf.count_rot];
@@ -841,6 +858,9 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
         R.cost_meta = sc->order.d_cost_meta; // (read by the instrumented kernel only)
         ht.mark("scheduling state (seed / sort launches)");
         { const int rc = pipeline_prepare(sc, p, f, R, stream, interleaved, ht, pf); if (rc != NRAYS_OK) return rc; }
+        // a timed pipelined frame is timed by its own kernels (Ring::d_stamps): none of the slot's events is recorded
+        if (pf.on && f.timed && sc->sw.lean_stamps && sc->ring.d_stamps) { timed_by = NraysScene::Ring::kByStamps; R.stamp = sc->ring.d_stamps + 4u * (size_t)f.slot; }
+        const bool ring_events = f.timed && timed_by == NraysScene::Ring::kByEvents;
         bool first_primary = true;
         for (uint32_t s0 = 0; s0 < p->ray_per_pixel; s0 += f.batch) {
             R.sample_begin = s0; R.sample_end = std::min<uint32_t>(p->ray_per_pixel, s0 + f.batch);
@@ -850,7 +870,7 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
             sc->buf.launch_index++;
             QueueOut qo; qo.q = sc->buf.queue[1].q; qo.capacity = f.queued ? sc->buf.queue_capacity : 0; qo.count = sc->buf.d_counts + 1;
             qo.overflow = &sc->buf.d_counters->overflow;
-            if (first_primary && f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_pbegin[f.slot], pf.lstream));
+            if (first_primary && ring_events) HIP_TRY(hipEventRecord(sc->ring.ev_pbegin[f.slot], pf.lstream));
             if (first_primary) ht.mark("event record before the launch");
             // a launch that records its tile costs is timed (nrays_get_tile_costs: NraysTileCosts::kernel_ms): by the ring's events when the frame has them, by a pair of its own otherwise
             const bool rec_events = first_primary && R.tile_cost && !f.timed && sc->order.ev_rec[0] && sc->order.ev_rec[1];
@@ -867,10 +887,11 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
             launch_primary(sc, stats, sc->facts.features, sc->facts.noxform, sc->facts.park, sc->facts.tiny, f.occ, f.grid, pf.lstream, dsc, R, qo, pf.on ? pf.stage : d_out, sc->buf.d_counters,
                            pf.on ? sc->pipe.spill[pf.pst] : sc->buf.d_spill, f.tiles_x, f.tiles_y, sc->buf.d_counts + kMaxGenerations + 2, f.grab, next_counts, R.first_batch ? next_ctr : nullptr, pf.on ? sc->pipe.ev_traced[pf.ps] : nullptr);
             HIP_TRY(hipGetLastError());
+            if (R.stamp && (sc->last.perm_last[0] || (sc->last.perm_last[1] & (uint32_t)kFeatMesh))) timed_by = NraysScene::Ring::kUntimed; // (a tuning build's fall-back kernel does not stamp)
             if (first_primary) ht.mark("k_primary launch");
             if (rec_events) HIP_TRY(hipEventRecord(sc->order.ev_rec[1], stream));
             if (first_primary) {
-                if (f.timed) HIP_TRY(hipEventRecord(sc->ring.ev_pend[f.slot], pf.lstream));
+                if (ring_events) HIP_TRY(hipEventRecord(sc->ring.ev_pend[f.slot], pf.lstream));
                 if (instrumented) HIP_TRY(hipMemcpyAsync(sc->ring.d_counters_primary, sc->buf.d_counters, sizeof(DeviceCounters), hipMemcpyDeviceToDevice, stream));
                 first_primary = false;
             }
@@ -880,14 +901,14 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
                 if (rc != NRAYS_OK) return rc;
             }
         }
-        if (pf.on) { const int rc = pipeline_compose(sc, p, f, pf, d_out, stream, ht); if (rc != NRAYS_OK) return rc; }
+        if (pf.on) { const int rc = pipeline_compose(sc, p, f, pf, d_out, stream, R.stamp, ht); if (rc != NRAYS_OK) return rc; }
     }
     if (p->ray_per_pixel > 1) {
         size_t n = (size_t)f.npix_local * 3;
         hipLaunchKernelGGL(k_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, n, (float)p->ray_per_pixel);
         HIP_TRY(hipGetLastError());
     }
-    return finish_frame(sc, p, f, pf, stream, instrumented, ht);
+    return finish_frame(sc, p, f, pf, stream, instrumented, timed_by, ht);
 }
 
 } // namespace nrays

@@ -354,6 +354,10 @@ static int allocate_handle_state(NraysScene* sc, StageClock& clock) {
     clock.mark("records, switches, counters");
     if (hipMalloc((void**)&sc->ring.d_counters_primary, sizeof(DeviceCounters)) != hipSuccess)
         return fail(NRAYS_ERR_OOM, "counter allocation failed");
+    // the stamps of timed pipelined frames (scene_handle.h: Ring::d_stamps): zeroed once, never cleared afterwards
+    if (sc->sw.lean_stamps && (hipMalloc((void**)&sc->ring.d_stamps, (size_t)NraysScene::kRing * 4 * sizeof(unsigned long long)) != hipSuccess ||
+                               hipMemset(sc->ring.d_stamps, 0, (size_t)NraysScene::kRing * 4 * sizeof(unsigned long long)) != hipSuccess))
+        return fail(NRAYS_ERR_OOM, "stamp allocation failed");
     // (own_stream is created by the first entry point that needs it, ensure_own_stream(): a handle that is only ever rendered on the caller's streams leaves its
     // hardware queue to the internal streams of the pipelined frames — a stream that exists holds a queue, and a process has four)
     // (the ring's timing events are created by the first frame that records into a slot: 1 024 hipEventCreate cost 0.6 ms of every scene creation)
@@ -431,6 +435,7 @@ void nrays_scene_destroy(NraysScene* sc) {
     for (int k = 0; k < 2; ++k) if (sc->order.ev_rec[k]) (void)hipEventDestroy(sc->order.ev_rec[k]);
     // ring
     if (sc->ring.d_counters_primary) (void)hipFree(sc->ring.d_counters_primary);
+    if (sc->ring.d_stamps) (void)hipFree(sc->ring.d_stamps);
     for (int k = 0; k < NraysScene::kRing; ++k)
         for (hipEvent_t e : {sc->ring.ev_begin[k], sc->ring.ev_pbegin[k], sc->ring.ev_pend[k], sc->ring.ev_end[k]}) if (e) (void)hipEventDestroy(e);
     // last
@@ -477,9 +482,21 @@ int nrays_get_stats(NraysScene* sc, NraysStats* out) {
     uint64_t first = sc->ring.frames_reported;
     if (sc->ring.frames_recorded - first > (uint64_t)NraysScene::kRing) first = sc->ring.frames_recorded - NraysScene::kRing;
     double sum_p = 0.0, sum_t = 0.0; uint64_t n = 0;
+    // (timed pipelined frames left 100 MHz ticks instead of events — trace start, trace end, compose end: the whole array in one copy, behind the synchronisation above)
+    std::vector<unsigned long long> stamps;
+    for (uint64_t f = first; f < sc->ring.frames_recorded && stamps.empty(); ++f)
+        if (sc->ring.timed_by[f % NraysScene::kRing] == NraysScene::Ring::kByStamps && sc->ring.d_stamps) {
+            stamps.resize((size_t)NraysScene::kRing * 4);
+            HIP_TRY(hipMemcpy(stamps.data(), sc->ring.d_stamps, stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        }
     for (uint64_t f = first; f < sc->ring.frames_recorded; ++f) {
         int k = (int)(f % NraysScene::kRing);
         float ms_p = 0.f, ms_t = 0.f;
+        if (sc->ring.timed_by[k] != NraysScene::Ring::kByEvents) { // a slot whose end is not later than its start is skipped, like an event pair that is not ready
+            const unsigned long long* w = stamps.empty() ? nullptr : &stamps[4 * (size_t)k];
+            if (sc->ring.timed_by[k] == NraysScene::Ring::kByStamps && w && w[1] > w[0] && w[2] >= w[1]) { sum_p += (double)(w[1] - w[0]) * 1e-5; sum_t += (double)(w[2] - w[0]) * 1e-5; ++n; }
+            continue;
+        }
         if (hipEventElapsedTime(&ms_p, sc->ring.ev_pbegin[k], sc->ring.ev_pend[k]) == hipSuccess &&
             hipEventElapsedTime(&ms_t, sc->ring.has_prepass[k] ? sc->ring.ev_begin[k] : sc->ring.ev_pbegin[k], sc->ring.single_launch[k] ? sc->ring.ev_pend[k] : sc->ring.ev_end[k]) == hipSuccess) { sum_p += ms_p; sum_t += ms_t; ++n; }
     }

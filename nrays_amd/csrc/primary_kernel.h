@@ -179,6 +179,15 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
     // 0.5 - 1 % of the analytic kernels' steady frames.
     __shared__ uint32_t clk_start[STATS ? 2 : 1];
     if (STATS && R.cost_meta && (blockIdx.x & 31u) == 0u && threadIdx.x == 0u) { clk_start[0] = (uint32_t)__builtin_readcyclecounter(); clk_start[1] = (uint32_t)__builtin_amdgcn_s_memrealtime(); }
+    // The trace half of a timed pipelined frame stamps itself (DRender::stamp) instead of being bracketed by two event records on the host: only the permutations such a
+    // frame can launch — analytic scenes, not instrumented — carry the code.
+    constexpr bool kStamps = !STATS && !(FEAT & kFeatMesh);
+    if constexpr (kStamps) {
+        if (blockIdx.x == 0 && threadIdx.x == 0u) {
+            unsigned long long* const stamp = *(unsigned long long* const volatile*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(DScene) + offsetof(DRender, stamp));
+            if (stamp) stamp[0] = __builtin_amdgcn_s_memrealtime();
+        }
+    }
     Cnt cnt; cnt.zero();
 #ifdef NR_PHASE_TIMING
     unsigned long long twave = __builtin_readcyclecounter();
@@ -459,6 +468,12 @@ __global__ void __launch_bounds__(kBlock, OCC ? NR_OCC3_AS : waves_per_simd(FEAT
         atomicAdd(&R.cost_meta[3], (unsigned long long)((uint32_t)__builtin_amdgcn_s_memrealtime() - clk_start[STATS ? 1 : 0]));
     }
     flush_counters(ctr, cnt, STATS);
+    if constexpr (kStamps) {
+        // (lane 0 of every WAVE, like the counters above: `threadIdx.x == 0` would keep v0 alive through the whole kernel — one VGPR more in the FEAT 1 and 5 general kernels.  The
+        // pointer is read from the kernel-argument segment here, like m_mem, not kept from the entry on.)
+        unsigned long long* const stamp = *(unsigned long long* const volatile*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(DScene) + offsetof(DRender, stamp));
+        if (stamp && __lane_id() == 0u) atomicMax(&stamp[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
 }
 
 } // namespace nrays

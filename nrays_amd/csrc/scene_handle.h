@@ -34,6 +34,21 @@ struct QueueMem {
 // the distance to the scene's bounding box.
 struct CamSnap { double eye[3] = {0, 0, 0}; double dir[4][3] = {}; double pix_angle = 0.0, depth = 1.0; bool valid = false; };
 
+// What plan_frame (frame_path.hip) decides once per frame.  The phases read it; the header comment of each names what it may still change: grid, grab, R.lead_*, R.tile_order,
+// R.tile_cost — and which group of the handle it writes.  Every phase reads sc->sw and sc->facts; none writes them.
+struct FramePlan {
+    uint32_t rows; uint64_t npix_local;    // rows and pixels of the local frame buffer
+    uint64_t owned_rows;                   // rows of the image this frame owns (all of them, or its bands): what the ray counts are made of
+    bool queued; uint32_t batch;           // the scene needs the HBM queue (double branching); samples per k_primary launch
+    uint32_t lane_log2, bwl, bhl;          // log2 of the lanes per pixel of an anti-aliased frame, of the width / height of a scheduling unit's pixel block
+    uint32_t tiles_x, tiles_y, ntiles;     // scheduling blocks of the frame; ntiles in units of four wave tiles
+    bool banded; uint32_t win_units;       // the frame owns bands of rows only; scheduling blocks inside the window (DRender::win_*)
+    int occ; uint32_t grid, grab;          // k_primary's OCC (0 or 3), its persistent grid, tiles per dequeue (0 = workgroup lists through LDS)
+    bool timed; int slot;                  // this frame is timed (events or stamps of the ring), into this slot
+    bool single_launch, staged;            // nothing follows the one k_primary launch; the staged path (wavefront.hip) renders the frame
+    uint64_t sched_key, cam; CamSnap snap; // geometry key, camera hash and camera of the per-camera scheduling state (not filled for staged frames)
+};
+
 constexpr int kNumCounts = kMaxGenerations + 2 + 8; // queue round counters + 8 per-XCD work counters
 constexpr int kMaxGrid = 2048;     // upper bound of the persistent grid (the launch uses CUs x waves/SIMD workgroups)
 
@@ -155,6 +170,10 @@ struct NraysScene {
         uint32_t* spill[kPipeStreams] = {};     // a traversal-stack spill region per internal stream (spill_entries != 0): traces that overlap must not share buf.d_spill
         hipEvent_t ev_traced[kPipeSlots] = {}, ev_composed[kPipeSlots] = {};
         bool last_pipelined = false;            // the previous work of the handle was a pipelined frame: last.done is its "composed" event
+        // Which composes the host knows to be over (Switches::lean_slots), in launch numbers (buf.launch_index of the frame's trace + 1; 0 = none).  Composes run in call order
+        // on the caller's streams, each ordered behind its predecessor, so a compose seen finished proves every earlier one: a trace into a slot whose last compose is at or below
+        // composed_seen needs neither a query nor a wait.  slot_launch[s]: the compose ev_composed[s] was last recorded behind; newest_launch: the handle's latest compose.
+        uint64_t composed_seen = 0, newest_launch = 0, slot_launch[kPipeSlots] = {};
     } pipe;
 
     // Ring of HIP event triples (frame begin, primary kernel begin/end, frame end) recorded on the render
@@ -166,7 +185,20 @@ struct NraysScene {
         bool has_prepass[kRing] = {}; // the frame started with k_tile_order: ev_begin was recorded before it
         uint64_t frames_recorded = 0, frames_reported = 0, frames_total = 0;
         DeviceCounters* d_counters_primary = nullptr; // snapshot taken right after the primary kernel
+        // A timed PIPELINED frame records none of the slot's events (three records cost its call 8 - 9 us): its trace and its compose leave 100 MHz ticks in the slot's four
+        // words of d_stamps (DRender::stamp; allocated and zeroed with the handle, Switches::lean_stamps), which nrays_get_stats copies in one piece.
+        enum : uint8_t { kByEvents = 0, kByStamps = 1, kUntimed = 2 }; // kUntimed: the launch fell back to a kernel that does not stamp (tuning builds)
+        uint8_t timed_by[kRing] = {};
+        unsigned long long* d_stamps = nullptr; // kRing x 4 words
     } ring;
+
+    // The plan of the last parameter block (Switches::lean_plan): a call whose block and `instrumented` flag are the same bytes reuses `f` and `R` as plan_frame left them —
+    // before the schedulers and pipeline_prepare changed anything — and recomputes only f.timed and f.slot.  What plan_frame reads of the handle (sw, facts) never changes.
+    struct Plan {
+        bool valid = false, instrumented = false;
+        NraysRenderParams p;
+        nrays::FramePlan f; nrays::DRender R;
+    } plan;
 
     // The last render: what the next call orders itself behind, what nrays_get_stats and the probes report.
     struct Last {

@@ -48,6 +48,7 @@ Switches read_switches() {
     if (const char* e = getenv("NRAYS_PIPELINE")) { s.pipeline = atoi(e) != 0; s.pipeline_always = atoi(e) == 2; }
     clamped("NRAYS_PIPELINE_DEPTH", s.pipe_depth, 1, 3);
     flag("NRAYS_PIPELINE_LEAD_WGS", s.pipe_lead_wgs);
+    if (const char* e = getenv("NRAYS_PIPELINE_LEAN")) { const int v = atoi(e); s.lean_stamps = (v & 1) != 0; s.lean_slots = (v & 2) != 0; s.lean_plan = (v & 4) != 0; }
     real("NRAYS_NEAR_PIXELS", s.near_pixels);
     if (const char* e = getenv("NRAYS_ORDER_AGE")) s.max_order_age = (uint32_t)std::max(0, atoi(e));
     flag("NRAYS_LEAD_WGS", s.lead_mode);

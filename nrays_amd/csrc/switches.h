@@ -39,6 +39,8 @@ struct Switches {
     bool pipeline = true, pipeline_always = false; // NRAYS_PIPELINE=0|2: every frame on the direct path (A/B, tests) / every eligible frame pipelined, in flight or not (tests: no dependence on timing)
     int pipe_depth = 3;                 // NRAYS_PIPELINE_DEPTH=1|2|3: traces of the handle in flight at once = its internal streams
     std::optional<bool> pipe_lead_wgs;  // NRAYS_PIPELINE_LEAD_WGS=0|1: a pipelined trace keeps the lead + second workgroups of a direct frame, or runs its lists on one workgroup per CU (unset: by the depth)
+    bool lean_stamps = true, lean_slots = true, lean_plan = true; // NRAYS_PIPELINE_LEAN=0: the host path of a pipelined frame as it was — event records on timed frames, a query of the slot's
+                                        // compose per frame, the plan recomputed per call (A/B; =n: the sum of 1 device stamps, 2 one slot query per several frames, 4 the plan of an unchanged block)
     std::optional<double> near_pixels;  // NRAYS_NEAR_PIXELS=x: a camera within x pixels of an order's camera reuses the order (unset: by the scene)
     std::optional<uint32_t> max_order_age; // NRAYS_ORDER_AGE=n: frames of nearby cameras an order serves before it is re-sorted (unset: by the scene)
     bool lead_mode = true;              // NRAYS_LEAD_WGS=0: cost-ordered lists run on one workgroup per CU instead of lead + second workgroups
