@@ -558,17 +558,24 @@ NR_DEV f4 tex_at(const ShadeTex& t, uint32_t x, uint32_t y) {
     }
     return r;
 }
+// Rust's `f32 as usize` (texture2d.rs:230-237): truncation, saturating, NaN and negative values -> 0.  The plain C++ cast is undefined for a NaN (an inf
+// uv under Wrap: inf % 1) and out of range, whatever v_cvt_u32_f32 does with it.
+NR_DEV uint32_t tex_index(float x) {
+    if (!(x > 0.0f)) return 0u;
+    return x >= 4294967296.0f ? 0xffffffffu : (uint32_t)x;
+}
 // Texture2d::sample (texture2d.rs:207-256), taps clamped to the last row/column.
 template <bool STATS>
 NR_DEV f4 tex_sample(const ShadeTex& t, double u, double v, Cnt& cnt) {
     if (STATS) cnt.tex++;
     float ux = (float)u, uy = (float)v;
     if (((t.mode >> 16) & 0xffu) == NRAYS_OVERFLOW_CLAMP) {
-        ux = ux < 0.0f ? 0.0f : (ux > 1.0f ? 1.0f : ux);
-        uy = uy < 0.0f ? 0.0f : (uy > 1.0f ? 1.0f : uy);
+        // na::clamp (texture2d.rs:213-214) is `if val > min { if val < max { val } else { max } } else { min }`: a NaN becomes 0.0, as there
+        ux = ux > 0.0f ? (ux < 1.0f ? ux : 1.0f) : 0.0f;
+        uy = uy > 0.0f ? (uy < 1.0f ? uy : 1.0f) : 0.0f;
     } else {
         // `% 1.0` (texture2d.rs:215-221) is fmodf(x, 1): the fractional part with the sign of x — x - trunc(x) is exact in f32, so
-        // three instructions give the library routine's value bit for bit (checked over 2 M values incl. -0, 2^23 and denormals)
+        // three instructions give the library routine's value bit for bit (tests/test_numerics_tables.py: 4 M values incl. -0, 2^23 and denormals)
         ux = copysignf(ux - truncf(ux), ux); uy = copysignf(uy - truncf(uy), uy);
         if (ux < 0.0f) ux = 1.0f + ux;
         if (uy < 0.0f) uy = 1.0f + uy;
@@ -577,12 +584,12 @@ NR_DEV f4 tex_sample(const ShadeTex& t, double u, double v, Cnt& cnt) {
     uy = uy * (float)(t.height - 1);
     uint32_t wm = t.width - 1, hm = t.height - 1;
     if (((t.mode >> 8) & 0xffu) == NRAYS_INTERP_NEAREST) {
-        uint32_t x = (uint32_t)roundf(ux), y = (uint32_t)roundf(uy);
+        uint32_t x = tex_index(roundf(ux)), y = tex_index(roundf(uy));
         if (x > wm) x = wm;
         if (y > hm) y = hm;
         return tex_at(t, x, y);
     }
-    uint32_t lx = (uint32_t)floorf(ux), ly = (uint32_t)floorf(uy);
+    uint32_t lx = tex_index(floorf(ux)), ly = tex_index(floorf(uy));
     if (lx > wm) lx = wm;
     if (ly > hm) ly = hm;
     uint32_t hx = lx + 1, hy = ly + 1;

@@ -745,13 +745,21 @@ static inline c4 tex_at(const NraysTexture* t, uint32_t x, uint32_t y) { /* text
     }
     return r;
 }
+/* Rust's `f32 as usize` (texture2d.rs:230-237): truncation, saturating, NaN and negative values -> 0.  The plain C cast is undefined for a NaN
+ * (an inf uv under Wrap: inf % 1) and out of range. */
+static inline uint32_t sat_u32(float x) {
+    if (!(x > 0.0f)) return 0u;
+    return x >= 4294967296.0f ? UINT32_MAX : (uint32_t)x;
+}
+/* na::clamp(val, min, max) of texture2d.rs:213-214: `if val > min { if val < max { val } else { max } } else { min }` — a NaN becomes min. */
+static inline float na_clamp(float x, float mn, float mx) { return x > mn ? (x < mx ? x : mx) : mn; }
 /* Texture2d::sample, src/texture2d.rs:207-256 (taps clamped: D-6). */
 static c4 tex_sample(const NraysTexture* t, double u, double v, Counters* cnt) {
     cnt->tex_samples++;
     float ux = (float)u, uy = (float)v;
     if (t->overflow == NRAYS_OVERFLOW_CLAMP) {
-        ux = ux < 0.0f ? 0.0f : (ux > 1.0f ? 1.0f : ux);
-        uy = uy < 0.0f ? 0.0f : (uy > 1.0f ? 1.0f : uy);
+        ux = na_clamp(ux, 0.0f, 1.0f);
+        uy = na_clamp(uy, 0.0f, 1.0f);
     } else {
         ux = fmodf(ux, 1.0f); uy = fmodf(uy, 1.0f);
         if (ux < 0.0f) ux = 1.0f + ux;
@@ -761,11 +769,11 @@ static c4 tex_sample(const NraysTexture* t, double u, double v, Counters* cnt) {
     uy = uy * (float)(t->height - 1);
     uint32_t wm = t->width - 1, hm = t->height - 1;
     if (t->interp == NRAYS_INTERP_NEAREST) {
-        uint32_t x = (uint32_t)roundf(ux), y = (uint32_t)roundf(uy);
+        uint32_t x = sat_u32(roundf(ux)), y = sat_u32(roundf(uy));
         if (x > wm) x = wm; if (y > hm) y = hm;
         return tex_at(t, x, y);
     }
-    uint32_t lx = (uint32_t)floorf(ux), ly = (uint32_t)floorf(uy);
+    uint32_t lx = sat_u32(floorf(ux)), ly = sat_u32(floorf(uy));
     if (lx > wm) lx = wm; if (ly > hm) ly = hm;
     uint32_t hx = lx + 1, hy = ly + 1;
     float sx = ux - (float)lx, sy = uy - (float)ly;
