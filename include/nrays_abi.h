@@ -32,7 +32,7 @@ extern "C" {
 /* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6); 6 = nrays_trace_rays_device / nrays_trace_rays /
  * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation.
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
- * nrays_intersects_rays_device_ex / nrays_debug_ray_order.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -289,6 +289,34 @@ int nrays_trace_rays_ex(NraysScene* scene, uint32_t n, const double* origins, co
                         const uint64_t* keys, uint32_t max_depth, float* out_rgb, uint32_t flags);
 int nrays_intersects_rays_device_ex(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
                                     float* out_filter, uint32_t* out_lit, uint32_t flags, void* hip_stream);
+
+/* Scene::trace's closest-hit query (src/scene.rs:164-166, 262-283) with the record SceneNode::cast returns (src/scene_node.rs:51-54) on n
+ * caller-supplied rays: WHICH node ray i meets first, where, with which normal and uv (picking, depth / normal / id passes, the first hop of
+ * a baker that builds its own secondary rays).  The query is the one a render's shading runs: ties between nodes and triangles are broken
+ * the same way and every accepted hit has passed the reference's exact AABB gates.
+ *   origins, dirs  n x 3 doubles, xyz interleaved; directions are used as given (nrays_trace_rays_device).
+ *   max_toi        n doubles, or NULL = unbounded.  The answer is that of the unbounded query if its toi <= max_toi[i] and a miss otherwise,
+ *                  bit for bit (the bound filters the finished query; it never changes which hit wins).  +inf = unbounded, NaN = a miss.
+ *   out_toi        n doubles, required.          out_node   n scene-node indices, required.
+ *   out_normal     n x 3 doubles, world space.   out_uv     n x 2 doubles (zeros where the record carries none).
+ *   out_prim       n: the triangle's index in its NraysMesh::indices (triangle t = indices[3t..3t+2]), -1 for an analytic shape.
+ *   out_flags      n: the bits of NraysCastResult::flags — bit 0 = hit, bit 1 = the record carries uvs.
+ *                  Each of these four may be NULL: that output is then not computed into memory at all (no store).
+ * A miss writes out_node = -1, out_toi = +inf, zeros in out_normal and out_uv, out_prim = -1, out_flags = 0; a hit's toi is finite, so depth
+ * compares and minima work on out_toi directly.
+ *   flags          0 or NRAYS_RAYS_UNORDERED (same meaning, threshold and reorder as for the other batches; results bit-identical); any other
+ *                  bit -> NRAYS_ERR_BAD_ARG.
+ * NULL scene / origins / dirs / out_toi / out_node -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK without work.  Otherwise the contract of
+ * nrays_intersects_rays_device: every pointer DEVICE memory on the scene's device, chunks of at most 2^22 rays, enqueued on `hip_stream`
+ * without read-back or synchronisation, ordered behind the handle's previous work; what the handle reports about its renders and its
+ * per-camera scheduling state stay untouched. */
+int nrays_cast_rays_device(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
+                           double* out_toi, int32_t* out_node, double* out_normal, double* out_uv, int32_t* out_prim,
+                           uint32_t* out_flags, uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_cast_rays(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
+                    double* out_toi, int32_t* out_node, double* out_normal, double* out_uv, int32_t* out_prim,
+                    uint32_t* out_flags, uint32_t flags);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

@@ -18,6 +18,7 @@ use std::ptr;
 use std::sync::Arc;
 
 use na::{Matrix4, Point2, Point3, Point4, Vector2, Vector3};
+use ncollide3d::query::Ray;
 use ncollide3d::shape::{Ball, Capsule, Cone, Cuboid, Cylinder, Plane, TriMesh};
 
 use gpu_ffi::*;
@@ -329,6 +330,15 @@ fn params(resolution: &Vless, ray_per_pixel: usize, window_width: Scalar, camera
     }
 }
 
+/// One closest hit of `GpuScene::cast_rays`: what `SceneNode::cast` returns (src/scene_node.rs:51-54) and which node returned it.
+pub struct CastHit {
+    pub node: usize,             // index into scene.nodes()
+    pub toi: f64,
+    pub normal: Vector3<f64>,    // world space
+    pub uvs: Option<Point2<f64>>,
+    pub triangle: Option<usize>, // index of the triangle in its TriMesh; None for an analytic shape
+}
+
 /// A scene resident on ONE GPU (the calling thread's current HIP device).
 pub struct GpuScene {
     raw: *mut NraysScene,
@@ -398,6 +408,45 @@ impl GpuScene {
     pub unsafe fn intersects_rays_unordered(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32,
                                             hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_intersects_rays_device_ex(self.raw, n, origins, dirs, max_toi, out_filter, out_lit, NRAYS_RAYS_UNORDERED, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// The closest-hit query of `scene.trace` (src/scene.rs:164-166, 262-283) with the record `SceneNode::cast` returns (src/scene_node.rs:51-54)
+    /// for every ray of the batch, in one call (nrays_cast_rays, blocking): `None` where ray i meets nothing within `max_toi[i]` (no bounds:
+    /// unbounded), otherwise the node's index in `scene.nodes()`, toi, world normal, uvs where the shape carries them, and the triangle's index in
+    /// its mesh (`None` for an analytic shape).  `unordered`: the rays come in no useful order (NRAYS_RAYS_UNORDERED); the results are the same.
+    pub fn cast_rays(&self, rays: &[Ray<Scalar>], max_toi: Option<&[f64]>, unordered: bool) -> Result<Vec<Option<CastHit>>, String> {
+        if let Some(t) = max_toi { if t.len() != rays.len() { return Err(format!("{} bounds for {} rays", t.len(), rays.len())); } }
+        let n = rays.len();
+        let mut o = Vec::with_capacity(3 * n);
+        let mut d = Vec::with_capacity(3 * n);
+        for r in rays {
+            o.extend_from_slice(&[r.origin.x, r.origin.y, r.origin.z]);
+            d.extend_from_slice(&[r.dir.x, r.dir.y, r.dir.z]);
+        }
+        let (mut toi, mut node, mut normal, mut uv) = (vec![0.0f64; n], vec![0i32; n], vec![0.0f64; 3 * n], vec![0.0f64; 2 * n]);
+        let (mut prim, mut flags) = (vec![0i32; n], vec![0u32; n]);
+        let tp = max_toi.map(|t| t.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe {
+            nrays_cast_rays(self.raw, n as u32, o.as_ptr(), d.as_ptr(), tp, toi.as_mut_ptr(), node.as_mut_ptr(), normal.as_mut_ptr(), uv.as_mut_ptr(), prim.as_mut_ptr(),
+                            flags.as_mut_ptr(), if unordered { NRAYS_RAYS_UNORDERED } else { 0 })
+        };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| if flags[i] & 1 == 0 { None } else {
+            Some(CastHit {
+                node: node[i] as usize, toi: toi[i], normal: Vector3::new(normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]),
+                uvs: if flags[i] & 2 != 0 { Some(Point2::new(uv[2 * i], uv[2 * i + 1])) } else { None },
+                triangle: if prim[i] >= 0 { Some(prim[i] as usize) } else { None },
+            })
+        }).collect())
+    }
+
+    /// `cast_rays` for n rays in DEVICE memory (nrays_cast_rays_device), enqueued on `hip_stream` without synchronisation: origins / dirs n x 3 f64,
+    /// max_toi n f64 or null, out_toi n f64, out_node n i32; out_normal (n x 3 f64), out_uv (n x 2 f64), out_prim (n i32) and out_flags (n u32) may
+    /// each be null.  A miss writes node -1 and toi +inf.  `flags`: 0 or NRAYS_RAYS_UNORDERED.
+    pub unsafe fn cast_rays_device(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_toi: *mut f64, out_node: *mut i32, out_normal: *mut f64,
+                                   out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_cast_rays_device(self.raw, n, origins, dirs, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 }

@@ -231,6 +231,8 @@ extern "C" {
     pub fn nrays_trace_rays_device_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_trace_rays_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, flags: u32) -> c_int;
     pub fn nrays_intersects_rays_device_ex(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_cast_rays_device(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_toi: *mut f64, out_node: *mut i32, out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_cast_rays(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_toi: *mut f64, out_node: *mut i32, out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;

@@ -1,5 +1,5 @@
-// ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*): k_trace_rays and
-// k_intersects_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
+// ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*): k_trace_rays,
+// k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  Device code only.
 #pragma once
@@ -91,6 +91,64 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_ray
                                                                                            float* __restrict__ out_filter, uint32_t* __restrict__ out_lit, uint32_t* spill) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     intersects_rays_body<FEAT, true>(lds_stack, S, n, order, ro, rd, max_toi, out_filter, out_lit, spill);
+}
+
+// Scene::trace's closest-hit query (scene.rs:164-166, 262-283) with SceneNode::cast's record (scene_node.rs:51-54) on caller-supplied rays
+// (nrays_cast_rays_device): k_cast_batch's mode 0 — ungated traversal, the winner checked against the reference's exact AABB gates, the fully
+// gated repeat for knife-edge rays — with one array per field.  max_toi (NULL = unbounded) filters the FINISHED query (toi <= max_toi[i]
+// keeps the hit; a NaN bound keeps nothing) and never enters the traversal, so a bounded result is the unbounded one or a miss.  The four
+// optional outputs are kernel arguments: a NULL test is wave-uniform and a NULL output costs no store.  A miss writes node -1, toi +inf,
+// zeros, prim -1, flags 0.
+template <int FEAT, bool ORDERED>
+__device__ __forceinline__ void cast_rays_body(uint32_t* lds_stack, const DScene& S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                               const double* __restrict__ rd, const double* __restrict__ max_toi, double* __restrict__ out_toi,
+                                               int32_t* __restrict__ out_node, double* __restrict__ out_normal, double* __restrict__ out_uv,
+                                               int32_t* __restrict__ out_prim, uint32_t* __restrict__ out_flags, uint32_t* spill) {
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t slot = base + threadIdx.x;
+        if (slot >= n) continue;
+        const uint32_t i = ORDERED ? order[slot] : slot;
+        const size_t i3 = 3 * (size_t)i;
+        const d3 o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]), d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
+        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+        Isect is; uint32_t node_id = 0; bool gated = false, any = false;
+        for (;;) {
+            any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
+            if (!any) break;
+            if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
+            gated = true;
+        }
+        if (any && max_toi) any = hit.t <= max_toi[i];
+        out_toi[i] = any ? hit.t : __longlong_as_double(0x7ff0000000000000ll);
+        out_node[i] = any ? (int32_t)node_id : -1;
+        if (out_normal) { out_normal[i3] = any ? is.n.x : 0.0; out_normal[i3 + 1] = any ? is.n.y : 0.0; out_normal[i3 + 2] = any ? is.n.z : 0.0; }
+        if (out_uv) { out_uv[2 * (size_t)i] = any ? is.u : 0.0; out_uv[2 * (size_t)i + 1] = any ? is.v : 0.0; }
+        if (out_prim) {
+            int32_t prim = -1; // (an analytic shape)
+            if (any && (FEAT & kFeatMesh) && (!(FEAT & kFeatAnalytic) || S.instances[hit.inst].kind == NRAYS_SHAPE_TRIMESH)) prim = (int32_t)S.tris[hit.prim].tri_id;
+            out_prim[i] = prim;
+        }
+        if (out_flags) out_flags[i] = any ? (1u | (is.has_uv ? 2u : 0u)) : 0u;
+    }
+}
+
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_rays(DScene S, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                             const double* __restrict__ max_toi, double* __restrict__ out_toi, int32_t* __restrict__ out_node,
+                                                                             double* __restrict__ out_normal, double* __restrict__ out_uv, int32_t* __restrict__ out_prim,
+                                                                             uint32_t* __restrict__ out_flags, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    cast_rays_body<FEAT, false>(lds_stack, S, n, nullptr, ro, rd, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, spill);
+}
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_rays_ordered(DScene S, uint32_t n, const uint32_t* __restrict__ order, const double* __restrict__ ro,
+                                                                                     const double* __restrict__ rd, const double* __restrict__ max_toi, double* __restrict__ out_toi,
+                                                                                     int32_t* __restrict__ out_node, double* __restrict__ out_normal, double* __restrict__ out_uv,
+                                                                                     int32_t* __restrict__ out_prim, uint32_t* __restrict__ out_flags, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    cast_rays_body<FEAT, true>(lds_stack, S, n, order, ro, rd, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, spill);
 }
 
 } // namespace nrays

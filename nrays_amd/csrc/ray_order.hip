@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -11,7 +11,7 @@
 //   k_ray_keys     one lane per ray: key, bin = its leading B bits, rank = the ray's place inside its bin (returning atomic on the bin's counter)
 //   k_bin_sums / k_bin_scan / k_bin_apply   exclusive prefix sum of the counters, in place (bvh_device.hip's three-launch scan, on a stream)
 //   k_ray_place    order[start[bin] + rank] = ray
-// then k_trace_rays_ordered / k_intersects_rays_ordered (ray_batch_kernel.h).  A counting sort on B bits, not a radix sort of the key: the
+// then k_trace_rays_ordered / k_intersects_rays_ordered / k_cast_rays_ordered (ray_batch_kernel.h).  A counting sort on B bits, not a radix sort of the key: the
 // order inside a bin is free, and need not be reproducible — a ray's arithmetic is its own, whatever wave it runs in.
 //
 // The atomics are spread over 2^21 counters, and the lanes of a wave that meet in one bin (the rays of a half-ordered batch do) are
@@ -364,6 +364,101 @@ static int trace_rays_device_impl(NraysScene* sc, uint32_t n, const double* o, c
     return rc;
 }
 
+// The outputs of a closest-hit batch (nrays_cast_rays*): toi and node always, the rest where the caller wants them.
+struct CastOut { double* toi; int32_t* node; double* normal; double* uv; int32_t* prim; uint32_t* flags; };
+// One chunk (nc <= kTraceChunk) of nrays_cast_rays_device: the reorder when it is due, then k_cast_rays or its ordered form.  `out` is the chunk's.
+static int cast_chunk(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t nc, const double* o, const double* d, const double* t, const CastOut& out, hipStream_t stream) {
+    const bool mesh = (sc->facts.features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_debug_cast_batch)
+    const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const uint32_t* order = nullptr;
+    const int rc = chunk_order(sc, w, reorder, nc, o, d, stream, &order);
+    if (rc != NRAYS_OK) return rc;
+    if (order && mesh) hipLaunchKernelGGL((k_cast_rays_ordered<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, order, o, d, t, out.toi, out.node, out.normal, out.uv, out.prim, out.flags, w->d_spill);
+    else if (order) hipLaunchKernelGGL((k_cast_rays_ordered<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, order, o, d, t, out.toi, out.node, out.normal, out.uv, out.prim, out.flags, w->d_spill);
+    else if (mesh) hipLaunchKernelGGL((k_cast_rays<kFeatMesh>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, o, d, t, out.toi, out.node, out.normal, out.uv, out.prim, out.flags, w->d_spill);
+    else hipLaunchKernelGGL((k_cast_rays<kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, o, d, t, out.toi, out.node, out.normal, out.uv, out.prim, out.flags, w->d_spill);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_cast_rays: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+static CastOut cast_out_at(const CastOut& out, size_t c0) {
+    return CastOut{out.toi + c0, out.node + c0, out.normal ? out.normal + 3 * c0 : nullptr, out.uv ? out.uv + 2 * c0 : nullptr, out.prim ? out.prim + c0 : nullptr,
+                   out.flags ? out.flags + c0 : nullptr};
+}
+static int check_cast_args(const NraysScene* sc, const double* origins, const double* dirs, const CastOut& out, uint32_t flags) {
+    if (!sc || !origins || !dirs || !out.toi || !out.node) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    return check_ray_flags(flags);
+}
+
+static int cast_rays_device_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, const CastOut& out, uint32_t flags,
+                                 hipStream_t stream) {
+    if (check_cast_args(sc, origins, dirs, out, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit ray indices far from overflow)
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        rc = cast_chunk(sc, w, reorder, nc, origins + 3 * (size_t)c0, dirs + 3 * (size_t)c0, max_toi ? max_toi + c0 : nullptr, cast_out_at(out, c0), stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form: one chunk at a time through the workspace's staging buffer.  A staged ray takes kCastStageBytes: origin, direction (3 f64), max_toi, toi (f64),
+// normal (3 f64), uv (2 f64), node, prim, flags (32 bits) — the 8-byte fields first, so that every array is aligned for any chunk size.
+constexpr size_t kStageUnit = 80, kCastStageBytes = 116; // TraceWorkspace::stage_rays counts units of kStageUnit bytes (a ray of nrays_trace_rays)
+static size_t cast_stage_units(uint32_t rays) { return ((size_t)rays * kCastStageBytes + kStageUnit - 1) / kStageUnit; }
+static int cast_rays_host_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, const CastOut& out, uint32_t flags) {
+    if (check_cast_args(sc, origins, dirs, out, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    const size_t cap = std::min<uint32_t>(n, kTraceChunk);
+    rc = grow_device(&w->d_stage, &w->stage_rays, cast_stage_units((uint32_t)cap), kStageUnit);
+    if (rc != NRAYS_OK) return rc;
+    double* s_o = (double*)w->d_stage; double* s_d = s_o + 3 * cap; double* s_t = s_d + 3 * cap;
+    CastOut s; s.toi = s_t + cap; s.normal = s.toi + cap; s.uv = s.normal + 3 * cap;
+    s.node = (int32_t*)(s.uv + 2 * cap); s.prim = s.node + cap; s.flags = (uint32_t*)(s.prim + cap);
+    if (!out.normal) s.normal = nullptr;
+    if (!out.uv) s.uv = nullptr;
+    if (!out.prim) s.prim = nullptr;
+    if (!out.flags) s.flags = nullptr;
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        hipError_t e = hipMemcpyAsync(s_o, origins + 3 * (size_t)c0, (size_t)nc * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s_d, dirs + 3 * (size_t)c0, (size_t)nc * 24, hipMemcpyHostToDevice, stream);
+        if (e == hipSuccess && max_toi) e = hipMemcpyAsync(s_t, max_toi + c0, (size_t)nc * 8, hipMemcpyHostToDevice, stream);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("cast batch upload: ") + hipGetErrorString(e)); break; }
+        rc = cast_chunk(sc, w, reorder, nc, s_o, s_d, max_toi ? s_t : nullptr, s, stream);
+        if (rc != NRAYS_OK) break;
+        const CastOut h = cast_out_at(out, c0);
+        auto down = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess; };
+        e = down(h.toi, s.toi, (size_t)nc * 8);
+        if (e == hipSuccess) e = down(h.node, s.node, (size_t)nc * 4);
+        if (e == hipSuccess) e = down(h.normal, s.normal, (size_t)nc * 24);
+        if (e == hipSuccess) e = down(h.uv, s.uv, (size_t)nc * 16);
+        if (e == hipSuccess) e = down(h.prim, s.prim, (size_t)nc * 4);
+        if (e == hipSuccess) e = down(h.flags, s.flags, (size_t)nc * 4);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("cast batch read-back: ") + hipGetErrorString(e));
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -414,7 +509,7 @@ static int trace_rays_host_impl(NraysScene* sc, uint32_t n, const double* origin
     int rc = trace_workspace(sc, &w);
     if (rc != NRAYS_OK) return rc;
     // device copies of one chunk's arrays: origins, directions (3 f64), refr (f64), keys (u64), energy (f32), colours (3 f32) — 80 bytes a ray
-    rc = grow_device(&w->d_stage, &w->stage_rays, std::min<uint32_t>(n, kTraceChunk), 80);
+    rc = grow_device(&w->d_stage, &w->stage_rays, std::min<uint32_t>(n, kTraceChunk), kStageUnit);
     if (rc != NRAYS_OK) return rc;
     const size_t cap = w->stage_rays;
     double* s_o = (double*)w->d_stage; double* s_d = s_o + 3 * cap; double* s_r = s_d + 3 * cap;
@@ -493,6 +588,15 @@ int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origi
 int nrays_intersects_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
                                     uint32_t* out_lit, uint32_t flags, void* hip_stream) {
     return intersects_rays_device_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, flags, hip_stream);
+}
+
+int nrays_cast_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node,
+                           double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream) {
+    return cast_rays_device_impl(sc, n, origins, dirs, max_toi, CastOut{out_toi, out_node, out_normal, out_uv, out_prim, out_flags}, flags, (hipStream_t)hip_stream);
+}
+int nrays_cast_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node,
+                    double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags) {
+    return cast_rays_host_impl(sc, n, origins, dirs, max_toi, CastOut{out_toi, out_node, out_normal, out_uv, out_prim, out_flags}, flags);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

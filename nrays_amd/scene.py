@@ -11,6 +11,7 @@ The geometry classes stand in for the ncollide3d shapes the loader constructs
 (examples/loader3d.rs:601-695).  Nothing here computes pixels: `render` calls the HIP library
 through the C ABI (include/nrays_abi.h) and fails loudly if it is missing.
 """
+import collections
 import ctypes as C
 import math
 
@@ -363,6 +364,10 @@ class Scene:
             self._handle = h
         return self._handle
 
+    def cast_rays(self, origins, dirs, max_toi=None, unordered=False, want=("normal", "uv", "prim", "flags")):
+        """The closest hits of caller-supplied rays on this scene: closest_hits(self, ...)."""
+        return closest_hits(self, origins, dirs, max_toi, unordered, want)
+
     def _release(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)
@@ -590,6 +595,58 @@ def intersects_rays(scene, origins, dirs, max_toi, unordered=False):
     if host:
         return lit.cpu().numpy() != 0, filt.cpu().numpy()
     return lit != 0, filt
+
+
+CAST_OUTPUTS = ("normal", "uv", "prim", "flags")  # the optional outputs of closest_hits, in the order of nrays_cast_rays_device's arguments
+CastHits = collections.namedtuple("CastHits", ("toi", "node") + CAST_OUTPUTS)
+
+
+def closest_hits(scene, origins, dirs, max_toi=None, unordered=False, want=CAST_OUTPUTS):
+    """Scene::trace's closest-hit query (src/scene.rs:164-166, 262-283) with SceneNode::cast's record on n caller-supplied rays, through
+    nrays_cast_rays_device / nrays_cast_rays: WHICH node each ray meets first, where, with which normal and uv (picking, depth / normal / id
+    passes, the first hop of a baker).  Also `scene.cast_rays(origins, dirs, ...)` on Scene and FileScene.  (The module-level `cast_rays`
+    is the older wrapper of the test probe nrays_debug_cast_batch.)
+    `origins`, `dirs`: (n, 3), directions used as given; `max_toi` (n,) or None: the unbounded answer where its toi <= max_toi[i], a miss
+    otherwise (NaN: a miss).  `unordered=True`: as for trace_rays; the results are bit-identical.  `want`: which of "normal", "uv", "prim",
+    "flags" to compute into memory.
+    Returns CastHits(toi (n,) f64, node (n,) i32, normal (n, 3) f64, uv (n, 2) f64, prim (n,) i32, flags (n,)), None for what was not wanted.
+    A miss has node -1, toi +inf, zeros, prim -1, flags 0; flags bit 0 = hit, bit 1 = the record carries uvs; prim = the triangle's index in
+    its mesh, -1 for an analytic shape.
+    numpy arrays -> nrays_cast_rays (blocking), numpy arrays (flags uint32).  torch tensors on the scene's GPU (float64) ->
+    nrays_cast_rays_device on torch.cuda.current_stream(), tensors (flags int32)."""
+    n = _n_of(origins, dirs)
+    _check_vec("max_toi", max_toi, n)
+    want = tuple(want)
+    for name in want:
+        if name not in CAST_OUTPUTS:
+            raise ValueError("want: unknown output %r (one of %s)" % (name, ", ".join(CAST_OUTPUTS)))
+    flags = abi.RAYS_UNORDERED if unordered else 0
+    shapes = {"toi": (n,), "node": (n,), "normal": (n, 3), "uv": (n, 2), "prim": (n,), "flags": (n,)}
+    if _is_tensor(origins):
+        import torch
+        if origins.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, origins is on %s" % origins.device)
+        o, d, t = _torch_args((("origins", origins, (torch.float64,)), ("dirs", dirs, (torch.float64,)), ("max_toi", max_toi, (torch.float64,))), origins.device)
+        dtypes = {"toi": torch.float64, "node": torch.int32, "normal": torch.float64, "uv": torch.float64, "prim": torch.int32, "flags": torch.int32}
+        out = {k: torch.empty(shapes[k], dtype=dtypes[k], device=origins.device) if k in ("toi", "node") or k in want else None for k in CastHits._fields}
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(origins.device):
+            abi.check(lib.nrays_cast_rays_device(scene.device_handle(), n, ptr(o), ptr(d), ptr(t), *[ptr(out[k]) for k in CastHits._fields], flags,
+                                                 torch.cuda.current_stream().cuda_stream))
+        return CastHits(**out)
+    if any(_is_tensor(a) for a in (dirs, max_toi)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    o, d = _np_floats("origins", origins, np.float64), _np_floats("dirs", dirs, np.float64)
+    t = None if max_toi is None else _np_floats("max_toi", max_toi, np.float64)
+    dtypes = {"toi": np.float64, "node": np.int32, "normal": np.float64, "uv": np.float64, "prim": np.int32, "flags": np.uint32}
+    ctypes_of = {np.float64: C.c_double, np.int32: C.c_int32, np.uint32: C.c_uint32}
+    out = {k: np.empty(shapes[k], dtype=dtypes[k]) if k in ("toi", "node") or k in want else None for k in CastHits._fields}
+    ptr = lambda a, ct: None if a is None else a.ctypes.data_as(C.POINTER(ct))  # noqa: E731
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_cast_rays(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(t, C.c_double),
+                                  *[ptr(out[k], ctypes_of[dtypes[k]]) for k in CastHits._fields], flags))
+    return CastHits(**out)
 
 
 def ray_order(scene, origins, dirs):

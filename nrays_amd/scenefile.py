@@ -98,6 +98,11 @@ class FileScene:
             self._handle = h
         return self._handle
 
+    def cast_rays(self, origins, dirs, max_toi=None, unordered=False, want=("normal", "uv", "prim", "flags")):
+        """The closest hits of caller-supplied rays on this scene: scene.closest_hits(self, ...)."""
+        from .scene import closest_hits
+        return closest_hits(self, origins, dirs, max_toi, unordered, want)
+
     def close(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)

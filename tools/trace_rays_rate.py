@@ -17,13 +17,18 @@ CPU figures per batch and order (as given / in the order the reorder probe retur
 "one_octant_waves", the share of waves whose 64 rays share their direction signs.  --sweep times the shuffled camera rays of both scenes
 for n = 2^10 .. 2^22 hinted and unhinted with every hinted batch reordered (NRAYS_RAY_REORDER=2): the threshold of DESIGN §5b.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep]
+The AO rays are built on the device from the camera rays' closest hits (nrays_cast_rays_device through closest_hits()).  Each scene also gets
+a row "closest hits, camera rays": closest_hits() of the camera rays in order, shuffled, and shuffled under the hint, beside the wall time of
+the blocking test probe nrays_debug_cast_batch on the same rays (upload, kernel, 64-byte records back).  --cast times these rows only.
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast]
 """
 import argparse
 import ctypes as C
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -114,29 +119,61 @@ def _render(sc, p, reps):
 
 
 def _first_hits(sc, o, d):
-    """Closest hits of the camera rays (nrays_debug_cast_batch mode 0, blocking): AO rays from each hit, cosine-weighted about the normal,
-    and the index of the camera ray each came from."""
+    """AO rays from the closest hits of the camera rays (closest_hits on the device: toi, node and normal only), cosine-weighted about the
+    normal on the side the camera ray came from, and the index of the camera ray each came from.  Built with torch on the GPU; returned as
+    numpy arrays, which the batches and the coherence figures take."""
+    import torch
+    import nrays_amd as nr
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    r = nr.closest_hits(sc, to, td, want=("normal",))
+    hit = r.node >= 0
+    to, td = to[hit], td[hit]
+    pt = to + td * r.toi[hit][:, None]
+    nrm = r.normal[hit]
+    nrm = nrm / torch.linalg.norm(nrm, dim=1)[:, None]
+    nrm = torch.where(((nrm * td).sum(dim=1) > 0.0)[:, None], -nrm, nrm)  # the side the camera ray came from
+    gen = torch.Generator(device="cuda").manual_seed(0)
+    u1 = torch.rand(len(pt), dtype=torch.float64, device="cuda", generator=gen)
+    u2 = torch.rand(len(pt), dtype=torch.float64, device="cuda", generator=gen)
+    rad, phi = torch.sqrt(u1), 2.0 * np.pi * u2
+    local = torch.stack([rad * torch.cos(phi), rad * torch.sin(phi), torch.sqrt(torch.clamp(1.0 - u1, min=0.0))], dim=1)
+    ey, ex = torch.tensor([[0.0, 1.0, 0.0]], dtype=torch.float64, device="cuda"), torch.tensor([[1.0, 0.0, 0.0]], dtype=torch.float64, device="cuda")
+    a = torch.where(torch.abs(nrm[:, 0:1]) > 0.9, ey, ex)
+    t = torch.linalg.cross(a.expand_as(nrm), nrm)
+    t = t / torch.linalg.norm(t, dim=1)[:, None]
+    b = torch.linalg.cross(nrm, t)
+    dirs = local[:, 0:1] * t + local[:, 1:2] * b + local[:, 2:3] * nrm
+    dirs = dirs / torch.linalg.norm(dirs, dim=1)[:, None]
+    return (pt + nrm * 1e-3).cpu().numpy(), dirs.cpu().numpy(), torch.nonzero(hit)[:, 0].cpu().numpy()
+
+
+def _closest_hits_row(sc, o, d, perm, reps):
+    """closest hits, camera rays: closest_hits() on device tensors in order, shuffled and shuffled under the hint (every output, and toi + node
+    alone), beside the blocking probe nrays_debug_cast_batch on the same host arrays (wall clock: it uploads, runs and copies 64-byte records back)."""
+    import torch
+    import nrays_amd as nr
     from nrays_amd import abi
     n = len(o)
+    rate = lambda ms: round(n / (ms * 1e-3) / 1e6, 2)  # noqa: E731
+    row = {"rays": int(n)}
+    so, sd = np.ascontiguousarray(o[perm]), np.ascontiguousarray(d[perm])
+    for name, (ho, hd), kw in (("in_order", (o, d), {}), ("shuffled", (so, sd), {}), ("shuffled_hinted", (so, sd), dict(unordered=True))):
+        to, td = torch.from_numpy(np.ascontiguousarray(ho)).cuda(), torch.from_numpy(np.ascontiguousarray(hd)).cuda()
+        ms = _time(lambda: nr.closest_hits(sc, to, td, **kw), reps)
+        ms2 = _time(lambda: nr.closest_hits(sc, to, td, want=(), **kw), reps)
+        row[name] = {"ms": round(ms, 4), "mrays_per_s": rate(ms), "toi_node_only_ms": round(ms2, 4), "toi_node_only_mrays_per_s": rate(ms2)}
     res = np.zeros(n, dtype=CAST_DTYPE)
-    abi.check(abi.load_hip_lib().nrays_debug_cast_batch(sc.device_handle(), 0, n, o.ctypes.data_as(C.POINTER(C.c_double)), d.ctypes.data_as(C.POINTER(C.c_double)),
-                                                        None, res.ctypes.data_as(C.POINTER(abi.NraysCastResult))))
-    hit = (res["flags"] & 1) != 0
-    pt = o[hit] + d[hit] * res["toi"][hit][:, None]
-    nrm = res["normal"][hit]
-    nrm = nrm / np.linalg.norm(nrm, axis=1)[:, None]
-    nrm = np.where(((nrm * d[hit]).sum(axis=1) > 0.0)[:, None], -nrm, nrm)  # the side the camera ray came from
-    rng = np.random.default_rng(0)
-    u1, u2 = rng.uniform(size=len(pt)), rng.uniform(size=len(pt))
-    r, phi = np.sqrt(u1), 2.0 * np.pi * u2
-    local = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(np.maximum(0.0, 1.0 - u1))], axis=1)
-    a = np.where(np.abs(nrm[:, 0:1]) > 0.9, np.asarray([[0.0, 1.0, 0.0]]), np.asarray([[1.0, 0.0, 0.0]]))
-    t = np.cross(a, nrm)
-    t /= np.linalg.norm(t, axis=1)[:, None]
-    b = np.cross(nrm, t)
-    dirs = local[:, 0:1] * t + local[:, 1:2] * b + local[:, 2:3] * nrm
-    dirs /= np.linalg.norm(dirs, axis=1)[:, None]
-    return pt + nrm * 1e-3, dirs, np.nonzero(hit)[0]
+    dp = C.POINTER(C.c_double)
+    lib, oo, dd = abi.load_hip_lib(), np.ascontiguousarray(o), np.ascontiguousarray(d)
+    probe = lambda: abi.check(lib.nrays_debug_cast_batch(sc.device_handle(), 0, n, oo.ctypes.data_as(dp), dd.ctypes.data_as(dp), None,  # noqa: E731
+                                                         res.ctypes.data_as(C.POINTER(abi.NraysCastResult))))
+    probe()
+    t0 = time.perf_counter()
+    for _ in range(max(1, reps // 4)):
+        probe()
+    ms = (time.perf_counter() - t0) * 1e3 / max(1, reps // 4)
+    row["blocking_probe_in_order"] = {"ms": round(ms, 4), "mrays_per_s": rate(ms)}
+    return row
 
 
 def main():
@@ -146,6 +183,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="320x180 instead of 1920x1080 (a rehearsal of the tool, not a measurement)")
     ap.add_argument("--coherence", action="store_true", help="add the CPU coherence figures of every batch, as given and reordered")
     ap.add_argument("--sweep", action="store_true", help="time the shuffled camera rays for n = 2^10 .. 2^22 with every hinted batch reordered, nothing else")
+    ap.add_argument("--cast", action="store_true", help="time the closest-hit rows of both scenes, nothing else")
     a = ap.parse_args()
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
@@ -166,9 +204,10 @@ def main():
     perm = np.random.default_rng(1).permutation(len(o))
     pix = np.arange(len(o)) if a.coherence else None
     coh = lambda p: dict(pix=p, width=w) if a.coherence else {}  # noqa: E731
+    res["workloads"]["e_balls_closest_hits_camera_rays"] = None if a.sweep else _closest_hits_row(sc, o, d, perm, a.reps)
     if a.sweep:
         res["sweep"] = {"balls_shuffled": _sweep(sc, o[perm], d[perm], k[perm], a.reps)}
-    else:
+    elif not a.cast:
         res["workloads"]["a_balls_image_order"] = _batch(sc, o, d, a.reps, k, **coh(pix))
         res["workloads"]["b_balls_shuffled"] = _batch(sc, o[perm], d[perm], a.reps, k[perm], **coh(perm))
         res["workloads"]["balls_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
@@ -177,9 +216,10 @@ def main():
     sc, cam = standins.sponza_scene()
     proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
     o, d, k = nr.camera_rays((w, h), cam["eye"], proj)
+    res["workloads"]["e_sponza_closest_hits_camera_rays"] = None if a.sweep else _closest_hits_row(sc, o, d, perm, a.reps)
     if a.sweep:
         res["sweep"]["sponza_shuffled"] = _sweep(sc, o[perm], d[perm], k[perm], a.reps)
-    else:
+    elif not a.cast:
         ao_o, ao_d, ao_pix = _first_hits(sc, o, d)
         ao_perm = np.random.default_rng(2).permutation(len(ao_o))
         res["workloads"]["c_sponza_camera_plus_ao"] = dict(_batch(sc, np.concatenate([o, ao_o]), np.concatenate([d, ao_d]), a.reps, **coh(np.concatenate([np.arange(len(o)), ao_pix]))),
@@ -189,6 +229,7 @@ def main():
         res["workloads"]["d_sponza_camera_shuffled"] = _batch(sc, o[perm], d[perm], a.reps, k[perm], **coh(perm))
         res["workloads"]["d_sponza_ao_shuffled"] = _batch(sc, ao_o[ao_perm], ao_d[ao_perm], a.reps, **coh(ao_pix[ao_perm]))
         res["workloads"]["sponza_render_device"] = _render(sc, nr.make_params((w, h), 1, 0.0, cam["eye"], proj), a.reps)
+    res["workloads"] = {k_: v for k_, v in res["workloads"].items() if v is not None}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(res, f, indent=1)
