@@ -32,7 +32,8 @@ extern "C" {
 /* Bumped whenever the exported surface grows or a struct changes: 3 = + nrays_debug_blas_build / NraysBlasDump, nrays_multi_get_timings / NraysMultiTimings (round 4); 4 = NraysStats::rays_shadow_elided (round 5); 5 = NraysStats::node_fetches, nrays_render_device_counted, NraysTileCosts::shader_clock_hz / kernel_ms (round 6); 6 = nrays_trace_rays_device / nrays_trace_rays /
  * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation.
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
- * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
+ * nrays_shade_points.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -317,6 +318,39 @@ int nrays_cast_rays_device(NraysScene* scene, uint32_t n, const double* origins,
 int nrays_cast_rays(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, const double* max_toi,
                     double* out_toi, int32_t* out_node, double* out_normal, double* out_uv, int32_t* out_prim,
                     uint32_t* out_flags, uint32_t flags);
+
+/* Material::compute (src/material.rs:8-16, src/phong_material.rs:72-151) on n caller-supplied surface points: the direct lighting of point i with
+ * the material of scene node nodes[i] — the ambient term with the texture and opacity-map samples, per light Light::sample's jittered
+ * positions, one transparent-shadow query per sample, the Phong diffuse and specular terms folded light after light.  It is the value
+ * Scene::trace gets from `sn.material.compute(ray, &pt, &inter.normal, &uvs, self)`, on its own: no closest-hit traversal, no reflection, no
+ * refraction (light-map and vertex bakers; the second step of nrays_cast_rays_device -> own shading; deferred shading of a camera's hits).
+ *   out_rgba       n x 4 floats, the reference's Point4<f32>: the lit colour and, in w, the MATERIAL's alpha (the opacity-map sample, or 1) —
+ *                  as compute returns it, before the node's alpha is multiplied in.
+ *   points         n x 3 doubles, world space, used as given.
+ *   normals        n x 3 doubles, used as given; unit length is expected, as the casts return it.
+ *   view_dirs      n x 3 doubles, required: `ray.ray.dir`, the direction the viewer looks along, TOWARDS the surface.  It feeds the specular term;
+ *                  nothing else of the ray is read.
+ *   uvs            n x 2 doubles, or NULL = None for every point.
+ *   nodes          n scene-node indices (the values out_node of nrays_cast_rays_device holds).  The node only selects the material; its alpha,
+ *                  refl_mix and refr_coeff are not applied (that is Scene::trace's business).
+ *   hit_flags      n words, or NULL: the bits of out_flags / NraysCastResult::flags.  Bit 0 clear = the point is skipped; bit 1 = the point carries
+ *                  a uv (it has one only if `uvs` is non-NULL too).  NULL = every point is shaded, and carries a uv exactly when `uvs` is non-NULL.
+ *   keys           n RNG path keys, or NULL = the key of point i is i (also across chunks).  Area lights hash the key exactly as the shading of a
+ *                  traced ray with the same key does (nrays_trace_rays_device).
+ *   flags          must be 0 (any bit -> NRAYS_ERR_BAD_ARG).  No reorder is offered: a baker's texels already come in surface order.
+ * A point is SKIPPED when bit 0 of hit_flags[i] is clear, when nodes[i] < 0 or when nodes[i] >= the scene's node count: it writes (0, 0, 0, 0) and
+ * reads no scene record, so the outputs of nrays_cast_rays_device can be passed on unfiltered, misses included.  Points, normals and view
+ * directions are expected to be finite.
+ * NULL scene / points / normals / view_dirs / nodes / out_rgba -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK without work.  Otherwise the contract of
+ * nrays_cast_rays_device: every pointer DEVICE memory on the scene's device, chunks of at most 2^22 points, enqueued on `hip_stream` without
+ * read-back or synchronisation, ordered behind the handle's previous work; what the handle reports about its renders and its per-camera
+ * scheduling state stay untouched. */
+int nrays_shade_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const double* view_dirs,
+                              const double* uvs, const int32_t* nodes, const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba,
+                              uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_shade_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs,
+                       const int32_t* nodes, const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

@@ -339,6 +339,15 @@ pub struct CastHit {
     pub triangle: Option<usize>, // index of the triangle in its TriMesh; None for an analytic shape
 }
 
+/// One surface point of `GpuScene::shade_points`: the arguments of `Material::compute` (src/material.rs:8-16) besides the scene.
+pub struct SurfacePoint {
+    pub node: usize,              // index into scene.nodes(): selects the material
+    pub point: Point3<f64>,       // world space
+    pub normal: Vector3<f64>,     // unit length, as the casts return it
+    pub view_dir: Vector3<f64>,   // ray.ray.dir: the direction the viewer looks along, towards the surface
+    pub uvs: Option<Point2<f64>>,
+}
+
 /// A scene resident on ONE GPU (the calling thread's current HIP device).
 pub struct GpuScene {
     raw: *mut NraysScene,
@@ -447,6 +456,38 @@ impl GpuScene {
     pub unsafe fn cast_rays_device(&self, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_toi: *mut f64, out_node: *mut i32, out_normal: *mut f64,
                                    out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_cast_rays_device(self.raw, n, origins, dirs, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// `scene.nodes()[p.node].material.compute(ray, &p.point, &p.normal, &p.uvs, scene)` (src/material.rs:8-16, src/phong_material.rs:72-151) for every
+    /// point of the batch, in one call (nrays_shade_points, blocking): the lit colour and the material's alpha as the reference's `Point4<f32>`, without
+    /// a closest-hit traversal and without reflection or refraction.  Of the ray only `dir` (p.view_dir) and the RNG path key matter: `keys[i]` is point
+    /// i's key for area-light sampling (None: key i).  A node index outside `scene.nodes()` gives (0, 0, 0, 0).
+    pub fn shade_points(&self, points: &[SurfacePoint], keys: Option<&[u64]>) -> Result<Vec<Point4<f32>>, String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        let n = points.len();
+        let (mut p, mut nm, mut v, mut uv) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n), Vec::with_capacity(3 * n), Vec::with_capacity(2 * n));
+        let (mut node, mut hf) = (Vec::with_capacity(n), Vec::with_capacity(n));
+        for s in points {
+            p.extend_from_slice(&[s.point.x, s.point.y, s.point.z]);
+            nm.extend_from_slice(&[s.normal.x, s.normal.y, s.normal.z]);
+            v.extend_from_slice(&[s.view_dir.x, s.view_dir.y, s.view_dir.z]);
+            match s.uvs { Some(t) => { uv.extend_from_slice(&[t.x, t.y]); hf.push(3u32); } None => { uv.extend_from_slice(&[0.0, 0.0]); hf.push(1u32); } }
+            node.push(if s.node <= i32::max_value() as usize { s.node as i32 } else { -1 });
+        }
+        let mut out: Vec<Point4<f32>> = vec![Point4::new(0.0f32, 0.0, 0.0, 0.0); n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_shade_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), v.as_ptr(), uv.as_ptr(), node.as_ptr(), hf.as_ptr(), kp, out.as_mut_ptr() as *mut f32, 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(out)
+    }
+
+    /// `shade_points` for n points in DEVICE memory (nrays_shade_points_device), enqueued on `hip_stream` without synchronisation: points / normals /
+    /// view_dirs n x 3 f64, uvs n x 2 f64 or null, nodes n i32 (what cast_rays_device wrote to out_node), hit_flags n u32 or null (its out_flags: bit 0
+    /// clear = skipped, bit 1 = the point carries a uv), keys n u64 or null, out_rgba n x 4 f32.  Skipped points write (0, 0, 0, 0).
+    pub unsafe fn shade_points_device(&self, n: u32, points: *const f64, normals: *const f64, view_dirs: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32,
+                                      keys: *const u64, out_rgba: *mut f32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_shade_points_device(self.raw, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 }

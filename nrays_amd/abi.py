@@ -135,6 +135,10 @@ HIP_SYMBOLS = {
                                          C.c_void_p, C.c_uint32, C.c_void_p]),
     "nrays_cast_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                   C.POINTER(C.c_int32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_shade_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_uint32, C.c_void_p]),
+    "nrays_shade_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_uint32]),
     "nrays_debug_ray_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "nrays_scene_create": (C.c_int, [C.POINTER(NraysSceneDesc), C.POINTER(C.c_void_p)]),
@@ -169,7 +173,7 @@ HIP_SYMBOLS = {
 
 # Added after ABI version 7 without a bump: an older version-7 library (NRAYS_HIP_LIB: A/B runs against a parent build) may lack them.
 POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_intersects_rays_device_ex", "nrays_debug_ray_order",
-                   "nrays_cast_rays_device", "nrays_cast_rays")
+                   "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 RAY_FRAME_DOUBLES = 20      # NRAYS_RAY_FRAME_DOUBLES
 

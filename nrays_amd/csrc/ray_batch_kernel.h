@@ -1,7 +1,8 @@
 // ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*): k_trace_rays,
 // k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
-// each, so that the two forms cannot drift apart.  Device code only.
+// each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
+// Device code only.
 #pragma once
 #include "primary_kernel.h"
 
@@ -149,6 +150,53 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_rays_orde
                                                                                      int32_t* __restrict__ out_prim, uint32_t* __restrict__ out_flags, uint32_t* spill) {
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     cast_rays_body<FEAT, true>(lds_stack, S, n, order, ro, rd, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, spill);
+}
+
+// Material::compute (material.rs:8-16, phong_material.rs:72-151) on caller-supplied surface points (nrays_shade_points_device): the direct lighting
+// of point i with the material of node nodes[i] — ambient term with the texture and opacity-map samples, Light::sample's jittered positions, one
+// transparent-shadow query per sample, Phong folded light after light — as out[4i..4i+3], the reference's Point4<f32>: rgb and the MATERIAL's alpha
+// (the node's alpha, refl_mix and refr_coeff are Scene::trace's business and are not applied).  The lane fills of an Isect and a RayState only what
+// material_compute reads (normal, uv; view direction, key) and calls it as shade_hit does for a hit that has nothing precomputed (pre = false,
+// alpha_in = -1).  FEAT must hold kFeatMultiSample: every shadow ray is then traced inside the light loop (the single-sample "pre" path lives in
+// shade_hit).  light_is_dark applies as in a render; shade_hit's transparent-hit elision does not — the caller asked for this value itself.
+// A point is SKIPPED — (0, 0, 0, 0), no scene record read — when bit 0 of hit_flags[i] is clear or nodes[i] is outside [0, num_nodes): the outputs
+// of k_cast_rays can be passed on unfiltered.  hit_flags bit 1: the point carries a uv (only if `uvs` is there at all); NULL hit_flags: every point
+// is shaded and carries a uv exactly when `uvs` is non-NULL.  NULL keys: key_base + i.  Points, normals and view directions are used as given and
+// are expected to be finite.
+template <bool STATS, int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_shade_points(DScene S, uint32_t n, uint32_t num_nodes, const double* __restrict__ points,
+                                                                                const double* __restrict__ normals, const double* __restrict__ view_dirs,
+                                                                                const double* __restrict__ uvs, const int32_t* __restrict__ nodes,
+                                                                                const uint32_t* __restrict__ hit_flags, const unsigned long long* __restrict__ keys,
+                                                                                unsigned long long key_base, float* __restrict__ out, DeviceCounters* ctr, uint32_t* spill) {
+    static_assert((FEAT & kFeatMultiSample) != 0, "k_shade_points traces its shadow rays inside the light loop");
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const size_t i3 = 3 * (size_t)i;
+        const int32_t node = nodes[i];
+        const uint32_t hf = hit_flags ? hit_flags[i] : 3u;
+        f4 c; c.x = c.y = c.z = c.w = 0.0f;
+        if ((hf & 1u) && node >= 0 && (uint32_t)node < num_nodes) {
+            Isect is;
+            is.toi = 0.0; is.hit = true;
+            is.n = D3(normals[i3], normals[i3 + 1], normals[i3 + 2]);
+            is.has_uv = uvs != nullptr && (hf & 2u) != 0u;
+            is.u = is.has_uv ? uvs[2 * (size_t)i] : 0.0; is.v = is.has_uv ? uvs[2 * (size_t)i + 1] : 0.0;
+            RayState ray;
+            ray.o = D3(0, 0, 0); ray.d = D3(view_dirs[i3], view_dirs[i3 + 1], view_dirs[i3 + 2]);
+            ray.refr = 1.0; ray.energy = 1.0f; ray.weight = 1.0f; ray.pixel = i;
+            ray.key = keys ? keys[i] : key_base + i;
+            d3 pt = D3(points[i3], points[i3 + 1], points[i3 + 2]);
+            c = material_compute<STATS, FEAT>(S, st, S.shade[node], ray, pt, is, cnt, false, false, F3(1.0f, 1.0f, 1.0f), 0u, -1.0f);
+        }
+        float* o = out + 4 * (size_t)i;
+        o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
+    }
+    flush_counters(ctr, cnt, STATS);
 }
 
 } // namespace nrays

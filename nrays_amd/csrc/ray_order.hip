@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -459,6 +459,92 @@ static int cast_rays_host_impl(NraysScene* sc, uint32_t n, const double* origins
     return rc;
 }
 
+// ---- nrays_shade_points*: Material::compute on caller-supplied surface points (material.rs:8-16, phong_material.rs:72-151) -----------------------
+struct ShadeIn { const double* points; const double* normals; const double* view_dirs; const double* uvs; const int32_t* nodes; const uint32_t* hit_flags; const uint64_t* keys; };
+static ShadeIn shade_in_at(const ShadeIn& in, size_t c0) {
+    return ShadeIn{in.points + 3 * c0, in.normals + 3 * c0, in.view_dirs + 3 * c0, in.uvs ? in.uvs + 2 * c0 : nullptr, in.nodes + c0,
+                   in.hit_flags ? in.hit_flags + c0 : nullptr, in.keys ? in.keys + c0 : nullptr};
+}
+static int check_shade_args(const NraysScene* sc, const ShadeIn& in, const float* out, uint32_t flags) {
+    if (!sc || !in.points || !in.normals || !in.view_dirs || !in.nodes || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_shade_points: flags must be 0");
+    return NRAYS_OK;
+}
+// One chunk (nc <= kTraceChunk) of nrays_shade_points_device; `in` and `out` are the chunk's, key_base the index of its first point in the batch.
+// kFeatAll is right for every scene (it holds kFeatMultiSample: the shadow rays are traced inside the light loop); a scene with a non-finite
+// light / colour / texel gets the kernel that skips nothing, as its renders, with the batch's own counter block.
+static int shade_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const ShadeIn& in, unsigned long long key_base, float* out, hipStream_t stream) {
+    const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const uint32_t num_nodes = (uint32_t)sc->facts.host.shade.size();
+    const unsigned long long* keys = (const unsigned long long*)in.keys;
+    if (sc->facts.d.no_elide) hipLaunchKernelGGL((k_shade_points<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, num_nodes, in.points, in.normals, in.view_dirs, in.uvs, in.nodes, in.hit_flags, keys, key_base, out, w->d_counters, w->d_spill);
+    else hipLaunchKernelGGL((k_shade_points<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, num_nodes, in.points, in.normals, in.view_dirs, in.uvs, in.nodes, in.hit_flags, keys, key_base, out, w->d_counters, w->d_spill);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_shade_points: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+
+static int shade_points_device_impl(NraysScene* sc, uint32_t n, const ShadeIn& in, float* out, uint32_t flags, hipStream_t stream) {
+    if (check_shade_args(sc, in, out, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) { // (chunks keep the kernel's 32-bit point indices far from overflow)
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        rc = shade_chunk(sc, w, nc, shade_in_at(in, c0), (unsigned long long)c0, out + 4 * (size_t)c0, stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form, through the workspace's staging buffer as cast_rays_host_impl.  A staged point takes kShadeStageBytes: point, normal, view direction (3 f64),
+// uv (2 f64), key (u64), colour (4 f32), node, hit flags (32 bits) — the 8-byte fields first.
+constexpr size_t kShadeStageBytes = 120;
+static size_t shade_stage_units(uint32_t points) { return ((size_t)points * kShadeStageBytes + kStageUnit - 1) / kStageUnit; }
+static int shade_points_host_impl(NraysScene* sc, uint32_t n, const ShadeIn& in, float* out, uint32_t flags) {
+    if (check_shade_args(sc, in, out, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    const size_t cap = std::min<uint32_t>(n, kTraceChunk);
+    rc = grow_device(&w->d_stage, &w->stage_rays, shade_stage_units((uint32_t)cap), kStageUnit);
+    if (rc != NRAYS_OK) return rc;
+    double* s_p = (double*)w->d_stage; double* s_n = s_p + 3 * cap; double* s_v = s_n + 3 * cap; double* s_uv = s_v + 3 * cap;
+    uint64_t* s_k = (uint64_t*)(s_uv + 2 * cap); float* s_out = (float*)(s_k + cap); int32_t* s_node = (int32_t*)(s_out + 4 * cap); uint32_t* s_hf = (uint32_t*)(s_node + cap);
+    const ShadeIn s{s_p, s_n, s_v, in.uvs ? s_uv : nullptr, s_node, in.hit_flags ? s_hf : nullptr, in.keys ? s_k : nullptr};
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, kTraceChunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, kTraceChunk);
+        const ShadeIn h = shade_in_at(in, c0);
+        auto up = [&](void* dst, const void* src, size_t bytes) { return src ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+        hipError_t e = up(s_p, h.points, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_n, h.normals, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_v, h.view_dirs, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_uv, h.uvs, (size_t)nc * 16);
+        if (e == hipSuccess) e = up(s_node, h.nodes, (size_t)nc * 4);
+        if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
+        if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("shade batch upload: ") + hipGetErrorString(e)); break; }
+        rc = shade_chunk(sc, w, nc, s, (unsigned long long)c0, s_out, stream);
+        if (rc != NRAYS_OK) break;
+        e = hipMemcpyAsync(out + 4 * (size_t)c0, s_out, (size_t)nc * 16, hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("shade batch read-back: ") + hipGetErrorString(e));
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -597,6 +683,15 @@ int nrays_cast_rays_device(NraysScene* sc, uint32_t n, const double* origins, co
 int nrays_cast_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node,
                     double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags) {
     return cast_rays_host_impl(sc, n, origins, dirs, max_toi, CastOut{out_toi, out_node, out_normal, out_uv, out_prim, out_flags}, flags);
+}
+
+int nrays_shade_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
+                              const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags, void* hip_stream) {
+    return shade_points_device_impl(sc, n, ShadeIn{points, normals, view_dirs, uvs, nodes, hit_flags, keys}, out_rgba, flags, (hipStream_t)hip_stream);
+}
+int nrays_shade_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
+                       const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags) {
+    return shade_points_host_impl(sc, n, ShadeIn{points, normals, view_dirs, uvs, nodes, hit_flags, keys}, out_rgba, flags);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

@@ -368,6 +368,10 @@ class Scene:
         """The closest hits of caller-supplied rays on this scene: closest_hits(self, ...)."""
         return closest_hits(self, origins, dirs, max_toi, unordered, want)
 
+    def shade_points(self, points, normals, view_dirs, nodes, uvs=None, hit_flags=None, keys=None):
+        """The direct lighting of caller-supplied surface points of this scene: shade_points(self, ...)."""
+        return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
+
     def _release(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)
@@ -462,15 +466,15 @@ def _is_tensor(x):
     return type(x).__module__.split(".")[0] == "torch"
 
 
-def _n_of(origins, dirs):
+def _n_of(origins, dirs, names=("origins", "dirs")):
     """Number of rays of an (n, 3) origins / directions pair (numpy arrays or torch tensors), checked before any device work."""
-    for name, a in (("origins", origins), ("dirs", dirs)):
+    for name, a in zip(names, (origins, dirs)):
         if a is None:
             raise ValueError("%s is required" % name)
         if len(a.shape) != 2 or a.shape[1] != 3:
             raise ValueError("%s must have shape (n, 3), got %s" % (name, tuple(a.shape)))
     if origins.shape[0] != dirs.shape[0]:
-        raise ValueError("origins and dirs hold %d and %d rays" % (origins.shape[0], dirs.shape[0]))
+        raise ValueError("%s and %s hold %d and %d rays" % (names[0], names[1], origins.shape[0], dirs.shape[0]))
     n = int(origins.shape[0])
     if n >= 1 << 32:
         raise ValueError("at most 2^32 - 1 rays per call")
@@ -647,6 +651,97 @@ def closest_hits(scene, origins, dirs, max_toi=None, unordered=False, want=CAST_
     abi.check(lib.nrays_cast_rays(scene.device_handle(), n, ptr(o, C.c_double), ptr(d, C.c_double), ptr(t, C.c_double),
                                   *[ptr(out[k], ctypes_of[dtypes[k]]) for k in CastHits._fields], flags))
     return CastHits(**out)
+
+
+def _check_rows(name, a, n, cols):
+    if len(a.shape) != 2 or a.shape[0] != n or a.shape[1] != cols:
+        raise ValueError("%s must have shape (%d, %d), got %s" % (name, n, cols, tuple(a.shape)))
+
+
+def _np_ints(name, a, dtype):
+    """An integer numpy array as `dtype`: int32 keeps out-of-range node indices out of range (clipped), uint32 keeps the low 32 bits (flag words)."""
+    a = np.asarray(a)
+    if not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s must be integers, got %s" % (name, a.dtype))
+    if dtype == np.int32 and a.dtype != np.int32:
+        a = np.clip(a, -(1 << 31), (1 << 31) - 1)
+    return np.ascontiguousarray(a.astype(dtype, copy=False))
+
+
+def shade_points(scene, points, normals, view_dirs, nodes, uvs=None, hit_flags=None, keys=None):
+    """Material::compute (src/material.rs:8-16, src/phong_material.rs:72-151) on n caller-supplied surface points, through
+    nrays_shade_points_device / nrays_shade_points: the direct lighting of each point with the material of scene node nodes[i] — ambient term,
+    texture and opacity map, the lights' samples with one transparent-shadow query each, Phong — without a closest-hit traversal and without
+    reflection or refraction.  Also `scene.shade_points(...)` on Scene and FileScene; shade_hits() feeds it from closest_hits().
+    `points`, `normals`, `view_dirs`: (n, 3), used as given (unit normals; view_dirs = the direction the viewer looks along, towards the surface:
+    it feeds the specular term).  `nodes` (n,) integers: the node only selects the material; its alpha / refl_mix / refr_coeff are not applied.
+    `uvs` (n, 2) or None (no point has a uv).  `hit_flags` (n,) integers or None: the flag words of closest_hits — bit 0 clear: the point is
+    skipped, bit 1: it carries a uv; None: every point is shaded and has a uv exactly when `uvs` is given.  `keys` (n,) RNG path keys for
+    area-light sampling (default: point i has key i), hashed as for a traced ray with the same key.
+    Returns (n, 4) float32: the lit colour and the material's alpha (the opacity-map sample, or 1).  A skipped point — flag bit 0 clear, node
+    < 0 or >= the scene's node count — is (0, 0, 0, 0), so the result of closest_hits can be passed on unfiltered.
+    numpy arrays -> nrays_shade_points (blocking), numpy array.  torch tensors on the scene's GPU (float64; nodes int32; hit_flags int32 /
+    uint32; keys int64 / uint64) -> nrays_shade_points_device on torch.cuda.current_stream(), tensor."""
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("view_dirs", view_dirs), ("nodes", nodes)):
+        if a is None:
+            raise ValueError("%s is required" % name)
+    _check_rows("view_dirs", view_dirs, n, 3)
+    if uvs is not None:
+        _check_rows("uvs", uvs, n, 2)
+    for name, a in (("nodes", nodes), ("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    if _is_tensor(points):
+        import torch
+        if points.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, points is on %s" % points.device)
+        f64 = (torch.float64,)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        flags_dt = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        p, nm, v, uv, nd, hf, k = _torch_args((("points", points, f64), ("normals", normals, f64), ("view_dirs", view_dirs, f64), ("uvs", uvs, f64),
+                                               ("nodes", nodes, (torch.int32,)), ("hit_flags", hit_flags, flags_dt), ("keys", keys, keys_dt)), points.device)
+        out = torch.empty((n, 4), dtype=torch.float32, device=points.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(points.device):
+            abi.check(lib.nrays_shade_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(v), ptr(uv), ptr(nd), ptr(hf), ptr(k), ptr(out), 0,
+                                                    torch.cuda.current_stream().cuda_stream))
+        return out
+    if any(_is_tensor(a) for a in (normals, view_dirs, nodes, uvs, hit_flags, keys)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    p, nm, v = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64), _np_floats("view_dirs", view_dirs, np.float64)
+    uv = None if uvs is None else _np_floats("uvs", uvs, np.float64)
+    nd = _np_ints("nodes", nodes, np.int32)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    out = np.empty((n, 4), dtype=np.float32)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_shade_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(v, C.c_double), ptr(uv, C.c_double),
+                                     ptr(nd, C.c_int32), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), ptr(out, C.c_float), 0))
+    return out
+
+
+def shade_hits(scene, origins, dirs, hits, keys=None):
+    """The direct lighting of the closest hits of caller-supplied rays: shade_points() at the hits of `hits = closest_hits(scene, origins, dirs)`
+    (a CastHits with normal, uv and flags), viewed along the rays.  The points are origins + dirs * toi — two separate element-wise operations,
+    the unfused `ray.o + ray.d * toi` of Scene::trace, with toi 0 at the misses — so that on a node that neither reflects nor refracts the colour
+    is trace_rays()'s, bit for bit.  Misses come back as (0, 0, 0, 0).  `keys` as for trace_rays.  (n, 4) float32, numpy or torch as the inputs."""
+    n = _n_of(origins, dirs)
+    for name in ("normal", "uv", "flags"):
+        if getattr(hits, name) is None:
+            raise ValueError("shade_hits: hits.%s is None (closest_hits must be asked for normal, uv and flags)" % name)
+    _check_vec("hits.toi", hits.toi, n)
+    if _is_tensor(origins) != _is_tensor(hits.toi):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    if _is_tensor(origins):
+        import torch
+        toi = torch.where((hits.flags & 1) != 0, hits.toi, torch.zeros_like(hits.toi))
+    else:
+        toi = np.where((np.asarray(hits.flags) & 1) != 0, hits.toi, 0.0)
+    step = dirs * toi[:, None]
+    points = origins + step
+    return shade_points(scene, points, hits.normal, dirs, hits.node, uvs=hits.uv, hit_flags=hits.flags, keys=keys)
 
 
 def ray_order(scene, origins, dirs):

@@ -103,6 +103,11 @@ class FileScene:
         from .scene import closest_hits
         return closest_hits(self, origins, dirs, max_toi, unordered, want)
 
+    def shade_points(self, points, normals, view_dirs, nodes, uvs=None, hit_flags=None, keys=None):
+        """The direct lighting of caller-supplied surface points of this scene: scene.shade_points(self, ...)."""
+        from .scene import shade_points
+        return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
+
     def close(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)

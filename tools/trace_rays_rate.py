@@ -21,7 +21,13 @@ The AO rays are built on the device from the camera rays' closest hits (nrays_ca
 a row "closest hits, camera rays": closest_hits() of the camera rays in order, shuffled, and shuffled under the hint, beside the wall time of
 the blocking test probe nrays_debug_cast_batch on the same rays (upload, kernel, 64-byte records back).  --cast times these rows only.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast]
+--shade times, and nothing else: on the sponza stand-in and on its 8-light variant, closest_hits() of the camera rays runs once, then shade_hits()
+at those hits (nrays_shade_points_device alone: the direct lighting without the closest-hit traversal) is timed beside trace_rays() of the same rays
+and closest_hits() itself — in alternating rounds, each of --reps launches between events, so that the spread of a figure is known; "ms" is the
+median round.  A library without the entry point (an older one under NRAYS_HIP_LIB) gets the trace_rays and closest_hits figures only, and
+--beside FILE copies the workloads of such an earlier run into this run's JSON under "beside".
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]]
 """
 import argparse
 import ctypes as C
@@ -176,6 +182,27 @@ def _closest_hits_row(sc, o, d, perm, reps):
     return row
 
 
+def _shade_row(sc, o, d, k, reps, rounds=5):
+    """shade_hits() at the closest hits of the rays, beside trace_rays() of the same rays and closest_hits() itself: device tensors, alternating rounds."""
+    import torch
+    import nrays_amd as nr
+    from nrays_amd import abi
+    to, td = torch.from_numpy(np.ascontiguousarray(o)).cuda(), torch.from_numpy(np.ascontiguousarray(d)).cuda()
+    tk = torch.from_numpy(k.astype(np.int64)).cuda()
+    hits = nr.closest_hits(sc, to, td)
+    fns = {"trace_rays": lambda: nr.trace_rays(sc, to, td, keys=tk), "closest_hits": lambda: nr.closest_hits(sc, to, td)}
+    if hasattr(abi.load_hip_lib(), "nrays_shade_points_device"):
+        fns["shade_hits"] = lambda: nr.shade_hits(sc, to, td, hits, keys=tk)
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps))
+    row = {"rays": int(len(o)), "hits": int((hits.node >= 0).sum().item()), "rounds": rounds}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    return row
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trace_rays_rate.json"))
@@ -184,6 +211,8 @@ def main():
     ap.add_argument("--coherence", action="store_true", help="add the CPU coherence figures of every batch, as given and reordered")
     ap.add_argument("--sweep", action="store_true", help="time the shuffled camera rays for n = 2^10 .. 2^22 with every hinted batch reordered, nothing else")
     ap.add_argument("--cast", action="store_true", help="time the closest-hit rows of both scenes, nothing else")
+    ap.add_argument("--shade", action="store_true", help="time shade_hits beside trace_rays and closest_hits on the sponza stand-in with 1 and 8 lights, nothing else")
+    ap.add_argument("--beside", default=None, help="with --shade: the JSON of an earlier run (another library), copied into this one under 'beside'")
     a = ap.parse_args()
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
@@ -197,6 +226,23 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.shade:
+        for name, lights in (("f_sponza_shade_hits_camera_rays", 1), ("f_sponza_8_lights_shade_hits_camera_rays", 8)):
+            sc, cam = standins.sponza_scene(n_lights=lights)
+            proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
+            o, d, k = nr.camera_rays((w, h), cam["eye"], proj)
+            res["workloads"][name] = _shade_row(sc, o, d, k, a.reps)
+            del sc
+        if a.beside:
+            with open(a.beside) as f:
+                other = json.load(f)
+            res["beside"] = {"library": other["library"], "workloads": other["workloads"]}
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
 
     sc, cam = su.balls_scene()
     proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
