@@ -33,7 +33,8 @@ extern "C" {
  * nrays_intersects_rays_device (caller-supplied rays); 7 = nrays_debug_last_permutation.
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
- * nrays_shade_points.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
+ * is new with them and changes no other).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -351,6 +352,55 @@ int nrays_shade_points_device(NraysScene* scene, uint32_t n, const double* point
 /* Same, every pointer HOST memory.  Blocking. */
 int nrays_shade_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs,
                        const int32_t* nodes, const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags);
+
+/* Ambient occlusion at n caller-supplied surface points (a baker's texel centres, the hits of nrays_cast_rays_device): the library builds
+ * num_dirs hemisphere rays per point ON THE DEVICE, runs Scene::intersects_ray (the transparent-shadow query of nrays_intersects_rays_device)
+ * on each and writes ONE folded value per point — no ray, max_toi or per-ray result array exists anywhere.
+ * The rays are defined exactly (f64 + - * /, copysign and integer arithmetic, every product evaluated left to right as written, nothing fused),
+ * so that a caller can restate them bit for bit (Python: nrays_amd.occlusion_rays; the library's own: nrays_debug_occlusion_rays).  For point p
+ * with normal n (used as given; unit length is expected, as the casts return it) and RNG key `key`:
+ *   frame      sg = copysign(1.0, n.z), a = -1.0 / (sg + n.z), b = n.x * n.y * a,
+ *              t = (1.0 + sg * n.x * n.x * a, sg * b, -sg * n.x), u = (b, sg + n.y * n.y * a, -n.y)   (Duff et al. 2017: no singular normal)
+ *   rotation   r = hash(key, salt) % num_rotations with the library's counter-based hash and the salt 0x300 << 32, (c, s) = rotations[r];
+ *              x = c * lx - s * ly, y = s * lx + c * ly.  num_rotations == 0: x = lx, y = ly, no table is read.
+ *   ray j      origin p + n * bias per component; direction d = (x * t + y * u) + lz * n per component for (lx, ly, lz) = dirs[j], a direction of
+ *              the local frame whose z axis is the normal.  d is not normalised (unit inputs give | |d| - 1 | <= 1e-15): directions are used as given.
+ *   fold       sum = 0 (f32 rgb); for j = 0 .. num_dirs - 1 in order: sum += blocked ? 0 : filter, open += !blocked;
+ *              out_filter[3i..3i+2] = sum / (float)num_dirs (one correctly rounded division per channel), out_open[i] = open.
+ * The result is defined by this text and never by how the library assigns rays to lanes. */
+/* (Declared as a struct plus a separate typedef, not in the one-statement typedef form of the structs above: tests/test_integration_rust.py lists those by that
+ * form and by name, and so does NOT compare this struct with its Rust twin; tests/test_occlusion.py does, field for field, and with the ctypes one.) */
+struct NraysOcclusionParams {
+    uint32_t num_dirs;       /* 1 .. 1024 */
+    uint32_t num_rotations;  /* 0 .. 1024; 0 = none */
+    const double* dirs;      /* num_dirs x 3 */
+    const double* rotations; /* num_rotations x 2 (cos, sin), or NULL when 0 */
+    double bias;
+    double max_toi;          /* > 0, +inf allowed */
+};
+typedef struct NraysOcclusionParams NraysOcclusionParams;
+/*   points, normals  n x 3 doubles, world space, used as given.
+ *   hit_flags        n words, or NULL: the bits of out_flags of nrays_cast_rays_device.  Bit 0 clear = the point is SKIPPED: out_filter (0, 0, 0), out_open 0,
+ *                    no traversal, neither its point nor its normal read (they may hold anything) — the outputs of nrays_cast_rays_device pass on unfiltered.
+ *   keys             n RNG keys, or NULL = the key of point i is i (also across chunks).  Only the rotation reads them.
+ *   params           HOST memory (the struct); params->dirs and params->rotations are DEVICE memory here, like every other array.
+ *   out_filter       n x 3 floats, required.      out_open   n words, or NULL (no store).
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG).
+ * NULL scene / points / normals / params / params->dirs / out_filter, num_dirs outside 1 .. 1024, num_rotations > 1024 or > 0 with NULL rotations,
+ * a NaN or <= 0 max_toi, a non-finite bias -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK without work.  Otherwise the contract of nrays_cast_rays_device:
+ * every array DEVICE memory on the scene's device, chunks of at most max(1, 2^22 / num_dirs) points, enqueued on `hip_stream` without read-back or
+ * synchronisation, ordered behind the handle's previous work; what the handle reports about its renders and its per-camera scheduling state stay
+ * untouched. */
+int nrays_occlusion_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                  const uint64_t* keys, const NraysOcclusionParams* params, float* out_filter, uint32_t* out_open,
+                                  uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables included) HOST memory.  Blocking. */
+int nrays_occlusion_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                           const uint64_t* keys, const NraysOcclusionParams* params, float* out_filter, uint32_t* out_open, uint32_t flags);
+/* Test probe: the ray generator of nrays_occlusion_points_device alone (the same device function), on HOST arrays, blocking: ray j of point i to
+ * out_origins / out_dirs [(i * num_dirs + j) * 3 ..], n x num_dirs x 3 doubles each.  keys NULL: key i.  max_toi is checked and not used. */
+int nrays_debug_occlusion_rays(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint64_t* keys,
+                               const NraysOcclusionParams* params, double* out_origins, double* out_dirs);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

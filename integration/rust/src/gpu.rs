@@ -490,6 +490,37 @@ impl GpuScene {
         if nrays_shade_points_device(self.raw, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
+
+    /// Ambient occlusion at caller-supplied surface points (nrays_occlusion_points, blocking): for every (point, unit normal) the library builds
+    /// `sample_dirs.len()` hemisphere rays on the device — `sample_dirs` are directions of a local frame whose z axis is the normal, `rotations` an optional
+    /// table of (cos, sin) pairs one of which is picked per point by hashing `keys[i]` (None: key i) —, runs `Scene::intersects_ray` with `max_toi` on each
+    /// from `point + normal * bias` and folds them: the mean colour filter of the rays (blocked rays count as black) and the number that got through.
+    /// The rays are defined bit for bit in include/nrays_abi.h (NraysOcclusionParams).
+    pub fn occlusion_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, max_toi: f64,
+                            keys: Option<&[u64]>) -> Result<Vec<(Vector3<f32>, u32)>, String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysOcclusionParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                            rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, max_toi };
+        let (mut filter, mut open) = (vec![0.0f32; 3 * n], vec![0u32; n]);
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_occlusion_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, filter.as_mut_ptr(), open.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| (Vector3::new(filter[3 * i], filter[3 * i + 1], filter[3 * i + 2]), open[i])).collect())
+    }
+
+    /// `occlusion_points` for n points in DEVICE memory (nrays_occlusion_points_device), enqueued on `hip_stream` without synchronisation: points / normals
+    /// n x 3 f64, hit_flags n u32 or null (out_flags of cast_rays_device: bit 0 clear = skipped, zeros), keys n u64 or null, out_filter n x 3 f32, out_open
+    /// n u32 or null.  `params` is host memory; its two tables are device memory.
+    pub unsafe fn occlusion_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: &NraysOcclusionParams,
+                                          out_filter: *mut f32, out_open: *mut u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_occlusion_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_filter, out_open, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
 }
 
 impl Drop for GpuScene {

@@ -198,6 +198,17 @@ pub struct NraysBlasDump {
     pub tri_ids: *mut u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysOcclusionParams {
+    pub num_dirs: u32,
+    pub num_rotations: u32,
+    pub dirs: *const f64,
+    pub rotations: *const f64,
+    pub bias: f64,
+    pub max_toi: f64,
+}
+
 pub enum NraysScene {}
 pub enum NraysComm {}
 pub enum NraysSceneSet {}
@@ -235,6 +246,9 @@ extern "C" {
     pub fn nrays_cast_rays(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_toi: *mut f64, out_node: *mut i32, out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
     pub fn nrays_shade_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, view_dirs: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, keys: *const u64, out_rgba: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_shade_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, view_dirs: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, keys: *const u64, out_rgba: *mut f32, flags: u32) -> c_int;
+    pub fn nrays_occlusion_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_occlusion_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_debug_occlusion_rays(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, keys: *const u64, params: *const NraysOcclusionParams, out_origins: *mut f64, out_dirs: *mut f64) -> c_int;
     pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;

@@ -6,5 +6,5 @@ front-end (host/), and this thin ctypes mirror of the reference's scene-model su
 from . import abi  # noqa: F401
 from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolation, Isometry3, Light,  # noqa: F401
                     NormalMaterial, Overflow, PhongMaterial, Plane, Scene, SceneDescriptor, SceneNode, Texture2d,
-                    TriMesh, UVMaterial, CastHits, camera_rays, cast_rays, closest_hits, get_stats, intersects_rays, last_permutation, make_params, ray_order, render, shade_hits, shade_points,
-                    shadow_rays, trace_rays)
+                    TriMesh, UVMaterial, CastHits, Occlusion, camera_rays, cast_rays, closest_hits, get_stats, hemisphere_dirs, intersects_rays, last_permutation, make_params,
+                    occlusion_hits, occlusion_points, occlusion_ray_probe, occlusion_rays, ray_order, render, rotation_table, shade_hits, shade_points, shadow_rays, trace_rays)

@@ -108,6 +108,11 @@ class NraysCastResult(C.Structure):
     _fields_ = [("toi", C.c_double), ("normal", C.c_double * 3), ("uv", C.c_double * 2), ("node_id", C.c_int32), ("flags", C.c_uint32)]
 
 
+class NraysOcclusionParams(C.Structure):
+    """The tables of nrays_occlusion_points*: `dirs` / `rotations` are addresses (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("max_toi", C.c_double)]
+
+
 class NraysBlasDump(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_refs", C.c_uint32), ("root", C.c_int32), ("max_depth", C.c_int32), ("hairy", C.c_uint32),
                 ("node_capacity", C.c_uint32), ("ref_capacity", C.c_uint32), ("pad", C.c_uint32), ("nodes", C.POINTER(C.c_float)), ("tri_ids", C.POINTER(C.c_uint32))]
@@ -139,6 +144,12 @@ HIP_SYMBOLS = {
                                             C.c_uint32, C.c_void_p]),
     "nrays_shade_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                      C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_float), C.c_uint32]),
+    "nrays_occlusion_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysOcclusionParams), C.c_void_p, C.c_void_p,
+                                                C.c_uint32, C.c_void_p]),
+    "nrays_occlusion_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(NraysOcclusionParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_debug_occlusion_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(NraysOcclusionParams),
+                                             C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nrays_debug_ray_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "nrays_scene_create": (C.c_int, [C.POINTER(NraysSceneDesc), C.POINTER(C.c_void_p)]),
@@ -173,7 +184,8 @@ HIP_SYMBOLS = {
 
 # Added after ABI version 7 without a bump: an older version-7 library (NRAYS_HIP_LIB: A/B runs against a parent build) may lack them.
 POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_intersects_rays_device_ex", "nrays_debug_ray_order",
-                   "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points")
+                   "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points", "nrays_occlusion_points_device",
+                   "nrays_occlusion_points", "nrays_debug_occlusion_rays")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 RAY_FRAME_DOUBLES = 20      # NRAYS_RAY_FRAME_DOUBLES
 

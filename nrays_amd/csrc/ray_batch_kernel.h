@@ -2,6 +2,7 @@
 // k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
+// k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value.
 // Device code only.
 #pragma once
 #include "primary_kernel.h"
@@ -197,6 +198,110 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_shade_points(D
         o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
     }
     flush_counters(ctr, cnt, STATS);
+}
+
+// ---- ambient occlusion at caller-supplied points (nrays_occlusion_points*) --------------------------------------------------------------------
+// The rays are DEFINED by include/nrays_abi.h (NraysOcclusionParams) and mirrored in numpy (nrays_amd.occlusion_rays): f64 + - * /, copysign and
+// integer arithmetic only, every product evaluated left to right as written, nothing fused (-ffp-contract=off).  occlusion_frame / occlusion_dir are
+// the one generator: k_occlusion_points traces their rays and k_occlusion_rays (nrays_debug_occlusion_rays) stores them.
+struct OcclusionSpec { uint32_t num_dirs, num_rotations; double bias, max_toi; };
+struct OccFrame { d3 o, t, u, n; double c, s; };
+
+// The branch-free orthonormal frame of Duff et al. 2017 around normal n (no singular normal), the biased origin, and the point's rotation
+// (c, s) = rotations[rng_hash(key, kSaltOcclusion) % R]; R = 0: no table is read and occlusion_dir leaves (lx, ly) untouched.
+NR_DEV OccFrame occlusion_frame(d3 p, d3 n, unsigned long long key, const OcclusionSpec& P, const double* __restrict__ rotations) {
+    OccFrame f;
+    const double s = copysign(1.0, n.z), a = -1.0 / (s + n.z), b = n.x * n.y * a;
+    f.t = D3(1.0 + s * n.x * n.x * a, s * b, -s * n.x);
+    f.u = D3(b, s + n.y * n.y * a, -n.y);
+    f.n = n;
+    f.o = D3(p.x + n.x * P.bias, p.y + n.y * P.bias, p.z + n.z * P.bias);
+    f.c = 1.0; f.s = 0.0;
+    if (P.num_rotations) {
+        const size_t r = (size_t)(rng_hash(key, kSaltOcclusion) % (unsigned long long)P.num_rotations);
+        f.c = rotations[2 * r]; f.s = rotations[2 * r + 1];
+    }
+    return f;
+}
+// Sample direction (lx, ly, lz) of the local frame (z = the normal) in world space.  Not normalised: the traversal uses directions as given.
+NR_DEV d3 occlusion_dir(const OccFrame& f, bool rotate, double lx, double ly, double lz) {
+    double x = lx, y = ly;
+    if (rotate) { x = f.c * lx - f.s * ly; y = f.s * lx + f.c * ly; }
+    return D3((x * f.t.x + y * f.u.x) + lz * f.n.x, (x * f.t.y + y * f.u.y) + lz * f.n.y, (x * f.t.z + y * f.u.z) + lz * f.n.z);
+}
+
+// Point i of the chunk: num_dirs transparent-shadow queries (Scene::intersects_ray, what k_intersects_rays runs) from p + n * bias, folded in the
+// order of the directions — f32 sum of the filters of the rays that got through, then ONE division by (float)num_dirs; out_open[i] counts them.
+// 2^LP lanes serve a point: lane `sub` takes the directions j = sub (mod 2^LP), and after every round the 2^LP partial values are added in the order of j
+// through __shfl, every lane of the point keeping the same running sum — the sequential f32 sum, so the result does not depend on LP.  The lanes of a point share
+// its origin; ray_order.hip gives a point as many lanes as its directions fill (measured: profiles/occlusion_rate.json).  LP = 0 is lane = point: no shuffle, and
+// direction j is wave-uniform, so the compiler can fetch its three doubles with scalar loads.
+// A point whose flag bit 0 is clear is skipped: zeros, no traversal, neither its point nor its normal read.  NULL keys: key_base + i.
+template <int FEAT, int LP>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_points(DScene S, uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                                                    const uint32_t* __restrict__ hit_flags, const unsigned long long* __restrict__ keys,
+                                                                                    unsigned long long key_base, OcclusionSpec P, const double* __restrict__ dirs,
+                                                                                    const double* __restrict__ rotations, float* __restrict__ out_filter,
+                                                                                    uint32_t* __restrict__ out_open, uint32_t* spill) {
+    static_assert(LP >= 0 && LP <= 6, "the lanes of a point share a wave");
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    constexpr uint32_t kLanes = 1u << LP;
+    const uint32_t k = P.num_dirs, slots = n << LP; // (n <= 2^22: ray_order.hip's chunks)
+    const bool rotate = P.num_rotations != 0u;
+    for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
+        const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
+        OccFrame f;
+        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
+        if (live) {
+            const size_t i3 = 3 * (size_t)i;
+            f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), keys ? keys[i] : key_base + i, P, rotations);
+        }
+        f3 sum = F3(0.0f, 0.0f, 0.0f);
+        uint32_t open = 0u;
+        for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
+            const uint32_t j = j0 + sub;
+            f3 c = F3(0.0f, 0.0f, 0.0f);
+            uint32_t lit = 0u;
+            if (live && j < k) {
+                const d3 d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
+                Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+                if (!traverse<true, false, FEAT>(S, st, f.o, d, P.max_toi, hit, filter, cnt)) { c = filter; lit = 1u; }
+            }
+            if constexpr (LP == 0) {
+                sum.x += c.x; sum.y += c.y; sum.z += c.z; open += lit;
+            } else {
+#pragma unroll
+                for (uint32_t s = 0; s < kLanes; ++s) {
+                    const float cx = __shfl(c.x, (int)s, (int)kLanes), cy = __shfl(c.y, (int)s, (int)kLanes), cz = __shfl(c.z, (int)s, (int)kLanes);
+                    const uint32_t l = (uint32_t)__shfl((int)lit, (int)s, (int)kLanes);
+                    if (j0 + s < k) { sum.x += cx; sum.y += cy; sum.z += cz; open += l; }
+                }
+            }
+        }
+        if (i < n && sub == 0u) {
+            const float fk = (float)k;
+            out_filter[3 * (size_t)i] = sum.x / fk; out_filter[3 * (size_t)i + 1] = sum.y / fk; out_filter[3 * (size_t)i + 2] = sum.z / fk;
+            if (out_open) out_open[i] = open;
+        }
+    }
+}
+
+// nrays_debug_occlusion_rays: ray j of point i, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].
+__global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                           const unsigned long long* __restrict__ keys, OcclusionSpec P, const double* __restrict__ dirs,
+                                                           const double* __restrict__ rotations, double* __restrict__ out_origins, double* __restrict__ out_dirs) {
+    const size_t rays = (size_t)n * P.num_dirs;
+    for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < rays; r += (size_t)gridDim.x * kBlock) {
+        const size_t i = r / P.num_dirs, j = r % P.num_dirs;
+        const OccFrame f = occlusion_frame(D3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), D3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]),
+                                           keys ? keys[i] : (unsigned long long)i, P, rotations);
+        const d3 d = occlusion_dir(f, P.num_rotations != 0u, dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
+        out_origins[3 * r] = f.o.x; out_origins[3 * r + 1] = f.o.y; out_origins[3 * r + 2] = f.o.z;
+        out_dirs[3 * r] = d.x; out_dirs[3 * r + 1] = d.y; out_dirs[3 * r + 2] = d.z;
+    }
 }
 
 } // namespace nrays

@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <string>
 
@@ -545,6 +546,162 @@ static int shade_points_host_impl(NraysScene* sc, uint32_t n, const ShadeIn& in,
     return rc;
 }
 
+// ---- nrays_occlusion_points*: ambient occlusion at caller-supplied points, the hemisphere rays built on the device ------------------------------------
+struct OcclusionIn { const double* points; const double* normals; const uint32_t* hit_flags; const uint64_t* keys; };
+static OcclusionIn occlusion_in_at(const OcclusionIn& in, size_t c0) {
+    return OcclusionIn{in.points + 3 * c0, in.normals + 3 * c0, in.hit_flags ? in.hit_flags + c0 : nullptr, in.keys ? in.keys + c0 : nullptr};
+}
+static int check_occlusion_params(const NraysOcclusionParams* p) {
+    if (!p || !p->dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: num_dirs must be in 1 .. 1024");
+    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: num_rotations > 1024, or rotations is NULL");
+    if (!(p->max_toi > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: max_toi must be > 0 (+inf allowed)");
+    if (!std::isfinite(p->bias)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: bias must be finite");
+    return NRAYS_OK;
+}
+static int check_occlusion_args(const NraysScene* sc, const OcclusionIn& in, const NraysOcclusionParams* p, const float* out_filter, uint32_t flags) {
+    if (!sc || !in.points || !in.normals || !out_filter) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_occlusion_params(p) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_occlusion_points: flags must be 0");
+    return NRAYS_OK;
+}
+static OcclusionSpec occlusion_spec(const NraysOcclusionParams* p) { return OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, p->max_toi}; }
+static uint32_t occlusion_chunk(const NraysOcclusionParams* p) { return std::max<uint32_t>(1u, kTraceChunk / p->num_dirs); } // points per chunk: at most kTraceChunk rays
+// Lanes per point (log2), among the instantiated 0, 3 and 6: as many lanes as there are directions to give them.  Measured (profiles/occlusion_rate.json, sponza
+// stand-in): at 2 M points x 16 directions 8 lanes take 3.07 ms against 4.77 ms with one lane per point and 3.03 ms for k_intersects_rays on the same rays; at
+// 16 384 points x 64 directions 64 lanes take 0.136 ms, 8 lanes 0.205, one lane 1.47 (a grid of 64 workgroups).  The lanes of a point share its origin, and that is
+// the coherence the traversal lives on; one lane per point is left to batches of fewer than 8 directions.  NRAYS_OCCLUSION_LANES=0|3|6 forces a form (the A/B of
+// tools/trace_rays_rate.py --occlusion; the results do not depend on it).
+static int occlusion_lanes_log2(const NraysScene* sc, uint32_t num_dirs) {
+    int lp = 6;
+    if (sc->sw.occlusion_lanes >= 0) lp = sc->sw.occlusion_lanes >= 6 ? 6 : (sc->sw.occlusion_lanes >= 3 ? 3 : 0);
+    while (lp > 0 && (1u << lp) > num_dirs) lp -= 3;
+    return lp;
+}
+// One chunk (nc <= occlusion_chunk) of nrays_occlusion_points_device; `in` and the outputs are the chunk's, key_base the index of its first point in the
+// batch, dirs / rotations device copies of the tables.  The permutation: kFeatMesh or kFeatAll, as k_intersects_rays.
+static int occlusion_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const OcclusionIn& in, unsigned long long key_base, const OcclusionSpec& spec,
+                                  const double* dirs, const double* rotations, float* out_filter, uint32_t* out_open, hipStream_t stream) {
+    const bool mesh = (sc->facts.features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_intersects_rays_device)
+    const int lp = occlusion_lanes_log2(sc, spec.num_dirs);
+    const uint32_t slots = nc << lp; // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+    const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const unsigned long long* keys = (const unsigned long long*)in.keys;
+#define NR_OCC_LAUNCH(FEAT, LP) hipLaunchKernelGGL((k_occlusion_points<FEAT, LP>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, nc, in.points, in.normals, in.hit_flags, keys, key_base, spec, dirs, rotations, out_filter, out_open, w->d_spill)
+    if (mesh) { if (lp == 0) NR_OCC_LAUNCH(kFeatMesh, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatMesh, 3); else NR_OCC_LAUNCH(kFeatMesh, 6); }
+    else { if (lp == 0) NR_OCC_LAUNCH(kFeatAll, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatAll, 3); else NR_OCC_LAUNCH(kFeatAll, 6); }
+#undef NR_OCC_LAUNCH
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_occlusion_points: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+
+static int occlusion_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysOcclusionParams* p, float* out_filter, uint32_t* out_open,
+                                        uint32_t flags, hipStream_t stream) {
+    if (check_occlusion_args(sc, in, p, out_filter, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const uint32_t chunk = occlusion_chunk(p);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        rc = occlusion_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, occlusion_spec(p), p->dirs, p->rotations, out_filter + 3 * (size_t)c0,
+                                    out_open ? out_open + c0 : nullptr, stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form, through the workspace's staging buffer as shade_points_host_impl: the two tables first, then per staged point kOcclusionStageBytes —
+// point, normal (3 f64), key (u64), filter (3 f32), hit flags, open count (32 bits), the 8-byte fields first.
+constexpr size_t kOcclusionStageBytes = 76;
+static int occlusion_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysOcclusionParams* p, float* out_filter, uint32_t* out_open, uint32_t flags) {
+    if (check_occlusion_args(sc, in, p, out_filter, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    const uint32_t chunk = occlusion_chunk(p);
+    const size_t cap = std::min<uint32_t>(n, chunk), table = 3 * (size_t)p->num_dirs + 2 * (size_t)p->num_rotations;
+    rc = grow_device(&w->d_stage, &w->stage_rays, (table * sizeof(double) + cap * kOcclusionStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc != NRAYS_OK) return rc;
+    double* s_dirs = (double*)w->d_stage; double* s_rot = s_dirs + 3 * (size_t)p->num_dirs; double* s_p = s_dirs + table; double* s_n = s_p + 3 * cap;
+    uint64_t* s_k = (uint64_t*)(s_n + 3 * cap); float* s_f = (float*)(s_k + cap); uint32_t* s_hf = (uint32_t*)(s_f + 3 * cap); uint32_t* s_open = s_hf + cap;
+    const OcclusionIn s{s_p, s_n, in.hit_flags ? s_hf : nullptr, in.keys ? s_k : nullptr};
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+    hipError_t e = up(s_dirs, p->dirs, 24 * (size_t)p->num_dirs);
+    if (e == hipSuccess) e = up(s_rot, p->rotations, 16 * (size_t)p->num_rotations);
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("occlusion tables upload: ") + hipGetErrorString(e));
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        const OcclusionIn h = occlusion_in_at(in, c0);
+        e = up(s_p, h.points, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_n, h.normals, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
+        if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("occlusion batch upload: ") + hipGetErrorString(e)); break; }
+        rc = occlusion_chunk_launch(sc, w, nc, s, (unsigned long long)c0, occlusion_spec(p), s_dirs, p->num_rotations ? s_rot : nullptr, s_f, out_open ? s_open : nullptr, stream);
+        if (rc != NRAYS_OK) break;
+        e = hipMemcpyAsync(out_filter + 3 * (size_t)c0, s_f, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && out_open) e = hipMemcpyAsync(out_open + c0, s_open, (size_t)nc * 4, hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("occlusion batch read-back: ") + hipGetErrorString(e));
+    }
+    if (rc != NRAYS_OK) (void)hipStreamSynchronize(stream); // (the tables' upload reads the caller's memory)
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// nrays_debug_occlusion_rays: the generator of k_occlusion_points alone, on host arrays, blocking; buffers of its own (a test probe).
+static int occlusion_rays_probe(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* p,
+                                double* out_origins, double* out_dirs) {
+    if (!sc || !points || !normals || !out_origins || !out_dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_occlusion_params(p) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    int rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    const size_t rays = (size_t)n * p->num_dirs, table = 3 * (size_t)p->num_dirs + 2 * (size_t)p->num_rotations;
+    const size_t doubles = table + 6 * (size_t)n + (keys ? n : 0) + 6 * rays;
+    double* d_all = nullptr;
+    {
+        const hipError_t e = hipMalloc((void**)&d_all, doubles * sizeof(double));
+        if (e != hipSuccess) return set_last_error(e == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string("occlusion probe: ") + hipGetErrorString(e));
+    }
+    double* d_dirs = d_all; double* d_rot = d_dirs + 3 * (size_t)p->num_dirs; double* d_p = d_all + table; double* d_n = d_p + 3 * (size_t)n;
+    double* d_k = d_n + 3 * (size_t)n; double* d_oo = d_k + (keys ? n : 0); double* d_od = d_oo + 3 * rays;
+    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+    hipError_t e = up(d_dirs, p->dirs, 24 * (size_t)p->num_dirs);
+    if (e == hipSuccess) e = up(d_rot, p->rotations, 16 * (size_t)p->num_rotations);
+    if (e == hipSuccess) e = up(d_p, points, 24 * (size_t)n);
+    if (e == hipSuccess) e = up(d_n, normals, 24 * (size_t)n);
+    if (e == hipSuccess) e = up(d_k, keys, 8 * (size_t)n);
+    if (e == hipSuccess) {
+        const uint32_t grid = (uint32_t)std::min<size_t>((rays + kBlock - 1) / kBlock, (size_t)kMaxGrid);
+        hipLaunchKernelGGL(k_occlusion_rays, dim3(grid), dim3(kBlock), 0, stream, n, (const double*)d_p, (const double*)d_n, keys ? (const unsigned long long*)d_k : nullptr,
+                           occlusion_spec(p), (const double*)d_dirs, p->num_rotations ? (const double*)d_rot : nullptr, d_oo, d_od);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(out_origins, d_oo, 24 * rays, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_dirs, d_od, 24 * rays, hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream);
+    if (e == hipSuccess) e = es;
+    (void)hipFree(d_all);
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("occlusion probe: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -692,6 +849,19 @@ int nrays_shade_points_device(NraysScene* sc, uint32_t n, const double* points, 
 int nrays_shade_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
                        const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags) {
     return shade_points_host_impl(sc, n, ShadeIn{points, normals, view_dirs, uvs, nodes, hit_flags, keys}, out_rgba, flags);
+}
+
+int nrays_occlusion_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                  const NraysOcclusionParams* params, float* out_filter, uint32_t* out_open, uint32_t flags, void* hip_stream) {
+    return occlusion_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_filter, out_open, flags, (hipStream_t)hip_stream);
+}
+int nrays_occlusion_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                           const NraysOcclusionParams* params, float* out_filter, uint32_t* out_open, uint32_t flags) {
+    return occlusion_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_filter, out_open, flags);
+}
+int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* params,
+                               double* out_origins, double* out_dirs) {
+    return occlusion_rays_probe(sc, n, points, normals, keys, params, out_origins, out_dirs);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

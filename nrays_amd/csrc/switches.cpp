@@ -56,6 +56,7 @@ Switches read_switches() {
     clamped("NRAYS_LEAD_PER_WG", s.lead_per_wg, 1, 64);
     clamped("NRAYS_GRID_WG_PER_CU", s.grid_wg_per_cu, 0, kIntMax);
     integer("NRAYS_RAY_REORDER", s.ray_reorder);
+    integer("NRAYS_OCCLUSION_LANES", s.occlusion_lanes);
     at_least("NRAYS_WF_MAX_PATHS", s.wf_max_paths, 4096);
     flag("NRAYS_WF_FUSE", s.wf_fuse);
     if (const char* e = getenv("NRAYS_WF_REFILL")) { s.wf_refill = atoi(e) != 0; s.wf_refill_aa = atoi(e) == 2; }

@@ -97,6 +97,8 @@ NR_DEV double rng_u01(unsigned long long key, unsigned long long dim) {
     return (double)(rng_hash(key, 0x1000ULL + dim) >> 11) * (1.0 / 9007199254740992.0);
 }
 constexpr unsigned long long kSaltPath = 2ULL, kSaltRefl = 0x100ULL, kSaltRefr = 0x101ULL, kSaltLight = 0x200ULL;
+// (kSaltLight + light index and rng_u01's 0x1000 + dimension stay below 2^33: kSaltOcclusion, the rotation pick of k_occlusion_points, is out of their reach)
+constexpr unsigned long long kSaltOcclusion = 0x300ULL << 32;
 
 // ---------------------------------------------------------------- counters -------------------
 #ifdef NR_PHASE_TIMING

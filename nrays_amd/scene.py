@@ -372,6 +372,10 @@ class Scene:
         """The direct lighting of caller-supplied surface points of this scene: shade_points(self, ...)."""
         return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
 
+    def occlusion_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, hit_flags=None, keys=None):
+        """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
+        return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
+
     def _release(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)
@@ -742,6 +746,186 @@ def shade_hits(scene, origins, dirs, hits, keys=None):
     step = dirs * toi[:, None]
     points = origins + step
     return shade_points(scene, points, hits.normal, dirs, hits.node, uvs=hits.uv, hit_flags=hits.flags, keys=keys)
+
+
+# ---- ambient occlusion at caller-supplied points: the hemisphere rays are built on the device (include/nrays_abi.h: NraysOcclusionParams) ----------
+
+Occlusion = collections.namedtuple("Occlusion", ("filter", "open"))
+SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
+OCCLUSION_MAX_TABLE = 1024
+
+
+def hemisphere_dirs(k, cosine=True):
+    """k sample directions of the local frame of occlusion_points (z = the normal), (k, 3) float64, unit length, z > 0: a golden-angle spiral,
+    cosine-weighted (the mean filter then IS the cosine-weighted ambient term) or uniform over the hemisphere.  A convenience: any values are valid."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    u = (np.arange(k, dtype=np.float64) + 0.5) / k
+    z = np.sqrt(1.0 - u) if cosine else 1.0 - u
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = np.arange(k, dtype=np.float64) * (math.pi * (3.0 - math.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    return d / np.sqrt((d * d).sum(axis=1))[:, None]
+
+
+def rotation_table(m):
+    """m rotations about the normal, evenly spaced, as the (m, 2) float64 table of (cos, sin) pairs occlusion_points picks from per point."""
+    m = int(m)
+    if m < 1 or m > OCCLUSION_MAX_TABLE:
+        raise ValueError("m must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    a = np.arange(m, dtype=np.float64) * (2.0 * math.pi / m)
+    return np.stack([np.cos(a), np.sin(a)], axis=1)
+
+
+def _occlusion_tables(sample_dirs, rotations, bias, max_toi):
+    """The two tables as contiguous float64 numpy arrays (or the torch tensors they came as), checked against NraysOcclusionParams' bounds."""
+    def table(name, a, cols, lo):
+        if not _is_tensor(a):
+            a = np.asarray(a)
+            if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("%s must be numbers, got %s" % (name, a.dtype))
+            a = np.ascontiguousarray(a, dtype=np.float64)
+        if len(a.shape) != 2 or a.shape[1] != cols or not lo <= a.shape[0] <= OCCLUSION_MAX_TABLE:
+            raise ValueError("%s must have shape (%d .. %d, %d), got %s" % (name, lo, OCCLUSION_MAX_TABLE, cols, tuple(a.shape)))
+        return a
+    if sample_dirs is None:
+        raise ValueError("sample_dirs is required")
+    L = table("sample_dirs", sample_dirs, 3, 1)
+    rot = None if rotations is None else table("rotations", rotations, 2, 0)
+    if rot is not None and rot.shape[0] == 0:
+        rot = None
+    bias, max_toi = float(bias), float(max_toi)
+    if not math.isfinite(bias):
+        raise ValueError("bias must be finite")
+    if not max_toi > 0.0:
+        raise ValueError("max_toi must be > 0 (inf allowed)")
+    return L, rot, bias, max_toi
+
+
+def occlusion_rays(points, normals, sample_dirs, rotations=None, bias=1e-3, keys=None):
+    """The numpy mirror of the rays nrays_occlusion_points* builds on the device, bit for bit (include/nrays_abi.h: NraysOcclusionParams — f64 + - * /,
+    copysign and integer arithmetic, products left to right).  Returns (origins (n, k, 3), dirs (n, k, 3)) float64: ray j of point i at [i, j].
+    `keys` (n,) integers, default arange(n): only the rotation pick reads them."""
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("keys", keys, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    if _is_tensor(points) or _is_tensor(normals) or _is_tensor(L) or _is_tensor(rot) or _is_tensor(keys):
+        raise ValueError("occlusion_rays takes numpy arrays")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    k = np.arange(n, dtype=np.uint64) if keys is None else _np_keys(keys)
+    nx, ny, nz = nm[:, 0], nm[:, 1], nm[:, 2]
+    with np.errstate(all="ignore"):
+        s = np.copysign(1.0, nz)
+        a = -1.0 / (s + nz)
+        b = nx * ny * a
+        t = (1.0 + s * nx * nx * a, s * b, -s * nx)
+        u = (b, s + ny * ny * a, -ny)
+        lx, ly, lz = (np.broadcast_to(L[:, c], (n, len(L))) for c in range(3))
+        if rot is None:
+            x, y = lx, ly
+        else:
+            r = (_rng_hash(k, SALT_OCCLUSION) % np.uint64(len(rot))).astype(np.int64)
+            c_r, s_r = rot[r, 0][:, None], rot[r, 1][:, None]
+            x, y = c_r * lx - s_r * ly, s_r * lx + c_r * ly
+        dirs = np.stack([(x * t[q][:, None] + y * u[q][:, None]) + lz * nm[:, q][:, None] for q in range(3)], axis=2)
+        o = p + nm * bias
+    origins = np.ascontiguousarray(np.broadcast_to(o[:, None, :], dirs.shape))
+    return origins, np.ascontiguousarray(dirs)
+
+
+def occlusion_ray_probe(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, keys=None):
+    """Test probe (nrays_debug_occlusion_rays): the rays as the library's own generator — the device function k_occlusion_points traces — builds them,
+    in occlusion_rays()' layout.  numpy arrays, blocking."""
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("keys", keys, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    k = None if keys is None else _np_keys(keys)
+    o, d = np.empty((n, len(L), 3), np.float64), np.empty((n, len(L), 3), np.float64)
+    params = abi.NraysOcclusionParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, math.inf)
+    dp = C.POINTER(C.c_double)
+    abi.check(abi.load_hip_lib().nrays_debug_occlusion_rays(scene.device_handle(), n, p.ctypes.data_as(dp), nm.ctypes.data_as(dp),
+                                                            None if k is None else k.ctypes.data_as(C.POINTER(C.c_uint64)), C.byref(params),
+                                                            o.ctypes.data_as(dp), d.ctypes.data_as(dp)))
+    return o, d
+
+
+def occlusion_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, hit_flags=None, keys=None):
+    """Ambient occlusion at n caller-supplied surface points, through nrays_occlusion_points_device / nrays_occlusion_points: per point the library
+    builds len(sample_dirs) hemisphere rays ON THE DEVICE (occlusion_rays() restates them bit for bit), runs Scene::intersects_ray — the query of
+    intersects_rays() — with `max_toi` on each and folds them in order: Occlusion(filter (n, 3) float32 — the mean colour filter, a blocked ray counting as
+    black —, open (n,) — the rays that got through).  No ray or per-ray result is ever in memory.  Also `scene.occlusion_points(...)` on Scene and FileScene;
+    occlusion_hits() feeds it from closest_hits().
+    `points`, `normals`: (n, 3), used as given (unit normals, pointing to the side to sample).  `sample_dirs` (k, 3), 1 <= k <= 1024: directions of the local
+    frame whose z axis is the normal (hemisphere_dirs()).  `rotations` (R, 2) (cos, sin) pairs, R <= 1024, or None: point i turns its directions about the
+    normal by entry hash(keys[i]) % R (rotation_table()).  `bias`: the rays start at point + normal * bias.  `hit_flags` (n,) integers or None: the flag words
+    of closest_hits — bit 0 clear: the point is skipped (zeros; its point and normal may hold anything).  `keys` (n,) integers, default: point i has key i.
+    numpy arrays -> nrays_occlusion_points (blocking), numpy arrays (open uint32).  torch tensors on the scene's GPU (float64; hit_flags int32 / uint32; keys
+    int64 / uint64; the tables tensors or anything numpy takes) -> nrays_occlusion_points_device on torch.cuda.current_stream(), tensors (open int32)."""
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, max_toi = _occlusion_tables(sample_dirs, rotations, bias, max_toi)
+    if _is_tensor(points):
+        import torch
+        if points.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, points is on %s" % points.device)
+        f64 = (torch.float64,)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        flags_dt = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        L, rot = (t if t is None or _is_tensor(t) else torch.from_numpy(t).to(points.device) for t in (L, rot))
+        p, nm, hf, k, L, rot = _torch_args((("points", points, f64), ("normals", normals, f64), ("hit_flags", hit_flags, flags_dt), ("keys", keys, keys_dt),
+                                            ("sample_dirs", L, f64), ("rotations", rot, f64)), points.device)
+        filt = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        opened = torch.empty((n,), dtype=torch.int32, device=points.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        params = abi.NraysOcclusionParams(L.shape[0], 0 if rot is None else rot.shape[0], ptr(L), ptr(rot), bias, max_toi)
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(points.device):
+            abi.check(lib.nrays_occlusion_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(filt), ptr(opened), 0,
+                                                        torch.cuda.current_stream().cuda_stream))
+        return Occlusion(filt, opened)
+    if any(_is_tensor(a) for a in (normals, hit_flags, keys, L, rot)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    filt, opened = np.empty((n, 3), dtype=np.float32), np.empty((n,), dtype=np.uint32)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    params = abi.NraysOcclusionParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, max_toi)
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_occlusion_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
+                                         ptr(filt, C.c_float), ptr(opened, C.c_uint32), 0))
+    return Occlusion(filt, opened)
+
+
+def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, keys=None):
+    """Ambient occlusion at the closest hits of caller-supplied rays: occlusion_points() at the hits of `hits = closest_hits(scene, origins, dirs)` (a
+    CastHits with normal and flags), on the side the rays came from.  The points are origins + dirs * toi — two separate element-wise operations, with toi 0
+    at the misses, as in shade_hits() —; a normal is negated where (nx * dx + ny * dy) + nz * dz > 0.  Misses come back as zeros.  numpy or torch as the
+    inputs."""
+    n = _n_of(origins, dirs)
+    for name in ("normal", "flags"):
+        if getattr(hits, name) is None:
+            raise ValueError("occlusion_hits: hits.%s is None (closest_hits must be asked for normal and flags)" % name)
+    _check_vec("hits.toi", hits.toi, n)
+    _check_rows("hits.normal", hits.normal, n, 3)
+    if _is_tensor(origins) != _is_tensor(hits.toi) or _is_tensor(origins) != _is_tensor(dirs) or _is_tensor(origins) != _is_tensor(hits.normal):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    nm = hits.normal
+    if _is_tensor(origins):
+        import torch
+        toi = torch.where((hits.flags & 1) != 0, hits.toi, torch.zeros_like(hits.toi))
+        where = torch.where
+    else:
+        toi = np.where((np.asarray(hits.flags) & 1) != 0, hits.toi, 0.0)
+        where = np.where
+    step = dirs * toi[:, None]
+    points = origins + step
+    facing = (nm[:, 0] * dirs[:, 0] + nm[:, 1] * dirs[:, 1]) + nm[:, 2] * dirs[:, 2]
+    normals = where((facing > 0)[:, None], -nm, nm)
+    return occlusion_points(scene, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags=hits.flags, keys=keys)
 
 
 def ray_order(scene, origins, dirs):

@@ -108,6 +108,11 @@ class FileScene:
         from .scene import shade_points
         return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
 
+    def occlusion_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=float("inf"), hit_flags=None, keys=None):
+        """Ambient occlusion at caller-supplied surface points of this scene: scene.occlusion_points(self, ...)."""
+        from .scene import occlusion_points
+        return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
+
     def close(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)

@@ -27,7 +27,13 @@ and closest_hits() itself — in alternating rounds, each of --reps launches bet
 median round.  A library without the entry point (an older one under NRAYS_HIP_LIB) gets the trace_rays and closest_hits figures only, and
 --beside FILE copies the workloads of such an earlier run into this run's JSON under "beside".
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]]
+--occlusion times, and nothing else, the leg e_sponza_occlusion: ambient occlusion at the first hits of the sponza stand-in's camera rays with 16 directions
+a point, and at a 16 384-point subset of them with 64.  The fused call (occlusion_points(): rays built in registers, one folded value per point) stands
+beside what the library offered before on the very same rays — the rays of the definition built with torch on the device, intersects_rays() on them unhinted
+and with unordered=True, and the torch fold of the per-ray results, timed apart — and beside itself on handles forced to one lane per point and to 8 / 64 lanes
+per point (NRAYS_OCCLUSION_LANES).  Alternating rounds, each of a few launches between events: min, median and max of every leg.
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion]
 """
 import argparse
 import ctypes as C
@@ -203,9 +209,103 @@ def _shade_row(sc, o, d, k, reps, rounds=5):
     return row
 
 
+OCCLUSION_MAX_TOI = 0.5  # the occlusion leg's radius (the stand-in is a closed hall about 7 units long: no ray gets out of it)
+
+
+def _torch_occlusion_rays(tp, tn, L, rot, bias, keys):
+    """nrays_amd.occlusion_rays() with torch on the device: the same element-wise f64 operations (the rotation index comes from the host: torch has no uint64
+    arithmetic).  Returns (origins, dirs) as (n * k, 3) tensors, point-major."""
+    import torch
+    from nrays_amd.scene import SALT_OCCLUSION, _rng_hash
+    n, k = tp.shape[0], len(L)
+    tl = torch.from_numpy(np.ascontiguousarray(L)).cuda()
+    nx, ny, nz = tn[:, 0:1], tn[:, 1:2], tn[:, 2:3]
+    s = torch.copysign(torch.ones_like(nz), nz)
+    a = -1.0 / (s + nz)
+    b = nx * ny * a
+    t = (1.0 + s * nx * nx * a, s * b, -s * nx)
+    u = (b, s + ny * ny * a, -ny)
+    lx, ly, lz = tl[None, :, 0], tl[None, :, 1], tl[None, :, 2]
+    r = torch.from_numpy((_rng_hash(keys, SALT_OCCLUSION) % np.uint64(len(rot))).astype(np.int64)).cuda()
+    tr = torch.from_numpy(np.ascontiguousarray(rot)).cuda()
+    c_r, s_r = tr[r, 0:1], tr[r, 1:2]
+    x, y = c_r * lx - s_r * ly, s_r * lx + c_r * ly
+    dirs = torch.stack([(x * t[q] + y * u[q]) + lz * tn[:, q:q + 1] for q in range(3)], dim=2)
+    origins = (tp + tn * bias)[:, None, :].expand(n, k, 3)
+    return origins.reshape(n * k, 3).contiguous(), dirs.reshape(n * k, 3).contiguous()
+
+
+def _occlusion_input(scenes, tp, tn, keys, k, reps, rounds=5):
+    """One input of the occlusion leg: n points, k directions, 8 rotations.  scenes: {"auto" | "lanes_1" | "lanes_8" | "lanes_64": handle}."""
+    import torch
+    import nrays_amd as nr
+    n = tp.shape[0]
+    L, rot = nr.hemisphere_dirs(k), nr.rotation_table(8)
+    tl, tr = torch.from_numpy(L).cuda(), torch.from_numpy(rot).cuda()
+    tk = torch.from_numpy(keys.astype(np.int64)).cuda()
+    ro, rd = _torch_occlusion_rays(tp, tn, L, rot, 1e-3, keys)
+    tmax = torch.full((n * k,), OCCLUSION_MAX_TOI, dtype=torch.float64, device="cuda")
+    sc = scenes["auto"]
+    lit, filt = nr.intersects_rays(sc, ro, rd, tmax)
+
+    def torch_fold():
+        f = filt.view(n, k, 3)
+        tot = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+        for j in range(k):
+            tot = tot + f[:, j]
+        return tot / float(k), lit.view(n, k).sum(dim=1)
+
+    fns = {"fused": lambda: nr.occlusion_points(sc, tp, tn, tl, tr, 1e-3, OCCLUSION_MAX_TOI, keys=tk),
+           "intersects_rays": lambda: nr.intersects_rays(sc, ro, rd, tmax),
+           "intersects_rays_unordered": lambda: nr.intersects_rays(sc, ro, rd, tmax, unordered=True),
+           "torch_fold": torch_fold}
+    for name, other in scenes.items():
+        if name != "auto":
+            fns["fused_" + name] = lambda other=other: nr.occlusion_points(other, tp, tn, tl, tr, 1e-3, OCCLUSION_MAX_TOI, keys=tk)
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=1))
+    got, (want_f, want_o) = nr.occlusion_points(sc, tp, tn, tl, tr, 1e-3, OCCLUSION_MAX_TOI, keys=tk), torch_fold()
+    row = {"points": int(n), "dirs": int(k), "rays": int(n * k), "max_toi": OCCLUSION_MAX_TOI, "rounds": rounds, "reps": reps, "open_share": round(float(lit.float().mean().item()), 4),
+           "points_that_differ_from_the_torch_fold": int(((got.filter != want_f).any(dim=1) | (got.open != want_o)).sum().item())}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    return row
+
+
+def _occlusion_leg(w, h, reps):
+    import torch
+    import nrays_amd as nr
+    from nrays_amd import math3d
+    from tools import standins
+    scenes = {}
+    for name, lanes in (("auto", None), ("lanes_1", "0"), ("lanes_8", "3"), ("lanes_64", "6")):
+        os.environ.pop("NRAYS_OCCLUSION_LANES", None)
+        if lanes is not None:
+            os.environ["NRAYS_OCCLUSION_LANES"] = lanes  # read when a handle is created
+        scenes[name], cam = standins.sponza_scene()
+        scenes[name].device_handle()
+    os.environ.pop("NRAYS_OCCLUSION_LANES", None)
+    proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
+    o, d, keys = nr.camera_rays((w, h), cam["eye"], proj)
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    hits = nr.closest_hits(scenes["auto"], to, td, want=("normal", "flags"))
+    hit = (hits.flags & 1) != 0
+    tp = (to + td * hits.toi[:, None])[hit].contiguous()
+    nm = hits.normal[hit]
+    tn = torch.where((((nm[:, 0] * td[hit][:, 0] + nm[:, 1] * td[hit][:, 1]) + nm[:, 2] * td[hit][:, 2]) > 0)[:, None], -nm, nm).contiguous()
+    keys = keys[hit.cpu().numpy()]
+    n = tp.shape[0]
+    sub = torch.from_numpy(np.linspace(0, n - 1, min(16384, n)).astype(np.int64)).cuda()
+    pick = lambda names: {k: scenes[k] for k in names}  # noqa: E731
+    return {"first_hits_16_dirs": _occlusion_input(pick(("auto", "lanes_1", "lanes_8")), tp, tn, keys, 16, max(1, reps // 4)),
+            "subset_16384_points_64_dirs": _occlusion_input(pick(("auto", "lanes_1", "lanes_8", "lanes_64")), tp[sub].contiguous(), tn[sub].contiguous(), keys[sub.cpu().numpy()], 64, reps)}
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trace_rays_rate.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="320x180 instead of 1920x1080 (a rehearsal of the tool, not a measurement)")
     ap.add_argument("--coherence", action="store_true", help="add the CPU coherence figures of every batch, as given and reordered")
@@ -213,7 +313,10 @@ def main():
     ap.add_argument("--cast", action="store_true", help="time the closest-hit rows of both scenes, nothing else")
     ap.add_argument("--shade", action="store_true", help="time shade_hits beside trace_rays and closest_hits on the sponza stand-in with 1 and 8 lights, nothing else")
     ap.add_argument("--beside", default=None, help="with --shade: the JSON of an earlier run (another library), copied into this one under 'beside'")
+    ap.add_argument("--occlusion", action="store_true", help="time occlusion_points beside intersects_rays on the same rays and the torch fold (leg e_sponza_occlusion), nothing else")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "occlusion_rate.json" if a.occlusion else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -226,6 +329,14 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.occlusion:
+        res["workloads"]["e_sponza_occlusion"] = _occlusion_leg(w, h, a.reps)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
 
     if a.shade:
         for name, lights in (("f_sponza_shade_hits_camera_rays", 1), ("f_sponza_8_lights_shade_hits_camera_rays", 8)):
