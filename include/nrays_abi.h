@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -401,6 +401,51 @@ int nrays_occlusion_points(NraysScene* scene, uint32_t n, const double* points, 
  * out_origins / out_dirs [(i * num_dirs + j) * 3 ..], n x num_dirs x 3 doubles each.  keys NULL: key i.  max_toi is checked and not used. */
 int nrays_debug_occlusion_rays(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint64_t* keys,
                                const NraysOcclusionParams* params, double* out_origins, double* out_dirs);
+
+/* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
+ * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and
+ * nrays_occlusion_points_device, which take the arrays written here unfiltered (out_node -> nodes, out_flags -> hit_flags, out_uv -> uvs); no
+ * host copy of the mesh, no rasteriser and no upload is needed.
+ * Every array holds width * height entries, lattice point (x, y) at index y * width + x; row 0 is the smallest v, the bottom row of NraysTexture.
+ * The result is defined exactly (f64 + - * /, sqrt and comparisons only, every expression evaluated left to right as written, nothing fused), so
+ * that a caller can restate it bit for bit (Python: nrays_amd.surface_texels_ref):
+ *   lattice    su = width > 1 ? x / (width - 1) : 0.0, sv likewise from y and height: the points where Texture2d::sample reads texel (x, y)
+ *              (texture2d.rs:225-233).  With NRAYS_TEXELS_CENTRES: su = (x + 0.5) / width, sv = (y + 0.5) / height.
+ *   triangle   t of the node's NraysMesh with uv corners A, B, C (f32 widened to f64): area2 = (B.u - A.u) * (C.v - A.v) - (B.v - A.v) * (C.u - A.u).
+ *              area2 == 0 or not finite: the triangle covers nothing.  s = area2 > 0 ? 1.0 : -1.0.
+ *   edge       E(P, Q) at (su, sv): order the endpoints so that (P.u, P.v) <= (Q.u, Q.v) lexicographically;
+ *              E = (Q.u - P.u) * (sv - P.v) - (Q.v - P.v) * (su - P.u); negated if the endpoints were swapped.  Two triangles that share an edge with
+ *              bit-identical uv endpoints get exactly opposite values: no lattice point falls between them (but see the box under `coverage`).
+ *   coverage   e0 = s * E(B, C), e1 = s * E(C, A), e2 = s * E(A, B), sum = (e0 + e1) + e2.  t covers the point iff (su, sv) lies in the triangle's uv
+ *              box (min / max of the corners per axis, compared exactly — in exact arithmetic no restriction at all; it is what lets the library
+ *              visit a triangle's own lattice points only) and e0 >= 0 && e1 >= 0 && e2 >= 0 && sum != 0.  Caveat: in f64 a point just OUTSIDE one
+ *              triangle's box may get a rounded edge value >= 0 on the shared edge while the neighbour, whose box holds it, gets the opposite value
+ *              < 0; such a point is then covered by neither.  It takes a point within a rounding of the edge's line and beyond the edge's own end.
+ *   winner     the covering triangle with the smallest index t, whatever order the device visits triangles in; the leaf references a pre-split
+ *              triangle has count as one triangle.  uvs are not wrapped: only triangles whose uvs reach a lattice point cover it.
+ *   record     w0 = e0 / sum, w1 = e1 / sum, w2 = e2 / sum; local point p = (a * w0 + b * w1) + c * w2 per component (a, b, c the corners);
+ *              world point R p + T with row k of R applied as (R[k][0] * p.x + R[k][1] * p.y) + R[k][2] * p.z — for a node whose axis_angle is zero
+ *              p + T, and p itself when the translation is zero too.  Normal: cross(b - a, c - a) / its norm (the normal a ray arriving from that side
+ *              gets from nrays_cast_rays), rotated by R the same way, negated with NRAYS_TEXELS_FLIP_NORMALS.  out_uv = (su, sv), the lattice point itself;
+ *              out_prim = t; out_node = node; out_flags = 3 (bit 0 covered, bit 1 the record carries a uv: the bits of NraysCastResult::flags).
+ *   uncovered  out_flags 0, out_node -1, out_prim -1, zeros elsewhere.
+ * out_points and out_flags are required; out_normals, out_uv, out_node and out_prim may each be NULL: a NULL output is not stored at all.
+ * NULL scene / out_points / out_flags, node >= the scene's node count, width or height outside 1 .. 16384, width * height > 2^24, an unknown
+ * flag bit -> NRAYS_ERR_BAD_ARG; a node that is not a NRAYS_SHAPE_TRIMESH, or whose mesh has no uvs -> NRAYS_ERR_UNSUPPORTED.  Otherwise the
+ * contract of nrays_cast_rays_device: every pointer DEVICE memory on the scene's device, enqueued on `hip_stream` without read-back or
+ * synchronisation, ordered behind the handle's previous work, workspace owned by the handle; what the handle reports about its renders and
+ * its per-camera scheduling state stay untouched. */
+#define NRAYS_TEXELS_CENTRES      1u  /* lattice (x + 0.5) / W instead of x / (W - 1) */
+#define NRAYS_TEXELS_FLIP_NORMALS 2u
+int nrays_surface_texels_device(NraysScene* scene, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals,
+                                double* out_uv, int32_t* out_node, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_surface_texels(NraysScene* scene, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals,
+                         double* out_uv, int32_t* out_node, int32_t* out_prim, uint32_t* out_flags, uint32_t flags);
+/* Timing probe: the two passes of nrays_surface_texels_device (owners: count, scan, one atomic per covering lane; resolve: the records) `repeats`
+ * times on a stream of the handle, between HIP events of their own; every output is written to scratch memory.  out_ms: repeats x 2 floats HOST
+ * memory, (owner pass, resolve pass) in milliseconds.  Blocking.  Statuses as above; repeats == 0 or NULL out_ms -> NRAYS_ERR_BAD_ARG. */
+int nrays_debug_surface_texels_passes(NraysScene* scene, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, uint32_t repeats, float* out_ms);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

@@ -339,6 +339,14 @@ pub struct CastHit {
     pub triangle: Option<usize>, // index of the triangle in its TriMesh; None for an analytic shape
 }
 
+/// One covered lattice point of `GpuScene::surface_texels`.
+pub struct SurfaceTexel {
+    pub point: Point3<f64>,
+    pub normal: Vector3<f64>,
+    pub uvs: Point2<f64>,
+    pub triangle: usize,
+}
+
 /// One surface point of `GpuScene::shade_points`: the arguments of `Material::compute` (src/material.rs:8-16) besides the scene.
 pub struct SurfacePoint {
     pub node: usize,              // index into scene.nodes(): selects the material
@@ -448,6 +456,34 @@ impl GpuScene {
                 triangle: if prim[i] >= 0 { Some(prim[i] as usize) } else { None },
             })
         }).collect())
+    }
+
+    /// The surface of TriMesh node `node` at the points of a `width` x `height` lattice in its uv space — a light map's texels (nrays_surface_texels,
+    /// blocking): per lattice point, row 0 = the smallest v, `None` where no triangle covers it, otherwise the world point, the world normal, the lattice
+    /// point's own (u, v) and the triangle's index in the node's mesh.  `centres`: the lattice (x + 0.5) / width instead of x / (width - 1), the points where
+    /// `Texture2d::sample` reads texel x.  The records are what `shade_points` and `occlusion_points` take: no mesh copy, rasteriser or upload on the host.
+    pub fn surface_texels(&self, node: usize, width: u32, height: u32, centres: bool, flip_normals: bool) -> Result<Vec<Option<SurfaceTexel>>, String> {
+        let n = width as usize * height as usize;
+        let (mut p, mut nm, mut uv) = (vec![0.0f64; 3 * n], vec![0.0f64; 3 * n], vec![0.0f64; 2 * n]);
+        let (mut prim, mut flags) = (vec![0i32; n], vec![0u32; n]);
+        let f = if centres { NRAYS_TEXELS_CENTRES } else { 0 } | if flip_normals { NRAYS_TEXELS_FLIP_NORMALS } else { 0 };
+        let rc = unsafe { nrays_surface_texels(self.raw, node as u32, width, height, p.as_mut_ptr(), nm.as_mut_ptr(), uv.as_mut_ptr(), ptr::null_mut(), prim.as_mut_ptr(), flags.as_mut_ptr(), f) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| if flags[i] & 1 == 0 { None } else {
+            Some(SurfaceTexel {
+                point: Point3::new(p[3 * i], p[3 * i + 1], p[3 * i + 2]), normal: Vector3::new(nm[3 * i], nm[3 * i + 1], nm[3 * i + 2]),
+                uvs: Point2::new(uv[2 * i], uv[2 * i + 1]), triangle: prim[i] as usize,
+            })
+        }).collect())
+    }
+
+    /// `surface_texels` into DEVICE memory (nrays_surface_texels_device), enqueued on `hip_stream` without synchronisation: out_points (n x 3 f64) and
+    /// out_flags (n u32) for n = width * height; out_normals (n x 3 f64), out_uv (n x 2 f64), out_node and out_prim (n i32) may each be null.  The arrays
+    /// pass unfiltered into `shade_points_device` (nodes, hit_flags, uvs) and `occlusion_points_device` (hit_flags).  `flags`: NRAYS_TEXELS_* bits.
+    pub unsafe fn surface_texels_device(&self, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32,
+                                        out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_surface_texels_device(self.raw, node, width, height, out_points, out_normals, out_uv, out_node, out_prim, out_flags, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
     }
 
     /// `cast_rays` for n rays in DEVICE memory (nrays_cast_rays_device), enqueued on `hip_stream` without synchronisation: origins / dirs n x 3 f64,

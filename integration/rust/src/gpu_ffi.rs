@@ -15,6 +15,8 @@ pub const NRAYS_ERR_QUEUE_OVERFLOW: c_int = -6;
 pub const NRAYS_ERR_RCCL: c_int = -7;
 /// flags of the `_ex` batch entry points: the rays come in no useful order, the library may trace them in an order of its own
 pub const NRAYS_RAYS_UNORDERED: u32 = 1;
+pub const NRAYS_TEXELS_CENTRES: u32 = 1;
+pub const NRAYS_TEXELS_FLIP_NORMALS: u32 = 2;
 
 // NraysShapeKind (examples/loader3d.rs:593-695)
 pub const NRAYS_SHAPE_BALL: u32 = 0;
@@ -249,6 +251,9 @@ extern "C" {
     pub fn nrays_occlusion_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_occlusion_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_occlusion_rays(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, keys: *const u64, params: *const NraysOcclusionParams, out_origins: *mut f64, out_dirs: *mut f64) -> c_int;
+    pub fn nrays_surface_texels_device(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_surface_texels(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_debug_surface_texels_passes(scene: *mut NraysScene, node: u32, width: u32, height: u32, flags: u32, repeats: u32, out_ms: *mut f32) -> c_int;
     pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;

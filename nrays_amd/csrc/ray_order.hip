@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -29,6 +29,7 @@
 #include "ray_batch_kernel.h"
 #include "ray_key.h"
 #include "scene_handle.h"
+#include "surface_texels_kernel.h"
 
 static_assert(NRAYS_RAY_FRAME_DOUBLES == nrays::kRayFrameDoubles, "include/nrays_abi.h and ray_key.h disagree on the frame");
 
@@ -270,7 +271,7 @@ void trace_workspace_release(NraysScene* sc) {
     if (!w) return;
     if (w->used) (void)hipStreamSynchronize(w->last_stream);
     for (int k = 0; k < 2; ++k) if (w->queue[k].block) (void)hipFree(w->queue[k].block);
-    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage, w->d_texel_owner, w->d_texel_off, (void*)w->d_texel_blocks}) if (q) (void)hipFree(q);
     ray_order_release(w);
     delete w;
     sc->tw = nullptr;
@@ -702,6 +703,154 @@ static int occlusion_rays_probe(NraysScene* sc, uint32_t n, const double* points
     return NRAYS_OK;
 }
 
+// ---- nrays_surface_texels*: the surface of a TriMesh node at the points of a lattice in uv space (surface_texels_kernel.h) -----------------------------------------
+constexpr uint32_t kTexelMaxSide = 16384u, kTexelMaxPoints = 1u << 24;
+static int check_texel_args(const NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, const TexelOutputs* out /* null: the caller has none (the probe) */, uint32_t flags) {
+    if (!sc || (out && (!out->points || !out->flags))) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (node >= sc->facts.host.surface.size()) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_surface_texels: no such node");
+    if (width < 1u || width > kTexelMaxSide || height < 1u || height > kTexelMaxSide || (uint64_t)width * height > kTexelMaxPoints)
+        return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_surface_texels: width and height must be in 1 .. 16384 and width * height <= 2^24");
+    if (flags & ~(uint32_t)(NRAYS_TEXELS_CENTRES | NRAYS_TEXELS_FLIP_NORMALS)) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_surface_texels: unknown flag");
+    const NodeSurface& s = sc->facts.host.surface[node];
+    if (!s.mesh) return set_last_error(NRAYS_ERR_UNSUPPORTED, "nrays_surface_texels: the node is not a TriMesh");
+    if (!s.has_uv) return set_last_error(NRAYS_ERR_UNSUPPORTED, "nrays_surface_texels: the node's mesh has no uvs");
+    return NRAYS_OK;
+}
+static int texel_workspace(TraceWorkspace* w, size_t points, size_t records) {
+    int rc = grow_device(&w->d_texel_owner, &w->texel_owner_words, points, sizeof(unsigned long long));
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_texel_off, &w->texel_off_words, std::max<size_t>(records, 1), sizeof(unsigned long long));
+    if (rc != NRAYS_OK) return rc;
+    if (!w->d_texel_blocks) HIP_TRY(hipMalloc((void**)&w->d_texel_blocks, (size_t)(kTexelMaxBlocks + 1u) * sizeof(unsigned long long)));
+    return NRAYS_OK;
+}
+// The owner pass of one call: memset, count, scan, items.  Launches only; texel_workspace() has run.
+static int texel_owner_pass(NraysScene* sc, TraceWorkspace* w, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, hipStream_t stream) {
+    const NodeSurface& s = sc->facts.host.surface[node];
+    const TexelLattice L{width, height, (flags & NRAYS_TEXELS_CENTRES) ? 1u : 0u, node};
+    unsigned long long* owner = (unsigned long long*)w->d_texel_owner; unsigned long long* off = (unsigned long long*)w->d_texel_off;
+    HIP_TRY(hipMemsetAsync(owner, 0xff, (size_t)width * height * sizeof(unsigned long long), stream));
+    if (s.count == 0u) return NRAYS_OK;
+    if (s.count > kTexelMaxRecords) return set_last_error(NRAYS_ERR_UNSUPPORTED, "nrays_surface_texels: too many triangle records");
+    const uint32_t rec_grid = (s.count + kTexelBlock - 1u) / kTexelBlock, scan_grid = (s.count + kTexelScanBlock - 1u) / kTexelScanBlock;
+    unsigned long long* total = w->d_texel_blocks + kTexelMaxBlocks;
+    hipLaunchKernelGGL(k_texel_count, dim3(rec_grid), dim3(kTexelBlock), 0, stream, sc->facts.d.tris, sc->facts.d.triuvs, s.first, s.count, L, off);
+    hipLaunchKernelGGL(k_texel_sums, dim3(scan_grid), dim3(kTexelBlock), 0, stream, (const unsigned long long*)off, s.count, w->d_texel_blocks);
+    hipLaunchKernelGGL(k_texel_scan, dim3(1), dim3(1024), 0, stream, w->d_texel_blocks, scan_grid, total);
+    hipLaunchKernelGGL(k_texel_apply, dim3(scan_grid), dim3(kTexelBlock), 0, stream, off, s.count, (const unsigned long long*)w->d_texel_blocks);
+    hipLaunchKernelGGL(k_texel_owner, dim3((uint32_t)sc->facts.num_cus * kTexelOwnerWgsPerCu), dim3(kTexelBlock), 0, stream, sc->facts.d.tris, sc->facts.d.triuvs, s.first, s.count, L,
+                       (const unsigned long long*)off, (const unsigned long long*)total, owner);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_texel_owner: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+static int texel_resolve_pass(NraysScene* sc, TraceWorkspace* w, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, const TexelOutputs& out, hipStream_t stream) {
+    const NodeSurface& s = sc->facts.host.surface[node];
+    const TexelLattice L{width, height, (flags & NRAYS_TEXELS_CENTRES) ? 1u : 0u, node};
+    TexelXform X;
+    for (int k = 0; k < 9; ++k) X.m.r[k] = s.rot[k];
+    X.m.t.x = s.trans[0]; X.m.t.y = s.trans[1]; X.m.t.z = s.trans[2];
+    X.flags = s.flags; X.flip = (flags & NRAYS_TEXELS_FLIP_NORMALS) ? 1u : 0u;
+    hipLaunchKernelGGL(k_texel_resolve, dim3((width * height + kTexelBlock - 1u) / kTexelBlock), dim3(kTexelBlock), 0, stream, sc->facts.d.tris, sc->facts.d.triuvs, L, X,
+                       (const unsigned long long*)w->d_texel_owner, out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_texel_resolve: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+
+static int surface_texels_device_impl(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, const TexelOutputs& out, uint32_t flags, hipStream_t stream) {
+    { const int rc = check_texel_args(sc, node, width, height, &out, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = texel_workspace(w, (size_t)width * height, sc->facts.host.surface[node].count);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    rc = texel_owner_pass(sc, w, node, width, height, flags, stream);
+    if (rc == NRAYS_OK) rc = texel_resolve_pass(sc, w, node, width, height, flags, out, stream);
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form, through the workspace's staging buffer as cast_rays_host_impl.  A staged lattice point takes kTexelStageBytes: point, normal (3 f64), uv (2 f64),
+// node, prim, flags (32 bits) — the 8-byte fields first.
+constexpr size_t kTexelStageBytes = 76;
+static TexelOutputs texel_stage(void* block, size_t n, const TexelOutputs* want /* null: every output */) {
+    TexelOutputs s; s.points = (double*)block; s.normals = s.points + 3 * n; s.uv = s.normals + 3 * n;
+    s.node = (int32_t*)(s.uv + 2 * n); s.prim = s.node + n; s.flags = (uint32_t*)(s.prim + n);
+    if (want && !want->normals) s.normals = nullptr;
+    if (want && !want->uv) s.uv = nullptr;
+    if (want && !want->node) s.node = nullptr;
+    if (want && !want->prim) s.prim = nullptr;
+    return s;
+}
+static int surface_texels_host_impl(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, const TexelOutputs& out, uint32_t flags) {
+    { const int rc = check_texel_args(sc, node, width, height, &out, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    const size_t n = (size_t)width * height;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = texel_workspace(w, n, sc->facts.host.surface[node].count);
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_stage, &w->stage_rays, (n * kTexelStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const TexelOutputs s = texel_stage(w->d_stage, n, &out);
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    rc = texel_owner_pass(sc, w, node, width, height, flags, stream);
+    if (rc == NRAYS_OK) rc = texel_resolve_pass(sc, w, node, width, height, flags, s, stream);
+    if (rc == NRAYS_OK) {
+        auto down = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess; };
+        hipError_t e = down(out.points, s.points, n * 24);
+        if (e == hipSuccess) e = down(out.normals, s.normals, n * 24);
+        if (e == hipSuccess) e = down(out.uv, s.uv, n * 16);
+        if (e == hipSuccess) e = down(out.node, s.node, n * 4);
+        if (e == hipSuccess) e = down(out.prim, s.prim, n * 4);
+        if (e == hipSuccess) e = down(out.flags, s.flags, n * 4);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("surface texels read-back: ") + hipGetErrorString(e));
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// nrays_debug_surface_texels_passes: the two passes of nrays_surface_texels_device between events of their own, `repeats` times, into the staging buffer (a timing probe).
+static int surface_texels_passes_probe(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, uint32_t repeats, float* out_ms) {
+    { const int rc = check_texel_args(sc, node, width, height, nullptr, flags); if (rc != NRAYS_OK) return rc; }
+    if (!out_ms || repeats == 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    const size_t n = (size_t)width * height;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = texel_workspace(w, n, sc->facts.host.surface[node].count);
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_stage, &w->stage_rays, (n * kTexelStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const TexelOutputs s = texel_stage(w->d_stage, n, nullptr); // (every output)
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 3 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+    for (uint32_t r = 0; r < repeats && rc == NRAYS_OK && e == hipSuccess; ++r) {
+        e = hipEventRecord(ev[0], stream);
+        rc = texel_owner_pass(sc, w, node, width, height, flags, stream);
+        if (e == hipSuccess) e = hipEventRecord(ev[1], stream);
+        if (rc == NRAYS_OK) rc = texel_resolve_pass(sc, w, node, width, height, flags, s, stream);
+        if (e == hipSuccess) e = hipEventRecord(ev[2], stream);
+        if (e == hipSuccess) e = hipEventSynchronize(ev[2]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&out_ms[2 * r], ev[0], ev[1]);
+        if (e == hipSuccess) e = hipEventElapsedTime(&out_ms[2 * r + 1], ev[1], ev[2]);
+    }
+    (void)hipStreamSynchronize(stream);
+    for (int k = 0; k < 3; ++k) if (ev[k]) (void)hipEventDestroy(ev[k]);
+    batch_end(sc, w, stream);
+    if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_surface_texels_passes: ") + hipGetErrorString(e));
+    return rc;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -862,6 +1011,18 @@ int nrays_occlusion_points(NraysScene* sc, uint32_t n, const double* points, con
 int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* params,
                                double* out_origins, double* out_dirs) {
     return occlusion_rays_probe(sc, n, points, normals, keys, params, out_origins, out_dirs);
+}
+
+int nrays_surface_texels_device(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,
+                                int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream) {
+    return surface_texels_device_impl(sc, node, width, height, TexelOutputs{out_points, out_normals, out_uv, out_node, out_prim, out_flags}, flags, (hipStream_t)hip_stream);
+}
+int nrays_surface_texels(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,
+                         int32_t* out_prim, uint32_t* out_flags, uint32_t flags) {
+    return surface_texels_host_impl(sc, node, width, height, TexelOutputs{out_points, out_normals, out_uv, out_node, out_prim, out_flags}, flags);
+}
+int nrays_debug_surface_texels_passes(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, uint32_t repeats, float* out_ms) {
+    return surface_texels_passes_probe(sc, node, width, height, flags, repeats, out_ms);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

@@ -556,6 +556,17 @@ int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out
         out.reflection_generations = k;
     }
 
+    out.surface.assign(d->num_nodes, NodeSurface());
+    for (uint32_t i = 0; i < d->num_nodes; ++i) {
+        const NraysNode& n = d->nodes[i];
+        NodeSurface& s = out.surface[i];
+        s.mesh = n.shape_kind == NRAYS_SHAPE_TRIMESH; s.has_uv = s.mesh && info[i].has_uv;
+        for (int k = 0; k < 9; ++k) s.rot[k] = info[i].R[k];
+        for (int k = 0; k < 3; ++k) s.trans[k] = n.translation[k];
+        s.flags = info[i].identity ? kInstIdentityRot : 0u;
+        if (info[i].identity && n.translation[0] == 0.0 && n.translation[1] == 0.0 && n.translation[2] == 0.0) s.flags |= kInstNoXform;
+    }
+
     std::vector<Instance> cinst, sinst, planes_c, planes_s;
     std::vector<PrimBounds> cbox, sbox;
 
@@ -610,7 +621,10 @@ int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out
         const std::vector<uint32_t>& ids = groups[key];
         uint32_t n0 = ids[0];
         auto add = [&](const std::vector<uint32_t>& sub, bool closest, bool shadow, bool anyhit, const Blas* reuse, Blas& blas) -> int {
+            const size_t dev0 = out.dev_tris, host0 = out.tris.size();
             if (!reuse) { int rc = append_blas(d, sw, sub, out, blas, err); if (rc != NRAYS_OK) return rc; } else blas = *reuse;
+            if (closest && !reuse) // the records of this BLAS: where nrays_surface_texels* finds the triangles of its nodes (host-built ranges move behind the device-built ones below)
+                for (uint32_t ni : sub) { NodeSurface& s = out.surface[ni]; s.device_built = blas.device; s.first = (uint32_t)(blas.device ? dev0 : host0); s.count = (uint32_t)(blas.device ? out.dev_tris - dev0 : out.tris.size() - host0); }
             if (!reuse && sub.size() == 1 && blas.device) single_bounds[sub[0]] = std::array<float, 6>{blas.mn[0], blas.mn[1], blas.mn[2], blas.mx[0], blas.mx[1], blas.mx[2]};
             Instance in = base_instance(n0);
             in.flags &= ~(uint32_t)kInstSolid; // TriMesh ignores `solid` (SURVEY B-8)
@@ -694,6 +708,7 @@ int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out
                 if (in.flags & kInstDeviceTmp) in.flags &= ~(uint32_t)kInstDeviceTmp; else in.blas_root = rebase_ref(in.blas_root, dn, dt);
             }
         if (out.tris.size() + out.dev_tris >= (1u << 28)) { err = "too many triangles"; return NRAYS_ERR_UNSUPPORTED; }
+        for (NodeSurface& s : out.surface) if (!s.device_built) s.first += dt;
     }
     out.instances.swap(cinst);
     out.shadow_instances.swap(sinst);

@@ -16,6 +16,15 @@ struct HostTexture {
     std::vector<uint8_t> bytes;   // copy of the texel data
 };
 
+// Where the surface of a TriMesh node lies in the flattened scene (nrays_surface_texels*, ray_order.hip): the leaf-ordered records of the closest-hit BLAS that
+// holds it — a BLAS may merge several nodes (TriRec::node_id tells them apart) and may hold a triangle several times after pre-splitting — and its isometry.
+struct NodeSurface {
+    uint32_t first = 0, count = 0; // records [first, first + count) of DScene::tris / triuvs; count 0: a mesh without triangles
+    bool mesh = false, has_uv = false, device_built = false;
+    uint32_t flags = 0;            // kInstIdentityRot, kInstNoXform
+    double rot[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, trans[3] = {0, 0, 0};
+};
+
 struct HostScene {
     // BLASes built on the device (bvh_device.hip) occupy the FIRST dev_nodes / dev_tris entries of the scene's node / triangle arrays,
     // in the order of dev_blas; the host-built arrays below follow them (their refs are shifted when the scene is complete).
@@ -32,6 +41,7 @@ struct HostScene {
     std::vector<ShadeRec> shade;             // per node; texel pointers patched after the texture upload
     std::vector<int32_t> shade_tex, shade_alpha_tex; // texture indices behind shade[i].tex / alpha_tex (-1 = none)
     std::vector<double> node_aabbs;          // 6 per node (mins, maxs), reference arithmetic
+    std::vector<NodeSurface> surface;        // per node
     std::vector<MaterialRec> materials;
     std::vector<HostTexture> textures;
     std::vector<LightRec> lights;

@@ -43,3 +43,19 @@ def inverse_projection(eye, at, fovy_deg, resx, resy, znear=1.0, zfar=100000.0):
 def column_major16(m):
     """nalgebra stores Matrix4 column-major; the ABI takes that layout."""
     return np.ascontiguousarray(np.asarray(m, dtype=np.float64).T).reshape(16)
+
+
+def rotation_from_axis_angle(axis_angle):
+    """The rotation matrix of Isometry3::new(_, axis_angle) (a scaled-axis rotation, through its unit quaternion) exactly as the library builds it for a
+    scene node: (3, 3) float64, row-major, local -> world; the identity for a zero vector.  sin and cos are two separate libm calls, as in the library."""
+    w = [float(x) for x in axis_angle]
+    angle = math.sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2])
+    if angle == 0.0:
+        return np.eye(3, dtype=np.float64)
+    s, qw = math.sin(angle / 2.0), math.cos(angle / 2.0)
+    qi, qj, qk = w[0] / angle * s, w[1] / angle * s, w[2] / angle * s
+    ww, ii, jj, kk = qw * qw, qi * qi, qj * qj, qk * qk
+    ij, wk, wj, ik, jk, wi = qi * qj * 2.0, qw * qk * 2.0, qw * qj * 2.0, qi * qk * 2.0, qj * qk * 2.0, qw * qi * 2.0
+    return np.array([[ww + ii - jj - kk, ij - wk, wj + ik],
+                     [wk + ij, ww - ii + jj - kk, jk - wi],
+                     [ik - wj, wi + jk, ww - ii - jj + kk]], dtype=np.float64)

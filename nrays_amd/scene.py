@@ -376,6 +376,14 @@ class Scene:
         """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
 
+    def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
+        """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
+        return surface_texels(self, node, width, height, centres, flip_normals, want, device)
+
+    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+        """A light map of mesh node `node`: bake_lightmap(self, node, ...)."""
+        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device)
+
     def _release(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)
@@ -926,6 +934,176 @@ def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias
     facing = (nm[:, 0] * dirs[:, 0] + nm[:, 1] * dirs[:, 1]) + nm[:, 2] * dirs[:, 2]
     normals = where((facing > 0)[:, None], -nm, nm)
     return occlusion_points(scene, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags=hits.flags, keys=keys)
+
+
+# ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------
+
+TEXEL_OUTPUTS = ("normals", "uv", "node", "prim")  # the optional outputs of surface_texels, in the order of nrays_surface_texels_device's arguments
+SurfaceTexels = collections.namedtuple("SurfaceTexels", ("points",) + TEXEL_OUTPUTS + ("flags",))
+TEXELS_MAX_SIDE, TEXELS_MAX_POINTS = 16384, 1 << 24
+
+
+def _texel_lattice(width, height):
+    width, height = int(width), int(height)
+    if not (1 <= width <= TEXELS_MAX_SIDE and 1 <= height <= TEXELS_MAX_SIDE and width * height <= TEXELS_MAX_POINTS):
+        raise ValueError("width and height must be in 1 .. %d and width * height <= 2^24, got %d x %d" % (TEXELS_MAX_SIDE, width, height))
+    return width, height
+
+
+def texel_coords(n, centres=False):
+    """The n lattice coordinates of one axis of surface_texels: x / (n - 1), where Texture2d::sample reads texel x (0.0 for n == 1), or the usual texel
+    centres (x + 0.5) / n.  float64, one correctly rounded division each."""
+    x = np.arange(n, dtype=np.float64)
+    if centres:
+        return (x + 0.5) / float(n)
+    return x / float(n - 1) if n > 1 else np.zeros(1, dtype=np.float64)
+
+
+def _texel_edge(pu, pv, qu, qv, su, sv):
+    swapped = qu < pu or (qu == pu and qv < pv)
+    if swapped:
+        pu, pv, qu, qv = qu, qv, pu, pv
+    e = (qu - pu) * (sv - pv) - (qv - pv) * (su - pu)
+    return -e if swapped else e
+
+
+def surface_texels_ref(points, indices, uvs, transform, width, height, centres=False, flip_normals=False, node=0, with_weights=False):
+    """The numpy mirror of nrays_surface_texels_device's definition (include/nrays_abi.h), bit for bit: what surface_texels() returns for a scene node `node`
+    whose geometry is TriMesh(points, indices, uvs) (coordinates and uvs exactly representable in float32, as a scene requires) under the Isometry3
+    `transform` (None: the identity; the rotation is math3d.rotation_from_axis_angle's).  Every operation is a float64 + - * /, sqrt or comparison in the
+    order the header writes it.  Returns SurfaceTexels of numpy arrays (flags uint32); with_weights=True: (texels, (n, 3) float64 barycentric weights
+    w0, w1, w2, zeros where uncovered)."""
+    from . import math3d
+    width, height = _texel_lattice(width, height)
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    I = np.asarray(indices).reshape(-1, 3).astype(np.int64)
+    UV = np.asarray(uvs, dtype=np.float64).reshape(-1, 2)
+    su, sv = texel_coords(width, centres), texel_coords(height, centres)
+    n = width * height
+    owner = np.full((height, width), -1, dtype=np.int64)
+    pts, nrm, wts = np.zeros((height, width, 3)), np.zeros((height, width, 3)), np.zeros((height, width, 3))
+    axis_angle = (0.0, 0.0, 0.0) if transform is None else tuple(transform.axis_angle)
+    trans = (0.0, 0.0, 0.0) if transform is None else tuple(transform.translation)
+    identity = axis_angle == (0.0, 0.0, 0.0)
+    noxform = identity and trans == (0.0, 0.0, 0.0)
+    R = math3d.rotation_from_axis_angle(axis_angle)
+    rot = lambda x, y, z: [(float(R[k, 0]) * x + float(R[k, 1]) * y) + float(R[k, 2]) * z for k in range(3)]  # noqa: E731
+    with np.errstate(all="ignore"):
+        for t in range(len(I)):
+            (au, av), (bu, bv), (cu, cv) = ((float(UV[v, 0]), float(UV[v, 1])) for v in I[t])
+            area2 = np.float64(bu - au) * np.float64(cv - av) - np.float64(bv - av) * np.float64(cu - au)
+            if area2 == 0.0 or not np.isfinite(area2):
+                continue
+            # the lattice points inside the triangle's uv box, by exact comparisons (the coordinates of an axis ascend)
+            x0, x1 = int(np.searchsorted(su, min(au, bu, cu), "left")), int(np.searchsorted(su, max(au, bu, cu), "right"))
+            y0, y1 = int(np.searchsorted(sv, min(av, bv, cv), "left")), int(np.searchsorted(sv, max(av, bv, cv), "right"))
+            if x0 >= x1 or y0 >= y1:
+                continue
+            s = 1.0 if area2 > 0.0 else -1.0
+            gu, gv = su[None, x0:x1], sv[y0:y1, None]
+            e0, e1, e2 = s * _texel_edge(bu, bv, cu, cv, gu, gv), s * _texel_edge(cu, cv, au, av, gu, gv), s * _texel_edge(au, av, bu, bv, gu, gv)
+            total = (e0 + e1) + e2
+            win = (e0 >= 0.0) & (e1 >= 0.0) & (e2 >= 0.0) & (total != 0.0) & (owner[y0:y1, x0:x1] < 0)  # (ascending t: the smallest covering index wins)
+            if not win.any():
+                continue
+            w0, w1, w2 = (e0 / total)[win], (e1 / total)[win], (e2 / total)[win]
+            a, b, c = (P[v] for v in I[t])
+            p = [(float(a[k]) * w0 + float(b[k]) * w1) + float(c[k]) * w2 for k in range(3)]
+            ab, ac = [float(b[k]) - float(a[k]) for k in range(3)], [float(c[k]) - float(a[k]) for k in range(3)]
+            cr = [ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]]
+            norm = np.sqrt(np.float64(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]))
+            nm = [float(np.float64(x) / norm) for x in cr]
+            if not noxform:
+                if identity:
+                    p = [p[k] + trans[k] for k in range(3)]
+                else:
+                    p = [q + trans[k] for k, q in enumerate(rot(*p))]
+                    nm = rot(*nm)
+            if flip_normals:
+                nm = [-x for x in nm]
+            own = owner[y0:y1, x0:x1]; own[win] = t
+            for k in range(3):
+                pts[y0:y1, x0:x1, k][win] = p[k]
+                nrm[y0:y1, x0:x1, k][win] = nm[k]
+            wts[y0:y1, x0:x1, 0][win], wts[y0:y1, x0:x1, 1][win], wts[y0:y1, x0:x1, 2][win] = w0, w1, w2
+    covered = (owner >= 0).reshape(n)
+    uv = np.stack(np.broadcast_arrays(su[None, :], sv[:, None]), axis=-1).reshape(n, 2) * covered[:, None]
+    out = SurfaceTexels(points=pts.reshape(n, 3), normals=nrm.reshape(n, 3), uv=np.ascontiguousarray(uv), node=np.where(covered, int(node), -1).astype(np.int32),
+                        prim=owner.reshape(n).astype(np.int32), flags=np.where(covered, 3, 0).astype(np.uint32))
+    return (out, wts.reshape(n, 3)) if with_weights else out
+
+
+def surface_texels(scene, node, width, height, centres=False, flip_normals=False, want=TEXEL_OUTPUTS, device=None):
+    """The surface of TriMesh node `node` of the scene at the points of a width x height lattice in its uv space — a light map's texels — through
+    nrays_surface_texels_device / nrays_surface_texels: per lattice point the triangle that owns it, the world point and normal there.  The baker's first
+    step: the arrays pass unfiltered into shade_points (nodes=node, hit_flags=flags, uvs=uv) and occlusion_points (hit_flags=flags); bake_lightmap() does.
+    Also `scene.surface_texels(node, ...)` on Scene and FileScene.  surface_texels_ref() restates the result bit for bit.
+    Lattice point (x, y) is entry y * width + x and lies at u = x / (width - 1), v = y / (height - 1) — where the scene's own Texture2d::sample reads texel
+    (x, y); row 0 is the smallest v, the bottom row of a texture.  `centres=True`: u = (x + 0.5) / width instead.  A point on a shared edge goes to the
+    triangle with the smaller index; none falls between two triangles whose edge has the same uv endpoints.  uvs are not wrapped into [0, 1].
+    `want`: which of "normals", "uv", "node", "prim" to compute into memory.  Returns SurfaceTexels(points (n, 3) f64, normals (n, 3) f64 (negated with
+    flip_normals), uv (n, 2) f64 — the lattice point —, node (n,) i32, prim (n,) i32 — the triangle's index in its mesh —, flags (n,): 3 where covered),
+    None for what was not wanted.  An uncovered point has flags 0, node -1, prim -1 and zeros.
+    `device=None` -> nrays_surface_texels (blocking), numpy arrays (flags uint32).  `device`: a torch device of the scene's GPU -> nrays_surface_texels_device
+    on torch.cuda.current_stream(), tensors there (flags int32)."""
+    width, height = _texel_lattice(width, height)
+    node = int(node)
+    if node < 0:
+        raise ValueError("node must be >= 0")
+    want = tuple(want)
+    for name in want:
+        if name not in TEXEL_OUTPUTS:
+            raise ValueError("want: unknown output %r (one of %s)" % (name, ", ".join(TEXEL_OUTPUTS)))
+    flags = (abi.TEXELS_CENTRES if centres else 0) | (abi.TEXELS_FLIP_NORMALS if flip_normals else 0)
+    n = width * height
+    shapes = {"points": (n, 3), "normals": (n, 3), "uv": (n, 2), "node": (n,), "prim": (n,), "flags": (n,)}
+    wanted = lambda k: k in ("points", "flags") or k in want  # noqa: E731
+    if device is not None:
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("device must be a GPU, got %s" % device)
+        dtypes = {"points": torch.float64, "normals": torch.float64, "uv": torch.float64, "node": torch.int32, "prim": torch.int32, "flags": torch.int32}
+        out = {k: torch.empty(shapes[k], dtype=dtypes[k], device=device) if wanted(k) else None for k in SurfaceTexels._fields}
+        ptr = lambda x: None if x is None else x.data_ptr()  # noqa: E731
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(device):
+            abi.check(lib.nrays_surface_texels_device(scene.device_handle(), node, width, height, *[ptr(out[k]) for k in SurfaceTexels._fields], flags,
+                                                      torch.cuda.current_stream().cuda_stream))
+        return SurfaceTexels(**out)
+    dtypes = {"points": np.float64, "normals": np.float64, "uv": np.float64, "node": np.int32, "prim": np.int32, "flags": np.uint32}
+    ctypes_of = {np.float64: C.c_double, np.int32: C.c_int32, np.uint32: C.c_uint32}
+    out = {k: np.empty(shapes[k], dtype=dtypes[k]) if wanted(k) else None for k in SurfaceTexels._fields}
+    ptr = lambda a, ct: None if a is None else a.ctypes.data_as(C.POINTER(ct))  # noqa: E731
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_surface_texels(scene.device_handle(), node, width, height, *[ptr(out[k], ctypes_of[dtypes[k]]) for k in SurfaceTexels._fields], flags))
+    return SurfaceTexels(**out)
+
+
+def surface_texels_passes(scene, node, width, height, centres=False, flip_normals=False, repeats=1):
+    """Timing probe (nrays_debug_surface_texels_passes): the owner pass and the resolve pass of surface_texels, `repeats` times between events of their own.
+    (repeats, 2) float32, milliseconds."""
+    width, height = _texel_lattice(width, height)
+    ms = np.zeros((int(repeats), 2), dtype=np.float32)
+    flags = (abi.TEXELS_CENTRES if centres else 0) | (abi.TEXELS_FLIP_NORMALS if flip_normals else 0)
+    abi.check(abi.load_hip_lib().nrays_debug_surface_texels_passes(scene.device_handle(), int(node), width, height, flags, int(repeats), ms.ctypes.data_as(C.POINTER(C.c_float))))
+    return ms
+
+
+def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+    """A light map of TriMesh node `node`: the direct lighting of its surface at the texels of a width x height map, (height, width, 4) float32 in
+    NraysTexture row order (row 0 = the bottom row): shade_points() on surface_texels(), viewed against the normal (view_dirs = -normals), rgb = the lit
+    colour, a = the material's alpha.  `occlusion=(sample_dirs, rotations, bias, max_toi)`: rgb is multiplied by the mean filter of occlusion_points() with
+    these arguments at the same texels.  Uncovered texels are zeros.  `keys` (width * height,) RNG keys for area lights and the occlusion rotations
+    (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, three calls on one stream; `keys` and
+    the tables are then tensors (the tables may be anything numpy takes).  Also `scene.bake_lightmap(node, ...)` on Scene and FileScene."""
+    tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals", "uv", "node"), device=device)
+    rgba = shade_points(scene, tx.points, tx.normals, -tx.normals, tx.node, uvs=tx.uv, hit_flags=tx.flags, keys=keys)
+    if occlusion is not None:
+        sample_dirs, rotations, bias, max_toi = occlusion
+        occ = occlusion_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, max_toi, hit_flags=tx.flags, keys=keys)
+        rgba[:, :3] = rgba[:, :3] * occ.filter
+    return rgba.reshape(int(height), int(width), 4)
 
 
 def ray_order(scene, origins, dirs):

@@ -113,6 +113,16 @@ class FileScene:
         from .scene import occlusion_points
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
 
+    def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
+        """The surface of mesh node `node` at a light map's texels: scene.surface_texels(self, node, ...)."""
+        from .scene import surface_texels
+        return surface_texels(self, node, width, height, centres, flip_normals, want, device)
+
+    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+        """A light map of mesh node `node`: scene.bake_lightmap(self, node, ...)."""
+        from .scene import bake_lightmap
+        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device)
+
     def close(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)

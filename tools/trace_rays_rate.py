@@ -33,7 +33,12 @@ beside what the library offered before on the very same rays — the rays of the
 and with unordered=True, and the torch fold of the per-ray results, timed apart — and beside itself on handles forced to one lane per point and to 8 / 64 lanes
 per point (NRAYS_OCCLUSION_LANES).  Alternating rounds, each of a few launches between events: min, median and max of every leg.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion]
+--texels times, and nothing else, the leg g_surface_texels: surface_texels() (nrays_surface_texels_device) of a grid mesh of about 500 k triangles with an atlas
+of its own at 1024^2 and 4096^2 lattice points, and of a two-triangle quad at 4096^2 (one triangle = half the atlas: the owner pass must not care) — the whole call,
+its owner and resolve passes between events of their own (nrays_debug_surface_texels_passes), shade_points() on the same texels, and for the 1024^2 lattice of the
+grid the numpy mirror surface_texels_ref() on the host, which is what a caller without the entry point does (plus the upload, not counted).
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--texels]
 """
 import argparse
 import ctypes as C
@@ -303,6 +308,50 @@ def _occlusion_leg(w, h, reps):
             "subset_16384_points_64_dirs": _occlusion_input(pick(("auto", "lanes_1", "lanes_8", "lanes_64")), tp[sub].contiguous(), tn[sub].contiguous(), keys[sub.cpu().numpy()], 64, reps)}
 
 
+def _texels_row(sc, mesh, size, reps, mirror, rounds=5):
+    import torch
+    import nrays_amd as nr
+    w, h = size
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tx = nr.surface_texels(sc, 0, w, h, want=("normals", "uv", "node"), device=dev)
+    view = -tx.normals
+    fns = {"surface_texels": lambda: nr.surface_texels(sc, 0, w, h, want=("normals", "uv", "node"), device=dev),
+           "shade_points": lambda: nr.shade_points(sc, tx.points, tx.normals, view, tx.node, uvs=tx.uv, hit_flags=tx.flags)}
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):  # alternating rounds, each timed by events around `reps` launches after a warm-up
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=2))
+    nr.surface_texels_passes(sc, 0, w, h, repeats=3)
+    passes = nr.surface_texels_passes(sc, 0, w, h, repeats=rounds * reps)
+    row = {"triangles": int(len(mesh[1])), "lattice": [w, h], "points": w * h, "covered_share": round(float((tx.flags != 0).float().mean().item()), 4), "rounds": rounds, "reps": reps}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    for k, name in enumerate(("owner_pass", "resolve_pass")):
+        row[name] = {"ms": round(float(np.median(passes[:, k])), 4), "min_ms": round(float(passes[:, k].min()), 4), "max_ms": round(float(passes[:, k].max()), 4)}
+    if mirror:
+        t0 = time.perf_counter()
+        ref = nr.surface_texels_ref(mesh[0], mesh[1], mesh[2], None, w, h)
+        row["numpy_mirror_host"] = {"ms": round((time.perf_counter() - t0) * 1e3, 1), "runs": 1}
+        row["points_that_differ_from_the_mirror"] = int((tx.flags.cpu().numpy().astype(np.uint32) != ref.flags).sum() + (tx.points.cpu().numpy() != ref.points).any(axis=1).sum())
+    return row
+
+
+def _texels_leg(reps, quick):
+    import nrays_amd as nr
+    from tools import scenes_util as su
+    from tools import standins
+    n = 64 if quick else 500
+    p, uv, idx = standins._surface(lambda u, v: np.stack([8.0 * u - 4.0, 0.5 * np.sin(6.0 * u) * np.cos(5.0 * v), 8.0 * v - 4.0], -1), n, n)  # 2 n^2 triangles, the atlas = the unit square
+    grid = (su.f32_exact(p), idx, su.f32_exact(uv))
+    quad = (su.f32_exact([[-4, 0, -4], [4, 0, -4], [4, 0, 4], [-4, 0, 4]]), np.asarray([[0, 2, 1], [0, 3, 2]], np.uint32), su.f32_exact([[0, 0], [1, 0], [1, 1], [0, 1]]))
+    mat = nr.PhongMaterial((0.2, 0.2, 0.2), (0.9, 0.9, 0.9), (0.5, 0.5, 0.5), su.checker_texture(64, 8), None, 40.0)
+    scene = lambda m: nr.Scene([nr.SceneNode(mat, 0.0, 0.0, 1.0, 1.0, nr.Isometry3(), nr.TriMesh(*m[:2], m[2]))], [nr.Light((1.0, 6.0, -2.0), 0.0, 1, (1.0, 1.0, 1.0))], (0, 0, 0))  # noqa: E731
+    small, large = ((128, 128), (512, 512)) if quick else ((1024, 1024), (4096, 4096))
+    sg, sq = scene(grid), scene(quad)
+    return {"grid_small_lattice": _texels_row(sg, grid, small, reps, True), "grid_large_lattice": _texels_row(sg, grid, large, max(1, reps // 4), False),
+            "quad_large_lattice": _texels_row(sq, quad, large, max(1, reps // 4), False)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json")
@@ -314,9 +363,10 @@ def main():
     ap.add_argument("--shade", action="store_true", help="time shade_hits beside trace_rays and closest_hits on the sponza stand-in with 1 and 8 lights, nothing else")
     ap.add_argument("--beside", default=None, help="with --shade: the JSON of an earlier run (another library), copied into this one under 'beside'")
     ap.add_argument("--occlusion", action="store_true", help="time occlusion_points beside intersects_rays on the same rays and the torch fold (leg e_sponza_occlusion), nothing else")
+    ap.add_argument("--texels", action="store_true", help="time surface_texels, its two passes, shade_points on its texels and the numpy mirror (leg g_surface_texels), nothing else")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "occlusion_rate.json" if a.occlusion else "trace_rays_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -329,6 +379,14 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.texels:
+        res["workloads"]["g_surface_texels"] = _texels_leg(a.reps, a.quick)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
 
     if a.occlusion:
         res["workloads"]["e_sponza_occlusion"] = _occlusion_leg(w, h, a.reps)
