@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -525,6 +525,12 @@ int nrays_debug_scene_flags(const NraysScene* scene, uint32_t out[2]);
  * render (sample batches; 0 = no render yet, or the staged path rendered the frame: out[0..3] are then 0); out[5] = 1 when those
  * launches did not all run the same permutation (of a batched frame only the first batch can be a plain one). */
 int nrays_debug_last_permutation(const NraysScene* scene, uint32_t out[6]);
+
+/* How the frames of this handle were enqueued since it was created (test probe; host bookkeeping only, no device work): out[0] = frames
+ * pipelined (trace on an internal stream, compose on the caller's), out[1] = frames on the direct path, out[2] = in-flight queries issued
+ * (hipEventQuery / hipStreamQuery of the handle's previous work, asked to decide between the two), out[3] = waits for a staging slot's
+ * last compose enqueued on a trace stream. */
+int nrays_debug_pipeline_counts(const NraysScene* scene, uint64_t out[4]);
 
 /* Test probe of `Scene::new`'s BVT construction for one TriMesh (src/scene.rs:119-133; ncollide's BVT::new_balanced inside TriMesh::new,
  * examples/loader3d.rs:695): builds the BLAS of `mesh` with the host builder (flags bit 0 clear) or the device builder (bit 0 set;

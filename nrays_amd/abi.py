@@ -124,6 +124,7 @@ HIP_SYMBOLS = {
     "nrays_debug_node_aabb": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
     "nrays_debug_scene_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "nrays_debug_last_permutation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "nrays_debug_pipeline_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "nrays_get_tile_costs": (C.c_int, [C.c_void_p, C.POINTER(NraysTileCosts)]),
     "nrays_debug_cast_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(NraysCastResult)]),
@@ -191,7 +192,7 @@ HIP_SYMBOLS = {
 POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_intersects_rays_device_ex", "nrays_debug_ray_order",
                    "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points", "nrays_occlusion_points_device",
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
-                   "nrays_debug_surface_texels_passes")
+                   "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

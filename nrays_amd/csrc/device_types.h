@@ -269,11 +269,13 @@ struct DRender {
     // 1: this launch writes the window's pixels only — the rows and columns outside the window are somebody else's (the trace half of a
     // pipelined frame, frame_path.hip: pipeline_prepare; k_compose writes them).  k_primary only.
     uint32_t no_rows;
-    // A timed pipelined frame's four words of the ring's device stamps (scene_handle.h: Ring::d_stamps), null otherwise: [0] the 100 MHz tick (s_memrealtime) at which
-    // workgroup 0 of the trace started (plain store), [1] the latest exit tick of its waves, [2] of k_compose's workgroups (atomicMax: the clock is monotonic, so a slot's
+    // A timed pipelined frame's block of the ring's device stamps, its first four words (scene_handle.h: Ring::d_stamps), null otherwise: [0] the 100 MHz tick (s_memrealtime) at which
+    // workgroup 0 of the trace started (plain store), [1] the latest exit tick of its waves, [2] of k_compose's workgroups, unless they spread theirs over the words behind these four (kStampWords) (atomicMax: the clock is monotonic, so a slot's
     // stale values lose and nothing is cleared).  Only the k_primary permutations a pipelined frame can launch look at it (primary_kernel.h: kStamps).
     unsigned long long* stamp;
 };
+// A ring slot's block of device stamps: the kStampHead words above, then kStampWords words for the exit ticks of k_compose's rows (frame_path.hip).
+constexpr uint32_t kStampHead = 4u, kStampWords = 64u;
 constexpr uint32_t kEntrySplit = 0x80000000u, kEntryTileMask = 0x0fffffffu;
 // A recorded tile cost (DRender::tile_cost, 16-cycle units): bit 31 = the tile ran as light-parallel / pixel-split parts and the value is its most expensive part's, scaled to the tile.
 constexpr uint32_t kCostSplit = 0x80000000u, kCostMask = 0x7fffffffu;

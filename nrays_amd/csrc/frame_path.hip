@@ -244,11 +244,12 @@ __global__ void k_resolve(float* out, size_t n, float spp) { // pxs.push(tot_c /
 // scene copied from the staging frame `win` the trace wrote (addressed like `out`), the background sums of fill_background_row_body
 // everywhere else.  Frames without bands only (row = global row, no padding rows).  It runs beside the next frame's persistent trace
 // grid: no LDS, a few registers, streaming 16-byte accesses.  [wi0, wi1) x [wr0, wr1): the window in pixels.
-// stamp: null, or the frame's words of the ring's stamps (DRender::stamp) — thread 0 of every workgroup leaves its exit tick in the third.
+// stamp: null, or the frame's block of the ring's stamps (DRender::stamp) — thread 0 of every workgroup leaves its exit tick in word kStampHead + (row & stamp_mask) of it
+// (Switches::host_stamps: the rows share stamp_mask + 1 words, nrays_get_stats takes their maximum), or, stamp_mask == ~0u, in the third word as every row did before.
 __global__ void __launch_bounds__(256) k_compose(float* __restrict__ out, const float* __restrict__ win, uint32_t width, uint32_t spp, float bg0, float bg1, float bg2,
-                                                 uint32_t wi0, uint32_t wi1, uint32_t wr0, uint32_t wr1, unsigned long long* stamp) {
+                                                 uint32_t wi0, uint32_t wi1, uint32_t wr0, uint32_t wr1, unsigned long long* stamp, uint32_t stamp_mask) {
     const uint32_t rl = blockIdx.x;
-    auto leave = [&]() { if (stamp && threadIdx.x == 0u) atomicMax(&stamp[2], (unsigned long long)__builtin_amdgcn_s_memrealtime()); };
+    auto leave = [&]() { if (stamp && threadIdx.x == 0u) atomicMax(&stamp[stamp_mask == ~0u ? 2u : kStampHead + (rl & stamp_mask)], (unsigned long long)__builtin_amdgcn_s_memrealtime()); };
     float b0 = 0.0f, b1 = 0.0f, b2 = 0.0f;
     for (uint32_t s = 0; s < spp; ++s) { b0 = b0 + bg0; b1 = b1 + bg1; b2 = b2 + bg2; }
     const bool split = rl >= wr0 && rl < wr1 && wi1 > wi0; // this row crosses the window
@@ -707,6 +708,20 @@ static int schedule_analytic(NraysScene* sc, FramePlan& f, DRender& R, hipStream
 // used, (n + pipe_depth) mod count_rot cleared: scene_handle.h), staging rows (n mod pipe_slots) and the traversal-stack spill region of their stream (pipe_spill; never the
 // handle's d_spill); the trace also waits for the compose that read its staging rows pipe_slots launches ago.  Every direct frame comes behind all composes on the
 // caller's stream, and the first pipelined frame after direct work makes ALL internal streams wait for the end of that work.
+// The start of a burst (Switches::host_burst): the first frame after a host synchronisation goes direct, the second is the first pipelined frame "after direct work".  When that
+// work is ONE plain direct frame of this handle, launch n on the caller's stream, straight behind pipelined frames (Pipe::burst_plain: one k_primary launch, nothing recorded or
+// sorted, not instrumented / multi-sample / queued / banded / staged, no prepass; a second direct frame, a batch of caller rays or a failed call in between clear it), the
+// traces n + 1 and n + 2 need not wait for it.  What they could share with it, item by item:
+//   counter sets     launch n counts into set n mod 6 and clears set n + 3; trace n + 1 uses n + 1 and clears n + 4, trace n + 2 uses n + 2 and clears n + 5 (the frame sets
+//                    likewise: the frames in between are single launches).  Trace n + 3 DOES share: it works from the set launch n clears and clears the set launch n counts
+//                    into — it runs on internal stream n mod 3, which therefore waits for the end of launch n as before (depth 3 with its six sets only; else all wait);
+//   spill region     launch n uses buf.d_spill, a trace the region of its own stream (pipe.spill);
+//   work order       read only: neither launch n nor a pipelined frame records or sorts (R.tile_cost null, no prepass), so d_tile_order / d_tile_cost are written by nobody;
+//   `out`            a trace writes its staging rows alone (ordered against the compose that last read them by the slot proof below, unchanged); `out` is written by launch n
+//                    and by the composes, all on the caller's stream(s), in call order;
+//   the queue pair, the fixed-point sums, cost_meta, the stamps: not touched by a plain launch (capacity 0, not queued, instrumented kernels only, R.stamp null).
+// The internal streams are ordered behind everything older than launch n by the waits of the burst before (or of this rule, by induction: a stream that skipped a wait then
+// ran no launch that shared anything with the frame it skipped).
 // Not pipelined: frames that record or sort tile costs, instrumented / multi-sample / queued / banded / staged frames, mesh scenes
 // (their moving frames sort every time), windows beyond half the frame (the copy would outweigh the rows it takes off the tracing waves).
 struct PipeFrame {
@@ -727,11 +742,18 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
 #endif
     if (pipe && !sc->sw.pipeline_always && interleaved) pipe = false; // another handle rendered in between (g_last_renderer)
     if (pipe && !sc->sw.pipeline_always) { // is the predecessor still in flight?  (a caller that waits for every frame stays on the direct path)
-        const hipError_t q = sc->pipe.last_pipelined ? hipEventQuery(sc->last.done) : hipStreamQuery(sc->last.stream);
-        if (q != hipSuccess) (void)hipGetLastError();
-        else if (sc->pipe.last_pipelined) sc->pipe.composed_seen = sc->pipe.newest_launch; // (last.done is the newest compose's event)
-        pipe = q == hipErrorNotReady;
-        ht.mark("pipeline: in-flight query");
+        // A call that comes within kInFlightProofUs of the return of the handle's last pipelined call is taken to be: its caller cannot have waited for that frame in between
+        // (switches.h: half the shortest gap a synchronising caller produces).  Being wrong costs speed, never pixels — NRAYS_PIPELINE=2 pipelines every frame, in flight or not.
+        const bool proved = sc->sw.host_time_proof && sc->pipe.last_pipelined &&
+                            std::chrono::steady_clock::now() - sc->pipe.last_return <= std::chrono::nanoseconds((long long)(kInFlightProofUs * 1e3));
+        if (!proved) {
+            const hipError_t q = sc->pipe.last_pipelined ? hipEventQuery(sc->last.done) : hipStreamQuery(sc->last.stream);
+            sc->pipe.n_inflight_queries++;
+            if (q != hipSuccess) (void)hipGetLastError();
+            else if (sc->pipe.last_pipelined) sc->pipe.composed_seen = sc->pipe.newest_launch; // (last.done is the newest compose's event)
+            pipe = q == hipErrorNotReady;
+        }
+        ht.mark(proved ? "pipeline: in flight by the time since the last call" : "pipeline: in-flight query");
     }
     // the window in pixels; a slot holds its rows [wr0, wr1s) and is handed to the kernels as if it began at row 0 (no pitch, no kernel argument: the trace writes and the
     // compose reads those rows only)
@@ -752,9 +774,12 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
     pf.stage = pipe ? sc->pipe.stage[pf.ps] - stage_skip : nullptr;
     if (pipe) {
         if (!sc->pipe.last_pipelined) { // direct work (a frame that sorted, a batch of caller rays, ...) precedes: every internal stream behind its end
+            // ... or, behind ONE plain direct frame (Pipe::burst_plain, the start of a burst: see above), only the stream of the launch that shares its counter sets
+            const bool one_plain = sc->sw.host_burst && sc->pipe.burst_plain && sc->sw.pipe_depth == 3 && sc->buf.count_rot == 2 * sc->sw.pipe_depth && sc->buf.launch_index == sc->pipe.burst_launch + 1u;
             if (!sc->last.ev_switch) HIP_TRY(hipEventCreateWithFlags(&sc->last.ev_switch, hipEventDisableTiming));
             HIP_TRY(hipEventRecord(sc->last.ev_switch, stream)); // (`stream` is behind the handle's previous stream by now)
-            for (int k = 0; k < sc->sw.pipe_depth; ++k) HIP_TRY(hipStreamWaitEvent(sc->pipe.stream[k], sc->last.ev_switch, 0));
+            for (int k = 0; k < sc->sw.pipe_depth; ++k)
+                if (!one_plain || k == (int)(sc->pipe.burst_launch % (uint64_t)sc->pipe.slots) % sc->sw.pipe_depth) HIP_TRY(hipStreamWaitEvent(sc->pipe.stream[k], sc->last.ev_switch, 0));
         }
         // the compose that last read this slot's staging rows, pipe_slots frames ago: when the host can see that it is over the wait (5 us of host time, which bounds
         // the pipelined frame rate) is not enqueued.  It sees that without a call when a compose at or after that one has been seen finished (Pipe::composed_seen); else
@@ -770,7 +795,7 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
         }
         if (!proved) {
             if (hipEventQuery(sc->pipe.ev_composed[pf.ps]) == hipSuccess) sc->pipe.composed_seen = std::max(sc->pipe.composed_seen, need);
-            else { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->pipe.ev_composed[pf.ps], 0)); }
+            else { (void)hipGetLastError(); HIP_TRY(hipStreamWaitEvent(pf.lstream, sc->pipe.ev_composed[pf.ps], 0)); sc->pipe.n_slot_waits++; }
         }
         ht.mark("pipeline: waits of the trace stream");
     }
@@ -779,10 +804,10 @@ static int pipeline_prepare(NraysScene* sc, const NraysRenderParams* p, FramePla
 // The second half of a pipelined frame: the caller's stream waits for the trace, then k_compose writes every float of `out`.
 // (an error from here on leaves a trace in flight that no compose follows: it is drained, and what comes next is ordered as after direct work)  Touches sc->pipe only.
 static int pipeline_compose(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, float* d_out, hipStream_t stream, unsigned long long* stamp, const HostTimes& ht) {
-    auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(pf.lstream); sc->pipe.last_pipelined = false; } return e; };
+    auto drained = [&](hipError_t e) { if (e != hipSuccess) { (void)hipStreamSynchronize(pf.lstream); sc->pipe.last_pipelined = false; sc->pipe.burst_plain = false; } return e; };
     HIP_TRY(drained(hipStreamWaitEvent(stream, sc->pipe.ev_traced[pf.ps], 0)));
     ht.mark("pipeline: wait of the caller's stream");
-    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->pipe.ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->facts.d.background[0], sc->facts.d.background[1], sc->facts.d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1, stamp);
+    hipExtLaunchKernelGGL(k_compose, dim3(f.rows), dim3(256), 0, stream, nullptr, sc->pipe.ev_composed[pf.ps], 0, d_out, (const float*)pf.stage, p->width, p->ray_per_pixel, sc->facts.d.background[0], sc->facts.d.background[1], sc->facts.d.background[2], pf.wi0, pf.wi1, pf.wr0, pf.wr1, stamp, sc->sw.host_stamps ? sc->sw.stamp_words - 1u : ~0u);
     HIP_TRY(drained(hipGetLastError()));
     sc->pipe.slot_launch[pf.ps] = sc->pipe.newest_launch = pf.launch;
     ht.mark("pipeline: k_compose launch");
@@ -791,7 +816,7 @@ static int pipeline_compose(NraysScene* sc, const NraysRenderParams* p, const Fr
 
 // End-of-frame bookkeeping: the frame's last event, what the handle's next call orders itself behind, what nrays_get_stats reports.  Writes sc->last, the frame's
 // slot of sc->ring and pipe.last_pipelined.
-static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, hipStream_t stream, bool instrumented, uint8_t timed_by, const HostTimes& ht) {
+static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FramePlan& f, const PipeFrame& pf, hipStream_t stream, bool instrumented, uint8_t timed_by, bool plain_direct, const HostTimes& ht) {
     const bool pipelined = pf.on;
     // (a pipelined frame's kernel_ms_total runs from its trace to the end of its compose; its "done" event is the compose's)
     if ((!f.single_launch || pipelined) && f.timed && timed_by == NraysScene::Ring::kByEvents) HIP_TRY(hipEventRecord(sc->ring.ev_end[f.slot], stream));
@@ -803,12 +828,17 @@ static int finish_frame(NraysScene* sc, const NraysRenderParams* p, const FrameP
         sc->ring.frames_recorded++;
     }
     if (pipelined) sc->last.done = sc->pipe.ev_composed[pf.ps];
+    // (the start of a burst, pipeline_prepare: a plain frame is one launch that recorded and sorted nothing — its scheduling state was read only)
+    sc->pipe.burst_plain = !pipelined && sc->pipe.last_pipelined && plain_direct;
+    sc->pipe.burst_launch = sc->buf.launch_index - 1u;
     sc->pipe.last_pipelined = pipelined;
+    if (pipelined) sc->pipe.n_pipelined++; else sc->pipe.n_direct++;
     sc->last.stream = stream; sc->last.have = true;
     ht.mark("end (event records after the launch)");
     sc->last.primary = f.owned_rows * p->width * p->ray_per_pixel;
     sc->last.primary_first_batch = f.owned_rows * p->width * std::min<uint32_t>(f.batch, p->ray_per_pixel);
     sc->last.instrumented = instrumented;
+    if (pipelined && sc->sw.host_time_proof) sc->pipe.last_return = std::chrono::steady_clock::now();
     return NRAYS_OK;
 }
 
@@ -859,7 +889,7 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
         ht.mark("scheduling state (seed / sort launches)");
         { const int rc = pipeline_prepare(sc, p, f, R, stream, interleaved, ht, pf); if (rc != NRAYS_OK) return rc; }
         // a timed pipelined frame is timed by its own kernels (Ring::d_stamps): none of the slot's events is recorded
-        if (pf.on && f.timed && sc->sw.lean_stamps && sc->ring.d_stamps) { timed_by = NraysScene::Ring::kByStamps; R.stamp = sc->ring.d_stamps + 4u * (size_t)f.slot; }
+        if (pf.on && f.timed && sc->sw.lean_stamps && sc->ring.d_stamps) { timed_by = NraysScene::Ring::kByStamps; R.stamp = sc->ring.d_stamps + (size_t)NraysScene::kStampBlock * (size_t)f.slot; }
         const bool ring_events = f.timed && timed_by == NraysScene::Ring::kByEvents;
         bool first_primary = true;
         for (uint32_t s0 = 0; s0 < p->ray_per_pixel; s0 += f.batch) {
@@ -908,7 +938,9 @@ int render_impl(NraysScene* sc, const NraysRenderParams* p, float* d_out, hipStr
         hipLaunchKernelGGL(k_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, d_out, n, (float)p->ray_per_pixel);
         HIP_TRY(hipGetLastError());
     }
-    return finish_frame(sc, p, f, pf, stream, instrumented, timed_by, ht);
+    // one launch of k_primary on the caller's stream that read the scheduling state and wrote none of it
+    const bool plain_direct = !pf.on && !f.staged && f.single_launch && !f.banded && !instrumented && !R.tile_cost && !sc->ring.has_prepass[f.slot] && sc->facts.d.no_elide == 0u;
+    return finish_frame(sc, p, f, pf, stream, instrumented, timed_by, plain_direct, ht);
 }
 
 } // namespace nrays

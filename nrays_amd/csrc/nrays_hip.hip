@@ -355,8 +355,8 @@ static int allocate_handle_state(NraysScene* sc, StageClock& clock) {
     if (hipMalloc((void**)&sc->ring.d_counters_primary, sizeof(DeviceCounters)) != hipSuccess)
         return fail(NRAYS_ERR_OOM, "counter allocation failed");
     // the stamps of timed pipelined frames (scene_handle.h: Ring::d_stamps): zeroed once, never cleared afterwards
-    if (sc->sw.lean_stamps && (hipMalloc((void**)&sc->ring.d_stamps, (size_t)NraysScene::kRing * 4 * sizeof(unsigned long long)) != hipSuccess ||
-                               hipMemset(sc->ring.d_stamps, 0, (size_t)NraysScene::kRing * 4 * sizeof(unsigned long long)) != hipSuccess))
+    if (sc->sw.lean_stamps && (hipMalloc((void**)&sc->ring.d_stamps, (size_t)NraysScene::kRing * NraysScene::kStampBlock * sizeof(unsigned long long)) != hipSuccess ||
+                               hipMemset(sc->ring.d_stamps, 0, (size_t)NraysScene::kRing * NraysScene::kStampBlock * sizeof(unsigned long long)) != hipSuccess))
         return fail(NRAYS_ERR_OOM, "stamp allocation failed");
     // (own_stream is created by the first entry point that needs it, ensure_own_stream(): a handle that is only ever rendered on the caller's streams leaves its
     // hardware queue to the internal streams of the pipelined frames — a stream that exists holds a queue, and a process has four)
@@ -486,15 +486,18 @@ int nrays_get_stats(NraysScene* sc, NraysStats* out) {
     std::vector<unsigned long long> stamps;
     for (uint64_t f = first; f < sc->ring.frames_recorded && stamps.empty(); ++f)
         if (sc->ring.timed_by[f % NraysScene::kRing] == NraysScene::Ring::kByStamps && sc->ring.d_stamps) {
-            stamps.resize((size_t)NraysScene::kRing * 4);
+            stamps.resize((size_t)NraysScene::kRing * NraysScene::kStampBlock);
             HIP_TRY(hipMemcpy(stamps.data(), sc->ring.d_stamps, stamps.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         }
     for (uint64_t f = first; f < sc->ring.frames_recorded; ++f) {
         int k = (int)(f % NraysScene::kRing);
         float ms_p = 0.f, ms_t = 0.f;
         if (sc->ring.timed_by[k] != NraysScene::Ring::kByEvents) { // a slot whose end is not later than its start is skipped, like an event pair that is not ready
-            const unsigned long long* w = stamps.empty() ? nullptr : &stamps[4 * (size_t)k];
-            if (sc->ring.timed_by[k] == NraysScene::Ring::kByStamps && w && w[1] > w[0] && w[2] >= w[1]) { sum_p += (double)(w[1] - w[0]) * 1e-5; sum_t += (double)(w[2] - w[0]) * 1e-5; ++n; }
+            const unsigned long long* w = stamps.empty() ? nullptr : &stamps[(size_t)NraysScene::kStampBlock * (size_t)k];
+            // the compose's end: its third word, or the latest of the words its rows shared (a handle uses one of the two for life, the other stays 0; stale ticks of a slot's earlier use are older and lose)
+            unsigned long long end = w ? w[2] : 0ull;
+            if (w && sc->sw.host_stamps) for (uint32_t j = 0; j < nrays::kStampWords; ++j) end = std::max(end, w[nrays::kStampHead + j]);
+            if (sc->ring.timed_by[k] == NraysScene::Ring::kByStamps && w && w[1] > w[0] && end >= w[1]) { sum_p += (double)(w[1] - w[0]) * 1e-5; sum_t += (double)(end - w[0]) * 1e-5; ++n; }
             continue;
         }
         if (hipEventElapsedTime(&ms_p, sc->ring.ev_pbegin[k], sc->ring.ev_pend[k]) == hipSuccess &&
@@ -662,6 +665,12 @@ int nrays_debug_last_permutation(const NraysScene* sc, uint32_t out[6]) {
     if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
     for (int a = 0; a < 4; ++a) out[a] = sc->last.perm_launches ? sc->last.perm_last[a] : 0u;
     out[4] = sc->last.perm_launches; out[5] = sc->last.perm_mixed ? 1u : 0u;
+    return NRAYS_OK;
+}
+
+int nrays_debug_pipeline_counts(const NraysScene* sc, uint64_t out[4]) {
+    if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    out[0] = sc->pipe.n_pipelined; out[1] = sc->pipe.n_direct; out[2] = sc->pipe.n_inflight_queries; out[3] = sc->pipe.n_slot_waits;
     return NRAYS_OK;
 }
 

@@ -290,7 +290,7 @@ static int batch_begin(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
 }
 static void batch_end(NraysScene* sc, TraceWorkspace* w, hipStream_t stream) {
     w->last_stream = stream; w->used = true;
-    if (sc->last.have) { sc->last.stream = stream; sc->last.timed = false; sc->pipe.last_pipelined = false; }
+    if (sc->last.have) { sc->last.stream = stream; sc->last.timed = false; sc->pipe.last_pipelined = false; sc->pipe.burst_plain = false; }
 }
 // Shading needs the permutation of the scene's own feature set: kFeatMesh for scenes of opaque meshes lit by one sample per hit, kFeatAll otherwise.
 static bool batch_mesh_only(const NraysScene* sc) { return (sc->facts.features & ~(int)kFeatLdsScene) == (int)kFeatMesh; }

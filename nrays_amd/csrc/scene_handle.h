@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <string>
 #include <vector>
 
@@ -85,6 +86,7 @@ struct NraysScene {
     static constexpr int kCountSets = 6;  // counter sets a handle allocates (Buffers)
     static constexpr int kPipeStreams = 3, kPipeSlots = 2 * kPipeStreams; // the most a handle uses: the caller's stream + 3 fill a process's four hardware queues
     static constexpr int kRing = 256;     // slots of the event ring
+    static constexpr int kStampBlock = (int)(nrays::kStampHead + nrays::kStampWords); // words of a ring slot's device stamps (Ring::d_stamps)
 
     nrays::Switches sw; // the environment's switches as nrays_scene_create found them: never written afterwards, never re-read in the frame path (switches.h)
 
@@ -176,6 +178,14 @@ struct NraysScene {
         // on the caller's streams, each ordered behind its predecessor, so a compose seen finished proves every earlier one: a trace into a slot whose last compose is at or below
         // composed_seen needs neither a query nor a wait.  slot_launch[s]: the compose ev_composed[s] was last recorded behind; newest_launch: the handle's latest compose.
         uint64_t composed_seen = 0, newest_launch = 0, slot_launch[kPipeSlots] = {};
+        // Switches::host_time_proof: when the handle's last pipelined call returned.  A call that arrives within kInFlightProofUs of it comes from a caller that did not wait for
+        // that frame (frame_path.hip: pipeline_prepare), so it is pipelined without asking the device.
+        std::chrono::steady_clock::time_point last_return{};
+        // Switches::host_burst: the handle's only work since its last pipelined frame is ONE plain direct frame of render_impl (single launch, nothing recorded or sorted,
+        // not instrumented / banded / staged), which was launch `burst_launch` (buf.launch_index before it).  Cleared by everything else that runs on the handle.
+        bool burst_plain = false; uint64_t burst_launch = 0;
+        // nrays_debug_pipeline_counts: host bookkeeping since the handle was created — frames pipelined, frames direct, in-flight queries issued, slot waits enqueued
+        uint64_t n_pipelined = 0, n_direct = 0, n_inflight_queries = 0, n_slot_waits = 0;
     } pipe;
 
     // Ring of HIP event triples (frame begin, primary kernel begin/end, frame end) recorded on the render
@@ -188,10 +198,11 @@ struct NraysScene {
         uint64_t frames_recorded = 0, frames_reported = 0, frames_total = 0;
         DeviceCounters* d_counters_primary = nullptr; // snapshot taken right after the primary kernel
         // A timed PIPELINED frame records none of the slot's events (three records cost its call 8 - 9 us): its trace and its compose leave 100 MHz ticks in the slot's four
-        // words of d_stamps (DRender::stamp; allocated and zeroed with the handle, Switches::lean_stamps), which nrays_get_stats copies in one piece.
+        // words of d_stamps (DRender::stamp; allocated and zeroed with the handle, Switches::lean_stamps), which nrays_get_stats copies in one piece.  A slot's block is
+        // kStampBlock words: the four of DRender::stamp, then kStampWords words the rows of k_compose spread their exit ticks over (Switches::host_stamps; their maximum counts).
         enum : uint8_t { kByEvents = 0, kByStamps = 1, kUntimed = 2 }; // kUntimed: the launch fell back to a kernel that does not stamp (tuning builds)
         uint8_t timed_by[kRing] = {};
-        unsigned long long* d_stamps = nullptr; // kRing x 4 words
+        unsigned long long* d_stamps = nullptr; // kRing x kStampBlock words
     } ring;
 
     // The plan of the last parameter block (Switches::lean_plan): a call whose block and `instrumented` flag are the same bytes reuses `f` and `R` as plan_frame left them —

@@ -49,6 +49,8 @@ Switches read_switches() {
     clamped("NRAYS_PIPELINE_DEPTH", s.pipe_depth, 1, 3);
     flag("NRAYS_PIPELINE_LEAD_WGS", s.pipe_lead_wgs);
     if (const char* e = getenv("NRAYS_PIPELINE_LEAN")) { const int v = atoi(e); s.lean_stamps = (v & 1) != 0; s.lean_slots = (v & 2) != 0; s.lean_plan = (v & 4) != 0; }
+    if (const char* e = getenv("NRAYS_STAMP_WORDS")) { const int v = std::max(1, std::min(64, atoi(e))); s.stamp_words = 1u; while ((int)(s.stamp_words * 2u) <= v) s.stamp_words *= 2u; }
+    if (const char* e = getenv("NRAYS_PIPELINE_HOST")) { const int v = atoi(e); s.host_stamps = (v & 1) != 0; s.host_time_proof = (v & 2) != 0; s.host_burst = (v & 4) != 0; }
     real("NRAYS_NEAR_PIXELS", s.near_pixels);
     if (const char* e = getenv("NRAYS_ORDER_AGE")) s.max_order_age = (uint32_t)std::max(0, atoi(e));
     flag("NRAYS_LEAD_WGS", s.lead_mode);

@@ -11,6 +11,12 @@
 
 namespace nrays {
 
+// Switches::host_time_proof: a call that comes within this many microseconds of the return of the handle's last pipelined call is pipelined without an in-flight query.
+// Half the shortest gap between return and next entry that a caller which synchronises after every frame produced: 35.0 us, the least of 200 frames of the balls scene
+// at 64 x 64 (the frame has to be enqueued, run and be seen finished in it; stream and device synchronisation alike, profiles/pipeline_host_ab.log) — the steady loop's
+// own gap between calls is 0.1 - 0.4 us from ctypes, 3 - 6 us from bench.py.  A wrong "in flight" costs speed, never pixels.
+constexpr double kInFlightProofUs = 17.5;
+
 struct Switches {
     // ---- what the scene's kernels may skip or specialise (nrays_scene_create: derive_scene_facts and the optional tables) ----
     bool elide = true;                  // NRAYS_ELIDE=0: no hit or light sample is skipped for being multiplied by exactly 0 (A/B)
@@ -39,8 +45,14 @@ struct Switches {
     bool pipeline = true, pipeline_always = false; // NRAYS_PIPELINE=0|2: every frame on the direct path (A/B, tests) / every eligible frame pipelined, in flight or not (tests: no dependence on timing)
     int pipe_depth = 3;                 // NRAYS_PIPELINE_DEPTH=1|2|3: traces of the handle in flight at once = its internal streams
     std::optional<bool> pipe_lead_wgs;  // NRAYS_PIPELINE_LEAD_WGS=0|1: a pipelined trace keeps the lead + second workgroups of a direct frame, or runs its lists on one workgroup per CU (unset: by the depth)
-    bool lean_stamps = true, lean_slots = true, lean_plan = true; // NRAYS_PIPELINE_LEAN=0: the host path of a pipelined frame as it was — event records on timed frames, a query of the slot's
-                                        // compose per frame, the plan recomputed per call (A/B; =n: the sum of 1 device stamps, 2 one slot query per several frames, 4 the plan of an unchanged block)
+    bool lean_stamps = true, lean_slots = true, lean_plan = false; // NRAYS_PIPELINE_LEAN=0: the host path of a pipelined frame as it was — event records on timed frames, a query of the slot's
+                                        // compose per frame, the plan recomputed per call (A/B; =n: the sum of 1 device stamps, 2 one slot query per several frames, 4 the plan of an unchanged block; unset: 3 —
+                                        // 1 + 2 separate from 0 by the three-widths rule, 4 does not: profiles/pipeline_host_ab.log)
+    uint32_t stamp_words = 64;          // NRAYS_STAMP_WORDS=1|2|..|64: words the rows of a timed k_compose spread their exit ticks over (a power of two; tuning, with bit 1 of NRAYS_PIPELINE_HOST)
+    bool host_stamps = false, host_time_proof = false, host_burst = false; // NRAYS_PIPELINE_HOST=n: the sum of 1 a kernel's exit ticks spread over kStampWords words of the frame's stamp block
+                                        // instead of one shared word, 2 no in-flight query when the call comes within kInFlightProofUs of the return of the handle's last pipelined
+                                        // call, 4 a burst that starts behind ONE plain direct frame orders only the internal stream that shares that frame's counter sets (A/B; unset: 0, the parent's path —
+                                        // none of the three separates on bench.py by the three-widths rule: profiles/pipeline_host_ab.log)
     std::optional<double> near_pixels;  // NRAYS_NEAR_PIXELS=x: a camera within x pixels of an order's camera reuses the order (unset: by the scene)
     std::optional<uint32_t> max_order_age; // NRAYS_ORDER_AGE=n: frames of nearby cameras an order serves before it is re-sorted (unset: by the scene)
     bool lead_mode = true;              // NRAYS_LEAD_WGS=0: cost-ordered lists run on one workgroup per CU instead of lead + second workgroups
