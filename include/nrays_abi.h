@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -401,6 +401,54 @@ int nrays_occlusion_points(NraysScene* scene, uint32_t n, const double* points, 
  * out_origins / out_dirs [(i * num_dirs + j) * 3 ..], n x num_dirs x 3 doubles each.  keys NULL: key i.  max_toi is checked and not used. */
 int nrays_debug_occlusion_rays(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint64_t* keys,
                                const NraysOcclusionParams* params, double* out_origins, double* out_dirs);
+
+/* The light arriving at n caller-supplied surface points from the rest of the scene — a light map's indirect term, a final gather: the library builds
+ * num_dirs hemisphere rays per point ON THE DEVICE, runs Scene::trace (what nrays_trace_rays_device runs) on each and writes ONE mean colour per point — the
+ * caller passes and receives per-point arrays only, and no ray, key or per-ray colour array exists anywhere except in double-branching scenes (below), where the
+ * library keeps the ray colours of one chunk in the handle's workspace.  The result is defined by this text, so that a caller can restate it from existing parts:
+ *   rays       ray j of point i is bit for bit the ray nrays_occlusion_points* builds from the same point, normal, key, dirs, rotations and bias: the same
+ *              frame, the same rotation pick (salt 0x300 << 32), origin p + n * bias, the same direction.  Occlusion and gather with the same tables use the
+ *              same rays; nrays_debug_occlusion_rays and Python's occlusion_rays serve both.
+ *   trace      each ray is the depth-0 RayWithEnergy nrays_trace_rays_device loads: refr 1.0, energy = params->energy, weight 1, RNG key
+ *              key_ij = hash(key_i, (0x301 << 32) + j) with the library's counter-based hash (Python: gather_ray_keys); the key is read only in scenes that
+ *              sample an area light, as there.  c_ij = Scene::trace(ray) with params->max_depth.
+ *   fold       sum = 0 (f32 rgb); for j = 0 .. num_dirs - 1 in order: sum += c_ij; out_rgb[3i..3i+2] = sum / (float)num_dirs (one correctly rounded division
+ *              per channel).  The result never depends on how the library assigns rays to lanes: it equals, bit for bit, nrays_trace_rays_device on these
+ *              rays and keys with energy params->energy, folded this way.
+ *   double-branching scenes (one hit spawns both a reflection and a refraction): the second children go to the continuation queue as for
+ *              nrays_trace_rays_device, PER RAY — ray j of point i is the queue's "pixel" i * num_dirs + j of its chunk, its queued chains are summed in
+ *              2^-32 fixed point and added to ITS colour before the fold, exactly as that call does — so the fold above holds bit for bit there too.  These
+ *              scenes alone keep per-ray memory in the handle's workspace between the trace and the fold (36 bytes a ray of one chunk, beside the queue);
+ *              the caller still passes and receives per-point arrays only.  NRAYS_ERR_QUEUE_OVERFLOW applies as for nrays_trace_rays_device; the queue is
+ *              sized by a chunk's rays with the same rule. */
+/* (Struct plus separate typedef, as NraysOcclusionParams and for the same reason; tests/test_gather.py compares it with its Rust and ctypes twins.) */
+struct NraysGatherParams {
+    uint32_t num_dirs;       /* 1 .. 1024 */
+    uint32_t num_rotations;  /* 0 .. 1024; 0 = none */
+    const double* dirs;      /* num_dirs x 3, local frame, z = the normal */
+    const double* rotations; /* num_rotations x 2 (cos, sin), or NULL when 0 */
+    double bias;             /* finite */
+    float energy;            /* RayWithEnergy::energy of every gathered ray; finite */
+    uint32_t max_depth;      /* as nrays_trace_rays_device: 0 = the energy rule only, the cap of 64 generations applies */
+};
+typedef struct NraysGatherParams NraysGatherParams;
+/*   points, normals  n x 3 doubles, world space, used as given (unit normals pointing to the side to gather on).
+ *   hit_flags        n words, or NULL = every point is live: the bits of out_flags of nrays_cast_rays_device / nrays_surface_texels_device.  Bit 0 clear = the
+ *                    point is SKIPPED: out_rgb (0, 0, 0), no traversal, neither its point nor its normal read (they may hold anything).
+ *   keys             n RNG keys, or NULL = the key of point i is i (also across chunks).  The rotation pick and the rays' keys read them.
+ *   params           HOST memory (the struct); params->dirs and params->rotations are DEVICE memory here, like every other array.
+ *   out_rgb          n x 3 floats, required.
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG).
+ * NULL scene / points / normals / params / params->dirs / out_rgb, num_dirs outside 1 .. 1024, num_rotations > 1024 or > 0 with NULL rotations, a non-finite
+ * bias or energy -> NRAYS_ERR_BAD_ARG; n == 0 -> NRAYS_OK without work.  Otherwise the contract of nrays_occlusion_points_device: every array DEVICE memory on
+ * the scene's device, chunks of at most max(1, 2^22 / num_dirs) points, the workspace owned by the handle, enqueued on `hip_stream` behind the handle's previous
+ * work, without read-back or synchronisation unless the scene is double-branching (the queue's rounds are controlled from the host, as for
+ * nrays_trace_rays_device); what the handle reports about its renders and its per-camera scheduling state stay untouched. */
+int nrays_gather_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                               const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables included) HOST memory.  Blocking. */
+int nrays_gather_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                        const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and

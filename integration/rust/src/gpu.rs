@@ -557,6 +557,35 @@ impl GpuScene {
         if nrays_occlusion_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_filter, out_open, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
+
+    /// The light arriving at caller-supplied surface points from the rest of the scene (nrays_gather_points, blocking): the rays of `occlusion_points` with the
+    /// same tables, `bias` and keys, each traced with `Scene::trace` as a `RayWithEnergy` of the given `energy` (`max_depth` as in `render`; its RNG key is
+    /// hashed from the point's key and the ray's index), the colours summed in order and divided by their number: one mean colour per point, a light map's
+    /// indirect term.  The value is defined in include/nrays_abi.h (NraysGatherParams).
+    pub fn gather_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32, max_depth: u32,
+                         keys: Option<&[u64]>) -> Result<Vec<Vector3<f32>>, String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysGatherParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                         rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, energy, max_depth };
+        let mut rgb = vec![0.0f32; 3 * n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_gather_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, rgb.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect())
+    }
+
+    /// `gather_points` for n points in DEVICE memory (nrays_gather_points_device), enqueued on `hip_stream`: points / normals n x 3 f64, hit_flags n u32 or null
+    /// (bit 0 clear = skipped, zeros), keys n u64 or null, out_rgb n x 3 f32.  `params` is host memory; its two tables are device memory.
+    pub unsafe fn gather_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: &NraysGatherParams,
+                                       out_rgb: *mut f32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_gather_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_rgb, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
 }
 
 impl Drop for GpuScene {

@@ -113,6 +113,12 @@ class NraysOcclusionParams(C.Structure):
     _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("max_toi", C.c_double)]
 
 
+class NraysGatherParams(C.Structure):
+    """The tables and ray settings of nrays_gather_points*: `dirs` / `rotations` are addresses (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("energy", C.c_float),
+                ("max_depth", C.c_uint32)]
+
+
 class NraysBlasDump(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_refs", C.c_uint32), ("root", C.c_int32), ("max_depth", C.c_int32), ("hairy", C.c_uint32),
                 ("node_capacity", C.c_uint32), ("ref_capacity", C.c_uint32), ("pad", C.c_uint32), ("nodes", C.POINTER(C.c_float)), ("tri_ids", C.POINTER(C.c_uint32))]
@@ -151,6 +157,9 @@ HIP_SYMBOLS = {
                                          C.POINTER(NraysOcclusionParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_debug_occlusion_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(NraysOcclusionParams),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nrays_gather_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysGatherParams), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_gather_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                      C.POINTER(NraysGatherParams), C.POINTER(C.c_float), C.c_uint32]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -192,7 +201,7 @@ HIP_SYMBOLS = {
 POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_intersects_rays_device_ex", "nrays_debug_ray_order",
                    "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points", "nrays_occlusion_points_device",
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
-                   "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts")
+                   "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

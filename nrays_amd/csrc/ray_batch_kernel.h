@@ -2,8 +2,9 @@
 // k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
-// k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value.
-// Device code only.
+// k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value;
+// k_gather_points (nrays_gather_points*) runs Scene::trace on the same rays and folds the colours (instantiated in gather_inst.hip).
+// Templates and inline device code only: ray_order.hip and gather_inst.hip both include this header.
 #pragma once
 #include "primary_kernel.h"
 
@@ -289,19 +290,80 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
     }
 }
 
-// nrays_debug_occlusion_rays: ray j of point i, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].
-__global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
-                                                           const unsigned long long* __restrict__ keys, OcclusionSpec P, const double* __restrict__ dirs,
-                                                           const double* __restrict__ rotations, double* __restrict__ out_origins, double* __restrict__ out_dirs) {
-    const size_t rays = (size_t)n * P.num_dirs;
-    for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < rays; r += (size_t)gridDim.x * kBlock) {
-        const size_t i = r / P.num_dirs, j = r % P.num_dirs;
-        const OccFrame f = occlusion_frame(D3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), D3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]),
-                                           keys ? keys[i] : (unsigned long long)i, P, rotations);
-        const d3 d = occlusion_dir(f, P.num_rotations != 0u, dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
-        out_origins[3 * r] = f.o.x; out_origins[3 * r + 1] = f.o.y; out_origins[3 * r + 2] = f.o.z;
-        out_dirs[3 * r] = d.x; out_dirs[3 * r + 1] = d.y; out_dirs[3 * r + 2] = d.z;
+// ---- incoming light at caller-supplied points (nrays_gather_points*): the mean of Scene::trace over a point's hemisphere rays -----------------------------
+// The rays are k_occlusion_points' (occlusion_frame / occlusion_dir with the same point, normal, key, tables and bias: bit for bit the same rays); ray j of point i
+// is traced as k_trace_rays traces a ray it loads — a depth-0 RayWithEnergy of refr 1, energy P.energy, weight 1, key rng_hash(key_i, kSaltGather + j), "pixel" i —
+// and the chains' sums are folded as the occlusion kernel folds its filters: 2^LP lanes serve a point, and after every round the 2^LP partial colours are added in
+// the order of j through __shfl, every lane of the point keeping the same running sum — the sequential f32 sum, whatever LP.  trace_chain holds ballots and
+// emit_rays: every lane of the wave reaches it in every round, the idle ones with alive = false.
+// The frame is REBUILT in every round from the point, the normal and the key (a handful of f64 operations and one hash beside a whole trace): only those seven
+// doubles' worth of registers stay live across trace_chain instead of the frame's 28 (profiles/gather_kres_change.txt, profiles/gather_isa_scratch.txt).
+// ray_out != nullptr (double-branching scenes): nothing is folded here.  Ray j of point i is "pixel" i * num_dirs + j of the chunk and its chain's sum goes to
+// ray_out[3 * pixel ..] (zeros for a skipped point), exactly as k_trace_rays stores a ray's; the k_bounce rounds and k_fold_fixed add the queued second children per
+// RAY, as for a chunk of nrays_trace_rays, and k_gather_fold (ray_order.hip) then runs the sequential fold — so the result is the definition's bit for bit there too.
+// A point whose flag bit 0 is clear is skipped: zeros, no traversal, neither its point nor its normal read.  NULL keys: key_base + i.
+struct GatherSpec { uint32_t num_dirs, num_rotations; double bias; float energy; uint32_t max_depth, keyed; };
+
+template <bool STATS, int FEAT, int LP>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(DScene S, uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                                                 const uint32_t* __restrict__ hit_flags, const unsigned long long* __restrict__ keys,
+                                                                                 unsigned long long key_base, GatherSpec P, const double* __restrict__ dirs,
+                                                                                 const double* __restrict__ rotations, float* __restrict__ out, float* __restrict__ ray_out,
+                                                                                 QueueOut qo, DeviceCounters* ctr, uint32_t* spill) {
+    static_assert(LP >= 0 && LP <= 6, "the lanes of a point share a wave");
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    constexpr uint32_t kLanes = 1u << LP;
+    const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: ray_order.hip's chunks)
+    const bool rotate = P.num_rotations != 0u;
+    const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
+    for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
+        const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
+        f3 sum = F3(0.0f, 0.0f, 0.0f);
+        for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
+            const uint32_t j = j0 + sub;
+            const bool alive = live && j < k;
+            RayState ray;
+            ray.o = D3(0, 0, 0); ray.d = D3(0, 0, 1); ray.refr = 1.0; ray.energy = 0.0f; ray.weight = 0.0f; ray.key = 0; ray.pixel = 0;
+            if (alive) {
+                const size_t i3 = 3 * (size_t)i;
+                const unsigned long long key = keys ? keys[i] : key_base + i;
+                const OccFrame f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), key, G, rotations);
+                ray.o = f.o; ray.d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
+                ray.energy = P.energy; ray.weight = 1.0f; ray.pixel = ray_out ? i * k + j : i;
+                ray.key = P.keyed ? rng_hash(key, kSaltGather + j) : 0ULL;
+            }
+            const f3 c = trace_chain<STATS, FEAT>(S, st, alive, ray, 0u, P.max_depth, qo, cnt, P.keyed != 0u);
+            if (ray_out) { // (kernel argument: wave-uniform)
+                if (i < n && j < k) { float* o = ray_out + 3 * ((size_t)i * k + j); o[0] = c.x; o[1] = c.y; o[2] = c.z; }
+                continue;
+            }
+            if constexpr (LP == 0) {
+                sum.x += c.x; sum.y += c.y; sum.z += c.z; // (a skipped point's chain is +0)
+            } else {
+#pragma unroll
+                for (uint32_t s = 0; s < kLanes; ++s) {
+                    const float cx = __shfl(c.x, (int)s, (int)kLanes), cy = __shfl(c.y, (int)s, (int)kLanes), cz = __shfl(c.z, (int)s, (int)kLanes);
+                    if (j0 + s < k) { sum.x += cx; sum.y += cy; sum.z += cz; }
+                }
+            }
+        }
+        if (!ray_out && i < n && sub == 0u) {
+            const float fk = (float)k;
+            out[3 * (size_t)i] = sum.x / fk; out[3 * (size_t)i + 1] = sum.y / fk; out[3 * (size_t)i + 2] = sum.z / fk;
+        }
     }
+    flush_counters(ctr, cnt, STATS);
 }
+
+// The arguments of one k_gather_points launch.  The instantiations (trace_chain is the expensive template) are compiled in gather_inst.hip, a translation unit of
+// their own beside ray_order.hip, which calls launch_gather_points: false = no such permutation.
+struct GatherLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys;
+    unsigned long long key_base; GatherSpec spec; const double* dirs; const double* rotations; float* out; float* ray_out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
+};
+bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
 
 } // namespace nrays

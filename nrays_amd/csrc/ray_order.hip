@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points*, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -271,7 +271,7 @@ void trace_workspace_release(NraysScene* sc) {
     if (!w) return;
     if (w->used) (void)hipStreamSynchronize(w->last_stream);
     for (int k = 0; k < 2; ++k) if (w->queue[k].block) (void)hipFree(w->queue[k].block);
-    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage, w->d_texel_owner, w->d_texel_off, (void*)w->d_texel_blocks}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage, w->d_texel_owner, w->d_texel_off, (void*)w->d_texel_blocks, w->d_gather_rays}) if (q) (void)hipFree(q);
     ray_order_release(w);
     delete w;
     sc->tw = nullptr;
@@ -663,6 +663,144 @@ static int occlusion_points_host_impl(NraysScene* sc, uint32_t n, const Occlusio
     return rc;
 }
 
+// ---- nrays_gather_points*: the mean of Scene::trace over the hemisphere rays of caller-supplied points, the rays built on the device --------------------------
+static int check_gather_args(const NraysScene* sc, const OcclusionIn& in, const NraysGatherParams* p, const float* out_rgb, uint32_t flags) {
+    if (!sc || !in.points || !in.normals || !p || !p->dirs || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_dirs must be in 1 .. 1024");
+    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_rotations > 1024, or rotations is NULL");
+    if (!std::isfinite(p->bias) || !std::isfinite(p->energy)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: bias and energy must be finite");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_points: flags must be 0");
+    return NRAYS_OK;
+}
+static uint32_t gather_chunk(const NraysGatherParams* p) { return std::max<uint32_t>(1u, kTraceChunk / p->num_dirs); } // points per chunk: at most kTraceChunk rays
+// Double-branching scenes: the fold that k_gather_points left to the end of the chunk's k_bounce rounds — point i's num_dirs finished ray colours, summed in the
+// order of j in f32 and divided once.  One lane per point; the colours were just written and sit in L2.
+__global__ void __launch_bounds__(kOrderBlock) k_gather_fold(const float* __restrict__ rays, uint32_t n, uint32_t k, float* __restrict__ out) {
+    const uint32_t i = blockIdx.x * kOrderBlock + threadIdx.x;
+    if (i >= n) return;
+    const float* c = rays + 3 * (size_t)i * k;
+    float x = 0.0f, y = 0.0f, z = 0.0f;
+    for (uint32_t j = 0; j < k; ++j) { x += c[3 * j]; y += c[3 * j + 1]; z += c[3 * j + 2]; }
+    const float fk = (float)k;
+    out[3 * (size_t)i] = x / fk; out[3 * (size_t)i + 1] = y / fk; out[3 * (size_t)i + 2] = z / fk;
+}
+// One chunk (nc <= gather_chunk) of nrays_gather_points_device; `in` and `out` are the chunk's, key_base the index of its first point in the batch, dirs / rotations
+// device copies of the tables.  The permutation is trace_chunk's, the lanes per point are occlusion_chunk_launch's.  Double-branching scenes: the kernel stores the
+// chunk's ray colours, trace_chunk's rounds run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by trace_chunk's
+// rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
+static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const OcclusionIn& in, unsigned long long key_base, const NraysGatherParams* p,
+                               const double* dirs, const double* rotations, float* out, hipStream_t stream) {
+    const bool queued = sc->facts.host.any_double_branch;
+    const size_t ray_floats = 3 * (size_t)nc * p->num_dirs; // (nc * num_dirs <= kTraceChunk)
+    if (queued) {
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * nc * p->num_dirs, 1u << 16), 1ull << 27);
+        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
+        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, ray_floats, stream);
+        if (rc == NRAYS_OK) rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
+        if (rc != NRAYS_OK) return rc;
+    }
+    float* ray_out = queued ? (float*)w->d_gather_rays : nullptr;
+    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
+    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
+    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
+    const int lp = occlusion_lanes_log2(sc, p->num_dirs);
+    const uint32_t slots = nc << lp; // (2^lp <= num_dirs)
+    const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const GatherSpec spec{p->num_dirs, p->num_rotations, p->bias, p->energy, p->max_depth, sc->facts.host.any_area_light ? 1u : 0u};
+    const bool stats = sc->facts.d.no_elide != 0u;
+    const GatherLaunch a{grid, stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base, spec, dirs, rotations, out, ray_out, &qo,
+                         w->d_counters, w->d_spill};
+    if (!launch_gather_points(a, stats, !stats && batch_mesh_only(sc) ? (int)kFeatMesh : (int)kFeatAll, lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_points: no such permutation");
+    HIP_TRY(hipGetLastError());
+    if (!queued) return NRAYS_OK;
+    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, stats, p->max_depth, ray_out, ray_floats, sc->facts.num_cus};
+    uint32_t overflowed = 0u;
+    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
+    if (rc != NRAYS_OK) return rc;
+    hipLaunchKernelGGL(k_gather_fold, dim3((nc + kOrderBlock - 1u) / kOrderBlock), dim3(kOrderBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
+    HIP_TRY(hipGetLastError());
+    if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some gathered colours are incomplete");
+    return NRAYS_OK;
+}
+
+static int gather_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, hipStream_t stream) {
+    if (check_gather_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const uint32_t chunk = gather_chunk(p);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        rc = gather_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, p->dirs, p->rotations, out_rgb + 3 * (size_t)c0, stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form, through the workspace's staging buffer as occlusion_points_host_impl: the two tables first, then per staged point kGatherStageBytes —
+// point, normal (3 f64), key (u64), colour (3 f32), hit flags (32 bits), the 8-byte fields first.
+constexpr size_t kGatherStageBytes = 72;
+static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags) {
+    if (check_gather_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    const uint32_t chunk = gather_chunk(p);
+    const size_t cap = std::min<uint32_t>(n, chunk), table = 3 * (size_t)p->num_dirs + 2 * (size_t)p->num_rotations;
+    rc = grow_device(&w->d_stage, &w->stage_rays, (table * sizeof(double) + cap * kGatherStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc != NRAYS_OK) return rc;
+    double* s_dirs = (double*)w->d_stage; double* s_rot = s_dirs + 3 * (size_t)p->num_dirs; double* s_p = s_dirs + table; double* s_n = s_p + 3 * cap;
+    uint64_t* s_k = (uint64_t*)(s_n + 3 * cap); float* s_c = (float*)(s_k + cap); uint32_t* s_hf = (uint32_t*)(s_c + 3 * cap);
+    const OcclusionIn s{s_p, s_n, in.hit_flags ? s_hf : nullptr, in.keys ? s_k : nullptr};
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+    hipError_t e = up(s_dirs, p->dirs, 24 * (size_t)p->num_dirs);
+    if (e == hipSuccess) e = up(s_rot, p->rotations, 16 * (size_t)p->num_rotations);
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather tables upload: ") + hipGetErrorString(e));
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        const OcclusionIn h = occlusion_in_at(in, c0);
+        e = up(s_p, h.points, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_n, h.normals, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
+        if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("gather batch upload: ") + hipGetErrorString(e)); break; }
+        rc = gather_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, stream);
+        if (rc != NRAYS_OK) break;
+        e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_c, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather batch read-back: ") + hipGetErrorString(e));
+    }
+    if (rc != NRAYS_OK) (void)hipStreamSynchronize(stream); // (the tables' upload reads the caller's memory)
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// nrays_debug_occlusion_rays: ray j of point i, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].
+__global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
+                                                           const unsigned long long* __restrict__ keys, OcclusionSpec P, const double* __restrict__ dirs,
+                                                           const double* __restrict__ rotations, double* __restrict__ out_origins, double* __restrict__ out_dirs) {
+    const size_t rays = (size_t)n * P.num_dirs;
+    for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < rays; r += (size_t)gridDim.x * kBlock) {
+        const size_t i = r / P.num_dirs, j = r % P.num_dirs;
+        const OccFrame f = occlusion_frame(D3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), D3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]),
+                                           keys ? keys[i] : (unsigned long long)i, P, rotations);
+        const d3 d = occlusion_dir(f, P.num_rotations != 0u, dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
+        out_origins[3 * r] = f.o.x; out_origins[3 * r + 1] = f.o.y; out_origins[3 * r + 2] = f.o.z;
+        out_dirs[3 * r] = d.x; out_dirs[3 * r + 1] = d.y; out_dirs[3 * r + 2] = d.z;
+    }
+}
+
 // nrays_debug_occlusion_rays: the generator of k_occlusion_points alone, on host arrays, blocking; buffers of its own (a test probe).
 static int occlusion_rays_probe(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* p,
                                 double* out_origins, double* out_dirs) {
@@ -1011,6 +1149,15 @@ int nrays_occlusion_points(NraysScene* sc, uint32_t n, const double* points, con
 int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* params,
                                double* out_origins, double* out_dirs) {
     return occlusion_rays_probe(sc, n, points, normals, keys, params, out_origins, out_dirs);
+}
+
+int nrays_gather_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                               const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream) {
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, (hipStream_t)hip_stream);
+}
+int nrays_gather_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                        const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags);
 }
 
 int nrays_surface_texels_device(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,

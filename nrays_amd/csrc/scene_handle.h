@@ -74,6 +74,8 @@ struct TraceWorkspace {
     uint32_t* d_ray_bins = nullptr; uint32_t* d_ray_scan = nullptr; // bin counts, scanned in place into bin starts; block sums of that scan
     // nrays_surface_texels* (surface_texels_kernel.h): the owner word of every lattice point, the scanned tile counts of the node's triangle records, the block sums of that scan + the total
     void* d_texel_owner = nullptr; size_t texel_owner_words = 0; void* d_texel_off = nullptr; size_t texel_off_words = 0; unsigned long long* d_texel_blocks = nullptr;
+    // nrays_gather_points* in double-branching scenes: the colours of one chunk's rays (x 3), between k_gather_points, the queue's rounds and k_gather_fold
+    void* d_gather_rays = nullptr; size_t gather_ray_floats = 0;
 };
 
 } // namespace nrays

@@ -99,6 +99,8 @@ NR_DEV double rng_u01(unsigned long long key, unsigned long long dim) {
 constexpr unsigned long long kSaltPath = 2ULL, kSaltRefl = 0x100ULL, kSaltRefr = 0x101ULL, kSaltLight = 0x200ULL;
 // (kSaltLight + light index and rng_u01's 0x1000 + dimension stay below 2^33: kSaltOcclusion, the rotation pick of k_occlusion_points, is out of their reach)
 constexpr unsigned long long kSaltOcclusion = 0x300ULL << 32;
+// (k_gather_points: the key of ray j of a point is rng_hash(point key, kSaltGather + j), j < 1024)
+constexpr unsigned long long kSaltGather = 0x301ULL << 32;
 
 // ---------------------------------------------------------------- counters -------------------
 #ifdef NR_PHASE_TIMING

@@ -376,6 +376,15 @@ class Scene:
         """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
 
+    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None):
+        """The incoming light at caller-supplied surface points of this scene: gather_points(self, ...)."""
+        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys)
+
+    def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
+                      device=None):
+        """The indirect term of a light map of mesh node `node`: bake_indirect(self, node, ...)."""
+        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device)
+
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
         return surface_texels(self, node, width, height, centres, flip_normals, want, device)
@@ -908,15 +917,12 @@ def occlusion_points(scene, points, normals, sample_dirs, rotations=None, bias=1
     return Occlusion(filt, opened)
 
 
-def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, keys=None):
-    """Ambient occlusion at the closest hits of caller-supplied rays: occlusion_points() at the hits of `hits = closest_hits(scene, origins, dirs)` (a
-    CastHits with normal and flags), on the side the rays came from.  The points are origins + dirs * toi — two separate element-wise operations, with toi 0
-    at the misses, as in shade_hits() —; a normal is negated where (nx * dx + ny * dy) + nz * dz > 0.  Misses come back as zeros.  numpy or torch as the
-    inputs."""
+def _hit_points(name, origins, dirs, hits):
+    """The surface points and the normals facing the rays of `hits = closest_hits(scene, origins, dirs)`, as occlusion_hits() builds them."""
     n = _n_of(origins, dirs)
-    for name in ("normal", "flags"):
-        if getattr(hits, name) is None:
-            raise ValueError("occlusion_hits: hits.%s is None (closest_hits must be asked for normal and flags)" % name)
+    for field in ("normal", "flags"):
+        if getattr(hits, field) is None:
+            raise ValueError("%s: hits.%s is None (closest_hits must be asked for normal and flags)" % (name, field))
     _check_vec("hits.toi", hits.toi, n)
     _check_rows("hits.normal", hits.normal, n, 3)
     if _is_tensor(origins) != _is_tensor(hits.toi) or _is_tensor(origins) != _is_tensor(dirs) or _is_tensor(origins) != _is_tensor(hits.normal):
@@ -932,8 +938,101 @@ def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias
     step = dirs * toi[:, None]
     points = origins + step
     facing = (nm[:, 0] * dirs[:, 0] + nm[:, 1] * dirs[:, 1]) + nm[:, 2] * dirs[:, 2]
-    normals = where((facing > 0)[:, None], -nm, nm)
+    return points, where((facing > 0)[:, None], -nm, nm)
+
+
+def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, keys=None):
+    """Ambient occlusion at the closest hits of caller-supplied rays: occlusion_points() at the hits of `hits = closest_hits(scene, origins, dirs)` (a
+    CastHits with normal and flags), on the side the rays came from.  The points are origins + dirs * toi — two separate element-wise operations, with toi 0
+    at the misses, as in shade_hits() —; a normal is negated where (nx * dx + ny * dy) + nz * dz > 0.  Misses come back as zeros.  numpy or torch as the
+    inputs."""
+    points, normals = _hit_points("occlusion_hits", origins, dirs, hits)
     return occlusion_points(scene, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags=hits.flags, keys=keys)
+
+
+# ---- incoming light at caller-supplied points (include/nrays_abi.h: nrays_gather_points_device) ------------------------------------------------------------
+
+SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
+
+
+def gather_ray_keys(keys, k):
+    """The RNG keys of the rays gather_points traces: (n, k) uint64, entry [i, j] = hash(keys[i], (0x301 << 32) + j) — ray j of the point whose key is keys[i]
+    (include/nrays_abi.h: NraysGatherParams).  With occlusion_rays() it restates gather_points from trace_rays."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    if _is_tensor(keys):
+        raise ValueError("gather_ray_keys takes a numpy array")
+    keys = _np_keys(keys)
+    if keys.ndim != 1:
+        raise ValueError("keys must have shape (n,), got %s" % (keys.shape,))
+    salts = np.uint64(SALT_GATHER) + np.arange(k, dtype=np.uint64)
+    return _rng_hash(np.broadcast_to(keys[:, None], (len(keys), k)), np.broadcast_to(salts[None, :], (len(keys), k)).copy())
+
+
+def _gather_settings(energy, max_depth):
+    energy = float(energy)
+    if not math.isfinite(energy) or abs(energy) > float(np.finfo(np.float32).max):
+        raise ValueError("energy must be a finite float32")
+    if int(max_depth) < 0 or int(max_depth) >= 1 << 32:
+        raise ValueError("max_depth must be in [0, 2^32)")
+    return energy, int(max_depth)
+
+
+def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None):
+    """The light arriving at n caller-supplied surface points from the rest of the scene — a light map's indirect term —, through nrays_gather_points_device /
+    nrays_gather_points: per point the library builds the len(sample_dirs) hemisphere rays of occlusion_points() ON THE DEVICE (the same rays bit for bit:
+    occlusion_rays()), runs Scene::trace — the query of trace_rays() — on each and folds the colours in order: (n, 3) float32, the mean.  It equals trace_rays
+    on occlusion_rays() with keys gather_ray_keys() and the given energy, summed over j in float32 and divided by float32(k), bit for bit.  No ray
+    or per-ray colour is ever in the caller's memory (the library keeps a chunk's ray colours only in scenes where one hit both reflects and refracts).
+    Also `scene.gather_points(...)` on Scene and FileScene; gather_hits() feeds it from closest_hits(), bake_indirect() from surface_texels().
+    `points`, `normals`, `sample_dirs`, `rotations`, `bias`, `hit_flags`, `keys`: as for occlusion_points.  `energy`: RayWithEnergy::energy of every gathered
+    ray (1.0: a primary ray's; less ends the reflection / refraction recursion earlier).  `max_depth` as in render().
+    numpy arrays -> nrays_gather_points (blocking), a numpy array.  torch tensors on the scene's GPU (float64; hit_flags int32 / uint32; keys int64 / uint64;
+    the tables tensors or anything numpy takes) -> nrays_gather_points_device on torch.cuda.current_stream(), a tensor."""
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    energy, max_depth = _gather_settings(energy, max_depth)
+    if _is_tensor(points):
+        import torch
+        if points.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, points is on %s" % points.device)
+        f64 = (torch.float64,)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        flags_dt = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        L, rot = (t if t is None or _is_tensor(t) else torch.from_numpy(t).to(points.device) for t in (L, rot))
+        p, nm, hf, k, L, rot = _torch_args((("points", points, f64), ("normals", normals, f64), ("hit_flags", hit_flags, flags_dt), ("keys", keys, keys_dt),
+                                            ("sample_dirs", L, f64), ("rotations", rot, f64)), points.device)
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        params = abi.NraysGatherParams(L.shape[0], 0 if rot is None else rot.shape[0], ptr(L), ptr(rot), bias, energy, max_depth)
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(points.device):
+            abi.check(lib.nrays_gather_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(rgb), 0,
+                                                     torch.cuda.current_stream().cuda_stream))
+        return rgb
+    if any(_is_tensor(a) for a in (normals, hit_flags, keys, L, rot)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    rgb = np.empty((n, 3), dtype=np.float32)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    params = abi.NraysGatherParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, energy, max_depth)
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_gather_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
+                                      ptr(rgb, C.c_float), 0))
+    return rgb
+
+
+def gather_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, keys=None):
+    """The incoming light at the closest hits of caller-supplied rays: gather_points() at the hits of `hits = closest_hits(scene, origins, dirs)` (a CastHits
+    with normal and flags), on the side the rays came from — the points and normals of occlusion_hits(), built the same way.  Misses come back as zeros.
+    numpy or torch as the inputs."""
+    points, normals = _hit_points("gather_hits", origins, dirs, hits)
+    return gather_points(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=hits.flags, keys=keys)
 
 
 # ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------
@@ -1104,6 +1203,17 @@ def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, fli
         occ = occlusion_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, max_toi, hit_flags=tx.flags, keys=keys)
         rgba[:, :3] = rgba[:, :3] * occ.filter
     return rgba.reshape(int(height), int(width), 4)
+
+
+def bake_indirect(scene, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
+                  device=None):
+    """The indirect term of a light map of TriMesh node `node`: the mean incoming light at the texels of a width x height map, (height, width, 3) float32 in
+    NraysTexture row order (row 0 = the bottom row): gather_points() with these arguments on surface_texels().  Uncovered texels are zeros.  `keys`
+    (width * height,) RNG keys (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, two calls on one
+    stream; `keys` is then a tensor (the tables may be anything numpy takes).  Also `scene.bake_indirect(node, ...)` on Scene and FileScene."""
+    tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals",), device=device)
+    rgb = gather_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=tx.flags, keys=keys)
+    return rgb.reshape(int(height), int(width), 3)
 
 
 def ray_order(scene, origins, dirs):

@@ -38,7 +38,14 @@ of its own at 1024^2 and 4096^2 lattice points, and of a two-triangle quad at 40
 its owner and resolve passes between events of their own (nrays_debug_surface_texels_passes), shade_points() on the same texels, and for the 1024^2 lattice of the
 grid the numpy mirror surface_texels_ref() on the host, which is what a caller without the entry point does (plus the upload, not counted).
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--texels]
+--gather times, and nothing else, the leg h_sponza_gather: the incoming light (gather_points(): Scene::trace on hemisphere rays built in registers, one mean
+colour per point) at the same two inputs as --occlusion — 16 directions at every first hit, 64 at a 16 384-point subset — beside what a caller did before it: the
+same rays built with torch on the device, trace_rays() on them with the keys of gather_ray_keys() unhinted and with unordered=True, and the torch fold of the
+per-ray colours, each timed apart — and beside itself on handles forced to one lane per point and to 8 / 64 lanes per point (NRAYS_OCCLUSION_LANES).  The same
+two inputs are then timed on the stand-in with a ball that reflects and refracts in the hall: a double-branching scene, where the call keeps a chunk's ray colours
+and runs the continuation queue per ray.  Alternating rounds, each of a few launches between events: min, median and max of every leg.
+
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels]
 """
 import argparse
 import ctypes as C
@@ -217,6 +224,23 @@ def _shade_row(sc, o, d, k, reps, rounds=5):
 OCCLUSION_MAX_TOI = 0.5  # the occlusion leg's radius (the stand-in is a closed hall about 7 units long: no ray gets out of it)
 
 
+def _first_hit_points(sc, w, h):
+    """The first hits of the scene's camera rays as device tensors (points, normals on the camera's side) and their keys: the inputs of the occlusion and gather legs."""
+    import torch
+    import nrays_amd as nr
+    from nrays_amd import math3d
+    cam = sc[1]
+    proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
+    o, d, keys = nr.camera_rays((w, h), cam["eye"], proj)
+    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
+    hits = nr.closest_hits(sc[0], to, td, want=("normal", "flags"))
+    hit = (hits.flags & 1) != 0
+    tp = (to + td * hits.toi[:, None])[hit].contiguous()
+    nm = hits.normal[hit]
+    tn = torch.where((((nm[:, 0] * td[hit][:, 0] + nm[:, 1] * td[hit][:, 1]) + nm[:, 2] * td[hit][:, 2]) > 0)[:, None], -nm, nm).contiguous()
+    return tp, tn, keys[hit.cpu().numpy()]
+
+
 def _torch_occlusion_rays(tp, tn, L, rot, bias, keys):
     """nrays_amd.occlusion_rays() with torch on the device: the same element-wise f64 operations (the rotation index comes from the host: torch has no uint64
     arithmetic).  Returns (origins, dirs) as (n * k, 3) tensors, point-major."""
@@ -281,8 +305,6 @@ def _occlusion_input(scenes, tp, tn, keys, k, reps, rounds=5):
 
 def _occlusion_leg(w, h, reps):
     import torch
-    import nrays_amd as nr
-    from nrays_amd import math3d
     from tools import standins
     scenes = {}
     for name, lanes in (("auto", None), ("lanes_1", "0"), ("lanes_8", "3"), ("lanes_64", "6")):
@@ -292,20 +314,86 @@ def _occlusion_leg(w, h, reps):
         scenes[name], cam = standins.sponza_scene()
         scenes[name].device_handle()
     os.environ.pop("NRAYS_OCCLUSION_LANES", None)
-    proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h)
-    o, d, keys = nr.camera_rays((w, h), cam["eye"], proj)
-    to, td = torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda()
-    hits = nr.closest_hits(scenes["auto"], to, td, want=("normal", "flags"))
-    hit = (hits.flags & 1) != 0
-    tp = (to + td * hits.toi[:, None])[hit].contiguous()
-    nm = hits.normal[hit]
-    tn = torch.where((((nm[:, 0] * td[hit][:, 0] + nm[:, 1] * td[hit][:, 1]) + nm[:, 2] * td[hit][:, 2]) > 0)[:, None], -nm, nm).contiguous()
-    keys = keys[hit.cpu().numpy()]
+    tp, tn, keys = _first_hit_points((scenes["auto"], cam), w, h)
     n = tp.shape[0]
     sub = torch.from_numpy(np.linspace(0, n - 1, min(16384, n)).astype(np.int64)).cuda()
     pick = lambda names: {k: scenes[k] for k in names}  # noqa: E731
     return {"first_hits_16_dirs": _occlusion_input(pick(("auto", "lanes_1", "lanes_8")), tp, tn, keys, 16, max(1, reps // 4)),
             "subset_16384_points_64_dirs": _occlusion_input(pick(("auto", "lanes_1", "lanes_8", "lanes_64")), tp[sub].contiguous(), tn[sub].contiguous(), keys[sub.cpu().numpy()], 64, reps)}
+
+
+def _gather_input(scenes, tp, tn, keys, k, reps, rounds=5):
+    """One input of the gather leg: n points, k directions, 8 rotations, energy 1, max_depth 0.  scenes: {"auto" | "lanes_1" | "lanes_8" | "lanes_64": handle}."""
+    import torch
+    import nrays_amd as nr
+    n = tp.shape[0]
+    L, rot = nr.hemisphere_dirs(k), nr.rotation_table(8)
+    tl, tr = torch.from_numpy(L).cuda(), torch.from_numpy(rot).cuda()
+    tk = torch.from_numpy(keys.astype(np.int64)).cuda()
+    rk = torch.from_numpy(nr.gather_ray_keys(keys, k).reshape(-1).view(np.int64)).cuda()
+    ro, rd = _torch_occlusion_rays(tp, tn, L, rot, 1e-3, keys)
+    sc = scenes["auto"]
+    rgb = nr.trace_rays(sc, ro, rd, keys=rk)
+
+    def torch_fold():
+        c = rgb.view(n, k, 3)
+        tot = torch.zeros((n, 3), dtype=torch.float32, device="cuda")
+        for j in range(k):
+            tot = tot + c[:, j]
+        return tot / float(k)
+
+    fns = {"fused": lambda: nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk),
+           "torch_build_rays": lambda: _torch_occlusion_rays(tp, tn, L, rot, 1e-3, keys),
+           "trace_rays": lambda: nr.trace_rays(sc, ro, rd, keys=rk),
+           "trace_rays_unordered": lambda: nr.trace_rays(sc, ro, rd, keys=rk, unordered=True),
+           "torch_fold": torch_fold}
+    for name, other in scenes.items():
+        if name != "auto":
+            fns["fused_" + name] = lambda other=other: nr.gather_points(other, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk)
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=1))
+    got, want = nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk), torch_fold()
+    row = {"points": int(n), "dirs": int(k), "rays": int(n * k), "energy": 1.0, "max_depth": 0, "rounds": rounds, "reps": reps,
+           "points_that_differ_from_the_torch_fold": int((got != want).any(dim=1).sum().item())}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    return row
+
+
+def _glass_sponza():
+    """The stand-in with a ball in the middle of the hall that reflects AND refracts: a double-branching scene, whose gather keeps per-ray colours and runs the queue."""
+    import nrays_amd as nr
+    from tools import standins
+    sc, cam = standins.sponza_scene()
+    glass = nr.PhongMaterial((0.1, 0.1, 0.15), (0.6, 0.7, 0.9), (1, 1, 1), None, None, 80.0)
+    ball = nr.SceneNode(glass, 0.3, 0.4, 0.5, 1.3, nr.Isometry3(cam["at"]), nr.Ball(30.0))
+    return nr.Scene(list(sc._nodes) + [ball], sc._lights, sc._background), cam
+
+
+def _gather_leg(w, h, reps):
+    import torch
+    from tools import standins
+    scenes = {}
+    for name, lanes in (("auto", None), ("lanes_1", "0"), ("lanes_8", "3"), ("lanes_64", "6")):
+        os.environ.pop("NRAYS_OCCLUSION_LANES", None)
+        if lanes is not None:
+            os.environ["NRAYS_OCCLUSION_LANES"] = lanes  # read when a handle is created
+        scenes[name], cam = standins.sponza_scene()
+        scenes[name].device_handle()
+    os.environ.pop("NRAYS_OCCLUSION_LANES", None)
+    pick = lambda names: {k: scenes[k] for k in names}  # noqa: E731
+    out = {}
+    for leg, group, cam_ in (("sponza", None, cam), ("sponza_glass_ball_double_branching",) + _glass_sponza()):
+        tp, tn, keys = _first_hit_points((scenes["auto"] if group is None else group, cam_), w, h)
+        n = tp.shape[0]
+        sub = torch.from_numpy(np.linspace(0, n - 1, min(16384, n)).astype(np.int64)).cuda()
+        many = pick(("auto", "lanes_1", "lanes_8")) if group is None else {"auto": group}
+        few = pick(("auto", "lanes_1", "lanes_8", "lanes_64")) if group is None else {"auto": group}
+        out[leg] = {"first_hits_16_dirs": _gather_input(many, tp, tn, keys, 16, max(1, reps // 4)),
+                    "subset_16384_points_64_dirs": _gather_input(few, tp[sub].contiguous(), tn[sub].contiguous(), keys[sub.cpu().numpy()], 64, reps)}
+    return out
 
 
 def _texels_row(sc, mesh, size, reps, mirror, rounds=5):
@@ -354,7 +442,7 @@ def _texels_leg(reps, quick):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json")
+    ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json, with --gather profiles/gather_rate.json")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--quick", action="store_true", help="320x180 instead of 1920x1080 (a rehearsal of the tool, not a measurement)")
     ap.add_argument("--coherence", action="store_true", help="add the CPU coherence figures of every batch, as given and reordered")
@@ -363,10 +451,11 @@ def main():
     ap.add_argument("--shade", action="store_true", help="time shade_hits beside trace_rays and closest_hits on the sponza stand-in with 1 and 8 lights, nothing else")
     ap.add_argument("--beside", default=None, help="with --shade: the JSON of an earlier run (another library), copied into this one under 'beside'")
     ap.add_argument("--occlusion", action="store_true", help="time occlusion_points beside intersects_rays on the same rays and the torch fold (leg e_sponza_occlusion), nothing else")
+    ap.add_argument("--gather", action="store_true", help="time gather_points beside building the rays with torch, trace_rays on them and the torch fold (leg h_sponza_gather), nothing else")
     ap.add_argument("--texels", action="store_true", help="time surface_texels, its two passes, shade_points on its texels and the numpy mirror (leg g_surface_texels), nothing else")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "trace_rays_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -382,6 +471,14 @@ def main():
 
     if a.texels:
         res["workloads"]["g_surface_texels"] = _texels_leg(a.reps, a.quick)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
+
+    if a.gather:
+        res["workloads"]["h_sponza_gather"] = _gather_leg(w, h, a.reps)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
