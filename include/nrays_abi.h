@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -449,6 +449,19 @@ int nrays_gather_points_device(NraysScene* scene, uint32_t n, const double* poin
 /* Same, every pointer (the two tables included) HOST memory.  Blocking. */
 int nrays_gather_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
                         const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags);
+/* The two entry points above with `flags` = 0 or NRAYS_RAYS_UNORDERED (any other bit -> NRAYS_ERR_BAD_ARG).  flags == 0 IS the entry point without _ex.  The hint
+ * means what it means for the ray batches: a statement about the input — the points come in no order that keeps neighbouring rays together (a light map's texels
+ * under many directions, gathered hits) — under which the library may trace the rays in an order of its own.  out_rgb is the value defined above, BIT FOR BIT,
+ * for every scene kind, double-branching included: only the time changes.  The rule and the switch are those of the ray batches, applied to the call's
+ * n * num_dirs rays: reordered from 2^19 rays, never under NRAYS_RAY_REORDER=0, always under =2; a hinted call that is not reordered runs the unhinted path.
+ * A reordered chunk bins its (point, direction) pairs by the key of the ray batches (each ray rebuilt in registers), traces them bin by bin, and folds per point.
+ * For that it holds, in the handle's workspace, 12 bytes of colour and 16 bytes of sort state per ray of ONE chunk (at most 2^22 rays) in every scene kind; the
+ * caller's interface stays per point: no ray, key or per-ray colour array crosses it.  Launches on the same stream; no read-back beyond the one double-branching
+ * scenes need anyway.  Everything else of the contracts above holds unchanged. */
+int nrays_gather_points_device_ex(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                  const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream);
+int nrays_gather_points_ex(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                           const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and
@@ -504,6 +517,16 @@ int nrays_debug_surface_texels_passes(NraysScene* scene, uint32_t node, uint32_t
 #define NRAYS_RAY_FRAME_DOUBLES 20
 int nrays_debug_ray_order(NraysScene* scene, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order,
                           double* out_frame, uint32_t out_info[4]);
+
+/* Test probe of the reordered gather: runs exactly the bounds, key and binning kernels of ONE reordered chunk of nrays_gather_points_device_ex
+ * (n * num_dirs <= 2^22) on n points.  Pair i * num_dirs + j is ray j of point i.
+ *   out_keys   n * num_dirs keys; the entries of a skipped point are left as the caller filled them,
+ *   out_order  n * num_dirs words, of which the first out_info[3] are written: the original pair indices in trace order (the live pairs, each once),
+ *   out_frame  NRAYS_RAY_FRAME_DOUBLES doubles: bit for bit the frame nrays_debug_ray_order computes from the live pairs' rays,
+ *   out_info   {K, B, 1 if a hinted call of n * num_dirs rays on this handle would be reordered, the number of live pairs}.  n == 0: out_info only.
+ * All HOST memory (the tables of params included).  Blocking.  Arguments are checked as by nrays_gather_points_ex; NULL outputs -> NRAYS_ERR_BAD_ARG. */
+int nrays_debug_gather_order(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                             const NraysGatherParams* params, uint64_t* out_keys, uint32_t* out_order, double* out_frame, uint32_t out_info[4]);
 
 /* Number of rows in the compact output buffer of a (possibly tiled) render. */
 uint32_t nrays_tile_rows(const NraysRenderParams* params);

@@ -564,6 +564,18 @@ impl GpuScene {
     /// indirect term.  The value is defined in include/nrays_abi.h (NraysGatherParams).
     pub fn gather_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32, max_depth: u32,
                          keys: Option<&[u64]>) -> Result<Vec<Vector3<f32>>, String> {
+        self.gather_points_flags(points, sample_dirs, rotations, bias, energy, max_depth, keys, 0)
+    }
+
+    /// `gather_points` for points that come in no useful order (NRAYS_RAYS_UNORDERED through nrays_gather_points_ex, as `trace_rays_unordered`): the library may
+    /// bin a chunk's (point, direction) pairs by a spatial key on the device and trace them in that order.  The colours are bit-identical to `gather_points`'.
+    pub fn gather_points_unordered(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32,
+                                   max_depth: u32, keys: Option<&[u64]>) -> Result<Vec<Vector3<f32>>, String> {
+        self.gather_points_flags(points, sample_dirs, rotations, bias, energy, max_depth, keys, NRAYS_RAYS_UNORDERED)
+    }
+
+    fn gather_points_flags(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32, max_depth: u32,
+                           keys: Option<&[u64]>, flags: u32) -> Result<Vec<Vector3<f32>>, String> {
         if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
         let n = points.len();
         let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
@@ -574,7 +586,10 @@ impl GpuScene {
                                          rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, energy, max_depth };
         let mut rgb = vec![0.0f32; 3 * n];
         let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
-        let rc = unsafe { nrays_gather_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, rgb.as_mut_ptr(), 0) };
+        let rc = unsafe {
+            if flags == 0 { nrays_gather_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, rgb.as_mut_ptr(), 0) }
+            else { nrays_gather_points_ex(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, rgb.as_mut_ptr(), flags) }
+        };
         if rc != NRAYS_OK { return Err(last_error()); }
         Ok((0..n).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect())
     }
@@ -584,6 +599,13 @@ impl GpuScene {
     pub unsafe fn gather_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: &NraysGatherParams,
                                        out_rgb: *mut f32, hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_gather_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_rgb, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// `gather_points_device` under NRAYS_RAYS_UNORDERED (nrays_gather_points_device_ex): the same values, bit for bit.
+    pub unsafe fn gather_points_device_unordered(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64,
+                                                 params: &NraysGatherParams, out_rgb: *mut f32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_gather_points_device_ex(self.raw, n, points, normals, hit_flags, keys, params, out_rgb, NRAYS_RAYS_UNORDERED, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 }

@@ -3,8 +3,9 @@
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
 // k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value;
-// k_gather_points (nrays_gather_points*) runs Scene::trace on the same rays and folds the colours (instantiated in gather_inst.hip).
-// Templates and inline device code only: ray_order.hip and gather_inst.hip both include this header.
+// k_gather_points (nrays_gather_points*) runs Scene::trace on the same rays and folds the colours (instantiated in gather_inst.hip);
+// k_gather_pairs_ordered traces the (point, direction) pairs of a reordered gather chunk in bin order (nrays_gather_points*_ex; gather_order_inst.hip).
+// Templates and inline device code only: ray_order.hip, gather_inst.hip and gather_order_inst.hip include this header.
 #pragma once
 #include "primary_kernel.h"
 
@@ -365,5 +366,61 @@ struct GatherLaunch {
     unsigned long long key_base; GatherSpec spec; const double* dirs; const double* rotations; float* out; float* ray_out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
 };
 bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
+
+// ---- the reordered form of a gather chunk (nrays_gather_points*_ex with NRAYS_RAYS_UNORDERED; host side and the binning kernels: ray_order.hip) -------------------
+// A chunk's (point, direction) pairs — pair i * num_dirs + j is ray j of point i — are binned by ray_key.h's key and traced in bin order, one lane per pair; the
+// rays exist in registers only, rebuilt from (i, j) wherever they are needed (bounds, keys, trace).  What crosses memory per ray is the sort state (key, rank,
+// order: 16 bytes) and the colour (12 bytes), both of ONE chunk, in the handle's workspace.
+struct GatherPoints { const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys; unsigned long long key_base; };
+// Bit 0 of a point's flags clear: the point is skipped — none of its pairs is live, neither its point nor its normal is read.
+NR_DEV bool gather_point_live(const GatherPoints& in, uint32_t i) { return !in.hit_flags || (in.hit_flags[i] & 1u) != 0u; }
+NR_DEV unsigned long long gather_point_key(const GatherPoints& in, uint32_t i) { return in.keys ? in.keys[i] : in.key_base + i; }
+// Ray j of LIVE point i, exactly as k_gather_points builds it (occlusion_frame / occlusion_dir: the one generator).
+NR_DEV void gather_pair_ray(const GatherPoints& in, uint32_t i, uint32_t j, const OcclusionSpec& G, const double* __restrict__ dirs, const double* __restrict__ rotations,
+                            d3& o, d3& d) {
+    const size_t i3 = 3 * (size_t)i;
+    const OccFrame f = occlusion_frame(D3(in.points[i3], in.points[i3 + 1], in.points[i3 + 2]), D3(in.normals[i3], in.normals[i3 + 1], in.normals[i3 + 2]),
+                                       gather_point_key(in, i), G, rotations);
+    o = f.o; d = occlusion_dir(f, G.num_rotations != 0u, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
+}
+
+// Lane t of the chunk traces pair order[t], t < *live (the number of placed pairs, known on the device only: the grid is sized by the chunk's `pairs` and the
+// lanes at or beyond *live idle).  The RayState is k_gather_points' — energy, weight 1, refr 1, key rng_hash(key_i, kSaltGather + j) in keyed scenes — with the
+// pair as its "pixel" always, and the chain's sum goes to ray_out[3 * pair ..] as k_trace_rays stores a ray's: the queue's rounds (double-branching scenes) and
+// k_gather_fold follow.  ray_out was cleared before: a skipped point's pairs are never placed and stay zero.  Every lane of a wave reaches trace_chain.
+template <bool STATS, int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_pairs_ordered(DScene S, uint32_t pairs, const uint32_t* __restrict__ order, const uint32_t* __restrict__ live,
+                                                                                        GatherPoints in, GatherSpec P, const double* __restrict__ dirs,
+                                                                                        const double* __restrict__ rotations, float* __restrict__ ray_out, QueueOut qo,
+                                                                                        DeviceCounters* ctr, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    const uint32_t k = P.num_dirs, placed = *live, m = placed < pairs ? placed : pairs; // (uniform for the grid)
+    const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
+    for (uint32_t base = blockIdx.x * kBlock; base < m; base += gridDim.x * kBlock) { // block-uniform trip count
+        const uint32_t t = base + threadIdx.x;
+        const uint32_t pair = t < m ? order[t] : 0xffffffffu;
+        const bool alive = pair < pairs; // (always for t < m: the order holds pair indices)
+        RayState ray;
+        ray.o = D3(0, 0, 0); ray.d = D3(0, 0, 1); ray.refr = 1.0; ray.energy = 0.0f; ray.weight = 0.0f; ray.key = 0; ray.pixel = 0;
+        if (alive) {
+            const uint32_t i = pair / k, j = pair - i * k;
+            gather_pair_ray(in, i, j, G, dirs, rotations, ray.o, ray.d);
+            ray.energy = P.energy; ray.weight = 1.0f; ray.pixel = pair;
+            ray.key = P.keyed ? rng_hash(gather_point_key(in, i), kSaltGather + j) : 0ULL;
+        }
+        const f3 c = trace_chain<STATS, FEAT>(S, st, alive, ray, 0u, P.max_depth, qo, cnt, P.keyed != 0u);
+        if (alive) { float* o = ray_out + 3 * (size_t)pair; o[0] = c.x; o[1] = c.y; o[2] = c.z; }
+    }
+    flush_counters(ctr, cnt, STATS);
+}
+
+// The arguments of one k_gather_pairs_ordered launch; the instantiations are compiled in gather_order_inst.hip, as k_gather_points' are in gather_inst.hip.
+struct GatherPairsLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t pairs; const uint32_t* order; const uint32_t* live; GatherPoints in; GatherSpec spec; const double* dirs;
+    const double* rotations; float* ray_out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
+};
+bool launch_gather_pairs_ordered(const GatherPairsLaunch& a, bool stats, int feat);
 
 } // namespace nrays

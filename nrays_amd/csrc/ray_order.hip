@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points*, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -86,6 +86,26 @@ __global__ void __launch_bounds__(kOrderBlock) k_ray_frame(const double* __restr
     }
 }
 
+// The place of a lane's ray inside its bin.  The lanes of the wave that meet in one bin issue ONE atomic: their first lane adds their number, the others take their
+// places from it.  The groups are found first (wave-uniform loop, one round per distinct bin, no memory access), then every group's atomic is in flight at once.
+// Every lane of the wave calls it; an inactive lane issues nothing and its result means nothing.
+__device__ __forceinline__ uint32_t wave_bin_rank(bool active, uint32_t bin, uint32_t* __restrict__ bins) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t leader = lane, below = 0u, count = 1u;
+    unsigned long long todo = __ballot(active);
+    while (todo) {
+        const int l = __ffsll((long long)todo) - 1;
+        const uint32_t b = (uint32_t)__shfl((int)bin, l);
+        const unsigned long long same = __ballot(active && bin == b);
+        if (active && bin == b) { leader = (uint32_t)l; below = (uint32_t)__popcll(same & ((1ull << lane) - 1ull)); count = (uint32_t)__popcll(same); }
+        todo &= ~same;
+    }
+    uint32_t first = 0u;
+    if (active && leader == lane) first = atomicAdd(&bins[bin], count);
+    first = (uint32_t)__shfl((int)first, (int)leader);
+    return first + below;
+}
+
 // One lane per ray (every lane of a workgroup stays to the end: the run detection below shuffles across the wave).
 __global__ void __launch_bounds__(kOrderBlock) k_ray_keys(uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd, const double* __restrict__ frame,
                                                           uint64_t* __restrict__ keys, uint32_t* __restrict__ bins, uint32_t* __restrict__ rank) {
@@ -102,22 +122,8 @@ __global__ void __launch_bounds__(kOrderBlock) k_ray_keys(uint32_t n, const doub
         keys[i] = key;
         bin = (uint32_t)(key >> (kRayKeyBits - kRayBinBits)); // < 2^B: a key is below 2^K
     }
-    // The lanes of the wave that meet in one bin issue ONE atomic: their first lane adds their number, the others take their places from it.
-    // The groups are found first (wave-uniform loop, one round per distinct bin, no memory access), then every group's atomic is in flight at once.
-    const uint32_t lane = threadIdx.x & 63u;
-    uint32_t leader = lane, below = 0u, count = 1u;
-    unsigned long long todo = __ballot(active);
-    while (todo) {
-        const int l = __ffsll((long long)todo) - 1;
-        const uint32_t b = (uint32_t)__shfl((int)bin, l);
-        const unsigned long long same = __ballot(active && bin == b);
-        if (active && bin == b) { leader = (uint32_t)l; below = (uint32_t)__popcll(same & ((1ull << lane) - 1ull)); count = (uint32_t)__popcll(same); }
-        todo &= ~same;
-    }
-    uint32_t first = 0u;
-    if (active && leader == lane) first = atomicAdd(&bins[bin], count);
-    first = (uint32_t)__shfl((int)first, (int)leader);
-    if (active) rank[i] = first + below;
+    const uint32_t r = wave_bin_rank(active, bin, bins);
+    if (active) rank[i] = r;
 }
 
 // Exclusive prefix sum of the bin counters in place, three launches (as bvh_device.hip's exclusive_scan_u32; a thread owns 16 consecutive items).
@@ -164,6 +170,59 @@ __global__ void __launch_bounds__(kOrderBlock) k_ray_place(uint32_t n, const uin
     if (at < n) order[at] = i; // (always: the counts sum to n)
 }
 
+// ---- the same three steps on the (point, direction) pairs of a gather chunk (nrays_gather_points*_ex; ray_batch_kernel.h: gather_pair_ray) -----------------------
+// Pair r = i * num_dirs + j is ray j of point i; the ray is rebuilt in registers, and only the pairs of LIVE points take part: a skipped point's point and normal
+// are never read (they may be NaN), its pairs enter no bounds, take no bin and no place.
+// k_gather_bounds is k_ray_bounds on the rays of the live pairs: min / max are exact and order-free, so k_ray_frame gives bit for bit the frame ray_order_chunk
+// computes from those rays as arrays.
+__global__ void __launch_bounds__(kOrderBlock) k_gather_bounds(uint32_t pairs, GatherPoints in, OcclusionSpec G, const double* __restrict__ dirs,
+                                                               const double* __restrict__ rotations, SceneBox box, double* __restrict__ partial) {
+    __shared__ double s[4 * 10];
+    RayBounds b; rk_bounds_init(b);
+    for (uint32_t r = blockIdx.x * kOrderBlock + threadIdx.x; r < pairs; r += gridDim.x * kOrderBlock) {
+        const uint32_t i = r / G.num_dirs, j = r - i * G.num_dirs;
+        if (!gather_point_live(in, i)) continue;
+        d3 ro, rd;
+        gather_pair_ray(in, i, j, G, dirs, rotations, ro, rd);
+        const double o[3] = {ro.x, ro.y, ro.z}, d[3] = {rd.x, rd.y, rd.z};
+        rk_bounds_add(b, o, d, box.v);
+    }
+    reduce_bounds(b, s);
+    if (threadIdx.x == 0u) for (int k = 0; k < 5; ++k) { partial[blockIdx.x * 10u + k] = b.lo[k]; partial[blockIdx.x * 10u + 5 + k] = b.hi[k]; }
+}
+// One lane per pair (every lane of a workgroup stays to the end, as in k_ray_keys): key, bin, rank of the live pairs.
+__global__ void __launch_bounds__(kOrderBlock) k_gather_keys(uint32_t pairs, GatherPoints in, OcclusionSpec G, const double* __restrict__ dirs,
+                                                             const double* __restrict__ rotations, const double* __restrict__ frame, uint64_t* __restrict__ keys,
+                                                             uint32_t* __restrict__ bins, uint32_t* __restrict__ rank) {
+    double fr[kRayFrameDoubles];
+    for (int k = 0; k < kRayFrameDoubles; ++k) fr[k] = frame[k]; // wave-uniform
+    RayKeyFrame f; rk_frame_decode(fr, f);
+    const uint32_t r = blockIdx.x * kOrderBlock + threadIdx.x;
+    const uint32_t i = r / G.num_dirs, j = r - i * G.num_dirs;
+    const bool active = r < pairs && gather_point_live(in, i);
+    uint32_t bin = 0xffffffffu;
+    if (active) {
+        d3 ro, rd;
+        gather_pair_ray(in, i, j, G, dirs, rotations, ro, rd);
+        const double o[3] = {ro.x, ro.y, ro.z}, d[3] = {rd.x, rd.y, rd.z};
+        const uint64_t key = rk_key(f, o, d);
+        keys[r] = key;
+        bin = (uint32_t)(key >> (kRayKeyBits - kRayBinBits)); // < 2^B
+    }
+    const uint32_t at = wave_bin_rank(active, bin, bins);
+    if (active) rank[r] = at;
+}
+// start[]: the scanned counters, with the number of live pairs in start[2^B] (the scan ran over 2^B + 1 words, the last one zero).
+__global__ void __launch_bounds__(kOrderBlock) k_gather_place(uint32_t pairs, uint32_t num_dirs, const uint32_t* __restrict__ hit_flags, const uint64_t* __restrict__ keys,
+                                                              const uint32_t* __restrict__ rank, const uint32_t* __restrict__ start, uint32_t* __restrict__ order) {
+    const uint32_t r = blockIdx.x * kOrderBlock + threadIdx.x;
+    if (r >= pairs) return;
+    if (hit_flags && (hit_flags[r / num_dirs] & 1u) == 0u) return;
+    const uint32_t bin = (uint32_t)(keys[r] >> (kRayKeyBits - kRayBinBits)) & (kNumBins - 1u);
+    const uint32_t at = start[bin] + rank[r];
+    if (at < pairs) order[at] = r; // (always: the counts sum to the number of live pairs)
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------------------
 static void free_per_ray(TraceWorkspace* w) {
     if (w->d_ray_keys) (void)hipFree(w->d_ray_keys);
@@ -184,8 +243,8 @@ static int ray_order_ensure(TraceWorkspace* w, uint32_t n) {
     if (n > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "ray_order_ensure: more rays than a chunk");
     if (!w->d_ray_frame) HIP_TRY(hipMalloc((void**)&w->d_ray_frame, kRayFrameDoubles * sizeof(double)));
     if (!w->d_ray_partial) HIP_TRY(hipMalloc((void**)&w->d_ray_partial, (size_t)kBoundsMaxGrid * 10 * sizeof(double)));
-    if (!w->d_ray_bins) HIP_TRY(hipMalloc((void**)&w->d_ray_bins, (size_t)kNumBins * sizeof(uint32_t)));
-    if (!w->d_ray_scan) HIP_TRY(hipMalloc((void**)&w->d_ray_scan, (size_t)((kNumBins + kScanBlock - 1u) / kScanBlock) * sizeof(uint32_t)));
+    if (!w->d_ray_bins) HIP_TRY(hipMalloc((void**)&w->d_ray_bins, (size_t)(kNumBins + 1u) * sizeof(uint32_t))); // (+ 1: gather_order_chunk's total)
+    if (!w->d_ray_scan) HIP_TRY(hipMalloc((void**)&w->d_ray_scan, (size_t)((kNumBins + 1u + kScanBlock - 1u) / kScanBlock) * sizeof(uint32_t)));
     if (n > w->order_rays) {
         free_per_ray(w);
         HIP_TRY(hipMalloc((void**)&w->d_ray_keys, (size_t)n * sizeof(uint64_t)));
@@ -664,13 +723,19 @@ static int occlusion_points_host_impl(NraysScene* sc, uint32_t n, const Occlusio
 }
 
 // ---- nrays_gather_points*: the mean of Scene::trace over the hemisphere rays of caller-supplied points, the rays built on the device --------------------------
-static int check_gather_args(const NraysScene* sc, const OcclusionIn& in, const NraysGatherParams* p, const float* out_rgb, uint32_t flags) {
+// `hinted`: the _ex entry points, which take NRAYS_RAYS_UNORDERED; the others take no flag at all.
+static int check_gather_args(const NraysScene* sc, const OcclusionIn& in, const NraysGatherParams* p, const float* out_rgb, uint32_t flags, bool hinted) {
     if (!sc || !in.points || !in.normals || !p || !p->dirs || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_dirs must be in 1 .. 1024");
     if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_rotations > 1024, or rotations is NULL");
     if (!std::isfinite(p->bias) || !std::isfinite(p->energy)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: bias and energy must be finite");
+    if (hinted) return check_ray_flags(flags);
     if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_points: flags must be 0");
     return NRAYS_OK;
+}
+// A hinted call is reordered by the rule of the other batches, applied to its rays: n * num_dirs of them.
+static bool gather_reorders(const NraysScene* sc, uint32_t n, const NraysGatherParams* p, uint32_t flags) {
+    return (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, (uint32_t)std::min<uint64_t>((uint64_t)n * p->num_dirs, 0xffffffffull));
 }
 static uint32_t gather_chunk(const NraysGatherParams* p) { return std::max<uint32_t>(1u, kTraceChunk / p->num_dirs); } // points per chunk: at most kTraceChunk rays
 // Double-branching scenes: the fold that k_gather_points left to the end of the chunk's k_bounce rounds — point i's num_dirs finished ray colours, summed in the
@@ -688,43 +753,89 @@ __global__ void __launch_bounds__(kOrderBlock) k_gather_fold(const float* __rest
 // device copies of the tables.  The permutation is trace_chunk's, the lanes per point are occlusion_chunk_launch's.  Double-branching scenes: the kernel stores the
 // chunk's ray colours, trace_chunk's rounds run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by trace_chunk's
 // rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
+// The reorder of one gather chunk's pairs (pairs = nc * num_dirs <= kTraceChunk), enqueued on `stream` as ray_order_chunk enqueues a ray chunk's: launches only.
+// Afterwards w->d_ray_order[0 .. m) holds the m live pairs in trace order and w->d_ray_bins[2^B] holds m; d_ray_keys / d_ray_frame hold the live pairs' keys and the frame.
+static int gather_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t pairs, const GatherPoints& in, const OcclusionSpec& G, const double* dirs, const double* rotations,
+                              hipStream_t stream) {
+    if (pairs == 0u || pairs > w->order_rays) return set_last_error(NRAYS_ERR_BAD_ARG, "gather_order_chunk: workspace too small");
+    SceneBox box;
+    for (int a = 0; a < 3; ++a) { box.v[a] = (double)sc->facts.host.bounds_mn[a]; box.v[3 + a] = (double)sc->facts.host.bounds_mx[a]; }
+    const uint32_t pair_grid = (pairs + kOrderBlock - 1u) / kOrderBlock, parts = pair_grid < kBoundsMaxGrid ? pair_grid : kBoundsMaxGrid;
+    const uint32_t words = kNumBins + 1u, scan_grid = (words + kScanBlock - 1u) / kScanBlock; // (the last word stays zero and becomes the total)
+    HIP_TRY(hipMemsetAsync(w->d_ray_bins, 0, (size_t)words * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_gather_bounds, dim3(parts), dim3(kOrderBlock), 0, stream, pairs, in, G, dirs, rotations, box, w->d_ray_partial);
+    hipLaunchKernelGGL(k_ray_frame, dim3(1), dim3(kOrderBlock), 0, stream, (const double*)w->d_ray_partial, parts, box, w->d_ray_frame);
+    hipLaunchKernelGGL(k_gather_keys, dim3(pair_grid), dim3(kOrderBlock), 0, stream, pairs, in, G, dirs, rotations, (const double*)w->d_ray_frame, w->d_ray_keys, w->d_ray_bins, w->d_ray_rank);
+    hipLaunchKernelGGL(k_bin_sums, dim3(scan_grid), dim3(kOrderBlock), 0, stream, (const uint32_t*)w->d_ray_bins, words, w->d_ray_scan);
+    hipLaunchKernelGGL(k_bin_scan, dim3(1), dim3(1024), 0, stream, w->d_ray_scan, scan_grid);
+    hipLaunchKernelGGL(k_bin_apply, dim3(scan_grid), dim3(kOrderBlock), 0, stream, w->d_ray_bins, words, (const uint32_t*)w->d_ray_scan);
+    hipLaunchKernelGGL(k_gather_place, dim3(pair_grid), dim3(kOrderBlock), 0, stream, pairs, G.num_dirs, in.hit_flags, (const uint64_t*)w->d_ray_keys, (const uint32_t*)w->d_ray_rank,
+                       (const uint32_t*)w->d_ray_bins, w->d_ray_order);
+    HIP_TRY(hipGetLastError());
+    return NRAYS_OK;
+}
+
+// One chunk (nc <= gather_chunk) of nrays_gather_points_device; `in` and `out` are the chunk's, key_base the index of its first point in the batch, dirs / rotations
+// device copies of the tables.  The permutation is trace_chunk's, the lanes per point are occlusion_chunk_launch's.  Double-branching scenes: the kernel stores the
+// chunk's ray colours, trace_chunk's rounds run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by trace_chunk's
+// rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
+// `reorder` (a hinted call that pays, nrays_gather_points*_ex): the chunk's pairs are binned (gather_order_chunk) and traced in bin order by k_gather_pairs_ordered, every
+// scene through the cleared per-ray colours and k_gather_fold: 12 bytes of colour and 16 of sort state a ray of the chunk, whatever the scene.
 static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const OcclusionIn& in, unsigned long long key_base, const NraysGatherParams* p,
-                               const double* dirs, const double* rotations, float* out, hipStream_t stream) {
+                               const double* dirs, const double* rotations, float* out, bool reorder, hipStream_t stream) {
     const bool queued = sc->facts.host.any_double_branch;
-    const size_t ray_floats = 3 * (size_t)nc * p->num_dirs; // (nc * num_dirs <= kTraceChunk)
+    const uint32_t pairs = nc * p->num_dirs; // (<= kTraceChunk)
+    const size_t ray_floats = 3 * (size_t)pairs;
     if (queued) {
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * nc * p->num_dirs, 1u << 16), 1ull << 27);
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * pairs, 1u << 16), 1ull << 27);
         int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
         if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, ray_floats, stream);
-        if (rc == NRAYS_OK) rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
         if (rc != NRAYS_OK) return rc;
     }
-    float* ray_out = queued ? (float*)w->d_gather_rays : nullptr;
+    if (queued || reorder) {
+        const int rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
+        if (rc != NRAYS_OK) return rc;
+    }
+    float* ray_out = queued || reorder ? (float*)w->d_gather_rays : nullptr;
     HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
     unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
     QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
-    const int lp = occlusion_lanes_log2(sc, p->num_dirs);
-    const uint32_t slots = nc << lp; // (2^lp <= num_dirs)
-    const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
     const GatherSpec spec{p->num_dirs, p->num_rotations, p->bias, p->energy, p->max_depth, sc->facts.host.any_area_light ? 1u : 0u};
     const bool stats = sc->facts.d.no_elide != 0u;
-    const GatherLaunch a{grid, stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base, spec, dirs, rotations, out, ray_out, &qo,
-                         w->d_counters, w->d_spill};
-    if (!launch_gather_points(a, stats, !stats && batch_mesh_only(sc) ? (int)kFeatMesh : (int)kFeatAll, lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_points: no such permutation");
+    const int feat = !stats && batch_mesh_only(sc) ? (int)kFeatMesh : (int)kFeatAll;
+    if (reorder) {
+        const GatherPoints pts{in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base};
+        int rc = ray_order_ensure(w, pairs);
+        if (rc == NRAYS_OK) rc = gather_order_chunk(sc, w, pairs, pts, OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, 0.0}, dirs, rotations, stream);
+        if (rc != NRAYS_OK) return rc;
+        HIP_TRY(hipMemsetAsync(ray_out, 0, ray_floats * sizeof(float), stream)); // (a skipped point's pairs are never traced: exact zeros)
+        const uint32_t grid = std::min<uint32_t>((pairs + kBlock - 1) / kBlock, (uint32_t)kMaxGrid); // (by the chunk's pairs: the live count stays on the device)
+        const GatherPairsLaunch a{grid, stream, &sc->facts.d, pairs, w->d_ray_order, w->d_ray_bins + kNumBins, pts, spec, dirs, rotations, ray_out, &qo, w->d_counters, w->d_spill};
+        if (!launch_gather_pairs_ordered(a, stats, feat)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_pairs_ordered: no such permutation");
+    } else {
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs);
+        const uint32_t slots = nc << lp; // (2^lp <= num_dirs)
+        const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const GatherLaunch a{grid, stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base, spec, dirs, rotations, out, ray_out, &qo,
+                             w->d_counters, w->d_spill};
+        if (!launch_gather_points(a, stats, feat, lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_points: no such permutation");
+    }
     HIP_TRY(hipGetLastError());
-    if (!queued) return NRAYS_OK;
-    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, stats, p->max_depth, ray_out, ray_floats, sc->facts.num_cus};
+    if (!ray_out) return NRAYS_OK;
     uint32_t overflowed = 0u;
-    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
-    if (rc != NRAYS_OK) return rc;
+    if (queued) {
+        const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, stats, p->max_depth, ray_out, ray_floats, sc->facts.num_cus};
+        const int rc = run_bounce_rounds(rounds, stream, &overflowed);
+        if (rc != NRAYS_OK) return rc;
+    }
     hipLaunchKernelGGL(k_gather_fold, dim3((nc + kOrderBlock - 1u) / kOrderBlock), dim3(kOrderBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
     HIP_TRY(hipGetLastError());
     if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some gathered colours are incomplete");
     return NRAYS_OK;
 }
 
-static int gather_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, hipStream_t stream) {
-    if (check_gather_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+static int gather_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted, hipStream_t stream) {
+    if (check_gather_args(sc, in, p, out_rgb, flags, hinted) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->facts.device));
     TraceWorkspace* w = nullptr;
@@ -732,9 +843,10 @@ static int gather_points_device_impl(NraysScene* sc, uint32_t n, const Occlusion
     if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
     if (rc != NRAYS_OK) return rc;
     const uint32_t chunk = gather_chunk(p);
+    const bool reorder = gather_reorders(sc, n, p, flags);
     for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
         const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
-        rc = gather_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, p->dirs, p->rotations, out_rgb + 3 * (size_t)c0, stream);
+        rc = gather_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, p->dirs, p->rotations, out_rgb + 3 * (size_t)c0, reorder, stream);
     }
     batch_end(sc, w, stream);
     return rc;
@@ -743,8 +855,8 @@ static int gather_points_device_impl(NraysScene* sc, uint32_t n, const Occlusion
 // The blocking form, through the workspace's staging buffer as occlusion_points_host_impl: the two tables first, then per staged point kGatherStageBytes —
 // point, normal (3 f64), key (u64), colour (3 f32), hit flags (32 bits), the 8-byte fields first.
 constexpr size_t kGatherStageBytes = 72;
-static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags) {
-    if (check_gather_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted) {
+    if (check_gather_args(sc, in, p, out_rgb, flags, hinted) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->facts.device));
     TraceWorkspace* w = nullptr;
@@ -766,6 +878,7 @@ static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn
     hipError_t e = up(s_dirs, p->dirs, 24 * (size_t)p->num_dirs);
     if (e == hipSuccess) e = up(s_rot, p->rotations, 16 * (size_t)p->num_rotations);
     if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather tables upload: ") + hipGetErrorString(e));
+    const bool reorder = gather_reorders(sc, n, p, flags);
     for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
         const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
         const OcclusionIn h = occlusion_in_at(in, c0);
@@ -774,7 +887,7 @@ static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn
         if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
         if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
         if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("gather batch upload: ") + hipGetErrorString(e)); break; }
-        rc = gather_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, stream);
+        rc = gather_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, reorder, stream);
         if (rc != NRAYS_OK) break;
         e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_c, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
         const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
@@ -1153,11 +1266,19 @@ int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points,
 
 int nrays_gather_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                                const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream) {
-    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, (hipStream_t)hip_stream);
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_gather_points_device_ex(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                  const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream) {
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true, (hipStream_t)hip_stream);
 }
 int nrays_gather_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                         const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
-    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags);
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false);
+}
+int nrays_gather_points_ex(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                           const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true);
 }
 
 int nrays_surface_texels_device(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,
@@ -1202,6 +1323,58 @@ int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, con
     }
     (void)hipFree(d_od);
     if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_ray_order: ") + hipGetErrorString(e));
+    return rc;
+}
+
+int nrays_debug_gather_order(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                             const NraysGatherParams* params, uint64_t* out_keys, uint32_t* out_order, double* out_frame, uint32_t out_info[4]) {
+    if (!out_keys || !out_order || !out_frame || !out_info) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_gather_args(sc, OcclusionIn{points, normals, hit_flags, keys}, params, (const float*)out_frame /* (none is written: any non-NULL address) */, 0u, true) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    const uint64_t pairs64 = (uint64_t)n * params->num_dirs;
+    if (pairs64 > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_debug_gather_order: at most one chunk (n * num_dirs <= 2^22)");
+    const uint32_t pairs = (uint32_t)pairs64;
+    out_info[0] = (uint32_t)kRayKeyBits; out_info[1] = (uint32_t)kRayBinBits; out_info[2] = reorder_pays(sc, pairs) ? 1u : 0u; out_info[3] = 0u;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = ray_order_ensure(w, pairs);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    // the tables, then per point: point, normal (3 f64), key (u64), hit flags (32 bits) — the 8-byte fields first
+    const size_t table = 3 * (size_t)params->num_dirs + 2 * (size_t)params->num_rotations;
+    double* d_all = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_all, table * sizeof(double) + (size_t)n * 60));
+    double* d_dirs = d_all; double* d_rot = d_dirs + 3 * (size_t)params->num_dirs; double* d_p = d_all + table; double* d_n = d_p + 3 * (size_t)n;
+    uint64_t* d_k = (uint64_t*)(d_n + 3 * (size_t)n); uint32_t* d_hf = (uint32_t*)(d_k + n);
+    rc = batch_begin(sc, w, stream);
+    hipError_t e = hipSuccess;
+    if (rc == NRAYS_OK) {
+        auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+        e = up(d_dirs, params->dirs, 24 * (size_t)params->num_dirs);
+        if (e == hipSuccess) e = up(d_rot, params->rotations, 16 * (size_t)params->num_rotations);
+        if (e == hipSuccess) e = up(d_p, points, 24 * (size_t)n);
+        if (e == hipSuccess) e = up(d_n, normals, 24 * (size_t)n);
+        if (e == hipSuccess) e = up(d_k, keys, 8 * (size_t)n);
+        if (e == hipSuccess) e = up(d_hf, hit_flags, 4 * (size_t)n);
+        if (e == hipSuccess) e = up(w->d_ray_keys, out_keys, (size_t)pairs * sizeof(uint64_t)); // (a skipped point's entries come back as the caller filled them)
+        if (e == hipSuccess) {
+            const GatherPoints pts{d_p, d_n, hit_flags ? d_hf : nullptr, keys ? (const unsigned long long*)d_k : nullptr, 0ull};
+            rc = gather_order_chunk(sc, w, pairs, pts, OcclusionSpec{params->num_dirs, params->num_rotations, params->bias, 0.0}, d_dirs, params->num_rotations ? d_rot : nullptr, stream);
+        }
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(&out_info[3], w->d_ray_bins + kNumBins, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipStreamSynchronize(stream);
+        if (e == hipSuccess && rc == NRAYS_OK && out_info[3] > pairs) rc = set_last_error(NRAYS_ERR_HIP, "nrays_debug_gather_order: more pairs placed than the chunk holds");
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_keys, w->d_ray_keys, (size_t)pairs * sizeof(uint64_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK && out_info[3]) e = hipMemcpyAsync(out_order, w->d_ray_order, (size_t)out_info[3] * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && rc == NRAYS_OK) e = hipMemcpyAsync(out_frame, w->d_ray_frame, NRAYS_RAY_FRAME_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream);
+        if (e == hipSuccess) e = es;
+        batch_end(sc, w, stream);
+    }
+    (void)hipFree(d_all);
+    if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_gather_order: ") + hipGetErrorString(e));
     return rc;
 }
 

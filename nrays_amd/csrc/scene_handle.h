@@ -71,10 +71,11 @@ struct TraceWorkspace {
     // Batches the caller called unordered (NRAYS_RAYS_UNORDERED; ray_order.hip): created on the first such chunk, grown only when a chunk holds more rays
     uint64_t* d_ray_keys = nullptr; uint32_t* d_ray_rank = nullptr; uint32_t* d_ray_order = nullptr; size_t order_rays = 0; // per ray: key, place inside its bin, order[j] = ray traced j-th
     double* d_ray_frame = nullptr; double* d_ray_partial = nullptr; // the chunk's quantisation frame (ray_key.h) and the per-workgroup bounds it is reduced from
-    uint32_t* d_ray_bins = nullptr; uint32_t* d_ray_scan = nullptr; // bin counts, scanned in place into bin starts; block sums of that scan
+    uint32_t* d_ray_bins = nullptr; uint32_t* d_ray_scan = nullptr; // bin counts (+ one word: a gather chunk's total), scanned in place into bin starts; block sums of that scan
     // nrays_surface_texels* (surface_texels_kernel.h): the owner word of every lattice point, the scanned tile counts of the node's triangle records, the block sums of that scan + the total
     void* d_texel_owner = nullptr; size_t texel_owner_words = 0; void* d_texel_off = nullptr; size_t texel_off_words = 0; unsigned long long* d_texel_blocks = nullptr;
-    // nrays_gather_points* in double-branching scenes: the colours of one chunk's rays (x 3), between k_gather_points, the queue's rounds and k_gather_fold
+    // nrays_gather_points* in double-branching scenes and in every reordered chunk of the _ex forms: the colours of one chunk's rays (x 3), between k_gather_points /
+    // k_gather_pairs_ordered, the queue's rounds and k_gather_fold
     void* d_gather_rays = nullptr; size_t gather_ray_floats = 0;
 };
 

@@ -376,14 +376,14 @@ class Scene:
         """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
 
-    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None):
+    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None, unordered=False):
         """The incoming light at caller-supplied surface points of this scene: gather_points(self, ...)."""
-        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys)
+        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
-                      device=None):
+                      device=None, unordered=False):
         """The indirect term of a light map of mesh node `node`: bake_indirect(self, node, ...)."""
-        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device)
+        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
@@ -979,7 +979,7 @@ def _gather_settings(energy, max_depth):
     return energy, int(max_depth)
 
 
-def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None):
+def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None, unordered=False):
     """The light arriving at n caller-supplied surface points from the rest of the scene — a light map's indirect term —, through nrays_gather_points_device /
     nrays_gather_points: per point the library builds the len(sample_dirs) hemisphere rays of occlusion_points() ON THE DEVICE (the same rays bit for bit:
     occlusion_rays()), runs Scene::trace — the query of trace_rays() — on each and folds the colours in order: (n, 3) float32, the mean.  It equals trace_rays
@@ -988,8 +988,13 @@ def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3
     Also `scene.gather_points(...)` on Scene and FileScene; gather_hits() feeds it from closest_hits(), bake_indirect() from surface_texels().
     `points`, `normals`, `sample_dirs`, `rotations`, `bias`, `hit_flags`, `keys`: as for occlusion_points.  `energy`: RayWithEnergy::energy of every gathered
     ray (1.0: a primary ray's; less ends the reflection / refraction recursion earlier).  `max_depth` as in render().
+    `unordered=True` (nrays_gather_points_device_ex / nrays_gather_points_ex with NRAYS_RAYS_UNORDERED): the rays of neighbouring points do not stay together,
+    so the library may bin a chunk's (point, direction) pairs on the device and trace them bin by bin, as trace_rays(unordered=True) does with rays from memory.
+    The result is bit-identical; a chunk then keeps 28 bytes a ray in the handle's workspace.  False calls the entry points without _ex.
     numpy arrays -> nrays_gather_points (blocking), a numpy array.  torch tensors on the scene's GPU (float64; hit_flags int32 / uint32; keys int64 / uint64;
     the tables tensors or anything numpy takes) -> nrays_gather_points_device on torch.cuda.current_stream(), a tensor."""
+    if not isinstance(unordered, (bool, np.bool_)):
+        raise ValueError("unordered must be True or False, got %r" % (unordered,))
     n = _n_of(points, normals, ("points", "normals"))
     for name, a in (("hit_flags", hit_flags), ("keys", keys)):
         _check_vec(name, a, n)
@@ -1010,8 +1015,12 @@ def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3
         params = abi.NraysGatherParams(L.shape[0], 0 if rot is None else rot.shape[0], ptr(L), ptr(rot), bias, energy, max_depth)
         lib = abi.load_hip_lib()
         with torch.cuda.device(points.device):
-            abi.check(lib.nrays_gather_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(rgb), 0,
-                                                     torch.cuda.current_stream().cuda_stream))
+            if unordered:
+                abi.check(lib.nrays_gather_points_device_ex(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(rgb), abi.RAYS_UNORDERED,
+                                                            torch.cuda.current_stream().cuda_stream))
+            else:
+                abi.check(lib.nrays_gather_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(rgb), 0,
+                                                         torch.cuda.current_stream().cuda_stream))
         return rgb
     if any(_is_tensor(a) for a in (normals, hit_flags, keys, L, rot)):
         raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
@@ -1022,17 +1031,21 @@ def gather_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3
     ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
     params = abi.NraysGatherParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, energy, max_depth)
     lib = abi.load_hip_lib()
-    abi.check(lib.nrays_gather_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
-                                      ptr(rgb, C.c_float), 0))
+    if unordered:
+        abi.check(lib.nrays_gather_points_ex(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
+                                             ptr(rgb, C.c_float), abi.RAYS_UNORDERED))
+    else:
+        abi.check(lib.nrays_gather_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
+                                          ptr(rgb, C.c_float), 0))
     return rgb
 
 
-def gather_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, keys=None):
+def gather_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, keys=None, unordered=False):
     """The incoming light at the closest hits of caller-supplied rays: gather_points() at the hits of `hits = closest_hits(scene, origins, dirs)` (a CastHits
     with normal and flags), on the side the rays came from — the points and normals of occlusion_hits(), built the same way.  Misses come back as zeros.
-    numpy or torch as the inputs."""
+    numpy or torch as the inputs.  `unordered`: as for gather_points."""
     points, normals = _hit_points("gather_hits", origins, dirs, hits)
-    return gather_points(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=hits.flags, keys=keys)
+    return gather_points(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=hits.flags, keys=keys, unordered=unordered)
 
 
 # ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------
@@ -1206,13 +1219,14 @@ def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, fli
 
 
 def bake_indirect(scene, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
-                  device=None):
+                  device=None, unordered=False):
     """The indirect term of a light map of TriMesh node `node`: the mean incoming light at the texels of a width x height map, (height, width, 3) float32 in
     NraysTexture row order (row 0 = the bottom row): gather_points() with these arguments on surface_texels().  Uncovered texels are zeros.  `keys`
     (width * height,) RNG keys (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, two calls on one
-    stream; `keys` is then a tensor (the tables may be anything numpy takes).  Also `scene.bake_indirect(node, ...)` on Scene and FileScene."""
+    stream; `keys` is then a tensor (the tables may be anything numpy takes).  `unordered`: as for gather_points.  Also
+    `scene.bake_indirect(node, ...)` on Scene and FileScene."""
     tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals",), device=device)
-    rgb = gather_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=tx.flags, keys=keys)
+    rgb = gather_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=tx.flags, keys=keys, unordered=unordered)
     return rgb.reshape(int(height), int(width), 3)
 
 
@@ -1233,6 +1247,31 @@ def ray_order(scene, origins, dirs):
     abi.check(abi.load_hip_lib().nrays_debug_ray_order(scene.device_handle(), n, o.ctypes.data_as(dp), d.ctypes.data_as(dp), keys.ctypes.data_as(C.POINTER(C.c_uint64)),
                                                        order.ctypes.data_as(C.POINTER(C.c_uint32)), frame.ctypes.data_as(dp), info))
     return keys, order, frame, (int(info[0]), int(info[1]), bool(info[2]))
+
+
+def gather_order(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, hit_flags=None, keys=None):
+    """Test probe (nrays_debug_gather_order): the bounds, key and binning kernels of one reordered chunk of gather_points(unordered=True) on n points with
+    n * len(sample_dirs) <= 2^22 (numpy).  Pair i * k + j is ray j of point i.  Returns (keys uint64 (n * k,) — zeros at a skipped point's pairs —,
+    order uint32 (m,) — the m live pairs in trace order —, frame float64 (abi.RAY_FRAME_DOUBLES,), (K, B, reordered, m)) as ray_order() does for rays."""
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    if any(_is_tensor(a) for a in (points, normals, hit_flags, keys, L, rot)):
+        raise ValueError("gather_order takes numpy arrays")
+    pairs = n * len(L)
+    if pairs > 1 << 22:
+        raise ValueError("at most one chunk (n * len(sample_dirs) <= 2^22)")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    out_keys, order = np.zeros(pairs, np.uint64), np.zeros(pairs, np.uint32)
+    frame, info = np.zeros(abi.RAY_FRAME_DOUBLES, np.float64), (C.c_uint32 * 4)()
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    params = abi.NraysGatherParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, 1.0, 0)
+    abi.check(abi.load_hip_lib().nrays_debug_gather_order(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64),
+                                                          C.byref(params), ptr(out_keys, C.c_uint64), ptr(order, C.c_uint32), ptr(frame, C.c_double), info))
+    return out_keys, order[:int(info[3])].copy(), frame, (int(info[0]), int(info[1]), bool(info[2]), int(info[3]))
 
 
 _U64 = (1 << 64) - 1

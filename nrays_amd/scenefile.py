@@ -113,16 +113,16 @@ class FileScene:
         from .scene import occlusion_points
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
 
-    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None):
+    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None, unordered=False):
         """The incoming light at caller-supplied surface points of this scene: scene.gather_points(self, ...)."""
         from .scene import gather_points
-        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys)
+        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
-                      device=None):
+                      device=None, unordered=False):
         """The indirect term of a light map of mesh node `node`: scene.bake_indirect(self, node, ...)."""
         from .scene import bake_indirect
-        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device)
+        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: scene.surface_texels(self, node, ...)."""

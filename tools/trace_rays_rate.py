@@ -41,7 +41,8 @@ grid the numpy mirror surface_texels_ref() on the host, which is what a caller w
 --gather times, and nothing else, the leg h_sponza_gather: the incoming light (gather_points(): Scene::trace on hemisphere rays built in registers, one mean
 colour per point) at the same two inputs as --occlusion — 16 directions at every first hit, 64 at a 16 384-point subset — beside what a caller did before it: the
 same rays built with torch on the device, trace_rays() on them with the keys of gather_ray_keys() unhinted and with unordered=True, and the torch fold of the
-per-ray colours, each timed apart — and beside itself on handles forced to one lane per point and to 8 / 64 lanes per point (NRAYS_OCCLUSION_LANES).  The same
+per-ray colours, each timed apart — beside itself under the hint (fused_unordered: gather_points(unordered=True), the reorder inside the call, in the same rounds)
+— and beside itself on handles forced to one lane per point and to 8 / 64 lanes per point (NRAYS_OCCLUSION_LANES).  The same
 two inputs are then timed on the stand-in with a ball that reflects and refracts in the hall: a double-branching scene, where the call keeps a chunk's ray colours
 and runs the continuation queue per ray.  Alternating rounds, each of a few launches between events: min, median and max of every leg.
 
@@ -343,6 +344,7 @@ def _gather_input(scenes, tp, tn, keys, k, reps, rounds=5):
         return tot / float(k)
 
     fns = {"fused": lambda: nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk),
+           "fused_unordered": lambda: nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk, unordered=True),
            "torch_build_rays": lambda: _torch_occlusion_rays(tp, tn, L, rot, 1e-3, keys),
            "trace_rays": lambda: nr.trace_rays(sc, ro, rd, keys=rk),
            "trace_rays_unordered": lambda: nr.trace_rays(sc, ro, rd, keys=rk, unordered=True),
@@ -355,8 +357,10 @@ def _gather_input(scenes, tp, tn, keys, k, reps, rounds=5):
         for name, fn in fns.items():
             ms[name].append(_time(fn, reps, warmup=1))
     got, want = nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk), torch_fold()
+    hinted = nr.gather_points(sc, tp, tn, tl, tr, 1e-3, 1.0, 0, keys=tk, unordered=True)
     row = {"points": int(n), "dirs": int(k), "rays": int(n * k), "energy": 1.0, "max_depth": 0, "rounds": rounds, "reps": reps,
-           "points_that_differ_from_the_torch_fold": int((got != want).any(dim=1).sum().item())}
+           "points_that_differ_from_the_torch_fold": int((got != want).any(dim=1).sum().item()),
+           "points_whose_hinted_bits_differ": int((hinted.view(torch.int32) != got.view(torch.int32)).any(dim=1).sum().item())}
     for name, v in ms.items():
         row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
     return row
