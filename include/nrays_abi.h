@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -507,6 +507,37 @@ int nrays_surface_texels(NraysScene* scene, uint32_t node, uint32_t width, uint3
  * times on a stream of the handle, between HIP events of their own; every output is written to scratch memory.  out_ms: repeats x 2 floats HOST
  * memory, (owner pass, resolve pass) in milliseconds.  Blocking.  Statuses as above; repeats == 0 or NULL out_ms -> NRAYS_ERR_BAD_ARG. */
 int nrays_debug_surface_texels_passes(NraysScene* scene, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, uint32_t repeats, float* out_ms);
+
+/* Gutter dilation of a baked light map: every lattice point that no triangle covers takes the values of the nearest covered point within `radius`, so
+ * that Texture2d::sample with Bilinear, which reads the four lattice points around a uv, meets no unlit point at a chart's border (radius >= 2: the
+ * diagonal neighbour of a border point lies at d2 = 2).  The baker's last step, behind nrays_shade_points_device / nrays_gather_points_device.
+ * The lattice is width x height, point (x, y) at index i = y * width + x — the layout of nrays_surface_texels*.  The result is defined exactly, in
+ * integers (Python: nrays_amd.dilate_texels_ref):
+ *   covered     point i is covered iff bit 0 of flags_in[i] is set; every other bit is ignored (out_flags of nrays_surface_texels* passes in unfiltered).
+ *   candidates  of an uncovered point (x, y): the covered points (x', y') with d2 = (x' - x)^2 + (y' - y)^2 <= radius * radius.  A Euclidean disc; no
+ *               wrap-around at the lattice's borders.
+ *   source      the candidate with the smallest d2, among equal d2 the one with the smallest index y' * width + x'.  A point with a source is FILLED.
+ *               A covered point is its own source; an uncovered point without a candidate has source -1.
+ *   values      optional, in place: `channels` (1 .. 4) floats per point, point i at values[i * channels ...].  For every filled point the `channels`
+ *               32-bit words of its source are copied as bit patterns (NaN payloads, -0 and infinities pass unchanged).  Covered points and points
+ *               with source -1 are not written at all.
+ *   out_source  optional: int32 per point, the source index, the point's own index, or -1.
+ *   out_flags   optional, may be the same pointer as flags_in: flags_in[i] for covered and unfilled points, flags_in[i] | NRAYS_TEXEL_FILLED for a
+ *               filled point.  Bit 0 stays clear there: a filled point is not a surface point and must not be shaded.
+ * The definition is separable, which is how the library computes it: per row the nearest covered column within `radius` (the left one on a tie), then
+ * per column the minimum over dy in [-radius, radius] of dx(y + dy)^2 + dy^2 under the same tie rule.
+ * NULL scene / flags_in, values, out_source and out_flags all NULL, values non-NULL with channels outside 1 .. 4, radius outside
+ * 1 .. NRAYS_DILATE_MAX_RADIUS, width or height outside 1 .. 16384, width * height > 2^24, flags != 0 (reserved) -> NRAYS_ERR_BAD_ARG.  Otherwise the
+ * contract of nrays_surface_texels_device: every pointer DEVICE memory on the scene's device, two launches enqueued on `hip_stream` without read-back
+ * or synchronisation, ordered behind the handle's previous work, workspace owned by the handle (2 bytes per lattice point, grown only when needed); what
+ * the handle reports about its renders and its per-camera scheduling state stay untouched. */
+#define NRAYS_DILATE_MAX_RADIUS 64u
+#define NRAYS_TEXEL_FILLED 4u
+int nrays_dilate_texels_device(NraysScene* scene, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius,
+                               uint32_t channels, float* values, int32_t* out_source, uint32_t* out_flags, uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_dilate_texels(NraysScene* scene, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius,
+                        uint32_t channels, float* values, int32_t* out_source, uint32_t* out_flags, uint32_t flags);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

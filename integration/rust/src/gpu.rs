@@ -486,6 +486,29 @@ impl GpuScene {
         Ok(())
     }
 
+    /// Gutter dilation of a `width` x `height` light map (nrays_dilate_texels, blocking): every texel whose `flags` word has bit 0 clear takes the
+    /// `channels` (1 ..= 4) floats of the nearest covered texel within `radius` (1 ..= NRAYS_DILATE_MAX_RADIUS; a Euclidean disc, no wrap-around, the
+    /// smaller index y * width + x among equals), in place in `values`; covered texels and texels with nothing in reach stay as they are.  `flags` are
+    /// the flags of `surface_texels_device` as they come.  Returns per texel the index it was filled from, its own index where covered, -1 where
+    /// nothing is in reach.  Bilinear sampling of the map needs `radius >= 2`.
+    pub fn dilate_texels(&self, width: u32, height: u32, flags: &[u32], radius: u32, channels: u32, values: &mut [f32]) -> Result<Vec<i32>, String> {
+        let n = width as usize * height as usize;
+        if flags.len() != n || values.len() != n * channels as usize { return Err("dilate_texels: flags / values do not match width * height".into()); }
+        let mut source = vec![0i32; n];
+        let rc = unsafe { nrays_dilate_texels(self.raw, width, height, flags.as_ptr(), radius, channels, values.as_mut_ptr(), source.as_mut_ptr(), ptr::null_mut(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(source)
+    }
+
+    /// `dilate_texels` on DEVICE memory (nrays_dilate_texels_device), two launches enqueued on `hip_stream` without synchronisation, behind the calls that
+    /// baked `values`: flags_in n u32; values (n x channels f32, in place), out_source (n i32) and out_flags (n u32: flags_in, | NRAYS_TEXEL_FILLED at a
+    /// filled texel; may be flags_in itself) may each be null, not all three.
+    pub unsafe fn dilate_texels_device(&self, width: u32, height: u32, flags_in: *const u32, radius: u32, channels: u32, values: *mut f32, out_source: *mut i32,
+                                       out_flags: *mut u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_dilate_texels_device(self.raw, width, height, flags_in, radius, channels, values, out_source, out_flags, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
     /// `cast_rays` for n rays in DEVICE memory (nrays_cast_rays_device), enqueued on `hip_stream` without synchronisation: origins / dirs n x 3 f64,
     /// max_toi n f64 or null, out_toi n f64, out_node n i32; out_normal (n x 3 f64), out_uv (n x 2 f64), out_prim (n i32) and out_flags (n u32) may
     /// each be null.  A miss writes node -1 and toi +inf.  `flags`: 0 or NRAYS_RAYS_UNORDERED.

@@ -17,6 +17,9 @@ pub const NRAYS_ERR_RCCL: c_int = -7;
 pub const NRAYS_RAYS_UNORDERED: u32 = 1;
 pub const NRAYS_TEXELS_CENTRES: u32 = 1;
 pub const NRAYS_TEXELS_FLIP_NORMALS: u32 = 2;
+pub const NRAYS_DILATE_MAX_RADIUS: u32 = 64;
+/// set in out_flags of nrays_dilate_texels* at a texel that was filled from a covered one (bit 0 stays clear there)
+pub const NRAYS_TEXEL_FILLED: u32 = 4;
 
 // NraysShapeKind (examples/loader3d.rs:593-695)
 pub const NRAYS_SHAPE_BALL: u32 = 0;
@@ -272,6 +275,8 @@ extern "C" {
     pub fn nrays_surface_texels_device(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_surface_texels(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_surface_texels_passes(scene: *mut NraysScene, node: u32, width: u32, height: u32, flags: u32, repeats: u32, out_ms: *mut f32) -> c_int;
+    pub fn nrays_dilate_texels_device(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, radius: u32, channels: u32, values: *mut f32, out_source: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_dilate_texels(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, radius: u32, channels: u32, values: *mut f32, out_source: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;

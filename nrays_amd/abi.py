@@ -170,6 +170,9 @@ HIP_SYMBOLS = {
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                        C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_debug_surface_texels_passes": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]),
+    "nrays_dilate_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_dilate_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                      C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_debug_ray_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "nrays_scene_create": (C.c_int, [C.POINTER(NraysSceneDesc), C.POINTER(C.c_void_p)]),
@@ -207,10 +210,12 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points", "nrays_occlusion_points_device",
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
                    "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points",
-                   "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order")
+                   "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS
+DILATE_MAX_RADIUS = 64       # NRAYS_DILATE_MAX_RADIUS
+TEXEL_FILLED = 4            # NRAYS_TEXEL_FILLED
 RAY_FRAME_DOUBLES = 20      # NRAYS_RAY_FRAME_DOUBLES
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

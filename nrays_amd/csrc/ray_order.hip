@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -30,6 +30,7 @@
 #include "ray_key.h"
 #include "scene_handle.h"
 #include "surface_texels_kernel.h"
+#include "texel_dilate_kernel.h"
 
 static_assert(NRAYS_RAY_FRAME_DOUBLES == nrays::kRayFrameDoubles, "include/nrays_abi.h and ray_key.h disagree on the frame");
 
@@ -330,7 +331,7 @@ void trace_workspace_release(NraysScene* sc) {
     if (!w) return;
     if (w->used) (void)hipStreamSynchronize(w->last_stream);
     for (int k = 0; k < 2; ++k) if (w->queue[k].block) (void)hipFree(w->queue[k].block);
-    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage, w->d_texel_owner, w->d_texel_off, (void*)w->d_texel_blocks, w->d_gather_rays}) if (q) (void)hipFree(q);
+    for (void* q : {(void*)w->d_fixed, (void*)w->d_counts, (void*)w->d_counters, (void*)w->d_spill, w->d_stage, w->d_texel_owner, w->d_texel_off, (void*)w->d_texel_blocks, w->d_gather_rays, w->d_dilate_dx}) if (q) (void)hipFree(q);
     ray_order_release(w);
     delete w;
     sc->tw = nullptr;
@@ -1102,6 +1103,81 @@ static int surface_texels_passes_probe(NraysScene* sc, uint32_t node, uint32_t w
     return rc;
 }
 
+// ---- nrays_dilate_texels*: uncovered lattice points take the values of the nearest covered point within a radius (texel_dilate_kernel.h) -----------------------------
+static_assert(kDilateMaxRadius == NRAYS_DILATE_MAX_RADIUS && kDilateFilled == NRAYS_TEXEL_FILLED, "texel_dilate_kernel.h restates the header's constants");
+struct DilateArgs { uint32_t width, height; const uint32_t* flags_in; uint32_t radius, channels; float* values; int32_t* source; uint32_t* flags_out; };
+static int check_dilate_args(const NraysScene* sc, const DilateArgs& a, uint32_t flags) {
+    if (!sc || !a.flags_in) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (!a.values && !a.source && !a.flags_out) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_dilate_texels: no output (values, out_source and out_flags are all null)");
+    if (a.values && (a.channels < 1u || a.channels > 4u)) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_dilate_texels: channels must be in 1 .. 4");
+    if (a.radius < 1u || a.radius > NRAYS_DILATE_MAX_RADIUS) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_dilate_texels: radius must be in 1 .. 64");
+    if (a.width < 1u || a.width > kTexelMaxSide || a.height < 1u || a.height > kTexelMaxSide || (uint64_t)a.width * a.height > kTexelMaxPoints)
+        return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_dilate_texels: width and height must be in 1 .. 16384 and width * height <= 2^24");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_dilate_texels: flags are reserved and must be 0");
+    return NRAYS_OK;
+}
+// The two launches of one call.  The workspace holds width * height dx words.
+static int dilate_passes(TraceWorkspace* w, const DilateArgs& a, hipStream_t stream) {
+    const DilateLattice L{a.width, a.height, a.radius, (a.width + 63u) / 64u};
+    int16_t* dx = (int16_t*)w->d_dilate_dx;
+    const uint32_t T = a.radius <= kDilateShortRadius ? 16u : 64u; // (dilate_rows_per_group)
+    const uint32_t vec4 = (a.values && a.channels == 4u && ((uintptr_t)a.values & 15u) == 0u) ? 1u : 0u;
+    hipLaunchKernelGGL(k_dilate_rows, dim3((L.h * L.col_blocks + kDilateWaves - 1u) / kDilateWaves), dim3(kDilateBlock), 0, stream, L, a.flags_in, dx);
+    hipLaunchKernelGGL(k_dilate_cols, dim3(L.col_blocks, (L.h + T - 1u) / T), dim3(kDilateBlock), (size_t)(T + 2u * a.radius) * 64u * sizeof(int16_t), stream, L,
+                       (const int16_t*)dx, a.flags_in, a.values ? a.channels : 0u, vec4, a.values, a.source, a.flags_out);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_dilate_cols: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+static int dilate_texels_device_impl(NraysScene* sc, const DilateArgs& a, uint32_t flags, hipStream_t stream) {
+    { const int rc = check_dilate_args(sc, a, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_dilate_dx, &w->dilate_points, (size_t)a.width * a.height, sizeof(int16_t));
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    rc = dilate_passes(w, a, stream);
+    batch_end(sc, w, stream);
+    return rc;
+}
+// The blocking form, through the workspace's staging buffer as surface_texels_host_impl: the values (16-byte aligned at the block's start), the flags — in and out in
+// one array, which the device form allows — and the sources.
+static int dilate_texels_host_impl(NraysScene* sc, const DilateArgs& a, uint32_t flags) {
+    { const int rc = check_dilate_args(sc, a, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    const size_t n = (size_t)a.width * a.height, value_bytes = a.values ? n * a.channels * sizeof(float) : 0;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_dilate_dx, &w->dilate_points, n, sizeof(int16_t));
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_stage, &w->stage_rays, (value_bytes + n * 8 + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    DilateArgs s = a;
+    s.values = a.values ? (float*)w->d_stage : nullptr;
+    uint32_t* s_flags = (uint32_t*)((char*)w->d_stage + value_bytes);
+    s.flags_in = s_flags; s.flags_out = a.flags_out ? s_flags : nullptr;
+    s.source = a.source ? (int32_t*)(s_flags + n) : nullptr;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    hipError_t e = hipMemcpyAsync(s_flags, a.flags_in, n * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && a.values) e = hipMemcpyAsync(s.values, a.values, value_bytes, hipMemcpyHostToDevice, stream);
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("dilate texels upload: ") + hipGetErrorString(e));
+    if (rc == NRAYS_OK) rc = dilate_passes(w, s, stream);
+    if (rc == NRAYS_OK) {
+        auto down = [&](void* dst, const void* src, size_t bytes) { return dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream) : hipSuccess; };
+        e = down(a.values, s.values, value_bytes);
+        if (e == hipSuccess) e = down(a.source, s.source, n * 4);
+        if (e == hipSuccess) e = down(a.flags_out, s_flags, n * 4);
+    }
+    const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next call, and the uploads read the caller's arrays)
+    if (e == hipSuccess) e = es;
+    if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("dilate texels read-back: ") + hipGetErrorString(e));
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -1291,6 +1367,15 @@ int nrays_surface_texels(NraysScene* sc, uint32_t node, uint32_t width, uint32_t
 }
 int nrays_debug_surface_texels_passes(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, uint32_t repeats, float* out_ms) {
     return surface_texels_passes_probe(sc, node, width, height, flags, repeats, out_ms);
+}
+
+int nrays_dilate_texels_device(NraysScene* sc, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius, uint32_t channels, float* values, int32_t* out_source,
+                               uint32_t* out_flags, uint32_t flags, void* hip_stream) {
+    return dilate_texels_device_impl(sc, DilateArgs{width, height, flags_in, radius, channels, values, out_source, out_flags}, flags, (hipStream_t)hip_stream);
+}
+int nrays_dilate_texels(NraysScene* sc, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius, uint32_t channels, float* values, int32_t* out_source,
+                        uint32_t* out_flags, uint32_t flags) {
+    return dilate_texels_host_impl(sc, DilateArgs{width, height, flags_in, radius, channels, values, out_source, out_flags}, flags);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

@@ -77,6 +77,8 @@ struct TraceWorkspace {
     // nrays_gather_points* in double-branching scenes and in every reordered chunk of the _ex forms: the colours of one chunk's rays (x 3), between k_gather_points /
     // k_gather_pairs_ordered, the queue's rounds and k_gather_fold
     void* d_gather_rays = nullptr; size_t gather_ray_floats = 0;
+    // nrays_dilate_texels* (texel_dilate_kernel.h): per lattice point the 16-bit dx word the row pass leaves for the column pass
+    void* d_dilate_dx = nullptr; size_t dilate_points = 0;
 };
 
 } // namespace nrays

@@ -13,6 +13,8 @@ through the C ABI (include/nrays_abi.h) and fails loudly if it is missing.
 """
 import collections
 import ctypes as C
+import functools
+import inspect
 import math
 
 import numpy as np
@@ -327,6 +329,28 @@ class SceneDescriptor:
         return C.byref(self.desc)
 
 
+def _dilate_keyword(bake):
+    """bake_indirect and its two methods take their arguments by position up to `unordered`, their last parameter, and callers and tests rely on that
+    order (tests/test_gather_order.py).  The gutter radius `dilate` that bake_lightmap takes as an ordinary parameter is therefore added AROUND them, as a
+    keyword-only option: inspect.signature() shows the positional parameters as they were, the docstring names the keyword.  dilate=0 calls the baker and
+    nothing else.  Otherwise the map it returns is dilated in place by dilate_texels() on the flags of one more surface_texels() call (no optional
+    output: a small fraction of the gather's time), on the same stream."""
+    sig = inspect.signature(bake)
+
+    @functools.wraps(bake)
+    def with_dilate(*args, dilate=0, **kw):
+        radius = _dilate_radius(dilate)
+        out = bake(*args, **kw)
+        if radius == 0:
+            return out
+        bound = sig.bind(*args, **kw)
+        bound.apply_defaults()
+        a, scene = bound.arguments, bound.args[0]
+        flags = surface_texels(scene, a["node"], a["width"], a["height"], a["centres"], a["flip_normals"], want=(), device=a["device"]).flags
+        return _bake_dilate(scene, flags, out.reshape(-1, out.shape[-1]), a["width"], a["height"], radius).reshape(out.shape)
+    return with_dilate
+
+
 class Scene:
     """Scene::new(nodes, lights, background) — src/scene.rs:119-133.  The device-resident scene (BVHs
     included) is created on first render on the current HIP device and reused afterwards."""
@@ -380,18 +404,23 @@ class Scene:
         """The incoming light at caller-supplied surface points of this scene: gather_points(self, ...)."""
         return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
+    @_dilate_keyword
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
                       device=None, unordered=False):
-        """The indirect term of a light map of mesh node `node`: bake_indirect(self, node, ...)."""
+        """The indirect term of a light map of mesh node `node`: bake_indirect(self, node, ...); `dilate=` as there, by keyword."""
         return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
         return surface_texels(self, node, width, height, centres, flip_normals, want, device)
 
-    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None, dilate=0):
         """A light map of mesh node `node`: bake_lightmap(self, node, ...)."""
-        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device)
+        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device, dilate)
+
+    def dilate_texels(self, flags, width, height, radius, values=None, want_source=False, device=None):
+        """Gutter dilation of a light map on this scene's GPU: dilate_texels(self, flags, ...)."""
+        return dilate_texels(self, flags, width, height, radius, values, want_source, device)
 
     def _release(self):
         if self._handle is not None:
@@ -1202,32 +1231,185 @@ def surface_texels_passes(scene, node, width, height, centres=False, flip_normal
     return ms
 
 
-def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None, dilate=0):
     """A light map of TriMesh node `node`: the direct lighting of its surface at the texels of a width x height map, (height, width, 4) float32 in
     NraysTexture row order (row 0 = the bottom row): shade_points() on surface_texels(), viewed against the normal (view_dirs = -normals), rgb = the lit
     colour, a = the material's alpha.  `occlusion=(sample_dirs, rotations, bias, max_toi)`: rgb is multiplied by the mean filter of occlusion_points() with
     these arguments at the same texels.  Uncovered texels are zeros.  `keys` (width * height,) RNG keys for area lights and the occlusion rotations
     (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, three calls on one stream; `keys` and
-    the tables are then tensors (the tables may be anything numpy takes).  Also `scene.bake_lightmap(node, ...)` on Scene and FileScene."""
+    the tables are then tensors (the tables may be anything numpy takes).  `dilate`: a radius in texels (1 .. 64): the gutters are filled from the nearest
+    covered texel by dilate_texels(), one more call on the same stream; 0 = off, the calls and the result above exactly.  A map that is sampled with
+    Bilinear (lightmap_texture()) needs dilate >= 2: the diagonal neighbour of a border texel lies at d2 = 2.
+    Also `scene.bake_lightmap(node, ...)` on Scene and FileScene."""
     tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals", "uv", "node"), device=device)
     rgba = shade_points(scene, tx.points, tx.normals, -tx.normals, tx.node, uvs=tx.uv, hit_flags=tx.flags, keys=keys)
     if occlusion is not None:
         sample_dirs, rotations, bias, max_toi = occlusion
         occ = occlusion_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, max_toi, hit_flags=tx.flags, keys=keys)
         rgba[:, :3] = rgba[:, :3] * occ.filter
+    rgba = _bake_dilate(scene, tx.flags, rgba, width, height, _dilate_radius(dilate))
     return rgba.reshape(int(height), int(width), 4)
 
 
+@_dilate_keyword
 def bake_indirect(scene, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
                   device=None, unordered=False):
     """The indirect term of a light map of TriMesh node `node`: the mean incoming light at the texels of a width x height map, (height, width, 3) float32 in
     NraysTexture row order (row 0 = the bottom row): gather_points() with these arguments on surface_texels().  Uncovered texels are zeros.  `keys`
     (width * height,) RNG keys (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, two calls on one
-    stream; `keys` is then a tensor (the tables may be anything numpy takes).  `unordered`: as for gather_points.  Also
-    `scene.bake_indirect(node, ...)` on Scene and FileScene."""
+    stream; `keys` is then a tensor (the tables may be anything numpy takes).  `unordered`: as for gather_points.  `dilate` (keyword only, see
+    _dilate_keyword): as for bake_lightmap — a radius in texels, filled by dilate_texels() on the same stream; 0 = off, today's calls and result exactly;
+    Bilinear sampling needs dilate >= 2 (the diagonal neighbour of a border texel lies at d2 = 2).  Also `scene.bake_indirect(node, ...)` on Scene and
+    FileScene."""
     tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals",), device=device)
     rgb = gather_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=tx.flags, keys=keys, unordered=unordered)
     return rgb.reshape(int(height), int(width), 3)
+
+
+def _dilate_args(flags, width, height, radius, values):
+    """Checks shared by dilate_texels and dilate_texels_ref: (width, height, radius, channels); channels 0 without values."""
+    width, height = _texel_lattice(width, height)
+    radius = int(radius)
+    if not 1 <= radius <= abi.DILATE_MAX_RADIUS:
+        raise ValueError("radius must be in 1 .. %d, got %d" % (abi.DILATE_MAX_RADIUS, radius))
+    n = width * height
+    if int(np.prod(tuple(flags.shape))) != n:
+        raise ValueError("flags must hold width * height = %d words, got shape %s" % (n, tuple(flags.shape)))
+    channels = 0
+    if values is not None:
+        size = int(np.prod(tuple(values.shape)))
+        channels = size // n
+        if channels * n != size or not 1 <= channels <= 4:
+            raise ValueError("values must hold 1 .. 4 floats per lattice point (%d points), got shape %s" % (n, tuple(values.shape)))
+    return width, height, radius, channels
+
+
+def dilate_texels_ref(flags, width, height, radius, values=None):
+    """The numpy mirror of nrays_dilate_texels_device's definition (include/nrays_abi.h), bit for bit: what dilate_texels() returns, as
+    (values, source int32 (n,), flags uint32 (n,)); `values` is a dilated COPY of the argument (None without one), the arguments stay as they are.
+    Integers only.  Written the separable way: per row the nearest covered column (running maximum / minimum of the covered column indices, the left
+    one on a tie), then rings |dy| = 1, 2, .. radius over the points that are still open — uncovered, and dy^2 not above the d2 they hold — so that the
+    cost follows the gutters' area and depth, not radius x the lattice."""
+    flags = np.asarray(flags)
+    if not np.issubdtype(flags.dtype, np.integer):
+        raise ValueError("flags must be integers, got %s" % flags.dtype)
+    w, h, r, channels = _dilate_args(flags, width, height, radius, None if values is None else np.asarray(values))
+    n, none = w * h, 1 << 20
+    f = flags.astype(np.uint32, copy=False).reshape(h, w)
+    cov = (f & np.uint32(1)) != 0
+    x = np.arange(w, dtype=np.int64)[None, :]
+    dl = x - np.maximum.accumulate(np.where(cov, x, -none), axis=1)
+    dr = np.minimum.accumulate(np.where(cov, x, none)[:, ::-1], axis=1)[:, ::-1] - x
+    dx = np.where(dl <= dr, -dl, dr)
+    dx = np.where(np.minimum(dl, dr) <= r, dx, none).reshape(n)  # per point: the row pass's word
+    i = np.arange(n, dtype=np.int64)
+    y = i // w
+    have = dx != none
+    best_d2 = np.where(have, dx * dx, r * r + 1)
+    best = np.where(have, i + dx, -1)
+    active = np.flatnonzero(~cov.reshape(n))
+    for k in range(1, r + 1):
+        active = active[best_d2[active] >= k * k]
+        if active.size == 0:
+            break
+        for sign in (-1, 1):  # the row above first: on equal (d2, index) nothing changes, and the comparison below is lexicographic anyway
+            yy = y[active] + sign * k
+            a = active[(yy >= 0) & (yy < h)]
+            j = a + sign * k * w
+            d = dx[j]
+            keep = d != none
+            a, j, d = a[keep], j[keep], d[keep]
+            d2, idx = d * d + k * k, j + d
+            better = (d2 < best_d2[a]) | ((d2 == best_d2[a]) & (idx < best[a]))
+            a = a[better]
+            best_d2[a], best[a] = d2[better], idx[better]
+    filled = ~cov.reshape(n) & (best >= 0)
+    out_flags = f.reshape(n) | np.where(filled, np.uint32(abi.TEXEL_FILLED), np.uint32(0))
+    out_values = None
+    if values is not None:
+        v = np.asarray(values)
+        if v.dtype != np.float32:
+            raise ValueError("values must be float32, got %s" % v.dtype)
+        out_values = np.array(v, order="C", copy=True)
+        words = out_values.view(np.uint32).reshape(n, channels)
+        words[filled] = words[best[filled]]
+    return out_values, best.astype(np.int32), out_flags.astype(np.uint32)
+
+
+def dilate_texels(scene, flags, width, height, radius, values=None, want_source=False, device=None):
+    """Gutter dilation of a width x height light map through nrays_dilate_texels_device / nrays_dilate_texels: every uncovered texel takes the values of
+    the nearest covered texel within `radius` (1 .. 64; a Euclidean disc, no wrap-around, the smaller index y * width + x among equals).  `flags`:
+    width * height words, texel (x, y) at y * width + x, covered iff bit 0 is set — the flags of surface_texels() as they are.  `values`: 1 .. 4
+    float32 per texel ((n, c), (height, width, c) or (n,)), dilated IN PLACE when it is a C-contiguous float32 array or tensor (a converted copy
+    otherwise): the words of the source are copied as bit patterns; covered texels and texels with nothing in reach are not written.
+    Returns (values or None, source or None, flags): source (n,) int32 with want_source — the texel copied from, the texel itself where covered, -1 where
+    nothing is in reach —; flags a new array, the input | abi.TEXEL_FILLED at the filled texels (bit 0 stays clear there).
+    numpy arrays -> nrays_dilate_texels (blocking; flags out uint32).  torch tensors on the scene's GPU (flags int32, values float32) ->
+    nrays_dilate_texels_device on torch.cuda.current_stream(), tensors there; `device` moves numpy arguments to that GPU first.
+    Also `scene.dilate_texels(flags, ...)` on Scene and FileScene.  dilate_texels_ref() restates the result bit for bit."""
+    w, h, r, channels = _dilate_args(flags, width, height, radius, values)
+    n = w * h
+    lib = abi.load_hip_lib()
+    if device is not None and not _is_tensor(flags):
+        import torch
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("device must be a GPU, got %s" % device)
+        flags = torch.from_numpy(_np_ints("flags", flags, np.uint32).view(np.int32)).to(device)
+        if values is not None:
+            values = torch.from_numpy(_np_floats("values", values, np.float32)).to(device)
+    if _is_tensor(flags):
+        import torch
+        dev = flags.device
+        if dev.type != "cuda":
+            raise ValueError("flags must be on a GPU, got %s" % dev)
+        if device is not None and torch.device(device).index not in (None, dev.index):
+            raise ValueError("flags is on %s, device is %s" % (dev, device))
+        f_in, v = _torch_args((("flags", flags, (torch.int32, torch.uint32)), ("values", values, (torch.float32,))), dev)
+        out_flags = torch.empty(n, dtype=torch.int32, device=dev)
+        source = torch.empty(n, dtype=torch.int32, device=dev) if want_source else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        with torch.cuda.device(dev):
+            abi.check(lib.nrays_dilate_texels_device(scene.device_handle(), w, h, ptr(f_in), r, channels, ptr(v), ptr(source), ptr(out_flags), 0,
+                                                     torch.cuda.current_stream().cuda_stream))
+        return v, source, out_flags
+    if _is_tensor(values):
+        raise ValueError("values: torch tensors and numpy arrays cannot be mixed in one call")
+    f_in = _np_ints("flags", flags, np.uint32).reshape(n)
+    v = None
+    if values is not None:
+        v = values if (isinstance(values, np.ndarray) and values.dtype == np.float32 and values.flags.c_contiguous and values.flags.writeable) else \
+            np.array(_np_floats("values", values, np.float32), copy=True)
+    out_flags = np.empty(n, dtype=np.uint32)
+    source = np.empty(n, dtype=np.int32) if want_source else None
+    ptr = lambda a, ct: None if a is None else a.ctypes.data_as(C.POINTER(ct))  # noqa: E731
+    abi.check(lib.nrays_dilate_texels(scene.device_handle(), w, h, ptr(f_in, C.c_uint32), r, channels, ptr(v, C.c_float), ptr(source, C.c_int32),
+                                      ptr(out_flags, C.c_uint32), 0))
+    return v, source, out_flags
+
+
+def lightmap_texture(rgba):
+    """A baked (height, width, 4) light map — bake_lightmap()'s result, row 0 = the bottom row as NraysTexture wants it — as the Texture2d a material
+    samples it through: float32 texels, Bilinear, ClampToEdges.  Bake with dilate >= 2, or the charts' borders blend with unlit texels."""
+    if _is_tensor(rgba):
+        rgba = rgba.detach().cpu().numpy()
+    return Texture2d(ImageData(np.ascontiguousarray(rgba, dtype=np.float32)), Interpolation.Bilinear, Overflow.ClampToEdges)
+
+
+def _dilate_radius(dilate):
+    dilate = int(dilate)
+    if dilate < 0 or dilate > abi.DILATE_MAX_RADIUS:
+        raise ValueError("dilate must be 0 (off) or a radius in 1 .. %d, got %d" % (abi.DILATE_MAX_RADIUS, dilate))
+    return dilate
+
+
+def _bake_dilate(scene, flags, out, width, height, radius):
+    """The bakers' last step: `out` (n, c) dilated in place by `radius` texels on the texels' `flags`; 0 = nothing is called."""
+    if radius == 0:
+        return out
+    if not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
+        out = out.contiguous() if _is_tensor(out) else np.ascontiguousarray(out)
+    return dilate_texels(scene, flags, width, height, radius, values=out)[0]
 
 
 def ray_order(scene, origins, dirs):

@@ -7,6 +7,7 @@ import os
 import numpy as np
 
 from . import abi
+from .scene import _dilate_keyword
 
 
 class NraysHostCamera(C.Structure):
@@ -118,9 +119,10 @@ class FileScene:
         from .scene import gather_points
         return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
+    @_dilate_keyword
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
                       device=None, unordered=False):
-        """The indirect term of a light map of mesh node `node`: scene.bake_indirect(self, node, ...)."""
+        """The indirect term of a light map of mesh node `node`: scene.bake_indirect(self, node, ...); `dilate=` as there, by keyword."""
         from .scene import bake_indirect
         return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
@@ -129,10 +131,15 @@ class FileScene:
         from .scene import surface_texels
         return surface_texels(self, node, width, height, centres, flip_normals, want, device)
 
-    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None):
+    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None, dilate=0):
         """A light map of mesh node `node`: scene.bake_lightmap(self, node, ...)."""
         from .scene import bake_lightmap
-        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device)
+        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device, dilate)
+
+    def dilate_texels(self, flags, width, height, radius, values=None, want_source=False, device=None):
+        """Gutter dilation of a light map on this scene's GPU: scene.dilate_texels(self, flags, ...)."""
+        from .scene import dilate_texels
+        return dilate_texels(self, flags, width, height, radius, values, want_source, device)
 
     def close(self):
         if self._handle is not None:

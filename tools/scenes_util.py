@@ -89,6 +89,19 @@ def torus_mesh(nu=48, nv=24, R=1.5, r=0.6):
     return pts, np.asarray(idx, dtype=np.uint32), uvs
 
 
+def atlas_quads_mesh(cells=64, chart_share=0.75):
+    """cells x cells flat quads (two triangles each) whose uv charts are squares of chart_share of a 1 / cells atlas cell, centred in it: an atlas with
+    gutters between its charts, (1 - chart_share) / cells wide in uv — 4 texels at 1024^2 for the defaults.  (points, indices, uvs), f32-exact."""
+    i, j = np.meshgrid(np.arange(cells), np.arange(cells), indexing="ij")
+    lo = (1.0 - chart_share) / 2.0
+    corner = np.asarray([[lo, lo], [1.0 - lo, lo], [1.0 - lo, 1.0 - lo], [lo, 1.0 - lo]])
+    uv = (np.stack([i, j], -1).reshape(-1, 1, 2) + corner[None]) / float(cells)  # (cells^2, 4, 2)
+    pts = np.concatenate([8.0 * uv[..., :1] - 4.0, np.zeros_like(uv[..., :1]), 8.0 * uv[..., 1:] - 4.0], -1)
+    base = 4 * np.arange(cells * cells, dtype=np.uint32)[:, None]
+    idx = np.concatenate([base + np.asarray([0, 2, 1], np.uint32), base + np.asarray([0, 3, 2], np.uint32)], 0)
+    return f32_exact(pts.reshape(-1, 3)), np.ascontiguousarray(idx), f32_exact(uv.reshape(-1, 2))
+
+
 def checker_texture(n=64, cells=8, alpha_holes=False):
     yy, xx = np.mgrid[0:n, 0:n]
     chk = ((xx * cells // n) + (yy * cells // n)) % 2

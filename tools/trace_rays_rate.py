@@ -38,6 +38,13 @@ of its own at 1024^2 and 4096^2 lattice points, and of a two-triangle quad at 40
 its owner and resolve passes between events of their own (nrays_debug_surface_texels_passes), shade_points() on the same texels, and for the 1024^2 lattice of the
 grid the numpy mirror surface_texels_ref() on the host, which is what a caller without the entry point does (plus the upload, not counted).
 
+--texels --dilate (or --dilate alone: that leg and nothing else, into profiles/dilate_rate.json) times the leg i_dilate_texels: dilate_texels()
+(nrays_dilate_texels_device) with four float channels on the surface_texels() flags of an atlas of 64 x 64 quad charts with gutters between them
+(tools/scenes_util.py: atlas_quads_mesh) at 1024^2 and 4096^2, radius 2, 8 and 64 — beside surface_texels() on the same lattice, beside what a caller paid
+before (`radius` passes of an 8-neighbour fill written with torch ops on the same device tensors; time only, its values differ by definition) and beside
+the traffic floor: the bytes the call must move over the 6.29 TB/s a float4 copy reaches.  The expectation, written before the first run, is judged in the
+JSON: cheaper than the torch passes in every row, and at radius <= 8 cheaper than surface_texels().
+
 --gather times, and nothing else, the leg h_sponza_gather: the incoming light (gather_points(): Scene::trace on hemisphere rays built in registers, one mean
 colour per point) at the same two inputs as --occlusion — 16 directions at every first hit, 64 at a 16 384-point subset — beside what a caller did before it: the
 same rays built with torch on the device, trace_rays() on them with the keys of gather_ray_keys() unhinted and with unordered=True, and the torch fold of the
@@ -46,7 +53,7 @@ per-ray colours, each timed apart — beside itself under the hint (fused_unorde
 two inputs are then timed on the stand-in with a ball that reflects and refracts in the hall: a double-branching scene, where the call keeps a chunk's ray colours
 and runs the continuation queue per ray.  Alternating rounds, each of a few launches between events: min, median and max of every leg.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels]
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels] [--dilate]
 """
 import argparse
 import ctypes as C
@@ -444,6 +451,85 @@ def _texels_leg(reps, quick):
             "quad_large_lattice": _texels_row(sq, quad, large, max(1, reps // 4), False)}
 
 
+def _torch_fill(values, covered, passes):
+    """What a caller without dilate_texels() writes: `passes` rounds of an 8-neighbour fill with torch ops (each round, an unfilled texel takes the first
+    filled neighbour in a fixed order).  Not the library's definition — compared for its time only."""
+    import torch
+    import torch.nn.functional as F
+    h, w = covered.shape
+    v, m = values.clone(), covered.clone()
+    for _ in range(passes):
+        vp = F.pad(v.permute(2, 0, 1)[None], (1, 1, 1, 1))[0]
+        mp = F.pad(m[None, None].to(torch.uint8), (1, 1, 1, 1))[0, 0].bool()
+        nv, nm = v.clone(), m.clone()
+        for dy in (-1, 0, 1):
+            for dx in (-1, 0, 1):
+                if dy == 0 and dx == 0:
+                    continue
+                take = mp[1 + dy:h + 1 + dy, 1 + dx:w + 1 + dx] & ~nm
+                nv = torch.where(take[..., None], vp[:, 1 + dy:h + 1 + dy, 1 + dx:w + 1 + dx].permute(1, 2, 0), nv)
+                nm = nm | take
+        v, m = nv, nm
+    return v
+
+
+HBM_COPY_BYTES_PER_S = 6.29e12  # MI355X, measured with a float4 copy
+
+
+def _dilate_row(sc, size, radius, reps, rounds=5):
+    import torch
+    import nrays_amd as nr
+    w, h = size
+    n = w * h
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tx = nr.surface_texels(sc, 0, w, h, want=(), device=dev)
+    covered = (tx.flags & 1) != 0
+    values = torch.rand((n, 4), dtype=torch.float32, device=dev) * covered[:, None]
+    work = values.clone()
+
+    def dilate():
+        work.copy_(values)  # (the call is in place; the copy is timed apart and subtracted)
+        nr.dilate_texels(sc, tx.flags, w, h, radius, values=work)
+    fns = {"copy_of_the_values": lambda: work.copy_(values), "copy_and_dilate_texels": dilate,
+           "surface_texels": lambda: nr.surface_texels(sc, 0, w, h, want=("normals", "uv", "node"), device=dev)}
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=2))
+    torch_reps = 1 if radius * n > 1 << 26 else 3
+    grid_values, grid_covered = values.view(h, w, 4), covered.view(h, w)
+    ms["torch_passes"] = [_time(lambda: _torch_fill(grid_values, grid_covered, radius), torch_reps, warmup=1) for _ in range(2)]
+    _, source, out_flags = nr.dilate_texels(sc, tx.flags, w, h, radius, values=work, want_source=True)
+    filled = int(((out_flags & 4) != 0).sum().item())
+    floor_bytes = 4 * n + 2 * n + 2 * n + 4 * n + 2 * 16 * filled  # flags read, dx written and read, out_flags written, four floats read and written per filled texel
+    row = {"lattice": [w, h], "points": n, "radius": radius, "channels": 4, "covered_share": round(float(covered.float().mean().item()), 4),
+           "filled_share": round(filled / n, 4), "left_unfilled_share": round(float((source < 0).float().mean().item()), 4), "rounds": rounds, "reps": reps, "torch_reps": torch_reps}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    t = row["copy_and_dilate_texels"]["ms"] - row["copy_of_the_values"]["ms"]
+    row["dilate_texels"] = {"ms": round(t, 4), "how": "copy_and_dilate_texels - copy_of_the_values (medians)"}
+    row["traffic_floor"] = {"bytes": floor_bytes, "ms": round(floor_bytes / HBM_COPY_BYTES_PER_S * 1e3, 4), "share_of_it_reached": round(floor_bytes / HBM_COPY_BYTES_PER_S * 1e3 / t, 3) if t > 0 else None}
+    row["expectation"] = {"cheaper_than_the_torch_passes": "MET" if t < row["torch_passes"]["ms"] else "MISSED"}
+    if radius <= 8:
+        row["expectation"]["cheaper_than_surface_texels"] = "MET" if t < row["surface_texels"]["ms"] else "MISSED"
+    return row
+
+
+def _dilate_leg(reps, quick):
+    import nrays_amd as nr
+    from tools import scenes_util as su
+    mesh = su.atlas_quads_mesh(16 if quick else 64)
+    mat = nr.PhongMaterial((0.2, 0.2, 0.2), (0.9, 0.9, 0.9), (0.5, 0.5, 0.5), None, None, 40.0)
+    sc = nr.Scene([nr.SceneNode(mat, 0.0, 0.0, 1.0, 1.0, nr.Isometry3(), nr.TriMesh(*mesh[:2], mesh[2]))], [nr.Light((1.0, 6.0, -2.0), 0.0, 1, (1.0, 1.0, 1.0))], (0, 0, 0))
+    small, large = ((128, 128), (512, 512)) if quick else ((1024, 1024), (4096, 4096))
+    out = {"expectation_written_before_the_first_run": "dilate_texels cheaper than `radius` torch passes in every row; at radius <= 8 cheaper than surface_texels on the same lattice",
+           "atlas": "64 x 64 quad charts, each 0.75 of its atlas cell (tools/scenes_util.py: atlas_quads_mesh)"}
+    for name, size, rp in (("small_lattice", small, reps), ("large_lattice", large, max(1, reps // 4))):
+        for radius in (2, 8, 64):
+            out["%s_r%d" % (name, radius)] = _dilate_row(sc, size, radius, rp)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json, with --gather profiles/gather_rate.json")
@@ -457,9 +543,10 @@ def main():
     ap.add_argument("--occlusion", action="store_true", help="time occlusion_points beside intersects_rays on the same rays and the torch fold (leg e_sponza_occlusion), nothing else")
     ap.add_argument("--gather", action="store_true", help="time gather_points beside building the rays with torch, trace_rays on them and the torch fold (leg h_sponza_gather), nothing else")
     ap.add_argument("--texels", action="store_true", help="time surface_texels, its two passes, shade_points on its texels and the numpy mirror (leg g_surface_texels), nothing else")
+    ap.add_argument("--dilate", action="store_true", help="time dilate_texels beside surface_texels, the torch passes a caller wrote before and the traffic floor (leg i_dilate_texels, into profiles/dilate_rate.json); alone: nothing else")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "dilate_rate.json" if a.dilate and not a.texels else "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -472,6 +559,16 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.dilate:
+        leg = dict(res, workloads={"i_dilate_texels": _dilate_leg(a.reps, a.quick)})
+        path = a.out if not a.texels else os.path.join(ROOT, "profiles", "dilate_rate.json")
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(leg, f, indent=1)
+        print(json.dumps(leg))
+        if not a.texels:
+            return
 
     if a.texels:
         res["workloads"]["g_surface_texels"] = _texels_leg(a.reps, a.quick)
