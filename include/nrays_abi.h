@@ -609,6 +609,17 @@ typedef struct NraysCastResult {
 int nrays_debug_cast_batch(NraysScene* scene, uint32_t mode, uint32_t n, const double* origins, const double* dirs,
                            const double* max_toi, NraysCastResult* out);
 
+/* Probe of the f32 box culling ALONE (no scene handle): ONE node visit of the traversals per case, through the product's own device functions —
+ * the f32 view of the ray, the f32 bound of the current best distance, the fetch of the node's planes, the four slab tests and the rule for
+ * f32-zero direction components.  Case i: origin and direction (3 doubles each), the current best distance `best[i]` (kDblMax / max_toi / a hit's
+ * toi), one box `boxes[6 i ..]` = {min x, y, z, max x, y, z} placed in child slot `slots[i]` (0..3) of a real 128-byte node whose other three
+ * children are absent.  mode 0: the per-lane fetch, a case per lane; mode 1: the wave-uniform scalar fetch, a case per wave.
+ * Out: `keys` n x 4 (entry distance of a child the ray may enter before `best`, +inf for a child it cannot), `bits` n (RayF::bits: 1 / 2 / 4 =
+ * component x / y / z is zero in f32, 16 / 32 / 64 = negative), `inv32` n x 3 (the f32 reciprocals the device computed).  All HOST memory.
+ * Blocking; runs on the current device's default stream. */
+int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* best, const float* boxes,
+                         const uint32_t* slots, float* keys, uint32_t* bits, float* inv32);
+
 /* World AABB of scene node `node` as the device holds it: geometry.bounding_volume(&transform) of src/scene_node.rs:41 in the
  * reference's arithmetic; the kernels apply ncollide's exact ray / AABB test to it for every accepted hit (the reference only casts
  * a node whose AABB the ray passes, src/scene.rs:276).  out = {min x, y, z, max x, y, z}. */

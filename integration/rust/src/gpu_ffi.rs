@@ -253,6 +253,7 @@ extern "C" {
     pub fn nrays_debug_pipeline_counts(scene: *const NraysScene, out: *mut u64) -> c_int; // out: [u64; 4]
     pub fn nrays_get_tile_costs(scene: *mut NraysScene, out: *mut NraysTileCosts) -> c_int;
     pub fn nrays_debug_cast_batch(scene: *mut NraysScene, mode: u32, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out: *mut NraysCastResult) -> c_int;
+    pub fn nrays_debug_box_cull(mode: u32, n: u32, origins: *const f64, dirs: *const f64, best: *const f64, boxes: *const f32, slots: *const u32, keys: *mut f32, bits: *mut u32, inv32: *mut f32) -> c_int;
     pub fn nrays_trace_rays_device(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_trace_rays(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, refr: *const f64, energy: *const f32, keys: *const u64, max_depth: u32, out_rgb: *mut f32) -> c_int;
     pub fn nrays_intersects_rays_device(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, max_toi: *const f64, out_filter: *mut f32, out_lit: *mut u32, hip_stream: *mut c_void) -> c_int;

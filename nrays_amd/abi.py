@@ -134,6 +134,8 @@ HIP_SYMBOLS = {
     "nrays_get_tile_costs": (C.c_int, [C.c_void_p, C.POINTER(NraysTileCosts)]),
     "nrays_debug_cast_batch": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                          C.POINTER(NraysCastResult)]),
+    "nrays_debug_box_cull": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float),
+                                       C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "nrays_trace_rays_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "nrays_trace_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_float),
                                    C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_float)]),
@@ -210,7 +212,8 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_cast_rays_device", "nrays_cast_rays", "nrays_shade_points_device", "nrays_shade_points", "nrays_occlusion_points_device",
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
                    "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points",
-                   "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels")
+                   "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels",
+                   "nrays_debug_box_cull")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch, nrays_debug_box_cull; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <new>
 #include <string>
@@ -310,6 +311,36 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DSc
             }
         }
         out[i] = r;
+    }
+}
+
+// nrays_debug_box_cull: ONE node visit of the traversals on a case from memory — make_rayf, best_f32, the fetch of the node's planes, box_keys4 and,
+// for a ray with an f32-zero component, zero_axis_cull: the product functions themselves, in the order traverse() calls them.  Case i reads node i.
+// uniform = 0: a case per lane, planes through load_planes.  uniform = 1: a case per WAVE (all its lanes compute the same case, so that they share
+// the node and the direction signs as load_planes_uniform requires; the first lane writes), planes through the scalar fetch.
+__global__ void __launch_bounds__(kBlock) k_box_cull(const BvhNode* __restrict__ nodes, uint32_t uniform, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                     const double* __restrict__ best, float* __restrict__ keys, uint32_t* __restrict__ bits, float* __restrict__ inv32) {
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, threads = gridDim.x * kBlock;
+    const uint32_t step = uniform ? threads >> 6 : threads;
+    for (uint32_t i = uniform ? tid >> 6 : tid; i < n; i += step) {
+        const d3 o = D3(ro[3 * (size_t)i], ro[3 * (size_t)i + 1], ro[3 * (size_t)i + 2]), d = D3(rd[3 * (size_t)i], rd[3 * (size_t)i + 1], rd[3 * (size_t)i + 2]);
+        const RayF rf = make_rayf(o, d);
+        const float btf = best_f32(best[i]);
+        float k0, k1, k2, k3;
+        if (uniform) {
+            const uint32_t ukey = (uint32_t)__builtin_amdgcn_readfirstlane((int)((i << 7) | rf.bits));
+            const NodePlanes np = load_planes_uniform(nodes, ukey);
+            box_keys4(np, rf, btf, k0, k1, k2, k3);
+            if ((rf.bits & 7u)) zero_axis_cull((rf.bits & 7u), o, np, k0, k1, k2, k3);
+        } else {
+            const NodePlanes np = load_planes(nodes, (int32_t)i, rf);
+            box_keys4(np, rf, btf, k0, k1, k2, k3);
+            if ((rf.bits & 7u)) zero_axis_cull((rf.bits & 7u), o, np, k0, k1, k2, k3);
+        }
+        if (uniform && (threadIdx.x & 63u)) continue;
+        keys[4 * (size_t)i] = k0; keys[4 * (size_t)i + 1] = k1; keys[4 * (size_t)i + 2] = k2; keys[4 * (size_t)i + 3] = k3;
+        bits[i] = rf.bits;
+        inv32[3 * (size_t)i] = rf.ix; inv32[3 * (size_t)i + 1] = rf.iy; inv32[3 * (size_t)i + 2] = rf.iz;
     }
 }
 
@@ -1205,6 +1236,42 @@ int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const doub
     CAST_TRY(hipStreamSynchronize(sc->buf.own_stream));
     CAST_TRY(hipMemcpy(out, d_r, (size_t)n * sizeof(NraysCastResult), hipMemcpyDeviceToHost));
 #undef CAST_TRY
+    release();
+    return NRAYS_OK;
+}
+
+int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* best, const float* boxes, const uint32_t* slots,
+                         float* keys, uint32_t* bits, float* inv32) {
+    if (!origins || !dirs || !best || !boxes || !slots || !keys || !bits || !inv32 || mode > 1u) return set_last_error(NRAYS_ERR_BAD_ARG, "bad box-cull arguments");
+    if (n > (1u << 24)) return set_last_error(NRAYS_ERR_BAD_ARG, "box-cull: more than 2^24 cases"); // (node index << 7 in 32 bits, as the scenes: scene_build.cpp)
+    if (n == 0) return NRAYS_OK;
+    for (uint32_t i = 0; i < n; ++i) if (slots[i] > 3u) return set_last_error(NRAYS_ERR_BAD_ARG, "box-cull: child slot above 3");
+    std::vector<BvhNode> nodes;
+    try { nodes.resize(n); } catch (const std::bad_alloc&) { return set_last_error(NRAYS_ERR_OOM, "box-cull nodes"); }
+    const float absent_mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, absent_mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (uint32_t i = 0; i < n; ++i) {
+        BvhNode& nd = nodes[i];
+        for (int k = 0; k < 4; ++k) { nd.slot[5][k] = 0.0f; nd.set_box(k, absent_mn, absent_mx); nd.children()[k] = kEmptyChild; }
+        nd.set_box((int)slots[i], boxes + 6 * (size_t)i, boxes + 6 * (size_t)i + 3);
+    }
+    BvhNode* d_n = nullptr; double *d_o = nullptr, *d_d = nullptr, *d_b = nullptr; float *d_k = nullptr, *d_i = nullptr; uint32_t* d_bits = nullptr;
+    auto release = [&]() { for (void* q : {(void*)d_n, (void*)d_o, (void*)d_d, (void*)d_b, (void*)d_k, (void*)d_i, (void*)d_bits}) if (q) (void)hipFree(q); };
+#define CULL_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    const size_t vb = (size_t)n * 3 * sizeof(double);
+    CULL_TRY(hipMalloc((void**)&d_n, (size_t)n * sizeof(BvhNode))); CULL_TRY(hipMalloc((void**)&d_o, vb)); CULL_TRY(hipMalloc((void**)&d_d, vb));
+    CULL_TRY(hipMalloc((void**)&d_b, (size_t)n * sizeof(double))); CULL_TRY(hipMalloc((void**)&d_k, (size_t)n * 4 * sizeof(float)));
+    CULL_TRY(hipMalloc((void**)&d_i, (size_t)n * 3 * sizeof(float))); CULL_TRY(hipMalloc((void**)&d_bits, (size_t)n * sizeof(uint32_t)));
+    CULL_TRY(hipMemcpy(d_n, nodes.data(), (size_t)n * sizeof(BvhNode), hipMemcpyHostToDevice));
+    CULL_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CULL_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
+    CULL_TRY(hipMemcpy(d_b, best, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    const uint64_t threads = mode == 1u ? (uint64_t)n * 64u : (uint64_t)n;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((threads + kBlock - 1) / kBlock, (uint64_t)kMaxGrid);
+    hipLaunchKernelGGL(k_box_cull, dim3(grid), dim3(kBlock), 0, (hipStream_t)0, (const BvhNode*)d_n, mode, n, (const double*)d_o, (const double*)d_d, (const double*)d_b, d_k, d_bits, d_i);
+    CULL_TRY(hipGetLastError());
+    CULL_TRY(hipDeviceSynchronize());
+    CULL_TRY(hipMemcpy(keys, d_k, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost)); CULL_TRY(hipMemcpy(bits, d_bits, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    CULL_TRY(hipMemcpy(inv32, d_i, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+#undef CULL_TRY
     release();
     return NRAYS_OK;
 }

@@ -687,10 +687,20 @@ struct RayF {
                             // upper plane of that axis inside a BvhNode); bits 0..2: component a is zero in f32
                             // (zero_axis_cull() handles that axis)
 };
+// A component beyond 1e30 in magnitude (caller-supplied rays are not unit vectors) is taken out of the slab arithmetic too, WITHOUT the
+// zero-axis rule: its reciprocal approaches the f32 denormals — v_rcp_f32 returns 0 for a denormal result, from ~8.5e37 on —, where "relative
+// error 3 * 2^-24" no longer holds, and a zero reciprocal used to hand the axis to zero_axis_cull, the rule for a ray PARALLEL to the slab, while
+// this ray crosses it at once: boxes the reference accepts were culled.  The axis now constrains nothing (inverse 0, addends -inf / +inf,
+// no zero-axis bit), which only widens the superset.  One thing must survive: the inverted box of an absent child has to get +inf, and with
+// ALL three axes unconstrained it would get 0.  Then the x axis keeps a slab that no real box constrains — inverse 1e-8, addends -1e29 /
+// +1e29: for |b| <= 1e36 the entry distance b 1e-8 - 1e29 is negative and the exit distance at least 9e28, far beyond the reference's own
+// exit on this axis, (|b| + |o|) / 1e30 <= 2e6 — while +-FLT_MAX gives entry 3.3e30 > exit -3.3e30.
+// (Written as three more compares here and one rare branch: a form that rewrites the three axes in one cold branch costs up to 8 VGPRs
+// in the trace kernels, profiles/README.md.)
 NR_DEV float inv_f32(double d) { // 0 = "this axis does not constrain the ray" (see above)
     float x = (float)d;
     float r = __builtin_amdgcn_rcpf(x);
-    return (fabsf(x) > 1e-30f && fabsf(r) < 1e30f) ? r : 0.0f;
+    return (fabsf(x) > 1e-30f && fabsf(r) < 1e30f && fabsf(r) > 1e-30f) ? r : 0.0f;
 }
 NR_DEV RayF make_rayf(d3 o, d3 d) {
     RayF r;
@@ -703,7 +713,8 @@ NR_DEV RayF make_rayf(d3 o, d3 d) {
     r.nny = r.iy != 0.0f ? -py - ey : -kInf; r.nfy = r.iy != 0.0f ? -py + ey : kInf;
     r.nnz = r.iz != 0.0f ? -pz - ez : -kInf; r.nfz = r.iz != 0.0f ? -pz + ez : kInf;
     r.bits = (r.ix < 0.0f ? 16u : 0u) | (r.iy < 0.0f ? 32u : 0u) | (r.iz < 0.0f ? 64u : 0u) |
-             (r.ix == 0.0f ? 1u : 0u) | (r.iy == 0.0f ? 2u : 0u) | (r.iz == 0.0f ? 4u : 0u);
+             (r.ix == 0.0f && fabsf((float)d.x) < 1.0f ? 1u : 0u) | (r.iy == 0.0f && fabsf((float)d.y) < 1.0f ? 2u : 0u) | (r.iz == 0.0f && fabsf((float)d.z) < 1.0f ? 4u : 0u);
+    if (__builtin_expect(r.bits == 0u && r.ix == 0.0f && r.iy == 0.0f && r.iz == 0.0f, 0)) { r.ix = 1e-8f; r.nnx = -1e29f; r.nfx = 1e29f; } // all three beyond 1e30
     return r;
 }
 // Upper f32 bound of the current best distance (ties with it must still be visited).
