@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -538,6 +538,45 @@ int nrays_dilate_texels_device(NraysScene* scene, uint32_t width, uint32_t heigh
 /* Same, every pointer HOST memory.  Blocking. */
 int nrays_dilate_texels(NraysScene* scene, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius,
                         uint32_t channels, float* values, int32_t* out_source, uint32_t* out_flags, uint32_t flags);
+
+/* Denoising of a baked light map: one pass of a 5 x 5 a-trous (B3-spline) joint-bilateral filter over the lattice, the step between
+ * nrays_gather_points_device (a Monte-Carlo mean, noisy at few rays) and nrays_dilate_texels_device.  Neighbouring lattice points are averaged only where they
+ * lie on the same piece of surface — close in the world, facing the same way —, never across a chart border, a gutter or a crease.
+ * The lattice, the indexing i = y * width + x and "covered iff bit 0 of flags_in[i]" are those of nrays_dilate_texels*; points / normals (3 doubles per
+ * lattice point) and flags_in are out_points / out_normals / out_flags of nrays_surface_texels*, unfiltered; values_in / values_out hold `channels`
+ * (1 .. 4) floats per point, point i at [i * channels ...].  The result is defined exactly (Python: nrays_amd.filter_texels_ref); nothing is fused:
+ * every product and every sum is rounded on its own.  For every COVERED point (x, y) with point p, normal n:
+ *   taps        (i, j) for j = -2 .. 2 (outer loop) and i = -2 .. 2 (inner loop) at x' = x + i * step, y' = y + j * step, with point p', normal n', values v'.
+ *               A tap outside the lattice or on an uncovered point is skipped.  No wrap-around.
+ *   kernel      k = (float)(h[i + 2] * h[j + 2]), h = {1, 4, 6, 4, 1}: the integers 1 .. 36; the division by 256 is left to the normalisation.
+ *   centre tap  (i = j = 0): w = 36, whatever its point and normal hold.  The weight sum is therefore never 0.
+ *   other taps  in f64, left to right as written:
+ *                 d2 = ((p'.x - p.x) * (p'.x - p.x) + (p'.y - p.y) * (p'.y - p.y)) + (p'.z - p.z) * (p'.z - p.z)
+ *                 wp = 1.0 - d2 / (pos_radius * pos_radius)          skipped unless wp > 0 (a NaN skips; pos_radius = +inf gives wp = 1 for finite points)
+ *                 c  = (n.x * n'.x + n.y * n'.y) + n.z * n'.z
+ *                 wn = (c - normal_cos) / (1.0 - normal_cos)         skipped unless wn > 0; wn > 1 becomes 1.0
+ *               then in f32:  w = (k * (float)wp) * (float)wn
+ *   sum         in f32, in tap order, for each channel: acc = acc + w * v' (the product rounded, then the sum), wsum = wsum + w, both from +0;
+ *               values_out = acc / wsum, one correctly rounded division per channel.
+ * An UNCOVERED point: the `channels` words of values_in are copied to values_out as bit patterns (NaN payloads and -0 pass unchanged), so that the output
+ * is a complete map which nrays_dilate_texels* can take next.  The result does not depend on how lanes and tiles are assigned.  A pass with
+ * step = 1, 2, 4, ... after one another (two buffers) is the a-trous sequence: three passes reach 4 * 7 + 1 = 29 texels across.
+ * NULL scene / flags_in / points / normals / values_in / values_out, values_out == values_in, channels outside 1 .. 4, step outside
+ * 1 .. NRAYS_FILTER_MAX_STEP, width or height outside 1 .. 16384, width * height > 2^24, a NaN or <= 0 pos_radius, a normal_cos that is not in [-1, 1),
+ * flags != 0 (reserved) -> NRAYS_ERR_BAD_ARG, checked before any device work.  Any other overlap of values_in and values_out is undefined.  Otherwise the contract of
+ * nrays_dilate_texels_device: every pointer DEVICE memory on the scene's device, one launch enqueued on `hip_stream` without read-back or
+ * synchronisation, ordered behind the handle's previous work; no workspace; what the handle reports about its renders and its per-camera scheduling
+ * state stay untouched. */
+#define NRAYS_FILTER_MAX_STEP 64u
+int nrays_filter_texels_device(NraysScene* scene, uint32_t width, uint32_t height, const uint32_t* flags_in,
+                               const double* points, const double* normals, uint32_t channels,
+                               const float* values_in, float* values_out,
+                               uint32_t step, double pos_radius, double normal_cos, uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_filter_texels(NraysScene* scene, uint32_t width, uint32_t height, const uint32_t* flags_in,
+                        const double* points, const double* normals, uint32_t channels,
+                        const float* values_in, float* values_out,
+                        uint32_t step, double pos_radius, double normal_cos, uint32_t flags);
 
 /* Test probe of the reorder: runs exactly the key and binning kernels of ONE hinted chunk (n <= 2^22) on n rays and returns
  *   out_keys   n keys (nrays_amd/csrc/ray_key.h), out_order  out_order[j] = index of the ray traced j-th (a permutation of 0..n-1),

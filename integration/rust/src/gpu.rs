@@ -509,6 +509,33 @@ impl GpuScene {
         Ok(())
     }
 
+    /// One pass of the edge-aware filter that denoises a baked `width` x `height` light map (nrays_filter_texels, blocking): a 5 x 5 a-trous joint-bilateral
+    /// filter with taps `step` (1 ..= NRAYS_FILTER_MAX_STEP) texels apart.  A texel whose `flags` word has bit 0 set becomes the weighted mean of the covered
+    /// texels among its taps, weighted by the B3 spline, by the squared world distance (0 at `pos_radius`; f64::INFINITY: off) and by the cosine between the
+    /// normals (0 at `normal_cos`, in [-1, 1)); every other texel keeps its words.  `flags`, `points`, `normals` (n x 3 f64) are those of
+    /// `surface_texels_device` as they come; `values` holds `channels` (1 ..= 4) floats per texel.  Returns the filtered copy; passes with step 1, 2, 4
+    /// after one another are the usual denoiser, between the gather and `dilate_texels`.
+    pub fn filter_texels(&self, width: u32, height: u32, flags: &[u32], points: &[f64], normals: &[f64], channels: u32, values: &[f32], step: u32, pos_radius: f64,
+                         normal_cos: f64) -> Result<Vec<f32>, String> {
+        let n = width as usize * height as usize;
+        if flags.len() != n || points.len() != 3 * n || normals.len() != 3 * n || values.len() != n * channels as usize {
+            return Err("filter_texels: flags / points / normals / values do not match width * height".into());
+        }
+        let mut out = vec![0f32; values.len()];
+        let rc = unsafe { nrays_filter_texels(self.raw, width, height, flags.as_ptr(), points.as_ptr(), normals.as_ptr(), channels, values.as_ptr(), out.as_mut_ptr(), step, pos_radius, normal_cos, 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(out)
+    }
+
+    /// `filter_texels` on DEVICE memory (nrays_filter_texels_device), one launch enqueued on `hip_stream` without synchronisation, behind the calls that baked
+    /// `values_in`: flags_in n u32, points / normals n x 3 f64, values_in / values_out n x channels f32.  values_out must not be values_in; any other
+    /// overlap of the two is undefined.
+    pub unsafe fn filter_texels_device(&self, width: u32, height: u32, flags_in: *const u32, points: *const f64, normals: *const f64, channels: u32, values_in: *const f32,
+                                       values_out: *mut f32, step: u32, pos_radius: f64, normal_cos: f64, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_filter_texels_device(self.raw, width, height, flags_in, points, normals, channels, values_in, values_out, step, pos_radius, normal_cos, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
     /// `cast_rays` for n rays in DEVICE memory (nrays_cast_rays_device), enqueued on `hip_stream` without synchronisation: origins / dirs n x 3 f64,
     /// max_toi n f64 or null, out_toi n f64, out_node n i32; out_normal (n x 3 f64), out_uv (n x 2 f64), out_prim (n i32) and out_flags (n u32) may
     /// each be null.  A miss writes node -1 and toi +inf.  `flags`: 0 or NRAYS_RAYS_UNORDERED.

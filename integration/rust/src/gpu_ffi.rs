@@ -20,6 +20,7 @@ pub const NRAYS_TEXELS_FLIP_NORMALS: u32 = 2;
 pub const NRAYS_DILATE_MAX_RADIUS: u32 = 64;
 /// set in out_flags of nrays_dilate_texels* at a texel that was filled from a covered one (bit 0 stays clear there)
 pub const NRAYS_TEXEL_FILLED: u32 = 4;
+pub const NRAYS_FILTER_MAX_STEP: u32 = 64;
 
 // NraysShapeKind (examples/loader3d.rs:593-695)
 pub const NRAYS_SHAPE_BALL: u32 = 0;
@@ -278,6 +279,8 @@ extern "C" {
     pub fn nrays_debug_surface_texels_passes(scene: *mut NraysScene, node: u32, width: u32, height: u32, flags: u32, repeats: u32, out_ms: *mut f32) -> c_int;
     pub fn nrays_dilate_texels_device(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, radius: u32, channels: u32, values: *mut f32, out_source: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_dilate_texels(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, radius: u32, channels: u32, values: *mut f32, out_source: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_filter_texels_device(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, points: *const f64, normals: *const f64, channels: u32, values_in: *const f32, values_out: *mut f32, step: u32, pos_radius: f64, normal_cos: f64, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_filter_texels(scene: *mut NraysScene, width: u32, height: u32, flags_in: *const u32, points: *const f64, normals: *const f64, channels: u32, values_in: *const f32, values_out: *mut f32, step: u32, pos_radius: f64, normal_cos: f64, flags: u32) -> c_int;
     pub fn nrays_debug_ray_order(scene: *mut NraysScene, n: u32, origins: *const f64, dirs: *const f64, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
 
     pub fn nrays_comm_unique_id(out_id: *mut u8) -> c_int;

@@ -175,6 +175,10 @@ HIP_SYMBOLS = {
     "nrays_dilate_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nrays_dilate_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_int32),
                                       C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_filter_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double,
+                                             C.c_uint32, C.c_void_p]),
+    "nrays_filter_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_float),
+                                      C.POINTER(C.c_float), C.c_uint32, C.c_double, C.c_double, C.c_uint32]),
     "nrays_debug_ray_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
     "nrays_scene_create": (C.c_int, [C.POINTER(NraysSceneDesc), C.POINTER(C.c_void_p)]),
@@ -213,12 +217,13 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
                    "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points",
                    "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels",
-                   "nrays_debug_box_cull")
+                   "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS
 DILATE_MAX_RADIUS = 64       # NRAYS_DILATE_MAX_RADIUS
 TEXEL_FILLED = 4            # NRAYS_TEXEL_FILLED
+FILTER_MAX_STEP = 64        # NRAYS_FILTER_MAX_STEP
 RAY_FRAME_DOUBLES = 20      # NRAYS_RAY_FRAME_DOUBLES
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

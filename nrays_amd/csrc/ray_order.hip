@@ -32,6 +32,7 @@
 #include "scene_handle.h"
 #include "surface_texels_kernel.h"
 #include "texel_dilate_kernel.h"
+#include "texel_filter_kernel.h"
 
 static_assert(NRAYS_RAY_FRAME_DOUBLES == nrays::kRayFrameDoubles, "include/nrays_abi.h and ray_key.h disagree on the frame");
 
@@ -1209,6 +1210,83 @@ static int dilate_texels_host_impl(NraysScene* sc, const DilateArgs& a, uint32_t
     return rc;
 }
 
+// ---- nrays_filter_texels*: one pass of the 5 x 5 a-trous joint-bilateral filter over a baked map (texel_filter_kernel.h) ---------------------------------------------
+static_assert(kFilterMaxStep == NRAYS_FILTER_MAX_STEP, "texel_filter_kernel.h restates the header's constant");
+struct FilterArgs { uint32_t width, height; const uint32_t* flags_in; const double* points; const double* normals; uint32_t channels; const float* values_in; float* values_out;
+                    uint32_t step; double pos_radius, normal_cos; };
+static int check_filter_args(const NraysScene* sc, const FilterArgs& a, uint32_t flags) {
+    if (!sc || !a.flags_in || !a.points || !a.normals || !a.values_in || !a.values_out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (a.values_out == a.values_in) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: values_out must not be values_in (a pass reads its neighbours' inputs)");
+    if (a.channels < 1u || a.channels > 4u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: channels must be in 1 .. 4");
+    if (a.step < 1u || a.step > NRAYS_FILTER_MAX_STEP) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: step must be in 1 .. 64");
+    if (a.width < 1u || a.width > kTexelMaxSide || a.height < 1u || a.height > kTexelMaxSide || (uint64_t)a.width * a.height > kTexelMaxPoints)
+        return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: width and height must be in 1 .. 16384 and width * height <= 2^24");
+    if (!(a.pos_radius > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: pos_radius must be > 0 (+inf: no position weight)");
+    if (!(a.normal_cos >= -1.0 && a.normal_cos < 1.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: normal_cos must be in [-1, 1)");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_filter_texels: flags are reserved and must be 0");
+    return NRAYS_OK;
+}
+// The one launch of a call: per axis ceil(ceil(side / step) / tile) blocks of each of the `step` residue classes.
+static int filter_pass(const FilterArgs& a, hipStream_t stream) {
+    const uint32_t sub_w = (a.width + a.step - 1u) / a.step, sub_h = (a.height + a.step - 1u) / a.step;
+    const FilterLattice L{a.width, a.height, a.step, (sub_w + kFilterTileX - 1u) / kFilterTileX, (sub_h + kFilterTileY - 1u) / kFilterTileY,
+                          a.pos_radius * a.pos_radius, a.normal_cos, 1.0 - a.normal_cos};
+    const dim3 grid(L.tiles_x * a.step, L.tiles_y * a.step);
+    const uint32_t vec4 = (a.channels == 4u && (((uintptr_t)a.values_in | (uintptr_t)a.values_out) & 15u) == 0u) ? 1u : 0u;
+    switch (a.channels) {
+    case 1u: hipLaunchKernelGGL(k_filter_texels<1>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, 0u); break;
+    case 2u: hipLaunchKernelGGL(k_filter_texels<2>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, 0u); break;
+    case 3u: hipLaunchKernelGGL(k_filter_texels<3>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, 0u); break;
+    default: hipLaunchKernelGGL(k_filter_texels<4>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, vec4); break;
+    }
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_filter_texels: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+static int filter_texels_device_impl(NraysScene* sc, const FilterArgs& a, uint32_t flags, hipStream_t stream) {
+    { const int rc = check_filter_args(sc, a, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr; // (for the handle's stream ordering alone: the call needs no workspace)
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    rc = filter_pass(a, stream);
+    batch_end(sc, w, stream);
+    return rc;
+}
+// The blocking form, through the workspace's staging buffer as dilate_texels_host_impl: points, normals, the two value arrays (each at a multiple of 16 bytes), flags.
+static int filter_texels_host_impl(NraysScene* sc, const FilterArgs& a, uint32_t flags) {
+    { const int rc = check_filter_args(sc, a, flags); if (rc != NRAYS_OK) return rc; }
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    const size_t n = (size_t)a.width * a.height, geo_bytes = n * 3 * sizeof(double), value_bytes = n * a.channels * sizeof(float), value_slot = (value_bytes + 15) & ~(size_t)15;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = grow_device(&w->d_stage, &w->stage_rays, (2 * geo_bytes + 2 * value_slot + n * 4 + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc == NRAYS_OK) rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    char* base = (char*)w->d_stage;
+    FilterArgs s = a;
+    s.points = (const double*)base; s.normals = (const double*)(base + geo_bytes);
+    s.values_in = (const float*)(base + 2 * geo_bytes); s.values_out = (float*)(base + 2 * geo_bytes + value_slot);
+    s.flags_in = (const uint32_t*)(base + 2 * geo_bytes + 2 * value_slot);
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    auto up = [&](const void* dst, const void* src, size_t bytes) { return hipMemcpyAsync((void*)dst, src, bytes, hipMemcpyHostToDevice, stream); };
+    hipError_t e = up(s.points, a.points, geo_bytes);
+    if (e == hipSuccess) e = up(s.normals, a.normals, geo_bytes);
+    if (e == hipSuccess) e = up(s.values_in, a.values_in, value_bytes);
+    if (e == hipSuccess) e = up(s.flags_in, a.flags_in, n * 4);
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("filter texels upload: ") + hipGetErrorString(e));
+    if (rc == NRAYS_OK) rc = filter_pass(s, stream);
+    if (rc == NRAYS_OK) e = hipMemcpyAsync(a.values_out, s.values_out, value_bytes, hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next call, and the uploads read the caller's arrays)
+    if (e == hipSuccess) e = es;
+    if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("filter texels read-back: ") + hipGetErrorString(e));
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -1443,6 +1521,15 @@ int nrays_dilate_texels_device(NraysScene* sc, uint32_t width, uint32_t height, 
 int nrays_dilate_texels(NraysScene* sc, uint32_t width, uint32_t height, const uint32_t* flags_in, uint32_t radius, uint32_t channels, float* values, int32_t* out_source,
                         uint32_t* out_flags, uint32_t flags) {
     return dilate_texels_host_impl(sc, DilateArgs{width, height, flags_in, radius, channels, values, out_source, out_flags}, flags);
+}
+
+int nrays_filter_texels_device(NraysScene* sc, uint32_t width, uint32_t height, const uint32_t* flags_in, const double* points, const double* normals, uint32_t channels,
+                               const float* values_in, float* values_out, uint32_t step, double pos_radius, double normal_cos, uint32_t flags, void* hip_stream) {
+    return filter_texels_device_impl(sc, FilterArgs{width, height, flags_in, points, normals, channels, values_in, values_out, step, pos_radius, normal_cos}, flags, (hipStream_t)hip_stream);
+}
+int nrays_filter_texels(NraysScene* sc, uint32_t width, uint32_t height, const uint32_t* flags_in, const double* points, const double* normals, uint32_t channels,
+                        const float* values_in, float* values_out, uint32_t step, double pos_radius, double normal_cos, uint32_t flags) {
+    return filter_texels_host_impl(sc, FilterArgs{width, height, flags_in, points, normals, channels, values_in, values_out, step, pos_radius, normal_cos}, flags);
 }
 
 int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, uint64_t* out_keys, uint32_t* out_order, double* out_frame,

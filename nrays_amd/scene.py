@@ -422,6 +422,14 @@ class Scene:
         """Gutter dilation of a light map on this scene's GPU: dilate_texels(self, flags, ...)."""
         return dilate_texels(self, flags, width, height, radius, values, want_source, device)
 
+    def filter_texels(self, flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0, device=None):
+        """One pass of the edge-aware light-map filter on this scene's GPU: filter_texels(self, flags, ...)."""
+        return filter_texels(self, flags, width, height, points, normals, values, step, pos_radius, normal_cos, device)
+
+    def denoise_texels(self, tx, values, passes=3, pos_radius=math.inf, normal_cos=0.0, width=None, height=None):
+        """A baked light map denoised on this scene's GPU: denoise_texels(self, tx, values, ...)."""
+        return denoise_texels(self, tx, values, passes, pos_radius, normal_cos, width, height)
+
     def _release(self):
         if self._handle is not None:
             abi.load_hip_lib().nrays_scene_destroy(self._handle)
@@ -1240,6 +1248,8 @@ def bake_lightmap(scene, node, width, height, occlusion=None, centres=False, fli
     the tables are then tensors (the tables may be anything numpy takes).  `dilate`: a radius in texels (1 .. 64): the gutters are filled from the nearest
     covered texel by dilate_texels(), one more call on the same stream; 0 = off, the calls and the result above exactly.  A map that is sampled with
     Bilinear (lightmap_texture()) needs dilate >= 2: the diagonal neighbour of a border texel lies at d2 = 2.
+    A noisy map is denoised BETWEEN the bake and the dilation, by the calls themselves: tx = surface_texels(...); rgb = gather_points(...);
+    rgb = denoise_texels(scene, tx, rgb, width=width, height=height); dilate_texels(..., values=rgb).
     Also `scene.bake_lightmap(node, ...)` on Scene and FileScene."""
     tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals", "uv", "node"), device=device)
     rgba = shade_points(scene, tx.points, tx.normals, -tx.normals, tx.node, uvs=tx.uv, hit_flags=tx.flags, keys=keys)
@@ -1259,8 +1269,9 @@ def bake_indirect(scene, node, width, height, sample_dirs, rotations=None, bias=
     (width * height,) RNG keys (default: texel i has key i).  `device` as for surface_texels: with a torch device everything stays on the GPU, two calls on one
     stream; `keys` is then a tensor (the tables may be anything numpy takes).  `unordered`: as for gather_points.  `dilate` (keyword only, see
     _dilate_keyword): as for bake_lightmap — a radius in texels, filled by dilate_texels() on the same stream; 0 = off, today's calls and result exactly;
-    Bilinear sampling needs dilate >= 2 (the diagonal neighbour of a border texel lies at d2 = 2).  Also `scene.bake_indirect(node, ...)` on Scene and
-    FileScene."""
+    Bilinear sampling needs dilate >= 2 (the diagonal neighbour of a border texel lies at d2 = 2).  The mean of few rays is noisy; the recipe with the
+    denoising step between the gather and the dilation: tx = surface_texels(...); rgb = gather_points(...); rgb = denoise_texels(scene, tx, rgb, width=width, height=height);
+    dilate_texels(..., values=rgb).  Also `scene.bake_indirect(node, ...)` on Scene and FileScene."""
     tx = surface_texels(scene, node, width, height, centres, flip_normals, want=("normals",), device=device)
     rgb = gather_points(scene, tx.points, tx.normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=tx.flags, keys=keys, unordered=unordered)
     return rgb.reshape(int(height), int(width), 3)
@@ -1410,6 +1421,171 @@ def _bake_dilate(scene, flags, out, width, height, radius):
     if not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
         out = out.contiguous() if _is_tensor(out) else np.ascontiguousarray(out)
     return dilate_texels(scene, flags, width, height, radius, values=out)[0]
+
+
+# ---- denoising a baked map: the a-trous joint-bilateral filter (include/nrays_abi.h: nrays_filter_texels_device) -----------------------------------------------
+
+FILTER_TAPS = (1, 4, 6, 4, 1)  # the B3 spline; a tap's kernel weight is the product of two of them, 1 .. 36
+
+
+def _filter_args(flags, width, height, points, normals, values, step, pos_radius, normal_cos):
+    """Checks shared by filter_texels, filter_texels_ref and denoise_texels: (width, height, step, pos_radius, normal_cos, channels)."""
+    width, height = _texel_lattice(width, height)
+    step, pos_radius, normal_cos = int(step), float(pos_radius), float(normal_cos)
+    if not 1 <= step <= abi.FILTER_MAX_STEP:
+        raise ValueError("step must be in 1 .. %d, got %d" % (abi.FILTER_MAX_STEP, step))
+    if not pos_radius > 0.0:
+        raise ValueError("pos_radius must be > 0 (math.inf: no position weight), got %r" % pos_radius)
+    if not -1.0 <= normal_cos < 1.0:
+        raise ValueError("normal_cos must be in [-1, 1), got %r" % normal_cos)
+    n = width * height
+    for name, a, per in (("flags", flags, 1), ("points", points, 3), ("normals", normals, 3)):
+        if a is None:
+            raise ValueError("%s is required" % name)
+        if int(np.prod(tuple(a.shape))) != n * per:
+            raise ValueError("%s must hold %d x width * height = %d words, got shape %s" % (name, per, n * per, tuple(a.shape)))
+    if values is None:
+        raise ValueError("values is required")
+    size = int(np.prod(tuple(values.shape)))
+    channels = size // n
+    if channels * n != size or not 1 <= channels <= 4:
+        raise ValueError("values must hold 1 .. 4 floats per lattice point (%d points), got shape %s" % (n, tuple(values.shape)))
+    return width, height, step, pos_radius, normal_cos, channels
+
+
+def filter_texels_ref(flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0):
+    """The numpy mirror of nrays_filter_texels_device's definition (include/nrays_abi.h), bit for bit: what filter_texels() returns, a new float32 array in
+    the shape of `values`.  Vectorised: every tap (i, j) is one pair of shifted slices of the lattice, the taps in the definition's order, a skipped tap
+    leaving acc and wsum as they are (np.where, not a weight of 0: 0 * inf would be a NaN).  f64 where the definition says f64, float32 arrays where it
+    says f32; numpy rounds every operation on its own."""
+    flags, values = np.asarray(flags), np.asarray(values)
+    if not np.issubdtype(flags.dtype, np.integer):
+        raise ValueError("flags must be integers, got %s" % flags.dtype)
+    if values.dtype != np.float32:
+        raise ValueError("values must be float32, got %s" % values.dtype)
+    points, normals = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    w, h, step, pos_radius, normal_cos, channels = _filter_args(flags, width, height, points, normals, values, step, pos_radius, normal_cos)
+    cov = (flags.astype(np.uint32, copy=False).reshape(h, w) & np.uint32(1)) != 0
+    p, nm, v = points.reshape(h, w, 3), normals.reshape(h, w, 3), np.ascontiguousarray(values).reshape(h, w, channels)
+    acc, wsum = np.zeros((h, w, channels), np.float32), np.zeros((h, w), np.float32)
+    r2, cos, den = np.float64(pos_radius) * np.float64(pos_radius), np.float64(normal_cos), np.float64(1.0) - np.float64(normal_cos)
+    with np.errstate(all="ignore"):
+        for j in range(-2, 3):
+            for i in range(-2, 3):
+                dx, dy = i * step, j * step
+                xa, xb, ya, yb = max(0, -dx), min(w, w - dx), max(0, -dy), min(h, h - dy)
+                if xa >= xb or ya >= yb:
+                    continue  # every tap of this offset lies outside the lattice
+                D, S = (slice(ya, yb), slice(xa, xb)), (slice(ya + dy, yb + dy), slice(xa + dx, xb + dx))
+                if i == 0 and j == 0:
+                    take, wt = cov, np.full((h, w), 36.0, np.float32)
+                else:
+                    take = cov[D] & cov[S]
+                    d = p[S] - p[D]
+                    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                    wp = np.float64(1.0) - d2 / r2
+                    c = (nm[D][..., 0] * nm[S][..., 0] + nm[D][..., 1] * nm[S][..., 1]) + nm[D][..., 2] * nm[S][..., 2]
+                    wn = (c - cos) / den
+                    take = take & (wp > 0.0) & (wn > 0.0)
+                    wn = np.where(wn > 1.0, np.float64(1.0), wn)
+                    wt = (np.float32(FILTER_TAPS[i + 2] * FILTER_TAPS[j + 2]) * wp.astype(np.float32)) * wn.astype(np.float32)
+                acc[D] = np.where(take[..., None], acc[D] + wt[..., None] * v[S], acc[D])
+                wsum[D] = np.where(take, wsum[D] + wt, wsum[D])
+        res = acc / wsum[..., None]
+    out = v.copy()  # uncovered points: the words as they are
+    out[cov] = res[cov]
+    return out.reshape(values.shape)
+
+
+def _filter_pass_device(lib, scene, w, h, f, p, nm, channels, v_in, v_out, step, pos_radius, normal_cos):
+    """One nrays_filter_texels_device call on contiguous tensors of one GPU, on torch.cuda.current_stream()."""
+    import torch
+    with torch.cuda.device(f.device):
+        abi.check(lib.nrays_filter_texels_device(scene.device_handle(), w, h, f.data_ptr(), p.data_ptr(), nm.data_ptr(), channels, v_in.data_ptr(), v_out.data_ptr(), step,
+                                                 pos_radius, normal_cos, 0, torch.cuda.current_stream().cuda_stream))
+
+
+def _filter_tensors(flags, points, normals, values, device):
+    """The four arrays of a filter call as contiguous tensors on one GPU (flags int32 / uint32, points / normals float64, values float32): tensors are
+    checked, numpy arrays are moved to `device`."""
+    import torch
+    if not _is_tensor(flags):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("device must be a GPU, got %s" % device)
+        flags = torch.from_numpy(_np_ints("flags", flags, np.uint32).view(np.int32)).to(device)
+        points, normals = (torch.from_numpy(_np_floats(name, a, np.float64)).to(device) for name, a in (("points", points), ("normals", normals)))
+        values = torch.from_numpy(_np_floats("values", values, np.float32)).to(device)
+    dev = flags.device
+    if dev.type != "cuda":
+        raise ValueError("flags must be on a GPU, got %s" % dev)
+    if device is not None and torch.device(device).index not in (None, dev.index):
+        raise ValueError("flags is on %s, device is %s" % (dev, device))
+    return _torch_args((("flags", flags, (torch.int32, torch.uint32)), ("points", points, (torch.float64,)), ("normals", normals, (torch.float64,)),
+                        ("values", values, (torch.float32,))), dev)
+
+
+def filter_texels(scene, flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0, device=None):
+    """One pass of the edge-aware filter that denoises a baked width x height light map, through nrays_filter_texels_device / nrays_filter_texels: a 5 x 5
+    a-trous (B3-spline) joint-bilateral filter whose taps lie `step` (1 .. 64) texels apart.  A covered texel becomes the weighted mean of the covered
+    texels among its 25 taps that lie on the same piece of surface: a tap's weight falls linearly with its squared world distance, reaching 0 at
+    `pos_radius` (math.inf: no position weight), and with the cosine between the normals, reaching 0 at `normal_cos` (in [-1, 1); -1 with unit normals:
+    no normal weight) — so nothing blends across a chart border, a gutter or a crease.  Uncovered texels keep their words.  `flags`, `points`,
+    `normals`: flags / points / normals of surface_texels() as they are; `values`: 1 .. 4 float32 per texel ((n, c), (height, width, c) or (n,)).
+    Returns a NEW array or tensor in the shape of `values`; the arguments stay as they are.
+    numpy arrays -> nrays_filter_texels (blocking).  torch tensors on the scene's GPU (flags int32, points / normals float64, values float32) ->
+    nrays_filter_texels_device on torch.cuda.current_stream(); `device` moves numpy arguments to that GPU first.  Also `scene.filter_texels(flags, ...)`
+    on Scene and FileScene; denoise_texels() runs the passes with steps 1, 2, 4, ...; filter_texels_ref() restates the result bit for bit."""
+    w, h, step, pos_radius, normal_cos, channels = _filter_args(flags, width, height, points, normals, values, step, pos_radius, normal_cos)
+    lib = abi.load_hip_lib()
+    if _is_tensor(flags) or device is not None:
+        import torch
+        f, p, nm, v = _filter_tensors(flags, points, normals, values, device)
+        out = torch.empty_like(v)
+        _filter_pass_device(lib, scene, w, h, f, p, nm, channels, v, out, step, pos_radius, normal_cos)
+        return out.reshape(tuple(values.shape))
+    for name, a in (("points", points), ("normals", normals), ("values", values)):
+        if _is_tensor(a):
+            raise ValueError("%s: torch tensors and numpy arrays cannot be mixed in one call" % name)
+    f = _np_ints("flags", flags, np.uint32)
+    p, nm, v = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64), _np_floats("values", values, np.float32)
+    out = np.empty_like(v)
+    ptr = lambda a, ct: a.ctypes.data_as(C.POINTER(ct))  # noqa: E731
+    abi.check(lib.nrays_filter_texels(scene.device_handle(), w, h, ptr(f, C.c_uint32), ptr(p, C.c_double), ptr(nm, C.c_double), channels, ptr(v, C.c_float), ptr(out, C.c_float),
+                                      step, pos_radius, normal_cos, 0))
+    return out.reshape(np.shape(values))
+
+
+def denoise_texels(scene, tx, values, passes=3, pos_radius=math.inf, normal_cos=0.0, width=None, height=None):
+    """A baked light map denoised: `passes` (1 .. 7) passes of filter_texels() with steps 1, 2, 4, ... on the texels `tx` — a SurfaceTexels with its normals,
+    surface_texels()'s result as it is — between two buffers, all on torch.cuda.current_stream(), nothing read back in between.  Three passes reach 29 texels
+    across at 75 taps.  `values`: (height, width, c) or, with `width` and `height` given, (n, c) / (n,); a tensor on the scene's GPU like tx's arrays, or
+    numpy arrays all of them, which are moved to the current GPU once and the result back.  Returns a new array or tensor in the shape of `values`.
+    The place of the call in a bake:
+        tx = surface_texels(...); rgb = gather_points(...); rgb = denoise_texels(scene, tx, rgb, width=w, height=h); dilate_texels(..., values=rgb)
+    Also `scene.denoise_texels(tx, values, ...)` on Scene and FileScene."""
+    passes = int(passes)
+    if not 1 <= passes <= 7:
+        raise ValueError("passes must be in 1 .. 7 (steps 1 .. %d), got %d" % (abi.FILTER_MAX_STEP, passes))
+    if width is None or height is None:
+        if len(values.shape) != 3:
+            raise ValueError("values must have shape (height, width, channels) unless width and height are given, got %s" % (tuple(values.shape),))
+        height, width = int(values.shape[0]), int(values.shape[1])
+    if getattr(tx, "normals", None) is None:
+        raise ValueError("tx must hold normals (surface_texels(..., want=('normals', ...)))")
+    w, h, _, pos_radius, normal_cos, channels = _filter_args(tx.flags, width, height, tx.points, tx.normals, values, 1, pos_radius, normal_cos)
+    lib = abi.load_hip_lib()
+    import torch
+    as_numpy = not _is_tensor(tx.flags)
+    f, p, nm, v = _filter_tensors(tx.flags, tx.points, tx.normals, values, torch.device("cuda", torch.cuda.current_device()) if as_numpy else None)
+    bufs = [v, torch.empty_like(v), torch.empty_like(v) if passes > 1 else None]  # the input is never written
+    src = 0
+    for k in range(passes):
+        dst = 1 if src != 1 else 2
+        _filter_pass_device(lib, scene, w, h, f, p, nm, channels, bufs[src], bufs[dst], 1 << k, pos_radius, normal_cos)
+        src = dst
+    out = bufs[src].reshape(tuple(values.shape))
+    return out.cpu().numpy() if as_numpy else out
 
 
 def ray_order(scene, origins, dirs):

@@ -2,6 +2,7 @@
 `.mtl`, `.obj` parsing and the PNG codec.  A FileScene exposes the same two members the render and
 oracle entry points need from nrays_amd.scene.Scene: `.descriptor.pointer()` and `.device_handle()`."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -140,6 +141,16 @@ class FileScene:
         """Gutter dilation of a light map on this scene's GPU: scene.dilate_texels(self, flags, ...)."""
         from .scene import dilate_texels
         return dilate_texels(self, flags, width, height, radius, values, want_source, device)
+
+    def filter_texels(self, flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0, device=None):
+        """One pass of the edge-aware light-map filter on this scene's GPU: scene.filter_texels(self, flags, ...)."""
+        from .scene import filter_texels
+        return filter_texels(self, flags, width, height, points, normals, values, step, pos_radius, normal_cos, device)
+
+    def denoise_texels(self, tx, values, passes=3, pos_radius=math.inf, normal_cos=0.0, width=None, height=None):
+        """A baked light map denoised on this scene's GPU: scene.denoise_texels(self, tx, values, ...)."""
+        from .scene import denoise_texels
+        return denoise_texels(self, tx, values, passes, pos_radius, normal_cos, width, height)
 
     def close(self):
         if self._handle is not None:

@@ -45,6 +45,13 @@ before (`radius` passes of an 8-neighbour fill written with torch ops on the sam
 the traffic floor: the bytes the call must move over the 6.29 TB/s a float4 copy reaches.  The expectation, written before the first run, is judged in the
 JSON: cheaper than the torch passes in every row, and at radius <= 8 cheaper than surface_texels().
 
+--filter (that leg and nothing else, into profiles/filter_rate.json) times the leg j_filter_texels: filter_texels() (nrays_filter_texels_device) with three float
+channels at steps 1, 2 and 4 and the three-pass denoise_texels() on the surface_texels() result of the --texels sine-surface grid (100 % covered) and of the
+--dilate atlas of 64 x 64 quad charts (gutters), at 1024^2 and 4096^2 — beside a torch restatement of one pass (25 shifted slices with the same weights; time
+only), beside the traffic floor ((52 + 8 * channels) bytes per texel over the 6.29 TB/s a float4 copy reaches), beside gather_points() with 16 directions on
+the same texels divided by 16 — what one more direction costs.  The expectations, written into the JSON before the first run, are judged per row: every pass
+cheaper than its torch restatement, and three passes cheaper than one more gathered direction.
+
 --gather times, and nothing else, the leg h_sponza_gather: the incoming light (gather_points(): Scene::trace on hemisphere rays built in registers, one mean
 colour per point) at the same two inputs as --occlusion — 16 directions at every first hit, 64 at a 16 384-point subset — beside what a caller did before it: the
 same rays built with torch on the device, trace_rays() on them with the keys of gather_ray_keys() unhinted and with unordered=True, and the torch fold of the
@@ -53,7 +60,7 @@ per-ray colours, each timed apart — beside itself under the hint (fused_unorde
 two inputs are then timed on the stand-in with a ball that reflects and refracts in the hall: a double-branching scene, where the call keeps a chunk's ray colours
 and runs the continuation queue per ray.  Alternating rounds, each of a few launches between events: min, median and max of every leg.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels] [--dilate]
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels] [--dilate] [--filter]
 """
 import argparse
 import ctypes as C
@@ -530,6 +537,96 @@ def _dilate_leg(reps, quick):
     return out
 
 
+def _torch_filter(cov, p, nm, v, step, pos_radius, normal_cos):
+    """What a caller without filter_texels() writes: one pass of the same filter as 25 shifted slices of the padded lattice, with torch ops on the same device
+    tensors (cov (h, w) bool, p / nm (h, w, 3) float64, v (h, w, c) float32).  Compared for its time only."""
+    import torch
+    import torch.nn.functional as F
+    h, w = cov.shape
+    pad = 2 * step
+    padded = lambda t: F.pad(t.permute(2, 0, 1), (pad, pad, pad, pad))  # noqa: E731
+    pp, nn, vv = padded(p), padded(nm), padded(v)
+    cc = F.pad(cov[None].to(torch.uint8), (pad, pad, pad, pad))[0].bool()
+    pc, nc = p.permute(2, 0, 1), nm.permute(2, 0, 1)
+    acc, wsum = torch.zeros_like(vv[:, pad:pad + h, pad:pad + w]), torch.zeros((h, w), dtype=torch.float32, device=v.device)
+    taps = (1.0, 4.0, 6.0, 4.0, 1.0)
+    for j in range(-2, 3):
+        for i in range(-2, 3):
+            ys, xs = pad + j * step, pad + i * step
+            if i == 0 and j == 0:
+                wt = cov.float() * 36.0
+            else:
+                d = pp[:, ys:ys + h, xs:xs + w] - pc
+                wp = 1.0 - (d * d).sum(0) / (pos_radius * pos_radius)
+                wn = (((nc * nn[:, ys:ys + h, xs:xs + w]).sum(0) - normal_cos) / (1.0 - normal_cos)).clamp(max=1.0)
+                take = cc[ys:ys + h, xs:xs + w] & cov & (wp > 0) & (wn > 0)
+                wt = torch.where(take, (taps[i + 2] * taps[j + 2]) * wp.float() * wn.float(), torch.zeros_like(wsum))
+            acc = acc + wt[None] * vv[:, ys:ys + h, xs:xs + w]
+            wsum = wsum + wt
+    return torch.where(cov[..., None], (acc / wsum[None]).permute(1, 2, 0), v)
+
+
+FILTER_EXPECTATION = ("every filter_texels pass cheaper than its torch restatement on the same device tensors; the three passes of denoise_texels cheaper than one more "
+                      "gathered direction (gather_points with 16 directions on the same texels / 16) on the same lattice — if they are not, adding rays beats filtering")
+
+
+def _filter_row(sc, size, reps, rounds=5, channels=3):
+    import torch
+    import nrays_amd as nr
+    w, h = size
+    n = w * h
+    dev = torch.device("cuda", torch.cuda.current_device())
+    tx = nr.surface_texels(sc, 0, w, h, want=("normals",), device=dev)
+    covered = (tx.flags & 1) != 0
+    values = torch.rand((n, channels), dtype=torch.float32, device=dev) * covered[:, None]
+    pos_radius, normal_cos = 16.0 * 8.0 / w, 0.5  # both meshes span 8 world units over the atlas: 16 texels of reach
+    dirs = nr.hemisphere_dirs(16)
+    fns = {"filter_step_%d" % s: (lambda s=s: nr.filter_texels(sc, tx.flags, w, h, tx.points, tx.normals, values, s, pos_radius, normal_cos)) for s in (1, 2, 4)}
+    fns["denoise_3_passes"] = lambda: nr.denoise_texels(sc, tx, values, 3, pos_radius, normal_cos, w, h)
+    ms = {name: [] for name in fns}
+    for _ in range(rounds):  # alternating rounds, each timed by events around `reps` launches after a warm-up
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=2))
+    grid = (covered.view(h, w), tx.points.view(h, w, 3), tx.normals.view(h, w, 3), values.view(h, w, channels))
+    torch_reps = 1 if n > 1 << 22 else 3
+    for s in (1, 2, 4):
+        ms["torch_step_%d" % s] = [_time(lambda: _torch_filter(*grid, s, pos_radius, normal_cos), torch_reps, warmup=1) for _ in range(2)]
+    gather_reps = 1 if n > 1 << 22 else 2
+    ms["gather_points_16_dirs"] = [_time(lambda: nr.gather_points(sc, tx.points, tx.normals, dirs, None, 1e-3, 1.0, 0, hit_flags=tx.flags), gather_reps, warmup=1) for _ in range(2)]
+    floor_ms = (52 + 8 * channels) * n / HBM_COPY_BYTES_PER_S * 1e3
+    row = {"lattice": [w, h], "points": n, "channels": channels, "covered_share": round(float(covered.float().mean().item()), 4), "pos_radius": pos_radius, "normal_cos": normal_cos,
+           "rounds": rounds, "reps": reps, "torch_reps": torch_reps, "gather_reps": gather_reps}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    row["one_more_gathered_direction"] = {"ms": round(row["gather_points_16_dirs"]["ms"] / 16.0, 4), "how": "gather_points_16_dirs / 16"}
+    row["traffic_floor"] = {"bytes": (52 + 8 * channels) * n, "ms": round(floor_ms, 4),
+                            "share_of_it_reached": {"step_%d" % s: round(floor_ms / row["filter_step_%d" % s]["ms"], 3) for s in (1, 2, 4)}}
+    row["expectation"] = {"step_%d_cheaper_than_its_torch_restatement" % s: "MET" if row["filter_step_%d" % s]["ms"] < row["torch_step_%d" % s]["ms"] else "MISSED" for s in (1, 2, 4)}
+    row["expectation"]["three_passes_cheaper_than_one_more_gathered_direction"] = "MET" if row["denoise_3_passes"]["ms"] < row["one_more_gathered_direction"]["ms"] else "MISSED"
+    return row
+
+
+def _filter_leg(reps, quick, path):
+    import nrays_amd as nr
+    from tools import scenes_util as su
+    from tools import standins
+    out = {"expectation_written_before_the_first_run": FILTER_EXPECTATION,
+           "inputs": "sine_grid: the --texels grid mesh, 100 % covered; atlas: 64 x 64 quad charts, each 0.75 of its atlas cell (tools/scenes_util.py: atlas_quads_mesh)"}
+    with open(path, "w") as f:  # the expectation is on file before anything is timed
+        json.dump({"workloads": {"j_filter_texels": out}}, f, indent=1)
+    n = 64 if quick else 500
+    p, uv, idx = standins._surface(lambda u, v: np.stack([8.0 * u - 4.0, 0.5 * np.sin(6.0 * u) * np.cos(5.0 * v), 8.0 * v - 4.0], -1), n, n)
+    meshes = {"sine_grid": (su.f32_exact(p), idx, su.f32_exact(uv)), "atlas": su.atlas_quads_mesh(16 if quick else 64)}
+    mat = nr.PhongMaterial((0.2, 0.2, 0.2), (0.9, 0.9, 0.9), (0.5, 0.5, 0.5), None, None, 40.0)
+    scene = lambda m: nr.Scene([nr.SceneNode(mat, 0.0, 0.0, 1.0, 1.0, nr.Isometry3(), nr.TriMesh(*m[:2], m[2]))], [nr.Light((1.0, 6.0, -2.0), 0.0, 1, (1.0, 1.0, 1.0))], (0.2, 0.3, 0.4))  # noqa: E731
+    small, large = ((128, 128), (512, 512)) if quick else ((1024, 1024), (4096, 4096))
+    for name, m in meshes.items():
+        sc = scene(m)
+        for tag, size, rp in (("small_lattice", small, reps), ("large_lattice", large, max(1, reps // 4))):
+            out["%s_%s" % (name, tag)] = _filter_row(sc, size, rp)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default: profiles/trace_rays_rate.json; with --occlusion profiles/occlusion_rate.json, with --gather profiles/gather_rate.json")
@@ -544,9 +641,10 @@ def main():
     ap.add_argument("--gather", action="store_true", help="time gather_points beside building the rays with torch, trace_rays on them and the torch fold (leg h_sponza_gather), nothing else")
     ap.add_argument("--texels", action="store_true", help="time surface_texels, its two passes, shade_points on its texels and the numpy mirror (leg g_surface_texels), nothing else")
     ap.add_argument("--dilate", action="store_true", help="time dilate_texels beside surface_texels, the torch passes a caller wrote before and the traffic floor (leg i_dilate_texels, into profiles/dilate_rate.json); alone: nothing else")
+    ap.add_argument("--filter", action="store_true", help="time filter_texels and denoise_texels beside a torch restatement, the traffic floor, and one more gathered direction (leg j_filter_texels, into profiles/filter_rate.json), nothing else")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "dilate_rate.json" if a.dilate and not a.texels else "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "filter_rate.json" if a.filter else "dilate_rate.json" if a.dilate and not a.texels else "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -559,6 +657,14 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.filter:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        leg = dict(res, workloads={"j_filter_texels": _filter_leg(a.reps, a.quick, a.out)})
+        with open(a.out, "w") as f:
+            json.dump(leg, f, indent=1)
+        print(json.dumps(leg))
+        return
 
     if a.dilate:
         leg = dict(res, workloads={"i_dilate_texels": _dilate_leg(a.reps, a.quick)})
