@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -462,6 +462,46 @@ int nrays_gather_points_device_ex(NraysScene* scene, uint32_t n, const double* p
                                   const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream);
 int nrays_gather_points_ex(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
                            const uint64_t* keys, const NraysGatherParams* params, float* out_rgb, uint32_t flags);
+
+/* The gathered light of nrays_gather_points*_ex kept by DIRECTION: per point the projection of its rays' colours onto the real spherical harmonics of bands
+ * 0 .. bands - 1 — 9 coefficients per channel at bands = 3 (Ramamoorthi and Hanrahan 2001) — instead of their mean.  An irradiance probe (a free point in space:
+ * normal (0, 0, 1), bias 0, no rotations and a table of sphere directions reproduce the table's directions from the point itself) and a directional light map
+ * (per texel) are this call.  The arguments, the rays, the ray keys, the trace, the double-branching rule, the chunks, the skipped points, the stream ordering
+ * and the untouched render state are those of nrays_gather_points_device_ex / nrays_gather_points_ex; `flags` is 0 or NRAYS_RAYS_UNORDERED with the reorder rule
+ * and NRAYS_RAY_REORDER as there.  Only the fold differs:
+ *   bands      1, 2 or 3; C = bands * bands coefficients.
+ *   out_sh     n x C x 3 floats, required: coefficient c, channel ch of point i at (i * C + c) * 3 + ch.
+ *   basis      d = the direction of ray j of point i exactly as the gather builds it (NraysOcclusionParams above; NOT normalised).  In f64, left to right as
+ *              written, nothing fused, with K0 = 0.28209479177387814, K1 = 0.4886025119029199, K2 = 1.0925484305920792, K3 = 0.31539156525252005,
+ *              K4 = 0.5462742152960396 (the doubles nearest 1/(2 sqrt(pi)), sqrt(3)/(2 sqrt(pi)), sqrt(15)/(2 sqrt(pi)), sqrt(5)/(4 sqrt(pi)), sqrt(15)/(4 sqrt(pi))):
+ *                Y0 = K0
+ *                Y1 = K1 * d.y                 Y2 = K1 * d.z                              Y3 = K1 * d.x
+ *                Y4 = (K2 * d.x) * d.y         Y5 = (K2 * d.y) * d.z                      Y6 = K3 * ((3.0 * d.z) * d.z - 1.0)
+ *                Y7 = (K2 * d.x) * d.z         Y8 = K4 * (d.x * d.x - d.y * d.y)
+ *              — the real basis without the Condon-Shortley sign (Python: sh_basis).
+ *   fold       in f32: y = (float)Yc; acc[c][ch] = +0; for j = 0 .. num_dirs - 1 in order: acc[c][ch] = acc[c][ch] + y * colour_ij[ch] (the product rounded, then
+ *              the sum); out = acc / (float)num_dirs (one correctly rounded division).  colour_ij is the finished colour nrays_trace_rays_device returns for that
+ *              ray and key, the queued second children of double-branching scenes included (Python: sh_fold_ref).  The first 1 and 4 coefficient rows of a
+ *              bands = 3 result are the bands = 1 and 2 results bit for bit.
+ *   measure    none is applied: the caller multiplies by 4 pi for uniform sphere directions and by 2 pi for a uniform hemisphere.
+ *   skipped    a point whose flag bit 0 is clear writes 3 C exact zeros; neither its point nor its normal is read, in the trace or in the fold.
+ * The result never depends on lanes, tiles or the reorder.  bands outside 1 .. 3, NULL out_sh, an unknown flag bit and every bad argument of nrays_gather_points
+ * -> NRAYS_ERR_BAD_ARG before any device work; n == 0 -> NRAYS_OK, out_sh untouched.
+ * Workspace: EVERY scene kind keeps the ray colours of one chunk (12 bytes a ray, at most 2^22 rays = 48 MiB) in the handle's workspace between the trace and
+ * the fold, which rebuilds each direction from (i, j); a reordered chunk adds its 16 bytes of sort state a ray and a double-branching scene its 24 bytes beside
+ * the queue, as for nrays_gather_points*_ex.  The caller still passes and receives per-point arrays only: no ray, direction or per-ray colour array crosses
+ * the interface.  The host form stages 60 + 12 C bytes a point. */
+int nrays_gather_sh_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                  const uint64_t* keys, const NraysGatherParams* params, uint32_t bands, float* out_sh, uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables included) HOST memory.  Blocking. */
+int nrays_gather_sh_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                           const uint64_t* keys, const NraysGatherParams* params, uint32_t bands, float* out_sh, uint32_t flags);
+/* Test probe: the fold kernel of nrays_gather_sh_points_device alone, on caller-supplied ray colours (n x num_dirs x 3 floats, ray j of point i at
+ * (i * num_dirs + j) * 3; n * num_dirs <= 2^22: one chunk) with the points, normals, flags, keys, tables and bands of that call; nothing is traced and energy and
+ * max_depth are not used.  keys NULL: key i.  out_kernel_ms, or NULL: the kernel's time between two HIP events of the probe's own.  All HOST memory (the tables
+ * of params included).  Blocking.  Arguments are checked as by nrays_gather_sh_points; NULL ray_colours -> NRAYS_ERR_BAD_ARG. */
+int nrays_debug_gather_sh_fold(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                               const NraysGatherParams* params, uint32_t bands, const float* ray_colours, float* out_sh, float* out_kernel_ms);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and

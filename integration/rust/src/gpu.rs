@@ -658,6 +658,48 @@ impl GpuScene {
         if nrays_gather_points_device_ex(self.raw, n, points, normals, hit_flags, keys, params, out_rgb, NRAYS_RAYS_UNORDERED, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
+
+    /// The gathered light of `gather_points` kept by direction (nrays_gather_sh_points, blocking): per point the projection of its rays' colours onto the real
+    /// spherical harmonics of bands 0 .. `bands` - 1 (1 ..= 3; C = bands * bands coefficients), `out[i][c]` = coefficient c of point i as an RGB vector.  No measure
+    /// is applied: multiply by 4 pi for uniform sphere directions.  An irradiance probe is a point with normal (0, 0, 1), bias 0 and no rotations under a table
+    /// of sphere directions.  The value is defined in include/nrays_abi.h (nrays_gather_sh_points_device).
+    pub fn gather_sh_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32, max_depth: u32,
+                            bands: u32, keys: Option<&[u64]>) -> Result<Vec<Vec<Vector3<f32>>>, String> {
+        self.gather_sh_points_flags(points, sample_dirs, rotations, bias, energy, max_depth, bands, keys, 0)
+    }
+
+    /// `gather_sh_points` for points that come in no useful order (NRAYS_RAYS_UNORDERED, as `gather_points_unordered`): the same values, bit for bit.
+    pub fn gather_sh_points_unordered(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32,
+                                      max_depth: u32, bands: u32, keys: Option<&[u64]>) -> Result<Vec<Vec<Vector3<f32>>>, String> {
+        self.gather_sh_points_flags(points, sample_dirs, rotations, bias, energy, max_depth, bands, keys, NRAYS_RAYS_UNORDERED)
+    }
+
+    fn gather_sh_points_flags(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, energy: f32, max_depth: u32,
+                              bands: u32, keys: Option<&[u64]>, flags: u32) -> Result<Vec<Vec<Vector3<f32>>>, String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        if bands < 1 || bands > 3 { return Err(format!("bands must be in 1 ..= 3, got {}", bands)); }
+        let (n, c) = (points.len(), (bands * bands) as usize);
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysGatherParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                         rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, energy, max_depth };
+        let mut sh = vec![0.0f32; 3 * c * n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_gather_sh_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, bands, sh.as_mut_ptr(), flags) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| (0..c).map(|q| { let o = 3 * (i * c + q); Vector3::new(sh[o], sh[o + 1], sh[o + 2]) }).collect()).collect())
+    }
+
+    /// `gather_sh_points` for n points in DEVICE memory (nrays_gather_sh_points_device), enqueued on `hip_stream`: the arrays of `gather_points_device`, out_sh
+    /// n x bands^2 x 3 f32.  `unordered` passes NRAYS_RAYS_UNORDERED.  `params` is host memory; its two tables are device memory.
+    pub unsafe fn gather_sh_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: &NraysGatherParams,
+                                          bands: u32, out_sh: *mut f32, unordered: bool, hip_stream: *mut c_void) -> Result<(), String> {
+        let flags = if unordered { NRAYS_RAYS_UNORDERED } else { 0 };
+        if nrays_gather_sh_points_device(self.raw, n, points, normals, hit_flags, keys, params, bands, out_sh, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
 }
 
 impl Drop for GpuScene {

@@ -167,6 +167,12 @@ HIP_SYMBOLS = {
                                          C.POINTER(NraysGatherParams), C.POINTER(C.c_float), C.c_uint32]),
     "nrays_debug_gather_order": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                            C.POINTER(NraysGatherParams), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32)]),
+    "nrays_gather_sh_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysGatherParams), C.c_uint32, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]),
+    "nrays_gather_sh_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                         C.POINTER(NraysGatherParams), C.c_uint32, C.POINTER(C.c_float), C.c_uint32]),
+    "nrays_debug_gather_sh_fold": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                             C.POINTER(NraysGatherParams), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -217,7 +223,8 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_occlusion_points", "nrays_debug_occlusion_rays", "nrays_surface_texels_device", "nrays_surface_texels",
                    "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points",
                    "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels",
-                   "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels")
+                   "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels", "nrays_gather_sh_points_device", "nrays_gather_sh_points",
+                   "nrays_debug_gather_sh_fold")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

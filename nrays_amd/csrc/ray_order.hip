@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch, nrays_debug_box_cull; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_gather_sh_points*, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch, nrays_debug_box_cull; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -27,6 +27,7 @@
 
 #include "../../include/nrays_abi.h"
 #include "bounce.h"
+#include "gather_sh_kernel.h"
 #include "ray_batch_kernel.h"
 #include "ray_key.h"
 #include "scene_handle.h"
@@ -770,6 +771,11 @@ static int check_gather_args(const NraysScene* sc, const OcclusionIn& in, const 
 static bool gather_reorders(const NraysScene* sc, uint32_t n, const NraysGatherParams* p, uint32_t flags) {
     return (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, (uint32_t)std::min<uint64_t>((uint64_t)n * p->num_dirs, 0xffffffffull));
 }
+static uint32_t gather_out_floats(uint32_t bands) { return bands ? 3u * bands * bands : 3u; } // floats a point of the output: the mean colour, or bands^2 coefficients of three channels
+static int check_sh_bands(uint32_t bands) {
+    if (bands < 1u || bands > 3u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_sh_points: bands must be in 1 .. 3");
+    return NRAYS_OK;
+}
 static uint32_t gather_chunk(const NraysGatherParams* p) { return std::max<uint32_t>(1u, kTraceChunk / p->num_dirs); } // points per chunk: at most kTraceChunk rays
 // Double-branching scenes: the fold that k_gather_points left to the end of the chunk's k_bounce rounds — point i's num_dirs finished ray colours, summed in the
 // order of j in f32 and divided once.  One lane per point; the colours were just written and sit in L2.
@@ -814,8 +820,10 @@ static int gather_order_chunk(const NraysScene* sc, TraceWorkspace* w, uint32_t 
 // rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
 // `reorder` (a hinted call that pays, nrays_gather_points*_ex): the chunk's pairs are binned (gather_order_chunk) and traced in bin order by k_gather_pairs_ordered, every
 // scene through the cleared per-ray colours and k_gather_fold: 12 bytes of colour and 16 of sort state a ray of the chunk, whatever the scene.
+// `bands` > 0 (nrays_gather_sh_points*): the same trace kernels, always through the per-ray colours — queued or not, reordered or not —, and k_gather_fold_sh
+// (gather_sh_kernel.h) folds them into 3 * bands^2 floats a point of `out` instead of k_gather_fold's 3.
 static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const OcclusionIn& in, unsigned long long key_base, const NraysGatherParams* p,
-                               const double* dirs, const double* rotations, float* out, bool reorder, hipStream_t stream) {
+                               const double* dirs, const double* rotations, float* out, bool reorder, uint32_t bands, hipStream_t stream) {
     const bool queued = sc->facts.host.any_double_branch;
     const uint32_t pairs = nc * p->num_dirs; // (<= kTraceChunk)
     const size_t ray_floats = 3 * (size_t)pairs;
@@ -825,11 +833,12 @@ static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, c
         if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, ray_floats, stream);
         if (rc != NRAYS_OK) return rc;
     }
-    if (queued || reorder) {
+    const bool per_ray = queued || reorder || bands != 0u;
+    if (per_ray) {
         const int rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
         if (rc != NRAYS_OK) return rc;
     }
-    float* ray_out = queued || reorder ? (float*)w->d_gather_rays : nullptr;
+    float* ray_out = per_ray ? (float*)w->d_gather_rays : nullptr;
     HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
     unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
     QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
@@ -861,13 +870,22 @@ static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, c
         const int rc = run_bounce_rounds(rounds, stream, &overflowed);
         if (rc != NRAYS_OK) return rc;
     }
-    hipLaunchKernelGGL(k_gather_fold, dim3((nc + kOrderBlock - 1u) / kOrderBlock), dim3(kOrderBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
+    if (bands) {
+        const GatherPoints pts{in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base};
+        const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
+        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, (const float*)ray_out, nc, pts, OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, 0.0}, dirs,
+                           rotations, bands * bands, out);
+    } else {
+        hipLaunchKernelGGL(k_gather_fold, dim3((nc + kOrderBlock - 1u) / kOrderBlock), dim3(kOrderBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
+    }
     HIP_TRY(hipGetLastError());
     if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some gathered colours are incomplete");
     return NRAYS_OK;
 }
 
-static int gather_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted, hipStream_t stream) {
+// `bands` = 0: nrays_gather_points* (3 floats a point); 1 .. 3: nrays_gather_sh_points* (3 * bands^2 floats a point), checked by the caller.
+static int gather_points_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted, uint32_t bands,
+                                     hipStream_t stream) {
     if (check_gather_args(sc, in, p, out_rgb, flags, hinted) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->facts.device));
@@ -879,16 +897,17 @@ static int gather_points_device_impl(NraysScene* sc, uint32_t n, const Occlusion
     const bool reorder = gather_reorders(sc, n, p, flags);
     for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
         const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
-        rc = gather_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, p->dirs, p->rotations, out_rgb + 3 * (size_t)c0, reorder, stream);
+        rc = gather_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, p->dirs, p->rotations, out_rgb + gather_out_floats(bands) * (size_t)c0, reorder, bands,
+                                 stream);
     }
     batch_end(sc, w, stream);
     return rc;
 }
 
-// The blocking form, through the workspace's staging buffer as occlusion_points_host_impl: the two tables first, then per staged point kGatherStageBytes —
-// point, normal (3 f64), key (u64), colour (3 f32), hit flags (32 bits), the 8-byte fields first.
-constexpr size_t kGatherStageBytes = 72;
-static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted) {
+// The blocking form, through the workspace's staging buffer as occlusion_points_host_impl: the two tables first, then per staged point gather_stage_bytes() —
+// point, normal (3 f64), key (u64), the output (3 f32, or 3 * bands^2 for the spherical-harmonic form), hit flags (32 bits), the 8-byte fields first.
+static size_t gather_stage_bytes(uint32_t bands) { return 60u + 4u * (size_t)gather_out_floats(bands); }
+static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherParams* p, float* out_rgb, uint32_t flags, bool hinted, uint32_t bands) {
     if (check_gather_args(sc, in, p, out_rgb, flags, hinted) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     HIP_TRY(hipSetDevice(sc->facts.device));
@@ -897,10 +916,11 @@ static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn
     if (rc != NRAYS_OK) return rc;
     const uint32_t chunk = gather_chunk(p);
     const size_t cap = std::min<uint32_t>(n, chunk), table = 3 * (size_t)p->num_dirs + 2 * (size_t)p->num_rotations;
-    rc = grow_device(&w->d_stage, &w->stage_rays, (table * sizeof(double) + cap * kGatherStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    rc = grow_device(&w->d_stage, &w->stage_rays, (table * sizeof(double) + cap * gather_stage_bytes(bands) + kStageUnit - 1) / kStageUnit, kStageUnit);
     if (rc != NRAYS_OK) return rc;
     double* s_dirs = (double*)w->d_stage; double* s_rot = s_dirs + 3 * (size_t)p->num_dirs; double* s_p = s_dirs + table; double* s_n = s_p + 3 * cap;
-    uint64_t* s_k = (uint64_t*)(s_n + 3 * cap); float* s_c = (float*)(s_k + cap); uint32_t* s_hf = (uint32_t*)(s_c + 3 * cap);
+    const size_t out_floats = gather_out_floats(bands);
+    uint64_t* s_k = (uint64_t*)(s_n + 3 * cap); float* s_c = (float*)(s_k + cap); uint32_t* s_hf = (uint32_t*)(s_c + out_floats * cap);
     const OcclusionIn s{s_p, s_n, in.hit_flags ? s_hf : nullptr, in.keys ? s_k : nullptr};
     rc = ensure_own_stream(sc);
     if (rc != NRAYS_OK) return rc;
@@ -920,9 +940,9 @@ static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn
         if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
         if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
         if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("gather batch upload: ") + hipGetErrorString(e)); break; }
-        rc = gather_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, reorder, stream);
+        rc = gather_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, reorder, bands, stream);
         if (rc != NRAYS_OK) break;
-        e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_c, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+        e = hipMemcpyAsync(out_rgb + out_floats * (size_t)c0, s_c, (size_t)nc * out_floats * sizeof(float), hipMemcpyDeviceToHost, stream);
         const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
         if (e == hipSuccess) e = es;
         if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather batch read-back: ") + hipGetErrorString(e));
@@ -1487,19 +1507,19 @@ int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points,
 
 int nrays_gather_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                                const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream) {
-    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false, (hipStream_t)hip_stream);
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false, 0u, (hipStream_t)hip_stream);
 }
 int nrays_gather_points_device_ex(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                                   const NraysGatherParams* params, float* out_rgb, uint32_t flags, void* hip_stream) {
-    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true, (hipStream_t)hip_stream);
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true, 0u, (hipStream_t)hip_stream);
 }
 int nrays_gather_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                         const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
-    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false);
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, false, 0u);
 }
 int nrays_gather_points_ex(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                            const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
-    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true);
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true, 0u);
 }
 
 int nrays_surface_texels_device(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,
@@ -1562,6 +1582,65 @@ int nrays_debug_ray_order(NraysScene* sc, uint32_t n, const double* origins, con
     }
     (void)hipFree(d_od);
     if (rc == NRAYS_OK && e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_ray_order: ") + hipGetErrorString(e));
+    return rc;
+}
+
+int nrays_gather_sh_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                  const NraysGatherParams* params, uint32_t bands, float* out_sh, uint32_t flags, void* hip_stream) {
+    if (check_sh_bands(bands) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    return gather_points_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_sh, flags, true, bands, (hipStream_t)hip_stream);
+}
+int nrays_gather_sh_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                           const NraysGatherParams* params, uint32_t bands, float* out_sh, uint32_t flags) {
+    if (check_sh_bands(bands) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_sh, flags, true, bands);
+}
+
+int nrays_debug_gather_sh_fold(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                               const NraysGatherParams* params, uint32_t bands, const float* ray_colours, float* out_sh, float* out_kernel_ms) {
+    if (!ray_colours) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_sh_bands(bands) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (check_gather_args(sc, OcclusionIn{points, normals, hit_flags, keys}, params, out_sh, 0u, true) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    const uint64_t pairs64 = (uint64_t)n * params->num_dirs;
+    if (pairs64 > kTraceChunk) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_debug_gather_sh_fold: at most one chunk (n * num_dirs <= 2^22)");
+    if (out_kernel_ms) *out_kernel_ms = 0.0f;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    int rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    // the tables, then per point: point, normal (3 f64), key (u64), hit flags (32 bits), the output; then the colours — the 8-byte fields first
+    const size_t table = 3 * (size_t)params->num_dirs + 2 * (size_t)params->num_rotations, out_floats = (size_t)n * gather_out_floats(bands), ray_floats = 3 * (size_t)pairs64;
+    double* d_all = nullptr;
+    HIP_TRY(hipMalloc((void**)&d_all, table * sizeof(double) + (size_t)n * 60 + (out_floats + ray_floats) * sizeof(float)));
+    double* d_dirs = d_all; double* d_rot = d_dirs + 3 * (size_t)params->num_dirs; double* d_p = d_all + table; double* d_n = d_p + 3 * (size_t)n;
+    uint64_t* d_k = (uint64_t*)(d_n + 3 * (size_t)n); uint32_t* d_hf = (uint32_t*)(d_k + n); float* d_out = (float*)(d_hf + n); float* d_rays = d_out + out_floats;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+    hipError_t e = up(d_dirs, params->dirs, 24 * (size_t)params->num_dirs);
+    if (e == hipSuccess) e = up(d_rot, params->rotations, 16 * (size_t)params->num_rotations);
+    if (e == hipSuccess) e = up(d_p, points, 24 * (size_t)n);
+    if (e == hipSuccess) e = up(d_n, normals, 24 * (size_t)n);
+    if (e == hipSuccess) e = up(d_k, keys, 8 * (size_t)n);
+    if (e == hipSuccess) e = up(d_hf, hit_flags, 4 * (size_t)n);
+    if (e == hipSuccess) e = up(d_rays, ray_colours, ray_floats * sizeof(float));
+    if (e == hipSuccess && out_kernel_ms) { e = hipEventCreate(&ev[0]); if (e == hipSuccess) e = hipEventCreate(&ev[1]); }
+    if (e == hipSuccess && out_kernel_ms) e = hipEventRecord(ev[0], stream);
+    if (e == hipSuccess) {
+        const GatherPoints pts{d_p, d_n, hit_flags ? d_hf : nullptr, keys ? (const unsigned long long*)d_k : nullptr, 0ull};
+        const uint32_t grid = std::min<uint32_t>((n + kShGroups - 1u) / kShGroups, kShMaxGrid);
+        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, (const float*)d_rays, n, pts, OcclusionSpec{params->num_dirs, params->num_rotations, params->bias, 0.0},
+                           (const double*)d_dirs, params->num_rotations ? (const double*)d_rot : nullptr, bands * bands, d_out);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess && out_kernel_ms) e = hipEventRecord(ev[1], stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_sh, d_out, out_floats * sizeof(float), hipMemcpyDeviceToHost, stream);
+    const hipError_t es = hipStreamSynchronize(stream); // (always: the uploads read the caller's memory)
+    if (e == hipSuccess) e = es;
+    if (e == hipSuccess && out_kernel_ms) e = hipEventElapsedTime(out_kernel_ms, ev[0], ev[1]);
+    for (hipEvent_t v : ev) if (v) (void)hipEventDestroy(v);
+    (void)hipFree(d_all);
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_gather_sh_fold: ") + hipGetErrorString(e));
     return rc;
 }
 

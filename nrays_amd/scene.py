@@ -404,6 +404,14 @@ class Scene:
         """The incoming light at caller-supplied surface points of this scene: gather_points(self, ...)."""
         return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
+    def gather_sh_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, bands=3, hit_flags=None, keys=None, unordered=False):
+        """The incoming light at caller-supplied points of this scene as spherical harmonics: gather_sh_points(self, ...)."""
+        return gather_sh_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, bands, hit_flags, keys, unordered)
+
+    def gather_probes(self, positions, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True):
+        """Irradiance probes at free points of this scene: gather_probes(self, ...)."""
+        return gather_probes(self, positions, sample_dirs, bands, energy, max_depth, keys, unordered)
+
     @_dilate_keyword
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
                       device=None, unordered=False):
@@ -1083,6 +1091,181 @@ def gather_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias=1e
     numpy or torch as the inputs.  `unordered`: as for gather_points."""
     points, normals = _hit_points("gather_hits", origins, dirs, hits)
     return gather_points(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags=hits.flags, keys=keys, unordered=unordered)
+
+
+# ---- gathered light kept by direction: spherical harmonics per point, irradiance probes (include/nrays_abi.h: nrays_gather_sh_points_device) ----------------
+
+# 1/(2 sqrt(pi)), sqrt(3)/(2 sqrt(pi)), sqrt(15)/(2 sqrt(pi)), sqrt(5)/(4 sqrt(pi)), sqrt(15)/(4 sqrt(pi)): the nearest doubles, as the header spells them
+SH_K = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+SH_MAX_BANDS = 3
+SH_COSINE_LOBE = (math.pi, 2.0 * math.pi / 3.0, math.pi / 4.0)  # A_l of Ramamoorthi and Hanrahan 2001, bands 0 .. 2
+
+
+def _sh_bands(bands):
+    if isinstance(bands, bool) or int(bands) != bands or not 1 <= int(bands) <= SH_MAX_BANDS:
+        raise ValueError("bands must be 1, 2 or 3, got %r" % (bands,))
+    return int(bands)
+
+
+def _sh_terms(x, y, z, C):
+    """The first C basis values at (x, y, z), each an array like x: the nine expressions of the header, left to right as written (numpy or torch, any dtype)."""
+    K0, K1, K2, K3, K4 = SH_K
+    Y = [K0 + 0.0 * x]
+    if C >= 4:
+        Y += [K1 * y, K1 * z, K1 * x]
+    if C >= 9:
+        Y += [(K2 * x) * y, (K2 * y) * z, K3 * ((3.0 * z) * z - 1.0), (K2 * x) * z, K4 * (x * x - y * y)]
+    return Y
+
+
+def sphere_dirs(k):
+    """k directions spread over the whole sphere, (k, 3) float64 — a probe's sample table for gather_probes(): Fibonacci points, with t = i + 0.5:
+    z = 1 - 2 t / k, r = sqrt(1 - z^2), phi = t * pi (3 - sqrt 5), direction (r cos phi, r sin phi, z).  A convenience: any values are valid."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    t = np.arange(k, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * t / k
+    r = np.sqrt(1.0 - z * z)
+    phi = t * (math.pi * (3.0 - math.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+
+
+def sh_basis(dirs, bands=3):
+    """The numpy mirror of the basis of nrays_gather_sh_points*: (..., 3) float64 directions, used as given -> (..., bands^2) float32 — the real spherical
+    harmonics without the Condon-Shortley sign, evaluated in float64 left to right as the header writes them and rounded once."""
+    bands = _sh_bands(bands)
+    if _is_tensor(dirs):
+        raise ValueError("sh_basis takes a numpy array")
+    d = np.asarray(dirs, dtype=np.float64)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("dirs must have shape (..., 3), got %s" % (d.shape,))
+    with np.errstate(all="ignore"):
+        return np.stack(_sh_terms(d[..., 0], d[..., 1], d[..., 2], bands * bands), axis=-1).astype(np.float32)
+
+
+def sh_fold_ref(ray_dirs, ray_colours, bands=3):
+    """The numpy mirror of the fold of nrays_gather_sh_points*: ray_dirs (n, k, 3) float64 (occlusion_rays()' directions), ray_colours (n, k, 3) float32 (what
+    trace_rays returns for them) -> (n, bands^2, 3) float32: acc = acc + float32(Y_c) * colour in float32 in the order of j, then acc / float32(k)."""
+    d, col = np.asarray(ray_dirs, dtype=np.float64), np.asarray(ray_colours)
+    if col.dtype != np.float32:
+        raise ValueError("ray_colours must be float32, got %s" % col.dtype)
+    if d.ndim != 3 or d.shape[2] != 3 or d.shape[1] < 1 or col.shape != d.shape:
+        raise ValueError("ray_dirs and ray_colours must both have shape (n, k >= 1, 3), got %s and %s" % (d.shape, col.shape))
+    y = sh_basis(d, bands)
+    acc = np.zeros((d.shape[0], y.shape[2], 3), np.float32)
+    with np.errstate(all="ignore"):
+        for j in range(d.shape[1]):
+            acc = acc + y[:, j, :, None] * col[:, j, None, :]
+        return acc / np.float32(d.shape[1])
+
+
+def sh_irradiance(sh, normals, measure=4.0 * math.pi):
+    """The irradiance E(n) = measure * sum_lm A_l sh_lm Y_lm(n) with A = pi, 2 pi / 3, pi / 4 (Ramamoorthi and Hanrahan 2001) from the coefficients gather_sh_points /
+    gather_probes return: sh (..., C, 3) with C = 1, 4 or 9, normals (..., 3) unit vectors whose leading shape broadcasts against sh's -> (..., 3).  `measure`: the
+    solid angle the sample table covers — 4 pi for sphere_dirs (the default), 2 pi for a uniform hemisphere.  Plain numpy or torch arithmetic, no kernel."""
+    C = sh.shape[-2] if len(sh.shape) >= 2 else 0
+    if C not in (1, 4, 9) or sh.shape[-1] != 3 or normals.shape[-1] != 3:
+        raise ValueError("sh must have shape (..., 1 | 4 | 9, 3) and normals (..., 3), got %s and %s" % (tuple(sh.shape), tuple(normals.shape)))
+    if _is_tensor(sh) != _is_tensor(normals):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    Y = _sh_terms(normals[..., 0], normals[..., 1], normals[..., 2], C)
+    band = (0, 1, 1, 1, 2, 2, 2, 2, 2)
+    e = None
+    for c in range(C):
+        term = (SH_COSINE_LOBE[band[c]] * Y[c])[..., None] * sh[..., c, :]
+        e = term if e is None else e + term
+    return measure * e
+
+
+def _gather_sh_call(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, bands, hit_flags, keys, unordered):
+    if not isinstance(unordered, (bool, np.bool_)):
+        raise ValueError("unordered must be True or False, got %r" % (unordered,))
+    bands = _sh_bands(bands)
+    n = _n_of(points, normals, ("points", "normals"))
+    for nm_, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(nm_, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    energy, max_depth = _gather_settings(energy, max_depth)
+    flags = abi.RAYS_UNORDERED if unordered else 0
+    C_ = bands * bands
+    if _is_tensor(points):
+        import torch
+        if points.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, points is on %s" % points.device)
+        f64 = (torch.float64,)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        flags_dt = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        L, rot = (t if t is None or _is_tensor(t) else torch.from_numpy(t).to(points.device) for t in (L, rot))
+        p, nm, hf, k, L, rot = _torch_args((("points", points, f64), ("normals", normals, f64), ("hit_flags", hit_flags, flags_dt), ("keys", keys, keys_dt),
+                                            ("sample_dirs", L, f64), ("rotations", rot, f64)), points.device)
+        sh = torch.empty((n, C_, 3), dtype=torch.float32, device=points.device)
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        params = abi.NraysGatherParams(L.shape[0], 0 if rot is None else rot.shape[0], ptr(L), ptr(rot), bias, energy, max_depth)
+        with torch.cuda.device(points.device):
+            abi.check(abi.load_hip_lib().nrays_gather_sh_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), bands, ptr(sh), flags,
+                                                                       torch.cuda.current_stream().cuda_stream))
+        return sh
+    if any(_is_tensor(a) for a in (normals, hit_flags, keys, L, rot)):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    sh = np.empty((n, C_, 3), dtype=np.float32)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    params = abi.NraysGatherParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, energy, max_depth)
+    abi.check(abi.load_hip_lib().nrays_gather_sh_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64),
+                                                        C.byref(params), bands, ptr(sh, C.c_float), flags))
+    return sh
+
+
+def gather_sh_points(scene, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, bands=3, hit_flags=None, keys=None, unordered=False):
+    """gather_points() that keeps WHERE the light came from, through nrays_gather_sh_points_device / nrays_gather_sh_points: the same rays, keys and traces, folded
+    on the device into the projection onto the real spherical harmonics of bands 0 .. bands - 1 of each ray's direction: (n, bands^2, 3) float32 — a directional
+    light map's texels, or irradiance probes (gather_probes()).  It equals sh_fold_ref(occlusion_rays()' directions, trace_rays' colours under gather_ray_keys())
+    bit for bit; no measure is applied (sh_irradiance() takes it).  Every scene kind keeps a chunk's ray colours (12 bytes a ray) in the handle's workspace;
+    no ray, direction or per-ray colour is ever in the caller's memory.  Arguments and numpy / torch forms: as for gather_points; `unordered=True` passes
+    NRAYS_RAYS_UNORDERED (bit-identical values).  Also `scene.gather_sh_points(...)` on Scene and FileScene."""
+    return _gather_sh_call(scene, points, normals, sample_dirs, rotations, bias, energy, max_depth, bands, hit_flags, keys, unordered)
+
+
+def gather_probes(scene, positions, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True):
+    """Irradiance probes at free points in space: gather_sh_points() with normals (0, 0, 1), bias 0 and no rotations — that frame reproduces `sample_dirs`
+    (sphere_dirs()) bit for bit as world directions and the origin is the position itself.  (n, bands^2, 3) float32; sh_irradiance(probes, normals) lights a
+    surface from them.  A probe's rays share an origin and nothing else, hence `unordered=True` by default.  numpy or torch as `positions`."""
+    if len(positions.shape) != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must have shape (n, 3), got %s" % (tuple(positions.shape),))
+    if _is_tensor(positions):
+        import torch
+        normals = torch.zeros_like(positions)
+    else:
+        normals = np.zeros((len(positions), 3), np.float64)
+    normals[:, 2] = 1.0
+    return _gather_sh_call(scene, positions, normals, sample_dirs, None, 0.0, energy, max_depth, bands, None, keys, unordered)
+
+
+def gather_sh_fold(scene, points, normals, sample_dirs, ray_colours, rotations=None, bias=1e-3, bands=3, hit_flags=None, keys=None, want_ms=False):
+    """Test probe (nrays_debug_gather_sh_fold): the fold kernel of gather_sh_points alone on caller-supplied per-ray colours (n, k, 3) float32, one chunk
+    (n * k <= 2^22).  numpy arrays, blocking: (n, bands^2, 3) float32; `want_ms`: also the kernel's time between two HIP events, in milliseconds."""
+    bands = _sh_bands(bands)
+    n = _n_of(points, normals, ("points", "normals"))
+    for nm_, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(nm_, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    if any(_is_tensor(a) for a in (points, normals, hit_flags, keys, L, rot, ray_colours)):
+        raise ValueError("gather_sh_fold takes numpy arrays")
+    col = np.ascontiguousarray(ray_colours, dtype=np.float32)
+    if col.shape != (n, len(L), 3):
+        raise ValueError("ray_colours must have shape (%d, %d, 3), got %s" % (n, len(L), col.shape))
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    sh, ms = np.empty((n, bands * bands, 3), dtype=np.float32), C.c_float(0.0)
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    params = abi.NraysGatherParams(len(L), 0 if rot is None else len(rot), L.ctypes.data, None if rot is None else rot.ctypes.data, bias, 1.0, 0)
+    abi.check(abi.load_hip_lib().nrays_debug_gather_sh_fold(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64),
+                                                            C.byref(params), bands, ptr(col, C.c_float), ptr(sh, C.c_float), C.byref(ms) if want_ms else None))
+    return (sh, float(ms.value)) if want_ms else sh
 
 
 # ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------

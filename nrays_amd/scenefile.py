@@ -120,6 +120,16 @@ class FileScene:
         from .scene import gather_points
         return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
 
+    def gather_sh_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, bands=3, hit_flags=None, keys=None, unordered=False):
+        """The incoming light at caller-supplied points of this scene as spherical harmonics: scene.gather_sh_points(self, ...)."""
+        from .scene import gather_sh_points
+        return gather_sh_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, bands, hit_flags, keys, unordered)
+
+    def gather_probes(self, positions, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True):
+        """Irradiance probes at free points of this scene: scene.gather_probes(self, ...)."""
+        from .scene import gather_probes
+        return gather_probes(self, positions, sample_dirs, bands, energy, max_depth, keys, unordered)
+
     @_dilate_keyword
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
                       device=None, unordered=False):

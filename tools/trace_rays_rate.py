@@ -52,6 +52,11 @@ only), beside the traffic floor ((52 + 8 * channels) bytes per texel over the 6.
 the same texels divided by 16 — what one more direction costs.  The expectations, written into the JSON before the first run, are judged per row: every pass
 cheaper than its torch restatement, and three passes cheaper than one more gathered direction.
 
+--gather-sh (that leg and nothing else, into profiles/gather_sh_rate.json) times the leg k_gather_sh: gather_sh_points() (nrays_gather_sh_points_device) at bands
+1 / 2 / 3, hinted and unhinted, beside gather_points() on the same input — the gather leg's two inputs and 4 096 probes on a grid in the hall under
+sphere_dirs(1024) —, the fold kernel alone (nrays_debug_gather_sh_fold, HIP events of its own) on the input's first chunk, the torch restatement of the fold
+on the same per-ray colours, and the fold's traffic floor (12 bytes a ray plus the outputs over the 6.29 TB/s a float4 copy reaches).  The expectations are
+written to the file before the first run and judged in it.
 --gather times, and nothing else, the leg h_sponza_gather: the incoming light (gather_points(): Scene::trace on hemisphere rays built in registers, one mean
 colour per point) at the same two inputs as --occlusion — 16 directions at every first hit, 64 at a 16 384-point subset — beside what a caller did before it: the
 same rays built with torch on the device, trace_rays() on them with the keys of gather_ray_keys() unhinted and with unordered=True, and the torch fold of the
@@ -60,7 +65,7 @@ per-ray colours, each timed apart — beside itself under the hint (fused_unorde
 two inputs are then timed on the stand-in with a ball that reflects and refracts in the hall: a double-branching scene, where the call keeps a chunk's ray colours
 and runs the continuation queue per ray.  Alternating rounds, each of a few launches between events: min, median and max of every leg.
 
-  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels] [--dilate] [--filter]
+  python tools/trace_rays_rate.py [--out profiles/trace_rays_rate.json] [--reps 20] [--quick] [--coherence] [--sweep] [--cast] [--shade [--beside FILE]] [--occlusion] [--gather] [--texels] [--dilate] [--filter] [--gather-sh]
 """
 import argparse
 import ctypes as C
@@ -414,6 +419,104 @@ def _gather_leg(w, h, reps):
     return out
 
 
+GATHER_SH_EXPECTATION = {
+    "a": "gather_sh_points(bands = 3, unordered=True) within 5 % of gather_points(unordered=True) on the same input: the trace costs about 1.6 ns a ray (52.4 ms / 33 M rays, "
+         "profiles/gather_order_rate.json); a fold at 10 % of its traffic floor — the low end of what dilate / filter reach — costs about 0.02 ns a ray, 1.3 % of the trace; "
+         "clearing and storing the ray colours adds less than that",
+    "b": "the fold alone (k_gather_fold_sh between two HIP events of nrays_debug_gather_sh_fold) is cheaper than its torch restatement (basis from the ray directions, "
+         "sequential f32 fold over j) in every row",
+    "c": "the fold alone as a share of its traffic floor (12 bytes a ray plus the outputs over the 6.29 TB/s a float4 copy reaches) is recorded; no threshold"}
+
+
+def _gather_sh_input(sc, tp, tn, keys, L, rot, bias, reps, rounds=3):
+    """One input of the gather-sh leg: n points under the table L (energy 1, max_depth 0).  Whole calls on device tensors; the fold alone and its torch restatement
+    on the input's first chunk (at most 2^22 rays: what one launch of the fold sees)."""
+    import torch
+    import nrays_amd as nr
+    from nrays_amd.scene import SH_K
+    n, k = tp.shape[0], len(L)
+    tl = torch.from_numpy(L).cuda()
+    tr = None if rot is None else torch.from_numpy(rot).cuda()
+    tk = torch.from_numpy(keys.astype(np.int64)).cuda()
+    fns = {"gather_points": lambda: nr.gather_points(sc, tp, tn, tl, tr, bias, 1.0, 0, keys=tk),
+           "gather_points_unordered": lambda: nr.gather_points(sc, tp, tn, tl, tr, bias, 1.0, 0, keys=tk, unordered=True)}
+    for bands in (1, 2, 3):
+        fns["gather_sh_bands_%d" % bands] = lambda bands=bands: nr.gather_sh_points(sc, tp, tn, tl, tr, bias, 1.0, 0, bands, keys=tk)
+        fns["gather_sh_bands_%d_unordered" % bands] = lambda bands=bands: nr.gather_sh_points(sc, tp, tn, tl, tr, bias, 1.0, 0, bands, keys=tk, unordered=True)
+    # the first chunk, on the host for the probe and on the device for the restatement
+    nc = min(n, max(1, (1 << 22) // k))
+    hp, hn, hk = tp[:nc].cpu().numpy(), tn[:nc].cpu().numpy(), np.ascontiguousarray(keys[:nc]).astype(np.uint64)
+    ro, rd = nr.occlusion_rays(hp, hn, L, rot, bias, hk)
+    rk = nr.gather_ray_keys(hk, k).reshape(-1)
+    t_rd = torch.from_numpy(rd).cuda()
+    colours = nr.trace_rays(sc, torch.from_numpy(ro.reshape(-1, 3)).cuda(), t_rd.view(-1, 3), keys=torch.from_numpy(rk.view(np.int64)).cuda()).view(nc, k, 3)
+    h_colours = colours.cpu().numpy()
+    K0, K1, K2, K3, K4 = SH_K
+
+    def torch_fold():
+        x, y, z = t_rd[..., 0], t_rd[..., 1], t_rd[..., 2]
+        Y = torch.stack([torch.full_like(x, K0), K1 * y, K1 * z, K1 * x, (K2 * x) * y, (K2 * y) * z, K3 * ((3.0 * z) * z - 1.0), (K2 * x) * z, K4 * (x * x - y * y)], dim=-1).float()
+        acc = torch.zeros((nc, 9, 3), dtype=torch.float32, device="cuda")
+        for j in range(k):
+            acc = acc + Y[:, j, :, None] * colours[:, j, None, :]
+        return acc / float(k)
+
+    ms = {name: [] for name in fns}
+    ms["torch_fold_bands_3_first_chunk"], fold_ms = [], {1: [], 2: [], 3: []}
+    for _ in range(rounds):
+        for name, fn in fns.items():
+            ms[name].append(_time(fn, reps, warmup=1))
+        ms["torch_fold_bands_3_first_chunk"].append(_time(torch_fold, max(1, reps // 2), warmup=1))
+        for bands in fold_ms:
+            nr.gather_sh_fold(sc, hp, hn, L, h_colours, rot, bias, bands, keys=hk)  # (warm)
+            fold_ms[bands].append(min(nr.gather_sh_fold(sc, hp, hn, L, h_colours, rot, bias, bands, keys=hk, want_ms=True)[1] for _ in range(max(2, reps))))
+    got = nr.gather_sh_points(sc, tp[:nc], tn[:nc], tl, tr, bias, 1.0, 0, 3, keys=tk[:nc])
+    hinted = nr.gather_sh_points(sc, tp[:nc], tn[:nc], tl, tr, bias, 1.0, 0, 3, keys=tk[:nc], unordered=True)
+    alone = torch.from_numpy(nr.gather_sh_fold(sc, hp, hn, L, h_colours, rot, bias, 3, keys=hk)).cuda()
+    row = {"points": int(n), "dirs": int(k), "rays": int(n * k), "energy": 1.0, "max_depth": 0, "rounds": rounds, "reps": reps, "first_chunk_points": int(nc),
+           "first_chunk_values_whose_bits_differ_hinted": int((hinted.view(torch.int32) != got.view(torch.int32)).sum().item()),
+           "first_chunk_values_whose_bits_differ_from_the_fold_alone": int((alone.view(torch.int32) != got.view(torch.int32)).sum().item()),
+           "first_chunk_values_that_differ_from_the_torch_fold": int((torch_fold() != got).sum().item())}
+    for name, v in ms.items():
+        row[name] = {"ms": round(float(np.median(v)), 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4)}
+    for bands, v in fold_ms.items():
+        floor_ms = (12.0 * nc * k + 12.0 * bands * bands * nc) / HBM_COPY_BYTES_PER_S * 1e3
+        med = float(np.median(v))
+        row["fold_alone_bands_%d_first_chunk" % bands] = {"ms": round(med, 4), "min_ms": round(min(v), 4), "max_ms": round(max(v), 4), "how": "the least of max(2, reps) probe calls per round; median of the rounds",
+                                                          "traffic_floor_ms": round(floor_ms, 5), "share_of_floor": round(floor_ms / med, 4) if med > 0 else None,
+                                                          "ns_per_ray": round(med * 1e6 / (nc * k), 5)}
+    a = row["gather_sh_bands_3_unordered"]["ms"] / row["gather_points_unordered"]["ms"]
+    row["expectation"] = {"a_bands_3_hinted_over_gather_points_hinted": round(a, 4), "a": "MET" if a <= 1.05 else "MISSED",
+                          "b": "MET" if row["fold_alone_bands_3_first_chunk"]["ms"] < row["torch_fold_bands_3_first_chunk"]["ms"] else "MISSED",
+                          "c_share_of_floor_bands_3": row["fold_alone_bands_3_first_chunk"]["share_of_floor"]}
+    return row
+
+
+def _gather_sh_leg(w, h, reps, path):
+    import torch
+    import nrays_amd as nr
+    from tools import standins
+    out = {"expectation_written_before_the_first_run": GATHER_SH_EXPECTATION,
+           "inputs": "first_hits_16_dirs / subset_16384_points_64_dirs: the gather leg's (8 rotations, bias 1e-3); probes_4096_sphere_1024: a 16^3 grid over the middle half of the "
+                     "first hits' bounding box, sphere_dirs(1024), normal (0, 0, 1), bias 0, no rotations"}
+    with open(path, "w") as f:  # the expectation is on file before anything is timed
+        json.dump({"workloads": {"k_gather_sh": out}}, f, indent=1)
+    sc, cam = standins.sponza_scene()
+    tp, tn, keys = _first_hit_points((sc, cam), w, h)
+    n = tp.shape[0]
+    sub = torch.from_numpy(np.linspace(0, n - 1, min(16384, n)).astype(np.int64)).cuda()
+    rot = nr.rotation_table(8)
+    out["first_hits_16_dirs"] = _gather_sh_input(sc, tp, tn, keys, nr.hemisphere_dirs(16), rot, 1e-3, max(1, reps // 4))
+    out["subset_16384_points_64_dirs"] = _gather_sh_input(sc, tp[sub].contiguous(), tn[sub].contiguous(), keys[sub.cpu().numpy()], nr.hemisphere_dirs(64), rot, 1e-3, reps)
+    lo, hi = tp.min(dim=0).values.cpu().numpy(), tp.max(dim=0).values.cpu().numpy()
+    g = (np.arange(16) + 0.5) / 16.0 * 0.5 + 0.25
+    grid = np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3) * (hi - lo) + lo
+    up = np.tile([0.0, 0.0, 1.0], (len(grid), 1))
+    out["probes_4096_sphere_1024"] = _gather_sh_input(sc, torch.from_numpy(grid).cuda(), torch.from_numpy(up).cuda(), np.arange(len(grid), dtype=np.uint64), nr.sphere_dirs(1024), None, 0.0,
+                                                      max(1, reps // 4))
+    return out
+
+
 def _texels_row(sc, mesh, size, reps, mirror, rounds=5):
     import torch
     import nrays_amd as nr
@@ -639,12 +742,13 @@ def main():
     ap.add_argument("--beside", default=None, help="with --shade: the JSON of an earlier run (another library), copied into this one under 'beside'")
     ap.add_argument("--occlusion", action="store_true", help="time occlusion_points beside intersects_rays on the same rays and the torch fold (leg e_sponza_occlusion), nothing else")
     ap.add_argument("--gather", action="store_true", help="time gather_points beside building the rays with torch, trace_rays on them and the torch fold (leg h_sponza_gather), nothing else")
+    ap.add_argument("--gather-sh", action="store_true", help="time gather_sh_points at bands 1 / 2 / 3 beside gather_points, the fold kernel alone, its torch restatement and its traffic floor (leg k_gather_sh, into profiles/gather_sh_rate.json), nothing else")
     ap.add_argument("--texels", action="store_true", help="time surface_texels, its two passes, shade_points on its texels and the numpy mirror (leg g_surface_texels), nothing else")
     ap.add_argument("--dilate", action="store_true", help="time dilate_texels beside surface_texels, the torch passes a caller wrote before and the traffic floor (leg i_dilate_texels, into profiles/dilate_rate.json); alone: nothing else")
     ap.add_argument("--filter", action="store_true", help="time filter_texels and denoise_texels beside a torch restatement, the traffic floor, and one more gathered direction (leg j_filter_texels, into profiles/filter_rate.json), nothing else")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "filter_rate.json" if a.filter else "dilate_rate.json" if a.dilate and not a.texels else "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
+        a.out = os.path.join(ROOT, "profiles", "gather_sh_rate.json" if a.gather_sh else "filter_rate.json" if a.filter else "dilate_rate.json" if a.dilate and not a.texels else "surface_texels_rate.json" if a.texels else "occlusion_rate.json" if a.occlusion else "gather_rate.json" if a.gather else "trace_rays_rate.json")
     if a.sweep:
         os.environ["NRAYS_RAY_REORDER"] = "2"  # read when a handle is created
     import torch
@@ -657,6 +761,14 @@ def main():
     w, h = (320, 180) if a.quick else (1920, 1080)
     res = {"tool": "tools/trace_rays_rate.py", "resolution": [w, h], "reps": a.reps, "device": torch.cuda.get_device_name(0),
            "library": "/".join((os.environ.get("NRAYS_HIP_LIB") or "nrays_amd/lib/libnrays_hip.so").split("/")[-2:]), "workloads": {}}
+
+    if a.gather_sh:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        leg = dict(res, workloads={"k_gather_sh": _gather_sh_leg(w, h, a.reps, a.out)})
+        with open(a.out, "w") as f:
+            json.dump(leg, f, indent=1)
+        print(json.dumps(leg))
+        return
 
     if a.filter:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
