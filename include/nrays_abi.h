@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -502,6 +502,75 @@ int nrays_gather_sh_points(NraysScene* scene, uint32_t n, const double* points, 
  * of params included).  Blocking.  Arguments are checked as by nrays_gather_sh_points; NULL ray_colours -> NRAYS_ERR_BAD_ARG. */
 int nrays_debug_gather_sh_fold(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                                const NraysGatherParams* params, uint32_t bands, const float* ray_colours, float* out_sh, float* out_kernel_ms);
+
+/* The light that BAKED MAPS hold at the closest hits of the hemisphere rays of n caller-supplied surface points — one diffuse bounce of a light-map baker: the
+ * library builds num_dirs rays per point ON THE DEVICE, finds each ray's closest hit, samples the light map of the node it hit at the hit's uv and writes ONE mean
+ * colour per point.  Feeding a baked map back in (Python: bake_bounces) gathers the next bounce without a new scene, a host copy or a material that stands in for
+ * the map.  No per-ray memory exists anywhere.  The result is defined by this text, so that a caller can restate it from existing parts:
+ *   rays       ray j of point i is bit for bit the ray nrays_occlusion_points* / nrays_gather_points* build from the same point, normal, key, dirs, rotations and
+ *              bias: the same frame, the same rotation pick (salt 0x300 << 32), origin p + n * bias, the same direction.  nrays_debug_occlusion_rays and Python's
+ *              occlusion_rays serve this call too.  Only the rotation reads `keys`.
+ *   query      each ray runs the closest-hit query of nrays_cast_rays_device (Scene::trace's first query, NOT Scene::intersects_ray): the ungated traversal, the
+ *              winner checked against the exact gates, the gated repeat.  max_toi filters the FINISHED query (toi <= max_toi keeps the hit), as the per-ray bound
+ *              of that call does.  Transparency is not looked at.
+ *   c_ij       (f32 rgb) and its class:
+ *                missed   no hit within max_toi: miss_rgb.
+ *                mapped   a hit on node d with m = node_map[d] in [0, num_maps) whose record carries a uv (bit 1 of nrays_cast_rays_device's out_flags): x, y, z
+ *                         of Texture2d::sample of maps[m] at the record's (u, v) (below); the sample's w is dropped.
+ *                dark     every other hit: (+0, +0, +0).  A node_map entry outside [0, num_maps) counts as -1.  The side of the surface the ray arrives on is
+ *                         not looked at.
+ *   sample     the value the library's materials get from a texture (texture2d.rs:207-256), with maps[m].interp and .overflow honoured as given; format must be
+ *              NRAYS_TEXEL_RGBA32F (what Python's bake_lightmap returns and lightmap_texture wraps), texel (x, y) at texels[4 * (y * width + x) ..], row 0 the
+ *              BOTTOM row.  All f32, every product and sum rounded on its own, left to right as written (Python: lightmap_sample_ref):
+ *                ux = (float)u, uy = (float)v
+ *                NRAYS_OVERFLOW_CLAMP:  ux = ux > 0 ? (ux < 1 ? ux : 1) : 0          (a NaN becomes 0); likewise uy
+ *                NRAYS_OVERFLOW_WRAP:   ux = copysign(ux - trunc(ux), ux)            (fmodf(ux, 1); inf gives NaN); if (ux < 0) ux = 1 + ux; likewise uy
+ *                ux = ux * (float)(width - 1), uy = uy * (float)(height - 1)
+ *                index(x) = 0 if !(x > 0), 2^32 - 1 if x >= 2^32, else trunc(x)      (Rust's `f32 as usize`)
+ *                NRAYS_INTERP_NEAREST:  the texel at (min(index(round(ux)), width - 1), min(index(round(uy)), height - 1)), round = half away from zero.
+ *                NRAYS_INTERP_BILINEAR: lx = min(index(floor(ux)), width - 1), hx = min(lx + 1, width - 1), ly, hy likewise;
+ *                                       sx = ux - (float)lx, sy = uy - (float)ly;
+ *                                       ul = texel(lx, hy), ur = texel(hx, hy), dl = texel(lx, ly), dr = texel(hx, ly); per channel
+ *                                       ui = ul * (1 - sx) + ur * sx;  di = dl * (1 - sx) + dr * sx;  r = ui * sy + di * (1 - sy).
+ *   fold       sum = +0 (f32 rgb); for j = 0 .. num_dirs - 1 in order: sum += c_ij; out_rgb[3i..3i+2] = sum / (float)num_dirs (one correctly rounded division per
+ *              channel): the fold of nrays_gather_points.  The result never depends on how the library assigns rays to lanes.
+ *   out_counts n x 2 words, or NULL (no store): the number of mapped and of missed rays of point i.
+ *   skipped    a point whose hit_flags bit 0 is clear: out_rgb (0, 0, 0), out_counts 0, 0, no traversal, neither its point nor its normal read. */
+#define NRAYS_GATHER_MAX_MAPS 16u
+/* (Struct plus separate typedef, as NraysGatherParams and for the same reason; tests/test_gather_maps.py compares it with its Rust and ctypes twins.) */
+struct NraysGatherMapsParams {
+    uint32_t num_dirs;        /* 1 .. 1024 */
+    uint32_t num_rotations;   /* 0 .. 1024; 0 = none */
+    const double* dirs;       /* num_dirs x 3, local frame, z = the normal */
+    const double* rotations;  /* num_rotations x 2 (cos, sin), or NULL when 0 */
+    double bias;              /* finite */
+    double max_toi;           /* > 0, +inf allowed */
+    uint32_t num_maps;        /* 1 .. NRAYS_GATHER_MAX_MAPS */
+    uint32_t num_nodes;       /* entries of node_map; must equal the scene's node count */
+    const NraysTexture* maps; /* HOST array of num_maps records (always host, like this struct); their `texels` as the call says */
+    const int32_t* node_map;  /* num_nodes entries: the map a node's surface reads, or -1 */
+    float miss_rgb[3];        /* what a ray that leaves the scene brings; finite */
+};
+typedef struct NraysGatherMapsParams NraysGatherMapsParams;
+/*   points, normals  n x 3 doubles, world space, used as given (unit normals pointing to the side to gather on).
+ *   hit_flags        n words, or NULL = every point is live: the bits of out_flags of nrays_cast_rays_device / nrays_surface_texels_device.
+ *   keys             n RNG keys, or NULL = the key of point i is i (also across chunks).
+ *   params           HOST memory (the struct and its `maps` records); params->dirs, ->rotations, ->node_map and every map's texels are DEVICE memory here, like
+ *                    every other array.  The records are copied into the kernel's arguments (16 x 24 bytes): nothing of them is read after the call returns.
+ *   out_rgb          n x 3 floats, required.      out_counts   n x 2 words, or NULL.
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG).
+ * NULL scene / points / normals / params / dirs / maps / node_map / out_rgb; num_dirs outside 1 .. 1024, num_rotations > 1024 or > 0 with NULL rotations; a
+ * non-finite bias or miss_rgb, a NaN or <= 0 max_toi; num_maps outside 1 .. 16, num_nodes other than the scene's node count; a map with NULL texels, width or
+ * height 0, a format other than NRAYS_TEXEL_RGBA32F or an unknown interp / overflow; flags != 0 -> NRAYS_ERR_BAD_ARG, before any device work.  n == 0 ->
+ * NRAYS_OK, the outputs untouched.  Otherwise the contract of nrays_gather_points_device: chunks of at most max(1, 2^22 / num_dirs) points, enqueued on
+ * `hip_stream` behind the handle's previous work, without read-back or synchronisation in ANY scene kind (nothing is queued here); what the handle reports
+ * about its renders and its per-camera scheduling state stay untouched. */
+int nrays_gather_maps_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                    const uint64_t* keys, const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts,
+                                    uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables, node_map and the maps' texels included) HOST memory.  Blocking.  The maps' texels are staged with the tables, once a call. */
+int nrays_gather_maps_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                             const uint64_t* keys, const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and

@@ -659,6 +659,40 @@ impl GpuScene {
         Ok(())
     }
 
+    /// The light that baked maps hold at the closest hits of the hemisphere rays of caller-supplied surface points (nrays_gather_maps_points, blocking): the rays
+    /// of `occlusion_points` with the same tables, `bias` and keys, each through the closest-hit query of `cast_rays` with `max_toi`; a hit on a node whose
+    /// `node_map` entry names one of `maps` (1 .. 16 records of float32 texels in host memory, row 0 the bottom row) brings that map's sample at the hit's uv, a
+    /// ray that leaves the scene brings `miss`, every other hit black; the colours are summed in order and divided by their number: one bounce of a light-map
+    /// baker.  `node_map` has one entry per scene node (-1: no map).  Returns the mean colours and, per point, the numbers of mapped and of missed rays.  The
+    /// value is defined in include/nrays_abi.h (NraysGatherMapsParams).
+    pub fn gather_maps_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, max_toi: f64,
+                              maps: &[NraysTexture], node_map: &[i32], miss: [f32; 3], keys: Option<&[u64]>) -> Result<(Vec<Vector3<f32>>, Vec<(u32, u32)>), String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        if maps.is_empty() || maps.len() > NRAYS_GATHER_MAX_MAPS as usize { return Err(format!("{} maps: 1 .. {} are allowed", maps.len(), NRAYS_GATHER_MAX_MAPS)); }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysGatherMapsParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                             rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, max_toi, num_maps: maps.len() as u32,
+                                             num_nodes: node_map.len() as u32, maps: maps.as_ptr(), node_map: node_map.as_ptr(), miss_rgb: miss };
+        let mut rgb = vec![0.0f32; 3 * n];
+        let mut counts = vec![0u32; 2 * n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_gather_maps_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, rgb.as_mut_ptr(), counts.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(((0..n).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect(), (0..n).map(|i| (counts[2 * i], counts[2 * i + 1])).collect()))
+    }
+
+    /// `gather_maps_points` for n points in DEVICE memory (nrays_gather_maps_points_device), enqueued on `hip_stream`: the arrays of `gather_points_device`,
+    /// out_counts n x 2 u32 or null.  `params` and its `maps` records are host memory; its two tables, `node_map` and the maps' texels are device memory.
+    pub unsafe fn gather_maps_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64,
+                                            params: &NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_gather_maps_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_rgb, out_counts, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
     /// The gathered light of `gather_points` kept by direction (nrays_gather_sh_points, blocking): per point the projection of its rays' colours onto the real
     /// spherical harmonics of bands 0 .. `bands` - 1 (1 ..= 3; C = bands * bands coefficients), `out[i][c]` = coefficient c of point i as an RGB vector.  No measure
     /// is applied: multiply by 4 pi for uniform sphere directions.  An irradiance probe is a point with normal (0, 0, 1), bias 0 and no rotations under a table

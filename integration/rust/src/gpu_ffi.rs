@@ -227,6 +227,24 @@ pub struct NraysGatherParams {
     pub max_depth: u32,
 }
 
+pub const NRAYS_GATHER_MAX_MAPS: u32 = 16;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysGatherMapsParams {
+    pub num_dirs: u32,
+    pub num_rotations: u32,
+    pub dirs: *const f64,
+    pub rotations: *const f64,
+    pub bias: f64,
+    pub max_toi: f64,
+    pub num_maps: u32,
+    pub num_nodes: u32,
+    pub maps: *const NraysTexture,
+    pub node_map: *const i32,
+    pub miss_rgb: [f32; 3],
+}
+
 pub enum NraysScene {}
 pub enum NraysComm {}
 pub enum NraysSceneSet {}
@@ -276,6 +294,8 @@ extern "C" {
     pub fn nrays_gather_sh_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, bands: u32, out_sh: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_gather_sh_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, bands: u32, out_sh: *mut f32, flags: u32) -> c_int;
     pub fn nrays_debug_gather_sh_fold(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, bands: u32, ray_colours: *const f32, out_sh: *mut f32, out_kernel_ms: *mut f32) -> c_int;
+    pub fn nrays_gather_maps_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_gather_maps_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_gather_order(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
     pub fn nrays_surface_texels_device(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_surface_texels(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;

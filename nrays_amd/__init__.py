@@ -10,4 +10,5 @@ from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolat
                     occlusion_hits, occlusion_points, occlusion_ray_probe, occlusion_rays, ray_order, render, rotation_table, shade_hits, shade_points, shadow_rays, trace_rays,
                     SurfaceTexels, bake_indirect, bake_lightmap, gather_hits, gather_order, gather_points, gather_ray_keys, surface_texels, surface_texels_passes, surface_texels_ref, texel_coords,
                     dilate_texels, dilate_texels_ref, lightmap_texture, denoise_texels, filter_texels, filter_texels_ref,
-                    gather_probes, gather_sh_fold, gather_sh_points, sh_basis, sh_fold_ref, sh_irradiance, sphere_dirs)
+                    gather_probes, gather_sh_fold, gather_sh_points, sh_basis, sh_fold_ref, sh_irradiance, sphere_dirs,
+                    bake_bounces, gather_maps_hits, gather_maps_points, lightmap_sample_ref)

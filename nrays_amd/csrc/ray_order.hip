@@ -1,4 +1,4 @@
-// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_points* and their _ex forms, nrays_gather_sh_points*, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch, nrays_debug_box_cull; host side below the kernels), and
+// ray_order.hip — the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*, nrays_shade_points*, nrays_occlusion_points*, nrays_gather_maps_points*, nrays_gather_points* and their _ex forms, nrays_gather_sh_points*, nrays_surface_texels*, nrays_dilate_texels*, nrays_debug_cast_batch, nrays_debug_box_cull; host side below the kernels), and
 // first what the batches need that come in no useful order (NRAYS_RAYS_UNORDERED): the rays of a chunk are binned by a spatial key
 // on the device and traced in bin order, every result written to the slot of the ray it belongs to.  The traversal lives on coherence
 // inside a wave (a wave-uniform node visit is one scalar fetch for 64 lanes, and only when the lanes agree on the direction signs); a wave
@@ -22,11 +22,13 @@
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
+#include <cstring>
 #include <new>
 #include <string>
 
 #include "../../include/nrays_abi.h"
 #include "bounce.h"
+#include "gather_maps_kernel.h"
 #include "gather_sh_kernel.h"
 #include "ray_batch_kernel.h"
 #include "ray_key.h"
@@ -952,6 +954,143 @@ static int gather_points_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn
     return rc;
 }
 
+// ---- nrays_gather_maps_points*: the light of baked maps at the closest hits of the hemisphere rays of caller-supplied points (gather_maps_kernel.h) -------------
+static int check_gather_maps_args(const NraysScene* sc, const OcclusionIn& in, const NraysGatherMapsParams* p, const float* out_rgb, uint32_t flags) {
+    if (!sc || !in.points || !in.normals || !p || !p->dirs || !p->maps || !p->node_map || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_dirs must be in 1 .. 1024");
+    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_rotations > 1024, or rotations is NULL");
+    if (!std::isfinite(p->bias) || !std::isfinite(p->miss_rgb[0]) || !std::isfinite(p->miss_rgb[1]) || !std::isfinite(p->miss_rgb[2]))
+        return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: bias and miss_rgb must be finite");
+    if (!(p->max_toi > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: max_toi must be > 0 (+inf allowed)");
+    if (p->num_maps < 1u || p->num_maps > NRAYS_GATHER_MAX_MAPS) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_maps must be in 1 .. 16");
+    if (p->num_nodes != (uint32_t)sc->facts.host.shade.size()) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_nodes is not the scene's node count");
+    for (uint32_t m = 0; m < p->num_maps; ++m) {
+        const NraysTexture& t = p->maps[m];
+        if (!t.texels || t.width == 0u || t.height == 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: a map without texels");
+        if (t.format != NRAYS_TEXEL_RGBA32F) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: a map's format must be NRAYS_TEXEL_RGBA32F");
+        if ((t.interp != NRAYS_INTERP_BILINEAR && t.interp != NRAYS_INTERP_NEAREST) || (t.overflow != NRAYS_OVERFLOW_WRAP && t.overflow != NRAYS_OVERFLOW_CLAMP))
+            return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: a map's interp or overflow is unknown");
+    }
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_maps_points: flags must be 0");
+    return NRAYS_OK;
+}
+static uint32_t gather_maps_chunk(const NraysGatherMapsParams* p) { return std::max<uint32_t>(1u, kTraceChunk / p->num_dirs); } // points per chunk: at most kTraceChunk rays
+// The kernel's view of the checked parameters: the map records as the shading records hold a texture (ShadeTex), texel address `texels[m]`.
+static void gather_maps_table(const NraysGatherMapsParams* p, const void* const* texels, GatherMapsTable* t) {
+    std::memset(t, 0, sizeof *t);
+    for (uint32_t m = 0; m < p->num_maps; ++m) {
+        const NraysTexture& s = p->maps[m];
+        t->map[m].texels = texels[m]; t->map[m].width = s.width; t->map[m].height = s.height; t->map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
+    }
+}
+// One chunk (nc <= gather_maps_chunk) of nrays_gather_maps_points_device; `in` and the outputs are the chunk's, key_base the index of its first point in the batch,
+// node_map / dirs / rotations and the table's texels device memory.  The permutation is cast_chunk's, the lanes per point are occlusion_chunk_launch's.
+static int gather_maps_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const OcclusionIn& in, unsigned long long key_base, const NraysGatherMapsParams* p,
+                                    const GatherMapsTable& table, const int32_t* node_map, const double* dirs, const double* rotations, float* out_rgb, uint32_t* out_counts,
+                                    hipStream_t stream) {
+    const bool mesh = (sc->facts.features & ~(int)kFeatMultiSample) == (int)kFeatMesh; // (traversal only: as nrays_cast_rays_device)
+    const int lp = occlusion_lanes_log2(sc, p->num_dirs);
+    const uint32_t slots = nc << lp; // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+    const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const GatherMapsSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_toi, p->num_maps, p->num_nodes, {p->miss_rgb[0], p->miss_rgb[1], p->miss_rgb[2]}};
+    const GatherMapsLaunch a{grid, stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, (const unsigned long long*)in.keys, key_base, spec, &table, node_map, dirs, rotations,
+                             out_rgb, out_counts, w->d_spill};
+    if (!launch_gather_maps_points(a, mesh ? (int)kFeatMesh : (int)kFeatAll, lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_maps_points: no such permutation");
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_gather_maps_points: ") + hipGetErrorString(e));
+    return NRAYS_OK;
+}
+
+static int gather_maps_device_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherMapsParams* p, float* out_rgb, uint32_t* out_counts, uint32_t flags,
+                                   hipStream_t stream) {
+    if (check_gather_maps_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc == NRAYS_OK) rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    const void* texels[NRAYS_GATHER_MAX_MAPS] = {};
+    for (uint32_t m = 0; m < p->num_maps; ++m) texels[m] = p->maps[m].texels;
+    GatherMapsTable table;
+    gather_maps_table(p, texels, &table);
+    const uint32_t chunk = gather_maps_chunk(p);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        rc = gather_maps_chunk_launch(sc, w, nc, occlusion_in_at(in, c0), (unsigned long long)c0, p, table, p->node_map, p->dirs, p->rotations, out_rgb + 3 * (size_t)c0,
+                                      out_counts ? out_counts + 2 * (size_t)c0 : nullptr, stream);
+    }
+    batch_end(sc, w, stream);
+    return rc;
+}
+
+// The blocking form, through the workspace's staging buffer as gather_points_host_impl: the two tables first, then the maps' texels (16 bytes each, on a 16-byte
+// boundary), node_map (padded to 8 bytes), then per staged point kGatherMapsStageBytes — point, normal (3 f64), key (u64), colour (3 f32), hit flags, the two
+// counts (32 bits each), the 8-byte fields first.
+constexpr size_t kGatherMapsStageBytes = 80;
+static int gather_maps_host_impl(NraysScene* sc, uint32_t n, const OcclusionIn& in, const NraysGatherMapsParams* p, float* out_rgb, uint32_t* out_counts, uint32_t flags) {
+    if (check_gather_maps_args(sc, in, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    TraceWorkspace* w = nullptr;
+    int rc = trace_workspace(sc, &w);
+    if (rc != NRAYS_OK) return rc;
+    const uint32_t chunk = gather_maps_chunk(p);
+    const size_t cap = std::min<uint32_t>(n, chunk);
+    const size_t table_bytes = (24 * (size_t)p->num_dirs + 16 * (size_t)p->num_rotations + 15) / 16 * 16;
+    size_t texel_bytes = 0;
+    for (uint32_t m = 0; m < p->num_maps; ++m) texel_bytes += 16 * (size_t)p->maps[m].width * p->maps[m].height;
+    const size_t node_bytes = (4 * (size_t)p->num_nodes + 7) / 8 * 8;
+    rc = grow_device(&w->d_stage, &w->stage_rays, (table_bytes + texel_bytes + node_bytes + cap * kGatherMapsStageBytes + kStageUnit - 1) / kStageUnit, kStageUnit);
+    if (rc != NRAYS_OK) return rc;
+    char* base = (char*)w->d_stage;
+    double* s_dirs = (double*)base; double* s_rot = s_dirs + 3 * (size_t)p->num_dirs;
+    char* s_tex = base + table_bytes;
+    int32_t* s_nodes = (int32_t*)(s_tex + texel_bytes);
+    double* s_p = (double*)((char*)s_nodes + node_bytes); double* s_n = s_p + 3 * cap;
+    uint64_t* s_k = (uint64_t*)(s_n + 3 * cap); float* s_c = (float*)(s_k + cap); uint32_t* s_hf = (uint32_t*)(s_c + 3 * cap); uint32_t* s_cnt = s_hf + cap;
+    const OcclusionIn s{s_p, s_n, in.hit_flags ? s_hf : nullptr, in.keys ? s_k : nullptr};
+    rc = ensure_own_stream(sc);
+    if (rc != NRAYS_OK) return rc;
+    const hipStream_t stream = sc->buf.own_stream;
+    rc = batch_begin(sc, w, stream);
+    if (rc != NRAYS_OK) return rc;
+    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
+    hipError_t e = up(s_dirs, p->dirs, 24 * (size_t)p->num_dirs);
+    if (e == hipSuccess) e = up(s_rot, p->rotations, 16 * (size_t)p->num_rotations);
+    if (e == hipSuccess) e = up(s_nodes, p->node_map, 4 * (size_t)p->num_nodes);
+    const void* texels[NRAYS_GATHER_MAX_MAPS] = {};
+    size_t off = 0;
+    for (uint32_t m = 0; m < p->num_maps && e == hipSuccess; ++m) {
+        const size_t bytes = 16 * (size_t)p->maps[m].width * p->maps[m].height;
+        texels[m] = s_tex + off;
+        e = up(s_tex + off, p->maps[m].texels, bytes);
+        off += bytes;
+    }
+    if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather maps tables upload: ") + hipGetErrorString(e));
+    GatherMapsTable table;
+    gather_maps_table(p, texels, &table);
+    for (uint32_t c0 = 0; c0 < n && rc == NRAYS_OK; c0 += std::min<uint32_t>(n - c0, chunk)) {
+        const uint32_t nc = std::min<uint32_t>(n - c0, chunk);
+        const OcclusionIn h = occlusion_in_at(in, c0);
+        e = up(s_p, h.points, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_n, h.normals, (size_t)nc * 24);
+        if (e == hipSuccess) e = up(s_hf, h.hit_flags, (size_t)nc * 4);
+        if (e == hipSuccess) e = up(s_k, h.keys, (size_t)nc * 8);
+        if (e != hipSuccess) { rc = set_last_error(NRAYS_ERR_HIP, std::string("gather maps batch upload: ") + hipGetErrorString(e)); break; }
+        rc = gather_maps_chunk_launch(sc, w, nc, s, (unsigned long long)c0, p, table, s_nodes, s_dirs, p->num_rotations ? s_rot : nullptr, s_c, out_counts ? s_cnt : nullptr, stream);
+        if (rc != NRAYS_OK) break;
+        e = hipMemcpyAsync(out_rgb + 3 * (size_t)c0, s_c, (size_t)nc * 12, hipMemcpyDeviceToHost, stream);
+        if (e == hipSuccess && out_counts) e = hipMemcpyAsync(out_counts + 2 * (size_t)c0, s_cnt, (size_t)nc * 8, hipMemcpyDeviceToHost, stream);
+        const hipError_t es = hipStreamSynchronize(stream); // (always: the staging buffer is reused by the next chunk and the next call)
+        if (e == hipSuccess) e = es;
+        if (e != hipSuccess) rc = set_last_error(NRAYS_ERR_HIP, std::string("gather maps batch read-back: ") + hipGetErrorString(e));
+    }
+    if (rc != NRAYS_OK) (void)hipStreamSynchronize(stream); // (the tables' upload reads the caller's memory)
+    batch_end(sc, w, stream);
+    return rc;
+}
+
 // nrays_debug_occlusion_rays: ray j of point i, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].
 __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
                                                            const unsigned long long* __restrict__ keys, OcclusionSpec P, const double* __restrict__ dirs,
@@ -1520,6 +1659,15 @@ int nrays_gather_points(NraysScene* sc, uint32_t n, const double* points, const 
 int nrays_gather_points_ex(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                            const NraysGatherParams* params, float* out_rgb, uint32_t flags) {
     return gather_points_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, flags, true, 0u);
+}
+
+int nrays_gather_maps_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                    const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags, void* hip_stream) {
+    return gather_maps_device_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, out_counts, flags, (hipStream_t)hip_stream);
+}
+int nrays_gather_maps_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                             const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags) {
+    return gather_maps_host_impl(sc, n, OcclusionIn{points, normals, hit_flags, keys}, params, out_rgb, out_counts, flags);
 }
 
 int nrays_surface_texels_device(NraysScene* sc, uint32_t node, uint32_t width, uint32_t height, double* out_points, double* out_normals, double* out_uv, int32_t* out_node,

@@ -418,6 +418,16 @@ class Scene:
         """The indirect term of a light map of mesh node `node`: bake_indirect(self, node, ...); `dilate=` as there, by keyword."""
         return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
+    def gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
+                           keys=None, want_counts=False):
+        """The light of baked maps at the closest hits of the hemisphere rays of caller-supplied points of this scene: gather_maps_points(self, ...)."""
+        return gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations, bias, max_toi, miss, hit_flags, keys, want_counts)
+
+    def bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations=None, bias=1e-3, miss=(0.0, 0.0, 0.0), dilate=2, flip_normals=False, keys=None,
+                     device=None):
+        """The multi-bounce light map of mesh node `node`: bake_bounces(self, node, ...)."""
+        return bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations, bias, miss, dilate, flip_normals, keys, device)
+
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
         return surface_texels(self, node, width, height, centres, flip_normals, want, device)
@@ -1604,6 +1614,231 @@ def _bake_dilate(scene, flags, out, width, height, radius):
     if not (out.is_contiguous() if _is_tensor(out) else out.flags.c_contiguous):
         out = out.contiguous() if _is_tensor(out) else np.ascontiguousarray(out)
     return dilate_texels(scene, flags, width, height, radius, values=out)[0]
+
+
+# ---- light gathered from baked maps at the rays' closest hits: the bounces of a light map (include/nrays_abi.h: nrays_gather_maps_points_device) -----------------
+
+def lightmap_sample_ref(texels, u, v, interp=Interpolation.Bilinear, overflow=Overflow.ClampToEdges):
+    """The numpy float32 mirror of the sample nrays_gather_maps_points* takes from a map, bit for bit (include/nrays_abi.h: NraysGatherMapsParams — the value the
+    library's materials get from a texture, Texture2d::sample): `texels` (height, width, 4) float32, row 0 = the bottom row; `u`, `v` (n,) coordinates (the float64
+    uv of a hit record, converted to float32 first).  Every product and sum is a float32 operation of its own, in the header's order.  Returns (n, 4) float32."""
+    t = np.asarray(texels)
+    if t.ndim != 3 or t.shape[2] != 4 or t.dtype != np.float32 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("texels must be a (height, width, 4) float32 array")
+    if interp not in (Interpolation.Bilinear, Interpolation.Nearest) or overflow not in (Overflow.Wrap, Overflow.ClampToEdges):
+        raise ValueError("unknown interp or overflow")
+    F = np.float32
+    h, w = t.shape[0], t.shape[1]
+    with np.errstate(all="ignore"):
+        c = [np.atleast_1d(np.asarray(a)).astype(F) for a in (u, v)]
+        if c[0].shape != c[1].shape or c[0].ndim != 1:
+            raise ValueError("u and v must have the same shape (n,)")
+        for q in range(2):
+            x = c[q]
+            if overflow == Overflow.ClampToEdges:
+                x = np.where(x > F(0), np.where(x < F(1), x, F(1)), F(0)).astype(F)
+            else:
+                x = np.copysign(x - np.trunc(x), x).astype(F)
+                x = np.where(x < F(0), F(1) + x, x).astype(F)
+            c[q] = x * F((w, h)[q] - 1)
+        ux, uy = c
+        index = lambda x: np.where(x > F(0), np.minimum(np.trunc(np.where(x > F(0), x, F(0))).astype(np.float64), 4294967295.0), 0.0).astype(np.int64)  # noqa: E731
+        if interp == Interpolation.Nearest:
+            rnd = lambda x: np.where(np.abs(x) < F(8388608.0), np.copysign(np.floor(np.abs(x.astype(np.float64)) + 0.5), x), x).astype(F)  # noqa: E731
+            return np.ascontiguousarray(t[np.minimum(index(rnd(uy)), h - 1), np.minimum(index(rnd(ux)), w - 1)])
+        lx, ly = np.minimum(index(np.floor(ux)), w - 1), np.minimum(index(np.floor(uy)), h - 1)
+        hx, hy = np.minimum(lx + 1, w - 1), np.minimum(ly + 1, h - 1)
+        sx, sy = (ux - lx.astype(F))[:, None], (uy - ly.astype(F))[:, None]
+        ul, ur, dl, dr = t[hy, lx], t[hy, hx], t[ly, lx], t[ly, hx]
+        ui = ul * (F(1) - sx) + ur * sx
+        di = dl * (F(1) - sx) + dr * sx
+        return np.ascontiguousarray((ui * sy + di * (F(1) - sy)).astype(F))
+
+
+def _gather_maps_args(scene, maps, node_map, max_toi, miss):
+    """The checks of gather_maps_points that need no library: [(texels, interp, overflow)] with texels a (h, w, 4) float32 array or tensor, the node map as an
+    int32 array of the scene's node count, max_toi and miss as floats."""
+    if isinstance(maps, (Texture2d, np.ndarray)) or _is_tensor(maps) or maps is None:
+        raise ValueError("maps must be a list of (height, width, 4) float32 arrays or tensors, or of Texture2d")
+    maps = list(maps)
+    if not 1 <= len(maps) <= abi.GATHER_MAX_MAPS:
+        raise ValueError("maps must hold 1 .. %d maps, got %d" % (abi.GATHER_MAX_MAPS, len(maps)))
+    out = []
+    for i, m in enumerate(maps):
+        interp, overflow = Interpolation.Bilinear, Overflow.ClampToEdges
+        if isinstance(m, Texture2d):
+            interp, overflow = m.interpol, m.overflow
+            if m.data.format != abi.TEXEL_RGBA32F:
+                raise ValueError("maps[%d]: a Texture2d of float32 texels is required" % i)
+            m = m.data.pixels
+        if interp not in (Interpolation.Bilinear, Interpolation.Nearest) or overflow not in (Overflow.Wrap, Overflow.ClampToEdges):
+            raise ValueError("maps[%d]: unknown interpolation or overflow" % i)
+        if _is_tensor(m):
+            import torch
+            ok = m.dtype == torch.float32
+        else:
+            if not isinstance(m, np.ndarray):
+                raise ValueError("maps[%d] must be a numpy array, a torch tensor or a Texture2d, got %s" % (i, type(m).__name__))
+            ok = m.dtype == np.float32
+        if not ok or len(m.shape) != 3 or m.shape[2] != 4 or m.shape[0] < 1 or m.shape[1] < 1:
+            raise ValueError("maps[%d] must be (height, width, 4) float32, got %s %s" % (i, tuple(m.shape), m.dtype))
+        out.append((m, interp, overflow))
+    num_nodes = int(scene.descriptor.desc.num_nodes)
+    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, (bool, np.bool_))  # noqa: E731
+    if isinstance(node_map, dict):
+        nodes = np.full(num_nodes, -1, dtype=np.int32)
+        for k, m in node_map.items():
+            if not is_int(k) or not is_int(m):
+                raise ValueError("node_map: nodes and maps must be integers, got %r: %r" % (k, m))
+            if not 0 <= k < num_nodes:
+                raise ValueError("node_map: node %d is not one of the scene's %d nodes" % (k, num_nodes))
+            nodes[k] = min(max(int(m), -1), abi.GATHER_MAX_MAPS)
+    else:
+        if node_map is None or _is_tensor(node_map) or isinstance(node_map, (str, bytes)):
+            raise ValueError("node_map must be a sequence of integers or a dict {node: map}")
+        entries = list(node_map)
+        if not all(is_int(m) for m in entries):
+            raise ValueError("node_map: every entry must be an integer")
+        if len(entries) != num_nodes:
+            raise ValueError("node_map must have one entry per node of the scene (%d), got %d" % (num_nodes, len(entries)))
+        nodes = np.array([min(max(int(m), -1), abi.GATHER_MAX_MAPS) for m in entries], dtype=np.int32).reshape(num_nodes)
+    max_toi = float(max_toi)
+    if not max_toi > 0.0:
+        raise ValueError("max_toi must be > 0 (inf allowed)")
+    miss = tuple(float(x) for x in np.asarray(miss, dtype=np.float64).reshape(-1))
+    if len(miss) != 3 or not all(math.isfinite(x) and abs(x) <= float(np.finfo(np.float32).max) for x in miss):
+        raise ValueError("miss must be 3 finite float32 values")
+    return out, nodes, max_toi, miss
+
+
+def _gather_maps_params(L, rot, bias, max_toi, recs, node_ptr, num_nodes, miss, ptr):
+    """NraysGatherMapsParams over `recs` = [(texel address, width, height, interp, overflow)]; returns (params, the records' array, which must outlive the call)."""
+    arr = (abi.NraysTexture * len(recs))()
+    for t, (addr, w, h, interp, overflow) in zip(arr, recs):
+        t.width, t.height, t.format, t.interp, t.overflow, t.texels = w, h, abi.TEXEL_RGBA32F, interp, overflow, addr
+    params = abi.NraysGatherMapsParams(L.shape[0], 0 if rot is None else rot.shape[0], ptr(L), ptr(rot), bias, max_toi, len(recs), num_nodes,
+                                       C.cast(arr, C.POINTER(abi.NraysTexture)), node_ptr, (C.c_float * 3)(*miss))
+    return params, arr
+
+
+def gather_maps_points(scene, points, normals, sample_dirs, maps, node_map, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
+                       keys=None, want_counts=False):
+    """The light that baked maps hold at the closest hits of the hemisphere rays of n caller-supplied surface points — one diffuse bounce of a light-map baker —
+    through nrays_gather_maps_points_device / nrays_gather_maps_points: per point the library builds the len(sample_dirs) rays of occlusion_points() ON THE DEVICE
+    (the same rays bit for bit: occlusion_rays()), finds each ray's closest hit (the query of closest_hits(), with `max_toi`), samples the map of the node it hit
+    at the hit's uv (lightmap_sample_ref() restates the sample bit for bit) and folds the colours in order: (n, 3) float32, the mean.  A ray that leaves the scene
+    brings `miss`; a hit on a node without a map, or whose record carries no uv, brings black.  It equals closest_hits on occlusion_rays(), lightmap_sample_ref at
+    the hits' uv, summed over j in float32 and divided by float32(k), bit for bit.  No ray or per-ray value is ever in memory.
+    Also `scene.gather_maps_points(...)` on Scene and FileScene; gather_maps_hits() feeds it from closest_hits(), bake_bounces() loops it over a map.
+    `maps`: 1 .. 16 maps, each a (height, width, 4) float32 array or CUDA tensor in NraysTexture row order (row 0 = the bottom row; what bake_lightmap returns),
+    sampled Bilinear / ClampToEdges (bake with dilate >= 2), or a Texture2d of float32 texels for another mode.  `node_map`: one entry per node of the scene — the
+    index of the map its surface reads, or -1 —, or a dict {node: map} (every other node -1).  `points`, `normals`, `sample_dirs`, `rotations`, `bias`,
+    `hit_flags`, `keys`: as for occlusion_points (only the rotation pick reads the keys).  `want_counts`: returns (rgb, counts) with counts (n, 2) — the mapped
+    and the missed rays of each point.
+    numpy arrays -> nrays_gather_maps_points (blocking), numpy arrays (counts uint32).  torch tensors on the scene's GPU (points / normals float64; maps tensors
+    there or numpy arrays, which are uploaded) -> nrays_gather_maps_points_device on torch.cuda.current_stream(), tensors (counts int32)."""
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    ms, nodes, max_toi, miss = _gather_maps_args(scene, maps, node_map, max_toi, miss)
+    if _is_tensor(points):
+        import torch
+        if points.device.type != "cuda":
+            raise ValueError("torch tensors must be on the GPU, points is on %s" % points.device)
+        f64 = (torch.float64,)
+        keys_dt = tuple(d for d in (torch.int64, getattr(torch, "uint64", None)) if d is not None)
+        flags_dt = tuple(d for d in (torch.int32, getattr(torch, "uint32", None)) if d is not None)
+        L, rot = (t if t is None or _is_tensor(t) else torch.from_numpy(t).to(points.device) for t in (L, rot))
+        p, nm, hf, k, L, rot = _torch_args((("points", points, f64), ("normals", normals, f64), ("hit_flags", hit_flags, flags_dt), ("keys", keys, keys_dt),
+                                            ("sample_dirs", L, f64), ("rotations", rot, f64)), points.device)
+        texels = [m if _is_tensor(m) else torch.from_numpy(np.ascontiguousarray(m)).to(points.device) for m, _, _ in ms]
+        texels = list(_torch_args(tuple(("maps[%d]" % i, t, (torch.float32,)) for i, t in enumerate(texels)), points.device))
+        node_t = torch.from_numpy(nodes).to(points.device)
+        rgb = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+        counts = torch.empty((n, 2), dtype=torch.int32, device=points.device) if want_counts else None
+        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
+        recs = [(t.data_ptr(), t.shape[1], t.shape[0], interp, overflow) for t, (_, interp, overflow) in zip(texels, ms)]
+        params, keep = _gather_maps_params(L, rot, bias, max_toi, recs, node_t.data_ptr(), len(nodes), miss, ptr)
+        lib = abi.load_hip_lib()
+        with torch.cuda.device(points.device):
+            abi.check(lib.nrays_gather_maps_points_device(scene.device_handle(), n, ptr(p), ptr(nm), ptr(hf), ptr(k), C.byref(params), ptr(rgb), ptr(counts), 0,
+                                                          torch.cuda.current_stream().cuda_stream))
+        del keep
+        return (rgb, counts) if want_counts else rgb
+    if any(_is_tensor(a) for a in (normals, hit_flags, keys, L, rot)) or any(_is_tensor(m) for m, _, _ in ms):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    hf = None if hit_flags is None else _np_ints("hit_flags", hit_flags, np.uint32)
+    k = None if keys is None else _np_keys(keys)
+    texels = [np.ascontiguousarray(m) for m, _, _ in ms]
+    rgb = np.empty((n, 3), dtype=np.float32)
+    counts = np.empty((n, 2), dtype=np.uint32) if want_counts else None
+    ptr = lambda a, t: None if a is None else a.ctypes.data_as(C.POINTER(t))  # noqa: E731
+    recs = [(t.ctypes.data, t.shape[1], t.shape[0], interp, overflow) for t, (_, interp, overflow) in zip(texels, ms)]
+    params, keep = _gather_maps_params(L, rot, bias, max_toi, recs, nodes.ctypes.data, len(nodes), miss, lambda a: None if a is None else a.ctypes.data)
+    lib = abi.load_hip_lib()
+    abi.check(lib.nrays_gather_maps_points(scene.device_handle(), n, ptr(p, C.c_double), ptr(nm, C.c_double), ptr(hf, C.c_uint32), ptr(k, C.c_uint64), C.byref(params),
+                                           ptr(rgb, C.c_float), ptr(counts, C.c_uint32), 0))
+    del keep
+    return (rgb, counts) if want_counts else rgb
+
+
+def gather_maps_hits(scene, origins, dirs, hits, sample_dirs, maps, node_map, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), keys=None,
+                     want_counts=False):
+    """The light of baked maps arriving at the closest hits of caller-supplied rays: gather_maps_points() at the hits of `hits = closest_hits(scene, origins, dirs)`
+    (a CastHits with normal and flags), on the side the rays came from — the points and normals of occlusion_hits(), built the same way.  Misses come back as
+    zeros.  numpy or torch as the inputs."""
+    points, normals = _hit_points("gather_maps_hits", origins, dirs, hits)
+    return gather_maps_points(scene, points, normals, sample_dirs, maps, node_map, rotations, bias, max_toi, miss, hit_flags=hits.flags, keys=keys,
+                              want_counts=want_counts)
+
+
+def bake_bounces(scene, node, width, height, sample_dirs, bounces, albedo, rotations=None, bias=1e-3, miss=(0.0, 0.0, 0.0), dilate=2, flip_normals=False, keys=None,
+                 device=None):
+    """The multi-bounce light map of TriMesh node `node`, (height, width, 4) float32 in NraysTexture row order (row 0 = the bottom row), on one stream, without a
+    scene rebuild and — with `device` — without a host copy:
+      tx  = surface_texels(node, width, height) on the default lattice, the one Texture2d::sample reads (there is no `centres` here);
+      L_0 = shade_points at the texels viewed against the normal — what bake_lightmap() computes —, dilated;
+      L_b = albedo * gather_maps_points(tx, maps=[L_{b-1}], node_map={node: 0}, miss = `miss` if b == 1 else 0), dilated, for b = 1 .. bounces: the sky reaches a
+            texel once — later bounces carry it inside L_{b-1};
+      the result is L_0 + L_1 + ... added in that order in float32, alpha from L_0.
+    `albedo`: 3 floats or a (height, width, 3) array, the diffuse reflectance a bounce is multiplied by.  `sample_dirs` cosine-weighted (hemisphere_dirs()) make
+    the mean the irradiance integral of a diffuse surface.  `dilate` (2 .. 64): every L_b is sampled Bilinear, which reads the diagonal neighbour of a border
+    texel, so less than 2 raises ValueError.  `keys`, `rotations`, `bias`, `flip_normals`, `device`: as for bake_lightmap / bake_indirect.
+    Denoising stays the caller's step, between the calls: this loop is tx = surface_texels(...); L = shade_points(...); dilate_texels(...);
+    rgb = gather_maps_points(...); rgb = denoise_texels(scene, tx, rgb, width=width, height=height); dilate_texels(..., values=rgb); and so on.
+    Also `scene.bake_bounces(node, ...)` on Scene and FileScene."""
+    width, height = _texel_lattice(width, height)
+    bounces = int(bounces)
+    if bounces < 0:
+        raise ValueError("bounces must be >= 0")
+    radius = _dilate_radius(dilate)
+    if radius < 2:
+        raise ValueError("dilate must be >= 2: a Bilinear sample reads the diagonal neighbour of a border texel")
+    _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    _, _, _, miss = _gather_maps_args(scene, [np.zeros((1, 1, 4), np.float32)], {}, math.inf, miss)
+    if _is_tensor(albedo):
+        albedo = albedo.detach().cpu().numpy()
+    a = np.asarray(albedo)
+    if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)) or a.shape not in ((3,), (height, width, 3)):
+        raise ValueError("albedo must be 3 numbers or a (height, width, 3) array, got shape %s" % (a.shape,))
+    a = np.array(a.astype(np.float32).reshape(-1, 3), copy=True, order="C")  # (n, 3) per texel, or (1, 3)
+    tx = surface_texels(scene, node, width, height, False, flip_normals, want=("normals", "uv", "node"), device=device)
+    level = shade_points(scene, tx.points, tx.normals, -tx.normals, tx.node, uvs=tx.uv, hit_flags=tx.flags, keys=keys)
+    level = _bake_dilate(scene, tx.flags, level, width, height, radius)
+    if _is_tensor(level):
+        import torch
+        a = torch.from_numpy(a).to(level.device)
+    total = level.clone() if _is_tensor(level) else level.copy()
+    for b in range(1, bounces + 1):
+        rgb = gather_maps_points(scene, tx.points, tx.normals, sample_dirs, [level.reshape(height, width, 4)], {int(node): 0}, rotations, bias, math.inf,
+                                 miss if b == 1 else (0.0, 0.0, 0.0), hit_flags=tx.flags, keys=keys)
+        nxt = total.clone() if _is_tensor(total) else total.copy()  # (alpha from L_0; the rgb of every texel is written below or left to the dilation)
+        nxt[:, :3] = a * rgb
+        level = _bake_dilate(scene, tx.flags, nxt, width, height, radius)
+        total[:, :3] = total[:, :3] + level[:, :3]
+    return total.reshape(height, width, 4)
 
 
 # ---- denoising a baked map: the a-trous joint-bilateral filter (include/nrays_abi.h: nrays_filter_texels_device) -----------------------------------------------

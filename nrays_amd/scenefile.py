@@ -137,6 +137,18 @@ class FileScene:
         from .scene import bake_indirect
         return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
 
+    def gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
+                           keys=None, want_counts=False):
+        """The light of baked maps at the closest hits of the hemisphere rays of caller-supplied points of this scene: scene.gather_maps_points(self, ...)."""
+        from .scene import gather_maps_points
+        return gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations, bias, max_toi, miss, hit_flags, keys, want_counts)
+
+    def bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations=None, bias=1e-3, miss=(0.0, 0.0, 0.0), dilate=2, flip_normals=False, keys=None,
+                     device=None):
+        """The multi-bounce light map of mesh node `node`: scene.bake_bounces(self, node, ...)."""
+        from .scene import bake_bounces
+        return bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations, bias, miss, dilate, flip_normals, keys, device)
+
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: scene.surface_texels(self, node, ...)."""
         from .scene import surface_texels
