@@ -1,0 +1,128 @@
+// batch_stage.h — how the arrays of a caller-batch call lie in the workspace's staging arena (TraceWorkspace::d_stage), and every family's table of them.
+// A family describes its arrays as a fixed table of columns; stage_layout() is the ONE computation of where they lie and how many bytes they take, so a
+// size cannot disagree with a layout.  batch_call.cpp turns the offsets into device pointers and copies; the families (ray_batches.hip, point_batches.hip,
+// texel_calls.hip, the probes of ray_order.hip) only fill tables and read a chunk's pointers by the indices below.
+// Needs <cstddef> and <cstdint> alone: the host compiler builds it for tests/test_batch_stage.py (tests/batch_stage_shim.cpp).
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace nrays {
+
+constexpr int kStageMaxColumns = 32; // the widest table: nrays_gather_maps_points with 16 maps (25 columns)
+enum : uint8_t { kStageIn = 1, kStageOut = 2, kStageInOut = 3 };
+
+// One array of a call.  `ptr`: the caller's array — host memory in the blocking form, device memory in the device form; null = absent (the kernel gets null).
+// A column holds item_bytes for every item of a chunk, uploaded / read back per chunk and advanced by the chunk's first item; a table (`table` = 1) holds
+// table_items items of the whole call, uploaded once.  `align`: of the column's start in the arena (16 for the value arrays the vec4 paths read).
+struct StageColumn { void* ptr; size_t item_bytes; size_t table_items; uint8_t dir, align, table; };
+
+inline StageColumn stage_in(const void* p, size_t item_bytes, uint8_t align = 8) { return StageColumn{const_cast<void*>(p), item_bytes, 0, kStageIn, align, 0}; }
+inline StageColumn stage_out(void* p, size_t item_bytes, uint8_t align = 8) { return StageColumn{p, item_bytes, 0, kStageOut, align, 0}; }
+inline StageColumn stage_inout(void* p, size_t item_bytes, uint8_t align = 8) { return StageColumn{p, item_bytes, 0, kStageInOut, align, 0}; }
+inline StageColumn stage_table(const void* p, size_t item_bytes, size_t items, uint8_t align = 8) { return StageColumn{const_cast<void*>(p), item_bytes, items, kStageIn, align, 1}; }
+
+inline size_t stage_column_bytes(const StageColumn& c, size_t cap) { return c.item_bytes * (c.table ? c.table_items : cap); }
+// A column the blocking form copies and hands to the kernel: the caller gave it, and it holds something.
+inline bool stage_present(const StageColumn& c) { return c.ptr && (!c.table || c.table_items); }
+
+// Offsets of the columns in an arena whose chunks hold up to `cap` items, and the arena's bytes.  Every column has its slot, present or not: the layout of a
+// family depends on its sizes alone.
+inline size_t stage_layout(const StageColumn* cols, int ncols, size_t cap, size_t* off) {
+    size_t at = 0;
+    for (int k = 0; k < ncols; ++k) {
+        const size_t a = cols[k].align;
+        at = (at + a - 1) / a * a;
+        off[k] = at;
+        at += stage_column_bytes(cols[k], cap);
+    }
+    return at;
+}
+
+// Points per chunk of the families that build num_dirs rays a point on the device: at most `chunk_rays` rays a chunk.
+inline uint32_t stage_point_chunk(uint32_t chunk_rays, uint32_t num_dirs) { const uint32_t c = chunk_rays / num_dirs; return c ? c : 1u; }
+
+// ---- the families' tables.  Within a table the `in` columns are in upload order, the `out` columns in read-back order, the tables in upload order. ----
+// Rays: origins and directions (nrays_debug_ray_order stages these two alone), then what each family adds.
+enum { kRayO, kRayD, kRayColumns };
+inline int ray_columns(StageColumn* c, const double* origins, const double* dirs) {
+    c[kRayO] = stage_in(origins, 24); c[kRayD] = stage_in(dirs, 24);
+    return kRayColumns;
+}
+enum { kTraceRefr = kRayColumns, kTraceKeys, kTraceEnergy, kTraceOut, kTraceColumns };
+inline int trace_columns(StageColumn* c, const double* origins, const double* dirs, const double* refr, const uint64_t* keys, const float* energy, float* out_rgb) {
+    ray_columns(c, origins, dirs);
+    c[kTraceRefr] = stage_in(refr, 8); c[kTraceKeys] = stage_in(keys, 8); c[kTraceEnergy] = stage_in(energy, 4); c[kTraceOut] = stage_out(out_rgb, 12);
+    return kTraceColumns;
+}
+enum { kIsectToi = kRayColumns, kIsectFilter, kIsectLit, kIsectColumns };
+inline int intersects_columns(StageColumn* c, const double* origins, const double* dirs, const double* max_toi, float* out_filter, uint32_t* out_lit) {
+    ray_columns(c, origins, dirs);
+    c[kIsectToi] = stage_in(max_toi, 8); c[kIsectFilter] = stage_out(out_filter, 12); c[kIsectLit] = stage_out(out_lit, 4);
+    return kIsectColumns;
+}
+enum { kCastMaxToi = kRayColumns, kCastToi, kCastNode, kCastNormal, kCastUv, kCastPrim, kCastFlags, kCastColumns };
+inline int cast_columns(StageColumn* c, const double* origins, const double* dirs, const double* max_toi, double* toi, int32_t* node, double* normal, double* uv, int32_t* prim,
+                        uint32_t* flags) {
+    ray_columns(c, origins, dirs);
+    c[kCastMaxToi] = stage_in(max_toi, 8);
+    c[kCastToi] = stage_out(toi, 8); c[kCastNode] = stage_out(node, 4); c[kCastNormal] = stage_out(normal, 24); c[kCastUv] = stage_out(uv, 16);
+    c[kCastPrim] = stage_out(prim, 4); c[kCastFlags] = stage_out(flags, 4);
+    return kCastColumns;
+}
+enum { kShadePoints, kShadeNormals, kShadeViews, kShadeUvs, kShadeNodes, kShadeHit, kShadeKeys, kShadeOut, kShadeColumns };
+inline int shade_columns(StageColumn* c, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags,
+                         const uint64_t* keys, float* out_rgba) {
+    c[kShadePoints] = stage_in(points, 24); c[kShadeNormals] = stage_in(normals, 24); c[kShadeViews] = stage_in(view_dirs, 24); c[kShadeUvs] = stage_in(uvs, 16);
+    c[kShadeNodes] = stage_in(nodes, 4); c[kShadeHit] = stage_in(hit_flags, 4); c[kShadeKeys] = stage_in(keys, 8); c[kShadeOut] = stage_out(out_rgba, 16);
+    return kShadeColumns;
+}
+// Points with a hemisphere of directions: the two tables and the points (nrays_debug_gather_order stages these alone), then what each family adds.
+enum { kPointDirs, kPointRotations, kPointPoints, kPointNormals, kPointHit, kPointKeys, kPointColumns };
+inline int point_columns(StageColumn* c, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, const double* points, const double* normals,
+                         const uint32_t* hit_flags, const uint64_t* keys) {
+    c[kPointDirs] = stage_table(dirs, 24, num_dirs); c[kPointRotations] = stage_table(rotations, 16, num_rotations);
+    c[kPointPoints] = stage_in(points, 24); c[kPointNormals] = stage_in(normals, 24); c[kPointHit] = stage_in(hit_flags, 4); c[kPointKeys] = stage_in(keys, 8);
+    return kPointColumns;
+}
+enum { kOccFilter = kPointColumns, kOccOpen, kOccColumns };
+inline int occlusion_columns(StageColumn* c, float* out_filter, uint32_t* out_open) { // (after point_columns)
+    c[kOccFilter] = stage_out(out_filter, 12); c[kOccOpen] = stage_out(out_open, 4);
+    return kOccColumns;
+}
+// out_floats: 3 (nrays_gather_points*) or 3 * bands^2 (nrays_gather_sh_points*).  ray_colours: nrays_debug_gather_sh_fold's input, 3 floats a ray; null elsewhere.
+enum { kGatherOut = kPointColumns, kGatherRays, kGatherColumns };
+inline int gather_columns(StageColumn* c, float* out, uint32_t out_floats, const float* ray_colours, uint32_t num_dirs) { // (after point_columns)
+    c[kGatherOut] = stage_out(out, 4 * (size_t)out_floats); c[kGatherRays] = stage_in(ray_colours, ray_colours ? 12 * (size_t)num_dirs : 0);
+    return kGatherColumns;
+}
+// map_texels[m], map_count[m]: the RGBA32F texels of map m and their number; column kMapsTexels + m.
+enum { kMapsRgb = kPointColumns, kMapsCounts, kMapsNodeMap, kMapsTexels };
+inline int gather_maps_columns(StageColumn* c, float* out_rgb, uint32_t* out_counts, const int32_t* node_map, uint32_t num_nodes, uint32_t num_maps, const void* const* map_texels,
+                               const size_t* map_count) { // (after point_columns)
+    c[kMapsRgb] = stage_out(out_rgb, 12); c[kMapsCounts] = stage_out(out_counts, 8); c[kMapsNodeMap] = stage_table(node_map, 4, num_nodes);
+    for (uint32_t m = 0; m < num_maps; ++m) c[kMapsTexels + m] = stage_table(map_texels[m], 16, map_count[m], 16);
+    return kMapsTexels + (int)num_maps;
+}
+// Lattices (one chunk of width * height items).
+enum { kTexelPoints, kTexelNormals, kTexelUv, kTexelNode, kTexelPrim, kTexelFlags, kTexelColumns };
+inline int surface_texel_columns(StageColumn* c, double* points, double* normals, double* uv, int32_t* node, int32_t* prim, uint32_t* flags) {
+    c[kTexelPoints] = stage_out(points, 24); c[kTexelNormals] = stage_out(normals, 24); c[kTexelUv] = stage_out(uv, 16);
+    c[kTexelNode] = stage_out(node, 4); c[kTexelPrim] = stage_out(prim, 4); c[kTexelFlags] = stage_out(flags, 4);
+    return kTexelColumns;
+}
+enum { kDilateFlagsIn, kDilateValues, kDilateSource, kDilateFlagsOut, kDilateColumns };
+inline int dilate_columns(StageColumn* c, const uint32_t* flags_in, float* values, uint32_t channels, int32_t* source, uint32_t* flags_out) {
+    c[kDilateFlagsIn] = stage_in(flags_in, 4); c[kDilateValues] = stage_inout(values, values ? 4 * (size_t)channels : 0, 16);
+    c[kDilateSource] = stage_out(source, 4); c[kDilateFlagsOut] = stage_out(flags_out, 4);
+    return kDilateColumns;
+}
+enum { kFilterPoints, kFilterNormals, kFilterValuesIn, kFilterValuesOut, kFilterFlags, kFilterColumns };
+inline int filter_columns(StageColumn* c, const double* points, const double* normals, const float* values_in, float* values_out, uint32_t channels, const uint32_t* flags_in) {
+    c[kFilterPoints] = stage_in(points, 24); c[kFilterNormals] = stage_in(normals, 24);
+    c[kFilterValuesIn] = stage_in(values_in, 4 * (size_t)channels, 16); c[kFilterValuesOut] = stage_out(values_out, 4 * (size_t)channels, 16);
+    c[kFilterFlags] = stage_in(flags_in, 4);
+    return kFilterColumns;
+}
+
+} // namespace nrays

@@ -1,5 +1,5 @@
 // bounce.h — the rounds over the queue of second children (double-branching scenes): what frame_path.hip runs after a sample batch's
-// k_primary and ray_order.hip after a chunk's k_trace_rays.  bounce.hip holds k_bounce and k_fold_fixed.  Host only.
+// k_primary, ray_batches.hip after a chunk's k_trace_rays and point_batches.hip after a chunk's gather kernel.  bounce.hip holds k_bounce and k_fold_fixed.  Host only.
 #pragma once
 #include "scene_handle.h"
 

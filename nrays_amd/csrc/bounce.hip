@@ -1,4 +1,4 @@
-// bounce.hip — the continuation queue's rounds, shared by the frames (frame_path.hip) and the caller-ray batches (ray_order.hip):
+// bounce.hip — the continuation queue's rounds, shared by the frames (frame_path.hip) and the caller-ray batches (ray_batches.hip, point_batches.hip):
 //   k_bounce      rounds over the compacted HBM queue (double-branching scenes only): the per-ray work of k_primary, the weighted contribution added to
 //                 the pixel's 64-bit fixed-point sum (order-independent), second children appended to the next round's queue;
 //   k_fold_fixed  adds those sums to the frame (or to a chunk's colours) after the rounds of a sample batch.

@@ -1,5 +1,5 @@
 // gather_inst.hip — the k_gather_points permutations (ray_batch_kernel.h), in a translation unit of their own: every one instantiates trace_chain, the
-// expensive template, and compiles beside ray_order.hip (which launches them through launch_gather_points) instead of behind it.
+// expensive template, and compiles beside point_batches.hip (which launches them through launch_gather_points) instead of behind it.
 // The permutations are trace_chunk's — kFeatMesh for scenes of opaque meshes, kFeatAll otherwise, the kernel that counts everything and skips nothing for
 // no_elide scenes — times the lanes per point of k_occlusion_points (2^0, 2^3, 2^6).
 #include <hip/hip_runtime.h>

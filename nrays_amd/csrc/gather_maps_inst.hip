@@ -1,5 +1,5 @@
-// gather_maps_inst.hip — the k_gather_maps_points permutations (gather_maps_kernel.h), in a translation unit of their own beside ray_order.hip, which launches them
-// through launch_gather_maps_points.  The permutations are cast_chunk's — kFeatMesh for scenes of meshes only, kFeatAll otherwise — times the lanes per point of
+// gather_maps_inst.hip — the k_gather_maps_points permutations (gather_maps_kernel.h), in a translation unit of their own beside point_batches.hip, which launches them
+// through launch_gather_maps_points.  The permutations are nrays_cast_rays' — kFeatMesh for scenes of meshes only, kFeatAll otherwise — times the lanes per point of
 // k_occlusion_points (2^0, 2^3, 2^6).
 #include <hip/hip_runtime.h>
 

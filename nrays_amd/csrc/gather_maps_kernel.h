@@ -2,7 +2,7 @@
 // into one mean colour per point — one diffuse bounce of a light-map baker, on the device.  The rays are k_occlusion_points' (occlusion_frame / occlusion_dir),
 // the query is k_cast_rays' (ungated traversal, resolve_hit, the gated repeat), the sample is the materials' (tex_sample) and the fold is k_occlusion_points'
 // (2^LP lanes a point, added in the order of the directions through __shfl).  The definition is include/nrays_abi.h (NraysGatherMapsParams).
-// Templates and inline device code only: gather_maps_inst.hip instantiates the kernel, ray_order.hip launches it through launch_gather_maps_points.
+// Templates and inline device code only: gather_maps_inst.hip instantiates the kernel, point_batches.hip launches it through launch_gather_maps_points.
 #pragma once
 #include "../../include/nrays_abi.h"
 #include "ray_batch_kernel.h"
@@ -57,7 +57,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_maps_po
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
     constexpr uint32_t kLanes = 1u << LP;
-    const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: ray_order.hip's chunks)
+    const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
     const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count

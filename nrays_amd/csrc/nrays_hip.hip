@@ -1,6 +1,6 @@
 // nrays_hip.hip — the handle behind the C ABI of include/nrays_abi.h: its lifetime (nrays_scene_create / _destroy), what it reports
 // (stats, tile costs, the debug probes), the blocking renders, and the last error.  The frame path lives in frame_path.hip, the rounds
-// over the continuation queue in bounce.hip, the caller-ray batches in ray_order.hip, the staged path in wavefront.hip.
+// over the continuation queue in bounce.hip, the caller batches in ray_batches.hip, point_batches.hip and texel_calls.hip (their driver: batch_call.cpp; their reorder: ray_order.hip), the staged path in wavefront.hip.
 //   k_quantize_rgb8  a finished frame as 8-bit RGB (nrays_render_rgb8).
 //   k_untile         un-permutes gathered multi-GPU tile buffers.
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // primary_kernel.h — k_primary, the persistent-grid megakernel of the trace loop (replaces the pixel loop of scene::render,
-// src/scene.rs:49-116), with the helpers it shares with k_bounce (bounce.hip) and the caller-ray kernels (ray_order.hip).  Device code only: the
+// src/scene.rs:49-116), with the helpers it shares with k_bounce (bounce.hip) and the caller-ray kernels (ray_batch_kernel.h).  Device code only: the
 // permutations are instantiated by primary_inst.hip, one translation unit per group (NR_PRIMARY_GROUP), so that the ~57
 // kernels compile side by side; frame_path.hip holds the host side and the small kernels.
 #pragma once

@@ -1,11 +1,12 @@
 // ray_batch_kernel.h — the kernels of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device*, nrays_cast_rays*): k_trace_rays,
 // k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
-// write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_order.hip launches both forms.  One body
+// write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_batches.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
 // k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value;
 // k_gather_points (nrays_gather_points*) runs Scene::trace on the same rays and folds the colours (instantiated in gather_inst.hip);
 // k_gather_pairs_ordered traces the (point, direction) pairs of a reordered gather chunk in bin order (nrays_gather_points*_ex; gather_order_inst.hip).
-// Templates and inline device code only: ray_order.hip, gather_inst.hip and gather_order_inst.hip include this header.
+// Templates and inline device code only: ray_batches.hip (which instantiates every kernel here that has no unit of its own), point_batches.hip, ray_order.hip,
+// gather_inst.hip and gather_order_inst.hip include this header.
 #pragma once
 #include "primary_kernel.h"
 
@@ -236,7 +237,7 @@ NR_DEV d3 occlusion_dir(const OccFrame& f, bool rotate, double lx, double ly, do
 // order of the directions — f32 sum of the filters of the rays that got through, then ONE division by (float)num_dirs; out_open[i] counts them.
 // 2^LP lanes serve a point: lane `sub` takes the directions j = sub (mod 2^LP), and after every round the 2^LP partial values are added in the order of j
 // through __shfl, every lane of the point keeping the same running sum — the sequential f32 sum, so the result does not depend on LP.  The lanes of a point share
-// its origin; ray_order.hip gives a point as many lanes as its directions fill (measured: profiles/occlusion_rate.json).  LP = 0 is lane = point: no shuffle, and
+// its origin; the host (batch_call.cpp: occlusion_lanes_log2) gives a point as many lanes as its directions fill (measured: profiles/occlusion_rate.json).  LP = 0 is lane = point: no shuffle, and
 // direction j is wave-uniform, so the compiler can fetch its three doubles with scalar loads.
 // A point whose flag bit 0 is clear is skipped: zeros, no traversal, neither its point nor its normal read.  NULL keys: key_base + i.
 template <int FEAT, int LP>
@@ -250,7 +251,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
     constexpr uint32_t kLanes = 1u << LP;
-    const uint32_t k = P.num_dirs, slots = n << LP; // (n <= 2^22: ray_order.hip's chunks)
+    const uint32_t k = P.num_dirs, slots = n << LP; // (n <= 2^22: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
         const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
@@ -301,7 +302,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
 // doubles' worth of registers stay live across trace_chain instead of the frame's 28 (profiles/gather_kres_change.txt, profiles/gather_isa_scratch.txt).
 // ray_out != nullptr (double-branching scenes): nothing is folded here.  Ray j of point i is "pixel" i * num_dirs + j of the chunk and its chain's sum goes to
 // ray_out[3 * pixel ..] (zeros for a skipped point), exactly as k_trace_rays stores a ray's; the k_bounce rounds and k_fold_fixed add the queued second children per
-// RAY, as for a chunk of nrays_trace_rays, and k_gather_fold (ray_order.hip) then runs the sequential fold — so the result is the definition's bit for bit there too.
+// RAY, as for a chunk of nrays_trace_rays, and k_gather_fold (point_batches.hip) then runs the sequential fold — so the result is the definition's bit for bit there too.
 // A point whose flag bit 0 is clear is skipped: zeros, no traversal, neither its point nor its normal read.  NULL keys: key_base + i.
 struct GatherSpec { uint32_t num_dirs, num_rotations; double bias; float energy; uint32_t max_depth, keyed; };
 
@@ -316,7 +317,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
     constexpr uint32_t kLanes = 1u << LP;
-    const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: ray_order.hip's chunks)
+    const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
     const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
@@ -360,14 +361,14 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(
 }
 
 // The arguments of one k_gather_points launch.  The instantiations (trace_chain is the expensive template) are compiled in gather_inst.hip, a translation unit of
-// their own beside ray_order.hip, which calls launch_gather_points: false = no such permutation.
+// their own beside point_batches.hip, which calls launch_gather_points: false = no such permutation.
 struct GatherLaunch {
     uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys;
     unsigned long long key_base; GatherSpec spec; const double* dirs; const double* rotations; float* out; float* ray_out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
 };
 bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
 
-// ---- the reordered form of a gather chunk (nrays_gather_points*_ex with NRAYS_RAYS_UNORDERED; host side and the binning kernels: ray_order.hip) -------------------
+// ---- the reordered form of a gather chunk (nrays_gather_points*_ex with NRAYS_RAYS_UNORDERED; host side: point_batches.hip; the binning kernels: ray_order.hip) -------------------
 // A chunk's (point, direction) pairs — pair i * num_dirs + j is ray j of point i — are binned by ray_key.h's key and traced in bin order, one lane per pair; the
 // rays exist in registers only, rebuilt from (i, j) wherever they are needed (bounds, keys, trace).  What crosses memory per ray is the sort state (key, rank,
 // order: 16 bytes) and the colour (12 bytes), both of ONE chunk, in the handle's workspace.

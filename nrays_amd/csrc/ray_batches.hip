@@ -1,0 +1,349 @@
+// ray_batches.hip — the caller-batch families that take rays or surface points as arrays, each a check, a column table (batch_stage.h) and a chunk launch run by
+// the driver of batch_call.h: nrays_trace_rays* (+ _ex), nrays_intersects_rays_device (+ _ex), nrays_cast_rays*, nrays_shade_points*; their kernels are the templates of
+// ray_batch_kernel.h, instantiated here, as is k_occlusion_points for point_batches.hip (launch_occlusion_points).  Also two probes with kernels of their own: nrays_debug_cast_batch (k_cast_batch) and nrays_debug_box_cull (k_box_cull).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cfloat>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/nrays_abi.h"
+#include "batch_call.h"
+#include "bounce.h"
+#include "ray_batch_kernel.h"
+#include "scene_handle.h"
+
+namespace nrays {
+
+// (FEAT: kFeatAll, or kFeatMesh for scenes of opaque TriMesh nodes only — the permutation whose node phases end by quorum in
+// hair-like meshes, so that the independent fixtures also cover that path.)
+// nrays_debug_cast_batch: the closest-hit query with the deferred exact gates exactly as shade_hit runs it (ungated traversal, the
+// winner checked against the reference's AABB gates, fully gated repeat for knife-edge rays), or the shadow query, on rays from memory.
+template <int FEAT>
+__global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DScene S, uint32_t mode, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                                              const double* __restrict__ max_toi, NraysCastResult* __restrict__ out, uint32_t* spill) {
+    __shared__ uint32_t lds_stack[kLdsStack * kBlock];
+    Stack st; st.setup(lds_stack, spill, nullptr);
+    Cnt cnt; cnt.zero();
+    for (uint32_t base = blockIdx.x * kBlock; base < n; base += gridDim.x * kBlock) {
+        const uint32_t i = base + threadIdx.x;
+        if (i >= n) continue;
+        const d3 o = D3(ro[3 * (size_t)i], ro[3 * (size_t)i + 1], ro[3 * (size_t)i + 2]), d = D3(rd[3 * (size_t)i], rd[3 * (size_t)i + 1], rd[3 * (size_t)i + 2]);
+        NraysCastResult r; r.toi = 0.0; r.normal[0] = r.normal[1] = r.normal[2] = 0.0; r.uv[0] = r.uv[1] = 0.0; r.node_id = -1; r.flags = 0u;
+        Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
+        if (mode == 1u) {
+            const bool blocked = traverse<true, false, FEAT>(S, st, o, d, max_toi[i], hit, filter, cnt);
+            r.flags = blocked ? 1u : 0u; r.normal[0] = filter.x; r.normal[1] = filter.y; r.normal[2] = filter.z;
+        } else {
+            Isect is; uint32_t node_id = 0; bool gated = false, any = false;
+            for (;;) {
+                any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
+                if (!any) break;
+                if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
+                gated = true;
+            }
+            if (any) {
+                r.toi = hit.t; r.normal[0] = is.n.x; r.normal[1] = is.n.y; r.normal[2] = is.n.z; r.uv[0] = is.u; r.uv[1] = is.v;
+                r.node_id = (int32_t)node_id; r.flags = 1u | (is.has_uv ? 2u : 0u);
+            }
+        }
+        out[i] = r;
+    }
+}
+
+// nrays_debug_box_cull: ONE node visit of the traversals on a case from memory — make_rayf, best_f32, the fetch of the node's planes, box_keys4 and,
+// for a ray with an f32-zero component, zero_axis_cull: the product functions themselves, in the order traverse() calls them.  Case i reads node i.
+// uniform = 0: a case per lane, planes through load_planes.  uniform = 1: a case per WAVE (all its lanes compute the same case, so that they share
+// the node and the direction signs as load_planes_uniform requires; the first lane writes), planes through the scalar fetch.
+__global__ void __launch_bounds__(kBlock) k_box_cull(const BvhNode* __restrict__ nodes, uint32_t uniform, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
+                                                     const double* __restrict__ best, float* __restrict__ keys, uint32_t* __restrict__ bits, float* __restrict__ inv32) {
+    const uint32_t tid = blockIdx.x * kBlock + threadIdx.x, threads = gridDim.x * kBlock;
+    const uint32_t step = uniform ? threads >> 6 : threads;
+    for (uint32_t i = uniform ? tid >> 6 : tid; i < n; i += step) {
+        const d3 o = D3(ro[3 * (size_t)i], ro[3 * (size_t)i + 1], ro[3 * (size_t)i + 2]), d = D3(rd[3 * (size_t)i], rd[3 * (size_t)i + 1], rd[3 * (size_t)i + 2]);
+        const RayF rf = make_rayf(o, d);
+        const float btf = best_f32(best[i]);
+        float k0, k1, k2, k3;
+        if (uniform) {
+            const uint32_t ukey = (uint32_t)__builtin_amdgcn_readfirstlane((int)((i << 7) | rf.bits));
+            const NodePlanes np = load_planes_uniform(nodes, ukey);
+            box_keys4(np, rf, btf, k0, k1, k2, k3);
+            if ((rf.bits & 7u)) zero_axis_cull((rf.bits & 7u), o, np, k0, k1, k2, k3);
+        } else {
+            const NodePlanes np = load_planes(nodes, (int32_t)i, rf);
+            box_keys4(np, rf, btf, k0, k1, k2, k3);
+            if ((rf.bits & 7u)) zero_axis_cull((rf.bits & 7u), o, np, k0, k1, k2, k3);
+        }
+        if (uniform && (threadIdx.x & 63u)) continue;
+        keys[4 * (size_t)i] = k0; keys[4 * (size_t)i + 1] = k1; keys[4 * (size_t)i + 2] = k2; keys[4 * (size_t)i + 3] = k3;
+        bits[i] = rf.bits;
+        inv32[3 * (size_t)i] = rf.ix; inv32[3 * (size_t)i + 1] = rf.iy; inv32[3 * (size_t)i + 2] = rf.iz;
+    }
+}
+
+// ---- nrays_trace_rays*: Scene::trace on caller-supplied rays (scene.rs:147-193) ----------------------------------------------------------------------
+// One chunk (n <= kTraceChunk) of nrays_trace_rays*: k_trace_rays (`order`: its ordered form, lane j traces ray order[j]), then — double-branching scenes only — the k_bounce rounds of the
+// queued second children and k_fold_fixed, as a frame runs them for a sample batch (bounce.h: run_bounce_rounds).
+static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
+                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream, const uint32_t* order) {
+    const bool queued = sc->facts.host.any_double_branch;
+    if (queued) { // a frame's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
+        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
+        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
+        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, (size_t)n * 3, stream);
+        if (rc != NRAYS_OK) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
+    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
+    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
+    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    const uint32_t keyed = sc->facts.host.any_area_light ? 1u : 0u;
+#define NR_TRACE_LAUNCH(STATS, FEAT)                                                                                                                                                     \
+    do {                                                                                                                                                                                 \
+        if (order) hipLaunchKernelGGL((k_trace_rays_ordered<STATS, FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill); \
+        else hipLaunchKernelGGL((k_trace_rays<STATS, FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill); \
+    } while (0)
+    // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
+    if (sc->facts.d.no_elide) NR_TRACE_LAUNCH(true, kFeatAll);
+    else if (shading_feat(sc) == (int)kFeatMesh) NR_TRACE_LAUNCH(false, kFeatMesh);
+    else NR_TRACE_LAUNCH(false, kFeatAll);
+#undef NR_TRACE_LAUNCH
+    HIP_TRY(hipGetLastError());
+    if (!queued) return NRAYS_OK;
+    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, sc->facts.d.no_elide != 0u, max_depth, out, (size_t)n * 3, sc->facts.num_cus};
+    uint32_t overflowed = 0u;
+    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
+    if (rc != NRAYS_OK) return rc;
+    if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some traced colours are incomplete");
+    return NRAYS_OK;
+}
+static int trace_rays_impl(NraysScene* sc, uint32_t n, const double* o, const double* d, const double* refr, const float* energy, const uint64_t* keys, uint32_t max_depth,
+                           float* out, uint32_t flags, bool staged, hipStream_t stream) {
+    if (!sc || !o || !d || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kTraceColumns];
+    trace_columns(cols, o, d, refr, keys, energy, out);
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
+        const double *co = (const double*)c[kRayO], *cd = (const double*)c[kRayD];
+        const uint32_t* order = nullptr;
+        const int rc = chunk_order(sc, b.w, reorder, nc, co, cd, b.stream, &order);
+        if (rc != NRAYS_OK) return rc;
+        return trace_chunk(sc, b.w, nc, co, cd, (const double*)c[kTraceRefr], (const float*)c[kTraceEnergy], (const unsigned long long*)c[kTraceKeys], key_base, max_depth,
+                           (float*)c[kTraceOut], b.stream, order);
+    };
+    return batch_run(sc, staged, stream, cols, kTraceColumns, n, kTraceChunk, "trace batch", launch);
+}
+
+// ---- nrays_intersects_rays_device*: Scene::intersects_ray (device form only) -----------------------------------------------------------------------------
+static int intersects_rays_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter, uint32_t* out_lit, uint32_t flags,
+                                hipStream_t stream) {
+    if (!sc || !origins || !dirs || !max_toi || !out_filter || !out_lit) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kIsectColumns];
+    intersects_columns(cols, origins, dirs, max_toi, out_filter, out_lit);
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD], *t = (const double*)c[kIsectToi];
+        float* filter = (float*)c[kIsectFilter]; uint32_t* lit = (uint32_t*)c[kIsectLit];
+        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const uint32_t* order = nullptr;
+        const int rc = chunk_order(sc, b.w, reorder, nc, o, d, b.stream, &order);
+        if (rc != NRAYS_OK) return rc;
+#define NR_ISECT_LAUNCH(FEAT)                                                                                                                                                \
+    do {                                                                                                                                                                     \
+        if (order) hipLaunchKernelGGL((k_intersects_rays_ordered<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, order, o, d, t, filter, lit, b.w->d_spill); \
+        else hipLaunchKernelGGL((k_intersects_rays<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, o, d, t, filter, lit, b.w->d_spill);                      \
+    } while (0)
+        if (traversal_feat(sc) == (int)kFeatMesh) NR_ISECT_LAUNCH(kFeatMesh); else NR_ISECT_LAUNCH(kFeatAll);
+#undef NR_ISECT_LAUNCH
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e));
+        return (int)NRAYS_OK;
+    };
+    return batch_run(sc, false, stream, cols, kIsectColumns, n, kTraceChunk, "intersects batch", launch);
+}
+
+// ---- nrays_cast_rays*: the closest hit of caller-supplied rays: toi and node always, the rest where the caller wants them ---------------------------------------
+static int cast_rays_impl(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node, double* out_normal,
+                          double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, bool staged, hipStream_t stream) {
+    if (!sc || !origins || !dirs || !out_toi || !out_node) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_ray_flags(flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kCastColumns];
+    cast_columns(cols, origins, dirs, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags);
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    // One chunk: the reorder when it is due, then k_cast_rays or its ordered form.
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD], *t = (const double*)c[kCastMaxToi];
+        double *toi = (double*)c[kCastToi], *normal = (double*)c[kCastNormal], *uv = (double*)c[kCastUv];
+        int32_t *node = (int32_t*)c[kCastNode], *prim = (int32_t*)c[kCastPrim]; uint32_t* hit = (uint32_t*)c[kCastFlags];
+        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const uint32_t* order = nullptr;
+        const int rc = chunk_order(sc, b.w, reorder, nc, o, d, b.stream, &order);
+        if (rc != NRAYS_OK) return rc;
+#define NR_CAST_LAUNCH(FEAT)                                                                                                                                                              \
+    do {                                                                                                                                                                                  \
+        if (order) hipLaunchKernelGGL((k_cast_rays_ordered<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, order, o, d, t, toi, node, normal, uv, prim, hit, b.w->d_spill); \
+        else hipLaunchKernelGGL((k_cast_rays<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, o, d, t, toi, node, normal, uv, prim, hit, b.w->d_spill);                      \
+    } while (0)
+        if (traversal_feat(sc) == (int)kFeatMesh) NR_CAST_LAUNCH(kFeatMesh); else NR_CAST_LAUNCH(kFeatAll);
+#undef NR_CAST_LAUNCH
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_cast_rays: ") + hipGetErrorString(e));
+        return (int)NRAYS_OK;
+    };
+    return batch_run(sc, staged, stream, cols, kCastColumns, n, kTraceChunk, "cast batch", launch);
+}
+
+// ---- nrays_shade_points*: Material::compute on caller-supplied surface points (material.rs:8-16, phong_material.rs:72-151) -----------------------
+// kFeatAll is right for every scene (it holds kFeatMultiSample: the shadow rays are traced inside the light loop); a scene with a non-finite
+// light / colour / texel gets the kernel that skips nothing, as its renders, with the batch's own counter block.
+static int shade_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
+                             const uint32_t* hit_flags, const uint64_t* keys, float* out, uint32_t flags, bool staged, hipStream_t stream) {
+    if (!sc || !points || !normals || !view_dirs || !nodes || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_shade_points: flags must be 0");
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kShadeColumns];
+    shade_columns(cols, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
+        const double *p = (const double*)c[kShadePoints], *nm = (const double*)c[kShadeNormals], *v = (const double*)c[kShadeViews], *uv = (const double*)c[kShadeUvs];
+        const int32_t* node = (const int32_t*)c[kShadeNodes]; const uint32_t* hit = (const uint32_t*)c[kShadeHit]; const unsigned long long* k = (const unsigned long long*)c[kShadeKeys];
+        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const uint32_t num_nodes = (uint32_t)sc->facts.host.shade.size();
+        if (sc->facts.d.no_elide) hipLaunchKernelGGL((k_shade_points<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, num_nodes, p, nm, v, uv, node, hit, k, key_base, (float*)c[kShadeOut], b.w->d_counters, b.w->d_spill);
+        else hipLaunchKernelGGL((k_shade_points<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, num_nodes, p, nm, v, uv, node, hit, k, key_base, (float*)c[kShadeOut], b.w->d_counters, b.w->d_spill);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_shade_points: ") + hipGetErrorString(e));
+        return (int)NRAYS_OK;
+    };
+    return batch_run(sc, staged, stream, cols, kShadeColumns, n, kTraceChunk, "shade batch", launch);
+}
+
+// k_occlusion_points (nrays_occlusion_points*, point_batches.hip) is instantiated in this unit, beside the other traversal kernels: in a unit without them the compiler
+// allocates and schedules its LP = 3 and 6 forms differently (profiles/README.md, batch_driver_kres_*).  feat: kFeatMesh or kFeatAll; lp: 0, 3 or 6.
+void launch_occlusion_points(int feat, int lp, uint32_t grid, hipStream_t stream, const DScene& S, uint32_t nc, const double* points, const double* normals, const uint32_t* hit_flags,
+                             const unsigned long long* keys, unsigned long long key_base, const OcclusionSpec& spec, const double* dirs, const double* rotations, float* out_filter,
+                             uint32_t* out_open, uint32_t* spill) {
+#define NR_OCC_LAUNCH(FEAT, LP) hipLaunchKernelGGL((k_occlusion_points<FEAT, LP>), dim3(grid), dim3(kBlock), 0, stream, S, nc, points, normals, hit_flags, keys, key_base, spec, dirs, rotations, out_filter, out_open, spill)
+    if (feat == (int)kFeatMesh) { if (lp == 0) NR_OCC_LAUNCH(kFeatMesh, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatMesh, 3); else NR_OCC_LAUNCH(kFeatMesh, 6); }
+    else { if (lp == 0) NR_OCC_LAUNCH(kFeatAll, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatAll, 3); else NR_OCC_LAUNCH(kFeatAll, 6); }
+#undef NR_OCC_LAUNCH
+}
+
+} // namespace nrays
+
+using namespace nrays;
+
+extern "C" {
+
+int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* max_toi, NraysCastResult* out) {
+    if (!sc || !origins || !dirs || !out || mode > 1u || (mode == 1u && !max_toi)) return set_last_error(NRAYS_ERR_BAD_ARG, "bad cast-batch arguments");
+    if (n == 0) return NRAYS_OK;
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    if (sc->last.have) HIP_TRY(hipStreamSynchronize(sc->last.stream));
+    { const int rs = ensure_spill(sc, &sc->buf.d_spill); if (rs != NRAYS_OK) return rs; }
+    double *d_o = nullptr, *d_d = nullptr, *d_t = nullptr; NraysCastResult* d_r = nullptr;
+    auto release = [&]() { if (d_o) (void)hipFree(d_o); if (d_d) (void)hipFree(d_d); if (d_t) (void)hipFree(d_t); if (d_r) (void)hipFree(d_r); };
+#define CAST_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    const size_t vb = (size_t)n * 3 * sizeof(double);
+    CAST_TRY(hipMalloc((void**)&d_o, vb)); CAST_TRY(hipMalloc((void**)&d_d, vb)); CAST_TRY(hipMalloc((void**)&d_r, (size_t)n * sizeof(NraysCastResult)));
+    CAST_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CAST_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
+    if (mode == 1u) { CAST_TRY(hipMalloc((void**)&d_t, (size_t)n * sizeof(double))); CAST_TRY(hipMemcpy(d_t, max_toi, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
+    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+    CAST_TRY(sc->buf.own_stream ? hipSuccess : hipStreamCreate(&sc->buf.own_stream));
+    if (traversal_feat(sc) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
+    else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
+    CAST_TRY(hipGetLastError());
+    CAST_TRY(hipStreamSynchronize(sc->buf.own_stream));
+    CAST_TRY(hipMemcpy(out, d_r, (size_t)n * sizeof(NraysCastResult), hipMemcpyDeviceToHost));
+#undef CAST_TRY
+    release();
+    return NRAYS_OK;
+}
+
+int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* best, const float* boxes, const uint32_t* slots,
+                         float* keys, uint32_t* bits, float* inv32) {
+    if (!origins || !dirs || !best || !boxes || !slots || !keys || !bits || !inv32 || mode > 1u) return set_last_error(NRAYS_ERR_BAD_ARG, "bad box-cull arguments");
+    if (n > (1u << 24)) return set_last_error(NRAYS_ERR_BAD_ARG, "box-cull: more than 2^24 cases"); // (node index << 7 in 32 bits, as the scenes: scene_build.cpp)
+    if (n == 0) return NRAYS_OK;
+    for (uint32_t i = 0; i < n; ++i) if (slots[i] > 3u) return set_last_error(NRAYS_ERR_BAD_ARG, "box-cull: child slot above 3");
+    std::vector<BvhNode> nodes;
+    try { nodes.resize(n); } catch (const std::bad_alloc&) { return set_last_error(NRAYS_ERR_OOM, "box-cull nodes"); }
+    const float absent_mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, absent_mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+    for (uint32_t i = 0; i < n; ++i) {
+        BvhNode& nd = nodes[i];
+        for (int k = 0; k < 4; ++k) { nd.slot[5][k] = 0.0f; nd.set_box(k, absent_mn, absent_mx); nd.children()[k] = kEmptyChild; }
+        nd.set_box((int)slots[i], boxes + 6 * (size_t)i, boxes + 6 * (size_t)i + 3);
+    }
+    BvhNode* d_n = nullptr; double *d_o = nullptr, *d_d = nullptr, *d_b = nullptr; float *d_k = nullptr, *d_i = nullptr; uint32_t* d_bits = nullptr;
+    auto release = [&]() { for (void* q : {(void*)d_n, (void*)d_o, (void*)d_d, (void*)d_b, (void*)d_k, (void*)d_i, (void*)d_bits}) if (q) (void)hipFree(q); };
+#define CULL_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+    const size_t vb = (size_t)n * 3 * sizeof(double);
+    CULL_TRY(hipMalloc((void**)&d_n, (size_t)n * sizeof(BvhNode))); CULL_TRY(hipMalloc((void**)&d_o, vb)); CULL_TRY(hipMalloc((void**)&d_d, vb));
+    CULL_TRY(hipMalloc((void**)&d_b, (size_t)n * sizeof(double))); CULL_TRY(hipMalloc((void**)&d_k, (size_t)n * 4 * sizeof(float)));
+    CULL_TRY(hipMalloc((void**)&d_i, (size_t)n * 3 * sizeof(float))); CULL_TRY(hipMalloc((void**)&d_bits, (size_t)n * sizeof(uint32_t)));
+    CULL_TRY(hipMemcpy(d_n, nodes.data(), (size_t)n * sizeof(BvhNode), hipMemcpyHostToDevice));
+    CULL_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CULL_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
+    CULL_TRY(hipMemcpy(d_b, best, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    const uint64_t threads = mode == 1u ? (uint64_t)n * 64u : (uint64_t)n;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((threads + kBlock - 1) / kBlock, (uint64_t)kMaxGrid);
+    hipLaunchKernelGGL(k_box_cull, dim3(grid), dim3(kBlock), 0, (hipStream_t)0, (const BvhNode*)d_n, mode, n, (const double*)d_o, (const double*)d_d, (const double*)d_b, d_k, d_bits, d_i);
+    CULL_TRY(hipGetLastError());
+    CULL_TRY(hipDeviceSynchronize());
+    CULL_TRY(hipMemcpy(keys, d_k, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost)); CULL_TRY(hipMemcpy(bits, d_bits, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    CULL_TRY(hipMemcpy(inv32, d_i, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost));
+#undef CULL_TRY
+    release();
+    return NRAYS_OK;
+}
+
+int nrays_trace_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                            uint32_t max_depth, float* out_rgb, void* hip_stream) {
+    return trace_rays_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u, false, (hipStream_t)hip_stream);
+}
+int nrays_trace_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                               uint32_t max_depth, float* out_rgb, uint32_t flags, void* hip_stream) {
+    return trace_rays_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_trace_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                     uint32_t max_depth, float* out_rgb) {
+    return trace_rays_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, 0u, true, nullptr);
+}
+int nrays_trace_rays_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* refr, const float* energy, const uint64_t* keys,
+                        uint32_t max_depth, float* out_rgb, uint32_t flags) {
+    return trace_rays_impl(sc, n, origins, dirs, refr, energy, keys, max_depth, out_rgb, flags, true, nullptr);
+}
+
+int nrays_intersects_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                 uint32_t* out_lit, void* hip_stream) {
+    return intersects_rays_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, 0u, (hipStream_t)hip_stream);
+}
+int nrays_intersects_rays_device_ex(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, float* out_filter,
+                                    uint32_t* out_lit, uint32_t flags, void* hip_stream) {
+    return intersects_rays_impl(sc, n, origins, dirs, max_toi, out_filter, out_lit, flags, (hipStream_t)hip_stream);
+}
+
+int nrays_cast_rays_device(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node,
+                           double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream) {
+    return cast_rays_impl(sc, n, origins, dirs, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_cast_rays(NraysScene* sc, uint32_t n, const double* origins, const double* dirs, const double* max_toi, double* out_toi, int32_t* out_node,
+                    double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags) {
+    return cast_rays_impl(sc, n, origins, dirs, max_toi, out_toi, out_node, out_normal, out_uv, out_prim, out_flags, flags, true, nullptr);
+}
+
+int nrays_shade_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
+                              const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags, void* hip_stream) {
+    return shade_points_impl(sc, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_shade_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
+                       const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags) {
+    return shade_points_impl(sc, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, flags, true, nullptr);
+}
+
+} // extern "C"

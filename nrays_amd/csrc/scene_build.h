@@ -16,7 +16,7 @@ struct HostTexture {
     std::vector<uint8_t> bytes;   // copy of the texel data
 };
 
-// Where the surface of a TriMesh node lies in the flattened scene (nrays_surface_texels*, ray_order.hip): the leaf-ordered records of the closest-hit BLAS that
+// Where the surface of a TriMesh node lies in the flattened scene (nrays_surface_texels*, texel_calls.hip): the leaf-ordered records of the closest-hit BLAS that
 // holds it — a BLAS may merge several nodes (TriRec::node_id tells them apart) and may hold a triangle several times after pre-splitting — and its isometry.
 struct NodeSurface {
     uint32_t first = 0, count = 0; // records [first, first + count) of DScene::tris / triuvs; count 0: a mesh without triangles

@@ -1,6 +1,6 @@
 // scene_handle.h — the scene handle behind the C ABI (NraysScene) and what the library's translation units share
-// around it.  Host only; frame_path.hip owns the megakernel path (k_primary), wavefront.hip the staged path, ray_order.hip the
-// caller-ray batches, nrays_hip.hip the handle's lifetime.
+// around it.  Host only; frame_path.hip owns the megakernel path (k_primary), wavefront.hip the staged path, batch_call.cpp the
+// caller batches' workspace and driver (their families: ray_batches.hip, point_batches.hip, texel_calls.hip; the reorder: ray_order.hip), nrays_hip.hip the handle's lifetime.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -53,7 +53,7 @@ struct FramePlan {
 constexpr int kNumCounts = kMaxGenerations + 2 + 8; // queue round counters + 8 per-XCD work counters
 constexpr int kMaxGrid = 2048;     // upper bound of the persistent grid (the launch uses CUs x waves/SIMD workgroups)
 
-// Workspace of the caller-ray batches (nrays_trace_rays*, nrays_intersects_rays_device; ray_order.hip): created on first use, grown
+// Workspace of the caller batches (nrays_trace_rays* and every later family; batch_call.cpp): created on first use, grown
 // only when a chunk needs more, freed with the handle.  It shares no device memory with the renders, so that a batch leaves their
 // per-frame state (queues, counters, fixed-point sums, scheduling state) exactly as it found it.
 constexpr uint32_t kTraceChunk = 1u << 22; // rays per chunk of a batch: bounds the queues and sums below for any batch size
@@ -66,7 +66,7 @@ struct TraceWorkspace {
     uint32_t* d_counts = nullptr;                           // kTraceCountWords
     DeviceCounters* d_counters = nullptr;                   // sink of the kernels' ray-class counters (never reported)
     uint32_t* d_spill = nullptr;                            // traversal-stack spill region of the batch kernels
-    void* d_stage = nullptr; size_t stage_rays = 0;         // nrays_trace_rays: device copies of one chunk's host arrays
+    void* d_stage = nullptr; size_t stage_bytes = 0;        // the blocking forms' staging arena: device copies of one chunk's host arrays (batch_stage.h lays them out)
     hipStream_t last_stream = nullptr; bool used = false;   // stream of the last batch (ordering, nrays_scene_destroy)
     // Batches the caller called unordered (NRAYS_RAYS_UNORDERED; ray_order.hip): created on the first such chunk, grown only when a chunk holds more rays
     uint64_t* d_ray_keys = nullptr; uint32_t* d_ray_rank = nullptr; uint32_t* d_ray_order = nullptr; size_t order_rays = 0; // per ray: key, place inside its bin, order[j] = ray traced j-th
@@ -253,5 +253,5 @@ uint32_t tile_rows(const NraysRenderParams* p);
 void preallocate_first_frame(NraysScene* sc);
 void pipeline_release(NraysScene* sc);
 constexpr double kNearPixels = 16.0; // (frame_path.hip: cam_shift_px; nrays_scene_create derives the handle's default from it)
-void trace_workspace_release(NraysScene* sc); // ray_order.hip: drains and frees the caller-ray workspace, if a batch ever ran
+void trace_workspace_release(NraysScene* sc); // batch_call.cpp: drains and frees the caller-ray workspace, if a batch ever ran
 } // namespace nrays

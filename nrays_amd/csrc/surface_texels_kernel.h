@@ -1,4 +1,4 @@
-// surface_texels_kernel.h — the kernels of nrays_surface_texels* (ray_order.hip launches them): which triangle of a TriMesh node owns each point of a
+// surface_texels_kernel.h — the kernels of nrays_surface_texels* (texel_calls.hip launches them): which triangle of a TriMesh node owns each point of a
 // width x height lattice in uv space, and the surface record there.  The definition is the text above nrays_surface_texels_device in
 // include/nrays_abi.h (f64 + - * /, sqrt and comparisons, left to right, nothing fused; Python mirror: nrays_amd.surface_texels_ref); the functions
 // texel_coord .. texel_cover below restate it and are the only arithmetic both passes run, so that the resolve pass finds its owner covering again.

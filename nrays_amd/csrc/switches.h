@@ -59,7 +59,7 @@ struct Switches {
     double lone_factor = 1.5;           // NRAYS_LONE_FACTOR=x: cost-ordered lead / second lists when sum / max of the tile costs < x * SIMDs
     int lead_per_wg = 4;                // NRAYS_LEAD_PER_WG=1..64: long entries per lead workgroup
     int grid_wg_per_cu = 0;             // NRAYS_GRID_WG_PER_CU=n: caps the persistent grid at n workgroups per CU (tuning)
-    // ---- caller-ray batches (ray_order.hip) ----
+    // ---- caller-ray batches (batch_call.cpp, ray_order.hip) ----
     int ray_reorder = 1;                // NRAYS_RAY_REORDER=0|2: a batch called unordered is traced as it comes / always reordered (unset: by its size, reorder_pays)
     int occlusion_lanes = -1;           // NRAYS_OCCLUSION_LANES=0|3|6: log2 of the lanes that serve a point of nrays_occlusion_points* and of nrays_gather_points* (unset: the most that the directions fill; A/B, results identical)
     // ---- the staged path (wavefront.hip) ----

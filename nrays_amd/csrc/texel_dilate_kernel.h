@@ -1,4 +1,4 @@
-// texel_dilate_kernel.h — the kernels of nrays_dilate_texels* (ray_order.hip launches them): every uncovered point of a width x height lattice takes the
+// texel_dilate_kernel.h — the kernels of nrays_dilate_texels* (texel_calls.hip launches them): every uncovered point of a width x height lattice takes the
 // values of the nearest covered point inside a Euclidean disc of radius r, the smallest index among equals.  The definition is the text above
 // nrays_dilate_texels_device in include/nrays_abi.h (integers only; Python mirror: nrays_amd.dilate_texels_ref).
 //

@@ -1,4 +1,4 @@
-// texel_filter_kernel.h — the kernel of nrays_filter_texels* (ray_order.hip launches it): one pass of a 5 x 5 a-trous (B3-spline) joint-bilateral filter over a
+// texel_filter_kernel.h — the kernel of nrays_filter_texels* (texel_calls.hip launches it): one pass of a 5 x 5 a-trous (B3-spline) joint-bilateral filter over a
 // width x height lattice of baked values, the weights taken from the texels' world points and normals.  The definition is the text above
 // nrays_filter_texels_device in include/nrays_abi.h (f64 weights, f32 sums, tap order fixed; Python mirror: nrays_amd.filter_texels_ref).  The library is
 // compiled with -ffp-contract=off and the definition relies on it: every product and every sum below is rounded on its own, nothing is fused.
