@@ -1,0 +1,431 @@
+"""The library's definitions restated in plain numpy, bit for bit where their docstrings say so: the references the tests compare the device against, and the
+sample tables and camera rays that feed the calls of scene.py.  Nothing here touches the library or a GPU.  scene.py re-exports every name."""
+import math
+
+import numpy as np
+
+from . import abi
+from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
+                      _occlusion_tables, _sh_bands, _texel_lattice)
+
+SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
+SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
+
+
+_U64 = (1 << 64) - 1
+def _rng_mix(z):
+    z = z ^ (z >> np.uint64(30))
+    z = z * np.uint64(0xbf58476d1ce4e5b9)
+    z = z ^ (z >> np.uint64(27))
+    z = z * np.uint64(0x94d049bb133111eb)
+    return z ^ (z >> np.uint64(31))
+
+
+def _rng_hash(key, salt):
+    """The library's counter-based RNG on uint64 arrays: mix((key ^ salt * golden) + c), wrapping.  `salt`: an int or a uint64 array."""
+    with np.errstate(over="ignore"):
+        if isinstance(salt, np.ndarray):
+            s = salt.astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)
+        else:
+            s = np.uint64((int(salt) * 0x9E3779B97F4A7C15) & _U64)
+        return _rng_mix((np.asarray(key, dtype=np.uint64) ^ s) + np.uint64(0xD1B54A32D192ED03))
+
+
+def camera_rays(resolution, camera_eye, projection, ray_per_pixel=1, window_width=0.0, seed=0):
+    """The rays scene::render traces (src/scene.rs:67-89), for trace_rays: returns (origins (n, 3) float64, dirs (n, 3) float64,
+    keys (n,) uint64) with n = width * height * ray_per_pixel, pixel-major (pixel i + j * width) with the samples innermost.
+    Same f64 operations in the same order as a render: jitter (window_width), NDC, unprojection by the column-major inverse
+    projection-view matrix, v / sqrt(x^2 + y^2 + z^2); key = hash(hash(hash(seed, pixel), sample), path salt).  Averaging the traced
+    colours of a pixel's samples in order (f32 sum, then / ray_per_pixel) gives render()'s pixel."""
+    from .math3d import column_major16
+    w, h, spp = int(resolution[0]), int(resolution[1]), int(ray_per_pixel)
+    if w <= 0 or h <= 0 or spp <= 0:
+        raise ValueError("empty resolution or ray_per_pixel <= 0")
+    M = [float(x) for x in column_major16(projection)]
+    eye0 = [float(x) for x in camera_eye]
+    pix = np.repeat(np.arange(w * h, dtype=np.uint64), spp)
+    s = np.tile(np.arange(spp, dtype=np.uint64), w * h)
+    i = (pix % np.uint64(w)).astype(np.float64)
+    j = (pix // np.uint64(w)).astype(np.float64)
+    pkey = _rng_hash(np.full(pix.shape, int(seed) & _U64, dtype=np.uint64), pix)
+    skey = _rng_hash(pkey, s)
+    ox, oy = i, j
+    if float(window_width) != 0.0:  # scene.rs:74-76
+        u0 = (_rng_hash(skey, 0x1000) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        u1 = (_rng_hash(skey, 0x1001) >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+        ox = ox + (u0 - 0.5) * float(window_width)
+        oy = oy + (u1 - 0.5) * float(window_width)
+    dx = (ox / float(w) - 0.5) * 2.0
+    dy = -(oy / float(h) - 0.5) * 2.0
+    hv = [M[r] * dx + M[4 + r] * dy + M[8 + r] * -1.0 + M[12 + r] * 1.0 for r in range(4)]
+    v = [hv[a] / hv[3] - eye0[a] for a in range(3)]
+    nrm = np.sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2])
+    dirs = np.stack([v[0] / nrm, v[1] / nrm, v[2] / nrm], axis=1)
+    origins = np.empty_like(dirs)
+    origins[:] = eye0
+    keys = _rng_hash(skey, 2)  # RNG_SALT_PATH
+    return origins, dirs, keys
+
+
+def hemisphere_dirs(k, cosine=True):
+    """k sample directions of the local frame of occlusion_points (z = the normal), (k, 3) float64, unit length, z > 0: a golden-angle spiral,
+    cosine-weighted (the mean filter then IS the cosine-weighted ambient term) or uniform over the hemisphere.  A convenience: any values are valid."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    u = (np.arange(k, dtype=np.float64) + 0.5) / k
+    z = np.sqrt(1.0 - u) if cosine else 1.0 - u
+    r = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = np.arange(k, dtype=np.float64) * (math.pi * (3.0 - math.sqrt(5.0)))
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+    return d / np.sqrt((d * d).sum(axis=1))[:, None]
+
+
+def rotation_table(m):
+    """m rotations about the normal, evenly spaced, as the (m, 2) float64 table of (cos, sin) pairs occlusion_points picks from per point."""
+    m = int(m)
+    if m < 1 or m > OCCLUSION_MAX_TABLE:
+        raise ValueError("m must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    a = np.arange(m, dtype=np.float64) * (2.0 * math.pi / m)
+    return np.stack([np.cos(a), np.sin(a)], axis=1)
+
+
+def sphere_dirs(k):
+    """k directions spread over the whole sphere, (k, 3) float64 — a probe's sample table for gather_probes(): Fibonacci points, with t = i + 0.5:
+    z = 1 - 2 t / k, r = sqrt(1 - z^2), phi = t * pi (3 - sqrt 5), direction (r cos phi, r sin phi, z).  A convenience: any values are valid."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    t = np.arange(k, dtype=np.float64) + 0.5
+    z = 1.0 - 2.0 * t / k
+    r = np.sqrt(1.0 - z * z)
+    phi = t * (math.pi * (3.0 - math.sqrt(5.0)))
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=1)
+
+
+def occlusion_rays(points, normals, sample_dirs, rotations=None, bias=1e-3, keys=None):
+    """The numpy mirror of the rays nrays_occlusion_points* builds on the device, bit for bit (include/nrays_abi.h: NraysOcclusionParams — f64 + - * /,
+    copysign and integer arithmetic, products left to right).  Returns (origins (n, k, 3), dirs (n, k, 3)) float64: ray j of point i at [i, j].
+    `keys` (n,) integers, default arange(n): only the rotation pick reads them."""
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("keys", keys, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    if _is_tensor(points) or _is_tensor(normals) or _is_tensor(L) or _is_tensor(rot) or _is_tensor(keys):
+        raise ValueError("occlusion_rays takes numpy arrays")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    k = np.arange(n, dtype=np.uint64) if keys is None else _np_keys(keys)
+    nx, ny, nz = nm[:, 0], nm[:, 1], nm[:, 2]
+    with np.errstate(all="ignore"):
+        s = np.copysign(1.0, nz)
+        a = -1.0 / (s + nz)
+        b = nx * ny * a
+        t = (1.0 + s * nx * nx * a, s * b, -s * nx)
+        u = (b, s + ny * ny * a, -ny)
+        lx, ly, lz = (np.broadcast_to(L[:, c], (n, len(L))) for c in range(3))
+        if rot is None:
+            x, y = lx, ly
+        else:
+            r = (_rng_hash(k, SALT_OCCLUSION) % np.uint64(len(rot))).astype(np.int64)
+            c_r, s_r = rot[r, 0][:, None], rot[r, 1][:, None]
+            x, y = c_r * lx - s_r * ly, s_r * lx + c_r * ly
+        dirs = np.stack([(x * t[q][:, None] + y * u[q][:, None]) + lz * nm[:, q][:, None] for q in range(3)], axis=2)
+        o = p + nm * bias
+    origins = np.ascontiguousarray(np.broadcast_to(o[:, None, :], dirs.shape))
+    return origins, np.ascontiguousarray(dirs)
+
+
+def gather_ray_keys(keys, k):
+    """The RNG keys of the rays gather_points traces: (n, k) uint64, entry [i, j] = hash(keys[i], (0x301 << 32) + j) — ray j of the point whose key is keys[i]
+    (include/nrays_abi.h: NraysGatherParams).  With occlusion_rays() it restates gather_points from trace_rays."""
+    k = int(k)
+    if k < 1 or k > OCCLUSION_MAX_TABLE:
+        raise ValueError("k must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    if _is_tensor(keys):
+        raise ValueError("gather_ray_keys takes a numpy array")
+    keys = _np_keys(keys)
+    if keys.ndim != 1:
+        raise ValueError("keys must have shape (n,), got %s" % (keys.shape,))
+    salts = np.uint64(SALT_GATHER) + np.arange(k, dtype=np.uint64)
+    return _rng_hash(np.broadcast_to(keys[:, None], (len(keys), k)), np.broadcast_to(salts[None, :], (len(keys), k)).copy())
+
+
+# 1/(2 sqrt(pi)), sqrt(3)/(2 sqrt(pi)), sqrt(15)/(2 sqrt(pi)), sqrt(5)/(4 sqrt(pi)), sqrt(15)/(4 sqrt(pi)): the nearest doubles, as the header spells them
+SH_K = (0.28209479177387814, 0.4886025119029199, 1.0925484305920792, 0.31539156525252005, 0.5462742152960396)
+SH_COSINE_LOBE = (math.pi, 2.0 * math.pi / 3.0, math.pi / 4.0)  # A_l of Ramamoorthi and Hanrahan 2001, bands 0 .. 2
+
+
+def _sh_terms(x, y, z, C):
+    """The first C basis values at (x, y, z), each an array like x: the nine expressions of the header, left to right as written (numpy or torch, any dtype)."""
+    K0, K1, K2, K3, K4 = SH_K
+    Y = [K0 + 0.0 * x]
+    if C >= 4:
+        Y += [K1 * y, K1 * z, K1 * x]
+    if C >= 9:
+        Y += [(K2 * x) * y, (K2 * y) * z, K3 * ((3.0 * z) * z - 1.0), (K2 * x) * z, K4 * (x * x - y * y)]
+    return Y
+
+
+def sh_basis(dirs, bands=3):
+    """The numpy mirror of the basis of nrays_gather_sh_points*: (..., 3) float64 directions, used as given -> (..., bands^2) float32 — the real spherical
+    harmonics without the Condon-Shortley sign, evaluated in float64 left to right as the header writes them and rounded once."""
+    bands = _sh_bands(bands)
+    if _is_tensor(dirs):
+        raise ValueError("sh_basis takes a numpy array")
+    d = np.asarray(dirs, dtype=np.float64)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("dirs must have shape (..., 3), got %s" % (d.shape,))
+    with np.errstate(all="ignore"):
+        return np.stack(_sh_terms(d[..., 0], d[..., 1], d[..., 2], bands * bands), axis=-1).astype(np.float32)
+
+
+def sh_fold_ref(ray_dirs, ray_colours, bands=3):
+    """The numpy mirror of the fold of nrays_gather_sh_points*: ray_dirs (n, k, 3) float64 (occlusion_rays()' directions), ray_colours (n, k, 3) float32 (what
+    trace_rays returns for them) -> (n, bands^2, 3) float32: acc = acc + float32(Y_c) * colour in float32 in the order of j, then acc / float32(k)."""
+    d, col = np.asarray(ray_dirs, dtype=np.float64), np.asarray(ray_colours)
+    if col.dtype != np.float32:
+        raise ValueError("ray_colours must be float32, got %s" % col.dtype)
+    if d.ndim != 3 or d.shape[2] != 3 or d.shape[1] < 1 or col.shape != d.shape:
+        raise ValueError("ray_dirs and ray_colours must both have shape (n, k >= 1, 3), got %s and %s" % (d.shape, col.shape))
+    y = sh_basis(d, bands)
+    acc = np.zeros((d.shape[0], y.shape[2], 3), np.float32)
+    with np.errstate(all="ignore"):
+        for j in range(d.shape[1]):
+            acc = acc + y[:, j, :, None] * col[:, j, None, :]
+        return acc / np.float32(d.shape[1])
+
+
+def sh_irradiance(sh, normals, measure=4.0 * math.pi):
+    """The irradiance E(n) = measure * sum_lm A_l sh_lm Y_lm(n) with A = pi, 2 pi / 3, pi / 4 (Ramamoorthi and Hanrahan 2001) from the coefficients gather_sh_points /
+    gather_probes return: sh (..., C, 3) with C = 1, 4 or 9, normals (..., 3) unit vectors whose leading shape broadcasts against sh's -> (..., 3).  `measure`: the
+    solid angle the sample table covers — 4 pi for sphere_dirs (the default), 2 pi for a uniform hemisphere.  Plain numpy or torch arithmetic, no kernel."""
+    C = sh.shape[-2] if len(sh.shape) >= 2 else 0
+    if C not in (1, 4, 9) or sh.shape[-1] != 3 or normals.shape[-1] != 3:
+        raise ValueError("sh must have shape (..., 1 | 4 | 9, 3) and normals (..., 3), got %s and %s" % (tuple(sh.shape), tuple(normals.shape)))
+    if _is_tensor(sh) != _is_tensor(normals):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    Y = _sh_terms(normals[..., 0], normals[..., 1], normals[..., 2], C)
+    band = (0, 1, 1, 1, 2, 2, 2, 2, 2)
+    e = None
+    for c in range(C):
+        term = (SH_COSINE_LOBE[band[c]] * Y[c])[..., None] * sh[..., c, :]
+        e = term if e is None else e + term
+    return measure * e
+
+
+def texel_coords(n, centres=False):
+    """The n lattice coordinates of one axis of surface_texels: x / (n - 1), where Texture2d::sample reads texel x (0.0 for n == 1), or the usual texel
+    centres (x + 0.5) / n.  float64, one correctly rounded division each."""
+    x = np.arange(n, dtype=np.float64)
+    if centres:
+        return (x + 0.5) / float(n)
+    return x / float(n - 1) if n > 1 else np.zeros(1, dtype=np.float64)
+
+
+def _texel_edge(pu, pv, qu, qv, su, sv):
+    swapped = qu < pu or (qu == pu and qv < pv)
+    if swapped:
+        pu, pv, qu, qv = qu, qv, pu, pv
+    e = (qu - pu) * (sv - pv) - (qv - pv) * (su - pu)
+    return -e if swapped else e
+
+
+def surface_texels_ref(points, indices, uvs, transform, width, height, centres=False, flip_normals=False, node=0, with_weights=False):
+    """The numpy mirror of nrays_surface_texels_device's definition (include/nrays_abi.h), bit for bit: what surface_texels() returns for a scene node `node`
+    whose geometry is TriMesh(points, indices, uvs) (coordinates and uvs exactly representable in float32, as a scene requires) under the Isometry3
+    `transform` (None: the identity; the rotation is math3d.rotation_from_axis_angle's).  Every operation is a float64 + - * /, sqrt or comparison in the
+    order the header writes it.  Returns SurfaceTexels of numpy arrays (flags uint32); with_weights=True: (texels, (n, 3) float64 barycentric weights
+    w0, w1, w2, zeros where uncovered)."""
+    from . import math3d
+    width, height = _texel_lattice(width, height)
+    P = np.asarray(points, dtype=np.float64).reshape(-1, 3)
+    I = np.asarray(indices).reshape(-1, 3).astype(np.int64)
+    UV = np.asarray(uvs, dtype=np.float64).reshape(-1, 2)
+    su, sv = texel_coords(width, centres), texel_coords(height, centres)
+    n = width * height
+    owner = np.full((height, width), -1, dtype=np.int64)
+    pts, nrm, wts = np.zeros((height, width, 3)), np.zeros((height, width, 3)), np.zeros((height, width, 3))
+    axis_angle = (0.0, 0.0, 0.0) if transform is None else tuple(transform.axis_angle)
+    trans = (0.0, 0.0, 0.0) if transform is None else tuple(transform.translation)
+    identity = axis_angle == (0.0, 0.0, 0.0)
+    noxform = identity and trans == (0.0, 0.0, 0.0)
+    R = math3d.rotation_from_axis_angle(axis_angle)
+    rot = lambda x, y, z: [(float(R[k, 0]) * x + float(R[k, 1]) * y) + float(R[k, 2]) * z for k in range(3)]  # noqa: E731
+    with np.errstate(all="ignore"):
+        for t in range(len(I)):
+            (au, av), (bu, bv), (cu, cv) = ((float(UV[v, 0]), float(UV[v, 1])) for v in I[t])
+            area2 = np.float64(bu - au) * np.float64(cv - av) - np.float64(bv - av) * np.float64(cu - au)
+            if area2 == 0.0 or not np.isfinite(area2):
+                continue
+            # the lattice points inside the triangle's uv box, by exact comparisons (the coordinates of an axis ascend)
+            x0, x1 = int(np.searchsorted(su, min(au, bu, cu), "left")), int(np.searchsorted(su, max(au, bu, cu), "right"))
+            y0, y1 = int(np.searchsorted(sv, min(av, bv, cv), "left")), int(np.searchsorted(sv, max(av, bv, cv), "right"))
+            if x0 >= x1 or y0 >= y1:
+                continue
+            s = 1.0 if area2 > 0.0 else -1.0
+            gu, gv = su[None, x0:x1], sv[y0:y1, None]
+            e0, e1, e2 = s * _texel_edge(bu, bv, cu, cv, gu, gv), s * _texel_edge(cu, cv, au, av, gu, gv), s * _texel_edge(au, av, bu, bv, gu, gv)
+            total = (e0 + e1) + e2
+            win = (e0 >= 0.0) & (e1 >= 0.0) & (e2 >= 0.0) & (total != 0.0) & (owner[y0:y1, x0:x1] < 0)  # (ascending t: the smallest covering index wins)
+            if not win.any():
+                continue
+            w0, w1, w2 = (e0 / total)[win], (e1 / total)[win], (e2 / total)[win]
+            a, b, c = (P[v] for v in I[t])
+            p = [(float(a[k]) * w0 + float(b[k]) * w1) + float(c[k]) * w2 for k in range(3)]
+            ab, ac = [float(b[k]) - float(a[k]) for k in range(3)], [float(c[k]) - float(a[k]) for k in range(3)]
+            cr = [ab[1] * ac[2] - ab[2] * ac[1], ab[2] * ac[0] - ab[0] * ac[2], ab[0] * ac[1] - ab[1] * ac[0]]
+            norm = np.sqrt(np.float64(cr[0] * cr[0] + cr[1] * cr[1] + cr[2] * cr[2]))
+            nm = [float(np.float64(x) / norm) for x in cr]
+            if not noxform:
+                if identity:
+                    p = [p[k] + trans[k] for k in range(3)]
+                else:
+                    p = [q + trans[k] for k, q in enumerate(rot(*p))]
+                    nm = rot(*nm)
+            if flip_normals:
+                nm = [-x for x in nm]
+            own = owner[y0:y1, x0:x1]; own[win] = t
+            for k in range(3):
+                pts[y0:y1, x0:x1, k][win] = p[k]
+                nrm[y0:y1, x0:x1, k][win] = nm[k]
+            wts[y0:y1, x0:x1, 0][win], wts[y0:y1, x0:x1, 1][win], wts[y0:y1, x0:x1, 2][win] = w0, w1, w2
+    covered = (owner >= 0).reshape(n)
+    uv = np.stack(np.broadcast_arrays(su[None, :], sv[:, None]), axis=-1).reshape(n, 2) * covered[:, None]
+    out = SurfaceTexels(points=pts.reshape(n, 3), normals=nrm.reshape(n, 3), uv=np.ascontiguousarray(uv), node=np.where(covered, int(node), -1).astype(np.int32),
+                        prim=owner.reshape(n).astype(np.int32), flags=np.where(covered, 3, 0).astype(np.uint32))
+    return (out, wts.reshape(n, 3)) if with_weights else out
+
+
+def dilate_texels_ref(flags, width, height, radius, values=None):
+    """The numpy mirror of nrays_dilate_texels_device's definition (include/nrays_abi.h), bit for bit: what dilate_texels() returns, as
+    (values, source int32 (n,), flags uint32 (n,)); `values` is a dilated COPY of the argument (None without one), the arguments stay as they are.
+    Integers only.  Written the separable way: per row the nearest covered column (running maximum / minimum of the covered column indices, the left
+    one on a tie), then rings |dy| = 1, 2, .. radius over the points that are still open — uncovered, and dy^2 not above the d2 they hold — so that the
+    cost follows the gutters' area and depth, not radius x the lattice."""
+    flags = np.asarray(flags)
+    if not np.issubdtype(flags.dtype, np.integer):
+        raise ValueError("flags must be integers, got %s" % flags.dtype)
+    w, h, r, channels = _dilate_args(flags, width, height, radius, None if values is None else np.asarray(values))
+    n, none = w * h, 1 << 20
+    f = flags.astype(np.uint32, copy=False).reshape(h, w)
+    cov = (f & np.uint32(1)) != 0
+    x = np.arange(w, dtype=np.int64)[None, :]
+    dl = x - np.maximum.accumulate(np.where(cov, x, -none), axis=1)
+    dr = np.minimum.accumulate(np.where(cov, x, none)[:, ::-1], axis=1)[:, ::-1] - x
+    dx = np.where(dl <= dr, -dl, dr)
+    dx = np.where(np.minimum(dl, dr) <= r, dx, none).reshape(n)  # per point: the row pass's word
+    i = np.arange(n, dtype=np.int64)
+    y = i // w
+    have = dx != none
+    best_d2 = np.where(have, dx * dx, r * r + 1)
+    best = np.where(have, i + dx, -1)
+    active = np.flatnonzero(~cov.reshape(n))
+    for k in range(1, r + 1):
+        active = active[best_d2[active] >= k * k]
+        if active.size == 0:
+            break
+        for sign in (-1, 1):  # the row above first: on equal (d2, index) nothing changes, and the comparison below is lexicographic anyway
+            yy = y[active] + sign * k
+            a = active[(yy >= 0) & (yy < h)]
+            j = a + sign * k * w
+            d = dx[j]
+            keep = d != none
+            a, j, d = a[keep], j[keep], d[keep]
+            d2, idx = d * d + k * k, j + d
+            better = (d2 < best_d2[a]) | ((d2 == best_d2[a]) & (idx < best[a]))
+            a = a[better]
+            best_d2[a], best[a] = d2[better], idx[better]
+    filled = ~cov.reshape(n) & (best >= 0)
+    out_flags = f.reshape(n) | np.where(filled, np.uint32(abi.TEXEL_FILLED), np.uint32(0))
+    out_values = None
+    if values is not None:
+        v = np.asarray(values)
+        if v.dtype != np.float32:
+            raise ValueError("values must be float32, got %s" % v.dtype)
+        out_values = np.array(v, order="C", copy=True)
+        words = out_values.view(np.uint32).reshape(n, channels)
+        words[filled] = words[best[filled]]
+    return out_values, best.astype(np.int32), out_flags.astype(np.uint32)
+
+
+def lightmap_sample_ref(texels, u, v, interp=Interpolation.Bilinear, overflow=Overflow.ClampToEdges):
+    """The numpy float32 mirror of the sample nrays_gather_maps_points* takes from a map, bit for bit (include/nrays_abi.h: NraysGatherMapsParams — the value the
+    library's materials get from a texture, Texture2d::sample): `texels` (height, width, 4) float32, row 0 = the bottom row; `u`, `v` (n,) coordinates (the float64
+    uv of a hit record, converted to float32 first).  Every product and sum is a float32 operation of its own, in the header's order.  Returns (n, 4) float32."""
+    t = np.asarray(texels)
+    if t.ndim != 3 or t.shape[2] != 4 or t.dtype != np.float32 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError("texels must be a (height, width, 4) float32 array")
+    if interp not in (Interpolation.Bilinear, Interpolation.Nearest) or overflow not in (Overflow.Wrap, Overflow.ClampToEdges):
+        raise ValueError("unknown interp or overflow")
+    F = np.float32
+    h, w = t.shape[0], t.shape[1]
+    with np.errstate(all="ignore"):
+        c = [np.atleast_1d(np.asarray(a)).astype(F) for a in (u, v)]
+        if c[0].shape != c[1].shape or c[0].ndim != 1:
+            raise ValueError("u and v must have the same shape (n,)")
+        for q in range(2):
+            x = c[q]
+            if overflow == Overflow.ClampToEdges:
+                x = np.where(x > F(0), np.where(x < F(1), x, F(1)), F(0)).astype(F)
+            else:
+                x = np.copysign(x - np.trunc(x), x).astype(F)
+                x = np.where(x < F(0), F(1) + x, x).astype(F)
+            c[q] = x * F((w, h)[q] - 1)
+        ux, uy = c
+        index = lambda x: np.where(x > F(0), np.minimum(np.trunc(np.where(x > F(0), x, F(0))).astype(np.float64), 4294967295.0), 0.0).astype(np.int64)  # noqa: E731
+        if interp == Interpolation.Nearest:
+            rnd = lambda x: np.where(np.abs(x) < F(8388608.0), np.copysign(np.floor(np.abs(x.astype(np.float64)) + 0.5), x), x).astype(F)  # noqa: E731
+            return np.ascontiguousarray(t[np.minimum(index(rnd(uy)), h - 1), np.minimum(index(rnd(ux)), w - 1)])
+        lx, ly = np.minimum(index(np.floor(ux)), w - 1), np.minimum(index(np.floor(uy)), h - 1)
+        hx, hy = np.minimum(lx + 1, w - 1), np.minimum(ly + 1, h - 1)
+        sx, sy = (ux - lx.astype(F))[:, None], (uy - ly.astype(F))[:, None]
+        ul, ur, dl, dr = t[hy, lx], t[hy, hx], t[ly, lx], t[ly, hx]
+        ui = ul * (F(1) - sx) + ur * sx
+        di = dl * (F(1) - sx) + dr * sx
+        return np.ascontiguousarray((ui * sy + di * (F(1) - sy)).astype(F))
+
+
+FILTER_TAPS = (1, 4, 6, 4, 1)  # the B3 spline; a tap's kernel weight is the product of two of them, 1 .. 36
+
+
+def filter_texels_ref(flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0):
+    """The numpy mirror of nrays_filter_texels_device's definition (include/nrays_abi.h), bit for bit: what filter_texels() returns, a new float32 array in
+    the shape of `values`.  Vectorised: every tap (i, j) is one pair of shifted slices of the lattice, the taps in the definition's order, a skipped tap
+    leaving acc and wsum as they are (np.where, not a weight of 0: 0 * inf would be a NaN).  f64 where the definition says f64, float32 arrays where it
+    says f32; numpy rounds every operation on its own."""
+    flags, values = np.asarray(flags), np.asarray(values)
+    if not np.issubdtype(flags.dtype, np.integer):
+        raise ValueError("flags must be integers, got %s" % flags.dtype)
+    if values.dtype != np.float32:
+        raise ValueError("values must be float32, got %s" % values.dtype)
+    points, normals = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    w, h, step, pos_radius, normal_cos, channels = _filter_args(flags, width, height, points, normals, values, step, pos_radius, normal_cos)
+    cov = (flags.astype(np.uint32, copy=False).reshape(h, w) & np.uint32(1)) != 0
+    p, nm, v = points.reshape(h, w, 3), normals.reshape(h, w, 3), np.ascontiguousarray(values).reshape(h, w, channels)
+    acc, wsum = np.zeros((h, w, channels), np.float32), np.zeros((h, w), np.float32)
+    r2, cos, den = np.float64(pos_radius) * np.float64(pos_radius), np.float64(normal_cos), np.float64(1.0) - np.float64(normal_cos)
+    with np.errstate(all="ignore"):
+        for j in range(-2, 3):
+            for i in range(-2, 3):
+                dx, dy = i * step, j * step
+                xa, xb, ya, yb = max(0, -dx), min(w, w - dx), max(0, -dy), min(h, h - dy)
+                if xa >= xb or ya >= yb:
+                    continue  # every tap of this offset lies outside the lattice
+                D, S = (slice(ya, yb), slice(xa, xb)), (slice(ya + dy, yb + dy), slice(xa + dx, xb + dx))
+                if i == 0 and j == 0:
+                    take, wt = cov, np.full((h, w), 36.0, np.float32)
+                else:
+                    take = cov[D] & cov[S]
+                    d = p[S] - p[D]
+                    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+                    wp = np.float64(1.0) - d2 / r2
+                    c = (nm[D][..., 0] * nm[S][..., 0] + nm[D][..., 1] * nm[S][..., 1]) + nm[D][..., 2] * nm[S][..., 2]
+                    wn = (c - cos) / den
+                    take = take & (wp > 0.0) & (wn > 0.0)
+                    wn = np.where(wn > 1.0, np.float64(1.0), wn)
+                    wt = (np.float32(FILTER_TAPS[i + 2] * FILTER_TAPS[j + 2]) * wp.astype(np.float32)) * wn.astype(np.float32)
+                acc[D] = np.where(take[..., None], acc[D] + wt[..., None] * v[S], acc[D])
+                wsum[D] = np.where(take, wsum[D] + wt, wsum[D])
+        res = acc / wsum[..., None]
+    out = v.copy()  # uncovered points: the words as they are
+    out[cov] = res[cov]
+    return out.reshape(values.shape)

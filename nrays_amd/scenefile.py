@@ -2,13 +2,12 @@
 `.mtl`, `.obj` parsing and the PNG codec.  A FileScene exposes the same two members the render and
 oracle entry points need from nrays_amd.scene.Scene: `.descriptor.pointer()` and `.device_handle()`."""
 import ctypes as C
-import math
 import os
 
 import numpy as np
 
 from . import abi
-from .scene import _dilate_keyword
+from .scene import BatchCalls
 
 
 class NraysHostCamera(C.Structure):
@@ -63,7 +62,7 @@ class _Descriptor:
         return self._ptr
 
 
-class FileScene:
+class FileScene(BatchCalls):
     """A scene loaded from a `.scene` file by the C++ front-end (examples/loader3d.rs:57-65)."""
 
     def __init__(self, path, allow_standins=False):
@@ -99,80 +98,6 @@ class FileScene:
             abi.check(lib.nrays_scene_create(self.descriptor.pointer(), C.byref(h)))
             self._handle = h
         return self._handle
-
-    def cast_rays(self, origins, dirs, max_toi=None, unordered=False, want=("normal", "uv", "prim", "flags")):
-        """The closest hits of caller-supplied rays on this scene: scene.closest_hits(self, ...)."""
-        from .scene import closest_hits
-        return closest_hits(self, origins, dirs, max_toi, unordered, want)
-
-    def shade_points(self, points, normals, view_dirs, nodes, uvs=None, hit_flags=None, keys=None):
-        """The direct lighting of caller-supplied surface points of this scene: scene.shade_points(self, ...)."""
-        from .scene import shade_points
-        return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
-
-    def occlusion_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=float("inf"), hit_flags=None, keys=None):
-        """Ambient occlusion at caller-supplied surface points of this scene: scene.occlusion_points(self, ...)."""
-        from .scene import occlusion_points
-        return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
-
-    def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None, unordered=False):
-        """The incoming light at caller-supplied surface points of this scene: scene.gather_points(self, ...)."""
-        from .scene import gather_points
-        return gather_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, hit_flags, keys, unordered)
-
-    def gather_sh_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, bands=3, hit_flags=None, keys=None, unordered=False):
-        """The incoming light at caller-supplied points of this scene as spherical harmonics: scene.gather_sh_points(self, ...)."""
-        from .scene import gather_sh_points
-        return gather_sh_points(self, points, normals, sample_dirs, rotations, bias, energy, max_depth, bands, hit_flags, keys, unordered)
-
-    def gather_probes(self, positions, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True):
-        """Irradiance probes at free points of this scene: scene.gather_probes(self, ...)."""
-        from .scene import gather_probes
-        return gather_probes(self, positions, sample_dirs, bands, energy, max_depth, keys, unordered)
-
-    @_dilate_keyword
-    def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
-                      device=None, unordered=False):
-        """The indirect term of a light map of mesh node `node`: scene.bake_indirect(self, node, ...); `dilate=` as there, by keyword."""
-        from .scene import bake_indirect
-        return bake_indirect(self, node, width, height, sample_dirs, rotations, bias, energy, max_depth, centres, flip_normals, keys, device, unordered)
-
-    def gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
-                           keys=None, want_counts=False):
-        """The light of baked maps at the closest hits of the hemisphere rays of caller-supplied points of this scene: scene.gather_maps_points(self, ...)."""
-        from .scene import gather_maps_points
-        return gather_maps_points(self, points, normals, sample_dirs, maps, node_map, rotations, bias, max_toi, miss, hit_flags, keys, want_counts)
-
-    def bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations=None, bias=1e-3, miss=(0.0, 0.0, 0.0), dilate=2, flip_normals=False, keys=None,
-                     device=None):
-        """The multi-bounce light map of mesh node `node`: scene.bake_bounces(self, node, ...)."""
-        from .scene import bake_bounces
-        return bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations, bias, miss, dilate, flip_normals, keys, device)
-
-    def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
-        """The surface of mesh node `node` at a light map's texels: scene.surface_texels(self, node, ...)."""
-        from .scene import surface_texels
-        return surface_texels(self, node, width, height, centres, flip_normals, want, device)
-
-    def bake_lightmap(self, node, width, height, occlusion=None, centres=False, flip_normals=False, keys=None, device=None, dilate=0):
-        """A light map of mesh node `node`: scene.bake_lightmap(self, node, ...)."""
-        from .scene import bake_lightmap
-        return bake_lightmap(self, node, width, height, occlusion, centres, flip_normals, keys, device, dilate)
-
-    def dilate_texels(self, flags, width, height, radius, values=None, want_source=False, device=None):
-        """Gutter dilation of a light map on this scene's GPU: scene.dilate_texels(self, flags, ...)."""
-        from .scene import dilate_texels
-        return dilate_texels(self, flags, width, height, radius, values, want_source, device)
-
-    def filter_texels(self, flags, width, height, points, normals, values, step=1, pos_radius=math.inf, normal_cos=0.0, device=None):
-        """One pass of the edge-aware light-map filter on this scene's GPU: scene.filter_texels(self, flags, ...)."""
-        from .scene import filter_texels
-        return filter_texels(self, flags, width, height, points, normals, values, step, pos_radius, normal_cos, device)
-
-    def denoise_texels(self, tx, values, passes=3, pos_radius=math.inf, normal_cos=0.0, width=None, height=None):
-        """A baked light map denoised on this scene's GPU: scene.denoise_texels(self, tx, values, ...)."""
-        from .scene import denoise_texels
-        return denoise_texels(self, tx, values, passes, pos_radius, normal_cos, width, height)
 
     def close(self):
         if self._handle is not None:
