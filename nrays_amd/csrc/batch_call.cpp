@@ -1,9 +1,10 @@
 // batch_call.cpp — the caller-batch driver of batch_call.h: the handle's batch workspace (trace_workspace, trace_workspace_release), the ordering of a batch
 // behind the handle's previous work (batch_begin / batch_end), batch_open / batch_close, the staging arena's copies, the chunked run, and the small helpers the
-// families share (reorder_pays, check_ray_flags, chunk_order, occlusion_lanes_log2).  Host only: no kernel, and the environment is switches.cpp's to read.
+// families share (reorder_pays, check_ray_flags, chunk_order, launch_status, no_permutation, check_hemisphere, occlusion_lanes_log2).  Host only: no kernel, and the environment is switches.cpp's to read.
 #include "batch_call.h"
 
 #include <algorithm>
+#include <cmath>
 #include <new>
 #include <string>
 
@@ -127,6 +128,19 @@ int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, con
     if (rc == NRAYS_OK) rc = ray_order_chunk(sc, w, n, o, d, stream);
     if (rc == NRAYS_OK) *order = w->d_ray_order;
     return rc;
+}
+int launch_status(const char* kernel) {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? (int)NRAYS_OK : set_last_error(NRAYS_ERR_HIP, std::string(kernel) + ": " + hipGetErrorString(e));
+}
+int no_permutation(const char* kernel) { return set_last_error(NRAYS_ERR_UNSUPPORTED, std::string(kernel) + ": no such permutation"); }
+int check_hemisphere(const char* struct_name, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, double bias, const char* with, bool with_finite) {
+    auto bad = [&](const std::string& what) { return set_last_error(NRAYS_ERR_BAD_ARG, struct_name + what); }; // (a string is built for an error alone)
+    if (!dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (num_dirs < 1u || num_dirs > 1024u) return bad(": num_dirs must be in 1 .. 1024");
+    if (num_rotations > 1024u || (num_rotations && !rotations)) return bad(": num_rotations > 1024, or rotations is NULL");
+    if (!std::isfinite(bias) || !with_finite) return bad(with ? std::string(": bias and ") + with + " must be finite" : ": bias must be finite");
+    return NRAYS_OK;
 }
 int occlusion_lanes_log2(const NraysScene* sc, uint32_t num_dirs) {
     int lp = 6;

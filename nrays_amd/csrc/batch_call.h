@@ -1,6 +1,7 @@
 // batch_call.h — the driver every caller-batch entry point runs through (batch_call.cpp; host only, no kernels).  A family — trace, intersects, cast, shade
-// (ray_batches.hip), occlusion, gather, gather_sh, gather_maps (point_batches.hip), surface / dilate / filter texels (texel_calls.hip) — is three things of its own:
-// its argument check (with the n == 0 return, before any HIP call), its column table (batch_stage.h) and its chunk launch.  The driver holds the rest once:
+// (ray_batches.hip), occlusion, gather, gather_sh, gather_maps (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
+// nrays_debug_cast_batch and nrays_debug_occlusion_rays — is four things of its own ("Adding a family on the C++ side"): its argument check (with the
+// n == 0 return, before any HIP call), its column table (batch_stage.h), its launch struct with a launch_if chain, and its chunk lambda.  The driver holds the rest once:
 //   batch_open    hipSetDevice, the handle's batch workspace, the family's own workspace (`ensure`), the staging arena, the stream — the caller's for the
 //                 device form, the handle's own for the blocking form — and the ordering behind the handle's previous work
 //   batch_run     the tables once; per chunk the `in` columns, the family's launch with the chunk's device pointers and key_base = its first item, the `out`
@@ -65,11 +66,18 @@ int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, con
 // the coherence the traversal lives on; one lane per point is left to batches of fewer than 8 directions.  NRAYS_OCCLUSION_LANES=0|3|6 forces a form (the A/B of
 // tools/trace_rays_rate.py --occlusion; the results do not depend on it).
 int occlusion_lanes_log2(const NraysScene* sc, uint32_t num_dirs);
-// ray_batches.hip: the launch of k_occlusion_points<feat, lp> for point_batches.hip (feat: kFeatMesh or kFeatAll; lp: 0, 3 or 6).
-struct OcclusionSpec; // ray_batch_kernel.h
-void launch_occlusion_points(int feat, int lp, uint32_t grid, hipStream_t stream, const DScene& S, uint32_t nc, const double* points, const double* normals, const uint32_t* hit_flags,
-                             const unsigned long long* keys, unsigned long long key_base, const OcclusionSpec& spec, const double* dirs, const double* rotations, float* out_filter,
-                             uint32_t* out_open, uint32_t* spill);
+// A kernel's launch is written in the unit that instantiates it (ray_batches.hip, gather_inst.hip, gather_order_inst.hip, gather_maps_inst.hip): an argument struct and
+// `bool launch_<kernel>(const Args&, ...selectors...)`, a chain launch_if<...>(a, ...) || ... of the instantiated permutations; false = none, NRAYS_ERR_UNSUPPORTED here.
+uint32_t launch_grid(uint64_t items);  // workgroups of kBlock lanes for `items` lanes, at most kMaxGrid: the kernels stride (ray_batches.hip, beside the kernels)
+int launch_status(const char* kernel); // after a launch: hipGetLastError() as NRAYS_OK, or NRAYS_ERR_HIP with "<kernel>: <the error>"
+int no_permutation(const char* kernel); // NRAYS_ERR_UNSUPPORTED, "<kernel>: no such permutation"
+// What the families at surface points share: the check of the hemisphere's tables and bias ("null argument" or "<struct_name>: ..."; `with` / `with_finite`: a value of
+// the struct reported together with the bias), the generator's view of them (max_toi 0) and the kernels' view of a chunk's point columns kPointPoints .. kPointKeys.
+struct GatherPoints; struct OcclusionSpec; // ray_batch_kernel.h
+int check_hemisphere(const char* struct_name, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, double bias, const char* with = nullptr,
+                     bool with_finite = true);
+OcclusionSpec hemisphere_spec(uint32_t num_dirs, uint32_t num_rotations, double bias);
+GatherPoints chunk_points(void* const* col, unsigned long long key_base);
 // point_batches.hip: the argument check of nrays_gather_points*, which the gather-order probe of ray_order.hip shares.  `hinted`: the _ex entry points, which take
 // NRAYS_RAYS_UNORDERED; the others take no flag at all.
 int check_gather_args(const NraysScene* sc, const double* points, const double* normals, const NraysGatherParams* p, const float* out_rgb, uint32_t flags, bool hinted);

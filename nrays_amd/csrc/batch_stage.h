@@ -70,6 +70,13 @@ inline int cast_columns(StageColumn* c, const double* origins, const double* dir
     c[kCastPrim] = stage_out(prim, 4); c[kCastFlags] = stage_out(flags, 4);
     return kCastColumns;
 }
+// nrays_debug_cast_batch: max_toi is the shadow query's (mode 1; null otherwise); one record a ray, result_bytes = sizeof(NraysCastResult).
+enum { kCastProbeMaxToi = kRayColumns, kCastProbeOut, kCastProbeColumns };
+inline int cast_probe_columns(StageColumn* c, const double* origins, const double* dirs, const double* max_toi, void* out, size_t result_bytes) {
+    ray_columns(c, origins, dirs);
+    c[kCastProbeMaxToi] = stage_in(max_toi, 8); c[kCastProbeOut] = stage_out(out, result_bytes);
+    return kCastProbeColumns;
+}
 enum { kShadePoints, kShadeNormals, kShadeViews, kShadeUvs, kShadeNodes, kShadeHit, kShadeKeys, kShadeOut, kShadeColumns };
 inline int shade_columns(StageColumn* c, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags,
                          const uint64_t* keys, float* out_rgba) {
@@ -89,6 +96,12 @@ enum { kOccFilter = kPointColumns, kOccOpen, kOccColumns };
 inline int occlusion_columns(StageColumn* c, float* out_filter, uint32_t* out_open) { // (after point_columns)
     c[kOccFilter] = stage_out(out_filter, 12); c[kOccOpen] = stage_out(out_open, 4);
     return kOccColumns;
+}
+// nrays_debug_occlusion_rays: the num_dirs rays of a point, origins and directions.
+enum { kOccRaysOrigins = kPointColumns, kOccRaysDirs, kOccRaysColumns };
+inline int occlusion_rays_columns(StageColumn* c, double* out_origins, double* out_dirs, uint32_t num_dirs) { // (after point_columns)
+    c[kOccRaysOrigins] = stage_out(out_origins, 24 * (size_t)num_dirs); c[kOccRaysDirs] = stage_out(out_dirs, 24 * (size_t)num_dirs);
+    return kOccRaysColumns;
 }
 // out_floats: 3 (nrays_gather_points*) or 3 * bands^2 (nrays_gather_sh_points*).  ray_colours: nrays_debug_gather_sh_fold's input, 3 floats a ray; null elsewhere.
 enum { kGatherOut = kPointColumns, kGatherRays, kGatherColumns };

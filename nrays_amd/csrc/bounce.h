@@ -24,4 +24,12 @@ struct BounceRounds {
 // every count and once more when the generation cap ended the rounds (caller-ray batches report it per call; a frame's is read by nrays_get_stats / the blocking renders).
 int run_bounce_rounds(const BounceRounds& b, hipStream_t stream, uint32_t* overflow_seen);
 
+// The queued trace of one chunk of a caller batch on its workspace (nrays_trace_rays*, nrays_gather_points*): `rays` rays, each the "pixel" of its own chain, 3 floats a ray.
+// queued_trace_begin, before the chunk's trace kernel: the counters cleared and *qo filled; double-branching scenes: the queue pair by a frame's rule per pixel, per ray
+// here (4 slots, at least 2^16, at most 2^27) and the fixed sums; other scenes: capacity 0.  queued_trace_finish, after it (double-branching scenes only): the rounds over
+// `colours`, then an overflow as NRAYS_ERR_QUEUE_OVERFLOW, "... some <noun> colours are incomplete" (every launch is enqueued all the same).
+struct QueueOut; // trace_device.h
+int queued_trace_begin(const NraysScene* sc, TraceWorkspace* w, uint32_t rays, hipStream_t stream, QueueOut* qo);
+int queued_trace_finish(const NraysScene* sc, TraceWorkspace* w, uint32_t rays, uint32_t max_depth, float* colours, const char* noun, hipStream_t stream);
+
 } // namespace nrays

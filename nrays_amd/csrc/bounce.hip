@@ -8,6 +8,7 @@
 #include <string>
 
 #include "../../include/nrays_abi.h"
+#include "batch_call.h"
 #include "bounce.h"
 #include "primary_kernel.h"
 
@@ -110,7 +111,7 @@ int run_bounce_rounds(const BounceRounds& b, hipStream_t stream, uint32_t* overf
             if (seen[0] == 0u) { drained = true; break; }
         }
         const uint32_t launch_n = std::min<uint32_t>(seen[0], b.capacity); // the group's first count bounds nothing, it only sizes the grid
-        const uint32_t grid = std::max<uint32_t>(std::min<uint32_t>((launch_n + kBlock - 1) / kBlock, kMaxGrid), std::min<uint32_t>((uint32_t)b.num_cus, kMaxGrid));
+        const uint32_t grid = std::max<uint32_t>(launch_grid(launch_n), std::min<uint32_t>((uint32_t)b.num_cus, kMaxGrid));
         QueueOut qn; qn.q = b.queue[(r + 1) & 1].q; qn.capacity = b.capacity; qn.count = b.counts + r + 1; qn.overflow = b.overflow;
         if (b.stats) hipLaunchKernelGGL(k_bounce<true>, dim3(grid), dim3(kBlock), 0, stream, *b.scene, b.queue[r & 1].q, b.counts + r, b.capacity, qn, b.fixed, b.counters, b.spill, b.max_depth);
         else hipLaunchKernelGGL(k_bounce<false>, dim3(grid), dim3(kBlock), 0, stream, *b.scene, b.queue[r & 1].q, b.counts + r, b.capacity, qn, b.fixed, b.counters, b.spill, b.max_depth);
@@ -130,6 +131,23 @@ int run_bounce_rounds(const BounceRounds& b, hipStream_t stream, uint32_t* overf
         *overflow_seen = seen[1];
     }
     return NRAYS_OK;
+}
+
+int queued_trace_begin(const NraysScene* sc, TraceWorkspace* w, uint32_t rays, hipStream_t stream, QueueOut* qo) {
+    const bool queued = sc->facts.host.any_double_branch;
+    int rc = queued ? ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)std::min<uint64_t>(std::max<uint64_t>(4ull * rays, 1u << 16), 1ull << 27)) : (int)NRAYS_OK;
+    if (rc == NRAYS_OK && queued) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, (size_t)rays * 3, stream);
+    if (rc != NRAYS_OK) return rc;
+    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
+    qo->q = w->queue[1].q; qo->capacity = queued ? w->queue_capacity : 0u; qo->count = w->d_counts + 1; qo->overflow = w->d_counts + kTraceCountWords - 1;
+    return NRAYS_OK;
+}
+int queued_trace_finish(const NraysScene* sc, TraceWorkspace* w, uint32_t rays, uint32_t max_depth, float* colours, const char* noun, hipStream_t stream) {
+    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, w->d_counts + kTraceCountWords - 1, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d,
+                              sc->facts.d.no_elide != 0u, max_depth, colours, (size_t)rays * 3, sc->facts.num_cus};
+    uint32_t overflowed = 0u;
+    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
+    return rc != NRAYS_OK || !overflowed ? rc : set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, std::string("continuation-ray queue overflow: some ") + noun + " colours are incomplete");
 }
 
 } // namespace nrays

@@ -10,8 +10,8 @@ namespace nrays {
 template <int FEAT, int LP>
 static bool launch_if(const GatherMapsLaunch& a, int feat, int lp) {
     if (feat != FEAT || lp != LP) return false;
-    hipLaunchKernelGGL((k_gather_maps_points<FEAT, LP>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.points, a.normals, a.hit_flags, a.keys, a.key_base, a.spec, *a.maps,
-                       a.node_map, a.dirs, a.rotations, a.out_rgb, a.out_counts, a.spill);
+    hipLaunchKernelGGL((k_gather_maps_points<FEAT, LP>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.in.points, a.in.normals, a.in.hit_flags, a.in.keys, a.in.key_base,
+                       a.spec, *a.maps, a.node_map, a.dirs, a.rotations, a.out_rgb, a.out_counts, a.spill);
     return true;
 }
 

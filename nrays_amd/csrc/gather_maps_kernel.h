@@ -101,9 +101,8 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_maps_po
 
 // The arguments of one k_gather_maps_points launch; the instantiations are compiled in gather_maps_inst.hip.  false = no such permutation.
 struct GatherMapsLaunch {
-    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys;
-    unsigned long long key_base; GatherMapsSpec spec; const GatherMapsTable* maps; const int32_t* node_map; const double* dirs; const double* rotations; float* out_rgb;
-    uint32_t* out_counts; uint32_t* spill;
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; GatherPoints in; GatherMapsSpec spec; const GatherMapsTable* maps; const int32_t* node_map; const double* dirs;
+    const double* rotations; float* out_rgb; uint32_t* out_counts; uint32_t* spill;
 };
 bool launch_gather_maps_points(const GatherMapsLaunch& a, int feat, int lp);
 

@@ -1,6 +1,6 @@
 // gather_order_inst.hip — the k_gather_pairs_ordered permutations (ray_batch_kernel.h): the trace of a reordered gather chunk, in a translation unit of its own
 // for the reason gather_inst.hip has one (every permutation instantiates trace_chain, and this unit compiles beside that one and point_batches.hip, which launches it).  The
-// permutations are trace_chunk's: kFeatMesh for scenes of opaque meshes, kFeatAll otherwise, the kernel that counts everything and skips nothing for no_elide scenes.
+// permutations are launch_trace_rays's: kFeatMesh for scenes of opaque meshes, kFeatAll otherwise, the kernel that counts everything and skips nothing for no_elide scenes.
 #include <hip/hip_runtime.h>
 
 #include "ray_batch_kernel.h"

@@ -22,19 +22,16 @@ namespace nrays {
 
 constexpr uint32_t kFoldBlock = 256u; // threads per workgroup of k_gather_fold
 
-// The points of a chunk, as the kernels take them (columns kPointPoints .. kPointKeys of the chunk).
-struct PointsIn { const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys; };
-static PointsIn points_in(void* const* c) {
-    return PointsIn{(const double*)c[kPointPoints], (const double*)c[kPointNormals], (const uint32_t*)c[kPointHit], (const unsigned long long*)c[kPointKeys]};
+GatherPoints chunk_points(void* const* c, unsigned long long key_base) {
+    return GatherPoints{(const double*)c[kPointPoints], (const double*)c[kPointNormals], (const uint32_t*)c[kPointHit], (const unsigned long long*)c[kPointKeys], key_base};
 }
+OcclusionSpec hemisphere_spec(uint32_t num_dirs, uint32_t num_rotations, double bias) { return OcclusionSpec{num_dirs, num_rotations, bias, 0.0}; }
 
 // ---- nrays_occlusion_points*: ambient occlusion at caller-supplied points, the hemisphere rays built on the device ------------------------------------
 static int check_occlusion_params(const NraysOcclusionParams* p) {
-    if (!p || !p->dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
-    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: num_dirs must be in 1 .. 1024");
-    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: num_rotations > 1024, or rotations is NULL");
+    if (!p) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_hemisphere("NraysOcclusionParams", p->dirs, p->num_dirs, p->rotations, p->num_rotations, p->bias) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (!(p->max_toi > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: max_toi must be > 0 (+inf allowed)");
-    if (!std::isfinite(p->bias)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysOcclusionParams: bias must be finite");
     return NRAYS_OK;
 }
 static OcclusionSpec occlusion_spec(const NraysOcclusionParams* p) { return OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, p->max_toi}; }
@@ -49,27 +46,18 @@ static int occlusion_points_impl(NraysScene* sc, uint32_t n, const double* point
     occlusion_columns(cols, out_filter, out_open);
     // One chunk (nc <= point_chunk); the permutation: kFeatMesh or kFeatAll, as k_intersects_rays.
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
-        const PointsIn in = points_in(c);
-        const OcclusionSpec spec = occlusion_spec(p);
-        const double *dirs = (const double*)c[kPointDirs], *rotations = (const double*)c[kPointRotations];
-        float* filter = (float*)c[kOccFilter]; uint32_t* open = (uint32_t*)c[kOccOpen];
-        const int lp = occlusion_lanes_log2(sc, spec.num_dirs);
-        const uint32_t slots = nc << lp; // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
-        const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-        launch_occlusion_points(traversal_feat(sc), lp, grid, b.stream, sc->facts.d, nc, in.points, in.normals, in.hit_flags, in.keys, key_base, spec, dirs, rotations, filter, open, b.w->d_spill);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_occlusion_points: ") + hipGetErrorString(e));
-        return NRAYS_OK;
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+        const OcclusionLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, chunk_points(c, key_base), occlusion_spec(p), (const double*)c[kPointDirs],
+                                (const double*)c[kPointRotations], (float*)c[kOccFilter], (uint32_t*)c[kOccOpen], b.w->d_spill};
+        return launch_occlusion_points(a, traversal_feat(sc), lp) ? launch_status("k_occlusion_points") : no_permutation("k_occlusion_points");
     };
     return batch_run(sc, staged, stream, cols, kOccColumns, n, point_chunk(p->num_dirs), "occlusion batch", launch);
 }
 
 // ---- nrays_gather_points*: the mean of Scene::trace over the hemisphere rays of caller-supplied points, the rays built on the device --------------------------
 int check_gather_args(const NraysScene* sc, const double* points, const double* normals, const NraysGatherParams* p, const float* out_rgb, uint32_t flags, bool hinted) {
-    if (!sc || !points || !normals || !p || !p->dirs || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
-    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_dirs must be in 1 .. 1024");
-    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: num_rotations > 1024, or rotations is NULL");
-    if (!std::isfinite(p->bias) || !std::isfinite(p->energy)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherParams: bias and energy must be finite");
+    if (!sc || !points || !normals || !p || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_hemisphere("NraysGatherParams", p->dirs, p->num_dirs, p->rotations, p->num_rotations, p->bias, "energy", std::isfinite(p->energy)) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (hinted) return check_ray_flags(flags);
     if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_points: flags must be 0");
     return NRAYS_OK;
@@ -94,72 +82,54 @@ __global__ void __launch_bounds__(kFoldBlock) k_gather_fold(const float* __restr
     const float fk = (float)k;
     out[3 * (size_t)i] = x / fk; out[3 * (size_t)i + 1] = y / fk; out[3 * (size_t)i + 2] = z / fk;
 }
-// One chunk (nc <= point_chunk) of nrays_gather_points*; `in` and `out` are the chunk's, key_base the index of its first point in the batch, dirs / rotations
-// device copies of the tables.  The permutation is trace_chunk's, the lanes per point are k_occlusion_points'.  Double-branching scenes: the kernel stores the
-// chunk's ray colours, trace_chunk's rounds run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by trace_chunk's
+// One chunk (nc <= point_chunk) of nrays_gather_points*; `pts` and `out` are the chunk's, dirs / rotations
+// device copies of the tables.  The permutation is launch_trace_rays', the lanes per point are k_occlusion_points'.  Double-branching scenes: the kernel stores the
+// chunk's ray colours, the rounds of queued_trace_finish run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by queued_trace_begin's
 // rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
 // `reorder` (a hinted call that pays, nrays_gather_points*_ex): the chunk's pairs are binned (gather_order_chunk) and traced in bin order by k_gather_pairs_ordered, every
 // scene through the cleared per-ray colours and k_gather_fold: 12 bytes of colour and 16 of sort state a ray of the chunk, whatever the scene.
 // `bands` > 0 (nrays_gather_sh_points*): the same trace kernels, always through the per-ray colours — queued or not, reordered or not —, and k_gather_fold_sh
 // (gather_sh_kernel.h) folds them into 3 * bands^2 floats a point of `out` instead of k_gather_fold's 3.
-static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const PointsIn& in, unsigned long long key_base, const NraysGatherParams* p,
-                               const double* dirs, const double* rotations, float* out, bool reorder, uint32_t bands, hipStream_t stream) {
+static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, const GatherPoints& pts, const NraysGatherParams* p, const double* dirs, const double* rotations,
+                               float* out, bool reorder, uint32_t bands, hipStream_t stream) {
     const bool queued = sc->facts.host.any_double_branch;
     const uint32_t pairs = nc * p->num_dirs; // (<= kTraceChunk)
     const size_t ray_floats = 3 * (size_t)pairs;
-    if (queued) {
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * pairs, 1u << 16), 1ull << 27);
-        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
-        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, ray_floats, stream);
-        if (rc != NRAYS_OK) return rc;
-    }
+    QueueOut qo;
+    int rc = queued_trace_begin(sc, w, pairs, stream, &qo);
     const bool per_ray = queued || reorder || bands != 0u;
-    if (per_ray) {
-        const int rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
-        if (rc != NRAYS_OK) return rc;
-    }
+    if (rc == NRAYS_OK && per_ray) rc = grow_device(&w->d_gather_rays, &w->gather_ray_floats, ray_floats, sizeof(float));
+    if (rc != NRAYS_OK) return rc;
     float* ray_out = per_ray ? (float*)w->d_gather_rays : nullptr;
-    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
-    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
-    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
     const GatherSpec spec{p->num_dirs, p->num_rotations, p->bias, p->energy, p->max_depth, sc->facts.host.any_area_light ? 1u : 0u};
+    const OcclusionSpec hemi = hemisphere_spec(p->num_dirs, p->num_rotations, p->bias);
     const bool stats = sc->facts.d.no_elide != 0u;
     const int feat = stats ? (int)kFeatAll : shading_feat(sc);
-    const GatherPoints pts{in.points, in.normals, in.hit_flags, in.keys, key_base};
     if (reorder) {
-        int rc = ray_order_ensure(w, pairs);
-        if (rc == NRAYS_OK) rc = gather_order_chunk(sc, w, pairs, pts, OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, 0.0}, dirs, rotations, stream);
+        rc = ray_order_ensure(w, pairs);
+        if (rc == NRAYS_OK) rc = gather_order_chunk(sc, w, pairs, pts, hemi, dirs, rotations, stream);
         if (rc != NRAYS_OK) return rc;
         HIP_TRY(hipMemsetAsync(ray_out, 0, ray_floats * sizeof(float), stream)); // (a skipped point's pairs are never traced: exact zeros)
-        const uint32_t grid = std::min<uint32_t>((pairs + kBlock - 1) / kBlock, (uint32_t)kMaxGrid); // (by the chunk's pairs: the live count stays on the device)
-        const GatherPairsLaunch a{grid, stream, &sc->facts.d, pairs, w->d_ray_order, w->d_ray_bins + kNumBins, pts, spec, dirs, rotations, ray_out, &qo, w->d_counters, w->d_spill};
-        if (!launch_gather_pairs_ordered(a, stats, feat)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_pairs_ordered: no such permutation");
+        // (the grid by the chunk's pairs: the live count stays on the device)
+        const GatherPairsLaunch a{launch_grid(pairs), stream, &sc->facts.d, pairs, w->d_ray_order, w->d_ray_bins + kNumBins, pts, spec, dirs, rotations, ray_out, &qo, w->d_counters, w->d_spill};
+        if (!launch_gather_pairs_ordered(a, stats, feat)) return no_permutation("k_gather_pairs_ordered");
     } else {
-        const int lp = occlusion_lanes_log2(sc, p->num_dirs);
-        const uint32_t slots = nc << lp; // (2^lp <= num_dirs)
-        const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-        const GatherLaunch a{grid, stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, in.keys, key_base, spec, dirs, rotations, out, ray_out, &qo,
-                             w->d_counters, w->d_spill};
-        if (!launch_gather_points(a, stats, feat, lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_points: no such permutation");
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (2^lp <= num_dirs)
+        const GatherLaunch a{launch_grid((uint64_t)nc << lp), stream, &sc->facts.d, nc, pts, spec, dirs, rotations, out, ray_out, &qo, w->d_counters, w->d_spill};
+        if (!launch_gather_points(a, stats, feat, lp)) return no_permutation("k_gather_points");
     }
     HIP_TRY(hipGetLastError());
     if (!ray_out) return NRAYS_OK;
-    uint32_t overflowed = 0u;
-    if (queued) {
-        const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, stats, p->max_depth, ray_out, ray_floats, sc->facts.num_cus};
-        const int rc = run_bounce_rounds(rounds, stream, &overflowed);
-        if (rc != NRAYS_OK) return rc;
-    }
+    if (queued) rc = queued_trace_finish(sc, w, pairs, p->max_depth, ray_out, "gathered", stream);
+    if (rc != NRAYS_OK && rc != NRAYS_ERR_QUEUE_OVERFLOW) return rc; // (an overflow: the incomplete colours are folded all the same, and the status is the call's)
     if (bands) {
         const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
-        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, (const float*)ray_out, nc, pts, OcclusionSpec{p->num_dirs, p->num_rotations, p->bias, 0.0}, dirs,
-                           rotations, bands * bands, out);
+        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, (const float*)ray_out, nc, pts, hemi, dirs, rotations, bands * bands, out);
     } else {
         hipLaunchKernelGGL(k_gather_fold, dim3((nc + kFoldBlock - 1u) / kFoldBlock), dim3(kFoldBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
     }
     HIP_TRY(hipGetLastError());
-    if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some gathered colours are incomplete");
-    return NRAYS_OK;
+    return rc;
 }
 // `bands` = 0: nrays_gather_points* (3 floats a point); 1 .. 3: nrays_gather_sh_points* (3 * bands^2 floats a point), checked by the caller.
 static int gather_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys, const NraysGatherParams* p,
@@ -171,18 +141,16 @@ static int gather_points_impl(NraysScene* sc, uint32_t n, const double* points, 
     gather_columns(cols, out, gather_out_floats(bands), nullptr, p->num_dirs);
     const bool reorder = gather_reorders(sc, n, p, flags);
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
-        return gather_chunk_launch(sc, b.w, nc, points_in(c), key_base, p, (const double*)c[kPointDirs], (const double*)c[kPointRotations], (float*)c[kGatherOut], reorder, bands, b.stream);
+        return gather_chunk_launch(sc, b.w, nc, chunk_points(c, key_base), p, (const double*)c[kPointDirs], (const double*)c[kPointRotations], (float*)c[kGatherOut], reorder, bands, b.stream);
     };
     return batch_run(sc, staged, stream, cols, kGatherColumns, n, point_chunk(p->num_dirs), "gather batch", launch);
 }
 
 // ---- nrays_gather_maps_points*: the light of baked maps at the closest hits of the hemisphere rays of caller-supplied points (gather_maps_kernel.h) -------------
 static int check_gather_maps_args(const NraysScene* sc, const double* points, const double* normals, const NraysGatherMapsParams* p, const float* out_rgb, uint32_t flags) {
-    if (!sc || !points || !normals || !p || !p->dirs || !p->maps || !p->node_map || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
-    if (p->num_dirs < 1u || p->num_dirs > 1024u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_dirs must be in 1 .. 1024");
-    if (p->num_rotations > 1024u || (p->num_rotations && !p->rotations)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_rotations > 1024, or rotations is NULL");
-    if (!std::isfinite(p->bias) || !std::isfinite(p->miss_rgb[0]) || !std::isfinite(p->miss_rgb[1]) || !std::isfinite(p->miss_rgb[2]))
-        return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: bias and miss_rgb must be finite");
+    if (!sc || !points || !normals || !p || !p->maps || !p->node_map || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_hemisphere("NraysGatherMapsParams", p->dirs, p->num_dirs, p->rotations, p->num_rotations, p->bias, "miss_rgb",
+                         std::isfinite(p->miss_rgb[0]) && std::isfinite(p->miss_rgb[1]) && std::isfinite(p->miss_rgb[2])) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (!(p->max_toi > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: max_toi must be > 0 (+inf allowed)");
     if (p->num_maps < 1u || p->num_maps > NRAYS_GATHER_MAX_MAPS) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_maps must be in 1 .. 16");
     if (p->num_nodes != (uint32_t)sc->facts.host.shade.size()) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysGatherMapsParams: num_nodes is not the scene's node count");
@@ -214,73 +182,28 @@ static int gather_maps_impl(NraysScene* sc, uint32_t n, const double* points, co
             const NraysTexture& s = p->maps[m];
             table.map[m].texels = c[kMapsTexels + m]; table.map[m].width = s.width; table.map[m].height = s.height; table.map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
         }
-        const PointsIn in = points_in(c);
-        const int lp = occlusion_lanes_log2(sc, p->num_dirs);
-        const uint32_t slots = nc << lp; // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
-        const uint32_t grid = std::min<uint32_t>((slots + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-        const GatherMapsLaunch a{grid, b.stream, &sc->facts.d, nc, in.points, in.normals, in.hit_flags, in.keys, key_base, spec, &table, (const int32_t*)c[kMapsNodeMap],
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+        const GatherMapsLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, chunk_points(c, key_base), spec, &table, (const int32_t*)c[kMapsNodeMap],
                                  (const double*)c[kPointDirs], (const double*)c[kPointRotations], (float*)c[kMapsRgb], (uint32_t*)c[kMapsCounts], b.w->d_spill};
-        if (!launch_gather_maps_points(a, traversal_feat(sc), lp)) return set_last_error(NRAYS_ERR_UNSUPPORTED, "k_gather_maps_points: no such permutation");
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_gather_maps_points: ") + hipGetErrorString(e));
-        return NRAYS_OK;
+        return launch_gather_maps_points(a, traversal_feat(sc), lp) ? launch_status("k_gather_maps_points") : no_permutation("k_gather_maps_points");
     };
     return batch_run(sc, staged, stream, cols, ncols, n, point_chunk(p->num_dirs), "gather maps batch", launch);
 }
 
-// nrays_debug_occlusion_rays: ray j of point i, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].
+// nrays_debug_occlusion_rays: ray j of point i of the chunk, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].  NULL keys: key_base + i.
 __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
-                                                           const unsigned long long* __restrict__ keys, OcclusionSpec P, const double* __restrict__ dirs,
-                                                           const double* __restrict__ rotations, double* __restrict__ out_origins, double* __restrict__ out_dirs) {
+                                                           const unsigned long long* __restrict__ keys, unsigned long long key_base, OcclusionSpec P,
+                                                           const double* __restrict__ dirs, const double* __restrict__ rotations, double* __restrict__ out_origins,
+                                                           double* __restrict__ out_dirs) {
     const size_t rays = (size_t)n * P.num_dirs;
     for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < rays; r += (size_t)gridDim.x * kBlock) {
         const size_t i = r / P.num_dirs, j = r % P.num_dirs;
         const OccFrame f = occlusion_frame(D3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), D3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]),
-                                           keys ? keys[i] : (unsigned long long)i, P, rotations);
+                                           keys ? keys[i] : key_base + i, P, rotations);
         const d3 d = occlusion_dir(f, P.num_rotations != 0u, dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
         out_origins[3 * r] = f.o.x; out_origins[3 * r + 1] = f.o.y; out_origins[3 * r + 2] = f.o.z;
         out_dirs[3 * r] = d.x; out_dirs[3 * r + 1] = d.y; out_dirs[3 * r + 2] = d.z;
     }
-}
-
-// nrays_debug_occlusion_rays: the generator of k_occlusion_points alone, on host arrays, blocking; buffers of its own (a test probe).
-static int occlusion_rays_probe(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* p,
-                                double* out_origins, double* out_dirs) {
-    if (!sc || !points || !normals || !out_origins || !out_dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
-    if (check_occlusion_params(p) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
-    if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->facts.device));
-    int rc = ensure_own_stream(sc);
-    if (rc != NRAYS_OK) return rc;
-    const hipStream_t stream = sc->buf.own_stream;
-    const size_t rays = (size_t)n * p->num_dirs, table = 3 * (size_t)p->num_dirs + 2 * (size_t)p->num_rotations;
-    const size_t doubles = table + 6 * (size_t)n + (keys ? n : 0) + 6 * rays;
-    double* d_all = nullptr;
-    {
-        const hipError_t e = hipMalloc((void**)&d_all, doubles * sizeof(double));
-        if (e != hipSuccess) return set_last_error(e == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string("occlusion probe: ") + hipGetErrorString(e));
-    }
-    double* d_dirs = d_all; double* d_rot = d_dirs + 3 * (size_t)p->num_dirs; double* d_p = d_all + table; double* d_n = d_p + 3 * (size_t)n;
-    double* d_k = d_n + 3 * (size_t)n; double* d_oo = d_k + (keys ? n : 0); double* d_od = d_oo + 3 * rays;
-    auto up = [&](void* dst, const void* src, size_t bytes) { return src && bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream) : hipSuccess; };
-    hipError_t e = up(d_dirs, p->dirs, 24 * (size_t)p->num_dirs);
-    if (e == hipSuccess) e = up(d_rot, p->rotations, 16 * (size_t)p->num_rotations);
-    if (e == hipSuccess) e = up(d_p, points, 24 * (size_t)n);
-    if (e == hipSuccess) e = up(d_n, normals, 24 * (size_t)n);
-    if (e == hipSuccess) e = up(d_k, keys, 8 * (size_t)n);
-    if (e == hipSuccess) {
-        const uint32_t grid = (uint32_t)std::min<size_t>((rays + kBlock - 1) / kBlock, (size_t)kMaxGrid);
-        hipLaunchKernelGGL(k_occlusion_rays, dim3(grid), dim3(kBlock), 0, stream, n, (const double*)d_p, (const double*)d_n, keys ? (const unsigned long long*)d_k : nullptr,
-                           occlusion_spec(p), (const double*)d_dirs, p->num_rotations ? (const double*)d_rot : nullptr, d_oo, d_od);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(out_origins, d_oo, 24 * rays, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_dirs, d_od, 24 * rays, hipMemcpyDeviceToHost, stream);
-    const hipError_t es = hipStreamSynchronize(stream);
-    if (e == hipSuccess) e = es;
-    (void)hipFree(d_all);
-    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("occlusion probe: ") + hipGetErrorString(e));
-    return NRAYS_OK;
 }
 
 } // namespace nrays
@@ -297,9 +220,22 @@ int nrays_occlusion_points(NraysScene* sc, uint32_t n, const double* points, con
                            const NraysOcclusionParams* params, float* out_filter, uint32_t* out_open, uint32_t flags) {
     return occlusion_points_impl(sc, n, points, normals, hit_flags, keys, params, out_filter, out_open, flags, true, nullptr);
 }
-int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* params,
+// nrays_debug_occlusion_rays: the generator of k_occlusion_points alone, on host arrays, blocking, in the family's chunks (a test probe).
+int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint64_t* keys, const NraysOcclusionParams* p,
                                double* out_origins, double* out_dirs) {
-    return occlusion_rays_probe(sc, n, points, normals, keys, params, out_origins, out_dirs);
+    if (!sc || !points || !normals || !out_origins || !out_dirs) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_occlusion_params(p) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kOccRaysColumns];
+    point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, nullptr, keys);
+    occlusion_rays_columns(cols, out_origins, out_dirs, p->num_dirs);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
+        const GatherPoints in = chunk_points(c, key_base);
+        hipLaunchKernelGGL(k_occlusion_rays, dim3(launch_grid((uint64_t)nc * p->num_dirs)), dim3(kBlock), 0, b.stream, nc, in.points, in.normals, in.keys, in.key_base, occlusion_spec(p),
+                           (const double*)c[kPointDirs], (const double*)c[kPointRotations], (double*)c[kOccRaysOrigins], (double*)c[kOccRaysDirs]);
+        return launch_status("k_occlusion_rays");
+    };
+    return batch_run(sc, true, nullptr, cols, kOccRaysColumns, n, point_chunk(p->num_dirs), "occlusion probe", launch);
 }
 
 int nrays_gather_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
@@ -362,11 +298,9 @@ int nrays_debug_gather_sh_fold(NraysScene* sc, uint32_t n, const double* points,
     hipError_t e = hipSuccess;
     if (rc == NRAYS_OK && out_kernel_ms) { e = hipEventCreate(&ev[0]); if (e == hipSuccess) e = hipEventCreate(&ev[1]); if (e == hipSuccess) e = hipEventRecord(ev[0], b.stream); }
     if (rc == NRAYS_OK && e == hipSuccess) {
-        const PointsIn in = points_in(c);
-        const GatherPoints pts{in.points, in.normals, in.hit_flags, in.keys, 0ull};
         const uint32_t grid = std::min<uint32_t>((n + kShGroups - 1u) / kShGroups, kShMaxGrid);
-        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, b.stream, (const float*)c[kGatherRays], n, pts, OcclusionSpec{params->num_dirs, params->num_rotations, params->bias, 0.0},
-                           (const double*)c[kPointDirs], (const double*)c[kPointRotations], bands * bands, (float*)c[kGatherOut]);
+        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, b.stream, (const float*)c[kGatherRays], n, chunk_points(c, 0ull),
+                           hemisphere_spec(params->num_dirs, params->num_rotations, params->bias), (const double*)c[kPointDirs], (const double*)c[kPointRotations], bands * bands, (float*)c[kGatherOut]);
         e = hipGetLastError();
     }
     if (rc == NRAYS_OK && e == hipSuccess && out_kernel_ms) e = hipEventRecord(ev[1], b.stream);

@@ -209,6 +209,9 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_shade_points(D
 // the one generator: k_occlusion_points traces their rays and k_occlusion_rays (nrays_debug_occlusion_rays) stores them.
 struct OcclusionSpec { uint32_t num_dirs, num_rotations; double bias, max_toi; };
 struct OccFrame { d3 o, t, u, n; double c, s; };
+// The points of a chunk (columns kPointPoints .. kPointKeys of batch_stage.h; batch_call.h: chunk_points) and the index of its first point in the call: what the
+// launch structs of the point families carry and the kernels of the reordered gather take as one argument.
+struct GatherPoints { const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys; unsigned long long key_base; };
 
 // The branch-free orthonormal frame of Duff et al. 2017 around normal n (no singular normal), the biased origin, and the point's rotation
 // (c, s) = rotations[rng_hash(key, kSaltOcclusion) % R]; R = 0: no table is read and occlusion_dir leaves (lx, ly) untouched.
@@ -291,6 +294,12 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
         }
     }
 }
+// The arguments of one k_occlusion_points launch; the instantiations are compiled in ray_batches.hip, beside the other traversal kernels.  false = no such permutation.
+struct OcclusionLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; GatherPoints in; OcclusionSpec spec; const double* dirs; const double* rotations; float* out_filter;
+    uint32_t* out_open; uint32_t* spill;
+};
+bool launch_occlusion_points(const OcclusionLaunch& a, int feat, int lp);
 
 // ---- incoming light at caller-supplied points (nrays_gather_points*): the mean of Scene::trace over a point's hemisphere rays -----------------------------
 // The rays are k_occlusion_points' (occlusion_frame / occlusion_dir with the same point, normal, key, tables and bias: bit for bit the same rays); ray j of point i
@@ -363,8 +372,8 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(
 // The arguments of one k_gather_points launch.  The instantiations (trace_chain is the expensive template) are compiled in gather_inst.hip, a translation unit of
 // their own beside point_batches.hip, which calls launch_gather_points: false = no such permutation.
 struct GatherLaunch {
-    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys;
-    unsigned long long key_base; GatherSpec spec; const double* dirs; const double* rotations; float* out; float* ray_out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; GatherPoints in; GatherSpec spec; const double* dirs; const double* rotations; float* out; float* ray_out;
+    const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
 };
 bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
 
@@ -372,7 +381,6 @@ bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
 // A chunk's (point, direction) pairs — pair i * num_dirs + j is ray j of point i — are binned by ray_key.h's key and traced in bin order, one lane per pair; the
 // rays exist in registers only, rebuilt from (i, j) wherever they are needed (bounds, keys, trace).  What crosses memory per ray is the sort state (key, rank,
 // order: 16 bytes) and the colour (12 bytes), both of ONE chunk, in the handle's workspace.
-struct GatherPoints { const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys; unsigned long long key_base; };
 // Bit 0 of a point's flags clear: the point is skipped — none of its pairs is live, neither its point nor its normal is read.
 NR_DEV bool gather_point_live(const GatherPoints& in, uint32_t i) { return !in.hit_flags || (in.hit_flags[i] & 1u) != 0u; }
 NR_DEV unsigned long long gather_point_key(const GatherPoints& in, uint32_t i) { return in.keys ? in.keys[i] : in.key_base + i; }

@@ -1,6 +1,7 @@
 // ray_batches.hip — the caller-batch families that take rays or surface points as arrays, each a check, a column table (batch_stage.h) and a chunk launch run by
 // the driver of batch_call.h: nrays_trace_rays* (+ _ex), nrays_intersects_rays_device (+ _ex), nrays_cast_rays*, nrays_shade_points*; their kernels are the templates of
-// ray_batch_kernel.h, instantiated here, as is k_occlusion_points for point_batches.hip (launch_occlusion_points).  Also two probes with kernels of their own: nrays_debug_cast_batch (k_cast_batch) and nrays_debug_box_cull (k_box_cull).
+// ray_batch_kernel.h, instantiated here, as is k_occlusion_points for point_batches.hip (launch_occlusion_points).  Also two probes with kernels of their own:
+// nrays_debug_cast_batch (k_cast_batch; through the driver) and nrays_debug_box_cull (k_box_cull; no scene handle, buffers of its own).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -83,42 +84,94 @@ __global__ void __launch_bounds__(kBlock) k_box_cull(const BvhNode* __restrict__
     }
 }
 
-// ---- nrays_trace_rays*: Scene::trace on caller-supplied rays (scene.rs:147-193) ----------------------------------------------------------------------
-// One chunk (n <= kTraceChunk) of nrays_trace_rays*: k_trace_rays (`order`: its ordered form, lane j traces ray order[j]), then — double-branching scenes only — the k_bounce rounds of the
-// queued second children and k_fold_fixed, as a frame runs them for a sample batch (bounce.h: run_bounce_rounds).
-static int trace_chunk(NraysScene* sc, TraceWorkspace* w, uint32_t n, const double* o, const double* d, const double* refr, const float* energy,
-                       const unsigned long long* keys, unsigned long long key_base, uint32_t max_depth, float* out, hipStream_t stream, const uint32_t* order) {
-    const bool queued = sc->facts.host.any_double_branch;
-    if (queued) { // a frame's rule per pixel, per ray here: 4 slots, at least 2^16, at most 2^27
-        const uint64_t want = std::min<uint64_t>(std::max<uint64_t>(4ull * n, 1u << 16), 1ull << 27);
-        int rc = ensure_queue_pair(w->queue, w->queue_capacity, (uint32_t)want);
-        if (rc == NRAYS_OK) rc = ensure_fixed_sums(&w->d_fixed, &w->fixed_slots, &w->fixed_dirty, (size_t)n * 3, stream);
-        if (rc != NRAYS_OK) return rc;
-    }
-    HIP_TRY(hipMemsetAsync(w->d_counts, 0, kTraceCountWords * sizeof(uint32_t), stream));
-    unsigned int* overflow = w->d_counts + kTraceCountWords - 1;
-    QueueOut qo; qo.q = w->queue[1].q; qo.capacity = queued ? w->queue_capacity : 0u; qo.count = w->d_counts + 1; qo.overflow = overflow;
-    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-    const uint32_t keyed = sc->facts.host.any_area_light ? 1u : 0u;
-#define NR_TRACE_LAUNCH(STATS, FEAT)                                                                                                                                                     \
-    do {                                                                                                                                                                                 \
-        if (order) hipLaunchKernelGGL((k_trace_rays_ordered<STATS, FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, order, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill); \
-        else hipLaunchKernelGGL((k_trace_rays<STATS, FEAT>), dim3(grid), dim3(kBlock), 0, stream, sc->facts.d, n, o, d, refr, energy, keys, key_base, keyed, max_depth, out, qo, w->d_counters, w->d_spill); \
-    } while (0)
-    // (a scene with a non-finite light / colour / texel: the kernel that skips nothing, as its renders; its counters go to the batch's own block)
-    if (sc->facts.d.no_elide) NR_TRACE_LAUNCH(true, kFeatAll);
-    else if (shading_feat(sc) == (int)kFeatMesh) NR_TRACE_LAUNCH(false, kFeatMesh);
-    else NR_TRACE_LAUNCH(false, kFeatAll);
-#undef NR_TRACE_LAUNCH
-    HIP_TRY(hipGetLastError());
-    if (!queued) return NRAYS_OK;
-    const BounceRounds rounds{w->queue, w->queue_capacity, w->d_counts, overflow, w->d_fixed, &w->fixed_dirty, w->d_counters, w->d_spill, &sc->facts.d, sc->facts.d.no_elide != 0u, max_depth, out, (size_t)n * 3, sc->facts.num_cus};
-    uint32_t overflowed = 0u;
-    const int rc = run_bounce_rounds(rounds, stream, &overflowed);
-    if (rc != NRAYS_OK) return rc;
-    if (overflowed) return set_last_error(NRAYS_ERR_QUEUE_OVERFLOW, "continuation-ray queue overflow: some traced colours are incomplete");
-    return NRAYS_OK;
+uint32_t launch_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + kBlock - 1) / kBlock, (uint64_t)kMaxGrid); }
+
+// ---- the launches of this unit's kernels (batch_call.h: the idiom).  `order` non-null selects the ordered form of a kernel: lane j serves ray order[j]. ------------------------
+struct TraceLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const uint32_t* order; const double* o; const double* dir; const double* refr; const float* energy;
+    const unsigned long long* keys; unsigned long long key_base; uint32_t keyed, max_depth; float* out; const QueueOut* qo; DeviceCounters* ctr; uint32_t* spill;
+};
+template <bool STATS, int FEAT, bool ORDERED>
+static bool launch_if(const TraceLaunch& a, bool stats, int feat) {
+    if (stats != STATS || feat != FEAT || (a.order != nullptr) != ORDERED) return false;
+    if constexpr (ORDERED) hipLaunchKernelGGL((k_trace_rays_ordered<STATS, FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.order, a.o, a.dir, a.refr, a.energy, a.keys, a.key_base,
+                                              a.keyed, a.max_depth, a.out, *a.qo, a.ctr, a.spill);
+    else hipLaunchKernelGGL((k_trace_rays<STATS, FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.o, a.dir, a.refr, a.energy, a.keys, a.key_base, a.keyed, a.max_depth, a.out,
+                            *a.qo, a.ctr, a.spill);
+    return true;
 }
+static bool launch_trace_rays(const TraceLaunch& a, bool stats, int feat) {
+    return launch_if<false, kFeatAll, false>(a, stats, feat) || launch_if<false, kFeatAll, true>(a, stats, feat) || launch_if<false, kFeatMesh, false>(a, stats, feat) ||
+           launch_if<false, kFeatMesh, true>(a, stats, feat) || launch_if<true, kFeatAll, false>(a, stats, feat) || launch_if<true, kFeatAll, true>(a, stats, feat);
+}
+struct IntersectsLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const uint32_t* order; const double* o; const double* dir; const double* max_toi; float* out_filter; uint32_t* out_lit;
+    uint32_t* spill;
+};
+template <int FEAT, bool ORDERED>
+static bool launch_if(const IntersectsLaunch& a, int feat) {
+    if (feat != FEAT || (a.order != nullptr) != ORDERED) return false;
+    if constexpr (ORDERED) hipLaunchKernelGGL((k_intersects_rays_ordered<FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.order, a.o, a.dir, a.max_toi, a.out_filter, a.out_lit, a.spill);
+    else hipLaunchKernelGGL((k_intersects_rays<FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.o, a.dir, a.max_toi, a.out_filter, a.out_lit, a.spill);
+    return true;
+}
+static bool launch_intersects_rays(const IntersectsLaunch& a, int feat) {
+    return launch_if<kFeatAll, false>(a, feat) || launch_if<kFeatAll, true>(a, feat) || launch_if<kFeatMesh, false>(a, feat) || launch_if<kFeatMesh, true>(a, feat);
+}
+struct CastLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n; const uint32_t* order; const double* o; const double* dir; const double* max_toi; double* toi; int32_t* node;
+    double* normal; double* uv; int32_t* prim; uint32_t* flags; uint32_t* spill;
+};
+template <int FEAT, bool ORDERED>
+static bool launch_if(const CastLaunch& a, int feat) {
+    if (feat != FEAT || (a.order != nullptr) != ORDERED) return false;
+    if constexpr (ORDERED) hipLaunchKernelGGL((k_cast_rays_ordered<FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.order, a.o, a.dir, a.max_toi, a.toi, a.node, a.normal, a.uv, a.prim,
+                                              a.flags, a.spill);
+    else hipLaunchKernelGGL((k_cast_rays<FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.o, a.dir, a.max_toi, a.toi, a.node, a.normal, a.uv, a.prim, a.flags, a.spill);
+    return true;
+}
+static bool launch_cast_rays(const CastLaunch& a, int feat) {
+    return launch_if<kFeatAll, false>(a, feat) || launch_if<kFeatAll, true>(a, feat) || launch_if<kFeatMesh, false>(a, feat) || launch_if<kFeatMesh, true>(a, feat);
+}
+// (kFeatAll is right for every scene: it holds kFeatMultiSample, and the shadow rays are traced inside the light loop)
+struct ShadeLaunch {
+    uint32_t grid; hipStream_t stream; const DScene* d; uint32_t n, num_nodes; const double* points; const double* normals; const double* view_dirs; const double* uvs; const int32_t* nodes;
+    const uint32_t* hit_flags; const unsigned long long* keys; unsigned long long key_base; float* out; DeviceCounters* ctr; uint32_t* spill;
+};
+template <bool STATS>
+static bool launch_if(const ShadeLaunch& a, bool stats) {
+    if (stats != STATS) return false;
+    hipLaunchKernelGGL((k_shade_points<STATS, kFeatAll>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.num_nodes, a.points, a.normals, a.view_dirs, a.uvs, a.nodes, a.hit_flags, a.keys,
+                       a.key_base, a.out, a.ctr, a.spill);
+    return true;
+}
+static bool launch_shade_points(const ShadeLaunch& a, bool stats) { return launch_if<false>(a, stats) || launch_if<true>(a, stats); }
+// k_occlusion_points (nrays_occlusion_points*, point_batches.hip) is instantiated in this unit, beside the other traversal kernels: in a unit without them the compiler
+// allocates and schedules its LP = 3 and 6 forms differently (profiles/README.md, batch_driver_kres_*).  feat: kFeatMesh or kFeatAll; lp: 0, 3 or 6.
+template <int FEAT, int LP>
+static bool launch_if(const OcclusionLaunch& a, int feat, int lp) {
+    if (feat != FEAT || lp != LP) return false;
+    hipLaunchKernelGGL((k_occlusion_points<FEAT, LP>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.n, a.in.points, a.in.normals, a.in.hit_flags, a.in.keys, a.in.key_base, a.spec, a.dirs,
+                       a.rotations, a.out_filter, a.out_open, a.spill);
+    return true;
+}
+bool launch_occlusion_points(const OcclusionLaunch& a, int feat, int lp) {
+    return launch_if<kFeatAll, 0>(a, feat, lp) || launch_if<kFeatAll, 3>(a, feat, lp) || launch_if<kFeatAll, 6>(a, feat, lp) || launch_if<kFeatMesh, 0>(a, feat, lp) ||
+           launch_if<kFeatMesh, 3>(a, feat, lp) || launch_if<kFeatMesh, 6>(a, feat, lp);
+}
+struct CastBatchLaunch { uint32_t grid; hipStream_t stream; const DScene* d; uint32_t mode, n; const double* o; const double* dir; const double* max_toi; NraysCastResult* out; uint32_t* spill; };
+template <int FEAT>
+static bool launch_if(const CastBatchLaunch& a, int feat) {
+    if (feat != FEAT) return false;
+    hipLaunchKernelGGL((k_cast_batch<FEAT>), dim3(a.grid), dim3(kBlock), 0, a.stream, *a.d, a.mode, a.n, a.o, a.dir, a.max_toi, a.out, a.spill);
+    return true;
+}
+static bool launch_cast_batch(const CastBatchLaunch& a, int feat) { return launch_if<kFeatAll>(a, feat) || launch_if<kFeatMesh>(a, feat); }
+
+// ---- nrays_trace_rays*: Scene::trace on caller-supplied rays (scene.rs:147-193) ----------------------------------------------------------------------
+// One chunk (nc <= kTraceChunk): the reorder when it is due, k_trace_rays or its ordered form, then — double-branching scenes only — the k_bounce rounds of the queued
+// second children and k_fold_fixed, as a frame runs them for a sample batch (bounce.h).  The permutation: a scene with a non-finite light / colour / texel gets the
+// kernel that skips nothing, as its renders (its counters go to the batch's own block); kFeatMesh for scenes of opaque meshes, kFeatAll otherwise.
 static int trace_rays_impl(NraysScene* sc, uint32_t n, const double* o, const double* d, const double* refr, const float* energy, const uint64_t* keys, uint32_t max_depth,
                            float* out, uint32_t flags, bool staged, hipStream_t stream) {
     if (!sc || !o || !d || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
@@ -126,14 +179,19 @@ static int trace_rays_impl(NraysScene* sc, uint32_t n, const double* o, const do
     if (n == 0) return NRAYS_OK;
     StageColumn cols[kTraceColumns];
     trace_columns(cols, o, d, refr, keys, energy, out);
-    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
+    const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n), stats = sc->facts.d.no_elide != 0u;
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
         const double *co = (const double*)c[kRayO], *cd = (const double*)c[kRayD];
         const uint32_t* order = nullptr;
-        const int rc = chunk_order(sc, b.w, reorder, nc, co, cd, b.stream, &order);
+        QueueOut qo;
+        int rc = chunk_order(sc, b.w, reorder, nc, co, cd, b.stream, &order);
+        if (rc == NRAYS_OK) rc = queued_trace_begin(sc, b.w, nc, b.stream, &qo);
         if (rc != NRAYS_OK) return rc;
-        return trace_chunk(sc, b.w, nc, co, cd, (const double*)c[kTraceRefr], (const float*)c[kTraceEnergy], (const unsigned long long*)c[kTraceKeys], key_base, max_depth,
-                           (float*)c[kTraceOut], b.stream, order);
+        const TraceLaunch a{launch_grid(nc), b.stream, &sc->facts.d, nc, order, co, cd, (const double*)c[kTraceRefr], (const float*)c[kTraceEnergy], (const unsigned long long*)c[kTraceKeys],
+                            key_base, sc->facts.host.any_area_light ? 1u : 0u, max_depth, (float*)c[kTraceOut], &qo, b.w->d_counters, b.w->d_spill};
+        if (!launch_trace_rays(a, stats, stats ? (int)kFeatAll : shading_feat(sc))) return no_permutation("k_trace_rays");
+        HIP_TRY(hipGetLastError());
+        return sc->facts.host.any_double_branch ? queued_trace_finish(sc, b.w, nc, max_depth, a.out, "traced", b.stream) : (int)NRAYS_OK;
     };
     return batch_run(sc, staged, stream, cols, kTraceColumns, n, kTraceChunk, "trace batch", launch);
 }
@@ -148,22 +206,12 @@ static int intersects_rays_impl(NraysScene* sc, uint32_t n, const double* origin
     intersects_columns(cols, origins, dirs, max_toi, out_filter, out_lit);
     const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
-        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD], *t = (const double*)c[kIsectToi];
-        float* filter = (float*)c[kIsectFilter]; uint32_t* lit = (uint32_t*)c[kIsectLit];
-        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD];
         const uint32_t* order = nullptr;
         const int rc = chunk_order(sc, b.w, reorder, nc, o, d, b.stream, &order);
         if (rc != NRAYS_OK) return rc;
-#define NR_ISECT_LAUNCH(FEAT)                                                                                                                                                \
-    do {                                                                                                                                                                     \
-        if (order) hipLaunchKernelGGL((k_intersects_rays_ordered<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, order, o, d, t, filter, lit, b.w->d_spill); \
-        else hipLaunchKernelGGL((k_intersects_rays<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, o, d, t, filter, lit, b.w->d_spill);                      \
-    } while (0)
-        if (traversal_feat(sc) == (int)kFeatMesh) NR_ISECT_LAUNCH(kFeatMesh); else NR_ISECT_LAUNCH(kFeatAll);
-#undef NR_ISECT_LAUNCH
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_intersects_rays: ") + hipGetErrorString(e));
-        return (int)NRAYS_OK;
+        const IntersectsLaunch a{launch_grid(nc), b.stream, &sc->facts.d, nc, order, o, d, (const double*)c[kIsectToi], (float*)c[kIsectFilter], (uint32_t*)c[kIsectLit], b.w->d_spill};
+        return launch_intersects_rays(a, traversal_feat(sc)) ? launch_status("k_intersects_rays") : no_permutation("k_intersects_rays");
     };
     return batch_run(sc, false, stream, cols, kIsectColumns, n, kTraceChunk, "intersects batch", launch);
 }
@@ -179,30 +227,19 @@ static int cast_rays_impl(NraysScene* sc, uint32_t n, const double* origins, con
     const bool reorder = (flags & NRAYS_RAYS_UNORDERED) && reorder_pays(sc, n);
     // One chunk: the reorder when it is due, then k_cast_rays or its ordered form.
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
-        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD], *t = (const double*)c[kCastMaxToi];
-        double *toi = (double*)c[kCastToi], *normal = (double*)c[kCastNormal], *uv = (double*)c[kCastUv];
-        int32_t *node = (int32_t*)c[kCastNode], *prim = (int32_t*)c[kCastPrim]; uint32_t* hit = (uint32_t*)c[kCastFlags];
-        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
+        const double *o = (const double*)c[kRayO], *d = (const double*)c[kRayD];
         const uint32_t* order = nullptr;
         const int rc = chunk_order(sc, b.w, reorder, nc, o, d, b.stream, &order);
         if (rc != NRAYS_OK) return rc;
-#define NR_CAST_LAUNCH(FEAT)                                                                                                                                                              \
-    do {                                                                                                                                                                                  \
-        if (order) hipLaunchKernelGGL((k_cast_rays_ordered<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, order, o, d, t, toi, node, normal, uv, prim, hit, b.w->d_spill); \
-        else hipLaunchKernelGGL((k_cast_rays<FEAT>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, o, d, t, toi, node, normal, uv, prim, hit, b.w->d_spill);                      \
-    } while (0)
-        if (traversal_feat(sc) == (int)kFeatMesh) NR_CAST_LAUNCH(kFeatMesh); else NR_CAST_LAUNCH(kFeatAll);
-#undef NR_CAST_LAUNCH
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_cast_rays: ") + hipGetErrorString(e));
-        return (int)NRAYS_OK;
+        const CastLaunch a{launch_grid(nc), b.stream, &sc->facts.d, nc, order, o, d, (const double*)c[kCastMaxToi], (double*)c[kCastToi], (int32_t*)c[kCastNode], (double*)c[kCastNormal],
+                           (double*)c[kCastUv], (int32_t*)c[kCastPrim], (uint32_t*)c[kCastFlags], b.w->d_spill};
+        return launch_cast_rays(a, traversal_feat(sc)) ? launch_status("k_cast_rays") : no_permutation("k_cast_rays");
     };
     return batch_run(sc, staged, stream, cols, kCastColumns, n, kTraceChunk, "cast batch", launch);
 }
 
 // ---- nrays_shade_points*: Material::compute on caller-supplied surface points (material.rs:8-16, phong_material.rs:72-151) -----------------------
-// kFeatAll is right for every scene (it holds kFeatMultiSample: the shadow rays are traced inside the light loop); a scene with a non-finite
-// light / colour / texel gets the kernel that skips nothing, as its renders, with the batch's own counter block.
+// A scene with a non-finite light / colour / texel gets the kernel that skips nothing, as its renders, with the batch's own counter block.
 static int shade_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
                              const uint32_t* hit_flags, const uint64_t* keys, float* out, uint32_t flags, bool staged, hipStream_t stream) {
     if (!sc || !points || !normals || !view_dirs || !nodes || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
@@ -211,28 +248,12 @@ static int shade_points_impl(NraysScene* sc, uint32_t n, const double* points, c
     StageColumn cols[kShadeColumns];
     shade_columns(cols, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out);
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
-        const double *p = (const double*)c[kShadePoints], *nm = (const double*)c[kShadeNormals], *v = (const double*)c[kShadeViews], *uv = (const double*)c[kShadeUvs];
-        const int32_t* node = (const int32_t*)c[kShadeNodes]; const uint32_t* hit = (const uint32_t*)c[kShadeHit]; const unsigned long long* k = (const unsigned long long*)c[kShadeKeys];
-        const uint32_t grid = std::min<uint32_t>((nc + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-        const uint32_t num_nodes = (uint32_t)sc->facts.host.shade.size();
-        if (sc->facts.d.no_elide) hipLaunchKernelGGL((k_shade_points<true, kFeatAll>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, num_nodes, p, nm, v, uv, node, hit, k, key_base, (float*)c[kShadeOut], b.w->d_counters, b.w->d_spill);
-        else hipLaunchKernelGGL((k_shade_points<false, kFeatAll>), dim3(grid), dim3(kBlock), 0, b.stream, sc->facts.d, nc, num_nodes, p, nm, v, uv, node, hit, k, key_base, (float*)c[kShadeOut], b.w->d_counters, b.w->d_spill);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_shade_points: ") + hipGetErrorString(e));
-        return (int)NRAYS_OK;
+        const ShadeLaunch a{launch_grid(nc), b.stream, &sc->facts.d, nc, (uint32_t)sc->facts.host.shade.size(), (const double*)c[kShadePoints], (const double*)c[kShadeNormals],
+                            (const double*)c[kShadeViews], (const double*)c[kShadeUvs], (const int32_t*)c[kShadeNodes], (const uint32_t*)c[kShadeHit], (const unsigned long long*)c[kShadeKeys],
+                            key_base, (float*)c[kShadeOut], b.w->d_counters, b.w->d_spill};
+        return launch_shade_points(a, sc->facts.d.no_elide != 0u) ? launch_status("k_shade_points") : no_permutation("k_shade_points");
     };
     return batch_run(sc, staged, stream, cols, kShadeColumns, n, kTraceChunk, "shade batch", launch);
-}
-
-// k_occlusion_points (nrays_occlusion_points*, point_batches.hip) is instantiated in this unit, beside the other traversal kernels: in a unit without them the compiler
-// allocates and schedules its LP = 3 and 6 forms differently (profiles/README.md, batch_driver_kres_*).  feat: kFeatMesh or kFeatAll; lp: 0, 3 or 6.
-void launch_occlusion_points(int feat, int lp, uint32_t grid, hipStream_t stream, const DScene& S, uint32_t nc, const double* points, const double* normals, const uint32_t* hit_flags,
-                             const unsigned long long* keys, unsigned long long key_base, const OcclusionSpec& spec, const double* dirs, const double* rotations, float* out_filter,
-                             uint32_t* out_open, uint32_t* spill) {
-#define NR_OCC_LAUNCH(FEAT, LP) hipLaunchKernelGGL((k_occlusion_points<FEAT, LP>), dim3(grid), dim3(kBlock), 0, stream, S, nc, points, normals, hit_flags, keys, key_base, spec, dirs, rotations, out_filter, out_open, spill)
-    if (feat == (int)kFeatMesh) { if (lp == 0) NR_OCC_LAUNCH(kFeatMesh, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatMesh, 3); else NR_OCC_LAUNCH(kFeatMesh, 6); }
-    else { if (lp == 0) NR_OCC_LAUNCH(kFeatAll, 0); else if (lp == 3) NR_OCC_LAUNCH(kFeatAll, 3); else NR_OCC_LAUNCH(kFeatAll, 6); }
-#undef NR_OCC_LAUNCH
 }
 
 } // namespace nrays
@@ -241,29 +262,19 @@ using namespace nrays;
 
 extern "C" {
 
+// k_cast_batch on host arrays, blocking, in the families' chunks (a test probe).
+static_assert(sizeof(NraysCastResult) == 56, "tests/batch_stage_shim.cpp restates the record's size");
 int nrays_debug_cast_batch(NraysScene* sc, uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* max_toi, NraysCastResult* out) {
     if (!sc || !origins || !dirs || !out || mode > 1u || (mode == 1u && !max_toi)) return set_last_error(NRAYS_ERR_BAD_ARG, "bad cast-batch arguments");
     if (n == 0) return NRAYS_OK;
-    HIP_TRY(hipSetDevice(sc->facts.device));
-    if (sc->last.have) HIP_TRY(hipStreamSynchronize(sc->last.stream));
-    { const int rs = ensure_spill(sc, &sc->buf.d_spill); if (rs != NRAYS_OK) return rs; }
-    double *d_o = nullptr, *d_d = nullptr, *d_t = nullptr; NraysCastResult* d_r = nullptr;
-    auto release = [&]() { if (d_o) (void)hipFree(d_o); if (d_d) (void)hipFree(d_d); if (d_t) (void)hipFree(d_t); if (d_r) (void)hipFree(d_r); };
-#define CAST_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { release(); return set_last_error(e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    const size_t vb = (size_t)n * 3 * sizeof(double);
-    CAST_TRY(hipMalloc((void**)&d_o, vb)); CAST_TRY(hipMalloc((void**)&d_d, vb)); CAST_TRY(hipMalloc((void**)&d_r, (size_t)n * sizeof(NraysCastResult)));
-    CAST_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CAST_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
-    if (mode == 1u) { CAST_TRY(hipMalloc((void**)&d_t, (size_t)n * sizeof(double))); CAST_TRY(hipMemcpy(d_t, max_toi, (size_t)n * sizeof(double), hipMemcpyHostToDevice)); }
-    const uint32_t grid = std::min<uint32_t>((n + kBlock - 1) / kBlock, (uint32_t)kMaxGrid);
-    CAST_TRY(sc->buf.own_stream ? hipSuccess : hipStreamCreate(&sc->buf.own_stream));
-    if (traversal_feat(sc) == (int)kFeatMesh) hipLaunchKernelGGL((k_cast_batch<kFeatMesh>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
-    else hipLaunchKernelGGL((k_cast_batch<kFeatAll>), dim3(grid), dim3(kBlock), 0, sc->buf.own_stream, sc->facts.d, mode, n, d_o, d_d, d_t, d_r, sc->buf.d_spill);
-    CAST_TRY(hipGetLastError());
-    CAST_TRY(hipStreamSynchronize(sc->buf.own_stream));
-    CAST_TRY(hipMemcpy(out, d_r, (size_t)n * sizeof(NraysCastResult), hipMemcpyDeviceToHost));
-#undef CAST_TRY
-    release();
-    return NRAYS_OK;
+    StageColumn cols[kCastProbeColumns];
+    cast_probe_columns(cols, origins, dirs, mode == 1u ? max_toi : nullptr, out, sizeof(NraysCastResult));
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const CastBatchLaunch a{launch_grid(nc), b.stream, &sc->facts.d, mode, nc, (const double*)c[kRayO], (const double*)c[kRayD], (const double*)c[kCastProbeMaxToi],
+                                (NraysCastResult*)c[kCastProbeOut], b.w->d_spill};
+        return launch_cast_batch(a, traversal_feat(sc)) ? launch_status("k_cast_batch") : no_permutation("k_cast_batch");
+    };
+    return batch_run(sc, true, nullptr, cols, kCastProbeColumns, n, kTraceChunk, "cast-batch probe", launch);
 }
 
 int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* best, const float* boxes, const uint32_t* slots,
@@ -291,8 +302,7 @@ int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const
     CULL_TRY(hipMemcpy(d_o, origins, vb, hipMemcpyHostToDevice)); CULL_TRY(hipMemcpy(d_d, dirs, vb, hipMemcpyHostToDevice));
     CULL_TRY(hipMemcpy(d_b, best, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
     const uint64_t threads = mode == 1u ? (uint64_t)n * 64u : (uint64_t)n;
-    const uint32_t grid = (uint32_t)std::min<uint64_t>((threads + kBlock - 1) / kBlock, (uint64_t)kMaxGrid);
-    hipLaunchKernelGGL(k_box_cull, dim3(grid), dim3(kBlock), 0, (hipStream_t)0, (const BvhNode*)d_n, mode, n, (const double*)d_o, (const double*)d_d, (const double*)d_b, d_k, d_bits, d_i);
+    hipLaunchKernelGGL(k_box_cull, dim3(launch_grid(threads)), dim3(kBlock), 0, (hipStream_t)0, (const BvhNode*)d_n, mode, n, (const double*)d_o, (const double*)d_d, (const double*)d_b, d_k, d_bits, d_i);
     CULL_TRY(hipGetLastError());
     CULL_TRY(hipDeviceSynchronize());
     CULL_TRY(hipMemcpy(keys, d_k, (size_t)n * 4 * sizeof(float), hipMemcpyDeviceToHost)); CULL_TRY(hipMemcpy(bits, d_bits, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));

@@ -345,10 +345,9 @@ int nrays_debug_gather_order(NraysScene* sc, uint32_t n, const double* points, c
     if (rc == NRAYS_OK) rc = batch_upload(b, 0, n, what);
     // (a skipped point's entries come back as the caller filled them)
     if (rc == NRAYS_OK) rc = order_status(hipMemcpyAsync(w->d_ray_keys, out_keys, (size_t)pairs * sizeof(uint64_t), hipMemcpyHostToDevice, b.stream), what);
-    if (rc == NRAYS_OK) {
-        const GatherPoints pts{(const double*)c[kPointPoints], (const double*)c[kPointNormals], (const uint32_t*)c[kPointHit], (const unsigned long long*)c[kPointKeys], 0ull};
-        rc = gather_order_chunk(sc, w, pairs, pts, OcclusionSpec{params->num_dirs, params->num_rotations, params->bias, 0.0}, (const double*)c[kPointDirs], (const double*)c[kPointRotations], b.stream);
-    }
+    if (rc == NRAYS_OK)
+        rc = gather_order_chunk(sc, w, pairs, chunk_points(c, 0ull), hemisphere_spec(params->num_dirs, params->num_rotations, params->bias), (const double*)c[kPointDirs],
+                                (const double*)c[kPointRotations], b.stream);
     if (rc == NRAYS_OK) rc = order_status(hipMemcpyAsync(&out_info[3], w->d_ray_bins + kNumBins, sizeof(uint32_t), hipMemcpyDeviceToHost, b.stream), what);
     if (rc == NRAYS_OK) rc = order_status(hipStreamSynchronize(b.stream), what);
     if (rc == NRAYS_OK && out_info[3] > pairs) rc = set_last_error(NRAYS_ERR_HIP, "nrays_debug_gather_order: more pairs placed than the chunk holds");

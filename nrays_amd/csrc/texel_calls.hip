@@ -51,9 +51,7 @@ static int texel_owner_pass(NraysScene* sc, TraceWorkspace* w, uint32_t node, ui
     hipLaunchKernelGGL(k_texel_apply, dim3(scan_grid), dim3(kTexelBlock), 0, stream, off, s.count, (const unsigned long long*)w->d_texel_blocks);
     hipLaunchKernelGGL(k_texel_owner, dim3((uint32_t)sc->facts.num_cus * kTexelOwnerWgsPerCu), dim3(kTexelBlock), 0, stream, sc->facts.d.tris, sc->facts.d.triuvs, s.first, s.count, L,
                        (const unsigned long long*)off, (const unsigned long long*)total, owner);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_texel_owner: ") + hipGetErrorString(e));
-    return NRAYS_OK;
+    return launch_status("k_texel_owner");
 }
 static int texel_resolve_pass(NraysScene* sc, TraceWorkspace* w, uint32_t node, uint32_t width, uint32_t height, uint32_t flags, const TexelOutputs& out, hipStream_t stream) {
     const NodeSurface& s = sc->facts.host.surface[node];
@@ -64,9 +62,7 @@ static int texel_resolve_pass(NraysScene* sc, TraceWorkspace* w, uint32_t node, 
     X.flags = s.flags; X.flip = (flags & NRAYS_TEXELS_FLIP_NORMALS) ? 1u : 0u;
     hipLaunchKernelGGL(k_texel_resolve, dim3((width * height + kTexelBlock - 1u) / kTexelBlock), dim3(kTexelBlock), 0, stream, sc->facts.d.tris, sc->facts.d.triuvs, L, X,
                        (const unsigned long long*)w->d_texel_owner, out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_texel_resolve: ") + hipGetErrorString(e));
-    return NRAYS_OK;
+    return launch_status("k_texel_resolve");
 }
 
 // The blocking forms and nrays_debug_surface_texels_passes stage every output of a lattice; the caller's absent ones are not read back.
@@ -141,9 +137,7 @@ static int dilate_passes(TraceWorkspace* w, const DilateArgs& a, hipStream_t str
     hipLaunchKernelGGL(k_dilate_rows, dim3((L.h * L.col_blocks + kDilateWaves - 1u) / kDilateWaves), dim3(kDilateBlock), 0, stream, L, a.flags_in, dx);
     hipLaunchKernelGGL(k_dilate_cols, dim3(L.col_blocks, (L.h + T - 1u) / T), dim3(kDilateBlock), (size_t)(T + 2u * a.radius) * 64u * sizeof(int16_t), stream, L,
                        (const int16_t*)dx, a.flags_in, a.values ? a.channels : 0u, vec4, a.values, a.source, a.flags_out);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_dilate_cols: ") + hipGetErrorString(e));
-    return NRAYS_OK;
+    return launch_status("k_dilate_cols");
 }
 // Device form: flags_in and flags_out may be one array.  Blocking form: the arena holds them apart.
 static int dilate_texels_impl(NraysScene* sc, const DilateArgs& a, uint32_t flags, bool staged, hipStream_t stream) {
@@ -189,9 +183,7 @@ static int filter_pass(const FilterArgs& a, hipStream_t stream) {
     case 3u: hipLaunchKernelGGL(k_filter_texels<3>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, 0u); break;
     default: hipLaunchKernelGGL(k_filter_texels<4>, grid, dim3(kFilterBlock), 0, stream, L, a.flags_in, a.points, a.normals, a.values_in, a.values_out, vec4); break;
     }
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_last_error(NRAYS_ERR_HIP, std::string("k_filter_texels: ") + hipGetErrorString(e));
-    return NRAYS_OK;
+    return launch_status("k_filter_texels");
 }
 static int filter_texels_impl(NraysScene* sc, const FilterArgs& a, uint32_t flags, bool staged, hipStream_t stream) {
     { const int rc = check_filter_args(sc, a, flags); if (rc != NRAYS_OK) return rc; }

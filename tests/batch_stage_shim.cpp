@@ -9,14 +9,14 @@ using namespace nrays;
 extern "C" {
 
 enum { kFamTrace, kFamIntersects, kFamCast, kFamShade, kFamOcclusion, kFamGather, kFamGatherMaps, kFamSurfaceTexels, kFamDilate, kFamFilter, kFamRayProbe, kFamPointProbe,
-       kFamShFoldProbe, kFamCount };
+       kFamShFoldProbe, kFamCastProbe, kFamOccRaysProbe, kFamCount };
 
 // mask: bit k = the family's k-th optional array is given.  bands: 0 = nrays_gather_points, 1 .. 3 = nrays_gather_sh_points.
 struct BatchStageCase { uint32_t family, mask, num_dirs, num_rotations, bands, channels, num_maps, map_w, map_h, num_nodes; };
 
 // The number of optional arrays of a family (the bits of BatchStageCase::mask that count).
 int batch_stage_optional(uint32_t family) {
-    static const int opt[kFamCount] = {3, 0, 5, 3, 3, 2, 3, 4, 3, 0, 0, 2, 2};
+    static const int opt[kFamCount] = {3, 0, 5, 3, 3, 2, 3, 4, 3, 0, 0, 2, 2, 1, 1};
     return family < kFamCount ? opt[family] : -1;
 }
 
@@ -55,6 +55,11 @@ int batch_stage_table(const BatchStageCase* cs, uint64_t cap, uint64_t* off, uin
     case kFamFilter: n = filter_columns(c, d8, d8, f4, f4 + 1, cs->channels, u4); break;
     case kFamRayProbe: n = ray_columns(c, d8, d8); break;
     case kFamPointProbe: n = point_columns(c, d8, cs->num_dirs, rot, cs->num_rotations, d8, d8, opt(0, u4), opt(1, u8)); break;
+    case kFamCastProbe: n = cast_probe_columns(c, d8, d8, opt(0, d8), u8, 56 /* sizeof(NraysCastResult) */); break;
+    case kFamOccRaysProbe:
+        point_columns(c, d8, cs->num_dirs, rot, cs->num_rotations, d8, d8, nullptr, opt(0, u8));
+        n = occlusion_rays_columns(c, d8, d8, cs->num_dirs);
+        break;
     default: return -1;
     }
     if (n < 0 || n > kStageMaxColumns) return -1;
@@ -91,7 +96,7 @@ uint64_t batch_stage_sweep(uint64_t* cases) {
                 for (uint32_t nd : dirs) for (uint32_t nr : rots)
                     for (uint32_t bands = 0; bands <= 3; ++bands) for (uint32_t ch = 1; ch <= 4; ++ch)
                         for (uint32_t nm : maps) for (auto& wh : sides) {
-                            const bool points = fam == kFamOcclusion || fam == kFamGather || fam == kFamGatherMaps || fam == kFamPointProbe || fam == kFamShFoldProbe;
+                            const bool points = fam == kFamOcclusion || fam == kFamGather || fam == kFamGatherMaps || fam == kFamPointProbe || fam == kFamShFoldProbe || fam == kFamOccRaysProbe;
                             if (!points && (nd != 1 || nr != 0)) continue;                                  // (the parameter does not reach the family's table: once)
                             if (fam != kFamGather && fam != kFamShFoldProbe && bands != 0) continue;
                             if (fam == kFamShFoldProbe && bands == 0) continue;

@@ -12,8 +12,9 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_COLUMNS = 32
-FAMILIES = ("trace", "intersects", "cast", "shade", "occlusion", "gather", "gather_maps", "surface_texels", "dilate", "filter", "ray_probe", "point_probe", "sh_fold_probe")
-POINT_FAMILIES = ("occlusion", "gather", "gather_maps", "point_probe", "sh_fold_probe")
+FAMILIES = ("trace", "intersects", "cast", "shade", "occlusion", "gather", "gather_maps", "surface_texels", "dilate", "filter", "ray_probe", "point_probe", "sh_fold_probe", "cast_probe",
+            "occlusion_rays_probe")
+POINT_FAMILIES = ("occlusion", "gather", "gather_maps", "point_probe", "sh_fold_probe", "occlusion_rays_probe")
 CAPS = (1, 2, 3, 63, 64, 65, 4097)
 
 
@@ -106,13 +107,17 @@ def test_an_absent_array_is_not_copied_and_moves_nothing(shim, family):
 
 def test_the_tables_are_what_the_calls_stage(shim):
     """Bytes an item, by hand from include/nrays_abi.h: a cast ray 24 + 24 + 8 in and 8 + 4 + 24 + 16 + 4 + 4 out; a gather_sh point of 3 bands 27 floats out; the value
-    arrays of the texel calls on 16-byte boundaries."""
+    arrays of the texel calls on 16-byte boundaries; a record of the cast probe 56 bytes (NraysCastResult); the rays of the occlusion probe 24 bytes a direction, twice."""
     cols, _ = shim.table(3, "cast", mask=31)
     assert [c[1] // 3 for c in cols] == [24, 24, 8, 8, 4, 24, 16, 4, 4]
     cols, _ = shim.table(1, "gather", mask=3, num_dirs=16, num_rotations=5, bands=3)
     assert [c[1] for c in cols] == [16 * 24, 5 * 16, 24, 24, 4, 8, 27 * 4, 0]
     cols, _ = shim.table(1, "gather_maps", mask=7, num_dirs=1, num_maps=16, map_w=3, map_h=5)
     assert len(cols) == 9 + 16 and all(c[1:3] == (15 * 16, 16) for c in cols[9:]) and cols[8][1] == 7 * 4
+    cols, _ = shim.table(3, "cast_probe", mask=1)
+    assert [c[1] // 3 for c in cols] == [24, 24, 8, 56]
+    cols, _ = shim.table(1, "occlusion_rays_probe", mask=1, num_dirs=16, num_rotations=5)
+    assert [c[1] for c in cols] == [16 * 24, 5 * 16, 24, 24, 4, 8, 16 * 24, 16 * 24] and not cols[4][3]  # (the probe has no hit flags)
     for family, value_columns in (("dilate", (1,)), ("filter", (2, 3))):
         cols, _ = shim.table(63, family, mask=7 if family == "dilate" else 0, channels=3)
         assert all(cols[k][2] == 16 and cols[k][1] == 63 * 12 for k in value_columns)

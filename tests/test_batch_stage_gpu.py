@@ -108,3 +108,34 @@ def test_the_blocking_forms_share_one_arena(gpu):
     fresh, _ = _scene()
     proj = math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], 96, 54)
     _same(nr.render(a, (96, 54), 1, 0.0, cam["eye"], proj), nr.render(fresh, (96, 54), 1, 0.0, cam["eye"], proj), "render")
+
+
+def test_the_probes_share_the_arena_with_the_blocking_forms(gpu):
+    """nrays_debug_cast_batch (both modes) and nrays_debug_occlusion_rays run through the driver and the arena like the blocking forms: on one handle, between blocking
+    cast and occlusion calls of other layouts and sizes — a single item, a wave less and more than one item, more than one workgroup; 1 and 16 directions — every
+    probe result equals, bit for bit, the same probe called alone on a fresh handle."""
+    a, cam = _scene()
+    rng = np.random.default_rng(23)
+    words = lambda pair: (pair[0].astype(np.uint32), pair[1])  # noqa: E731  (the probes' wrappers return a bool mask and float64 records)
+    for w, h in ((1, 1), (9, 7), (13, 5), (257, 1)):
+        n = w * h
+        o, d, _ = nr.camera_rays((w, h), cam["eye"], math3d.inverse_projection(cam["eye"], cam["at"], cam["fovy"], w, h), seed=5)
+        assert len(o) == n
+        hits = nr.closest_hits(a, o, d)                      # blocking cast: nine columns
+        probe = nr.cast_rays(a, o, d)                        # the probe, mode 0: four columns in the same arena
+        _same(words(probe), words(nr.cast_rays(_scene()[0], o, d)), "cast probe, %d rays" % n)
+        assert np.array_equal(probe[0], (hits.flags & 1) != 0) and np.array_equal(bits(probe[1][:, 0][probe[0]]), bits(hits.toi[probe[0]]))
+        points, normals = hit_points(o, d, hits)
+        normals[(hits.flags & 1) == 0] = (0.0, 0.0, 1.0)
+        keys = rng.integers(0, 2**63, size=n, dtype=np.int64).astype(np.uint64)
+        max_toi = rng.uniform(0.5, 6.0, size=n)
+        for num_dirs in (1, 16):
+            L, R = nr.hemisphere_dirs(num_dirs), nr.rotation_table(5)
+            occ = nr.occlusion_points(a, points, normals, L, R, hit_flags=hits.flags, keys=keys)  # blocking occlusion: tables, points, two outputs
+            rays = nr.occlusion_ray_probe(a, points, normals, L, R, keys=keys)                    # the probe: the same tables and points, 48 * num_dirs bytes a point out
+            _same(rays, nr.occlusion_ray_probe(_scene()[0], points, normals, L, R, keys=keys), "occlusion probe, %d points x %d" % (n, num_dirs))
+            _same(rays, nr.occlusion_rays(points, normals, L, R, 1e-3, keys=keys), "occlusion probe against the numpy mirror")
+            shadow = nr.shadow_rays(a, o, d, max_toi)                                             # the probe, mode 1: max_toi staged
+            _same(words(shadow), words(nr.shadow_rays(_scene()[0], o, d, max_toi)), "shadow probe, %d rays" % n)
+            _same(tuple(occ), tuple(nr.occlusion_points(a, points, normals, L, R, hit_flags=hits.flags, keys=keys)), "occlusion repeated")
+        _same(tuple(nr.closest_hits(a, o, d)), tuple(hits), "cast repeated")
