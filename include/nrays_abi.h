@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -502,6 +502,63 @@ int nrays_gather_sh_points(NraysScene* scene, uint32_t n, const double* points, 
  * of params included).  Blocking.  Arguments are checked as by nrays_gather_sh_points; NULL ray_colours -> NRAYS_ERR_BAD_ARG. */
 int nrays_debug_gather_sh_fold(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                                const NraysGatherParams* params, uint32_t bands, const float* ray_colours, float* out_sh, float* out_kernel_ms);
+
+/* The CONSUMER of the probes nrays_gather_sh_points* writes: the irradiance at n caller-supplied points with normals from a regular GRID of SH probes — the
+ * indirect term of whatever moves through a baked scene.  Per point the eight probes around it are blended (trilinear weights, optionally a facing factor that
+ * holds down probes behind the surface, and a per-probe validity word that leaves out a probe inside a wall; which probes are valid is the caller's to decide)
+ * and the blended coefficients are folded with the cosine lobe at the normal.  No ray is traced and the scene's geometry is not read: the handle gives the device,
+ * the stream ordering and the staging arena.  The result is defined by this text; nothing is fused, every product and sum is rounded on its own and expressions
+ * are evaluated left to right as written (Python: irradiance_points_ref).  With c_a = counts[a], for a live point p with normal n (f64, used as given):
+ *   cell coordinate  per axis a: c_a == 1: g = 0.0 (and cell_a is taken as 0.0 below, whatever it holds).  Otherwise g = (p_a - origin_a) / cell_a, then
+ *                    g = g > 0 ? (g < (double)(c_a - 1) ? g : (double)(c_a - 1)) : 0.0 — a NaN becomes 0, a point outside the grid takes the border's value.
+ *                    i_a = min((uint32)g, max(c_a, 2) - 2);  f_a = (float)(g - (double)i_a).
+ *   corners          k = 0 .. 7: d = (k & 1, (k >> 1) & 1, (k >> 2) & 1); the probe's index per axis is min(i_a + d_a, c_a - 1), its row
+ *                    (index_z * counts[1] + index_y) * counts[0] + index_x.  In f32: w_k = (X * Y) * Z with X = d_x ? f_x : 1.0f - f_x, likewise Y and Z.
+ *   facing           only with NRAYS_IRRADIANCE_FACING, in f64: q_a = origin_a + (double)index_a * cell_a;  v = q - p;  l2 = (v.x*v.x + v.y*v.y) + v.z*v.z;
+ *                    c = (v.x*n.x + v.y*n.y) + v.z*n.z;  t = l2 > 0 ? (c / sqrt(l2) + 1.0) * 0.5 : 1.0;  w_k = w_k * (float)(t * t + 0.2) — a factor in
+ *                    [0.2, 1.2] for a unit normal.
+ *   validity         with valid != NULL and bit 0 of the corner probe's word clear: w_k = 0.
+ *   normalisation    in f32: wsum = +0; for k = 0 .. 7 in order: wsum = wsum + w_k.  If !(wsum > 0): out_rgb (0, 0, 0), out_sh 3 C zeros, out_weight wsum as
+ *                    computed.  Otherwise wn_k = w_k / wsum, one correctly rounded division each.
+ *   interpolation    s[c][ch] = +0; for k = 0 .. 7 in order: a corner with wn_k == 0 is SKIPPED — its probe's row is not read, so a NaN in an invalid probe never
+ *                    reaches a result —, otherwise s[c][ch] = s[c][ch] + wn_k * sh[row_k][c][ch].
+ *   irradiance       Y_c(n): the nine expressions of nrays_gather_sh_points_device's basis at d = n, in f64.  a_c = (float)(A_band(c) * Y_c) with
+ *                    A = 3.141592653589793, 2.0943951023931953, 0.7853981633974483 (pi, 2 pi / 3, pi / 4: the cosine lobe of Ramamoorthi and Hanrahan 2001) for
+ *                    bands 0, 1, 2.  e[ch] = +0; for c = 0 .. C - 1 in order: e[ch] = e[ch] + a_c * s[c][ch].  out_rgb = measure * e.
+ *   outputs          out_rgb n x 3, out_sh n x C x 3 (the interpolated coefficients s, laid out as nrays_gather_sh_points* lays them out), out_weight n (wsum).
+ *                    Each may be NULL (no store); at least one of out_rgb and out_sh is required.
+ *   skipped          a point whose hit_flags bit 0 is clear: zeros in every output; neither its point nor its normal is read.
+ * The result never depends on how the library assigns points to lanes or chunks. */
+#define NRAYS_IRRADIANCE_FACING 1u
+/* (Struct plus separate typedef, as NraysGatherMapsParams and for the same reason; tests/test_irradiance.py compares it with its Rust and ctypes twins.) */
+struct NraysIrradianceGrid {
+    double origin[3];      /* position of probe (0, 0, 0); finite */
+    double cell[3];        /* spacing per axis; finite and > 0 on every axis with counts > 1, ignored (any value) where counts == 1 */
+    uint32_t counts[3];    /* probes per axis, each 1 .. 1024, product <= 2^22 */
+    uint32_t bands;        /* 1, 2 or 3; C = bands * bands */
+    const float* sh;       /* P x C x 3 floats, what nrays_gather_sh_points* writes: probe (ix, iy, iz) is row (iz * counts[1] + iy) * counts[0] + ix */
+    const uint32_t* valid; /* P words or NULL = every probe valid; bit 0 clear = the probe is never read */
+    float measure;         /* solid angle of the probes' sample table (4 pi for sphere_dirs); finite */
+    uint32_t reserved;     /* must be 0 */
+};
+typedef struct NraysIrradianceGrid NraysIrradianceGrid;
+/*   points, normals  n x 3 doubles, world space, used as given (unit normals).
+ *   hit_flags        n words, or NULL = every point is live: the bits of out_flags of nrays_cast_rays_device / nrays_surface_texels_device.
+ *   grid             HOST memory (the struct); grid->sh and grid->valid are DEVICE memory here, like every other array.  Nothing of the struct is read after the
+ *                    call returns.
+ *   flags            0 or NRAYS_IRRADIANCE_FACING.
+ * NULL scene / points / normals / grid / grid->sh; out_rgb and out_sh both NULL; a count outside 1 .. 1024 or a product above 2^22; bands outside 1 .. 3; a
+ * non-finite origin or measure; on an axis with counts > 1 a cell that is not finite and > 0; reserved != 0; an unknown flag bit -> NRAYS_ERR_BAD_ARG, before any
+ * device work.  n == 0 -> NRAYS_OK, the outputs untouched.  Otherwise the contract of nrays_filter_texels_device, in chunks of at most 2^22 points: every array is
+ * device memory on the scene's device, the call is enqueued on `hip_stream` behind the handle's previous work without read-back or synchronisation, and what the
+ * handle reports about its renders and its per-camera scheduling state stay untouched.  Traffic: 48 bytes in (52 with hit_flags) and 12 + 12 C + 4 bytes out a
+ * point as asked for; the corner rows come from the grid, which lanes in surface order share. */
+int nrays_irradiance_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                   const NraysIrradianceGrid* grid, float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, void* hip_stream);
+/* Same, every pointer (grid->sh and grid->valid included) HOST memory.  Blocking.  The grid's coefficients and validity words are staged with the tables, once
+ * a call. */
+int nrays_irradiance_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                            const NraysIrradianceGrid* grid, float* out_rgb, float* out_sh, float* out_weight, uint32_t flags);
 
 /* The light that BAKED MAPS hold at the closest hits of the hemisphere rays of n caller-supplied surface points — one diffuse bounce of a light-map baker: the
  * library builds num_dirs rays per point ON THE DEVICE, finds each ray's closest hit, samples the light map of the node it hit at the hit's uv and writes ONE mean

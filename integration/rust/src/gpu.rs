@@ -734,6 +734,40 @@ impl GpuScene {
         if nrays_gather_sh_points_device(self.raw, n, points, normals, hit_flags, keys, params, bands, out_sh, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
+
+    /// The irradiance at caller-supplied points with normals from a regular grid of the probes `gather_sh_points` writes (nrays_irradiance_points, blocking): the
+    /// eight probes around a point blended with trilinear weights, folded with the cosine lobe at the normal and multiplied by `measure` (4 pi for sphere
+    /// directions).  Probe (ix, iy, iz) sits at origin + (ix, iy, iz) * cell and is row (iz * counts[1] + iy) * counts[0] + ix of `sh` (P x bands^2 x 3 f32);
+    /// `valid` (P words, bit 0 clear: the probe is never read) leaves probes out — which ones is the caller's to decide; `facing` holds down probes behind the
+    /// surface.  Returns per point the colour and the sum of its weights (0: no probe counted).  The value is defined in include/nrays_abi.h (NraysIrradianceGrid).
+    pub fn irradiance_points(&self, points: &[(Point3<f64>, Vector3<f64>)], origin: [f64; 3], cell: [f64; 3], counts: [u32; 3], bands: u32, sh: &[f32], valid: Option<&[u32]>,
+                             measure: f32, facing: bool) -> Result<(Vec<Vector3<f32>>, Vec<f32>), String> {
+        if bands < 1 || bands > 3 { return Err(format!("bands must be in 1 ..= 3, got {}", bands)); }
+        let probes = counts.iter().map(|&c| c as usize).product::<usize>();
+        if counts.iter().any(|&c| c < 1 || c > 1024) || probes > 1 << 22 { return Err(format!("counts must be in 1 ..= 1024 with a product <= 2^22, got {:?}", counts)); }
+        if sh.len() != probes * (bands * bands) as usize * 3 { return Err(format!("{} coefficients for {} probes of {} bands", sh.len(), probes, bands)); }
+        if let Some(v) = valid { if v.len() != probes { return Err(format!("{} validity words for {} probes", v.len(), probes)); } }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let grid = NraysIrradianceGrid { origin, cell, counts, bands, sh: sh.as_ptr(), valid: valid.map(|v| v.as_ptr()).unwrap_or(ptr::null()), measure, reserved: 0 };
+        let mut rgb = vec![0.0f32; 3 * n];
+        let mut weight = vec![0.0f32; n];
+        let flags = if facing { NRAYS_IRRADIANCE_FACING } else { 0 };
+        let rc = unsafe { nrays_irradiance_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), &grid, rgb.as_mut_ptr(), ptr::null_mut(), weight.as_mut_ptr(), flags) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(((0..n).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect(), weight))
+    }
+
+    /// `irradiance_points` for n points in DEVICE memory (nrays_irradiance_points_device), enqueued on `hip_stream`: points / normals n x 3 f64, hit_flags n u32 or
+    /// null, out_rgb n x 3, out_sh n x bands^2 x 3 and out_weight n f32, each or null (out_rgb or out_sh is required).  `grid` is host memory; its `sh` and `valid`
+    /// are device memory.
+    pub unsafe fn irradiance_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: &NraysIrradianceGrid, out_rgb: *mut f32,
+                                           out_sh: *mut f32, out_weight: *mut f32, facing: bool, hip_stream: *mut c_void) -> Result<(), String> {
+        let flags = if facing { NRAYS_IRRADIANCE_FACING } else { 0 };
+        if nrays_irradiance_points_device(self.raw, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
 }
 
 impl Drop for GpuScene {

@@ -245,6 +245,22 @@ pub struct NraysGatherMapsParams {
     pub miss_rgb: [f32; 3],
 }
 
+/// flag of nrays_irradiance_points*: a probe's weight also falls with the angle between the normal and the direction to the probe
+pub const NRAYS_IRRADIANCE_FACING: u32 = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysIrradianceGrid {
+    pub origin: [f64; 3],
+    pub cell: [f64; 3],
+    pub counts: [u32; 3],
+    pub bands: u32,
+    pub sh: *const f32,
+    pub valid: *const u32,
+    pub measure: f32,
+    pub reserved: u32,
+}
+
 pub enum NraysScene {}
 pub enum NraysComm {}
 pub enum NraysSceneSet {}
@@ -296,6 +312,8 @@ extern "C" {
     pub fn nrays_debug_gather_sh_fold(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, bands: u32, ray_colours: *const f32, out_sh: *mut f32, out_kernel_ms: *mut f32) -> c_int;
     pub fn nrays_gather_maps_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_gather_maps_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_irradiance_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_irradiance_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
     pub fn nrays_debug_gather_order(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
     pub fn nrays_surface_texels_device(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_surface_texels(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;

@@ -11,4 +11,5 @@ from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolat
                     SurfaceTexels, bake_indirect, bake_lightmap, gather_hits, gather_order, gather_points, gather_ray_keys, surface_texels, surface_texels_passes, surface_texels_ref, texel_coords,
                     dilate_texels, dilate_texels_ref, lightmap_texture, denoise_texels, filter_texels, filter_texels_ref,
                     gather_probes, gather_sh_fold, gather_sh_points, sh_basis, sh_fold_ref, sh_irradiance, sphere_dirs,
-                    bake_bounces, gather_maps_hits, gather_maps_points, lightmap_sample_ref)
+                    bake_bounces, gather_maps_hits, gather_maps_points, lightmap_sample_ref,
+                    Irradiance, ProbeGrid, bake_probe_grid, irradiance_points, irradiance_points_ref, probe_grid_positions)

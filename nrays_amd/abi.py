@@ -129,6 +129,16 @@ class NraysGatherMapsParams(C.Structure):
                 ("num_maps", C.c_uint32), ("num_nodes", C.c_uint32), ("maps", C.POINTER(NraysTexture)), ("node_map", C.c_void_p), ("miss_rgb", C.c_float * 3)]
 
 
+IRRADIANCE_FACING = 1       # NRAYS_IRRADIANCE_FACING
+IRRADIANCE_MAX_COUNT, IRRADIANCE_MAX_PROBES = 1024, 1 << 22
+
+
+class NraysIrradianceGrid(C.Structure):
+    """The probe grid of nrays_irradiance_points*: `sh` / `valid` are addresses (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("origin", C.c_double * 3), ("cell", C.c_double * 3), ("counts", C.c_uint32 * 3), ("bands", C.c_uint32), ("sh", C.c_void_p), ("valid", C.c_void_p),
+                ("measure", C.c_float), ("reserved", C.c_uint32)]
+
+
 class NraysBlasDump(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_refs", C.c_uint32), ("root", C.c_int32), ("max_depth", C.c_int32), ("hairy", C.c_uint32),
                 ("node_capacity", C.c_uint32), ("ref_capacity", C.c_uint32), ("pad", C.c_uint32), ("nodes", C.POINTER(C.c_float)), ("tri_ids", C.POINTER(C.c_uint32))]
@@ -187,6 +197,10 @@ HIP_SYMBOLS = {
                                                   C.c_uint32, C.c_void_p]),
     "nrays_gather_maps_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                            C.POINTER(NraysGatherMapsParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_irradiance_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysIrradianceGrid), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p]),
+    "nrays_irradiance_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(NraysIrradianceGrid),
+                                          C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -238,7 +252,8 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_debug_surface_texels_passes", "nrays_debug_pipeline_counts", "nrays_gather_points_device", "nrays_gather_points",
                    "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels",
                    "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels", "nrays_gather_sh_points_device", "nrays_gather_sh_points",
-                   "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points")
+                   "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
+                   "nrays_irradiance_points")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

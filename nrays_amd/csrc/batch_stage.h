@@ -117,6 +117,15 @@ inline int gather_maps_columns(StageColumn* c, float* out_rgb, uint32_t* out_cou
     for (uint32_t m = 0; m < num_maps; ++m) c[kMapsTexels + m] = stage_table(map_texels[m], 16, map_count[m], 16);
     return kMapsTexels + (int)num_maps;
 }
+// nrays_irradiance_points*: points against a grid of SH probes.  The grid's coefficients (12 C bytes a probe) and validity words are tables; out_sh holds 3 C floats a point.
+enum { kIrrSh, kIrrValid, kIrrPoints, kIrrNormals, kIrrHit, kIrrRgb, kIrrOutSh, kIrrWeight, kIrrColumns };
+inline int irradiance_columns(StageColumn* c, const float* grid_sh, const uint32_t* grid_valid, size_t probes, uint32_t coefs, const double* points, const double* normals,
+                              const uint32_t* hit_flags, float* out_rgb, float* out_sh, float* out_weight) {
+    c[kIrrSh] = stage_table(grid_sh, 12 * (size_t)coefs, probes); c[kIrrValid] = stage_table(grid_valid, 4, probes);
+    c[kIrrPoints] = stage_in(points, 24); c[kIrrNormals] = stage_in(normals, 24); c[kIrrHit] = stage_in(hit_flags, 4);
+    c[kIrrRgb] = stage_out(out_rgb, 12); c[kIrrOutSh] = stage_out(out_sh, 12 * (size_t)coefs); c[kIrrWeight] = stage_out(out_weight, 4);
+    return kIrrColumns;
+}
 // Lattices (one chunk of width * height items).
 enum { kTexelPoints, kTexelNormals, kTexelUv, kTexelNode, kTexelPrim, kTexelFlags, kTexelColumns };
 inline int surface_texel_columns(StageColumn* c, double* points, double* normals, double* uv, int32_t* node, int32_t* prim, uint32_t* flags) {

@@ -1,7 +1,8 @@
 // point_batches.hip — the caller-batch families that take surface points and build a hemisphere of rays a point on the device, each a check, a column table
 // (batch_stage.h) and a chunk launch run by the driver of batch_call.h: nrays_occlusion_points* (k_occlusion_points: instantiated in ray_batches.hip beside the other traversal kernels, launched through launch_occlusion_points),
 // nrays_gather_points* (+ _ex) and nrays_gather_sh_points* (kernels: gather_inst.hip, gather_order_inst.hip; k_gather_fold here, k_gather_fold_sh of gather_sh_kernel.h),
-// nrays_gather_maps_points* (gather_maps_inst.hip).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
+// nrays_gather_maps_points* (gather_maps_inst.hip), and the one family at points that builds no ray: nrays_irradiance_points* (k_irradiance_points of irradiance_kernel.h,
+// instantiated here).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -14,6 +15,7 @@
 #include "bounce.h"
 #include "gather_maps_kernel.h"
 #include "gather_sh_kernel.h"
+#include "irradiance_kernel.h"
 #include "ray_batch_kernel.h"
 #include "ray_order.h"
 #include "scene_handle.h"
@@ -190,6 +192,58 @@ static int gather_maps_impl(NraysScene* sc, uint32_t n, const double* points, co
     return batch_run(sc, staged, stream, cols, ncols, n, point_chunk(p->num_dirs), "gather maps batch", launch);
 }
 
+// ---- nrays_irradiance_points*: the irradiance at caller-supplied points from a regular grid of SH probes (irradiance_kernel.h) ----------------------------------
+template <int BANDS, bool WANT_SH, bool FACING>
+static bool launch_if(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
+    if (bands != (uint32_t)BANDS || want_sh != WANT_SH || facing != FACING) return false;
+    hipLaunchKernelGGL((k_irradiance_points<BANDS, WANT_SH, FACING>), dim3(a.grid), dim3(kBlock), 0, a.stream, a.n, a.points, a.normals, a.hit_flags, a.g, a.out_rgb, a.out_sh, a.out_weight);
+    return true;
+}
+template <int BANDS>
+static bool launch_if_bands(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
+    return launch_if<BANDS, false, false>(a, bands, want_sh, facing) || launch_if<BANDS, false, true>(a, bands, want_sh, facing) ||
+           launch_if<BANDS, true, false>(a, bands, want_sh, facing) || launch_if<BANDS, true, true>(a, bands, want_sh, facing);
+}
+bool launch_irradiance_points(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
+    return launch_if_bands<1>(a, bands, want_sh, facing) || launch_if_bands<2>(a, bands, want_sh, facing) || launch_if_bands<3>(a, bands, want_sh, facing);
+}
+constexpr uint32_t kIrradianceMaxCount = 1024u, kIrradianceMaxProbes = 1u << 22;
+static int check_irradiance_args(const NraysScene* sc, const double* points, const double* normals, const NraysIrradianceGrid* g, const float* out_rgb, const float* out_sh, uint32_t flags) {
+    if (!sc || !points || !normals || !g || !g->sh) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (!out_rgb && !out_sh) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_irradiance_points: no output (out_rgb and out_sh are both null)");
+    uint64_t probes = 1;
+    for (int a = 0; a < 3; ++a) {
+        if (g->counts[a] < 1u || g->counts[a] > kIrradianceMaxCount) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: counts must be in 1 .. 1024");
+        probes *= g->counts[a];
+        if (!std::isfinite(g->origin[a])) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: origin must be finite");
+        if (g->counts[a] > 1u && !(std::isfinite(g->cell[a]) && g->cell[a] > 0.0))
+            return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: cell must be finite and > 0 on every axis with more than one probe");
+    }
+    if (probes > kIrradianceMaxProbes) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: at most 2^22 probes");
+    if (g->bands < 1u || g->bands > 3u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: bands must be in 1 .. 3");
+    if (!std::isfinite(g->measure)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: measure must be finite");
+    if (g->reserved != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceGrid: reserved must be 0");
+    if (flags & ~(uint32_t)NRAYS_IRRADIANCE_FACING) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_irradiance_points: unknown flag");
+    return NRAYS_OK;
+}
+static int irradiance_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* g,
+                                  float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, bool staged, hipStream_t stream) {
+    if (check_irradiance_args(sc, points, normals, g, out_rgb, out_sh, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    const uint32_t coefs = g->bands * g->bands;
+    StageColumn cols[kIrrColumns];
+    irradiance_columns(cols, g->sh, g->valid, (size_t)g->counts[0] * g->counts[1] * g->counts[2], coefs, points, normals, hit_flags, out_rgb, out_sh, out_weight);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        IrradianceGrid k;
+        for (int a = 0; a < 3; ++a) { k.origin[a] = g->origin[a]; k.counts[a] = g->counts[a]; k.cell[a] = g->counts[a] > 1u ? g->cell[a] : 0.0; }
+        k.sh = (const float*)c[kIrrSh]; k.valid = (const uint32_t*)c[kIrrValid]; k.measure = g->measure;
+        const IrradianceLaunch a{launch_grid(nc), b.stream, nc, (const double*)c[kIrrPoints], (const double*)c[kIrrNormals], (const uint32_t*)c[kIrrHit], k,
+                                 (float*)c[kIrrRgb], (float*)c[kIrrOutSh], (float*)c[kIrrWeight]};
+        return launch_irradiance_points(a, g->bands, out_sh != nullptr, (flags & NRAYS_IRRADIANCE_FACING) != 0u) ? launch_status("k_irradiance_points") : no_permutation("k_irradiance_points");
+    };
+    return batch_run(sc, staged, stream, cols, kIrrColumns, n, kTraceChunk, "irradiance batch", launch);
+}
+
 // nrays_debug_occlusion_rays: ray j of point i of the chunk, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].  NULL keys: key_base + i.
 __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
                                                            const unsigned long long* __restrict__ keys, unsigned long long key_base, OcclusionSpec P,
@@ -272,6 +326,15 @@ int nrays_gather_maps_points_device(NraysScene* sc, uint32_t n, const double* po
 int nrays_gather_maps_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                              const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags) {
     return gather_maps_impl(sc, n, points, normals, hit_flags, keys, params, out_rgb, out_counts, flags, true, nullptr);
+}
+
+int nrays_irradiance_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
+                                   float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, void* hip_stream) {
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_irradiance_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
+                            float* out_rgb, float* out_sh, float* out_weight, uint32_t flags) {
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, true, nullptr);
 }
 
 // k_gather_fold_sh alone on caller-supplied ray colours, one chunk, through the staging arena; the kernel between events of its own when out_kernel_ms is wanted.

@@ -238,6 +238,59 @@ def _sh_bands(bands):
     return int(bands)
 
 
+ProbeGrid = collections.namedtuple("ProbeGrid", ("origin", "cell", "counts", "sh", "valid", "measure"), defaults=(None, 4.0 * math.pi))
+ProbeGrid.__doc__ = """A regular grid of SH probes (NraysIrradianceGrid): probe (ix, iy, iz) sits at origin + (ix, iy, iz) * cell and is row (iz * counts[1] + iy) * counts[0] + ix
+of `sh` ((P, bands^2, 3) float32, what gather_probes returns at probe_grid_positions()); `valid` (P,) integers or None: bit 0 clear = the probe is never read;
+`measure`: the solid angle of the probes' sample table."""
+
+
+def _probe_lattice(origin, cell, counts):
+    """origin, cell and counts of a ProbeGrid as tuples of plain numbers, checked against NraysIrradianceGrid's bounds."""
+    vec = []
+    for name, v in (("origin", origin), ("cell", cell), ("counts", counts)):
+        v = np.asarray(v).reshape(-1)
+        if v.shape != (3,) or not (np.issubdtype(v.dtype, np.integer) if name == "counts" else np.issubdtype(v.dtype, np.number)) or v.dtype == np.bool_:
+            raise ValueError("grid.%s must be three %s" % (name, "integers" if name == "counts" else "numbers"))
+        vec.append(v)
+    origin, cell, counts = tuple(float(x) for x in vec[0]), tuple(float(x) for x in vec[1]), tuple(int(x) for x in vec[2])
+    if not all(math.isfinite(x) for x in origin):
+        raise ValueError("grid.origin must be finite")
+    if not all(1 <= c <= abi.IRRADIANCE_MAX_COUNT for c in counts) or counts[0] * counts[1] * counts[2] > abi.IRRADIANCE_MAX_PROBES:
+        raise ValueError("grid.counts must be in 1 .. %d with a product <= 2^22, got %s" % (abi.IRRADIANCE_MAX_COUNT, counts))
+    if not all(c == 1 or (math.isfinite(x) and x > 0.0) for c, x in zip(counts, cell)):
+        raise ValueError("grid.cell must be finite and > 0 on every axis with more than one probe, got %s" % (cell,))
+    return origin, cell, counts
+
+
+def _probe_grid(grid):
+    """The checks of NraysIrradianceGrid that need no library: (origin, cell, counts, bands, sh, valid, measure) with plain Python numbers, sh a float32 array or
+    tensor (P, bands^2, 3), valid None or integers of P words."""
+    if not isinstance(grid, tuple) or len(grid) != 6:
+        raise ValueError("grid must be a ProbeGrid(origin, cell, counts, sh, valid, measure)")
+    origin, cell, counts, sh, valid, measure = grid
+    origin, cell, counts = _probe_lattice(origin, cell, counts)
+    probes = counts[0] * counts[1] * counts[2]
+    if sh is None or not (_is_tensor(sh) or isinstance(sh, np.ndarray)):
+        raise ValueError("grid.sh must be a float32 numpy array or torch tensor")
+    coefs = sh.shape[-2] if len(sh.shape) >= 2 else 0
+    if str(sh.dtype).split(".")[-1] != "float32" or coefs not in (1, 4, 9) or sh.shape[-1] != 3 or int(np.prod(tuple(sh.shape))) != probes * coefs * 3:
+        raise ValueError("grid.sh must be float32 of shape (%d, 1 | 4 | 9, 3), got %s %s" % (probes, tuple(sh.shape), sh.dtype))
+    if valid is not None:
+        if not _is_tensor(valid):
+            valid = np.asarray(valid)
+            if valid.dtype == np.bool_:
+                valid = valid.astype(np.uint32)
+            if not np.issubdtype(valid.dtype, np.integer):
+                raise ValueError("grid.valid must be integers, got %s" % valid.dtype)
+        if int(np.prod(tuple(valid.shape))) != probes:
+            raise ValueError("grid.valid must hold one word per probe (%d), got shape %s" % (probes, tuple(valid.shape)))
+        valid = valid.reshape(-1)
+    measure = float(measure)
+    if not math.isfinite(measure) or abs(measure) > float(np.finfo(np.float32).max):
+        raise ValueError("grid.measure must be a finite float32")
+    return origin, cell, counts, {1: 1, 4: 2, 9: 3}[coefs], sh.reshape(probes, coefs, 3), valid, measure
+
+
 class Interpolation:
     Bilinear = abi.INTERP_BILINEAR
     Nearest = abi.INTERP_NEAREST

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import abi
 from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
-                      _occlusion_tables, _sh_bands, _texel_lattice)
+                      _occlusion_tables, _probe_grid, _probe_lattice, _sh_bands, _texel_lattice)
 
 SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
 SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
@@ -210,6 +210,81 @@ def sh_irradiance(sh, normals, measure=4.0 * math.pi):
         term = (SH_COSINE_LOBE[band[c]] * Y[c])[..., None] * sh[..., c, :]
         e = term if e is None else e + term
     return measure * e
+
+
+def probe_grid_positions(origin, cell, counts):
+    """The positions of a ProbeGrid's probes, (P, 3) float64 in the grid's row order (x fastest, then y, then z): origin + index * cell, one product and one sum
+    per axis — the q of nrays_irradiance_points_device's facing factor, bit for bit."""
+    origin, cell, counts = _probe_lattice(origin, cell, counts)
+    axes = [origin[a] + np.arange(counts[a], dtype=np.float64) * (cell[a] if counts[a] > 1 else 0.0) for a in range(3)]
+    z, y, x = np.meshgrid(axes[2], axes[1], axes[0], indexing="ij")
+    return np.ascontiguousarray(np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1))
+
+
+def irradiance_points_ref(points, normals, grid, facing=False, hit_flags=None):
+    """The numpy mirror of nrays_irradiance_points*, bit for bit (include/nrays_abi.h: NraysIrradianceGrid — cell coordinates, the facing factor and the basis at
+    the normal in float64, weights and folds in float32, every product and sum rounded on its own, left to right as the header writes them).  `grid`: a ProbeGrid of
+    numpy arrays.  Returns (rgb (n, 3), sh (n, bands^2, 3), weight (n,)) float32: the three outputs of the call."""
+    origin, cell, counts, bands, sh, valid, measure = _probe_grid(grid)
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("hit_flags", hit_flags, n)
+    if any(_is_tensor(a) for a in (points, normals, hit_flags, sh, valid)):
+        raise ValueError("irradiance_points_ref takes numpy arrays")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    live = np.ones(n, bool) if hit_flags is None else (np.asarray(hit_flags).astype(np.uint64) & np.uint64(1)) != 0
+    C_ = bands * bands
+    f32, one = np.float32, np.float32(1.0)
+    cell = tuple(cell[a] if counts[a] > 1 else 0.0 for a in range(3))
+    if valid is not None:
+        valid = (np.asarray(valid).astype(np.uint64) & np.uint64(1)) != 0
+    with np.errstate(all="ignore"):
+        lo, hi, f = [], [], []
+        for a in range(3):
+            c = counts[a]
+            if c == 1:
+                g = np.zeros(n, np.float64)
+            else:
+                g = (p[:, a] - origin[a]) / cell[a]
+                top = float(c - 1)
+                g = np.where(g > 0.0, np.where(g < top, g, top), 0.0)
+            i = np.minimum(g.astype(np.int64), max(c, 2) - 2)
+            lo.append(i)
+            hi.append(np.minimum(i + 1, c - 1))
+            f.append((g - i.astype(np.float64)).astype(f32))
+        w, rows = np.zeros((8, n), f32), np.zeros((8, n), np.int64)
+        for k in range(8):
+            d = (k & 1, (k >> 1) & 1, (k >> 2) & 1)
+            idx = [hi[a] if d[a] else lo[a] for a in range(3)]
+            X, Y, Z = (f[a] if d[a] else one - f[a] for a in range(3))
+            wk = (X * Y) * Z
+            if facing:
+                v = [(origin[a] + idx[a].astype(np.float64) * cell[a]) - p[:, a] for a in range(3)]
+                l2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+                c = (v[0] * nm[:, 0] + v[1] * nm[:, 1]) + v[2] * nm[:, 2]
+                t = np.where(l2 > 0.0, (c / np.sqrt(l2) + 1.0) * 0.5, 1.0)
+                wk = wk * (t * t + 0.2).astype(f32)
+            rows[k] = (idx[2] * counts[1] + idx[1]) * counts[0] + idx[0]
+            if valid is not None:
+                wk = np.where(valid[rows[k]], wk, f32(0.0))
+            w[k] = wk
+        wsum = np.zeros(n, f32)
+        for k in range(8):
+            wsum = wsum + w[k]
+        lit = live & (wsum > 0)
+        wn = w / np.where(lit, wsum, one)[None, :]
+        s = np.zeros((n, C_, 3), f32)
+        for k in range(8):
+            use = lit & (wn[k] != 0)
+            s[use] = s[use] + wn[k][use, None, None] * sh[rows[k][use]]
+        Yn = _sh_terms(nm[:, 0], nm[:, 1], nm[:, 2], C_)
+        Yn[0] = np.full(n, SH_K[0])
+        band = (0, 1, 1, 1, 2, 2, 2, 2, 2)
+        e = np.zeros((n, 3), f32)
+        for c in range(C_):
+            a_c = (SH_COSINE_LOBE[band[c]] * Yn[c]).astype(f32)
+            e = e + a_c[:, None] * s[:, c, :]
+        rgb = np.where(lit[:, None], f32(measure) * e, f32(0.0)).astype(f32)
+    return rgb, s, np.where(live, wsum, f32(0.0)).astype(f32)
 
 
 def texel_coords(n, centres=False):

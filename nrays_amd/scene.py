@@ -21,10 +21,10 @@ import numpy as np
 
 from . import abi
 from .marshal import (CURRENT, F32, F64, I32, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
-                      Overflow, SurfaceTexels, _check_rows, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _occlusion_tables,
-                      _sh_bands, _texel_lattice, np_ptr, upload)
+                      Overflow, ProbeGrid, SurfaceTexels, _check_rows, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _occlusion_tables,
+                      _probe_grid, _probe_lattice, _sh_bands, _texel_lattice, np_ptr, upload)
 from .restated import (FILTER_TAPS, SALT_GATHER, SALT_OCCLUSION, SH_COSINE_LOBE, SH_K, _rng_hash, _rng_mix, _sh_terms, _texel_edge, camera_rays, dilate_texels_ref,  # noqa: F401
-                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, lightmap_sample_ref, occlusion_rays, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
+                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, occlusion_rays, probe_grid_positions, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
                        sphere_dirs, surface_texels_ref, texel_coords)
 
 
@@ -374,6 +374,14 @@ class BatchCalls:
     def gather_probes(self, positions, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True):
         """Irradiance probes at free points of this scene: gather_probes(self, ...)."""
         return gather_probes(self, positions, sample_dirs, bands, energy, max_depth, keys, unordered)
+
+    def irradiance_points(self, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False):
+        """The irradiance at caller-supplied points from a grid of SH probes, on this scene's GPU: irradiance_points(self, ...)."""
+        return irradiance_points(self, points, normals, grid, facing, hit_flags, want_sh, want_weight)
+
+    def bake_probe_grid(self, origin, cell, counts, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True, valid=None, measure=4.0 * math.pi, device=None):
+        """A grid of irradiance probes of this scene: bake_probe_grid(self, ...)."""
+        return bake_probe_grid(self, origin, cell, counts, sample_dirs, bands, energy, max_depth, keys, unordered, valid, measure, device)
 
     @_dilate_keyword
     def bake_indirect(self, node, width, height, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, centres=False, flip_normals=False, keys=None,
@@ -848,6 +856,49 @@ def gather_sh_fold(scene, points, normals, sample_dirs, ray_colours, rotations=N
     params, ms = abi.NraysGatherParams(*_tables(b), bias, 1.0, 0), C.c_float(0.0)
     b.call(scene, "nrays_debug_gather_sh_fold", n, *b.pin[:4], C.byref(params), bands, b.pin[6], *b.pout, C.byref(ms) if want_ms else None)
     return (b.outs[0], float(ms.value)) if want_ms else b.outs[0]
+
+
+# ---- the consumer of the probes: irradiance at caller-supplied points from a grid of them (include/nrays_abi.h: nrays_irradiance_points_device) ---------------
+
+Irradiance = collections.namedtuple("Irradiance", ("rgb", "sh", "weight"))
+
+
+def irradiance_points(scene, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False):
+    """The irradiance at n caller-supplied points with normals from a regular grid of SH probes — the indirect term of whatever moves through a baked scene —
+    through nrays_irradiance_points_device / nrays_irradiance_points: per point the eight probes around it are blended with trilinear weights, the blend is folded
+    with the cosine lobe at the normal and multiplied by grid.measure: (n, 3) float32.  irradiance_points_ref() restates it bit for bit; on a probe's position
+    it is sh_irradiance() of that probe up to float32 rounding.  No ray is traced: the scene gives the GPU, the stream ordering and the staging memory.
+    `grid`: a ProbeGrid — bake_probe_grid() makes one.  A point outside the grid takes the border's value.  `facing=True` (NRAYS_IRRADIANCE_FACING) multiplies a
+    probe's weight by ((cos + 1) / 2)^2 + 0.2, cos between the normal and the direction to the probe: probes behind the surface count less.  grid.valid leaves
+    probes out (bit 0 clear: never read, so its row may hold anything); deciding which probes are valid — inside a wall, say — is the caller's job.  A point none
+    of whose probes counts gets zeros and weight 0.  `hit_flags` (n,) integers or None: bit 0 clear skips a point (zeros; its point and normal may hold anything).
+    `want_sh` / `want_weight`: returns Irradiance(rgb, sh, weight) with the blended coefficients (n, bands^2, 3) and the weight sums (n,) that were asked for (None
+    otherwise) instead of rgb alone.
+    numpy arrays -> nrays_irradiance_points (blocking; the grid is staged once a call), numpy arrays.  torch tensors on the scene's GPU (points / normals float64;
+    hit_flags int32 / uint32; grid.sh float32 and grid.valid int32 / uint32 tensors there, or numpy arrays, which are uploaded every call) ->
+    nrays_irradiance_points_device on torch's current stream, tensors."""
+    if not isinstance(facing, (bool, np.bool_)):
+        raise ValueError("facing must be True or False, got %r" % (facing,))
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("hit_flags", hit_flags, n)
+    origin, cell, counts, bands, sh, valid, measure = _probe_grid(grid)
+    b = Batch((("points", points, F64), ("normals", normals, F64), ("hit_flags", hit_flags, U32), ("grid.sh", sh, F32, True), ("grid.valid", valid, U32, True)),
+              (("rgb", (n, 3), F32), ("sh", (n, bands * bands, 3), F32, bool(want_sh)), ("weight", (n,), F32, bool(want_weight))))
+    g = abi.NraysIrradianceGrid((C.c_double * 3)(*origin), (C.c_double * 3)(*cell), (C.c_uint32 * 3)(*counts), bands, b.addr(b.ins[3]), b.addr(b.ins[4]), measure, 0)
+    b.call(scene, "nrays_irradiance_points", n, *b.pin[:3], C.byref(g), *b.pout, abi.IRRADIANCE_FACING if facing else 0)
+    return Irradiance(*b.outs) if want_sh or want_weight else b.outs[0]
+
+
+def bake_probe_grid(scene, origin, cell, counts, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True, valid=None, measure=4.0 * math.pi, device=None):
+    """A grid of irradiance probes: gather_probes() at probe_grid_positions(origin, cell, counts) with the sphere table `sample_dirs`, as a ProbeGrid for
+    irradiance_points().  `valid` and `measure` are passed through (the solid angle of sphere_dirs is 4 pi); which probes are valid stays the caller's to decide.
+    `device`: None bakes through the blocking form into numpy arrays; a GPU (or CURRENT) keeps the positions and the coefficients there as tensors."""
+    origin, cell, counts = _probe_lattice(origin, cell, counts)
+    positions = probe_grid_positions(origin, cell, counts)
+    if device is not None:
+        import torch
+        positions = upload(positions, torch.device("cuda", torch.cuda.current_device()) if device is CURRENT else device)
+    return ProbeGrid(origin, cell, counts, gather_probes(scene, positions, sample_dirs, bands, energy, max_depth, keys, unordered), valid, measure)
 
 
 # ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------
