@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/nrays_abi.h"
 #include "device_types.h"
 
 namespace nrays {
@@ -49,7 +50,13 @@ int build_blas_device(const std::vector<DeviceMeshPart>& parts, const DeviceBuil
                       DeviceBlas& out, std::string& err);
 void free_device_blas(DeviceBlas& b);
 
-// Test probe (nrays_debug_blas_build): copies a device-built BLAS back to the host.
-struct HostBlasCopy { std::vector<BvhNode> nodes; std::vector<TriRec> tris; int32_t root; int max_depth; bool hairy; };
+// Why either builder refuses a mesh; k_tri_records reports them as bits 0, 1, 2 of its error word, in this order.  Sets `err`, returns the status.
+enum MeshError { kMeshIndexRange = 0, kMeshVertexInexact = 1, kMeshUvInexact = 2 };
+inline int refuse_mesh(MeshError why, std::string& err) {
+    static const char* const text[3] = {"triangle index out of range", "mesh vertex coordinate is not exactly representable in f32 (see DESIGN.md: f32-exact mesh storage)",
+                                        "mesh uv is not exactly representable in f32"};
+    err = text[why];
+    return why == kMeshIndexRange ? NRAYS_ERR_BAD_ARG : NRAYS_ERR_UNSUPPORTED;
+}
 
 } // namespace nrays

@@ -22,12 +22,11 @@
 #include <chrono>
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
-#include <limits>
 #include <map>
 
 #include "../../include/nrays_abi.h"
+#include "bvh_arena.h"
 #include "bvh_build.h"
 #include "bvh_device.h"
 #include "presplit_clip.h"
@@ -36,10 +35,6 @@ namespace nrays {
 namespace {
 
 static_assert(kSahBins == 32, "the device builder maps one SAH bin to one lane of a 32-lane half wave");
-constexpr uint32_t kChunk = 1024;  // references per workgroup of the large-node kernels
-constexpr uint32_t kSmall = 256;   // nodes up to this many references are finished by one wave in LDS
-constexpr int kBinWords = 96 * 6;  // min (or max) words of one node's bins: [axis][bin][box xyz, centroid xyz]
-constexpr uint32_t kHistShift = 13, kHistBins = 1u << (32 - kHistShift);
 #define INF_F __builtin_huge_valf()
 
 struct Task {
@@ -67,7 +62,7 @@ struct Counters {
 
 // ---- order-preserving float <-> uint encoding (min / max through integer atomics) -----------------------------------
 __device__ inline uint32_t enc(float f) { uint32_t b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }
-__device__ inline float dec(uint32_t e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
+__host__ __device__ inline float dec(uint32_t e) { return __builtin_bit_cast(float, (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
 __device__ inline float dec_min(uint32_t e) { return e == 0xffffffffu ? INF_F : dec(e); } // identity of min = all ones (memset 0xff)
 __device__ inline float dec_max(uint32_t e) { return e == 0u ? -INF_F : dec(e); }          // identity of max = zero (memset 0)
 
@@ -280,7 +275,7 @@ enum { kModeHist = 1, kModeEmit = 2 }; // count the extra references of every tr
 // workgroup's region of an unordered list (`u`: an LDS cursor hands out the places) — so that once the prefix sum over the counts is known k_place_extra moves them to where
 // kModeEmit's second walk would have written them (reference n + offsets[t] + slot: the same arrays, bit for bit) and the split trees are not walked again.  Only the LAST
 // counting pass's list is used (every pass starts its regions afresh); a region that overflows sets u_count[gridDim.x] and the host falls back to the second walk.
-struct PieceList { float* box; uint32_t* key; float* base_box; uint32_t* count; uint32_t region_cap; }; // box: 6 floats, key: (t, slot) per piece; count[wg], count[grid] = overflow
+struct PieceList { float* box = nullptr; uint32_t* key = nullptr; float* base_box = nullptr; uint32_t* count = nullptr; uint32_t region_cap = 0u; }; // box: 6 floats, key: (t, slot) per piece; count[wg], count[grid] = overflow
 template <int MODE>
 __global__ __launch_bounds__(256) void k_presplit(const TriRec* recs, const float* tbox, uint32_t n, double thr, int depth_cap, SplitFrame* frames, uint32_t* counts,
                                                   const uint32_t* offsets, uint32_t* hist, float* ref_box, uint32_t* ref_tri, uint32_t* capped, PieceList u) {
@@ -504,7 +499,6 @@ __global__ __launch_bounds__(256) void k_select(const Task* tasks, uint32_t nt, 
 // Exclusive prefix sum of n 32-bit counts (the per-triangle reference counts of the pre-splitting passes) in three launches: k_scan_sums (one sum per block of
 // kScanBlock items), k_scan_blocks (ONE workgroup scans the block sums in place), k_scan_apply (every block scans its items from its base).  A thread owns 16
 // consecutive items; the block's 256 thread sums are scanned through LDS.  Wrap-around arithmetic like any u32 sum (the caller bounds the total).
-constexpr uint32_t kScanItems = 16u, kScanBlock = 256u * kScanItems;
 __global__ __launch_bounds__(256) void k_scan_sums(const uint32_t* __restrict__ in, uint32_t n, uint32_t* __restrict__ block_sum) {
     __shared__ uint32_t s_w[4];
     const uint32_t base = blockIdx.x * kScanBlock + threadIdx.x * kScanItems;
@@ -887,13 +881,14 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t* order, const uin
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------
-struct Arena { // one allocation carved into 256-byte aligned pieces
-    char* base = nullptr; size_t size = 0, used = 0;
-    hipError_t reserve(size_t bytes) { size = bytes; used = 0; return hipMalloc((void**)&base, bytes); }
-    template <typename T> T* take(size_t n) { used = (used + 255u) & ~(size_t)255u; T* p = (T*)(base + used); used += n * sizeof(T); return used <= size ? p : nullptr; }
-    void release() { if (base) (void)hipFree(base); base = nullptr; }
-};
-template <typename T> size_t padded(size_t n) { return ((n * sizeof(T)) + 255u + 256u) & ~(size_t)255u; }
+// Build::run() goes through the stages named at the top of this file on three arenas, one per allocation phase; where a phase's buffers lie is the business of
+// its carve function (bvh_arena.h), which gives the bytes to reserve (on a measuring arena) and the pointers (on the reserved one).
+struct Records { using Task = nrays::Task; using Node2 = nrays::Node2; using SplitInfo = nrays::SplitInfo; using Counters = nrays::Counters; using SplitFrame = nrays::SplitFrame;
+                 using PartDev = nrays::PartDev; using Tmp4 = nrays::Tmp4; };
+static_assert(sizeof(Task) == kTaskBytes && sizeof(Node2) == kNode2Bytes && sizeof(SplitInfo) == kSplitInfoBytes && sizeof(Counters) == kCountersBytes &&
+              sizeof(SplitFrame) == kSplitFrameBytes && sizeof(PartDev) == kPartDevBytes && sizeof(Tmp4) == kTmp4Bytes, "bvh_arena.h states the sizes of these records");
+hipError_t reserve(Arena& a, size_t bytes) { a.size = bytes; a.used = 0; return hipMalloc((void**)&a.base, bytes); }
+void release(Arena& a) { if (a.base) (void)hipFree(a.base); a.base = nullptr; }
 
 struct Stopwatch {
     bool on; std::chrono::steady_clock::time_point t0;
@@ -913,93 +908,82 @@ struct Stopwatch {
         if (e_ != hipSuccess) { err = std::string("device BLAS build: ") + #expr + ": " + hipGetErrorString(e_); return e_ == hipErrorOutOfMemory ? NRAYS_ERR_OOM : NRAYS_ERR_HIP; } \
     } while (0)
 
-int build_impl(const std::vector<DeviceMeshPart>& parts, const DeviceBuildOptions& opt, int32_t node_base, uint32_t prim_base, DeviceBlas& out, std::string& err,
-               Arena& a1, Arena& a2, Arena& a3) {
-    const bool verbose = opt.verbose;
-    Stopwatch sw(verbose);
-    size_t n = 0;
-    for (const DeviceMeshPart& p : parts) n += p.num_triangles;
-    if (n == 0 || n >= (1u << 28)) { err = "device BLAS build: bad triangle count"; return NRAYS_ERR_BAD_ARG; }
-    out.num_triangles = n;
-    const uint32_t nblocks_tri = [&] { uint32_t b = 0; for (const DeviceMeshPart& p : parts) b += (p.num_triangles + 255u) / 256u; return b; }();
-    const uint32_t split_grid = (uint32_t)std::min<size_t>(opt.split_grid_max, (n + 255) / 256);
-
-    // ---- phase 1: inputs, triangle records, pre-split counts ----
+struct Build { // what crosses the stages, then the stages in the order run() calls them
+    const std::vector<DeviceMeshPart>& parts; const DeviceBuildOptions& opt; const int32_t node_base; const uint32_t prim_base; DeviceBlas& out; std::string& err;
+    Arena* arena; // one per allocation phase
+    Stopwatch sw;
+    size_t n = 0; // triangles
     std::map<const void*, std::pair<size_t, void*>> uploads; // host array -> (bytes, device copy): meshes alias their vertex arrays
-    for (const DeviceMeshPart& p : parts) {
-        if (!p.vertices || !p.indices) { err = "device BLAS build: null mesh array"; return NRAYS_ERR_BAD_ARG; }
-        auto note = [&](const void* h, size_t bytes) { if (h) { auto& u = uploads[h]; u.first = std::max(u.first, bytes); u.second = nullptr; } };
-        note(p.vertices, (size_t)p.num_vertices * 24u); note(p.uvs, (size_t)p.num_vertices * 16u); note(p.indices, (size_t)p.num_triangles * 12u);
-    }
-    size_t bytes1 = 0;
-    for (auto& kv : uploads) bytes1 += padded<char>(kv.second.first);
-    // the per-thread stacks of k_presplit (0.9 GB from 131 k triangles on) exist only if pre-splitting can run at all
-    const bool may_split = opt.presplit && n >= 64 && opt.budget > 0.0;
-    const size_t frame_count = may_split ? (size_t)split_grid * 256u * (kSplitDepthMax + 1) : 1u;
-    const size_t scan_bytes = ((n + 1 + kScanBlock - 1) / kScanBlock) * sizeof(uint32_t); // block sums of the prefix sum over the per-triangle reference counts (exclusive_scan_u32)
-    // one-walk pre-splitting: the pieces of the last counting pass are kept (PieceList): 1.25 x the larger budget in all, dealt to the workgroups' regions (their triangles are
-    // a uniform sample of the mesh); NRAYS_PRESPLIT_ONE_WALK=0: walk twice as before (A/B)
-    const bool one_walk = may_split && opt.one_walk;
-    // (NRAYS_DEBUG_PIECE_CAP=c: c places per region — tests: the regions overflow and the second walk takes over)
-    const uint32_t region_cap = !one_walk ? 0u : opt.debug_piece_cap ? opt.debug_piece_cap
-                                : (uint32_t)((size_t)(1.25 * std::max(opt.budget, opt.budget_hairy) * (double)n) / split_grid + 1024u);
-    const size_t u_pieces = (size_t)region_cap * split_grid;
-    bytes1 += padded<TriRec>(n) + padded<TriUv>(n) + padded<float>(6 * n) + 2 * padded<double>(nblocks_tri) + padded<Counters>(1) + 2 * padded<uint32_t>(n + 1) +
-              padded<uint32_t>(kHistBins) + padded<SplitFrame>(frame_count) + padded<char>(scan_bytes) + padded<PartDev>(parts.size()) + 4096;
-    if (one_walk) bytes1 += padded<float>(6 * u_pieces) + padded<uint32_t>(2 * u_pieces) + padded<float>(6 * n) + padded<uint32_t>(split_grid + 1u);
-    DB_TRY(a1.reserve(bytes1));
-    sw.lap("allocation (phase 1)");
-    {   // A merged group (the sponza stand-in: 270 meshes under one isometry, ~800 small arrays) paid one synchronous hipMemcpy per array — 4-5 ms of
-        // a 12 ms build.  Arrays below 1 MB are staged into one host buffer in the order the arena hands out their device pieces (consecutive, 256-byte
-        // aligned) and go over in ONE copy per run; large arrays are copied from where they lie.
-        std::vector<char> stage;
-        char* run_dst = nullptr;
-        auto flush = [&]() -> hipError_t {
-            hipError_t e = hipSuccess;
-            if (run_dst && !stage.empty()) e = hipMemcpy(run_dst, stage.data(), stage.size(), hipMemcpyHostToDevice);
-            stage.clear(); run_dst = nullptr;
-            return e;
-        };
-        size_t small_arrays = 0, small_bytes = 0;
-        for (auto& kv : uploads) {
-            const size_t bytes = kv.second.first;
-            char* dst = a1.take<char>(bytes);
-            kv.second.second = dst;
-            if (!dst) { err = "device BLAS build: arena overflow (uploads)"; return NRAYS_ERR_OOM; }
-            if (bytes >= (1u << 20)) {
-                DB_TRY(flush());
-                DB_TRY(hipMemcpy(dst, kv.first, bytes, hipMemcpyHostToDevice));
-                if (verbose) { char what[64]; snprintf(what, sizeof what, "  upload of %.1f MB", bytes / 1048576.0); sw.lap(what); }
-                continue;
-            }
-            if (!run_dst) run_dst = dst;
-            const size_t at = (size_t)(dst - run_dst); // the arena's pieces are consecutive: the staging buffer mirrors their layout
-            if (stage.size() < at + bytes) stage.resize(at + bytes);
-            std::memcpy(stage.data() + at, kv.first, bytes);
-            ++small_arrays; small_bytes += bytes;
+    Phase1Sizes s1; Phase1Buffers<Records> b1; PieceList pieces;
+    Counters h_ctr;
+    size_t nrefs = 0; bool hairy = false, do_split = false; double thr = 0.0; // what pre-splitting decided
+    Phase2Sizes s2; Phase2Buffers<Records> b2;
+    float prim_cost = 0.f; int max_leaf = 0;
+
+    // Phase 1's arena and the caller's arrays in it.
+    int upload() {
+        Arena& a1 = arena[0]; const bool verbose = opt.verbose;
+        uint32_t nblocks_tri = 0;
+        for (const DeviceMeshPart& p : parts) {
+            if (!p.vertices || !p.indices) { err = "device BLAS build: null mesh array"; return NRAYS_ERR_BAD_ARG; }
+            auto note = [&](const void* h, size_t bytes) { if (h) { auto& u = uploads[h]; u.first = std::max(u.first, bytes); u.second = nullptr; } };
+            note(p.vertices, (size_t)p.num_vertices * 24u); note(p.uvs, (size_t)p.num_vertices * 16u); note(p.indices, (size_t)p.num_triangles * 12u);
+            nblocks_tri += (p.num_triangles + 255u) / 256u;
         }
-        DB_TRY(flush());
-        if (verbose && small_arrays) { char what[96]; snprintf(what, sizeof what, "  upload of %zu small arrays (%.1f MB) in staged runs", small_arrays, small_bytes / 1048576.0); sw.lap(what); }
+        std::vector<size_t> upload_bytes;
+        for (auto& kv : uploads) upload_bytes.push_back(kv.second.first);
+        s1 = phase1_sizes(std::move(upload_bytes), n, parts.size(), nblocks_tri, opt);
+        DB_TRY(reserve(a1, measure(carve1<Records>, s1)));
+        sw.lap("allocation (phase 1)");
+        carve1<Records>(a1, s1, b1);
+        {   // A merged group (the sponza stand-in: 270 meshes under one isometry, ~800 small arrays) paid one synchronous hipMemcpy per array — 4-5 ms of
+            // a 12 ms build.  Arrays below 1 MB are staged into one host buffer in the order the arena hands out their device pieces (consecutive, 256-byte
+            // aligned) and go over in ONE copy per run; large arrays are copied from where they lie.
+            std::vector<char> stage;
+            char* run_dst = nullptr;
+            auto flush = [&]() -> hipError_t {
+                hipError_t e = hipSuccess;
+                if (run_dst && !stage.empty()) e = hipMemcpy(run_dst, stage.data(), stage.size(), hipMemcpyHostToDevice);
+                stage.clear(); run_dst = nullptr;
+                return e;
+            };
+            size_t small_arrays = 0, small_bytes = 0, k = 0;
+            for (auto& kv : uploads) {
+                const size_t bytes = kv.second.first;
+                char* dst = b1.uploads[k++];
+                kv.second.second = dst;
+                if (!dst) { err = "device BLAS build: arena overflow (uploads)"; return NRAYS_ERR_OOM; }
+                if (bytes >= (1u << 20)) {
+                    DB_TRY(flush());
+                    DB_TRY(hipMemcpy(dst, kv.first, bytes, hipMemcpyHostToDevice));
+                    if (verbose) { char what[64]; snprintf(what, sizeof what, "  upload of %.1f MB", bytes / 1048576.0); sw.lap(what); }
+                    continue;
+                }
+                if (!run_dst) run_dst = dst;
+                const size_t at = (size_t)(dst - run_dst); // the arena's pieces are consecutive: the staging buffer mirrors their layout
+                if (stage.size() < at + bytes) stage.resize(at + bytes);
+                std::memcpy(stage.data() + at, kv.first, bytes);
+                ++small_arrays; small_bytes += bytes;
+            }
+            DB_TRY(flush());
+            if (verbose && small_arrays) { char what[96]; snprintf(what, sizeof what, "  upload of %zu small arrays (%.1f MB) in staged runs", small_arrays, small_bytes / 1048576.0); sw.lap(what); }
+        }
+        if (!b1.frames || !b1.scan_tmp || !b1.parts) { err = "device BLAS build: arena overflow (phase 1)"; return NRAYS_ERR_OOM; }
+        pieces.region_cap = s1.region_cap;
+        if (s1.one_walk) {
+            pieces.box = b1.piece_box; pieces.key = b1.piece_key; pieces.base_box = b1.piece_base_box; pieces.count = b1.piece_count;
+            if (!pieces.count) { err = "device BLAS build: arena overflow (phase 1, piece list)"; return NRAYS_ERR_OOM; }
+        }
+        sw.lap("upload of the mesh arrays");
+        return NRAYS_OK;
     }
-    TriRec* recs = a1.take<TriRec>(n); TriUv* uvs = a1.take<TriUv>(n); float* tbox = a1.take<float>(6 * n);
-    double* part_area = a1.take<double>(nblocks_tri); double* part_tri2 = a1.take<double>(nblocks_tri);
-    Counters* ctr = a1.take<Counters>(1);
-    uint32_t* counts = a1.take<uint32_t>(n + 1); uint32_t* offsets = a1.take<uint32_t>(n + 1); uint32_t* hist = a1.take<uint32_t>(kHistBins);
-    SplitFrame* frames = a1.take<SplitFrame>(frame_count);
-    void* scan_tmp1 = a1.take<char>(scan_bytes + 16);
-    PartDev* dparts = a1.take<PartDev>(parts.size());
-    if (!frames || !scan_tmp1 || !dparts) { err = "device BLAS build: arena overflow (phase 1)"; return NRAYS_ERR_OOM; }
-    PieceList pieces; pieces.box = nullptr; pieces.key = nullptr; pieces.base_box = nullptr; pieces.count = nullptr; pieces.region_cap = region_cap;
-    if (one_walk) {
-        pieces.box = a1.take<float>(6 * u_pieces); pieces.key = a1.take<uint32_t>(2 * u_pieces); pieces.base_box = a1.take<float>(6 * n); pieces.count = a1.take<uint32_t>(split_grid + 1u);
-        if (!pieces.count) { err = "device BLAS build: arena overflow (phase 1, piece list)"; return NRAYS_ERR_OOM; }
-    }
-    sw.lap("upload of the mesh arrays");
-    Counters h_ctr; std::memset(&h_ctr, 0, sizeof h_ctr);
-    for (int k = 0; k < 6; ++k) { h_ctr.bounds[k] = 0xffffffffu; h_ctr.bounds[6 + k] = 0u; }
-    h_ctr.root_ref = kEmptyChild;
-    DB_TRY(hipMemcpy(ctr, &h_ctr, sizeof h_ctr, hipMemcpyHostToDevice));
-    {
+    // Stage 1: records, uvs and f32 boxes of all parts in one launch; the checks of the caller's data and the bounds of the BLAS come back in the counters.
+    int triangle_records() {
+        Counters* ctr = b1.ctr;
+        std::memset(&h_ctr, 0, sizeof h_ctr);
+        for (int k = 0; k < 6; ++k) { h_ctr.bounds[k] = 0xffffffffu; h_ctr.bounds[6 + k] = 0u; }
+        h_ctr.root_ref = kEmptyChild;
+        DB_TRY(hipMemcpy(ctr, &h_ctr, sizeof h_ctr, hipMemcpyHostToDevice));
         std::vector<PartDev> hp;
         uint32_t tri_base = 0, block_base = 0;
         for (const DeviceMeshPart& p : parts) {
@@ -1010,205 +994,222 @@ int build_impl(const std::vector<DeviceMeshPart>& parts, const DeviceBuildOption
             hp.push_back(d);
             tri_base += p.num_triangles; block_base += (p.num_triangles + 255u) / 256u;
         }
-        DB_TRY(hipMemcpy(dparts, hp.data(), hp.size() * sizeof(PartDev), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_tri_records, dim3(block_base), dim3(256), 0, 0, (const PartDev*)dparts, (uint32_t)hp.size(), recs, uvs, tbox, part_area, part_tri2, ctr);
+        DB_TRY(hipMemcpy(b1.parts, hp.data(), hp.size() * sizeof(PartDev), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_tri_records, dim3(block_base), dim3(256), 0, 0, (const PartDev*)b1.parts, (uint32_t)hp.size(), b1.recs, b1.uvs, b1.tbox, b1.part_area, b1.part_tri2, ctr);
+        DB_TRY(hipGetLastError());
+        DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
+        for (int k = 0; k < 3; ++k) if (h_ctr.err & (1u << k)) return refuse_mesh((MeshError)k, err);
+        for (int a = 0; a < 3; ++a) { out.mn[a] = dec(h_ctr.bounds[a]); out.mx[a] = dec(h_ctr.bounds[6 + a]); }
+        sw.lap("triangle records");
+        return NRAYS_OK;
     }
-    DB_TRY(hipGetLastError());
-    DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
-    if (h_ctr.err & 1u) { err = "triangle index out of range"; return NRAYS_ERR_BAD_ARG; }
-    if (h_ctr.err & 2u) { err = "mesh vertex coordinate is not exactly representable in f32 (see DESIGN.md: f32-exact mesh storage)"; return NRAYS_ERR_UNSUPPORTED; }
-    if (h_ctr.err & 4u) { err = "mesh uv is not exactly representable in f32"; return NRAYS_ERR_UNSUPPORTED; }
-    auto dec_host = [](uint32_t e) { uint32_t b = (e & 0x80000000u) ? (e & 0x7fffffffu) : ~e; float f; std::memcpy(&f, &b, 4); return f; };
-    for (int a = 0; a < 3; ++a) { out.mn[a] = dec_host(h_ctr.bounds[a]); out.mx[a] = dec_host(h_ctr.bounds[6 + a]); }
-    sw.lap("triangle records");
-
-    // pre-splitting: the rule and the constants of scene_build.cpp: presplit()
-    size_t nrefs = n; bool hairy = false; double thr = 0.0; bool do_split = false;
-    if (may_split) {
+    // One counting pass of k_presplit against threshold t, at most `cap` levels deep; extra = the references the pass would add.
+    int count_pass(double t, int cap, uint32_t& extra) {
+        const Phase1Buffers<Records>& b = b1; const uint32_t split_grid = s1.split_grid; uint32_t* capped = &b.ctr->pad;
+        DB_TRY(hipMemset(b.hist, 0, kHistBins * sizeof(uint32_t)));
+        DB_TRY(hipMemset(capped, 0, 4));
+        if (pieces.count) DB_TRY(hipMemset(pieces.count + split_grid, 0, 4)); // the overflow mark of this pass's piece list
+        hipLaunchKernelGGL(k_presplit<kModeHist>, dim3(split_grid), dim3(256), 0, 0, b.recs, b.tbox, (uint32_t)n, t, cap, b.frames, b.counts, b.offsets, b.hist, (float*)nullptr, (uint32_t*)nullptr, capped, pieces);
+        DB_TRY(exclusive_scan_u32(b.counts, b.offsets, (uint32_t)(n + 1), b.scan_tmp));
+        DB_TRY(hipMemcpy(&extra, b.offsets + n, 4, hipMemcpyDeviceToHost));
+        return NRAYS_OK;
+    }
+    // The threshold the plan's budget amounts to (the rule and the constants of scene_build.cpp: presplit()), and with it the number of references.
+    // Survey pass: every piece split against min_gain, but at most kSurveyDepth levels deep (a handful of huge degenerate triangles among small
+    // ones would otherwise make single threads walk up to 2^20 pieces each before the budget is even known), with a histogram of the empty
+    // areas of the splits.  If nothing was cut short and the count fits the budget, that is the answer.  Otherwise the threshold the budget
+    // amounts to is read off the histogram and the split trees are walked again, full depth, against it — each such pass files its own
+    // histogram, so a second correction (the first histogram missed what lay below the survey depth) lands within a bin of the budget.
+    int settle_threshold() {
+        const Phase1Buffers<Records>& b = b1; const uint32_t nblocks_tri = s1.nblocks_tri;
         std::vector<double> pa(nblocks_tri), pt(nblocks_tri);
-        DB_TRY(hipMemcpy(pa.data(), part_area, nblocks_tri * sizeof(double), hipMemcpyDeviceToHost));
-        DB_TRY(hipMemcpy(pt.data(), part_tri2, nblocks_tri * sizeof(double), hipMemcpyDeviceToHost));
+        DB_TRY(hipMemcpy(pa.data(), b.part_area, nblocks_tri * sizeof(double), hipMemcpyDeviceToHost));
+        DB_TRY(hipMemcpy(pt.data(), b.part_tri2, nblocks_tri * sizeof(double), hipMemcpyDeviceToHost));
         double total_area = 0.0, total_tri2 = 0.0;
-        for (uint32_t b = 0; b < nblocks_tri; ++b) { total_area += pa[b]; total_tri2 += pt[b]; }
-        hairy = total_area > 0.0 && (total_area - total_tri2) > opt.hairy_emptiness * total_area;
-        const double min_gain = (hairy ? opt.min_gain_hairy : opt.min_gain) * total_area / (double)n;
-        const size_t budget = (size_t)((hairy ? opt.budget_hairy : opt.budget) * (double)n);
-        // Survey pass: every piece split against min_gain, but at most kSurveyDepth levels deep (a handful of huge degenerate triangles among small
-        // ones would otherwise make single threads walk up to 2^20 pieces each before the budget is even known), with a histogram of the empty
-        // areas of the splits.  If nothing was cut short and the count fits the budget, that is the answer.  Otherwise the threshold the budget
-        // amounts to is read off the histogram and the split trees are walked again, full depth, against it — each such pass files its own
-        // histogram, so a second correction (the first histogram missed what lay below the survey depth) lands within a bin of the budget.
+        for (uint32_t k = 0; k < nblocks_tri; ++k) { total_area += pa[k]; total_tri2 += pt[k]; }
+        const PresplitPlan plan = presplit_plan(total_area, total_tri2, n, opt.budget, opt.budget_hairy, opt.min_gain, opt.min_gain_hairy, opt.hairy_emptiness);
+        hairy = plan.hairy;
         constexpr int kSurveyDepth = 10;
-        uint32_t* capped = &ctr->pad;
-        uint32_t extra = 0; thr = min_gain;
-        auto pass = [&](double t, int cap) -> int {
-            DB_TRY(hipMemset(hist, 0, kHistBins * sizeof(uint32_t)));
-            DB_TRY(hipMemset(capped, 0, 4));
-            if (pieces.count) DB_TRY(hipMemset(pieces.count + split_grid, 0, 4)); // the overflow mark of this pass's piece list
-            hipLaunchKernelGGL(k_presplit<kModeHist>, dim3(split_grid), dim3(256), 0, 0, recs, tbox, (uint32_t)n, t, cap, frames, counts, offsets, hist, (float*)nullptr, (uint32_t*)nullptr, capped, pieces);
-            DB_TRY(exclusive_scan_u32(counts, offsets, (uint32_t)(n + 1), (uint32_t*)scan_tmp1));
-            DB_TRY(hipMemcpy(&extra, offsets + n, 4, hipMemcpyDeviceToHost));
-            return NRAYS_OK;
-        };
-        { const int rc = pass(min_gain, kSurveyDepth); if (rc != NRAYS_OK) return rc; }
+        uint32_t extra = 0; thr = plan.min_gain;
+        { const int rc = count_pass(plan.min_gain, kSurveyDepth, extra); if (rc != NRAYS_OK) return rc; }
         uint32_t was_capped = 0;
-        DB_TRY(hipMemcpy(&was_capped, capped, 4, hipMemcpyDeviceToHost));
+        DB_TRY(hipMemcpy(&was_capped, &b.ctr->pad, 4, hipMemcpyDeviceToHost));
         bool exact = !was_capped; // `counts` describe the full-depth walk against `thr`
-        for (int round = 0; round < 6 && ((size_t)extra > budget || !exact); ++round) {
-            if ((size_t)extra > budget) { // the budget binds: the threshold is the empty area below which the budget-th largest split falls
+        for (int round = 0; round < 6 && ((size_t)extra > plan.budget || !exact); ++round) {
+            if ((size_t)extra > plan.budget) { // the budget binds: the threshold is the empty area below which the budget-th largest split falls
                 std::vector<uint32_t> h(kHistBins);
-                DB_TRY(hipMemcpy(h.data(), hist, kHistBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
-                size_t cum = 0; uint32_t b = kHistBins;
-                while (b > 0 && cum + h[b - 1] <= budget) { cum += h[b - 1]; --b; } // bins >= b fit in the budget
-                uint32_t bits = b << kHistShift; float edge; std::memcpy(&edge, &bits, 4);
+                DB_TRY(hipMemcpy(h.data(), b.hist, kHistBins * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                size_t cum = 0; uint32_t bin = kHistBins;
+                while (bin > 0 && cum + h[bin - 1] <= plan.budget) { cum += h[bin - 1]; --bin; } // bins >= bin fit in the budget
+                uint32_t bits = bin << kHistShift; float edge; std::memcpy(&edge, &bits, 4);
                 // (float)gain rounds to nearest: a piece just below the edge may have been filed above it; `gain > thr` is what every pass applies
-                thr = std::max(std::max(min_gain, (double)edge), round ? thr * 1.05 : 0.0); // (strictly rising: the loop ends)
+                thr = std::max(std::max(plan.min_gain, (double)edge), round ? thr * 1.05 : 0.0); // (strictly rising: the loop ends)
             }
-            const int rc = pass(thr, kSplitDepthMax); if (rc != NRAYS_OK) return rc;
+            const int rc = count_pass(thr, kSplitDepthMax, extra); if (rc != NRAYS_OK) return rc;
             exact = true;
         }
-        if ((size_t)extra > 2 * budget + 1024) { err = "device BLAS build: pre-splitting does not settle on its budget"; return NRAYS_ERR_HIP; }
+        if ((size_t)extra > 2 * plan.budget + 1024) { err = "device BLAS build: pre-splitting does not settle on its budget"; return NRAYS_ERR_HIP; }
         nrefs = n + extra; do_split = extra > 0;
         if (pieces.count) { // did the last pass's pieces fit their regions?
             uint32_t over = 0;
-            DB_TRY(hipMemcpy(&over, pieces.count + split_grid, 4, hipMemcpyDeviceToHost));
-            if (over) { pieces.box = nullptr; if (verbose) fprintf(stderr, "  device build: piece list overflow, the split trees are walked a second time\n"); }
+            DB_TRY(hipMemcpy(&over, pieces.count + s1.split_grid, 4, hipMemcpyDeviceToHost));
+            if (over) { pieces.box = nullptr; if (opt.verbose) fprintf(stderr, "  device build: piece list overflow, the split trees are walked a second time\n"); }
         }
-    }
-    out.hairy = hairy;
-    if (nrefs + (size_t)prim_base >= (1u << 28)) { err = "too many triangles"; return NRAYS_ERR_UNSUPPORTED; }
-    sw.lap("pre-split counts");
-
-    // ---- phase 2: references, binary build ----
-    const uint32_t R = (uint32_t)nrefs;
-    const size_t cap_div = (size_t)std::max(1, opt.debug_cap_div);
-    const size_t max_t = (R / (kSmall + 1u)) / cap_div + 2u, max_c = R / kChunk + max_t + 2u, small_cap = (R / 8u + 1024u) / cap_div + 1u;
-    size_t bytes2 = padded<float>(6 * (size_t)R) + 3 * padded<uint32_t>(R) + padded<Node2>(R) + 2 * padded<Task>(max_t) + padded<Task>(small_cap) + 2 * padded<uint32_t>(max_t * kBinWords) +
-                    padded<uint32_t>(max_t * 96u) + padded<SplitInfo>(max_t) + padded<uint32_t>(max_t + 1) + 4 * padded<uint32_t>(max_c) + padded<uint32_t>(max_c * 96u) + (1u << 16);
-    DB_TRY(a2.reserve(bytes2));
-    sw.lap("allocation (phase 2)");
-    float* ref_box = a2.take<float>(6 * (size_t)R); uint32_t* ref_tri = a2.take<uint32_t>(R);
-    uint32_t* order0 = a2.take<uint32_t>(R); uint32_t* order1 = a2.take<uint32_t>(R);
-    Node2* node2 = a2.take<Node2>(R);
-    Task* tasks[2] = {a2.take<Task>(max_t), a2.take<Task>(max_t)}; Task* small = a2.take<Task>(small_cap);
-    uint32_t* gmn = a2.take<uint32_t>(max_t * kBinWords); uint32_t* gmx = a2.take<uint32_t>(max_t * kBinWords); uint32_t* gcnt = a2.take<uint32_t>(max_t * 96u);
-    SplitInfo* split = a2.take<SplitInfo>(max_t); uint32_t* chunk_base = a2.take<uint32_t>(max_t + 1);
-    uint32_t* chunk_task = a2.take<uint32_t>(max_c); uint32_t* chunk_off = a2.take<uint32_t>(max_c); uint32_t* scan_tmp = a2.take<uint32_t>(max_c); uint32_t* chunk_lefts = a2.take<uint32_t>(max_c);
-    uint32_t* chunk_cnt = a2.take<uint32_t>(max_c * 96u);
-    uint32_t* level2 = a2.take<uint32_t>(2); // k_chunk_scan_next: {tasks, chunks} of the next level
-    if (!chunk_cnt || !level2) { err = "device BLAS build: arena overflow (phase 2)"; return NRAYS_ERR_OOM; }
-    if (do_split && pieces.box) { // one walk: the kept pieces to their places (k_iota_refs: reference t = the unsplit piece of triangle t)
-        hipLaunchKernelGGL(k_iota_refs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)n, (const float*)pieces.base_box, ref_box, ref_tri);
-        hipLaunchKernelGGL(k_place_extra, dim3(split_grid), dim3(256), 0, 0, pieces, (const uint32_t*)offsets, (uint32_t)n, ref_box, ref_tri);
-    } else if (do_split) { PieceList none; none.box = nullptr; none.key = nullptr; none.base_box = nullptr; none.count = nullptr; none.region_cap = 0u;
-        hipLaunchKernelGGL(k_presplit<kModeEmit>, dim3(split_grid), dim3(256), 0, 0, recs, tbox, (uint32_t)n, thr, kSplitDepthMax, frames, counts, offsets, hist, ref_box, ref_tri, (uint32_t*)nullptr, none); }
-    else hipLaunchKernelGGL(k_iota_refs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)n, tbox, ref_box, ref_tri);
-    sw.lap("reference boxes");
-    const float prim_cost = hairy ? opt.prim_cost_hairy : opt.prim_cost;
-    const int max_leaf = std::min(std::max(opt.max_leaf, 1), 8);
-    for (int k = 0; k < 6; ++k) { h_ctr.bounds[k] = 0xffffffffu; h_ctr.bounds[6 + k] = 0u; }
-    h_ctr.n_next = h_ctr.n_small = h_ctr.overflow = h_ctr.n_binary = 0; h_ctr.root_ref = kEmptyChild;
-    DB_TRY(hipMemcpy(ctr, &h_ctr, sizeof h_ctr, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_root_bounds, dim3(std::min<uint32_t>(1024u, (R + 255u) / 256u)), dim3(256), 0, 0, ref_box, R, order0, ctr);
-    hipLaunchKernelGGL(k_root_task, dim3(1), dim3(1), 0, 0, tasks[0], small, R, ctr);
-    uint32_t nt = R > kSmall ? 1u : 0u; int cur = 0, levels = 0;
-    uint32_t nchunks = 0;
-    if (nt > 0) { // the first level's chunks; every later level's come back with its task count (k_chunk_scan_next)
-        hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, 0, tasks[cur], nt, chunk_base);
-        DB_TRY(hipMemcpy(&nchunks, chunk_base + nt, 4, hipMemcpyDeviceToHost));
-    }
-    while (nt > 0) {
-        if (nt > max_t) { err = "device BLAS build: task list overflow"; return NRAYS_ERR_HIP; }
-        if (nchunks == 0 || nchunks > max_c) { err = "device BLAS build: chunk list overflow"; return NRAYS_ERR_HIP; }
-        DB_TRY(hipMemsetAsync(gmn, 0xff, (size_t)nt * kBinWords * 4u, 0));
-        DB_TRY(hipMemsetAsync(gmx, 0, (size_t)nt * kBinWords * 4u, 0));
-        DB_TRY(hipMemsetAsync(gcnt, 0, (size_t)nt * 96u * 4u, 0));
-        DB_TRY(hipMemsetAsync(&ctr->n_next, 0, 4, 0));
-        hipLaunchKernelGGL(k_bin, dim3(nchunks), dim3(256), 0, 0, tasks[cur], nt, chunk_base, chunk_task, order0, order1, ref_box, gmn, gmx, gcnt, chunk_cnt);
-        hipLaunchKernelGGL(k_select, dim3((nt + 3u) / 4u), dim3(256), 0, 0, tasks[cur], nt, gmn, gmx, gcnt, split, tasks[cur ^ 1], small, (uint32_t)small_cap, node2, order0, order1, order0,
-                           ref_box, ctr, max_leaf, prim_cost);
-        hipLaunchKernelGGL(k_chunk_lefts, dim3((nchunks + 255u) / 256u), dim3(256), 0, 0, chunk_task, chunk_cnt, split, nchunks, chunk_lefts);
-        hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, 0, chunk_task, chunk_base, chunk_lefts, nchunks, chunk_off, scan_tmp);
-        hipLaunchKernelGGL(k_scatter, dim3(nchunks), dim3(256), 0, 0, tasks[cur], chunk_task, chunk_base, chunk_off, split, order0, order1, ref_box);
-        hipLaunchKernelGGL(k_chunk_scan_next, dim3(1), dim3(1024), 0, 0, tasks[cur ^ 1], (const uint32_t*)&ctr->n_next, (uint32_t)max_t, chunk_base, level2);
-        uint32_t two[2] = {0u, 0u};
-        DB_TRY(hipMemcpy(two, level2, 8, hipMemcpyDeviceToHost));
-        nt = two[0]; nchunks = two[1];
-        cur ^= 1; ++levels;
-        if (levels > 4096) { err = "device BLAS build: the large-node phase does not end"; return NRAYS_ERR_HIP; }
-    }
-    DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
-    if (h_ctr.overflow || h_ctr.n_small > small_cap) { err = "device BLAS build: small-node list overflow"; return NRAYS_ERR_HIP; }
-    if (verbose) fprintf(stderr, "  device build: %d large-node levels, %u small subtrees\n", levels, h_ctr.n_small);
-    sw.lap("large nodes");
-    if (h_ctr.n_small) hipLaunchKernelGGL(k_small, dim3((h_ctr.n_small + 3u) / 4u), dim3(256), 0, 0, small, h_ctr.n_small, order0, order1, order0, ref_box, node2, ctr, max_leaf, prim_cost);
-    DB_TRY(hipGetLastError());
-    DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
-#ifdef NR_BUILD_PHASES
-    fprintf(stderr, "  k_small wave cycles: load %llu, clear %llu, bin %llu, select %llu, partition %llu, node+leaf writes %llu, pop %llu\n", h_ctr.phase[0], h_ctr.phase[1], h_ctr.phase[2],
-            h_ctr.phase[3], h_ctr.phase[4], h_ctr.phase[5], h_ctr.phase[6]);
-#endif
-    sw.lap("small subtrees");
-
-    // ---- phase 3: collapse, layout, gather ----
-    DB_TRY(hipMalloc((void**)&out.tris, (size_t)R * sizeof(TriRec)));
-    DB_TRY(hipMalloc((void**)&out.uvs, (size_t)R * sizeof(TriUv)));
-    out.num_refs = R;
-    hipLaunchKernelGGL(k_gather, dim3((R + 255u) / 256u), dim3(256), 0, 0, order0, ref_tri, recs, uvs, R, out.tris, out.uvs);
-    if (h_ctr.root_ref < 0) { // a single leaf
-        const uint32_t v = (uint32_t)~h_ctr.root_ref;
-        out.root = h_ctr.root_ref == kEmptyChild ? kEmptyChild : make_leaf_ref((v >> 3) + prim_base, (v & 7u) + 1u);
-        if (h_ctr.root_ref == kEmptyChild) { err = "device BLAS build: no root"; return NRAYS_ERR_HIP; }
-        out.num_nodes = 0; out.max_depth = 0;
-        DB_TRY(hipDeviceSynchronize());
         return NRAYS_OK;
     }
-    const uint32_t nb = h_ctr.n_binary;
-    DB_TRY(a3.reserve(padded<Tmp4>(nb) + 4096));
-    Tmp4* tmp = a3.take<Tmp4>(nb);
-    {
-        Tmp4 root; std::memset(&root, 0, sizeof root); root.broot = (uint32_t)h_ctr.root_ref; root.dfs = 0;
-        DB_TRY(hipMemcpy(tmp, &root, sizeof root, hipMemcpyHostToDevice));
-        uint32_t one = 1; DB_TRY(hipMemcpy(&ctr->next_id, &one, 4, hipMemcpyHostToDevice));
+    // Stage 2, counting half: how many references pre-splitting makes of the triangles (none: one per triangle).
+    int presplit_counts() {
+        nrefs = n;
+        if (s1.may_split) { const int rc = settle_threshold(); if (rc != NRAYS_OK) return rc; }
+        out.hairy = hairy;
+        if (nrefs + (size_t)prim_base >= (1u << 28)) { err = "too many triangles"; return NRAYS_ERR_UNSUPPORTED; }
+        sw.lap("pre-split counts");
+        return NRAYS_OK;
     }
-    std::vector<uint32_t> level_start{0u};
-    uint32_t end = 1;
-    while (level_start.back() < end) {
-        const uint32_t s = level_start.back();
-        hipLaunchKernelGGL(k_collapse_level, dim3((end - s + 255u) / 256u), dim3(256), 0, 0, node2, tmp, s, end, ctr);
-        level_start.push_back(end);
-        DB_TRY(hipMemcpy(&end, &ctr->next_id, 4, hipMemcpyDeviceToHost));
-        if (end > nb) { err = "device BLAS build: more 4-wide nodes than binary nodes"; return NRAYS_ERR_HIP; }
-        if (level_start.size() > 4096) { err = "device BLAS build: the collapse does not end"; return NRAYS_ERR_HIP; }
+    // Phase 2's arena; stage 2, writing half: the reference boxes — the kept pieces to their places (one walk), a second walk, or one per triangle.
+    int reference_boxes() {
+        const uint32_t split_grid = s1.split_grid;
+        s2 = phase2_sizes(nrefs, opt.debug_cap_div);
+        DB_TRY(reserve(arena[1], measure(carve2<Records>, s2)));
+        sw.lap("allocation (phase 2)");
+        carve2<Records>(arena[1], s2, b2);
+        if (!b2.chunk_cnt || !b2.level2) { err = "device BLAS build: arena overflow (phase 2)"; return NRAYS_ERR_OOM; }
+        if (do_split && pieces.box) { // one walk: the kept pieces to their places (k_iota_refs: reference t = the unsplit piece of triangle t)
+            hipLaunchKernelGGL(k_iota_refs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)n, (const float*)pieces.base_box, b2.ref_box, b2.ref_tri);
+            hipLaunchKernelGGL(k_place_extra, dim3(split_grid), dim3(256), 0, 0, pieces, (const uint32_t*)b1.offsets, (uint32_t)n, b2.ref_box, b2.ref_tri);
+        } else if (do_split)
+            hipLaunchKernelGGL(k_presplit<kModeEmit>, dim3(split_grid), dim3(256), 0, 0, b1.recs, b1.tbox, (uint32_t)n, thr, kSplitDepthMax, b1.frames, b1.counts, b1.offsets, b1.hist, b2.ref_box, b2.ref_tri,
+                               (uint32_t*)nullptr, PieceList());
+        else hipLaunchKernelGGL(k_iota_refs, dim3((uint32_t)((n + 255) / 256)), dim3(256), 0, 0, (uint32_t)n, b1.tbox, b2.ref_box, b2.ref_tri);
+        sw.lap("reference boxes");
+        return NRAYS_OK;
     }
-    level_start.pop_back(); // the last entry opened an empty level
-    const uint32_t n4 = end;
-    for (size_t l = level_start.size(); l-- > 0;) {
-        const uint32_t s = level_start[l], e = l + 1 < level_start.size() ? level_start[l + 1] : n4;
-        if (e > s) hipLaunchKernelGGL(k_sizes_level, dim3((e - s + 255u) / 256u), dim3(256), 0, 0, tmp, s, e);
+    // Stage 3, large nodes: level by level until every range is a small subtree's.
+    int large_nodes() {
+        const Phase2Buffers<Records>& b = b2; Counters* ctr = b1.ctr;
+        const uint32_t R = s2.R; const size_t max_t = s2.max_t, max_c = s2.max_c, small_cap = s2.small_cap;
+        prim_cost = hairy ? opt.prim_cost_hairy : opt.prim_cost;
+        max_leaf = std::min(std::max(opt.max_leaf, 1), 8);
+        for (int k = 0; k < 6; ++k) { h_ctr.bounds[k] = 0xffffffffu; h_ctr.bounds[6 + k] = 0u; }
+        h_ctr.n_next = h_ctr.n_small = h_ctr.overflow = h_ctr.n_binary = 0; h_ctr.root_ref = kEmptyChild;
+        DB_TRY(hipMemcpy(ctr, &h_ctr, sizeof h_ctr, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_root_bounds, dim3(std::min<uint32_t>(1024u, (R + 255u) / 256u)), dim3(256), 0, 0, b.ref_box, R, b.order0, ctr);
+        hipLaunchKernelGGL(k_root_task, dim3(1), dim3(1), 0, 0, b.tasks[0], b.small, R, ctr);
+        uint32_t nt = R > kSmall ? 1u : 0u, nchunks = 0; int cur = 0, levels = 0;
+        if (nt > 0) { // the first level's chunks; every later level's come back with its task count (k_chunk_scan_next)
+            hipLaunchKernelGGL(k_chunk_scan, dim3(1), dim3(1024), 0, 0, b.tasks[cur], nt, b.chunk_base);
+            DB_TRY(hipMemcpy(&nchunks, b.chunk_base + nt, 4, hipMemcpyDeviceToHost));
+        }
+        while (nt > 0) {
+            if (nt > max_t) { err = "device BLAS build: task list overflow"; return NRAYS_ERR_HIP; }
+            if (nchunks == 0 || nchunks > max_c) { err = "device BLAS build: chunk list overflow"; return NRAYS_ERR_HIP; }
+            DB_TRY(hipMemsetAsync(b.gmn, 0xff, (size_t)nt * kBinWords * 4u, 0));
+            DB_TRY(hipMemsetAsync(b.gmx, 0, (size_t)nt * kBinWords * 4u, 0));
+            DB_TRY(hipMemsetAsync(b.gcnt, 0, (size_t)nt * 96u * 4u, 0));
+            DB_TRY(hipMemsetAsync(&ctr->n_next, 0, 4, 0));
+            hipLaunchKernelGGL(k_bin, dim3(nchunks), dim3(256), 0, 0, b.tasks[cur], nt, b.chunk_base, b.chunk_task, b.order0, b.order1, b.ref_box, b.gmn, b.gmx, b.gcnt, b.chunk_cnt);
+            hipLaunchKernelGGL(k_select, dim3((nt + 3u) / 4u), dim3(256), 0, 0, b.tasks[cur], nt, b.gmn, b.gmx, b.gcnt, b.split, b.tasks[cur ^ 1], b.small, (uint32_t)small_cap, b.node2, b.order0, b.order1, b.order0,
+                               b.ref_box, ctr, max_leaf, prim_cost);
+            hipLaunchKernelGGL(k_chunk_lefts, dim3((nchunks + 255u) / 256u), dim3(256), 0, 0, b.chunk_task, b.chunk_cnt, b.split, nchunks, b.chunk_lefts);
+            hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, 0, b.chunk_task, b.chunk_base, b.chunk_lefts, nchunks, b.chunk_off, b.scan_tmp);
+            hipLaunchKernelGGL(k_scatter, dim3(nchunks), dim3(256), 0, 0, b.tasks[cur], b.chunk_task, b.chunk_base, b.chunk_off, b.split, b.order0, b.order1, b.ref_box);
+            hipLaunchKernelGGL(k_chunk_scan_next, dim3(1), dim3(1024), 0, 0, b.tasks[cur ^ 1], (const uint32_t*)&ctr->n_next, (uint32_t)max_t, b.chunk_base, b.level2);
+            uint32_t two[2] = {0u, 0u};
+            DB_TRY(hipMemcpy(two, b.level2, 8, hipMemcpyDeviceToHost));
+            nt = two[0]; nchunks = two[1];
+            cur ^= 1; ++levels;
+            if (levels > 4096) { err = "device BLAS build: the large-node phase does not end"; return NRAYS_ERR_HIP; }
+        }
+        DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
+        if (h_ctr.overflow || h_ctr.n_small > small_cap) { err = "device BLAS build: small-node list overflow"; return NRAYS_ERR_HIP; }
+        if (opt.verbose) fprintf(stderr, "  device build: %d large-node levels, %u small subtrees\n", levels, h_ctr.n_small);
+        sw.lap("large nodes");
+        return NRAYS_OK;
     }
-    DB_TRY(hipMalloc((void**)&out.nodes, ((size_t)n4 + opt.node_tail) * sizeof(BvhNode)));
-    out.num_nodes = n4; out.node_capacity = (size_t)n4 + opt.node_tail;
-    for (size_t l = 0; l < level_start.size(); ++l) {
-        const uint32_t s = level_start[l], e = l + 1 < level_start.size() ? level_start[l + 1] : n4;
-        if (e > s) hipLaunchKernelGGL(k_emit_level, dim3((e - s + 255u) / 256u), dim3(256), 0, 0, tmp, s, e, out.nodes, node_base, prim_base);
+    // Stage 3, small nodes: one wave finishes each subtree in LDS.
+    int small_subtrees() {
+        const Phase2Buffers<Records>& b = b2; Counters* ctr = b1.ctr;
+        if (h_ctr.n_small) hipLaunchKernelGGL(k_small, dim3((h_ctr.n_small + 3u) / 4u), dim3(256), 0, 0, b.small, h_ctr.n_small, b.order0, b.order1, b.order0, b.ref_box, b.node2, ctr, max_leaf, prim_cost);
+        DB_TRY(hipGetLastError());
+        DB_TRY(hipMemcpy(&h_ctr, ctr, sizeof h_ctr, hipMemcpyDeviceToHost));
+#ifdef NR_BUILD_PHASES
+        fprintf(stderr, "  k_small wave cycles: load %llu, clear %llu, bin %llu, select %llu, partition %llu, node+leaf writes %llu, pop %llu\n", h_ctr.phase[0], h_ctr.phase[1], h_ctr.phase[2],
+                h_ctr.phase[3], h_ctr.phase[4], h_ctr.phase[5], h_ctr.phase[6]);
+#endif
+        sw.lap("small subtrees");
+        return NRAYS_OK;
     }
-    out.root = node_base; // the root of the collapse is node 0 of this BLAS
-    out.max_depth = (int)level_start.size() - 1;
-    DB_TRY(hipGetLastError());
-    DB_TRY(hipDeviceSynchronize());
-    if (verbose) fprintf(stderr, "  device build: %zu triangles, %u refs%s, %u binary nodes, %u 4-wide nodes, depth %d\n", n, R, hairy ? ", hair-like" : "", nb, n4, out.max_depth);
-    sw.lap("collapse + layout + gather");
-    return NRAYS_OK;
-}
+    // Stages 4 and 5 and phase 3's arena: the leaf-ordered triangles, the collapse level by level, subtree sizes bottom-up, the depth-first layout top-down.
+    int collapse_layout_gather() {
+        Counters* ctr = b1.ctr; const uint32_t R = s2.R;
+        DB_TRY(hipMalloc((void**)&out.tris, (size_t)R * sizeof(TriRec)));
+        DB_TRY(hipMalloc((void**)&out.uvs, (size_t)R * sizeof(TriUv)));
+        out.num_refs = R;
+        hipLaunchKernelGGL(k_gather, dim3((R + 255u) / 256u), dim3(256), 0, 0, b2.order0, b2.ref_tri, b1.recs, b1.uvs, R, out.tris, out.uvs);
+        if (h_ctr.root_ref < 0) { // a single leaf
+            const uint32_t v = (uint32_t)~h_ctr.root_ref;
+            out.root = h_ctr.root_ref == kEmptyChild ? kEmptyChild : make_leaf_ref((v >> 3) + prim_base, (v & 7u) + 1u);
+            if (h_ctr.root_ref == kEmptyChild) { err = "device BLAS build: no root"; return NRAYS_ERR_HIP; }
+            out.num_nodes = 0; out.max_depth = 0;
+            DB_TRY(hipDeviceSynchronize());
+            return NRAYS_OK;
+        }
+        const uint32_t nb = h_ctr.n_binary;
+        const Phase3Sizes s3{nb}; Phase3Buffers<Records> b3;
+        DB_TRY(reserve(arena[2], measure(carve3<Records>, s3)));
+        carve3<Records>(arena[2], s3, b3);
+        Tmp4* tmp = b3.tmp;
+        {
+            Tmp4 root; std::memset(&root, 0, sizeof root); root.broot = (uint32_t)h_ctr.root_ref; root.dfs = 0;
+            DB_TRY(hipMemcpy(tmp, &root, sizeof root, hipMemcpyHostToDevice));
+            uint32_t one = 1; DB_TRY(hipMemcpy(&ctr->next_id, &one, 4, hipMemcpyHostToDevice));
+        }
+        std::vector<std::pair<uint32_t, uint32_t>> levels; // compact ids [s, e) of each level of the 4-wide tree
+        uint32_t s = 0, end = 1;
+        while (s < end) {
+            hipLaunchKernelGGL(k_collapse_level, dim3((end - s + 255u) / 256u), dim3(256), 0, 0, b2.node2, tmp, s, end, ctr);
+            levels.emplace_back(s, end);
+            s = end;
+            DB_TRY(hipMemcpy(&end, &ctr->next_id, 4, hipMemcpyDeviceToHost));
+            if (end > nb) { err = "device BLAS build: more 4-wide nodes than binary nodes"; return NRAYS_ERR_HIP; }
+            if (levels.size() >= 4096) { err = "device BLAS build: the collapse does not end"; return NRAYS_ERR_HIP; }
+        }
+        const uint32_t n4 = end;
+        for (size_t l = levels.size(); l-- > 0;) hipLaunchKernelGGL(k_sizes_level, dim3((levels[l].second - levels[l].first + 255u) / 256u), dim3(256), 0, 0, tmp, levels[l].first, levels[l].second);
+        DB_TRY(hipMalloc((void**)&out.nodes, ((size_t)n4 + opt.node_tail) * sizeof(BvhNode)));
+        out.num_nodes = n4; out.node_capacity = (size_t)n4 + opt.node_tail;
+        for (const auto& l : levels) hipLaunchKernelGGL(k_emit_level, dim3((l.second - l.first + 255u) / 256u), dim3(256), 0, 0, tmp, l.first, l.second, out.nodes, node_base, prim_base);
+        out.root = node_base; // the root of the collapse is node 0 of this BLAS
+        out.max_depth = (int)levels.size() - 1;
+        DB_TRY(hipGetLastError());
+        DB_TRY(hipDeviceSynchronize());
+        if (opt.verbose) fprintf(stderr, "  device build: %zu triangles, %u refs%s, %u binary nodes, %u 4-wide nodes, depth %d\n", n, R, hairy ? ", hair-like" : "", nb, n4, out.max_depth);
+        sw.lap("collapse + layout + gather");
+        return NRAYS_OK;
+    }
+    int run() {
+        for (const DeviceMeshPart& p : parts) n += p.num_triangles;
+        if (n == 0 || n >= (1u << 28)) { err = "device BLAS build: bad triangle count"; return NRAYS_ERR_BAD_ARG; }
+        out.num_triangles = n;
+        int rc = upload();
+        if (rc == NRAYS_OK) rc = triangle_records();
+        if (rc == NRAYS_OK) rc = presplit_counts();
+        if (rc == NRAYS_OK) rc = reference_boxes();
+        if (rc == NRAYS_OK) rc = large_nodes();
+        if (rc == NRAYS_OK) rc = small_subtrees();
+        if (rc == NRAYS_OK) rc = collapse_layout_gather();
+        return rc;
+    }
+};
 
 } // namespace
 
 int build_blas_device(const std::vector<DeviceMeshPart>& parts, const DeviceBuildOptions& opt, int32_t node_base, uint32_t prim_base, DeviceBlas& out, std::string& err) {
-    Arena a1, a2, a3;
-    int rc = build_impl(parts, opt, node_base, prim_base, out, err, a1, a2, a3);
+    Arena arenas[3];
+    Build build{parts, opt, node_base, prim_base, out, err, arenas, Stopwatch(opt.verbose)};
+    const int rc = build.run();
     (void)hipDeviceSynchronize();
-    a1.release(); a2.release(); a3.release();
+    for (Arena& a : arenas) release(a);
     if (rc != NRAYS_OK) { free_device_blas(out); (void)hipGetLastError(); }
     return rc;
 }
@@ -1221,3 +1222,4 @@ void free_device_blas(DeviceBlas& b) {
 }
 
 } // namespace nrays
+

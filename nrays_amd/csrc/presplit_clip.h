@@ -3,6 +3,7 @@
 // (f64 +, -, *, /, sqrt are correctly rounded on gfx950 and -ffp-contract=off holds on both sides: identical boxes).
 #pragma once
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 
 #include "bvh_build.h"
@@ -95,5 +96,17 @@ NR_HD inline bool split_piece(const ClipPoly& poly, const PrimBounds& box, ClipP
 }
 // The rule both builders apply to a piece: it is split while its empty box area exceeds `thr` and half of its box.
 NR_HD inline bool piece_qualifies(double half_area, double gain, double thr) { return gain > thr && gain > NR_PRESPLIT_EMPTY * half_area; }
+
+// The plan both builders make for a mesh of n triangles from the sums of its box half areas and doubled triangle areas.  Hair-like meshes (most
+// triangles are thin and diagonal: the average box is more than `hairy_emptiness` empty) get the aggressive pair of knobs; architectural meshes,
+// where only a few curved parts qualify, the mild one.  min_gain: the least empty area worth a split; budget: extra references in all.
+struct PresplitPlan { bool hairy; double min_gain; size_t budget; };
+inline PresplitPlan presplit_plan(double total_area, double total_tri2, size_t n, double budget, double budget_hairy, double min_gain, double min_gain_hairy, double hairy_emptiness) {
+    PresplitPlan p;
+    p.hairy = total_area > 0.0 && (total_area - total_tri2) > hairy_emptiness * total_area;
+    p.min_gain = (p.hairy ? min_gain_hairy : min_gain) * total_area / (double)n;
+    p.budget = (size_t)((p.hairy ? budget_hairy : budget) * (double)n);
+    return p;
+}
 
 } // namespace nrays

@@ -130,6 +130,19 @@ void node_world_aabb(const NraysNode& n, const double R[9], const float mesh_mn[
     }
 }
 
+void empty_box(float mn[3], float mx[3]) {
+    for (int a = 0; a < 3; ++a) { mn[a] = std::numeric_limits<float>::infinity(); mx[a] = -std::numeric_limits<float>::infinity(); }
+}
+// Extends [mn, mx] by the local f32 bounds of a mesh = the union of its faces' vertices (TriMesh BVT root), checking the indices on the way.
+int extend_by_mesh(const NraysMesh& m, float mn[3], float mx[3], std::string& err) {
+    for (size_t t = 0; t < (size_t)m.num_triangles * 3u; ++t) {
+        const uint32_t vi = m.indices[t];
+        if (vi >= m.num_vertices) return refuse_mesh(kMeshIndexRange, err);
+        for (int a = 0; a < 3; ++a) { const float f = (float)m.vertices[3 * (size_t)vi + a]; mn[a] = std::min(mn[a], f); mx[a] = std::max(mx[a], f); }
+    }
+    return NRAYS_OK;
+}
+
 struct Blas {
     int32_t root;
     float mn[3], mx[3]; // local bounds
@@ -231,29 +244,23 @@ static void split_rec(const ClipPoly& poly, const PrimBounds& box, uint32_t tri,
 static bool presplit(const std::vector<TriRec>& recs, std::vector<PrimBounds>& refs_box, std::vector<uint32_t>& refs_tri) {
     const size_t n = recs.size();
     if (n < 64 || NR_PRESPLIT_BUDGET <= 0.0) return false;
-    double total_area = 0.0;
+    double total_area = 0.0, total_tri2 = 0.0;
     for (size_t i = 0; i < n; ++i) total_area += box_half_area(refs_box[i]);
-    // Hair-like meshes (most triangles are thin and diagonal: the average box is more than NR_PRESPLIT_HAIRY empty)
-    // get the aggressive setting; architectural meshes, where only a few curved parts qualify, the mild one.
-    double total_tri2 = 0.0;
     for (size_t i = 0; i < n; ++i) { ClipPoly p; tri_poly(recs[i], p); total_tri2 += poly_area2(p); }
-    const bool hairy = total_area > 0.0 && (total_area - total_tri2) > NR_PRESPLIT_HAIRY * total_area;
-    const double budget_per_tri = hairy ? NR_PRESPLIT_BUDGET_HAIRY : NR_PRESPLIT_BUDGET;
-    const double min_gain = (hairy ? NR_PRESPLIT_MINGAIN_HAIRY : NR_PRESPLIT_MINGAIN) * total_area / (double)n;
-    const size_t budget = (size_t)(budget_per_tri * (double)n);
+    const PresplitPlan plan = presplit_plan(total_area, total_tri2, n, NR_PRESPLIT_BUDGET, NR_PRESPLIT_BUDGET_HAIRY, NR_PRESPLIT_MINGAIN, NR_PRESPLIT_MINGAIN_HAIRY, NR_PRESPLIT_HAIRY);
     constexpr size_t kExactBelow = 400000; // triangles: below this the heap runs on the whole mesh
     if (n <= kExactBelow) {
         std::vector<uint32_t> all(n);
         for (size_t i = 0; i < n; ++i) all[i] = (uint32_t)i;
-        presplit_heap(recs, all, refs_box, refs_tri, budget, min_gain);
-        return hairy;
+        presplit_heap(recs, all, refs_box, refs_tri, plan.budget, plan.min_gain);
+        return plan.hairy;
     }
     // Large meshes: the threshold is measured on every s-th triangle with 1/s of the budget, then all triangles are
     // split against it in parallel.
     const size_t stride = (n + kExactBelow / 4 - 1) / (kExactBelow / 4);
     std::vector<uint32_t> sample; std::vector<PrimBounds> sbox; std::vector<uint32_t> sowner;
     for (size_t i = 0; i < n; i += stride) { sample.push_back((uint32_t)i); sbox.push_back(refs_box[i]); sowner.push_back((uint32_t)i); }
-    const double thr = presplit_heap(recs, sample, sbox, sowner, budget / stride, min_gain);
+    const double thr = presplit_heap(recs, sample, sbox, sowner, plan.budget / stride, plan.min_gain);
     const unsigned hw = std::thread::hardware_concurrency();
     const size_t tasks = std::min<size_t>(std::max<unsigned>(hw, 1u), 64);
     std::vector<SplitOut> outs(tasks);
@@ -273,7 +280,7 @@ static bool presplit(const std::vector<TriRec>& recs, std::vector<PrimBounds>& r
     for (const SplitOut& o : outs) extra += o.box.size();
     refs_box.reserve(n + extra); refs_tri.reserve(n + extra);
     for (const SplitOut& o : outs) { refs_box.insert(refs_box.end(), o.box.begin(), o.box.end()); refs_tri.insert(refs_tri.end(), o.tri.begin(), o.tri.end()); }
-    return hairy;
+    return plan.hairy;
 }
 
 // Appends a BLAS over the triangles of `node_ids` (TriMesh nodes sharing one isometry).
@@ -333,17 +340,14 @@ int append_blas(const NraysSceneDesc* d, const Switches& sw, const std::vector<u
             TriRec r; TriUv uv; PrimBounds b;
             std::memset(&uv, 0, sizeof uv);
             float* vs[3] = {r.v0, r.v1, r.v2};
-            for (int a = 0; a < 3; ++a) { b.mn[a] = std::numeric_limits<float>::infinity(); b.mx[a] = -std::numeric_limits<float>::infinity(); }
+            empty_box(b.mn, b.mx);
             for (int k = 0; k < 3; ++k) {
-                uint32_t vi = m.indices[3 * t + k];
-                if (vi >= m.num_vertices) { err = "triangle index out of range"; return NRAYS_ERR_BAD_ARG; }
+                const uint32_t vi = m.indices[3 * t + k];
+                if (vi >= m.num_vertices) return refuse_mesh(kMeshIndexRange, err);
                 for (int a = 0; a < 3; ++a) {
                     double x = m.vertices[3 * (size_t)vi + a];
                     float f = (float)x;
-                    if (!((double)f == x)) { // also rejects NaN
-                        err = "mesh vertex coordinate is not exactly representable in f32 (see DESIGN.md: f32-exact mesh storage)";
-                        return NRAYS_ERR_UNSUPPORTED;
-                    }
+                    if (!((double)f == x)) return refuse_mesh(kMeshVertexInexact, err); // also rejects NaN
                     vs[k][a] = f;
                     b.mn[a] = std::min(b.mn[a], f); b.mx[a] = std::max(b.mx[a], f);
                 }
@@ -351,7 +355,7 @@ int append_blas(const NraysSceneDesc* d, const Switches& sw, const std::vector<u
                     for (int a = 0; a < 2; ++a) {
                         double x = m.uvs[2 * (size_t)vi + a];
                         float f = (float)x;
-                        if (!((double)f == x)) { err = "mesh uv is not exactly representable in f32"; return NRAYS_ERR_UNSUPPORTED; }
+                        if (!((double)f == x)) return refuse_mesh(kMeshUvInexact, err);
                         uv.uv[2 * k + a] = f;
                     }
                 }
@@ -360,7 +364,7 @@ int append_blas(const NraysSceneDesc* d, const Switches& sw, const std::vector<u
             recs.push_back(r); uvs.push_back(uv); pb.push_back(b);
         }
     }
-    for (int a = 0; a < 3; ++a) { blas.mn[a] = std::numeric_limits<float>::infinity(); blas.mx[a] = -std::numeric_limits<float>::infinity(); }
+    empty_box(blas.mn, blas.mx); // the local bounds: the union of the triangles' boxes, which this pass makes anyway (no second scan of the mesh)
     for (const PrimBounds& b : pb) for (int a = 0; a < 3; ++a) { blas.mn[a] = std::min(blas.mn[a], b.mn[a]); blas.mx[a] = std::max(blas.mx[a], b.mx[a]); }
     std::vector<uint32_t> ref_tri(recs.size());
     for (size_t k = 0; k < ref_tri.size(); ++k) ref_tri[k] = (uint32_t)k;
@@ -445,278 +449,308 @@ int build_blas_probe(const NraysMesh* mesh, const Switches& sw, bool device, boo
     return NRAYS_OK;
 }
 
-int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out, std::string& err) {
-    if (!d) { err = "null scene descriptor"; return NRAYS_ERR_BAD_ARG; }
-    if ((d->num_lights && !d->lights) || (d->num_materials && !d->materials) || (d->num_textures && !d->textures) ||
-        (d->num_meshes && !d->meshes) || (d->num_nodes && !d->nodes)) { err = "null array with non-zero count"; return NRAYS_ERR_BAD_ARG; }
-    for (int a = 0; a < 3; ++a) out.background[a] = d->background[a];
+// ---- build_host_scene: the phases, in the order the driver at the end of the file runs them ---------------------------------
+namespace {
 
-    for (uint32_t i = 0; i < d->num_lights; ++i) {
-        const NraysLight& l = d->lights[i];
-        LightRec r;
-        for (int a = 0; a < 3; ++a) { r.pos[a] = l.pos[a]; r.color[a] = l.color[a]; }
-        r.radius = l.radius; r.racsample = l.racsample;
-        if (l.radius != 0.0) out.any_area_light = true;
-        out.lights.push_back(r);
-    }
-    for (uint32_t i = 0; i < d->num_textures; ++i) {
-        const NraysTexture& t = d->textures[i];
-        if (t.width < 1 || t.height < 1 || !t.texels || t.format > NRAYS_TEXEL_RGBA32F) { err = "bad texture"; return NRAYS_ERR_BAD_ARG; }
-        HostTexture h;
-        h.rec.width = t.width; h.rec.height = t.height; h.rec.format = t.format; h.rec.interp = t.interp;
-        h.rec.overflow = t.overflow; h.rec.pad = 0; h.rec.texels = nullptr;
-        size_t nbytes = (size_t)t.width * t.height * (t.format == NRAYS_TEXEL_RGBA8 ? 4 : 16);
-        h.bytes.assign((const uint8_t*)t.texels, (const uint8_t*)t.texels + nbytes);
-        out.textures.push_back(std::move(h));
-    }
-    for (uint32_t i = 0; i < d->num_materials; ++i) {
-        const NraysMaterial& m = d->materials[i];
-        if (m.kind > NRAYS_MAT_UV) { err = "bad material kind"; return NRAYS_ERR_BAD_ARG; }
-        if (m.texture_id >= (int32_t)d->num_textures || m.alpha_texture_id >= (int32_t)d->num_textures) { err = "bad texture id"; return NRAYS_ERR_BAD_ARG; }
-        MaterialRec r; std::memset(&r, 0, sizeof r);
-        r.kind = m.kind;
-        for (int a = 0; a < 3; ++a) { r.ka[a] = m.ambiant[a]; r.kd[a] = m.diffuse[a]; r.ks[a] = m.specular[a]; }
-        r.shininess = m.shininess;
-        r.tex = m.texture_id < 0 ? -1 : m.texture_id;
-        r.alpha_tex = m.alpha_texture_id < 0 ? -1 : m.alpha_texture_id;
-        out.materials.push_back(r);
-    }
+struct NodeInfo { double R[9]; bool identity; bool opaque; bool has_uv; bool no_uv_values; };
 
-    // ---- per-node records, opacity classification, transform groups ----------------------
-    struct NodeInfo { double R[9]; bool identity; bool opaque; bool has_uv; bool no_uv_values; };
-    std::vector<NodeInfo> info(d->num_nodes);
-    std::vector<uint32_t> pending_aabb;                       // TriMesh nodes whose local AABB comes from their device-built BLAS (below)
+struct Flatten { // what crosses the phases, then the phases in the order run() calls them
+    const NraysSceneDesc* d; const Switches& sw; HostScene& out; std::string& err;
+    std::vector<NodeInfo> info;                               // per node
+    std::vector<Instance> cinst, sinst, planes_c, planes_s;   // leaves of the closest-hit / shadow TLAS; the planes stay outside them
+    std::vector<PrimBounds> cbox, sbox;                       // parallel to cinst / sinst
+    std::vector<uint32_t> pending_aabb;                       // TriMesh nodes whose local AABB comes from their device-built BLAS
     std::map<uint32_t, std::array<float, 6>> single_bounds;   // node -> local bounds of a device-built BLAS that holds this node alone
-    float att_min = std::numeric_limits<float>::infinity();
-    for (uint32_t i = 0; i < d->num_nodes; ++i) {
-        const NraysNode& n = d->nodes[i];
-        if (n.shape_kind > NRAYS_SHAPE_TRIMESH) { err = "bad shape kind"; return NRAYS_ERR_BAD_ARG; }
-        if (n.material_id >= d->num_materials) { err = "bad material id"; return NRAYS_ERR_BAD_ARG; }
-        if (n.shape_kind == NRAYS_SHAPE_TRIMESH && (n.mesh_id < 0 || (uint32_t)n.mesh_id >= d->num_meshes)) { err = "bad mesh id"; return NRAYS_ERR_BAD_ARG; }
-        rotation_from_axis_angle(n.axis_angle, info[i].R, info[i].identity);
-        const NraysMaterial& m = d->materials[n.material_id];
-        bool has_uv = n.shape_kind == NRAYS_SHAPE_TRIMESH ? d->meshes[n.mesh_id].uvs != nullptr : shape_has_uv(n.shape_kind);
-        info[i].has_uv = has_uv;
-        info[i].no_uv_values = m.kind == NRAYS_MAT_NORMAL || (m.kind == NRAYS_MAT_PHONG && m.texture_id < 0 && m.alpha_texture_id < 0);
-        // ambiant().w is 1 for NormalMaterial, 1/0 for UVMaterial with/without uvs, and the alpha
-        // map's w (or 1) for PhongMaterial; a node blocks shadow rays iff w * node.alpha >= 1 (scene.rs:322-331).
-        bool w_is_one = m.kind == NRAYS_MAT_NORMAL || (m.kind == NRAYS_MAT_UV && has_uv) ||
-                        (m.kind == NRAYS_MAT_PHONG && (m.alpha_texture_id < 0 || !has_uv));
-        info[i].opaque = w_is_one && n.alpha >= 1.0f;
-        if (!(w_is_one && n.alpha == 1.0f)) out.any_transparent = true;
-        if (!(w_is_one && n.alpha == 1.0f) && n.refl_mix != 0.0f) out.any_double_branch = true;
-        if (n.refl_mix != 0.0f) { out.any_reflective = true; att_min = std::min(att_min, n.refl_atenuation); }
-        NodeRec r;
-        r.refl_mix = n.refl_mix; r.refl_atenuation = n.refl_atenuation; r.alpha = n.alpha; r.material_id = n.material_id;
-        r.refr_coeff = n.refr_coeff; r.pad[0] = has_uv ? 1u : 0u; r.pad[1] = 0;
-        out.node_recs.push_back(r);
-        {
-            ShadeRec sr; std::memset(&sr, 0, sizeof sr);
-            sr.refl_mix = n.refl_mix; sr.refl_atenuation = n.refl_atenuation; sr.alpha = n.alpha; sr.refr_coeff = n.refr_coeff;
-            sr.flags = (has_uv ? 1u : 0u) | (m.kind << 8);
-            for (int a = 0; a < 3; ++a) { sr.ka[a] = m.ambiant[a]; sr.kd[a] = m.diffuse[a]; sr.ks[a] = m.specular[a]; }
-            sr.shininess = m.shininess;
-            auto fill = [&](ShadeTex& t, int32_t id) {
-                if (id < 0) return;
-                const NraysTexture& x = d->textures[id];
-                t.width = x.width; t.height = x.height; t.mode = x.format | (x.interp << 8) | (x.overflow << 16);
-            };
-            fill(sr.tex, m.texture_id); fill(sr.alpha_tex, m.alpha_texture_id);
-            out.shade.push_back(sr);
+    int fail(const char* what, int rc = NRAYS_ERR_BAD_ARG) { err = what; return rc; }
+    static bool no_xform(const NodeInfo& i, const NraysNode& n) { return i.identity && n.translation[0] == 0.0 && n.translation[1] == 0.0 && n.translation[2] == 0.0; }
+
+    int copy_tables() { // lights, textures, materials
+        for (uint32_t i = 0; i < d->num_lights; ++i) {
+            const NraysLight& l = d->lights[i];
+            LightRec r;
+            for (int a = 0; a < 3; ++a) { r.pos[a] = l.pos[a]; r.color[a] = l.color[a]; }
+            r.radius = l.radius; r.racsample = l.racsample;
+            if (l.radius != 0.0) out.any_area_light = true;
+            out.lights.push_back(r);
+        }
+        for (uint32_t i = 0; i < d->num_textures; ++i) {
+            const NraysTexture& t = d->textures[i];
+            if (t.width < 1 || t.height < 1 || !t.texels || t.format > NRAYS_TEXEL_RGBA32F) return fail("bad texture");
+            HostTexture h;
+            h.rec.width = t.width; h.rec.height = t.height; h.rec.format = t.format; h.rec.interp = t.interp;
+            h.rec.overflow = t.overflow; h.rec.pad = 0; h.rec.texels = nullptr;
+            size_t nbytes = (size_t)t.width * t.height * (t.format == NRAYS_TEXEL_RGBA8 ? 4 : 16);
+            h.bytes.assign((const uint8_t*)t.texels, (const uint8_t*)t.texels + nbytes);
+            out.textures.push_back(std::move(h));
+        }
+        for (uint32_t i = 0; i < d->num_materials; ++i) {
+            const NraysMaterial& m = d->materials[i];
+            if (m.kind > NRAYS_MAT_UV) return fail("bad material kind");
+            if (m.texture_id >= (int32_t)d->num_textures || m.alpha_texture_id >= (int32_t)d->num_textures) return fail("bad texture id");
+            MaterialRec r; std::memset(&r, 0, sizeof r);
+            r.kind = m.kind;
+            for (int a = 0; a < 3; ++a) { r.ka[a] = m.ambiant[a]; r.kd[a] = m.diffuse[a]; r.ks[a] = m.specular[a]; }
+            r.shininess = m.shininess;
+            r.tex = m.texture_id < 0 ? -1 : m.texture_id;
+            r.alpha_tex = m.alpha_texture_id < 0 ? -1 : m.alpha_texture_id;
+            out.materials.push_back(r);
+        }
+        return NRAYS_OK;
+    }
+    ShadeRec shade_record(const NraysNode& n, const NraysMaterial& m, bool has_uv) {
+        ShadeRec sr; std::memset(&sr, 0, sizeof sr);
+        sr.refl_mix = n.refl_mix; sr.refl_atenuation = n.refl_atenuation; sr.alpha = n.alpha; sr.refr_coeff = n.refr_coeff;
+        sr.flags = (has_uv ? 1u : 0u) | (m.kind << 8);
+        for (int a = 0; a < 3; ++a) { sr.ka[a] = m.ambiant[a]; sr.kd[a] = m.diffuse[a]; sr.ks[a] = m.specular[a]; }
+        sr.shininess = m.shininess;
+        auto fill = [&](ShadeTex& t, int32_t id) {
+            if (id < 0) return;
+            const NraysTexture& x = d->textures[id];
+            t.width = x.width; t.height = x.height; t.mode = x.format | (x.interp << 8) | (x.overflow << 16);
+        };
+        fill(sr.tex, m.texture_id); fill(sr.alpha_tex, m.alpha_texture_id);
+        return sr;
+    }
+    // NodeRec, ShadeRec, the opacity class and the world AABB of every node (or "pending"), the scene's generation facts.
+    int node_records() {
+        info.resize(d->num_nodes);
+        float att_min = std::numeric_limits<float>::infinity();
+        for (uint32_t i = 0; i < d->num_nodes; ++i) {
+            const NraysNode& n = d->nodes[i];
+            NodeInfo& me = info[i];
+            if (n.shape_kind > NRAYS_SHAPE_TRIMESH) return fail("bad shape kind");
+            if (n.material_id >= d->num_materials) return fail("bad material id");
+            if (n.shape_kind == NRAYS_SHAPE_TRIMESH && (n.mesh_id < 0 || (uint32_t)n.mesh_id >= d->num_meshes)) return fail("bad mesh id");
+            rotation_from_axis_angle(n.axis_angle, me.R, me.identity);
+            const NraysMaterial& m = d->materials[n.material_id];
+            const bool has_uv = n.shape_kind == NRAYS_SHAPE_TRIMESH ? d->meshes[n.mesh_id].uvs != nullptr : shape_has_uv(n.shape_kind);
+            me.has_uv = has_uv;
+            me.no_uv_values = m.kind == NRAYS_MAT_NORMAL || (m.kind == NRAYS_MAT_PHONG && m.texture_id < 0 && m.alpha_texture_id < 0);
+            // ambiant().w is 1 for NormalMaterial, 1/0 for UVMaterial with/without uvs, and the alpha
+            // map's w (or 1) for PhongMaterial; a node blocks shadow rays iff w * node.alpha >= 1 (scene.rs:322-331).
+            const bool w_is_one = m.kind == NRAYS_MAT_NORMAL || (m.kind == NRAYS_MAT_UV && has_uv) ||
+                                  (m.kind == NRAYS_MAT_PHONG && (m.alpha_texture_id < 0 || !has_uv));
+            me.opaque = w_is_one && n.alpha >= 1.0f;
+            if (!(w_is_one && n.alpha == 1.0f)) out.any_transparent = true;
+            if (!(w_is_one && n.alpha == 1.0f) && n.refl_mix != 0.0f) out.any_double_branch = true;
+            if (n.refl_mix != 0.0f) { out.any_reflective = true; att_min = std::min(att_min, n.refl_atenuation); }
+            NodeRec r;
+            r.refl_mix = n.refl_mix; r.refl_atenuation = n.refl_atenuation; r.alpha = n.alpha; r.material_id = n.material_id;
+            r.refr_coeff = n.refr_coeff; r.pad[0] = has_uv ? 1u : 0u; r.pad[1] = 0;
+            out.node_recs.push_back(r);
+            out.shade.push_back(shade_record(n, m, has_uv));
             out.shade_tex.push_back(m.texture_id < 0 ? -1 : m.texture_id);
             out.shade_alpha_tex.push_back(m.alpha_texture_id < 0 ? -1 : m.alpha_texture_id);
-        }
-        {
-            float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
             // A mesh large enough for the device builder gets its local AABB from that build (k_tri_records reduces the same f32 min / max over the faces' vertices and checks
-            // the indices): the host scan of the hairball stand-in's 8.6 M indices — random vertex reads — took 8 of its 100 ms.  Filled in below, once its BLAS exists.
+            // the indices): the host scan of the hairball stand-in's 8.6 M indices — random vertex reads — took 8 of its 100 ms.  Filled in by pending_aabbs(), once its BLAS exists.
             if (n.shape_kind == NRAYS_SHAPE_TRIMESH && d->meshes[n.mesh_id].num_triangles >= device_build_min(sw)) { // (NRAYS_GPU_BUILD=0: the minimum is SIZE_MAX)
                 pending_aabb.push_back(i);
                 out.node_aabbs.insert(out.node_aabbs.end(), 6, 0.0);
                 continue;
             }
-            if (n.shape_kind == NRAYS_SHAPE_TRIMESH) { // local AABB = union of the faces' vertices (TriMesh BVT root)
-                const NraysMesh& m = d->meshes[n.mesh_id];
-                for (int a = 0; a < 3; ++a) { mn[a] = std::numeric_limits<float>::infinity(); mx[a] = -std::numeric_limits<float>::infinity(); }
-                for (uint32_t t = 0; t < m.num_triangles * 3u; ++t) {
-                    uint32_t vi = m.indices[t];
-                    if (vi >= m.num_vertices) { err = "triangle index out of range"; return NRAYS_ERR_BAD_ARG; }
-                    for (int a = 0; a < 3; ++a) { float f = (float)m.vertices[3 * (size_t)vi + a]; mn[a] = std::min(mn[a], f); mx[a] = std::max(mx[a], f); }
-                }
+            float mn[3] = {0, 0, 0}, mx[3] = {0, 0, 0};
+            if (n.shape_kind == NRAYS_SHAPE_TRIMESH) {
+                empty_box(mn, mx);
+                const int rc = extend_by_mesh(d->meshes[n.mesh_id], mn, mx, err);
+                if (rc != NRAYS_OK) return rc;
+            }
+            double bb[6];
+            node_world_aabb(n, me.R, mn, mx, bb);
+            out.node_aabbs.insert(out.node_aabbs.end(), bb, bb + 6);
+        }
+        if (out.any_reflective) {
+            uint32_t k = 0; float e = 1.0f;
+            if (!(att_min > 0.0f)) k = kMaxGenerations;
+            else while (e > 0.1f && k < (uint32_t)kMaxGenerations) { ++k; e = e - att_min; }
+            out.reflection_generations = k;
+        }
+        return NRAYS_OK;
+    }
+    void node_surfaces() { // (first / count / device_built: mesh_group_blas)
+        out.surface.assign(d->num_nodes, NodeSurface());
+        for (uint32_t i = 0; i < d->num_nodes; ++i) {
+            const NraysNode& n = d->nodes[i];
+            NodeSurface& s = out.surface[i];
+            s.mesh = n.shape_kind == NRAYS_SHAPE_TRIMESH; s.has_uv = s.mesh && info[i].has_uv;
+            for (int k = 0; k < 9; ++k) s.rot[k] = info[i].R[k];
+            for (int k = 0; k < 3; ++k) s.trans[k] = n.translation[k];
+            s.flags = (info[i].identity ? kInstIdentityRot : 0u) | (no_xform(info[i], n) ? kInstNoXform : 0u);
+        }
+    }
+    Instance base_instance(uint32_t ni) {
+        const NraysNode& n = d->nodes[ni];
+        const NodeInfo& me = info[ni];
+        Instance in; std::memset(&in, 0, sizeof in);
+        for (int k = 0; k < 9; ++k) in.rot[k] = me.R[k];
+        for (int k = 0; k < 3; ++k) { in.trans[k] = n.translation[k]; in.params[k] = n.params[k]; }
+        in.kind = n.shape_kind;
+        in.flags = (n.solid ? kInstSolid : 0u) | (me.identity ? kInstIdentityRot : 0u) | (me.has_uv ? kInstHasUv : 0u) | (me.no_uv_values ? kInstNoUvValues : 0u) |
+                   (no_xform(me, n) ? kInstNoXform : 0u);
+        in.node_id = (int32_t)ni; in.blas_root = kEmptyChild;
+        return in;
+    }
+    void analytic_instances() {
+        for (uint32_t i = 0; i < d->num_nodes; ++i) {
+            const NraysNode& n = d->nodes[i];
+            if (n.shape_kind == NRAYS_SHAPE_TRIMESH) continue;
+            Instance in = base_instance(i);
+            Instance si = in;
+            if (info[i].opaque) si.flags |= kInstAnyHit;
+            if (n.shape_kind == NRAYS_SHAPE_PLANE) { planes_c.push_back(in); planes_s.push_back(si); continue; }
+            double c[3] = {0, 0, 0}, h[3];
+            double Rid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+            const double* R = info[i].R;
+            switch (n.shape_kind) {
+            case NRAYS_SHAPE_BALL: h[0] = h[1] = h[2] = n.params[0]; R = Rid; break; // rotation ignored (SURVEY B-4)
+            case NRAYS_SHAPE_CUBOID: h[0] = n.params[0]; h[1] = n.params[1]; h[2] = n.params[2]; break;
+            case NRAYS_SHAPE_CAPSULE: h[0] = h[2] = n.params[1]; h[1] = n.params[0] + n.params[1]; break;
+            default: h[0] = h[2] = n.params[1]; h[1] = n.params[0]; break; // cylinder, cone
+            }
+            for (int a = 0; a < 3; ++a) h[a] = std::fabs(h[a]);
+            PrimBounds b = world_box(R, n.translation, c, h);
+            cinst.push_back(in); cbox.push_back(b);
+            sinst.push_back(si); sbox.push_back(b);
+        }
+    }
+    // One BLAS over the nodes `sub` of the group whose first node is n0, and its leaf in the closest-hit TLAS, the shadow TLAS or both.
+    enum BlasUse : unsigned { kUseClosest = 1u, kUseShadow = 2u, kShadowAnyHit = 4u };
+    int mesh_group_blas(uint32_t n0, const std::vector<uint32_t>& sub, unsigned use) {
+        const size_t dev0 = out.dev_tris, host0 = out.tris.size();
+        Blas blas;
+        const int rc = append_blas(d, sw, sub, out, blas, err);
+        if (rc != NRAYS_OK) return rc;
+        if (use & kUseClosest) // the records of this BLAS: where nrays_surface_texels* finds the triangles of its nodes (host-built ranges move behind the device-built ones in link_scene)
+            for (uint32_t ni : sub) { NodeSurface& s = out.surface[ni]; s.device_built = blas.device; s.first = (uint32_t)(blas.device ? dev0 : host0); s.count = (uint32_t)(blas.device ? out.dev_tris - dev0 : out.tris.size() - host0); }
+        if (sub.size() == 1 && blas.device) single_bounds[sub[0]] = std::array<float, 6>{blas.mn[0], blas.mn[1], blas.mn[2], blas.mx[0], blas.mx[1], blas.mx[2]};
+        Instance in = base_instance(n0);
+        in.flags &= ~(uint32_t)kInstSolid; // TriMesh ignores `solid` (SURVEY B-8)
+        in.node_id = sub.size() == 1 ? (int32_t)sub[0] : -1;
+        in.blas_root = blas.root;
+        if (blas.device) in.flags |= kInstDeviceTmp;
+        if (blas.hairy) { in.flags |= kInstIncoherent; out.any_incoherent = true; }
+        double c[3], h[3];
+        for (int a = 0; a < 3; ++a) { c[a] = 0.5 * ((double)blas.mn[a] + (double)blas.mx[a]); h[a] = 0.5 * ((double)blas.mx[a] - (double)blas.mn[a]); }
+        PrimBounds b = world_box(info[n0].R, d->nodes[n0].translation, c, h);
+        if (use & kUseClosest) { cinst.push_back(in); cbox.push_back(b); }
+        if (use & kUseShadow) { Instance si = in; if (use & kShadowAnyHit) si.flags |= kInstAnyHit; sinst.push_back(si); sbox.push_back(b); }
+        return NRAYS_OK;
+    }
+    // TriMesh nodes with triangles, grouped by identical isometry.  A group takes one of three shapes:
+    //   all opaque              one BLAS in both TLASes; its first hit blocks a shadow ray
+    //   some node transparent   one BLAS of all nodes for closest hits; for shadow rays one any-hit BLAS of the opaque nodes (if any) ...
+    //                           ... and one BLAS per transparent node, whose hits are filtered by that node's alpha
+    int mesh_groups() {
+        std::map<std::vector<uint64_t>, std::vector<uint32_t>> groups;
+        std::vector<std::vector<uint64_t>> group_order;
+        for (uint32_t i = 0; i < d->num_nodes; ++i) {
+            const NraysNode& n = d->nodes[i];
+            if (n.shape_kind != NRAYS_SHAPE_TRIMESH || d->meshes[n.mesh_id].num_triangles == 0) continue;
+            std::vector<uint64_t> key(6);
+            std::memcpy(&key[0], n.translation, 24); std::memcpy(&key[3], n.axis_angle, 24);
+            if (!groups.count(key)) group_order.push_back(key);
+            groups[key].push_back(i);
+        }
+        for (const auto& key : group_order) {
+            const std::vector<uint32_t>& ids = groups[key];
+            std::vector<uint32_t> opaque, transp;
+            for (uint32_t i : ids) (info[i].opaque ? opaque : transp).push_back(i);
+            int rc = mesh_group_blas(ids[0], ids, transp.empty() ? kUseClosest | kUseShadow | kShadowAnyHit : kUseClosest);
+            if (rc == NRAYS_OK && !transp.empty() && !opaque.empty()) rc = mesh_group_blas(ids[0], opaque, kUseShadow | kShadowAnyHit);
+            for (size_t k = 0; rc == NRAYS_OK && k < transp.size(); ++k) rc = mesh_group_blas(ids[0], std::vector<uint32_t>{transp[k]}, kUseShadow);
+            if (rc != NRAYS_OK) return rc;
+        }
+        return NRAYS_OK;
+    }
+    // The local AABBs node_records left open: from the node's own device-built BLAS, else (merged groups, host fall-back) by the scan.
+    int pending_aabbs() {
+        for (uint32_t i : pending_aabb) {
+            const NraysNode& n = d->nodes[i];
+            float mn[3], mx[3];
+            const auto it = single_bounds.find(i);
+            if (it != single_bounds.end()) { for (int a = 0; a < 3; ++a) { mn[a] = it->second[a]; mx[a] = it->second[3 + a]; } }
+            else {
+                empty_box(mn, mx);
+                const int rc = extend_by_mesh(d->meshes[n.mesh_id], mn, mx, err);
+                if (rc != NRAYS_OK) return rc;
             }
             double bb[6];
             node_world_aabb(n, info[i].R, mn, mx, bb);
-            out.node_aabbs.insert(out.node_aabbs.end(), bb, bb + 6);
+            for (int a = 0; a < 6; ++a) out.node_aabbs[6 * (size_t)i + a] = bb[a];
         }
+        return NRAYS_OK;
     }
-    if (out.any_reflective) {
-        uint32_t k = 0; float e = 1.0f;
-        if (!(att_min > 0.0f)) k = kMaxGenerations;
-        else while (e > 0.1f && k < (uint32_t)kMaxGenerations) { ++k; e = e - att_min; }
-        out.reflection_generations = k;
-    }
-
-    out.surface.assign(d->num_nodes, NodeSurface());
-    for (uint32_t i = 0; i < d->num_nodes; ++i) {
-        const NraysNode& n = d->nodes[i];
-        NodeSurface& s = out.surface[i];
-        s.mesh = n.shape_kind == NRAYS_SHAPE_TRIMESH; s.has_uv = s.mesh && info[i].has_uv;
-        for (int k = 0; k < 9; ++k) s.rot[k] = info[i].R[k];
-        for (int k = 0; k < 3; ++k) s.trans[k] = n.translation[k];
-        s.flags = info[i].identity ? kInstIdentityRot : 0u;
-        if (info[i].identity && n.translation[0] == 0.0 && n.translation[1] == 0.0 && n.translation[2] == 0.0) s.flags |= kInstNoXform;
-    }
-
-    std::vector<Instance> cinst, sinst, planes_c, planes_s;
-    std::vector<PrimBounds> cbox, sbox;
-
-    auto base_instance = [&](uint32_t ni) {
-        const NraysNode& n = d->nodes[ni];
-        Instance in; std::memset(&in, 0, sizeof in);
-        for (int k = 0; k < 9; ++k) in.rot[k] = info[ni].R[k];
-        for (int k = 0; k < 3; ++k) { in.trans[k] = n.translation[k]; in.params[k] = n.params[k]; }
-        in.kind = n.shape_kind;
-        in.flags = (n.solid ? kInstSolid : 0u) | (info[ni].identity ? kInstIdentityRot : 0u) | (info[ni].has_uv ? kInstHasUv : 0u) | (info[ni].no_uv_values ? kInstNoUvValues : 0u);
-        if (info[ni].identity && n.translation[0] == 0.0 && n.translation[1] == 0.0 && n.translation[2] == 0.0) in.flags |= kInstNoXform;
-        in.node_id = (int32_t)ni; in.blas_root = kEmptyChild;
-        return in;
-    };
-
-    // analytic shapes
-    for (uint32_t i = 0; i < d->num_nodes; ++i) {
-        const NraysNode& n = d->nodes[i];
-        if (n.shape_kind == NRAYS_SHAPE_TRIMESH) continue;
-        Instance in = base_instance(i);
-        Instance si = in;
-        if (info[i].opaque) si.flags |= kInstAnyHit;
-        if (n.shape_kind == NRAYS_SHAPE_PLANE) { planes_c.push_back(in); planes_s.push_back(si); continue; }
-        double c[3] = {0, 0, 0}, h[3];
-        double Rid[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        const double* R = info[i].R;
-        switch (n.shape_kind) {
-        case NRAYS_SHAPE_BALL: h[0] = h[1] = h[2] = n.params[0]; R = Rid; break; // rotation ignored (SURVEY B-4)
-        case NRAYS_SHAPE_CUBOID: h[0] = n.params[0]; h[1] = n.params[1]; h[2] = n.params[2]; break;
-        case NRAYS_SHAPE_CAPSULE: h[0] = h[2] = n.params[1]; h[1] = n.params[0] + n.params[1]; break;
-        default: h[0] = h[2] = n.params[1]; h[1] = n.params[0]; break; // cylinder, cone
-        }
-        for (int a = 0; a < 3; ++a) h[a] = std::fabs(h[a]);
-        PrimBounds b = world_box(R, n.translation, c, h);
-        cinst.push_back(in); cbox.push_back(b);
-        sinst.push_back(si); sbox.push_back(b);
-    }
-
-    // TriMesh nodes grouped by identical isometry
-    std::map<std::vector<uint64_t>, std::vector<uint32_t>> groups;
-    std::vector<std::vector<uint64_t>> group_order;
-    for (uint32_t i = 0; i < d->num_nodes; ++i) {
-        const NraysNode& n = d->nodes[i];
-        if (n.shape_kind != NRAYS_SHAPE_TRIMESH) continue;
-        if (d->meshes[n.mesh_id].num_triangles == 0) continue;
-        std::vector<uint64_t> key(6);
-        std::memcpy(&key[0], n.translation, 24); std::memcpy(&key[3], n.axis_angle, 24);
-        if (!groups.count(key)) group_order.push_back(key);
-        groups[key].push_back(i);
-    }
-    for (const auto& key : group_order) {
-        const std::vector<uint32_t>& ids = groups[key];
-        uint32_t n0 = ids[0];
-        auto add = [&](const std::vector<uint32_t>& sub, bool closest, bool shadow, bool anyhit, const Blas* reuse, Blas& blas) -> int {
-            const size_t dev0 = out.dev_tris, host0 = out.tris.size();
-            if (!reuse) { int rc = append_blas(d, sw, sub, out, blas, err); if (rc != NRAYS_OK) return rc; } else blas = *reuse;
-            if (closest && !reuse) // the records of this BLAS: where nrays_surface_texels* finds the triangles of its nodes (host-built ranges move behind the device-built ones below)
-                for (uint32_t ni : sub) { NodeSurface& s = out.surface[ni]; s.device_built = blas.device; s.first = (uint32_t)(blas.device ? dev0 : host0); s.count = (uint32_t)(blas.device ? out.dev_tris - dev0 : out.tris.size() - host0); }
-            if (!reuse && sub.size() == 1 && blas.device) single_bounds[sub[0]] = std::array<float, 6>{blas.mn[0], blas.mn[1], blas.mn[2], blas.mx[0], blas.mx[1], blas.mx[2]};
-            Instance in = base_instance(n0);
-            in.flags &= ~(uint32_t)kInstSolid; // TriMesh ignores `solid` (SURVEY B-8)
-            in.node_id = sub.size() == 1 ? (int32_t)sub[0] : -1;
-            in.blas_root = blas.root;
-            if (blas.device) in.flags |= kInstDeviceTmp;
-            if (blas.hairy) { in.flags |= kInstIncoherent; out.any_incoherent = true; }
-            double c[3], h[3];
-            for (int a = 0; a < 3; ++a) { c[a] = 0.5 * ((double)blas.mn[a] + (double)blas.mx[a]); h[a] = 0.5 * ((double)blas.mx[a] - (double)blas.mn[a]); }
-            PrimBounds b = world_box(info[n0].R, d->nodes[n0].translation, c, h);
-            if (closest) { cinst.push_back(in); cbox.push_back(b); }
-            if (shadow) { Instance si = in; if (anyhit) si.flags |= kInstAnyHit; sinst.push_back(si); sbox.push_back(b); }
-            return NRAYS_OK;
-        };
-        std::vector<uint32_t> opaque, transp;
-        for (uint32_t i : ids) (info[i].opaque ? opaque : transp).push_back(i);
-        Blas all; int rc;
-        if (transp.empty()) {
-            rc = add(ids, true, true, true, nullptr, all); if (rc != NRAYS_OK) return rc;
-        } else {
-            rc = add(ids, true, false, false, nullptr, all); if (rc != NRAYS_OK) return rc;
-            Blas tmp;
-            if (!opaque.empty()) { rc = add(opaque, false, true, true, nullptr, tmp); if (rc != NRAYS_OK) return rc; }
-            for (uint32_t i : transp) { rc = add(std::vector<uint32_t>{i}, false, true, false, nullptr, tmp); if (rc != NRAYS_OK) return rc; }
-        }
-    }
-
-    for (uint32_t i : pending_aabb) { // the local AABBs left open above: from the node's own device-built BLAS, else (merged groups, host fall-back) by the scan
-        const NraysNode& n = d->nodes[i];
-        const NraysMesh& m = d->meshes[n.mesh_id];
-        float mn[3], mx[3];
-        const auto it = single_bounds.find(i);
-        if (it != single_bounds.end()) { for (int a = 0; a < 3; ++a) { mn[a] = it->second[a]; mx[a] = it->second[3 + a]; } }
-        else {
-            for (int a = 0; a < 3; ++a) { mn[a] = std::numeric_limits<float>::infinity(); mx[a] = -std::numeric_limits<float>::infinity(); }
-            for (uint32_t t = 0; t < m.num_triangles * 3u; ++t) {
-                const uint32_t vi = m.indices[t];
-                if (vi >= m.num_vertices) { err = "triangle index out of range"; return NRAYS_ERR_BAD_ARG; }
-                for (int a = 0; a < 3; ++a) { const float f = (float)m.vertices[3 * (size_t)vi + a]; mn[a] = std::min(mn[a], f); mx[a] = std::max(mx[a], f); }
-            }
-        }
-        double bb[6];
-        node_world_aabb(n, info[i].R, mn, mx, bb);
-        for (int a = 0; a < 6; ++a) out.node_aabbs[6 * (size_t)i + a] = bb[a];
-    }
-
-    {   // kernel permutation: 1 = analytic shapes, 2 = meshes, 4 = some node may be non-opaque to shadow rays
-        int f = 0;
+    void feature_bits() { // kernel permutation: 1 = analytic shapes, 2 = meshes, 4 = some node may be non-opaque to shadow rays
+        int bits = 0;
         for (uint32_t i = 0; i < d->num_nodes; ++i) {
             const NraysNode& n = d->nodes[i];
-            if (n.shape_kind == NRAYS_SHAPE_TRIMESH) { if (d->meshes[n.mesh_id].num_triangles) f |= 2; } else f |= 1;
-            if (!info[i].opaque) f |= 4;
+            if (n.shape_kind == NRAYS_SHAPE_TRIMESH) { if (d->meshes[n.mesh_id].num_triangles) bits |= 2; } else bits |= 1;
+            if (!info[i].opaque) bits |= 4;
         }
-        if (f == 4 || f == 0) f |= 1; // empty scenes take the lightest kernel
-        out.any_mesh = (f & 2) != 0;
-        if (out.any_double_branch) f = 15; // reflection + refraction at one hit: full kernel with the HBM queue
-        if (!(d->num_lights == 1 && d->lights[0].racsample == 1)) f |= 16; // more than one light sample per hit
-        out.features = f;
+        if (bits == 4 || bits == 0) bits |= 1; // empty scenes take the lightest kernel
+        out.any_mesh = (bits & 2) != 0;
+        if (out.any_double_branch) bits = 15; // reflection + refraction at one hit: full kernel with the HBM queue
+        if (!(d->num_lights == 1 && d->lights[0].racsample == 1)) bits |= 16; // more than one light sample per hit
+        out.features = bits;
     }
-    const size_t host_blas_nodes = out.nodes.size(); // what follows are TLAS nodes
-    out.bounded = planes_c.empty();
-    for (int a = 0; a < 3; ++a) { out.bounds_mn[a] = std::numeric_limits<float>::infinity(); out.bounds_mx[a] = -std::numeric_limits<float>::infinity(); }
-    for (const PrimBounds& b : cbox) for (int a = 0; a < 3; ++a) { out.bounds_mn[a] = std::min(out.bounds_mn[a], b.mn[a]); out.bounds_mx[a] = std::max(out.bounds_mx[a], b.mx[a]); }
-    out.closest_root = append_tlas(cinst, cbox, out);
-    out.shadow_root = append_tlas(sinst, sbox, out);
-    for (size_t k = 0; k < planes_c.size(); ++k) {
-        out.planes.push_back((int32_t)cinst.size()); cinst.push_back(planes_c[k]);
-        out.shadow_planes.push_back((int32_t)sinst.size()); sinst.push_back(planes_s[k]);
+    // The two TLASes over the instance lists, the planes behind their leaves, everything host-built moved behind the device-built arrays, the links.
+    int link_scene() {
+        const size_t host_blas_nodes = out.nodes.size(); // what follows are TLAS nodes
+        out.bounded = planes_c.empty();
+        empty_box(out.bounds_mn, out.bounds_mx);
+        for (const PrimBounds& b : cbox) for (int a = 0; a < 3; ++a) { out.bounds_mn[a] = std::min(out.bounds_mn[a], b.mn[a]); out.bounds_mx[a] = std::max(out.bounds_mx[a], b.mx[a]); }
+        out.closest_root = append_tlas(cinst, cbox, out);
+        out.shadow_root = append_tlas(sinst, sbox, out);
+        for (size_t k = 0; k < planes_c.size(); ++k) {
+            out.planes.push_back((int32_t)cinst.size()); cinst.push_back(planes_c[k]);
+            out.shadow_planes.push_back((int32_t)sinst.size()); sinst.push_back(planes_s[k]);
+        }
+        if (out.dev_nodes || out.dev_tris) {
+            // Device-built BLASes come FIRST in the scene's node / triangle arrays (their refs were absolute from the start); everything the
+            // host built moves behind them: BLAS nodes (child and leaf refs), TLAS nodes (child refs; their leaves are instance indices), roots.
+            const int32_t dn = (int32_t)out.dev_nodes; const uint32_t dt = (uint32_t)out.dev_tris;
+            for (size_t i = 0; i < out.nodes.size(); ++i)
+                for (int k = 0; k < 4; ++k) { int32_t& c = out.nodes[i].children()[k]; c = i < host_blas_nodes ? rebase_ref(c, dn, dt) : (c >= 0 ? c + dn : c); }
+            if (out.closest_root >= 0) out.closest_root += dn;
+            if (out.shadow_root >= 0) out.shadow_root += dn;
+            for (std::vector<Instance>* list : {&cinst, &sinst})
+                for (Instance& in : *list) {
+                    if (in.kind != NRAYS_SHAPE_TRIMESH) continue;
+                    if (in.flags & kInstDeviceTmp) in.flags &= ~(uint32_t)kInstDeviceTmp; else in.blas_root = rebase_ref(in.blas_root, dn, dt);
+                }
+            if (out.tris.size() + out.dev_tris >= (1u << 28)) return fail("too many triangles", NRAYS_ERR_UNSUPPORTED);
+            for (NodeSurface& s : out.surface) if (!s.device_built) s.first += dt;
+        }
+        out.instances.swap(cinst);
+        out.shadow_instances.swap(sinst);
+        for (const Instance& in : out.instances) out.links.push_back(InstLink{in.blas_root, in.flags});
+        for (const Instance& in : out.shadow_instances) out.shadow_links.push_back(InstLink{in.blas_root, in.flags});
+        // the traversal addresses a node as base + 32-bit byte offset (trace_device.h: load_planes)
+        if (out.nodes.size() + out.dev_nodes >= ((size_t)1 << 25)) return fail("scene too large: more than 2^25 BVH nodes");
+        return NRAYS_OK;
     }
-    if (out.dev_nodes || out.dev_tris) {
-        // Device-built BLASes come FIRST in the scene's node / triangle arrays (their refs were absolute from the start); everything the
-        // host built moves behind them: BLAS nodes (child and leaf refs), TLAS nodes (child refs; their leaves are instance indices), roots.
-        const int32_t dn = (int32_t)out.dev_nodes; const uint32_t dt = (uint32_t)out.dev_tris;
-        for (size_t i = 0; i < out.nodes.size(); ++i)
-            for (int k = 0; k < 4; ++k) { int32_t& c = out.nodes[i].children()[k]; c = i < host_blas_nodes ? rebase_ref(c, dn, dt) : (c >= 0 ? c + dn : c); }
-        if (out.closest_root >= 0) out.closest_root += dn;
-        if (out.shadow_root >= 0) out.shadow_root += dn;
-        for (std::vector<Instance>* list : {&cinst, &sinst})
-            for (Instance& in : *list) {
-                if (in.kind != NRAYS_SHAPE_TRIMESH) continue;
-                if (in.flags & kInstDeviceTmp) in.flags &= ~(uint32_t)kInstDeviceTmp; else in.blas_root = rebase_ref(in.blas_root, dn, dt);
-            }
-        if (out.tris.size() + out.dev_tris >= (1u << 28)) { err = "too many triangles"; return NRAYS_ERR_UNSUPPORTED; }
-        for (NodeSurface& s : out.surface) if (!s.device_built) s.first += dt;
+    int run() {
+        int rc = copy_tables();
+        if (rc == NRAYS_OK) rc = node_records();
+        if (rc != NRAYS_OK) return rc;
+        node_surfaces();
+        analytic_instances();
+        rc = mesh_groups();
+        if (rc == NRAYS_OK) rc = pending_aabbs();
+        if (rc != NRAYS_OK) return rc;
+        feature_bits();
+        return link_scene();
     }
-    out.instances.swap(cinst);
-    out.shadow_instances.swap(sinst);
-    for (const Instance& in : out.instances) out.links.push_back(InstLink{in.blas_root, in.flags});
-    for (const Instance& in : out.shadow_instances) out.shadow_links.push_back(InstLink{in.blas_root, in.flags});
-    // the traversal addresses a node as base + 32-bit byte offset (trace_device.h: load_planes)
-    if (out.nodes.size() + out.dev_nodes >= ((size_t)1 << 25)) { err = "scene too large: more than 2^25 BVH nodes"; return NRAYS_ERR_BAD_ARG; }
-    return NRAYS_OK;
+};
+
+} // namespace
+
+int build_host_scene(const NraysSceneDesc* d, const Switches& sw, HostScene& out, std::string& err) {
+    if (!d) { err = "null scene descriptor"; return NRAYS_ERR_BAD_ARG; }
+    if ((d->num_lights && !d->lights) || (d->num_materials && !d->materials) || (d->num_textures && !d->textures) ||
+        (d->num_meshes && !d->meshes) || (d->num_nodes && !d->nodes)) { err = "null array with non-zero count"; return NRAYS_ERR_BAD_ARG; }
+    for (int a = 0; a < 3; ++a) out.background[a] = d->background[a];
+    return Flatten{d, sw, out, err}.run();
 }
 
 } // namespace nrays
+
