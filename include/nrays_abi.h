@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -505,7 +505,7 @@ int nrays_debug_gather_sh_fold(NraysScene* scene, uint32_t n, const double* poin
 
 /* The CONSUMER of the probes nrays_gather_sh_points* writes: the irradiance at n caller-supplied points with normals from a regular GRID of SH probes — the
  * indirect term of whatever moves through a baked scene.  Per point the eight probes around it are blended (trilinear weights, optionally a facing factor that
- * holds down probes behind the surface, and a per-probe validity word that leaves out a probe inside a wall; which probes are valid is the caller's to decide)
+ * holds down probes behind the surface, and a per-probe validity word that leaves out a probe inside a wall; which probes are valid is the caller's to decide, from the counts of nrays_probe_depth_points*)
  * and the blended coefficients are folded with the cosine lobe at the normal.  No ray is traced and the scene's geometry is not read: the handle gives the device,
  * the stream ordering and the staging arena.  The result is defined by this text; nothing is fused, every product and sum is rounded on its own and expressions
  * are evaluated left to right as written (Python: irradiance_points_ref).  With c_a = counts[a], for a live point p with normal n (f64, used as given):
@@ -628,6 +628,89 @@ int nrays_gather_maps_points_device(NraysScene* scene, uint32_t n, const double*
 /* Same, every pointer (the two tables, node_map and the maps' texels included) HOST memory.  Blocking.  The maps' texels are staged with the tables, once a call. */
 int nrays_gather_maps_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
                              const uint64_t* keys, const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags);
+
+/* What a probe SEES of the geometry around it (Majercik et al. 2019, DDGI): per point a small octahedral map of the mean and the mean squared distance to the
+ * nearest surface, the number of rays that end close by or nowhere, and the nearest hit.  The moments are what nrays_irradiance_points_vis* reads to hold down
+ * a probe on the other side of a wall; the counts are what a caller decides a probe's validity with (a probe inside geometry sees surfaces at once in most
+ * directions; Python: probe_valid_words); the nearest hit is what a caller moves a probe off a surface with.  Defined by this text:
+ *   rays       ray j of point i is bit for bit the ray nrays_occlusion_points* builds: the same frame, rotation pick, origin and direction d (NOT normalised).
+ *              A probe is a point with normal (0, 0, 1), bias 0 and no rotations.
+ *   query      the closest-hit query of nrays_cast_rays_device, unbounded, as nrays_gather_maps_points* runs it.
+ *   per ray    in f64, left to right, nothing fused: L = sqrt((d.x*d.x + d.y*d.y) + d.z*d.z);  dist = hit ? toi * L : +inf;
+ *              r = dist < max_dist ? dist : max_dist;  rf = (float)r.
+ *   texel      of a direction (x, y, z) at resolution R, in f64 (Python: oct_texel): s = (fabs(x) + fabs(y)) + fabs(z).  If !(s > 0): a = b = 0.0, otherwise
+ *              a = x / s, b = y / s.  If z < 0, both from the OLD a and b: a' = (1.0 - fabs(b)) * copysign(1.0, a), b' = (1.0 - fabs(a)) * copysign(1.0, b).
+ *              gx = (a * 0.5 + 0.5) * (double)R;  tx = gx > 0 ? min((uint32)gx, R - 1) : 0 (a NaN gives 0);  ty likewise from b;  t = ty * R + tx.  The octahedral
+ *              map of the unit sphere; scaling a direction by a power of two does not change its texel.
+ *   fold       per texel t of point i, in f32: s1 = s2 = +0, cnt = 0; for j = 0 .. num_dirs - 1 in order, if texel(d_ij) == t: s1 = s1 + rf;
+ *              s2 = s2 + rf * rf (the product rounded, then the sum); cnt += 1.  out_moments[(i * R*R + t) * 2 + 0] = cnt ? s1 / (float)cnt : (float)max_dist,
+ *              [.. + 1] = cnt ? s2 / (float)cnt : (float)max_dist * (float)max_dist; each division the correctly rounded one (Python: probe_depth_ref).
+ *   out_counts n x 2 words, or NULL (no store): the rays of point i with dist < near_dist, and its rays with no hit at all.
+ *   out_nearest      n doubles, or NULL: the minimum of dist over the rays of point i, +inf if none hit.
+ *   out_nearest_dir  n words, or NULL: the smallest j that attains that minimum, 0xFFFFFFFF if none hit.
+ *   skipped    a point whose hit_flags bit 0 is clear: (float)max_dist, (float)max_dist * (float)max_dist in every texel, counts 0, 0, nearest +inf and
+ *              0xFFFFFFFF; no traversal, neither its point nor its normal read.
+ * The result never depends on lanes, rounds or chunks. */
+/* (Struct plus separate typedef, as NraysGatherMapsParams and for the same reason; tests/test_probe_depth.py compares it with its Rust and ctypes twins.) */
+struct NraysProbeDepthParams {
+    uint32_t num_dirs;        /* 1 .. 1024 */
+    uint32_t num_rotations;   /* 0 .. 1024; 0 = none */
+    const double* dirs;       /* num_dirs x 3, local frame, z = the normal */
+    const double* rotations;  /* num_rotations x 2 (cos, sin), or NULL when 0 */
+    double bias;              /* finite */
+    double max_dist;          /* finite, > 0: distances are clamped to it, and an empty texel holds it */
+    double near_dist;         /* finite, >= 0: out_counts[2i] counts the rays that end closer than this */
+    uint32_t res;             /* R: 4, 8 or 16; R * R texels a point */
+    uint32_t reserved;        /* must be 0 */
+};
+typedef struct NraysProbeDepthParams NraysProbeDepthParams;
+/*   points, normals, hit_flags, keys   as for nrays_gather_maps_points_device.
+ *   params           HOST memory (the struct); params->dirs and ->rotations are DEVICE memory here, like every other array.
+ *   out_moments      n x R*R x 2 floats, required.   out_counts n x 2 words, out_nearest n doubles, out_nearest_dir n words: each may be NULL.
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG).
+ * NULL scene / points / normals / params / dirs / out_moments; num_dirs outside 1 .. 1024, num_rotations > 1024 or > 0 with NULL rotations; a non-finite bias;
+ * a max_dist that is not finite and > 0; a near_dist that is not finite and >= 0; res other than 4, 8 or 16; reserved != 0; flags != 0 -> NRAYS_ERR_BAD_ARG,
+ * before any device work.  n == 0 -> NRAYS_OK, the outputs untouched.  Otherwise the contract of nrays_gather_maps_points_device: chunks of at most
+ * max(1, 2^22 / num_dirs) points, enqueued on `hip_stream` behind the handle's previous work, without read-back or synchronisation in ANY scene kind; what the
+ * handle reports about its renders and its per-camera scheduling state stay untouched.
+ * Workspace: the per-texel sums depend on the order of j, so they are not folded through the lanes that trace: the handle's workspace keeps rf of ONE chunk
+ * (4 bytes a ray, at most 2^22 rays = 16 MiB) between the trace and a fold that gives every (point, texel) a lane and rebuilds each direction from (i, j).  No
+ * ray, direction or per-ray distance crosses the interface. */
+int nrays_probe_depth_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                    const uint64_t* keys, const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts,
+                                    double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables included) HOST memory.  Blocking. */
+int nrays_probe_depth_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                             const uint64_t* keys, const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts,
+                             double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags);
+
+/* nrays_irradiance_points* with VISIBILITY: the value defined there with one step inserted per corner k, after the facing factor and the validity rule, for a
+ * corner whose probe is valid (an invalid probe's moment row is never read, like its SH row).  With q the probe's position as the facing step computes it
+ * (q_a = origin_a + (double)index_a * cell_a) and `texel` the function of nrays_probe_depth_points_device at R = vis->res:
+ *   in f64: pb_a = p_a + n_a * bias;  v = pb - q;  l2 = (v.x*v.x + v.y*v.y) + v.z*v.z.  If l2 > 0: t = texel(v) (v is not normalised);  m1, m2 = the two floats
+ *   of row row_k, texel t of vis->moments;  df = (float)sqrt(l2).  If df > m1, in f32 with every operation rounded on its own: var = m2 - m1 * m1;
+ *   var = var > 0 ? var : 0;  diff = df - m1;  den = var + diff * diff;  ch = den > 0 ? var / den : 0;  c3 = (ch * ch) * ch;
+ *   w_k = w_k * (c3 > floor ? c3 : floor) — Chebyshev's bound on the part of the probe's rays that reach as far as the point, cubed (DDGI).  Otherwise, and
+ *   where l2 == 0, there is no factor.
+ * Everything after that is unchanged: wsum, the normalisation, the corner with a zero weight that is skipped, interpolation, the lobe and the outputs.  Moments
+ * larger than every distance (1e30) give nrays_irradiance_points* bit for bit (Python: irradiance_points_ref(visibility=...)). */
+struct NraysIrradianceVisibility {
+    const float* moments;  /* P x R*R x 2 floats, what nrays_probe_depth_points* writes at the grid's probes; rows as grid->sh */
+    uint32_t res;          /* R: 4, 8 or 16 */
+    float floor;           /* in [0, 1]: the least factor, so that a point no probe sees keeps some light (0: none) */
+    double bias;           /* finite: the point is moved along its normal by this before its distance to a probe is taken */
+};
+typedef struct NraysIrradianceVisibility NraysIrradianceVisibility;
+/* The arguments of nrays_irradiance_points_device plus `vis` (HOST memory; vis->moments DEVICE memory here).  flags: 0 or NRAYS_IRRADIANCE_FACING.  Every bad
+ * argument of that call, and NULL vis or vis->moments, res other than 4, 8 or 16, a floor outside [0, 1] or NaN, a non-finite bias -> NRAYS_ERR_BAD_ARG before
+ * any device work.  The rest of its contract holds unchanged. */
+int nrays_irradiance_points_vis_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                       const NraysIrradianceGrid* grid, const NraysIrradianceVisibility* vis, float* out_rgb, float* out_sh, float* out_weight,
+                                       uint32_t flags, void* hip_stream);
+/* Same, every pointer (grid->sh, grid->valid and vis->moments included) HOST memory.  Blocking.  The moments are staged with the grid, once a call. */
+int nrays_irradiance_points_vis(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                const NraysIrradianceGrid* grid, const NraysIrradianceVisibility* vis, float* out_rgb, float* out_sh, float* out_weight,
+                                uint32_t flags);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and

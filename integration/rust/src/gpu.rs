@@ -738,7 +738,7 @@ impl GpuScene {
     /// The irradiance at caller-supplied points with normals from a regular grid of the probes `gather_sh_points` writes (nrays_irradiance_points, blocking): the
     /// eight probes around a point blended with trilinear weights, folded with the cosine lobe at the normal and multiplied by `measure` (4 pi for sphere
     /// directions).  Probe (ix, iy, iz) sits at origin + (ix, iy, iz) * cell and is row (iz * counts[1] + iy) * counts[0] + ix of `sh` (P x bands^2 x 3 f32);
-    /// `valid` (P words, bit 0 clear: the probe is never read) leaves probes out — which ones is the caller's to decide; `facing` holds down probes behind the
+    /// `valid` (P words, bit 0 clear: the probe is never read) leaves probes out — which ones is the caller's to decide, from the counts of `probe_depth_points`; `facing` holds down probes behind the
     /// surface.  Returns per point the colour and the sum of its weights (0: no probe counted).  The value is defined in include/nrays_abi.h (NraysIrradianceGrid).
     pub fn irradiance_points(&self, points: &[(Point3<f64>, Vector3<f64>)], origin: [f64; 3], cell: [f64; 3], counts: [u32; 3], bands: u32, sh: &[f32], valid: Option<&[u32]>,
                              measure: f32, facing: bool) -> Result<(Vec<Vector3<f32>>, Vec<f32>), String> {
@@ -766,6 +766,79 @@ impl GpuScene {
                                            out_sh: *mut f32, out_weight: *mut f32, facing: bool, hip_stream: *mut c_void) -> Result<(), String> {
         let flags = if facing { NRAYS_IRRADIANCE_FACING } else { 0 };
         if nrays_irradiance_points_device(self.raw, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// `irradiance_points` with visibility (nrays_irradiance_points_vis, blocking): `moments` (P x res^2 x 2 f32, what `probe_depth_points` writes at the grid's
+    /// probes, rows as `sh`; res 4, 8 or 16) hold down a valid probe whose mean depth towards a point is shorter than the point's distance — Chebyshev's bound,
+    /// cubed, never below `floor` (in [0, 1]); `vis_bias` moves a point along its normal before that distance is taken.  The value is defined in
+    /// include/nrays_abi.h (NraysIrradianceVisibility).
+    pub fn irradiance_points_vis(&self, points: &[(Point3<f64>, Vector3<f64>)], origin: [f64; 3], cell: [f64; 3], counts: [u32; 3], bands: u32, sh: &[f32], valid: Option<&[u32]>,
+                                 measure: f32, facing: bool, moments: &[f32], res: u32, floor: f32, vis_bias: f64) -> Result<(Vec<Vector3<f32>>, Vec<f32>), String> {
+        if bands < 1 || bands > 3 { return Err(format!("bands must be in 1 ..= 3, got {}", bands)); }
+        if res != 4 && res != 8 && res != 16 { return Err(format!("res must be 4, 8 or 16, got {}", res)); }
+        let probes = counts.iter().map(|&c| c as usize).product::<usize>();
+        if counts.iter().any(|&c| c < 1 || c > 1024) || probes > 1 << 22 { return Err(format!("counts must be in 1 ..= 1024 with a product <= 2^22, got {:?}", counts)); }
+        if sh.len() != probes * (bands * bands) as usize * 3 { return Err(format!("{} coefficients for {} probes of {} bands", sh.len(), probes, bands)); }
+        if moments.len() != probes * (res * res) as usize * 2 { return Err(format!("{} moments for {} probes at res {}", moments.len(), probes, res)); }
+        if let Some(v) = valid { if v.len() != probes { return Err(format!("{} validity words for {} probes", v.len(), probes)); } }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let grid = NraysIrradianceGrid { origin, cell, counts, bands, sh: sh.as_ptr(), valid: valid.map(|v| v.as_ptr()).unwrap_or(ptr::null()), measure, reserved: 0 };
+        let vis = NraysIrradianceVisibility { moments: moments.as_ptr(), res, floor, bias: vis_bias };
+        let mut rgb = vec![0.0f32; 3 * n];
+        let mut weight = vec![0.0f32; n];
+        let flags = if facing { NRAYS_IRRADIANCE_FACING } else { 0 };
+        let rc = unsafe { nrays_irradiance_points_vis(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), &grid, &vis, rgb.as_mut_ptr(), ptr::null_mut(), weight.as_mut_ptr(), flags) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok(((0..n).map(|i| Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2])).collect(), weight))
+    }
+
+    /// `irradiance_points_vis` for n points in DEVICE memory (nrays_irradiance_points_vis_device), enqueued on `hip_stream`: the arrays of
+    /// `irradiance_points_device`.  `grid` and `vis` are host memory; `sh`, `valid` and `moments` are device memory.
+    pub unsafe fn irradiance_points_vis_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: &NraysIrradianceGrid,
+                                               vis: &NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, facing: bool,
+                                               hip_stream: *mut c_void) -> Result<(), String> {
+        let flags = if facing { NRAYS_IRRADIANCE_FACING } else { 0 };
+        if nrays_irradiance_points_vis_device(self.raw, n, points, normals, hit_flags, grid, vis, out_rgb, out_sh, out_weight, flags, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// What caller-supplied points see of the geometry around them (nrays_probe_depth_points, blocking): the rays of `occlusion_points` with the same tables, `bias`
+    /// and keys, each through the closest-hit query of `cast_rays`; per point res x res (4, 8 or 16) octahedral texels of the mean and mean squared distance
+    /// clamped to `max_dist` (the moments `irradiance_points_vis` reads), the numbers of rays that end closer than `near_dist` and of rays that hit nothing, the
+    /// least distance (inf: none) and the index of its direction (u32::MAX: none).  A probe is a point with normal (0, 0, 1), bias 0 and no rotations.  The
+    /// value is defined in include/nrays_abi.h (NraysProbeDepthParams).
+    pub fn probe_depth_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, max_dist: f64, near_dist: f64,
+                              res: u32, keys: Option<&[u64]>) -> Result<(Vec<f32>, Vec<(u32, u32)>, Vec<f64>, Vec<u32>), String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        if res != 4 && res != 8 && res != 16 { return Err(format!("res must be 4, 8 or 16, got {}", res)); }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysProbeDepthParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                             rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, max_dist, near_dist, res, reserved: 0 };
+        let mut moments = vec![0.0f32; 2 * (res * res) as usize * n];
+        let mut counts = vec![0u32; 2 * n];
+        let mut nearest = vec![0.0f64; n];
+        let mut nearest_dir = vec![0u32; n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe { nrays_probe_depth_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, moments.as_mut_ptr(), counts.as_mut_ptr(),
+                                                   nearest.as_mut_ptr(), nearest_dir.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((moments, (0..n).map(|i| (counts[2 * i], counts[2 * i + 1])).collect(), nearest, nearest_dir))
+    }
+
+    /// `probe_depth_points` for n points in DEVICE memory (nrays_probe_depth_points_device), enqueued on `hip_stream`: the arrays of `gather_points_device`,
+    /// out_moments n x res^2 x 2 f32; out_counts n x 2 u32, out_nearest n f64 and out_nearest_dir n u32, each or null.  `params` is host memory; its two tables
+    /// are device memory.
+    pub unsafe fn probe_depth_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: &NraysProbeDepthParams,
+                                            out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32,
+                                            hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_probe_depth_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_moments, out_counts, out_nearest, out_nearest_dir, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 }

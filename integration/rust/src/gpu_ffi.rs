@@ -261,6 +261,29 @@ pub struct NraysIrradianceGrid {
     pub reserved: u32,
 }
 
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysProbeDepthParams {
+    pub num_dirs: u32,
+    pub num_rotations: u32,
+    pub dirs: *const f64,
+    pub rotations: *const f64,
+    pub bias: f64,
+    pub max_dist: f64,
+    pub near_dist: f64,
+    pub res: u32,
+    pub reserved: u32,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysIrradianceVisibility {
+    pub moments: *const f32,
+    pub res: u32,
+    pub floor: f32,
+    pub bias: f64,
+}
+
 pub enum NraysScene {}
 pub enum NraysComm {}
 pub enum NraysSceneSet {}
@@ -314,6 +337,10 @@ extern "C" {
     pub fn nrays_gather_maps_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, out_rgb: *mut f32, out_counts: *mut u32, flags: u32) -> c_int;
     pub fn nrays_irradiance_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_irradiance_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
+    pub fn nrays_irradiance_points_vis_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, vis: *const NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_irradiance_points_vis(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, vis: *const NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
+    pub fn nrays_probe_depth_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysProbeDepthParams, out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_probe_depth_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysProbeDepthParams, out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_gather_order(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;
     pub fn nrays_surface_texels_device(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_surface_texels(scene: *mut NraysScene, node: u32, width: u32, height: u32, out_points: *mut f64, out_normals: *mut f64, out_uv: *mut f64, out_node: *mut i32, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;

@@ -139,6 +139,20 @@ class NraysIrradianceGrid(C.Structure):
                 ("measure", C.c_float), ("reserved", C.c_uint32)]
 
 
+class NraysProbeDepthParams(C.Structure):
+    """The tables and settings of nrays_probe_depth_points*: `dirs` / `rotations` are addresses (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("max_dist", C.c_double),
+                ("near_dist", C.c_double), ("res", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+PROBE_DEPTH_RES = (4, 8, 16)  # the resolutions of a probe's octahedral depth map
+
+
+class NraysIrradianceVisibility(C.Structure):
+    """The depth moments of nrays_irradiance_points_vis*: `moments` is an address (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("moments", C.c_void_p), ("res", C.c_uint32), ("floor", C.c_float), ("bias", C.c_double)]
+
+
 class NraysBlasDump(C.Structure):
     _fields_ = [("num_nodes", C.c_uint32), ("num_refs", C.c_uint32), ("root", C.c_int32), ("max_depth", C.c_int32), ("hairy", C.c_uint32),
                 ("node_capacity", C.c_uint32), ("ref_capacity", C.c_uint32), ("pad", C.c_uint32), ("nodes", C.POINTER(C.c_float)), ("tri_ids", C.POINTER(C.c_uint32))]
@@ -201,6 +215,14 @@ HIP_SYMBOLS = {
                                                  C.c_uint32, C.c_void_p]),
     "nrays_irradiance_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(NraysIrradianceGrid),
                                           C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32]),
+    "nrays_irradiance_points_vis_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysIrradianceGrid), C.POINTER(NraysIrradianceVisibility),
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_irradiance_points_vis": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(NraysIrradianceGrid),
+                                              C.POINTER(NraysIrradianceVisibility), C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint32]),
+    "nrays_probe_depth_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysProbeDepthParams), C.c_void_p, C.c_void_p,
+                                                  C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_probe_depth_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                           C.POINTER(NraysProbeDepthParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -253,7 +275,8 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_gather_points_device_ex", "nrays_gather_points_ex", "nrays_debug_gather_order", "nrays_dilate_texels_device", "nrays_dilate_texels",
                    "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels", "nrays_gather_sh_points_device", "nrays_gather_sh_points",
                    "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
-                   "nrays_irradiance_points")
+                   "nrays_irradiance_points", "nrays_probe_depth_points_device", "nrays_probe_depth_points", "nrays_irradiance_points_vis_device",
+                   "nrays_irradiance_points_vis")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

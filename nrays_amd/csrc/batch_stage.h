@@ -117,6 +117,13 @@ inline int gather_maps_columns(StageColumn* c, float* out_rgb, uint32_t* out_cou
     for (uint32_t m = 0; m < num_maps; ++m) c[kMapsTexels + m] = stage_table(map_texels[m], 16, map_count[m], 16);
     return kMapsTexels + (int)num_maps;
 }
+// nrays_probe_depth_points*: per point res^2 texels of two moments, two counts, the nearest distance and its direction's index.
+enum { kDepthMoments = kPointColumns, kDepthCounts, kDepthNearest, kDepthNearestDir, kDepthColumns };
+inline int probe_depth_columns(StageColumn* c, float* out_moments, uint32_t res, uint32_t* out_counts, double* out_nearest, uint32_t* out_nearest_dir) { // (after point_columns)
+    c[kDepthMoments] = stage_out(out_moments, 8 * (size_t)res * res); c[kDepthCounts] = stage_out(out_counts, 8);
+    c[kDepthNearest] = stage_out(out_nearest, 8); c[kDepthNearestDir] = stage_out(out_nearest_dir, 4);
+    return kDepthColumns;
+}
 // nrays_irradiance_points*: points against a grid of SH probes.  The grid's coefficients (12 C bytes a probe) and validity words are tables; out_sh holds 3 C floats a point.
 enum { kIrrSh, kIrrValid, kIrrPoints, kIrrNormals, kIrrHit, kIrrRgb, kIrrOutSh, kIrrWeight, kIrrColumns };
 inline int irradiance_columns(StageColumn* c, const float* grid_sh, const uint32_t* grid_valid, size_t probes, uint32_t coefs, const double* points, const double* normals,
@@ -125,6 +132,12 @@ inline int irradiance_columns(StageColumn* c, const float* grid_sh, const uint32
     c[kIrrPoints] = stage_in(points, 24); c[kIrrNormals] = stage_in(normals, 24); c[kIrrHit] = stage_in(hit_flags, 4);
     c[kIrrRgb] = stage_out(out_rgb, 12); c[kIrrOutSh] = stage_out(out_sh, 12 * (size_t)coefs); c[kIrrWeight] = stage_out(out_weight, 4);
     return kIrrColumns;
+}
+// nrays_irradiance_points_vis*: the probes' depth moments (8 res^2 bytes a probe) are one more table, staged with the grid.
+enum { kIrrMoments = kIrrColumns, kIrrVisColumns };
+inline int irradiance_vis_columns(StageColumn* c, const float* moments, size_t probes, uint32_t res) { // (after irradiance_columns)
+    c[kIrrMoments] = stage_table(moments, 8 * (size_t)res * res, probes);
+    return kIrrVisColumns;
 }
 // Lattices (one chunk of width * height items).
 enum { kTexelPoints, kTexelNormals, kTexelUv, kTexelNode, kTexelPrim, kTexelFlags, kTexelColumns };

@@ -12,19 +12,24 @@
 // too: 0.72 ms in surface order, though twice as fast as this one on shuffled points (profiles/irradiance_layouts_ab.json).  BANDS, the out_sh store and the
 // facing factor are template parameters (launch_irradiance_points): the loops over c unroll and the a_c that a smaller C does not need are never computed.  No
 // scratch (profiles/irradiance_kres.txt).
+// VIS (nrays_irradiance_points_vis*): one more factor a corner, after the facing factor and the validity rule — Chebyshev's bound from the probe's two depth moments
+// towards the point (probe_depth_kernel.h: oct_texel), cubed and held above G.floor: one 8-byte load a valid corner beside the corner's 12 C floats.  VIS = false is
+// the kernel of nrays_irradiance_points*: the moments are not looked at.
 // A skipped point (bit 0 of its flags clear) stores zeros and reads neither its point nor its normal.
 #pragma once
 
 #include "gather_sh_kernel.h"
+#include "probe_depth_kernel.h"
 
 namespace nrays {
 
 // The checked grid as the kernel takes it: cell[a] = 0 where counts[a] == 1 (the header's rule), sh / valid the call's device addresses; bands is a template parameter.
-struct IrradianceGrid { double origin[3], cell[3]; uint32_t counts[3]; const float* sh; const uint32_t* valid; float measure; };
+// moments / res / floor / bias: NraysIrradianceVisibility's, read by the VIS permutations only (null and zeros otherwise).
+struct IrradianceGrid { double origin[3], cell[3]; uint32_t counts[3]; const float* sh; const uint32_t* valid; float measure; const float* moments; uint32_t res; float floor; double bias; };
 struct IrradianceLaunch { uint32_t grid; hipStream_t stream; uint32_t n; const double* points; const double* normals; const uint32_t* hit_flags; IrradianceGrid g;
                           float* out_rgb; float* out_sh; float* out_weight; };
-// point_batches.hip: false = no such permutation.  bands 1 .. 3; want_sh: a.out_sh is stored; facing: NRAYS_IRRADIANCE_FACING.
-bool launch_irradiance_points(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing);
+// point_batches.hip: false = no such permutation.  bands 1 .. 3; want_sh: a.out_sh is stored; facing: NRAYS_IRRADIANCE_FACING; vis: a.g.moments are applied.
+bool launch_irradiance_points(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing, bool vis);
 
 constexpr double kShLobe0 = 3.141592653589793, kShLobe1 = 2.0943951023931953, kShLobe2 = 0.7853981633974483; // pi, 2 pi / 3, pi / 4
 
@@ -44,7 +49,7 @@ NR_DEV void irradiance_lobe(d3 n, float* a) {
     a[8] = (float)(kShLobe2 * (kShK4 * (n.x * n.x - n.y * n.y)));
 }
 
-template <int BANDS, bool WANT_SH, bool FACING>
+template <int BANDS, bool WANT_SH, bool FACING, bool VIS>
 __global__ void __launch_bounds__(kBlock) k_irradiance_points(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
                                                               const uint32_t* __restrict__ hit_flags, IrradianceGrid G, float* __restrict__ out_rgb,
                                                               float* __restrict__ out_sh, float* __restrict__ out_weight) {
@@ -83,8 +88,9 @@ __global__ void __launch_bounds__(kBlock) k_irradiance_points(uint32_t n, const 
                 const uint32_t ix = (k & 1) ? hi[0] : lo[0], iy = (k & 2) ? hi[1] : lo[1], iz = (k & 4) ? hi[2] : lo[2];
                 const float X = (k & 1) ? f[0] : 1.0f - f[0], Y = (k & 2) ? f[1] : 1.0f - f[1], Z = (k & 4) ? f[2] : 1.0f - f[2];
                 float wk = (X * Y) * Z;
+                d3 q = D3(0.0, 0.0, 0.0); // the probe's position
+                if (FACING || VIS) q = D3(G.origin[0] + (double)ix * G.cell[0], G.origin[1] + (double)iy * G.cell[1], G.origin[2] + (double)iz * G.cell[2]);
                 if (FACING) {
-                    const d3 q = D3(G.origin[0] + (double)ix * G.cell[0], G.origin[1] + (double)iy * G.cell[1], G.origin[2] + (double)iz * G.cell[2]);
                     const d3 v = D3(q.x - p[0], q.y - p[1], q.z - p[2]);
                     const double l2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
                     const double c = (v.x * nm.x + v.y * nm.y) + v.z * nm.z;
@@ -92,7 +98,23 @@ __global__ void __launch_bounds__(kBlock) k_irradiance_points(uint32_t n, const 
                     wk = wk * (float)(t * t + 0.2);
                 }
                 row[k] = (iz * G.counts[1] + iy) * G.counts[0] + ix; // (< 2^22)
-                if (G.valid && !(G.valid[row[k]] & 1u)) wk = 0.0f;
+                bool valid = true;
+                if (G.valid && !(G.valid[row[k]] & 1u)) { wk = 0.0f; valid = false; }
+                if (VIS && valid) {
+                    const d3 v = D3((p[0] + nm.x * G.bias) - q.x, (p[1] + nm.y * G.bias) - q.y, (p[2] + nm.z * G.bias) - q.z);
+                    const double l2 = (v.x * v.x + v.y * v.y) + v.z * v.z;
+                    if (l2 > 0.0) {
+                        const float* m = G.moments + ((size_t)row[k] * (G.res * G.res) + oct_texel(v.x, v.y, v.z, G.res)) * 2u;
+                        const float m1 = m[0], m2 = m[1], df = (float)sqrt(l2);
+                        if (df > m1) {
+                            float var = m2 - m1 * m1;
+                            var = var > 0.0f ? var : 0.0f;
+                            const float diff = df - m1, den = var + diff * diff;
+                            const float ch = den > 0.0f ? var / den : 0.0f, c3 = (ch * ch) * ch;
+                            wk = wk * (c3 > G.floor ? c3 : G.floor);
+                        }
+                    }
+                }
                 w[k] = wk;
             }
 #pragma unroll

@@ -1,8 +1,8 @@
 // point_batches.hip — the caller-batch families that take surface points and build a hemisphere of rays a point on the device, each a check, a column table
 // (batch_stage.h) and a chunk launch run by the driver of batch_call.h: nrays_occlusion_points* (k_occlusion_points: instantiated in ray_batches.hip beside the other traversal kernels, launched through launch_occlusion_points),
 // nrays_gather_points* (+ _ex) and nrays_gather_sh_points* (kernels: gather_inst.hip, gather_order_inst.hip; k_gather_fold here, k_gather_fold_sh of gather_sh_kernel.h),
-// nrays_gather_maps_points* (gather_maps_inst.hip), and the one family at points that builds no ray: nrays_irradiance_points* (k_irradiance_points of irradiance_kernel.h,
-// instantiated here).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
+// nrays_gather_maps_points* (gather_maps_inst.hip), nrays_probe_depth_points* (probe_depth_inst.hip), and the one family at points that builds no ray:
+// nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +16,7 @@
 #include "gather_maps_kernel.h"
 #include "gather_sh_kernel.h"
 #include "irradiance_kernel.h"
+#include "probe_depth_kernel.h"
 #include "ray_batch_kernel.h"
 #include "ray_order.h"
 #include "scene_handle.h"
@@ -192,20 +193,58 @@ static int gather_maps_impl(NraysScene* sc, uint32_t n, const double* points, co
     return batch_run(sc, staged, stream, cols, ncols, n, point_chunk(p->num_dirs), "gather maps batch", launch);
 }
 
+// ---- nrays_probe_depth_points*: the depth moments, near / miss counts and nearest hit of the rays of caller-supplied points (probe_depth_kernel.h) -------------
+static int check_probe_depth_args(const NraysScene* sc, const double* points, const double* normals, const NraysProbeDepthParams* p, const float* out_moments, uint32_t flags) {
+    if (!sc || !points || !normals || !p || !out_moments) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_hemisphere("NraysProbeDepthParams", p->dirs, p->num_dirs, p->rotations, p->num_rotations, p->bias) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (!(std::isfinite(p->max_dist) && p->max_dist > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: max_dist must be finite and > 0");
+    if (!(std::isfinite(p->near_dist) && p->near_dist >= 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: near_dist must be finite and >= 0");
+    if (p->res != 4u && p->res != 8u && p->res != 16u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: res must be 4, 8 or 16");
+    if (p->reserved != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: reserved must be 0");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_probe_depth_points: flags must be 0");
+    return NRAYS_OK;
+}
+static int probe_depth_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys, const NraysProbeDepthParams* p,
+                            float* out_moments, uint32_t* out_counts, double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags, bool staged, hipStream_t stream) {
+    if (check_probe_depth_args(sc, points, normals, p, out_moments, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kDepthColumns];
+    point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, hit_flags, keys);
+    probe_depth_columns(cols, out_moments, p->res, out_counts, out_nearest, out_nearest_dir);
+    const ProbeDepthSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_dist, p->near_dist, p->res};
+    // One chunk (nc <= point_chunk): the trace (the permutation is k_cast_rays', the lanes per point are k_occlusion_points') leaves rf of the chunk's rays in the
+    // workspace, 4 bytes a ray, and the fold reads them in the order of j.
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
+        const size_t rays = (size_t)nc * p->num_dirs; // (<= kTraceChunk, or one point's)
+        const int rc = grow_device(&b.w->d_gather_rays, &b.w->gather_ray_floats, rays, sizeof(float));
+        if (rc != NRAYS_OK) return rc;
+        const GatherPoints pts = chunk_points(c, key_base);
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+        const ProbeDepthLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, pts, spec, (const double*)c[kPointDirs], (const double*)c[kPointRotations],
+                                 (float*)b.w->d_gather_rays, (uint32_t*)c[kDepthCounts], (double*)c[kDepthNearest], (uint32_t*)c[kDepthNearestDir], b.w->d_spill};
+        if (!launch_probe_depth_points(a, traversal_feat(sc), lp)) return no_permutation("k_probe_depth_points");
+        HIP_TRY(hipGetLastError());
+        const ProbeDepthFoldLaunch f{b.stream, nc, pts, spec, (const double*)c[kPointDirs], (const double*)c[kPointRotations], (const float*)b.w->d_gather_rays, (float*)c[kDepthMoments]};
+        return launch_probe_depth_fold(f, p->res) ? launch_status("k_probe_depth_fold") : no_permutation("k_probe_depth_fold");
+    };
+    return batch_run(sc, staged, stream, cols, kDepthColumns, n, point_chunk(p->num_dirs), "probe depth batch", launch);
+}
+
 // ---- nrays_irradiance_points*: the irradiance at caller-supplied points from a regular grid of SH probes (irradiance_kernel.h) ----------------------------------
-template <int BANDS, bool WANT_SH, bool FACING>
-static bool launch_if(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
-    if (bands != (uint32_t)BANDS || want_sh != WANT_SH || facing != FACING) return false;
-    hipLaunchKernelGGL((k_irradiance_points<BANDS, WANT_SH, FACING>), dim3(a.grid), dim3(kBlock), 0, a.stream, a.n, a.points, a.normals, a.hit_flags, a.g, a.out_rgb, a.out_sh, a.out_weight);
+template <int BANDS, bool WANT_SH, bool FACING, bool VIS>
+static bool launch_if(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing, bool vis) {
+    if (bands != (uint32_t)BANDS || want_sh != WANT_SH || facing != FACING || vis != VIS) return false;
+    hipLaunchKernelGGL((k_irradiance_points<BANDS, WANT_SH, FACING, VIS>), dim3(a.grid), dim3(kBlock), 0, a.stream, a.n, a.points, a.normals, a.hit_flags, a.g, a.out_rgb, a.out_sh, a.out_weight);
     return true;
 }
-template <int BANDS>
-static bool launch_if_bands(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
-    return launch_if<BANDS, false, false>(a, bands, want_sh, facing) || launch_if<BANDS, false, true>(a, bands, want_sh, facing) ||
-           launch_if<BANDS, true, false>(a, bands, want_sh, facing) || launch_if<BANDS, true, true>(a, bands, want_sh, facing);
+template <int BANDS, bool VIS>
+static bool launch_if_bands(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing, bool vis) {
+    return launch_if<BANDS, false, false, VIS>(a, bands, want_sh, facing, vis) || launch_if<BANDS, false, true, VIS>(a, bands, want_sh, facing, vis) ||
+           launch_if<BANDS, true, false, VIS>(a, bands, want_sh, facing, vis) || launch_if<BANDS, true, true, VIS>(a, bands, want_sh, facing, vis);
 }
-bool launch_irradiance_points(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing) {
-    return launch_if_bands<1>(a, bands, want_sh, facing) || launch_if_bands<2>(a, bands, want_sh, facing) || launch_if_bands<3>(a, bands, want_sh, facing);
+bool launch_irradiance_points(const IrradianceLaunch& a, uint32_t bands, bool want_sh, bool facing, bool vis) {
+    return launch_if_bands<1, false>(a, bands, want_sh, facing, vis) || launch_if_bands<2, false>(a, bands, want_sh, facing, vis) || launch_if_bands<3, false>(a, bands, want_sh, facing, vis) ||
+           launch_if_bands<1, true>(a, bands, want_sh, facing, vis) || launch_if_bands<2, true>(a, bands, want_sh, facing, vis) || launch_if_bands<3, true>(a, bands, want_sh, facing, vis);
 }
 constexpr uint32_t kIrradianceMaxCount = 1024u, kIrradianceMaxProbes = 1u << 22;
 static int check_irradiance_args(const NraysScene* sc, const double* points, const double* normals, const NraysIrradianceGrid* g, const float* out_rgb, const float* out_sh, uint32_t flags) {
@@ -226,22 +265,34 @@ static int check_irradiance_args(const NraysScene* sc, const double* points, con
     if (flags & ~(uint32_t)NRAYS_IRRADIANCE_FACING) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_irradiance_points: unknown flag");
     return NRAYS_OK;
 }
+static int check_irradiance_vis(const NraysIrradianceVisibility* v) {
+    if (!v || !v->moments) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (v->res != 4u && v->res != 8u && v->res != 16u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceVisibility: res must be 4, 8 or 16");
+    if (!(v->floor >= 0.0f && v->floor <= 1.0f)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceVisibility: floor must be in [0, 1]");
+    if (!std::isfinite(v->bias)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysIrradianceVisibility: bias must be finite");
+    return NRAYS_OK;
+}
+// `v`: null for nrays_irradiance_points*; NraysIrradianceVisibility (checked here) for nrays_irradiance_points_vis*, one more table and the VIS permutations.
 static int irradiance_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* g,
-                                  float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, bool staged, hipStream_t stream) {
+                                  const NraysIrradianceVisibility* v, bool vis, float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, bool staged, hipStream_t stream) {
     if (check_irradiance_args(sc, points, normals, g, out_rgb, out_sh, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (vis && check_irradiance_vis(v) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     const uint32_t coefs = g->bands * g->bands;
-    StageColumn cols[kIrrColumns];
-    irradiance_columns(cols, g->sh, g->valid, (size_t)g->counts[0] * g->counts[1] * g->counts[2], coefs, points, normals, hit_flags, out_rgb, out_sh, out_weight);
+    const size_t probes = (size_t)g->counts[0] * g->counts[1] * g->counts[2];
+    StageColumn cols[kIrrVisColumns];
+    irradiance_columns(cols, g->sh, g->valid, probes, coefs, points, normals, hit_flags, out_rgb, out_sh, out_weight);
+    const int ncols = vis ? irradiance_vis_columns(cols, v->moments, probes, v->res) : (int)kIrrColumns;
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
         IrradianceGrid k;
         for (int a = 0; a < 3; ++a) { k.origin[a] = g->origin[a]; k.counts[a] = g->counts[a]; k.cell[a] = g->counts[a] > 1u ? g->cell[a] : 0.0; }
         k.sh = (const float*)c[kIrrSh]; k.valid = (const uint32_t*)c[kIrrValid]; k.measure = g->measure;
+        k.moments = vis ? (const float*)c[kIrrMoments] : nullptr; k.res = vis ? v->res : 0u; k.floor = vis ? v->floor : 0.0f; k.bias = vis ? v->bias : 0.0;
         const IrradianceLaunch a{launch_grid(nc), b.stream, nc, (const double*)c[kIrrPoints], (const double*)c[kIrrNormals], (const uint32_t*)c[kIrrHit], k,
                                  (float*)c[kIrrRgb], (float*)c[kIrrOutSh], (float*)c[kIrrWeight]};
-        return launch_irradiance_points(a, g->bands, out_sh != nullptr, (flags & NRAYS_IRRADIANCE_FACING) != 0u) ? launch_status("k_irradiance_points") : no_permutation("k_irradiance_points");
+        return launch_irradiance_points(a, g->bands, out_sh != nullptr, (flags & NRAYS_IRRADIANCE_FACING) != 0u, vis) ? launch_status("k_irradiance_points") : no_permutation("k_irradiance_points");
     };
-    return batch_run(sc, staged, stream, cols, kIrrColumns, n, kTraceChunk, "irradiance batch", launch);
+    return batch_run(sc, staged, stream, cols, ncols, n, kTraceChunk, "irradiance batch", launch);
 }
 
 // nrays_debug_occlusion_rays: ray j of point i of the chunk, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].  NULL keys: key_base + i.
@@ -330,11 +381,29 @@ int nrays_gather_maps_points(NraysScene* sc, uint32_t n, const double* points, c
 
 int nrays_irradiance_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
                                    float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, void* hip_stream) {
-    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, false, (hipStream_t)hip_stream);
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, nullptr, false, out_rgb, out_sh, out_weight, flags, false, (hipStream_t)hip_stream);
 }
 int nrays_irradiance_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
                             float* out_rgb, float* out_sh, float* out_weight, uint32_t flags) {
-    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, out_rgb, out_sh, out_weight, flags, true, nullptr);
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, nullptr, false, out_rgb, out_sh, out_weight, flags, true, nullptr);
+}
+int nrays_irradiance_points_vis_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
+                                       const NraysIrradianceVisibility* vis, float* out_rgb, float* out_sh, float* out_weight, uint32_t flags, void* hip_stream) {
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, vis, true, out_rgb, out_sh, out_weight, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_irradiance_points_vis(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,
+                                const NraysIrradianceVisibility* vis, float* out_rgb, float* out_sh, float* out_weight, uint32_t flags) {
+    return irradiance_points_impl(sc, n, points, normals, hit_flags, grid, vis, true, out_rgb, out_sh, out_weight, flags, true, nullptr);
+}
+
+int nrays_probe_depth_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                    const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts, double* out_nearest, uint32_t* out_nearest_dir,
+                                    uint32_t flags, void* hip_stream) {
+    return probe_depth_impl(sc, n, points, normals, hit_flags, keys, params, out_moments, out_counts, out_nearest, out_nearest_dir, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_probe_depth_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                             const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts, double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags) {
+    return probe_depth_impl(sc, n, points, normals, hit_flags, keys, params, out_moments, out_counts, out_nearest, out_nearest_dir, flags, true, nullptr);
 }
 
 // k_gather_fold_sh alone on caller-supplied ray colours, one chunk, through the staging arena; the kernel between events of its own when out_kernel_ms is wanted.

@@ -291,6 +291,36 @@ def _probe_grid(grid):
     return origin, cell, counts, {1: 1, 4: 2, 9: 3}[coefs], sh.reshape(probes, coefs, 3), valid, measure
 
 
+ProbeVisibility = collections.namedtuple("ProbeVisibility", ("moments", "res", "floor", "bias"), defaults=(0.05, 0.0))
+ProbeVisibility.__doc__ = """The depth moments of a ProbeGrid's probes (NraysIrradianceVisibility): `moments` (P, res^2, 2) float32, what probe_depth() returns at the grid's
+probe_grid_positions(), rows as grid.sh; `res` 4, 8 or 16; `floor` in [0, 1]: the least visibility factor; `bias`: a point is moved along its normal by this before
+its distance to a probe is taken."""
+
+
+def _depth_res(res):
+    if isinstance(res, bool) or int(res) != res or int(res) not in abi.PROBE_DEPTH_RES:
+        raise ValueError("res must be 4, 8 or 16, got %r" % (res,))
+    return int(res)
+
+
+def _probe_visibility(vis, probes):
+    """The checks of NraysIrradianceVisibility that need no library: (moments (P, res^2, 2) float32 array or tensor, res, floor, bias) with plain Python numbers."""
+    if not isinstance(vis, tuple) or len(vis) != 4:
+        raise ValueError("visibility must be a ProbeVisibility(moments, res, floor, bias)")
+    moments, res, floor, bias = vis
+    res = _depth_res(res)
+    if moments is None or not (_is_tensor(moments) or isinstance(moments, np.ndarray)):
+        raise ValueError("visibility.moments must be a float32 numpy array or torch tensor")
+    if str(moments.dtype).split(".")[-1] != "float32" or int(np.prod(tuple(moments.shape))) != probes * res * res * 2:
+        raise ValueError("visibility.moments must be float32 of shape (%d, %d, 2), got %s %s" % (probes, res * res, tuple(moments.shape), moments.dtype))
+    floor, bias = float(floor), float(bias)
+    if not 0.0 <= floor <= 1.0:
+        raise ValueError("visibility.floor must be in [0, 1], got %r" % floor)
+    if not math.isfinite(bias):
+        raise ValueError("visibility.bias must be finite")
+    return moments.reshape(probes, res * res, 2), res, floor, bias
+
+
 class Interpolation:
     Bilinear = abi.INTERP_BILINEAR
     Nearest = abi.INTERP_NEAREST

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import abi
 from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
-                      _occlusion_tables, _probe_grid, _probe_lattice, _sh_bands, _texel_lattice)
+                      _depth_res, _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
 
 SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
 SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
@@ -221,11 +221,88 @@ def probe_grid_positions(origin, cell, counts):
     return np.ascontiguousarray(np.stack([x.reshape(-1), y.reshape(-1), z.reshape(-1)], axis=1))
 
 
-def irradiance_points_ref(points, normals, grid, facing=False, hit_flags=None):
+def oct_texel(dirs, res):
+    """The numpy mirror of the texel function of nrays_probe_depth_points* (include/nrays_abi.h): (..., 3) float64 directions, used as given -> (...) uint32 texel
+    indices ty * res + tx of the res x res octahedral map.  Scaling a direction by a power of two does not change its texel; a zero or NaN direction gives the
+    middle texel (res / 2, res / 2)."""
+    R = _depth_res(res)
+    if _is_tensor(dirs):
+        raise ValueError("oct_texel takes a numpy array")
+    d = np.asarray(dirs, dtype=np.float64)
+    if d.ndim < 1 or d.shape[-1] != 3:
+        raise ValueError("dirs must have shape (..., 3), got %s" % (d.shape,))
+    x, y, z = d[..., 0], d[..., 1], d[..., 2]
+
+    def axis(a):
+        g = (a * 0.5 + 0.5) * float(R)
+        pos = g > 0.0
+        return np.where(pos, np.minimum(np.where(pos, g, 0.0).astype(np.int64), R - 1), 0)
+    with np.errstate(all="ignore"):
+        s = (np.abs(x) + np.abs(y)) + np.abs(z)
+        some = s > 0.0
+        den = np.where(some, s, 1.0)
+        a, b = np.where(some, x / den, 0.0), np.where(some, y / den, 0.0)
+        below = z < 0.0
+        a, b = (np.where(below, (1.0 - np.abs(b)) * np.copysign(1.0, a), a), np.where(below, (1.0 - np.abs(a)) * np.copysign(1.0, b), b))
+        return (axis(b) * R + axis(a)).astype(np.uint32)
+
+
+PROBE_NO_DIR = 0xFFFFFFFF  # nearest_dir of a point none of whose rays hit
+
+
+def probe_depth_ref(ray_dirs, tois, hit, res=8, max_dist=None, near_dist=0.0, hit_flags=None):
+    """The numpy mirror of the fold of nrays_probe_depth_points*, bit for bit: ray_dirs (n, k, 3) float64 (occlusion_rays()' directions), tois (n, k) float64 and
+    hit (n, k) booleans or flag words with bit 0 (closest_hits' toi and flags for those rays) -> (moments (n, res^2, 2) float32, counts (n, 2) uint32, nearest (n,)
+    float64, nearest_dir (n,) uint32).  dist = toi * |d| in float64 (+inf at a miss), clamped to max_dist and rounded to float32; per texel of oct_texel(d) the
+    float32 sums of rf and rf * rf in the order of j over the count, or (max_dist, max_dist^2) where no ray fell.  hit_flags (n,): bit 0 clear skips a point."""
+    R = _depth_res(res)
+    if max_dist is None:
+        raise ValueError("max_dist is required")
+    max_dist, near_dist = float(max_dist), float(near_dist)
+    if not (math.isfinite(max_dist) and max_dist > 0.0):
+        raise ValueError("max_dist must be finite and > 0")
+    if not (math.isfinite(near_dist) and near_dist >= 0.0):
+        raise ValueError("near_dist must be finite and >= 0")
+    d, toi, hit = np.asarray(ray_dirs, dtype=np.float64), np.asarray(tois, dtype=np.float64), np.asarray(hit)
+    if d.ndim != 3 or d.shape[2] != 3 or d.shape[1] < 1 or toi.shape != d.shape[:2] or hit.shape != d.shape[:2]:
+        raise ValueError("ray_dirs must have shape (n, k >= 1, 3), tois and hit (n, k), got %s, %s and %s" % (d.shape, toi.shape, hit.shape))
+    n, k = toi.shape
+    _check_vec("hit_flags", hit_flags, n)
+    hit = hit if hit.dtype == np.bool_ else (hit.astype(np.uint64) & np.uint64(1)) != 0
+    live = np.ones(n, bool) if hit_flags is None else (np.asarray(hit_flags).astype(np.uint64) & np.uint64(1)) != 0
+    hit = hit & live[:, None]
+    f32 = np.float32
+    with np.errstate(all="ignore"):
+        L = np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+        dist = np.where(hit, toi * L, math.inf)
+        rf = np.where(dist < max_dist, dist, max_dist).astype(f32)
+        tex = oct_texel(d, R).astype(np.int64)
+        s1, s2, cnt = np.zeros((n, R * R), f32), np.zeros((n, R * R), f32), np.zeros((n, R * R), np.int64)
+        rows = np.arange(n)[live]
+        for j in range(k):
+            at = (rows, tex[rows, j])
+            r = rf[rows, j]
+            s1[at] = s1[at] + r
+            s2[at] = s2[at] + r * r
+            cnt[at] += 1
+        some = cnt > 0
+        fc = np.where(some, cnt, 1).astype(f32)
+        moments = np.stack([np.where(some, s1 / fc, f32(max_dist)), np.where(some, s2 / fc, f32(max_dist) * f32(max_dist))], axis=2).astype(f32)
+        counts = np.stack([((dist < near_dist) & live[:, None]).sum(axis=1), (~hit & live[:, None]).sum(axis=1)], axis=1).astype(np.uint32)
+        nearest = dist.min(axis=1)
+        nearest_dir = np.where(nearest < math.inf, np.argmin(dist, axis=1), PROBE_NO_DIR).astype(np.uint32)
+    return moments, counts, nearest, nearest_dir
+
+
+def irradiance_points_ref(points, normals, grid, facing=False, hit_flags=None, visibility=None):
     """The numpy mirror of nrays_irradiance_points*, bit for bit (include/nrays_abi.h: NraysIrradianceGrid — cell coordinates, the facing factor and the basis at
     the normal in float64, weights and folds in float32, every product and sum rounded on its own, left to right as the header writes them).  `grid`: a ProbeGrid of
-    numpy arrays.  Returns (rgb (n, 3), sh (n, bands^2, 3), weight (n,)) float32: the three outputs of the call."""
+    numpy arrays.  `visibility`: a ProbeVisibility of numpy arrays — the mirror of nrays_irradiance_points_vis*: per valid corner the Chebyshev factor from the probe's
+    depth moments towards the point —, or None.  Returns (rgb (n, 3), sh (n, bands^2, 3), weight (n,)) float32: the three outputs of the call."""
     origin, cell, counts, bands, sh, valid, measure = _probe_grid(grid)
+    vis = None if visibility is None else _probe_visibility(visibility, counts[0] * counts[1] * counts[2])
+    if vis is not None and _is_tensor(vis[0]):
+        raise ValueError("irradiance_points_ref takes numpy arrays")
     n = _n_of(points, normals, ("points", "normals"))
     _check_vec("hit_flags", hit_flags, n)
     if any(_is_tensor(a) for a in (points, normals, hit_flags, sh, valid)):
@@ -266,6 +343,20 @@ def irradiance_points_ref(points, normals, grid, facing=False, hit_flags=None):
             rows[k] = (idx[2] * counts[1] + idx[1]) * counts[0] + idx[0]
             if valid is not None:
                 wk = np.where(valid[rows[k]], wk, f32(0.0))
+            if vis is not None:
+                moments, R, floor, vbias = vis
+                v = [(p[:, a] + nm[:, a] * vbias) - (origin[a] + idx[a].astype(np.float64) * cell[a]) for a in range(3)]
+                l2 = (v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]
+                m = moments[rows[k], oct_texel(np.stack(v, axis=1), R).astype(np.int64)]
+                m1, m2, df = m[:, 0], m[:, 1], np.sqrt(l2).astype(f32)
+                var = m2 - m1 * m1
+                var = np.where(var > 0, var, f32(0.0))
+                diff = df - m1
+                den = var + diff * diff
+                ch = np.where(den > 0, var / np.where(den > 0, den, one), f32(0.0))
+                c3 = (ch * ch) * ch
+                held = (l2 > 0.0) & (df > m1) & (True if valid is None else valid[rows[k]])
+                wk = np.where(held, wk * np.where(c3 > f32(floor), c3, f32(floor)), wk).astype(f32)
             w[k] = wk
         wsum = np.zeros(n, f32)
         for k in range(8):

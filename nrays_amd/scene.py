@@ -21,10 +21,10 @@ import numpy as np
 
 from . import abi
 from .marshal import (CURRENT, F32, F64, I32, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
-                      Overflow, ProbeGrid, SurfaceTexels, _check_rows, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _occlusion_tables,
-                      _probe_grid, _probe_lattice, _sh_bands, _texel_lattice, np_ptr, upload)
+                      Overflow, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats,
+                      _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice, np_ptr, upload)
 from .restated import (FILTER_TAPS, SALT_GATHER, SALT_OCCLUSION, SH_COSINE_LOBE, SH_K, _rng_hash, _rng_mix, _sh_terms, _texel_edge, camera_rays, dilate_texels_ref,  # noqa: F401
-                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, occlusion_rays, probe_grid_positions, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
+                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
                        sphere_dirs, surface_texels_ref, texel_coords)
 
 
@@ -375,9 +375,22 @@ class BatchCalls:
         """Irradiance probes at free points of this scene: gather_probes(self, ...)."""
         return gather_probes(self, positions, sample_dirs, bands, energy, max_depth, keys, unordered)
 
-    def irradiance_points(self, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False):
+    def irradiance_points(self, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False, visibility=None):
         """The irradiance at caller-supplied points from a grid of SH probes, on this scene's GPU: irradiance_points(self, ...)."""
-        return irradiance_points(self, points, normals, grid, facing, hit_flags, want_sh, want_weight)
+        return irradiance_points(self, points, normals, grid, facing, hit_flags, want_sh, want_weight, visibility)
+
+    def probe_depth_points(self, points, normals, sample_dirs, res=8, max_dist=None, near_dist=0.0, rotations=None, bias=1e-3, hit_flags=None, keys=None,
+                           want=("counts", "nearest", "nearest_dir")):
+        """The depth moments, near / miss counts and nearest hit of the rays of caller-supplied points of this scene: probe_depth_points(self, ...)."""
+        return probe_depth_points(self, points, normals, sample_dirs, res, max_dist, near_dist, rotations, bias, hit_flags, keys, want)
+
+    def probe_depth(self, positions, sample_dirs, res=8, max_dist=None, near_dist=0.0, keys=None, want=("counts", "nearest", "nearest_dir")):
+        """What probes at free points of this scene see of its geometry: probe_depth(self, ...)."""
+        return probe_depth(self, positions, sample_dirs, res, max_dist, near_dist, keys, want)
+
+    def bake_probe_visibility(self, grid, sample_dirs, res=8, max_dist=None, near_dist=None, max_near_fraction=0.25, floor=0.05, bias=0.0):
+        """The depth moments and validity words of a grid of probes of this scene: bake_probe_visibility(self, grid, ...)."""
+        return bake_probe_visibility(self, grid, sample_dirs, res, max_dist, near_dist, max_near_fraction, floor, bias)
 
     def bake_probe_grid(self, origin, cell, counts, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True, valid=None, measure=4.0 * math.pi, device=None):
         """A grid of irradiance probes of this scene: bake_probe_grid(self, ...)."""
@@ -863,15 +876,18 @@ def gather_sh_fold(scene, points, normals, sample_dirs, ray_colours, rotations=N
 Irradiance = collections.namedtuple("Irradiance", ("rgb", "sh", "weight"))
 
 
-def irradiance_points(scene, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False):
+def irradiance_points(scene, points, normals, grid, facing=False, hit_flags=None, want_sh=False, want_weight=False, visibility=None):
     """The irradiance at n caller-supplied points with normals from a regular grid of SH probes — the indirect term of whatever moves through a baked scene —
     through nrays_irradiance_points_device / nrays_irradiance_points: per point the eight probes around it are blended with trilinear weights, the blend is folded
     with the cosine lobe at the normal and multiplied by grid.measure: (n, 3) float32.  irradiance_points_ref() restates it bit for bit; on a probe's position
     it is sh_irradiance() of that probe up to float32 rounding.  No ray is traced: the scene gives the GPU, the stream ordering and the staging memory.
     `grid`: a ProbeGrid — bake_probe_grid() makes one.  A point outside the grid takes the border's value.  `facing=True` (NRAYS_IRRADIANCE_FACING) multiplies a
     probe's weight by ((cos + 1) / 2)^2 + 0.2, cos between the normal and the direction to the probe: probes behind the surface count less.  grid.valid leaves
-    probes out (bit 0 clear: never read, so its row may hold anything); deciding which probes are valid — inside a wall, say — is the caller's job.  A point none
-    of whose probes counts gets zeros and weight 0.  `hit_flags` (n,) integers or None: bit 0 clear skips a point (zeros; its point and normal may hold anything).
+    probes out (bit 0 clear: never read, so its row may hold anything); deciding which probes are valid — inside a wall, say — is the caller's job, and
+    bake_probe_visibility() / probe_valid_words() do it from what the probes see.  A point none of whose probes counts gets zeros and weight 0.
+    `visibility`: None (nrays_irradiance_points*, exactly as without the keyword) or a ProbeVisibility — bake_probe_visibility() makes one — for
+    nrays_irradiance_points_vis*: a valid probe whose mean depth towards the point is shorter than the point's distance is held down by Chebyshev's bound, cubed and
+    kept above visibility.floor, so a point behind a wall is not lit by the probe on its other side.  Its moments follow the form of grid.sh.  `hit_flags` (n,) integers or None: bit 0 clear skips a point (zeros; its point and normal may hold anything).
     `want_sh` / `want_weight`: returns Irradiance(rgb, sh, weight) with the blended coefficients (n, bands^2, 3) and the weight sums (n,) that were asked for (None
     otherwise) instead of rgb alone.
     numpy arrays -> nrays_irradiance_points (blocking; the grid is staged once a call), numpy arrays.  torch tensors on the scene's GPU (points / normals float64;
@@ -882,16 +898,23 @@ def irradiance_points(scene, points, normals, grid, facing=False, hit_flags=None
     n = _n_of(points, normals, ("points", "normals"))
     _check_vec("hit_flags", hit_flags, n)
     origin, cell, counts, bands, sh, valid, measure = _probe_grid(grid)
-    b = Batch((("points", points, F64), ("normals", normals, F64), ("hit_flags", hit_flags, U32), ("grid.sh", sh, F32, True), ("grid.valid", valid, U32, True)),
+    vis = None if visibility is None else _probe_visibility(visibility, counts[0] * counts[1] * counts[2])
+    more = () if vis is None else (("visibility.moments", vis[0], F32, True),)
+    b = Batch((("points", points, F64), ("normals", normals, F64), ("hit_flags", hit_flags, U32), ("grid.sh", sh, F32, True), ("grid.valid", valid, U32, True)) + more,
               (("rgb", (n, 3), F32), ("sh", (n, bands * bands, 3), F32, bool(want_sh)), ("weight", (n,), F32, bool(want_weight))))
     g = abi.NraysIrradianceGrid((C.c_double * 3)(*origin), (C.c_double * 3)(*cell), (C.c_uint32 * 3)(*counts), bands, b.addr(b.ins[3]), b.addr(b.ins[4]), measure, 0)
-    b.call(scene, "nrays_irradiance_points", n, *b.pin[:3], C.byref(g), *b.pout, abi.IRRADIANCE_FACING if facing else 0)
+    if vis is None:
+        b.call(scene, "nrays_irradiance_points", n, *b.pin[:3], C.byref(g), *b.pout, abi.IRRADIANCE_FACING if facing else 0)
+    else:
+        v = abi.NraysIrradianceVisibility(b.addr(b.ins[5]), vis[1], vis[2], vis[3])
+        b.call(scene, "nrays_irradiance_points_vis", n, *b.pin[:3], C.byref(g), C.byref(v), *b.pout, abi.IRRADIANCE_FACING if facing else 0)
     return Irradiance(*b.outs) if want_sh or want_weight else b.outs[0]
 
 
 def bake_probe_grid(scene, origin, cell, counts, sample_dirs, bands=3, energy=1.0, max_depth=0, keys=None, unordered=True, valid=None, measure=4.0 * math.pi, device=None):
     """A grid of irradiance probes: gather_probes() at probe_grid_positions(origin, cell, counts) with the sphere table `sample_dirs`, as a ProbeGrid for
-    irradiance_points().  `valid` and `measure` are passed through (the solid angle of sphere_dirs is 4 pi); which probes are valid stays the caller's to decide.
+    irradiance_points().  `valid` and `measure` are passed through (the solid angle of sphere_dirs is 4 pi); which probes are valid stays the caller's to decide —
+    bake_probe_visibility() on the grid returns validity words from what the probes see.
     `device`: None bakes through the blocking form into numpy arrays; a GPU (or CURRENT) keeps the positions and the coefficients there as tensors."""
     origin, cell, counts = _probe_lattice(origin, cell, counts)
     positions = probe_grid_positions(origin, cell, counts)
@@ -899,6 +922,109 @@ def bake_probe_grid(scene, origin, cell, counts, sample_dirs, bands=3, energy=1.
         import torch
         positions = upload(positions, torch.device("cuda", torch.cuda.current_device()) if device is CURRENT else device)
     return ProbeGrid(origin, cell, counts, gather_probes(scene, positions, sample_dirs, bands, energy, max_depth, keys, unordered), valid, measure)
+
+
+# ---- what a probe sees of the geometry: depth moments, near / miss counts, the nearest hit (include/nrays_abi.h: nrays_probe_depth_points_device) -------------
+
+DEPTH_OUTPUTS = ("counts", "nearest", "nearest_dir")  # the optional outputs of probe_depth_points, in the order of nrays_probe_depth_points_device's arguments
+ProbeDepth = collections.namedtuple("ProbeDepth", ("moments",) + DEPTH_OUTPUTS)
+
+
+def _depth_settings(res, max_dist, near_dist):
+    res = _depth_res(res)
+    if max_dist is None:
+        raise ValueError("max_dist is required")
+    max_dist, near_dist = float(max_dist), float(near_dist)
+    if not (math.isfinite(max_dist) and max_dist > 0.0):
+        raise ValueError("max_dist must be finite and > 0, got %r" % max_dist)
+    if not (math.isfinite(near_dist) and near_dist >= 0.0):
+        raise ValueError("near_dist must be finite and >= 0, got %r" % near_dist)
+    return res, max_dist, near_dist
+
+
+def probe_depth_points(scene, points, normals, sample_dirs, res=8, max_dist=None, near_dist=0.0, rotations=None, bias=1e-3, hit_flags=None, keys=None, want=DEPTH_OUTPUTS):
+    """What n caller-supplied points SEE of the geometry around them, through nrays_probe_depth_points_device / nrays_probe_depth_points: per point the library builds
+    the len(sample_dirs) rays of occlusion_points() ON THE DEVICE (the same rays bit for bit: occlusion_rays()), runs the closest-hit query of closest_hits() on each
+    and folds the distances into ProbeDepth(moments, counts, nearest, nearest_dir): moments (n, res^2, 2) float32 — per texel of the res x res octahedral map
+    (oct_texel()) the mean and the mean square of the distances, clamped to `max_dist`, of the rays that fall into it, (max_dist, max_dist^2) where none does: the
+    visibility term of DDGI (Majercik et al. 2019) that irradiance_points(visibility=) reads —, counts (n, 2): the rays that end closer than `near_dist` and the
+    rays that hit nothing (probe_valid_words() decides a probe's validity from them), nearest (n,) float64 and nearest_dir (n,): the least distance and the index of
+    its direction (inf and 0xFFFFFFFF when nothing was hit) — what moving a probe off a surface needs.  It equals probe_depth_ref(occlusion_rays()' directions,
+    closest_hits' toi and flags) bit for bit.  No ray or per-ray distance is ever in the caller's memory; the handle's workspace keeps 4 bytes a ray of one chunk.
+    `res`: 4, 8 or 16.  `max_dist` is required (finite, > 0).  `points`, `normals`, `sample_dirs`, `rotations`, `bias`, `hit_flags`, `keys`: as for occlusion_points;
+    a skipped point holds the empty-texel pair everywhere, counts 0, inf and 0xFFFFFFFF.  `want`: which of "counts", "nearest", "nearest_dir" to compute (None otherwise).
+    numpy arrays -> nrays_probe_depth_points (blocking), numpy arrays (words uint32).  torch tensors on the scene's GPU -> nrays_probe_depth_points_device on
+    torch's current stream, tensors (words int32).  Also `scene.probe_depth_points(...)` on Scene and FileScene; probe_depth() is the form at free points."""
+    res, max_dist, near_dist = _depth_settings(res, max_dist, near_dist)
+    want = tuple(want)
+    for w in want:
+        if w not in DEPTH_OUTPUTS:
+            raise ValueError("want must name outputs among %s, got %r" % (DEPTH_OUTPUTS, w))
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    b = _point_batch(points, normals, hit_flags, keys, L, rot, (("moments", (n, res * res, 2), F32), ("counts", (n, 2), U32, "counts" in want),
+                                                                ("nearest", (n,), F64, "nearest" in want), ("nearest_dir", (n,), U32, "nearest_dir" in want)))
+    params = abi.NraysProbeDepthParams(*_tables(b), bias, max_dist, near_dist, res, 0)
+    b.call(scene, "nrays_probe_depth_points", n, *b.pin[:4], C.byref(params), *b.pout, 0)
+    return ProbeDepth(*b.outs)
+
+
+def probe_depth(scene, positions, sample_dirs, res=8, max_dist=None, near_dist=0.0, keys=None, want=DEPTH_OUTPUTS):
+    """probe_depth_points() at free points in space, as gather_probes() is gather_sh_points() there: normals (0, 0, 1), bias 0 and no rotations — that frame reproduces
+    `sample_dirs` (sphere_dirs()) bit for bit as world directions and the origin is the position itself.  A ProbeDepth; numpy or torch as `positions`."""
+    if len(positions.shape) != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must have shape (n, 3), got %s" % (tuple(positions.shape),))
+    if _is_tensor(positions):
+        import torch
+        normals = torch.zeros_like(positions)
+    else:
+        normals = np.zeros((len(positions), 3), np.float64)
+    normals[:, 2] = 1.0
+    return probe_depth_points(scene, positions, normals, sample_dirs, res, max_dist, near_dist, None, 0.0, None, keys, want)
+
+
+def probe_valid_words(counts, num_dirs, max_near_fraction=0.25):
+    """Validity words for ProbeGrid.valid from the counts of probe_depth(): 1 where at most max_near_fraction of a probe's num_dirs rays ended closer than
+    near_dist, 0 otherwise — a probe inside geometry sees a surface at once in most directions.  Compared in integers: counts[:, 0] <= floor(max_near_fraction *
+    num_dirs).  (P, 2) integers, numpy or torch -> (P,) uint32 (numpy) or int32 (torch)."""
+    num_dirs, frac = int(num_dirs), float(max_near_fraction)
+    if not 1 <= num_dirs <= OCCLUSION_MAX_TABLE:
+        raise ValueError("num_dirs must be in 1 .. %d" % OCCLUSION_MAX_TABLE)
+    if not 0.0 <= frac <= 1.0:
+        raise ValueError("max_near_fraction must be in [0, 1], got %r" % frac)
+    if len(counts.shape) != 2 or counts.shape[1] != 2:
+        raise ValueError("counts must have shape (P, 2), got %s" % (tuple(counts.shape),))
+    limit = int(math.floor(frac * num_dirs))
+    if _is_tensor(counts):
+        import torch
+        return (counts[:, 0].to(torch.int64) <= limit).to(torch.int32)
+    counts = np.asarray(counts)
+    if not np.issubdtype(counts.dtype, np.integer):
+        raise ValueError("counts must be integers, got %s" % counts.dtype)
+    return (counts[:, 0].astype(np.int64) <= limit).astype(np.uint32)
+
+
+def bake_probe_visibility(scene, grid, sample_dirs, res=8, max_dist=None, near_dist=None, max_near_fraction=0.25, floor=0.05, bias=0.0):
+    """The visibility of a ProbeGrid: probe_depth() at the grid's probe_grid_positions() with the sphere table `sample_dirs` -> (ProbeVisibility(moments, res, floor,
+    bias), valid_words): the first for irradiance_points(visibility=), the second — probe_valid_words() of the counts — for ProbeGrid.valid (grid._replace(valid=...)).
+    `max_dist=None`: 1.5 x the diagonal of a cell (the axes with more than one probe), DDGI's convention; `near_dist=None`: a fifth of the smallest cell spacing (0 for
+    a single probe).  Both defaults are conventions, not measured numbers.  The form follows grid.sh: numpy arrays bake through the blocking form, tensors on their GPU."""
+    origin, cell, counts, _, sh, _, _ = _probe_grid(grid)
+    spans = [c for c, k in zip(cell, counts) if k > 1]
+    if max_dist is None:
+        if not spans:
+            raise ValueError("max_dist is required for a grid of one probe")
+        max_dist = 1.5 * math.sqrt(sum(c * c for c in spans))
+    if near_dist is None:
+        near_dist = 0.2 * min(spans) if spans else 0.0
+    L, _, _, _ = _occlusion_tables(sample_dirs, None, 0.0, math.inf)
+    positions = probe_grid_positions(origin, cell, counts)
+    if _is_tensor(sh):
+        positions = upload(positions, sh.device)
+    d = probe_depth(scene, positions, L, res, max_dist, near_dist, None, ("counts",))
+    return ProbeVisibility(d.moments, _depth_res(res), float(floor), float(bias)), probe_valid_words(d.counts, len(L), max_near_fraction)
 
 
 # ---- the surface of a mesh node at a light map's texels (include/nrays_abi.h: nrays_surface_texels_device) ---------------------------------------------
