@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -683,6 +683,53 @@ int nrays_probe_depth_points_device(NraysScene* scene, uint32_t n, const double*
 int nrays_probe_depth_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
                              const uint64_t* keys, const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts,
                              double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags);
+
+/* A PROBE FILLED FROM BAKED MAPS, and what it sees of the geometry, from ONE traversal of its rays (post ABI 7): the spherical harmonics of the light that baked
+ * maps hold at the closest hits of a point's rays — so a probe sees the bounced light the maps of its scene already hold —, and, when `depth` is given, the
+ * outputs of nrays_probe_depth_points* from the same query (DDGI updates radiance and depth from one ray set).  Defined by this text from calls above:
+ *   rays, query, c_ij, class   those of nrays_gather_maps_points_device under the same `params` (used unchanged): the same rays, the same closest-hit query, the
+ *              same contribution c_ij and class per ray.  The query runs ONCE per ray, unbounded; params->max_toi filters the FINISHED query for c_ij and the
+ *              class only.
+ *   out_sh     n x bands^2 x 3 floats, required: the fold of nrays_gather_sh_points_device with colour_ij = c_ij — the same basis evaluated at the direction as
+ *              generated (not normalised), rounded once to f32; per accumulator acc = acc + y * c in f32 in the order of j; ONE division by (float)num_dirs.  No
+ *              measure is applied.  The first 1 and 4 coefficient rows of a 3-band result are the 1-band and 2-band results bit for bit.
+ *   out_counts n x 2 words, or NULL (no store): the mapped and the missed rays of point i, as nrays_gather_maps_points_device counts them.
+ *   depth      NULL: out_moments, out_depth_counts, out_nearest and out_nearest_dir must all be NULL.  Otherwise out_moments is required and the other three may be
+ *              NULL, and the four hold exactly what nrays_probe_depth_points_device writes for the same points, hit_flags, keys, dirs, rotations and bias with
+ *              max_dist, near_dist and res from `depth`.  dist comes from the UNFILTERED query: params->max_toi does not touch the depth side.
+ *   skipped    a point whose hit_flags bit 0 is clear: out_sh 3 * bands^2 exact zeros, out_counts 0, 0, the depth outputs nrays_probe_depth_points_device's skipped
+ *              values; no traversal, neither its point nor its normal read.
+ * The result never depends on lanes, rounds or chunks. */
+/* (Struct plus separate typedef, as NraysGatherMapsParams and for the same reason; tests/test_gather_maps_sh.py compares it with its Rust and ctypes twins.) */
+struct NraysGatherDepthSpec {
+    double max_dist;          /* finite, > 0: distances are clamped to it, and an empty texel holds it */
+    double near_dist;         /* finite, >= 0: out_depth_counts[2i] counts the rays that end closer than this */
+    uint32_t res;             /* R: 4, 8 or 16; R * R texels a point */
+    uint32_t reserved;        /* must be 0 */
+};
+typedef struct NraysGatherDepthSpec NraysGatherDepthSpec;
+/*   points, normals, hit_flags, keys, params   as for nrays_gather_maps_points_device (params and its `maps` records HOST memory; the tables, node_map and every
+ *                    map's texels DEVICE memory here).
+ *   bands            1 .. 3.          depth   HOST memory, or NULL.
+ *   out_moments      n x R*R x 2 floats.   out_depth_counts n x 2 words, out_nearest n doubles, out_nearest_dir n words.
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG).
+ * Every bad argument of nrays_gather_maps_points_device (out_sh in the place of out_rgb) and of nrays_probe_depth_points_device (depth's max_dist, near_dist and
+ * res); bands outside 1 .. 3; depth->reserved != 0; a depth output without `depth`, or `depth` without out_moments; flags != 0 -> NRAYS_ERR_BAD_ARG, before any
+ * device work.  n == 0 -> NRAYS_OK, the outputs untouched.  Otherwise the contract of nrays_gather_maps_points_device: chunks of at most max(1, 2^22 / num_dirs)
+ * points, enqueued on `hip_stream` behind the handle's previous work, without read-back or synchronisation in ANY scene kind; what the handle reports about its
+ * renders and its per-camera scheduling state stay untouched.
+ * Workspace: the handle's workspace keeps c_ij of ONE chunk (12 bytes a ray) and, with `depth`, rf behind it (4 bytes a ray): at most 2^22 rays = 64 MiB, between
+ * the trace and the two folds of the parent calls, which run unchanged: three launches a chunk, two without `depth`.  No ray, direction, per-ray colour or per-ray
+ * distance crosses the interface. */
+int nrays_gather_maps_sh_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                       const uint64_t* keys, const NraysGatherMapsParams* params, uint32_t bands, float* out_sh, uint32_t* out_counts,
+                                       const NraysGatherDepthSpec* depth, float* out_moments, uint32_t* out_depth_counts, double* out_nearest,
+                                       uint32_t* out_nearest_dir, uint32_t flags, void* hip_stream);
+/* Same, every pointer (the two tables, node_map and the maps' texels included) HOST memory.  Blocking. */
+int nrays_gather_maps_sh_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                                const uint64_t* keys, const NraysGatherMapsParams* params, uint32_t bands, float* out_sh, uint32_t* out_counts,
+                                const NraysGatherDepthSpec* depth, float* out_moments, uint32_t* out_depth_counts, double* out_nearest,
+                                uint32_t* out_nearest_dir, uint32_t flags);
 
 /* nrays_irradiance_points* with VISIBILITY: the value defined there with one step inserted per corner k, after the facing factor and the validity rule, for a
  * corner whose probe is valid (an invalid probe's moment row is never read, like its SH row).  With q the probe's position as the facing step computes it

@@ -841,6 +841,62 @@ impl GpuScene {
         if nrays_probe_depth_points_device(self.raw, n, points, normals, hit_flags, keys, params, out_moments, out_counts, out_nearest, out_nearest_dir, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
+
+    /// Probes filled from baked maps, and what they see of the geometry, from one traversal of their rays (nrays_gather_maps_sh_points, blocking): the rays, the
+    /// query, the maps and the colours of `gather_maps_points` (`max_toi` filters the colours and the counts only), folded as `gather_sh_points` folds its colours
+    /// — `sh[i][c]` = coefficient c of point i as an RGB vector, C = bands * bands, no measure applied — with the numbers of mapped and of missed rays per point;
+    /// with `depth` (max_dist, near_dist, res) also exactly what `probe_depth_points` returns for the same points, from the same query.  The value is defined in
+    /// include/nrays_abi.h (nrays_gather_maps_sh_points_device).
+    pub fn gather_maps_sh_points(&self, points: &[(Point3<f64>, Vector3<f64>)], sample_dirs: &[Vector3<f64>], rotations: &[(f64, f64)], bias: f64, max_toi: f64,
+                                 maps: &[NraysTexture], node_map: &[i32], miss: [f32; 3], bands: u32, keys: Option<&[u64]>, depth: Option<(f64, f64, u32)>)
+                                 -> Result<(Vec<Vec<Vector3<f32>>>, Vec<(u32, u32)>, Option<(Vec<f32>, Vec<(u32, u32)>, Vec<f64>, Vec<u32>)>), String> {
+        if let Some(k) = keys { if k.len() != points.len() { return Err(format!("{} keys for {} points", k.len(), points.len())); } }
+        if maps.is_empty() || maps.len() > NRAYS_GATHER_MAX_MAPS as usize { return Err(format!("{} maps: 1 .. {} are allowed", maps.len(), NRAYS_GATHER_MAX_MAPS)); }
+        if bands < 1 || bands > 3 { return Err(format!("bands must be in 1 ..= 3, got {}", bands)); }
+        if let Some((_, _, res)) = depth { if res != 4 && res != 8 && res != 16 { return Err(format!("res must be 4, 8 or 16, got {}", res)); } }
+        let (n, c) = (points.len(), (bands * bands) as usize);
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let dirs: Vec<f64> = sample_dirs.iter().flat_map(|d| vec![d.x, d.y, d.z]).collect();
+        let rot: Vec<f64> = rotations.iter().flat_map(|r| vec![r.0, r.1]).collect();
+        let params = NraysGatherMapsParams { num_dirs: sample_dirs.len() as u32, num_rotations: rotations.len() as u32, dirs: dirs.as_ptr(),
+                                             rotations: if rot.is_empty() { ptr::null() } else { rot.as_ptr() }, bias, max_toi, num_maps: maps.len() as u32,
+                                             num_nodes: node_map.len() as u32, maps: maps.as_ptr(), node_map: node_map.as_ptr(), miss_rgb: miss };
+        let spec = depth.map(|(max_dist, near_dist, res)| NraysGatherDepthSpec { max_dist, near_dist, res, reserved: 0 });
+        let texels = spec.map(|s| (s.res * s.res) as usize).unwrap_or(0);
+        let mut sh = vec![0.0f32; 3 * c * n];
+        let mut counts = vec![0u32; 2 * n];
+        let mut moments = vec![0.0f32; 2 * texels * n];
+        let mut depth_counts = vec![0u32; 2 * n];
+        let mut nearest = vec![0.0f64; n];
+        let mut nearest_dir = vec![0u32; n];
+        let kp = keys.map(|k| k.as_ptr()).unwrap_or(ptr::null());
+        let rc = unsafe {
+            match spec.as_ref() {
+                Some(s) => nrays_gather_maps_sh_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, bands, sh.as_mut_ptr(), counts.as_mut_ptr(), s,
+                                                       moments.as_mut_ptr(), depth_counts.as_mut_ptr(), nearest.as_mut_ptr(), nearest_dir.as_mut_ptr(), 0),
+                None => nrays_gather_maps_sh_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), kp, &params, bands, sh.as_mut_ptr(), counts.as_mut_ptr(), ptr::null(),
+                                                    ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), ptr::null_mut(), 0),
+            }
+        };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        let pairs = |w: &Vec<u32>| -> Vec<(u32, u32)> { (0..n).map(|i| (w[2 * i], w[2 * i + 1])).collect() };
+        let sh_rows = (0..n).map(|i| (0..c).map(|k| { let at = 3 * (i * c + k); Vector3::new(sh[at], sh[at + 1], sh[at + 2]) }).collect()).collect();
+        Ok((sh_rows, pairs(&counts), spec.map(|_| (moments, pairs(&depth_counts), nearest, nearest_dir))))
+    }
+
+    /// `gather_maps_sh_points` for n points in DEVICE memory (nrays_gather_maps_sh_points_device), enqueued on `hip_stream`: the arrays of
+    /// `gather_maps_points_device`, out_sh n x bands^2 x 3 f32, out_counts n x 2 u32 or null.  `depth` None: the four depth outputs must be null; otherwise
+    /// out_moments n x res^2 x 2 f32 is required and out_depth_counts, out_nearest, out_nearest_dir may each be null.  `params`, its `maps` records and `depth` are
+    /// host memory; the two tables, `node_map` and the maps' texels are device memory.
+    pub unsafe fn gather_maps_sh_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64,
+                                               params: &NraysGatherMapsParams, bands: u32, out_sh: *mut f32, out_counts: *mut u32, depth: Option<&NraysGatherDepthSpec>,
+                                               out_moments: *mut f32, out_depth_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32,
+                                               hip_stream: *mut c_void) -> Result<(), String> {
+        let spec = depth.map(|d| d as *const NraysGatherDepthSpec).unwrap_or(ptr::null());
+        if nrays_gather_maps_sh_points_device(self.raw, n, points, normals, hit_flags, keys, params, bands, out_sh, out_counts, spec, out_moments, out_depth_counts, out_nearest, out_nearest_dir, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
 }
 
 impl Drop for GpuScene {

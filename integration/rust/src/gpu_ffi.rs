@@ -284,6 +284,16 @@ pub struct NraysIrradianceVisibility {
     pub bias: f64,
 }
 
+/// the depth side of nrays_gather_maps_sh_points*: the settings of NraysProbeDepthParams that NraysGatherMapsParams does not carry
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysGatherDepthSpec {
+    pub max_dist: f64,
+    pub near_dist: f64,
+    pub res: u32,
+    pub reserved: u32,
+}
+
 pub enum NraysScene {}
 pub enum NraysComm {}
 pub enum NraysSceneSet {}
@@ -339,6 +349,8 @@ extern "C" {
     pub fn nrays_irradiance_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
     pub fn nrays_irradiance_points_vis_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, vis: *const NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_irradiance_points_vis(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, vis: *const NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
+    pub fn nrays_gather_maps_sh_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, bands: u32, out_sh: *mut f32, out_counts: *mut u32, depth: *const NraysGatherDepthSpec, out_moments: *mut f32, out_depth_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_gather_maps_sh_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, bands: u32, out_sh: *mut f32, out_counts: *mut u32, depth: *const NraysGatherDepthSpec, out_moments: *mut f32, out_depth_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32) -> c_int;
     pub fn nrays_probe_depth_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysProbeDepthParams, out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_probe_depth_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysProbeDepthParams, out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_gather_order(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_keys: *mut u64, out_order: *mut u32, out_frame: *mut f64, out_info: *mut u32) -> c_int;

@@ -13,4 +13,5 @@ from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolat
                     gather_probes, gather_sh_fold, gather_sh_points, sh_basis, sh_fold_ref, sh_irradiance, sphere_dirs,
                     bake_bounces, gather_maps_hits, gather_maps_points, lightmap_sample_ref,
                     Irradiance, ProbeGrid, bake_probe_grid, irradiance_points, irradiance_points_ref, probe_grid_positions,
-                    ProbeDepth, ProbeVisibility, bake_probe_visibility, oct_texel, probe_depth, probe_depth_points, probe_depth_ref, probe_valid_words)
+                    ProbeDepth, ProbeVisibility, bake_probe_visibility, oct_texel, probe_depth, probe_depth_points, probe_depth_ref, probe_valid_words,
+                    GatherMapsSh, bake_probe_grid_maps, gather_maps_probes, gather_maps_sh_points)

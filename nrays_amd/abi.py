@@ -148,6 +148,11 @@ class NraysProbeDepthParams(C.Structure):
 PROBE_DEPTH_RES = (4, 8, 16)  # the resolutions of a probe's octahedral depth map
 
 
+class NraysGatherDepthSpec(C.Structure):
+    """The depth side of nrays_gather_maps_sh_points*: the settings of NraysProbeDepthParams that its NraysGatherMapsParams does not carry."""
+    _fields_ = [("max_dist", C.c_double), ("near_dist", C.c_double), ("res", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class NraysIrradianceVisibility(C.Structure):
     """The depth moments of nrays_irradiance_points_vis*: `moments` is an address (device memory for the _device form, host memory otherwise)."""
     _fields_ = [("moments", C.c_void_p), ("res", C.c_uint32), ("floor", C.c_float), ("bias", C.c_double)]
@@ -223,6 +228,11 @@ HIP_SYMBOLS = {
                                                   C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
     "nrays_probe_depth_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                            C.POINTER(NraysProbeDepthParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_gather_maps_sh_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysGatherMapsParams), C.c_uint32, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(NraysGatherDepthSpec), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_gather_maps_sh_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
+                                              C.POINTER(NraysGatherMapsParams), C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(NraysGatherDepthSpec),
+                                              C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -276,7 +286,7 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_debug_box_cull", "nrays_filter_texels_device", "nrays_filter_texels", "nrays_gather_sh_points_device", "nrays_gather_sh_points",
                    "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
                    "nrays_irradiance_points", "nrays_probe_depth_points_device", "nrays_probe_depth_points", "nrays_irradiance_points_vis_device",
-                   "nrays_irradiance_points_vis")
+                   "nrays_irradiance_points_vis", "nrays_gather_maps_sh_points_device", "nrays_gather_maps_sh_points")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

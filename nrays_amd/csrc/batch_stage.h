@@ -9,7 +9,7 @@
 
 namespace nrays {
 
-constexpr int kStageMaxColumns = 32; // the widest table: nrays_gather_maps_points with 16 maps (25 columns)
+constexpr int kStageMaxColumns = 32; // the widest table: nrays_gather_maps_sh_points with 16 maps (29 columns)
 enum : uint8_t { kStageIn = 1, kStageOut = 2, kStageInOut = 3 };
 
 // One array of a call.  `ptr`: the caller's array — host memory in the blocking form, device memory in the device form; null = absent (the kernel gets null).
@@ -124,6 +124,20 @@ inline int probe_depth_columns(StageColumn* c, float* out_moments, uint32_t res,
     c[kDepthNearest] = stage_out(out_nearest, 8); c[kDepthNearestDir] = stage_out(out_nearest_dir, 4);
     return kDepthColumns;
 }
+// nrays_gather_maps_sh_points*: the outputs of a probe filled from maps — 3 * coefs floats of SH and the two counts of nrays_gather_maps_points*, then the four outputs of
+// nrays_probe_depth_points* (absent without a depth spec: res = 0) — and the tables of gather_maps_columns; column kMapsShTexels + m holds map m.
+enum { kMapsShSh = kPointColumns, kMapsShCounts, kMapsShMoments, kMapsShDepthCounts, kMapsShNearest, kMapsShNearestDir, kMapsShNodeMap, kMapsShTexels };
+inline int gather_maps_sh_columns(StageColumn* c, float* out_sh, uint32_t coefs, uint32_t* out_counts, float* out_moments, uint32_t res, uint32_t* out_depth_counts, double* out_nearest,
+                                  uint32_t* out_nearest_dir, const int32_t* node_map, uint32_t num_nodes, uint32_t num_maps, const void* const* map_texels,
+                                  const size_t* map_count) { // (after point_columns)
+    c[kMapsShSh] = stage_out(out_sh, 12 * (size_t)coefs); c[kMapsShCounts] = stage_out(out_counts, 8);
+    c[kMapsShMoments] = stage_out(out_moments, 8 * (size_t)res * res); c[kMapsShDepthCounts] = stage_out(out_depth_counts, 8);
+    c[kMapsShNearest] = stage_out(out_nearest, 8); c[kMapsShNearestDir] = stage_out(out_nearest_dir, 4);
+    c[kMapsShNodeMap] = stage_table(node_map, 4, num_nodes);
+    for (uint32_t m = 0; m < num_maps; ++m) c[kMapsShTexels + m] = stage_table(map_texels[m], 16, map_count[m], 16);
+    return kMapsShTexels + (int)num_maps;
+}
+static_assert(kMapsShTexels + 16 <= kStageMaxColumns, "the widest table fits");
 // nrays_irradiance_points*: points against a grid of SH probes.  The grid's coefficients (12 C bytes a probe) and validity words are tables; out_sh holds 3 C floats a point.
 enum { kIrrSh, kIrrValid, kIrrPoints, kIrrNormals, kIrrHit, kIrrRgb, kIrrOutSh, kIrrWeight, kIrrColumns };
 inline int irradiance_columns(StageColumn* c, const float* grid_sh, const uint32_t* grid_valid, size_t probes, uint32_t coefs, const double* points, const double* normals,

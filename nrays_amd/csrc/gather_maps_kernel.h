@@ -15,21 +15,26 @@ struct GatherMapsSpec { uint32_t num_dirs, num_rotations; double bias, max_toi; 
 // The class of a ray's contribution; k_gather_maps_points counts the mapped and the missed ones.
 constexpr uint32_t kGatherDark = 0u, kGatherMapped = 1u, kGatherMissed = 2u;
 
-// Ray (o, d) -> its contribution and class.  The closest-hit query of cast_rays_body, max_toi filtering the FINISHED query; a miss brings P.miss; a hit on a
-// node whose node_map entry names a map, with a record that carries a uv, brings x, y, z of Texture2d::sample of that map at the record's (u, v) — tex_sample, the
-// value the library's materials get; every other hit is dark (+0).  Transparency and the side of the surface are not looked at.
+// The closest-hit query of cast_rays_body on ray (o, d), unbounded: the ungated traversal, the winner checked against the exact gates, the gated repeat.  true = a hit,
+// with `hit`, `is` and `node_id` its record.  k_gather_maps_points and k_gather_maps_rays (gather_maps_sh_kernel.h) run it once per ray.
 template <int FEAT>
-NR_DEV f3 gather_maps_ray(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, const GatherMapsSpec& P, const GatherMapsTable& M, const int32_t* __restrict__ node_map,
-                          uint32_t& cls) {
-    Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
-    Isect is; uint32_t node_id = 0; bool gated = false, any = false;
+NR_DEV bool gather_maps_query(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, Hit& hit, Isect& is, uint32_t& node_id) {
+    f3 filter = F3(1.0f, 1.0f, 1.0f);
+    bool gated = false, any = false;
+    node_id = 0;
     for (;;) {
         any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
         if (!any) break;
         if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
         gated = true;
     }
-    if (any) any = hit.t <= P.max_toi;
+    return any;
+}
+// The finished query -> its contribution and class; `any`: a hit that max_toi kept.  A miss brings P.miss; a hit on a node whose node_map entry names a map, with a
+// record that carries a uv, brings x, y, z of Texture2d::sample of that map at the record's (u, v) — tex_sample, the value the library's materials get; every other
+// hit is dark (+0).  Transparency and the side of the surface are not looked at.
+NR_DEV f3 gather_maps_contribution(bool any, const Isect& is, uint32_t node_id, Cnt& cnt, const GatherMapsSpec& P, const GatherMapsTable& M, const int32_t* __restrict__ node_map,
+                                   uint32_t& cls) {
     if (!any) { cls = kGatherMissed; return F3(P.miss[0], P.miss[1], P.miss[2]); }
     cls = kGatherDark;
     if (!is.has_uv || node_id >= P.num_nodes) return F3(0.0f, 0.0f, 0.0f);
@@ -38,6 +43,15 @@ NR_DEV f3 gather_maps_ray(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, cons
     const f4 c = tex_sample<false>(M.map[m], is.u, is.v, cnt);
     cls = kGatherMapped;
     return F3(c.x, c.y, c.z);
+}
+// Ray (o, d) -> its contribution and class: the query, max_toi filtering the FINISHED query, the contribution.
+template <int FEAT>
+NR_DEV f3 gather_maps_ray(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, const GatherMapsSpec& P, const GatherMapsTable& M, const int32_t* __restrict__ node_map,
+                          uint32_t& cls) {
+    Hit hit; Isect is; uint32_t node_id;
+    bool any = gather_maps_query<FEAT>(S, st, cnt, o, d, hit, is, node_id);
+    if (any) any = hit.t <= P.max_toi;
+    return gather_maps_contribution(any, is, node_id, cnt, P, M, node_map, cls);
 }
 
 // Point i of the chunk: its num_dirs rays, each through gather_maps_ray, folded in the order of the directions — f32 sum, then ONE division by (float)num_dirs;

@@ -1,7 +1,8 @@
 // point_batches.hip — the caller-batch families that take surface points and build a hemisphere of rays a point on the device, each a check, a column table
 // (batch_stage.h) and a chunk launch run by the driver of batch_call.h: nrays_occlusion_points* (k_occlusion_points: instantiated in ray_batches.hip beside the other traversal kernels, launched through launch_occlusion_points),
 // nrays_gather_points* (+ _ex) and nrays_gather_sh_points* (kernels: gather_inst.hip, gather_order_inst.hip; k_gather_fold here, k_gather_fold_sh of gather_sh_kernel.h),
-// nrays_gather_maps_points* (gather_maps_inst.hip), nrays_probe_depth_points* (probe_depth_inst.hip), and the one family at points that builds no ray:
+// nrays_gather_maps_points* (gather_maps_inst.hip), nrays_probe_depth_points* (probe_depth_inst.hip), nrays_gather_maps_sh_points* (gather_maps_sh_inst.hip, then the two
+// folds), and the one family at points that builds no ray:
 // nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 #include "batch_call.h"
 #include "bounce.h"
 #include "gather_maps_kernel.h"
+#include "gather_maps_sh_kernel.h"
 #include "gather_sh_kernel.h"
 #include "irradiance_kernel.h"
 #include "probe_depth_kernel.h"
@@ -194,13 +196,16 @@ static int gather_maps_impl(NraysScene* sc, uint32_t n, const double* points, co
 }
 
 // ---- nrays_probe_depth_points*: the depth moments, near / miss counts and nearest hit of the rays of caller-supplied points (probe_depth_kernel.h) -------------
+// The settings NraysProbeDepthParams and NraysGatherDepthSpec share.
+static int check_depth_settings(const char* struct_name, double max_dist, double near_dist, uint32_t res, uint32_t reserved) {
+    const char* bad = !(std::isfinite(max_dist) && max_dist > 0.0) ? "max_dist must be finite and > 0" : !(std::isfinite(near_dist) && near_dist >= 0.0) ? "near_dist must be finite and >= 0"
+                      : (res != 4u && res != 8u && res != 16u) ? "res must be 4, 8 or 16" : reserved != 0u ? "reserved must be 0" : nullptr;
+    return bad ? set_last_error(NRAYS_ERR_BAD_ARG, std::string(struct_name) + ": " + bad) : NRAYS_OK;
+}
 static int check_probe_depth_args(const NraysScene* sc, const double* points, const double* normals, const NraysProbeDepthParams* p, const float* out_moments, uint32_t flags) {
     if (!sc || !points || !normals || !p || !out_moments) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
     if (check_hemisphere("NraysProbeDepthParams", p->dirs, p->num_dirs, p->rotations, p->num_rotations, p->bias) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
-    if (!(std::isfinite(p->max_dist) && p->max_dist > 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: max_dist must be finite and > 0");
-    if (!(std::isfinite(p->near_dist) && p->near_dist >= 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: near_dist must be finite and >= 0");
-    if (p->res != 4u && p->res != 8u && p->res != 16u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: res must be 4, 8 or 16");
-    if (p->reserved != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysProbeDepthParams: reserved must be 0");
+    if (check_depth_settings("NraysProbeDepthParams", p->max_dist, p->near_dist, p->res, p->reserved) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_probe_depth_points: flags must be 0");
     return NRAYS_OK;
 }
@@ -228,6 +233,59 @@ static int probe_depth_impl(NraysScene* sc, uint32_t n, const double* points, co
         return launch_probe_depth_fold(f, p->res) ? launch_status("k_probe_depth_fold") : no_permutation("k_probe_depth_fold");
     };
     return batch_run(sc, staged, stream, cols, kDepthColumns, n, point_chunk(p->num_dirs), "probe depth batch", launch);
+}
+
+// ---- nrays_gather_maps_sh_points*: a probe filled from baked maps and what it sees of the geometry, from one traversal (gather_maps_sh_kernel.h) ------------------
+static int gather_maps_sh_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys, const NraysGatherMapsParams* p,
+                               uint32_t bands, float* out_sh, uint32_t* out_counts, const NraysGatherDepthSpec* depth, float* out_moments, uint32_t* out_depth_counts,
+                               double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags, bool staged, hipStream_t stream) {
+    if (check_gather_maps_args(sc, points, normals, p, out_sh, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (check_sh_bands(bands) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (!depth && (out_moments || out_depth_counts || out_nearest || out_nearest_dir))
+        return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_maps_sh_points: depth outputs without a depth spec");
+    if (depth && !out_moments) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (depth && check_depth_settings("NraysGatherDepthSpec", depth->max_dist, depth->near_dist, depth->res, depth->reserved) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    const void* texels[NRAYS_GATHER_MAX_MAPS]; size_t texel_count[NRAYS_GATHER_MAX_MAPS];
+    for (uint32_t m = 0; m < p->num_maps; ++m) { texels[m] = p->maps[m].texels; texel_count[m] = (size_t)p->maps[m].width * p->maps[m].height; }
+    StageColumn cols[kStageMaxColumns];
+    point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, hit_flags, keys);
+    const int ncols = gather_maps_sh_columns(cols, out_sh, bands * bands, out_counts, out_moments, depth ? depth->res : 0u, out_depth_counts, out_nearest, out_nearest_dir, p->node_map,
+                                             p->num_nodes, p->num_maps, texels, texel_count);
+    const GatherMapsSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_toi, p->num_maps, p->num_nodes, {p->miss_rgb[0], p->miss_rgb[1], p->miss_rgb[2]}};
+    // One chunk (nc <= point_chunk): the trace (the permutations and the lanes per point are k_gather_maps_points') leaves c_ij of the chunk's rays in the workspace, 12 bytes
+    // a ray, and with a depth spec rf behind them, 4 bytes a ray; the two folds of the parent calls read the planes in the order of j.
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
+        const size_t rays = (size_t)nc * p->num_dirs; // (<= kTraceChunk, or one point's)
+        const int rc = grow_device(&b.w->d_gather_rays, &b.w->gather_ray_floats, rays * (depth ? 4u : 3u), sizeof(float));
+        if (rc != NRAYS_OK) return rc;
+        float* ray_rgb = (float*)b.w->d_gather_rays;
+        GatherMapsTable table; // (as nrays_gather_maps_points*: the map records at the chunk's texel addresses)
+        std::memset(&table, 0, sizeof table);
+        for (uint32_t m = 0; m < p->num_maps; ++m) {
+            const NraysTexture& s = p->maps[m];
+            table.map[m].texels = c[kMapsShTexels + m]; table.map[m].width = s.width; table.map[m].height = s.height; table.map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
+        }
+        const GatherPoints pts = chunk_points(c, key_base);
+        const double* dirs = (const double*)c[kPointDirs];
+        const double* rotations = (const double*)c[kPointRotations];
+        GatherMapsDepth dd{0.0, 0.0, nullptr, nullptr, nullptr, nullptr};
+        if (depth) dd = GatherMapsDepth{depth->max_dist, depth->near_dist, ray_rgb + 3 * rays, (uint32_t*)c[kMapsShDepthCounts], (double*)c[kMapsShNearest], (uint32_t*)c[kMapsShNearestDir]};
+        const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
+        const GatherMapsRaysLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, pts, spec, &table, (const int32_t*)c[kMapsShNodeMap], dirs, rotations, ray_rgb,
+                                     (uint32_t*)c[kMapsShCounts], depth ? &dd : nullptr, b.w->d_spill};
+        if (!launch_gather_maps_rays(a, traversal_feat(sc), lp)) return no_permutation("k_gather_maps_rays");
+        HIP_TRY(hipGetLastError());
+        const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
+        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, b.stream, (const float*)ray_rgb, nc, pts, hemisphere_spec(p->num_dirs, p->num_rotations, p->bias), dirs, rotations,
+                           bands * bands, (float*)c[kMapsShSh]);
+        if (!depth) return launch_status("k_gather_fold_sh");
+        HIP_TRY(hipGetLastError());
+        const ProbeDepthFoldLaunch f{b.stream, nc, pts, ProbeDepthSpec{p->num_dirs, p->num_rotations, p->bias, depth->max_dist, depth->near_dist, depth->res}, dirs, rotations,
+                                     (const float*)dd.ray_rf, (float*)c[kMapsShMoments]};
+        return launch_probe_depth_fold(f, depth->res) ? launch_status("k_probe_depth_fold") : no_permutation("k_probe_depth_fold");
+    };
+    return batch_run(sc, staged, stream, cols, ncols, n, point_chunk(p->num_dirs), "gather maps sh batch", launch);
 }
 
 // ---- nrays_irradiance_points*: the irradiance at caller-supplied points from a regular grid of SH probes (irradiance_kernel.h) ----------------------------------
@@ -377,6 +435,19 @@ int nrays_gather_maps_points_device(NraysScene* sc, uint32_t n, const double* po
 int nrays_gather_maps_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                              const NraysGatherMapsParams* params, float* out_rgb, uint32_t* out_counts, uint32_t flags) {
     return gather_maps_impl(sc, n, points, normals, hit_flags, keys, params, out_rgb, out_counts, flags, true, nullptr);
+}
+
+int nrays_gather_maps_sh_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                       const NraysGatherMapsParams* params, uint32_t bands, float* out_sh, uint32_t* out_counts, const NraysGatherDepthSpec* depth,
+                                       float* out_moments, uint32_t* out_depth_counts, double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags, void* hip_stream) {
+    return gather_maps_sh_impl(sc, n, points, normals, hit_flags, keys, params, bands, out_sh, out_counts, depth, out_moments, out_depth_counts, out_nearest, out_nearest_dir, flags, false,
+                               (hipStream_t)hip_stream);
+}
+int nrays_gather_maps_sh_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
+                                const NraysGatherMapsParams* params, uint32_t bands, float* out_sh, uint32_t* out_counts, const NraysGatherDepthSpec* depth, float* out_moments,
+                                uint32_t* out_depth_counts, double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags) {
+    return gather_maps_sh_impl(sc, n, points, normals, hit_flags, keys, params, bands, out_sh, out_counts, depth, out_moments, out_depth_counts, out_nearest, out_nearest_dir, flags, true,
+                               nullptr);
 }
 
 int nrays_irradiance_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysIrradianceGrid* grid,

@@ -412,6 +412,20 @@ class BatchCalls:
         """The multi-bounce light map of mesh node `node`: bake_bounces(self, node, ...)."""
         return bake_bounces(self, node, width, height, sample_dirs, bounces, albedo, rotations, bias, miss, dilate, flip_normals, keys, device)
 
+    def gather_maps_sh_points(self, points, normals, sample_dirs, maps, node_map, bands=3, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
+                              keys=None, depth=None, want=("counts", "depth_counts", "nearest", "nearest_dir")):
+        """The light of baked maps at caller-supplied points of this scene as spherical harmonics, with depth moments from the same rays: gather_maps_sh_points(self, ...)."""
+        return gather_maps_sh_points(self, points, normals, sample_dirs, maps, node_map, bands, rotations, bias, max_toi, miss, hit_flags, keys, depth, want)
+
+    def gather_maps_probes(self, positions, sample_dirs, maps, node_map, bands=3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), keys=None, depth=None,
+                           want=("counts", "depth_counts", "nearest", "nearest_dir")):
+        """Irradiance probes at free points of this scene, filled from baked maps: gather_maps_probes(self, ...)."""
+        return gather_maps_probes(self, positions, sample_dirs, maps, node_map, bands, max_toi, miss, keys, depth, want)
+
+    def bake_probe_grid_maps(self, origin, cell, counts, sample_dirs, maps, node_map, bands=3, miss=(0.0, 0.0, 0.0), visibility=None, measure=4.0 * math.pi, device=None):
+        """A grid of irradiance probes of this scene filled from baked maps, with its visibility from the same rays: bake_probe_grid_maps(self, ...)."""
+        return bake_probe_grid_maps(self, origin, cell, counts, sample_dirs, maps, node_map, bands, miss, visibility, measure, device)
+
     def surface_texels(self, node, width, height, centres=False, flip_normals=False, want=("normals", "uv", "node", "prim"), device=None):
         """The surface of mesh node `node` at a light map's texels: surface_texels(self, node, ...)."""
         return surface_texels(self, node, width, height, centres, flip_normals, want, device)
@@ -1006,12 +1020,8 @@ def probe_valid_words(counts, num_dirs, max_near_fraction=0.25):
     return (counts[:, 0].astype(np.int64) <= limit).astype(np.uint32)
 
 
-def bake_probe_visibility(scene, grid, sample_dirs, res=8, max_dist=None, near_dist=None, max_near_fraction=0.25, floor=0.05, bias=0.0):
-    """The visibility of a ProbeGrid: probe_depth() at the grid's probe_grid_positions() with the sphere table `sample_dirs` -> (ProbeVisibility(moments, res, floor,
-    bias), valid_words): the first for irradiance_points(visibility=), the second — probe_valid_words() of the counts — for ProbeGrid.valid (grid._replace(valid=...)).
-    `max_dist=None`: 1.5 x the diagonal of a cell (the axes with more than one probe), DDGI's convention; `near_dist=None`: a fifth of the smallest cell spacing (0 for
-    a single probe).  Both defaults are conventions, not measured numbers.  The form follows grid.sh: numpy arrays bake through the blocking form, tensors on their GPU."""
-    origin, cell, counts, _, sh, _, _ = _probe_grid(grid)
+def _visibility_distances(cell, counts, max_dist, near_dist):
+    """The defaults of bake_probe_visibility(): max_dist None -> 1.5 x the diagonal of a cell, near_dist None -> a fifth of the smallest spacing (axes with more than one probe)."""
     spans = [c for c, k in zip(cell, counts) if k > 1]
     if max_dist is None:
         if not spans:
@@ -1019,6 +1029,16 @@ def bake_probe_visibility(scene, grid, sample_dirs, res=8, max_dist=None, near_d
         max_dist = 1.5 * math.sqrt(sum(c * c for c in spans))
     if near_dist is None:
         near_dist = 0.2 * min(spans) if spans else 0.0
+    return max_dist, near_dist
+
+
+def bake_probe_visibility(scene, grid, sample_dirs, res=8, max_dist=None, near_dist=None, max_near_fraction=0.25, floor=0.05, bias=0.0):
+    """The visibility of a ProbeGrid: probe_depth() at the grid's probe_grid_positions() with the sphere table `sample_dirs` -> (ProbeVisibility(moments, res, floor,
+    bias), valid_words): the first for irradiance_points(visibility=), the second — probe_valid_words() of the counts — for ProbeGrid.valid (grid._replace(valid=...)).
+    `max_dist=None`: 1.5 x the diagonal of a cell (the axes with more than one probe), DDGI's convention; `near_dist=None`: a fifth of the smallest cell spacing (0 for
+    a single probe).  Both defaults are conventions, not measured numbers.  The form follows grid.sh: numpy arrays bake through the blocking form, tensors on their GPU."""
+    origin, cell, counts, _, sh, _, _ = _probe_grid(grid)
+    max_dist, near_dist = _visibility_distances(cell, counts, max_dist, near_dist)
     L, _, _, _ = _occlusion_tables(sample_dirs, None, 0.0, math.inf)
     positions = probe_grid_positions(origin, cell, counts)
     if _is_tensor(sh):
@@ -1295,6 +1315,115 @@ def bake_bounces(scene, node, width, height, sample_dirs, bounces, albedo, rotat
         level = _bake_dilate(scene, tx.flags, nxt, width, height, radius)
         total[:, :3] = total[:, :3] + level[:, :3]
     return total.reshape(height, width, 4)
+
+
+# ---- probes filled from baked maps, with their depth from the same rays (include/nrays_abi.h: nrays_gather_maps_sh_points_device) ------------------------------
+
+GATHER_MAPS_SH_OUTPUTS = ("counts", "depth_counts", "nearest", "nearest_dir")  # the optional outputs of gather_maps_sh_points, in the order of the call's arguments
+GatherMapsSh = collections.namedtuple("GatherMapsSh", ("sh", "counts", "depth"))
+GatherMapsSh.__doc__ = """What gather_maps_sh_points returns: `sh` (n, bands^2, 3) float32; `counts` (n, 2) — the mapped and the missed rays — or None; `depth` a ProbeDepth
+(moments, counts, nearest, nearest_dir), or None when no depth settings were given."""
+_DEPTH_KEYS = ("res", "max_dist", "near_dist")
+
+
+def _gather_depth(depth):
+    """depth=None, or dict(res=, max_dist=, near_dist=) through _depth_settings (res 8 and near_dist 0 when left out, as probe_depth_points; max_dist is required)."""
+    if depth is None:
+        return None
+    if not isinstance(depth, dict) or any(k not in _DEPTH_KEYS for k in depth):
+        raise ValueError("depth must be None or a dict with keys among %s, got %r" % (_DEPTH_KEYS, depth))
+    return _depth_settings(depth.get("res", 8), depth.get("max_dist"), depth.get("near_dist", 0.0))
+
+
+def gather_maps_sh_points(scene, points, normals, sample_dirs, maps, node_map, bands=3, rotations=None, bias=1e-3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), hit_flags=None,
+                          keys=None, depth=None, want=GATHER_MAPS_SH_OUTPUTS):
+    """gather_maps_points() that keeps WHERE the light came from, and probe_depth_points() from the same rays, through nrays_gather_maps_sh_points_device /
+    nrays_gather_maps_sh_points: per point the len(sample_dirs) rays of occlusion_points() are built ON THE DEVICE and each runs the closest-hit query ONCE; the
+    colours gather_maps_points() would average (a map's sample at the hit, `miss`, or black) are folded like gather_sh_points() folds its colours — the projection
+    onto the real spherical harmonics of bands 0 .. bands - 1 of each ray's direction, (n, bands^2, 3) float32, no measure applied — and, with `depth`, the
+    distances are folded into what probe_depth_points() returns.  A probe filled this way sees the bounced light the scene's baked maps hold.  It equals
+    sh_fold_ref(occlusion_rays()' directions, the contributions of closest_hits + lightmap_sample_ref) and probe_depth_points() on the same inputs, bit for bit.
+    `depth`: None, or dict(res=4 | 8 | 16, max_dist=finite > 0 (required), near_dist=0.0): the settings of probe_depth_points.  `max_toi` turns far hits into
+    `miss` for the colours and counts only; the depth side sees the unbounded query.  `want`: which of "counts" (mapped, missed), "depth_counts", "nearest",
+    "nearest_dir" to compute; the last three only with `depth`.  The other arguments, the numpy / torch forms and the maps: as for gather_maps_points.
+    Returns GatherMapsSh(sh, counts, depth): depth a ProbeDepth, or None without `depth`.  The handle's workspace keeps 12 (16 with depth) bytes a ray of one
+    chunk; no ray or per-ray value is ever in the caller's memory.  Also `scene.gather_maps_sh_points(...)` on Scene and FileScene; gather_maps_probes() is the form
+    at free points."""
+    bands = _sh_bands(bands)
+    spec = _gather_depth(depth)
+    want = tuple(want)
+    for w in want:
+        if w not in GATHER_MAPS_SH_OUTPUTS:
+            raise ValueError("want must name outputs among %s, got %r" % (GATHER_MAPS_SH_OUTPUTS, w))
+    n = _n_of(points, normals, ("points", "normals"))
+    for name, a in (("hit_flags", hit_flags), ("keys", keys)):
+        _check_vec(name, a, n)
+    L, rot, bias, _ = _occlusion_tables(sample_dirs, rotations, bias, math.inf)
+    ms, nodes, max_toi, miss = _gather_maps_args(scene, maps, node_map, max_toi, miss)
+    deep, texels = spec is not None, (spec[0] * spec[0] if spec is not None else 0)
+    b = _point_batch(points, normals, hit_flags, keys, L, rot,
+                     (("sh", (n, bands * bands, 3), F32), ("counts", (n, 2), U32, "counts" in want), ("moments", (n, texels, 2), F32, deep),
+                      ("depth_counts", (n, 2), U32, deep and "depth_counts" in want), ("nearest", (n,), F64, deep and "nearest" in want),
+                      ("nearest_dir", (n,), U32, deep and "nearest_dir" in want)),
+                     tuple(("maps[%d]" % i, m, F32, True) for i, (m, _, _) in enumerate(ms)) + (("node_map", nodes, I32, True),))
+    recs = (abi.NraysTexture * len(ms))()  # only the params struct refers to it: it lives until this function returns
+    for t, m, (_, interp, overflow) in zip(recs, b.ins[6:-1], ms):
+        t.width, t.height, t.format, t.interp, t.overflow, t.texels = m.shape[1], m.shape[0], abi.TEXEL_RGBA32F, interp, overflow, b.addr(m)
+    params = abi.NraysGatherMapsParams(*_tables(b), bias, max_toi, len(ms), len(nodes), C.cast(recs, C.POINTER(abi.NraysTexture)), b.addr(b.ins[-1]), (C.c_float * 3)(*miss))
+    dspec = abi.NraysGatherDepthSpec(spec[1], spec[2], spec[0], 0) if deep else None
+    b.call(scene, "nrays_gather_maps_sh_points", n, *b.pin[:4], C.byref(params), bands, b.pout[0], b.pout[1], C.byref(dspec) if deep else None, *b.pout[2:], 0)
+    return GatherMapsSh(b.outs[0], b.outs[1], ProbeDepth(*b.outs[2:]) if deep else None)
+
+
+def gather_maps_probes(scene, positions, sample_dirs, maps, node_map, bands=3, max_toi=math.inf, miss=(0.0, 0.0, 0.0), keys=None, depth=None, want=GATHER_MAPS_SH_OUTPUTS):
+    """Irradiance probes at free points in space, filled from baked maps: gather_maps_sh_points() with normals (0, 0, 1), bias 0 and no rotations, as gather_probes()
+    is gather_sh_points() and probe_depth() is probe_depth_points() there — that frame reproduces `sample_dirs` (sphere_dirs()) bit for bit as world directions and
+    the origin is the position itself.  A GatherMapsSh; numpy or torch as `positions`."""
+    if len(positions.shape) != 2 or positions.shape[1] != 3:
+        raise ValueError("positions must have shape (n, 3), got %s" % (tuple(positions.shape),))
+    if _is_tensor(positions):
+        import torch
+        normals = torch.zeros_like(positions)
+    else:
+        normals = np.zeros((len(positions), 3), np.float64)
+    normals[:, 2] = 1.0
+    return gather_maps_sh_points(scene, positions, normals, sample_dirs, maps, node_map, bands, None, 0.0, max_toi, miss, None, keys, depth, want)
+
+
+_VISIBILITY_KEYS = {"res": 8, "max_dist": None, "near_dist": None, "max_near_fraction": 0.25, "floor": 0.05, "bias": 0.0}
+
+
+def bake_probe_grid_maps(scene, origin, cell, counts, sample_dirs, maps, node_map, bands=3, miss=(0.0, 0.0, 0.0), visibility=None, measure=4.0 * math.pi, device=None):
+    """A grid of irradiance probes filled from baked maps, and its visibility from the same rays, in ONE call into the library: gather_maps_probes() at
+    probe_grid_positions(origin, cell, counts) with the sphere table `sample_dirs` -> (ProbeGrid, ProbeVisibility or None) for irradiance_points(grid, visibility=).
+    The probes see what the maps hold — every bounce that was baked into them —, where bake_probe_grid() sees direct light only.
+    `visibility`: None (no depth side; the grid's `valid` is None), or a dict with keys among res=8, max_dist=None, near_dist=None, max_near_fraction=0.25,
+    floor=0.05, bias=0.0 — the parameters of bake_probe_visibility(), with its defaults for max_dist and near_dist: the moments are bit for bit what that call
+    returns on the same grid, and the grid's `valid` is probe_valid_words() of the depth counts.  `maps`, `node_map`, `miss`: as for gather_maps_points.
+    `device`: None bakes through the blocking form into numpy arrays; a GPU (or CURRENT) keeps positions and results there as tensors."""
+    origin, cell, counts = _probe_lattice(origin, cell, counts)
+    L, _, _, _ = _occlusion_tables(sample_dirs, None, 0.0, math.inf)
+    depth = v = None
+    if visibility is not None:
+        if not isinstance(visibility, dict) or any(k not in _VISIBILITY_KEYS for k in visibility):
+            raise ValueError("visibility must be None or a dict with keys among %s, got %r" % (tuple(_VISIBILITY_KEYS), visibility))
+        v = dict(_VISIBILITY_KEYS, **visibility)
+        max_dist, near_dist = _visibility_distances(cell, counts, v["max_dist"], v["near_dist"])
+        depth = dict(res=v["res"], max_dist=max_dist, near_dist=near_dist)
+        _gather_depth(depth)
+        floor, vbias = float(v["floor"]), float(v["bias"])
+        if not 0.0 <= floor <= 1.0 or not math.isfinite(vbias):
+            raise ValueError("visibility: floor must be in [0, 1] and bias finite, got %r, %r" % (floor, vbias))
+        probe_valid_words(np.zeros((1, 2), np.uint32), len(L), v["max_near_fraction"])  # (its checks, before any device work)
+    positions = probe_grid_positions(origin, cell, counts)
+    if device is not None:
+        import torch
+        positions = upload(positions, torch.device("cuda", torch.cuda.current_device()) if device is CURRENT else device)
+    g = gather_maps_probes(scene, positions, L, maps, node_map, bands, math.inf, miss, None, depth, ("depth_counts",))
+    if v is None:
+        return ProbeGrid(origin, cell, counts, g.sh, None, measure), None
+    valid = probe_valid_words(g.depth.counts, len(L), v["max_near_fraction"])
+    return ProbeGrid(origin, cell, counts, g.sh, valid, measure), ProbeVisibility(g.depth.moments, _depth_res(v["res"]), floor, vbias)
 
 
 # ---- denoising a baked map: the a-trous joint-bilateral filter (include/nrays_abi.h: nrays_filter_texels_device) -----------------------------------------------
