@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -758,6 +758,49 @@ int nrays_irradiance_points_vis_device(NraysScene* scene, uint32_t n, const doub
 int nrays_irradiance_points_vis(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
                                 const NraysIrradianceGrid* grid, const NraysIrradianceVisibility* vis, float* out_rgb, float* out_sh, float* out_weight,
                                 uint32_t flags);
+
+/* The MATERIAL TERMS at n caller-supplied surface points, without the lights: what Material::ambiant (src/material.rs:7; Scene::intersects_ray calls it,
+ * src/scene.rs:317) returns there, the diffuse reflectance `diffuse_color.component_mul(tex_color)` of phong_material.rs:120-121, the specular constants, and the
+ * per-hit constants Scene::trace reads from the node.  nrays_shade_points* folds the first three with the lights into one colour; this call hands them out, so that
+ * nrays_cast_rays* + this call is all an integrator of the caller's own needs on top of the library's traversal, a baker gets the albedo of a textured node
+ * (Python: texel_albedo), and the irradiance of nrays_irradiance_points* becomes a colour (Python: indirect_points).  No ray is traced and no light is read.
+ * The result is defined by this text (Python: material_points_ref), never by how the library assigns points to lanes or chunks.
+ *   nodes          n scene-node indices, required (the values out_node of nrays_cast_rays_device holds).
+ *   hit_flags      n words, or NULL: the bits of out_flags / NraysCastResult::flags.
+ *   uvs            n x 2 doubles, or NULL; used as given, any double.
+ *   normals        n x 3 doubles, used as given; may be NULL only when out_ambient is NULL (only the NORMAL material reads it).
+ *   live           point i is LIVE when bit 0 of hit_flags[i] is set (or hit_flags == NULL) and 0 <= nodes[i] < the scene's node count.  It CARRIES A UV when
+ *                  uvs != NULL and bit 1 of hit_flags[i] is set (or hit_flags == NULL) — nrays_shade_points_device's rule: the caller's word decides, the shape's
+ *                  own uv bit is not looked at.  Below, m is the material of node nodes[i], (u, v) = uvs[2i], uvs[2i + 1], n = normals[3i .. 3i + 2].
+ *   sample         sample(t, u, v) is Texture2d::sample of texture t exactly as written out under nrays_gather_maps_points_device (`sample`), with t's own interp
+ *                  and overflow and either texel format: an NRAYS_TEXEL_RGBA32F texel is its four floats, a channel of an NRAYS_TEXEL_RGBA8 texel is
+ *                  `u8 as f32 / 255.0`, the correctly rounded f32 quotient.  The colour texture is sampled ONCE for out_ambient and out_diffuse together, and not
+ *                  at all when neither is asked for; the opacity map is sampled only for out_ambient.
+ *   out_ambient    n x 4 floats, Material::ambiant(pt, normal, uv):
+ *                    NRAYS_MAT_PHONG with a uv   tc = (1, 1, 1, 1); with a texture: tc = sample(texture, u, v), then tc.w = 1; with an opacity map:
+ *                                                tc.w = sample(alpha, u, v).w; the result is (ka.x * tc.x, ka.y * tc.y, ka.z * tc.z, 1.0f * tc.w).
+ *                    NRAYS_MAT_PHONG without     (ka.x, ka.y, ka.z, 1).
+ *                    NRAYS_MAT_NORMAL            ((1.0f + (float)n.x) / 2.0f, (1.0f + (float)n.y) / 2.0f, (1.0f + (float)n.z) / 2.0f, 1).
+ *                    NRAYS_MAT_UV                ((float)u, (float)v, 0, 1) with a uv, (0, 0, 0, 0) without.
+ *   out_diffuse    n x 3 floats.  NRAYS_MAT_PHONG: (kd.x * t.x, kd.y * t.y, kd.z * t.z) with t = x, y, z of sample(texture, u, v) when the point carries a uv and
+ *                  the material has a texture, else (1, 1, 1).  NRAYS_MAT_NORMAL / NRAYS_MAT_UV: (+0, +0, +0).
+ *   out_specular   n x 4 floats.  NRAYS_MAT_PHONG: (ks.x, ks.y, ks.z, shininess).  Otherwise zeros.
+ *   out_node       n x 4 doubles, for every material kind: ((double)alpha, (double)refl_mix, (double)refl_atenuation, refr_coeff) of node nodes[i].
+ *   skipped        a point that is not live writes zeros into every output; neither its normal nor its uv is read, so the outputs of nrays_cast_rays_device pass
+ *                  on unfiltered, misses included.
+ *   Each output may be NULL (no store); at least one is required.
+ *   flags          must be 0.
+ * NULL scene / nodes; no output at all; NULL normals with out_ambient; any flag bit -> NRAYS_ERR_BAD_ARG, before any device work.  n == 0 -> NRAYS_OK, the outputs
+ * untouched.  Otherwise the contract of nrays_irradiance_points_device: every array device memory on the scene's device, chunks of at most 2^22 points, one launch
+ * a chunk enqueued on `hip_stream` behind the handle's previous work, without read-back, synchronisation or workspace; what the handle reports about its renders
+ * and its per-camera scheduling state stay untouched.  Traffic: 4 bytes in for the node, 4 with hit_flags, 16 with uvs where a uv is read, 24 with normals where
+ * out_ambient is asked for; 16 + 12 + 16 + 32 bytes out a point as asked for. */
+int nrays_material_points_device(NraysScene* scene, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes,
+                                 const uint32_t* hit_flags, float* out_ambient, float* out_diffuse, float* out_specular, double* out_node,
+                                 uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_material_points(NraysScene* scene, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes,
+                          const uint32_t* hit_flags, float* out_ambient, float* out_diffuse, float* out_specular, double* out_node, uint32_t flags);
 
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and

@@ -356,6 +356,18 @@ pub struct SurfacePoint {
     pub uvs: Option<Point2<f64>>,
 }
 
+/// What `GpuScene::material_points` returns for one surface point: the terms of its node's material without the lights, and the node's own constants.
+pub struct MaterialTerms {
+    pub ambient: Point4<f32>,     // Material::ambiant(pt, normal, uvs), src/material.rs:7
+    pub diffuse: Vector3<f32>,    // diffuse_color ⊙ texture.sample(uvs); zeros for the Normal and UV materials
+    pub specular: Vector3<f32>,   // specular_color; zeros for the Normal and UV materials
+    pub shininess: f32,
+    pub alpha: f64,               // the SceneNode's: alpha, refl_mix, refl_atenuation, refr_coeff (src/scene_node.rs:8-19)
+    pub refl_mix: f64,
+    pub refl_atenuation: f64,
+    pub refr_coeff: f64,
+}
+
 /// A scene resident on ONE GPU (the calling thread's current HIP device).
 pub struct GpuScene {
     raw: *mut NraysScene,
@@ -574,6 +586,38 @@ impl GpuScene {
     pub unsafe fn shade_points_device(&self, n: u32, points: *const f64, normals: *const f64, view_dirs: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32,
                                       keys: *const u64, out_rgba: *mut f32, hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_shade_points_device(self.raw, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// The terms of the points' materials without the lights, in one call (nrays_material_points, blocking): per point
+    /// `scene.nodes()[p.node].material.ambiant(&p.point, &p.normal, &p.uvs)` (src/material.rs:7) as the reference's `Point4<f32>`, the diffuse reflectance
+    /// `diffuse_color.component_mul(tex_color)` (src/phong_material.rs:120-121), (specular_color, shininess), and the node's (alpha, refl_mix, refl_atenuation,
+    /// refr_coeff) as f64 — everything `Scene::trace` reads from a hit besides the lights.  Of a SurfacePoint only normal, uvs and node matter.  A node index
+    /// outside `scene.nodes()` gives zeros.
+    pub fn material_points(&self, points: &[SurfacePoint]) -> Result<Vec<MaterialTerms>, String> {
+        let n = points.len();
+        let (mut nm, mut uv, mut node, mut hf) = (Vec::with_capacity(3 * n), Vec::with_capacity(2 * n), Vec::with_capacity(n), Vec::with_capacity(n));
+        for s in points {
+            nm.extend_from_slice(&[s.normal.x, s.normal.y, s.normal.z]);
+            match s.uvs { Some(t) => { uv.extend_from_slice(&[t.x, t.y]); hf.push(3u32); } None => { uv.extend_from_slice(&[0.0, 0.0]); hf.push(1u32); } }
+            node.push(if s.node <= i32::max_value() as usize { s.node as i32 } else { -1 });
+        }
+        let (mut amb, mut dif, mut spec, mut nd) = (vec![0.0f32; 4 * n], vec![0.0f32; 3 * n], vec![0.0f32; 4 * n], vec![0.0f64; 4 * n]);
+        let rc = unsafe { nrays_material_points(self.raw, n as u32, nm.as_ptr(), uv.as_ptr(), node.as_ptr(), hf.as_ptr(), amb.as_mut_ptr(), dif.as_mut_ptr(), spec.as_mut_ptr(), nd.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| MaterialTerms { ambient: Point4::new(amb[4 * i], amb[4 * i + 1], amb[4 * i + 2], amb[4 * i + 3]),
+                                          diffuse: Vector3::new(dif[3 * i], dif[3 * i + 1], dif[3 * i + 2]),
+                                          specular: Vector3::new(spec[4 * i], spec[4 * i + 1], spec[4 * i + 2]), shininess: spec[4 * i + 3],
+                                          alpha: nd[4 * i], refl_mix: nd[4 * i + 1], refl_atenuation: nd[4 * i + 2], refr_coeff: nd[4 * i + 3] }).collect())
+    }
+
+    /// `material_points` for n points in DEVICE memory (nrays_material_points_device), enqueued on `hip_stream` without synchronisation: normals n x 3 f64 (may
+    /// be null when out_ambient is), uvs n x 2 f64 or null, nodes n i32 (what cast_rays_device wrote to out_node), hit_flags n u32 or null (its out_flags: bit 0
+    /// clear = skipped, bit 1 = the point carries a uv); out_ambient n x 4 f32, out_diffuse n x 3 f32, out_specular n x 4 f32, out_node n x 4 f64, each may be
+    /// null, not all.  Skipped points write zeros.
+    pub unsafe fn material_points_device(&self, n: u32, normals: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, out_ambient: *mut f32,
+                                         out_diffuse: *mut f32, out_specular: *mut f32, out_node: *mut f64, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_material_points_device(self.raw, n, normals, uvs, nodes, hit_flags, out_ambient, out_diffuse, out_specular, out_node, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 

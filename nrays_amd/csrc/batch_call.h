@@ -1,5 +1,5 @@
-// batch_call.h — the driver every caller-batch entry point runs through (batch_call.cpp; host only, no kernels).  A family — trace, intersects, cast, shade
-// (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, probe_depth, irradiance (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
+// batch_call.h — the driver every caller-batch entry point runs through (batch_call.cpp; host only, no kernels).  A family — trace, intersects, cast, shade,
+// material (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, probe_depth, irradiance (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
 // nrays_debug_cast_batch and nrays_debug_occlusion_rays — is four things of its own ("Adding a family on the C++ side"): its argument check (with the
 // n == 0 return, before any HIP call), its column table (batch_stage.h), its launch struct with a launch_if chain, and its chunk lambda.  The driver holds the rest once:
 //   batch_open    hipSetDevice, the handle's batch workspace, the family's own workspace (`ensure`), the staging arena, the stream — the caller's for the

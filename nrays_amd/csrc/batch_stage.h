@@ -84,6 +84,15 @@ inline int shade_columns(StageColumn* c, const double* points, const double* nor
     c[kShadeNodes] = stage_in(nodes, 4); c[kShadeHit] = stage_in(hit_flags, 4); c[kShadeKeys] = stage_in(keys, 8); c[kShadeOut] = stage_out(out_rgba, 16);
     return kShadeColumns;
 }
+// nrays_material_points*: the terms of the points' materials.  Every column but the nodes may be absent; ambient and specular are stored as one 16-byte vector.
+enum { kMatNormals, kMatUvs, kMatNodes, kMatHit, kMatAmbient, kMatDiffuse, kMatSpecular, kMatNode, kMatColumns };
+inline int material_columns(StageColumn* c, const double* normals, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags, float* out_ambient, float* out_diffuse,
+                            float* out_specular, double* out_node) {
+    c[kMatNormals] = stage_in(normals, 24); c[kMatUvs] = stage_in(uvs, 16); c[kMatNodes] = stage_in(nodes, 4); c[kMatHit] = stage_in(hit_flags, 4);
+    c[kMatAmbient] = stage_out(out_ambient, 16, 16); c[kMatDiffuse] = stage_out(out_diffuse, 12); c[kMatSpecular] = stage_out(out_specular, 16, 16);
+    c[kMatNode] = stage_out(out_node, 32, 16);
+    return kMatColumns;
+}
 // Points with a hemisphere of directions: the two tables and the points (nrays_debug_gather_order stages these alone), then what each family adds.
 enum { kPointDirs, kPointRotations, kPointPoints, kPointNormals, kPointHit, kPointKeys, kPointColumns };
 inline int point_columns(StageColumn* c, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, const double* points, const double* normals,

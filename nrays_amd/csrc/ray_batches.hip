@@ -1,6 +1,6 @@
 // ray_batches.hip — the caller-batch families that take rays or surface points as arrays, each a check, a column table (batch_stage.h) and a chunk launch run by
-// the driver of batch_call.h: nrays_trace_rays* (+ _ex), nrays_intersects_rays_device (+ _ex), nrays_cast_rays*, nrays_shade_points*; their kernels are the templates of
-// ray_batch_kernel.h, instantiated here, as is k_occlusion_points for point_batches.hip (launch_occlusion_points).  Also two probes with kernels of their own:
+// the driver of batch_call.h: nrays_trace_rays* (+ _ex), nrays_intersects_rays_device (+ _ex), nrays_cast_rays*, nrays_shade_points*, nrays_material_points*
+// (k_material_points of material_points_kernel.h); their kernels are the templates of ray_batch_kernel.h, instantiated here, as is k_occlusion_points for point_batches.hip (launch_occlusion_points).  Also two probes with kernels of their own:
 // nrays_debug_cast_batch (k_cast_batch; through the driver) and nrays_debug_box_cull (k_box_cull; no scene handle, buffers of its own).
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include "../../include/nrays_abi.h"
 #include "batch_call.h"
 #include "bounce.h"
+#include "material_points_kernel.h"
 #include "ray_batch_kernel.h"
 #include "scene_handle.h"
 
@@ -146,6 +147,11 @@ static bool launch_if(const ShadeLaunch& a, bool stats) {
     return true;
 }
 static bool launch_shade_points(const ShadeLaunch& a, bool stats) { return launch_if<false>(a, stats) || launch_if<true>(a, stats); }
+// (one form: which outputs are stored is a null test in the kernel, uniform over the grid)
+void launch_material_points(const MaterialLaunch& a) {
+    hipLaunchKernelGGL(k_material_points, dim3(a.grid), dim3(kBlock), 0, a.stream, a.shade, a.n, a.num_nodes, a.normals, a.uvs, a.nodes, a.hit_flags, a.out_ambient, a.out_diffuse,
+                       a.out_specular, a.out_node);
+}
 // k_occlusion_points (nrays_occlusion_points*, point_batches.hip) is instantiated in this unit, beside the other traversal kernels: in a unit without them the compiler
 // allocates and schedules its LP = 3 and 6 forms differently (profiles/README.md, batch_driver_kres_*).  feat: kFeatMesh or kFeatAll; lp: 0, 3 or 6.
 template <int FEAT, int LP>
@@ -256,6 +262,25 @@ static int shade_points_impl(NraysScene* sc, uint32_t n, const double* points, c
     return batch_run(sc, staged, stream, cols, kShadeColumns, n, kTraceChunk, "shade batch", launch);
 }
 
+// ---- nrays_material_points*: the terms of the points' materials without the lights (material.rs:7, phong_material.rs:39-70 and 120-121; material_points_kernel.h) -------
+static int material_points_impl(NraysScene* sc, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags, float* out_ambient,
+                                float* out_diffuse, float* out_specular, double* out_node, uint32_t flags, bool staged, hipStream_t stream) {
+    if (!sc || !nodes) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (!out_ambient && !out_diffuse && !out_specular && !out_node) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_material_points: no output (every out_ pointer is null)");
+    if (out_ambient && !normals) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_material_points: out_ambient needs normals");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_material_points: flags must be 0");
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kMatColumns];
+    material_columns(cols, normals, uvs, nodes, hit_flags, out_ambient, out_diffuse, out_specular, out_node);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const MaterialLaunch a{launch_grid(nc), b.stream, sc->facts.d.shade, nc, (uint32_t)sc->facts.host.shade.size(), (const double*)c[kMatNormals], (const double*)c[kMatUvs],
+                               (const int32_t*)c[kMatNodes], (const uint32_t*)c[kMatHit], (float*)c[kMatAmbient], (float*)c[kMatDiffuse], (float*)c[kMatSpecular], (double*)c[kMatNode]};
+        launch_material_points(a);
+        return launch_status("k_material_points");
+    };
+    return batch_run(sc, staged, stream, cols, kMatColumns, n, kTraceChunk, "material batch", launch);
+}
+
 } // namespace nrays
 
 using namespace nrays;
@@ -354,6 +379,14 @@ int nrays_shade_points_device(NraysScene* sc, uint32_t n, const double* points, 
 int nrays_shade_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const double* view_dirs, const double* uvs, const int32_t* nodes,
                        const uint32_t* hit_flags, const uint64_t* keys, float* out_rgba, uint32_t flags) {
     return shade_points_impl(sc, n, points, normals, view_dirs, uvs, nodes, hit_flags, keys, out_rgba, flags, true, nullptr);
+}
+int nrays_material_points_device(NraysScene* sc, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags, float* out_ambient,
+                                 float* out_diffuse, float* out_specular, double* out_node, uint32_t flags, void* hip_stream) {
+    return material_points_impl(sc, n, normals, uvs, nodes, hit_flags, out_ambient, out_diffuse, out_specular, out_node, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_material_points(NraysScene* sc, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes, const uint32_t* hit_flags, float* out_ambient,
+                          float* out_diffuse, float* out_specular, double* out_node, uint32_t flags) {
+    return material_points_impl(sc, n, normals, uvs, nodes, hit_flags, out_ambient, out_diffuse, out_specular, out_node, flags, true, nullptr);
 }
 
 } // extern "C"

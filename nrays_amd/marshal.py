@@ -336,6 +336,41 @@ SurfaceTexels = collections.namedtuple("SurfaceTexels", ("points",) + TEXEL_OUTP
 TEXELS_MAX_SIDE, TEXELS_MAX_POINTS = 16384, 1 << 24
 
 
+MATERIAL_OUTPUTS = ("ambient", "diffuse", "specular", "node")  # the outputs of material_points, in the order of nrays_material_points_device's arguments
+MaterialTerms = collections.namedtuple("MaterialTerms", MATERIAL_OUTPUTS)
+MaterialTerms.__doc__ = """What material_points returns: `ambient` (n, 4) float32, Material::ambiant; `diffuse` (n, 3) float32, kd * texture; `specular` (n, 4) float32, (ks, shininess);
+`node` (n, 4) float64, the node's (alpha, refl_mix, refl_atenuation, refr_coeff).  None for what was not asked for."""
+
+
+def _material_args(node_ids, normals, uvs, hit_flags, want):
+    """The checks material_points and material_points_ref share: (n, want as a tuple)."""
+    if node_ids is None:
+        raise ValueError("nodes is required")
+    if len(node_ids.shape) != 1:
+        raise ValueError("nodes must have shape (n,), got %s" % (tuple(node_ids.shape),))
+    if not _is_tensor(node_ids) and not np.issubdtype(np.asarray(node_ids).dtype, np.integer):
+        raise ValueError("nodes must be integers, got %s" % np.asarray(node_ids).dtype)
+    n = int(node_ids.shape[0])
+    if n >= 1 << 32:
+        raise ValueError("at most 2^32 - 1 points per call")
+    if isinstance(want, str):
+        raise ValueError("want must be a sequence of names, got %r" % (want,))
+    want = tuple(want)
+    for name in want:
+        if name not in MATERIAL_OUTPUTS:
+            raise ValueError("want: unknown output %r (one of %s)" % (name, ", ".join(MATERIAL_OUTPUTS)))
+    if not want:
+        raise ValueError("want: at least one of %s" % ", ".join(MATERIAL_OUTPUTS))
+    if normals is None and "ambient" in want:
+        raise ValueError("normals is required for the ambient term (the Normal material reads it)")
+    if normals is not None:
+        _check_rows("normals", normals, n, 3)
+    if uvs is not None:
+        _check_rows("uvs", uvs, n, 2)
+    _check_vec("hit_flags", hit_flags, n)
+    return n, want
+
+
 def _texel_lattice(width, height):
     width, height = int(width), int(height)
     if not (1 <= width <= TEXELS_MAX_SIDE and 1 <= height <= TEXELS_MAX_SIDE and width * height <= TEXELS_MAX_POINTS):

@@ -5,8 +5,8 @@ import math
 import numpy as np
 
 from . import abi
-from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
-                      _depth_res, _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
+from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, MaterialTerms, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
+                      _depth_res, _material_args, _np_ints, _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
 
 SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
 SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
@@ -548,6 +548,69 @@ def lightmap_sample_ref(texels, u, v, interp=Interpolation.Bilinear, overflow=Ov
         ui = ul * (F(1) - sx) + ur * sx
         di = dl * (F(1) - sx) + dr * sx
         return np.ascontiguousarray((ui * sy + di * (F(1) - sy)).astype(F))
+
+
+def _texture_sample_ref(tex, u, v):
+    """Texture2d::sample of a scene's Texture2d at float64 (u, v): lightmap_sample_ref on its texels, an RGBA8 channel being `u8 as f32 / 255.0`, one correctly rounded
+    float32 division."""
+    px = tex.data.pixels
+    if px.dtype == np.uint8:
+        px = px.astype(np.float32) / np.float32(255.0)
+    return lightmap_sample_ref(px, u, v, tex.interpol, tex.overflow)
+
+
+def material_points_ref(nodes, node_ids, normals=None, uvs=None, hit_flags=None, want=("ambient", "diffuse")):
+    """The numpy mirror of nrays_material_points*, bit for bit (include/nrays_abi.h: nrays_material_points_device), over `nodes`, the SceneNode list a Scene is made
+    from: per point the terms of the material of nodes[node_ids[i]] — Material::ambiant, kd * texture, (ks, shininess) — and the node's own constants.  Every float32
+    step is a numpy float32 operation of its own, in the header's order; the texture sample is lightmap_sample_ref.  `node_ids` (n,) integers, `normals` (n, 3),
+    `uvs` (n, 2) or None, `hit_flags` (n,) integers or None, `want` as for material_points.  Returns MaterialTerms of numpy arrays, None for what was not asked for."""
+    if any(_is_tensor(a) for a in (node_ids, normals, uvs, hit_flags)):
+        raise ValueError("material_points_ref takes numpy arrays")
+    node_ids = np.asarray(node_ids)
+    n, want = _material_args(node_ids, None if normals is None else np.asarray(normals), None if uvs is None else np.asarray(uvs),
+                             None if hit_flags is None else np.asarray(hit_flags), want)
+    ids = _np_ints("nodes", node_ids, np.int32).astype(np.int64)
+    F = np.float32
+    hf = np.full(n, 3, np.uint64) if hit_flags is None else np.asarray(hit_flags).astype(np.uint64)
+    live = ((hf & np.uint64(1)) != 0) & (ids >= 0) & (ids < len(nodes))
+    has_uv = ((hf & np.uint64(2)) != 0) if uvs is not None else np.zeros(n, bool)
+    uv = None if uvs is None else _np_floats("uvs", uvs, np.float64)
+    nm = None if normals is None else _np_floats("normals", normals, np.float64)
+    amb, dif, spec, nd = np.zeros((n, 4), F), np.zeros((n, 3), F), np.zeros((n, 4), F), np.zeros((n, 4), np.float64)
+    with np.errstate(all="ignore"):
+        for k in np.unique(ids[live]):
+            node, at = nodes[int(k)], live & (ids == k)
+            m = node.material
+            nd[at] = (float(F(node.alpha)), float(F(node.refl_mix)), float(F(node.refl_atenuation)), node.refr_coeff)
+            if m.kind == abi.MAT_NORMAL:
+                if "ambient" in want:
+                    amb[at, :3] = (F(1.0) + nm[at].astype(F)) / F(2.0)
+                    amb[at, 3] = F(1.0)
+                continue
+            if m.kind == abi.MAT_UV:
+                with_uv = at & has_uv
+                if "ambient" in want and with_uv.any():
+                    amb[with_uv, :2] = uv[with_uv].astype(F)
+                    amb[with_uv, 3] = F(1.0)
+                continue
+            ka, kd = np.asarray(m.ambiant_color, F), np.asarray(m.diffuse_color, F)
+            spec[at] = np.asarray(m.specular_color + (m.shininess,), F)
+            with_uv, without = at & has_uv, at & ~has_uv
+            tc = np.ones((int(with_uv.sum()), 4), F)
+            if with_uv.any() and m.texture is not None and ("ambient" in want or "diffuse" in want):
+                tc = _texture_sample_ref(m.texture, uv[with_uv, 0], uv[with_uv, 1])
+            dif[with_uv] = kd[None, :] * tc[:, :3]
+            dif[without] = kd * F(1.0)
+            if "ambient" in want:
+                w = np.ones(len(tc), F)
+                if with_uv.any() and m.alpha is not None:
+                    w = _texture_sample_ref(m.alpha, uv[with_uv, 0], uv[with_uv, 1])[:, 3]
+                amb[with_uv, :3] = ka[None, :] * tc[:, :3]
+                amb[with_uv, 3] = F(1.0) * w
+                amb[without, :3] = ka
+                amb[without, 3] = F(1.0)
+    out = dict(ambient=amb, diffuse=dif, specular=spec, node=nd)
+    return MaterialTerms(*(out[name] if name in want else None for name in MaterialTerms._fields))
 
 
 FILTER_TAPS = (1, 4, 6, 4, 1)  # the B3 spline; a tap's kernel weight is the product of two of them, 1 .. 36

@@ -20,11 +20,11 @@ import math
 import numpy as np
 
 from . import abi
-from .marshal import (CURRENT, F32, F64, I32, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
-                      Overflow, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats,
+from .marshal import (CURRENT, F32, F64, I32, MATERIAL_OUTPUTS, MaterialTerms, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
+                      Overflow, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _material_args, _n_of, _np_floats,
                       _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice, np_ptr, upload)
 from .restated import (FILTER_TAPS, SALT_GATHER, SALT_OCCLUSION, SH_COSINE_LOBE, SH_K, _rng_hash, _rng_mix, _sh_terms, _texel_edge, camera_rays, dilate_texels_ref,  # noqa: F401
-                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
+                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, material_points_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
                        sphere_dirs, surface_texels_ref, texel_coords)
 
 
@@ -359,6 +359,22 @@ class BatchCalls:
         """The direct lighting of caller-supplied surface points of this scene: shade_points(self, ...)."""
         return shade_points(self, points, normals, view_dirs, nodes, uvs, hit_flags, keys)
 
+    def material_points(self, nodes, normals=None, uvs=None, hit_flags=None, want=("ambient", "diffuse")):
+        """The material terms at caller-supplied surface points of this scene, without the lights: material_points(self, ...)."""
+        return material_points(self, nodes, normals, uvs, hit_flags, want)
+
+    def material_hits(self, hits, want=("ambient", "diffuse")):
+        """The material terms at the closest hits of caller-supplied rays on this scene: material_hits(self, hits, ...)."""
+        return material_hits(self, hits, want)
+
+    def texel_albedo(self, node, width, height, flip_normals=False, device=None):
+        """The diffuse reflectance of mesh node `node` at a light map's texels, the albedo bake_bounces takes: texel_albedo(self, node, ...)."""
+        return texel_albedo(self, node, width, height, flip_normals, device)
+
+    def indirect_points(self, points, normals, nodes, grid, uvs=None, hit_flags=None, facing=False, visibility=None):
+        """The diffuse light a probe grid gives surface points of this scene: indirect_points(self, ...)."""
+        return indirect_points(self, points, normals, nodes, grid, uvs, hit_flags, facing, visibility)
+
     def occlusion_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, hit_flags=None, keys=None):
         """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
@@ -690,6 +706,70 @@ def shade_hits(scene, origins, dirs, hits, keys=None):
     step = dirs * toi[:, None]
     points = origins + step
     return shade_points(scene, points, hits.normal, dirs, hits.node, uvs=hits.uv, hit_flags=hits.flags, keys=keys)
+
+
+# ---- the material terms at caller-supplied points, without the lights (include/nrays_abi.h: nrays_material_points_device) -----------------------------
+
+def material_points(scene, nodes, normals=None, uvs=None, hit_flags=None, want=("ambient", "diffuse")):
+    """The terms of the materials at n caller-supplied surface points WITHOUT the lights, through nrays_material_points_device / nrays_material_points: what
+    shade_points folds into one colour, handed out.  Per point, with the material of scene node nodes[i]:
+      ambient  (n, 4) float32: Material::ambiant (src/material.rs:7) — ka times the colour texture's sample, the opacity map's sample (or 1) in w; the Normal
+               and UV materials' colour;
+      diffuse  (n, 3) float32: kd times the colour texture's sample — the diffuse reflectance (albedo) of the point; zeros for the Normal and UV materials;
+      specular (n, 4) float32: (ks, shininess); zeros for the Normal and UV materials;
+      node     (n, 4) float64: the node's (alpha, refl_mix, refl_atenuation, refr_coeff), the constants Scene::trace reads at a hit.
+    `want`: which of them to compute into memory (at least one); the colour texture is sampled once for ambient and diffuse together.  With closest_hits()
+    this is all an integrator of the caller's own needs on top of the library's traversal.  Also `scene.material_points(...)` on Scene and FileScene;
+    material_hits() feeds it from closest_hits(); material_points_ref() restates it bit for bit.
+    `nodes` (n,) integers.  `normals` (n, 3), required for "ambient" (the Normal material reads it), else optional.  `uvs` (n, 2) or None (no point has a uv).
+    `hit_flags` (n,) integers or None: the flag words of closest_hits — bit 0 clear: the point is skipped, bit 1: it carries a uv; None: every point is live
+    and has a uv exactly when `uvs` is given.  A skipped point — flag bit 0 clear, node < 0 or >= the scene's node count — is zeros in every output.
+    Returns MaterialTerms(ambient, diffuse, specular, node), None for what was not asked for.
+    numpy arrays -> nrays_material_points (blocking), numpy arrays.  torch tensors on the scene's GPU (nodes int32; normals / uvs float64; hit_flags int32 /
+    uint32) -> nrays_material_points_device on torch's current stream, tensors."""
+    n, want = _material_args(nodes, normals, uvs, hit_flags, want)
+    b = Batch((("nodes", nodes, I32), ("normals", normals, F64), ("uvs", uvs, F64), ("hit_flags", hit_flags, U32)),
+              (("ambient", (n, 4), F32, "ambient" in want), ("diffuse", (n, 3), F32, "diffuse" in want), ("specular", (n, 4), F32, "specular" in want),
+               ("node", (n, 4), F64, "node" in want)))
+    b.call(scene, "nrays_material_points", n, b.pin[1], b.pin[2], b.pin[0], b.pin[3], *b.pout, 0)
+    return MaterialTerms(*b.outs)
+
+
+def material_hits(scene, hits, want=("ambient", "diffuse")):
+    """The material terms at the closest hits of caller-supplied rays: material_points() at `hits = closest_hits(scene, origins, dirs)` (a CastHits with uv and
+    flags, and normal when "ambient" is wanted).  Misses come back as zeros.  MaterialTerms, numpy or torch as the hits."""
+    for name in ("uv", "flags") + (("normal",) if not isinstance(want, str) and "ambient" in tuple(want) else ()):
+        if getattr(hits, name) is None:
+            raise ValueError("material_hits: hits.%s is None (closest_hits must be asked for it)" % name)
+    return material_points(scene, hits.node, hits.normal, hits.uv, hits.flags, want)
+
+
+def texel_albedo(scene, node, width, height, flip_normals=False, device=None):
+    """The diffuse reflectance of TriMesh node `node` at the texels of a width x height light map — the `albedo` array bake_bounces() takes —, (height, width, 3)
+    float32 in NraysTexture row order (row 0 = the bottom row): material_points(want=("diffuse",)) on surface_texels() on the default lattice, the one
+    Texture2d::sample reads, two calls on one stream.  Texels no triangle covers are zeros.  `flip_normals`, `device`: as for surface_texels (with a torch device
+    the array stays on the GPU as a tensor).  Also `scene.texel_albedo(node, ...)` on Scene and FileScene."""
+    width, height = _texel_lattice(width, height)
+    tx = surface_texels(scene, node, width, height, False, flip_normals, want=("uv", "node"), device=device)
+    return material_points(scene, tx.node, None, tx.uv, tx.flags, want=("diffuse",)).diffuse.reshape(height, width, 3)
+
+
+INV_PI_F32 = float(np.float32(0.3183098861837907))  # the float32 nearest 1 / pi
+
+
+def indirect_points(scene, points, normals, nodes, grid, uvs=None, hit_flags=None, facing=False, visibility=None):
+    """The diffuse light a probe grid gives n surface points, (n, 3) float32: the irradiance E = irradiance_points(points, normals, grid, facing, hit_flags,
+    visibility=visibility) reflected by the surface's own diffuse reflectance d = material_points(nodes, uvs=uvs, hit_flags=hit_flags, want=("diffuse",)) —
+    a Lambertian surface's radiance, in float32, each product rounded: (d * E) * float32(0.3183098861837907).  Two calls on one stream and two element-wise
+    products; the numpy and the torch form are the same expression.  A skipped point (flag bit 0 clear, node outside the scene) gives zeros.  Arguments as for
+    irradiance_points and material_points.  Also `scene.indirect_points(...)` on Scene and FileScene."""
+    n = _n_of(points, normals, ("points", "normals"))
+    if nodes is not None:
+        _check_vec("nodes", nodes, n)
+    _material_args(nodes, None, uvs, hit_flags, ("diffuse",))
+    E =irradiance_points(scene, points, normals, grid, facing, hit_flags, visibility=visibility)
+    d = material_points(scene, nodes, None, uvs, hit_flags, want=("diffuse",)).diffuse
+    return (d * E) * INV_PI_F32
 
 
 # ---- ambient occlusion at caller-supplied points: the hemisphere rays are built on the device (include/nrays_abi.h: NraysOcclusionParams) ----------
