@@ -186,6 +186,9 @@ struct Blas {
 #ifndef NR_PRESPLIT_MINGAIN_HAIRY
 #define NR_PRESPLIT_MINGAIN_HAIRY 0.02 // round 4, tools/build_sweep.py (profiles/r04_build_sweep.log): 0.05 -> 0.02: hairball 2.04 -> 1.95 ms (9.0 -> 6.1 triangle tests per ray, 1.5 -> 2.3 GB); below it the frame stays at 1.95 (the node loop, not the triangle tests, bounds it)
 #endif
+#ifndef NR_PRESPLIT_EXACT_BELOW
+#define NR_PRESPLIT_EXACT_BELOW 400000 // triangles up to which presplit() runs the heap on the whole mesh (tests/test_blas_cover.py builds with 512 to reach the threshold path)
+#endif
 // The exact procedure: pieces split in order of decreasing empty area until the budget is used up.  `tris` lists the
 // triangles taking part (all of them, or a sample); boxes[k] / owner[k] describe reference k (k < tris.size(): the
 // k-th listed triangle).  Returns the empty area of the last piece split (the threshold the budget amounts to), or
@@ -248,7 +251,7 @@ static bool presplit(const std::vector<TriRec>& recs, std::vector<PrimBounds>& r
     for (size_t i = 0; i < n; ++i) total_area += box_half_area(refs_box[i]);
     for (size_t i = 0; i < n; ++i) { ClipPoly p; tri_poly(recs[i], p); total_tri2 += poly_area2(p); }
     const PresplitPlan plan = presplit_plan(total_area, total_tri2, n, NR_PRESPLIT_BUDGET, NR_PRESPLIT_BUDGET_HAIRY, NR_PRESPLIT_MINGAIN, NR_PRESPLIT_MINGAIN_HAIRY, NR_PRESPLIT_HAIRY);
-    constexpr size_t kExactBelow = 400000; // triangles: below this the heap runs on the whole mesh
+    constexpr size_t kExactBelow = NR_PRESPLIT_EXACT_BELOW; // triangles: below this the heap runs on the whole mesh
     if (n <= kExactBelow) {
         std::vector<uint32_t> all(n);
         for (size_t i = 0; i < n; ++i) all[i] = (uint32_t)i;
