@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points / nrays_nearest_points_device / nrays_nearest_points / nrays_debug_nearest_bound.  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -802,6 +802,70 @@ int nrays_material_points_device(NraysScene* scene, uint32_t n, const double* no
 int nrays_material_points(NraysScene* scene, uint32_t n, const double* normals, const double* uvs, const int32_t* nodes,
                           const uint32_t* hit_flags, float* out_ambient, float* out_diffuse, float* out_specular, double* out_node, uint32_t flags);
 
+/* The NEAREST SURFACE to n caller-supplied points: how far it is, where, and on which node and triangle — ncollide's PointQuery beside the RayCast the other
+ * families restate.  The first six found outputs carry the names and layouts of nrays_cast_rays_device, so they pass unfiltered into nrays_shade_points*,
+ * nrays_material_points*, nrays_occlusion_points*, nrays_gather_*_points* and nrays_irradiance_points* (out_point -> points, out_node -> nodes, out_flags -> hit_flags).
+ * The result is defined by this text (Python: nearest_points_ref restates it bit for bit), never by the order the device visits anything in.  Every operation is an
+ * f64 + - * / sqrt or comparison, evaluated left to right as written, nothing fused.  dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; a vector expression is applied
+ * per component.
+ *   candidates     every scene node.  For node k with rotation R (row-major, local -> world) and translation T, the query in local space is
+ *                  pl = (R00 v.x + R10 v.y) + R20 v.z, ... (the transposed rows) with v = p - T; pl = p - T for a node whose axis_angle is zero; pl = p when the
+ *                  translation is zero too.
+ *   closest point  ql, in local space, by shape:
+ *     TRIMESH      per triangle with corners a, b, c (f32 widened to f64), Ericson, Real-Time Collision Detection 5.1.5, tested in this order:
+ *                    ab = b - a, ac = c - a, ap = pl - a, d1 = dot(ab, ap), d2 = dot(ac, ap);     d1 <= 0 and d2 <= 0:            (v, w) = (0, 0), ql = a
+ *                    bp = pl - b, d3 = dot(ab, bp), d4 = dot(ac, bp);                             d3 >= 0 and d4 <= d3:           (v, w) = (1, 0), ql = b
+ *                    vc = d1 d4 - d3 d2;                        vc <= 0 and d1 >= 0 and d3 <= 0:  v = d1 / (d1 - d3), w = 0, ql = a + ab v
+ *                    cp = pl - c, d5 = dot(ab, cp), d6 = dot(ac, cp);                             d6 >= 0 and d5 <= d6:           (v, w) = (0, 1), ql = c
+ *                    vb = d5 d2 - d1 d6;                        vb <= 0 and d2 >= 0 and d6 <= 0:  w = d2 / (d2 - d6), v = 0, ql = a + ac w
+ *                    va = d3 d6 - d5 d4;       va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0:         w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w, ql = b + (c - b) w
+ *                    otherwise den = (va + vb) + vc, v = vb / den, w = vc / den, ql = (a + ab v) + ac w, a candidate only if v >= 0, w >= 0 and (1 - v) - w >= 0.
+ *                    One step beyond the book, for triangles whose corners are collinear (va, vb, vc are then rounding noise, and so were the tests above): in this
+ *                    last branch the candidate competes with the three edge projections t1 = d1 / (d1 - d3) on AB, t2 = d2 / (d2 - d6) on AC,
+ *                    t3 = (d4 - d3) / ((d4 - d3) + (d5 - d6)) on BC, each clamped as t >= 0 ? (t <= 1 ? t : 1) : 0, with ql = a + ab t1, a + ac t2, b + (c - b) t3
+ *                    and (v, w) = (t1, 0), (0, t2), (1 - t3, t3); the smallest key wins, a later one only with a strictly smaller key.  Inside a real triangle
+ *                    the interior candidate wins; on a collinear one an edge holds the true closest point.
+ *     BALL         len = sqrt(dot(pl, pl)); ql = pl (r / len), nl = pl / len; len == 0: ql = (r, 0, 0), nl = (1, 0, 0).  Behind: len < r.
+ *     CUBOID       g_k = h_k - |pl_k|.  All g_k >= 0 (inside or on it): the axis with the smallest g_k, the lowest among equals, moves to its face:
+ *                  ql_k = copysign(h_k, pl_k), nl = copysign(1, pl_k) e_k; behind: all g_k > 0.  Otherwise ql_k = pl_k < -h_k ? -h_k : (pl_k > h_k ? h_k : pl_k)
+ *                  and nl = (pl - ql) / sqrt(d2): at an edge or a corner the direction from that feature to the point.
+ *     PLANE        the half-space's boundary: t = dot(nrm, pl), ql = pl - nrm t; behind: t < 0; nl = behind ? -nrm : nrm (the side cast_plane reports).
+ *     CYLINDER, CAPSULE, CONE   surfaces of revolution about local y, the solids the casts intersect (the cone's apex at y = +hh, its base of radius r at -hh).
+ *                  rho = sqrt(pl.x pl.x + pl.z pl.z), y = pl.y, (cx, cz) = rho == 0 ? (1, 0) : (pl.x / rho, pl.z / rho); the 2-D closest point (qr, qy) and
+ *                  normal (nr, ny) lift to ql = (qr cx, qy, qr cz), nl = (nr cx, ny, nr cz).  Where no normal is named, (nr, ny) = (rho - qr, y - qy) / sqrt of their
+ *                  squares' sum: the direction from the feature (a rim, the apex) to the point.
+ *       CYLINDER   gs = r - rho, gc = hh - |y|.  Both >= 0: gs <= gc ? (qr, qy) = (r, y), normal (1, 0) : (qr, qy) = (rho, copysign(hh, y)), normal
+ *                  (0, copysign(1, y)); behind: both > 0.  Otherwise qr = rho > r ? r : rho, qy = y clamped to [-hh, hh].
+ *       CAPSULE    yc = y clamped to [-hh, hh], ey = y - yc, len = sqrt(rho rho + ey ey); normal (rho / len, ey / len), or (1, 0) for len == 0;
+ *                  (qr, qy) = (nr r, yc + ny r); behind: len < r.
+ *       CONE       up = y + hh, h2 = 2 hh.  Base: br = rho > r ? r : rho, db = (rho - br)^2 + up up.  Slant: t = (((rho - r) * -r + up h2) / (r r + h2 h2))
+ *                  clamped to [0, 1], (sr, sy) = (r + -r t, -hh + h2 t), ds = (rho - sr)^2 + (y - sy)^2.  db <= ds: (qr, qy) = (br, -hh), else (sr, sy).
+ *                  f = (rho - r) h2 + up r.  up >= 0 and f <= 0 (inside or on it): normal (0, -1) for the base, (h2, r) / sqrt(h2 h2 + r r) for the slant;
+ *                  behind: up > 0 and f < 0.
+ *   key            d2 = (dx dx + dy dy) + dz dz with dl = pl - ql, in local space.
+ *   winner         the candidate with the smallest d2; among equal d2 the smallest node index, then the smallest triangle index in NraysMesh::indices (the leaf
+ *                  references of a pre-split triangle are one triangle).
+ *   max_dist       n doubles, or NULL = unbounded; +inf allowed; NaN or negative = a miss.  Found iff sqrt(d2) <= max_dist[i]: the unbounded answer, or a miss.
+ *   hit_flags      n words or NULL; bit 0 clear: the point is skipped — the miss record, its coordinates are not read.
+ *   found record   out_dist = sqrt(d2); out_point = R ql + T row-wise, ((R00 q.x + R01 q.y) + R02 q.z) + T.x, ..., = ql + T without a rotation, = ql without either;
+ *                  out_node; out_prim = the triangle's index, -1 for an analytic shape; out_normal = the normal SceneNode::cast gives a ray arriving at that point
+ *                  from p's side, in world space (R nl row-wise; nl without a rotation): for a triangle cr = cross(b - a, c - a), nl = cr / sqrt(dot(cr, cr)),
+ *                  negated iff dot(pl - a, cr) < 0 (that is "behind"); for an analytic shape the nl above.  out_uv: for a mesh with uvs
+ *                  (ua b0 + ub v) + uc w per coordinate with b0 = (1 - v) - w; for a ball the ball cast's uv of the world normal n,
+ *                  (0.5 + atan2(n.z, n.x) / (2 pi), 0.5 - asin(n.y) / pi) — the one place outside + - * / sqrt: equal up to the math library; otherwise zeros.
+ *                  out_flags: bit 0 = found, bit 1 = the record carries a uv, bit 2 = p lies behind the surface (the back of the triangle's winding, inside a
+ *                  closed analytic shape, under a plane).
+ *   miss record    out_dist = +inf, out_node = -1, out_prim = -1, zeros elsewhere, flags 0.  An empty scene gives a miss for every point.
+ *   out_dist and out_node are required; the other five outputs may each be NULL (no store).  flags must be 0.
+ * NULL scene / points / out_dist / out_node, or any flag bit -> NRAYS_ERR_BAD_ARG before any HIP call.  n == 0 -> NRAYS_OK without work.  Otherwise the contract of
+ * nrays_cast_rays_device: every pointer device memory on the scene's device, chunks of at most 2^22 points enqueued on `hip_stream` behind the handle's previous
+ * work, no read-back and no synchronisation; the handle's render statistics and per-camera scheduling state are untouched. */
+int nrays_nearest_points_device(NraysScene* scene, uint32_t n, const double* points, const double* max_dist, const uint32_t* hit_flags, double* out_dist, int32_t* out_node,
+                                double* out_point, double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream);
+/* Same, every pointer HOST memory.  Blocking. */
+int nrays_nearest_points(NraysScene* scene, uint32_t n, const double* points, const double* max_dist, const uint32_t* hit_flags, double* out_dist, int32_t* out_node,
+                         double* out_point, double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags);
+
 /* The surface of TriMesh node `node` at the points of a width x height lattice in its uv space — a light map's texels: for every lattice point
  * the triangle that owns it, the world position and normal there.  This is the baker's first step, in front of nrays_shade_points_device and
  * nrays_occlusion_points_device, which take the arrays written here unfiltered (out_node -> nodes, out_flags -> hit_flags, out_uv -> uvs); no
@@ -997,6 +1061,11 @@ int nrays_debug_cast_batch(NraysScene* scene, uint32_t mode, uint32_t n, const d
  * Blocking; runs on the current device's default stream. */
 int nrays_debug_box_cull(uint32_t mode, uint32_t n, const double* origins, const double* dirs, const double* best, const float* boxes,
                          const uint32_t* slots, float* keys, uint32_t* bits, float* inv32);
+
+/* Probe of the nearest-surface walk's box bound ALONE (no scene handle): the product's device function on `n` points x `boxes` boxes.  points n x 3 doubles;
+ * box_bounds boxes x 6 doubles {min x, y, z, max x, y, z}, narrowed to f32 as a BVH node holds them; out[i * boxes + j] = a lower bound of the exact squared
+ * distance from point i to box j (Python: nearest_box_bound_ref, bit for bit).  All HOST memory.  Blocking; runs on the current device's default stream. */
+int nrays_debug_nearest_bound(uint32_t n, uint32_t boxes, const double* points, const double* box_bounds, double* out);
 
 /* World AABB of scene node `node` as the device holds it: geometry.bounding_volume(&transform) of src/scene_node.rs:41 in the
  * reference's arithmetic; the kernels apply ncollide's exact ray / AABB test to it for every accepted hit (the reference only casts

@@ -368,6 +368,17 @@ pub struct MaterialTerms {
     pub refr_coeff: f64,
 }
 
+/// What `GpuScene::nearest_points` returns for one query point whose nearest surface lies within its bound: ncollide's PointQuery beside the RayCast.
+pub struct NearestSurface {
+    pub dist: f64,                // the distance from the query point to `point`
+    pub node: usize,              // index into scene.nodes()
+    pub point: Point3<f64>,       // the nearest surface point, in world space
+    pub normal: Vector3<f64>,     // the normal there, facing the query point
+    pub uvs: Option<Point2<f64>>,
+    pub prim: Option<usize>,      // the triangle's index in its mesh; None for an analytic shape
+    pub behind: bool,             // the query point lies behind the surface: the back of the triangle's winding, inside a closed shape, under a plane
+}
+
 /// A scene resident on ONE GPU (the calling thread's current HIP device).
 pub struct GpuScene {
     raw: *mut NraysScene,
@@ -618,6 +629,33 @@ impl GpuScene {
     pub unsafe fn material_points_device(&self, n: u32, normals: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, out_ambient: *mut f32,
                                          out_diffuse: *mut f32, out_specular: *mut f32, out_node: *mut f64, hip_stream: *mut c_void) -> Result<(), String> {
         if nrays_material_points_device(self.raw, n, normals, uvs, nodes, hit_flags, out_ambient, out_diffuse, out_specular, out_node, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
+    /// The nearest surface to caller-supplied points (nrays_nearest_points, blocking): per point the closest point over every node of the scene — triangles by
+    /// Ericson's closest point, the analytic shapes in closed form —, None where nothing lies within `max_dist` (None: unbounded).  Defined bit for bit in
+    /// include/nrays_abi.h; ties go to the smaller node, then the smaller triangle.  A `SurfacePoint` for `shade_points` / `material_points` follows from a result
+    /// field by field.
+    pub fn nearest_points(&self, points: &[Point3<f64>], max_dist: Option<f64>) -> Result<Vec<Option<NearestSurface>>, String> {
+        let n = points.len();
+        let mut p = Vec::with_capacity(3 * n);
+        for q in points { p.extend_from_slice(&[q.x, q.y, q.z]); }
+        let md: Option<Vec<f64>> = max_dist.map(|m| vec![m; n]);
+        let (mut dist, mut node, mut pt, mut nm, mut uv, mut prim, mut fl) = (vec![0.0f64; n], vec![0i32; n], vec![0.0f64; 3 * n], vec![0.0f64; 3 * n], vec![0.0f64; 2 * n], vec![0i32; n], vec![0u32; n]);
+        let rc = unsafe { nrays_nearest_points(self.raw, n as u32, p.as_ptr(), md.as_ref().map_or(ptr::null(), |m| m.as_ptr()), ptr::null(), dist.as_mut_ptr(), node.as_mut_ptr(), pt.as_mut_ptr(),
+                                               nm.as_mut_ptr(), uv.as_mut_ptr(), prim.as_mut_ptr(), fl.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| if fl[i] & 1 == 0 { None } else { Some(NearestSurface {
+            dist: dist[i], node: node[i] as usize, point: Point3::new(pt[3 * i], pt[3 * i + 1], pt[3 * i + 2]), normal: Vector3::new(nm[3 * i], nm[3 * i + 1], nm[3 * i + 2]),
+            uvs: if fl[i] & 2 != 0 { Some(Point2::new(uv[2 * i], uv[2 * i + 1])) } else { None }, prim: if prim[i] >= 0 { Some(prim[i] as usize) } else { None }, behind: fl[i] & 4 != 0 }) }).collect())
+    }
+
+    /// `nearest_points` for n points in DEVICE memory (nrays_nearest_points_device), enqueued on `hip_stream` without synchronisation: points n x 3 f64, max_dist n f64
+    /// or null, hit_flags n u32 or null (bit 0 clear = skipped); out_dist n f64 and out_node n i32 required; out_point / out_normal n x 3 f64, out_uv n x 2 f64,
+    /// out_prim n i32, out_flags n u32 may each be null.  The outputs carry cast_rays_device's layouts and pass unfiltered into the calls at surface points.
+    pub unsafe fn nearest_points_device(&self, n: u32, points: *const f64, max_dist: *const f64, hit_flags: *const u32, out_dist: *mut f64, out_node: *mut i32, out_point: *mut f64,
+                                        out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_nearest_points_device(self.raw, n, points, max_dist, hit_flags, out_dist, out_node, out_point, out_normal, out_uv, out_prim, out_flags, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
         Ok(())
     }
 

@@ -351,6 +351,9 @@ extern "C" {
     pub fn nrays_irradiance_points_vis(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, grid: *const NraysIrradianceGrid, vis: *const NraysIrradianceVisibility, out_rgb: *mut f32, out_sh: *mut f32, out_weight: *mut f32, flags: u32) -> c_int;
     pub fn nrays_material_points_device(scene: *mut NraysScene, n: u32, normals: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, out_ambient: *mut f32, out_diffuse: *mut f32, out_specular: *mut f32, out_node: *mut f64, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_material_points(scene: *mut NraysScene, n: u32, normals: *const f64, uvs: *const f64, nodes: *const i32, hit_flags: *const u32, out_ambient: *mut f32, out_diffuse: *mut f32, out_specular: *mut f32, out_node: *mut f64, flags: u32) -> c_int;
+    pub fn nrays_nearest_points_device(scene: *mut NraysScene, n: u32, points: *const f64, max_dist: *const f64, hit_flags: *const u32, out_dist: *mut f64, out_node: *mut i32, out_point: *mut f64, out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_nearest_points(scene: *mut NraysScene, n: u32, points: *const f64, max_dist: *const f64, hit_flags: *const u32, out_dist: *mut f64, out_node: *mut i32, out_point: *mut f64, out_normal: *mut f64, out_uv: *mut f64, out_prim: *mut i32, out_flags: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_debug_nearest_bound(n: u32, boxes: u32, points: *const f64, box_bounds: *const f64, out: *mut f64) -> c_int;
     pub fn nrays_gather_maps_sh_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, bands: u32, out_sh: *mut f32, out_counts: *mut u32, depth: *const NraysGatherDepthSpec, out_moments: *mut f32, out_depth_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_gather_maps_sh_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherMapsParams, bands: u32, out_sh: *mut f32, out_counts: *mut u32, depth: *const NraysGatherDepthSpec, out_moments: *mut f32, out_depth_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32) -> c_int;
     pub fn nrays_probe_depth_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysProbeDepthParams, out_moments: *mut f32, out_counts: *mut u32, out_nearest: *mut f64, out_nearest_dir: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;

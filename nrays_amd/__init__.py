@@ -15,4 +15,5 @@ from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolat
                     Irradiance, ProbeGrid, bake_probe_grid, irradiance_points, irradiance_points_ref, probe_grid_positions,
                     ProbeDepth, ProbeVisibility, bake_probe_visibility, oct_texel, probe_depth, probe_depth_points, probe_depth_ref, probe_valid_words,
                     GatherMapsSh, bake_probe_grid_maps, gather_maps_probes, gather_maps_sh_points,
-                    MaterialTerms, indirect_points, material_hits, material_points, material_points_ref, texel_albedo)
+                    MaterialTerms, indirect_points, material_hits, material_points, material_points_ref, texel_albedo,
+                    NEAREST_BEHIND, NearestHits, ProbeClearance, nearest_bound_probe, nearest_box_bound_ref, nearest_points, nearest_points_ref, probe_clearance)

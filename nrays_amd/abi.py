@@ -237,6 +237,11 @@ HIP_SYMBOLS = {
                                                C.c_void_p]),
     "nrays_material_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_float),
                                         C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_double), C.c_uint32]),
+    "nrays_nearest_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_nearest_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_double), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_debug_nearest_bound": (C.c_int, [C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "nrays_surface_texels_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_uint32, C.c_void_p]),
     "nrays_surface_texels": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -291,7 +296,7 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
                    "nrays_irradiance_points", "nrays_probe_depth_points_device", "nrays_probe_depth_points", "nrays_irradiance_points_vis_device",
                    "nrays_irradiance_points_vis", "nrays_gather_maps_sh_points_device", "nrays_gather_maps_sh_points", "nrays_material_points_device",
-                   "nrays_material_points")
+                   "nrays_material_points", "nrays_nearest_points_device", "nrays_nearest_points", "nrays_debug_nearest_bound")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

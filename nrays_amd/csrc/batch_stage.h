@@ -93,6 +93,15 @@ inline int material_columns(StageColumn* c, const double* normals, const double*
     c[kMatNode] = stage_out(out_node, 32, 16);
     return kMatColumns;
 }
+// nrays_nearest_points*: points in, the nearest-surface record out; every output but the distance and the node may be absent.
+enum { kNearPoints, kNearMaxDist, kNearHit, kNearDist, kNearNode, kNearPoint, kNearNormal, kNearUv, kNearPrim, kNearFlags, kNearColumns };
+inline int nearest_columns(StageColumn* c, const double* points, const double* max_dist, const uint32_t* hit_flags, double* dist, int32_t* node, double* point, double* normal, double* uv,
+                           int32_t* prim, uint32_t* flags) {
+    c[kNearPoints] = stage_in(points, 24); c[kNearMaxDist] = stage_in(max_dist, 8); c[kNearHit] = stage_in(hit_flags, 4);
+    c[kNearDist] = stage_out(dist, 8); c[kNearNode] = stage_out(node, 4); c[kNearPoint] = stage_out(point, 24); c[kNearNormal] = stage_out(normal, 24); c[kNearUv] = stage_out(uv, 16);
+    c[kNearPrim] = stage_out(prim, 4); c[kNearFlags] = stage_out(flags, 4);
+    return kNearColumns;
+}
 // Points with a hemisphere of directions: the two tables and the points (nrays_debug_gather_order stages these alone), then what each family adds.
 enum { kPointDirs, kPointRotations, kPointPoints, kPointNormals, kPointHit, kPointKeys, kPointColumns };
 inline int point_columns(StageColumn* c, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, const double* points, const double* normals,

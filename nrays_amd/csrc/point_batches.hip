@@ -3,7 +3,9 @@
 // nrays_gather_points* (+ _ex) and nrays_gather_sh_points* (kernels: gather_inst.hip, gather_order_inst.hip; k_gather_fold here, k_gather_fold_sh of gather_sh_kernel.h),
 // nrays_gather_maps_points* (gather_maps_inst.hip), nrays_probe_depth_points* (probe_depth_inst.hip), nrays_gather_maps_sh_points* (gather_maps_sh_inst.hip, then the two
 // folds), and the one family at points that builds no ray:
-// nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here).  Also two probes: nrays_debug_occlusion_rays (k_occlusion_rays) and nrays_debug_gather_sh_fold.
+// nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here), and the one that takes points anywhere in space:
+// nrays_nearest_points* (k_nearest_points of nearest_kernel.h: nearest_inst.hip).  Also three probes: nrays_debug_occlusion_rays (k_occlusion_rays), nrays_debug_gather_sh_fold and
+// nrays_debug_nearest_bound.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,6 +20,7 @@
 #include "gather_maps_sh_kernel.h"
 #include "gather_sh_kernel.h"
 #include "irradiance_kernel.h"
+#include "nearest_kernel.h"
 #include "probe_depth_kernel.h"
 #include "ray_batch_kernel.h"
 #include "ray_order.h"
@@ -353,6 +356,37 @@ static int irradiance_points_impl(NraysScene* sc, uint32_t n, const double* poin
     return batch_run(sc, staged, stream, cols, ncols, n, kTraceChunk, "irradiance batch", launch);
 }
 
+// ---- nrays_nearest_points*: the nearest surface to caller-supplied points (nearest_kernel.h) ----------------------------------------------------------------------
+static int check_nearest_args(const NraysScene* sc, const double* points, const double* out_dist, const int32_t* out_node, uint32_t flags) {
+    if (!sc || !points || !out_dist || !out_node) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_nearest_points: flags must be 0");
+    return NRAYS_OK;
+}
+// The scene's coordinate bound, the absolute term of the cull's margin (nearest_margin): the largest |coordinate| of a bounded node's world AABB plus the largest
+// |translation| of an instance.  Every local coordinate the leaf arithmetic sees is within sqrt(3) times it.
+static double nearest_coord_bound(const NraysScene* sc) {
+    const HostScene& h = sc->facts.host;
+    double box = 0.0, trans = 0.0;
+    for (double v : h.node_aabbs) if (std::fabs(v) < 1e300) box = std::max(box, std::fabs(v)); // (a plane's AABB is +-MAX)
+    for (const Instance& in : h.instances) for (double v : in.trans) if (std::isfinite(v)) trans = std::max(trans, std::fabs(v));
+    return box + trans;
+}
+static int nearest_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* max_dist, const uint32_t* hit_flags, double* out_dist, int32_t* out_node,
+                               double* out_point, double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, bool staged, hipStream_t stream) {
+    if (check_nearest_args(sc, points, out_dist, out_node, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kNearColumns];
+    nearest_columns(cols, points, max_dist, hit_flags, out_dist, out_node, out_point, out_normal, out_uv, out_prim, out_flags);
+    const double coord_bound = nearest_coord_bound(sc);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const NearestLaunch a{launch_grid(nc), b.stream, &sc->facts.d, nc, (const double*)c[kNearPoints], (const double*)c[kNearMaxDist], (const uint32_t*)c[kNearHit], coord_bound,
+                              (double*)c[kNearDist], (int32_t*)c[kNearNode], (double*)c[kNearPoint], (double*)c[kNearNormal], (double*)c[kNearUv], (int32_t*)c[kNearPrim],
+                              (uint32_t*)c[kNearFlags], b.w->d_spill};
+        return launch_nearest_points(a, traversal_feat(sc)) ? launch_status("k_nearest_points") : no_permutation("k_nearest_points");
+    };
+    return batch_run(sc, staged, stream, cols, kNearColumns, n, kTraceChunk, "nearest batch", launch);
+}
+
 // nrays_debug_occlusion_rays: ray j of point i of the chunk, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].  NULL keys: key_base + i.
 __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
                                                            const unsigned long long* __restrict__ keys, unsigned long long key_base, OcclusionSpec P,
@@ -475,6 +509,31 @@ int nrays_probe_depth_points_device(NraysScene* sc, uint32_t n, const double* po
 int nrays_probe_depth_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,
                              const NraysProbeDepthParams* params, float* out_moments, uint32_t* out_counts, double* out_nearest, uint32_t* out_nearest_dir, uint32_t flags) {
     return probe_depth_impl(sc, n, points, normals, hit_flags, keys, params, out_moments, out_counts, out_nearest, out_nearest_dir, flags, true, nullptr);
+}
+
+int nrays_nearest_points_device(NraysScene* sc, uint32_t n, const double* points, const double* max_dist, const uint32_t* hit_flags, double* out_dist, int32_t* out_node,
+                                double* out_point, double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags, void* hip_stream) {
+    return nearest_points_impl(sc, n, points, max_dist, hit_flags, out_dist, out_node, out_point, out_normal, out_uv, out_prim, out_flags, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_nearest_points(NraysScene* sc, uint32_t n, const double* points, const double* max_dist, const uint32_t* hit_flags, double* out_dist, int32_t* out_node, double* out_point,
+                         double* out_normal, double* out_uv, int32_t* out_prim, uint32_t* out_flags, uint32_t flags) {
+    return nearest_points_impl(sc, n, points, max_dist, hit_flags, out_dist, out_node, out_point, out_normal, out_uv, out_prim, out_flags, flags, true, nullptr);
+}
+// nrays_debug_nearest_bound: nearest_box_bound alone, points x boxes, on host arrays, blocking (a test probe; no scene).
+int nrays_debug_nearest_bound(uint32_t n, uint32_t boxes, const double* points, const double* box_bounds, double* out) {
+    if (!points || !box_bounds || !out) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (n == 0 || boxes == 0) return NRAYS_OK;
+    const size_t total = (size_t)n * boxes;
+    double *d_p = nullptr, *d_b = nullptr, *d_o = nullptr;
+    hipError_t e = hipMalloc((void**)&d_p, 24 * (size_t)n);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_b, 48 * (size_t)boxes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_o, 8 * total);
+    if (e == hipSuccess) e = hipMemcpy(d_p, points, 24 * (size_t)n, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d_b, box_bounds, 48 * (size_t)boxes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) { launch_nearest_bound(launch_grid(total), (hipStream_t)0, n, boxes, d_p, d_b, d_o); e = hipGetLastError(); }
+    if (e == hipSuccess) e = hipMemcpy(out, d_o, 8 * total, hipMemcpyDeviceToHost);
+    for (double* q : {d_p, d_b, d_o}) if (q) (void)hipFree(q);
+    return e == hipSuccess ? NRAYS_OK : set_last_error(NRAYS_ERR_HIP, std::string("nrays_debug_nearest_bound: ") + hipGetErrorString(e));
 }
 
 // k_gather_fold_sh alone on caller-supplied ray colours, one chunk, through the staging arena; the kernel between events of its own when out_kernel_ms is wanted.

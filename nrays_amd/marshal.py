@@ -338,6 +338,9 @@ TEXELS_MAX_SIDE, TEXELS_MAX_POINTS = 16384, 1 << 24
 
 MATERIAL_OUTPUTS = ("ambient", "diffuse", "specular", "node")  # the outputs of material_points, in the order of nrays_material_points_device's arguments
 MaterialTerms = collections.namedtuple("MaterialTerms", MATERIAL_OUTPUTS)
+NEAREST_OUTPUTS = ("point", "normal", "uv", "prim", "flags")  # the optional outputs of nearest_points, in the order of nrays_nearest_points_device's arguments
+NearestHits = collections.namedtuple("NearestHits", ("dist", "node") + NEAREST_OUTPUTS)  # closest_hits' record with `dist` for `toi`, plus `point`
+NEAREST_BEHIND = 4  # flag bit 2 of a nearest-surface record: the query point lies behind the surface
 MaterialTerms.__doc__ = """What material_points returns: `ambient` (n, 4) float32, Material::ambiant; `diffuse` (n, 3) float32, kd * texture; `specular` (n, 4) float32, (ks, shininess);
 `node` (n, 4) float64, the node's (alpha, refl_mix, refl_atenuation, refr_coeff).  None for what was not asked for."""
 

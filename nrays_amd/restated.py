@@ -5,7 +5,7 @@ import math
 import numpy as np
 
 from . import abi
-from .marshal import (OCCLUSION_MAX_TABLE, Interpolation, MaterialTerms, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
+from .marshal import (NEAREST_BEHIND, NearestHits, OCCLUSION_MAX_TABLE, Interpolation, MaterialTerms, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
                       _depth_res, _material_args, _np_ints, _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
 
 SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
@@ -658,3 +658,275 @@ def filter_texels_ref(flags, width, height, points, normals, values, step=1, pos
     out = v.copy()  # uncovered points: the words as they are
     out[cov] = res[cov]
     return out.reshape(values.shape)
+
+
+# ---- the nearest surface to caller-supplied points (include/nrays_abi.h: nrays_nearest_points_device) ------------------------------------------------------------
+
+NEAREST_MARGIN = 2.0 ** -38  # the cull's margin is NEAREST_MARGIN * (bound + scale2): DESIGN, "Nearest-surface queries"
+
+
+def nearest_box_bound_ref(points, boxes):
+    """The numpy mirror of the device's nearest_box_bound (nearest_kernel.h), bit for bit: a lower bound of the exact squared distance from each of the (n, 3) float64
+    `points` to each of the (m, 6) `boxes` {min x, y, z, max x, y, z}, narrowed to float32 as a BVH node holds them.  Per axis the gap max(mn - p, p - mx, 0), the
+    squares summed left to right, capped at DBL_MAX, scaled by 1 - 2^-50; below 1e-290 the bound is 0.  Returns (n, m) float64."""
+    P = np.asarray(points, np.float64).reshape(-1, 1, 3)
+    B = np.asarray(boxes, np.float64).reshape(1, -1, 6).astype(np.float32).astype(np.float64)
+    with np.errstate(all="ignore"):
+        g = np.fmax(np.fmax(B[..., :3] - P, P - B[..., 3:]), 0.0)
+        s = np.fmin((g[..., 0] * g[..., 0] + g[..., 1] * g[..., 1]) + g[..., 2] * g[..., 2], np.finfo(np.float64).max)
+        b = s * (1.0 - 2.0 ** -50)
+    return np.where(b < 1e-290, 0.0, b)
+
+
+def nearest_margin_ref(bound, scale2):
+    """The margin the walk grants a box bound: NEAREST_MARGIN * (bound + scale2), scale2 = (max |p_k| + the scene's coordinate bound)^2."""
+    with np.errstate(all="ignore"):
+        return NEAREST_MARGIN * (np.asarray(bound, np.float64) + scale2)
+
+
+def nearest_skips_ref(bound, margin, best):
+    """Whether the walk skips a box: iff bound - margin > best.  Equal values are visited (the tie-break); a NaN skips nothing."""
+    with np.errstate(all="ignore"):
+        return np.asarray(bound, np.float64) - margin > best
+
+
+def _dot3(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def _d2_of(p, q):
+    e = p - q
+    return (e[..., 0] * e[..., 0] + e[..., 1] * e[..., 1]) + e[..., 2] * e[..., 2]
+
+
+def tri_closest_ref(a, b, c, p):
+    """Ericson's closest point on a triangle as the header writes it, element-wise over broadcastable (..., 3) float64 arrays: (v, w, q, region), region 0 .. 6 =
+    vertex A, vertex B, edge AB, vertex C, edge AC, edge BC, interior."""
+    a, b, c, p = np.broadcast_arrays(*(np.asarray(x, np.float64) for x in (a, b, c, p)))
+    with np.errstate(all="ignore"):
+        ab, ac, ap = b - a, c - a, p - a
+        d1, d2 = _dot3(ab, ap), _dot3(ac, ap)
+        bp = p - b
+        d3, d4 = _dot3(ab, bp), _dot3(ac, bp)
+        vc = d1 * d4 - d3 * d2
+        cp = p - c
+        d5, d6 = _dot3(ab, cp), _dot3(ac, cp)
+        vb = d5 * d2 - d1 * d6
+        va = d3 * d6 - d5 * d4
+        den = (va + vb) + vc
+        tests = [(d1 <= 0.0) & (d2 <= 0.0), (d3 >= 0.0) & (d4 <= d3), (vc <= 0.0) & (d1 >= 0.0) & (d3 <= 0.0), (d6 >= 0.0) & (d5 <= d6),
+                 (vb <= 0.0) & (d2 >= 0.0) & (d6 <= 0.0), (va <= 0.0) & ((d4 - d3) >= 0.0) & ((d5 - d6) >= 0.0)]
+        region = np.full(d1.shape, 6, np.int64)
+        for k in range(5, -1, -1):
+            region = np.where(tests[k], k, region)
+        vab, wac, wbc = d1 / (d1 - d3), d2 / (d2 - d6), (d4 - d3) / ((d4 - d3) + (d5 - d6))
+        vi, wi = vb / den, vc / den
+        one, zero = np.ones_like(d1), np.zeros_like(d1)
+        # the last branch: the interior point, if its weights are in range, against the three clamped edge projections (strict <, in the order AB, AC, BC)
+        clamp01 = lambda t: np.where(t >= 0.0, np.where(t <= 1.0, t, 1.0), 0.0)  # noqa: E731
+        qi = (a + ab * vi[..., None]) + ac * wi[..., None]
+        best = np.where((vi >= 0.0) & (wi >= 0.0) & ((1.0 - vi) - wi >= 0.0), _d2_of(p, qi), np.inf)
+        t1, t2, t3 = clamp01(vab), clamp01(wac), clamp01(wbc)
+        for t, qe, ve, we in ((t1, a + ab * t1[..., None], t1, zero), (t2, a + ac * t2[..., None], zero, t2), (t3, b + (c - b) * t3[..., None], 1.0 - t3, t3)):
+            e = _d2_of(p, qe)
+            take = e < best
+            best, qi, vi, wi = np.where(take, e, best), np.where(take[..., None], qe, qi), np.where(take, ve, vi), np.where(take, we, wi)
+        v = np.choose(region, [zero, one, vab, zero, zero, 1.0 - wbc, vi])
+        w = np.choose(region, [zero, zero, zero, one, wac, wbc, wi])
+        r = region[..., None]
+        q = np.where(r == 0, a, np.where(r == 1, b, np.where(r == 2, a + ab * vab[..., None], np.where(r == 3, c, np.where(
+            r == 4, a + ac * wac[..., None], np.where(r == 5, b + (c - b) * wbc[..., None], qi))))))
+    return v, w, q, region
+
+
+def _clamp(x, lo, hi):
+    return np.where(x < lo, lo, np.where(x > hi, hi, x))
+
+
+def nearest_shape_ref(kind, params, pl):
+    """An analytic shape's closest point to the (n, 3) local points `pl` as the header defines it: (ql, nl, behind)."""
+    pl = np.asarray(pl, np.float64).reshape(-1, 3)
+    p0, p1, p2 = (float(x) for x in params)
+    x, y, z = pl[:, 0], pl[:, 1], pl[:, 2]
+    with np.errstate(all="ignore"):
+        if kind == abi.SHAPE_BALL:
+            ln = np.sqrt((x * x + y * y) + z * z)
+            at0 = (ln == 0.0)[:, None]
+            q = np.where(at0, np.array([p0, 0.0, 0.0]), pl * (p0 / ln)[:, None])
+            nl = np.where(at0, np.array([1.0, 0.0, 0.0]), pl / ln[:, None])
+            return q, nl, ln < p0
+        if kind == abi.SHAPE_CUBOID:
+            h = np.array([p0, p1, p2])
+            g = h - np.abs(pl)
+            inside = (g >= 0.0).all(axis=1)
+            ax = np.where((g[:, 0] <= g[:, 1]) & (g[:, 0] <= g[:, 2]), 0, np.where(g[:, 1] <= g[:, 2], 1, 2))
+            on = np.arange(3)[None, :] == ax[:, None]
+            qi, ni = np.where(on, np.copysign(h, pl), pl), np.where(on, np.copysign(1.0, pl), 0.0)
+            qo = _clamp(pl, -h, h)
+            no = (pl - qo) / np.sqrt(_d2_of(pl, qo))[:, None]
+            return np.where(inside[:, None], qi, qo), np.where(inside[:, None], ni, no), inside & (g > 0.0).all(axis=1)
+        if kind == abi.SHAPE_PLANE:
+            nrm = np.array([p0, p1, p2])
+            t = _dot3(np.broadcast_to(nrm, pl.shape), pl)
+            behind = t < 0.0
+            return pl - nrm * t[:, None], np.where(behind[:, None], -nrm, nrm), behind
+        hh, r = p0, p1
+        rho = np.sqrt(x * x + z * z)
+        cx, cz = np.where(rho == 0.0, 1.0, x / rho), np.where(rho == 0.0, 0.0, z / rho)
+        if kind == abi.SHAPE_CYLINDER:
+            gs, gc = r - rho, hh - np.abs(y)
+            named = (gs >= 0.0) & (gc >= 0.0)
+            side = gs <= gc
+            qr, qy = np.where(named, np.where(side, r, rho), np.where(rho > r, r, rho)), np.where(named, np.where(side, y, np.copysign(hh, y)), _clamp(y, -hh, hh))
+            nr, ny = np.where(side, 1.0, 0.0), np.where(side, 0.0, np.copysign(1.0, y))
+            behind = (gs > 0.0) & (gc > 0.0)
+        elif kind == abi.SHAPE_CAPSULE:
+            yc = _clamp(y, -hh, hh)
+            ey = y - yc
+            ln = np.sqrt(rho * rho + ey * ey)
+            nr, ny = np.where(ln == 0.0, 1.0, rho / ln), np.where(ln == 0.0, 0.0, ey / ln)
+            qr, qy = nr * r, yc + ny * r
+            named, behind = np.ones(len(pl), bool), ln < r
+        elif kind == abi.SHAPE_CONE:
+            up, h2 = y + hh, 2.0 * hh
+            br = np.where(rho > r, r, rho)
+            e0 = rho - br
+            db = e0 * e0 + up * up
+            t = _clamp(((rho - r) * -r + up * h2) / (r * r + h2 * h2), 0.0, 1.0)
+            sr, sy = r + -r * t, -hh + h2 * t
+            e1, e2 = rho - sr, y - sy
+            ds = e1 * e1 + e2 * e2
+            f = (rho - r) * h2 + up * r
+            base = db <= ds
+            qr, qy = np.where(base, br, sr), np.where(base, -hh, sy)
+            behind, named = (up > 0.0) & (f < 0.0), (up >= 0.0) & (f <= 0.0)
+            ln = np.sqrt(h2 * h2 + r * r)
+            nr, ny = np.where(base, 0.0, h2 / ln), np.where(base, -1.0, r / ln)
+        else:
+            raise ValueError("nearest_shape_ref: not an analytic shape kind: %r" % (kind,))
+        er, ey = rho - qr, y - qy
+        ln = np.sqrt(er * er + ey * ey)
+        nr, ny = np.where(named, nr, er / ln), np.where(named, ny, ey / ln)
+        return np.stack([qr * cx, qy, qr * cz], axis=1), np.stack([nr * cx, ny, nr * cz], axis=1), behind
+
+
+def _nearest_frame(transform):
+    from . import math3d
+    aa = (0.0, 0.0, 0.0) if transform is None else tuple(transform.axis_angle)
+    T = np.array((0.0, 0.0, 0.0) if transform is None else tuple(transform.translation), np.float64)
+    identity = aa == (0.0, 0.0, 0.0)
+    return math3d.rotation_from_axis_angle(aa), T, identity, identity and not T.any()
+
+
+def nearest_local_ref(transform, p):
+    """The query points in a node's local space, with the header's shortcuts: R^T (p - T) in inv_rot's order, p - T without a rotation, p without either."""
+    R, T, identity, noxform = _nearest_frame(transform)
+    p = np.asarray(p, np.float64).reshape(-1, 3)
+    if noxform:
+        return p
+    v = p - T
+    if identity:
+        return v
+    return np.stack([(R[0, k] * v[:, 0] + R[1, k] * v[:, 1]) + R[2, k] * v[:, 2] for k in range(3)], axis=1)
+
+
+def _nearest_world(transform, q, nl):
+    R, T, identity, noxform = _nearest_frame(transform)
+    if noxform:
+        return q, nl
+    if identity:
+        return q + T, nl
+    rot = lambda a: np.stack([(R[k, 0] * a[:, 0] + R[k, 1] * a[:, 1]) + R[k, 2] * a[:, 2] for k in range(3)], axis=1)  # noqa: E731
+    return rot(q) + T, rot(nl)
+
+
+def _mesh_arrays(g):
+    P = np.asarray(g.points, np.float64).astype(np.float32).astype(np.float64)
+    I = np.asarray(g.indices).reshape(-1, 3).astype(np.int64)
+    UV = None if g.uvs is None else np.asarray(g.uvs, np.float64).astype(np.float32).astype(np.float64)
+    return P, I, UV
+
+
+def nearest_node_d2_ref(node, points, block=1 << 21):
+    """The keys of one scene node: (d2 (n,) float64, tri (n,) int64) — the smallest key over the node's triangles with the smallest triangle index among equals
+    (-1 and d2 NaN for a mesh without triangles), or the analytic shape's key with tri -1.  A NaN key is no candidate."""
+    g = node.geometry
+    pl = nearest_local_ref(node.transform, points)
+    n = len(pl)
+    with np.errstate(all="ignore"):
+        if g.kind != abi.SHAPE_TRIMESH:
+            q, _, _ = nearest_shape_ref(g.kind, g.params, pl)
+            return _d2_of(pl, q), np.full(n, -1, np.int64)
+        P, I, _ = _mesh_arrays(g)
+        best, tri = np.full(n, np.nan), np.full(n, -1, np.int64)
+        pstep = max(1, min(n, 8192))
+        tstep = max(1, block // pstep)
+        for p0 in range(0, n, pstep):
+            pp = pl[p0:p0 + pstep, None, :]
+            for t0 in range(0, len(I), tstep):
+                T = I[t0:t0 + tstep]
+                _, _, q, _ = tri_closest_ref(P[T[:, 0]][None], P[T[:, 1]][None], P[T[:, 2]][None], pp)
+                d2 = _d2_of(pp, q)
+                d2c = np.where(np.isnan(d2), np.inf, d2)
+                k = np.argmin(d2c, axis=1)  # (the first of equals: the smallest index)
+                rows = np.arange(len(k))
+                cand, valid = d2[rows, k], ~np.isnan(d2[rows, k])
+                cur, curt = best[p0:p0 + pstep], tri[p0:p0 + pstep]
+                take = valid & ((curt < 0) | (cand < cur))
+                cur[take], curt[take] = cand[take], (k + t0)[take]
+        return best, tri
+
+
+def nearest_points_ref(nodes, points, max_dist=None, hit_flags=None):
+    """The numpy mirror of nrays_nearest_points*, bit for bit (include/nrays_abi.h: nrays_nearest_points_device), by brute force over `nodes`, the SceneNode list a Scene
+    is made from: every node and every triangle is a candidate, in ascending order, a later one winning only with a strictly smaller key.  `points` (n, 3) float64;
+    `max_dist` (n,) or None; `hit_flags` (n,) integers or None.  Returns NearestHits of numpy arrays (flags uint32).  The ball's uv goes through numpy's arctan2 and
+    arcsin: equal to the device's up to the math library; everything else is + - * / sqrt."""
+    P = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    n = len(P)
+    md = np.full(n, np.inf) if max_dist is None else np.asarray(max_dist, np.float64).reshape(n)
+    with np.errstate(invalid="ignore"):
+        live = md >= 0.0
+    if hit_flags is not None:
+        live &= (np.asarray(hit_flags).astype(np.uint64) & np.uint64(1)) != 0
+    idx = np.nonzero(live)[0]
+    Q = P[idx]
+    m = len(Q)
+    bd2, bnode, btri = np.full(m, np.inf), np.full(m, -1, np.int64), np.full(m, -1, np.int64)
+    with np.errstate(all="ignore"):
+        for k, node in enumerate(nodes):
+            d2, tri = nearest_node_d2_ref(node, Q)
+            take = ~np.isnan(d2) & ((bnode < 0) | (d2 < bd2))
+            bd2[take], bnode[take], btri[take] = d2[take], k, tri[take]
+        dist = np.sqrt(bd2)
+        found = (bnode >= 0) & (dist <= md[idx])
+        out = NearestHits(dist=np.full(n, np.inf), node=np.full(n, -1, np.int32), point=np.zeros((n, 3)), normal=np.zeros((n, 3)), uv=np.zeros((n, 2)),
+                          prim=np.full(n, -1, np.int32), flags=np.zeros(n, np.uint32))
+        for k in np.unique(bnode[found]):
+            node, at = nodes[int(k)], found & (bnode == k)
+            g, rows = node.geometry, idx[at]
+            pl = nearest_local_ref(node.transform, Q[at])
+            flags = np.full(len(rows), 1, np.uint32)
+            if g.kind == abi.SHAPE_TRIMESH:
+                V, I, UV = _mesh_arrays(g)
+                T = I[btri[at]]
+                a, b, c = V[T[:, 0]], V[T[:, 1]], V[T[:, 2]]
+                v, w, q, _ = tri_closest_ref(a, b, c, pl)
+                cr = np.cross(b - a, c - a)  # (each component x y' - y x': two products and a difference, as cross())
+                behind = _dot3(pl - a, cr) < 0.0
+                nl = cr / np.sqrt(_dot3(cr, cr))[:, None]
+                nl = np.where(behind[:, None], -nl, nl)
+                out.prim[rows] = btri[at]
+                if UV is not None:
+                    b0 = (1.0 - v) - w
+                    out.uv[rows] = (UV[T[:, 0]] * b0[:, None] + UV[T[:, 1]] * v[:, None]) + UV[T[:, 2]] * w[:, None]
+                    flags |= np.uint32(2)
+            else:
+                q, nl, behind = nearest_shape_ref(g.kind, g.params, pl)
+            wp, wn = _nearest_world(node.transform, q, nl)
+            if g.kind == abi.SHAPE_BALL:
+                out.uv[rows] = np.stack([0.5 + np.arctan2(wn[:, 2], wn[:, 0]) / (math.pi * 2.0), 0.5 - np.arcsin(wn[:, 1]) / math.pi], axis=1)
+                flags |= np.uint32(2)
+            out.dist[rows], out.node[rows], out.point[rows], out.normal[rows] = dist[at], k, wp, wn
+            out.flags[rows] = flags | np.where(behind, np.uint32(NEAREST_BEHIND), np.uint32(0))
+    return out

@@ -20,11 +20,11 @@ import math
 import numpy as np
 
 from . import abi
-from .marshal import (CURRENT, F32, F64, I32, MATERIAL_OUTPUTS, MaterialTerms, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
+from .marshal import (CURRENT, F32, F64, I32, MATERIAL_OUTPUTS, NEAREST_BEHIND, NEAREST_OUTPUTS, MaterialTerms, NearestHits, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
                       Overflow, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _material_args, _n_of, _np_floats,
                       _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice, np_ptr, upload)
 from .restated import (FILTER_TAPS, SALT_GATHER, SALT_OCCLUSION, SH_COSINE_LOBE, SH_K, _rng_hash, _rng_mix, _sh_terms, _texel_edge, camera_rays, dilate_texels_ref,  # noqa: F401
-                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, material_points_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
+                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, material_points_ref, nearest_box_bound_ref, nearest_points_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
                        sphere_dirs, surface_texels_ref, texel_coords)
 
 
@@ -362,6 +362,14 @@ class BatchCalls:
     def material_points(self, nodes, normals=None, uvs=None, hit_flags=None, want=("ambient", "diffuse")):
         """The material terms at caller-supplied surface points of this scene, without the lights: material_points(self, ...)."""
         return material_points(self, nodes, normals, uvs, hit_flags, want)
+
+    def nearest_points(self, points, max_dist=None, hit_flags=None, want=NEAREST_OUTPUTS):
+        """The nearest surface of this scene to caller-supplied points: nearest_points(self, ...)."""
+        return nearest_points(self, points, max_dist, hit_flags, want)
+
+    def probe_clearance(self, positions, max_dist=None):
+        """The distance from probe positions to this scene's nearest surface, and whether they lie behind it: probe_clearance(self, ...)."""
+        return probe_clearance(self, positions, max_dist)
 
     def material_hits(self, hits, want=("ambient", "diffuse")):
         """The material terms at the closest hits of caller-supplied rays on this scene: material_hits(self, hits, ...)."""
@@ -733,6 +741,70 @@ def material_points(scene, nodes, normals=None, uvs=None, hit_flags=None, want=(
                ("node", (n, 4), F64, "node" in want)))
     b.call(scene, "nrays_material_points", n, b.pin[1], b.pin[2], b.pin[0], b.pin[3], *b.pout, 0)
     return MaterialTerms(*b.outs)
+
+
+# ---- the nearest surface to caller-supplied points (include/nrays_abi.h: nrays_nearest_points_device) -----------------------------------------------
+
+def nearest_points(scene, points, max_dist=None, hit_flags=None, want=NEAREST_OUTPUTS):
+    """The nearest surface to n caller-supplied points, through nrays_nearest_points_device / nrays_nearest_points: how far it is, where, and on which node and
+    triangle — the question the ray families cannot answer (probe clearance, transfer of baked light to points off the surface, distance fields).  A
+    distance-pruned walk of both BVH levels, one lane a point; the result is the header's definition, restated bit for bit by nearest_points_ref().  Also
+    `scene.nearest_points(...)` on Scene and FileScene.
+    `points` (n, 3).  `max_dist` (n,) or None: the unbounded answer where its distance <= max_dist[i], a miss otherwise (NaN or negative: a miss).  `hit_flags` (n,)
+    integers or None: bit 0 clear skips the point (the miss record; its coordinates may hold anything).  `want`: which of "point", "normal", "uv", "prim", "flags"
+    to compute into memory.
+    Returns NearestHits(dist (n,) f64, node (n,) i32, point (n, 3) f64, normal (n, 3) f64, uv (n, 2) f64, prim (n,) i32, flags (n,)), None for what was not wanted:
+    closest_hits' record with `dist` for `toi`, plus `point`, so that point / normal / node / uv / flags pass unfiltered into shade_points, material_points,
+    occlusion_points, the gather families and irradiance_points.  A miss has node -1, dist +inf, zeros, prim -1, flags 0; flags bit 0 = found, bit 1 = the record
+    carries a uv, bit 2 (NEAREST_BEHIND) = the point lies behind the surface.  The normal faces the point.
+    numpy arrays -> nrays_nearest_points (blocking), numpy arrays (flags uint32).  torch tensors on the scene's GPU (float64; hit_flags int32 / uint32) ->
+    nrays_nearest_points_device on torch's current stream, tensors (flags int32)."""
+    if points is None:
+        raise ValueError("points is required")
+    _check_rows("points", points, int(points.shape[0]) if len(points.shape) else 0, 3)
+    n = int(points.shape[0])
+    if n >= 1 << 32:
+        raise ValueError("at most 2^32 - 1 points per call")
+    _check_vec("max_dist", max_dist, n)
+    _check_vec("hit_flags", hit_flags, n)
+    want = tuple(want)
+    for name in want:
+        if name not in NEAREST_OUTPUTS:
+            raise ValueError("want: unknown output %r (one of %s)" % (name, ", ".join(NEAREST_OUTPUTS)))
+    b = Batch((("points", points, F64), ("max_dist", max_dist, F64), ("hit_flags", hit_flags, U32)),
+              (("dist", (n,), F64), ("node", (n,), I32), ("point", (n, 3), F64, "point" in want), ("normal", (n, 3), F64, "normal" in want), ("uv", (n, 2), F64, "uv" in want),
+               ("prim", (n,), I32, "prim" in want), ("flags", (n,), U32, "flags" in want)))
+    b.call(scene, "nrays_nearest_points", n, *b.pin, *b.pout, 0)
+    return NearestHits(*b.outs)
+
+
+ProbeClearance = collections.namedtuple("ProbeClearance", ("dist", "behind"))
+
+
+def probe_clearance(scene, positions, max_dist=None):
+    """What a probe's validity and relocation should rest on: per probe position the distance to the scene's nearest surface (+inf beyond `max_dist`, a scalar or
+    None) and whether the position lies behind it (flag bit 2 of nearest_points: inside a closed shape, under a plane, on the back of a triangle's winding).
+    probe_depth() reports the nearest of its SAMPLED rays and misses what lies between them; this does not sample.  The rule stays the caller's
+    (probe_valid_words is unchanged).  Returns ProbeClearance(dist (n,) float64, behind (n,) bool), numpy or torch as `positions`."""
+    n = int(positions.shape[0])
+    md = None
+    if max_dist is not None:
+        if _is_tensor(positions):
+            import torch
+            md = torch.full((n,), float(max_dist), dtype=torch.float64, device=positions.device)
+        else:
+            md = np.full(n, float(max_dist), np.float64)
+    hits = nearest_points(scene, positions, md, want=("flags",))
+    return ProbeClearance(hits.dist, (hits.flags & NEAREST_BEHIND) != 0)
+
+
+def nearest_bound_probe(points, boxes):
+    """nearest_box_bound of the device (nrays_debug_nearest_bound), points x boxes: (n, m) float64.  nearest_box_bound_ref() is its mirror."""
+    P = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+    B = np.ascontiguousarray(np.asarray(boxes, np.float64).reshape(-1, 6))
+    out = np.zeros((len(P), len(B)), np.float64)
+    abi.check(abi.load_hip_lib().nrays_debug_nearest_bound(len(P), len(B), np_ptr(P), np_ptr(B), np_ptr(out)))
+    return out
 
 
 def material_hits(scene, hits, want=("ambient", "diffuse")):
