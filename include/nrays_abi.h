@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points / nrays_nearest_points_device / nrays_nearest_points / nrays_debug_nearest_bound.  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points / nrays_nearest_points_device / nrays_nearest_points / nrays_debug_nearest_bound / nrays_debug_scene_dump (its struct NraysSceneDump likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -1071,6 +1071,58 @@ int nrays_debug_nearest_bound(uint32_t n, uint32_t boxes, const double* points, 
  * reference's arithmetic; the kernels apply ncollide's exact ray / AABB test to it for every accepted hit (the reference only casts
  * a node whose AABB the ray passes, src/scene.rs:276).  out = {min x, y, z, max x, y, z}. */
 int nrays_debug_node_aabb(NraysScene* scene, uint32_t node, double out[6]);
+
+/* Test probe: the flattened scene as the kernels read it — both TLASes, every BLAS, both instance lists — copied back FROM DEVICE MEMORY
+ * (tests/scene_cover.py validates it against the scene description).  The caller provides the buffers and their capacities in entries;
+ * a call with a capacity too small fills in the num_* fields and the scalars and returns NRAYS_ERR_BAD_ARG ("dump buffers too small"),
+ * as nrays_debug_blas_build does.  All HOST memory.  Blocking.
+ *   nodes             num_nodes x 32 floats: the 128-byte 4-wide node of NraysBlasDump, child refs ABSOLUTE indices into this array
+ *                     (TLAS leaves: ~((instance index << 3) | bits), bits 1 = untransformed, 2 = any-hit, 4 = mesh)
+ *   tris              num_tris x 48 bytes: v0.xyz f32, node id u32, v1.xyz, triangle id u32, v2.xyz, 0
+ *   instances /       num_instances / num_shadow_instances x 136 bytes, the TLAS's leaves in leaf order and the planes behind them:
+ *   shadow_instances  f64 rot[9] at byte 0 (local -> world, row-major), f64 trans[3] at 72, f64 params[3] at 96, u32 kind at 120 (NraysShapeKind),
+ *                     u32 flags at 124 (1 solid, 2 identity rotation, 4 any-hit, 8 has uvs, 16 untransformed, 32 no uv values, 64 hair-like),
+ *                     i32 node_id at 128 (-1: a BLAS of several nodes), i32 blas_root at 132 (a node index, or a leaf ref < 0)
+ *   links /           one {i32 blas_root, u32 flags} pair per instance of the list
+ *   shadow_links
+ *   planes /          num_planes indices into instances / shadow_instances
+ *   shadow_planes
+ *   node_aabbs        num_scene_nodes x 6 doubles (nrays_debug_node_aabb)
+ * closest_root / shadow_root: a node index, a leaf ref, or INT32_MIN for an empty list.  bounds_mn / bounds_mx / bounded: the f32 box of the
+ * closest-hit TLAS's leaves and whether the scene has no plane; max_bvh_depth; dev_nodes / dev_tris: how many leading entries of nodes /
+ * tris the device builder made (the host-built ones were moved behind them) — these six are host bookkeeping. */
+typedef struct NraysSceneDump {
+    uint32_t num_nodes;
+    uint32_t num_tris;
+    uint32_t num_instances;
+    uint32_t num_shadow_instances;
+    uint32_t num_planes;
+    uint32_t num_scene_nodes;
+    uint32_t node_capacity;
+    uint32_t tri_capacity;
+    uint32_t instance_capacity;
+    uint32_t shadow_instance_capacity;
+    uint32_t plane_capacity;
+    uint32_t scene_node_capacity;
+    int32_t closest_root;
+    int32_t shadow_root;
+    int32_t max_bvh_depth;
+    uint32_t bounded;
+    uint32_t dev_nodes;
+    uint32_t dev_tris;
+    float bounds_mn[3];
+    float bounds_mx[3];
+    float* nodes;
+    uint8_t* tris;
+    uint8_t* instances;
+    uint8_t* shadow_instances;
+    int32_t* links;
+    int32_t* shadow_links;
+    int32_t* planes;
+    int32_t* shadow_planes;
+    double* node_aabbs;
+} NraysSceneDump;
+int nrays_debug_scene_dump(NraysScene* scene, NraysSceneDump* out);
 
 /* How the library classified the scene's content (test probe): out[0] = the feature bits of the descriptor (1 analytic shapes, 2 meshes,
  * 4 some node may be non-opaque to shadow rays, 16 more than one light sample per hit; 15 / 31 when a node can both reflect and refract),

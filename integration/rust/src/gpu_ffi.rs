@@ -206,6 +206,40 @@ pub struct NraysBlasDump {
 
 #[repr(C)]
 #[derive(Clone, Copy)]
+pub struct NraysSceneDump {
+    pub num_nodes: u32,
+    pub num_tris: u32,
+    pub num_instances: u32,
+    pub num_shadow_instances: u32,
+    pub num_planes: u32,
+    pub num_scene_nodes: u32,
+    pub node_capacity: u32,
+    pub tri_capacity: u32,
+    pub instance_capacity: u32,
+    pub shadow_instance_capacity: u32,
+    pub plane_capacity: u32,
+    pub scene_node_capacity: u32,
+    pub closest_root: i32,
+    pub shadow_root: i32,
+    pub max_bvh_depth: i32,
+    pub bounded: u32,
+    pub dev_nodes: u32,
+    pub dev_tris: u32,
+    pub bounds_mn: [f32; 3],
+    pub bounds_mx: [f32; 3],
+    pub nodes: *mut f32,
+    pub tris: *mut u8,
+    pub instances: *mut u8,
+    pub shadow_instances: *mut u8,
+    pub links: *mut i32,
+    pub shadow_links: *mut i32,
+    pub planes: *mut i32,
+    pub shadow_planes: *mut i32,
+    pub node_aabbs: *mut f64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy)]
 pub struct NraysOcclusionParams {
     pub num_dirs: u32,
     pub num_rotations: u32,
@@ -316,6 +350,7 @@ extern "C" {
     pub fn nrays_get_primary_kernel_stats(scene: *mut NraysScene, out_stats: *mut NraysStats) -> c_int;
     pub fn nrays_debug_blas_build(mesh: *const NraysMesh, flags: u32, out: *mut NraysBlasDump) -> c_int;
     pub fn nrays_debug_node_aabb(scene: *mut NraysScene, node: u32, out: *mut f64) -> c_int;
+    pub fn nrays_debug_scene_dump(scene: *mut NraysScene, out: *mut NraysSceneDump) -> c_int;
     pub fn nrays_debug_scene_flags(scene: *const NraysScene, out: *mut u32) -> c_int;
     pub fn nrays_debug_last_permutation(scene: *const NraysScene, out: *mut u32) -> c_int; // out: [u32; 6]
     pub fn nrays_debug_pipeline_counts(scene: *const NraysScene, out: *mut u64) -> c_int; // out: [u64; 4]

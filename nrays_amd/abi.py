@@ -163,10 +163,22 @@ class NraysBlasDump(C.Structure):
                 ("node_capacity", C.c_uint32), ("ref_capacity", C.c_uint32), ("pad", C.c_uint32), ("nodes", C.POINTER(C.c_float)), ("tri_ids", C.POINTER(C.c_uint32))]
 
 
+class NraysSceneDump(C.Structure):
+    """The buffers of nrays_debug_scene_dump: capacities in, sizes and scalars out (include/nrays_abi.h spells the record layouts)."""
+    _fields_ = [("num_nodes", C.c_uint32), ("num_tris", C.c_uint32), ("num_instances", C.c_uint32), ("num_shadow_instances", C.c_uint32), ("num_planes", C.c_uint32),
+                ("num_scene_nodes", C.c_uint32), ("node_capacity", C.c_uint32), ("tri_capacity", C.c_uint32), ("instance_capacity", C.c_uint32),
+                ("shadow_instance_capacity", C.c_uint32), ("plane_capacity", C.c_uint32), ("scene_node_capacity", C.c_uint32), ("closest_root", C.c_int32),
+                ("shadow_root", C.c_int32), ("max_bvh_depth", C.c_int32), ("bounded", C.c_uint32), ("dev_nodes", C.c_uint32), ("dev_tris", C.c_uint32),
+                ("bounds_mn", C.c_float * 3), ("bounds_mx", C.c_float * 3), ("nodes", C.POINTER(C.c_float)), ("tris", C.POINTER(C.c_uint8)),
+                ("instances", C.POINTER(C.c_uint8)), ("shadow_instances", C.POINTER(C.c_uint8)), ("links", C.POINTER(C.c_int32)), ("shadow_links", C.POINTER(C.c_int32)),
+                ("planes", C.POINTER(C.c_int32)), ("shadow_planes", C.POINTER(C.c_int32)), ("node_aabbs", C.POINTER(C.c_double))]
+
+
 # Every symbol include/nrays_abi.h declares, with its ctypes signature.
 HIP_SYMBOLS = {
     "nrays_debug_blas_build": (C.c_int, [C.POINTER(NraysMesh), C.c_uint32, C.POINTER(NraysBlasDump)]),
     "nrays_debug_node_aabb": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
+    "nrays_debug_scene_dump": (C.c_int, [C.c_void_p, C.POINTER(NraysSceneDump)]),
     "nrays_debug_scene_flags": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "nrays_debug_last_permutation": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "nrays_debug_pipeline_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
@@ -296,7 +308,7 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
                    "nrays_irradiance_points", "nrays_probe_depth_points_device", "nrays_probe_depth_points", "nrays_irradiance_points_vis_device",
                    "nrays_irradiance_points_vis", "nrays_gather_maps_sh_points_device", "nrays_gather_maps_sh_points", "nrays_material_points_device",
-                   "nrays_material_points", "nrays_nearest_points_device", "nrays_nearest_points", "nrays_debug_nearest_bound")
+                   "nrays_material_points", "nrays_nearest_points_device", "nrays_nearest_points", "nrays_debug_nearest_bound", "nrays_debug_scene_dump")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

@@ -404,6 +404,7 @@ int nrays_scene_create(const NraysSceneDesc* desc, NraysScene** out_scene) {
                 std::chrono::duration<double>(std::chrono::steady_clock::now() - t_create1).count());
     derive_scene_facts(sc);
     if ((rc = upload_lds_scene(sc)) != NRAYS_OK || (rc = upload_tiny_leaves(sc)) != NRAYS_OK || (rc = upload_seed_boxes(sc)) != NRAYS_OK) return bail(rc);
+    sc->facts.num_nodes = h.dev_nodes + h.nodes.size(); sc->facts.num_tris = h.dev_tris + h.tris.size();
     // release bulk host copies
     std::vector<BvhNode>().swap(h.nodes); std::vector<TriRec>().swap(h.tris); std::vector<TriUv>().swap(h.triuvs);
     for (HostTexture& t : h.textures) std::vector<uint8_t>().swap(t.bytes);
@@ -695,6 +696,40 @@ int nrays_debug_node_aabb(NraysScene* sc, uint32_t node, double out[6]) {
     HIP_TRY(hipSetDevice(sc->facts.device));
     HIP_TRY(hipMemcpy(out, sc->facts.d.node_aabbs + 6 * (size_t)node, 6 * sizeof(double), hipMemcpyDeviceToHost));
     return NRAYS_OK;
+}
+
+// One array of the dump: `count` records of `elem` bytes from device memory into the caller's buffer.
+static int dump_array(void* dst, const void* src, size_t count, size_t elem, const char* what) {
+    if (count == 0) return NRAYS_OK;
+    if (!dst) return fail(NRAYS_ERR_BAD_ARG, std::string("null dump buffer: ") + what);
+    if (!src) return fail(NRAYS_ERR_HIP, std::string("the scene holds no device array: ") + what);
+    HIP_TRY(hipMemcpy(dst, src, count * elem, hipMemcpyDeviceToHost));
+    return NRAYS_OK;
+}
+
+int nrays_debug_scene_dump(NraysScene* sc, NraysSceneDump* out) {
+    if (!sc || !out) return fail(NRAYS_ERR_BAD_ARG, "null argument");
+    const HostScene& h = sc->facts.host; const DScene& d = sc->facts.d;
+    // the counts of the uploaded arrays (the host copies of the records stay with the handle; the kernels' own words are d's)
+    const size_t nodes = sc->facts.num_nodes, tris = sc->facts.num_tris, insts = h.instances.size(), sinsts = h.shadow_instances.size(), planes = d.num_planes, snodes = h.node_aabbs.size() / 6;
+    out->num_nodes = (uint32_t)nodes; out->num_tris = (uint32_t)tris; out->num_instances = (uint32_t)insts; out->num_shadow_instances = (uint32_t)sinsts;
+    out->num_planes = (uint32_t)planes; out->num_scene_nodes = (uint32_t)snodes;
+    out->closest_root = d.closest_root; out->shadow_root = d.shadow_root;
+    out->max_bvh_depth = h.max_bvh_depth; out->bounded = h.bounded ? 1u : 0u; out->dev_nodes = (uint32_t)h.dev_nodes; out->dev_tris = (uint32_t)h.dev_tris;
+    for (int a = 0; a < 3; ++a) { out->bounds_mn[a] = h.bounds_mn[a]; out->bounds_mx[a] = h.bounds_mx[a]; }
+    if (nodes > out->node_capacity || tris > out->tri_capacity || insts > out->instance_capacity || sinsts > out->shadow_instance_capacity || planes > out->plane_capacity ||
+        snodes > out->scene_node_capacity) return fail(NRAYS_ERR_BAD_ARG, "dump buffers too small");
+    HIP_TRY(hipSetDevice(sc->facts.device));
+    int rc = dump_array(out->nodes, d.nodes, nodes, sizeof(BvhNode), "nodes");
+    if (rc == NRAYS_OK) rc = dump_array(out->tris, d.tris, tris, sizeof(TriRec), "tris");
+    if (rc == NRAYS_OK) rc = dump_array(out->instances, d.instances, insts, sizeof(Instance), "instances");
+    if (rc == NRAYS_OK) rc = dump_array(out->shadow_instances, d.shadow_instances, sinsts, sizeof(Instance), "shadow_instances");
+    if (rc == NRAYS_OK) rc = dump_array(out->links, d.links, insts, sizeof(InstLink), "links");
+    if (rc == NRAYS_OK) rc = dump_array(out->shadow_links, d.shadow_links, sinsts, sizeof(InstLink), "shadow_links");
+    if (rc == NRAYS_OK) rc = dump_array(out->planes, d.planes, planes, sizeof(int32_t), "planes");
+    if (rc == NRAYS_OK) rc = dump_array(out->shadow_planes, d.shadow_planes, planes, sizeof(int32_t), "shadow_planes");
+    if (rc == NRAYS_OK) rc = dump_array(out->node_aabbs, d.node_aabbs, snodes * 6, sizeof(double), "node_aabbs");
+    return rc;
 }
 
 int nrays_untile_device(const float* gathered, float* out_rgb_device, uint32_t width, uint32_t height, uint32_t band_rows,

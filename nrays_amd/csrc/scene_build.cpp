@@ -45,15 +45,33 @@ void rotation_from_axis_angle(const double w[3], double R[9], bool& identity) {
     R[6] = ik - wj;           R[7] = wi + jk;           R[8] = ww - ii - jj + kk;
 }
 
-// Conservative f32 world box of a local box [c - h, c + h] under (R, t).
-PrimBounds world_box(const double R[9], const double t[3], const double c[3], const double h[3]) {
+// Conservative f32 world box of a local box [c - h, c + h] under (R, t): it contains the exact image of the local box under the stored R and t, and the AABB the
+// reference computes for every node inside that local box (node_world_aabb below), which the kernels gate accepted hits with — tests/scene_cover.py, S7 and S8.
+// With u = 2^-53 and S_i = sum_j |R_ij| |c_j| + |t_i| + sum_j |R_ij| h_j (every term of face i, taken positive), to first order in u:
+//   this function   wc: three products and three sums, <= 4 u of its terms; wh: three products, two sums, <= 3 u; the difference or sum of the two: u (|wc| + wh);
+//                   c and h themselves (halved sums of two f32 numbers, exact unless their exponents lie 29 apart): u (|c_j| + h_j).             <= 6 u S_i
+//   the reference   ball t -+ r: u.  Cuboid |R| h, then t -+ it: 4 u.  TriMesh: its own c and h (u), R c (3 u), + t (u), |R| h (3 u), the difference (u): the terms of a
+//                   member of a merged group are below the group's, |c_m| + h_m <= |c| + h on every axis.  Cylinder and cone: the support point's x and z are
+//                   d / sqrt(dx^2 + dz^2) * r, <= 4 u each, then R p (3 u) and + t (u): 8 u; in exact arithmetic r sqrt(R_i0^2 + R_i2^2) + hh |R_i1| is below the
+//                   bounding cylinder's |R| h.  Capsule: p = (dx r, +-hh + dy r, dz r) with d = row i of R as it is, 2 u, then R p and + t, 4 u: the extent is
+//                   r |row i|^2 + hh |R_i1|, and x^2 <= |x| holds up to |x| <= 1 only — an entry of R from rotation_from_axis_angle is at most
+//                   |q|^2 (1 + 4 u) <= 1 + 15 u (libm's sin and cos within an ulp, the axis 3.5 u, the quaternion 5.5 u per component), so 16 u r on top.   <= 22 u S_i
+// 28 u S_i in all; the margin is 32 u S_i = 2^-48 S_i (S_i in f64: eight more roundings, and one for applying it, inside the four to spare).
+// One f32 step of the RESULT, which is all the faces got before, is that much only while |face| >= 2^-24 S_i: where wc and wh cancel — a face in a coordinate plane of
+// the world — the result and its f32 step shrink and the error of the terms does not (a capsule resting on x = 0 got min x = +4.4e-16, above the reference's 0.0).
+// A face is the lower of the two (upper, for a maximum), so no box shrinks, and away from cancellation every face keeps its bits: there m <= one f32 step of the face.
+// `exact`: R is the identity, t is zero and c -+ h are the local box's own faces — local space is world space, every product and sum here and in the reference is exact
+// (a mesh face at 0.0 stays one f32 step below 0.0): no margin.
+PrimBounds world_box(const double R[9], const double t[3], const double c[3], const double h[3], bool exact = false) {
+    const double kMargin = exact ? 0.0 : 0x1p-48;
     PrimBounds b;
     for (int i = 0; i < 3; ++i) {
         double wc = R[3 * i] * c[0] + R[3 * i + 1] * c[1] + R[3 * i + 2] * c[2] + t[i];
         double wh = std::fabs(R[3 * i]) * h[0] + std::fabs(R[3 * i + 1]) * h[1] + std::fabs(R[3 * i + 2]) * h[2];
-        // outward f32 rounding plus one more ulp to absorb the f64 rounding of the transform itself
-        b.mn[i] = std::nextafterf(round_down_f32(wc - wh), -std::numeric_limits<float>::infinity());
-        b.mx[i] = std::nextafterf(round_up_f32(wc + wh), std::numeric_limits<float>::infinity());
+        const double m = kMargin * (std::fabs(R[3 * i]) * std::fabs(c[0]) + std::fabs(R[3 * i + 1]) * std::fabs(c[1]) + std::fabs(R[3 * i + 2]) * std::fabs(c[2]) + std::fabs(t[i]) + wh);
+        // outward f32 rounding plus one more ulp, or the margin where that is more
+        b.mn[i] = std::min(std::nextafterf(round_down_f32(wc - wh), -std::numeric_limits<float>::infinity()), round_down_f32((wc - wh) - m));
+        b.mx[i] = std::max(std::nextafterf(round_up_f32(wc + wh), std::numeric_limits<float>::infinity()), round_up_f32((wc + wh) + m));
     }
     return b;
 }
@@ -610,7 +628,8 @@ struct Flatten { // what crosses the phases, then the phases in the order run() 
             default: h[0] = h[2] = n.params[1]; h[1] = n.params[0]; break; // cylinder, cone
             }
             for (int a = 0; a < 3; ++a) h[a] = std::fabs(h[a]);
-            PrimBounds b = world_box(R, n.translation, c, h);
+            const bool at_origin = n.translation[0] == 0.0 && n.translation[1] == 0.0 && n.translation[2] == 0.0;
+            PrimBounds b = world_box(R, n.translation, c, h, at_origin && (n.shape_kind == NRAYS_SHAPE_BALL || info[i].identity));
             cinst.push_back(in); cbox.push_back(b);
             sinst.push_back(si); sbox.push_back(b);
         }
@@ -633,7 +652,9 @@ struct Flatten { // what crosses the phases, then the phases in the order run() 
         if (blas.hairy) { in.flags |= kInstIncoherent; out.any_incoherent = true; }
         double c[3], h[3];
         for (int a = 0; a < 3; ++a) { c[a] = 0.5 * ((double)blas.mn[a] + (double)blas.mx[a]); h[a] = 0.5 * ((double)blas.mx[a] - (double)blas.mn[a]); }
-        PrimBounds b = world_box(info[n0].R, d->nodes[n0].translation, c, h);
+        bool exact = no_xform(info[n0], d->nodes[n0]);
+        for (int a = 0; a < 3; ++a) exact = exact && c[a] - h[a] == (double)blas.mn[a] && c[a] + h[a] == (double)blas.mx[a];
+        PrimBounds b = world_box(info[n0].R, d->nodes[n0].translation, c, h, exact);
         if (use & kUseClosest) { cinst.push_back(in); cbox.push_back(b); }
         if (use & kUseShadow) { Instance si = in; if (use & kShadowAnyHit) si.flags |= kInstAnyHit; sinst.push_back(si); sbox.push_back(b); }
         return NRAYS_OK;

@@ -102,6 +102,7 @@ struct NraysScene {
         DScene d;
         std::vector<void*> allocs;
         uint64_t scene_bytes = 0; // device bytes of the uploaded scene arrays (BVH nodes, triangles, records, textures)
+        size_t num_nodes = 0, num_tris = 0; // entries of d.nodes / d.tris, device-built and host-built together (nrays_debug_scene_dump)
         int num_cus = 256;
         int features = nrays::kFeatAll;
         bool park = true;     // kFeatPark permutations for the three-wave multi-light kernels (Switches::park)

@@ -383,13 +383,27 @@ def scene_nodes(name):
     raise KeyError(name)
 
 
+def world_box_f32(lo, hi, terms=None):
+    """scene_build.cpp's world_box for an unrotated box with the f64 faces lo, hi (n x 3): each face rounded outward to f32 and moved one step further, or moved
+    outward by 2^-48 x `terms` (per axis |centre| + |translation| + half extent) and rounded outward, whichever is further out.  terms None: local space is world
+    space, every sum is exact, no margin.  Returns n x 6 f32."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+
+    def down(v):
+        f = v.astype(F32)
+        return np.where(f.astype(np.float64) > v, np.nextafter(f, F32(-np.inf)), f).astype(F32)
+    m = 0.0 if terms is None else 2.0 ** -48 * np.asarray(terms, np.float64)
+    mn = np.minimum(np.nextafter(down(lo), F32(-np.inf)), down(lo - m))
+    mx = np.maximum(np.nextafter(-down(-hi), F32(np.inf)), -down(-(hi + m)))
+    return np.concatenate([mn, mx], axis=1).astype(F32)
+
+
 def rungs_tree(shim):
-    """The shadow TLAS of scene (g) as scene_build.cpp builds it: one instance per rung, its box the triangle's widened by an f32 ulp (world_box),
-    one instance per leaf."""
+    """The shadow TLAS of scene (g) as scene_build.cpp builds it: one instance per rung, its box the triangle's widened by an f32 ulp (world_box: the rungs are
+    untransformed), one instance per leaf."""
     pts, idx, _, _ = ladder()
     tri = pts[idx.astype(np.int64)]
-    boxes = np.concatenate([np.nextafter(tri.min(axis=1), F32(-np.inf)), np.nextafter(tri.max(axis=1), F32(np.inf))], axis=1)
-    return shim.build_boxes(boxes, 1)
+    return shim.build_boxes(world_box_f32(tri.min(axis=1), tri.max(axis=1)), 1)
 
 
 def trees(shim):
@@ -597,13 +611,14 @@ def plates_cameras(n):
 
 def plates_reach(shim, key32=True, cam=None):
     """simulate() in closest-hit order, sort keys rounded to f32, over the TLAS scene_build.cpp builds (leaves of one, the boxes of world_box: the
-    plate's, an f32 ulp wider; a plate stands in as a triangle over its front face): the primary rays of the plates' frame, and for those that
+    plate's, an f32 ulp wider (world_box_f32); a plate stands in as a triangle over its front face): the primary rays of the plates' frame, and for those that
     meet a plate the ray that goes on from the plate's back in the same direction.  Returns (tree, heights of the primary rays, heights of the
     rays that go on (0 where there is none), the plate the primary ray meets or -1)."""
     x, h, y = _plates()
-    mn = np.stack([x - h, y - 2.0, np.full_like(x, -1.0)], axis=1).astype(F32)
-    mx = np.stack([x + h, y + 2.0, np.full_like(x, 3.0)], axis=1).astype(F32)
-    tree = shim.build_boxes(np.concatenate([np.nextafter(mn, F32(-np.inf)), np.nextafter(mx, F32(np.inf))], axis=1), 1)
+    mn = np.stack([x - h, y - 2.0, np.full_like(x, -1.0)], axis=1)
+    mx = np.stack([x + h, y + 2.0, np.full_like(x, 3.0)], axis=1)
+    terms = np.stack([np.abs(x) + h, np.abs(y) + 2.0, np.full_like(x, 3.0)], axis=1)   # (no face of a plate lies near a coordinate plane: the margin moves none of them)
+    tree = shim.build_boxes(world_box_f32(mn, mx, terms), 1)
     tris = np.zeros((len(x), 3, 3))
     tris[:, :, 0] = (x + h)[:, None]
     tris[:, :, 1] = (y - 2.0)[:, None] + np.array([0.0, 8.0, 0.0])

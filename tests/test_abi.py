@@ -37,7 +37,7 @@ def test_struct_layout_matches_c(built):
     """Compiles a tiny C program printing sizeof/offsetof of every ABI struct."""
     structs = {"NraysLight": abi.NraysLight, "NraysTexture": abi.NraysTexture, "NraysMaterial": abi.NraysMaterial,
                "NraysMesh": abi.NraysMesh, "NraysNode": abi.NraysNode, "NraysSceneDesc": abi.NraysSceneDesc,
-               "NraysRenderParams": abi.NraysRenderParams, "NraysStats": abi.NraysStats}
+               "NraysRenderParams": abi.NraysRenderParams, "NraysStats": abi.NraysStats, "NraysSceneDump": abi.NraysSceneDump}
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "nrays_abi.h"', 'int main(void){']
     for name, cls in structs.items():
         lines.append('printf("%s %%zu\\n", sizeof(%s));' % (name, name))
@@ -75,6 +75,8 @@ def test_null_arguments_are_errors_not_crashes(built):
     assert lib.nrays_debug_scene_flags(None, None) == abi.ERR_BAD_ARG
     assert lib.nrays_debug_last_permutation(None, None) == abi.ERR_BAD_ARG
     assert lib.nrays_debug_last_permutation(None, (C.c_uint32 * 6)()) == abi.ERR_BAD_ARG
+    assert lib.nrays_debug_scene_dump(None, None) == abi.ERR_BAD_ARG
+    assert lib.nrays_debug_scene_dump(None, C.byref(abi.NraysSceneDump())) == abi.ERR_BAD_ARG
     lib.nrays_scene_destroy(None)
 
 

@@ -3,7 +3,11 @@ branch of the builder — empty, every analytic shape, an untransformed quad, me
 that is pre-split, an area light, a rotated group, device-built BLASes (a deterministic fake) in front of host-built ones, and the refusals — and reports each HostScene
 member's length and FNV-1a digest plus the scalars.  They are compared with tests/golden/host_scene_digests.json, recorded from the builder before it was split into
 phases (`python tests/test_host_scene.py --record` rewrites the file).  Rotated cases go through libm's sin / cos: the golden file holds the bit patterns of the half-angle
-values it was recorded with, and only where this machine's differ are the rotated cases skipped.  No GPU.  tests/host_scene_main.cpp runs the cases under the sanitizers."""
+values it was recorded with, and only where this machine's differ are the rotated cases skipped.  No GPU.  tests/host_scene_main.cpp runs the cases under the sanitizers.
+
+What the digests do NOT prove: that the recorded scene is a correct one.  They pin the builder to itself — a box one ulp too tight, or a node missing from the shadow side
+of a grouping no case here has, is recorded and then defended.  Whether both TLASes hold and cover every node of a scene is tests/scene_cover.py's question, asked of a
+dump and the scene description without any code of the builder's (tests/test_scene_cover.py here, tests/test_scene_cover_gpu.py on the device's arrays)."""
 import ctypes as C
 import json
 import os
