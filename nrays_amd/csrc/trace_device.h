@@ -363,11 +363,13 @@ NR_DEV bool cast_cylinder(double hh, double r, const Xform& m, d3 o, d3 d, bool 
     return convex_interval_hit(t0, t1, n0, n1, ld, m, solid, out);
 }
 
-NR_DEV d3 cone_side_normal(d3 p, double hh, double k2) {
-    d3 g = D3(p.x, k2 * (hh - p.y), p.z);
-    double s = norm(g);
-    if (s == 0.0) return D3(0.0, 1.0, 0.0);
-    return g / s;
+// The side's outward normal at p is (x, k rho, z) / |.| with rho = |(x, z)|: on the surface k rho is k^2 (hh - y), but taken from rho the
+// normal keeps the side's slope whatever the rounding of p — close to the apex k^2 (hh - y) carries none of p's digits.
+NR_DEV d3 cone_side_normal(d3 p, double k) {
+    double rho = sqrt(p.x * p.x + p.z * p.z);
+    if (rho == 0.0) return D3(0.0, 1.0, 0.0);
+    d3 g = D3(p.x, k * rho, p.z);
+    return g / norm(g);
 }
 NR_DEV bool cast_cone(double hh, double r, const Xform& m, d3 o, d3 d, bool solid, Isect& out) {
     d3 lo = inv_rot(m, o - m.t), ld = inv_rot(m, d);
@@ -381,41 +383,55 @@ NR_DEV bool cast_cone(double hh, double r, const Xform& m, d3 o, d3 d, bool soli
         if (ta <= tb) { s0 = ta; s0_kind = 1; s1 = tb; s1_kind = 2; }
         else { s0 = tb; s0_kind = 2; s1 = ta; s1_kind = 1; }
     }
+    // The quadratic A u^2 + 2 B u + C of the double cone is formed about p = o + tc d, the ray's point nearest the apex, and its roots are
+    // moved back by tc.  From a far origin B and C are small differences of large terms for a ray that passes the apex or runs along a
+    // generator close to the side: toi lost up to 1e-7 there although the entry is well conditioned (DESIGN D-3).
+    double dd = dot(ld, ld);
+    double tc = dd > 0.0 ? -(lo.x * ld.x + lo.z * ld.z + ow * dw) / dd : 0.0;
+    double px = lo.x + ld.x * tc, pz = lo.z + ld.z * tc, pw = ow + dw * tc;
     double A = ld.x * ld.x + ld.z * ld.z - k2 * dw * dw;
-    double B = lo.x * ld.x + lo.z * ld.z - k2 * ow * dw;
-    double C = lo.x * lo.x + lo.z * lo.z - k2 * ow * ow;
+    double B = px * ld.x + pz * ld.z - k2 * pw * dw;
+    double C = px * px + pz * pz - k2 * pw * pw;
     double t0 = s0, t1 = s1;
     int k0 = s0_kind, k1 = s1_kind;
+    // Both roots of A t^2 + 2 B t + C come from the stable pair q = -(B + copysign(sq, B)): q / A and C / q.  A ray nearly
+    // parallel to a generator has a tiny A, and (-B +- sq) / A cancels in the root that matters (DESIGN D-3).
     if (A > 0.0) {
         double disc = B * B - A * C;
         if (disc < 0.0) return false;
         double sq = sqrt(disc);
-        double ra = (-B - sq) / A, rb = (-B + sq) / A;
+        double q = -(B + copysign(sq, B));
+        double r1 = q / A, r2 = q != 0.0 ? C / q : r1;
+        r1 += tc; r2 += tc;
+        double ra = r1 < r2 ? r1 : r2, rb = r1 < r2 ? r2 : r1;
         if (ra > t0) { t0 = ra; k0 = 0; }
         if (rb < t1) { t1 = rb; k1 = 0; }
     } else if (A < 0.0) {
         double disc = B * B - A * C;
         if (disc > 0.0) {
             double sq = sqrt(disc);
-            double lo_r = (-B + sq) / A, hi_r = (-B - sq) / A;
-            double a1 = hi_r > s0 ? hi_r : s0;
-            double b0 = lo_r < s1 ? lo_r : s1;
-            if (a1 <= s1) { if (hi_r > s0) { t0 = hi_r; k0 = 0; } }
-            else if (s0 <= b0) { if (lo_r < s1) { t1 = lo_r; k1 = 0; } }
-            else return false;
+            double q = -(B + copysign(sq, B));
+            double r1 = q / A, r2 = C / q; // disc > 0: q != 0
+            r1 += tc; r2 += tc;
+            double lo_r = r1 < r2 ? r1 : r2, hi_r = r1 < r2 ? r2 : r1; // inside the double cone for t <= lo_r or t >= hi_r
+            // The apex plane is crossed between the roots, so the nappe below the apex (w > 0) is the one at t >= hi_r when w grows along the ray
+            // and the one at t <= lo_r when it shrinks.  (Trying [max(s0,hi_r), s1] first and [s0, min(s1,lo_r)] second took the mirror nappe's
+            // root for a ray that leaves through the apex itself, where hi_r == s1 up to rounding.)
+            if (dw > 0.0) { if (hi_r > s0) { t0 = hi_r; k0 = 0; } }
+            else { if (lo_r < s1) { t1 = lo_r; k1 = 0; } }
         }
     } else {
         if (B == 0.0) { if (C > 0.0) return false; }
         else {
-            double ts = -C / (2.0 * B);
+            double ts = -C / (2.0 * B) + tc;
             if (B > 0.0) { if (ts < t1) { t1 = ts; k1 = 0; } }
             else { if (ts > t0) { t0 = ts; k0 = 0; } }
         }
     }
     if (!(t0 <= t1) || t1 < 0.0) return false;
     d3 n0, n1;
-    if (k0 == 0) n0 = cone_side_normal(lo + ld * t0, hh, k2); else n0 = D3(0.0, k0 == 1 ? 1.0 : -1.0, 0.0);
-    if (k1 == 0) n1 = cone_side_normal(lo + ld * t1, hh, k2); else n1 = D3(0.0, k1 == 1 ? 1.0 : -1.0, 0.0);
+    if (k0 == 0) n0 = cone_side_normal(lo + ld * t0, k); else n0 = D3(0.0, k0 == 1 ? 1.0 : -1.0, 0.0);
+    if (k1 == 0) n1 = cone_side_normal(lo + ld * t1, k); else n1 = D3(0.0, k1 == 1 ? 1.0 : -1.0, 0.0);
     return convex_interval_hit(t0, t1, n0, n1, ld, m, solid, out);
 }
 
@@ -434,20 +450,21 @@ NR_DEV bool cast_capsule(double hh, double r, const Xform& m, d3 o, d3 d, bool s
             if (disc < 0.0) ok = false;
             else { double sq = sqrt(disc); a0 = (-B - sq) / A; a1 = (-B + sq) / A; }
         }
-        bool e_side = true, x_side = true;
         if (ok) {
             if (ld.y == 0.0) { if (lo.y < -hh || lo.y > hh) ok = false; }
             else {
                 double ta = (-hh - lo.y) / ld.y, tb = (hh - lo.y) / ld.y;
                 if (ta > tb) { double s = ta; ta = tb; tb = s; }
-                if (ta > a0) { a0 = ta; e_side = false; }
-                if (tb < a1) { a1 = tb; x_side = false; }
+                if (ta > a0) a0 = ta;
+                if (tb < a1) a1 = tb;
             }
         }
         if (ok && a0 <= a1) {
+            // A bound on an end plane lies in that end's ball, which takes it over below on a strict improvement.  On the seam circle itself
+            // the two coincide and rounding may leave the plane's bound standing: its normal is the radial one there, as on the side.
             t0 = a0; t1 = a1;
-            if (e_side) { d3 p = lo + ld * a0; n0 = D3(p.x / r, 0.0, p.z / r); }
-            if (x_side) { d3 p = lo + ld * a1; n1 = D3(p.x / r, 0.0, p.z / r); }
+            { d3 p = lo + ld * a0; n0 = D3(p.x / r, 0.0, p.z / r); }
+            { d3 p = lo + ld * a1; n1 = D3(p.x / r, 0.0, p.z / r); }
         }
     }
 #pragma unroll

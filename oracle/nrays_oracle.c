@@ -454,11 +454,13 @@ static int cast_cylinder(double hh, double r, const Iso* iso, const Ray* ray, in
 }
 
 /* D-3 Cone(half_height, radius): apex at (0,+hh,0), base disc at y = -hh. */
-static v3 cone_side_normal(v3 p, double hh, double k2) {
-    v3 g = V(p.x, k2 * (hh - p.y), p.z);
-    double s = vnorm(g);
-    if (s == 0.0) return V(0.0, 1.0, 0.0);
-    return vdiv(g, s);
+/* The side's outward normal at p is (x, k rho, z) / |.| with rho = |(x, z)|: on the surface k rho is k^2 (hh - y), but taken from rho the
+ * normal keeps the side's slope whatever the rounding of p — close to the apex k^2 (hh - y) carries none of p's digits. */
+static v3 cone_side_normal(v3 p, double k) {
+    double rho = sqrt(p.x * p.x + p.z * p.z);
+    if (rho == 0.0) return V(0.0, 1.0, 0.0);
+    v3 g = V(p.x, k * rho, p.z);
+    return vdiv(g, vnorm(g));
 }
 static int cast_cone(double hh, double r, const Iso* iso, const Ray* ray, int solid, Inter* out) {
     Ray l = iso_inv_ray(iso, ray);
@@ -472,41 +474,55 @@ static int cast_cone(double hh, double r, const Iso* iso, const Ray* ray, int so
         if (ta <= tb) { s0 = ta; s0_kind = 1; s1 = tb; s1_kind = 2; }
         else { s0 = tb; s0_kind = 2; s1 = ta; s1_kind = 1; }
     }
+    /* The quadratic A u^2 + 2 B u + C of the double cone is formed about p = o + tc d, the ray's point nearest the apex, and its roots are
+     * moved back by tc.  From a far origin B and C are small differences of large terms for a ray that passes the apex or runs along a
+     * generator close to the side: toi lost up to 1e-7 there although the entry is well conditioned (DESIGN D-3). */
+    double dd = vdot(l.d, l.d);
+    double tc = dd > 0.0 ? -(l.o.x * l.d.x + l.o.z * l.d.z + ow * dw) / dd : 0.0;
+    double px = l.o.x + l.d.x * tc, pz = l.o.z + l.d.z * tc, pw = ow + dw * tc;
     double A = l.d.x * l.d.x + l.d.z * l.d.z - k2 * dw * dw;
-    double B = l.o.x * l.d.x + l.o.z * l.d.z - k2 * ow * dw;
-    double C = l.o.x * l.o.x + l.o.z * l.o.z - k2 * ow * ow;
+    double B = px * l.d.x + pz * l.d.z - k2 * pw * dw;
+    double C = px * px + pz * pz - k2 * pw * pw;
     double t0 = s0, t1 = s1;
     int k0 = s0_kind, k1 = s1_kind; /* 0 = lateral surface */
+    /* Both roots of A t^2 + 2 B t + C come from the stable pair q = -(B + copysign(sq, B)): q / A and C / q.  A ray nearly
+     * parallel to a generator has a tiny A, and (-B +- sq) / A cancels in the root that matters (DESIGN D-3). */
     if (A > 0.0) {
         double disc = B * B - A * C;
         if (disc < 0.0) return 0;
         double sq = sqrt(disc);
-        double ra = (-B - sq) / A, rb = (-B + sq) / A;
+        double q = -(B + copysign(sq, B));
+        double r1 = q / A, r2 = q != 0.0 ? C / q : r1;
+        r1 += tc; r2 += tc;
+        double ra = r1 < r2 ? r1 : r2, rb = r1 < r2 ? r2 : r1;
         if (ra > t0) { t0 = ra; k0 = 0; }
         if (rb < t1) { t1 = rb; k1 = 0; }
     } else if (A < 0.0) {
         double disc = B * B - A * C;
         if (disc > 0.0) {
             double sq = sqrt(disc);
-            double lo = (-B + sq) / A, hi = (-B - sq) / A; /* lo < hi; inside the double cone for t<=lo or t>=hi */
-            double a1 = hi > s0 ? hi : s0; /* candidate [max(s0,hi), s1] */
-            double b0 = lo < s1 ? lo : s1; /* candidate [s0, min(s1,lo)] */
-            if (a1 <= s1) { if (hi > s0) { t0 = hi; k0 = 0; } }
-            else if (s0 <= b0) { if (lo < s1) { t1 = lo; k1 = 0; } }
-            else return 0;
+            double q = -(B + copysign(sq, B));
+            double r1 = q / A, r2 = C / q; /* disc > 0: q != 0 */
+            r1 += tc; r2 += tc;
+            double lo = r1 < r2 ? r1 : r2, hi = r1 < r2 ? r2 : r1; /* lo < hi; inside the double cone for t<=lo or t>=hi */
+            /* The apex plane is crossed between the roots, so the nappe below the apex (w > 0) is the one at t >= hi when w grows along the ray
+             * and the one at t <= lo when it shrinks.  (Trying [max(s0,hi), s1] first and [s0, min(s1,lo)] second took the mirror nappe's root
+             * for a ray that leaves through the apex itself, where hi == s1 up to rounding.) */
+            if (dw > 0.0) { if (hi > s0) { t0 = hi; k0 = 0; } }
+            else { if (lo < s1) { t1 = lo; k1 = 0; } }
         }
     } else {
         if (B == 0.0) { if (C > 0.0) return 0; }
         else {
-            double ts = -C / (2.0 * B);
+            double ts = -C / (2.0 * B) + tc;
             if (B > 0.0) { if (ts < t1) { t1 = ts; k1 = 0; } }
             else { if (ts > t0) { t0 = ts; k0 = 0; } }
         }
     }
     if (!(t0 <= t1) || t1 < 0.0) return 0;
     v3 n0, n1;
-    if (k0 == 0) n0 = cone_side_normal(vadd(l.o, vmul(l.d, t0)), hh, k2); else n0 = V(0.0, k0 == 1 ? 1.0 : -1.0, 0.0);
-    if (k1 == 0) n1 = cone_side_normal(vadd(l.o, vmul(l.d, t1)), hh, k2); else n1 = V(0.0, k1 == 1 ? 1.0 : -1.0, 0.0);
+    if (k0 == 0) n0 = cone_side_normal(vadd(l.o, vmul(l.d, t0)), k); else n0 = V(0.0, k0 == 1 ? 1.0 : -1.0, 0.0);
+    if (k1 == 0) n1 = cone_side_normal(vadd(l.o, vmul(l.d, t1)), k); else n1 = V(0.0, k1 == 1 ? 1.0 : -1.0, 0.0);
     return convex_interval_hit(t0, t1, n0, n1, &l, iso, solid, out);
 }
 
@@ -527,20 +543,21 @@ static int cast_capsule(double hh, double r, const Iso* iso, const Ray* ray, int
             if (disc < 0.0) ok = 0;
             else { double sq = sqrt(disc); a0 = (-B - sq) / A; a1 = (-B + sq) / A; }
         }
-        int e_side = 1, x_side = 1;
         if (ok) {
             if (l.d.y == 0.0) { if (l.o.y < -hh || l.o.y > hh) ok = 0; }
             else {
                 double ta = (-hh - l.o.y) / l.d.y, tb = (hh - l.o.y) / l.d.y;
                 if (ta > tb) { double s = ta; ta = tb; tb = s; }
-                if (ta > a0) { a0 = ta; e_side = 0; }
-                if (tb < a1) { a1 = tb; x_side = 0; }
+                if (ta > a0) a0 = ta;
+                if (tb < a1) a1 = tb;
             }
         }
         if (ok && a0 <= a1) {
+            /* A bound on an end plane lies in that end's ball, which takes it over below on a strict improvement.  On the seam circle itself
+             * the two coincide and rounding may leave the plane's bound standing: its normal is the radial one there, as on the side. */
             t0 = a0; t1 = a1;
-            if (e_side) { v3 p = vadd(l.o, vmul(l.d, a0)); n0 = V(p.x / r, 0.0, p.z / r); }
-            if (x_side) { v3 p = vadd(l.o, vmul(l.d, a1)); n1 = V(p.x / r, 0.0, p.z / r); }
+            { v3 p = vadd(l.o, vmul(l.d, a0)); n0 = V(p.x / r, 0.0, p.z / r); }
+            { v3 p = vadd(l.o, vmul(l.d, a1)); n1 = V(p.x / r, 0.0, p.z / r); }
         }
     }
     for (int s = 0; s < 2; ++s) { /* the two end balls; they own the bound on a strict improvement */
