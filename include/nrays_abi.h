@@ -165,7 +165,10 @@ typedef struct NraysRenderParams {
     uint64_t seed;            /* counter-based RNG seed (reference RNG is OS-seeded, scene.rs:75) */
     /* Framebuffer tiling (multi-GPU): rows are grouped in bands of `band_rows`; band b is rendered
      * iff b % band_owners == band_owner.  band_rows == 0 renders the whole frame.  The output of a
-     * tiled render is the compact buffer of the owner's bands in increasing order. */
+     * tiled render is the compact buffer of the owner's bands in increasing order: nrays_tile_rows(params)
+     * rows, the same for every owner.  The rows of it behind the owner's last real row — the part of a
+     * ragged last band below the frame, and a whole band where the owner holds one band fewer than others —
+     * are padding rows: every render writes them, as exactly +0.0 in every float (0 in nrays_render_rgb8). */
     uint32_t band_rows;
     uint32_t band_owner;
     uint32_t band_owners;
