@@ -1,5 +1,5 @@
 // batch_call.h — the driver every caller-batch entry point runs through (batch_call.cpp; host only, no kernels).  A family — trace, intersects, cast, shade,
-// material (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, probe_depth, irradiance (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
+// material (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, gather_maps_sh, probe_depth, irradiance, nearest (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
 // nrays_debug_cast_batch and nrays_debug_occlusion_rays — is four things of its own ("Adding a family on the C++ side"): its argument check (with the
 // n == 0 return, before any HIP call), its column table (batch_stage.h), its launch struct with a launch_if chain, and its chunk lambda.  The driver holds the rest once:
 //   batch_open    hipSetDevice, the handle's batch workspace, the family's own workspace (`ensure`), the staging arena, the stream — the caller's for the
@@ -73,7 +73,7 @@ int launch_status(const char* kernel); // after a launch: hipGetLastError() as N
 int no_permutation(const char* kernel); // NRAYS_ERR_UNSUPPORTED, "<kernel>: no such permutation"
 // What the families at surface points share: the check of the hemisphere's tables and bias ("null argument" or "<struct_name>: ..."; `with` / `with_finite`: a value of
 // the struct reported together with the bias), the generator's view of them (max_toi 0) and the kernels' view of a chunk's point columns kPointPoints .. kPointKeys.
-struct GatherPoints; struct OcclusionSpec; // ray_batch_kernel.h
+struct GatherPoints; struct OcclusionSpec; // hemisphere_device.h
 int check_hemisphere(const char* struct_name, const double* dirs, uint32_t num_dirs, const double* rotations, uint32_t num_rotations, double bias, const char* with = nullptr,
                      bool with_finite = true);
 OcclusionSpec hemisphere_spec(uint32_t num_dirs, uint32_t num_rotations, double bias);

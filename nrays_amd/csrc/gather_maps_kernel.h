@@ -1,7 +1,7 @@
 // gather_maps_kernel.h — k_gather_maps_points (nrays_gather_maps_points*): the light that baked maps hold at the closest hits of a point's hemisphere rays, folded
-// into one mean colour per point — one diffuse bounce of a light-map baker, on the device.  The rays are k_occlusion_points' (occlusion_frame / occlusion_dir),
-// the query is k_cast_rays' (ungated traversal, resolve_hit, the gated repeat), the sample is the materials' (tex_sample) and the fold is k_occlusion_points'
-// (2^LP lanes a point, added in the order of the directions through __shfl).  The definition is include/nrays_abi.h (NraysGatherMapsParams).
+// into one mean colour per point — one diffuse bounce of a light-map baker, on the device.  The rays, the lanes of a point and the mean are
+// hemisphere_device.h's (point_lane, point_frame_live, hemisphere_dir, store_mean), the query is closest_hit (trace_device.h), the sample is the materials'
+// (tex_sample) and the fold is the ordered one: 2^LP lanes a point, added in the order of the directions through __shfl.  The definition is include/nrays_abi.h (NraysGatherMapsParams).
 // Templates and inline device code only: gather_maps_inst.hip instantiates the kernel, point_batches.hip launches it through launch_gather_maps_points.
 #pragma once
 #include "../../include/nrays_abi.h"
@@ -15,21 +15,6 @@ struct GatherMapsSpec { uint32_t num_dirs, num_rotations; double bias, max_toi; 
 // The class of a ray's contribution; k_gather_maps_points counts the mapped and the missed ones.
 constexpr uint32_t kGatherDark = 0u, kGatherMapped = 1u, kGatherMissed = 2u;
 
-// The closest-hit query of cast_rays_body on ray (o, d), unbounded: the ungated traversal, the winner checked against the exact gates, the gated repeat.  true = a hit,
-// with `hit`, `is` and `node_id` its record.  k_gather_maps_points and k_gather_maps_rays (gather_maps_sh_kernel.h) run it once per ray.
-template <int FEAT>
-NR_DEV bool gather_maps_query(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, Hit& hit, Isect& is, uint32_t& node_id) {
-    f3 filter = F3(1.0f, 1.0f, 1.0f);
-    bool gated = false, any = false;
-    node_id = 0;
-    for (;;) {
-        any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
-        if (!any) break;
-        if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
-        gated = true;
-    }
-    return any;
-}
 // The finished query -> its contribution and class; `any`: a hit that max_toi kept.  A miss brings P.miss; a hit on a node whose node_map entry names a map, with a
 // record that carries a uv, brings x, y, z of Texture2d::sample of that map at the record's (u, v) — tex_sample, the value the library's materials get; every other
 // hit is dark (+0).  Transparency and the side of the surface are not looked at.
@@ -49,14 +34,14 @@ template <int FEAT>
 NR_DEV f3 gather_maps_ray(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, const GatherMapsSpec& P, const GatherMapsTable& M, const int32_t* __restrict__ node_map,
                           uint32_t& cls) {
     Hit hit; Isect is; uint32_t node_id;
-    bool any = gather_maps_query<FEAT>(S, st, cnt, o, d, hit, is, node_id);
+    bool any = closest_hit<FEAT>(S, st, cnt, o, d, hit, is, node_id);
     if (any) any = hit.t <= P.max_toi;
     return gather_maps_contribution(any, is, node_id, cnt, P, M, node_map, cls);
 }
 
 // Point i of the chunk: its num_dirs rays, each through gather_maps_ray, folded in the order of the directions — f32 sum, then ONE division by (float)num_dirs;
-// out_counts[2i], [2i + 1] count the mapped and the missed rays.  The lanes of a point, the rounds and the shuffles are k_occlusion_points'; the two counts are
-// per-lane integers folded through the same shuffles.  The frame is built once per point, as there: what stays live across the traversal is the closest-hit
+// out_counts[2i], [2i + 1] count the mapped and the missed rays.  The two counts are per-lane integers: a ray's class goes through the shuffles
+// beside its colour.  The frame is built once per point: what stays live across the traversal is the closest-hit
 // query's own state, which fits (profiles/gather_maps_kres.txt: no scratch).
 // A point whose flag bit 0 is clear is skipped: zeros, no traversal, neither its point nor its normal read.  NULL keys: key_base + i.
 template <int FEAT, int LP>
@@ -66,7 +51,6 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_maps_po
                                                                                       const int32_t* __restrict__ node_map, const double* __restrict__ dirs,
                                                                                       const double* __restrict__ rotations, float* __restrict__ out_rgb,
                                                                                       uint32_t* __restrict__ out_counts, uint32_t* spill) {
-    static_assert(LP >= 0 && LP <= 6, "the lanes of a point share a wave");
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
@@ -74,25 +58,18 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_maps_po
     const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
     const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
+    const GatherPoints in{points, normals, hit_flags, keys, key_base};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
-        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
-        const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
-        OccFrame f;
-        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
-        if (live) {
-            const size_t i3 = 3 * (size_t)i;
-            f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), keys ? keys[i] : key_base + i, G, rotations);
-        }
+        const PointLane L = point_lane<LP>(base, n, in);
+        OccFrame f = neutral_frame();
+        if (L.live) f = point_frame_live(in, L.i, G, rotations);
         f3 sum = F3(0.0f, 0.0f, 0.0f);
         uint32_t mapped = 0u, missed = 0u;
         for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
-            const uint32_t j = j0 + sub;
+            const uint32_t j = j0 + L.sub;
             f3 c = F3(0.0f, 0.0f, 0.0f);
             uint32_t cls = kGatherDark;
-            if (live && j < k) {
-                const d3 d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
-                c = gather_maps_ray<FEAT>(S, st, cnt, f.o, d, P, M, node_map, cls);
-            }
+            if (L.live && j < k) c = gather_maps_ray<FEAT>(S, st, cnt, f.o, hemisphere_dir(f, rotate, dirs, j), P, M, node_map, cls);
             if constexpr (LP == 0) {
                 sum.x += c.x; sum.y += c.y; sum.z += c.z; // (a skipped point's contribution is +0, its class dark)
                 mapped += cls == kGatherMapped ? 1u : 0u; missed += cls == kGatherMissed ? 1u : 0u;
@@ -105,10 +82,9 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_maps_po
                 }
             }
         }
-        if (i < n && sub == 0u) {
-            const float fk = (float)k;
-            out_rgb[3 * (size_t)i] = sum.x / fk; out_rgb[3 * (size_t)i + 1] = sum.y / fk; out_rgb[3 * (size_t)i + 2] = sum.z / fk;
-            if (out_counts) { out_counts[2 * (size_t)i] = mapped; out_counts[2 * (size_t)i + 1] = missed; }
+        if (L.i < n && L.sub == 0u) {
+            store_mean(out_rgb, L.i, sum, k);
+            if (out_counts) { out_counts[2 * (size_t)L.i] = mapped; out_counts[2 * (size_t)L.i + 1] = missed; }
         }
     }
 }

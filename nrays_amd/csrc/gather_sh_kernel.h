@@ -57,22 +57,14 @@ __global__ void __launch_bounds__(kShBlock) k_gather_fold_sh(const float* __rest
     for (uint32_t base = blockIdx.x * kShGroups; base < n; base += gridDim.x * kShGroups) { // block-uniform trip count
         const uint32_t i = base + g;
         const bool live = i < n && gather_point_live(in, i); // (the same for all lanes of a point)
-        OccFrame f;
-        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
-        if (live) {
-            const size_t i3 = 3 * (size_t)i;
-            f = occlusion_frame(D3(in.points[i3], in.points[i3 + 1], in.points[i3 + 2]), D3(in.normals[i3], in.normals[i3 + 1], in.normals[i3 + 2]),
-                                gather_point_key(in, i), G, rotations);
-        }
+        OccFrame f = neutral_frame();
+        if (live) f = point_frame_live(in, i, G, rotations);
         const float* src = rays + 3 * (size_t)i * k; // (dereferenced for live points only)
         float acc = 0.0f;
         for (uint32_t j0 = 0; j0 < k; j0 += kShGroup) { // block-uniform trip count: the barriers below are reached by every thread
             const uint32_t m = k - j0 < kShGroup ? k - j0 : kShGroup; // directions of this tile
             if (live) {
-                if (lane < m) {
-                    const size_t j3 = 3 * (size_t)(j0 + lane);
-                    sh_basis_store(occlusion_dir(f, rotate, dirs[j3], dirs[j3 + 1], dirs[j3 + 2]), C, y + lane * kShMaxCoef);
-                }
+                if (lane < m) sh_basis_store(hemisphere_dir(f, rotate, dirs, j0 + lane), C, y + lane * kShMaxCoef);
                 for (uint32_t t = lane; t < 3u * m; t += kShGroup) col[t] = src[3 * (size_t)j0 + t];
             }
             __syncthreads();

@@ -5,7 +5,8 @@
 // folds), and the one family at points that builds no ray:
 // nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here), and the one that takes points anywhere in space:
 // nrays_nearest_points* (k_nearest_points of nearest_kernel.h: nearest_inst.hip).  Also three probes: nrays_debug_occlusion_rays (k_occlusion_rays), nrays_debug_gather_sh_fold and
-// nrays_debug_nearest_bound.
+// nrays_debug_nearest_bound.  What the hemisphere kernels share on the device is hemisphere_device.h; what the two maps families and the three callers of
+// k_gather_fold_sh share on the host is here (maps_texels, maps_spec, maps_table, launch_gather_fold_sh).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -87,11 +88,17 @@ __global__ void __launch_bounds__(kFoldBlock) k_gather_fold(const float* __restr
     const float* c = rays + 3 * (size_t)i * k;
     float x = 0.0f, y = 0.0f, z = 0.0f;
     for (uint32_t j = 0; j < k; ++j) { x += c[3 * j]; y += c[3 * j + 1]; z += c[3 * j + 2]; }
-    const float fk = (float)k;
+    const float fk = (float)k; // (store_mean, kept as text: through the call this kernel compiles to other instructions)
     out[3 * (size_t)i] = x / fk; out[3 * (size_t)i + 1] = y / fk; out[3 * (size_t)i + 2] = z / fk;
 }
+// k_gather_fold_sh (gather_sh_kernel.h) on the finished colours `rays` of a chunk's nc points: 3 * bands^2 floats a point to `out`.
+static void launch_gather_fold_sh(hipStream_t stream, const float* rays, uint32_t nc, const GatherPoints& pts, const OcclusionSpec& hemi, const double* dirs, const double* rotations,
+                                  uint32_t bands, float* out) {
+    const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
+    hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, rays, nc, pts, hemi, dirs, rotations, bands * bands, out);
+}
 // One chunk (nc <= point_chunk) of nrays_gather_points*; `pts` and `out` are the chunk's, dirs / rotations
-// device copies of the tables.  The permutation is launch_trace_rays', the lanes per point are k_occlusion_points'.  Double-branching scenes: the kernel stores the
+// device copies of the tables.  The permutation is launch_trace_rays', the lanes per point are occlusion_lanes_log2's.  Double-branching scenes: the kernel stores the
 // chunk's ray colours, the rounds of queued_trace_finish run over the queued second children with a ray as the "pixel" (queue and sums sized by the chunk's RAYS, by queued_trace_begin's
 // rule), and k_gather_fold folds: the only case with per-ray memory, 36 bytes a ray of the workspace beside the queue.
 // `reorder` (a hinted call that pays, nrays_gather_points*_ex): the chunk's pairs are binned (gather_order_chunk) and traced in bin order by k_gather_pairs_ordered, every
@@ -130,12 +137,8 @@ static int gather_chunk_launch(NraysScene* sc, TraceWorkspace* w, uint32_t nc, c
     if (!ray_out) return NRAYS_OK;
     if (queued) rc = queued_trace_finish(sc, w, pairs, p->max_depth, ray_out, "gathered", stream);
     if (rc != NRAYS_OK && rc != NRAYS_ERR_QUEUE_OVERFLOW) return rc; // (an overflow: the incomplete colours are folded all the same, and the status is the call's)
-    if (bands) {
-        const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
-        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, stream, (const float*)ray_out, nc, pts, hemi, dirs, rotations, bands * bands, out);
-    } else {
-        hipLaunchKernelGGL(k_gather_fold, dim3((nc + kFoldBlock - 1u) / kFoldBlock), dim3(kFoldBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
-    }
+    if (bands) launch_gather_fold_sh(stream, ray_out, nc, pts, hemi, dirs, rotations, bands, out);
+    else hipLaunchKernelGGL(k_gather_fold, dim3((nc + kFoldBlock - 1u) / kFoldBlock), dim3(kFoldBlock), 0, stream, (const float*)ray_out, nc, p->num_dirs, out);
     HIP_TRY(hipGetLastError());
     return rc;
 }
@@ -172,24 +175,36 @@ static int check_gather_maps_args(const NraysScene* sc, const double* points, co
     if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_gather_maps_points: flags must be 0");
     return NRAYS_OK;
 }
+// What the two maps families make of the checked parameters: the host side of the texel columns, the kernels' spec, and per chunk the kernels' view of the maps —
+// the map records as the shading records hold a texture (ShadeTex), at the chunk's texel addresses, columns first_texel_column .. of c.
+static void maps_texels(const NraysGatherMapsParams* p, const void** texels, size_t* texel_count) {
+    for (uint32_t m = 0; m < p->num_maps; ++m) { texels[m] = p->maps[m].texels; texel_count[m] = (size_t)p->maps[m].width * p->maps[m].height; }
+}
+static GatherMapsSpec maps_spec(const NraysGatherMapsParams* p) {
+    return GatherMapsSpec{p->num_dirs, p->num_rotations, p->bias, p->max_toi, p->num_maps, p->num_nodes, {p->miss_rgb[0], p->miss_rgb[1], p->miss_rgb[2]}};
+}
+static GatherMapsTable maps_table(const NraysGatherMapsParams* p, void* const* c, int first_texel_column) {
+    GatherMapsTable table;
+    std::memset(&table, 0, sizeof table);
+    for (uint32_t m = 0; m < p->num_maps; ++m) {
+        const NraysTexture& s = p->maps[m];
+        table.map[m].texels = c[first_texel_column + m]; table.map[m].width = s.width; table.map[m].height = s.height; table.map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
+    }
+    return table;
+}
 static int gather_maps_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys, const NraysGatherMapsParams* p,
                             float* out_rgb, uint32_t* out_counts, uint32_t flags, bool staged, hipStream_t stream) {
     if (check_gather_maps_args(sc, points, normals, p, out_rgb, flags) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     const void* texels[NRAYS_GATHER_MAX_MAPS]; size_t texel_count[NRAYS_GATHER_MAX_MAPS];
-    for (uint32_t m = 0; m < p->num_maps; ++m) { texels[m] = p->maps[m].texels; texel_count[m] = (size_t)p->maps[m].width * p->maps[m].height; }
+    maps_texels(p, texels, texel_count);
     StageColumn cols[kMapsTexels + NRAYS_GATHER_MAX_MAPS];
     point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, hit_flags, keys);
     const int ncols = gather_maps_columns(cols, out_rgb, out_counts, p->node_map, p->num_nodes, p->num_maps, texels, texel_count);
-    const GatherMapsSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_toi, p->num_maps, p->num_nodes, {p->miss_rgb[0], p->miss_rgb[1], p->miss_rgb[2]}};
-    // One chunk (nc <= point_chunk).  The permutation is k_cast_rays', the lanes per point are k_occlusion_points'.
+    const GatherMapsSpec spec = maps_spec(p);
+    // One chunk (nc <= point_chunk).  The permutation is the traversal's (traversal_feat), the lanes per point are occlusion_lanes_log2's.
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
-        GatherMapsTable table; // the kernel's view of the checked parameters: the map records as the shading records hold a texture (ShadeTex), at the chunk's texel addresses
-        std::memset(&table, 0, sizeof table);
-        for (uint32_t m = 0; m < p->num_maps; ++m) {
-            const NraysTexture& s = p->maps[m];
-            table.map[m].texels = c[kMapsTexels + m]; table.map[m].width = s.width; table.map[m].height = s.height; table.map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
-        }
+        const GatherMapsTable table = maps_table(p, c, kMapsTexels);
         const int lp = occlusion_lanes_log2(sc, p->num_dirs); // (nc * num_dirs <= kTraceChunk and 2^lp <= num_dirs)
         const GatherMapsLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, chunk_points(c, key_base), spec, &table, (const int32_t*)c[kMapsNodeMap],
                                  (const double*)c[kPointDirs], (const double*)c[kPointRotations], (float*)c[kMapsRgb], (uint32_t*)c[kMapsCounts], b.w->d_spill};
@@ -220,7 +235,7 @@ static int probe_depth_impl(NraysScene* sc, uint32_t n, const double* points, co
     point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, hit_flags, keys);
     probe_depth_columns(cols, out_moments, p->res, out_counts, out_nearest, out_nearest_dir);
     const ProbeDepthSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_dist, p->near_dist, p->res};
-    // One chunk (nc <= point_chunk): the trace (the permutation is k_cast_rays', the lanes per point are k_occlusion_points') leaves rf of the chunk's rays in the
+    // One chunk (nc <= point_chunk): the trace (the permutation is the traversal's, the lanes per point are occlusion_lanes_log2's) leaves rf of the chunk's rays in the
     // workspace, 4 bytes a ray, and the fold reads them in the order of j.
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
         const size_t rays = (size_t)nc * p->num_dirs; // (<= kTraceChunk, or one point's)
@@ -250,25 +265,20 @@ static int gather_maps_sh_impl(NraysScene* sc, uint32_t n, const double* points,
     if (depth && check_depth_settings("NraysGatherDepthSpec", depth->max_dist, depth->near_dist, depth->res, depth->reserved) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
     if (n == 0) return NRAYS_OK;
     const void* texels[NRAYS_GATHER_MAX_MAPS]; size_t texel_count[NRAYS_GATHER_MAX_MAPS];
-    for (uint32_t m = 0; m < p->num_maps; ++m) { texels[m] = p->maps[m].texels; texel_count[m] = (size_t)p->maps[m].width * p->maps[m].height; }
+    maps_texels(p, texels, texel_count);
     StageColumn cols[kStageMaxColumns];
     point_columns(cols, p->dirs, p->num_dirs, p->rotations, p->num_rotations, points, normals, hit_flags, keys);
     const int ncols = gather_maps_sh_columns(cols, out_sh, bands * bands, out_counts, out_moments, depth ? depth->res : 0u, out_depth_counts, out_nearest, out_nearest_dir, p->node_map,
                                              p->num_nodes, p->num_maps, texels, texel_count);
-    const GatherMapsSpec spec{p->num_dirs, p->num_rotations, p->bias, p->max_toi, p->num_maps, p->num_nodes, {p->miss_rgb[0], p->miss_rgb[1], p->miss_rgb[2]}};
-    // One chunk (nc <= point_chunk): the trace (the permutations and the lanes per point are k_gather_maps_points') leaves c_ij of the chunk's rays in the workspace, 12 bytes
+    const GatherMapsSpec spec = maps_spec(p);
+    // One chunk (nc <= point_chunk): the trace (the permutations and the lanes per point as for nrays_gather_maps_points*) leaves c_ij of the chunk's rays in the workspace, 12 bytes
     // a ray, and with a depth spec rf behind them, 4 bytes a ray; the two folds of the parent calls read the planes in the order of j.
     auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long key_base) -> int {
         const size_t rays = (size_t)nc * p->num_dirs; // (<= kTraceChunk, or one point's)
         const int rc = grow_device(&b.w->d_gather_rays, &b.w->gather_ray_floats, rays * (depth ? 4u : 3u), sizeof(float));
         if (rc != NRAYS_OK) return rc;
         float* ray_rgb = (float*)b.w->d_gather_rays;
-        GatherMapsTable table; // (as nrays_gather_maps_points*: the map records at the chunk's texel addresses)
-        std::memset(&table, 0, sizeof table);
-        for (uint32_t m = 0; m < p->num_maps; ++m) {
-            const NraysTexture& s = p->maps[m];
-            table.map[m].texels = c[kMapsShTexels + m]; table.map[m].width = s.width; table.map[m].height = s.height; table.map[m].mode = s.format | (s.interp << 8) | (s.overflow << 16);
-        }
+        const GatherMapsTable table = maps_table(p, c, kMapsShTexels);
         const GatherPoints pts = chunk_points(c, key_base);
         const double* dirs = (const double*)c[kPointDirs];
         const double* rotations = (const double*)c[kPointRotations];
@@ -279,9 +289,7 @@ static int gather_maps_sh_impl(NraysScene* sc, uint32_t n, const double* points,
                                      (uint32_t*)c[kMapsShCounts], depth ? &dd : nullptr, b.w->d_spill};
         if (!launch_gather_maps_rays(a, traversal_feat(sc), lp)) return no_permutation("k_gather_maps_rays");
         HIP_TRY(hipGetLastError());
-        const uint32_t grid = std::min<uint32_t>((nc + kShGroups - 1u) / kShGroups, kShMaxGrid);
-        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, b.stream, (const float*)ray_rgb, nc, pts, hemisphere_spec(p->num_dirs, p->num_rotations, p->bias), dirs, rotations,
-                           bands * bands, (float*)c[kMapsShSh]);
+        launch_gather_fold_sh(b.stream, ray_rgb, nc, pts, hemisphere_spec(p->num_dirs, p->num_rotations, p->bias), dirs, rotations, bands, (float*)c[kMapsShSh]);
         if (!depth) return launch_status("k_gather_fold_sh");
         HIP_TRY(hipGetLastError());
         const ProbeDepthFoldLaunch f{b.stream, nc, pts, ProbeDepthSpec{p->num_dirs, p->num_rotations, p->bias, depth->max_dist, depth->near_dist, depth->res}, dirs, rotations,
@@ -393,11 +401,11 @@ __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const dou
                                                            const double* __restrict__ dirs, const double* __restrict__ rotations, double* __restrict__ out_origins,
                                                            double* __restrict__ out_dirs) {
     const size_t rays = (size_t)n * P.num_dirs;
+    const GatherPoints in{points, normals, nullptr, keys, key_base};
     for (size_t r = (size_t)blockIdx.x * kBlock + threadIdx.x; r < rays; r += (size_t)gridDim.x * kBlock) {
         const size_t i = r / P.num_dirs, j = r % P.num_dirs;
-        const OccFrame f = occlusion_frame(D3(points[3 * i], points[3 * i + 1], points[3 * i + 2]), D3(normals[3 * i], normals[3 * i + 1], normals[3 * i + 2]),
-                                           keys ? keys[i] : key_base + i, P, rotations);
-        const d3 d = occlusion_dir(f, P.num_rotations != 0u, dirs[3 * j], dirs[3 * j + 1], dirs[3 * j + 2]);
+        const OccFrame f = point_frame_live(in, i, P, rotations);
+        const d3 d = hemisphere_dir(f, P.num_rotations != 0u, dirs, j);
         out_origins[3 * r] = f.o.x; out_origins[3 * r + 1] = f.o.y; out_origins[3 * r + 2] = f.o.z;
         out_dirs[3 * r] = d.x; out_dirs[3 * r + 1] = d.y; out_dirs[3 * r + 2] = d.z;
     }
@@ -560,9 +568,8 @@ int nrays_debug_gather_sh_fold(NraysScene* sc, uint32_t n, const double* points,
     hipError_t e = hipSuccess;
     if (rc == NRAYS_OK && out_kernel_ms) { e = hipEventCreate(&ev[0]); if (e == hipSuccess) e = hipEventCreate(&ev[1]); if (e == hipSuccess) e = hipEventRecord(ev[0], b.stream); }
     if (rc == NRAYS_OK && e == hipSuccess) {
-        const uint32_t grid = std::min<uint32_t>((n + kShGroups - 1u) / kShGroups, kShMaxGrid);
-        hipLaunchKernelGGL(k_gather_fold_sh, dim3(grid), dim3(kShBlock), 0, b.stream, (const float*)c[kGatherRays], n, chunk_points(c, 0ull),
-                           hemisphere_spec(params->num_dirs, params->num_rotations, params->bias), (const double*)c[kPointDirs], (const double*)c[kPointRotations], bands * bands, (float*)c[kGatherOut]);
+        launch_gather_fold_sh(b.stream, (const float*)c[kGatherRays], n, chunk_points(c, 0ull), hemisphere_spec(params->num_dirs, params->num_rotations, params->bias),
+                              (const double*)c[kPointDirs], (const double*)c[kPointRotations], bands, (float*)c[kGatherOut]);
         e = hipGetLastError();
     }
     if (rc == NRAYS_OK && e == hipSuccess && out_kernel_ms) e = hipEventRecord(ev[1], b.stream);

@@ -1,8 +1,8 @@
 // probe_depth_kernel.h — nrays_probe_depth_points*: what a probe sees of the geometry around it — per point an octahedral map of the mean and mean squared
 // distance to the nearest surface (the visibility term of DDGI, read by k_irradiance_points<.., VIS = true>), the rays that end close by or nowhere, and the
 // nearest hit.  The definition is include/nrays_abi.h (NraysProbeDepthParams), mirrored in numpy (nrays_amd.oct_texel / probe_depth_ref).
-// Two kernels.  k_probe_depth_points is k_gather_maps_points with another payload: the rays are k_occlusion_points' (occlusion_frame / occlusion_dir), the query is
-// k_cast_rays', 2^LP lanes serve a point.  What does not depend on the order of the rays — the two counts and the nearest (dist, j), a lexicographic minimum — stays in
+// Two kernels.  k_probe_depth_points: the rays and the lanes of a point are hemisphere_device.h's (point_lane, point_frame_live, hemisphere_dir: 2^LP lanes serve a
+// point), the query is closest_hit (trace_device.h).  What does not depend on the order of the rays — the two counts and the nearest (dist, j), a lexicographic minimum — stays in
 // the lane across its rounds and is folded through the lanes of the point ONCE, after the last round (__shfl_xor: log2 steps instead of the 2^LP steps a round of an ordered
 // fold).  What does depend on it — the f32 sums of a texel — cannot go through lanes: the kernel stores rf, 4 bytes a ray of one chunk, into the handle's workspace, as
 // the gather keeps a chunk's colours for k_gather_fold_sh.
@@ -42,9 +42,9 @@ NR_DEV uint32_t oct_texel(double x, double y, double z, uint32_t R) {
     return oct_axis(b, R) * R + oct_axis(a, R);
 }
 
-// Point i of the chunk: its num_dirs rays, each through the closest-hit query of cast_rays_body (unbounded); ray_out[i * num_dirs + j] = rf, the clamped distance
-// in f32, for k_probe_depth_fold.  out_counts[2i], [2i + 1]: the rays with dist < near_dist and the rays without a hit; out_nearest / out_nearest_dir: the least dist
-// and the smallest j that has it.  Each of the three may be null (kernel arguments: wave-uniform).  The lanes of a point and the rounds are k_occlusion_points'.
+// Point i of the chunk: its num_dirs rays, each through closest_hit (unbounded); ray_out[i * num_dirs + j] = rf, the clamped distance in f32, for
+// k_probe_depth_fold.  out_counts[2i], [2i + 1]: the rays with dist < near_dist and the rays without a hit; out_nearest / out_nearest_dir: the least dist
+// and the smallest j that has it.  Each of the three may be null.
 // A point whose flag bit 0 is clear is skipped: no traversal, neither its point nor its normal read, nothing stored to ray_out (the fold does not read it);
 // counts 0, 0, nearest +inf, kDepthNoDir.  NULL keys: key_base + i.
 template <int FEAT, int LP>
@@ -54,7 +54,6 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_probe_depth_po
                                                                                       const double* __restrict__ rotations, float* __restrict__ ray_out,
                                                                                       uint32_t* __restrict__ out_counts, double* __restrict__ out_nearest,
                                                                                       uint32_t* __restrict__ out_nearest_dir, uint32_t* spill) {
-    static_assert(LP >= 0 && LP <= 6, "the lanes of a point share a wave");
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
@@ -62,33 +61,23 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_probe_depth_po
     const uint32_t k = P.num_dirs, slots = n << LP; // (n * num_dirs <= 2^22 and 2^LP <= num_dirs: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
     const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
-    const double inf = __longlong_as_double(0x7ff0000000000000ll);
+    const GatherPoints in{points, normals, hit_flags, keys, key_base};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
-        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
-        const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
-        OccFrame f;
-        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
-        if (live) {
-            const size_t i3 = 3 * (size_t)i;
-            f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), keys ? keys[i] : key_base + i, G, rotations);
-        }
+        const PointLane L = point_lane<LP>(base, n, in);
+        OccFrame f = neutral_frame();
+        if (L.live) f = point_frame_live(in, L.i, G, rotations);
+        const double inf = __longlong_as_double(0x7ff0000000000000ll);
         uint32_t nearby = 0u, missed = 0u, best_j = kDepthNoDir;
         double best = inf;
         for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
-            const uint32_t j = j0 + sub;
-            if (live && j < k) {
-                const d3 d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
-                Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
-                Isect is; uint32_t node_id = 0; bool gated = false, any = false;
-                for (;;) {
-                    any = traverse<false, false, FEAT>(S, st, f.o, d, kDblMax, hit, filter, cnt, gated, &is);
-                    if (!any) break;
-                    if (resolve_hit<false, FEAT, true>(S, f.o, d, hit, is, node_id) || gated) break;
-                    gated = true;
-                }
-                const double L = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
-                const double dist = any ? hit.t * L : inf;
-                ray_out[(size_t)i * k + j] = (float)(dist < P.max_dist ? dist : P.max_dist);
+            const uint32_t j = j0 + L.sub;
+            if (L.live && j < k) {
+                const d3 d = hemisphere_dir(f, rotate, dirs, j);
+                Hit hit; Isect is; uint32_t node_id;
+                const bool any = closest_hit<FEAT>(S, st, cnt, f.o, d, hit, is, node_id);
+                const double len = sqrt((d.x * d.x + d.y * d.y) + d.z * d.z);
+                const double dist = any ? hit.t * len : inf;
+                ray_out[(size_t)L.i * k + j] = (float)(dist < P.max_dist ? dist : P.max_dist);
                 nearby += dist < P.near_dist ? 1u : 0u; missed += any ? 0u : 1u;
                 if (dist < best) { best = dist; best_j = j; } // (a lane's j only grow: the smallest j of its least dist)
             }
@@ -102,10 +91,10 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_probe_depth_po
                 if (od < best || (od == best && oj < best_j)) { best = od; best_j = oj; }
             }
         }
-        if (i < n && sub == 0u) {
-            if (out_counts) { out_counts[2 * (size_t)i] = nearby; out_counts[2 * (size_t)i + 1] = missed; }
-            if (out_nearest) out_nearest[i] = best;
-            if (out_nearest_dir) out_nearest_dir[i] = best_j;
+        if (L.i < n && L.sub == 0u) {
+            if (out_counts) { out_counts[2 * (size_t)L.i] = nearby; out_counts[2 * (size_t)L.i + 1] = missed; }
+            if (out_nearest) out_nearest[L.i] = best;
+            if (out_nearest_dir) out_nearest_dir[L.i] = best_j;
         }
     }
 }
@@ -126,21 +115,15 @@ __global__ void __launch_bounds__(kDepthBlock) k_probe_depth_fold(const float* _
     for (uint32_t base = blockIdx.x * kGroups; base < n; base += gridDim.x * kGroups) { // block-uniform trip count
         const uint32_t i = base + g;
         const bool live = i < n && gather_point_live(in, i); // (the same for all lanes of a point)
-        OccFrame f;
-        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
-        if (live) {
-            const size_t i3 = 3 * (size_t)i;
-            f = occlusion_frame(D3(in.points[i3], in.points[i3 + 1], in.points[i3 + 2]), D3(in.normals[i3], in.normals[i3 + 1], in.normals[i3 + 2]),
-                                gather_point_key(in, i), G, rotations);
-        }
+        OccFrame f = neutral_frame();
+        if (live) f = point_frame_live(in, i, G, rotations);
         const float* src = rays + (size_t)i * k; // (dereferenced for live points only)
         float s1 = 0.0f, s2 = 0.0f;
         uint32_t cnt = 0u;
         for (uint32_t j0 = 0; j0 < k; j0 += kGroup) { // block-uniform trip count: the barriers below are reached by every thread
             const uint32_t m = k - j0 < kGroup ? k - j0 : kGroup; // directions of this tile
             if (live && lane < m) {
-                const size_t j3 = 3 * (size_t)(j0 + lane);
-                const d3 d = occlusion_dir(f, rotate, dirs[j3], dirs[j3 + 1], dirs[j3 + 2]);
+                const d3 d = hemisphere_dir(f, rotate, dirs, j0 + lane);
                 tex[lane] = oct_texel(d.x, d.y, d.z, (uint32_t)R);
                 rf[lane] = src[j0 + lane];
             }

@@ -2,12 +2,13 @@
 // k_intersects_rays and k_cast_rays trace ray j of a chunk in lane j; their _ordered forms trace ray order[j] there and
 // write its result to ITS slot (a batch the caller called unordered, binned by ray_key.h's key).  ray_batches.hip launches both forms.  One body
 // each, so that the two forms cannot drift apart.  k_shade_points (nrays_shade_points*) lights surface point j in lane j; it has no ordered form.
-// k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers, traces them and folds them into one value;
+// k_occlusion_points (nrays_occlusion_points*) builds the hemisphere rays of a point in registers (hemisphere_device.h), traces them and folds them into one value;
 // k_gather_points (nrays_gather_points*) runs Scene::trace on the same rays and folds the colours (instantiated in gather_inst.hip);
 // k_gather_pairs_ordered traces the (point, direction) pairs of a reordered gather chunk in bin order (nrays_gather_points*_ex; gather_order_inst.hip).
 // Templates and inline device code only: ray_batches.hip (which instantiates every kernel here that has no unit of its own), point_batches.hip, ray_order.hip,
 // gather_inst.hip and gather_order_inst.hip include this header.
 #pragma once
+#include "hemisphere_device.h"
 #include "primary_kernel.h"
 
 namespace nrays {
@@ -99,8 +100,8 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_intersects_ray
 }
 
 // Scene::trace's closest-hit query (scene.rs:164-166, 262-283) with SceneNode::cast's record (scene_node.rs:51-54) on caller-supplied rays
-// (nrays_cast_rays_device): k_cast_batch's mode 0 — ungated traversal, the winner checked against the reference's exact AABB gates, the fully
-// gated repeat for knife-edge rays — with one array per field.  max_toi (NULL = unbounded) filters the FINISHED query (toi <= max_toi[i]
+// (nrays_cast_rays_device): k_cast_batch's mode 0 — closest_hit (trace_device.h): ungated traversal, the winner checked against the reference's exact AABB
+// gates, the fully gated repeat for knife-edge rays — with one array per field.  max_toi (NULL = unbounded) filters the FINISHED query (toi <= max_toi[i]
 // keeps the hit; a NaN bound keeps nothing) and never enters the traversal, so a bounded result is the unbounded one or a miss.  The four
 // optional outputs are kernel arguments: a NULL test is wave-uniform and a NULL output costs no store.  A miss writes node -1, toi +inf,
 // zeros, prim -1, flags 0.
@@ -119,7 +120,7 @@ __device__ __forceinline__ void cast_rays_body(uint32_t* lds_stack, const DScene
         const d3 o = D3(ro[i3], ro[i3 + 1], ro[i3 + 2]), d = D3(rd[i3], rd[i3 + 1], rd[i3 + 2]);
         Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
         Isect is; uint32_t node_id = 0; bool gated = false, any = false;
-        for (;;) {
+        for (;;) { // (closest_hit, kept as text: through the call this kernel's registers are numbered differently)
             any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
             if (!any) break;
             if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
@@ -204,38 +205,8 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_shade_points(D
 }
 
 // ---- ambient occlusion at caller-supplied points (nrays_occlusion_points*) --------------------------------------------------------------------
-// The rays are DEFINED by include/nrays_abi.h (NraysOcclusionParams) and mirrored in numpy (nrays_amd.occlusion_rays): f64 + - * /, copysign and
-// integer arithmetic only, every product evaluated left to right as written, nothing fused (-ffp-contract=off).  occlusion_frame / occlusion_dir are
-// the one generator: k_occlusion_points traces their rays and k_occlusion_rays (nrays_debug_occlusion_rays) stores them.
-struct OcclusionSpec { uint32_t num_dirs, num_rotations; double bias, max_toi; };
-struct OccFrame { d3 o, t, u, n; double c, s; };
-// The points of a chunk (columns kPointPoints .. kPointKeys of batch_stage.h; batch_call.h: chunk_points) and the index of its first point in the call: what the
-// launch structs of the point families carry and the kernels of the reordered gather take as one argument.
-struct GatherPoints { const double* points; const double* normals; const uint32_t* hit_flags; const unsigned long long* keys; unsigned long long key_base; };
-
-// The branch-free orthonormal frame of Duff et al. 2017 around normal n (no singular normal), the biased origin, and the point's rotation
-// (c, s) = rotations[rng_hash(key, kSaltOcclusion) % R]; R = 0: no table is read and occlusion_dir leaves (lx, ly) untouched.
-NR_DEV OccFrame occlusion_frame(d3 p, d3 n, unsigned long long key, const OcclusionSpec& P, const double* __restrict__ rotations) {
-    OccFrame f;
-    const double s = copysign(1.0, n.z), a = -1.0 / (s + n.z), b = n.x * n.y * a;
-    f.t = D3(1.0 + s * n.x * n.x * a, s * b, -s * n.x);
-    f.u = D3(b, s + n.y * n.y * a, -n.y);
-    f.n = n;
-    f.o = D3(p.x + n.x * P.bias, p.y + n.y * P.bias, p.z + n.z * P.bias);
-    f.c = 1.0; f.s = 0.0;
-    if (P.num_rotations) {
-        const size_t r = (size_t)(rng_hash(key, kSaltOcclusion) % (unsigned long long)P.num_rotations);
-        f.c = rotations[2 * r]; f.s = rotations[2 * r + 1];
-    }
-    return f;
-}
-// Sample direction (lx, ly, lz) of the local frame (z = the normal) in world space.  Not normalised: the traversal uses directions as given.
-NR_DEV d3 occlusion_dir(const OccFrame& f, bool rotate, double lx, double ly, double lz) {
-    double x = lx, y = ly;
-    if (rotate) { x = f.c * lx - f.s * ly; y = f.s * lx + f.c * ly; }
-    return D3((x * f.t.x + y * f.u.x) + lz * f.n.x, (x * f.t.y + y * f.u.y) + lz * f.n.y, (x * f.t.z + y * f.u.z) + lz * f.n.z);
-}
-
+// The rays, the lanes of a point and the mean are hemisphere_device.h's (point_lane, point_frame_live, hemisphere_dir, store_mean): k_occlusion_points traces
+// the rays and k_occlusion_rays (nrays_debug_occlusion_rays) stores them.
 // Point i of the chunk: num_dirs transparent-shadow queries (Scene::intersects_ray, what k_intersects_rays runs) from p + n * bias, folded in the
 // order of the directions — f32 sum of the filters of the rays that got through, then ONE division by (float)num_dirs; out_open[i] counts them.
 // 2^LP lanes serve a point: lane `sub` takes the directions j = sub (mod 2^LP), and after every round the 2^LP partial values are added in the order of j
@@ -249,22 +220,18 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
                                                                                     unsigned long long key_base, OcclusionSpec P, const double* __restrict__ dirs,
                                                                                     const double* __restrict__ rotations, float* __restrict__ out_filter,
                                                                                     uint32_t* __restrict__ out_open, uint32_t* spill) {
-    static_assert(LP >= 0 && LP <= 6, "the lanes of a point share a wave");
     __shared__ uint32_t lds_stack[kLdsStack * kBlock];
     Stack st; st.setup(lds_stack, spill, nullptr);
     Cnt cnt; cnt.zero();
     constexpr uint32_t kLanes = 1u << LP;
     const uint32_t k = P.num_dirs, slots = n << LP; // (n <= 2^22: batch_call.h's chunks)
     const bool rotate = P.num_rotations != 0u;
+    const GatherPoints in{points, normals, hit_flags, keys, key_base};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
-        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
-        const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
-        OccFrame f;
-        f.o = f.t = f.u = f.n = D3(0.0, 0.0, 0.0); f.c = 1.0; f.s = 0.0;
-        if (live) {
-            const size_t i3 = 3 * (size_t)i;
-            f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), keys ? keys[i] : key_base + i, P, rotations);
-        }
+        const PointLane L = point_lane<LP>(base, n, in);
+        const uint32_t i = L.i, sub = L.sub; const bool live = L.live;
+        OccFrame f = neutral_frame();
+        if (live) f = point_frame_live(in, i, P, rotations);
         f3 sum = F3(0.0f, 0.0f, 0.0f);
         uint32_t open = 0u;
         for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
@@ -272,7 +239,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
             f3 c = F3(0.0f, 0.0f, 0.0f);
             uint32_t lit = 0u;
             if (live && j < k) {
-                const d3 d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
+                const d3 d = hemisphere_dir(f, rotate, dirs, j);
                 Hit hit; f3 filter = F3(1.0f, 1.0f, 1.0f);
                 if (!traverse<true, false, FEAT>(S, st, f.o, d, P.max_toi, hit, filter, cnt)) { c = filter; lit = 1u; }
             }
@@ -288,8 +255,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_occlusion_poin
             }
         }
         if (i < n && sub == 0u) {
-            const float fk = (float)k;
-            out_filter[3 * (size_t)i] = sum.x / fk; out_filter[3 * (size_t)i + 1] = sum.y / fk; out_filter[3 * (size_t)i + 2] = sum.z / fk;
+            store_mean(out_filter, i, sum, k);
             if (out_open) out_open[i] = open;
         }
     }
@@ -302,7 +268,7 @@ struct OcclusionLaunch {
 bool launch_occlusion_points(const OcclusionLaunch& a, int feat, int lp);
 
 // ---- incoming light at caller-supplied points (nrays_gather_points*): the mean of Scene::trace over a point's hemisphere rays -----------------------------
-// The rays are k_occlusion_points' (occlusion_frame / occlusion_dir with the same point, normal, key, tables and bias: bit for bit the same rays); ray j of point i
+// The rays are hemisphere_device.h's (occlusion_frame / hemisphere_dir with the same point, normal, key, tables and bias as the occlusion call: bit for bit the same rays); ray j of point i
 // is traced as k_trace_rays traces a ray it loads — a depth-0 RayWithEnergy of refr 1, energy P.energy, weight 1, key rng_hash(key_i, kSaltGather + j), "pixel" i —
 // and the chains' sums are folded as the occlusion kernel folds its filters: 2^LP lanes serve a point, and after every round the 2^LP partial colours are added in
 // the order of j through __shfl, every lane of the point keeping the same running sum — the sequential f32 sum, whatever LP.  trace_chain holds ballots and
@@ -330,7 +296,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(
     const bool rotate = P.num_rotations != 0u;
     const OcclusionSpec G{P.num_dirs, P.num_rotations, P.bias, 0.0};
     for (uint32_t base = blockIdx.x * kBlock; base < slots; base += gridDim.x * kBlock) { // block-uniform trip count
-        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u);
+        const uint32_t slot = base + threadIdx.x, i = slot >> LP, sub = slot & (kLanes - 1u); // (point_lane and point_frame_live as text: through the calls this kernel compiles to other instructions)
         const bool live = i < n && (!hit_flags || (hit_flags[i] & 1u) != 0u); // (the same for all lanes of a point)
         f3 sum = F3(0.0f, 0.0f, 0.0f);
         for (uint32_t j0 = 0; j0 < k; j0 += kLanes) { // wave-uniform rounds
@@ -342,7 +308,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_gather_points(
                 const size_t i3 = 3 * (size_t)i;
                 const unsigned long long key = keys ? keys[i] : key_base + i;
                 const OccFrame f = occlusion_frame(D3(points[i3], points[i3 + 1], points[i3 + 2]), D3(normals[i3], normals[i3 + 1], normals[i3 + 2]), key, G, rotations);
-                ray.o = f.o; ray.d = occlusion_dir(f, rotate, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
+                ray.o = f.o; ray.d = hemisphere_dir(f, rotate, dirs, j);
                 ray.energy = P.energy; ray.weight = 1.0f; ray.pixel = ray_out ? i * k + j : i;
                 ray.key = P.keyed ? rng_hash(key, kSaltGather + j) : 0ULL;
             }
@@ -381,18 +347,7 @@ bool launch_gather_points(const GatherLaunch& a, bool stats, int feat, int lp);
 // A chunk's (point, direction) pairs — pair i * num_dirs + j is ray j of point i — are binned by ray_key.h's key and traced in bin order, one lane per pair; the
 // rays exist in registers only, rebuilt from (i, j) wherever they are needed (bounds, keys, trace).  What crosses memory per ray is the sort state (key, rank,
 // order: 16 bytes) and the colour (12 bytes), both of ONE chunk, in the handle's workspace.
-// Bit 0 of a point's flags clear: the point is skipped — none of its pairs is live, neither its point nor its normal is read.
-NR_DEV bool gather_point_live(const GatherPoints& in, uint32_t i) { return !in.hit_flags || (in.hit_flags[i] & 1u) != 0u; }
-NR_DEV unsigned long long gather_point_key(const GatherPoints& in, uint32_t i) { return in.keys ? in.keys[i] : in.key_base + i; }
-// Ray j of LIVE point i, exactly as k_gather_points builds it (occlusion_frame / occlusion_dir: the one generator).
-NR_DEV void gather_pair_ray(const GatherPoints& in, uint32_t i, uint32_t j, const OcclusionSpec& G, const double* __restrict__ dirs, const double* __restrict__ rotations,
-                            d3& o, d3& d) {
-    const size_t i3 = 3 * (size_t)i;
-    const OccFrame f = occlusion_frame(D3(in.points[i3], in.points[i3 + 1], in.points[i3 + 2]), D3(in.normals[i3], in.normals[i3 + 1], in.normals[i3 + 2]),
-                                       gather_point_key(in, i), G, rotations);
-    o = f.o; d = occlusion_dir(f, G.num_rotations != 0u, dirs[3 * (size_t)j], dirs[3 * (size_t)j + 1], dirs[3 * (size_t)j + 2]);
-}
-
+// Bit 0 of a point's flags clear: the point is skipped — none of its pairs is live, neither its point nor its normal is read (hemisphere_device.h: gather_pair_ray).
 // Lane t of the chunk traces pair order[t], t < *live (the number of placed pairs, known on the device only: the grid is sized by the chunk's `pairs` and the
 // lanes at or beyond *live idle).  The RayState is k_gather_points' — energy, weight 1, refr 1, key rng_hash(key_i, kSaltGather + j) in keyed scenes — with the
 // pair as its "pixel" always, and the chain's sum goes to ray_out[3 * pair ..] as k_trace_rays stores a ray's: the queue's rounds (double-branching scenes) and

@@ -21,7 +21,7 @@ namespace nrays {
 
 // (FEAT: kFeatAll, or kFeatMesh for scenes of opaque TriMesh nodes only — the permutation whose node phases end by quorum in
 // hair-like meshes, so that the independent fixtures also cover that path.)
-// nrays_debug_cast_batch: the closest-hit query with the deferred exact gates exactly as shade_hit runs it (ungated traversal, the
+// nrays_debug_cast_batch: the closest-hit query with the deferred exact gates exactly as shade_hit runs it (closest_hit, trace_device.h: ungated traversal, the
 // winner checked against the reference's AABB gates, fully gated repeat for knife-edge rays), or the shadow query, on rays from memory.
 template <int FEAT>
 __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DScene S, uint32_t mode, uint32_t n, const double* __restrict__ ro, const double* __restrict__ rd,
@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(kBlock, NRAYS_WAVES_PER_SIMD) k_cast_batch(DSc
             r.flags = blocked ? 1u : 0u; r.normal[0] = filter.x; r.normal[1] = filter.y; r.normal[2] = filter.z;
         } else {
             Isect is; uint32_t node_id = 0; bool gated = false, any = false;
-            for (;;) {
+            for (;;) { // (closest_hit, kept as text: through the call this kernel compiles to other instructions)
                 any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
                 if (!any) break;
                 if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;

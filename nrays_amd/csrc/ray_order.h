@@ -5,7 +5,7 @@
 
 namespace nrays {
 
-struct GatherPoints; struct OcclusionSpec; // ray_batch_kernel.h
+struct GatherPoints; struct OcclusionSpec; // hemisphere_device.h
 constexpr uint32_t kNumBins = 1u << kRayBinBits; // counters of the counting sort; TraceWorkspace::d_ray_bins holds one word more (a gather chunk's live pairs)
 
 // Grows the reorder buffers of `w` to n rays (n <= kTraceChunk).  NRAYS_OK or a negative status with the last error set.

@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(kOrderBlock) k_ray_place(uint32_t n, const uin
     if (at < n) order[at] = i; // (always: the counts sum to n)
 }
 
-// ---- the same three steps on the (point, direction) pairs of a gather chunk (nrays_gather_points*_ex; ray_batch_kernel.h: gather_pair_ray) -----------------------
+// ---- the same three steps on the (point, direction) pairs of a gather chunk (nrays_gather_points*_ex; hemisphere_device.h: gather_pair_ray) -----------------------
 // Pair r = i * num_dirs + j is ray j of point i; the ray is rebuilt in registers, and only the pairs of LIVE points take part: a skipped point's point and normal
 // are never read (they may be NaN), its pairs enter no bounds, take no bin and no place.
 // k_gather_bounds is k_ray_bounds on the rays of the live pairs: min / max are exact and order-free, so k_ray_frame gives bit for bit the frame ray_order_chunk

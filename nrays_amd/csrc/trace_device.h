@@ -1156,6 +1156,22 @@ NR_DEV bool traverse(const DScene& S, Stack& st, d3 o, d3 d, double tlimit, Hit&
     return bhit;
 }
 
+// The closest-hit query on ray (o, d), unbounded, in its plain form: the ungated traversal, the winner checked against the exact gates (resolve_hit), the gated
+// repeat for knife-edge rays.  true = a hit, with `hit`, `is` and `node_id` its record.  The caller-batch kernels run it once per ray.
+template <int FEAT>
+NR_DEV bool closest_hit(const DScene& S, Stack& st, Cnt& cnt, d3 o, d3 d, Hit& hit, Isect& is, uint32_t& node_id) {
+    f3 filter = F3(1.0f, 1.0f, 1.0f);
+    bool gated = false, any = false;
+    node_id = 0;
+    for (;;) {
+        any = traverse<false, false, FEAT>(S, st, o, d, kDblMax, hit, filter, cnt, gated, &is);
+        if (!any) break;
+        if (resolve_hit<false, FEAT, true>(S, o, d, hit, is, node_id) || gated) break;
+        gated = true;
+    }
+    return any;
+}
+
 // ---------------------------------------------------------------- stackless queries ----------
 // kFeatTinyScene (opaque analytic-only scenes of at most kTinyLeaves TLAS leaves): the two queries test EVERY leaf of the TLAS,
 // in a wave-uniform loop over DScene::tiny, instead of walking it — no node fetches, slab tests, sort or LDS stack, and a ball's
@@ -1430,7 +1446,7 @@ NR_DEV f3 shade_hit(const DScene& S, Stack& st, RayState& ray, uint32_t depth, u
     Isect is; uint32_t node_id;
     bool gated = false;
     bool pre = false, pre_lit = false; f3 pre_filter = F3(1.0f, 1.0f, 1.0f);
-    for (;;) { // second iteration only when the ungated winner fails the reference's AABB gates (knife-edge rays)
+    for (;;) { // second iteration only when the ungated winner fails the reference's AABB gates (knife-edge rays); closest_hit is the plain form of this loop
         NR_TIC(tq);
         const bool any_hit = tiny_queries<STATS, FEAT>() ? tiny_closest<FEAT>(S, ray.o, ray.d, gated, hit, is)
                                                          : traverse<false, STATS, FEAT>(S, st, ray.o, ray.d, kDblMax, hit, nofilter, cnt, gated, &is);

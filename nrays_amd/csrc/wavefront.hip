@@ -168,7 +168,7 @@ NR_DEV bool wf_load_hit(const WfQueue& q, uint32_t i, Hit& h) {
 }
 
 // Scene::trace's closest-hit query with the deferred exact gates, exactly as shade_hit runs it: ungated traversal, the
-// winner checked against the reference's AABB gates, fully gated repeat for knife-edge rays.
+// winner checked against the reference's AABB gates, fully gated repeat for knife-edge rays.  (trace_device.h's closest_hit is the plain form, with the record.)
 template <int FEAT>
 NR_DEV bool wf_closest(const DScene& S, Stack& st, d3 o, d3 d, Hit& hit, Cnt& cnt) {
     static_assert((FEAT & kFeatMesh) != 0, "the staged path renders scenes with TriMesh nodes");
