@@ -5,8 +5,11 @@
 //
 // traverse() (trace_device.h) runs 64 rays from start to end together: a wave iterates until its SLOWEST lane is done —
 // in a hair-like mesh 17 - 31 % of the lanes are active per node step, the rest have finished or missed.  Here the node /
-// leaf phases are the same code ("while-while", quorum-ended node phases, LDS stack, deferred exact gates: see traverse()),
-// but between two rounds of phases the wave looks at its lanes: finished ones deliver (a wave-uniform point: results are
+// leaf phases are a COPY of traverse()'s text ("while-while", quorum-ended node phases, LDS stack, deferred exact gates: see traverse()),
+// without its counters and its analytic leaf, and with `return true` turned into a `stop` flag: a repair inside a node or leaf step of
+// traverse() has to be made here too.  (The copy is deliberate: the fetch-and-keys step and the shadow push order, written as functions
+// that both walks call, compile to other instructions in every kernel that walks — profiles/one_walk_isa.txt.)
+// Between two rounds of phases the wave looks at its lanes: finished ones deliver (a wave-uniform point: results are
 // compacted by ballot -> prefix into the next queue), and once kRefillMin of them are free the stream fills them again.
 // Results do not depend on which rays share a wave or on the visiting order (ties: D-2), so the rays' results — and the
 // frames — are bit-identical to traverse()'s.  The wave-uniform scalar node fetch survives where the lanes still agree.
@@ -32,9 +35,13 @@ constexpr int32_t kFin = (int32_t)0x80000004;  // the lane's ray is finished, it
 
 template <bool SHADOW, int FEAT, class Source>
 NR_DEV void traverse_stream(const DScene& S, Stack& st, Source& src, Cnt& cnt) {
-    constexpr bool kAnalytic = (FEAT & kFeatAnalytic) != 0, kMesh = (FEAT & kFeatMesh) != 0;
+    // The staged path takes scenes of TriMesh nodes only (wavefront.hip: wf_eligible), so traverse()'s plane pushes and its analytic leaf have no copy here:
+    // a permutation with analytic shapes would walk past them in silence.
+    static_assert(!(FEAT & kFeatAnalytic), "traverse_stream() has no analytic leaf and pushes no planes: mesh-only permutations");
+    constexpr bool kMesh = (FEAT & kFeatMesh) != 0;
     constexpr bool kAlpha = (FEAT & kFeatAlphaShadow) != 0; // shadow mode: otherwise every hit within tlimit blocks
-    constexpr bool kQuorum = NR_NODE_QUORUM_DEN != 0 && kMesh && !kAnalytic && !kAlpha;
+    constexpr bool kQuorum = NR_NODE_QUORUM_DEN != 0 && kMesh && !kAlpha;
+    constexpr bool kNoXf = (FEAT & kFeatNoXform) != 0; // as in traverse(): no instance moves the ray
     const Instance* insts = SHADOW ? S.shadow_instances : S.instances;
     const InstLink* links = SHADOW ? S.shadow_links : S.links;
     // per-lane state of one ray's traversal (traverse(): the locals of one call)
@@ -52,10 +59,6 @@ NR_DEV void traverse_stream(const DScene& S, Stack& st, Source& src, Cnt& cnt) {
         bt = SHADOW ? tlimit : kDblMax; btf = best_f32(bt); bkey = ~0ULL; bhit = false; binst = 0; bprim = 0;
         in_blas = false; cur_inst = 0; cur_flags = 0; blocked = false; filter = F3(1.0f, 1.0f, 1.0f);
         st.reset();
-        if (kAnalytic) {
-            const int32_t* planes = SHADOW ? S.shadow_planes : S.planes;
-            for (uint32_t p = 0; p < S.num_planes; ++p) st.push(~(int32_t)(((uint32_t)planes[p]) << 3));
-        }
         cur = SHADOW ? S.shadow_root : S.closest_root;
         if (cur == kEmptyChild) cur = st.pop();
     };
@@ -145,7 +148,7 @@ NR_DEV void traverse_stream(const DScene& S, Stack& st, Source& src, Cnt& cnt) {
         if (cur == kEmptyChild) { cur = kFin; continue; }            // the stack is empty: this ray is done
         if (kMesh && cur == kSentinel) { // the BLAS of `cur_inst` is exhausted: back to world space
             in_blas = false;
-            if (!(cur_flags & kInstNoXform)) { co = o; cd = d; rf = make_rayf(o, d); }
+            if (!kNoXf && !(cur_flags & kInstNoXform)) { co = o; cd = d; rf = make_rayf(o, d); }
             bool stop = false;
             if (SHADOW && kAlpha && !(cur_flags & kInstAnyHit)) {
                 if (bhit) {
@@ -185,11 +188,11 @@ NR_DEV void traverse_stream(const DScene& S, Stack& st, Source& src, Cnt& cnt) {
             if (stop) { blocked = true; cur = kFin; } else cur = after_leaf;
             continue;
         }
-        if (kMesh && (!kAnalytic || (bits & kLeafMesh))) { // TLAS leaf: a BLAS
+        if (kMesh) { // TLAS leaf: a BLAS
             cur_inst = first;
             InstLink link = links[first];
             cur_flags = link.flags;
-            if (!(bits & kLeafNoXform)) {
+            if (!kNoXf && !(bits & kLeafNoXform)) {
                 const Instance& in = insts[first];
                 Xform m; load_xform(in, m);
                 if (in.flags & kInstIdentityRot) { co = o - m.t; cd = d; }
@@ -201,23 +204,6 @@ NR_DEV void traverse_stream(const DScene& S, Stack& st, Source& src, Cnt& cnt) {
             cur = link.blas_root;
             if (cur == kEmptyChild) cur = st.pop();
             continue;
-        }
-        if (kAnalytic) { // TLAS leaf: an analytic shape (or a plane pseudo-leaf)
-            const Instance& in = insts[first];
-            bool stop = false;
-            Isect is = cast_instance<FEAT>(in, o, d, !(SHADOW && !kAlpha));
-            if (is.hit && (!GATED || in.kind == NRAYS_SHAPE_PLANE || node_aabb_pass(S, (uint32_t)in.node_id, o, d))) {
-                if (SHADOW) {
-                    if (is.toi <= tlimit) {
-                        if (!kAlpha) stop = true;
-                        else if (shadow_node_hit<false>(S, (uint32_t)in.node_id, is, filter, cnt)) stop = true;
-                    }
-                } else {
-                    unsigned long long key = (unsigned long long)(uint32_t)in.node_id << 32;
-                    if (is.toi < bt || (is.toi == bt && key < bkey)) { bt = is.toi; bkey = key; bhit = true; binst = first; bprim = 0; btf = best_f32(bt); }
-                }
-            }
-            if (stop) { blocked = true; cur = kFin; continue; }
         }
         cur = st.pop();
     }
