@@ -34,7 +34,7 @@ extern "C" {
  * Added after 7 WITHOUT a bump (plain functions over plain arrays, no struct): nrays_trace_rays_device_ex / nrays_trace_rays_ex /
  * nrays_intersects_rays_device_ex / nrays_debug_ray_order / nrays_cast_rays_device / nrays_cast_rays / nrays_shade_points_device /
  * nrays_shade_points / nrays_occlusion_points_device / nrays_occlusion_points / nrays_debug_occlusion_rays (their struct NraysOcclusionParams
- * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points / nrays_nearest_points_device / nrays_nearest_points / nrays_debug_nearest_bound / nrays_debug_scene_dump (its struct NraysSceneDump likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
+ * is new with them and changes no other) / nrays_gather_points_device / nrays_gather_points (their struct NraysGatherParams likewise) / nrays_gather_points_device_ex / nrays_gather_points_ex / nrays_debug_gather_order / nrays_surface_texels_device / nrays_surface_texels / nrays_debug_surface_texels_passes / nrays_debug_pipeline_counts / nrays_dilate_texels_device / nrays_dilate_texels / nrays_filter_texels_device / nrays_filter_texels / nrays_gather_sh_points_device / nrays_gather_sh_points / nrays_debug_gather_sh_fold / nrays_gather_maps_points_device / nrays_gather_maps_points (their struct NraysGatherMapsParams likewise) / nrays_irradiance_points_device / nrays_irradiance_points (their struct NraysIrradianceGrid likewise) / nrays_probe_depth_points_device / nrays_probe_depth_points (their struct NraysProbeDepthParams likewise) / nrays_irradiance_points_vis_device / nrays_irradiance_points_vis (their struct NraysIrradianceVisibility likewise) / nrays_gather_maps_sh_points_device / nrays_gather_maps_sh_points (their struct NraysGatherDepthSpec likewise) / nrays_material_points_device / nrays_material_points / nrays_nearest_points_device / nrays_nearest_points / nrays_debug_nearest_bound / nrays_debug_scene_dump (its struct NraysSceneDump likewise) / nrays_light_points_device / nrays_light_points / nrays_debug_light_rays (their struct NraysPointLights likewise).  A caller that may meet an older version-7 library finds them by symbol lookup. */
 #define NRAYS_ABI_VERSION 7
 
 typedef enum NraysStatus {
@@ -404,6 +404,60 @@ int nrays_occlusion_points(NraysScene* scene, uint32_t n, const double* points, 
  * out_origins / out_dirs [(i * num_dirs + j) * 3 ..], n x num_dirs x 3 doubles each.  keys NULL: key i.  max_toi is checked and not used. */
 int nrays_debug_occlusion_rays(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint64_t* keys,
                                const NraysOcclusionParams* params, double* out_origins, double* out_dirs);
+
+/* Direct light at n caller-supplied surface points from a CALLER-SUPPLIED table of point lights — a baker's per-light layers, a light that moves, the virtual
+ * point lights of instant radiosity (Keller 1997), a rig that is not in the scene description: the library builds the shadow ray of every (point, light) pair ON THE
+ * DEVICE, weights it with Lambert's cosine (and, for an emitter with a normal, the emitter's; optionally the inverse-square falloff), runs Scene::intersects_ray (the
+ * transparent-shadow query of nrays_intersects_rays_device) on it and writes ONE summed colour per point.  A light behind the surface costs nothing.  The scene's own
+ * lights are not read.  The arithmetic is defined exactly — f64 + - * / and sqrt, f32 + *, every product evaluated left to right as written, nothing fused; what
+ * Material::compute does for a light of the scene (phong_material.rs:106-147) — so that a caller can restate it bit for bit (Python: nrays_amd.light_rays; the
+ * library's own: nrays_debug_light_rays).  Per point p with normal nm (used as given; unit length is expected), for light k = 0 .. num_lights - 1 in order, with L,
+ * col, e row k of positions, colors, normals:
+ *   origin     q = p + nm * bias per component.
+ *   direction  v = L - q, nrm = sqrt((v.x * v.x + v.y * v.y) + v.z * v.z); !(nrm > 0): the light is skipped.  ldir = v / nrm (three divisions).
+ *   weight     cr = (float)((ldir.x * nm.x + ldir.y * nm.y) + ldir.z * nm.z), cr = cr > 0 ? cr : 0;
+ *              ce = 1.0f when normals is NULL, else (float)(-((ldir.x * e.x + ldir.y * e.y) + ldir.z * e.z)), clamped the same way;
+ *              g = 1.0f without NRAYS_LIGHTS_INVERSE_SQUARE, else (float)(1.0 / max(nrm * nrm, min_dist * min_dist));
+ *              w = (cr * ce) * g; !(w > 0): the light is skipped — no ray exists for it.
+ *   ray        origin q + ldir * offset per component, direction ldir, t_max = nrm - offset.  !(t_max > 0): the light is open with filter (1, 1, 1) and nothing is
+ *              traversed.  Otherwise Scene::intersects_ray with max_toi = t_max, exactly the query of nrays_intersects_rays_device.
+ *   fold       sum = +0 (f32 rgb); a blocked light adds nothing, an open one adds col * (filter * w) per channel, in the order of k.  out_rgb[3i..3i+2] = sum (no
+ *              division: lights add); out_counts[2i] = the lights that got as far as `ray`, out_counts[2i + 1] = how many of them were open.
+ * The result is defined by this text and never by how the library assigns lights to lanes. */
+/* (Struct plus separate typedef, as NraysOcclusionParams and for the same reason; tests/test_light_points.py compares it with its Rust and ctypes twins.) */
+#define NRAYS_LIGHTS_INVERSE_SQUARE 1u
+struct NraysPointLights {
+    uint32_t num_lights;      /* 1 .. 4096 */
+    uint32_t flags;           /* 0 or NRAYS_LIGHTS_INVERSE_SQUARE */
+    const double* positions;  /* num_lights x 3, world space */
+    const float* colors;      /* num_lights x 3 */
+    const double* normals;    /* num_lights x 3 unit emitter normals (VPLs), or NULL = lights shine every way */
+    double bias;              /* finite: the point is moved along its normal first */
+    double offset;            /* finite, >= 0: the ray starts this far towards the light and ends this far before it (the reference's 0.001, phong_material.rs:109-112) */
+    double min_dist;          /* finite, > 0 when INVERSE_SQUARE is set: the falloff's clamp; otherwise unread */
+};
+typedef struct NraysPointLights NraysPointLights;
+/*   points, normals  n x 3 doubles, world space, used as given.
+ *   hit_flags        n words, or NULL: the bits of out_flags of nrays_cast_rays_device / nrays_surface_texels_device.  Bit 0 clear = the point is SKIPPED: out_rgb
+ *                    (0, 0, 0), out_counts (0, 0), no traversal, neither its point nor its normal read — those outputs pass in unfiltered.
+ *   lights           HOST memory (the struct); its three tables are DEVICE memory here, like every other array.  Nothing is random: there are no keys.
+ *   out_rgb          n x 3 floats, required.      out_counts   n x 2 words, or NULL (no store).
+ *   flags            must be 0 (any bit -> NRAYS_ERR_BAD_ARG): neighbouring points send coherent rays towards one light, so no reorder is offered.
+ * NULL scene / points / normals / lights / positions / colors / out_rgb, num_lights outside 1 .. 4096, an unknown bit in either flags word, a non-finite bias, a
+ * negative or non-finite offset, under NRAYS_LIGHTS_INVERSE_SQUARE a min_dist that is not finite or not > 0 -> NRAYS_ERR_BAD_ARG before any HIP call; n == 0 ->
+ * NRAYS_OK without work.  Otherwise the contract of nrays_occlusion_points_device: every array DEVICE memory on the scene's device, chunks of at most
+ * max(1, 2^22 / num_lights) points, enqueued on `hip_stream` without read-back, synchronisation or workspace, ordered behind the handle's previous work; what the
+ * handle reports about its renders and its per-camera scheduling state stay untouched. */
+int nrays_light_points_device(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                              const NraysPointLights* lights, float* out_rgb, uint32_t* out_counts, uint32_t flags, void* hip_stream);
+/* Same, every pointer (the three tables included) HOST memory.  Blocking. */
+int nrays_light_points(NraysScene* scene, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags,
+                       const NraysPointLights* lights, float* out_rgb, uint32_t* out_counts, uint32_t flags);
+/* Test probe: the ray generator of nrays_light_points_device alone (the same device function), on HOST arrays, blocking: the ray of (point i, light k) to
+ * out_origins / out_dirs [(i * num_lights + k) * 3 ..], out_tmax / out_w [i * num_lights + k].  w == 0 marks a skipped light; one with !(nrm > 0) has origin q,
+ * direction (0, 0, 0) and t_max 0, every other skipped light the origin, direction and t_max of the text above. */
+int nrays_debug_light_rays(NraysScene* scene, uint32_t n, const double* points, const double* normals, const NraysPointLights* lights,
+                           double* out_origins, double* out_dirs, double* out_tmax, float* out_w);
 
 /* The light arriving at n caller-supplied surface points from the rest of the scene — a light map's indirect term, a final gather: the library builds
  * num_dirs hemisphere rays per point ON THE DEVICE, runs Scene::trace (what nrays_trace_rays_device runs) on each and writes ONE mean colour per point — the

@@ -690,6 +690,38 @@ impl GpuScene {
         Ok(())
     }
 
+    /// Direct light at caller-supplied surface points from a caller-supplied table of point lights (nrays_light_points, blocking): for every (point, unit normal)
+    /// and every light (position, colour, optional unit emitter normal) the library builds the shadow ray on the device, weights it with the cosine at the point
+    /// (times the emitter's cosine for a light with a normal, times 1 / max(d^2, min_dist^2) when `min_dist` is Some), runs `Scene::intersects_ray` on the rays
+    /// whose weight is > 0 and sums colour * (filter * weight) over the open ones in the table's order.  Per point: the sum, the lights that got a ray, the open ones.
+    /// The scene's own lights are not read.  The arithmetic is defined bit for bit in include/nrays_abi.h (NraysPointLights).
+    pub fn light_points(&self, points: &[(Point3<f64>, Vector3<f64>)], lights: &[(Point3<f64>, Vector3<f32>)], emitter_normals: Option<&[Vector3<f64>]>, min_dist: Option<f64>,
+                        bias: f64, offset: f64) -> Result<Vec<(Vector3<f32>, u32, u32)>, String> {
+        if let Some(e) = emitter_normals { if e.len() != lights.len() { return Err(format!("{} emitter normals for {} lights", e.len(), lights.len())); } }
+        let n = points.len();
+        let (mut p, mut nm) = (Vec::with_capacity(3 * n), Vec::with_capacity(3 * n));
+        for (pt, normal) in points { p.extend_from_slice(&[pt.x, pt.y, pt.z]); nm.extend_from_slice(&[normal.x, normal.y, normal.z]); }
+        let pos: Vec<f64> = lights.iter().flat_map(|l| vec![l.0.x, l.0.y, l.0.z]).collect();
+        let col: Vec<f32> = lights.iter().flat_map(|l| vec![l.1.x, l.1.y, l.1.z]).collect();
+        let en: Vec<f64> = emitter_normals.map(|e| e.iter().flat_map(|v| vec![v.x, v.y, v.z]).collect()).unwrap_or_default();
+        let table = NraysPointLights { num_lights: lights.len() as u32, flags: if min_dist.is_some() { NRAYS_LIGHTS_INVERSE_SQUARE } else { 0 }, positions: pos.as_ptr(),
+                                       colors: col.as_ptr(), normals: if emitter_normals.is_some() { en.as_ptr() } else { ptr::null() }, bias, offset,
+                                       min_dist: min_dist.unwrap_or(1.0) };
+        let (mut rgb, mut counts) = (vec![0.0f32; 3 * n], vec![0u32; 2 * n]);
+        let rc = unsafe { nrays_light_points(self.raw, n as u32, p.as_ptr(), nm.as_ptr(), ptr::null(), &table, rgb.as_mut_ptr(), counts.as_mut_ptr(), 0) };
+        if rc != NRAYS_OK { return Err(last_error()); }
+        Ok((0..n).map(|i| (Vector3::new(rgb[3 * i], rgb[3 * i + 1], rgb[3 * i + 2]), counts[2 * i], counts[2 * i + 1])).collect())
+    }
+
+    /// `light_points` for n points in DEVICE memory (nrays_light_points_device), enqueued on `hip_stream` without synchronisation: points / normals n x 3 f64,
+    /// hit_flags n u32 or null (out_flags of cast_rays_device or surface_texels_device: bit 0 clear = skipped, zeros), out_rgb n x 3 f32, out_counts n x 2 u32 or
+    /// null.  `lights` is host memory; its three tables are device memory.
+    pub unsafe fn light_points_device(&self, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, lights: &NraysPointLights, out_rgb: *mut f32,
+                                      out_counts: *mut u32, hip_stream: *mut c_void) -> Result<(), String> {
+        if nrays_light_points_device(self.raw, n, points, normals, hit_flags, lights, out_rgb, out_counts, 0, hip_stream) != NRAYS_OK { return Err(last_error()); }
+        Ok(())
+    }
+
     /// The light arriving at caller-supplied surface points from the rest of the scene (nrays_gather_points, blocking): the rays of `occlusion_points` with the
     /// same tables, `bias` and keys, each traced with `Scene::trace` as a `RayWithEnergy` of the given `energy` (`max_depth` as in `render`; its RNG key is
     /// hashed from the point's key and the ray's index), the colours summed in order and divided by their number: one mean colour per point, a light map's

@@ -249,6 +249,21 @@ pub struct NraysOcclusionParams {
     pub max_toi: f64,
 }
 
+pub const NRAYS_LIGHTS_INVERSE_SQUARE: u32 = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct NraysPointLights {
+    pub num_lights: u32,
+    pub flags: u32,
+    pub positions: *const f64,
+    pub colors: *const f32,
+    pub normals: *const f64,
+    pub bias: f64,
+    pub offset: f64,
+    pub min_dist: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy)]
 pub struct NraysGatherParams {
@@ -371,6 +386,9 @@ extern "C" {
     pub fn nrays_occlusion_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_occlusion_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysOcclusionParams, out_filter: *mut f32, out_open: *mut u32, flags: u32) -> c_int;
     pub fn nrays_debug_occlusion_rays(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, keys: *const u64, params: *const NraysOcclusionParams, out_origins: *mut f64, out_dirs: *mut f64) -> c_int;
+    pub fn nrays_light_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, lights: *const NraysPointLights, out_rgb: *mut f32, out_counts: *mut u32, flags: u32, hip_stream: *mut c_void) -> c_int;
+    pub fn nrays_light_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, lights: *const NraysPointLights, out_rgb: *mut f32, out_counts: *mut u32, flags: u32) -> c_int;
+    pub fn nrays_debug_light_rays(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, lights: *const NraysPointLights, out_origins: *mut f64, out_dirs: *mut f64, out_tmax: *mut f64, out_w: *mut f32) -> c_int;
     pub fn nrays_gather_points_device(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_rgb: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;
     pub fn nrays_gather_points(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_rgb: *mut f32, flags: u32) -> c_int;
     pub fn nrays_gather_points_device_ex(scene: *mut NraysScene, n: u32, points: *const f64, normals: *const f64, hit_flags: *const u32, keys: *const u64, params: *const NraysGatherParams, out_rgb: *mut f32, flags: u32, hip_stream: *mut c_void) -> c_int;

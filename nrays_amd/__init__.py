@@ -16,4 +16,5 @@ from .scene import (Ball, Capsule, Cone, Cuboid, Cylinder, ImageData, Interpolat
                     ProbeDepth, ProbeVisibility, bake_probe_visibility, oct_texel, probe_depth, probe_depth_points, probe_depth_ref, probe_valid_words,
                     GatherMapsSh, bake_probe_grid_maps, gather_maps_probes, gather_maps_sh_points,
                     MaterialTerms, indirect_points, material_hits, material_points, material_points_ref, texel_albedo,
-                    NEAREST_BEHIND, NearestHits, ProbeClearance, nearest_bound_probe, nearest_box_bound_ref, nearest_points, nearest_points_ref, probe_clearance)
+                    NEAREST_BEHIND, NearestHits, ProbeClearance, nearest_bound_probe, nearest_box_bound_ref, nearest_points, nearest_points_ref, probe_clearance,
+                    PointLighting, PointLights, light_hits, light_points, light_points_ref, light_ray_probe, light_rays, scene_point_lights, vpls_from_hits)

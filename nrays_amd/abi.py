@@ -113,6 +113,16 @@ class NraysOcclusionParams(C.Structure):
     _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("max_toi", C.c_double)]
 
 
+LIGHTS_INVERSE_SQUARE = 1   # NRAYS_LIGHTS_INVERSE_SQUARE
+LIGHTS_MAX = 4096           # the most rows of an NraysPointLights table
+
+
+class NraysPointLights(C.Structure):
+    """The light table of nrays_light_points*: `positions` / `colors` / `normals` are addresses (device memory for the _device form, host memory otherwise)."""
+    _fields_ = [("num_lights", C.c_uint32), ("flags", C.c_uint32), ("positions", C.c_void_p), ("colors", C.c_void_p), ("normals", C.c_void_p), ("bias", C.c_double),
+                ("offset", C.c_double), ("min_dist", C.c_double)]
+
+
 class NraysGatherParams(C.Structure):
     """The tables and ray settings of nrays_gather_points*: `dirs` / `rotations` are addresses (device memory for the _device form, host memory otherwise)."""
     _fields_ = [("num_dirs", C.c_uint32), ("num_rotations", C.c_uint32), ("dirs", C.c_void_p), ("rotations", C.c_void_p), ("bias", C.c_double), ("energy", C.c_float),
@@ -210,6 +220,11 @@ HIP_SYMBOLS = {
                                          C.POINTER(NraysOcclusionParams), C.POINTER(C.c_float), C.POINTER(C.c_uint32), C.c_uint32]),
     "nrays_debug_occlusion_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.POINTER(NraysOcclusionParams),
                                              C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "nrays_light_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysPointLights), C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "nrays_light_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(NraysPointLights), C.POINTER(C.c_float),
+                                     C.POINTER(C.c_uint32), C.c_uint32]),
+    "nrays_debug_light_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(NraysPointLights), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                         C.POINTER(C.c_double), C.POINTER(C.c_float)]),
     "nrays_gather_points_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(NraysGatherParams), C.c_void_p, C.c_uint32, C.c_void_p]),
     "nrays_gather_points": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64),
                                       C.POINTER(NraysGatherParams), C.POINTER(C.c_float), C.c_uint32]),
@@ -308,7 +323,8 @@ POST_V7_SYMBOLS = ("nrays_trace_rays_device_ex", "nrays_trace_rays_ex", "nrays_i
                    "nrays_debug_gather_sh_fold", "nrays_gather_maps_points_device", "nrays_gather_maps_points", "nrays_irradiance_points_device",
                    "nrays_irradiance_points", "nrays_probe_depth_points_device", "nrays_probe_depth_points", "nrays_irradiance_points_vis_device",
                    "nrays_irradiance_points_vis", "nrays_gather_maps_sh_points_device", "nrays_gather_maps_sh_points", "nrays_material_points_device",
-                   "nrays_material_points", "nrays_nearest_points_device", "nrays_nearest_points", "nrays_debug_nearest_bound", "nrays_debug_scene_dump")
+                   "nrays_material_points", "nrays_nearest_points_device", "nrays_nearest_points", "nrays_debug_nearest_bound", "nrays_debug_scene_dump",
+                   "nrays_light_points_device", "nrays_light_points", "nrays_debug_light_rays")
 RAYS_UNORDERED = 1          # NRAYS_RAYS_UNORDERED
 TEXELS_CENTRES = 1          # NRAYS_TEXELS_CENTRES
 TEXELS_FLIP_NORMALS = 2     # NRAYS_TEXELS_FLIP_NORMALS

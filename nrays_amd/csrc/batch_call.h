@@ -1,6 +1,6 @@
 // batch_call.h — the driver every caller-batch entry point runs through (batch_call.cpp; host only, no kernels).  A family — trace, intersects, cast, shade,
-// material (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, gather_maps_sh, probe_depth, irradiance, nearest (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
-// nrays_debug_cast_batch and nrays_debug_occlusion_rays — is four things of its own ("Adding a family on the C++ side"): its argument check (with the
+// material (ray_batches.hip), occlusion, gather, gather_sh, gather_maps, gather_maps_sh, probe_depth, irradiance, nearest, light (point_batches.hip), surface / dilate / filter texels (texel_calls.hip), the probes
+// nrays_debug_cast_batch, nrays_debug_occlusion_rays and nrays_debug_light_rays — is four things of its own ("Adding a family on the C++ side"): its argument check (with the
 // n == 0 return, before any HIP call), its column table (batch_stage.h), its launch struct with a launch_if chain, and its chunk lambda.  The driver holds the rest once:
 //   batch_open    hipSetDevice, the handle's batch workspace, the family's own workspace (`ensure`), the staging arena, the stream — the caller's for the
 //                 device form, the handle's own for the blocking form — and the ordering behind the handle's previous work
@@ -66,7 +66,7 @@ int chunk_order(NraysScene* sc, TraceWorkspace* w, bool reorder, uint32_t n, con
 // the coherence the traversal lives on; one lane per point is left to batches of fewer than 8 directions.  NRAYS_OCCLUSION_LANES=0|3|6 forces a form (the A/B of
 // tools/trace_rays_rate.py --occlusion; the results do not depend on it).
 int occlusion_lanes_log2(const NraysScene* sc, uint32_t num_dirs);
-// A kernel's launch is written in the unit that instantiates it (ray_batches.hip, gather_inst.hip, gather_order_inst.hip, gather_maps_inst.hip, probe_depth_inst.hip): an argument struct and
+// A kernel's launch is written in the unit that instantiates it (ray_batches.hip, gather_inst.hip, gather_order_inst.hip, gather_maps_inst.hip, probe_depth_inst.hip, light_points_inst.hip): an argument struct and
 // `bool launch_<kernel>(const Args&, ...selectors...)`, a chain launch_if<...>(a, ...) || ... of the instantiated permutations; false = none, NRAYS_ERR_UNSUPPORTED here.
 uint32_t launch_grid(uint64_t items);  // workgroups of kBlock lanes for `items` lanes, at most kMaxGrid: the kernels stride (ray_batches.hip, beside the kernels)
 int launch_status(const char* kernel); // after a launch: hipGetLastError() as NRAYS_OK, or NRAYS_ERR_HIP with "<kernel>: <the error>"

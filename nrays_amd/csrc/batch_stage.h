@@ -171,6 +171,23 @@ inline int irradiance_vis_columns(StageColumn* c, const float* moments, size_t p
     c[kIrrMoments] = stage_table(moments, 8 * (size_t)res * res, probes);
     return kIrrVisColumns;
 }
+// nrays_light_points*: points against a table of point lights.  The lights' positions, colours and emitter normals (absent: the lights shine every way) are tables;
+// hit_flags and out_counts may be absent.
+enum { kLightPositions, kLightColors, kLightNormals, kLightPoints, kLightPointNormals, kLightHit, kLightRgb, kLightCounts, kLightColumns };
+inline int light_columns(StageColumn* c, const double* positions, const float* colors, const double* light_normals, uint32_t num_lights, const double* points, const double* normals,
+                         const uint32_t* hit_flags, float* out_rgb, uint32_t* out_counts) {
+    c[kLightPositions] = stage_table(positions, 24, num_lights); c[kLightColors] = stage_table(colors, 12, num_lights); c[kLightNormals] = stage_table(light_normals, 24, num_lights);
+    c[kLightPoints] = stage_in(points, 24); c[kLightPointNormals] = stage_in(normals, 24); c[kLightHit] = stage_in(hit_flags, 4);
+    c[kLightRgb] = stage_out(out_rgb, 12); c[kLightCounts] = stage_out(out_counts, 8);
+    return kLightColumns;
+}
+// nrays_debug_light_rays: the num_lights rays of a point — origins, directions, t_max and weights — after the tables and the points of light_columns.
+enum { kLightRaysOrigins = kLightRgb, kLightRaysDirs, kLightRaysTmax, kLightRaysW, kLightRaysColumns };
+inline int light_rays_columns(StageColumn* c, double* out_origins, double* out_dirs, double* out_tmax, float* out_w, uint32_t num_lights) { // (after light_columns)
+    c[kLightRaysOrigins] = stage_out(out_origins, 24 * (size_t)num_lights); c[kLightRaysDirs] = stage_out(out_dirs, 24 * (size_t)num_lights);
+    c[kLightRaysTmax] = stage_out(out_tmax, 8 * (size_t)num_lights); c[kLightRaysW] = stage_out(out_w, 4 * (size_t)num_lights);
+    return kLightRaysColumns;
+}
 // Lattices (one chunk of width * height items).
 enum { kTexelPoints, kTexelNormals, kTexelUv, kTexelNode, kTexelPrim, kTexelFlags, kTexelColumns };
 inline int surface_texel_columns(StageColumn* c, double* points, double* normals, double* uv, int32_t* node, int32_t* prim, uint32_t* flags) {

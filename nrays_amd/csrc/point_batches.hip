@@ -4,7 +4,8 @@
 // nrays_gather_maps_points* (gather_maps_inst.hip), nrays_probe_depth_points* (probe_depth_inst.hip), nrays_gather_maps_sh_points* (gather_maps_sh_inst.hip, then the two
 // folds), and the one family at points that builds no ray:
 // nrays_irradiance_points* and nrays_irradiance_points_vis* (k_irradiance_points of irradiance_kernel.h, instantiated here), and the one that takes points anywhere in space:
-// nrays_nearest_points* (k_nearest_points of nearest_kernel.h: nearest_inst.hip).  Also three probes: nrays_debug_occlusion_rays (k_occlusion_rays), nrays_debug_gather_sh_fold and
+// nrays_nearest_points* (k_nearest_points of nearest_kernel.h: nearest_inst.hip), and the one whose rays go towards a table of lights: nrays_light_points* (k_light_points of
+// light_points_kernel.h: light_points_inst.hip).  Also four probes: nrays_debug_occlusion_rays (k_occlusion_rays), nrays_debug_light_rays (k_light_rays), nrays_debug_gather_sh_fold and
 // nrays_debug_nearest_bound.  What the hemisphere kernels share on the device is hemisphere_device.h; what the two maps families and the three callers of
 // k_gather_fold_sh share on the host is here (maps_texels, maps_spec, maps_table, launch_gather_fold_sh).
 #include <hip/hip_runtime.h>
@@ -21,6 +22,7 @@
 #include "gather_maps_sh_kernel.h"
 #include "gather_sh_kernel.h"
 #include "irradiance_kernel.h"
+#include "light_points_kernel.h"
 #include "nearest_kernel.h"
 #include "probe_depth_kernel.h"
 #include "ray_batch_kernel.h"
@@ -395,6 +397,41 @@ static int nearest_points_impl(NraysScene* sc, uint32_t n, const double* points,
     return batch_run(sc, staged, stream, cols, kNearColumns, n, kTraceChunk, "nearest batch", launch);
 }
 
+// ---- nrays_light_points*: direct light at caller-supplied points from a caller-supplied table of point lights (light_points_kernel.h: light_points_inst.hip) --------
+constexpr uint32_t kLightMaxLights = 4096u;
+static int check_point_lights(const NraysPointLights* l) {
+    if (!l || !l->positions || !l->colors) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (l->num_lights < 1u || l->num_lights > kLightMaxLights) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysPointLights: num_lights must be in 1 .. 4096");
+    if (l->flags & ~(uint32_t)NRAYS_LIGHTS_INVERSE_SQUARE) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysPointLights: unknown flag");
+    if (!std::isfinite(l->bias)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysPointLights: bias must be finite");
+    if (!(std::isfinite(l->offset) && l->offset >= 0.0)) return set_last_error(NRAYS_ERR_BAD_ARG, "NraysPointLights: offset must be finite and >= 0");
+    if ((l->flags & NRAYS_LIGHTS_INVERSE_SQUARE) && !(std::isfinite(l->min_dist) && l->min_dist > 0.0))
+        return set_last_error(NRAYS_ERR_BAD_ARG, "NraysPointLights: min_dist must be finite and > 0 with NRAYS_LIGHTS_INVERSE_SQUARE");
+    return NRAYS_OK;
+}
+static LightSpec light_spec(const NraysPointLights* l) {
+    const bool falloff = (l->flags & NRAYS_LIGHTS_INVERSE_SQUARE) != 0u;
+    return LightSpec{l->num_lights, falloff ? 1u : 0u, l->bias, l->offset, falloff ? l->min_dist : 1.0};
+}
+static LightTables light_tables(void* const* c) { return LightTables{(const double*)c[kLightPositions], (const float*)c[kLightColors], (const double*)c[kLightNormals]}; }
+static int light_points_impl(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysPointLights* l, float* out_rgb,
+                             uint32_t* out_counts, uint32_t flags, bool staged, hipStream_t stream) {
+    if (!sc || !points || !normals || !out_rgb) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_point_lights(l) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (flags != 0u) return set_last_error(NRAYS_ERR_BAD_ARG, "nrays_light_points: flags must be 0");
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kLightColumns];
+    light_columns(cols, l->positions, l->colors, l->normals, l->num_lights, points, normals, hit_flags, out_rgb, out_counts);
+    // One chunk (nc <= point_chunk); the permutation: kFeatMesh or kFeatAll, as k_intersects_rays; the lanes per point are occlusion_lanes_log2's, by the lights.
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        const int lp = occlusion_lanes_log2(sc, l->num_lights); // (nc << lp <= kTraceChunk: nc * num_lights <= kTraceChunk and 2^lp <= num_lights, or nc == 1)
+        const LightPointsLaunch a{launch_grid((uint64_t)nc << lp), b.stream, &sc->facts.d, nc, (const double*)c[kLightPoints], (const double*)c[kLightPointNormals],
+                                  (const uint32_t*)c[kLightHit], light_spec(l), light_tables(c), (float*)c[kLightRgb], (uint32_t*)c[kLightCounts], b.w->d_spill};
+        return launch_light_points(a, traversal_feat(sc), lp) ? launch_status("k_light_points") : no_permutation("k_light_points");
+    };
+    return batch_run(sc, staged, stream, cols, kLightColumns, n, point_chunk(l->num_lights), "light batch", launch);
+}
+
 // nrays_debug_occlusion_rays: ray j of point i of the chunk, as k_occlusion_points generates it, to out[(i * num_dirs + j) * 3 ..].  NULL keys: key_base + i.
 __global__ void __launch_bounds__(kBlock) k_occlusion_rays(uint32_t n, const double* __restrict__ points, const double* __restrict__ normals,
                                                            const unsigned long long* __restrict__ keys, unsigned long long key_base, OcclusionSpec P,
@@ -441,6 +478,31 @@ int nrays_debug_occlusion_rays(NraysScene* sc, uint32_t n, const double* points,
         return launch_status("k_occlusion_rays");
     };
     return batch_run(sc, true, nullptr, cols, kOccRaysColumns, n, point_chunk(p->num_dirs), "occlusion probe", launch);
+}
+
+int nrays_light_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysPointLights* lights,
+                              float* out_rgb, uint32_t* out_counts, uint32_t flags, void* hip_stream) {
+    return light_points_impl(sc, n, points, normals, hit_flags, lights, out_rgb, out_counts, flags, false, (hipStream_t)hip_stream);
+}
+int nrays_light_points(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const NraysPointLights* lights, float* out_rgb,
+                       uint32_t* out_counts, uint32_t flags) {
+    return light_points_impl(sc, n, points, normals, hit_flags, lights, out_rgb, out_counts, flags, true, nullptr);
+}
+// nrays_debug_light_rays: the generator of k_light_points alone, on host arrays, blocking, in the family's chunks (a test probe).
+int nrays_debug_light_rays(NraysScene* sc, uint32_t n, const double* points, const double* normals, const NraysPointLights* l, double* out_origins, double* out_dirs,
+                           double* out_tmax, float* out_w) {
+    if (!sc || !points || !normals || !out_origins || !out_dirs || !out_tmax || !out_w) return set_last_error(NRAYS_ERR_BAD_ARG, "null argument");
+    if (check_point_lights(l) != NRAYS_OK) return NRAYS_ERR_BAD_ARG;
+    if (n == 0) return NRAYS_OK;
+    StageColumn cols[kLightRaysColumns];
+    light_columns(cols, l->positions, l->colors, l->normals, l->num_lights, points, normals, nullptr, nullptr, nullptr);
+    light_rays_columns(cols, out_origins, out_dirs, out_tmax, out_w, l->num_lights);
+    auto launch = [&](const BatchCall& b, uint32_t nc, void* const* c, unsigned long long) -> int {
+        launch_light_rays(LightRaysLaunch{launch_grid((uint64_t)nc * l->num_lights), b.stream, nc, (const double*)c[kLightPoints], (const double*)c[kLightPointNormals], light_spec(l),
+                                          light_tables(c), (double*)c[kLightRaysOrigins], (double*)c[kLightRaysDirs], (double*)c[kLightRaysTmax], (float*)c[kLightRaysW]});
+        return launch_status("k_light_rays");
+    };
+    return batch_run(sc, true, nullptr, cols, kLightRaysColumns, n, point_chunk(l->num_lights), "light probe", launch);
 }
 
 int nrays_gather_points_device(NraysScene* sc, uint32_t n, const double* points, const double* normals, const uint32_t* hit_flags, const uint64_t* keys,

@@ -61,7 +61,7 @@ struct Switches {
     int grid_wg_per_cu = 0;             // NRAYS_GRID_WG_PER_CU=n: caps the persistent grid at n workgroups per CU (tuning)
     // ---- caller-ray batches (batch_call.cpp, ray_order.hip) ----
     int ray_reorder = 1;                // NRAYS_RAY_REORDER=0|2: a batch called unordered is traced as it comes / always reordered (unset: by its size, reorder_pays)
-    int occlusion_lanes = -1;           // NRAYS_OCCLUSION_LANES=0|3|6: log2 of the lanes that serve a point of nrays_occlusion_points* and of nrays_gather_points* (unset: the most that the directions fill; A/B, results identical)
+    int occlusion_lanes = -1;           // NRAYS_OCCLUSION_LANES=0|3|6: log2 of the lanes that serve a point of nrays_occlusion_points* and of nrays_gather_points*, and by the lights of nrays_light_points* (unset: the most that the directions or lights fill; A/B, results identical)
     // ---- the staged path (wavefront.hip) ----
     uint64_t wf_max_paths = 64ull << 20; // NRAYS_WF_MAX_PATHS=n: (pixel, sample) paths per pass over a range of wave tiles
     bool wf_fuse = false;               // NRAYS_WF_FUSE=1: single-light scenes trace their shadow ray inside k_wf_shade instead of k_wf_shadow (A/B)

@@ -229,6 +229,45 @@ def _occlusion_tables(sample_dirs, rotations, bias, max_toi):
     return L, rot, bias, max_toi
 
 
+PointLights = collections.namedtuple("PointLights", ("positions", "colors", "normals", "inverse_square", "min_dist", "bias", "offset"), defaults=(None, False, 1e-3, 1e-3, 1e-3))
+PointLights.__doc__ = """A table of point lights for light_points (NraysPointLights): `positions` (m, 3) float64, world space; `colors` (m, 3) float32; `normals` (m, 3) float64 unit
+emitter normals (virtual point lights: vpls_from_hits()) or None: the lights shine every way; 1 <= m <= 4096.  `inverse_square`: the weight falls with
+1 / max(d^2, min_dist^2).  `bias`: a lit point is moved along its normal by this first.  `offset`: the shadow ray starts this far towards the light and ends this far
+before it."""
+
+
+def _point_lights(lights):
+    """The checks of NraysPointLights that need no library: (positions, colors, normals or None — contiguous numpy arrays of their kinds, or the torch tensors they came
+    as —, flags, bias, offset, min_dist)."""
+    if not isinstance(lights, tuple) or len(lights) != 7:
+        raise ValueError("lights must be a PointLights(positions, colors, normals, inverse_square, min_dist, bias, offset)")
+    positions, colors, normals, inverse_square, min_dist, bias, offset = lights
+
+    def table(name, a, dtype):
+        if a is None:
+            raise ValueError("lights.%s is required" % name)
+        if not _is_tensor(a):
+            a = np.asarray(a)
+            if not (np.issubdtype(a.dtype, np.floating) or np.issubdtype(a.dtype, np.integer)):
+                raise ValueError("lights.%s must be numbers, got %s" % (name, a.dtype))
+            a = np.ascontiguousarray(a, dtype=dtype)
+        if len(a.shape) != 2 or a.shape[1] != 3 or not 1 <= a.shape[0] <= abi.LIGHTS_MAX:
+            raise ValueError("lights.%s must have shape (1 .. %d, 3), got %s" % (name, abi.LIGHTS_MAX, tuple(a.shape)))
+        return a
+    pos, col = table("positions", positions, np.float64), table("colors", colors, np.float32)
+    en = None if normals is None else table("normals", normals, np.float64)
+    if col.shape[0] != pos.shape[0] or (en is not None and en.shape[0] != pos.shape[0]):
+        raise ValueError("lights: positions, colors and normals must hold the same number of rows")
+    bias, offset, min_dist = float(bias), float(offset), float(min_dist)
+    if not math.isfinite(bias):
+        raise ValueError("lights.bias must be finite")
+    if not (math.isfinite(offset) and offset >= 0.0):
+        raise ValueError("lights.offset must be finite and >= 0")
+    if inverse_square and not (math.isfinite(min_dist) and min_dist > 0.0):
+        raise ValueError("lights.min_dist must be finite and > 0 with inverse_square")
+    return pos, col, en, abi.LIGHTS_INVERSE_SQUARE if inverse_square else 0, bias, offset, min_dist
+
+
 SH_MAX_BANDS = 3
 
 

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import abi
 from .marshal import (NEAREST_BEHIND, NearestHits, OCCLUSION_MAX_TABLE, Interpolation, MaterialTerms, Overflow, SurfaceTexels, _check_vec, _dilate_args, _filter_args, _is_tensor, _n_of, _np_floats, _np_keys,
-                      _depth_res, _material_args, _np_ints, _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
+                      _depth_res, _material_args, _np_ints, _occlusion_tables, _point_lights, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice)
 
 SALT_OCCLUSION = 0x300 << 32  # kSaltOcclusion (csrc/trace_device.h)
 SALT_GATHER = 0x301 << 32  # kSaltGather (csrc/trace_device.h)
@@ -132,6 +132,42 @@ def occlusion_rays(points, normals, sample_dirs, rotations=None, bias=1e-3, keys
         o = p + nm * bias
     origins = np.ascontiguousarray(np.broadcast_to(o[:, None, :], dirs.shape))
     return origins, np.ascontiguousarray(dirs)
+
+
+def light_rays(points, normals, lights):
+    """The numpy mirror of the shadow rays and weights nrays_light_points* builds on the device, bit for bit (include/nrays_abi.h: NraysPointLights — f64 + - * / and
+    sqrt, f32 *, products left to right).  `lights`: a PointLights of numpy tables.  Returns (origins (n, m, 3) float64, dirs (n, m, 3) float64, t_max (n, m) float64,
+    w (n, m) float32): the ray of (point i, light k) at [i, k]; w == 0 marks a skipped light — one at the biased point itself has origin q, direction 0 and t_max 0, every
+    other skipped light the origin, direction and t_max of the definition."""
+    n = _n_of(points, normals, ("points", "normals"))
+    pos, col, en, flags, bias, offset, min_dist = _point_lights(lights)
+    if _is_tensor(points) or _is_tensor(normals) or _is_tensor(pos) or _is_tensor(col) or _is_tensor(en):
+        raise ValueError("light_rays takes numpy arrays")
+    p, nm = _np_floats("points", points, np.float64), _np_floats("normals", normals, np.float64)
+    zero = np.float32(0.0)
+    with np.errstate(all="ignore"):
+        q = (p + nm * bias)[:, None, :]
+        v = pos[None, :, :] - q
+        vx, vy, vz = v[..., 0], v[..., 1], v[..., 2]
+        nrm = np.sqrt((vx * vx + vy * vy) + vz * vz)
+        there = nrm > 0.0
+        ldir = v / nrm[..., None]
+        lx, ly, lz = ldir[..., 0], ldir[..., 1], ldir[..., 2]
+        cr = ((lx * nm[:, None, 0] + ly * nm[:, None, 1]) + lz * nm[:, None, 2]).astype(np.float32)
+        cr = np.where(cr > zero, cr, zero)
+        ce = np.ones_like(cr)
+        if en is not None:
+            ce = (-((lx * en[None, :, 0] + ly * en[None, :, 1]) + lz * en[None, :, 2])).astype(np.float32)
+            ce = np.where(ce > zero, ce, zero)
+        g = np.ones_like(cr)
+        if flags & abi.LIGHTS_INVERSE_SQUARE:
+            g = (1.0 / np.maximum(nrm * nrm, min_dist * min_dist)).astype(np.float32)
+        w = (cr * ce) * g
+        w = np.where(there & (w > zero), w, zero).astype(np.float32)
+        origins = np.where(there[..., None], q + ldir * offset, np.broadcast_to(q, ldir.shape))
+        dirs = np.where(there[..., None], ldir, 0.0)
+        t_max = np.where(there, nrm - offset, 0.0)
+    return np.ascontiguousarray(origins), np.ascontiguousarray(dirs), np.ascontiguousarray(t_max), np.ascontiguousarray(w)
 
 
 def gather_ray_keys(keys, k):

@@ -21,10 +21,10 @@ import numpy as np
 
 from . import abi
 from .marshal import (CURRENT, F32, F64, I32, MATERIAL_OUTPUTS, NEAREST_BEHIND, NEAREST_OUTPUTS, MaterialTerms, NearestHits, OCCLUSION_MAX_TABLE, SH_MAX_BANDS, TEXEL_OUTPUTS, TEXELS_MAX_POINTS, TEXELS_MAX_SIDE, U32, U64, Batch, Interpolation,  # noqa: F401
-                      Overflow, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _material_args, _n_of, _np_floats,
-                      _occlusion_tables, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice, np_ptr, upload)
+                      Overflow, PointLights, ProbeGrid, ProbeVisibility, SurfaceTexels, _check_rows, _check_vec, _depth_res, _dilate_args, _filter_args, _is_tensor, _material_args, _n_of, _np_floats,
+                      _occlusion_tables, _point_lights, _probe_grid, _probe_lattice, _probe_visibility, _sh_bands, _texel_lattice, np_ptr, upload)
 from .restated import (FILTER_TAPS, SALT_GATHER, SALT_OCCLUSION, SH_COSINE_LOBE, SH_K, _rng_hash, _rng_mix, _sh_terms, _texel_edge, camera_rays, dilate_texels_ref,  # noqa: F401
-                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, lightmap_sample_ref, material_points_ref, nearest_box_bound_ref, nearest_points_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
+                       filter_texels_ref, gather_ray_keys, hemisphere_dirs, irradiance_points_ref, light_rays, lightmap_sample_ref, material_points_ref, nearest_box_bound_ref, nearest_points_ref, occlusion_rays, oct_texel, probe_depth_ref, probe_grid_positions, PROBE_NO_DIR, rotation_table, sh_basis, sh_fold_ref, sh_irradiance,
                        sphere_dirs, surface_texels_ref, texel_coords)
 
 
@@ -386,6 +386,10 @@ class BatchCalls:
     def occlusion_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, max_toi=math.inf, hit_flags=None, keys=None):
         """Ambient occlusion at caller-supplied surface points of this scene: occlusion_points(self, ...)."""
         return occlusion_points(self, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags, keys)
+
+    def light_points(self, points, normals, lights, hit_flags=None, want_counts=True):
+        """The direct light of a caller-supplied table of point lights at caller-supplied surface points of this scene: light_points(self, ...)."""
+        return light_points(self, points, normals, lights, hit_flags, want_counts)
 
     def gather_points(self, points, normals, sample_dirs, rotations=None, bias=1e-3, energy=1.0, max_depth=0, hit_flags=None, keys=None, unordered=False):
         """The incoming light at caller-supplied surface points of this scene: gather_points(self, ...)."""
@@ -926,6 +930,111 @@ def occlusion_hits(scene, origins, dirs, hits, sample_dirs, rotations=None, bias
     inputs."""
     points, normals = _hit_points("occlusion_hits", origins, dirs, hits)
     return occlusion_points(scene, points, normals, sample_dirs, rotations, bias, max_toi, hit_flags=hits.flags, keys=keys)
+
+
+# ---- direct light at caller-supplied points from a caller-supplied table of point lights (include/nrays_abi.h: NraysPointLights) ------------------------------
+
+PointLighting = collections.namedtuple("PointLighting", ("rgb", "counts"))
+
+
+def _light_batch(points, normals, hit_flags, lights, outs):
+    """The columns of a call with a light table — points, normals, flags, then the three tables of the params struct, which may be numpy next to tensors — and the
+    struct's settings."""
+    pos, col, en, flags, bias, offset, min_dist = _point_lights(lights)
+    b = Batch((("points", points, F64), ("normals", normals, F64), ("hit_flags", hit_flags, U32), ("lights.positions", pos, F64, True), ("lights.colors", col, F32, True),
+               ("lights.normals", en, F64, True)), outs)
+    return b, abi.NraysPointLights(len(pos), flags, b.addr(b.ins[3]), b.addr(b.ins[4]), b.addr(b.ins[5]), bias, offset, min_dist)
+
+
+def light_ray_probe(scene, points, normals, lights):
+    """Test probe (nrays_debug_light_rays): the shadow rays and weights as the library's own generator — the device function k_light_points traces — builds them, in
+    light_rays()' layout.  numpy arrays, blocking."""
+    n = _n_of(points, normals, ("points", "normals"))
+    m = len(_point_lights(lights)[0])
+    b, params = _light_batch(points, normals, None, lights, (("origins", (n, m, 3), F64), ("dirs", (n, m, 3), F64), ("t_max", (n, m), F64), ("w", (n, m), F32)))
+    b.call(scene, "nrays_debug_light_rays", n, b.pin[0], b.pin[1], C.byref(params), *b.pout)
+    return tuple(b.outs)
+
+
+def light_points(scene, points, normals, lights, hit_flags=None, want_counts=True):
+    """The direct light of a caller-supplied table of point lights at n caller-supplied surface points, through nrays_light_points_device / nrays_light_points: per
+    point the library builds the shadow ray towards every light ON THE DEVICE (light_rays() restates them bit for bit), weights it with the cosine at the point — for
+    lights with emitter normals also the emitter's cosine, with `inverse_square` the falloff —, runs Scene::intersects_ray — the query of intersects_rays() — on the
+    rays whose weight is > 0 and sums colour * (filter * weight) over the open ones in the order of the table: PointLighting(rgb (n, 3) float32, counts (n, 2) — the
+    lights that got a ray and the open ones among them; None without `want_counts`).  A light behind the surface costs nothing, the scene's own lights are not read
+    (scene_point_lights() makes a table of them), and no ray or per-ray result is ever in memory.  Also `scene.light_points(...)` on Scene and FileScene; light_hits()
+    feeds it from closest_hits(), vpls_from_hits() makes virtual point lights for it.
+    `points`, `normals`: (n, 3), used as given (unit normals, pointing to the lit side).  `lights`: a PointLights.  `hit_flags` (n,) integers or None: the flag words of
+    closest_hits / surface_texels — bit 0 clear: the point is skipped (zeros; its point and normal may hold anything).
+    numpy arrays -> nrays_light_points (blocking), numpy arrays (counts uint32).  torch tensors on the scene's GPU (float64; hit_flags int32 / uint32; the tables
+    tensors — colours float32 — or anything numpy takes) -> nrays_light_points_device on torch's current stream, tensors (counts int32)."""
+    n = _n_of(points, normals, ("points", "normals"))
+    _check_vec("hit_flags", hit_flags, n)
+    b, params = _light_batch(points, normals, hit_flags, lights, (("rgb", (n, 3), F32), ("counts", (n, 2), U32, bool(want_counts))))
+    b.call(scene, "nrays_light_points", n, *b.pin[:3], C.byref(params), *b.pout, 0)
+    return PointLighting(*b.outs)
+
+
+def light_points_ref(scene, points, normals, lights, hit_flags=None):
+    """The definition of light_points from parts that existed before it, bit for bit: the mirror's rays (light_rays()) with a weight > 0 and a t_max > 0 through
+    intersects_rays(), and the fold of the header in numpy float32 in the order of the lights.  numpy arrays; PointLighting(rgb, counts uint32)."""
+    ro, rd, t_max, w = light_rays(points, normals, lights)
+    col = _point_lights(lights)[1]
+    n, m = w.shape
+    live = np.ones(n, bool) if hit_flags is None else (np.asarray(hit_flags).astype(np.uint32) & 1) != 0
+    ray = (w > 0) & live[:, None]
+    traced = ray & (t_max > 0.0)
+    open_, filt = ray.copy(), np.ones((n, m, 3), np.float32)
+    if traced.any():
+        lit, f = intersects_rays(scene, np.ascontiguousarray(ro[traced]), np.ascontiguousarray(rd[traced]), np.ascontiguousarray(t_max[traced]))
+        open_[traced], filt[traced] = lit, f
+    total = np.zeros((n, 3), np.float32)
+    with np.errstate(all="ignore"):
+        for k in range(m):
+            c = col[k][None, :] * (filt[:, k] * w[:, k, None])
+            total = np.where(open_[:, k, None], total + c, total)
+    return PointLighting(total, np.stack([ray.sum(axis=1), open_.sum(axis=1)], axis=1).astype(np.uint32))
+
+
+def light_hits(scene, origins, dirs, hits, lights, want_counts=True):
+    """The direct light of a table of point lights at the closest hits of caller-supplied rays: light_points() at the hits of `hits = closest_hits(scene, origins,
+    dirs)` (a CastHits with normal and flags), on the side the rays came from — the points and normals of occlusion_hits(), built the same way.  Misses come back as
+    zeros.  numpy or torch as the inputs."""
+    points, normals = _hit_points("light_hits", origins, dirs, hits)
+    return light_points(scene, points, normals, lights, hit_flags=hits.flags, want_counts=want_counts)
+
+
+def scene_point_lights(scene, **kw):
+    """The scene's own lights of radius 0 as a PointLights (positions float64, colours float32, no emitter normals); `kw`: its other fields.  With bias=0 and
+    offset=1e-3 light_points() then computes what shade_points() computes for a Phong node of ambient 0, diffuse (1, 1, 1), specular 0 and no texture, bit for bit."""
+    d = scene.descriptor.desc
+    rows = [d.lights[i] for i in range(d.num_lights) if d.lights[i].radius == 0.0]
+    if not rows:
+        raise ValueError("the scene has no light of radius 0")
+    return PointLights(np.asarray([tuple(r.pos) for r in rows], np.float64), np.asarray([tuple(r.color) for r in rows], np.float32), None, **kw)
+
+
+def vpls_from_hits(origins, dirs, hits, diffuse, power, **kw):
+    """Virtual point lights (instant radiosity, Keller 1997) from the closest hits of caller-supplied rays: every hit (flags bit 0) becomes a light at the hit point
+    — origins + dirs * toi, as occlusion_hits() builds it —, with the normal on the side the ray came from as its emitter normal and the colour
+    float32(power) * diffuse[i]; misses make no light.  `diffuse` (n, 3) float32: the surface's diffuse reflectance, material_hits(want=("diffuse",)).diffuse.  `power`:
+    what one VPL carries, e.g. the light's colour scale / (pi * paths).  `kw`: the other fields of the PointLights (inverse_square=True for a physical falloff).  The
+    chain, every step on the device:
+        hits = closest_hits(scene, origins, dirs)                                  # where the light's paths land
+        diffuse = material_hits(scene, hits, want=("diffuse",)).diffuse             # what the surface there reflects
+        vpls = vpls_from_hits(origins, dirs, hits, diffuse, power, inverse_square=True)
+        indirect = light_points(scene, points, normals, vpls).rgb                  # one bounce at the points to be lit
+    numpy or torch as the inputs; at most 4096 lights a table (split the hits otherwise)."""
+    points, normals = _hit_points("vpls_from_hits", origins, dirs, hits)
+    _check_rows("diffuse", diffuse, int(points.shape[0]), 3)
+    if _is_tensor(points) != _is_tensor(diffuse):
+        raise ValueError("torch tensors and numpy arrays cannot be mixed in one call")
+    hit = (hits.flags & 1) != 0
+    if _is_tensor(points):
+        colors = diffuse.float() * float(np.float32(power))
+    else:
+        colors = np.float32(power) * np.asarray(diffuse, np.float32)
+    return PointLights(points[hit], colors[hit], normals[hit], **kw)
 
 
 # ---- incoming light at caller-supplied points (include/nrays_abi.h: nrays_gather_points_device) ------------------------------------------------------------
